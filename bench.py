@@ -12,7 +12,13 @@ Workload at N = 1: BASELINE.json config 3 — 10^8 sessions / 10^5 users / 32 di
 int32 user/disc, resident in HBM before the timed region.
 
 What one run measures (rank 0 prints ONE JSON line on stdout, everything else goes to stderr):
-  value / ms_per_step   the headline loop: K steps, R times (median; min / max beside it), two scans in flight
+  value / ms_per_step   the headline loop: set-up, warm-up (W steps; at least WARMUP_MIN_S of steps where they leave no
+                        state behind), then ONE timed region of exactly K steps
+  --dump-outputs DIR    after the timed steps: what the last step computed (per query: counts, offsets, rows of the feeds)
+                        as DIR/*.npy, float64, a fixed seeded sample of users and rows (see dump_outputs)
+With --full, also (each leg as before, all after the timed steps unless noted):
+  value / ms_per_step   R timed regions of K steps (--repeat, default 5; median, min / max beside it), HIP events
+                        around the table pass of every n-th step inside them
   roofline              the dominant kernel of that loop, HIP-event timed in the run; frac = HBM traffic / time / peak
                         (traffic: rocprofv3 PMC of this very command, committed under profiles/; a byte model from the
                         run's own row counters beside it) — never above 1; the 24 B/row figure is `alg_equiv_gbs`
@@ -21,6 +27,7 @@ What one run measures (rank 0 prints ONE JSON line on stdout, everything else go
   value_with_d2h        the headline loop with counts + offsets delivered to pinned host memory by every scan
   cpu_baseline          oracle C port on this box's host cores: full N on 1 thread and on all threads, checked against
                         the GPU result; reference-faithful JS (Map of session objects) beside it
+  gather_verified       N > 1: the gathered lists against every rank's own result, and scan_only_ms_per_step beside them
 """
 import argparse
 import json
@@ -36,6 +43,8 @@ sys.path.insert(0, REPO)
 SEED = 0x5EED5EED
 T0_MS = 1700000000000
 DAY = 86400 * 1000
+WARMUP_MIN_S = 0.5     # the step time settles within tens of ms of continuous steps (a first region right after 10 warm-up
+                       # steps ran ~1 % slower than later ones); steps that leave no state behind warm up at least this long
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (/opt/skills/guides/MI355X_MICROARCH.md)
 
 
@@ -173,6 +182,28 @@ def cpu_baseline(args, U, D, now, cutoff, mask, flags, gpu_result, js_proc):
     return out
 
 
+DUMP_USERS, DUMP_ROWS = 32768, 16384   # at most 64 queries: 64 x (2 x 32768 + 16384) float64 = 42 MB
+
+
+def dump_outputs(directory, results):
+    """`results`: (counts[U], offsets[U+1], idx[M]) of every query of the last timed step -> DIR/<name>.npy, float64:
+    users[S] (up to DUMP_USERS user ids, a sample seeded by SEED when there are more), counts[Q, S] and offsets[Q, S] at
+    those users, selected_rows[Q] (M of each query), idx[Q, DUMP_ROWS] (query q's row list at up to DUMP_ROWS positions, a
+    sample seeded by (SEED, q) when M is larger, in the list's order; -1 pads)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    n_users = results[0][0].size
+    users = np.arange(n_users) if n_users <= DUMP_USERS else np.sort(np.random.default_rng(SEED).choice(n_users, DUMP_USERS, replace=False))
+    idx = np.full((len(results), DUMP_ROWS), -1.0)
+    for q, (_, _, rows) in enumerate(results):
+        pos = np.arange(rows.size) if rows.size <= DUMP_ROWS else np.sort(np.random.default_rng([SEED, q]).choice(rows.size, DUMP_ROWS, replace=False))
+        idx[q, : pos.size] = rows[pos]
+    arrays = {"users": users, "counts": [r[0][users] for r in results], "offsets": [r[1][users] for r in results],
+              "selected_rows": [r[2].size for r in results], "idx": idx}
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), np.asarray(a, np.float64))
+
+
 def main():
     # exactly ONE JSON line may reach stdout: libraries (RCCL prints a version banner) write to fd 1, so fd 1 is
     # pointed at stderr for the whole run and the result line goes to the saved descriptor
@@ -183,7 +214,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--repeat", type=int, default=5, help="timed regions of --steps steps each (median / min / max reported)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: repeated timed regions with kernel events, roofline, the other "
+                         "batches, single query, every-byte form, read ceiling, D2H, CPU baselines, gather check (off: set-up, "
+                         "warm-up, one timed region of --steps steps, the result line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/*.npy (dump_outputs)")
+    ap.add_argument("--repeat", type=int, default=None,
+                    help="timed regions of --steps steps each (median / min / max reported); default 5 with --full, else 1")
     ap.add_argument("--rows", type=int, default=10 ** 8, help="sessions of the whole corpus (sharded over the ranks)")
     ap.add_argument("--users", type=int, default=10 ** 5, help="users of the whole corpus")
     ap.add_argument("--disc", type=int, default=32)
@@ -240,6 +277,14 @@ def main():
         local_rank = int(os.environ["PIE_BENCH_DEVICE"])
     if world != args.gpus:
         log("warning: --gpus %d but WORLD_SIZE %d; using WORLD_SIZE" % (args.gpus, world))
+    # PIE_BENCH_FORCE_GATHER=1 exercises the RCCL exchange step with a single rank (rehearsal on a 1-GPU box)
+    gather = world > 1 or os.environ.get("PIE_BENCH_FORCE_GATHER") == "1"
+    if args.dump_outputs and (gather or args.mode not in ("scan", "mixed")):
+        ap.error("--dump-outputs: one process without the exchange step, --mode scan or mixed")
+    if args.repeat is None:
+        args.repeat = 5 if args.full else 1
+    if not args.full:   # a plain run: the headline loop and nothing else
+        args.no_cpu_baseline = args.no_extra = True
 
     N, U, D = args.rows, args.users, args.disc
     js_proc = None
@@ -249,17 +294,18 @@ def main():
         js_proc = start_js_baseline(args, U, D)
 
     import numpy as np
-    import torch
-    import torch.distributed as dist
-    import sph_pie_amd as pie
-    from sph_pie_amd.shard import BatchedFeeds, HipShardBackend, ShardedFeeds
+    torch = None
+    if gather or args.full:   # torch drives the exchange step and pins the D2H leg's buffer; a plain 1-GPU run does without it
+        import torch
+        import torch.distributed as dist
+        from sph_pie_amd.shard import BatchedFeeds, HipShardBackend, ShardedFeeds
 
-    if not torch.cuda.is_available():
-        raise SystemExit("bench.py needs a GPU: the scan path has no CPU fallback")
-    torch.cuda.set_device(local_rank)
-    dev = torch.device("cuda", local_rank)
-    # PIE_BENCH_FORCE_GATHER=1 exercises the RCCL exchange step with a single rank (rehearsal on a 1-GPU box)
-    gather = world > 1 or os.environ.get("PIE_BENCH_FORCE_GATHER") == "1"
+        if not torch.cuda.is_available():
+            raise SystemExit("bench.py needs a GPU: the scan path has no CPU fallback")
+        torch.cuda.set_device(local_rank)
+        dev = torch.device("cuda", local_rank)
+    import sph_pie_amd as pie
+
     if gather:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         os.environ.setdefault("MASTER_PORT", "29531")
@@ -267,7 +313,7 @@ def main():
             dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
         else:
             dist.init_process_group("gloo", rank=rank, world_size=world)
-    cdev = dev if args.transport == "nccl" else torch.device("cpu")   # where the small control collectives run
+    cdev = (dev if args.transport == "nccl" else torch.device("cpu")) if gather else None   # where the small control collectives run
     transport = "device" if args.transport == "nccl" else "host"
 
     flags = (pie.PIE_GEN_INTERVAL if args.variant == "interval" else 0) | (pie.PIE_GEN_CLUSTERED if args.order == "clustered" else 0) | \
@@ -283,7 +329,10 @@ def main():
     mask &= (1 << D) - 1 if D < 64 else 2 ** 64 - 1
 
     pie.build_hip()
-    ctx = pie.PieScan(local_rank)
+    try:
+        ctx = pie.PieScan(local_rank)
+    except pie.PieError as ex:
+        raise SystemExit("bench.py needs a GPU: the scan path has no CPU fallback (%s)" % ex)
     t_gen = time.perf_counter()
     strong = world > 1 and args.scaling == "strong"
     if args.users_dist == "zipf":
@@ -399,7 +448,8 @@ def main():
 
     def fence():
         ctx.synchronize()
-        torch.cuda.synchronize()
+        if torch is not None:
+            torch.cuda.synchronize()
         if gather:
             dist.barrier()
             torch.cuda.synchronize()
@@ -417,14 +467,21 @@ def main():
             dt = float(t.item())
         return dt, out
 
-    run_steps(max(args.warmup, 1))
+    k_warm, t_warm = max(args.warmup, 1), time.perf_counter()
+    run_steps(k_warm)
     fence()
+    if not gather and args.mode != "mixed":   # every rank would have to agree on k; mixed steps grow the table
+        while time.perf_counter() - t_warm < WARMUP_MIN_S:
+            k_warm *= 2
+            run_steps(k_warm)
+            fence()
     ctx.stats_reset()
     mixed_state.update({"append_s": 0.0, "touch_s": 0.0, "scan_s": 0.0, "n": 0})
     # HIP events around the scan kernels, on the stream they are launched on; every 16th step (at least three per region)
     # carries them (an event between two kernels drains the pipeline for a few microseconds)
     profile_every = args.profile_every if args.profile_every > 0 else max(1, min(16, args.steps // 3))
-    ctx.set_profiling(1 if args.mode in ("expired", "archive") else profile_every)
+    if args.full:
+        ctx.set_profiling(1 if args.mode in ("expired", "archive") else profile_every)
     region_ms, kernel_ms_regions, scan_ms_regions, n_prof = [], [], [], 0
     last = None
     mixed_regions = []
@@ -447,6 +504,8 @@ def main():
             arch_acc[2] = a[2]
         ctx.stats_reset()
     arch_stats = tuple(arch_acc)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, [ctx.batch_read_results(q) for q in range(Q)] if args.mode == "scan" and Q > 1 else [ctx.read_results()])
     ctx.set_profiling(0)
     st = ctx.stats()
     # With batch lanes (pie_set_batch_lanes: several batches side by side on the chip) a launch's event time is its duration
@@ -454,7 +513,7 @@ def main():
     # more on one lane, profiled, after the timed regions (not part of value).
     lanes = ctx.batch_lanes()
     k1_ms_lanes = None
-    if lanes > 1 and Q > 1 and not gather and args.mode == "scan":
+    if lanes > 1 and Q > 1 and not gather and args.mode == "scan" and args.full:
         k1_ms_lanes = statistics.median(kernel_ms_regions) if kernel_ms_regions else None
         ctx.set_batch_lanes(1)
         ctx.scan_batch_pipelined(max(args.warmup, 1), batch_queries)
@@ -498,7 +557,7 @@ def main():
 
     scan_only_ms = None
     gather_ok = None
-    if gather and args.mode == "scan":
+    if gather and args.mode == "scan" and args.full:
         # the gathered lists of this rank (as every rank received them) against this rank's own result of the same query
         if bfeeds is not None:
             ok = True
@@ -562,6 +621,8 @@ def main():
                          "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": a_alg / (chain_ms * 1e-3) / 1e9 / HBM_PEAK_GBS if chain_ms > 0 else None,
                          "traffic": None},
         }
+        if not args.full:   # chain_ms comes from the events of a --full run
+            del line["roofline"]
         os.write(result_fd, (json.dumps(line) + "\n").encode())
         ctx.close()
         return
@@ -917,6 +978,8 @@ def main():
     if rank == 0:
         if world == 1 and not args.no_cpu_baseline and args.mode == "scan":
             line["cpu_baseline"] = cpu_baseline(args, U, D, now, cutoff, mask, flags, gpu_result, js_proc)
+        if not args.full:   # kernel_ms comes from the events and the one-lane leg of a --full run
+            del line["roofline"]
         os.write(result_fd, (json.dumps(line) + "\n").encode())
     if gather:
         dist.barrier()

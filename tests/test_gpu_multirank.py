@@ -58,7 +58,7 @@ def test_bench_two_ranks_one_gpu(pie, extra):
     every timed region, gather_verified and the scan-only leg; rank 0 prints one well-formed line."""
     port = 32500 + (os.getpid() % 2000) + len(extra) + (7 if "64" in extra else 0)
     base = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--rows", "2000000", "--users", "3000", "--steps", "6", "--warmup", "2",
-            "--repeat", "2", "--gather-batch", "4", "--no-cpu-baseline"] + extra
+            "--repeat", "2", "--gather-batch", "4", "--no-cpu-baseline", "--full"] + extra
     outs = _run_ranks([base, base], [_env(r, 2, port) for r in range(2)], 600)
     lines = [ln for ln in outs[0][0].splitlines() if ln.startswith("{")]
     assert len(lines) == 1 and not [ln for ln in outs[1][0].splitlines() if ln.startswith("{")]

@@ -5,7 +5,7 @@ mkdir -p gpurun_out
 : > $out
 run() {
   echo "== PIE_ORDERED=${PIE_ORDERED:-1} $*" >> $out
-  python3 bench.py --steps 60 --warmup 10 --repeat 3 --no-cpu-baseline --no-extra "$@" 2>/dev/null \
+  python3 bench.py --full --steps 60 --warmup 10 --repeat 3 --no-cpu-baseline --no-extra "$@" 2>/dev/null \
     | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); r=d['roofline']; print('ms_per_step', round(d['ms_per_step'],5), 'Q', d.get('queries_per_launch'), 'feeds/s %.3e' % d['value'], r['kernel'], r['kernel_variant'], 'k1_ms', round(r['kernel_ms'],5), 'M', d['config']['selected_rows_rank0'], 'ordered', d['index']['ordered_run'])" >> $out
 }
 run --query wide --queries-per-launch 1

@@ -5,7 +5,7 @@ out=gpurun_out/keyed_sweep.txt
 mkdir -p gpurun_out
 : > $out
 run() {
-  python3 bench.py --steps 300 --warmup 20 --no-cpu-baseline 2>/dev/null \
+  python3 bench.py --full --steps 300 --warmup 20 --no-cpu-baseline 2>/dev/null \
     | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); r=d['roofline']; print(d['ms_per_step'], r['kernel'], r['kernel_variant'], r['kernel_ms'], r['k1_blocks'])" >> $out
 }
 for v in ${KEYED_FORMS:-0xC85 0xC05}; do
