@@ -304,6 +304,17 @@ int pie_archive_queue(pie_ctx *ctx, int64_t now, int64_t window_ms, int32_t *que
  * the chains since pie_stats_reset and their number; the algorithmic bytes of the last one: 20 B/row for the group statistics
  * (start, end, user) + 12 B/row for the selection (end, user) + 4 B per queued row. */
 int pie_archive_stats(pie_ctx *ctx, double *ms_sum_out, uint32_t *calls_out, uint64_t *alg_bytes_out);
+/* The queue the last pie_expired_queue / pie_archive_queue left on the device, for the cross-shard merge (pie_comm_*_queue).
+ * pie_queue_info: kind 1 = expired, 2 = archive (0: none — a scan, batch or table change since forgot it), its rows, and for
+ * the archive queue its groups.  PIE_E_STATE when there is none, or when the table holds rows its shard map does not cover
+ * (appended after pie_shard_table: they have no global row).
+ * pie_queue_pack_device: pack it into ONE int32 message in caller-owned device memory, one launch on the context's stream:
+ *   [ n_rows | n_groups | global rows (cap_rows) | local rows (cap_rows) | group offsets (cap_groups + 1) ]
+ * global row = the shard map's entry (the row itself on a context that was never sharded); group offsets = the exclusive
+ * scan of the group sizes in group order, closed by n_rows (expired: n_groups = 0).  2 + 2 cap_rows + cap_groups + 1 words;
+ * PIE_E_CAPACITY if the queue has more rows or groups than that, PIE_E_STATE as pie_queue_info. */
+int pie_queue_info(pie_ctx *ctx, int32_t *kind_out, size_t *rows_out, size_t *groups_out);
+int pie_queue_pack_device(pie_ctx *ctx, void *dst_i32, size_t cap_rows, size_t cap_groups);
 
 /* ---- measurement ------------------------------------------------------------------------------------- */
 /* Pin the form of the table pass (the codes of pie_stats.k1_variant, DESIGN.md section 8: 0x01 reads every byte of the
@@ -394,6 +405,26 @@ int pie_comm_gathered_device_ptr(pie_comm *comm, int32_t at_rank, void **base_ou
                                  size_t *query_stride_words, size_t *u_pad_out);
 int pie_comm_read_gathered(pie_comm *comm, int32_t at_rank, int32_t src_rank, int32_t qi, int32_t *offsets_out /* u_pad + 1 */,
                            int32_t *idx_out, size_t idx_cap, size_t *m_out);
+/* Cross-shard dispatch queues: every local shard computes its own queue (pie_expired_queue / pie_archive_queue), packs it
+ * (pie_queue_pack_device's layout), the messages are exchanged (direct pattern) and merged on every rank's device into the
+ * one queue of the unsharded table: the ascending global rows with prev_now < end <= now, or the archive queue (groups = users,
+ * each on one rank, ordered by the global row of their first queued row; rows in table order).  Two header words per rank
+ * (rows, groups) are exchanged first and size the messages; a rank whose local step failed sends {-1, status} and EVERY rank
+ * returns that status (the lowest failing rank's), with nothing left waiting in ncclSend / ncclRecv.  PIE_E_STATE while
+ * pipelined steps are uncollected.  Every rank of a process-per-GPU communicator makes the same calls in the same order.
+ * queue_out (may be NULL) receives the global rows as the first local rank holds them; *q_out = the total on every rank;
+ * PIE_E_CAPACITY (with *q_out set) if cap is below it.  The merged queue stays with the communicator until the next call:
+ * pie_comm_queue_read copies it as a local rank holds it (global row, source rank, source local row; any output may be NULL),
+ * pie_comm_queue_device_ptrs hands out the device arrays. */
+int pie_comm_expired_queue(pie_comm *comm, int64_t prev_now, int64_t now, int32_t *queue_out, size_t cap, size_t *q_out);
+int pie_comm_archive_queue(pie_comm *comm, int64_t now, int64_t window_ms, int32_t *queue_out, size_t cap, size_t *q_out);
+int pie_comm_queue_read(pie_comm *comm, int32_t at_rank, int32_t *rows_out, int32_t *src_rank_out, int32_t *src_row_out,
+                        size_t cap, size_t *q_out);
+int pie_comm_queue_device_ptrs(pie_comm *comm, int32_t at_rank, void **rows_dev, void **src_rank_dev, void **src_row_dev,
+                               size_t *q_out);
+/* Device time of the phases of the last queue call on the first local rank's stream (ms): [0] local queue + header exchange,
+ * [1] pack, [2] payload exchange, [3] merge. */
+int pie_comm_queue_timing(pie_comm *comm, float *ms_out_4);
 
 /* ---- the pipelined exchange: ONE union message per step (layout: pie_scan_batch_begin_union), written by each shard's own
  * batch kernels; the exchange of step i runs on a side stream while the shards scan steps i+1, i+2.  Order of calls:

@@ -110,6 +110,8 @@ _SIGS = [
     ("pie_fetch_rows", C.c_int, [_P, _P, C.c_size_t, _P, _P, _P, _P]),
     ("pie_expired_queue", C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("pie_archive_queue", C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("pie_queue_info", C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    ("pie_queue_pack_device", C.c_int, [_P, _P, C.c_size_t, C.c_size_t]),
     ("pie_archive_stats", C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
     ("pie_set_profiling", C.c_int, [_P, C.c_int]),
     ("pie_stats_get", C.c_int, [_P, C.POINTER(PieStats)]),
@@ -138,6 +140,11 @@ _SIGS = [
     ("pie_comm_step_read_gathered", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int64, _P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("pie_comm_gathered_device_ptr", C.c_int, [_P, C.c_int32, C.POINTER(_P), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     ("pie_comm_read_gathered", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("pie_comm_expired_queue", C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("pie_comm_archive_queue", C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("pie_comm_queue_read", C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("pie_comm_queue_device_ptrs", C.c_int, [_P, C.c_int32, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_size_t)]),
+    ("pie_comm_queue_timing", C.c_int, [_P, C.POINTER(C.c_float)]),
 ]
 ABI_SYMBOLS = [s[0] for s in _SIGS]
 
@@ -602,6 +609,18 @@ class PieScan:
         self._check(self._lib.pie_archive_queue(self._ctx, int(now), int(window_ms), _ptr(out), self.n, C.byref(q)))
         return out[: q.value].copy()
 
+    def queue_info(self):
+        """-> (kind, rows, groups) of the queue the last expired_queue / archive_queue left on the device (kind 1 expired,
+        2 archive).  PieError(PIE_E_STATE) when there is none or the table has rows its shard map does not cover."""
+        kind, rows, groups = C.c_int32(0), C.c_size_t(0), C.c_size_t(0)
+        self._check(self._lib.pie_queue_info(self._ctx, C.byref(kind), C.byref(rows), C.byref(groups)))
+        return kind.value, rows.value, groups.value
+
+    def queue_pack_device(self, dst_ptr, cap_rows, cap_groups):
+        """Pack that queue into device memory: [n_rows | n_groups | global rows (cap_rows) | local rows (cap_rows) |
+        group offsets (cap_groups + 1)] int32 words, on the context's stream."""
+        self._check(self._lib.pie_queue_pack_device(self._ctx, dst_ptr, int(cap_rows), int(cap_groups)))
+
     def archive_stats(self):
         """-> (device ms summed over the profiled archive chains, their number, algorithmic bytes of the last one)"""
         ms, calls, alg = C.c_double(0), C.c_uint32(0), C.c_uint64(0)
@@ -769,6 +788,43 @@ class PieComm:
         rows, masks = np.empty(max(mu.value, 1), np.int32), np.empty(max(mu.value, 1), np.uint64)
         self._check(self._lib.pie_comm_step_read_gathered(self._c, int(at_rank), int(src_rank), int(step), None, _ptr(rows), _ptr(masks), mu.value, C.byref(mu)))
         return uoff, rows[: mu.value], masks[: mu.value]
+
+    # ---- cross-shard dispatch queues (pie_comm_expired_queue / pie_comm_archive_queue)
+    def local_ranks(self):
+        return [r for r in range(self.world) if self._lib.pie_comm_ctx(self._c, r)]
+
+    def _queue(self, rc, sources):
+        self._check(rc)
+        return self.queue_read(self.local_ranks()[0], sources)
+
+    def expired_queue(self, prev_now, now, sources=False):
+        """Ascending global rows with prev_now < end <= now over every shard, merged on the devices.  sources=True:
+        (rows, src_rank, src_row) — the shard that holds each row and its local row there."""
+        q = C.c_size_t(0)
+        return self._queue(self._lib.pie_comm_expired_queue(self._c, int(prev_now), int(now), None, 0, C.byref(q)), sources)
+
+    def archive_queue(self, now, window_ms=43200000, sources=False):
+        """The archive queue of the whole table (groups = users, ordered by the global row of their first queued row), merged on
+        the devices.  sources=True: (rows, src_rank, src_row)."""
+        q = C.c_size_t(0)
+        return self._queue(self._lib.pie_comm_archive_queue(self._c, int(now), int(window_ms), None, 0, C.byref(q)), sources)
+
+    def queue_read(self, at_rank, sources=False):
+        """The merged queue of the last queue call as local rank at_rank holds it."""
+        q = C.c_size_t(0)
+        self._check(self._lib.pie_comm_queue_read(self._c, int(at_rank), None, None, None, 0, C.byref(q)))
+        rows, src_rank, src_row = (np.empty(max(q.value, 1), np.int32) for _ in range(3))
+        self._check(self._lib.pie_comm_queue_read(self._c, int(at_rank), _ptr(rows), _ptr(src_rank) if sources else None,
+                                                  _ptr(src_row) if sources else None, q.value, C.byref(q)))
+        n = q.value
+        return (rows[:n].copy(), src_rank[:n].copy(), src_row[:n].copy()) if sources else rows[:n].copy()
+
+    def queue_timing(self):
+        """-> device ms of the last queue call's phases on the first local rank's stream: (local queue + header exchange,
+        pack, payload exchange, merge)"""
+        ms = (C.c_float * 4)()
+        self._check(self._lib.pie_comm_queue_timing(self._c, ms))
+        return tuple(float(v) for v in ms)
 
     def read_gathered(self, at_rank, src_rank, qi):
         """-> (offsets[u_pad + 1] int32, idx[M] int32) of (src_rank, query qi) as rank at_rank holds it."""

@@ -17,7 +17,9 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <ctime>
 #include <new>
+#include <string>
 #include <vector>
 
 namespace {
@@ -113,6 +115,18 @@ struct pie_comm {
     long long begun = 0, finished = 0, collected = 0;  // steps begun / exchanges issued / exchanges collected
     int step_nq[kSets] = {};
     int step_rc[kSets] = {};   // a step whose finish failed on this process: its collect reports it
+    // cross-shard dispatch queues (pie_comm_expired_queue / _archive_queue): buffers of their own, sized by the header exchange
+    std::vector<int*> qh_msg, qh_gath;            // local index -> header words [2] / gathered headers [world][2]
+    int* h_qhead = nullptr;                       // pinned: [local index][2] headers to send, then [world][2] as gathered
+    std::vector<int*> q_msg, q_gath;              // local index -> queue message [QL] / gathered messages [world][QL]
+    long long q_msg_words = 0;                    // words allocated per message
+    std::vector<int*> q_rows, q_src_rank, q_src_row; // local index -> the merged queue
+    long long q_out_cap = 0;
+    long long q_total = -1;                       // length of the merged queue (-1: none)
+    std::vector<hipEvent_t> q_ev;                 // local index -> completion of a queue phase
+    hipEvent_t q_tev[5] = {};                     // timing of the last queue call on the first local rank's stream
+    bool q_timed = false;
+    double wait_deadline_ms = 20000.0;            // bound of every wait of the queue path (PIE_WAIT_DEADLINE_MS)
     char err[512] = "";
 };
 
@@ -188,8 +202,13 @@ pie_comm* new_comm(int world, int n_local)
     c->stream.assign((size_t)n_local, nullptr);
     c->msg.assign((size_t)n_local, nullptr);
     c->gath.assign((size_t)n_local, nullptr);
+    for (auto* v : {&c->qh_msg, &c->qh_gath, &c->q_msg, &c->q_gath, &c->q_rows, &c->q_src_rank, &c->q_src_row}) v->assign((size_t)n_local, nullptr);
+    c->q_ev.assign((size_t)n_local, nullptr);
+    if (const char* v = getenv("PIE_WAIT_DEADLINE_MS")) { const double d = atof(v); if (d > 0) c->wait_deadline_ms = d; }
     return c;
 }
+
+void free_queue_buffers(pie_comm* c);
 
 void free_step_buffers(pie_comm* c);
 
@@ -307,6 +326,7 @@ int pie_comm_destroy(pie_comm* c)
     }
     free_buffers(c);
     free_step_buffers(c);
+    free_queue_buffers(c);
     for (int k = 0; k < c->n_local; ++k) {
         (void)hipSetDevice(c->device[k]);
         for (int s = 0; s < pie_comm::kSets; ++s) {
@@ -701,6 +721,361 @@ int pie_comm_read_gathered(pie_comm* c, int32_t at_rank, int32_t src_rank, int32
         if ((size_t)m32 > idx_cap) return cfail(c, PIE_E_CAPACITY, "idx_cap %zu < %d rows", idx_cap, m32);
         if (m32 > 0) PIE_CHIP(c, hipMemcpy(idx_out, msg + c->u_pad + 2, (size_t)m32 * 4, hipMemcpyDeviceToHost));
     }
+    return PIE_OK;
+}
+
+} // extern "C"
+
+// ---- cross-shard dispatch queues (pie_comm_expired_queue / pie_comm_archive_queue) ---------------------------------------
+// Each shard's queue is packed on its device into one message of global rows (pie_queue_pack_device:
+// [n_rows | n_groups | global rows (cap_rows) | local rows (cap_rows) | group offsets (cap_groups + 1)]), exchanged with the direct
+// pattern and merged on every rank's device.  Global rows are unique across ranks and every shard's list is ascending in them
+// (the shard maps are ascending), so an element's place in the merged order is its place in its own list plus, for every other
+// rank, how many of that rank's keys are smaller (a lower bound): no sort, no atomics, the same result on every rank.
+namespace {
+
+constexpr int kQueueMaxWorld = 64; // one lane per rank in the archive merge
+
+// rows / groups of every gathered message, clamped to the message's capacities (the kernels never read past a message)
+__device__ void queue_heads(const int* __restrict__ gath, long long ql, long long cap_rows, long long cap_groups, int world, int* s_n, int* s_g,
+                            long long* s_pre, bool by_groups)
+{
+    if (threadIdx.x == 0) {
+        long long acc = 0;
+        for (int r = 0; r < world; ++r) {
+            const int* m = gath + (long long)r * ql;
+            const long long n = min(max((long long)m[0], 0LL), cap_rows);
+            const long long g = n > 0 ? min(max((long long)m[1], 0LL), cap_groups) : 0;
+            s_n[r] = (int)n;
+            s_g[r] = (int)g;
+            s_pre[r] = acc;
+            acc += by_groups ? g : n;
+        }
+        s_pre[world] = acc;
+    }
+    __syncthreads();
+}
+
+// expired queue: one lane per element, the merged position by co-rank (binary search in every other rank's list)
+__global__ __launch_bounds__(256) void k_merge_expired(const int* __restrict__ gath, long long ql, long long cap_rows, int world, long long out_cap,
+                                                       int* __restrict__ out_rows, int* __restrict__ out_rank, int* __restrict__ out_row)
+{
+    __shared__ int s_n[kQueueMaxWorld], s_g[kQueueMaxWorld];
+    __shared__ long long s_pre[kQueueMaxWorld + 1];
+    queue_heads(gath, ql, cap_rows, 0, world, s_n, s_g, s_pre, false);
+    const long long total = s_pre[world];
+    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long long)gridDim.x * blockDim.x) {
+        int r = 0;
+        while (s_pre[r + 1] <= e) ++r;
+        const long long i = e - s_pre[r];
+        const int* grow = gath + (long long)r * ql + 2;
+        const int v = grow[i];
+        long long pos = i;
+        for (int p = 0; p < world; ++p) {
+            if (p == r) continue;
+            const int* other = gath + (long long)p * ql + 2;
+            int lo = 0, hi = s_n[p];
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (other[mid] < v) lo = mid + 1;
+                else hi = mid;
+            }
+            pos += lo;
+        }
+        if (pos < out_cap) {
+            out_rows[pos] = v;
+            out_rank[pos] = r;
+            out_row[pos] = grow[cap_rows + i];
+        }
+    }
+}
+
+// archive queue: one wave per group; lane p finds how many of rank p's groups have a smaller key (the global row of a group's first
+// queued row) and contributes the rows they hold (their group offset); the wave then copies the group's rows to its place
+__global__ __launch_bounds__(256) void k_merge_archive(const int* __restrict__ gath, long long ql, long long cap_rows, long long cap_groups, int world,
+                                                       long long out_cap, int* __restrict__ out_rows, int* __restrict__ out_rank, int* __restrict__ out_row)
+{
+    __shared__ int s_n[kQueueMaxWorld], s_g[kQueueMaxWorld];
+    __shared__ long long s_pre[kQueueMaxWorld + 1];
+    queue_heads(gath, ql, cap_rows, cap_groups, world, s_n, s_g, s_pre, true);
+    const long long groups = s_pre[world];
+    const int lane = (int)(threadIdx.x & 63);
+    const long long waves = ((long long)gridDim.x * blockDim.x) >> 6;
+    auto goff_at = [&](const int* goff, int j, int n) { return min(max(goff[j], 0), n); };
+    for (long long f = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6; f < groups; f += waves) { // wave-uniform
+        int r = 0;
+        while (s_pre[r + 1] <= f) ++r;
+        const int j = (int)(f - s_pre[r]);
+        const int* grow = gath + (long long)r * ql + 2;
+        const int* lrow = grow + cap_rows;
+        const int* goff = lrow + cap_rows;
+        const int b = goff_at(goff, j, s_n[r]);
+        const int e = max(goff_at(goff, j + 1, s_n[r]), b);
+        const int key = b < s_n[r] ? grow[b] : 0x7FFFFFFF;
+        int before = 0;
+        if (lane < world && lane != r) {
+            const int* g_p = gath + (long long)lane * ql + 2;
+            const int* goff_p = g_p + 2 * cap_rows;
+            const int n_p = s_n[lane];
+            int lo = 0, hi = s_g[lane];
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (g_p[min(goff_at(goff_p, mid, n_p), n_p - 1)] < key) lo = mid + 1;
+                else hi = mid;
+            }
+            before = goff_at(goff_p, lo, n_p);
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) before += __shfl_xor(before, o, 64);
+        const long long dst = (long long)b + before;
+        for (int t = lane; t < e - b; t += 64) {
+            const long long pos = dst + t;
+            if (pos < out_cap) {
+                out_rows[pos] = grow[b + t];
+                out_rank[pos] = r;
+                out_row[pos] = lrow[b + t];
+            }
+        }
+    }
+}
+
+// a bounded wait for an event (PIE_WAIT_DEADLINE_MS): a peer that never sends must not hang the caller
+int wait_event(pie_comm* c, int k, hipEvent_t ev, const char* what)
+{
+    PIE_CHIP(c, hipSetDevice(c->device[k]));
+    timespec t0{};
+    clock_gettime(CLOCK_MONOTONIC, &t0);
+    for (unsigned long long spins = 0;; ++spins) {
+        const hipError_t e = hipEventQuery(ev);
+        if (e == hipSuccess) return PIE_OK;
+        if (e != hipErrorNotReady) return cfail(c, PIE_E_HIP, "rank %d, %s: %s", c->rank_of[k], what, hipGetErrorString(e));
+        timespec t1{};
+        clock_gettime(CLOCK_MONOTONIC, &t1);
+        const double ms = (double)(t1.tv_sec - t0.tv_sec) * 1e3 + (double)(t1.tv_nsec - t0.tv_nsec) * 1e-6;
+        if (ms > c->wait_deadline_ms)
+            return cfail(c, PIE_E_HIP, "rank %d: %s not complete within %.0f ms (PIE_WAIT_DEADLINE_MS): a peer never sent?", c->rank_of[k], what, ms);
+        if (spins < 256) __builtin_ia32_pause();
+        else {
+            const timespec nap{0, 20000};
+            nanosleep(&nap, nullptr);
+        }
+    }
+}
+
+void free_queue_buffers(pie_comm* c)
+{
+    for (int k = 0; k < c->n_local; ++k) {
+        (void)hipSetDevice(c->device[k]);
+        for (auto* v : {&c->qh_msg, &c->qh_gath, &c->q_msg, &c->q_gath, &c->q_rows, &c->q_src_rank, &c->q_src_row})
+            if (k < (int)v->size() && (*v)[k]) { (void)hipFree((*v)[k]); (*v)[k] = nullptr; }
+        if (k < (int)c->q_ev.size() && c->q_ev[k]) { (void)hipEventDestroy(c->q_ev[k]); c->q_ev[k] = nullptr; }
+    }
+    if (c->n_local > 0) (void)hipSetDevice(c->device[0]);
+    for (hipEvent_t& e : c->q_tev)
+        if (e) { (void)hipEventDestroy(e); e = nullptr; }
+    if (c->h_qhead) (void)hipHostFree(c->h_qhead);
+    c->h_qhead = nullptr;
+    c->q_msg_words = c->q_out_cap = 0;
+    c->q_total = -1;
+}
+
+// header buffers and events: once per communicator
+int ensure_queue_heads(pie_comm* c)
+{
+    if (c->h_qhead) return PIE_OK;
+    PIE_CHIP(c, hipHostMalloc(&c->h_qhead, (size_t)c->n_local * (size_t)(c->world + 1) * 8, hipHostMallocDefault));
+    for (int k = 0; k < c->n_local; ++k) {
+        PIE_CHIP(c, hipSetDevice(c->device[k]));
+        PIE_CHIP(c, hipMalloc(&c->qh_msg[k], 8));
+        PIE_CHIP(c, hipMalloc(&c->qh_gath[k], (size_t)c->world * 8));
+        PIE_CHIP(c, hipEventCreateWithFlags(&c->q_ev[k], hipEventDisableTiming));
+    }
+    PIE_CHIP(c, hipSetDevice(c->device[0]));
+    for (hipEvent_t& e : c->q_tev) PIE_CHIP(c, hipEventCreate(&e));
+    return PIE_OK;
+}
+
+// message and merged-queue buffers, grown to what the gathered headers call for (the message length is the same on every rank)
+int ensure_queue_msgs(pie_comm* c, long long words, long long total)
+{
+    for (int k = 0; k < c->n_local; ++k) {
+        PIE_CHIP(c, hipSetDevice(c->device[k]));
+        if (words > c->q_msg_words) {
+            if (c->q_msg[k]) { PIE_CHIP(c, hipFree(c->q_msg[k])); c->q_msg[k] = nullptr; }
+            if (c->q_gath[k]) { PIE_CHIP(c, hipFree(c->q_gath[k])); c->q_gath[k] = nullptr; }
+        }
+        if (total > c->q_out_cap)
+            for (auto* v : {&c->q_rows, &c->q_src_rank, &c->q_src_row})
+                if ((*v)[k]) { PIE_CHIP(c, hipFree((*v)[k])); (*v)[k] = nullptr; }
+    }
+    const long long w = words > c->q_msg_words ? words + words / 16 + 64 : c->q_msg_words;
+    const long long o = total > c->q_out_cap ? total + total / 16 + 64 : c->q_out_cap;
+    c->q_msg_words = 0;
+    c->q_out_cap = 0;
+    for (int k = 0; k < c->n_local; ++k) {
+        PIE_CHIP(c, hipSetDevice(c->device[k]));
+        if (!c->q_msg[k]) PIE_CHIP(c, hipMalloc(&c->q_msg[k], (size_t)w * 4));
+        if (!c->q_gath[k]) PIE_CHIP(c, hipMalloc(&c->q_gath[k], (size_t)w * 4 * (size_t)c->world));
+        for (auto* v : {&c->q_rows, &c->q_src_rank, &c->q_src_row})
+            if (!(*v)[k]) PIE_CHIP(c, hipMalloc(&(*v)[k], (size_t)o * 4));
+    }
+    c->q_msg_words = w;
+    c->q_out_cap = o;
+    return PIE_OK;
+}
+
+// kind 1: expired (a = prev_now, b = now), 2: archive (a = now, b = window_ms)
+int comm_queue(pie_comm* c, int kind, int64_t a, int64_t b, int32_t* queue_out, size_t cap, size_t* q_out)
+{
+    if (!c) return PIE_E_INVAL;
+    if (q_out) *q_out = 0;
+    if (c->world > kQueueMaxWorld) return cfail(c, PIE_E_INVAL, "the queue merge takes at most %d ranks (world %d)", kQueueMaxWorld, c->world);
+    if (c->begun != c->collected) return cfail(c, PIE_E_STATE, "pipelined steps are in flight (pie_comm_step_*): collect them first");
+    c->q_total = -1;
+    c->q_timed = false;
+    int rc = ensure_queue_heads(c);
+    if (rc) return rc;
+    int* h_send = c->h_qhead;                        // [n_local][2]
+    int* h_recv = c->h_qhead + 2 * c->n_local;       // [n_local][world][2]
+    // 1. every local shard's queue stays on its device; its header is {rows, groups}, or {-1, status} when the step failed
+    PIE_CHIP(c, hipSetDevice(c->device[0]));
+    PIE_CHIP(c, hipEventRecord(c->q_tev[0], c->stream[0]));
+    std::vector<int> local_rc((size_t)c->n_local, PIE_OK);
+    std::vector<std::string> local_err((size_t)c->n_local);
+    for (int k = 0; k < c->n_local; ++k) {
+        size_t rows = 0, groups = 0;
+        int r = kind == 1 ? pie_expired_queue(c->ctx[k], a, b, nullptr, 0, &rows) : pie_archive_queue(c->ctx[k], a, b, nullptr, 0, &rows);
+        if (r == PIE_OK) r = pie_queue_info(c->ctx[k], nullptr, &rows, &groups);
+        if (r != PIE_OK) local_err[k] = pie_last_error(c->ctx[k]);
+        local_rc[k] = r;
+        h_send[2 * k] = r == PIE_OK ? (int)rows : -1;
+        h_send[2 * k + 1] = r == PIE_OK ? (int)groups : r;
+        PIE_CHIP(c, hipSetDevice(c->device[k]));
+        PIE_CHIP(c, hipMemcpyAsync(c->qh_msg[k], h_send + 2 * k, 8, hipMemcpyHostToDevice, c->stream[k]));
+    }
+    // 2. the header exchange: the same path in a single-process and a process-per-GPU communicator
+    rc = exchange(c, c->qh_msg, c->qh_gath, 2, 2, c->stream);
+    if (rc) return rc;
+    for (int k = 0; k < c->n_local; ++k) {
+        PIE_CHIP(c, hipSetDevice(c->device[k]));
+        PIE_CHIP(c, hipMemcpyAsync(h_recv + (size_t)k * 2 * c->world, c->qh_gath[k], (size_t)c->world * 8, hipMemcpyDeviceToHost, c->stream[k]));
+        PIE_CHIP(c, hipEventRecord(c->q_ev[k], c->stream[k]));
+    }
+    for (int k = 0; k < c->n_local; ++k) {
+        rc = wait_event(c, k, c->q_ev[k], "queue header exchange");
+        if (rc) return rc;
+    }
+    PIE_CHIP(c, hipSetDevice(c->device[0]));
+    PIE_CHIP(c, hipEventRecord(c->q_tev[1], c->stream[0]));
+    const int* hd = h_recv; // every rank holds the same world headers
+    for (int p = 0; p < c->world; ++p) {
+        if (hd[2 * p] >= 0) continue;
+        int status = hd[2 * p + 1];
+        if (status >= 0 || status < PIE_E_STATE) status = PIE_E_STATE;
+        const int k = local_index(c, p);
+        if (k >= 0 && !local_err[k].empty()) return cfail(c, status, "rank %d: %s", p, local_err[k].c_str());
+        return cfail(c, status, "rank %d could not produce its queue (status %d): no rank merged", p, status);
+    }
+    long long cap_rows = 0, cap_groups = 0, total = 0;
+    for (int p = 0; p < c->world; ++p) {
+        cap_rows = hd[2 * p] > cap_rows ? hd[2 * p] : cap_rows;
+        cap_groups = hd[2 * p + 1] > cap_groups ? hd[2 * p + 1] : cap_groups;
+        total += hd[2 * p];
+    }
+    if (total >= 0x7FFFFFFFLL) return cfail(c, PIE_E_INVAL, "a merged queue of %lld rows does not fit int32", total);
+    const long long ql = 2 + 2 * cap_rows + cap_groups + 1;
+    rc = ensure_queue_msgs(c, ql, total);
+    if (rc) return rc;
+    // 3. pack (global rows through the shard map, on the device) and exchange the messages
+    for (int k = 0; k < c->n_local; ++k) PIE_CCTX(c, k, pie_queue_pack_device(c->ctx[k], c->q_msg[k], (size_t)cap_rows, (size_t)cap_groups));
+    PIE_CHIP(c, hipSetDevice(c->device[0]));
+    PIE_CHIP(c, hipEventRecord(c->q_tev[2], c->stream[0]));
+    rc = exchange(c, c->q_msg, c->q_gath, (size_t)ql, (size_t)ql, c->stream);
+    if (rc) return rc;
+    PIE_CHIP(c, hipSetDevice(c->device[0]));
+    PIE_CHIP(c, hipEventRecord(c->q_tev[3], c->stream[0]));
+    // 4. the merge, on every local rank's device
+    for (int k = 0; k < c->n_local; ++k) {
+        PIE_CHIP(c, hipSetDevice(c->device[k]));
+        if (kind == 1) {
+            const long long blocks = total > 0 ? (total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048 : 1;
+            hipLaunchKernelGGL(k_merge_expired, dim3((unsigned)blocks), dim3(256), 0, c->stream[k], c->q_gath[k], ql, cap_rows, c->world, total,
+                               c->q_rows[k], c->q_src_rank[k], c->q_src_row[k]);
+        } else {
+            long long groups = 0;
+            for (int p = 0; p < c->world; ++p) groups += hd[2 * p + 1];
+            const long long blocks = groups > 0 ? (groups + 3) / 4 < 2048 ? (groups + 3) / 4 : 2048 : 1;
+            hipLaunchKernelGGL(k_merge_archive, dim3((unsigned)blocks), dim3(256), 0, c->stream[k], c->q_gath[k], ql, cap_rows, cap_groups, c->world,
+                               total, c->q_rows[k], c->q_src_rank[k], c->q_src_row[k]);
+        }
+        PIE_CHIP(c, hipGetLastError());
+        if (k == 0) PIE_CHIP(c, hipEventRecord(c->q_tev[4], c->stream[0]));
+        PIE_CHIP(c, hipEventRecord(c->q_ev[k], c->stream[k]));
+    }
+    for (int k = 0; k < c->n_local; ++k) {
+        rc = wait_event(c, k, c->q_ev[k], "queue merge");
+        if (rc) return rc;
+    }
+    c->q_total = total;
+    c->q_timed = true;
+    if (q_out) *q_out = (size_t)total;
+    if (queue_out && (size_t)total > cap) return cfail(c, PIE_E_CAPACITY, "queue cap %zu < %lld", cap, total);
+    if (queue_out && total) {
+        PIE_CHIP(c, hipSetDevice(c->device[0]));
+        PIE_CHIP(c, hipMemcpy(queue_out, c->q_rows[0], (size_t)total * 4, hipMemcpyDeviceToHost));
+    }
+    return PIE_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int pie_comm_expired_queue(pie_comm* c, int64_t prev_now, int64_t now, int32_t* queue_out, size_t cap, size_t* q_out)
+{
+    return comm_queue(c, 1, prev_now, now, queue_out, cap, q_out);
+}
+
+int pie_comm_archive_queue(pie_comm* c, int64_t now, int64_t window_ms, int32_t* queue_out, size_t cap, size_t* q_out)
+{
+    return comm_queue(c, 2, now, window_ms, queue_out, cap, q_out);
+}
+
+int pie_comm_queue_device_ptrs(pie_comm* c, int32_t at_rank, void** rows_dev, void** src_rank_dev, void** src_row_dev, size_t* q_out)
+{
+    if (!c) return PIE_E_INVAL;
+    const int k = local_index(c, at_rank);
+    if (k < 0) return cfail(c, PIE_E_INVAL, "rank %d is not local to this communicator", at_rank);
+    if (c->q_total < 0) return cfail(c, PIE_E_STATE, "no merged queue: pie_comm_expired_queue / pie_comm_archive_queue first");
+    if (rows_dev) *rows_dev = c->q_rows[k];
+    if (src_rank_dev) *src_rank_dev = c->q_src_rank[k];
+    if (src_row_dev) *src_row_dev = c->q_src_row[k];
+    if (q_out) *q_out = (size_t)c->q_total;
+    return PIE_OK;
+}
+
+int pie_comm_queue_read(pie_comm* c, int32_t at_rank, int32_t* rows_out, int32_t* src_rank_out, int32_t* src_row_out, size_t cap, size_t* q_out)
+{
+    void *rows = nullptr, *src_rank = nullptr, *src_row = nullptr;
+    size_t q = 0;
+    const int rc = pie_comm_queue_device_ptrs(c, at_rank, &rows, &src_rank, &src_row, &q);
+    if (rc) return rc;
+    if (q_out) *q_out = q;
+    if ((rows_out || src_rank_out || src_row_out) && q > cap) return cfail(c, PIE_E_CAPACITY, "cap %zu < %zu queued rows", cap, q);
+    if (!q) return PIE_OK;
+    PIE_CHIP(c, hipSetDevice(c->device[local_index(c, at_rank)]));
+    if (rows_out) PIE_CHIP(c, hipMemcpy(rows_out, rows, q * 4, hipMemcpyDeviceToHost));
+    if (src_rank_out) PIE_CHIP(c, hipMemcpy(src_rank_out, src_rank, q * 4, hipMemcpyDeviceToHost));
+    if (src_row_out) PIE_CHIP(c, hipMemcpy(src_row_out, src_row, q * 4, hipMemcpyDeviceToHost));
+    return PIE_OK;
+}
+
+int pie_comm_queue_timing(pie_comm* c, float* ms_out_4)
+{
+    if (!c || !ms_out_4) return PIE_E_INVAL;
+    if (!c->q_timed) return cfail(c, PIE_E_STATE, "no completed queue call to time");
+    PIE_CHIP(c, hipSetDevice(c->device[0]));
+    for (int i = 0; i < 4; ++i) PIE_CHIP(c, hipEventElapsedTime(&ms_out_4[i], c->q_tev[i], c->q_tev[i + 1]));
     return PIE_OK;
 }
 

@@ -3133,6 +3133,33 @@ __global__ __launch_bounds__(256) void k_pack_results(const long long* __restric
     }
 }
 
+// The queue message of one shard (pie_queue_pack_device), for the cross-shard merge of pie_comm_expired_queue / _archive_queue:
+//   [ n_rows | n_groups | global rows (cap_rows) | local rows (cap_rows) | group offsets (cap_groups + 1) ]
+// global row = shard_rows[local row] (the identity without a shard map); group offsets = the exclusive scan of the group sizes
+// in group order, closed by n_rows (n_groups = 0: only goff[0] = n_rows).  One grid-stride pass over the words it writes:
+// consecutive lanes store consecutive words of each part.  Words past n_rows / n_groups + 1 are not written.
+__global__ __launch_bounds__(256) void k_queue_pack(const int* __restrict__ queue, long long n_rows, const unsigned int* __restrict__ goff,
+                                                    int n_groups, const int* __restrict__ shard_rows, long long cap_rows, int* __restrict__ dst)
+{
+    const long long work = 2 + n_rows + (long long)n_groups + 1;
+    int* g_rows = dst + 2;
+    int* l_rows = g_rows + cap_rows;
+    int* g_off = l_rows + cap_rows;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < work; i += (long long)gridDim.x * blockDim.x) {
+        if (i < 2) {
+            dst[i] = i == 0 ? (int)n_rows : n_groups;
+        } else if (i < 2 + n_rows) {
+            const long long k = i - 2;
+            const int r = queue[k];
+            g_rows[k] = shard_rows ? shard_rows[r] : r;
+            l_rows[k] = r;
+        } else {
+            const long long j = i - 2 - n_rows;
+            g_off[j] = j < n_groups ? (int)goff[j] : (int)n_rows;
+        }
+    }
+}
+
 // the same message from lists whose M the host knows (a batch's per-query lists)
 __global__ __launch_bounds__(256) void k_pack_lists(const long long* __restrict__ offsets, int n_users, int u_pad, long long m,
                                                     const int* __restrict__ out_idx, long long cap, int* __restrict__ dst)

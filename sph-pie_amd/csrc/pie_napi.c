@@ -70,7 +70,11 @@
     X(int, pie_comm_step_finish, (pie_comm *, size_t *))                                                            \
     X(int, pie_comm_step_collect, (pie_comm *, int64_t *))                                                          \
     X(int, pie_comm_step_gathered_ptr, (pie_comm *, int32_t, int64_t, void **, size_t *, size_t *, size_t *))       \
-    X(int, pie_comm_step_read_gathered, (pie_comm *, int32_t, int32_t, int64_t, int32_t *, int32_t *, uint64_t *, size_t, size_t *))
+    X(int, pie_comm_step_read_gathered, (pie_comm *, int32_t, int32_t, int64_t, int32_t *, int32_t *, uint64_t *, size_t, size_t *)) \
+    X(int, pie_comm_expired_queue, (pie_comm *, int64_t, int64_t, int32_t *, size_t, size_t *))                     \
+    X(int, pie_comm_archive_queue, (pie_comm *, int64_t, int64_t, int32_t *, size_t, size_t *))                     \
+    X(int, pie_comm_queue_read, (pie_comm *, int32_t, int32_t *, int32_t *, int32_t *, size_t, size_t *))            \
+    X(int, pie_shard_maps, (pie_ctx *, int32_t *, int32_t *))
 
 #define X(ret, name, args) static ret(*p_##name) args;
 PIE_SYMBOLS(X)
@@ -1345,6 +1349,67 @@ static napi_value fn_comm_read(napi_env env, napi_callback_info info)
     return js_int(env, (int64_t)m);
 }
 
+/* commExpiredQueue(comm, prevNow, now, rows Int32Array[, srcRank Int32Array, srcRow Int32Array]) -> q
+ * commArchiveQueue(comm, now, windowMs, rows Int32Array[, srcRank, srcRow]) -> q
+ * The dispatch queue of the whole sharded table, merged on the devices: ascending global rows (expired), or the archive
+ * queue's global rows; srcRank / srcRow (optional, both or neither) = the shard that holds each row and its local row there.
+ * Throws with .code = PIE_E_CAPACITY (-5) when rows is shorter than the queue, like expiredQueue / archiveQueue. */
+static napi_value comm_queue_call(napi_env env, napi_callback_info info, int archive)
+{
+    size_t argc = 6;
+    napi_value argv[6];
+    CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    const char *usage = archive ? "commArchiveQueue(comm, now, windowMs, Int32Array rows[, Int32Array srcRank, Int32Array srcRow])"
+                                : "commExpiredQueue(comm, prevNow, now, Int32Array rows[, Int32Array srcRank, Int32Array srcRow])";
+    if (argc != 4 && argc != 6) {
+        napi_throw_type_error(env, NULL, usage);
+        return NULL;
+    }
+    comm_box *cbx = get_comm_box(env, argv[0]); /* refuses while scanAsync runs on one of the shard contexts */
+    if (!cbx) return NULL;
+    pie_comm *cm = cbx->comm;
+    int64_t a = 0, b = 0;
+    size_t cap = 0, c1 = 0, c2 = 0, q = 0;
+    int32_t *rows = typed(env, argv[3], napi_int32_array, &cap);
+    int32_t *src_rank = argc == 6 ? typed(env, argv[4], napi_int32_array, &c1) : NULL;
+    int32_t *src_row = argc == 6 ? typed(env, argv[5], napi_int32_array, &c2) : NULL;
+    if (!get_i64(env, argv[1], &a) || !get_i64(env, argv[2], &b) || !rows || (argc == 6 && (!src_rank || !src_row))) {
+        napi_throw_type_error(env, NULL, usage);
+        return NULL;
+    }
+    int rc = archive ? p_pie_comm_archive_queue(cm, a, b, rows, cap, &q) : p_pie_comm_expired_queue(cm, a, b, rows, cap, &q);
+    if (rc) return throw_comm(env, cm, rc);
+    if (src_rank) {
+        int32_t at = 0; /* the first local rank: the copy rows came from */
+        while (at < p_pie_comm_world(cm) && !p_pie_comm_ctx(cm, at)) ++at;
+        rc = p_pie_comm_queue_read(cm, at, NULL, src_rank, src_row, c1 < c2 ? c1 : c2, &q);
+        if (rc) return throw_comm(env, cm, rc);
+    }
+    return js_int(env, (int64_t)q);
+}
+static napi_value fn_comm_expired_queue(napi_env env, napi_callback_info info) { return comm_queue_call(env, info, 0); }
+static napi_value fn_comm_archive_queue(napi_env env, napi_callback_info info) { return comm_queue_call(env, info, 1); }
+
+/* shardMaps(ctx, rowsOut Int32Array[>= rows], usersOut Int32Array[>= users]) -> rows: a shard's local row -> global row and
+ * local user -> global user (pie_shard_maps) */
+static napi_value fn_shard_maps(napi_env env, napi_callback_info info)
+{
+    ARGS(3)
+    pie_ctx *ctx = get_ctx(env, argv[0]);
+    if (!ctx) return NULL;
+    size_t rows = 0, users = 0, cr = 0, cu = 0;
+    int rc = table_shape(ctx, &rows, &users);
+    if (rc) return throw_pie(env, ctx, rc);
+    int32_t *r = typed(env, argv[1], napi_int32_array, &cr), *u = typed(env, argv[2], napi_int32_array, &cu);
+    if (!r || !u || cr < rows || cu < users) {
+        napi_throw_type_error(env, NULL, "shardMaps(ctx, Int32Array rowsOut[>= rows], Int32Array usersOut[>= users])");
+        return NULL;
+    }
+    rc = p_pie_shard_maps(ctx, r, u);
+    if (rc) return throw_pie(env, ctx, rc);
+    return js_int(env, (int64_t)rows);
+}
+
 /* commUPad(comm, atRank) -> users per message (the largest shard's user count) of the last exchange */
 static napi_value fn_comm_upad(napi_env env, napi_callback_info info)
 {
@@ -1568,7 +1633,8 @@ static napi_value init(napi_env env, napi_value exports)
         {"commGenSyntheticSharded", fn_comm_gen}, {"commScanBatchGather", fn_comm_scan_gather}, {"commReadGathered", fn_comm_read}, {"commUPad", fn_comm_upad},
         {"commNeededCap", fn_comm_needed_cap}, {"commStepReserve", fn_comm_step_reserve}, {"commStepBegin", fn_comm_step_begin},
         {"commStepFinish", fn_comm_step_finish}, {"commStepCollect", fn_comm_step_collect}, {"commStepReadGathered", fn_comm_step_read},
-        {"commStepUPad", fn_comm_step_upad},
+        {"commStepUPad", fn_comm_step_upad}, {"commExpiredQueue", fn_comm_expired_queue}, {"commArchiveQueue", fn_comm_archive_queue},
+        {"shardMaps", fn_shard_maps},
     };
     for (size_t i = 0; i < sizeof table / sizeof table[0]; ++i) {
         napi_value fn;

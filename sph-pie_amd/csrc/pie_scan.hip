@@ -356,6 +356,13 @@ struct pie_ctx {
     unsigned long long arch_alg_bytes = 0; // algorithmic bytes of the last archive queue (32 B/row + 4 B per queued row)
     double arch_ms_sum = 0;                // with profiling on: device time of the archive chains (first kernel -> last sort)
     unsigned arch_calls = 0;
+    // the queue the last pie_expired_queue / pie_archive_queue left on the device (pie_queue_info, pie_queue_pack_device); any
+    // call that reuses the slots' workspace forgets it (queue_forget)
+    int q_kind = 0;                        // 0: none, 1: expired, 2: archive
+    long long q_rows = 0;                  // its length
+    int q_groups = 0;                      // archive: qualifying groups
+    const int* q_dev = nullptr;            // the queue (local rows)
+    const unsigned int* q_goff = nullptr;  // archive: exclusive scan of the group sizes, in group order
 
     // shared scratch
     long long* d_blk_off = nullptr;
@@ -438,8 +445,18 @@ Slot* oldest_in_flight(pie_ctx* c)
     return &c->slot[c->n_flight == 2 ? c->next_slot : (c->next_slot ^ 1)];
 }
 
+void queue_forget(pie_ctx* c)
+{
+    c->q_kind = 0;
+    c->q_rows = 0;
+    c->q_groups = 0;
+    c->q_dev = nullptr;
+    c->q_goff = nullptr;
+}
+
 void free_slots(pie_ctx* c)
 {
+    queue_forget(c);
     for (Slot& s : c->slot) {
         s.counts = nullptr; s.sum = nullptr;
         s.tile_pub = nullptr; s.ctl = nullptr;
@@ -616,6 +633,7 @@ int ensure_sel(pie_ctx* c)
         if (span > need) need = span;
     }
     if (need <= c->sel_cap && c->slot[0].sel) return PIE_OK;
+    queue_forget(c);
     PIE_HIP(c, hipStreamSynchronize(c->stream));
     for (Slot& s : c->slot) {
         dfree(s.sel);
@@ -1550,6 +1568,7 @@ int scan_begin(pie_ctx* c, long long now, long long cutoff, int* msg = nullptr, 
                int* msg_counts = nullptr);
 int scan_begin(pie_ctx* c, long long now, long long cutoff, int* msg, int msg_u_pad, long long msg_cap, int* msg_counts)
 {
+    queue_forget(c); // the slots' workspace is about to be reused
     if (c->cap_rows == 0) return fail(c, PIE_E_STATE, "no table loaded");
     if (c->n_flight >= 2) return fail(c, PIE_E_STATE, "two scans are already in flight: call pie_scan_finish first");
     if (c->key_rebuild && c->n_flight == 0) {
@@ -2003,6 +2022,7 @@ template <int MODE>
 int run_row_list(pie_ctx* c, long long a, long long b, int32_t* out, size_t cap, size_t* k_out)
 {
     if (k_out) *k_out = 0;
+    queue_forget(c);
     if (c->cap_rows == 0) return fail(c, PIE_E_STATE, "no table loaded");
     if (c->n == 0) return PIE_OK;
     if (c->n_flight || c->b_flight) return fail(c, PIE_E_STATE, "a scan is in flight");
@@ -2226,6 +2246,7 @@ void launch_batch_k2(pie_ctx* c, BatchSlot& b, hipStream_t s)
 int batch_begin(pie_ctx* c, const pie_query* qs, int n_q, int msg_kind, int* msg, long long msg_stride, int u_pad, long long msg_cap,
                 int* msg_counts, long long msg_counts_stride)
 {
+    queue_forget(c); // the ordered run's union stages in the slots' workspace
     if (c->cap_rows == 0) return fail(c, PIE_E_STATE, "no table loaded");
     if (!qs || n_q < 1 || n_q > kBatchMax) return fail(c, PIE_E_INVAL, "a batch holds 1..%d queries (got %d)", kBatchMax, n_q);
     if (c->n_flight) return fail(c, PIE_E_STATE, "a single scan is in flight: finish it before beginning a batch");
@@ -3810,11 +3831,17 @@ int pie_expired_queue(pie_ctx* c, int64_t prev_now, int64_t now, int32_t* queue_
 {
     if (!c) return PIE_E_INVAL;
     if (q_out) *q_out = 0;
+    queue_forget(c);
     if (c->cap_rows == 0) return fail(c, PIE_E_STATE, "no table loaded");
-    if (c->n == 0) return PIE_OK;
+    if (c->n == 0) { c->q_kind = 1; return PIE_OK; } // an empty queue: nothing on the device to read
     if (c->n_flight || c->b_flight) return fail(c, PIE_E_STATE, "a scan is in flight");
-    if (getenv("PIE_EXPIRED_TWO_PASS")) // the count / prefix / write form, kept for A-B runs
-        return run_row_list<0>(c, (long long)prev_now, (long long)now, queue_out, cap, q_out);
+    if (getenv("PIE_EXPIRED_TWO_PASS")) { // the count / prefix / write form, kept for A-B runs
+        size_t k = 0;
+        const int rc = run_row_list<0>(c, (long long)prev_now, (long long)now, queue_out, cap, &k);
+        if (rc == PIE_OK || rc == PIE_E_CAPACITY) { c->q_kind = 1; c->q_rows = (long long)k; c->q_dev = c->slot[0].out_idx; }
+        if (q_out) *q_out = k;
+        return rc;
+    }
     PIE_HIP(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
     // workspace: slot 0's out_idx is the device-side queue, slot 1's out_idx the per-wave staging, slot 0's
@@ -3880,6 +3907,9 @@ int pie_expired_queue(pie_ctx* c, int64_t prev_now, int64_t now, int32_t* queue_
         __atomic_thread_fence(__ATOMIC_ACQUIRE);
         k = (size_t)q.h_sum->s.m;
     }
+    c->q_kind = 1;
+    c->q_rows = (long long)k;
+    c->q_dev = q.out_idx;
     if (q_out) *q_out = k;
     if (queue_out && k > cap) return fail(c, PIE_E_CAPACITY, "queue cap %zu < %zu", cap, k);
     if (queue_out && k) {
@@ -3908,8 +3938,9 @@ int pie_archive_queue(pie_ctx* c, int64_t now, int64_t window_ms, int32_t* queue
 {
     if (!c) return PIE_E_INVAL;
     if (q_out) *q_out = 0;
+    queue_forget(c);
     if (c->cap_rows == 0) return fail(c, PIE_E_STATE, "no table loaded");
-    if (c->n == 0) return PIE_OK;
+    if (c->n == 0) { c->q_kind = 2; return PIE_OK; } // an empty queue: nothing on the device to read
     if (c->n_flight || c->b_flight) return fail(c, PIE_E_STATE, "a scan is in flight");
     PIE_HIP(c, hipSetDevice(c->device));
     int rc = sync_all(c);
@@ -4020,10 +4051,15 @@ int pie_archive_queue(pie_ctx* c, int64_t now, int64_t window_ms, int32_t* queue
         if (ev1) PIE_HIP(c, hipEventRecord(ev1, s));
         if (queue_out) PIE_HIP(c, hipMemcpyAsync(queue_out, d_queue, q * 4, hipMemcpyDeviceToHost, s));
         PIE_HIP(c, hipStreamSynchronize(s));
+        c->q_dev = d_queue;
+        c->q_goff = d_off;
+        c->q_groups = (int)n_qual;
     } else if (ev1) {
         PIE_HIP(c, hipEventRecord(ev1, s));
         PIE_HIP(c, hipStreamSynchronize(s));
     }
+    c->q_kind = 2;
+    c->q_rows = (long long)q;
     if (ev0) {
         float ms = 0;
         if (hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) { c->arch_ms_sum += ms; c->arch_calls++; }
@@ -4039,6 +4075,37 @@ int pie_archive_stats(pie_ctx* c, double* ms_sum_out, uint32_t* calls_out, uint6
     if (ms_sum_out) *ms_sum_out = c->arch_ms_sum;
     if (calls_out) *calls_out = c->arch_calls;
     if (alg_bytes_out) *alg_bytes_out = c->arch_alg_bytes;
+    return PIE_OK;
+}
+
+int pie_queue_info(pie_ctx* c, int32_t* kind_out, size_t* rows_out, size_t* groups_out)
+{
+    if (!c) return PIE_E_INVAL;
+    if (kind_out) *kind_out = c->q_kind;
+    if (rows_out) *rows_out = (size_t)c->q_rows;
+    if (groups_out) *groups_out = (size_t)c->q_groups;
+    if (c->q_kind == 0) return fail(c, PIE_E_STATE, "no queue on the device: pie_expired_queue / pie_archive_queue first");
+    if (c->d_shard_rows && c->n > c->shard_rows_n)
+        return fail(c, PIE_E_STATE, "%lld rows were added after pie_shard_table: they have no global row", c->n - c->shard_rows_n);
+    return PIE_OK;
+}
+
+int pie_queue_pack_device(pie_ctx* c, void* dst_i32, size_t cap_rows, size_t cap_groups)
+{
+    if (!c) return PIE_E_INVAL;
+    int rc = pie_queue_info(c, nullptr, nullptr, nullptr);
+    if (rc) return rc;
+    if (!dst_i32) return fail(c, PIE_E_INVAL, "dst is NULL");
+    if (cap_rows > 0x3FFFFFF0u || cap_groups > 0x3FFFFFF0u) return fail(c, PIE_E_INVAL, "cap_rows / cap_groups above 2^30");
+    if ((size_t)c->q_rows > cap_rows || (size_t)c->q_groups > cap_groups)
+        return fail(c, PIE_E_CAPACITY, "queue of %lld rows / %d groups above cap %zu / %zu", c->q_rows, c->q_groups, cap_rows, cap_groups);
+    PIE_HIP(c, hipSetDevice(c->device));
+    const long long work = 2 + c->q_rows + (long long)c->q_groups + 1;
+    long long grid = (work + 255) / 256;
+    if (grid > (long long)c->n_cus * 8) grid = (long long)c->n_cus * 8;
+    hipLaunchKernelGGL(k_queue_pack, dim3((unsigned)grid), dim3(256), 0, c->stream, c->q_dev, c->q_rows, c->q_goff, c->q_groups,
+                       (const int*)c->d_shard_rows, (long long)cap_rows, (int*)dst_i32);
+    PIE_HIP(c, hipGetLastError());
     return PIE_OK;
 }
 

@@ -1,0 +1,113 @@
+'use strict';
+// A dispatch-queue source over a SHARDED table: the shape dispatchQueue.js drains (expiredRows / archivedRows / fetchRows /
+// userIds) on top of a communicator (pie_comm_*).  The queues are the whole table's — every shard computes its own, the
+// communicator merges them on the devices into global rows (pie_comm_expired_queue / pie_comm_archive_queue) — and each row
+// comes back with the shard that holds it and its local row there, which is how fetchRows reads it: one pie_fetch_rows per
+// source shard with local rows, users mapped back to global ids through the shard's map (pie_shard_maps).  So
+// dispatchQueue.dispatchExpiredSessions / dispatchArchivedGroups run unchanged over a sharded table.
+//   createShardedQueue(native, comm[, {userIds, windowMs}])
+//     native   the addon (pieNative.load())
+//     comm     a communicator (native.commCreate) whose shards hold the table (commGenSyntheticSharded, or loaded and sharded)
+//     userIds  global user id -> userId string (default: 'user-' + id, the names of a synthetic base)
+const SESSION_TTL_MS = 12 * 60 * 60 * 1000;
+const END_NONE = -(2n ** 63n);
+const PIE_E_CAPACITY = -5;
+
+function createShardedQueue(native, comm, options){
+  const opts = options || {};
+  const world = native.commWorld(comm);
+  const shards = [];
+  let totalRows = 0;
+  let nUsers = 0;
+  for(let r = 0; r < world; r++){
+    const ctx = native.commCtx(comm, r);
+    const st = native.stats(ctx);
+    const rows = Number(st.rows), users = Number(st.users);
+    const rowMap = new Int32Array(Math.max(rows, 1)), userMap = new Int32Array(Math.max(users, 1)).fill(-1);
+    native.shardMaps(ctx, rowMap, userMap);
+    for(let u = 0; u < users; u++){ nUsers = Math.max(nUsers, userMap[u] + 1); }
+    shards.push({ctx, users: userMap});
+    totalRows += rows;
+  }
+  let userIds = opts.userIds || null;
+
+  // the merged queue of the last call and where each row lives
+  let cap = 1024;
+  let bufRows = new Int32Array(cap), bufRank = new Int32Array(cap), bufLocal = new Int32Array(cap);
+  let last = null;                                  // {rows, rank, local}
+
+  function merged(call){
+    for(;;){
+      try{
+        const q = call(bufRows, bufRank, bufLocal);
+        last = {rows: bufRows.slice(0, q), rank: bufRank.slice(0, q), local: bufLocal.slice(0, q)};
+        return last.rows;
+      }catch(err){
+        if(err.code !== PIE_E_CAPACITY || cap >= totalRows){ throw err; }
+        cap = Math.max(totalRows, 1);               // the queue outgrew the buffers: room for every row, once
+        bufRows = new Int32Array(cap); bufRank = new Int32Array(cap); bufLocal = new Int32Array(cap);
+      }
+    }
+  }
+
+  // ascending global rows with prevNow < expiresAt <= now over every shard
+  function expiredRows(prevNow, now){
+    const prev = prevNow === null || prevNow === undefined ? END_NONE : prevNow;
+    return merged((rows, rank, local) => native.commExpiredQueue(comm, prev, now, rows, rank, local));
+  }
+
+  // the archive queue of the whole table: users whose earliest session is at least windowMs old, in order of first appearance
+  function archivedRows(now, windowMs){
+    const w = windowMs === undefined ? (opts.windowMs === undefined ? SESSION_TTL_MS : opts.windowMs) : windowMs;
+    return merged((rows, rank, local) => native.commArchiveQueue(comm, now, w, rows, rank, local));
+  }
+
+  // columns of global rows of the last queue (any subset, any order): {start, end, user (global id), disc}
+  function fetchRows(globalRows){
+    const m = globalRows.length;
+    const out = {start: new BigInt64Array(m), end: new BigInt64Array(m), user: new Int32Array(m), disc: new Int32Array(m)};
+    if(m === 0){ return out; }
+    let rank = null, local = null;
+    if(last !== null && globalRows === last.rows){
+      rank = last.rank; local = last.local;
+    }else{
+      const at = new Map();
+      if(last !== null){ last.rows.forEach((g, i) => at.set(g, i)); }
+      rank = new Int32Array(m); local = new Int32Array(m);
+      for(let i = 0; i < m; i++){
+        const k = at.get(globalRows[i]);
+        if(k === undefined){ throw new Error('row ' + globalRows[i] + ' is not in the last queue of this source'); }
+        rank[i] = last.rank[k]; local[i] = last.local[k];
+      }
+    }
+    const per = shards.map(() => []);
+    for(let i = 0; i < m; i++){ per[rank[i]].push(i); }
+    per.forEach((pos, r) => {
+      if(pos.length === 0){ return; }
+      const k = pos.length;
+      const idx = Int32Array.from(pos, i => local[i]);
+      const s = new BigInt64Array(k), e = new BigInt64Array(k), u = new Int32Array(k), d = new Int32Array(k);
+      native.fetchRows(shards[r].ctx, idx, k, s, e, u, d);
+      const users = shards[r].users;
+      for(let j = 0; j < k; j++){
+        const i = pos[j];
+        out.start[i] = s[j]; out.end[i] = e[j]; out.disc[i] = d[j];
+        out.user[i] = users[u[j]];
+      }
+    });
+    return out;
+  }
+
+  return {
+    expiredRows, archivedRows, fetchRows,
+    userIds: () => {
+      if(userIds === null){ userIds = Array.from({length: nUsers}, (_, g) => 'user-' + g); }
+      return userIds;
+    },
+    world: () => world,
+    tableRows: () => totalRows,
+    native
+  };
+}
+
+module.exports = {createShardedQueue};
