@@ -211,6 +211,29 @@ int pie_batch_union_device_ptrs(pie_ctx *ctx, void **uoff_dev /* int64[U+1] */, 
                                 void **mask_lo_dev /* uint32[Mu]: queries 0..31 */, void **mask_hi_dev /* uint32[Mu]: 32..63, NULL for n_q <= 32 */,
                                 size_t *mu_out);
 int pie_batch_read_union(pie_ctx *ctx, int64_t *uoff_out, int32_t *rows_out, uint64_t *masks_out, size_t cap, size_t *mu_out);
+/* ---- WIDE batches: 1..PIE_WIDE_MAX queries, one table pass.  The same pie_query records and the same semantics as the batch
+ * above: Feed(q, u) is bit for bit what pie_scan with query q's (now, cutoff, mask) gives.  Wide and ordinary batches share the
+ * context's lanes, slots and FIFO (pie_batch_room counts both; finish order is begin order).  pie_scan_batch_finish[_packed]
+ * return PIE_E_STATE and consume nothing when the oldest batch in flight is wide; pie_scan_wide_finish finishes the oldest batch
+ * of either kind (m_out: n_q counts; PIE_E_CAPACITY if m_cap < n_q, nothing consumed).  After a wide batch the readers that take
+ * a query index (pie_batch_read_results, pie_batch_result_device_ptrs, pie_batch_read_user_feed, pie_batch_fetch_requests) accept
+ * every qi < n_q; the 32/64-bit union readers (pie_batch_union_device_ptrs, pie_batch_read_union, pie_batch_pack_union_device)
+ * return PIE_E_STATE.  A wide batch whose queries fall back (dense queries, a user whose union outgrows 64 slots, bad rows), on a
+ * table whose batches take the ordered run, or on a table that cannot run the batched pass, has exact per-query results and no
+ * union: the wide union readers return PIE_E_STATE.  The wide state (mask words, host summaries) is allocated by the first wide
+ * batch of a context. */
+#define PIE_WIDE_MAX 512
+int pie_scan_wide_begin(pie_ctx *ctx, const pie_query *queries, int n_q);
+int pie_scan_wide_finish(pie_ctx *ctx, size_t *m_out, size_t m_cap, int *n_q_out);
+/* The union of the last finished wide batch: words = ceil(n_q / 64) uint64 mask words per union row, bit q of row r =
+ * masks[r * words + q / 64] >> (q % 64) & 1.  Device pointers are valid until three more batches have begun on the lane. */
+int pie_batch_union_wide_device_ptrs(pie_ctx *ctx, void **uoff_dev /* int64[U+1] */, void **rows_dev /* int32[Mu] */,
+                                     void **masks_dev /* uint64[Mu][words] */, int *words_out, size_t *mu_out);
+int pie_batch_read_union_wide(pie_ctx *ctx, int64_t *uoff_out, int32_t *rows_out, uint64_t *masks_out /* [cap][words] */, size_t cap,
+                              int *words_out, size_t *mu_out);
+/* The exchange message of the wide union into device memory, enqueued on the context's stream:
+ * [ uoff[0..u_pad] | Mu | rows[0..cap) | masks[0..cap) as 2 * words int32 words per row ] (rows beyond cap are cut). */
+int pie_batch_pack_union_wide_device(pie_ctx *ctx, void *dst_i32, size_t u_pad, size_t cap);
 /* Batch LANES.  A batch over a shard-sized table (a tenth of 10^8 rows) is one launch of ~20 us that occupies a fraction of
  * the chip: its time is latency, not bytes, and that floor is what would cap an 8-GPU split of the table at 2.5x.  A context
  * therefore deals its batches to up to four lanes — independent pipelines, each with its own HIP stream, three batch slots and

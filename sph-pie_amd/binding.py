@@ -39,6 +39,7 @@ class PieQuery(C.Structure):
 
 
 PIE_BATCH_MAX = 64
+PIE_WIDE_MAX = 512
 
 
 class PieStats(C.Structure):
@@ -98,6 +99,11 @@ _SIGS = [
     ("pie_batch_read_union", C.c_int, [_P, _P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("pie_scan_batch_begin_packed", C.c_int, [_P, C.POINTER(PieQuery), C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t]),
     ("pie_scan_batch_finish_packed", C.c_int, [_P, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
+    ("pie_scan_wide_begin", C.c_int, [_P, C.POINTER(PieQuery), C.c_int]),
+    ("pie_scan_wide_finish", C.c_int, [_P, _P, C.c_size_t, C.POINTER(C.c_int)]),
+    ("pie_batch_union_wide_device_ptrs", C.c_int, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_int), C.POINTER(C.c_size_t)]),
+    ("pie_batch_read_union_wide", C.c_int, [_P, _P, _P, _P, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_size_t)]),
+    ("pie_batch_pack_union_wide_device", C.c_int, [_P, _P, C.c_size_t, C.c_size_t]),
     ("pie_batch_read_results", C.c_int, [_P, C.c_int, _P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("pie_batch_result_device_ptrs", C.c_int, [_P, C.c_int, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P)]),
     ("pie_batch_read_user_feed", C.c_int, [_P, C.c_int, C.c_int32, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
@@ -486,6 +492,63 @@ class PieScan:
             self._check(rc)
         ms = m[:nq] if want_m else None
         return (ms, bool(ready.value)) if packed else ms
+
+    # ---- wide batches: up to PIE_WIDE_MAX queries, one table pass (same semantics as scan_batch)
+    @staticmethod
+    def _wide_queries(queries):
+        # marshalled on every call: no identity cache (a list changed in place must not re-run the old queries)
+        arr = (PieQuery * max(len(queries), 1))()
+        for k, (now, cutoff, mask) in enumerate(queries):
+            arr[k].now, arr[k].cutoff, arr[k].mask = int(now), int(cutoff), int(mask) & (2 ** 64 - 1)
+        return arr
+
+    def scan_wide_begin(self, queries):
+        """queries: sequence of (now, cutoff, mask), 1..PIE_WIDE_MAX.  Shares the lanes and the FIFO with scan_batch_begin."""
+        queries = list(queries)
+        self._check(self._lib.pie_scan_wide_begin(self._ctx, self._wide_queries(queries), len(queries)))
+        self._batches = getattr(self, "_batches", [])
+        self._batches.append(len(queries))
+
+    def scan_wide_finish(self):
+        """-> list of M per query of the oldest batch in flight, wide or not."""
+        m = (C.c_size_t * PIE_WIDE_MAX)()
+        nq = C.c_int(0)
+        rc = self._lib.pie_scan_wide_finish(self._ctx, m, PIE_WIDE_MAX, C.byref(nq))
+        if getattr(self, "_batches", None) and rc not in (-6, PIE_E_CAPACITY):
+            self._batches.pop(0)
+        self._check(rc)
+        return [int(x) for x in m[: nq.value]]
+
+    def scan_wide(self, queries):
+        """-> [(counts, offsets, idx)] per query; bit for bit what scan() gives for each (now, cutoff) under its mask."""
+        queries = list(queries)
+        self.scan_wide_begin(queries)
+        self.scan_wide_finish()
+        return [self.batch_read_results(k) for k in range(len(queries))]
+
+    def batch_read_union_wide(self):
+        """Union of the last finished wide batch: (uoff[U+1] int64, rows[Mu] int32, masks[Mu, words] uint64) — bit q of row r is
+        masks[r, q // 64] >> (q % 64) & 1 — or None when the batch has no union (queries fell back)."""
+        a, b, mk, words, mu = _P(), _P(), _P(), C.c_int(0), C.c_size_t(0)
+        rc = self._lib.pie_batch_union_wide_device_ptrs(self._ctx, C.byref(a), C.byref(b), C.byref(mk), C.byref(words), C.byref(mu))
+        if rc == -6 and b"has no union result" in (self._lib.pie_last_error(self._ctx) or b""):
+            return None              # the last batch is wide and its queries fell back; any other misuse raises
+        self._check(rc)
+        w, n = int(words.value), int(mu.value)
+        uoff = np.empty(self.n_users + 1, np.int64)
+        rows, masks = np.empty(max(n, 1), np.int32), np.empty((max(n, 1), w), np.uint64)
+        self._check(self._lib.pie_batch_read_union_wide(self._ctx, _ptr(uoff), _ptr(rows), _ptr(masks), n, C.byref(words), C.byref(mu)))
+        return uoff, rows[:n], masks[:n]
+
+    def batch_union_wide_device_ptrs(self):
+        """-> (uoff, rows, masks device addresses, words, Mu) of the last finished wide batch (PieError PIE_E_STATE without a union)"""
+        a, b, mk, words, mu = _P(), _P(), _P(), C.c_int(0), C.c_size_t(0)
+        self._check(self._lib.pie_batch_union_wide_device_ptrs(self._ctx, C.byref(a), C.byref(b), C.byref(mk), C.byref(words), C.byref(mu)))
+        return a.value, b.value, mk.value, int(words.value), int(mu.value)
+
+    def batch_pack_union_wide_device(self, dst_ptr, u_pad, cap):
+        """Wide union message into device memory (pie_batch_pack_union_wide_device); enqueued on the context's stream."""
+        self._check(self._lib.pie_batch_pack_union_wide_device(self._ctx, dst_ptr, int(u_pad), int(cap)))
 
     def batch_pack_union_device(self, dst_ptr, u_pad, cap):
         """Union message of the last finished batch into device memory (pie_batch_pack_union_device); enqueued, not waited for."""

@@ -2729,6 +2729,380 @@ __global__ __launch_bounds__(256) void k_union_pack(int n_users, int u_pad, cons
     }
 }
 
+// ------------------------------------------------------------------------------------------------ wide batches: up to 512 queries, one table pass
+//
+// The same union as the batched pass above (per user the rows any query selected, in (start, row) order, with a query mask per
+// row), for up to kWideMax queries: eight 64-bit mask words per row instead of two 32-bit ones.  The prefix tables of BatchTables
+// would be 65 KB at 512 queries (live / win: 513 x 8 words each), more LDS than three blocks per CU can share, so the predicate
+// is turned around: lane l of a wave HOLDS queries 8 l .. 8 l + 7 (their now, cutoff, key(now) and discipline mask in registers)
+// and the wave evaluates its queued candidates one after the other, every lane answering for its eight queries.  Candidate j's
+// 512-bit mask is then byte l of lane l: the wave writes it to a 64-byte LDS row, and the candidate's own lane issues the ONE
+// histogram atomic and stores the bucket record and its 64-byte mask row — the same atomics as a single query, whatever Q.
+// Caller indices are the mask bits: no relabelling to undo.  Per-query selected totals are counted by the same lanes (eight
+// counters per lane) and added up once per block.
+constexpr int kWideMax = 512;
+constexpr int kWideWords = kWideMax / 64;        // mask words per bucket slot
+constexpr int kWideQPerLane = kWideMax / kWave;  // queries a lane evaluates
+
+struct alignas(16) WideQuery { // one query as its lane holds it; an unused or falling-back query has mask 0 and selects nothing
+    long long now, cutoff;
+    unsigned long long mask;   // discipline mask, cut to the context's n_disc
+    unsigned nk;               // key(now)
+    unsigned pad;
+};
+
+template <class KT>
+struct WideScanArgs {
+    const PayRec* pay;
+    const long long* end;
+    const KT* key;
+    long long n;
+    int n_users;
+    int dshift;                // log2 of the union bucket's slot capacity
+    int run_shift;             // see KeyedArgs
+    unsigned min_key;          // smallest key(now) of the queries that take part
+    int* counts;               // union histogram (hist_index order)
+    Summary* summary;          // bad_rows, cand, chunk_max
+    BktRec* direct;            // union bucket slots, (1 << dshift) per user (BktRec::pad unused)
+    unsigned long long* dmask; // kWideWords mask words per bucket slot
+    unsigned* mq;              // [kWideMax] selected rows per query
+    const WideQuery* wq;       // [kWideMax]
+};
+
+__device__ __forceinline__ long long readlane_i64(long long v, int j)
+{
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(unsigned long long)v, j);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)((unsigned long long)v >> 32), j);
+    return (long long)(((unsigned long long)hi << 32) | lo);
+}
+
+template <int UNROLL, bool NT, class KT>
+__device__ __forceinline__ void scan_wide_body(const WideScanArgs<KT>& a, int bid, int n_scan_blocks)
+{
+    __shared__ int ring_row[kK1Waves][kLiveRing];
+    __shared__ int ring_key[kK1Waves][kLiveRing];
+    __shared__ alignas(16) unsigned char s_qm[kK1Waves][kWave][kWave]; // per wave: candidate j's query mask, byte l from lane l
+    __shared__ unsigned s_mq[kWideMax];
+    __shared__ int blk_cand;
+    __shared__ int blk_chunk_max;
+    constexpr int kLogUnroll = UNROLL >= 8 ? 3 : UNROLL >= 4 ? 2 : UNROLL >= 2 ? 1 : 0;
+    const int run_shift = a.run_shift < kLogUnroll ? (a.run_shift < 0 ? 0 : a.run_shift) : kLogUnroll;
+    int pushed = 0, chunk_max = 0, chunk_mark = 0;
+    constexpr int kPerLane = 16 / (int)sizeof(KT);
+    constexpr int kRowsPerLoad = kPerLane * kWave;
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = threadIdx.x >> 6;
+    if (threadIdx.x == 0) { blk_cand = 0; blk_chunk_max = 0; }
+    for (int i = threadIdx.x; i < kWideMax; i += kK1Threads) s_mq[i] = 0;
+    long long qnow[kWideQPerLane], qcut[kWideQPerLane];
+    unsigned long long qdm[kWideQPerLane];
+    unsigned qnk[kWideQPerLane], qcnt[kWideQPerLane];
+#pragma unroll
+    for (int k = 0; k < kWideQPerLane; ++k) {
+        const WideQuery w = a.wq[lane * kWideQPerLane + k];
+        qnow[k] = w.now; qcut[k] = w.cutoff; qdm[k] = w.mask; qnk[k] = w.nk; qcnt[k] = 0;
+    }
+    __syncthreads();
+    int* rrow = ring_row[wave];
+    int* rkey = ring_key[wave];
+    unsigned char* qm = &s_qm[wave][0][0];
+    int lhead = 0, lfill = 0, ncand = 0; // wave-uniform
+    const int cap = 1 << a.dshift;
+
+    // evaluate `cnt` queued candidates (cnt <= 64) against every query: candidate j in turn, each lane for its eight queries
+    auto drain = [&](int cnt) {
+        const bool valid = lane < cnt;
+        int row = 0;
+        unsigned key = 0;
+        PayRec pr;
+        pr.start = 0; pr.user = 0; pr.disc = -1;
+        if (valid) {
+            const int slot = (lhead + lane) & (kLiveRing - 1);
+            row = rrow[slot];
+            key = (unsigned)rkey[slot];
+            pr = a.pay[row]; // ONE gather per candidate, shared by all queries
+        }
+        bool sel = false;
+        for (int j = 0; j < cnt; ++j) {
+            const unsigned kj = (unsigned)__builtin_amdgcn_readlane((int)key, j);
+            const int rj = __builtin_amdgcn_readlane(row, j);
+            const int dj = __builtin_amdgcn_readlane(pr.disc, j);
+            const int uj = __builtin_amdgcn_readlane(pr.user, j);
+            const long long sj = readlane_i64(pr.start, j);
+            // a query whose key(now) EQUALS the row's key is decided by the 8-byte `end` (see scan_batch_body)
+            bool amb = false;
+#pragma unroll
+            for (int k = 0; k < kWideQPerLane; ++k) amb = amb || qnk[k] == kj;
+            long long ej = 0;
+            if (__ballot(amb)) ej = a.end[rj];
+            unsigned byte = 0;
+#pragma unroll
+            for (int k = 0; k < kWideQPerLane; ++k) {
+                const bool live = qnk[k] < kj || (qnk[k] == kj && qnow[k] < ej);
+                const bool hit = live && sj >= qcut[k] && ((qdm[k] >> (dj & 63)) & 1ull);
+                byte |= hit ? (1u << k) : 0u;
+            }
+            if ((unsigned)dj >= 64u) byte = 0;
+            if (__ballot(byte != 0)) {
+                if ((unsigned)uj >= (unsigned)a.n_users) {
+                    if (lane == 0) atomicAdd(&a.summary->bad_rows, 1u);
+                    byte = 0;
+                } else {
+#pragma unroll
+                    for (int k = 0; k < kWideQPerLane; ++k) qcnt[k] += (byte >> k) & 1u;
+                    if (lane == j) sel = true;
+                }
+            }
+            qm[j * kWave + lane] = (unsigned char)byte;
+        }
+        __builtin_amdgcn_wave_barrier();
+        if (sel) {
+            const int rank = atomicAdd(&a.counts[hist_index(pr.user, a.n_users)], 1);
+            if (rank < cap) {
+                BktRec rec;
+                rec.start = pr.start;
+                rec.idx = row;
+                rec.pad = 0;
+                const long long slot = ((long long)pr.user << a.dshift) + rank;
+                a.direct[slot] = rec;
+                const uint4* src = reinterpret_cast<const uint4*>(qm + lane * kWave);
+                uint4* dst = reinterpret_cast<uint4*>(a.dmask + slot * kWideWords);
+#pragma unroll
+                for (int i = 0; i < kWave / 16; ++i) dst[i] = src[i];
+            }
+        }
+        __builtin_amdgcn_wave_barrier();
+        ncand += cnt;
+        lhead = (lhead + cnt) & (kLiveRing - 1);
+        lfill -= cnt;
+    };
+    auto push = [&](bool cand, int row, unsigned key) {
+        const unsigned long long b = __ballot(cand);
+        if (b == 0) return false;
+        if (cand) {
+            const int slot = (lhead + lfill + prefix_in_ballot(b)) & (kLiveRing - 1);
+            rrow[slot] = row;
+            rkey[slot] = (int)key;
+        }
+        lfill += __popcll(b);
+        pushed += __popcll(b);
+        __builtin_amdgcn_wave_barrier();
+        if (lfill >= kWave) drain(kWave);
+        __builtin_amdgcn_wave_barrier();
+        return true;
+    };
+
+    // the candidate stream of scan_batch_body: SWAR test against the smallest key(now), chunks dealt round robin
+    typedef unsigned u4_t __attribute__((ext_vector_type(4)));
+    constexpr unsigned kTop = sizeof(KT) == 2 ? 0x80008000u : 0x80808080u;
+    const unsigned mk = a.min_key;
+    const unsigned nkr = sizeof(KT) == 2 ? (mk | (mk << 16)) : mk * 0x01010101u;
+    const long long n_chunks = a.n / kRowsPerLoad;
+    const long long W = (long long)n_scan_blocks * kK1Waves;
+    const long long gw = (long long)bid * kK1Waves + wave;
+    for (long long cb = gw << run_shift; cb < n_chunks; cb += W * UNROLL) {
+        u4_t kv[UNROLL];
+#pragma unroll
+        for (int j = 0; j < UNROLL; ++j) {
+            const long long ch = cb + (((long long)(j >> run_shift) * W) << run_shift) + (j & ((1 << run_shift) - 1));
+            kv[j] = (u4_t){0u, 0u, 0u, 0u};
+            if (ch < n_chunks) kv[j] = stream_load<NT>(reinterpret_cast<const u4_t*>(a.key + ch * kRowsPerLoad + kPerLane * lane));
+        }
+#pragma unroll
+        for (int j = 0; j < UNROLL; ++j) {
+            const long long ch = cb + (((long long)(j >> run_shift) * W) << run_shift) + (j & ((1 << run_shift) - 1));
+            if (ch >= n_chunks) continue;
+            chunk_max = max(chunk_max, pushed - chunk_mark);
+            chunk_mark = pushed;
+            const int r0 = (int)(ch * kRowsPerLoad + kPerLane * lane);
+            const unsigned g0 = ((kv[j].x | kTop) - nkr) & kTop, g1 = ((kv[j].y | kTop) - nkr) & kTop;
+            const unsigned g2 = ((kv[j].z | kTop) - nkr) & kTop, g3 = ((kv[j].w | kTop) - nkr) & kTop;
+            if constexpr (sizeof(KT) == 2) {
+                unsigned long long m = ((unsigned long long)g0 | ((unsigned long long)g1 << 32)) |
+                                       (((unsigned long long)g2 | ((unsigned long long)g3 << 32)) >> 8);
+                for (;;) {
+                    const bool has = m != 0;
+                    const int pbit = __ffsll((long long)m) - 1;
+                    const int q = (pbit >> 4) + ((pbit & 8) ? 0 : 4);
+                    const unsigned w = q < 4 ? (q < 2 ? kv[j].x : kv[j].y) : (q < 6 ? kv[j].z : kv[j].w);
+                    const unsigned kq = (w >> ((q & 1) * 16)) & 0xFFFFu;
+                    if (!push(has, r0 + q, kq)) break;
+                    m &= m - 1;
+                }
+            } else {
+                unsigned m = (g0 >> 7) | (g1 >> 6) | (g2 >> 5) | (g3 >> 4);
+                for (;;) {
+                    const bool has = m != 0;
+                    const int pbit = __ffs((int)m) - 1;
+                    const int w = pbit & 7, b = pbit >> 3;
+                    const unsigned word = w < 2 ? (w == 0 ? kv[j].x : kv[j].y) : (w == 2 ? kv[j].z : kv[j].w);
+                    const unsigned kq = (word >> (8 * b)) & 0xFFu;
+                    if (!push(has, r0 + 4 * w + b, kq)) break;
+                    m &= m - 1;
+                }
+            }
+        }
+    }
+    if (gw == (n_chunks >> run_shift) % W) {
+        for (long long r0 = n_chunks * kRowsPerLoad; r0 < a.n; r0 += kWave) {
+            const long long r = r0 + lane;
+            const unsigned kq = r < a.n ? a.key[r] : 0u;
+            push(r < a.n && kq >= mk, (int)r, kq);
+        }
+    }
+    if (lfill > 0) drain(lfill);
+    if (lane == 0 && ncand) atomicAdd(&blk_cand, ncand);
+    chunk_max = max(chunk_max, pushed - chunk_mark);
+    if (lane == 0 && chunk_max) atomicMax(&blk_chunk_max, chunk_max);
+#pragma unroll
+    for (int k = 0; k < kWideQPerLane; ++k)
+        if (qcnt[k]) atomicAdd(&s_mq[lane * kWideQPerLane + k], qcnt[k]);
+    __syncthreads();
+    for (int i = threadIdx.x; i < kWideMax; i += kK1Threads)
+        if (s_mq[i]) atomicAdd(&a.mq[i], s_mq[i]);
+    if (threadIdx.x == 0) {
+        if (blk_cand) atomicAdd(&a.summary->cand, (unsigned long long)blk_cand);
+        if (blk_chunk_max) atomicMax(&a.summary->chunk_max, (unsigned)blk_chunk_max);
+    }
+}
+
+template <int UNROLL, bool NT, class KT>
+__global__ __launch_bounds__(kK1Threads) void k_scan_wide(WideScanArgs<KT> a)
+{
+    scan_wide_body<UNROLL, NT, KT>(a, (int)blockIdx.x, (int)gridDim.x);
+}
+
+// The union of a wide pass, two launches of 256-user tiles: k_wide_tiles sums each tile's (capped) bucket sizes and flags
+// outgrown buckets; k_wide_order adds up the sums of the tiles in front of its own (no look-back, no tickets), writes uoff and
+// orders each bucket by ranking, one wave per bucket (<= 64 rows), copying `words` mask words per row.
+struct WideTailArgs {
+    int n_users, dshift, words;
+    const int* counts;               // the pass's union histogram
+    long long* tile_sum;             // [tiles]
+    Summary* summary;                // m (Mu), max_count, n_over
+    const BktRec* direct;
+    const unsigned long long* dmask; // kWideWords words per bucket slot
+    long long* uoff;                 // [n_users + 1]
+    int* urows;
+    unsigned long long* umask;       // `words` words per union row
+};
+
+__global__ __launch_bounds__(256) void k_wide_tiles(WideTailArgs t)
+{
+    __shared__ long long s_sum[4];
+    __shared__ unsigned s_max[4];
+    const int U = t.n_users, cap = 1 << t.dshift;
+    const int u = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    const int n_raw = u < U ? t.counts[hist_index(u, U)] : 0;
+    const int nn = n_raw < cap ? n_raw : cap;
+    if (n_raw > cap) atomicAdd(&t.summary->n_over, 1u);
+    long long s = nn;
+    unsigned mx = (unsigned)nn;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        s += __shfl_xor(s, o, kWave);
+        mx = max(mx, (unsigned)__shfl_xor((int)mx, o, kWave));
+    }
+    if ((threadIdx.x & 63) == 0) { s_sum[threadIdx.x >> 6] = s; s_max[threadIdx.x >> 6] = mx; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        t.tile_sum[blockIdx.x] = s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3];
+        const unsigned m = max(max(s_max[0], s_max[1]), max(s_max[2], s_max[3]));
+        if (m) atomicMax(&t.summary->max_count, m);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_wide_order(WideTailArgs t)
+{
+    __shared__ long long lds4[4];
+    __shared__ int s_wsum[4];
+    const int U = t.n_users, cap = 1 << t.dshift;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    long long part = 0;
+    for (int i = threadIdx.x; i < (int)blockIdx.x; i += 256) part += t.tile_sum[i];
+    const long long base = block_sum_256(part, lds4);
+    const int u = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    const bool in_u = u < U;
+    const int n_raw = in_u ? t.counts[hist_index(u, U)] : 0;
+    const int nn = n_raw < cap ? n_raw : cap;
+    const int incl = wave_incl_scan_i32(nn, lane);
+    if (lane == 63) s_wsum[wave] = incl;
+    __syncthreads();
+    long long run = base + incl - nn;
+    for (int w = 0; w < wave; ++w) run += s_wsum[w];
+    if (in_u) {
+        t.uoff[u] = run;
+        if (u == U - 1) {
+            t.uoff[U] = run + nn;
+            t.summary->m = (unsigned long long)(run + nn);
+        }
+    }
+    unsigned long long todo = __ballot(in_u && nn > 0);
+    while (todo) {
+        const int src_lane = __ffsll((long long)todo) - 1;
+        todo &= todo - 1;
+        const int nb = __shfl(nn, src_lane, kWave);
+        const int ub = __shfl(u, src_lane, kWave);
+        const long long rq = __shfl(run, src_lane, kWave);
+        const long long slot = ((long long)ub << t.dshift) + lane;
+        BktRec r;
+        r.start = INT64_MAX;
+        r.idx = INT32_MAX;
+        r.pad = 0;
+        if (lane < nb) r = t.direct[slot];
+        int rank = 0;
+        for (int j = 0; j < nb; ++j) {
+            const long long sj = __shfl(r.start, j, kWave);
+            const int ij = __shfl(r.idx, j, kWave);
+            rank += key_less(sj, ij, r.start, r.idx) ? 1 : 0;
+        }
+        if (lane < nb) {
+            const long long pos = rq + rank;
+            t.urows[pos] = r.idx;
+            for (int w = 0; w < t.words; ++w) t.umask[pos * t.words + w] = t.dmask[slot * kWideWords + w];
+        }
+    }
+}
+
+// query q's counts / offsets / row list out of a wide union (off the hot path: one query per launch; the prefix is k_block_prefix)
+__global__ __launch_bounds__(256) void k_wide_mat_count(int n_users, const long long* __restrict__ uoff, const unsigned long long* __restrict__ umask,
+                                                        int words, int q, int* __restrict__ counts)
+{
+    const int u = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    if (u >= n_users) return;
+    int c = 0;
+    for (long long r = uoff[u]; r < uoff[u + 1]; ++r) c += (int)((umask[r * words + (q >> 6)] >> (q & 63)) & 1ull);
+    counts[u] = c;
+}
+
+__global__ __launch_bounds__(256) void k_wide_mat_write(int n_users, const long long* __restrict__ uoff, const int* __restrict__ urows,
+                                                        const unsigned long long* __restrict__ umask, int words, int q,
+                                                        const long long* __restrict__ offsets, int* __restrict__ idx, long long idx_cap)
+{
+    const int u = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    if (u >= n_users) return;
+    long long o = offsets[u];
+    for (long long r = uoff[u]; r < uoff[u + 1] && o < idx_cap; ++r)
+        if ((umask[r * words + (q >> 6)] >> (q & 63)) & 1ull) idx[o++] = urows[r];
+}
+
+// the wide union message: [uoff[0..u_pad] | Mu | rows[0..cap) | masks[0..cap) as 2 * words int32 words per row]
+__global__ __launch_bounds__(256) void k_wide_pack(int n_users, int u_pad, const long long* __restrict__ uoff, const int* __restrict__ urows,
+                                                   const unsigned long long* __restrict__ umask, int words, long long cap, int* __restrict__ dst)
+{
+    const long long mu = uoff[n_users];
+    const long long k = mu < cap ? mu : cap;
+    const long long head = (long long)u_pad + 2;
+    int* rows = dst + head;
+    int* masks = rows + cap;
+    const int* src = reinterpret_cast<const int*>(umask);
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    const long long i0 = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    for (long long i = i0; i < head; i += stride) dst[i] = i <= n_users ? (int)uoff[i] : (int)mu;
+    for (long long i = i0; i < k; i += stride) rows[i] = urows[i];
+    for (long long i = i0; i < k * 2 * words; i += stride) masks[i] = src[i];
+}
+
 // ------------------------------------------------------------------------------------------------ K3 scatter
 
 // Records of K1 block b (blk_count[b] of them, in that block's private region) -> bucket slot

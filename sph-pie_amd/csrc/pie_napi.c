@@ -54,6 +54,8 @@
     X(int, pie_stats_get, (pie_ctx *, pie_stats *))                                                                 \
     X(int, pie_stats_reset, (pie_ctx *))                                                                            \
     X(int, pie_scan_batch, (pie_ctx *, const pie_query *, int, size_t *))                                           \
+    X(int, pie_scan_wide_begin, (pie_ctx *, const pie_query *, int))                                                \
+    X(int, pie_scan_wide_finish, (pie_ctx *, size_t *, size_t, int *))                                              \
     X(int, pie_batch_read_user_feed, (pie_ctx *, int, int32_t, int32_t *, size_t, size_t *))                        \
     X(int, pie_comm_create, (const int32_t *, int32_t, pie_comm **))                                                \
     X(int, pie_comm_destroy, (pie_comm *))                                                                          \
@@ -1080,6 +1082,52 @@ static napi_value fn_scan_batch(napi_env env, napi_callback_info info)
     return out;
 }
 
+/* scanWide(ctx, nows, cutoffs, masks) -> Array of M per query: ONE wide batch of 1..PIE_WIDE_MAX queries (pie_scan_wide_*),
+ * begun and finished; batchUserFeed / batchFetchRequests then read it for any query index.  The queries and counts live on the
+ * heap, not on the stack. */
+static napi_value fn_scan_wide(napi_env env, napi_callback_info info)
+{
+    ARGS(4)
+    pie_ctx *ctx = get_ctx(env, argv[0]);
+    if (!ctx) return NULL;
+    size_t a = 0, b = 0, c = 0;
+    int64_t *pn = typed(env, argv[1], napi_bigint64_array, &a), *pc = typed(env, argv[2], napi_bigint64_array, &b);
+    uint64_t *pm = typed(env, argv[3], napi_biguint64_array, &c);
+    if (!pn || !pc || !pm || a != b || a != c || a < 1 || a > PIE_WIDE_MAX) {
+        napi_throw_type_error(env, NULL, "scanWide(ctx, BigInt64Array nows, BigInt64Array cutoffs, BigUint64Array masks): 1..512 queries, equal lengths");
+        return NULL;
+    }
+    pie_query *q = (pie_query *)malloc(a * sizeof(pie_query));
+    size_t *m = (size_t *)malloc(a * sizeof(size_t));
+    if (!q || !m) {
+        free(q);
+        free(m);
+        napi_throw_error(env, NULL, "scanWide: out of host memory");
+        return NULL;
+    }
+    for (size_t k = 0; k < a; ++k) {
+        q[k].now = pn[k];
+        q[k].cutoff = pc[k];
+        q[k].mask = pm[k];
+    }
+    int n_q = 0;
+    int rc = p_pie_scan_wide_begin(ctx, q, (int)a);
+    if (rc == 0) rc = p_pie_scan_wide_finish(ctx, m, a, &n_q);
+    free(q);
+    if (rc) {
+        free(m);
+        return throw_pie(env, ctx, rc);
+    }
+    napi_value out;
+    if (napi_create_array_with_length(env, (size_t)n_q, &out) != napi_ok) {
+        free(m);
+        return NULL;
+    }
+    for (int k = 0; k < n_q; ++k) napi_set_element(env, out, (uint32_t)k, js_int(env, (int64_t)m[k]));
+    free(m);
+    return out;
+}
+
 /* batchUserFeed(ctx, qi, user, idx Int32Array) -> k */
 static napi_value fn_batch_user_feed(napi_env env, napi_callback_info info)
 {
@@ -1628,7 +1676,7 @@ static napi_value init(napi_env env, napi_value exports)
         {"setDisciplines", fn_set_disc}, {"scan", fn_scan}, {"scanDevice", fn_scan_device}, {"userFeed", fn_user_feed}, {"scanAsync", fn_scan_async}, {"fetchRows", fn_fetch_rows},
         {"expiredQueue", fn_expired_queue}, {"archiveQueue", fn_archive_queue}, {"serializeEvents", fn_serialize_events}, {"serializeICal", fn_serialize_ical}, {"stats", fn_stats}, {"setProfiling", fn_set_profiling},
         {"setOrderedRun", fn_set_ordered_run}, {"setBatchLanes", fn_set_batch_lanes},
-        {"serializeCsv", fn_serialize_csv}, {"scanBatch", fn_scan_batch}, {"batchUserFeed", fn_batch_user_feed}, {"batchFetchRequests", fn_batch_fetch_requests},
+        {"serializeCsv", fn_serialize_csv}, {"scanBatch", fn_scan_batch}, {"scanWide", fn_scan_wide}, {"batchUserFeed", fn_batch_user_feed}, {"batchFetchRequests", fn_batch_fetch_requests},
         {"commCreate", fn_comm_create}, {"commDestroy", fn_comm_destroy}, {"commWorld", fn_comm_world}, {"commCtx", fn_comm_ctx},
         {"commGenSyntheticSharded", fn_comm_gen}, {"commScanBatchGather", fn_comm_scan_gather}, {"commReadGathered", fn_comm_read}, {"commUPad", fn_comm_upad},
         {"commNeededCap", fn_comm_needed_cap}, {"commStepReserve", fn_comm_step_reserve}, {"commStepBegin", fn_comm_step_begin},

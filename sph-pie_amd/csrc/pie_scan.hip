@@ -34,6 +34,7 @@
 #include <algorithm>
 #include <cstring>
 #include <ctime>
+#include <sched.h>
 #include <string>
 #include <vector>
 
@@ -108,6 +109,25 @@ struct Slot {
 constexpr int kBatchSlots = 3;
 constexpr int kLaneMax = 4;     // batch lanes of a context (pie_set_batch_lanes): independent streams, kBatchSlots batches in flight on each
 
+// what a batch slot needs for a WIDE batch (pie_kernels.h "wide batches"), allocated the first time the slot runs one
+struct WideSlot {
+    int dshift = -1;                        // the bucket capacity the arrays below were sized for
+    unsigned long long* dmask = nullptr;    // bucket-slot masks: kWideWords words per slot
+    unsigned long long* umask = nullptr;    // union masks: `words` words per union row, for up to (cap_users << dshift) rows
+    int umask_words = 0;                    // mask words per row umask was sized for
+    WideQuery* d_wq = nullptr;              // the batch's queries as the lanes hold them
+    WideQuery* h_wq = nullptr;              // pinned staging of d_wq
+    Summary* h_sum = nullptr;               // pinned: the pass's summary, then kWideMax per-query totals
+    hipEvent_t done = nullptr;              // the summary has landed
+    int words = 0;
+    std::vector<pie_query> q;
+    std::vector<unsigned char> fallback;
+    std::vector<unsigned long long> m;      // selected rows per query
+    // per-query lists: the fallback queries' (built at finish) and the ones somebody asked for (not every query of the batch)
+    struct List { int* counts = nullptr; long long* offsets = nullptr; int* idx = nullptr; long long idx_cap = 0; bool ok = false; };
+    std::vector<List> lists;
+};
+
 // everything one batch of queries owns (see pie_kernels.h "batched scan").  The primary result of a batch on the general pass
 // is the UNION (uoff / urows / umlo / umhi); per-query lists are materialised from it on request, or produced directly by the
 // paths that work per query (fallback scans on the general path, a batch on the ordered run).
@@ -154,6 +174,8 @@ struct BatchSlot {
     int lane = 0;                      // the lane (stream) the batch ran on
     hipStream_t stream = nullptr;
     bool main_ordered = true;          // the context's main stream is ordered behind the batch's kernels (see order_after_batch)
+    bool wide = false;                 // a wide batch (pie_scan_wide_begin): its queries and results live in *w, not above
+    WideSlot* w = nullptr;
 };
 
 // the ordered run of the resident table (pie_ordered.h)
@@ -481,6 +503,16 @@ void free_batch(pie_ctx* c)
         for (int q = 0; q < kBatchMax; ++q) { dfree(b.over_idx[q]); b.over_cap[q] = 0; b.idx_of[q] = nullptr; b.list_ok[q] = false; }
         b.in_flight = b.k2_pending = b.have_result = b.union_ok = b.union_part = false;
         b.n_q = 0;
+        b.wide = false;
+        if (WideSlot* w = b.w) {
+            dfree(w->dmask); dfree(w->umask); dfree(w->d_wq);
+            if (w->h_wq) (void)hipHostFree(w->h_wq);
+            if (w->h_sum) (void)hipHostFree(w->h_sum);
+            if (w->done) (void)hipEventDestroy(w->done);
+            for (WideSlot::List& l : w->lists) { dfree(l.counts); dfree(l.offsets); dfree(l.idx); }
+            delete w;
+            b.w = nullptr;
+        }
     }
     for (char*& sp : c->bspan) dfree(sp);
     dfree(c->d_mat_tile); dfree(c->d_mat_qmax);
@@ -2293,6 +2325,7 @@ int batch_begin(pie_ctx* c, const pie_query* qs, int n_q, int msg_kind, int* msg
     hipStream_t s = lane_stream_of(c, lane);
     b.lane = lane;
     b.n_q = n_q;
+    b.wide = false;
     b.have_result = false;
     b.union_ok = b.union_part = false;
     b.mu = 0;
@@ -2581,6 +2614,7 @@ int batch_finish(pie_ctx* c, int* ready_out)
     if (ready_out) *ready_out = 0;
     BatchSlot* bp = oldest_batch(c);
     if (!bp) return fail(c, PIE_E_STATE, "pie_scan_batch_finish without pie_scan_batch_begin");
+    if (bp->wide) return fail(c, PIE_E_STATE, "the oldest batch in flight is wide: finish it with pie_scan_wide_finish");
     BatchSlot& b = *bp;
     hipStream_t s = b.stream ? b.stream : c->stream; // the lane the batch runs on
     bool all_ready = true;
@@ -2754,6 +2788,382 @@ int batch_pack_union(pie_ctx* c, BatchSlot& b, void* dst_i32, size_t u_pad, size
     hipLaunchKernelGGL(k_union_write, dim3(wblocks), dim3(256), 0, s, c->n_users, (int)u_pad, c->d_union_local, gbase, c->d_union_cnt, c->d_union, over,
                        (long long)cap, (int*)dst_i32);
     PIE_HIP(c, hipGetLastError());
+    return PIE_OK;
+}
+
+
+// ---- wide batches (pie_scan_wide_begin; pie_kernels.h "wide batches").  A wide batch takes a slot of a lane like any batch and
+// shares the FIFO; its pass and its union tail (two small launches) are queued at begin — no tail rides in a later launch — and
+// the summary with the per-query totals is copied to pinned host memory behind them.  Queries that fall back run on the general
+// path at finish for their counts only; their lists are produced again when somebody asks for them, so list storage grows with
+// the queries asked for, not with the batch.
+
+// the wide pass's device arrays of a slot: bucket-slot masks (kWideWords words per slot) and union masks (`words` words per
+// union row; a union row holds a bucket slot, so (cap_users << dshift) rows bound it)
+size_t wide_slot_bytes(const pie_ctx* c) { return ((size_t)c->cap_users << c->bdshift) * kWideWords * 8; }
+
+int ensure_wide(pie_ctx* c, BatchSlot& b)
+{
+    WideSlot& w = *b.w;
+    if (!w.done) PIE_HIP(c, hipEventCreateWithFlags(&w.done, hipEventDisableTiming));
+    if (!w.h_sum) PIE_HIP(c, hipHostMalloc(&w.h_sum, (size_t)kSummaryBytes + (size_t)kWideMax * 4, hipHostMallocDefault));
+    if (!w.h_wq) PIE_HIP(c, hipHostMalloc(&w.h_wq, (size_t)kWideMax * sizeof(WideQuery), hipHostMallocDefault));
+    if (!w.d_wq) PIE_HIP(c, hipMalloc(&w.d_wq, (size_t)kWideMax * sizeof(WideQuery)));
+    const size_t slots = (size_t)c->cap_users << c->bdshift;
+    if (w.dshift != c->bdshift || !w.dmask) {
+        dfree(w.dmask); dfree(w.umask);
+        w.umask_words = 0;
+        PIE_HIP(c, hipMalloc(&w.dmask, slots * kWideWords * 8));
+        w.dshift = c->bdshift;
+    }
+    if (w.umask_words < w.words) {
+        dfree(w.umask);
+        w.umask_words = 0;
+        PIE_HIP(c, hipMalloc(&w.umask, slots * (size_t)w.words * 8));
+        w.umask_words = w.words;
+    }
+    return PIE_OK;
+}
+
+int wide_begin(pie_ctx* c, const pie_query* qs, int n_q)
+{
+    queue_forget(c);
+    if (c->cap_rows == 0) return fail(c, PIE_E_STATE, "no table loaded");
+    if (!qs || n_q < 1 || n_q > kWideMax) return fail(c, PIE_E_INVAL, "a wide batch holds 1..%d queries (got %d)", kWideMax, n_q);
+    if (c->n_flight) return fail(c, PIE_E_STATE, "a single scan is in flight: finish it before beginning a batch");
+    if (c->key_rebuild && c->b_flight == 0) {
+        int rc = build_keys(c, 0, true);
+        if (rc) return rc;
+    }
+    // a table whose batches take the ordered run, or that cannot run the batched pass: every query falls back
+    const bool ord_table = batch_supported(c) && ordered_batch_wanted(c) && !c->ord_lists_only;
+    bool unsupported = ord_table || !batch_supported(c) || c->key_poor || c->batch_poor;
+    std::vector<unsigned char> dense((size_t)n_q, 0);
+    int n_batched = 0;
+    bool fine = (c->k1_keyed & 0x800) && !c->fkey_poor;
+    if (!unsupported) {
+        const bool hist_ok = !c->key_dirty && c->key_hist_rows == c->n;
+        for (int q = 0; q < n_q; ++q) {
+            dense[q] = hist_ok && (double)rows_keyed_at_or_above(c, qs[q].now) >= kLiveFirstBelow * (double)c->n;
+            if (!dense[q]) {
+                ++n_batched;
+                if (qs[q].now < c->fkey_base) fine = false;
+            }
+        }
+        if (n_batched == 0) unsupported = true;
+    }
+    int lane = 0;
+    {
+        const int lanes = ord_table ? 1 : c->n_lanes;
+        int tried = 0;
+        lane = lanes > 1 ? c->lane_rr % lanes : 0;
+        while (tried < lanes && c->lane_flight[lane] >= kBatchSlots) { lane = (lane + 1) % lanes; ++tried; }
+        if (tried == lanes)
+            return fail(c, PIE_E_STATE, "%d batches are already in flight (%d per lane, %d lane%s): finish one first", c->b_flight, kBatchSlots,
+                        lanes, lanes > 1 ? "s" : "");
+        if (lanes > 1) c->lane_rr = (lane + 1) % lanes;
+    }
+    if (!unsupported && c->bdshift_want > c->bdshift && c->b_flight == 0 && any_lane_alloc(c)) {
+        // larger union buckets (as batch_begin): every slot's arrays are replaced
+        int rc0 = sync_all(c);
+        if (rc0) return rc0;
+        const size_t slots = (size_t)c->cap_users << c->bdshift_want;
+        if (slots * sizeof(BktRec) <= kDirectMaxBytes) {
+            c->bdshift = c->bdshift_want;
+            for (BatchSlot& x : c->bslot) {
+                dfree(x.direct); dfree(x.direct_hi); dfree(x.uoff); dfree(x.urows); dfree(x.umlo); dfree(x.umhi);
+                x.have_result = false;
+            }
+            for (char*& sp : c->bspan) dfree(sp);
+            c->bres = nullptr;
+            for (bool& a : c->lane_alloc) a = false;
+        } else {
+            c->bdshift_want = c->bdshift;
+        }
+    }
+    // the bucket-slot masks are four times the bucket records: the same bound as the direct slots
+    if (!unsupported && wide_slot_bytes(c) > kDirectMaxBytes) unsupported = true;
+    BatchSlot* const lane_slots = c->bslot + lane * kBatchSlots;
+    BatchSlot& b = lane_slots[c->lane_next[lane]];
+    hipStream_t s = lane_stream_of(c, lane);
+    if (!b.w) b.w = new WideSlot();
+    WideSlot& w = *b.w;
+    w.words = (n_q + 63) / 64;
+    int rc = unsupported ? PIE_OK : ensure_batch(c, lane);
+    if (rc) return rc;
+    if (!unsupported) {
+        rc = ensure_wide(c, b);
+        if (rc) return rc;
+    }
+    b.lane = lane;
+    b.n_q = n_q;
+    b.wide = true;
+    b.have_result = false;
+    b.union_ok = b.union_part = false;
+    b.mu = 0;
+    if (c->bres == &b) c->bres = nullptr;
+    b.msg_kind = 0; b.msg = nullptr; b.msg_counts = nullptr;
+    b.ev_index = -1;
+    b.ordered = false;
+    b.unsupported = unsupported;
+    b.stream = s;
+    b.k2_pending = false;
+    w.q.assign(qs, qs + n_q);
+    w.fallback.assign((size_t)n_q, 0);
+    w.m.assign((size_t)n_q, 0);
+    if ((int)w.lists.size() < n_q) w.lists.resize((size_t)n_q);
+    for (WideSlot::List& l : w.lists) l.ok = false;
+    for (int q = 0; q < n_q; ++q) w.fallback[q] = unsupported ? 1 : dense[q];
+    if (unsupported) { // finish runs every query on the general path
+        b.main_ordered = true;
+        b.in_flight = true;
+        batch_begun(c, lane);
+        return PIE_OK;
+    }
+    b.main_ordered = lane == 0;
+    if (lane > 0 && c->lane_epoch[lane] != c->idle_epoch) { // see idle_epoch
+        PIE_HIP(c, hipEventRecord(c->lane_event[lane][0], c->stream));
+        PIE_HIP(c, hipStreamWaitEvent(s, c->lane_event[lane][0], 0));
+        c->lane_epoch[lane] = c->idle_epoch;
+    }
+    b.fine_key = fine;
+    b.dshift = c->bdshift;
+    char** const lane_spans = c->bspan + lane * 3;
+    b.span = lane_spans[c->lane_span_next[lane]];
+    c->lane_span_next[lane] = (c->lane_span_next[lane] + 1) % 3;
+    b.zero_span = lane_spans[(c->lane_span_next[lane] + 1) % 3];
+    b.seq = ++c->bseq_counter;
+    b.k1_blocks = c->plan_blocks[fine ? 3 : 2];
+    c->scans_begun++;
+    // the batch begun just before this one on this lane has its tail queued first (tails run in the order of their batches)
+    BatchSlot& other = lane_slots[(c->lane_next[lane] + kBatchSlots - 1) % kBatchSlots];
+    if (c->lane_flight[lane] >= 1 && other.in_flight && other.k2_pending && !other.ordered) launch_batch_k2(c, other, s);
+    // the queries as the lanes hold them: a query that falls back has mask 0 and selects nothing here
+    const unsigned long long table = c->n_disc >= 64 ? ~0ull : ((1ull << c->n_disc) - 1ull);
+    unsigned mk = fine ? 0xFFu : 0xFFFFu;
+    for (int i = 0; i < kWideMax; ++i) {
+        WideQuery& x = w.h_wq[i];
+        x.pad = 0;
+        if (i < n_q && !w.fallback[i]) {
+            x.now = qs[i].now;
+            x.cutoff = qs[i].cutoff;
+            x.mask = qs[i].mask & table;
+            x.nk = fine ? host_fine_key_of(c, qs[i].now) : host_key_of(c, qs[i].now);
+            if (x.nk < mk) mk = x.nk;
+        } else {
+            x.now = INT64_MAX;
+            x.cutoff = INT64_MAX;
+            x.mask = 0;
+            x.nk = ~0u;
+        }
+    }
+    PIE_HIP(c, hipMemcpyAsync(w.d_wq, w.h_wq, (size_t)kWideMax * sizeof(WideQuery), hipMemcpyHostToDevice, s));
+    char* const sp = b.span;
+    Summary* const sum = reinterpret_cast<Summary*>(sp + span_counts_bytes(c) + span_tiles_bytes(c) + span_parts_bytes() + 128);
+    unsigned* const mq = reinterpret_cast<unsigned*>(sp + counts_span(c));
+#define PIE_WIDE(KT, KEYPTR)                                                                                            \
+    do {                                                                                                                \
+        WideScanArgs<KT> a;                                                                                             \
+        a.pay = c->d_pay; a.end = c->d_end; a.key = KEYPTR; a.n = c->n; a.n_users = c->n_users;                         \
+        a.dshift = c->bdshift; a.run_shift = c->run_shift; a.min_key = mk;                                              \
+        a.counts = reinterpret_cast<int*>(sp); a.summary = sum; a.direct = b.direct; a.dmask = w.dmask; a.mq = mq;      \
+        a.wq = w.d_wq;                                                                                                  \
+        hipLaunchKernelGGL((k_scan_wide<8, true, KT>), dim3((unsigned)b.k1_blocks), dim3(kK1Threads), 0, s, a);       \
+    } while (0)
+    if (fine) PIE_WIDE(fkey_t, c->d_fkey);
+    else PIE_WIDE(lkey_t, c->d_key);
+#undef PIE_WIDE
+    WideTailArgs t;
+    t.n_users = c->n_users;
+    t.dshift = c->bdshift;
+    t.words = w.words;
+    t.counts = reinterpret_cast<const int*>(sp);
+    t.tile_sum = reinterpret_cast<long long*>(sp + span_counts_bytes(c));
+    t.summary = sum;
+    t.direct = b.direct;
+    t.dmask = w.dmask;
+    t.uoff = b.uoff;
+    t.urows = b.urows;
+    t.umask = w.umask;
+    const unsigned tiles = (unsigned)((c->n_users + 255) / 256);
+    hipLaunchKernelGGL(k_wide_tiles, dim3(tiles), dim3(256), 0, s, t);
+    hipLaunchKernelGGL(k_wide_order, dim3(tiles), dim3(256), 0, s, t);
+    PIE_HIP(c, hipGetLastError());
+    PIE_HIP(c, hipMemcpyAsync(w.h_sum, sum, sizeof(Summary), hipMemcpyDeviceToHost, s));
+    PIE_HIP(c, hipMemcpyAsync(reinterpret_cast<char*>(w.h_sum) + kSummaryBytes, mq, (size_t)n_q * 4, hipMemcpyDeviceToHost, s));
+    PIE_HIP(c, hipEventRecord(w.done, s));
+    // the span of the batch before this one on the lane (done in stream order) is zeroed for the batch after the next
+    PIE_HIP(c, hipMemsetAsync(b.zero_span, 0, batch_span_bytes(c), s));
+    b.in_flight = true;
+    batch_begun(c, lane);
+    return PIE_OK;
+}
+
+// query q's lists of a wide batch in its per-query storage (idx sized for m rows)
+int wide_list_alloc(pie_ctx* c, WideSlot& w, int q, long long m)
+{
+    WideSlot::List& l = w.lists[q];
+    if (!l.counts) PIE_HIP(c, hipMalloc(&l.counts, ((size_t)c->cap_users + 1) * 4));
+    if (!l.offsets) PIE_HIP(c, hipMalloc(&l.offsets, ((size_t)c->cap_users + 1) * 8));
+    if (!l.idx || l.idx_cap < m) {
+        PIE_HIP(c, hipStreamSynchronize(c->stream)); // an earlier copy may still read the old buffer
+        dfree(l.idx);
+        l.idx_cap = 0;
+        PIE_HIP(c, hipMalloc(&l.idx, (size_t)(m > 0 ? m : 1) * 4));
+        l.idx_cap = m > 0 ? m : 1;
+    }
+    return PIE_OK;
+}
+
+// the listed queries of a wide batch on the general path, two scans in flight (as batch_fallback_many): their counts, and with
+// `keep` their lists too
+int wide_rerun(pie_ctx* c, BatchSlot& b, const int* list, int n_list, bool keep, unsigned* bad_out)
+{
+    if (n_list == 0) return PIE_OK;
+    WideSlot& w = *b.w;
+    const unsigned long long keep_mask = c->disc_mask;
+    auto begin = [&](int q) {
+        c->disc_mask = w.q[q].mask;
+        return scan_begin(c, w.q[q].now, w.q[q].cutoff);
+    };
+    int rc = begin(list[0]);
+    for (int i = 0; i < n_list && rc == PIE_OK; ++i) {
+        if (i + 1 < n_list) rc = begin(list[i + 1]);
+        if (rc == PIE_OK) rc = scan_finish(c);
+        if (rc != PIE_OK) break;
+        const int q = list[i];
+        Slot& sl = *c->res;
+        const long long m = (long long)sl.last.m;
+        w.m[q] = (unsigned long long)m;
+        if (bad_out && sl.last.bad_rows > *bad_out) *bad_out = sl.last.bad_rows;
+        if (keep) {
+            rc = wide_list_alloc(c, w, q, m);
+            if (rc) break;
+            WideSlot::List& l = w.lists[q];
+            hipStream_t s = c->stream;
+            PIE_HIP(c, hipMemcpyAsync(l.counts, sl.counts_ord, (size_t)c->n_users * 4, hipMemcpyDeviceToDevice, s));
+            PIE_HIP(c, hipMemcpyAsync(l.offsets, sl.offsets, ((size_t)c->n_users + 1) * 8, hipMemcpyDeviceToDevice, s));
+            if (m) PIE_HIP(c, hipMemcpyAsync(l.idx, sl.out_idx, (size_t)m * 4, hipMemcpyDeviceToDevice, s));
+            l.ok = true;
+        }
+    }
+    c->disc_mask = keep_mask;
+    if (rc != PIE_OK) {
+        while (c->n_flight) (void)scan_finish(c);
+        return rc;
+    }
+    PIE_HIP(c, hipStreamSynchronize(c->stream));
+    for (Slot& sl : c->slot) sl.have_result = false;
+    c->res = nullptr;
+    return PIE_OK;
+}
+
+// query q's counts / offsets / row list of the last finished (wide) batch, produced on first use
+int wide_need_list(pie_ctx* c, BatchSlot& b, int q)
+{
+    WideSlot& w = *b.w;
+    if (w.lists[q].ok) return PIE_OK;
+    if (w.fallback[q] || !b.union_part) return fail(c, PIE_E_STATE, "query %d of the wide batch has no list", q); // built at finish
+    int rc = wide_list_alloc(c, w, q, (long long)w.m[q]);
+    if (rc) return rc;
+    WideSlot::List& l = w.lists[q];
+    hipStream_t s = c->stream;
+    const unsigned tiles = (unsigned)((c->n_users + 255) / 256);
+    hipLaunchKernelGGL(k_wide_mat_count, dim3(tiles ? tiles : 1u), dim3(256), 0, s, c->n_users, (const long long*)b.uoff,
+                       (const unsigned long long*)w.umask, w.words, q, l.counts);
+    hipLaunchKernelGGL(k_block_prefix, dim3(1), dim3(256), 0, s, (const int*)l.counts, c->n_users, l.offsets, (unsigned long long*)nullptr);
+    hipLaunchKernelGGL(k_wide_mat_write, dim3(tiles ? tiles : 1u), dim3(256), 0, s, c->n_users, (const long long*)b.uoff, (const int*)b.urows,
+                       (const unsigned long long*)w.umask, w.words, q, (const long long*)l.offsets, l.idx, l.idx_cap);
+    PIE_HIP(c, hipGetLastError());
+    PIE_HIP(c, hipStreamSynchronize(s));
+    l.ok = true;
+    return PIE_OK;
+}
+
+int wide_finish(pie_ctx* c, size_t* m_out, size_t m_cap, int* n_q_out)
+{
+    BatchSlot* bp = oldest_batch(c);
+    if (!bp) return fail(c, PIE_E_STATE, "pie_scan_wide_finish without a batch in flight");
+    if (n_q_out) *n_q_out = bp->n_q;
+    if (m_out && m_cap < (size_t)bp->n_q) return fail(c, PIE_E_CAPACITY, "m_cap %zu < %d queries", m_cap, bp->n_q);
+    if (!bp->wide) { // an ordinary batch is the oldest: finished as pie_scan_batch_finish does
+        int rc = batch_finish(c, nullptr);
+        if (rc) return rc;
+        if (m_out)
+            for (int q = 0; q < c->bres->n_q; ++q) m_out[q] = (size_t)c->bres->last[q].m;
+        return PIE_OK;
+    }
+    BatchSlot& b = *bp;
+    WideSlot& w = *b.w;
+    if (!b.unsupported) {
+        // wait for the summary's copy, bounded like batch_finish's wait (PIE_WAIT_DEADLINE_MS)
+        timespec t0{};
+        clock_gettime(CLOCK_MONOTONIC, &t0);
+        for (unsigned long long spins = 0;; ++spins) {
+            const hipError_t e = hipEventQuery(w.done);
+            if (e == hipSuccess) break;
+            timespec t1{};
+            clock_gettime(CLOCK_MONOTONIC, &t1);
+            const double waited_ms = (double)(t1.tv_sec - t0.tv_sec) * 1e3 + (double)(t1.tv_nsec - t0.tv_nsec) * 1e-6;
+            if (e != hipErrorNotReady || waited_ms > c->wait_deadline_ms) {
+                batch_left(c, b);
+                if (e != hipErrorNotReady) return fail(c, PIE_E_HIP, "wide batch failed: %s", hipGetErrorString(e));
+                return fail(c, PIE_E_HIP, "wide batch not finished within %.0f ms (PIE_WAIT_DEADLINE_MS): kernel hung?", waited_ms);
+            }
+            if (spins > 64) sched_yield();
+            else __builtin_ia32_pause();
+        }
+        const Summary us = *w.h_sum;
+        const unsigned* mq = reinterpret_cast<const unsigned*>(reinterpret_cast<const char*>(w.h_sum) + kSummaryBytes);
+        b.mu = us.m;
+        // a bucket outgrew its slots or a selected row has a bad user id: every query is rerun on the general path
+        const bool overflow = us.n_over > 0 || us.bad_rows > 0;
+        for (int q = 0; q < b.n_q; ++q) {
+            w.m[q] = mq[q];
+            if (overflow) w.fallback[q] = 1;
+        }
+        if (us.n_over > 0) {
+            if (c->bdshift < kUnionShiftMax) c->bdshift_want = c->bdshift + 1;
+            else c->batch_poor = true;
+        }
+        b.last[0] = us; // the pass's statistics (pie_stats_get)
+        b.union_part = !overflow;
+        b.union_ok = !overflow;
+        for (int q = 0; q < b.n_q; ++q) b.union_ok = b.union_ok && !w.fallback[q];
+        choose_run_shift(c, us.cand, us.chunk_max, b.fine_key);
+    }
+    batch_left(c, b);
+    unsigned bad = 0;
+    {
+        std::vector<int> list;
+        for (int q = 0; q < b.n_q; ++q)
+            if (w.fallback[q]) list.push_back(q);
+        if (!list.empty()) {
+            int rc = order_after_batch(c, b);
+            if (rc) return rc;
+            // their lists are built now, as batch_fallback_many does: a snapshot of the table as the batch saw it
+            rc = wide_rerun(c, b, list.data(), (int)list.size(), true, &bad);
+            if (rc) return rc;
+        }
+    }
+    b.have_result = true;
+    c->bres = &b;
+    c->last_was_batch = true;
+    if (bad) return fail(c, PIE_E_INVAL, "%u selected rows carry a user id outside [0, %d)", bad, c->n_users);
+    if (m_out)
+        for (int q = 0; q < b.n_q; ++q) m_out[q] = (size_t)w.m[q];
+    return PIE_OK;
+}
+
+// the last finished batch, when it is wide and kept its union
+int wide_union_of(pie_ctx* c, BatchSlot** out)
+{
+    if (!c->bres || !c->bres->have_result) return fail(c, PIE_E_STATE, "no batch result on this context");
+    if (!c->bres->wide) return fail(c, PIE_E_STATE, "the last finished batch is not wide: use the batch union readers");
+    if (int rc_o = order_after_batch(c, *c->bres)) return rc_o;
+    if (!c->bres->union_ok)
+        return fail(c, PIE_E_STATE, "this wide batch has no union result (queries fell back to the general path): read the per-query results");
+    *out = c->bres;
     return PIE_OK;
 }
 
@@ -3466,6 +3876,77 @@ int pie_scan_batch(pie_ctx* c, const pie_query* queries, int n_q, size_t* m_out)
     return pie_scan_batch_finish(c, m_out);
 }
 
+int pie_scan_wide_begin(pie_ctx* c, const pie_query* queries, int n_q)
+{
+    if (!c) return PIE_E_INVAL;
+    PIE_HIP(c, hipSetDevice(c->device));
+    return wide_begin(c, queries, n_q);
+}
+
+int pie_scan_wide_finish(pie_ctx* c, size_t* m_out, size_t m_cap, int* n_q_out)
+{
+    if (!c) return PIE_E_INVAL;
+    if (n_q_out) *n_q_out = 0;
+    PIE_HIP(c, hipSetDevice(c->device));
+    return wide_finish(c, m_out, m_cap, n_q_out);
+}
+
+int pie_batch_union_wide_device_ptrs(pie_ctx* c, void** uoff_dev, void** rows_dev, void** masks_dev, int* words_out, size_t* mu_out)
+{
+    if (!c) return PIE_E_INVAL;
+    if (uoff_dev) *uoff_dev = nullptr;
+    if (rows_dev) *rows_dev = nullptr;
+    if (masks_dev) *masks_dev = nullptr;
+    if (words_out) *words_out = 0;
+    if (mu_out) *mu_out = 0;
+    BatchSlot* b = nullptr;
+    if (int rc = wide_union_of(c, &b)) return rc;
+    if (uoff_dev) *uoff_dev = b->uoff;
+    if (rows_dev) *rows_dev = b->urows;
+    if (masks_dev) *masks_dev = b->w->umask;
+    if (words_out) *words_out = b->w->words;
+    if (mu_out) *mu_out = (size_t)b->mu;
+    return PIE_OK;
+}
+
+int pie_batch_read_union_wide(pie_ctx* c, int64_t* uoff_out, int32_t* rows_out, uint64_t* masks_out, size_t cap, int* words_out, size_t* mu_out)
+{
+    if (!c) return PIE_E_INVAL;
+    if (mu_out) *mu_out = 0;
+    if (words_out) *words_out = 0;
+    PIE_HIP(c, hipSetDevice(c->device));
+    BatchSlot* b = nullptr;
+    if (int rc = wide_union_of(c, &b)) return rc;
+    hipStream_t a = c->stream;
+    const size_t mu = (size_t)b->mu, words = (size_t)b->w->words;
+    if (mu_out) *mu_out = mu;
+    if (words_out) *words_out = (int)words;
+    if ((rows_out || masks_out) && mu > cap) return fail(c, PIE_E_CAPACITY, "cap %zu < union rows %zu", cap, mu);
+    if (uoff_out) PIE_HIP(c, hipMemcpyAsync(uoff_out, b->uoff, ((size_t)c->n_users + 1) * 8, hipMemcpyDeviceToHost, a));
+    if (rows_out && mu) PIE_HIP(c, hipMemcpyAsync(rows_out, b->urows, mu * 4, hipMemcpyDeviceToHost, a));
+    if (masks_out && mu) PIE_HIP(c, hipMemcpyAsync(masks_out, b->w->umask, mu * words * 8, hipMemcpyDeviceToHost, a));
+    PIE_HIP(c, hipStreamSynchronize(a));
+    return PIE_OK;
+}
+
+int pie_batch_pack_union_wide_device(pie_ctx* c, void* dst_i32, size_t u_pad, size_t cap)
+{
+    if (!c) return PIE_E_INVAL;
+    if (!dst_i32 || u_pad < (size_t)c->n_users || u_pad > 0x7FFFFFF0u) return fail(c, PIE_E_INVAL, "bad union destination / u_pad < n_users");
+    PIE_HIP(c, hipSetDevice(c->device));
+    BatchSlot* b = nullptr;
+    if (int rc = wide_union_of(c, &b)) return rc;
+    const size_t words = (size_t)b->w->words;
+    const size_t k = (size_t)b->mu < cap ? (size_t)b->mu : cap;
+    const size_t total = u_pad + 2 + k * (1 + 2 * words);
+    size_t grid = (total + 255) / 256;
+    if (grid > (size_t)c->n_cus * 8) grid = (size_t)c->n_cus * 8;
+    hipLaunchKernelGGL(k_wide_pack, dim3((unsigned)(grid ? grid : 1)), dim3(256), 0, c->stream, c->n_users, (int)u_pad, (const long long*)b->uoff,
+                       (const int*)b->urows, (const unsigned long long*)b->w->umask, (int)words, (long long)cap, (int*)dst_i32);
+    PIE_HIP(c, hipGetLastError());
+    return PIE_OK;
+}
+
 int pie_batch_union_device_ptrs(pie_ctx* c, void** uoff_dev, void** rows_dev, void** mask_lo_dev, void** mask_hi_dev, size_t* mu_out)
 {
     if (!c) return PIE_E_INVAL;
@@ -3475,6 +3956,7 @@ int pie_batch_union_device_ptrs(pie_ctx* c, void** uoff_dev, void** rows_dev, vo
     if (mask_hi_dev) *mask_hi_dev = nullptr;
     if (mu_out) *mu_out = 0;
     if (!c->bres || !c->bres->have_result) return fail(c, PIE_E_STATE, "no batch result on this context");
+    if (c->bres->wide) return fail(c, PIE_E_STATE, "the last batch is wide: use pie_batch_union_wide_device_ptrs");
     if (int rc_o = order_after_batch(c, *c->bres)) return rc_o; // the batch may have run on another lane's stream
     const BatchSlot& b = *c->bres;
     if (!b.union_ok) return PIE_OK; // queries fell back / the batch ran on the ordered run: per-query lists only
@@ -3491,6 +3973,7 @@ int pie_batch_read_union(pie_ctx* c, int64_t* uoff_out, int32_t* rows_out, uint6
     if (!c) return PIE_E_INVAL;
     if (mu_out) *mu_out = 0;
     if (!c->bres || !c->bres->have_result) return fail(c, PIE_E_STATE, "no batch result on this context");
+    if (c->bres->wide) return fail(c, PIE_E_STATE, "the last batch is wide: use pie_batch_read_union_wide");
     if (int rc_o = order_after_batch(c, *c->bres)) return rc_o; // the batch may have run on another lane's stream
     const BatchSlot& b = *c->bres;
     if (!b.union_ok) return fail(c, PIE_E_STATE, "this batch has no union result (queries fell back to the general path, or it ran on the ordered run): read the per-query results");
@@ -3526,6 +4009,15 @@ int pie_batch_result_device_ptrs(pie_ctx* c, int qi, void** counts_dev, void** o
     if (int rc_o = order_after_batch(c, *c->bres)) return rc_o; // the batch may have run on another lane's stream
     if (qi < 0 || qi >= c->bres->n_q) return fail(c, PIE_E_INVAL, "query %d outside the batch of %d", qi, c->bres->n_q);
     PIE_HIP(c, hipSetDevice(c->device));
+    if (c->bres->wide) {
+        int rc = wide_need_list(c, *c->bres, qi);
+        if (rc) return rc;
+        const WideSlot::List& l = c->bres->w->lists[qi];
+        if (counts_dev) *counts_dev = l.counts;
+        if (offsets_dev) *offsets_dev = l.offsets;
+        if (idx_dev) *idx_dev = l.idx;
+        return PIE_OK;
+    }
     int rc = batch_need_list(c, *c->bres, qi);
     if (rc) return rc;
     const long long us = batch_users_stride(c);
@@ -3545,7 +4037,31 @@ int pie_batch_read_user_feed(pie_ctx* c, int qi, int32_t user, int32_t* idx_out,
     if (qi < 0 || qi >= b.n_q) return fail(c, PIE_E_INVAL, "query %d outside the batch of %d", qi, b.n_q);
     if (user < 0 || user >= c->n_users) return PIE_OK;
     PIE_HIP(c, hipSetDevice(c->device));
-    if (b.union_ok && !b.list_ok[qi]) {
+    if (b.wide && b.union_part && !b.w->fallback[qi] && !b.w->lists[qi].ok) {
+        // straight from the wide union: the user's (<= 64) union rows and their mask words, filtered by the query's bit
+        const WideSlot& w = *b.w;
+        long long off[2] = {0, 0};
+        PIE_HIP(c, hipMemcpyAsync(off, b.uoff + user, sizeof off, hipMemcpyDeviceToHost, c->stream));
+        PIE_HIP(c, hipStreamSynchronize(c->stream));
+        const size_t ku = (size_t)(off[1] - off[0]);
+        if (ku == 0) return PIE_OK;
+        std::vector<int> rows(ku);
+        std::vector<unsigned long long> masks(ku * (size_t)w.words);
+        PIE_HIP(c, hipMemcpyAsync(rows.data(), b.urows + off[0], ku * 4, hipMemcpyDeviceToHost, c->stream));
+        PIE_HIP(c, hipMemcpyAsync(masks.data(), w.umask + (size_t)off[0] * w.words, ku * w.words * 8, hipMemcpyDeviceToHost, c->stream));
+        PIE_HIP(c, hipStreamSynchronize(c->stream));
+        auto hit = [&](size_t i) { return ((masks[i * w.words + (qi >> 6)] >> (qi & 63)) & 1ull) != 0; };
+        size_t k = 0;
+        for (size_t i = 0; i < ku; ++i) k += hit(i) ? 1 : 0;
+        if (k_out) *k_out = k;
+        if (k == 0) return PIE_OK;
+        if (!idx_out || k > idx_cap) return fail(c, PIE_E_CAPACITY, "idx_cap %zu < feed length %zu", idx_cap, k);
+        size_t at = 0;
+        for (size_t i = 0; i < ku; ++i)
+            if (hit(i)) idx_out[at++] = rows[i];
+        return PIE_OK;
+    }
+    if (!b.wide && b.union_ok && !b.list_ok[qi]) {
         // straight from the union: the user's (few) union rows, filtered by the query's bit — no per-query list is ever built
         long long off[2] = {0, 0};
         PIE_HIP(c, hipMemcpyAsync(off, b.uoff + user, sizeof off, hipMemcpyDeviceToHost, c->stream));
@@ -3606,8 +4122,8 @@ int pie_batch_fetch_requests(pie_ctx* c, const int32_t* qi, const int32_t* user,
         if (qi[i] < 0 || qi[i] >= b.n_q) return fail(c, PIE_E_INVAL, "request %zu: query %d outside the batch of %d", i, qi[i], b.n_q);
     PIE_HIP(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    if (!b.union_ok || !c->d_pay) {
-        // a batch without a union (queries fell back, the ordered run) or a table without the payload column: request by request
+    if (b.wide || !b.union_ok || !c->d_pay) {
+        // a wide batch, a batch without a union (queries fell back, the ordered run) or a table without the payload column: request by request
         size_t total = 0;
         std::vector<int32_t> tmp;
         for (size_t i = 0; i < n_req; ++i) {
@@ -3677,7 +4193,7 @@ int pie_batch_read_results(pie_ctx* c, int qi, int32_t* counts_out, int64_t* off
     if (rc) return rc;
     PIE_HIP(c, hipSetDevice(c->device));
     hipStream_t a = c->stream;
-    const size_t m = (size_t)c->bres->last[qi].m;
+    const size_t m = c->bres->wide ? (size_t)c->bres->w->m[qi] : (size_t)c->bres->last[qi].m;
     if (m_out) *m_out = m;
     if (counts_out) PIE_HIP(c, hipMemcpyAsync(counts_out, dc, (size_t)c->n_users * 4, hipMemcpyDeviceToHost, a));
     if (offsets_out) PIE_HIP(c, hipMemcpyAsync(offsets_out, dof, ((size_t)c->n_users + 1) * 8, hipMemcpyDeviceToHost, a));
@@ -3788,6 +4304,7 @@ int pie_batch_pack_union_device(pie_ctx* c, void* dst_i32, size_t u_pad, size_t 
 {
     if (!c) return PIE_E_INVAL;
     if (!c->bres || !c->bres->have_result) return fail(c, PIE_E_STATE, "no batch result on this context");
+    if (c->bres->wide) return fail(c, PIE_E_STATE, "the last batch is wide: use pie_batch_pack_union_wide_device");
     if (int rc_o = order_after_batch(c, *c->bres)) return rc_o; // the batch may have run on another lane's stream
     if (!dst_i32 || u_pad < (size_t)c->n_users || u_pad > 0x7FFFFFF0u) return fail(c, PIE_E_INVAL, "bad union destination / u_pad < n_users");
     PIE_HIP(c, hipSetDevice(c->device));
@@ -4148,6 +4665,13 @@ int pie_table_info_get(pie_ctx* c, pie_table_info* out)
                                     3 * (uint64_t)batch_span_bytes(c);
     for (const BatchSlot& b : c->bslot) // per-query list storage, where somebody asked for lists
         out->workspace_bytes += (uint64_t)b.lists_q * ((uint64_t)batch_users_stride(c) * 12 + (uint64_t)batch_out_stride(c) * 4);
+    for (const BatchSlot& b : c->bslot) { // the wide state of slots that ran wide batches
+        if (!b.w) continue;
+        if (b.w->dmask) out->workspace_bytes += ((uint64_t)c->cap_users << b.w->dshift) * (kWideWords + (uint64_t)b.w->umask_words) * 8;
+        if (b.w->d_wq) out->workspace_bytes += (uint64_t)kWideMax * sizeof(WideQuery);
+        for (const WideSlot::List& l : b.w->lists)
+            if (l.counts) out->workspace_bytes += ((uint64_t)c->cap_users + 1) * 12 + (uint64_t)l.idx_cap * 4;
+    }
     out->index_build_ms = c->index_build_ms;
     out->ordered_rows = c->ord.valid ? (uint64_t)c->ord.held : 0u;
     out->ordered_positions = c->ord.valid ? (uint64_t)c->ord.n : 0u;
@@ -4238,7 +4762,12 @@ int pie_stats_get(pie_ctx* c, pie_stats* out)
         const BatchSlot& b = *c->bres;
         uint64_t m = 0;
         uint32_t mx = 0;
-        for (int q = 0; q < b.n_q; ++q) { m += b.last[q].m; mx = mx > b.last[q].max_count ? mx : b.last[q].max_count; }
+        if (b.wide) {
+            for (int q = 0; q < b.n_q; ++q) m += b.w->m[q];
+            mx = b.unsupported ? 0u : b.last[0].max_count;
+        } else {
+            for (int q = 0; q < b.n_q; ++q) { m += b.last[q].m; mx = mx > b.last[q].max_count ? mx : b.last[q].max_count; }
+        }
         out->selected = m;
         out->max_bucket = mx;
         out->n_segments = out->n_big = 0;

@@ -160,7 +160,8 @@ function createFeedService(store, options){
 
   // ---- the requests of one event-loop turn, ONE table pass ---------------------------------------------------------
   // requests: [{userId, query}] -> response bodies ({"events":[...]} bytes), in request order.  Requests are grouped by
-  // their (now, cutoff, discipline filter); up to store.BATCH_MAX distinct groups share one batched device scan
+  // their (now, cutoff, discipline filter); up to store.BATCH_MAX distinct groups share one batched device scan — with the
+  // opt-in option {wide: true}, up to store.WIDE_MAX groups share one wide batch (pie_scan_wide_*)
   // (pie_scan_batch: the key column is streamed once, every candidate row is evaluated against all the queries), each
   // request then reads its user's slice of its query's result.  Same bytes as eventsJsonForUser, request by request.
   let batchesRun = 0;
@@ -180,11 +181,13 @@ function createFeedService(store, options){
       }
       g.members.push(i);
     });
-    const maxQ = store.BATCH_MAX || 16;
+    const wide = opts.wide === true;
+    const maxQ = wide ? store.WIDE_MAX : (store.BATCH_MAX || 16);
     for(let at = 0; at < groups.length; at += maxQ){
       const chunk = groups.slice(at, at + maxQ);
       const ts = process.hrtime.bigint();
-      store.scanBatchDevice(chunk.map(g => ({now: g.k.now, cutoff: g.k.cutoff, disciplines: g.k.disciplines})));
+      const qs = chunk.map(g => ({now: g.k.now, cutoff: g.k.cutoff, disciplines: g.k.disciplines}));
+      if(wide){ store.scanWideDevice(qs); }else{ store.scanBatchDevice(qs); }
       timing.scanNs += Number(process.hrtime.bigint() - ts);
       batchesRun++;
       last = null;                     // the device now holds a batch result, not a single scan's

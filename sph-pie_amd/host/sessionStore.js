@@ -345,6 +345,15 @@ function createStore(options){
   const BATCH_MAX = 64;
   function scanBatchDevice(queries){
     if(queries.length < 1 || queries.length > BATCH_MAX){ throw new Error('a batch holds 1..' + BATCH_MAX + ' queries'); }
+    return scanQueries(queries, 'scanBatch');
+  }
+  // a WIDE batch (pie_scan_wide_*): up to WIDE_MAX queries in one table pass; batchUserFeed / batchFetch then take qi < WIDE_MAX
+  const WIDE_MAX = 512;
+  function scanWideDevice(queries){
+    if(queries.length < 1 || queries.length > WIDE_MAX){ throw new Error('a wide batch holds 1..' + WIDE_MAX + ' queries'); }
+    return scanQueries(queries, 'scanWide');
+  }
+  function scanQueries(queries, fn){
     flush();
     const nows = new BigInt64Array(queries.length), cutoffs = new BigInt64Array(queries.length);
     const masks = new BigUint64Array(queries.length);
@@ -355,7 +364,7 @@ function createStore(options){
     });
     native.setDisciplines(ctx, (1n << BigInt(disciplineConfig.DISCIPLINES.length)) - 1n, disciplineConfig.DISCIPLINES.length);
     generation++;                                   // a single-scan result on the device is gone
-    return native.scanBatch(ctx, nows, cutoffs, masks);
+    return native[fn](ctx, nows, cutoffs, masks);
   }
   function batchUserFeed(qi, u){
     const want = Math.max(base > 0 ? 4096 : rows.length, 1);
@@ -437,7 +446,7 @@ function createStore(options){
   return {
     createSession, getSession, touchSession, deleteSession, deleteSessionsForUser, purgeExpiredSessions, purgeRetention,
     SESSION_TTL_MS, SESSION_COOKIE_NAME,
-    scanFeeds, scanDevice, userFeed, scanBatchDevice, batchUserFeed, batchFetch, BATCH_MAX, fetchRows, expiredRows, archivedRows, flush, close, save, restore,
+    scanFeeds, scanDevice, userFeed, scanBatchDevice, batchUserFeed, batchFetch, BATCH_MAX, scanWideDevice, WIDE_MAX, fetchRows, expiredRows, archivedRows, flush, close, save, restore,
     compact, compactions: () => compactions, tableRows: () => base + rows.length, baseRows: () => base,
     userIds: () => userIds,
     userIndexOf: userId => (userIndex.has(userId) ? userIndex.get(userId) : -1),
