@@ -358,6 +358,9 @@ typedef struct pie_table_info {
     uint64_t ordered_builds;  /* times it was built for this context */
     uint64_t ordered_positions; /* positions a scan of the run visits: its rows + the spare slots of every user's segment */
     uint64_t ordered_respreads; /* times appends filled a segment and the run was moved into fresh segments (a linear pass) */
+    uint64_t hot_rows;        /* rows the end-ordered hot index holds, its delta aside (0: there is none, or it was dropped) */
+    uint64_t hot_bytes;       /* device memory of the hot index (32 B per entry and delta slot + 4 B per row of capacity + build scratch) */
+    uint64_t hot_builds;      /* times it was built for this context */
 } pie_table_info;
 int pie_table_info_get(pie_ctx *ctx, pie_table_info *out);
 /* The ordered run (sph-pie_amd/csrc/pie_ordered.h): the table's rows a second time, in (user, start, row) order — the order

@@ -30,7 +30,7 @@ class PieTableInfo(C.Structure):
         ("table_bytes", C.c_uint64), ("derived_bytes", C.c_uint64), ("workspace_bytes", C.c_uint64),
         ("index_build_ms", C.c_double), ("ordered_rows", C.c_uint64), ("ordered_bytes", C.c_uint64),
         ("ordered_build_ms", C.c_double), ("ordered_builds", C.c_uint64), ("ordered_positions", C.c_uint64),
-        ("ordered_respreads", C.c_uint64),
+        ("ordered_respreads", C.c_uint64), ("hot_rows", C.c_uint64), ("hot_bytes", C.c_uint64), ("hot_builds", C.c_uint64),
     ]
 
 

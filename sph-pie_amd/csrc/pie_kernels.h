@@ -740,6 +740,150 @@ struct alignas(16) PayRec {
     int disc;
 };
 
+// ------------------------------------------------------------------------------------------------ end-ordered hot index
+//
+// The rows with a fine key >= 1 (end >= fkey_base: about a tenth of the table, every row a top-of-range query can find) a
+// second time, as 32-byte records grouped by fine-key bin 1..127, rows ascending inside a bin.  A batch whose smallest
+// key(now) is k >= 1 finds exactly the candidates of the keyed pass in the suffix [off[k], n_main), read coalesced — no key
+// stream, no 128-byte sector per 16-byte payload gather — plus the delta region [n_main, n_main + *delta_n), always read whole.
+// Exactness under mutation rests on one invariant the writers keep (hot_mirror_end): every row with fine key f >= 1 has
+// one live entry, in a bin >= f or in the delta; a row has at most one live entry, and it holds the row's current `end`.
+struct alignas(16) HotRec {
+    long long start;
+    long long end;
+    int user;
+    int disc; // -1: dead (the row moved to the delta)
+    int row;
+    int bin;  // fine-key bin the entry sits in; kHotDeltaBin in the delta
+};
+constexpr int kHotDeltaBin = 128;
+
+struct HotMirror {
+    int* pos;          // nullptr: no index.  row -> entry, -1 for rows it does not hold
+    HotRec* rec;
+    unsigned* delta_n; // delta cursor
+    long long n_main;
+    unsigned delta_cap;
+    const PayRec* pay; // start / user / disc of a re-ended row that moves to the delta
+};
+// Every writer of `end` that does not rebuild the keys: an entry whose bin is at or above the new fine key, or that sits in
+// the delta, takes the new `end` in place (the pass ranks the stored `end`, so a lower one is exact where it stands); a row
+// whose new fine key lies above its entry's bin, or a row the index does not hold whose new `end` reaches fkey_base, gets a
+// record in the delta and its old entry, if any, is marked dead.  The host bounds the delta's growth (pie_ctx::HotIndex).
+__device__ __forceinline__ void hot_mirror_end(const HotMirror& h, long long row, long long e, unsigned fk, const PayRec* pr = nullptr)
+{
+    if (!h.pos) return;
+    const int p = h.pos[row];
+    if (p >= 0 && (p >= h.n_main || (int)fk <= h.rec[p].bin)) {
+        h.rec[p].end = e;
+        return;
+    }
+    if (fk == 0) return; // p < 0 here: the row stays out
+    const unsigned q = atomicAdd(h.delta_n, 1u);
+    if (q >= h.delta_cap) return; // unreachable: the host drops the index before its bound on the delta could pass the capacity
+    const PayRec pv = pr ? *pr : h.pay[row];
+    HotRec r;
+    r.start = pv.start;
+    r.end = e;
+    r.user = pv.user;
+    r.disc = pv.disc;
+    r.row = (int)row;
+    r.bin = kHotDeltaBin;
+    const int at = (int)(h.n_main + q);
+    h.rec[at] = r;
+    __threadfence(); // the record is complete before the row points at it: of two writers of one row, the later retires the earlier's
+    const int old = atomicExch(&h.pos[row], at);
+    if (old >= 0) atomicExch(&h.rec[old].disc, -1);
+}
+
+// Build, a stable counting sort by bin over segments of the table (one per wave, rows [seg * seg_len, ..)):
+// k_hot_count   cnt[bin * S + seg] = rows of the segment in that bin (bin 0 counts nothing)
+// k_hot_scan    exclusive prefix of cnt in (bin, segment) order, in place; off[b] = first entry of bin b, off[128] = n_main
+// k_hot_scatter the records, in row order inside each (bin, segment), and pos[] of every row they hold
+__global__ __launch_bounds__(256) void k_hot_count(const fkey_t* __restrict__ fkey, long long n, long long seg_len, unsigned* __restrict__ cnt)
+{
+    __shared__ unsigned h[4][128];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long S = (long long)gridDim.x * 4, seg = (long long)blockIdx.x * 4 + wave;
+    h[wave][lane] = 0;
+    h[wave][lane + 64] = 0;
+    __builtin_amdgcn_wave_barrier();
+    const long long r0 = seg * seg_len, r1 = min(n, r0 + seg_len);
+    for (long long r = r0 + lane; r < r1; r += kWave) {
+        const unsigned k = fkey[r];
+        if (k) atomicAdd(&h[wave][k], 1u);
+    }
+    __builtin_amdgcn_wave_barrier();
+    cnt[(long long)lane * S + seg] = h[wave][lane];
+    cnt[(long long)(lane + 64) * S + seg] = h[wave][lane + 64];
+}
+
+__global__ __launch_bounds__(1024) void k_hot_scan(unsigned* __restrict__ cnt, long long S, long long* __restrict__ off)
+{
+    __shared__ unsigned long long part[1024];
+    const long long total = 128 * S, per = (total + 1023) / 1024;
+    const long long i0 = (long long)threadIdx.x * per, i1 = min(total, i0 + per);
+    unsigned long long s = 0;
+    for (long long i = i0; i < i1; ++i) s += cnt[i];
+    part[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = 1; o < 1024; o <<= 1) {
+        const unsigned long long v = (int)threadIdx.x >= o ? part[threadIdx.x - o] : 0ull;
+        __syncthreads();
+        part[threadIdx.x] += v;
+        __syncthreads();
+    }
+    unsigned long long run = part[threadIdx.x] - s;
+    for (long long i = i0; i < i1; ++i) {
+        const unsigned c = cnt[i];
+        if (i % S == 0) off[i / S] = (long long)run;
+        cnt[i] = (unsigned)run;
+        run += c;
+    }
+    if (threadIdx.x == 1023) off[128] = (long long)part[1023];
+}
+
+__global__ __launch_bounds__(256) void k_hot_scatter(const fkey_t* __restrict__ fkey, const long long* __restrict__ end,
+                                                     const PayRec* __restrict__ pay, long long n, long long seg_len,
+                                                     const unsigned* __restrict__ cnt, HotRec* __restrict__ rec, int* __restrict__ pos)
+{
+    __shared__ unsigned at[4][128];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long S = (long long)gridDim.x * 4, seg = (long long)blockIdx.x * 4 + wave;
+    at[wave][lane] = cnt[(long long)lane * S + seg];
+    at[wave][lane + 64] = cnt[(long long)(lane + 64) * S + seg];
+    __builtin_amdgcn_wave_barrier();
+    const unsigned long long lt = (1ull << lane) - 1ull;
+    const long long r0 = seg * seg_len, r1 = min(n, r0 + seg_len);
+    for (long long rb = r0; rb < r1; rb += kWave) {
+        const long long r = rb + lane;
+        const unsigned k = r < r1 ? fkey[r] : 0u;
+        unsigned long long todo = __ballot(k != 0);
+        while (todo) { // one distinct bin of these 64 rows per round, its rows ranked in row order
+            const unsigned kb = (unsigned)__shfl((int)k, __ffsll((long long)todo) - 1, kWave);
+            const unsigned long long m = __ballot(k == kb);
+            const unsigned base = at[wave][kb];
+            if (k == kb) {
+                const int e = (int)(base + (unsigned)__popcll(m & lt));
+                const PayRec p = pay[r];
+                HotRec h;
+                h.start = p.start;
+                h.end = end[r];
+                h.user = p.user;
+                h.disc = p.disc;
+                h.row = (int)r;
+                h.bin = (int)kb;
+                rec[e] = h;
+                pos[r] = e;
+            }
+            __builtin_amdgcn_wave_barrier();
+            if (lane == 0) at[wave][kb] = base + (unsigned)__popcll(m);
+            __builtin_amdgcn_wave_barrier();
+            todo &= ~m;
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void k_build_key(const long long* __restrict__ end, long long row0, long long n, long long base,
                                                    int shift, lkey_t* __restrict__ key, const long long* __restrict__ start,
                                                    const int* __restrict__ user, const int* __restrict__ disc,
@@ -1912,6 +2056,10 @@ struct BatchScanArgs {
     BktRec* direct;            // union bucket slots, (1 << dshift) per user; BktRec::pad = the queries (0..31) that selected the row
     unsigned* direct_hi;       // queries 32..63 of every slot (written when n_q > 32)
     int run_shift;             // see KeyedArgs
+    const HotRec* hot;         // non-null: the candidates are the hot index's entries [hot_lo, hot_main + *hot_delta_n), not the key stream
+    long long hot_lo, hot_main;
+    const unsigned* hot_delta_n;
+    unsigned hot_delta_cap;
     BatchTables tab;
 };
 
@@ -1958,24 +2106,9 @@ __device__ __forceinline__ void scan_batch_body(const BatchScanArgs<KT>& a, int 
     const int nq = a.n_q;
     const int cap = 1 << a.dshift;
 
-    // evaluate `cnt` queued candidates (cnt <= 64), one per lane, against every query of the batch
-    auto drain = [&](int cnt) {
-        const bool valid = lane < cnt;
-        int row = 0;
-        unsigned key = 0;
-        PayRec pr;
-        pr.start = 0; pr.user = 0; pr.disc = -1;
-        if (valid) {
-            const int slot = (lhead + lane) & (kLiveRing - 1);
-            row = rrow[slot];
-            key = (unsigned)rkey[slot];
-            pr = a.pay[row]; // ONE gather per candidate, shared by all queries
-        }
-        // liveness: the queries whose key(now) lies below the row's key form a prefix of the sorted order; a row whose key
-        // EQUALS some query's is ranked by its 8-byte `end` instead (key() is monotone, so that is exact for every query)
-        int r = rank_in_64<true>(tab.nk, key);
-        const bool amb = valid && r < kBatchMax && tab.nk[r < kBatchMax ? r : 0] == key;
-        if (amb) r = rank_in_64<true>(tab.now, a.end[row]);
+    // the Q predicates of one candidate per lane, `r` = the queries whose `now` lies below the row's `end` (a prefix of the
+    // sorted order); a row that any query selects costs ONE histogram atomic and ONE slot store, whatever Q
+    auto emit = [&](bool valid, int row, const PayRec& pr, int r) {
         const int w = rank_in_64<false>(tab.cutoff, pr.start);
         unsigned long long qmask = 0;
         if (valid && (unsigned)pr.disc < 64u) qmask = tab.live[r] & tab.win[w] & tab.disc[pr.disc & 63];
@@ -1994,6 +2127,26 @@ __device__ __forceinline__ void scan_batch_body(const BatchScanArgs<KT>& a, int 
                 if (nq > 32) a.direct_hi[((long long)pr.user << a.dshift) + rank] = (unsigned)(qmask >> 32);
             }
         }
+    };
+    // evaluate `cnt` queued candidates (cnt <= 64), one per lane, against every query of the batch
+    auto drain = [&](int cnt) {
+        const bool valid = lane < cnt;
+        int row = 0;
+        unsigned key = 0;
+        PayRec pr;
+        pr.start = 0; pr.user = 0; pr.disc = -1;
+        if (valid) {
+            const int slot = (lhead + lane) & (kLiveRing - 1);
+            row = rrow[slot];
+            key = (unsigned)rkey[slot];
+            pr = a.pay[row]; // ONE gather per candidate, shared by all queries
+        }
+        // liveness: the queries whose key(now) lies below the row's key form a prefix of the sorted order; a row whose key
+        // EQUALS some query's is ranked by its 8-byte `end` instead (key() is monotone, so that is exact for every query)
+        int r = rank_in_64<true>(tab.nk, key);
+        const bool amb = valid && r < kBatchMax && tab.nk[r < kBatchMax ? r : 0] == key;
+        if (amb) r = rank_in_64<true>(tab.now, a.end[row]);
+        emit(valid, row, pr, r);
         ncand += cnt;
         lhead = (lhead + cnt) & (kLiveRing - 1);
         lfill -= cnt;
@@ -2014,63 +2167,84 @@ __device__ __forceinline__ void scan_batch_body(const BatchScanArgs<KT>& a, int 
         return true;
     };
 
-    // SWAR candidate test against the batch's smallest key(now) (see scan_keyed_body)
-    typedef unsigned u4_t __attribute__((ext_vector_type(4)));
-    constexpr unsigned kTop = sizeof(KT) == 2 ? 0x80008000u : 0x80808080u;
-    const unsigned mk = a.min_key;
-    const unsigned nkr = sizeof(KT) == 2 ? (mk | (mk << 16)) : mk * 0x01010101u;
-    // rows dealt to the launch's waves in chunks of one load per lane, round robin (see scan_keyed_body)
-    const long long n_chunks = a.n / kRowsPerLoad;
-    const long long W = (long long)n_scan_blocks * kK1Waves;
-    const long long gw = (long long)bid * kK1Waves + wave;
-    for (long long cb = gw << run_shift; cb < n_chunks; cb += W * UNROLL) {
-        u4_t kv[UNROLL];
-#pragma unroll
-        for (int j = 0; j < UNROLL; ++j) {
-            const long long ch = cb + (((long long)(j >> run_shift) * W) << run_shift) + (j & ((1 << run_shift) - 1));
-            kv[j] = (u4_t){0u, 0u, 0u, 0u};
-            if (ch < n_chunks) kv[j] = stream_load<NT>(reinterpret_cast<const u4_t*>(a.key + ch * kRowsPerLoad + kPerLane * lane));
+    if (a.hot) {
+        // the hot index (HotRec): one record per lane — the suffix of the batch's smallest key, then the whole delta — ranked
+        // by its stored `end`; groups of 64 records dealt to the launch's waves round robin.  No chunk statistics: the host
+        // tunes nothing from this pass but the candidate count.
+        const unsigned dn = *a.hot_delta_n;
+        const long long n_rec = a.hot_main - a.hot_lo + (long long)(dn < a.hot_delta_cap ? dn : a.hot_delta_cap);
+        const HotRec* src = a.hot + a.hot_lo;
+        const long long W = (long long)n_scan_blocks * kK1Waves;
+        for (long long g = ((long long)bid * kK1Waves + wave) * kWave; g < n_rec; g += W * kWave) {
+            const long long i = g + lane;
+            const bool valid = i < n_rec;
+            HotRec h;
+            h.start = 0; h.end = INT64_MIN; h.user = 0; h.disc = -1; h.row = 0; h.bin = 0;
+            if (valid) h = src[i];
+            PayRec pr;
+            pr.start = h.start; pr.user = h.user; pr.disc = h.disc;
+            emit(valid, h.row, pr, rank_in_64<true>(tab.now, h.end));
+            ncand += n_rec - g < kWave ? (int)(n_rec - g) : kWave;
         }
-#pragma unroll
-        for (int j = 0; j < UNROLL; ++j) {
-            const long long ch = cb + (((long long)(j >> run_shift) * W) << run_shift) + (j & ((1 << run_shift) - 1));
-            if (ch >= n_chunks) continue;
-            chunk_max = max(chunk_max, pushed - chunk_mark);
-            chunk_mark = pushed;
-            const int r0 = (int)(ch * kRowsPerLoad + kPerLane * lane);
-            const unsigned g0 = ((kv[j].x | kTop) - nkr) & kTop, g1 = ((kv[j].y | kTop) - nkr) & kTop;
-            const unsigned g2 = ((kv[j].z | kTop) - nkr) & kTop, g3 = ((kv[j].w | kTop) - nkr) & kTop;
-            if constexpr (sizeof(KT) == 2) {
-                unsigned long long m = ((unsigned long long)g0 | ((unsigned long long)g1 << 32)) |
-                                       (((unsigned long long)g2 | ((unsigned long long)g3 << 32)) >> 8);
-                for (;;) {
-                    const bool has = m != 0;
-                    const int pbit = __ffsll((long long)m) - 1;
-                    const int q = (pbit >> 4) + ((pbit & 8) ? 0 : 4);
-                    const unsigned w = q < 4 ? (q < 2 ? kv[j].x : kv[j].y) : (q < 6 ? kv[j].z : kv[j].w);
-                    const unsigned kq = (w >> ((q & 1) * 16)) & 0xFFFFu;
-                    if (!push(has, r0 + q, kq)) break;
-                    m &= m - 1;
-                }
-            } else {
-                unsigned m = (g0 >> 7) | (g1 >> 6) | (g2 >> 5) | (g3 >> 4);
-                for (;;) {
-                    const bool has = m != 0;
-                    const int pbit = __ffs((int)m) - 1;
-                    const int w = pbit & 7, b = pbit >> 3;
-                    const unsigned word = w < 2 ? (w == 0 ? kv[j].x : kv[j].y) : (w == 2 ? kv[j].z : kv[j].w);
-                    const unsigned kq = (word >> (8 * b)) & 0xFFu;
-                    if (!push(has, r0 + 4 * w + b, kq)) break;
-                    m &= m - 1;
+    } else {
+        // SWAR candidate test against the batch's smallest key(now) (see scan_keyed_body)
+        typedef unsigned u4_t __attribute__((ext_vector_type(4)));
+        constexpr unsigned kTop = sizeof(KT) == 2 ? 0x80008000u : 0x80808080u;
+        const unsigned mk = a.min_key;
+        const unsigned nkr = sizeof(KT) == 2 ? (mk | (mk << 16)) : mk * 0x01010101u;
+        // rows dealt to the launch's waves in chunks of one load per lane, round robin (see scan_keyed_body)
+        const long long n_chunks = a.n / kRowsPerLoad;
+        const long long W = (long long)n_scan_blocks * kK1Waves;
+        const long long gw = (long long)bid * kK1Waves + wave;
+        for (long long cb = gw << run_shift; cb < n_chunks; cb += W * UNROLL) {
+            u4_t kv[UNROLL];
+    #pragma unroll
+            for (int j = 0; j < UNROLL; ++j) {
+                const long long ch = cb + (((long long)(j >> run_shift) * W) << run_shift) + (j & ((1 << run_shift) - 1));
+                kv[j] = (u4_t){0u, 0u, 0u, 0u};
+                if (ch < n_chunks) kv[j] = stream_load<NT>(reinterpret_cast<const u4_t*>(a.key + ch * kRowsPerLoad + kPerLane * lane));
+            }
+    #pragma unroll
+            for (int j = 0; j < UNROLL; ++j) {
+                const long long ch = cb + (((long long)(j >> run_shift) * W) << run_shift) + (j & ((1 << run_shift) - 1));
+                if (ch >= n_chunks) continue;
+                chunk_max = max(chunk_max, pushed - chunk_mark);
+                chunk_mark = pushed;
+                const int r0 = (int)(ch * kRowsPerLoad + kPerLane * lane);
+                const unsigned g0 = ((kv[j].x | kTop) - nkr) & kTop, g1 = ((kv[j].y | kTop) - nkr) & kTop;
+                const unsigned g2 = ((kv[j].z | kTop) - nkr) & kTop, g3 = ((kv[j].w | kTop) - nkr) & kTop;
+                if constexpr (sizeof(KT) == 2) {
+                    unsigned long long m = ((unsigned long long)g0 | ((unsigned long long)g1 << 32)) |
+                                           (((unsigned long long)g2 | ((unsigned long long)g3 << 32)) >> 8);
+                    for (;;) {
+                        const bool has = m != 0;
+                        const int pbit = __ffsll((long long)m) - 1;
+                        const int q = (pbit >> 4) + ((pbit & 8) ? 0 : 4);
+                        const unsigned w = q < 4 ? (q < 2 ? kv[j].x : kv[j].y) : (q < 6 ? kv[j].z : kv[j].w);
+                        const unsigned kq = (w >> ((q & 1) * 16)) & 0xFFFFu;
+                        if (!push(has, r0 + q, kq)) break;
+                        m &= m - 1;
+                    }
+                } else {
+                    unsigned m = (g0 >> 7) | (g1 >> 6) | (g2 >> 5) | (g3 >> 4);
+                    for (;;) {
+                        const bool has = m != 0;
+                        const int pbit = __ffs((int)m) - 1;
+                        const int w = pbit & 7, b = pbit >> 3;
+                        const unsigned word = w < 2 ? (w == 0 ? kv[j].x : kv[j].y) : (w == 2 ? kv[j].z : kv[j].w);
+                        const unsigned kq = (word >> (8 * b)) & 0xFFu;
+                        if (!push(has, r0 + 4 * w + b, kq)) break;
+                        m &= m - 1;
+                    }
                 }
             }
         }
-    }
-    if (gw == (n_chunks >> run_shift) % W) {
-        for (long long r0 = n_chunks * kRowsPerLoad; r0 < a.n; r0 += kWave) {
-            const long long r = r0 + lane;
-            const unsigned kq = r < a.n ? a.key[r] : 0u;
-            push(r < a.n && kq >= mk, (int)r, kq);
+        if (gw == (n_chunks >> run_shift) % W) {
+            for (long long r0 = n_chunks * kRowsPerLoad; r0 < a.n; r0 += kWave) {
+                const long long r = r0 + lane;
+                const unsigned kq = r < a.n ? a.key[r] : 0u;
+                push(r < a.n && kq >= mk, (int)r, kq);
+            }
         }
     }
     if (lfill > 0) drain(lfill);
@@ -3662,7 +3836,8 @@ __global__ __launch_bounds__(256) void k_union_write(int n_users, int u_pad, con
 __global__ __launch_bounds__(256) void k_set_end(long long* __restrict__ end, const int* __restrict__ rows,
                                                  const long long* __restrict__ new_end, long long k, long long n,
                                                  lkey_t* __restrict__ key, long long key_base, int key_shift,
-                                                 fkey_t* __restrict__ fkey, long long fkey_base, int fkey_shift, OrdMirror ord)
+                                                 fkey_t* __restrict__ fkey, long long fkey_base, int fkey_shift, OrdMirror ord,
+                                                 HotMirror hot)
 {
     const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (t < k && (unsigned)rows[t] < (unsigned long long)n) {
@@ -3671,6 +3846,7 @@ __global__ __launch_bounds__(256) void k_set_end(long long* __restrict__ end, co
         if (key) key[rows[t]] = (lkey_t)kk;
         if (fkey) fkey[rows[t]] = (fkey_t)fk;
         ord_mirror_end(ord, rows[t], new_end[t], kk, fk);
+        hot_mirror_end(hot, rows[t], new_end[t], fk);
     }
 }
 
@@ -3684,7 +3860,7 @@ __global__ __launch_bounds__(256) void k_append_rows(const long long* __restrict
                                                      long long* __restrict__ end, int* __restrict__ user, int* __restrict__ disc,
                                                      lkey_t* __restrict__ key, long long key_base, int key_shift,
                                                      fkey_t* __restrict__ fkey, long long fkey_base, int fkey_shift,
-                                                     PayRec* __restrict__ pay, unsigned int* __restrict__ bad)
+                                                     PayRec* __restrict__ pay, unsigned int* __restrict__ bad, HotMirror hot)
 {
     unsigned int local = 0;
     for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < k; t += (long long)gridDim.x * blockDim.x) {
@@ -3698,13 +3874,12 @@ __global__ __launch_bounds__(256) void k_append_rows(const long long* __restrict
         disc[r] = dv;
         if (key) key[r] = (lkey_t)key_of(ev, key_base, key_shift);
         if (fkey) fkey[r] = (fkey_t)key_of(ev, fkey_base, fkey_shift, kFineKeyMax);
-        if (pay) {
-            PayRec pr;
-            pr.start = sv;
-            pr.user = uv;
-            pr.disc = dv;
-            pay[r] = pr;
-        }
+        PayRec pr;
+        pr.start = sv;
+        pr.user = uv;
+        pr.disc = dv;
+        if (pay) pay[r] = pr;
+        hot_mirror_end(hot, r, ev, key_of(ev, fkey_base, fkey_shift, kFineKeyMax), &pr);
     }
     for (int o = 32; o > 0; o >>= 1) local += __shfl_xor(local, o, kWave);
     if ((threadIdx.x & 63) == 0 && local) atomicAdd(bad, local);
@@ -3892,7 +4067,7 @@ template <int MODE>
 __global__ __launch_bounds__(256) void k_list_write(long long* __restrict__ end, const int* __restrict__ user, long long n,
                                                     long long rows_per_block, long long a, long long b,
                                                     const long long* __restrict__ blk_off, int* __restrict__ queue, long long cap,
-                                                    lkey_t* __restrict__ key, fkey_t* __restrict__ fkey, OrdMirror ord)
+                                                    lkey_t* __restrict__ key, fkey_t* __restrict__ fkey, OrdMirror ord, HotMirror hot)
 {
     __shared__ int wcount[4];
     __shared__ long long carry_s;
@@ -3917,6 +4092,7 @@ __global__ __launch_bounds__(256) void k_list_write(long long* __restrict__ end,
                 if (key) key[r] = 0;
                 if (fkey) fkey[r] = 0;
                 ord_mirror_end(ord, r, INT64_MIN, 0u, 0u);
+                hot_mirror_end(hot, r, INT64_MIN, 0u);
             }
         }
         __syncthreads();

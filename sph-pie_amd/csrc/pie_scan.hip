@@ -108,6 +108,7 @@ struct Slot {
 // the next launch is always queued before the host waits.
 constexpr int kBatchSlots = 3;
 constexpr int kLaneMax = 4;     // batch lanes of a context (pie_set_batch_lanes): independent streams, kBatchSlots batches in flight on each
+constexpr long long kHotDeltaMin = 1 << 16; // delta entries of the hot index at least (an eighth of its entries where that is more)
 
 // what a batch slot needs for a WIDE batch (pie_kernels.h "wide batches"), allocated the first time the slot runs one
 struct WideSlot {
@@ -138,6 +139,7 @@ struct BatchSlot {
     bool ordered = false;              // this batch ran on the ordered run (pie_ordered.h "batched form"): no tail, nothing rides
     bool unsupported = false;          // this table cannot run the batched pass (no key columns / no direct slots): every query falls back
     bool fine_key = false;
+    bool hot = false;                  // the pass read the hot index (pie_ctx::HotIndex) instead of the 1-byte key column
     unsigned long long seq = 0;
     char* span = nullptr;              // this batch's span (histogram | tile granules | ctl | summary + row statistics | mq slots)
     char* zero_span = nullptr;         // the span its tail zeroes
@@ -322,6 +324,26 @@ struct pie_ctx {
     int union_users = 0;
     OrderedRun ord;
     bool ord_building = false;  // the scan being begun is the ordered run's build
+    // The end-ordered hot index (pie_kernels.h HotRec): where the 1-byte batched pass would stream the key column, a batch reads
+    // the index's suffix for its smallest key(now) and the delta instead.  Built at the first batch begin that can use it with
+    // nothing in flight; dropped by every key build or refit (build_keys).  Writers keep it exact in place (hot_mirror_of) and
+    // never wait for it: the delta's cursor lives on the device, and the host bounds it by the rows its writers could move there
+    // (delta_bound: the k of every set_end / append since the build), dropping the index before that bound passes delta_cap.
+    struct HotIndex {
+        HotRec* rec = nullptr;    // [n_main) grouped by bin | [delta_cap) delta
+        long long rec_cap = 0;
+        int* pos = nullptr;       // [pos_cap] row -> entry (-1: not held)
+        long long pos_cap = 0;
+        unsigned* cnt = nullptr;  // build scratch: 128 x segments counts / offsets
+        long long cnt_cap = 0;
+        long long* d_off = nullptr; // [129] bin offsets, device
+        unsigned* delta_n = nullptr;
+        long long off[129] = {};  // host copy: off[k] = first entry of bin k, off[128] = n_main
+        long long n_main = 0, delta_cap = 0, delta_bound = 0;
+        bool valid = false;
+        bool enabled = true;      // PIE_HOT_INDEX=0: never built (A/B runs)
+        unsigned long long builds = 0;
+    } hix;
     Slot slot[2];
     // Batch lanes.  A batch over a SHARD-sized table (a tenth of cfg3) is one launch of ~20 us that fills a fraction of the chip:
     // its time is latency (key load -> candidate gather -> atomic -> store; then the tail's prefix chain), not bytes.  Lanes are
@@ -563,6 +585,36 @@ void ord_invalidate(pie_ctx* c, bool new_table = false, bool out_of_order = fals
 // (a user with a handful of rows then takes a few hundred appends' worth of new sessions before anything has to move), else 4
 int ord_spare(const pie_ctx* c) { return (long long)16 * c->cap_users <= c->cap_rows / 4 ? 16 : 4; }
 
+HotMirror hot_mirror_of(const pie_ctx* c)
+{
+    HotMirror m{};
+    if (c->hix.valid) {
+        m.pos = c->hix.pos;
+        m.rec = c->hix.rec;
+        m.delta_n = c->hix.delta_n;
+        m.n_main = c->hix.n_main;
+        m.delta_cap = (unsigned)c->hix.delta_cap;
+        m.pay = c->d_pay;
+    }
+    return m;
+}
+
+// a writer about to move up to k rows into the delta: the index stays only while the host's bound says they fit
+void hot_reserve(pie_ctx* c, long long k)
+{
+    if (!c->hix.valid) return;
+    if (c->hix.delta_bound + k > c->hix.delta_cap) c->hix.valid = false;
+    else c->hix.delta_bound += k;
+}
+
+void hot_free(pie_ctx* c)
+{
+    pie_ctx::HotIndex& h = c->hix;
+    dfree(h.rec); dfree(h.pos); dfree(h.cnt); dfree(h.d_off); dfree(h.delta_n);
+    h.rec_cap = h.pos_cap = h.cnt_cap = 0;
+    h.valid = false;
+}
+
 OrdMirror ord_mirror_of(const pie_ctx* c)
 {
     OrdMirror m{};
@@ -583,6 +635,7 @@ void free_table(pie_ctx* c)
     dfree(c->d_union); dfree(c->d_union_cnt); dfree(c->d_union_local); dfree(c->d_union_off);
     c->union_users = 0;
     ord_free(c);
+    hot_free(c);
     free_batch(c);
     dfree(c->d_start); dfree(c->d_end); dfree(c->d_user); dfree(c->d_disc); dfree(c->d_key); dfree(c->d_pay); dfree(c->d_fkey);
     dfree(c->d_arch);
@@ -858,6 +911,7 @@ int validate_users(pie_ctx* c, long long row0 = 0)
 // (out-of-range values clamp; the column stays exact, only less selective).
 int build_keys(pie_ctx* c, long long row0, bool rebuild = false)
 {
+    c->hix.valid = false; // its bins are the fine key's
     if (!c->d_key || !c->d_pay || !c->d_fkey) { c->key_ok = false; return PIE_OK; }
     const bool write_pay = !(rebuild && c->key_ok); // a refit of the key leaves the (immutable) payload alone
     if (c->n == 0) { c->key_ok = true; c->key_base = 0; c->key_shift = 0; c->key_dirty = false; return PIE_OK; }
@@ -943,6 +997,51 @@ int build_keys(pie_ctx* c, long long row0, bool rebuild = false)
         clock_gettime(CLOCK_MONOTONIC, &tb1);
         c->index_build_ms = (double)(tb1.tv_sec - tb0.tv_sec) * 1e3 + (double)(tb1.tv_nsec - tb0.tv_nsec) * 1e-6;
     }
+    return PIE_OK;
+}
+
+// The hot index of the current fine key (see pie_ctx::HotIndex), on the main stream with nothing in flight; waits for the
+// bin offsets.  Device memory it cannot get leaves the batches on the key stream.
+int hot_build(pie_ctx* c)
+{
+    pie_ctx::HotIndex& h = c->hix;
+    hipStream_t s = c->stream;
+    const long long blocks = (long long)c->n_cus * 16, S = blocks * 4; // one segment per wave
+    const long long seg_len = ((c->n + S - 1) / S + kWave - 1) / kWave * kWave;
+    auto grow = [&](auto*& p, long long& cap, long long want, size_t elem) {
+        if (cap >= want) return true;
+        dfree(p);
+        cap = 0;
+        if (hipMalloc(&p, (size_t)want * elem) != hipSuccess) { (void)hipGetLastError(); return false; }
+        cap = want;
+        return true;
+    };
+    long long one = 0;
+    if (!h.d_off) grow(h.d_off, one, 129, sizeof(long long));
+    one = 0;
+    if (!h.delta_n) grow(h.delta_n, one, 1, sizeof(unsigned));
+    if (!h.d_off || !h.delta_n || !grow(h.pos, h.pos_cap, c->cap_rows, sizeof(int)) || !grow(h.cnt, h.cnt_cap, 128 * S, sizeof(unsigned))) {
+        h.enabled = false;
+        return PIE_OK;
+    }
+    PIE_HIP(c, hipMemsetAsync(h.pos, 0xFF, (size_t)c->cap_rows * sizeof(int), s));
+    hipLaunchKernelGGL(k_hot_count, dim3((unsigned)blocks), dim3(256), 0, s, c->d_fkey, c->n, seg_len, h.cnt);
+    hipLaunchKernelGGL(k_hot_scan, dim3(1), dim3(1024), 0, s, h.cnt, S, h.d_off);
+    PIE_HIP(c, hipGetLastError());
+    PIE_HIP(c, hipMemcpyAsync(h.off, h.d_off, sizeof h.off, hipMemcpyDeviceToHost, s));
+    PIE_HIP(c, hipStreamSynchronize(s));
+    h.n_main = h.off[128];
+    h.delta_cap = h.n_main / 8 > kHotDeltaMin ? h.n_main / 8 : kHotDeltaMin;
+    if (!grow(h.rec, h.rec_cap, h.n_main + h.delta_cap, sizeof(HotRec))) {
+        h.enabled = false;
+        return PIE_OK;
+    }
+    hipLaunchKernelGGL(k_hot_scatter, dim3((unsigned)blocks), dim3(256), 0, s, c->d_fkey, c->d_end, c->d_pay, c->n, seg_len, h.cnt, h.rec, h.pos);
+    PIE_HIP(c, hipGetLastError());
+    PIE_HIP(c, hipMemsetAsync(h.delta_n, 0, sizeof(unsigned), s));
+    h.delta_bound = 0;
+    h.valid = true;
+    h.builds++;
     return PIE_OK;
 }
 
@@ -2072,7 +2171,7 @@ int run_row_list(pie_ctx* c, long long a, long long b, int32_t* out, size_t cap,
     hipLaunchKernelGGL(k_list_count<MODE>, dim3(blocks), dim3(256), 0, s, c->d_end, col2, c->n, rpb, a, b, sl.blk_count);
     hipLaunchKernelGGL(k_block_prefix, dim3(1), dim3(256), 0, s, sl.blk_count, blocks, c->d_blk_off, &c->d_summary->m);
     hipLaunchKernelGGL(k_list_write<MODE>, dim3(blocks), dim3(256), 0, s, c->d_end, col2, c->n, rpb, a, b,
-                       c->d_blk_off, sl.out_idx, c->cap_rows, c->d_key, c->d_fkey, ord_mirror_of(c));
+                       c->d_blk_off, sl.out_idx, c->cap_rows, c->d_key, c->d_fkey, ord_mirror_of(c), hot_mirror_of(c));
     PIE_HIP(c, hipGetLastError());
     PIE_HIP(c, hipMemcpyAsync(c->h_summary, c->d_summary, sizeof(Summary), hipMemcpyDeviceToHost, s));
     PIE_HIP(c, hipStreamSynchronize(s));
@@ -2371,12 +2470,18 @@ int batch_begin(pie_ctx* c, const pie_query* qs, int n_q, int msg_kind, int* msg
     }
     int rc = ord_batch ? PIE_OK : ensure_batch(c, lane);
     if (rc) return rc;
+    // the 1-byte pass reads the hot index instead of the key column; built here, on the main stream, the first time it can be
+    if (fine && !ord_batch && c->hix.enabled && !c->hix.valid && c->b_flight == 0) {
+        rc = hot_build(c);
+        if (rc) return rc;
+    }
     if (lane > 0 && c->lane_epoch[lane] != c->idle_epoch) { // see idle_epoch
         PIE_HIP(c, hipEventRecord(c->lane_event[lane][0], c->stream));
         PIE_HIP(c, hipStreamWaitEvent(s, c->lane_event[lane][0], 0));
         c->lane_epoch[lane] = c->idle_epoch;
     }
     b.fine_key = fine;
+    b.hot = fine && !ord_batch && c->hix.valid;
     b.dshift = c->bdshift;
     if (c->profiling && (c->scans_begun % (unsigned long long)c->profile_every) == 0) {
         if (c->ring_used == kEventRing) {
@@ -2445,6 +2550,14 @@ int batch_begin(pie_ctx* c, const pie_query* qs, int n_q, int msg_kind, int* msg
             if (!b.fallback[q] && nk[q] < mk) mk = nk[q];                                                               \
         }                                                                                                               \
         a.min_key = mk;                                                                                                 \
+        a.hot = nullptr; a.hot_lo = a.hot_main = 0; a.hot_delta_n = nullptr; a.hot_delta_cap = 0;                       \
+        if (b.hot && mk >= 1 && mk <= kFineKeyMax) { /* the suffix of bin mk and the delta, a wave per 2 x 64 records */ \
+            a.hot = c->hix.rec; a.hot_lo = c->hix.off[mk]; a.hot_main = c->hix.n_main;                                  \
+            a.hot_delta_n = c->hix.delta_n; a.hot_delta_cap = (unsigned)c->hix.delta_cap;                               \
+            const long long recs = a.hot_main - a.hot_lo + c->hix.delta_bound;                                          \
+            const long long want = (recs + 2 * kK1Threads - 1) / (2 * kK1Threads);                                     \
+            b.k1_blocks = (int)(want < 1 ? 1 : want < b.k1_blocks ? want : b.k1_blocks);                                \
+        }                                                                                                               \
         fill_batch_tables(c, b, qs, nk, a.tab);                                                                         \
         PIE_PROF_TICK(2);                                                                                               \
         if (ride) {                                                                                                     \
@@ -2669,7 +2782,7 @@ int batch_finish(pie_ctx* c, int* ready_out)
             b.union_part = !overflow;
             b.union_ok = !overflow;
             for (int q = 0; q < b.n_q; ++q) b.union_ok = b.union_ok && !b.fallback[q];
-            if (!b.ordered) choose_run_shift(c, us.cand, us.chunk_max, b.fine_key);
+            if (!b.ordered && !b.hot) choose_run_shift(c, us.cand, us.chunk_max, b.fine_key);
         }
         if (b.ev_index >= 0) PIE_HIP(c, hipEventRecord(c->ring[b.ev_index].e2, s));
     }
@@ -3238,6 +3351,7 @@ int pie_ctx_create(int device_id, pie_ctx** ctx_out)
     if (const char* v = getenv("PIE_K2_RIDE")) c->no_ride = atoi(v) == 0;
     if (const char* v = getenv("PIE_EXPIRED_COPY_TOTAL")) c->expired_copy_total = atoi(v) != 0;
     if (const char* v = getenv("PIE_ASYNC_MUTATIONS")) c->async_mutations = atoi(v) != 0;
+    if (const char* v = getenv("PIE_HOT_INDEX")) c->hix.enabled = atoi(v) != 0;
     if (const char* v = getenv("PIE_BATCH_LANES")) { const int l = atoi(v); if (l >= 0 && l <= kLaneMax) c->lanes_want = l; }
     if (const char* v = getenv("PIE_ORDER_BLOCK")) { const int b = atoi(v); if (b == 256 || b == 512 || b == 1024) c->order_block = b; }
     if (const char* v = getenv("PIE_RUN_SHIFT")) { const int r = atoi(v); if (r >= 0 && r <= 3) { c->run_shift = r; c->run_shift_pinned = true; } }
@@ -3369,6 +3483,7 @@ int pie_append_rows(pie_ctx* c, const int64_t* start, const int64_t* end, const 
         // burst costs tens of microseconds, not the half-dozen blocking calls of the general path below.
         if (c->n_flight || c->b_flight) return fail(c, PIE_E_STATE, "table change while a scan is in flight");
         if (old_n + (long long)k >= (1LL << 31) - 1) return fail(c, PIE_E_INVAL, "row count outside [0, 2^31 - 1)");
+        hot_reserve(c, (long long)k);
         if (c->async_mutations && !c->ord.valid) {
             // nothing to read back: user ids are checked here, the rows are staged and queued, the call returns (see AsyncStage)
             unsigned bad = 0;
@@ -3388,7 +3503,7 @@ int pie_append_rows(pie_ctx* c, const int64_t* start, const int64_t* end, const 
                                reinterpret_cast<const long long*>(a->d + k * 8), reinterpret_cast<const int*>(a->d + k * 16),
                                reinterpret_cast<const int*>(a->d + k * 20), (long long)k, old_n, n_users, c->d_start, c->d_end, c->d_user,
                                c->d_disc, c->d_key, c->key_base, c->key_shift, c->d_fkey, c->fkey_base, c->fkey_shift, c->d_pay,
-                               &c->d_summary->bad_rows);
+                               &c->d_summary->bad_rows, hot_mirror_of(c));
             PIE_HIP(c, hipGetLastError());
             PIE_HIP(c, hipEventRecord(a->ev, s));
             a->pending = true;
@@ -3417,7 +3532,7 @@ int pie_append_rows(pie_ctx* c, const int64_t* start, const int64_t* end, const 
                            reinterpret_cast<const long long*>(c->d_stage + k * 8), reinterpret_cast<const int*>(c->d_stage + k * 16),
                            reinterpret_cast<const int*>(c->d_stage + k * 20), (long long)k, old_n, n_users, c->d_start, c->d_end, c->d_user,
                            c->d_disc, c->d_key, c->key_base, c->key_shift, c->d_fkey, c->fkey_base, c->fkey_shift, c->d_pay,
-                           &c->d_summary->bad_rows);
+                           &c->d_summary->bad_rows, hot_mirror_of(c));
         // the ordered run takes rows that arrive in time order into the spare slots of their users' segments
         bool ord_kept = false;
         if (c->ord.valid && c->ord.rows == old_n && k <= (size_t)kOrdAppendMax && n_users <= c->ord.users && c->key_ok) {
@@ -3427,7 +3542,8 @@ int pie_append_rows(pie_ctx* c, const int64_t* start, const int64_t* end, const 
         PIE_HIP(c, hipGetLastError());
         PIE_HIP(c, hipMemcpyAsync(c->h_summary, c->d_summary, sizeof(Summary), hipMemcpyDeviceToHost, s));
         PIE_HIP(c, hipStreamSynchronize(s));
-        if (c->h_summary->bad_rows) { // the rows were written beyond n: the table itself is unchanged
+        if (c->h_summary->bad_rows) { // the rows were written beyond n: the table itself is unchanged (the hot index is not)
+            c->hix.valid = false;
             if (ord_kept) { // ... but some of them may sit in the run's spare slots
                 ord_invalidate(c);
                 c->ord.h_stale[0] = c->ord.h_stale[1] = 0;
@@ -3628,6 +3744,7 @@ int pie_set_end(pie_ctx* c, const int32_t* rows, const int64_t* new_end, size_t 
     for (size_t i = 0; i < k; ++i)
         if (rows[i] < 0 || rows[i] >= c->n) return fail(c, PIE_E_INVAL, "row %d outside the table", rows[i]);
     PIE_HIP(c, hipSetDevice(c->device));
+    hot_reserve(c, (long long)k);
     if (c->async_mutations && !c->ord.valid) { // queued, not waited for (see AsyncStage); the rows were checked above
         pie_ctx::AsyncStage* a = nullptr;
         int rca = async_stage(c, k * 12 + 64, &a);
@@ -3637,7 +3754,7 @@ int pie_set_end(pie_ctx* c, const int32_t* rows, const int64_t* new_end, size_t 
         PIE_HIP(c, hipMemcpyAsync(a->d, a->h, k * 12, hipMemcpyHostToDevice, c->stream));
         hipLaunchKernelGGL(k_set_end, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, c->stream, c->d_end,
                            reinterpret_cast<const int*>(a->d + k * 8), reinterpret_cast<const long long*>(a->d), (long long)k, c->n,
-                           c->d_key, c->key_base, c->key_shift, c->d_fkey, c->fkey_base, c->fkey_shift, ord_mirror_of(c));
+                           c->d_key, c->key_base, c->key_shift, c->d_fkey, c->fkey_base, c->fkey_shift, ord_mirror_of(c), hot_mirror_of(c));
         PIE_HIP(c, hipGetLastError());
         PIE_HIP(c, hipEventRecord(a->ev, c->stream));
         a->pending = true;
@@ -3652,7 +3769,7 @@ int pie_set_end(pie_ctx* c, const int32_t* rows, const int64_t* new_end, size_t 
     PIE_HIP(c, hipMemcpyAsync(c->d_stage, c->h_stage, k * 12, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(k_set_end, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, c->stream, c->d_end,
                        reinterpret_cast<const int*>(c->d_stage + k * 8), reinterpret_cast<const long long*>(c->d_stage), (long long)k, c->n,
-                       c->d_key, c->key_base, c->key_shift, c->d_fkey, c->fkey_base, c->fkey_shift, ord_mirror_of(c));
+                       c->d_key, c->key_base, c->key_shift, c->d_fkey, c->fkey_base, c->fkey_shift, ord_mirror_of(c), hot_mirror_of(c));
     PIE_HIP(c, hipGetLastError());
     c->key_dirty = true;
     PIE_HIP(c, hipStreamSynchronize(c->stream));
@@ -4683,6 +4800,9 @@ int pie_table_info_get(pie_ctx* c, pie_table_info* out)
     out->ordered_build_ms = c->ord.build_ms;
     out->ordered_builds = c->ord.builds;
     out->ordered_respreads = c->ord.respreads;
+    out->hot_rows = c->hix.valid ? (uint64_t)c->hix.n_main : 0u;
+    out->hot_bytes = (uint64_t)c->hix.rec_cap * sizeof(HotRec) + (uint64_t)c->hix.pos_cap * 4 + (uint64_t)c->hix.cnt_cap * 4 + (c->hix.d_off ? 129 * 8 + 4 : 0);
+    out->hot_builds = c->hix.builds;
     return PIE_OK;
 }
 
