@@ -1,0 +1,687 @@
+"""TEST INFRASTRUCTURE — a numpy model of the session table behind the C ABI, a seeded step generator over its mutators and
+readers, and the runner that drives a PieScan context and the model side by side (tests/test_gpu_model.py, tools/fuzz_gpu.py).
+
+Nothing here needs a GPU to import.  The model is the only source of expected values: scans come from
+oracle_py.scan_numpy (the lexsort restatement) on the model's columns, every CHECK_C_EVERY-th one is also compared with
+the C oracle, so a mistake shared by one oracle and the kernels cannot hide."""
+import os
+
+import numpy as np
+
+INT64_MIN = -(2 ** 63)
+INT64_MAX = 2 ** 63 - 1
+ALL = 2 ** 64 - 1
+HOUR = 3600 * 1000
+DAY = 24 * HOUR
+YEAR = 365 * DAY
+PIE_E_STATE = -6
+MAX_ROWS = 1 << 20
+CHECK_C_EVERY = 7
+
+KEY_MAX, FINE_KEY_MAX, KEY_HIST_BINS = 32767, 127, 4096
+
+# every way a reader call can be answered; test_model_sequences_reached_every_path wants each of them seen
+PATHS = ("general", "keyed_2byte", "keyed_1byte", "hot_clean", "hot_delta", "ordered_scan", "ordered_batch", "wide_pass",
+         "wide_fallback")
+
+
+# ------------------------------------------------------------------------------------------------ the key definition
+def key_of(e, base, shift, kmax=KEY_MAX):
+    """0 below `base`, else min(((e - base) >> shift) + 1, kmax).  Python ints: no overflow anywhere."""
+    e = int(e)
+    if e < base:
+        return 0
+    return min(((e - base) >> shift) + 1, kmax)
+
+
+def key_params(end):
+    """(key_base, key_shift, fkey_base, fkey_shift) as the table derives them at a full key build:
+    base = the smallest live `end`, shift = the smallest that keeps the largest below the clamp; the fine key's base = the
+    lower edge of the histogram bin (4096 bins of 8 keys) that holds the 90th percentile of the 15-bit keys of ALL rows
+    (tombstones are key 0), its shift the smallest that keeps the top occupied bin's upper edge below its clamp."""
+    end = np.asarray(end, np.int64)
+    live = end[end != INT64_MIN]
+    if live.size == 0:
+        return 0, 0, 0, 0
+    base, top = int(live.min()), int(live.max())
+    shift = 0
+    while shift < 63 and ((top - base) >> shift) >= KEY_MAX - 1:
+        shift += 1
+    keys = np.array([key_of(v, base, shift) for v in np.unique(end)], np.int64)
+    hist = np.zeros(KEY_HIST_BINS, np.int64)
+    np.add.at(hist, keys >> 3, np.unique(end, return_counts=True)[1])
+    want, cum, b = int(float(end.size) * 0.9), 0, 0
+    top_bin = int(np.nonzero(hist)[0].max())
+    while b < KEY_HIST_BINS - 1:
+        if cum + int(hist[b]) > want:
+            break
+        cum += int(hist[b])
+        b += 1
+    b = min(b, top_bin)
+    fbase = base if b == 0 else base + ((8 * b - 1) << shift)
+    fspan = base + ((8 * top_bin + 8) << shift) - fbase
+    fshift = 0
+    while fshift < 63 and (fspan >> fshift) >= FINE_KEY_MAX - 1:
+        fshift += 1
+    return base, shift, fbase, fshift
+
+
+# ------------------------------------------------------------------------------------------------ calendar months
+def add_months(ts, months, tz_offset_ms=0):
+    """JS `setMonth(getMonth() + months)` on a local Date at a fixed offset, vectorised: the month moves, the day of the
+    month is kept and overflows into the following month (Dec 31 + 2 -> "Feb 31" -> Mar 3), the time of day is kept."""
+    local = np.asarray(ts, np.int64) + int(tz_offset_ms)
+    days = np.floor_divide(local, DAY)
+    tod = local - days * DAY
+    date = days.astype("datetime64[D]")
+    month = date.astype("datetime64[M]")
+    dom = (date - month.astype("datetime64[D]")).astype(np.int64)
+    moved = (month + int(months)).astype("datetime64[D]").astype(np.int64) + dom
+    return moved * DAY + tod - int(tz_offset_ms)
+
+
+# ------------------------------------------------------------------------------------------------ the model
+class TableModel:
+    """start / end / user / disc and the user and discipline counts; every table operation of include/pie_scan.h restated."""
+
+    def __init__(self, oracle):
+        self.oracle = oracle
+        self.scans = 0
+        self.load(np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, np.int32), np.zeros(0, np.int32), 1, 1)
+
+    @property
+    def n(self):
+        return self.start.size
+
+    def load(self, start, end, user, disc, U, D):
+        self.start, self.end = np.array(start, np.int64), np.array(end, np.int64)
+        self.user, self.disc = np.array(user, np.int32), np.array(disc, np.int32)
+        self.U, self.D = int(U), int(D)
+
+    def columns(self):
+        return self.start, self.end, self.user, self.disc
+
+    def lim(self):
+        return ALL if self.D >= 64 else (1 << self.D) - 1
+
+    # ---- mutators
+    def append_rows(self, start, end, user, disc, U):
+        self.start = np.concatenate([self.start, np.asarray(start, np.int64)])
+        self.end = np.concatenate([self.end, np.asarray(end, np.int64)])
+        self.user = np.concatenate([self.user, np.asarray(user, np.int32)])
+        self.disc = np.concatenate([self.disc, np.asarray(disc, np.int32)])
+        self.U = int(U)
+
+    def set_end(self, rows, new_end):
+        self.end[np.asarray(rows, np.int64)] = np.asarray(new_end, np.int64)
+
+    def _tombstone(self, sel):
+        rows = np.nonzero(sel & (self.end != INT64_MIN))[0].astype(np.int32)
+        self.end[rows] = INT64_MIN
+        return rows
+
+    def delete_user(self, u):
+        if not 0 <= u < self.U:
+            return np.zeros(0, np.int32)
+        return self._tombstone(self.user == u)
+
+    def prune_before(self, cutoff):
+        return self._tombstone(self.start < cutoff)
+
+    def retention_purge(self, now, months, tz_offset_ms=0):
+        return self._tombstone(add_months(self.start, months, tz_offset_ms) <= now)
+
+    def shard_rows(self, rank, world):
+        owner = np.array([self.oracle.shard_of(u, world) for u in range(self.U)], np.int32)
+        return owner, np.nonzero(owner[self.user] == rank)[0] if self.n else np.zeros(0, np.int64)
+
+    def shard_table(self, rank, world):
+        """Rows of the users that hash to `rank` stay, in table order; those users are re-numbered densely, ascending."""
+        owner, rows = self.shard_rows(rank, world)
+        users = np.nonzero(owner == rank)[0]
+        local = np.full(self.U, -1, np.int32)
+        local[users] = np.arange(users.size, dtype=np.int32)
+        self.start, self.end, self.disc = self.start[rows], self.end[rows], self.disc[rows]
+        self.user = local[self.user[rows]]
+        self.U = max(int(users.size), 1)
+        return self.n, self.U
+
+    # ---- readers
+    def scan(self, now, cutoff, mask):
+        return self.scan_many([(now, cutoff, mask)])[0]
+
+    def scan_many(self, queries):
+        """[(counts, offsets, idx)] per (now, cutoff, mask); bits of the mask at or above D are ignored.  Sparse queries
+        share one pre-filter (rows with end <= the smallest of their `now`s are selected by none of them; the candidates stay
+        in row order, so the restatement's tie order by row index is unchanged): the restatement then sorts only those."""
+        o, lim = self.oracle, self.lim()
+        out = [None] * len(queries)
+        live = int(np.count_nonzero(self.end != INT64_MIN))
+        sparse = []
+        for qi, (now, cutoff, mask) in enumerate(queries):
+            if self.n > 50000 and int(np.count_nonzero(self.end > now)) * 8 < max(live, 1):
+                sparse.append(qi)
+                continue
+            out[qi] = o.scan_numpy(self.start, self.end, self.user, self.disc, self.U, now, cutoff, mask & lim)
+        if sparse:
+            cand = np.nonzero(self.end > min(queries[qi][0] for qi in sparse))[0]
+            cs, ce, cu, cd = self.start[cand], self.end[cand], self.user[cand], self.disc[cand]
+            for qi in sparse:
+                now, cutoff, mask = queries[qi]
+                c, off, idx = o.scan_numpy(cs, ce, cu, cd, self.U, now, cutoff, mask & lim)
+                out[qi] = (c, off, cand[idx].astype(np.int32))
+        for qi, (now, cutoff, mask) in enumerate(queries):
+            self.scans += 1
+            if self.scans % CHECK_C_EVERY == 0:   # the C oracle on the whole table: the two restatements must agree
+                for name, a, b in zip(("counts", "offsets", "idx"), out[qi], o.scan(*self.columns(), self.U, now, cutoff, mask & lim)):
+                    assert a.dtype == b.dtype and np.array_equal(a, b), ("the oracles disagree", name, queries[qi])
+        return out
+
+    def expired_queue(self, prev_now, now):
+        return np.nonzero((self.end > prev_now) & (self.end <= now))[0].astype(np.int32)
+
+    def archive_queue(self, now, window_ms):
+        """Groups (users) whose earliest start over their non-tombstoned rows is at least window_ms old, in order of first
+        appearance; their non-tombstoned rows in table order."""
+        rows = np.nonzero(self.end != INT64_MIN)[0]
+        if rows.size == 0:
+            return np.zeros(0, np.int32)
+        g = self.user[rows]
+        earliest = np.full(self.U, INT64_MAX, np.int64)
+        np.minimum.at(earliest, g, self.start[rows])
+        first = np.full(self.U, INT64_MAX, np.int64)
+        np.minimum.at(first, g, rows)
+        qual = np.array([e != INT64_MAX and int(now) - int(e) >= int(window_ms) for e in earliest.tolist()], bool)
+        keep = rows[qual[g]]
+        return keep[np.lexsort((keep, first[self.user[keep]]))].astype(np.int32)
+
+
+# ------------------------------------------------------------------------------------------------ hand-made edge tables
+LATTICE_SHIFT = 12   # pitch 4096 ms
+LATTICE_TOP = 20000  # lattice index of the largest end
+
+
+def lattice_table(oracle, seed=1):
+    """A few thousand rows whose `end` values all lie on base + j * 2^LATTICE_SHIFT, j in [0, LATTICE_TOP].
+
+    The pitch follows from the key definition: key_shift is the smallest s with (span >> s) < 32766 and
+    span = LATTICE_TOP << LATTICE_SHIFT, so with 16383 <= LATTICE_TOP < 32766 it is exactly LATTICE_SHIFT: the pitch equals
+    the 15-bit key's bin width (the largest shift this span can produce), key(base + j * pitch) = j + 1, and EVERY lattice value
+    is the lower edge of a bin.  The fine key's base is base + ((8 b - 1) << key_shift) for the histogram bin b of the 90th
+    percentile: lattice index 8 b - 1.  The top of the lattice (indices LATTICE_TOP - 400 .. LATTICE_TOP, every one occupied)
+    holds four fifths of the rows, so that index is an occupied value; the fine key's shift is at most key_shift (its range is a
+    few dozen pitches over 126 bins), so every lattice value at or above its base is the lower edge of a fine bin too.
+    -> (start, end, user, disc, U, D, occupied lattice values ascending)."""
+    rng = np.random.default_rng(seed)
+    U, D = 53, 32
+    pitch = 1 << LATTICE_SHIFT
+    base = oracle.T0_MS - LATTICE_TOP * pitch
+    low = np.unique(np.concatenate([[0], rng.choice(np.arange(1, LATTICE_TOP - 3000), 150, replace=False)]))
+    top = np.arange(LATTICE_TOP - 400, LATTICE_TOP + 1)
+    j = np.concatenate([np.repeat(low, 4), np.repeat(top, 6)])
+    j = j[rng.permutation(j.size)]
+    n = j.size
+    end = (base + j * pitch).astype(np.int64)
+    start = (oracle.T0_MS - 70 * DAY + rng.integers(0, 69 * DAY, n)).astype(np.int64)
+    user = ((np.arange(n) * 7 + j) % U).astype(np.int32)   # rows of one value get different users and disciplines
+    disc = ((np.arange(n) * 5 + j // 3) % D).astype(np.int32)
+    values = (base + np.concatenate([low, top]) * pitch).astype(np.int64)
+    return start, end, user, disc, U, D, values
+
+
+def tie_table(oracle, seed=2):
+    """Per-user runs of equal starts: user 0 has 150 rows on one start (more than a wave, more than the 16-record direct
+    bucket), user 1 has 70 on another and 20 on a third, the rest a few equal starts each; disciplines include 0, 63 and
+    values outside [0, 64).  -> (start, end, user, disc, U, D)."""
+    rng = np.random.default_rng(seed)
+    U, D = 47, 64
+    t0 = oracle.T0_MS
+    starts = [np.full(150, t0 - 40 * DAY), np.full(70, t0 - 30 * DAY), np.full(20, t0 - 30 * DAY + 1)]
+    users = [np.zeros(150), np.ones(70), np.ones(20)]
+    n_rest = 2400
+    pool = t0 - 50 * DAY + rng.integers(0, 60, n_rest) * (DAY // 2)      # 60 distinct starts for everybody else
+    starts.append(pool)
+    users.append(rng.integers(2, U, n_rest))
+    start, user = np.concatenate(starts).astype(np.int64), np.concatenate(users).astype(np.int32)
+    p = rng.permutation(start.size)
+    start, user = start[p], user[p]
+    n = start.size
+    end = (t0 + rng.integers(-2 * HOUR, 10 * HOUR, n)).astype(np.int64)
+    big = np.nonzero(user < 2)[0]
+    end[big[::4]] = t0 + 11 * HOUR   # a quarter of the long tie runs stays live for top-of-range queries
+    disc = rng.choice(np.array([0, 0, 1, 5, 31, 32, 62, 63, 63, 64, 65, 200, -1, -7], np.int32), n).astype(np.int32)
+    return start, end, user, disc, U, D
+
+
+# ------------------------------------------------------------------------------------------------ the seeded chain
+def same(got, want, tag):
+    for name, a, b in zip(("counts", "offsets", "idx"), got, want):
+        assert a.dtype == b.dtype and np.array_equal(a, b), (tag, name)
+
+
+def ctx_with_env(pie, hot, async_mut):
+    """A context created under PIE_HOT_INDEX / PIE_ASYNC_MUTATIONS; the environment is restored before returning."""
+    want = {"PIE_HOT_INDEX": "1" if hot else "0", "PIE_ASYNC_MUTATIONS": "1" if async_mut else "0"}
+    old = {k: os.environ.get(k) for k in want}
+    os.environ.update(want)
+    try:
+        return pie.PieScan(0)
+    finally:
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+
+
+def chain_config(seed):
+    rng = np.random.default_rng([seed, 0xC0F])
+    return {
+        "n": int(rng.choice([1, 65, 4099, 70001, 300007, 1 << 20])), "U": int(rng.choice([1, 3, 997, 40009])),
+        "D": int(rng.choice([1, 7, 32, 64])), "flags": int(rng.integers(8)), "heavy": bool(rng.random() < 0.3),
+        "hourly": bool(rng.random() < 0.3), "hot": int(rng.integers(2)), "ordered": int(rng.integers(3)),
+        "lanes": int(rng.integers(1, 5)), "async": int(rng.integers(2)), "steps": int(rng.integers(30, 61)),
+        "gen_seed": int(rng.integers(1, 2 ** 60)),
+    }
+
+
+class Chain:
+    """One seeded chain: a table, a context configuration, 30 to 60 steps.  run() raises at the first difference."""
+
+    MUTATORS = ("set_end", "set_end", "set_end", "append", "append", "delete_user", "prune", "retention", "shard", "flood")
+    READERS = ("scan", "scan", "batch", "batch", "batch", "wide", "pipeline", "expired", "archive")
+
+    def __init__(self, pie, oracle, seed, cfg=None, log=None):
+        self.pie, self.oracle, self.seed = pie, oracle, seed
+        self.cfg = dict(chain_config(seed), **(cfg or {}))
+        self.rng = np.random.default_rng([seed, 0x57E9])
+        self.rng_after = np.random.default_rng([seed, 0xAF7E])   # the batch that follows every append draws from its own stream
+        self.m = TableModel(oracle)
+        self.paths = {}
+        self.both_valid_at_set_end = False
+        self.rebuilt_after_drop = False
+        self.sharded = False
+        self.touched = True       # a touch or append since hot_builds last rose (nothing is built yet)
+        self.builds_seen, self.dropped = 0, False
+        self.log = log
+        self.t0 = oracle.T0_MS
+
+    # ---- set-up
+    def make_table(self):
+        c, rng, o = self.cfg, self.rng, self.oracle
+        n, U, D = c["n"], c["U"], c["D"]
+        s, e, u, d = [a.copy() for a in o.gen(c["gen_seed"], n, 0, n, U, D, c["flags"])]
+        if c["heavy"]:
+            u = np.where(rng.random(n) < 0.5, int(rng.integers(U)), u).astype(np.int32)
+        if c["hourly"]:
+            e, s = (e // HOUR) * HOUR, (s // HOUR) * HOUR
+        self.m.load(s, e, u, d, U, D)
+        self.mask = ALL if rng.random() < 0.4 else int(rng.integers(0, 2 ** 63)) | (int(rng.integers(0, 2)) << 63) | 1
+
+    def run(self):
+        self.make_table()
+        c = self.cfg
+        ctx = self.ctx = ctx_with_env(self.pie, c["hot"], c["async"])
+        try:
+            ctx.set_ordered_run(c["ordered"])
+            ctx.set_batch_lanes(c["lanes"])
+            ctx.load_columns(*self.m.columns(), self.m.U)
+            ctx.set_disciplines(self.mask, self.m.D)
+            self.check_columns("load")
+            for step in range(c["steps"]):
+                # the chain opens with readers (they build the ordered run and the hot index), then mixes
+                kind = self.rng.choice(self.READERS) if step < 3 or self.rng.random() < 0.5 else self.rng.choice(self.MUTATORS)
+                if self.log:
+                    self.log("seed %d step %d %s n %d U %d" % (self.seed, step, kind, self.m.n, self.m.U))
+                getattr(self, "do_" + str(kind))("seed %d step %d %s" % (self.seed, step, kind))
+                self.watch_index()
+        finally:
+            ctx.close()
+        return self
+
+    # ---- bookkeeping
+    def saw(self, path):
+        assert path in PATHS, path
+        self.paths[path] = self.paths.get(path, 0) + 1
+
+    def watch_index(self):
+        info = self.ctx.table_info()
+        if info["hot_builds"] > self.builds_seen:
+            if self.dropped:
+                self.rebuilt_after_drop = True
+            self.builds_seen, self.dropped, self.touched = info["hot_builds"], False, False
+        elif self.builds_seen and info["hot_rows"] == 0:
+            self.dropped = True
+        return info
+
+    def check_columns(self, tag):
+        assert self.ctx.n == self.m.n and self.ctx.n_users == self.m.U, (tag, "shape")
+        assert int(self.ctx.stats()["rows"]) == self.m.n and int(self.ctx.stats()["users"]) == self.m.U, (tag, "stats shape")
+        for name, got, want in zip(("start", "end", "user", "disc"), self.ctx.read_columns(), self.m.columns()):
+            assert got.dtype == want.dtype and np.array_equal(got, want), (tag, "column " + name)
+
+    # ---- queries: sparse top-of-range, below the 90th percentile, dense, above everything; on values and next to them
+    def ends_in_range(self):
+        e = self.m.end
+        e = e[(e != INT64_MIN) & (e < self.t0 + YEAR)]
+        return e if e.size else np.array([self.t0], np.int64)
+
+    def pick_now(self, kind):
+        rng, e = self.rng, self.ends_in_range()
+        if kind == "above":      # at or above every end: selects nothing
+            top = int(self.m.end.max()) if self.m.n else 0
+            return top if top == INT64_MAX or rng.random() < 0.5 else int(rng.integers(top, min(top + DAY, INT64_MAX)))
+        if kind == "far":        # above the range the keys were fitted for (rows re-ended far ahead are still live there)
+            return int(rng.choice([INT64_MAX - 1, int(e.max()), self.t0 + 10 * YEAR, self.t0 + 11 * YEAR]))
+        if kind == "dense":
+            return int(rng.choice([INT64_MIN, int(np.quantile(e, 0.3)), int(e.min()) - 1]))
+        if kind == "below_p90":
+            return int(np.quantile(e, float(rng.uniform(0.80, 0.895))))
+        lo = int(np.quantile(e, 0.97))
+        now = int(rng.integers(lo, int(e.max()) + 1))
+        r = rng.random()
+        if r < 0.3:      # exactly on a value of the column, or one below it
+            v = e[e >= lo]
+            now = int(v[int(rng.integers(v.size))]) - int(rng.integers(2))
+        return now
+
+    def pick_query(self, kind):
+        rng, m = self.rng, self.m
+        cutoff = int(rng.choice([INT64_MIN, self.t0 - 61 * DAY, int(m.start[int(rng.integers(m.n))]) if m.n else 0]))
+        mask = ALL if rng.random() < 0.4 else int(rng.integers(0, 2 ** 63)) | (int(rng.integers(0, 2)) << 63)
+        return self.pick_now(kind), cutoff, mask
+
+    def query_set(self, k, dense=True):
+        """k queries of all four kinds (k >= 4: at least one of each; smaller sets take them in turn)."""
+        kinds = ["sparse", "below_p90", "dense", "above", "far"] if dense else ["sparse", "above", "sparse", "far"]
+        qs = [self.pick_query(kinds[i] if i < len(kinds) else "sparse") for i in range(k)]
+        if k < len(kinds):
+            qs = [self.pick_query(kinds[int(self.rng.integers(len(kinds)))]) for _ in range(k)]
+        order = self.rng.permutation(k)
+        return [qs[int(i)] for i in order]
+
+    # ---- readers
+    def do_scan(self, tag):
+        ctx, m = self.ctx, self.m
+        for kind in ("sparse", "sparse", "sparse", "below_p90", "dense", "above"):
+            now = self.pick_now(kind)
+            cutoff = int(self.rng.choice([INT64_MIN, self.t0 - 61 * DAY]))
+            want = m.scan(now, cutoff, self.mask)
+            reps = 3 if kind == "sparse" else 1      # repeats let the adaptive forms engage
+            for _ in range(reps):
+                same(ctx.scan(now, cutoff), want, (tag, kind, now, cutoff))
+                v = ctx.stats()["k1_variant"]
+                self.saw("ordered_scan" if v & 0x2000 else "keyed_1byte" if v & 0x800 else "keyed_2byte" if v & 0x400 else "general")
+            for u in {0, m.U - 1, int(self.rng.integers(m.U)), -1, m.U}:
+                feed = want[2][want[1][u]:want[1][u + 1]] if 0 <= u < m.U else np.zeros(0, np.int32)
+                assert np.array_equal(ctx.read_user_feed(u), feed), (tag, kind, "feed of user", u)
+
+    def batch_path(self, hot_rows_at_begin):
+        v = self.ctx.stats()["k1_variant"]
+        if v == 0:
+            return "general"
+        if v & 0x2000:
+            return "ordered_batch"
+        if not v & 0x800:
+            return "keyed_2byte"
+        if not hot_rows_at_begin:
+            return "keyed_1byte"
+        return "hot_delta" if self.touched else "hot_clean"
+
+    def check_batch_results(self, tag, qs, wants, which=None):
+        ctx, m = self.ctx, self.m
+        for qi in (range(len(qs)) if which is None else which):
+            same(ctx.batch_read_results(qi), wants[qi], (tag, "query", qi, qs[qi]))
+        for _ in range(3):
+            qi, u = int(self.rng.integers(len(qs))), int(self.rng.integers(m.U))
+            w = wants[qi]
+            assert np.array_equal(ctx.batch_read_user_feed(qi, u), w[2][w[1][u]:w[1][u + 1]]), (tag, "feed", qi, u)
+
+    def check_union(self, tag, un, wants, wide):
+        """Every query's list is a filter of the union, in order; no union row without a query, no bit beyond the batch."""
+        uoff, rows, masks = un
+        nq = len(wants)
+        bits = masks.reshape(rows.size, (nq + 63) // 64)
+        any_bit = np.zeros(rows.size, bool)
+        for qi, w in enumerate(wants):
+            sel = ((bits[:, qi // 64] >> np.uint64(qi % 64)) & np.uint64(1)) == 1
+            any_bit |= sel
+            csum = np.concatenate([[0], np.cumsum(sel)])
+            assert np.array_equal(rows[sel], w[2]) and np.array_equal(csum[uoff], w[1]), (tag, "union", "wide" if wide else "", qi)
+        assert np.all(any_bit), (tag, "a union row no query selected")
+        if nq % 64:
+            assert not np.any(bits[:, nq // 64] >> np.uint64(nq % 64)), (tag, "a query bit beyond the batch")
+
+    def one_batch(self, tag, qs):
+        ctx = self.ctx
+        wants = self.m.scan_many(qs)
+        ctx.scan_batch_begin(qs)
+        hot_rows = self.watch_index()["hot_rows"]
+        ms = ctx.scan_batch_finish()
+        assert list(ms) == [int(w[2].size) for w in wants], (tag, "M per query")
+        self.saw(self.batch_path(hot_rows))
+        un = ctx.batch_read_union()
+        if un is not None:
+            self.check_union(tag, un, wants, False)
+        self.check_batch_results(tag, qs, wants)
+        return un is not None
+
+    def do_batch(self, tag):
+        k = int(self.rng.choice([1, 3, 16, 33, 64]))
+        self.one_batch((tag, k, "mixed"), self.query_set(k))
+        # the same shape without the dense query: a batch that keeps its union
+        self.one_batch((tag, k, "sparse"), self.query_set(k, dense=False))
+
+    def one_wide(self, tag, qs):
+        ctx = self.ctx
+        wants = self.m.scan_many(qs)
+        ctx.scan_wide_begin(qs)
+        self.watch_index()
+        ms = ctx.scan_wide_finish()
+        assert ms == [int(w[2].size) for w in wants], (tag, "M per query")
+        un = ctx.batch_read_union_wide()
+        v = ctx.stats()["k1_variant"]
+        if un is not None:
+            self.saw("wide_pass")
+            self.check_union(tag, un, wants, True)
+        else:
+            self.saw("ordered_batch" if v & 0x2000 else "wide_fallback")
+        # per query: all of them on small tables, a spread of them on large ones (the union check covers every query)
+        which = None if self.m.n <= 5000 else sorted({0, len(qs) - 1} | {int(i) for i in self.rng.integers(0, len(qs), 24)})
+        self.check_batch_results(tag, qs, wants, which)
+
+    def do_wide(self, tag):
+        k = int(self.rng.choice([65, 200, 512]))
+        self.one_wide((tag, k, "mixed"), self.query_set(k))
+        self.one_wide((tag, k, "sparse"), self.query_set(k, dense=False))
+
+    def do_pipeline(self, tag):
+        """Batches begun until the lanes are full, one wide batch among them; one more begin and a mutation are refused with
+        PIE_E_STATE; everything is finished in the order it was begun."""
+        ctx, rng = self.ctx, self.rng
+        begun = []
+        wide_at = int(rng.integers(0, 3))
+        while ctx.batch_room() > 0:
+            assert len(begun) < 12, (tag, "more than twelve batches in flight")
+            wide = len(begun) == wide_at
+            qs = self.query_set(int(rng.choice([70, 130])) if wide else int(rng.choice([3, 5, 16, 40])), dense=len(begun) == 1)
+            (ctx.scan_wide_begin if wide else ctx.scan_batch_begin)(qs)
+            begun.append((wide, qs, self.watch_index()["hot_rows"]))
+        for call in (lambda: ctx.scan_batch_begin(begun[0][1] if not begun[0][0] else begun[1][1]),
+                     lambda: ctx.set_end(np.zeros(1, np.int32), np.full(1, self.t0, np.int64)),
+                     lambda: ctx.append_rows(self.m.start[:1], self.m.end[:1], self.m.user[:1], self.m.disc[:1], self.m.U)):
+            n_before = ctx.n
+            try:
+                call()
+            except self.pie.PieError as exc:
+                assert exc.code == PIE_E_STATE, (tag, "refused with", exc.code)
+                ctx.n = n_before
+            else:
+                raise AssertionError((tag, "a call the header refuses while batches are in flight went through"))
+        for k, (wide, qs, hot_rows) in enumerate(begun):
+            wants = self.m.scan_many(qs)
+            if wide:
+                try:
+                    ctx.scan_batch_finish()
+                except self.pie.PieError as exc:   # the oldest batch is wide: nothing consumed
+                    assert exc.code == PIE_E_STATE, (tag, "batch finish of a wide batch", exc.code)
+                else:
+                    raise AssertionError((tag, "pie_scan_batch_finish took a wide batch"))
+                ms = ctx.scan_wide_finish()
+                un = ctx.batch_read_union_wide()
+                self.saw("wide_pass" if un is not None else "ordered_batch" if ctx.stats()["k1_variant"] & 0x2000 else "wide_fallback")
+            else:
+                ms = list(ctx.scan_batch_finish())
+                un = ctx.batch_read_union()
+                self.saw(self.batch_path(hot_rows))
+            assert ms == [int(w[2].size) for w in wants], (tag, "batch", k, "M per query")
+            if un is not None:
+                self.check_union((tag, "batch", k), un, wants, wide)
+            self.check_batch_results((tag, "batch", k), qs, wants, sorted({0, len(qs) - 1, int(rng.integers(len(qs)))}))
+        assert ctx.batch_room() >= 3, (tag, "room after the burst")
+
+    def do_expired(self, tag):
+        now = self.pick_now(str(self.rng.choice(["sparse", "below_p90", "above", "dense"])))
+        prev = now - int(self.rng.integers(0, 3 * DAY)) if now > INT64_MIN + 4 * DAY else INT64_MIN
+        assert np.array_equal(self.ctx.expired_queue(prev, now), self.m.expired_queue(prev, now)), (tag, prev, now)
+
+    def do_archive(self, tag):
+        m = self.m
+        if m.n > 300007:
+            return self.do_expired(tag)
+        now = int(self.rng.choice([self.t0, self.t0 - 100 * DAY, self.t0 - 119 * DAY, int(m.start[int(self.rng.integers(m.n))]) if m.n else 0, 2 ** 62, INT64_MIN + 5]))
+        win = int(self.rng.choice([0, HOUR, 12 * HOUR, 30 * DAY, 2 ** 62]))
+        assert np.array_equal(self.ctx.archive_queue(now, win), m.archive_queue(now, win)), (tag, now, win)
+
+    # ---- mutators
+    def mutated(self, tag, touch):
+        if touch:
+            self.touched = True
+        self.check_columns(tag)
+
+    def apply_set_end(self, tag, rows, ne):
+        info = self.ctx.table_info()
+        if info["ordered_rows"] > 0 and info["hot_rows"] > 0:
+            self.both_valid_at_set_end = True
+        self.ctx.set_end(rows, ne)
+        self.m.set_end(rows, ne)
+        self.mutated(tag, True)
+
+    def do_set_end(self, tag):
+        rng, m, t0 = self.rng, self.m, self.t0
+        if m.n == 0:
+            return
+        e = m.end
+        parts = []
+
+        def take(pool, k, values):
+            pool = np.asarray(pool)
+            if pool.size:
+                r = rng.choice(pool, min(k, pool.size), replace=False)
+                parts.append((r, values(r.size)))
+
+        k = int(rng.choice([1, 7, 200, 3000]))
+        kinds = rng.choice(["raise", "held", "tomb", "revive", "far", "any"], 3, replace=False)
+        for kind in kinds:
+            if kind == "raise":      # rows far below the index's range, into it
+                take(np.nonzero((e != INT64_MIN) & (e < t0 - 30 * DAY))[0], k, lambda c: t0 + rng.integers(-6 * HOUR, 12 * HOUR, c))
+            elif kind == "held":     # rows it holds, up and down
+                take(np.nonzero(e > t0 - 12 * HOUR)[0], k, lambda c: t0 + rng.integers(-20 * DAY, 12 * HOUR, c))
+            elif kind == "tomb":
+                take(np.nonzero(e != INT64_MIN)[0], max(k // 4, 1), lambda c: np.full(c, INT64_MIN))
+            elif kind == "revive":
+                take(np.nonzero(e == INT64_MIN)[0], k, lambda c: t0 + rng.integers(-HOUR, 6 * HOUR, c))
+            elif kind == "far":      # far above the range the keys were fitted for
+                take(np.arange(m.n), max(k // 8, 2), lambda c: rng.choice(np.array([t0 + 10 * YEAR, INT64_MAX, t0 + 10 * YEAR + 1], np.int64), c))
+            else:
+                take(np.arange(m.n), k, lambda c: rng.integers(t0 - 200 * DAY, t0 + 50 * DAY, c))
+        if not parts:
+            take(np.arange(m.n), k, lambda c: rng.integers(t0 - 200 * DAY, t0 + 50 * DAY, c))
+        rows = np.concatenate([p[0] for p in parts]).astype(np.int32)
+        ne = np.concatenate([p[1] for p in parts]).astype(np.int64)
+        _, first = np.unique(rows, return_index=True)   # one value per row in a call
+        first.sort()
+        rows, ne = rows[first], ne[first]
+        twice = rng.integers(0, rows.size, max(rows.size // 10, 1))   # the same row again, with the same value
+        at = rng.permutation(rows.size + twice.size)
+        rows, ne = np.concatenate([rows, rows[twice]])[at], np.concatenate([ne, ne[twice]])[at]
+        self.apply_set_end(tag, rows, ne)
+
+    def do_flood(self, tag):
+        """Enough touches in one call to pass the delta's bound on the second (the index is dropped and rebuilt)."""
+        m = self.m
+        if m.n < 70001:
+            return self.do_set_end(tag)
+        rows = self.rng.choice(m.n, 40000, replace=False).astype(np.int32)
+        ne = (self.t0 + self.rng.integers(-6 * HOUR, 12 * HOUR, rows.size)).astype(np.int64)
+        self.apply_set_end(tag, rows, ne)
+
+    def do_append(self, tag):
+        rng, m, t0 = self.rng, self.m, self.t0
+        mode = str(rng.choice(["ordered", "ordered", "late", "burst", "users"]))
+        k = int(rng.choice([1, 40, 1500]))
+        if mode == "burst":          # more rows than the table holds: the columns are re-allocated
+            k = m.n + 1
+        if m.n + k > MAX_ROWS:
+            return self.do_set_end(tag)
+        U = m.U + (int(rng.integers(1, 40)) if mode == "users" else 0)
+        top = int(m.start.max()) if m.n else t0
+        if mode == "late":
+            s2 = top - rng.integers(0, 20 * HOUR, k)
+        else:
+            s2 = top + np.sort(rng.integers(0, 4000, k))
+        s2 = s2.astype(np.int64)
+        e2 = s2 + rng.integers(-2 * DAY, DAY, k)
+        e2 = np.where(rng.random(k) < 0.5, t0 + rng.integers(-12 * HOUR, 12 * HOUR, k), e2).astype(np.int64)
+        u2, d2 = rng.integers(0, U, k).astype(np.int32), rng.integers(0, m.D, k).astype(np.int32)
+        if mode == "users":
+            u2[-1] = U - 1
+        self.ctx.append_rows(s2, e2, u2, d2, U)
+        m.append_rows(s2, e2, u2, d2, U)
+        self.mutated((tag, mode, k), True)
+        # a top-of-range batch at once: an append that re-allocated has dropped the hot index and this batch rebuilds it, so
+        # that the next append, which lands in place, is mirrored into a live index and read back from it by the batch after it
+        main, self.rng = self.rng, self.rng_after
+        try:
+            self.one_batch((tag, mode, k, "batch after the append"), self.query_set(16, dense=False))
+        finally:
+            self.rng = main
+
+    def listed(self, tag, got, want):
+        assert got.dtype == want.dtype and np.array_equal(got, want), (tag, "rows listed")
+        self.mutated(tag, False)
+
+    def do_delete_user(self, tag):
+        m = self.m
+        u = int(self.rng.integers(-1, m.U + 1))
+        if m.n and self.rng.random() < 0.3:
+            u = int(np.bincount(m.user, minlength=m.U).argmax())
+        self.listed((tag, u), self.ctx.delete_user(u), m.delete_user(u))
+
+    def do_prune(self, tag):
+        m = self.m
+        cutoff = int(np.quantile(m.start, float(self.rng.uniform(0, 0.05)))) + int(self.rng.integers(2)) if m.n else 0
+        self.listed((tag, cutoff), self.ctx.prune_before(cutoff), m.prune_before(cutoff))
+
+    def do_retention(self, tag):
+        m = self.m
+        months, tz = int(self.rng.choice([1, 2, 3])), int(self.rng.choice([0, 0, 330 * 60000, -5 * HOUR]))
+        first = int(m.start.min()) if m.n else self.t0
+        now = int(add_months(np.array([first], np.int64), months, tz)[0]) + int(self.rng.integers(-DAY, 4 * DAY))
+        self.listed((tag, now, months, tz), self.ctx.retention_purge(now, months, tz), m.retention_purge(now, months, tz))
+
+    def do_shard(self, tag):
+        m = self.m
+        world = int(self.rng.choice([2, 3]))
+        rank = int(self.rng.integers(world))
+        if self.sharded or m.U < 3 or m.shard_rows(rank, world)[1].size == 0:
+            return self.do_delete_user(tag)
+        self.sharded = True
+        got = self.ctx.shard_table(rank, world)
+        assert got == m.shard_table(rank, world), (tag, "shard shape", got)
+        self.ctx.set_disciplines(self.mask, m.D)
+        self.mutated((tag, rank, world), True)
+
+
+def run_chain(pie, oracle, seed, cfg=None, log=None):
+    return Chain(pie, oracle, seed, cfg, log).run()

@@ -1,0 +1,94 @@
+"""CPU self-checks of tests/table_model.py: the model's scans and mutators against the C oracle on chains of mutations, and the
+lattice table's values against the bin edges of the documented key definition."""
+import numpy as np
+import pytest
+
+import table_model as T
+from table_model import ALL, DAY, HOUR, INT64_MIN
+
+
+def test_model_imports_without_a_gpu():
+    assert len(T.PATHS) == 9 and T.chain_config(3) == T.chain_config(3) and T.chain_config(3) != T.chain_config(4)
+
+
+@pytest.mark.parametrize("seed", [1, 2, 3])
+def test_model_scans_match_the_c_oracle_over_mutations(oracle, seed):
+    rng = np.random.default_rng(seed)
+    n, U, D = 60011, (3, 211, 997)[seed - 1], (7, 32, 64)[seed - 1]
+    t0 = oracle.T0_MS
+    m = T.TableModel(oracle)
+    m.load(*oracle.gen(seed, n, 0, n, U, D, seed), U, D)
+
+    def check(tag):
+        qs = [(t0 - 6 * HOUR, t0 - 61 * DAY, ALL), (t0 - 30 * DAY, INT64_MIN, 0x5555555555555555), (INT64_MIN, INT64_MIN, 1 << 63 | 1),
+              (int(m.end.max()), INT64_MIN, ALL), (int(m.end[m.end != INT64_MIN][7]) - 1, int(m.start[9]), ALL)]
+        for q, got in zip(qs, m.scan_many(qs)):
+            T.same(got, oracle.scan(*m.columns(), m.U, q[0], q[1], q[2] & m.lim()), (tag, q))
+        assert np.array_equal(m.expired_queue(t0 - DAY, t0), oracle.expired_queue(m.end, t0 - DAY, t0))
+        for now, win in ((t0, 12 * HOUR), (t0 - 100 * DAY, 0), (2 ** 62, 30 * DAY)):
+            assert np.array_equal(m.archive_queue(now, win), oracle.archive_queue(m.start, m.end, m.user, m.U, now, win)), (tag, now, win)
+
+    check("loaded")
+    rows = rng.choice(n, 4000, replace=False).astype(np.int32)
+    ne = (t0 + rng.integers(-40 * DAY, DAY, rows.size)).astype(np.int64)
+    ne[:100], ne[100:200] = INT64_MIN, 2 ** 63 - 1
+    m.set_end(rows, ne)
+    check("set_end")
+    gone = m.delete_user(1)
+    assert gone.size and np.all(m.end[gone] == INT64_MIN) and m.delete_user(1).size == 0 and m.delete_user(U).size == 0
+    for months, tz in ((3, -5 * HOUR), (2, 0), (1, 330 * 60000)):   # each purges what the one before left
+        now = t0 - 20 * DAY
+        want = oracle.retention_queue(m.start, m.end, now, months, tz)
+        assert np.array_equal(m.retention_purge(now, months, tz), want) and want.size
+    cutoff = int(np.quantile(m.start, 0.05))
+    want = np.nonzero((m.start < cutoff) & (m.end != INT64_MIN))[0]
+    assert np.array_equal(m.prune_before(cutoff), want)
+    check("tombstoned")
+    k = 900
+    s2 = (t0 + rng.integers(-DAY, DAY, k)).astype(np.int64)
+    m.append_rows(s2, s2 + 12 * HOUR, rng.integers(0, U + 4, k).astype(np.int32), rng.integers(0, D, k).astype(np.int32), U + 4)
+    check("appended")
+    if U >= 3:
+        from sph_pie_amd.shard import partition_by_user_hash
+        sh = partition_by_user_hash(*m.columns(), m.U, 3)[1]
+        assert m.shard_table(1, 3) == (sh["rows"].size, sh["n_users"])
+        for got, name in zip(m.columns(), ("start", "end", "user", "disc")):
+            assert np.array_equal(got, sh[name]), name
+        check("sharded")
+
+
+def test_add_months_matches_the_oracle(oracle):
+    rng = np.random.default_rng(9)
+    ts = np.concatenate([oracle.T0_MS + rng.integers(-900 * DAY, 900 * DAY, 3000), [1706659200000, 1703980800000 + 5, 1709164800000]]).astype(np.int64)
+    for months in (1, 2, 3, 14, -2):
+        for tz in (0, 330 * 60000, -5 * HOUR):
+            got = T.add_months(ts, months, tz)
+            assert [int(x) for x in got] == [oracle.add_months(int(t), months, tz) for t in ts], (months, tz)
+
+
+def test_lattice_values_are_bin_edges(oracle):
+    """Under the key definition the table derives from its own `end` column, every lattice value is the lower edge of a bin of
+    the 15-bit key, the fine key's base is an occupied lattice value, and every lattice value at or above it (below the fine
+    clamp) is the lower edge of a fine bin."""
+    s, e, u, d, U, D, values = T.lattice_table(oracle)
+    pitch = 1 << T.LATTICE_SHIFT
+    base, shift, fbase, fshift = T.key_params(e)
+    assert 2000 < e.size < 5000 and np.array_equal(np.unique(e), values)
+    assert base == int(values[0]) and np.all((values - base) % pitch == 0)
+    assert shift == T.LATTICE_SHIFT, "the pitch is the bin width of the 15-bit key"
+    assert fshift <= shift and fbase in set(values.tolist()) and (fbase - base) % pitch == 0
+    frac_below = np.count_nonzero(e < fbase) / e.size
+    assert 0.85 < frac_below <= 0.9, "the fine key's base sits just below the 90th percentile"
+    for v in values.tolist():
+        assert T.key_of(v, base, shift) == T.key_of(v - 1, base, shift) + 1 == (v - base) // pitch + 1
+        assert T.key_of(v, base, shift) < T.KEY_MAX
+        if v >= fbase:
+            fk = T.key_of(v, fbase, fshift, T.FINE_KEY_MAX)
+            assert fk == T.key_of(v - 1, fbase, fshift, T.FINE_KEY_MAX) + 1 and fk < T.FINE_KEY_MAX
+    # several rows on every value, with different users and disciplines
+    for v in values[[0, 5, -200, -1]].tolist():
+        at = np.nonzero(e == v)[0]
+        assert at.size >= 4 and np.unique(u[at]).size >= 3 and np.unique(d[at]).size >= 2
+    # the tie table: a run of equal starts longer than a wave and than the 16-record direct bucket, for one user
+    s, e, u, d, U, D = T.tie_table(oracle)
+    assert np.unique(s[u == 0]).size == 1 and np.count_nonzero(u == 0) > 64 and np.any(d >= 64) and np.any(d < 0) and np.any(d == 63)

@@ -1,6 +1,11 @@
 #!/usr/bin/env python3
 """Differential fuzz on the GPU box: random tables, mutations, queries and scan forms against the CPU oracle, for a time
-budget.  usage: python tools/fuzz_gpu.py [seconds] [seed]   (prints the failing case's seed and stops at the first mismatch)"""
+budget.  usage: python tools/fuzz_gpu.py [seconds] [seed]   (prints the failing case's seed and stops at the first mismatch)
+
+Every case is followed by one chain of tests/table_model.py under the same seed: the model, the step generator and the runner
+of tests/test_gpu_model.py (every mutator read back against the model, batches, wide batches, pipelined lanes, the queues),
+so the endless fuzz and the suite exercise the same operations.  A failing chain prints "chain seed N": reproduce it with
+table_model.run_chain(pie, oracle, N)."""
 import os
 import sys
 import time
@@ -10,8 +15,10 @@ import numpy as np
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "oracle"))
+sys.path.insert(0, os.path.join(REPO, "tests"))
 import oracle_py as oracle  # noqa: E402  (the checker)
 import sph_pie_amd as pie  # noqa: E402
+import table_model  # noqa: E402  (tests/table_model.py)
 import torch  # noqa: E402
 
 INT64_MIN = -(2 ** 63)
@@ -20,7 +27,7 @@ FORMS = [None, None, None, 0x03, 0x01, 0x85, 0xC5, 0x485, 0x4C5, 0xC85, 0xCC5, 0
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 120.0
 seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else int(time.time())
 t_end = time.time() + budget
-cases = scans = 0
+cases = scans = chains = 0
 dev = torch.device("cuda", 0)
 
 
@@ -282,6 +289,13 @@ while time.time() < t_end:
     except Exception as exc:  # noqa: BLE001
         print("FAIL %s: %r" % (what, exc), flush=True)
         sys.exit(1)
+    os.environ.pop("PIE_K1_VARIANT", None)   # the chains run the adaptive forms
+    try:
+        table_model.run_chain(pie, oracle, case_seed)
+        chains += 1
+    except Exception as exc:  # noqa: BLE001
+        print("FAIL chain seed %d %s: %r" % (case_seed, table_model.chain_config(case_seed), exc), flush=True)
+        sys.exit(1)
     if cases % 20 == 0:
         print("ok: %d cases, %d scans, %.0f s left" % (cases, scans, t_end - time.time()), flush=True)
-print("fuzz ok: %d cases, %d scans in %.0f s (first seed %d)" % (cases, scans, budget, seed0 + 1))
+print("fuzz ok: %d cases, %d scans, %d model chains in %.0f s (first seed %d)" % (cases, scans, chains, budget, seed0 + 1))
