@@ -361,6 +361,11 @@ typedef struct pie_table_info {
     uint64_t hot_rows;        /* rows the end-ordered hot index holds, its delta aside (0: there is none, or it was dropped) */
     uint64_t hot_bytes;       /* device memory of the hot index (32 B per entry and delta slot + 4 B per row of capacity + build scratch) */
     uint64_t hot_builds;      /* times it was built for this context */
+    /* fields below were added with pie_compact_rows: a caller that sets struct_size to the size without them gets the rest */
+    uint64_t compact_bytes;   /* device memory of the two maps of the last compaction (0: there are none) */
+    uint64_t compactions;     /* pie_compact_rows calls that succeeded on this context */
+    double compact_count_ms;  /* device time (HIP events around the two kernels) of the last compaction's count pass and prefix ... */
+    double compact_write_ms;  /* ... and of its write pass */
 } pie_table_info;
 int pie_table_info_get(pie_ctx *ctx, pie_table_info *out);
 /* The ordered run (sph-pie_amd/csrc/pie_ordered.h): the table's rows a second time, in (user, start, row) order — the order
@@ -389,6 +394,45 @@ int32_t pie_shard_of(int32_t user, int32_t n_shards);
  * users_global_out[k] = the global id of local user k (n_users); either may be NULL. */
 int pie_shard_table(pie_ctx *ctx, int32_t rank, int32_t world, size_t *n_rows_out, int32_t *n_users_out);
 int pie_shard_maps(pie_ctx *ctx, int32_t *rows_global_out, int32_t *users_global_out);
+
+/* ---- compaction: the table's counterpart of `sessions.delete()` (server/sessionStore.js:47-53,66-73) ---------------------
+ * Every mutator above appends rows or tombstones them; pie_compact_rows is what removes rows from the device table.
+ * Keep, in table order, exactly the rows with end > dead_before; drop the rest.  dead_before = PIE_END_NONE drops
+ * tombstones only; dead_before = T also drops sessions that expired at or before T (e.g. the `now` of the last purge
+ * that reported them).  Users are NOT renumbered; n_users is unchanged.  *n_kept_out = new row count.  Row order is
+ * kept, so under the tie rule (start asc, row index asc) every feed is the old one with its rows renumbered.
+ *   PIE_E_STATE with no table, or while a scan or batch is in flight; queued asynchronous appends and touches land first.
+ *   Afterwards the four columns hold the kept rows in their old order; the 2-byte key, 1-byte key and payload records are
+ *   rebuilt and in step (has_keys unchanged); the hot index is dropped and rebuilt by the next batch that can use it, the
+ *   ordered run is invalid and comes back under its mode's rule, what the scans had learned about the table is forgotten —
+ *   all as after a load.  The last scan / batch results and the queue of pie_queue_info are forgotten (kind 0).
+ *   Without PIE_COMPACT_SHRINK capacity and workspace stay: the kept rows are written into fresh columns of the same capacity,
+ *   which then replace the old ones (no second copy).  With it the table and its workspace are re-sized to the kept rows,
+ *   as pie_shard_table does: pie_table_info.table_bytes and workspace_bytes fall to those of a load of the kept rows.
+ *   Every row dropped leaves a valid empty table (0 rows, capacity >= 1): scans answer empty, appends work.
+ *   On a sharded context the local row -> global row map is gathered with the columns: pie_shard_maps, pie_queue_pack_device
+ *   and the pie_comm_*_queue calls keep reporting the ORIGINAL global rows; the user map is untouched.
+ *   When nothing is dropped the columns and everything derived from them are left alone; the maps are the identity.
+ *   Memory: the kept rows are written out of place, so while the call runs the device holds a second set of columns — 24 B x
+ *   capacity without PIE_COMPACT_SHRINK, 24 B x kept rows with it — beside the two maps (4 B per old row + 4 B per kept row,
+ *   which stay: pie_table_info.compact_bytes).  PIE_E_NOMEM before anything was moved leaves the table as it was; with
+ *   PIE_COMPACT_SHRINK a failure while the right-sized workspace is allocated leaves the context without a table, as a failed
+ *   pie_shard_table does. */
+#define PIE_COMPACT_SHRINK 1u   /* also re-size the table and its workspace to the kept rows (as pie_shard_table does) */
+int pie_compact_rows(pie_ctx *ctx, int64_t dead_before, uint32_t flags, size_t *n_kept_out);
+/* Maps of the last compaction, resident on the device until the next table change that renumbers rows (load, gen,
+ * shard, compact):  new_of_old[n_old] (-1 = dropped), old_of_new[n_kept] (ascending).  Host copies (either may be NULL);
+ * PIE_E_STATE when there are none. */
+int pie_compact_maps(pie_ctx *ctx, int32_t *new_of_old_out, int32_t *old_of_new_out, size_t *n_old_out, size_t *n_kept_out);
+/* ... their device pointers (int32 arrays, valid as long as the maps are) ... */
+int pie_compact_map_device_ptrs(pie_ctx *ctx, void **new_of_old_dev, void **old_of_new_dev, size_t *n_old_out, size_t *n_kept_out);
+/* ... and k old row indices rewritten in place to their new ones (-1 = dropped; an index outside [0, n_old) -> -1):
+ * one small gather, for a host that holds only a few rows of a huge table. */
+int pie_compact_translate(pie_ctx *ctx, int32_t *rows_inout, size_t k);
+/* How the two passes would cut a table of n rows: rows a wave takes per step, rows the waves of a block take per step, rows of
+ * the contiguous unit every wave owns, blocks of the grid (any output may be NULL).  For tests that straddle the boundaries. */
+int pie_compact_geometry(pie_ctx *ctx, size_t n, int32_t *rows_per_wave_step_out, int32_t *rows_per_block_step_out,
+                         int64_t *rows_per_unit_out, int32_t *blocks_out);
 
 /* ---- communicator: the sharded table behind the C ABI (SURVEY.md 8b "pie_ctx_create(device_ids[], n, ...)", 8e) --------
  * A pie_comm owns one scan context per GPU and one RCCL communicator; the session table is sharded by user hash

@@ -16,6 +16,8 @@ PIE_END_NONE = -(2 ** 63)
 INT64_MIN = -(2 ** 63)
 
 PIE_E_CAPACITY = -5
+PIE_E_STATE = -6
+PIE_COMPACT_SHRINK = 1
 
 
 class PieError(RuntimeError):
@@ -31,6 +33,7 @@ class PieTableInfo(C.Structure):
         ("index_build_ms", C.c_double), ("ordered_rows", C.c_uint64), ("ordered_bytes", C.c_uint64),
         ("ordered_build_ms", C.c_double), ("ordered_builds", C.c_uint64), ("ordered_positions", C.c_uint64),
         ("ordered_respreads", C.c_uint64), ("hot_rows", C.c_uint64), ("hot_bytes", C.c_uint64), ("hot_builds", C.c_uint64),
+        ("compact_bytes", C.c_uint64), ("compactions", C.c_uint64), ("compact_count_ms", C.c_double), ("compact_write_ms", C.c_double),
     ]
 
 
@@ -126,6 +129,11 @@ _SIGS = [
     ("pie_shard_of", C.c_int32, [C.c_int32, C.c_int32]),
     ("pie_shard_table", C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(C.c_size_t), C.POINTER(C.c_int32)]),
     ("pie_shard_maps", C.c_int, [_P, _P, _P]),
+    ("pie_compact_rows", C.c_int, [_P, C.c_int64, C.c_uint32, C.POINTER(C.c_size_t)]),
+    ("pie_compact_maps", C.c_int, [_P, _P, _P, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    ("pie_compact_map_device_ptrs", C.c_int, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    ("pie_compact_translate", C.c_int, [_P, _P, C.c_size_t]),
+    ("pie_compact_geometry", C.c_int, [_P, C.c_size_t, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     ("pie_comm_create", C.c_int, [C.POINTER(C.c_int32), C.c_int32, C.POINTER(_P)]),
     ("pie_comm_unique_id", C.c_int, [_P]),
     ("pie_comm_create_rank", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_P)]),
@@ -704,6 +712,42 @@ class PieScan:
         users = np.full(max(self.n_users, 1), -1, np.int32)
         self._check(self._lib.pie_shard_maps(self._ctx, _ptr(rows), _ptr(users)))
         return rows[: self.n], users
+
+    # ---- compaction on the device
+    def compact_rows(self, dead_before=INT64_MIN, shrink=False):
+        """Keep, in table order, the rows with end > dead_before (the default drops tombstones only); shrink: also re-size the
+        table and its workspace to the kept rows.  -> the new row count."""
+        k = C.c_size_t(0)
+        self._check(self._lib.pie_compact_rows(self._ctx, int(dead_before), PIE_COMPACT_SHRINK if shrink else 0, C.byref(k)))
+        self.n = int(k.value)
+        return self.n
+
+    def compact_maps(self):
+        """-> (new_of_old[n_old] int32, -1 = dropped; old_of_new[n_kept] int32, ascending) of the last compaction."""
+        n_old, n_kept = C.c_size_t(0), C.c_size_t(0)
+        self._check(self._lib.pie_compact_map_device_ptrs(self._ctx, None, None, C.byref(n_old), C.byref(n_kept)))
+        new_of_old, old_of_new = np.empty(n_old.value, np.int32), np.empty(n_kept.value, np.int32)
+        self._check(self._lib.pie_compact_maps(self._ctx, _ptr(new_of_old), _ptr(old_of_new), None, None))
+        return new_of_old, old_of_new
+
+    def compact_map_device_ptrs(self):
+        """-> (new_of_old device address, old_of_new device address, n_old, n_kept)"""
+        a, b, n_old, n_kept = _P(), _P(), C.c_size_t(0), C.c_size_t(0)
+        self._check(self._lib.pie_compact_map_device_ptrs(self._ctx, C.byref(a), C.byref(b), C.byref(n_old), C.byref(n_kept)))
+        return a.value, b.value, n_old.value, n_kept.value
+
+    def compact_translate(self, rows):
+        """Old row indices -> their new ones (-1: dropped, or not a row of the old table), as a new int32 array."""
+        rows = np.array(rows, dtype=np.int32, copy=True).reshape(-1)
+        self._check(self._lib.pie_compact_translate(self._ctx, _ptr(rows), rows.shape[0]))
+        return rows
+
+    def compact_geometry(self, n=None):
+        """How the compaction passes cut a table of n rows (default: the resident one) ->
+        {rows_per_wave_step, rows_per_block_step, rows_per_unit, blocks}."""
+        a, b, u, g = C.c_int32(0), C.c_int32(0), C.c_int64(0), C.c_int32(0)
+        self._check(self._lib.pie_compact_geometry(self._ctx, int(self.n if n is None else n), C.byref(a), C.byref(b), C.byref(u), C.byref(g)))
+        return {"rows_per_wave_step": a.value, "rows_per_block_step": b.value, "rows_per_unit": u.value, "blocks": g.value}
 
     # ---- measurement / plumbing
     def set_stream(self, hip_stream):

@@ -4533,5 +4533,172 @@ __global__ __launch_bounds__(256) void k_arch_gather(const int* __restrict__ ord
     }
 }
 
+// ------------------------------------------------------------------------------------------------ compaction of the table
+//
+// pie_compact_rows: keep, in table order, the rows with end > dead_before.  Two passes and no communication between blocks
+// beyond the prefix kernel that runs between them: every WAVE owns a contiguous unit of rows (a multiple of kCmpWaveRows);
+// the count pass streams `end` alone (8 B/row) and leaves one count per unit, the prefix of the counts is where a unit's
+// kept rows start in the new columns, and the write pass re-reads `end`, places every kept row by ballot + mbcnt (no
+// atomics, nothing to wait for), loads start / user / disc (and the shard map) of the kept rows only, and stages a step's
+// kept rows in the wave's own LDS so that they leave as contiguous 16-byte stores.  Order is the row order by construction:
+// units are ascending row ranges, steps ascend inside a unit, a lane's two rows are neighbours and lanes ascend.
+constexpr int kCmpWaveRows = 2 * kWave;                 // rows of one step of a wave: one 16-byte load of `end` per lane
+constexpr int kCmpBlockRows = kCmpWaveRows * kK1Waves;  // rows the four waves of a block take per step
+typedef long long cmp_ll2 __attribute__((ext_vector_type(2)));
+
+struct CmpStage {  // one wave's kept rows of one step
+    long long start[kCmpWaveRows], end[kCmpWaveRows];
+    int user[kCmpWaveRows], disc[kCmpWaveRows], old_row[kCmpWaveRows], global_row[kCmpWaveRows];
+};
+
+// the lane's two values of `end` (rows r, r + 1; r even); rows at or past r1 read as the tombstone, which no predicate keeps
+__device__ __forceinline__ void cmp_load_end(const long long* __restrict__ end, long long r, long long r1, long long& e0, long long& e1)
+{
+    e0 = e1 = INT64_MIN;
+    if (r + 1 < r1) {
+        const cmp_ll2 v = __builtin_nontemporal_load(reinterpret_cast<const cmp_ll2*>(end + r));
+        e0 = v.x;
+        e1 = v.y;
+    } else if (r < r1) {
+        e0 = __builtin_nontemporal_load(end + r);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_compact_count(const long long* __restrict__ end, long long n, long long rows_per_unit,
+                                                       long long dead_before, int* __restrict__ unit_count)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long unit = (long long)blockIdx.x * kK1Waves + wave;
+    const long long u0 = unit * rows_per_unit < n ? unit * rows_per_unit : n;
+    const long long u1 = min(n, u0 + rows_per_unit);
+    int kept = 0;
+    for (long long r0 = u0; r0 < u1; r0 += kCmpWaveRows) {
+        long long e0, e1;
+        cmp_load_end(end, r0 + 2 * lane, u1, e0, e1);
+        kept += __popcll(__ballot(e0 > dead_before)) + __popcll(__ballot(e1 > dead_before));
+    }
+    if (lane == 0) unit_count[unit] = kept;
+}
+
+// lds[0 .. total) -> out[pos .. pos + total): the aligned middle as one 16-byte store per lane, the ragged ends by single lanes
+__device__ __forceinline__ void cmp_store64(long long* __restrict__ out, long long pos, int total, const long long* lds, int lane)
+{
+    const int head = min((int)(pos & 1), total);
+    const int pairs = (total - head) >> 1;
+    if (lane < pairs) {
+        cmp_ll2 v;
+        v.x = lds[head + 2 * lane];
+        v.y = lds[head + 2 * lane + 1];
+        *reinterpret_cast<cmp_ll2*>(out + pos + head + 2 * lane) = v;
+    }
+    if (lane == 62 && head) out[pos] = lds[0];
+    if (lane == 63 && ((total - head) & 1)) out[pos + total - 1] = lds[total - 1];
+}
+
+__device__ __forceinline__ void cmp_store32(int* __restrict__ out, long long pos, int total, const int* lds, int lane)
+{
+    const int head = min((int)((4 - (pos & 3)) & 3), total);
+    const int quads = (total - head) >> 2;
+    const int tail = (total - head) & 3;
+    if (lane < quads) {
+        int4 v;
+        v.x = lds[head + 4 * lane];
+        v.y = lds[head + 4 * lane + 1];
+        v.z = lds[head + 4 * lane + 2];
+        v.w = lds[head + 4 * lane + 3];
+        *reinterpret_cast<int4*>(out + pos + head + 4 * lane) = v;
+    }
+    if (lane >= 56 && lane - 56 < head) out[pos + (lane - 56)] = lds[lane - 56];
+    if (lane >= 60 && lane - 60 < tail) out[pos + head + 4 * quads + (lane - 60)] = lds[head + 4 * quads + (lane - 60)];
+}
+
+// shard_rows (may be null): local row -> global row of a sharded table, covering rows [0, shard_n); gathered like a column
+__global__ __launch_bounds__(256) void k_compact_write(const long long* __restrict__ start, const long long* __restrict__ end,
+                                                       const int* __restrict__ user, const int* __restrict__ disc,
+                                                       const int* __restrict__ shard_rows, long long shard_n, long long n,
+                                                       long long rows_per_unit, long long dead_before, const long long* __restrict__ unit_off,
+                                                       long long* __restrict__ o_start, long long* __restrict__ o_end, int* __restrict__ o_user,
+                                                       int* __restrict__ o_disc, int* __restrict__ o_shard, int* __restrict__ new_of_old,
+                                                       int* __restrict__ old_of_new)
+{
+    __shared__ CmpStage stage[kK1Waves];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long unit = (long long)blockIdx.x * kK1Waves + wave;
+    const long long u0 = unit * rows_per_unit;
+    if (u0 >= n) return; // wave-uniform; the kernel has no block-wide barrier
+    const long long u1 = min(n, u0 + rows_per_unit);
+    CmpStage& st = stage[wave];
+    long long carry = unit_off[unit];
+    for (long long r0 = u0; r0 < u1; r0 += kCmpWaveRows) {
+        const long long r = r0 + 2 * lane;
+        long long e0, e1;
+        cmp_load_end(end, r, u1, e0, e1);
+        const bool k0 = e0 > dead_before, k1 = e1 > dead_before;
+        const unsigned long long b0 = __ballot(k0), b1 = __ballot(k1);
+        const int pre = prefix_in_ballot(b0) + prefix_in_ballot(b1);
+        const int total = __popcll(b0) + __popcll(b1);
+        const int n0 = k0 ? (int)(carry + pre) : -1, n1 = k1 ? (int)(carry + pre + (k0 ? 1 : 0)) : -1;
+        if (r + 1 < u1) *reinterpret_cast<int2*>(new_of_old + r) = make_int2(n0, n1);
+        else if (r < u1) new_of_old[r] = n0;
+        if (k0) {
+            st.start[pre] = __builtin_nontemporal_load(start + r);
+            st.end[pre] = e0;
+            st.user[pre] = __builtin_nontemporal_load(user + r);
+            st.disc[pre] = __builtin_nontemporal_load(disc + r);
+            st.old_row[pre] = (int)r;
+            if (shard_rows) st.global_row[pre] = r < shard_n ? shard_rows[r] : -1;
+        }
+        if (k1) {
+            const int p = pre + (k0 ? 1 : 0);
+            st.start[p] = __builtin_nontemporal_load(start + r + 1);
+            st.end[p] = e1;
+            st.user[p] = __builtin_nontemporal_load(user + r + 1);
+            st.disc[p] = __builtin_nontemporal_load(disc + r + 1);
+            st.old_row[p] = (int)(r + 1);
+            if (shard_rows) st.global_row[p] = r + 1 < shard_n ? shard_rows[r + 1] : -1;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        cmp_store64(o_start, carry, total, st.start, lane);
+        cmp_store64(o_end, carry, total, st.end, lane);
+        cmp_store32(o_user, carry, total, st.user, lane);
+        cmp_store32(o_disc, carry, total, st.disc, lane);
+        cmp_store32(old_of_new, carry, total, st.old_row, lane);
+        if (shard_rows) cmp_store32(o_shard, carry, total, st.global_row, lane);
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        carry += total;
+    }
+}
+
+// nothing was dropped: both maps are the identity
+__global__ __launch_bounds__(256) void k_compact_identity(long long n, int* __restrict__ new_of_old, int* __restrict__ old_of_new)
+{
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        new_of_old[i] = (int)i;
+        old_of_new[i] = (int)i;
+    }
+}
+
+// first new row whose old row is at or past `bound` (old_of_new ascends): how many kept rows lie below it.  One thread.
+__global__ void k_compact_lower_bound(const int* __restrict__ old_of_new, long long n_kept, long long bound, long long* __restrict__ out)
+{
+    long long lo = 0, hi = n_kept;
+    while (lo < hi) {
+        const long long mid = (lo + hi) / 2;
+        if ((long long)old_of_new[mid] < bound) lo = mid + 1;
+        else hi = mid;
+    }
+    *out = lo;
+}
+
+// pie_compact_translate: old row -> new row (-1: dropped, or not a row of the old table)
+__global__ __launch_bounds__(256) void k_compact_translate(int* __restrict__ rows, long long k, const int* __restrict__ new_of_old, long long n_old)
+{
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < k; i += (long long)gridDim.x * blockDim.x) {
+        const int r = rows[i];
+        rows[i] = (r >= 0 && (long long)r < n_old) ? new_of_old[r] : -1;
+    }
+}
 
 } // namespace pie

@@ -76,7 +76,11 @@
     X(int, pie_comm_expired_queue, (pie_comm *, int64_t, int64_t, int32_t *, size_t, size_t *))                     \
     X(int, pie_comm_archive_queue, (pie_comm *, int64_t, int64_t, int32_t *, size_t, size_t *))                     \
     X(int, pie_comm_queue_read, (pie_comm *, int32_t, int32_t *, int32_t *, int32_t *, size_t, size_t *))            \
-    X(int, pie_shard_maps, (pie_ctx *, int32_t *, int32_t *))
+    X(int, pie_shard_maps, (pie_ctx *, int32_t *, int32_t *))                                                       \
+    X(int, pie_compact_rows, (pie_ctx *, int64_t, uint32_t, size_t *))                                              \
+    X(int, pie_compact_maps, (pie_ctx *, int32_t *, int32_t *, size_t *, size_t *))                                 \
+    X(int, pie_compact_map_device_ptrs, (pie_ctx *, void **, void **, size_t *, size_t *))                          \
+    X(int, pie_compact_translate, (pie_ctx *, int32_t *, size_t))
 
 #define X(ret, name, args) static ret(*p_##name) args;
 PIE_SYMBOLS(X)
@@ -415,6 +419,74 @@ static napi_value fn_set_end(napi_env env, napi_callback_info info)
         return NULL;
     }
     int rc = p_pie_set_end(ctx, rows, ne, k);
+    if (rc) return throw_pie(env, ctx, rc);
+    return js_int(env, (int64_t)k);
+}
+
+/* compactRows(ctx, deadBefore BigInt|Number, shrink) -> rows kept: drop the rows with end <= deadBefore, order preserved
+ * (pie_compact_rows; the device's counterpart of sessions.delete(), sessionStore.js:47-53,66-73) */
+static napi_value fn_compact_rows(napi_env env, napi_callback_info info)
+{
+    ARGS(3)
+    pie_ctx *ctx = get_ctx(env, argv[0]);
+    if (!ctx) return NULL;
+    int64_t dead_before = 0;
+    bool shrink = false;
+    size_t kept = 0;
+    if (!get_i64(env, argv[1], &dead_before)) {
+        napi_throw_type_error(env, NULL, "compactRows(ctx, deadBefore BigInt|Number, shrink)");
+        return NULL;
+    }
+    CHECK(env, napi_get_value_bool(env, argv[2], &shrink));
+    int rc = p_pie_compact_rows(ctx, dead_before, shrink ? PIE_COMPACT_SHRINK : 0u, &kept);
+    if (rc) return throw_pie(env, ctx, rc);
+    return js_int(env, (int64_t)kept);
+}
+
+/* compactMaps(ctx, newOfOldOut Int32Array|null, oldOfNewOut Int32Array|null) -> {nOld, nKept}; an array given is filled and must
+ * be long enough (call with nulls first to learn the sizes) */
+static napi_value fn_compact_maps(napi_env env, napi_callback_info info)
+{
+    ARGS(3)
+    pie_ctx *ctx = get_ctx(env, argv[0]);
+    if (!ctx) return NULL;
+    size_t n_old = 0, n_kept = 0, cap_new = 0, cap_old = 0;
+    int rc = p_pie_compact_map_device_ptrs(ctx, NULL, NULL, &n_old, &n_kept);
+    if (rc) return throw_pie(env, ctx, rc);
+    napi_valuetype t0, t1;
+    CHECK(env, napi_typeof(env, argv[1], &t0));
+    CHECK(env, napi_typeof(env, argv[2], &t1));
+    int32_t *m_new = (t0 == napi_null || t0 == napi_undefined) ? NULL : typed(env, argv[1], napi_int32_array, &cap_new);
+    int32_t *m_old = (t1 == napi_null || t1 == napi_undefined) ? NULL : typed(env, argv[2], napi_int32_array, &cap_old);
+    if ((t0 != napi_null && t0 != napi_undefined && (!m_new || cap_new < n_old)) ||
+        (t1 != napi_null && t1 != napi_undefined && (!m_old || cap_old < n_kept))) {
+        napi_throw_type_error(env, NULL, "compactMaps(ctx, Int32Array[nOld]|null, Int32Array[nKept]|null)");
+        return NULL;
+    }
+    if (m_new || m_old) {
+        rc = p_pie_compact_maps(ctx, m_new, m_old, NULL, NULL);
+        if (rc) return throw_pie(env, ctx, rc);
+    }
+    napi_value out;
+    CHECK(env, napi_create_object(env, &out));
+    CHECK(env, napi_set_named_property(env, out, "nOld", js_int(env, (int64_t)n_old)));
+    CHECK(env, napi_set_named_property(env, out, "nKept", js_int(env, (int64_t)n_kept)));
+    return out;
+}
+
+/* compactTranslate(ctx, rows Int32Array) -> its length; old row indices rewritten in place to the new ones (-1: dropped) */
+static napi_value fn_compact_translate(napi_env env, napi_callback_info info)
+{
+    ARGS(2)
+    pie_ctx *ctx = get_ctx(env, argv[0]);
+    if (!ctx) return NULL;
+    size_t k = 0;
+    int32_t *rows = typed(env, argv[1], napi_int32_array, &k);
+    if (!rows && k) {
+        napi_throw_type_error(env, NULL, "compactTranslate(ctx, Int32Array rows)");
+        return NULL;
+    }
+    int rc = k ? p_pie_compact_translate(ctx, rows, k) : 0;
     if (rc) return throw_pie(env, ctx, rc);
     return js_int(env, (int64_t)k);
 }
@@ -1672,7 +1744,7 @@ static napi_value init(napi_env env, napi_value exports)
     } table[] = {
         {"open", fn_open}, {"deviceCount", fn_device_count}, {"ctxCreate", fn_ctx_create}, {"ctxDestroy", fn_ctx_destroy},
         {"loadColumns", fn_load_columns}, {"appendRows", fn_append_rows}, {"genSynthetic", fn_gen},
-        {"readColumns", fn_read_columns}, {"saveColumns", fn_save_columns}, {"loadColumnsDir", fn_load_columns_dir}, {"setEnd", fn_set_end}, {"deleteUser", fn_delete_user}, {"retentionPurgeTz", fn_retention_purge_tz},
+        {"readColumns", fn_read_columns}, {"saveColumns", fn_save_columns}, {"loadColumnsDir", fn_load_columns_dir}, {"setEnd", fn_set_end}, {"compactRows", fn_compact_rows}, {"compactMaps", fn_compact_maps}, {"compactTranslate", fn_compact_translate}, {"deleteUser", fn_delete_user}, {"retentionPurgeTz", fn_retention_purge_tz},
         {"setDisciplines", fn_set_disc}, {"scan", fn_scan}, {"scanDevice", fn_scan_device}, {"userFeed", fn_user_feed}, {"scanAsync", fn_scan_async}, {"fetchRows", fn_fetch_rows},
         {"expiredQueue", fn_expired_queue}, {"archiveQueue", fn_archive_queue}, {"serializeEvents", fn_serialize_events}, {"serializeICal", fn_serialize_ical}, {"stats", fn_stats}, {"setProfiling", fn_set_profiling},
         {"setOrderedRun", fn_set_ordered_run}, {"setBatchLanes", fn_set_batch_lanes},

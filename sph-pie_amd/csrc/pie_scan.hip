@@ -29,6 +29,7 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include <cstdarg>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <algorithm>
@@ -291,6 +292,16 @@ struct pie_ctx {
     int* d_shard_users = nullptr;  // ... local user -> global user
     long long shard_rows_n = 0;
     int shard_users_n = 0;
+    // pie_compact_rows: the maps of the last compaction (old row -> new row or -1, new row -> old row), until rows are renumbered again
+    int* d_cmp_new_of_old = nullptr;
+    int* d_cmp_old_of_new = nullptr;
+    long long cmp_n_old = 0, cmp_n_kept = 0;
+    bool cmp_valid = false;
+    long long *adopt_start = nullptr, *adopt_end = nullptr; // set by pie_compact_rows around its ensure_capacity call only: columns the
+    int *adopt_user = nullptr, *adopt_disc = nullptr;       // re-allocated table takes over instead of allocating its own
+    unsigned long long compactions = 0;
+    double cmp_count_ms = 0;       // ... of its count pass and prefix alone
+    double cmp_write_ms = 0;       // ... of its write pass (HIP events)
 
     // predicate table
     unsigned long long disc_mask = ~0ull;
@@ -628,6 +639,14 @@ OrdMirror ord_mirror_of(const pie_ctx* c)
     return m;
 }
 
+void cmp_forget(pie_ctx* c)
+{
+    dfree(c->d_cmp_new_of_old);
+    dfree(c->d_cmp_old_of_new);
+    c->cmp_n_old = c->cmp_n_kept = 0;
+    c->cmp_valid = false;
+}
+
 void free_table(pie_ctx* c)
 {
     for (int l = 1; l < kLaneMax; ++l) // nothing of a lane's may still be running when its arrays go
@@ -763,6 +782,7 @@ int ensure_capacity(pie_ctx* c, long long n, int n_users, long long keep_rows = 
     int rc = sync_all(c);
     if (rc) return rc;
     ord_invalidate(c, keep_rows == 0);
+    if (keep_rows == 0) cmp_forget(c); // a new table (load, gen, shard, compact) renumbers the rows: the last compaction's maps go
     long long rows = n > 0 ? n : 1;
     if (rows > c->cap_rows || n_users > c->cap_users) {
         int users = n_users;
@@ -778,10 +798,16 @@ int ensure_capacity(pie_ctx* c, long long n, int n_users, long long keep_rows = 
         if (keep_rows > 0) { c->d_start = c->d_end = nullptr; c->d_user = c->d_disc = nullptr; }
         else old_s = old_e = nullptr, old_u = old_d = nullptr;
         free_table(c);
-        PIE_HIP(c, hipMalloc(&c->d_start, rows * 8));
-        PIE_HIP(c, hipMalloc(&c->d_end, rows * 8));
-        PIE_HIP(c, hipMalloc(&c->d_user, rows * 4));
-        PIE_HIP(c, hipMalloc(&c->d_disc, rows * 4));
+        if (c->adopt_start) { // pie_compact_rows hands over columns of exactly `rows` rows that already hold the table
+            c->d_start = c->adopt_start; c->d_end = c->adopt_end; c->d_user = c->adopt_user; c->d_disc = c->adopt_disc;
+            c->adopt_start = c->adopt_end = nullptr;
+            c->adopt_user = c->adopt_disc = nullptr;
+        } else {
+            PIE_HIP(c, hipMalloc(&c->d_start, rows * 8));
+            PIE_HIP(c, hipMalloc(&c->d_end, rows * 8));
+            PIE_HIP(c, hipMalloc(&c->d_user, rows * 4));
+            PIE_HIP(c, hipMalloc(&c->d_disc, rows * 4));
+        }
         // derived columns, rebuilt by build_keys after every (re)allocation; a table too large to carry them (19 B/row)
         // simply runs without the keyed form
         if (hipMalloc(&c->d_key, rows * sizeof(lkey_t) + 64) != hipSuccess || hipMalloc(&c->d_pay, rows * sizeof(PayRec)) != hipSuccess ||
@@ -3378,6 +3404,7 @@ int pie_ctx_destroy(pie_ctx* c)
     free_table(c);
     dfree(c->d_shard_rows);
     dfree(c->d_shard_users);
+    cmp_forget(c);
     dfree(c->d_stage);
     if (c->h_stage) (void)hipHostFree(c->h_stage);
     for (auto& a : c->astage) {
@@ -4760,7 +4787,13 @@ int pie_set_scan_form(pie_ctx* c, int form)
 int pie_table_info_get(pie_ctx* c, pie_table_info* out)
 {
     if (!c || !out) return PIE_E_INVAL;
-    if (out->struct_size != sizeof(pie_table_info)) return fail(c, PIE_E_INVAL, "pie_table_info.struct_size mismatch");
+    // the struct grows at its end: a caller built against the form without the compaction fields gets the fields it knows
+    const uint32_t caller_size = out->struct_size;
+    if (caller_size != sizeof(pie_table_info) && caller_size != offsetof(pie_table_info, compact_bytes))
+        return fail(c, PIE_E_INVAL, "pie_table_info.struct_size mismatch");
+    pie_table_info full{};
+    pie_table_info* const caller = out;
+    out = &full;
     const size_t rows = (size_t)c->cap_rows, users = (size_t)c->cap_users;
     out->has_keys = (c->key_ok && c->d_key && c->d_pay && c->d_fkey) ? 1u : 0u;
     out->rows = (uint64_t)c->n;
@@ -4803,6 +4836,12 @@ int pie_table_info_get(pie_ctx* c, pie_table_info* out)
     out->hot_rows = c->hix.valid ? (uint64_t)c->hix.n_main : 0u;
     out->hot_bytes = (uint64_t)c->hix.rec_cap * sizeof(HotRec) + (uint64_t)c->hix.pos_cap * 4 + (uint64_t)c->hix.cnt_cap * 4 + (c->hix.d_off ? 129 * 8 + 4 : 0);
     out->hot_builds = c->hix.builds;
+    out->compact_bytes = c->cmp_valid ? (uint64_t)(c->cmp_n_old > 0 ? c->cmp_n_old : 1) * 4 + (uint64_t)(c->cmp_n_kept > 0 ? c->cmp_n_kept : 1) * 4 : 0u;
+    out->compactions = c->compactions;
+    out->compact_count_ms = c->cmp_count_ms;
+    out->compact_write_ms = c->cmp_write_ms;
+    full.struct_size = caller_size;
+    memcpy(caller, &full, caller_size);
     return PIE_OK;
 }
 
@@ -5019,6 +5058,231 @@ int pie_shard_maps(pie_ctx* c, int32_t* rows_global_out, int32_t* users_global_o
     if (users_global_out && c->shard_users_n)
         PIE_HIP(c, hipMemcpyAsync(users_global_out, c->d_shard_users, (size_t)c->shard_users_n * 4, hipMemcpyDeviceToHost, c->stream));
     PIE_HIP(c, hipStreamSynchronize(c->stream));
+    return PIE_OK;
+}
+
+// Rows per unit (= per wave) and the grid of the two compaction passes: every wave of every block owns one contiguous unit, a
+// whole number of 128-row steps; the grid comes from the chip (8 blocks per CU: the passes are streams, and a wave keeps one
+// step in flight), a small table gets as many units as it has steps.
+static void compact_plan(const pie_ctx* c, long long n, int* blocks_out, long long* rows_per_unit_out)
+{
+    long long blocks = (n + kCmpBlockRows - 1) / kCmpBlockRows;
+    const long long most = (long long)(c->n_cus > 0 ? c->n_cus : 1) * 8;
+    if (blocks > most) blocks = most;
+    if (blocks < 1) blocks = 1;
+    const long long units = blocks * kK1Waves;
+    long long rpu = (n + units - 1) / units;
+    rpu = (rpu + kCmpWaveRows - 1) / kCmpWaveRows * kCmpWaveRows;
+    if (rpu < kCmpWaveRows) rpu = kCmpWaveRows;
+    *blocks_out = (int)blocks;
+    *rows_per_unit_out = rpu;
+}
+
+int pie_compact_geometry(pie_ctx* c, size_t n, int32_t* rows_per_wave_step_out, int32_t* rows_per_block_step_out, int64_t* rows_per_unit_out,
+                         int32_t* blocks_out)
+{
+    if (!c) return PIE_E_INVAL;
+    int blocks = 0;
+    long long rpu = 0;
+    compact_plan(c, (long long)n, &blocks, &rpu);
+    if (rows_per_wave_step_out) *rows_per_wave_step_out = kCmpWaveRows;
+    if (rows_per_block_step_out) *rows_per_block_step_out = kCmpBlockRows;
+    if (rows_per_unit_out) *rows_per_unit_out = rpu;
+    if (blocks_out) *blocks_out = blocks;
+    return PIE_OK;
+}
+
+int pie_compact_rows(pie_ctx* c, int64_t dead_before, uint32_t flags, size_t* n_kept_out)
+{
+    if (!c) return PIE_E_INVAL;
+    if (flags & ~PIE_COMPACT_SHRINK) return fail(c, PIE_E_INVAL, "unknown compaction flags 0x%x", flags);
+    if (c->cap_rows == 0) return fail(c, PIE_E_STATE, "no table loaded");
+    if (c->n_flight || c->b_flight) return fail(c, PIE_E_STATE, "a scan is in flight");
+    PIE_HIP(c, hipSetDevice(c->device));
+    int rc = sync_all(c); // queued appends and touches land first
+    if (rc) return rc;
+    hipStream_t s = c->stream;
+    const long long n = c->n;
+    const int users = c->n_users;
+    const bool shrink = (flags & PIE_COMPACT_SHRINK) != 0;
+    const bool sharded = c->d_shard_rows != nullptr;
+    int blocks = 0;
+    long long rpu = 0;
+    compact_plan(c, n, &blocks, &rpu);
+    const int units = blocks * kK1Waves;
+    int *d_cnt = nullptr, *m_new = nullptr, *m_old = nullptr, *o_user = nullptr, *o_disc = nullptr, *o_row = nullptr;
+    long long *d_off = nullptr, *o_start = nullptr, *o_end = nullptr;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    auto cleanup = [&]() {
+        dfree(d_cnt); dfree(d_off); dfree(m_new); dfree(m_old);
+        dfree(o_start); dfree(o_end); dfree(o_user); dfree(o_disc); dfree(o_row);
+        for (hipEvent_t& e : ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
+    };
+#define PIE_TRY(call)                                                                                 \
+    do {                                                                                              \
+        hipError_t e_ = (call);                                                                       \
+        if (e_ != hipSuccess) {                                                                       \
+            cleanup();                                                                                \
+            return fail(c, e_ == hipErrorOutOfMemory ? PIE_E_NOMEM : PIE_E_HIP, "%s: %s", #call, hipGetErrorString(e_)); \
+        }                                                                                             \
+    } while (0)
+    for (hipEvent_t& e : ev) PIE_TRY(hipEventCreate(&e));
+    // 1. how many rows every unit keeps -> where its rows go
+    PIE_TRY(hipMalloc(&d_cnt, (size_t)units * 4));
+    PIE_TRY(hipMalloc(&d_off, ((size_t)units + 1) * 8));
+    PIE_TRY(hipMalloc(&m_new, (size_t)(n > 0 ? n : 1) * 4));
+    PIE_TRY(hipEventRecord(ev[0], s));
+    hipLaunchKernelGGL(k_compact_count, dim3(blocks), dim3(256), 0, s, c->d_end, n, rpu, (long long)dead_before, d_cnt);
+    // one block's sweep holds a few thousand counts; beyond that the two-level form (a chunk per thread, one block-wide scan)
+    if (units <= 4096) hipLaunchKernelGGL(k_block_prefix, dim3(1), dim3(256), 0, s, d_cnt, units, d_off, (unsigned long long*)nullptr);
+    else hipLaunchKernelGGL(k_block_prefix_wide, dim3(1), dim3(1024), 0, s, d_cnt, units, d_off, (unsigned long long*)nullptr, (HostSummary*)nullptr, 0ull);
+    PIE_TRY(hipGetLastError());
+    PIE_TRY(hipEventRecord(ev[1], s)); // the count pass ends here: the copy, the wait and the allocations below are host time
+    long long kept = 0;
+    PIE_TRY(hipMemcpyAsync(&kept, d_off + units, 8, hipMemcpyDeviceToHost, s));
+    PIE_TRY(hipStreamSynchronize(s));
+    if (kept < 0 || kept > n) { cleanup(); return fail(c, PIE_E_HIP, "compaction counted %lld kept rows of %lld", kept, n); }
+    const size_t rows_kept = (size_t)(kept > 0 ? kept : 1);
+    PIE_TRY(hipMalloc(&m_old, rows_kept * 4));
+    const bool same = kept == n && !(shrink && c->cap_rows > (long long)rows_kept);
+    long long shard_kept = 0;
+    float ms_count = 0, ms_write = 0;
+    if (same) {
+        // nothing to move: the columns, their keys and everything derived from them stay as they are
+        PIE_TRY(hipEventRecord(ev[2], s));
+        if (n > 0) hipLaunchKernelGGL(k_compact_identity, dim3(c->n_cus * 8), dim3(256), 0, s, n, m_new, m_old);
+        PIE_TRY(hipGetLastError());
+        PIE_TRY(hipEventRecord(ev[3], s));
+        PIE_TRY(hipStreamSynchronize(s));
+    } else {
+        // 2. the kept rows into fresh columns: of the table's capacity (swapped in below), or of the kept rows (a right-sized table)
+        const size_t rows_out = shrink ? rows_kept : (size_t)c->cap_rows;
+        PIE_TRY(hipMalloc(&o_start, rows_out * 8));
+        PIE_TRY(hipMalloc(&o_end, rows_out * 8));
+        PIE_TRY(hipMalloc(&o_user, rows_out * 4));
+        PIE_TRY(hipMalloc(&o_disc, rows_out * 4));
+        if (sharded) PIE_TRY(hipMalloc(&o_row, rows_kept * 4));
+        PIE_TRY(hipEventRecord(ev[2], s));
+        if (n > 0) hipLaunchKernelGGL(k_compact_write, dim3(blocks), dim3(256), 0, s, c->d_start, c->d_end, c->d_user, c->d_disc,
+                                      (const int*)c->d_shard_rows, c->shard_rows_n, n, rpu, (long long)dead_before, d_off, o_start, o_end, o_user,
+                                      o_disc, o_row, m_new, m_old);
+        PIE_TRY(hipGetLastError());
+        PIE_TRY(hipEventRecord(ev[3], s));
+        PIE_TRY(hipStreamSynchronize(s));
+        if (sharded) {
+            // rows appended after pie_shard_table have no global row and sit behind the mapped ones, before and after: the map
+            // now covers the kept rows among the first shard_rows_n, i.e. the new rows whose old row lies below shard_rows_n
+            if (c->shard_rows_n >= n) shard_kept = kept;
+            else {
+                hipLaunchKernelGGL(k_compact_lower_bound, dim3(1), dim3(1), 0, s, (const int*)m_old, kept, c->shard_rows_n, d_off);
+                PIE_TRY(hipGetLastError());
+                PIE_TRY(hipMemcpyAsync(&shard_kept, d_off, 8, hipMemcpyDeviceToHost, s));
+                PIE_TRY(hipStreamSynchronize(s));
+            }
+        }
+    }
+    PIE_TRY(hipEventElapsedTime(&ms_count, ev[0], ev[1]));
+    PIE_TRY(hipEventElapsedTime(&ms_write, ev[2], ev[3]));
+#undef PIE_TRY
+    if (!same) {
+        // 3. the table takes the new columns: as a new table of the same users (what the last scans learned is forgotten, the
+        // ordered run is invalid, results and queues are gone), in the old capacity or a right-sized one
+        if (shrink) {
+            // the kept rows already sit in right-sized columns: the new table is built around them (as in pie_shard_table, a
+            // failure past this point leaves the context without a table)
+            free_table(c);
+            c->adopt_start = o_start; c->adopt_end = o_end; c->adopt_user = o_user; c->adopt_disc = o_disc;
+            o_start = o_end = nullptr;
+            o_user = o_disc = nullptr;
+            rc = ensure_capacity(c, kept, users);
+            dfree(c->adopt_start); dfree(c->adopt_end); dfree(c->adopt_user); dfree(c->adopt_disc); // taken (null by now) unless it failed early
+            if (rc) { cleanup(); return rc; }
+        } else {
+            rc = ensure_capacity(c, kept, users);
+            if (rc) { cleanup(); return rc; }
+            dfree(c->d_start); dfree(c->d_end); dfree(c->d_user); dfree(c->d_disc);
+            c->d_start = o_start; c->d_end = o_end; c->d_user = o_user; c->d_disc = o_disc;
+            o_start = o_end = nullptr;
+            o_user = o_disc = nullptr;
+        }
+        if (sharded) {
+            dfree(c->d_shard_rows);
+            c->d_shard_rows = o_row;
+            o_row = nullptr;
+            c->shard_rows_n = shard_kept;
+        }
+    } else {
+        cmp_forget(c);
+    }
+    // results name rows by index, and so does a dispatch queue: whatever is left of earlier calls is forgotten
+    queue_forget(c);
+    c->res = nullptr;
+    for (Slot& sl : c->slot) sl.have_result = false;
+    c->bres = nullptr;
+    for (BatchSlot& b : c->bslot) b.have_result = false;
+    c->d_cmp_new_of_old = m_new;
+    c->d_cmp_old_of_new = m_old;
+    m_new = m_old = nullptr;
+    c->cmp_n_old = n;
+    c->cmp_n_kept = kept;
+    c->cmp_valid = true;
+    c->compactions++;
+    c->cmp_write_ms = (double)ms_write;
+    c->cmp_count_ms = (double)ms_count;
+    cleanup();
+    if (n_kept_out) *n_kept_out = (size_t)kept;
+    if (same) return PIE_OK;
+    rc = build_keys(c, 0);
+    if (rc) return rc;
+    PIE_HIP(c, hipStreamSynchronize(s));
+    return PIE_OK;
+}
+
+int pie_compact_maps(pie_ctx* c, int32_t* new_of_old_out, int32_t* old_of_new_out, size_t* n_old_out, size_t* n_kept_out)
+{
+    if (!c) return PIE_E_INVAL;
+    if (!c->cmp_valid) return fail(c, PIE_E_STATE, "no compaction maps: the rows were renumbered since, or never compacted");
+    PIE_HIP(c, hipSetDevice(c->device));
+    if (new_of_old_out && c->cmp_n_old)
+        PIE_HIP(c, hipMemcpyAsync(new_of_old_out, c->d_cmp_new_of_old, (size_t)c->cmp_n_old * 4, hipMemcpyDeviceToHost, c->stream));
+    if (old_of_new_out && c->cmp_n_kept)
+        PIE_HIP(c, hipMemcpyAsync(old_of_new_out, c->d_cmp_old_of_new, (size_t)c->cmp_n_kept * 4, hipMemcpyDeviceToHost, c->stream));
+    PIE_HIP(c, hipStreamSynchronize(c->stream));
+    if (n_old_out) *n_old_out = (size_t)c->cmp_n_old;
+    if (n_kept_out) *n_kept_out = (size_t)c->cmp_n_kept;
+    return PIE_OK;
+}
+
+int pie_compact_map_device_ptrs(pie_ctx* c, void** new_of_old_dev, void** old_of_new_dev, size_t* n_old_out, size_t* n_kept_out)
+{
+    if (!c) return PIE_E_INVAL;
+    if (!c->cmp_valid) return fail(c, PIE_E_STATE, "no compaction maps: the rows were renumbered since, or never compacted");
+    if (new_of_old_dev) *new_of_old_dev = c->d_cmp_new_of_old;
+    if (old_of_new_dev) *old_of_new_dev = c->d_cmp_old_of_new;
+    if (n_old_out) *n_old_out = (size_t)c->cmp_n_old;
+    if (n_kept_out) *n_kept_out = (size_t)c->cmp_n_kept;
+    return PIE_OK;
+}
+
+int pie_compact_translate(pie_ctx* c, int32_t* rows_inout, size_t k)
+{
+    if (!c) return PIE_E_INVAL;
+    if (!c->cmp_valid) return fail(c, PIE_E_STATE, "no compaction maps: the rows were renumbered since, or never compacted");
+    if (k == 0) return PIE_OK;
+    if (!rows_inout) return fail(c, PIE_E_INVAL, "NULL row list");
+    PIE_HIP(c, hipSetDevice(c->device));
+    int rc = ensure_stage(c, k * 4);
+    if (rc) return rc;
+    hipStream_t s = c->stream;
+    memcpy(c->h_stage, rows_inout, k * 4);
+    PIE_HIP(c, hipMemcpyAsync(c->d_stage, c->h_stage, k * 4, hipMemcpyHostToDevice, s));
+    const unsigned grid = (unsigned)((k + 255) / 256) < (unsigned)c->n_cus * 8 ? (unsigned)((k + 255) / 256) : (unsigned)c->n_cus * 8;
+    hipLaunchKernelGGL(k_compact_translate, dim3(grid), dim3(256), 0, s, reinterpret_cast<int*>(c->d_stage), (long long)k,
+                       (const int*)c->d_cmp_new_of_old, c->cmp_n_old);
+    PIE_HIP(c, hipGetLastError());
+    PIE_HIP(c, hipMemcpyAsync(c->h_stage, c->d_stage, k * 4, hipMemcpyDeviceToHost, s));
+    PIE_HIP(c, hipStreamSynchronize(s));
+    memcpy(rows_inout, c->h_stage, k * 4);
     return PIE_OK;
 }
 

@@ -15,7 +15,8 @@
 // (its row index may still sit in a result the caller holds), and once the dead rows outweigh the live ones the table is
 // compacted — live rows re-uploaded in order, the token map re-pointed — so N follows the live sessions, not every login
 // ever made.  A session that getSession() finds expired keeps its real `end` on the device (it is dead for every scan
-// anyway) so that the expired-session dispatch queue still reports it.
+// anyway) so that the expired-session dispatch queue still reports it.  compactDevice() does the same on the device
+// (pie_compact_rows: no re-upload, works behind a synthetic base); createStore({deviceCompact: true}) makes it the automatic one.
 const crypto = require('crypto');
 const fs = require('fs');
 const path = require('path');
@@ -50,12 +51,14 @@ function createStore(options){
   let nGone = 0;                                   // rows that no scan, queue or lookup will ever need again
   let listBuf = new Int32Array(1024);              // reused row-list buffer of the device scans (grown, never per call)
   const compactMinRows = opts.compactMinRows === undefined ? 4096 : opts.compactMinRows;
+  const deviceCompact = opts.deviceCompact === true;   // the automatic compaction runs on the device (compactDevice) instead of re-uploading
   // A resident BASE of anonymous rows (opts.base = {rows, users, disc, seed?, flags?}): the synthetic corpus of SURVEY.md 8d
   // generated on the device (pie_gen_synthetic), users 'user-0' .. pre-registered — the way a 10^8-session table exists at all
   // on one Node process (the host keeps a map entry per session it ISSUED, not per row of history).  Sessions created through
   // this module are appended behind the base; device row = base + host row.  The full-table list operations that report rows
   // back to the host map (deleteSessionsForUser, purges, compaction, save) are not offered on a based store.
   let base = 0;
+  const based = !!opts.base;                       // a kind of store, not a row count: compactDevice may bring `base` down to 0
   if(opts.base){
     const b = opts.base;
     for(let u = 0; u < b.users; u++){ denseUserEarly('user-' + u); }
@@ -63,7 +66,7 @@ function createStore(options){
     base = b.rows;
   }
   function denseUserEarly(userId){ userIndex.set(userId, userIds.length); userIds.push(userId); }
-  const noBase = what => { if(base > 0){ throw new Error(what + ' is not offered on a store with a synthetic base'); } };
+  const noBase = what => { if(based){ throw new Error(what + ' is not offered on a store with a synthetic base'); } };
 
   function rowList(){
     if(listBuf.length < rows.length){
@@ -85,11 +88,15 @@ function createStore(options){
   // push host-side mutations to the device: appended rows first, then end updates, so a row that was created
   // and touched in the same batch ends with the touched value
   function flush(){
-    if(base === 0 && rows.length >= compactMinRows && nGone * 2 > rows.length){
-      compact();
+    if(rows.length >= compactMinRows && nGone * 2 > rows.length){
+      if(deviceCompact){ compactDevice(); return; }   // it flushes what is pending itself
+      if(!based){ compact(); }
     }
+    flushPending();
+  }
+  function flushPending(){
     const k = rows.length - uploaded;
-    if(k > 0 || (uploaded === 0 && base === 0)){
+    if(k > 0 || (uploaded === 0 && !based)){
       const s = new BigInt64Array(k), e = new BigInt64Array(k);
       const u = new Int32Array(k), d = new Int32Array(k);
       for(let i = 0; i < k; i++){
@@ -101,7 +108,7 @@ function createStore(options){
         pendingEnd.delete(uploaded + i);
       }
       const nUsers = Math.max(userIds.length, 1);
-      if(uploaded === 0 && base === 0){
+      if(uploaded === 0 && !based){
         native.loadColumns(ctx, s, e, u, d, nUsers);
       }else{
         native.appendRows(ctx, s, e, u, d, nUsers);
@@ -164,6 +171,51 @@ function createStore(options){
     compactions++;
   }
   let compactions = 0;
+
+  // The same on the device (pie_compact_rows): the dead rows are dropped in place, in table order, nothing is re-uploaded and
+  // no host record per row is needed — so it also works behind a synthetic base, whose rows only the device knows.
+  // deadBefore (ms; default: tombstones only) also drops the sessions that expired at or before it; shrink re-sizes the
+  // device table and its workspace to the kept rows.  The host's own records follow through ONE translate call: records whose
+  // row was dropped go (their tokens with them), the others are re-pointed.  -> {kept, base, dropped}: device rows kept, the
+  // base rows among them (device row = base + host row, as before), host records dropped.
+  function compactDevice(options){
+    const o = options || {};
+    const deadBefore = o.deadBefore === undefined || o.deadBefore === null ? END_NONE : BigInt(o.deadBefore);
+    // a row a purge reported is gone for the host but keeps its real `end` on the device: it becomes a tombstone now, so that
+    // the device drops exactly what the host compaction would
+    for(let i = 0; i < uploaded; i++){
+      if(rows[i].gone){ pendingEnd.set(i, END_NONE); }
+    }
+    flushPending();
+    const kept = native.compactRows(ctx, deadBefore, o.shrink === true);
+    const list = new Int32Array(rows.length);
+    for(let i = 0; i < rows.length; i++){ list[i] = base + i; }
+    native.compactTranslate(ctx, list);
+    const keep = [];
+    for(let i = 0; i < rows.length; i++){
+      if(list[i] >= 0){ keep.push(rows[i]); }
+      else if(rows[i].tokenHash !== null){ rowOfToken.delete(rows[i].tokenHash); rows[i].tokenHash = null; }
+    }
+    const dropped = rows.length - keep.length;
+    // order is preserved and the host's rows are the tail of the table: the base rows that were kept come first
+    const newBase = keep.length > 0 ? list[rows.indexOf(keep[0])] : kept;
+    if(newBase + keep.length !== kept){ throw new Error('compactDevice: the host rows are not the tail of the compacted table'); }
+    rows.length = 0;
+    rowOfToken.clear();
+    nGone = 0;
+    for(const r of keep){
+      if(r.tokenHash !== null){ rowOfToken.set(r.tokenHash, rows.length); }
+      if(r.gone){ nGone++; }
+      rows.push(r);
+    }
+    base = newBase;
+    uploaded = rows.length;
+    pendingEnd = new Map();
+    out = null;
+    generation++;
+    compactions++;
+    return {kept, base, dropped};
+  }
 
   // createSession(userId[, disciplineId]) -> {token, expiresAt}.  The second argument is [DERIVED] (the reference
   // record has no discipline field): an id of disciplineConfig.DISCIPLINES, default = the default discipline.
@@ -309,7 +361,7 @@ function createStore(options){
   }
   var feedBuf = null;
   function userFeed(u){
-    const want = Math.max(base > 0 ? 65536 : rows.length, 1);
+    const want = Math.max(based ? 65536 : rows.length, 1);
     if(feedBuf === null || feedBuf.length < want){
       feedBuf = new Int32Array(want);
     }
@@ -367,7 +419,7 @@ function createStore(options){
     return native[fn](ctx, nows, cutoffs, masks);
   }
   function batchUserFeed(qi, u){
-    const want = Math.max(base > 0 ? 4096 : rows.length, 1);
+    const want = Math.max(based ? 4096 : rows.length, 1);
     if(feedBuf === null || feedBuf.length < want){
       feedBuf = new Int32Array(want);
     }
@@ -447,7 +499,7 @@ function createStore(options){
     createSession, getSession, touchSession, deleteSession, deleteSessionsForUser, purgeExpiredSessions, purgeRetention,
     SESSION_TTL_MS, SESSION_COOKIE_NAME,
     scanFeeds, scanDevice, userFeed, scanBatchDevice, batchUserFeed, batchFetch, BATCH_MAX, scanWideDevice, WIDE_MAX, fetchRows, expiredRows, archivedRows, flush, close, save, restore,
-    compact, compactions: () => compactions, tableRows: () => base + rows.length, baseRows: () => base,
+    compact, compactDevice, compactions: () => compactions, tableRows: () => base + rows.length, baseRows: () => base,
     userIds: () => userIds,
     userIndexOf: userId => (userIndex.has(userId) ? userIndex.get(userId) : -1),
     size: () => rowOfToken.size,
