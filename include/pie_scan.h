@@ -434,6 +434,15 @@ int pie_compact_translate(pie_ctx *ctx, int32_t *rows_inout, size_t k);
 int pie_compact_geometry(pie_ctx *ctx, size_t n, int32_t *rows_per_wave_step_out, int32_t *rows_per_block_step_out,
                          int64_t *rows_per_unit_out, int32_t *blocks_out);
 
+/* Host only, no context, no GPU: what the batched pass stores per selected row.  A row's 64-bit query mask is
+ * live[r] & win[w] & disc[d] (r: queries whose `now` lies below the row's end, w: queries whose cutoff is <= its start, d: its
+ * discipline), so the pass keeps the 20-bit code r | w << 7 | d << 14 in the row's bucket slot and the tail expands it through
+ * the batch's tables.  For every given row: code_out = that code, mask_out = the code expanded through the tables the host
+ * builds for these queries (bit q = query q selects the row; queries marked in fallback[], which may be NULL, are left out of
+ * the tables).  Either output may be NULL.  For tests. */
+int pie_batch_mask_codes(const pie_query *queries, int n_q, const uint8_t *fallback, int32_t n_disc, const int64_t *start,
+                         const int64_t *end, const int32_t *disc, size_t n_rows, uint32_t *code_out, uint64_t *mask_out);
+
 /* ---- communicator: the sharded table behind the C ABI (SURVEY.md 8b "pie_ctx_create(device_ids[], n, ...)", 8e) --------
  * A pie_comm owns one scan context per GPU and one RCCL communicator; the session table is sharded by user hash
  * (pie_shard_of) and the cross-user reassembly — every rank receives every rank's per-user offsets and row lists — is an

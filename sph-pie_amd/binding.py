@@ -107,6 +107,7 @@ _SIGS = [
     ("pie_batch_union_wide_device_ptrs", C.c_int, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_int), C.POINTER(C.c_size_t)]),
     ("pie_batch_read_union_wide", C.c_int, [_P, _P, _P, _P, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_size_t)]),
     ("pie_batch_pack_union_wide_device", C.c_int, [_P, _P, C.c_size_t, C.c_size_t]),
+    ("pie_batch_mask_codes", C.c_int, [C.POINTER(PieQuery), C.c_int, _P, C.c_int32, _P, _P, _P, C.c_size_t, _P, _P]),
     ("pie_batch_read_results", C.c_int, [_P, C.c_int, _P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("pie_batch_result_device_ptrs", C.c_int, [_P, C.c_int, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P)]),
     ("pie_batch_read_user_feed", C.c_int, [_P, C.c_int, C.c_int32, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
@@ -947,6 +948,23 @@ class PieComm:
 
 def shard_of(user, n_shards):
     return load_library().pie_shard_of(int(user), int(n_shards))
+
+
+def batch_mask_codes(queries, n_disc, start, end, disc, fallback=None):
+    """Host only (pie_batch_mask_codes): per row the 20-bit code r | w << 7 | d << 14 the batched pass stores in a bucket slot,
+    and that code expanded to the row's 64-bit query mask through the tables the library builds for `queries`.
+    -> (codes uint32[n], masks uint64[n])"""
+    arr = (PieQuery * len(queries))()
+    for k, (now, cutoff, mask) in enumerate(queries):
+        arr[k].now, arr[k].cutoff, arr[k].mask = int(now), int(cutoff), int(mask) & (2 ** 64 - 1)
+    start, end, disc = _col(start, np.int64), _col(end, np.int64), _col(disc, np.int32)
+    fb = None if fallback is None else _col(fallback, np.uint8)
+    n = start.shape[0]
+    codes, masks = np.empty(n, np.uint32), np.empty(n, np.uint64)
+    rc = load_library().pie_batch_mask_codes(arr, len(queries), _ptr(fb), int(n_disc), _ptr(start), _ptr(end), _ptr(disc), n, _ptr(codes), _ptr(masks))
+    if rc != 0:
+        raise PieError(rc, "pie_batch_mask_codes: bad argument")
+    return codes, masks
 
 
 def tz_table(zone, from_ms=0, to_ms=4102444800000):

@@ -2041,6 +2041,22 @@ struct BatchTables {
 };
 static_assert(sizeof(BatchTables) % 4 == 0, "copied to LDS word by word");
 
+// The query mask of a selected row is never arbitrary: it is live[r] & win[w] & disc[d] with r, w in 0..64 and d in 0..63 —
+// 20 bits.  The pass stores that CODE in the row's bucket slot (BktRec::pad) instead of the mask (one 16-byte store per selected
+// row whatever Q; a first version kept mask bits 32..63 in a second array: a second scattered store per row, and a second
+// scattered load per bucket row in the tail), and one block of the pass publishes the batch's three tables (kMaskTabWords x 8 =
+// 1552 bytes) to memory of the batch slot; the tail, a later launch, copies them to LDS and expands every code it loads.
+constexpr int kMaskTabWords = 2 * (kBatchMax + 1) + 64; // live[65] | win[65] | disc[64], as they lie in BatchTables
+static_assert(offsetof(BatchTables, win) == offsetof(BatchTables, live) + (kBatchMax + 1) * 8 &&
+              offsetof(BatchTables, disc) == offsetof(BatchTables, win) + (kBatchMax + 1) * 8 &&
+              offsetof(BatchTables, nk) == offsetof(BatchTables, live) + kMaskTabWords * 8, "the three mask tables are published as one block");
+__host__ __device__ __forceinline__ int mask_code(int r, int w, int d) { return r | (w << 7) | ((d & 63) << 14); }
+// mt = live[65] | win[65] | disc[64]; an empty slot's code is 0: live[0] = 0
+__host__ __device__ __forceinline__ unsigned long long mask_of_code(const unsigned long long* mt, int code)
+{
+    return mt[code & 127] & mt[(kBatchMax + 1) + ((code >> 7) & 127)] & mt[2 * (kBatchMax + 1) + ((code >> 14) & 63)];
+}
+
 template <class KT>
 struct BatchScanArgs {
     const PayRec* pay;
@@ -2053,8 +2069,8 @@ struct BatchScanArgs {
     int dshift;                // log2 of the union bucket's slot capacity
     int* counts;               // union histogram (transposed user order, hist_index)
     Summary* summary;          // the batch's summary: bad rows and the row statistics of the pass
-    BktRec* direct;            // union bucket slots, (1 << dshift) per user; BktRec::pad = the queries (0..31) that selected the row
-    unsigned* direct_hi;       // queries 32..63 of every slot (written when n_q > 32)
+    BktRec* direct;            // union bucket slots, (1 << dshift) per user; BktRec::pad = the row's mask code (mask_code)
+    unsigned long long* mtab;  // [kMaskTabWords] of the batch slot: the tables the tail expands the codes with (written by block 0)
     int run_shift;             // see KeyedArgs
     const HotRec* hot;         // non-null: the candidates are the hot index's entries [hot_lo, hot_main + *hot_delta_n), not the key stream
     long long hot_lo, hot_main;
@@ -2100,10 +2116,11 @@ __device__ __forceinline__ void scan_batch_body(const BatchScanArgs<KT>& a, int 
         for (int i = threadIdx.x; i < (int)(sizeof(BatchTables) / 4); i += kK1Threads) dst[i] = src[i];
     }
     __syncthreads();
+    if (bid == 0) // the batch's mask tables for its tail (a later launch)
+        for (int i = threadIdx.x; i < kMaskTabWords; i += kK1Threads) a.mtab[i] = reinterpret_cast<const unsigned long long*>(reinterpret_cast<const char*>(&tab) + offsetof(BatchTables, live))[i];
     int* rrow = ring_row[wave];
     int* rkey = ring_key[wave];
     int lhead = 0, lfill = 0, ncand = 0; // wave-uniform
-    const int nq = a.n_q;
     const int cap = 1 << a.dshift;
 
     // the Q predicates of one candidate per lane, `r` = the queries whose `now` lies below the row's `end` (a prefix of the
@@ -2122,9 +2139,8 @@ __device__ __forceinline__ void scan_batch_body(const BatchScanArgs<KT>& a, int 
                 BktRec rec;
                 rec.start = pr.start;
                 rec.idx = row;
-                rec.pad = (int)(unsigned)qmask;
+                rec.pad = mask_code(r, w, pr.disc);
                 a.direct[((long long)pr.user << a.dshift) + rank] = rec;
-                if (nq > 32) a.direct_hi[((long long)pr.user << a.dshift) + rank] = (unsigned)(qmask >> 32);
             }
         }
     };
@@ -2279,8 +2295,8 @@ struct UnionTailArgs {
     long long tiles_off, ctl_off, summary_off, mq_off; // byte offsets inside a span
     char* zero_span;           // the span the batch after the next will use: zeroed here
     long long zero_total16;    // 16-byte vectors of a span
-    const BktRec* direct;      // union bucket slots (BktRec::pad = query bits 0..31)
-    const unsigned* direct_hi; // query bits 32..63 of every slot (batches of more than 32 queries)
+    const BktRec* direct;      // union bucket slots (BktRec::pad = the row's mask code)
+    const unsigned long long* mtab; // the batch's mask tables (kMaskTabWords), published by its pass
     long long* uoff;           // [n_users + 1]
     int* urows;                // [n_users << dshift]
     unsigned* umlo;
@@ -2339,8 +2355,22 @@ __device__ __forceinline__ void union_tail_body(const UnionTailArgs& t, int gbid
     __shared__ long long s_total;
     __shared__ unsigned int tile_s;
     __shared__ int is_last;
+    __shared__ unsigned long long s_mt[kMaskTabWords];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int nblk = t.tiles, U = t.n_users, nq = t.n_q;
+    if ((int)threadIdx.x < kMaskTabWords) s_mt[threadIdx.x] = t.mtab[threadIdx.x];
+    // a slot's mask code -> the row's query mask (lo: queries 0..31, hi: 32..63)
+    auto expand = [&](int code, unsigned& lo, unsigned& hi) {
+        if constexpr (HI) {
+            const unsigned long long m = mask_of_code(s_mt, code);
+            lo = (unsigned)m;
+            hi = (unsigned)(m >> 32);
+        } else { // the low words alone
+            const unsigned* w = reinterpret_cast<const unsigned*>(s_mt);
+            lo = w[2 * (code & 127)] & w[2 * ((kBatchMax + 1) + ((code >> 7) & 127))] & w[2 * (2 * (kBatchMax + 1) + ((code >> 14) & 63))];
+            hi = 0;
+        }
+    };
     if (t.zero_span) {
         const int4 z = make_int4(0, 0, 0, 0);
         int4* zs = reinterpret_cast<int4*>(t.zero_span);
@@ -2371,15 +2401,10 @@ __device__ __forceinline__ void union_tail_body(const UnionTailArgs& t, int gbid
         r.start = INT64_MAX;
         r.idx = INT32_MAX;
         r.pad = 0;
-        unsigned h = 0;
-        if (nn <= 8 && k < nn) {
-            r = src[k];
-            if constexpr (HI) h = t.direct_hi[slot0 + k];
-        }
+        if (nn <= 8 && k < nn) r = src[k];
         ks[k] = r.start;
         ki[k] = r.idx;
-        km[k] = (unsigned)r.pad;
-        kh[k] = h;
+        expand(r.pad, km[k], kh[k]);
     }
     if (nn >= 2 && nn <= 8) {
 #pragma unroll
@@ -2557,27 +2582,25 @@ __device__ __forceinline__ void union_tail_body(const UnionTailArgs& t, int gbid
             r.start = INT64_MAX;
             r.idx = INT32_MAX;
             r.pad = 0;
-            unsigned hi = 0;
-            if (l < nb) {
-                r = (t.direct + ((long long)ub << t.dshift))[l];
-                if constexpr (HI) hi = t.direct_hi[((long long)ub << t.dshift) + l];
-            }
+            if (l < nb) r = (t.direct + ((long long)ub << t.dshift))[l];
+            unsigned lo, hi;
+            expand(r.pad, lo, hi);
             const int rank = rank_in_row16(r.start, r.idx);
             if (l < nb) {
                 const long long pos = rq + rank;
                 t.urows[pos] = r.idx;
-                t.umlo[pos] = (unsigned)r.pad;
+                t.umlo[pos] = lo;
                 if constexpr (HI) t.umhi[pos] = hi;
                 if (t.msg && pos < t.msg_cap) {
                     msg_store(msg_rows + pos, r.idx);
-                    msg_store(msg_lo + pos, r.pad);
+                    msg_store(msg_lo + pos, (int)lo);
                     if constexpr (HI) msg_store(msg_hi + pos, (int)hi);
                 }
             }
             // per-query totals of these (up to 64) records: lane q collects query q's
 #pragma unroll 4
             for (int q = 0; q < (nq < 32 ? nq : 32); ++q) {
-                const unsigned c = (unsigned)__popcll(__ballot(((unsigned)r.pad >> q) & 1u));
+                const unsigned c = (unsigned)__popcll(__ballot((lo >> q) & 1u));
                 if (lane == q) acc += c;
             }
             if constexpr (HI) {
@@ -2602,18 +2625,16 @@ __device__ __forceinline__ void union_tail_body(const UnionTailArgs& t, int gbid
             r.start = INT64_MAX;
             r.idx = INT32_MAX;
             r.pad = 0;
-            unsigned hi = 0;
-            if (lane < nb) {
-                r = (t.direct + ((long long)ub << t.dshift))[lane];
-                if constexpr (HI) hi = t.direct_hi[((long long)ub << t.dshift) + lane];
-            }
+            if (lane < nb) r = (t.direct + ((long long)ub << t.dshift))[lane];
+            unsigned lo, hi;
+            expand(r.pad, lo, hi);
             int rank = 0;
             for (int j = 0; j < nb; ++j) {
                 const long long sj = __shfl(r.start, j, kWave);
                 const int ij = __shfl(r.idx, j, kWave);
                 rank += key_less(sj, ij, r.start, r.idx) ? 1 : 0;
                 // lane q counts the rows of this bucket that query q selected (the per-query totals)
-                unsigned mj = (unsigned)__shfl(r.pad, j, kWave);
+                unsigned mj = (unsigned)__shfl((int)lo, j, kWave);
                 if constexpr (HI) {
                     const unsigned hj = (unsigned)__shfl((int)hi, j, kWave);
                     mj = lane >= 32 ? hj : mj;
@@ -2623,11 +2644,11 @@ __device__ __forceinline__ void union_tail_body(const UnionTailArgs& t, int gbid
             if (lane < nb) {
                 const long long pos = rq + rank;
                 t.urows[pos] = r.idx;
-                t.umlo[pos] = (unsigned)r.pad;
+                t.umlo[pos] = lo;
                 if constexpr (HI) t.umhi[pos] = hi;
                 if (t.msg && pos < t.msg_cap) {
                     msg_store(msg_rows + pos, r.idx);
-                    msg_store(msg_lo + pos, r.pad);
+                    msg_store(msg_lo + pos, (int)lo);
                     if constexpr (HI) msg_store(msg_hi + pos, (int)hi);
                 }
             }

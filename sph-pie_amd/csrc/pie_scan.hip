@@ -144,8 +144,8 @@ struct BatchSlot {
     unsigned long long seq = 0;
     char* span = nullptr;              // this batch's span (histogram | tile granules | ctl | summary + row statistics | mq slots)
     char* zero_span = nullptr;         // the span its tail zeroes
-    BktRec* direct = nullptr;          // union bucket slots: [cap_users << bdshift]; BktRec::pad = queries 0..31 that selected the row
-    unsigned* direct_hi = nullptr;     // ... queries 32..63
+    BktRec* direct = nullptr;          // union bucket slots: [cap_users << bdshift]; BktRec::pad = the row's mask code (mask_code)
+    unsigned long long* mtab = nullptr; // [kMaskTabWords] the tables that expand the codes: written by this batch's pass, read by its tail
     long long* uoff = nullptr;         // the union result: [cap_users + 1]
     int* urows = nullptr;              // [cap_users << bdshift]
     unsigned* umlo = nullptr;
@@ -531,7 +531,7 @@ void free_batch(pie_ctx* c)
 {
     for (BatchSlot& b : c->bslot) {
         dfree(b.counts_ord); dfree(b.offsets); dfree(b.direct); dfree(b.out_idx);
-        dfree(b.direct_hi); dfree(b.uoff); dfree(b.urows); dfree(b.umlo); dfree(b.umhi);
+        dfree(b.mtab); dfree(b.uoff); dfree(b.urows); dfree(b.umlo); dfree(b.umhi);
         b.lists_q = 0;
         for (int q = 0; q < kBatchMax; ++q) { dfree(b.over_idx[q]); b.over_cap[q] = 0; b.idx_of[q] = nullptr; b.list_ok[q] = false; }
         b.in_flight = b.k2_pending = b.have_result = b.union_ok = b.union_part = false;
@@ -1587,6 +1587,7 @@ bool ordered_batch_wanted(const pie_ctx* c)
 }
 
 void fill_batch_tables(const pie_ctx* c, const BatchSlot& b, const pie_query* qs, const unsigned* nk, BatchTables& t);
+void fill_batch_tables(int n_disc, int n_q, const bool* fallback, const pie_query* qs, const unsigned* nk, BatchTables& t);
 
 // a batch on the ordered run (up to 64 queries): scan, ONE prefix, emit, publish — see pie_ordered.h "the UNION form"
 void launch_ordered_union(pie_ctx* c, BatchSlot& b, hipStream_t s, const pie_query* qs, bool fine)
@@ -2260,7 +2261,7 @@ int ensure_batch(pie_ctx* c, int lane)
     for (int i = 0; i < kBatchSlots; ++i) {
         BatchSlot& b = c->bslot[lane * kBatchSlots + i];
         PIE_HIP(c, hipMalloc(&b.direct, slots * sizeof(BktRec)));
-        PIE_HIP(c, hipMalloc(&b.direct_hi, slots * 4));
+        PIE_HIP(c, hipMalloc(&b.mtab, kMaskTabWords * 8));
         PIE_HIP(c, hipMalloc(&b.uoff, ((size_t)c->cap_users + 2) * 8));
         PIE_HIP(c, hipMalloc(&b.urows, ucap * 4));
         PIE_HIP(c, hipMalloc(&b.umlo, ucap * 4));
@@ -2348,7 +2349,7 @@ void fill_tail_args(pie_ctx* c, BatchSlot& b, UnionTailArgs& t)
     t.zero_span = b.zero_span;   // the next-but-one batch's span
     t.zero_total16 = (long long)(batch_span_bytes(c) / 16);
     t.direct = b.direct;
-    t.direct_hi = b.direct_hi;
+    t.mtab = b.mtab;
     t.uoff = b.uoff; t.urows = b.urows; t.umlo = b.umlo; t.umhi = b.umhi;
     t.host = b.bh_dev;
     t.seq = b.seq;
@@ -2360,9 +2361,15 @@ void fill_tail_args(pie_ctx* c, BatchSlot& b, UnionTailArgs& t)
 // the predicate tables of a batch (pie_kernels.h BatchTables) over the queries that take part in the pass
 void fill_batch_tables(const pie_ctx* c, const BatchSlot& b, const pie_query* qs, const unsigned* nk, BatchTables& t)
 {
+    fill_batch_tables(c->n_disc, b.n_q, b.fallback, qs, nk, t);
+}
+
+// ... of n_q queries, those marked in fallback[] left out, over a table of n_disc disciplines
+void fill_batch_tables(int n_disc, int n_q, const bool* fallback, const pie_query* qs, const unsigned* nk, BatchTables& t)
+{
     int by_now[kBatchMax], by_cut[kBatchMax], nb = 0;
-    for (int q = 0; q < b.n_q; ++q)
-        if (!b.fallback[q]) { by_now[nb] = q; by_cut[nb] = q; ++nb; }
+    for (int q = 0; q < n_q; ++q)
+        if (!fallback[q]) { by_now[nb] = q; by_cut[nb] = q; ++nb; }
     std::stable_sort(by_now, by_now + nb, [&](int x, int y) { return qs[x].now < qs[y].now; });
     std::stable_sort(by_cut, by_cut + nb, [&](int x, int y) { return qs[x].cutoff < qs[y].cutoff; });
     unsigned long long lv = 0, wn = 0;
@@ -2384,7 +2391,7 @@ void fill_batch_tables(const pie_ctx* c, const BatchSlot& b, const pie_query* qs
         t.win[i + 1] = wn;
     }
     for (int d = 0; d < 64; ++d) t.disc[d] = 0;
-    const unsigned long long table = c->n_disc >= 64 ? ~0ull : ((1ull << c->n_disc) - 1ull);
+    const unsigned long long table = n_disc >= 64 ? ~0ull : ((1ull << n_disc) - 1ull);
     for (int i = 0; i < nb; ++i) { // every set bit of every query's mask, once
         const int q = by_now[i];
         for (unsigned long long m = qs[q].mask & table; m; m &= m - 1) t.disc[__builtin_ctzll(m)] |= 1ull << q;
@@ -2484,7 +2491,7 @@ int batch_begin(pie_ctx* c, const pie_query* qs, int n_q, int msg_kind, int* msg
         if (slots * sizeof(BktRec) <= kDirectMaxBytes) {
             c->bdshift = c->bdshift_want;
             for (BatchSlot& x : c->bslot) {
-                dfree(x.direct); dfree(x.direct_hi); dfree(x.uoff); dfree(x.urows); dfree(x.umlo); dfree(x.umhi);
+                dfree(x.direct); dfree(x.mtab); dfree(x.uoff); dfree(x.urows); dfree(x.umlo); dfree(x.umhi);
                 x.have_result = false;
             }
             for (char*& sp : c->bspan) dfree(sp);
@@ -2568,7 +2575,7 @@ int batch_begin(pie_ctx* c, const pie_query* qs, int n_q, int msg_kind, int* msg
         a.n_users = c->n_users; a.n_q = n_q; a.dshift = c->bdshift;                                                     \
         a.counts = reinterpret_cast<int*>(b.span);                                                                      \
         a.summary = reinterpret_cast<Summary*>(b.span + span_counts_bytes(c) + span_tiles_bytes(c) + span_parts_bytes() + 128); \
-        a.direct = b.direct; a.direct_hi = b.direct_hi; a.run_shift = c->run_shift;                                     \
+        a.direct = b.direct; a.mtab = b.mtab; a.run_shift = c->run_shift;                                               \
         unsigned nk[kBatchMax];                                                                                         \
         unsigned mk = IMPOSSIBLE;                                                                                       \
         for (int q = 0; q < n_q; ++q) {                                                                                 \
@@ -3010,7 +3017,7 @@ int wide_begin(pie_ctx* c, const pie_query* qs, int n_q)
         if (slots * sizeof(BktRec) <= kDirectMaxBytes) {
             c->bdshift = c->bdshift_want;
             for (BatchSlot& x : c->bslot) {
-                dfree(x.direct); dfree(x.direct_hi); dfree(x.uoff); dfree(x.urows); dfree(x.umlo); dfree(x.umhi);
+                dfree(x.direct); dfree(x.mtab); dfree(x.uoff); dfree(x.urows); dfree(x.umlo); dfree(x.umhi);
                 x.have_result = false;
             }
             for (char*& sp : c->bspan) dfree(sp);
@@ -4809,9 +4816,9 @@ int pie_table_info_get(pie_ctx* c, pie_table_info* out)
         per_slot += (uint64_t)kPartMax * kPartCap * sizeof(SelRec);
     }
     out->workspace_bytes = rows ? 2 * per_slot + 3 * (uint64_t)counts_span(c) : 0;
-    for (bool alloc : c->lane_alloc) // batched scans, per lane: three slots (union bucket slots 20 B each, the union result 12 B per entry, 8 per user), three spans
+    for (bool alloc : c->lane_alloc) // batched scans, per lane: three slots (union bucket slots 16 B each, the mask tables, the union result 12 B per entry, 8 per user), three spans
         if (alloc)
-            out->workspace_bytes += kBatchSlots * (((uint64_t)users << c->bdshift) * (sizeof(BktRec) + 4) + (uint64_t)batch_ucap(c) * 12 + ((uint64_t)users + 2) * 8) +
+            out->workspace_bytes += kBatchSlots * (((uint64_t)users << c->bdshift) * sizeof(BktRec) + kMaskTabWords * 8u + (uint64_t)batch_ucap(c) * 12 + ((uint64_t)users + 2) * 8) +
                                     3 * (uint64_t)batch_span_bytes(c);
     for (const BatchSlot& b : c->bslot) // per-query list storage, where somebody asked for lists
         out->workspace_bytes += (uint64_t)b.lists_q * ((uint64_t)batch_users_stride(c) * 12 + (uint64_t)batch_out_stride(c) * 4);
@@ -5283,6 +5290,26 @@ int pie_compact_translate(pie_ctx* c, int32_t* rows_inout, size_t k)
     PIE_HIP(c, hipMemcpyAsync(c->h_stage, c->d_stage, k * 4, hipMemcpyDeviceToHost, s));
     PIE_HIP(c, hipStreamSynchronize(s));
     memcpy(rows_inout, c->h_stage, k * 4);
+    return PIE_OK;
+}
+
+int pie_batch_mask_codes(const pie_query* queries, int n_q, const uint8_t* fallback, int32_t n_disc, const int64_t* start, const int64_t* end,
+                         const int32_t* disc, size_t n_rows, uint32_t* code_out, uint64_t* mask_out)
+{
+    if (!queries || n_q < 1 || n_q > kBatchMax || n_disc < 1 || n_disc > 64 || (n_rows && (!start || !end || !disc))) return PIE_E_INVAL;
+    bool fb[kBatchMax];
+    unsigned nk[kBatchMax];
+    for (int q = 0; q < kBatchMax; ++q) { fb[q] = q < n_q && fallback && fallback[q]; nk[q] = 0; }
+    BatchTables t;
+    fill_batch_tables(n_disc, n_q, fb, queries, nk, t);
+    for (size_t i = 0; i < n_rows; ++i) {
+        if ((uint32_t)disc[i] >= 64u) return PIE_E_INVAL;
+        int r = 0, w = 0; // as the pass ranks a row: the queries with now < end, the queries with cutoff <= start
+        for (int k = 0; k < kBatchMax; ++k) { r += t.now[k] < end[i] ? 1 : 0; w += t.cutoff[k] <= start[i] ? 1 : 0; }
+        const int code = mask_code(r, w, disc[i]);
+        if (code_out) code_out[i] = (uint32_t)code;
+        if (mask_out) mask_out[i] = mask_of_code(t.live, code);
+    }
     return PIE_OK;
 }
 
