@@ -234,6 +234,21 @@ int pie_batch_read_union_wide(pie_ctx *ctx, int64_t *uoff_out, int32_t *rows_out
 /* The exchange message of the wide union into device memory, enqueued on the context's stream:
  * [ uoff[0..u_pad] | Mu | rows[0..cap) | masks[0..cap) as 2 * words int32 words per row ] (rows beyond cap are cut). */
 int pie_batch_pack_union_wide_device(pie_ctx *ctx, void *dst_i32, size_t u_pad, size_t cap);
+/* A wide batch that writes that exchange message itself (the wide counterpart of pie_scan_batch_begin_union): the launch that
+ * orders the union buckets also stores the message words, so no pack launch follows.  Layout as above with words =
+ * ceil(n_q / 64): u_pad + 2 + cap * (1 + 2 * words) int32 words; uoff[u] = Mu for u >= users; rows beyond cap are cut, Mu
+ * still says how many there are.  msg_i32 is device-visible memory (device or mapped host, pie_host_alloc) that stays valid
+ * until the matching finish; u_pad >= users.
+ * pie_scan_wide_finish_packed finishes the oldest batch of either kind, as pie_scan_wide_finish does.  *ready_out = 1: the
+ * batch kept its union and the message was complete when the call returned.  *ready_out = 0: the batch has no union (queries
+ * fell back, the table is on the ordered run or cannot run the batched pass, the slot masks exceed the direct bound); the
+ * header — uoff[0..u_pad] and the Mu word, all -1 — is written on the context's stream (order the consumer behind
+ * pie_ctx_aux_stream); the per-query results stay exact and readable through the readers above.  The first wide batch on a
+ * table normally overflows its 16 union slots per user and reruns on the general path while the slot capacity grows, so it
+ * reports ready = 0 / Mu = -1: a caller repeats the batch.  pie_scan_wide_finish also finishes a batch begun here; the
+ * message is then ordered on the context's stream, as with ready = 0. */
+int pie_scan_wide_begin_union(pie_ctx *ctx, const pie_query *queries, int n_q, void *msg_i32, size_t u_pad, size_t cap);
+int pie_scan_wide_finish_packed(pie_ctx *ctx, size_t *m_out, size_t m_cap, int *n_q_out, int *ready_out);
 /* Batch LANES.  A batch over a shard-sized table (a tenth of 10^8 rows) is one launch of ~20 us that occupies a fraction of
  * the chip: its time is latency, not bytes, and that floor is what would cap an 8-GPU split of the table at 2.5x.  A context
  * therefore deals its batches to up to four lanes — independent pipelines, each with its own HIP stream, three batch slots and
@@ -526,6 +541,50 @@ int pie_comm_step_gathered_ptr(pie_comm *comm, int32_t at_rank, int64_t step, vo
                                size_t *u_pad_out, size_t *cap_out);
 int pie_comm_step_read_gathered(pie_comm *comm, int32_t at_rank, int32_t src_rank, int64_t step, int32_t *uoff_out /* u_pad + 1 */,
                                 int32_t *rows_out, uint64_t *masks_out, size_t cap, size_t *mu_out);
+
+/* ---- the pipelined WIDE exchange: the same pipeline for steps of 1..PIE_WIDE_MAX queries.  One wide union message per step
+ * and shard (layout: pie_scan_wide_begin_union), written by the shard's own wide tail; entry points, counters, buffer sets and
+ * u_pad of its own — a reservation here never moves the geometry of pie_comm_step_* and the reverse.  Order of calls as above:
+ *     wide_step_reserve;  begin(0); begin(1); finish(0); begin(2); collect(0); finish(1); ...
+ * The two kinds do not mix in flight: pie_comm_wide_step_begin returns PIE_E_STATE while ordinary steps are uncollected;
+ * pie_comm_step_begin, pie_comm_scan_batch_gather and the queue calls return PIE_E_STATE while wide steps are uncollected.
+ * Limits: steps begun and unfinished — what the shards' batch slots hold (pie_batch_room) and at most 6; steps uncollected —
+ * the EIGHT rotating buffer sets.  Device memory per set and local rank:
+ *     4 B x (u_pad + 2 + cap x (1 + 2 x words_max)) x (1 + world),   words_max = ceil(n_q_max / 64).
+ * wide_step_reserve: n_q_max 1..PIE_WIDE_MAX fixes the message length; u_pad as in pie_comm_scan_batch_gather; union_cap =
+ *               rows per message.  PIE_E_STATE if the geometry would change while wide steps are in flight.
+ * wide_step_begin:  pie_scan_wide_begin_union on every local shard into the step's buffer set.  If a shard fails after others
+ *               began, every wide step in flight on this process is finished and marked failed (its collect returns
+ *               PIE_E_STATE) together with what this call began; the step is not counted.
+ * wide_step_finish: waits (bounded) for the oldest begun step's batches; m_out (may be NULL): local_ranks x n_q counts,
+ *               PIE_E_CAPACITY with nothing consumed if m_cap is below that.  Queues the exchange on the side streams, which
+ *               wait for a context's stream only where its shard said ready = 0.  Only the prefix the step uses is exchanged:
+ *               u_pad + 2 + cap x (1 + 2 x ceil(n_q / 64)) words — every rank knows n_q.
+ * wide_step_collect: waits (bounded by PIE_WAIT_DEADLINE_MS) for the oldest queued exchange; *step_out = its number.
+ *               PIE_E_CAPACITY on every rank alike, from the gathered Mu words, when a union outgrew union_cap (reserve
+ *               pie_comm_needed_cap() once nothing is in flight, repeat) or when some rank's Mu is -1.
+ * wide_step_status: the gathered Mu word of every rank (mu_out: world values) of a collected step; -1: that rank kept no
+ *               union.  This tells "re-reserve" from "rerun the batch": the first wide batch on a table normally overflows
+ *               its 16 union slots per user and reruns on the general path while the slot capacity grows, so that step reports
+ *               Mu = -1 — the caller REPEATS the step.  A caller whose queries really are dense (they keep falling back) uses
+ *               pie_comm_scan_batch_gather in groups of at most PIE_BATCH_MAX.
+ * The gathered messages of a collected step as rank at_rank holds them are valid until eight more steps have begun: message of
+ * rank r at base + r * rank_stride_words, its masks as 2 x *words_out int32 per row behind rows[*cap_out];
+ * wide_step_read_gathered copies one to the host (masks_out: [cap][words] uint64; PIE_E_CAPACITY if cap < min(Mu, union_cap));
+ * wide_step_read_feed reads ONE user's feed of query qi straight from a gathered message (a few small copies and a filter on the
+ * host, like pie_batch_read_user_feed); local_user and the rows are src_rank's local ids (pie_shard_maps).
+ * Like the ordinary steps, this has run against a one-GPU stand-in for RCCL and a 1-rank RCCL communicator only. */
+int pie_comm_wide_step_reserve(pie_comm *comm, int32_t n_q_max, int32_t u_pad, size_t union_cap);
+int pie_comm_wide_step_begin(pie_comm *comm, const pie_query *queries, int32_t n_q);
+int pie_comm_wide_step_finish(pie_comm *comm, size_t *m_out, size_t m_cap);
+int pie_comm_wide_step_collect(pie_comm *comm, int64_t *step_out);
+int pie_comm_wide_step_status(pie_comm *comm, int64_t step, int32_t *mu_out /* world */);
+int pie_comm_wide_step_gathered_ptr(pie_comm *comm, int32_t at_rank, int64_t step, void **base_out, size_t *rank_stride_words,
+                                    size_t *u_pad_out, size_t *cap_out, int *words_out);
+int pie_comm_wide_step_read_gathered(pie_comm *comm, int32_t at_rank, int32_t src_rank, int64_t step, int32_t *uoff_out /* u_pad + 1 */,
+                                     int32_t *rows_out, uint64_t *masks_out /* [cap][words] */, size_t cap, int *words_out, size_t *mu_out);
+int pie_comm_wide_step_read_feed(pie_comm *comm, int32_t at_rank, int32_t src_rank, int64_t step, int32_t qi, int32_t local_user,
+                                 int32_t *idx_out, size_t idx_cap, size_t *k_out);
 
 #ifdef __cplusplus
 }

@@ -107,6 +107,8 @@ _SIGS = [
     ("pie_batch_union_wide_device_ptrs", C.c_int, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_int), C.POINTER(C.c_size_t)]),
     ("pie_batch_read_union_wide", C.c_int, [_P, _P, _P, _P, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_size_t)]),
     ("pie_batch_pack_union_wide_device", C.c_int, [_P, _P, C.c_size_t, C.c_size_t]),
+    ("pie_scan_wide_begin_union", C.c_int, [_P, C.POINTER(PieQuery), C.c_int, _P, C.c_size_t, C.c_size_t]),
+    ("pie_scan_wide_finish_packed", C.c_int, [_P, _P, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("pie_batch_mask_codes", C.c_int, [C.POINTER(PieQuery), C.c_int, _P, C.c_int32, _P, _P, _P, C.c_size_t, _P, _P]),
     ("pie_batch_read_results", C.c_int, [_P, C.c_int, _P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("pie_batch_result_device_ptrs", C.c_int, [_P, C.c_int, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P)]),
@@ -153,6 +155,15 @@ _SIGS = [
     ("pie_comm_step_collect", C.c_int, [_P, C.POINTER(C.c_int64)]),
     ("pie_comm_step_gathered_ptr", C.c_int, [_P, C.c_int32, C.c_int64, C.POINTER(_P), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     ("pie_comm_step_read_gathered", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int64, _P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("pie_comm_wide_step_reserve", C.c_int, [_P, C.c_int32, C.c_int32, C.c_size_t]),
+    ("pie_comm_wide_step_begin", C.c_int, [_P, C.POINTER(PieQuery), C.c_int32]),
+    ("pie_comm_wide_step_finish", C.c_int, [_P, C.POINTER(C.c_size_t), C.c_size_t]),
+    ("pie_comm_wide_step_collect", C.c_int, [_P, C.POINTER(C.c_int64)]),
+    ("pie_comm_wide_step_status", C.c_int, [_P, C.c_int64, C.POINTER(C.c_int32)]),
+    ("pie_comm_wide_step_gathered_ptr", C.c_int, [_P, C.c_int32, C.c_int64, C.POINTER(_P), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
+                                                  C.POINTER(C.c_int)]),
+    ("pie_comm_wide_step_read_gathered", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int64, _P, _P, _P, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_size_t)]),
+    ("pie_comm_wide_step_read_feed", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("pie_comm_gathered_device_ptr", C.c_int, [_P, C.c_int32, C.POINTER(_P), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     ("pie_comm_read_gathered", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("pie_comm_expired_queue", C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
@@ -528,6 +539,25 @@ class PieScan:
         self._check(rc)
         return [int(x) for x in m[: nq.value]]
 
+    def scan_wide_begin_union(self, queries, msg_ptr, u_pad, cap):
+        """A wide batch whose own tail writes the wide union message (layout: split_wide_message) into msg_ptr, device-visible
+        int32 memory of u_pad + 2 + cap * (1 + 2 * ceil(len(queries) / 64)) words."""
+        queries = list(queries)
+        self._check(self._lib.pie_scan_wide_begin_union(self._ctx, self._wide_queries(queries), len(queries), msg_ptr, int(u_pad), int(cap)))
+        self._batches = getattr(self, "_batches", [])
+        self._batches.append(len(queries))
+
+    def scan_wide_finish_packed(self):
+        """-> (list of M per query of the oldest batch in flight, ready).  ready: the batch kept its union and its message was
+        complete on return; otherwise the header says Mu = -1 once the context's stream has passed."""
+        m = (C.c_size_t * PIE_WIDE_MAX)()
+        nq, ready = C.c_int(0), C.c_int(0)
+        rc = self._lib.pie_scan_wide_finish_packed(self._ctx, m, PIE_WIDE_MAX, C.byref(nq), C.byref(ready))
+        if getattr(self, "_batches", None) and rc not in (-6, PIE_E_CAPACITY):
+            self._batches.pop(0)
+        self._check(rc)
+        return [int(x) for x in m[: nq.value]], bool(ready.value)
+
     def scan_wide(self, queries):
         """-> [(counts, offsets, idx)] per query; bit for bit what scan() gives for each (now, cutoff) under its mask."""
         queries = list(queries)
@@ -897,6 +927,63 @@ class PieComm:
         self._check(self._lib.pie_comm_step_read_gathered(self._c, int(at_rank), int(src_rank), int(step), None, _ptr(rows), _ptr(masks), mu.value, C.byref(mu)))
         return uoff, rows[: mu.value], masks[: mu.value]
 
+    # ---- the pipelined WIDE union exchange (pie_comm_wide_step_*): up to PIE_WIDE_MAX queries per step
+    def wide_step_reserve(self, n_q_max, u_pad=0, union_cap=1024):
+        self._check(self._lib.pie_comm_wide_step_reserve(self._c, int(n_q_max), int(u_pad), int(union_cap)))
+
+    def wide_step_begin(self, queries):
+        queries = list(queries)      # marshalled on every call: no identity cache
+        self._check(self._lib.pie_comm_wide_step_begin(self._c, PieScan._wide_queries(queries), len(queries)))
+        self._wide_nq = getattr(self, "_wide_nq", [])
+        self._wide_nq.append(len(queries))
+
+    def wide_step_finish(self):
+        """-> M[local rank][query] of the oldest begun wide step; its exchange is queued, not waited for."""
+        nq = self._wide_nq[0]
+        nl = int(self._lib.pie_comm_local_ranks(self._c))
+        m = (C.c_size_t * (nl * nq))()
+        rc = self._lib.pie_comm_wide_step_finish(self._c, m, nl * nq)
+        if rc != PIE_E_CAPACITY:
+            self._wide_nq.pop(0)
+        self._check(rc)
+        return [[int(m[k * nq + q]) for q in range(nq)] for k in range(nl)]
+
+    def wide_step_collect(self):
+        """Wait for the oldest queued wide exchange.  -> its step number.  PieError(PIE_E_CAPACITY) on every rank alike when a
+        union outgrew the reserved capacity (needed_cap()) or some rank kept no union (wide_step_status shows -1: repeat)."""
+        step = C.c_int64(-1)
+        self._check(self._lib.pie_comm_wide_step_collect(self._c, C.byref(step)))
+        return int(step.value)
+
+    def wide_step_status(self, step):
+        """-> int32[world]: the gathered Mu word of every rank for a collected step (-1: that rank kept no union)."""
+        mu = np.empty(self.world, np.int32)
+        self._check(self._lib.pie_comm_wide_step_status(self._c, int(step), mu.ctypes.data_as(C.POINTER(C.c_int32))))
+        return mu
+
+    def wide_step_read_gathered(self, at_rank, src_rank, step):
+        """-> (uoff[u_pad + 1] int32, rows[k] int32, masks[k, words] uint64, Mu) of src_rank's wide message of `step` as at_rank
+        holds it; k = min(Mu, reserved capacity)."""
+        base, rs, up, cap, words = _P(), C.c_size_t(0), C.c_size_t(0), C.c_size_t(0), C.c_int(0)
+        self._check(self._lib.pie_comm_wide_step_gathered_ptr(self._c, int(at_rank), int(step), C.byref(base), C.byref(rs), C.byref(up), C.byref(cap),
+                                                              C.byref(words)))
+        uoff = np.empty(up.value + 1, np.int32)
+        mu = C.c_size_t(0)
+        self._check(self._lib.pie_comm_wide_step_read_gathered(self._c, int(at_rank), int(src_rank), int(step), _ptr(uoff), None, None, 0, C.byref(words),
+                                                               C.byref(mu)))
+        k, w = min(mu.value, cap.value), int(words.value)
+        rows, masks = np.empty(max(k, 1), np.int32), np.empty((max(k, 1), w), np.uint64)
+        self._check(self._lib.pie_comm_wide_step_read_gathered(self._c, int(at_rank), int(src_rank), int(step), None, _ptr(rows), _ptr(masks), k,
+                                                               C.byref(words), C.byref(mu)))
+        return uoff, rows[:k], masks[:k], int(mu.value)
+
+    def wide_step_read_feed(self, at_rank, src_rank, step, qi, local_user, idx_cap=64):
+        """-> Feed(qi, local_user) of src_rank's shard (its local rows) read from the gathered message of `step`."""
+        idx, k = np.empty(max(int(idx_cap), 1), np.int32), C.c_size_t(0)
+        self._check(self._lib.pie_comm_wide_step_read_feed(self._c, int(at_rank), int(src_rank), int(step), int(qi), int(local_user), _ptr(idx),
+                                                           int(idx_cap), C.byref(k)))
+        return idx[: k.value].copy()
+
     # ---- cross-shard dispatch queues (pie_comm_expired_queue / pie_comm_archive_queue)
     def local_ranks(self):
         return [r for r in range(self.world) if self._lib.pie_comm_ctx(self._c, r)]
@@ -944,6 +1031,22 @@ class PieComm:
         idx = np.empty(max(m.value, 1), np.int32)
         self._check(self._lib.pie_comm_read_gathered(self._c, int(at_rank), int(src_rank), int(qi), None, _ptr(idx), m.value, C.byref(m)))
         return off, idx[: m.value]
+
+
+def split_wide_message(msg, u_pad, cap, words):
+    """Pure numpy: a wide union message [uoff[0..u_pad] | Mu | rows[0..cap) | masks[0..cap) as 2 * words int32 per row] ->
+    (uoff int32[u_pad + 1], Mu, rows int32[k], masks uint64[k, words]) with k = min(max(Mu, 0), cap); Mu = -1: no union."""
+    msg = np.ascontiguousarray(msg, np.int32)
+    u_pad, cap, words = int(u_pad), int(cap), int(words)
+    if msg.shape[0] < u_pad + 2 + cap * (1 + 2 * words):
+        raise ValueError("message shorter than u_pad + 2 + cap * (1 + 2 * words)")
+    uoff = msg[: u_pad + 1].copy()
+    mu = int(msg[u_pad + 1])
+    k = min(max(mu, 0), cap)
+    rows = msg[u_pad + 2: u_pad + 2 + k].copy()
+    base = u_pad + 2 + cap
+    masks = msg[base: base + k * 2 * words].astype("<i4").view("<u8").reshape(k, words).astype(np.uint64)
+    return uoff, mu, rows, masks
 
 
 def shard_of(user, n_shards):

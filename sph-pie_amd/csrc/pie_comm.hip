@@ -115,6 +115,18 @@ struct pie_comm {
     long long begun = 0, finished = 0, collected = 0;  // steps begun / exchanges issued / exchanges collected
     int step_nq[kSets] = {};
     int step_rc[kSets] = {};   // a step whose finish failed on this process: its collect reports it
+    // pipelined WIDE union exchange (pie_comm_wide_step_*): state of its own beside the above — buffer sets, counters and u_pad
+    // are not shared with the ordinary steps (a reservation of one kind never moves the other's message geometry)
+    static constexpr int kWideSets = 8;
+    std::vector<int*> wmsg[kWideSets], wgath[kWideSets];  // [set][local index]: this rank's wide message [WL] / the gathered ones [world][WL]
+    std::vector<hipEvent_t> w_ready[kWideSets], w_done[kWideSets];
+    int* w_h_mu[kWideSets] = {};   // mapped pinned: [local index][world] the Mu word of every gathered message
+    int* w_h_mu_dev[kWideSets] = {};
+    long long w_u_pad = 0, w_cap = 0, WL = 0;  // users per message, union rows per message, words per message (for w_words_max)
+    int w_words_max = 0;           // 64-bit mask words per row the reservation holds (ceil(n_q_max / 64))
+    long long w_begun = 0, w_finished = 0, w_collected = 0;
+    int w_step_nq[kWideSets] = {};
+    int w_step_rc[kWideSets] = {};
     // cross-shard dispatch queues (pie_comm_expired_queue / _archive_queue): buffers of their own, sized by the header exchange
     std::vector<int*> qh_msg, qh_gath;            // local index -> header words [2] / gathered headers [world][2]
     int* h_qhead = nullptr;                       // pinned: [local index][2] headers to send, then [world][2] as gathered
@@ -211,6 +223,8 @@ pie_comm* new_comm(int world, int n_local)
 void free_queue_buffers(pie_comm* c);
 
 void free_step_buffers(pie_comm* c);
+
+void free_wide_step_buffers(pie_comm* c, bool events);
 
 int local_index(const pie_comm* c, int rank)
 {
@@ -326,6 +340,7 @@ int pie_comm_destroy(pie_comm* c)
     }
     free_buffers(c);
     free_step_buffers(c);
+    free_wide_step_buffers(c, true);
     free_queue_buffers(c);
     for (int k = 0; k < c->n_local; ++k) {
         (void)hipSetDevice(c->device[k]);
@@ -478,6 +493,7 @@ int pie_comm_scan_batch_gather(pie_comm* c, const pie_query* queries, int32_t n_
     if (!c) return PIE_E_INVAL;
     if (!queries || n_q < 1 || n_q > PIE_BATCH_MAX) return cfail(c, PIE_E_INVAL, "a batch holds 1..%d queries (got %d)", PIE_BATCH_MAX, n_q);
     if (c->begun != c->collected) return cfail(c, PIE_E_STATE, "pipelined steps are in flight (pie_comm_step_*): collect them first");
+    if (c->w_begun != c->w_collected) return cfail(c, PIE_E_STATE, "wide steps are in flight (pie_comm_wide_step_*): collect them first");
     long long u_pad = 0;
     int rc = resolve_u_pad(c, u_pad_in, &u_pad);
     if (rc) return rc;
@@ -548,6 +564,7 @@ int pie_comm_step_begin(pie_comm* c, const pie_query* queries, int32_t n_q)
     if (!c) return PIE_E_INVAL;
     if (!queries || n_q < 1 || n_q > PIE_BATCH_MAX) return cfail(c, PIE_E_INVAL, "a batch holds 1..%d queries (got %d)", PIE_BATCH_MAX, n_q);
     if (c->UL <= 0) return cfail(c, PIE_E_STATE, "pie_comm_step_reserve first");
+    if (c->w_begun != c->w_collected) return cfail(c, PIE_E_STATE, "wide steps are in flight (pie_comm_wide_step_*): collect them first");
     if ((n_q > 32 ? 3 : 2) > c->u_words) return cfail(c, PIE_E_STATE, "reserved for batches of at most 32 queries: pie_comm_step_reserve again");
     // steps begun and unfinished: what the shards' batch lanes hold (three per lane, pie_set_batch_lanes; lane 0 only on the ordered run)
     if (c->begun - c->finished >= pie_comm::kSets - 4)
@@ -931,6 +948,7 @@ int comm_queue(pie_comm* c, int kind, int64_t a, int64_t b, int32_t* queue_out, 
     if (q_out) *q_out = 0;
     if (c->world > kQueueMaxWorld) return cfail(c, PIE_E_INVAL, "the queue merge takes at most %d ranks (world %d)", kQueueMaxWorld, c->world);
     if (c->begun != c->collected) return cfail(c, PIE_E_STATE, "pipelined steps are in flight (pie_comm_step_*): collect them first");
+    if (c->w_begun != c->w_collected) return cfail(c, PIE_E_STATE, "wide steps are in flight (pie_comm_wide_step_*): collect them first");
     c->q_total = -1;
     c->q_timed = false;
     int rc = ensure_queue_heads(c);
@@ -1076,6 +1094,288 @@ int pie_comm_queue_timing(pie_comm* c, float* ms_out_4)
     if (!c->q_timed) return cfail(c, PIE_E_STATE, "no completed queue call to time");
     PIE_CHIP(c, hipSetDevice(c->device[0]));
     for (int i = 0; i < 4; ++i) PIE_CHIP(c, hipEventElapsedTime(&ms_out_4[i], c->q_tev[i], c->q_tev[i + 1]));
+    return PIE_OK;
+}
+
+} // extern "C"
+
+// ---- the pipelined WIDE exchange (pie_comm_wide_step_*): one wide union message per step (layout:
+// pie_scan_wide_begin_union), written by each shard's own wide tail; otherwise the shape of pie_comm_step_* above, with state
+// of its own.  Every wait is bounded (wait_event, PIE_WAIT_DEADLINE_MS).
+namespace {
+
+void free_wide_step_buffers(pie_comm* c, bool events)
+{
+    for (int s = 0; s < pie_comm::kWideSets; ++s) {
+        for (int k = 0; k < c->n_local; ++k) {
+            (void)hipSetDevice(c->device[k]);
+            if (k < (int)c->wmsg[s].size() && c->wmsg[s][k]) (void)hipFree(c->wmsg[s][k]);
+            if (k < (int)c->wgath[s].size() && c->wgath[s][k]) (void)hipFree(c->wgath[s][k]);
+            if (events) {
+                if (k < (int)c->w_ready[s].size() && c->w_ready[s][k]) { (void)hipEventDestroy(c->w_ready[s][k]); c->w_ready[s][k] = nullptr; }
+                if (k < (int)c->w_done[s].size() && c->w_done[s][k]) { (void)hipEventDestroy(c->w_done[s][k]); c->w_done[s][k] = nullptr; }
+            }
+        }
+        c->wmsg[s].assign((size_t)c->n_local, nullptr);
+        c->wgath[s].assign((size_t)c->n_local, nullptr);
+        if (c->w_h_mu[s]) (void)hipHostFree(c->w_h_mu[s]);
+        c->w_h_mu[s] = nullptr;
+    }
+    c->w_cap = c->WL = 0;
+    c->w_words_max = 0;
+}
+
+long long wide_msg_words(long long u_pad, long long cap, int words) { return u_pad + 2 + cap * (1 + 2 * (long long)words); }
+
+// the gathered Mu words of a collected step whose buffers have not been reused: nullptr otherwise
+const int* wide_step_mu(pie_comm* c, int64_t step)
+{
+    if (step < 0 || step >= c->w_collected || step + pie_comm::kWideSets <= c->w_begun) return nullptr;
+    const int s = (int)(step % pie_comm::kWideSets);
+    return c->w_step_rc[s] == PIE_OK ? c->w_h_mu[s] : nullptr;
+}
+
+// a partial failure left batches begun on some shards: every wide step in flight on this process is finished in order and
+// marked failed (its collect says so), then the batches of the step that failed to begin; nothing is left in the shards' FIFOs
+void wide_step_drain(pie_comm* c, int begun_here, int why)
+{
+    while (c->w_finished < c->w_begun) {
+        const int s = (int)(c->w_finished % pie_comm::kWideSets);
+        for (int k = 0; k < c->n_local; ++k) (void)pie_scan_wide_finish(c->ctx[k], nullptr, 0, nullptr);
+        c->w_step_rc[s] = why;
+        c->w_finished++;
+    }
+    for (int k = 0; k < begun_here; ++k) (void)pie_scan_wide_finish(c->ctx[k], nullptr, 0, nullptr);
+}
+
+} // namespace
+
+extern "C" {
+
+int pie_comm_wide_step_reserve(pie_comm* c, int32_t n_q_max, int32_t u_pad_in, size_t union_cap)
+{
+    if (!c) return PIE_E_INVAL;
+    if (n_q_max < 1 || n_q_max > PIE_WIDE_MAX) return cfail(c, PIE_E_INVAL, "a wide step holds 1..%d queries (got %d)", PIE_WIDE_MAX, n_q_max);
+    long long u_pad = 0;
+    int rc = resolve_u_pad(c, u_pad_in, &u_pad);
+    if (rc) return rc;
+    const long long cap = (long long)(union_cap > 0 ? union_cap : 1024);
+    const int words = (n_q_max + 63) / 64;
+    if (wide_msg_words(u_pad, cap, words) > 0x7FFFFFF0LL) return cfail(c, PIE_E_INVAL, "a message of %lld words is too long", wide_msg_words(u_pad, cap, words));
+    if (c->WL > 0 && c->w_u_pad == u_pad && cap <= c->w_cap && words <= c->w_words_max && c->wmsg[0].size() == (size_t)c->n_local && c->wmsg[0][0]) return PIE_OK;
+    if (c->w_begun != c->w_collected) return cfail(c, PIE_E_STATE, "wide steps are in flight: collect them before the message size changes");
+    free_wide_step_buffers(c, false);
+    c->w_u_pad = u_pad;
+    c->w_cap = cap;
+    c->w_words_max = words;
+    c->WL = wide_msg_words(u_pad, cap, words);
+    if (c->xstream.size() != (size_t)c->n_local) c->xstream.assign((size_t)c->n_local, nullptr);
+    for (int s = 0; s < pie_comm::kWideSets; ++s) {
+        if (c->w_ready[s].size() != (size_t)c->n_local) { c->w_ready[s].assign((size_t)c->n_local, nullptr); c->w_done[s].assign((size_t)c->n_local, nullptr); }
+        PIE_CHIP(c, hipHostMalloc(&c->w_h_mu[s], (size_t)c->n_local * (size_t)c->world * 4, hipHostMallocMapped));
+        PIE_CHIP(c, hipHostGetDevicePointer((void**)&c->w_h_mu_dev[s], c->w_h_mu[s], 0));
+    }
+    for (int k = 0; k < c->n_local; ++k) {
+        PIE_CHIP(c, hipSetDevice(c->device[k]));
+        if (!c->xstream[k]) PIE_CHIP(c, hipStreamCreateWithFlags(&c->xstream[k], hipStreamNonBlocking));
+        for (int s = 0; s < pie_comm::kWideSets; ++s) {
+            PIE_CHIP(c, hipMalloc(&c->wmsg[s][k], (size_t)c->WL * 4));
+            PIE_CHIP(c, hipMalloc(&c->wgath[s][k], (size_t)c->WL * 4 * (size_t)c->world));
+            PIE_CHIP(c, hipMemset(c->wmsg[s][k], 0, (size_t)c->WL * 4));
+            if (!c->w_ready[s][k]) PIE_CHIP(c, hipEventCreateWithFlags(&c->w_ready[s][k], hipEventDisableTiming));
+            if (!c->w_done[s][k]) PIE_CHIP(c, hipEventCreateWithFlags(&c->w_done[s][k], hipEventDisableTiming));
+        }
+    }
+    return PIE_OK;
+}
+
+int pie_comm_wide_step_begin(pie_comm* c, const pie_query* queries, int32_t n_q)
+{
+    if (!c) return PIE_E_INVAL;
+    if (!queries || n_q < 1 || n_q > PIE_WIDE_MAX) return cfail(c, PIE_E_INVAL, "a wide step holds 1..%d queries (got %d)", PIE_WIDE_MAX, n_q);
+    if (c->WL <= 0) return cfail(c, PIE_E_STATE, "pie_comm_wide_step_reserve first");
+    if (c->begun != c->collected) return cfail(c, PIE_E_STATE, "ordinary steps are in flight (pie_comm_step_*): collect them first");
+    if ((n_q + 63) / 64 > c->w_words_max) return cfail(c, PIE_E_STATE, "reserved for at most %d queries: pie_comm_wide_step_reserve again", c->w_words_max * 64);
+    if (c->w_begun - c->w_finished >= pie_comm::kWideSets - 2)
+        return cfail(c, PIE_E_STATE, "%d wide steps are already begun: pie_comm_wide_step_finish first", pie_comm::kWideSets - 2);
+    for (int k = 0; k < c->n_local; ++k)
+        if (pie_batch_room(c->ctx[k]) <= 0)
+            return cfail(c, PIE_E_STATE, "rank %d: the steps begun fill its batch slots (three per batch lane): pie_comm_wide_step_finish first", c->rank_of[k]);
+    if (c->w_begun - c->w_collected >= pie_comm::kWideSets)
+        return cfail(c, PIE_E_STATE, "%d wide steps are uncollected: pie_comm_wide_step_collect first", pie_comm::kWideSets);
+    const int s = (int)(c->w_begun % pie_comm::kWideSets);
+    int begun = 0, rc = PIE_OK;
+    for (int k = 0; k < c->n_local && rc == PIE_OK; ++k) {
+        rc = pie_scan_wide_begin_union(c->ctx[k], queries, n_q, c->wmsg[s][k], (size_t)c->w_u_pad, (size_t)c->w_cap);
+        if (rc == PIE_OK) ++begun;
+        else cfail(c, rc, "rank %d: %s", c->rank_of[k], pie_last_error(c->ctx[k]));
+    }
+    if (rc != PIE_OK) { // the step is not counted
+        if (begun > 0) wide_step_drain(c, begun, rc);
+        return rc;
+    }
+    c->w_step_nq[s] = n_q;
+    c->w_step_rc[s] = PIE_OK;
+    c->w_begun++;
+    return PIE_OK;
+}
+
+int pie_comm_wide_step_finish(pie_comm* c, size_t* m_out, size_t m_cap)
+{
+    if (!c) return PIE_E_INVAL;
+    if (c->w_finished >= c->w_begun) return cfail(c, PIE_E_STATE, "pie_comm_wide_step_finish without pie_comm_wide_step_begin");
+    const int s = (int)(c->w_finished % pie_comm::kWideSets);
+    const int n_q = c->w_step_nq[s];
+    if (m_out && m_cap < (size_t)c->n_local * (size_t)n_q)
+        return cfail(c, PIE_E_CAPACITY, "m_cap %zu < %d local ranks x %d queries", m_cap, c->n_local, n_q);
+    std::vector<size_t> m((size_t)c->n_local * (size_t)n_q, 0);
+    int first_rc = PIE_OK;
+    for (int k = 0; k < c->n_local; ++k) {
+        int ready = 0, nq = 0;
+        const int rc = pie_scan_wide_finish_packed(c->ctx[k], &m[(size_t)k * n_q], (size_t)n_q, &nq, &ready);
+        if (rc != PIE_OK && first_rc == PIE_OK) {
+            first_rc = rc;
+            cfail(c, rc, "rank %d: %s", c->rank_of[k], pie_last_error(c->ctx[k]));
+        }
+        // ready = 0: the header (Mu = -1) was written on the context's stream behind the batch: the exchange stream waits for exactly that
+        PIE_CHIP(c, hipSetDevice(c->device[k]));
+        if (!ready) {
+            PIE_CHIP(c, hipEventRecord(c->w_ready[s][k], c->stream[k]));
+            PIE_CHIP(c, hipStreamWaitEvent(c->xstream[k], c->w_ready[s][k], 0));
+        }
+    }
+    c->w_finished++;
+    c->w_step_rc[s] = first_rc;
+    if (first_rc != PIE_OK) return first_rc; // every local batch has been finished; no exchange is queued for this step (its collect says so)
+    // only the prefix this step uses: every rank knows n_q, so every rank agrees on the length
+    const size_t count = (size_t)wide_msg_words(c->w_u_pad, c->w_cap, (n_q + 63) / 64);
+    int rc = exchange(c, c->wmsg[s], c->wgath[s], count, (size_t)c->WL, c->xstream);
+    if (rc) { c->w_step_rc[s] = rc; return rc; }
+    for (int k = 0; k < c->n_local; ++k) {
+        PIE_CHIP(c, hipSetDevice(c->device[k]));
+        hipLaunchKernelGGL(k_pick_words, dim3(1), dim3(64), 0, c->xstream[k], c->wgath[s][k], (long long)c->WL, (long long)c->w_u_pad + 1, c->world,
+                           c->w_h_mu_dev[s] + (size_t)k * (size_t)c->world);
+        PIE_CHIP(c, hipEventRecord(c->w_done[s][k], c->xstream[k]));
+    }
+    if (m_out) memcpy(m_out, m.data(), m.size() * sizeof(size_t));
+    return PIE_OK;
+}
+
+int pie_comm_wide_step_collect(pie_comm* c, int64_t* step_out)
+{
+    if (!c) return PIE_E_INVAL;
+    if (c->w_collected >= c->w_finished) return cfail(c, PIE_E_STATE, "no exchange to collect: pie_comm_wide_step_finish first");
+    const int s = (int)(c->w_collected % pie_comm::kWideSets);
+    if (step_out) *step_out = (int64_t)c->w_collected;
+    if (c->w_step_rc[s] != PIE_OK) {
+        c->w_collected++;
+        return cfail(c, PIE_E_STATE, "wide step %lld failed before its exchange (status %d): nothing was exchanged", (long long)c->w_collected - 1, c->w_step_rc[s]);
+    }
+    int wrc = PIE_OK;
+    for (int k = 0; k < c->n_local && wrc == PIE_OK; ++k) wrc = wait_event(c, k, c->w_done[s][k], "wide step exchange"); // the side stream only
+    c->w_collected++;
+    if (wrc != PIE_OK) { c->w_step_rc[s] = wrc; return wrc; }
+    long long need = 0;
+    bool no_union = false;
+    for (int p = 0; p < c->world; ++p) { // every rank holds the same world Mu words
+        const int mu = c->w_h_mu[s][p];
+        if (mu < 0) no_union = true;
+        if (mu > need) need = mu;
+    }
+    c->need = need;
+    if (no_union)
+        return cfail(c, PIE_E_CAPACITY, "a shard's wide batch kept no union (Mu = -1, pie_comm_wide_step_status): repeat the step; dense queries go through pie_comm_scan_batch_gather");
+    if (need > c->w_cap)
+        return cfail(c, PIE_E_CAPACITY, "a union of %lld rows exceeds the reserved capacity %lld on some rank: collect what is in flight, pie_comm_wide_step_reserve(pie_comm_needed_cap), repeat the step", need, c->w_cap);
+    return PIE_OK;
+}
+
+int pie_comm_wide_step_status(pie_comm* c, int64_t step, int32_t* mu_out)
+{
+    if (!c) return PIE_E_INVAL;
+    const int* mu = wide_step_mu(c, step);
+    if (!mu) return cfail(c, PIE_E_STATE, "wide step %lld is not collected, failed before its exchange, or its buffers were reused", (long long)step);
+    if (mu_out)
+        for (int p = 0; p < c->world; ++p) mu_out[p] = mu[p];
+    return PIE_OK;
+}
+
+int pie_comm_wide_step_gathered_ptr(pie_comm* c, int32_t at_rank, int64_t step, void** base_out, size_t* rank_stride_words, size_t* u_pad_out,
+                                    size_t* cap_out, int* words_out)
+{
+    if (!c) return PIE_E_INVAL;
+    const int k = local_index(c, at_rank);
+    if (k < 0 || c->WL <= 0) return cfail(c, PIE_E_STATE, "rank %d is not local to this communicator or nothing was reserved", at_rank);
+    if (!wide_step_mu(c, step)) return cfail(c, PIE_E_STATE, "wide step %lld is not collected, failed before its exchange, or its buffers were reused", (long long)step);
+    const int s = (int)(step % pie_comm::kWideSets);
+    if (base_out) *base_out = c->wgath[s][k];
+    if (rank_stride_words) *rank_stride_words = (size_t)c->WL;
+    if (u_pad_out) *u_pad_out = (size_t)c->w_u_pad;
+    if (cap_out) *cap_out = (size_t)c->w_cap;
+    if (words_out) *words_out = (c->w_step_nq[s] + 63) / 64;
+    return PIE_OK;
+}
+
+int pie_comm_wide_step_read_gathered(pie_comm* c, int32_t at_rank, int32_t src_rank, int64_t step, int32_t* uoff_out, int32_t* rows_out,
+                                     uint64_t* masks_out, size_t cap, int* words_out, size_t* mu_out)
+{
+    if (!c) return PIE_E_INVAL;
+    if (mu_out) *mu_out = 0;
+    if (words_out) *words_out = 0;
+    void* base = nullptr;
+    int words = 0;
+    int rc = pie_comm_wide_step_gathered_ptr(c, at_rank, step, &base, nullptr, nullptr, nullptr, &words);
+    if (rc) return rc;
+    if (src_rank < 0 || src_rank >= c->world) return cfail(c, PIE_E_INVAL, "source rank outside the communicator");
+    const int k = local_index(c, at_rank);
+    PIE_CHIP(c, hipSetDevice(c->device[k]));
+    const int* msg = static_cast<const int*>(base) + (size_t)src_rank * (size_t)c->WL;
+    const int mu32 = wide_step_mu(c, step)[(size_t)k * (size_t)c->world + (size_t)src_rank];
+    const size_t mu = mu32 > 0 ? (size_t)mu32 : 0;
+    if (mu_out) *mu_out = mu;
+    if (words_out) *words_out = words;
+    if (uoff_out) PIE_CHIP(c, hipMemcpy(uoff_out, msg, ((size_t)c->w_u_pad + 1) * 4, hipMemcpyDeviceToHost));
+    const size_t have = mu < (size_t)c->w_cap ? mu : (size_t)c->w_cap;
+    if ((rows_out || masks_out) && have > cap) return cfail(c, PIE_E_CAPACITY, "cap %zu < %zu union rows", cap, have);
+    if (rows_out && have) PIE_CHIP(c, hipMemcpy(rows_out, msg + c->w_u_pad + 2, have * 4, hipMemcpyDeviceToHost));
+    // two int32 words per 64-bit mask word, low word first: the host's uint64 as it stands
+    if (masks_out && have) PIE_CHIP(c, hipMemcpy(masks_out, msg + c->w_u_pad + 2 + c->w_cap, have * (size_t)words * 8, hipMemcpyDeviceToHost));
+    return PIE_OK;
+}
+
+int pie_comm_wide_step_read_feed(pie_comm* c, int32_t at_rank, int32_t src_rank, int64_t step, int32_t qi, int32_t local_user, int32_t* idx_out,
+                                 size_t idx_cap, size_t* k_out)
+{
+    if (!c) return PIE_E_INVAL;
+    if (k_out) *k_out = 0;
+    void* base = nullptr;
+    int words = 0;
+    int rc = pie_comm_wide_step_gathered_ptr(c, at_rank, step, &base, nullptr, nullptr, nullptr, &words);
+    if (rc) return rc;
+    const int n_q = c->w_step_nq[step % pie_comm::kWideSets];
+    if (src_rank < 0 || src_rank >= c->world || qi < 0 || qi >= n_q || local_user < 0 || (long long)local_user >= c->w_u_pad)
+        return cfail(c, PIE_E_INVAL, "source rank / query / user outside the step");
+    const int k = local_index(c, at_rank);
+    PIE_CHIP(c, hipSetDevice(c->device[k]));
+    const int* msg = static_cast<const int*>(base) + (size_t)src_rank * (size_t)c->WL;
+    int ab[2] = {0, 0};
+    PIE_CHIP(c, hipMemcpy(ab, msg + local_user, 8, hipMemcpyDeviceToHost));
+    if (ab[0] < 0 || ab[1] < ab[0]) return cfail(c, PIE_E_STATE, "rank %d kept no union in wide step %lld (Mu = -1)", src_rank, (long long)step);
+    if ((long long)ab[1] > c->w_cap) return cfail(c, PIE_E_CAPACITY, "the user's rows were cut: the union outgrew the reserved capacity %lld", c->w_cap);
+    const size_t n = (size_t)(ab[1] - ab[0]);
+    if (n == 0) return PIE_OK;
+    std::vector<int32_t> rows(n);
+    std::vector<uint64_t> masks(n * (size_t)words);
+    PIE_CHIP(c, hipMemcpy(rows.data(), msg + c->w_u_pad + 2 + ab[0], n * 4, hipMemcpyDeviceToHost));
+    PIE_CHIP(c, hipMemcpy(masks.data(), msg + c->w_u_pad + 2 + c->w_cap + (size_t)ab[0] * 2 * (size_t)words, n * (size_t)words * 8, hipMemcpyDeviceToHost));
+    size_t kk = 0;
+    for (size_t i = 0; i < n; ++i)
+        if ((masks[i * (size_t)words + (size_t)(qi >> 6)] >> (qi & 63)) & 1ull) {
+            if (idx_out && kk < idx_cap) idx_out[kk] = rows[i];
+            ++kk;
+        }
+    if (k_out) *k_out = kk;
+    if (idx_out && kk > idx_cap) return cfail(c, PIE_E_CAPACITY, "idx_cap %zu < %zu rows", idx_cap, kk);
     return PIE_OK;
 }
 

@@ -3207,7 +3207,17 @@ __global__ __launch_bounds__(256) void k_wide_tiles(WideTailArgs t)
     }
 }
 
-__global__ __launch_bounds__(256) void k_wide_order(WideTailArgs t)
+// the message a wide tail writes beside the union arrays (pie_scan_wide_begin_union): the layout of k_wide_pack below,
+// [uoff[0..u_pad] | Mu | rows[0..cap) | masks[0..cap) as 2 * words int32 words per row], stored with msg_store (the
+// message may be mapped host memory, as the ordinary union tail's)
+struct WideMsgArgs {
+    int* msg;
+    int u_pad;
+    long long cap;
+};
+
+template <bool MSG>
+__device__ __forceinline__ void wide_order_body(const WideTailArgs& t, const WideMsgArgs& g)
 {
     __shared__ long long lds4[4];
     __shared__ int s_wsum[4];
@@ -3227,11 +3237,25 @@ __global__ __launch_bounds__(256) void k_wide_order(WideTailArgs t)
     for (int w = 0; w < wave; ++w) run += s_wsum[w];
     if (in_u) {
         t.uoff[u] = run;
+        if constexpr (MSG) msg_store(g.msg + u, (int)run);
         if (u == U - 1) {
             t.uoff[U] = run + nn;
             t.summary->m = (unsigned long long)(run + nn);
         }
     }
+    if constexpr (MSG) {
+        // message tail, by the last tile: uoff[u] = Mu for the padding users, then the Mu word (words U .. u_pad + 1)
+        if (blockIdx.x == gridDim.x - 1) {
+            const int last = (U - 1) & 255; // the thread that holds user U - 1
+            __shared__ long long s_mu;
+            if ((int)threadIdx.x == last) s_mu = run + nn;
+            __syncthreads();
+            const int mu = (int)s_mu;
+            for (int uu = U + (int)threadIdx.x; uu <= g.u_pad + 1; uu += 256) msg_store(g.msg + uu, mu);
+        }
+    }
+    int* const msg_rows = MSG ? g.msg + g.u_pad + 2 : nullptr;
+    int* const msg_masks = MSG ? msg_rows + g.cap : nullptr;
     unsigned long long todo = __ballot(in_u && nn > 0);
     while (todo) {
         const int src_lane = __ffsll((long long)todo) - 1;
@@ -3254,9 +3278,40 @@ __global__ __launch_bounds__(256) void k_wide_order(WideTailArgs t)
         if (lane < nb) {
             const long long pos = rq + rank;
             t.urows[pos] = r.idx;
-            for (int w = 0; w < t.words; ++w) t.umask[pos * t.words + w] = t.dmask[slot * kWideWords + w];
+            const bool in_msg = MSG && pos < g.cap;
+            if constexpr (MSG)
+                if (in_msg) msg_store(msg_rows + pos, r.idx);
+            for (int w = 0; w < t.words; ++w) {
+                const unsigned long long mw = t.dmask[slot * kWideWords + w];
+                t.umask[pos * t.words + w] = mw;
+                if constexpr (MSG) {
+                    if (in_msg) {
+                        int* const d = msg_masks + (pos * t.words + w) * 2;
+                        msg_store(d, (int)(unsigned)mw);
+                        msg_store(d + 1, (int)(unsigned)(mw >> 32));
+                    }
+                }
+            }
         }
     }
+}
+
+__global__ __launch_bounds__(256) void k_wide_order(WideTailArgs t)
+{
+    wide_order_body<false>(t, WideMsgArgs{nullptr, 0, 0});
+}
+
+// the message-writing form: the same launch also stores the message words at their positions, so the message is complete
+// when the batch's event has passed
+__global__ __launch_bounds__(256) void k_wide_order_msg(WideTailArgs t, WideMsgArgs g)
+{
+    wide_order_body<true>(t, g);
+}
+
+// the header of a wide batch that kept no union: uoff[0..u_pad] and the Mu word all -1
+__global__ __launch_bounds__(256) void k_wide_msg_none(int* __restrict__ msg, int u_pad)
+{
+    for (int i = (int)(blockIdx.x * blockDim.x + threadIdx.x); i <= u_pad + 1; i += (int)(gridDim.x * blockDim.x)) msg_store(msg + i, -1);
 }
 
 // query q's counts / offsets / row list out of a wide union (off the hot path: one query per launch; the prefix is k_block_prefix)

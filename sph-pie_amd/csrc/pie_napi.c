@@ -73,6 +73,13 @@
     X(int, pie_comm_step_collect, (pie_comm *, int64_t *))                                                          \
     X(int, pie_comm_step_gathered_ptr, (pie_comm *, int32_t, int64_t, void **, size_t *, size_t *, size_t *))       \
     X(int, pie_comm_step_read_gathered, (pie_comm *, int32_t, int32_t, int64_t, int32_t *, int32_t *, uint64_t *, size_t, size_t *)) \
+    X(int, pie_comm_wide_step_reserve, (pie_comm *, int32_t, int32_t, size_t))                                      \
+    X(int, pie_comm_wide_step_begin, (pie_comm *, const pie_query *, int32_t))                                      \
+    X(int, pie_comm_wide_step_finish, (pie_comm *, size_t *, size_t))                                               \
+    X(int, pie_comm_wide_step_collect, (pie_comm *, int64_t *))                                                     \
+    X(int, pie_comm_wide_step_status, (pie_comm *, int64_t, int32_t *))                                             \
+    X(int, pie_comm_wide_step_gathered_ptr, (pie_comm *, int32_t, int64_t, void **, size_t *, size_t *, size_t *, int *)) \
+    X(int, pie_comm_wide_step_read_gathered, (pie_comm *, int32_t, int32_t, int64_t, int32_t *, int32_t *, uint64_t *, size_t, int *, size_t *)) \
     X(int, pie_comm_expired_queue, (pie_comm *, int64_t, int64_t, int32_t *, size_t, size_t *))                     \
     X(int, pie_comm_archive_queue, (pie_comm *, int64_t, int64_t, int32_t *, size_t, size_t *))                     \
     X(int, pie_comm_queue_read, (pie_comm *, int32_t, int32_t *, int32_t *, int32_t *, size_t, size_t *))            \
@@ -1236,6 +1243,10 @@ static napi_value throw_comm(napi_env env, pie_comm *cm, int rc)
 typedef struct comm_box_s {
     pie_comm *comm;
     ctx_box *boxes; /* context handles handed out by commCtx and still alive */
+    /* queries of the WIDE steps begun and not finished on THIS communicator (at most six): kept here, not in file-static state,
+     * so two communicators (or two Node workers) never pop each other's n_q */
+    int wide_nq_ring[8];
+    unsigned wide_nq_head, wide_nq_tail;
 } comm_box;
 
 static void comm_unlink_ctx(ctx_box *b)
@@ -1343,6 +1354,7 @@ static napi_value fn_comm_destroy(napi_env env, napi_callback_info info)
     comm_orphan_ctxs(b); /* handles handed out by commCtx now read as destroyed contexts */
     if (b->comm) p_pie_comm_destroy(b->comm);
     b->comm = NULL;
+    b->wide_nq_head = b->wide_nq_tail = 0;
     return js_int(env, 0);
 }
 
@@ -1674,6 +1686,154 @@ static napi_value fn_comm_step_upad(napi_env env, napi_callback_info info)
     return js_int(env, (int64_t)u_pad);
 }
 
+/* ---- the pipelined WIDE exchange (pie_comm_wide_step_*): commWideStepReserve(comm, nQMax, unionCap); commWideStepBegin(comm, nows,
+ * cutoffs, masks) with 1..512 queries; commWideStepFinish(comm) -> [rank][query] M; commWideStepCollect(comm) -> step number
+ * (throws code -5 on every rank alike when a union outgrew the reservation or a rank kept no union); commWideStepStatus(comm, step)
+ * -> Int32Array[world] of Mu words (-1: that rank kept no union: repeat the step); commWideStepReadGathered(comm, at, src, step,
+ * uoff, rows, masks) -> {mu, words}, masks holding `words` 64-bit words per row. */
+static napi_value fn_comm_wide_step_reserve(napi_env env, napi_callback_info info)
+{
+    ARGS(3)
+    comm_box *cbx = get_comm_box(env, argv[0]);
+    if (!cbx) return NULL;
+    int32_t n_q = 0;
+    int64_t cap = 0;
+    CHECK(env, napi_get_value_int32(env, argv[1], &n_q));
+    CHECK(env, napi_get_value_int64(env, argv[2], &cap));
+    int rc = p_pie_comm_wide_step_reserve(cbx->comm, n_q, 0, (size_t)(cap > 0 ? cap : 0));
+    if (rc) return throw_comm(env, cbx->comm, rc);
+    return js_int(env, 0);
+}
+
+static napi_value fn_comm_wide_step_begin(napi_env env, napi_callback_info info)
+{
+    ARGS(4)
+    comm_box *cbx = get_comm_box(env, argv[0]);
+    if (!cbx) return NULL;
+    size_t a = 0, b = 0, c = 0;
+    int64_t *pn = typed(env, argv[1], napi_bigint64_array, &a), *pc = typed(env, argv[2], napi_bigint64_array, &b);
+    uint64_t *pm = typed(env, argv[3], napi_biguint64_array, &c);
+    if (!pn || !pc || !pm || a != b || a != c || a < 1 || a > PIE_WIDE_MAX) {
+        napi_throw_type_error(env, NULL, "commWideStepBegin(comm, BigInt64Array nows, BigInt64Array cutoffs, BigUint64Array masks): 1..512 queries, equal lengths");
+        return NULL;
+    }
+    if (cbx->wide_nq_head - cbx->wide_nq_tail >= 8) return throw_state(env, "pie_comm error -6: eight wide steps are begun: commWideStepFinish first");
+    pie_query *q = (pie_query *)malloc(a * sizeof(pie_query));
+    if (!q) {
+        napi_throw_error(env, NULL, "commWideStepBegin: out of host memory");
+        return NULL;
+    }
+    for (size_t k = 0; k < a; ++k) {
+        q[k].now = pn[k];
+        q[k].cutoff = pc[k];
+        q[k].mask = pm[k];
+    }
+    int rc = p_pie_comm_wide_step_begin(cbx->comm, q, (int32_t)a);
+    free(q);
+    if (rc) {
+        /* a partial failure drained every wide step in flight inside the library: nothing is left to finish here either */
+        if (rc != PIE_E_STATE && rc != PIE_E_INVAL) cbx->wide_nq_tail = cbx->wide_nq_head;
+        return throw_comm(env, cbx->comm, rc);
+    }
+    cbx->wide_nq_ring[cbx->wide_nq_head++ & 7] = (int)a;
+    return js_int(env, 0);
+}
+
+static napi_value fn_comm_wide_step_finish(napi_env env, napi_callback_info info)
+{
+    ARGS(1)
+    comm_box *cbx = get_comm_box(env, argv[0]);
+    if (!cbx) return NULL;
+    if (cbx->wide_nq_tail == cbx->wide_nq_head) return throw_state(env, "pie_comm error -6: commWideStepFinish without commWideStepBegin");
+    const int n_q = cbx->wide_nq_ring[cbx->wide_nq_tail & 7];
+    const int world = p_pie_comm_world(cbx->comm);
+    const size_t m_cap = (size_t)world * (size_t)n_q; /* the library checks it against local_ranks x the step's own n_q */
+    size_t *m = (size_t *)calloc(m_cap, sizeof *m);
+    if (!m) {
+        napi_throw_error(env, NULL, "out of memory");
+        return NULL;
+    }
+    int rc = p_pie_comm_wide_step_finish(cbx->comm, m, m_cap);
+    if (rc != PIE_E_CAPACITY) cbx->wide_nq_tail++; /* PIE_E_CAPACITY consumed nothing */
+    if (rc) {
+        free(m);
+        return throw_comm(env, cbx->comm, rc);
+    }
+    napi_value out;
+    napi_create_array_with_length(env, (size_t)world, &out);
+    for (int r = 0; r < world; ++r) {
+        napi_value row;
+        napi_create_array_with_length(env, (size_t)n_q, &row);
+        for (int k = 0; k < n_q; ++k) napi_set_element(env, row, (uint32_t)k, js_int(env, (int64_t)m[(size_t)r * n_q + k]));
+        napi_set_element(env, out, (uint32_t)r, row);
+    }
+    free(m);
+    return out;
+}
+
+static napi_value fn_comm_wide_step_collect(napi_env env, napi_callback_info info)
+{
+    ARGS(1)
+    comm_box *cbx = get_comm_box(env, argv[0]);
+    if (!cbx) return NULL;
+    int64_t step = -1;
+    int rc = p_pie_comm_wide_step_collect(cbx->comm, &step);
+    if (rc) return throw_comm(env, cbx->comm, rc);
+    return js_int(env, step);
+}
+
+/* commWideStepStatus(comm, step) -> Int32Array[world] */
+static napi_value fn_comm_wide_step_status(napi_env env, napi_callback_info info)
+{
+    ARGS(2)
+    pie_comm *cm = get_comm(env, argv[0]);
+    if (!cm) return NULL;
+    int64_t step = 0;
+    CHECK(env, napi_get_value_int64(env, argv[1], &step));
+    const int world = p_pie_comm_world(cm);
+    napi_value buf, out;
+    void *data = NULL;
+    CHECK(env, napi_create_arraybuffer(env, (size_t)world * 4, &data, &buf));
+    int rc = p_pie_comm_wide_step_status(cm, step, (int32_t *)data);
+    if (rc) return throw_comm(env, cm, rc);
+    CHECK(env, napi_create_typedarray(env, napi_int32_array, (size_t)world, buf, 0, &out));
+    return out;
+}
+
+/* commWideStepReadGathered(comm, atRank, srcRank, step, uoff Int32Array[>= uPad + 1], rows Int32Array, masks BigUint64Array) ->
+ * {mu, words, uPad}; masks must hold words x rows.length entries */
+static napi_value fn_comm_wide_step_read(napi_env env, napi_callback_info info)
+{
+    ARGS(7)
+    pie_comm *cm = get_comm(env, argv[0]);
+    if (!cm) return NULL;
+    int32_t at = 0, src = 0;
+    int64_t step = 0;
+    size_t no = 0, nr = 0, nm = 0, mu = 0, u_pad = 0, rs = 0, cap = 0;
+    int words = 0;
+    void *base = NULL;
+    CHECK(env, napi_get_value_int32(env, argv[1], &at));
+    CHECK(env, napi_get_value_int32(env, argv[2], &src));
+    CHECK(env, napi_get_value_int64(env, argv[3], &step));
+    int32_t *off = typed(env, argv[4], napi_int32_array, &no), *rows = typed(env, argv[5], napi_int32_array, &nr);
+    uint64_t *masks = typed(env, argv[6], napi_biguint64_array, &nm);
+    int rc = p_pie_comm_wide_step_gathered_ptr(cm, at, step, &base, &rs, &u_pad, &cap, &words);
+    if (rc) return throw_comm(env, cm, rc);
+    if (!off || !rows || !masks || no < u_pad + 1 || words < 1) {
+        napi_throw_type_error(env, NULL, "commWideStepReadGathered(comm, at, src, step, Int32Array[>= uPad + 1], Int32Array rows, BigUint64Array masks)");
+        return NULL;
+    }
+    const size_t room = nr < nm / (size_t)words ? nr : nm / (size_t)words;
+    rc = p_pie_comm_wide_step_read_gathered(cm, at, src, step, off, rows, masks, room, &words, &mu);
+    if (rc) return throw_comm(env, cm, rc);
+    napi_value out;
+    CHECK(env, napi_create_object(env, &out));
+    napi_set_named_property(env, out, "mu", js_int(env, (int64_t)mu));
+    napi_set_named_property(env, out, "words", js_int(env, words));
+    napi_set_named_property(env, out, "uPad", js_int(env, (int64_t)u_pad));
+    return out;
+}
+
 /* stats(ctx) -> {rows, users, selected, algBytes, k1MsSum, scanMsSum, nProfiled, maxBucket} */
 static napi_value fn_stats(napi_env env, napi_callback_info info)
 {
@@ -1753,7 +1913,9 @@ static napi_value init(napi_env env, napi_value exports)
         {"commGenSyntheticSharded", fn_comm_gen}, {"commScanBatchGather", fn_comm_scan_gather}, {"commReadGathered", fn_comm_read}, {"commUPad", fn_comm_upad},
         {"commNeededCap", fn_comm_needed_cap}, {"commStepReserve", fn_comm_step_reserve}, {"commStepBegin", fn_comm_step_begin},
         {"commStepFinish", fn_comm_step_finish}, {"commStepCollect", fn_comm_step_collect}, {"commStepReadGathered", fn_comm_step_read},
-        {"commStepUPad", fn_comm_step_upad}, {"commExpiredQueue", fn_comm_expired_queue}, {"commArchiveQueue", fn_comm_archive_queue},
+        {"commStepUPad", fn_comm_step_upad}, {"commWideStepReserve", fn_comm_wide_step_reserve}, {"commWideStepBegin", fn_comm_wide_step_begin},
+        {"commWideStepFinish", fn_comm_wide_step_finish}, {"commWideStepCollect", fn_comm_wide_step_collect},
+        {"commWideStepStatus", fn_comm_wide_step_status}, {"commWideStepReadGathered", fn_comm_wide_step_read}, {"commExpiredQueue", fn_comm_expired_queue}, {"commArchiveQueue", fn_comm_archive_queue},
         {"shardMaps", fn_shard_maps},
     };
     for (size_t i = 0; i < sizeof table / sizeof table[0]; ++i) {

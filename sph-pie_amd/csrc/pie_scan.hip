@@ -2971,7 +2971,7 @@ int ensure_wide(pie_ctx* c, BatchSlot& b)
     return PIE_OK;
 }
 
-int wide_begin(pie_ctx* c, const pie_query* qs, int n_q)
+int wide_begin(pie_ctx* c, const pie_query* qs, int n_q, int* msg = nullptr, int u_pad = 0, long long msg_cap = 0)
 {
     queue_forget(c);
     if (c->cap_rows == 0) return fail(c, PIE_E_STATE, "no table loaded");
@@ -3048,7 +3048,8 @@ int wide_begin(pie_ctx* c, const pie_query* qs, int n_q)
     b.union_ok = b.union_part = false;
     b.mu = 0;
     if (c->bres == &b) c->bres = nullptr;
-    b.msg_kind = 0; b.msg = nullptr; b.msg_counts = nullptr;
+    b.msg_kind = msg ? 2 : 0; b.msg = msg; b.msg_counts = nullptr; // (2: the tail writes the wide union message, pie_scan_wide_begin_union)
+    b.msg_u_pad = u_pad; b.msg_cap = msg_cap;
     b.ev_index = -1;
     b.ordered = false;
     b.unsupported = unsupported;
@@ -3133,7 +3134,8 @@ int wide_begin(pie_ctx* c, const pie_query* qs, int n_q)
     t.umask = w.umask;
     const unsigned tiles = (unsigned)((c->n_users + 255) / 256);
     hipLaunchKernelGGL(k_wide_tiles, dim3(tiles), dim3(256), 0, s, t);
-    hipLaunchKernelGGL(k_wide_order, dim3(tiles), dim3(256), 0, s, t);
+    if (b.msg) hipLaunchKernelGGL(k_wide_order_msg, dim3(tiles), dim3(256), 0, s, t, WideMsgArgs{b.msg, b.msg_u_pad, b.msg_cap});
+    else hipLaunchKernelGGL(k_wide_order, dim3(tiles), dim3(256), 0, s, t);
     PIE_HIP(c, hipGetLastError());
     PIE_HIP(c, hipMemcpyAsync(w.h_sum, sum, sizeof(Summary), hipMemcpyDeviceToHost, s));
     PIE_HIP(c, hipMemcpyAsync(reinterpret_cast<char*>(w.h_sum) + kSummaryBytes, mq, (size_t)n_q * 4, hipMemcpyDeviceToHost, s));
@@ -3226,14 +3228,15 @@ int wide_need_list(pie_ctx* c, BatchSlot& b, int q)
     return PIE_OK;
 }
 
-int wide_finish(pie_ctx* c, size_t* m_out, size_t m_cap, int* n_q_out)
+int wide_finish(pie_ctx* c, size_t* m_out, size_t m_cap, int* n_q_out, int* ready_out = nullptr)
 {
+    if (ready_out) *ready_out = 0;
     BatchSlot* bp = oldest_batch(c);
     if (!bp) return fail(c, PIE_E_STATE, "pie_scan_wide_finish without a batch in flight");
     if (n_q_out) *n_q_out = bp->n_q;
     if (m_out && m_cap < (size_t)bp->n_q) return fail(c, PIE_E_CAPACITY, "m_cap %zu < %d queries", m_cap, bp->n_q);
     if (!bp->wide) { // an ordinary batch is the oldest: finished as pie_scan_batch_finish does
-        int rc = batch_finish(c, nullptr);
+        int rc = batch_finish(c, ready_out);
         if (rc) return rc;
         if (m_out)
             for (int q = 0; q < c->bres->n_q; ++q) m_out[q] = (size_t)c->bres->last[q].m;
@@ -3295,6 +3298,22 @@ int wide_finish(pie_ctx* c, size_t* m_out, size_t m_cap, int* n_q_out)
     b.have_result = true;
     c->bres = &b;
     c->last_was_batch = true;
+    if (b.msg_kind == 2) {
+        // the tail wrote the message (complete: its event has passed) unless the batch kept no union: then the header says so
+        // (Mu = -1, uoff all -1), written on the context's stream behind the batch
+        const bool kept = !b.unsupported && b.union_ok;
+        if (!kept || !ready_out) {
+            int rc = order_after_batch(c, b);
+            if (rc) return rc;
+        }
+        if (!kept) {
+            unsigned grid = (unsigned)((b.msg_u_pad + 2 + 255) / 256);
+            if (grid > (unsigned)c->n_cus * 8) grid = (unsigned)c->n_cus * 8;
+            hipLaunchKernelGGL(k_wide_msg_none, dim3(grid), dim3(256), 0, c->stream, b.msg, b.msg_u_pad);
+            PIE_HIP(c, hipGetLastError());
+        }
+        if (ready_out) *ready_out = kept ? 1 : 0;
+    } else if (ready_out) *ready_out = 1; // no message to wait for (as pie_scan_batch_finish_packed)
     if (bad) return fail(c, PIE_E_INVAL, "%u selected rows carry a user id outside [0, %d)", bad, c->n_users);
     if (m_out)
         for (int q = 0; q < b.n_q; ++q) m_out[q] = (size_t)w.m[q];
@@ -4040,6 +4059,26 @@ int pie_scan_wide_finish(pie_ctx* c, size_t* m_out, size_t m_cap, int* n_q_out)
     if (n_q_out) *n_q_out = 0;
     PIE_HIP(c, hipSetDevice(c->device));
     return wide_finish(c, m_out, m_cap, n_q_out);
+}
+
+int pie_scan_wide_begin_union(pie_ctx* c, const pie_query* queries, int n_q, void* msg_i32, size_t u_pad, size_t cap)
+{
+    if (!c) return PIE_E_INVAL;
+    if (!msg_i32 || u_pad < (size_t)c->n_users || u_pad > 0x7FFFFFF0u) return fail(c, PIE_E_INVAL, "bad union destination / u_pad < n_users");
+    if (cap > ((size_t)1 << 40)) return fail(c, PIE_E_INVAL, "cap %zu is not a row capacity", cap);
+    PIE_HIP(c, hipSetDevice(c->device));
+    return wide_begin(c, queries, n_q, (int*)msg_i32, (int)u_pad, (long long)cap);
+}
+
+int pie_scan_wide_finish_packed(pie_ctx* c, size_t* m_out, size_t m_cap, int* n_q_out, int* ready_out)
+{
+    if (!c) return PIE_E_INVAL;
+    if (n_q_out) *n_q_out = 0;
+    int ready = 0;
+    PIE_HIP(c, hipSetDevice(c->device));
+    int rc = wide_finish(c, m_out, m_cap, n_q_out, &ready);
+    if (ready_out) *ready_out = rc == PIE_OK ? ready : 0;
+    return rc;
 }
 
 int pie_batch_union_wide_device_ptrs(pie_ctx* c, void** uoff_dev, void** rows_dev, void** masks_dev, int* words_out, size_t* mu_out)
