@@ -108,8 +108,15 @@ int pie_save_columns(pie_ctx *ctx, const char *dir);
 int pie_load_columns_dir(pie_ctx *ctx, const char *dir);
 /* Copy the resident columns back (any pointer may be NULL). */
 int pie_read_columns(pie_ctx *ctx, int64_t *start, int64_t *end, int32_t *user, int32_t *disc, size_t n);
-/* touchSession (server/sessionStore.js:37-45): end[row] = new_end.  deleteSession (:47-53): new_end = PIE_END_NONE. */
+/* touchSession (server/sessionStore.js:37-45): end[row] = new_end.  deleteSession (:47-53): new_end = PIE_END_NONE.
+ * A call that names a row more than once behaves as its elements applied in array order, as two touches or deletes of one token
+ * run one after the other in the reference: the last occurrence's value is the row's `end`, and every derived structure (both
+ * liveness keys, the hot index, the ordered run) agrees with that value.  The repeats are resolved on the host before the
+ * rows are staged (scratch sized by k, never by the table); the call stays queued and un-waited where it was. */
 int pie_set_end(pie_ctx *ctx, const int32_t *rows, const int64_t *new_end, size_t k);
+/* Host only, no context, no GPU: the reduction pie_set_end applies to its call.  keep_out[i] = 1 iff element i is the last
+ * occurrence of rows[i] in rows[0, k), else 0 (any int32 is a row here; k = 0 is allowed).  For tests. */
+int pie_set_end_last_writers(const int32_t *rows, size_t k, uint8_t *keep_out);
 /* deleteSessionsForUser (server/sessionStore.js:55-64): tombstone every live row with user == u (strict match;
  * unknown ids are a no-op like the falsy-id guard :56-58).  rows_out (may be NULL) receives the tombstoned row
  * indices in ascending order so the host can drop their token-map entries; *n_deleted their number. */

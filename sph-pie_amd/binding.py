@@ -71,6 +71,7 @@ _SIGS = [
     ("pie_load_columns_dir", C.c_int, [_P, C.c_char_p]),
     ("pie_read_columns", C.c_int, [_P, _P, _P, _P, _P, C.c_size_t]),
     ("pie_set_end", C.c_int, [_P, _P, _P, C.c_size_t]),
+    ("pie_set_end_last_writers", C.c_int, [_P, C.c_size_t, _P]),
     ("pie_delete_user", C.c_int, [_P, C.c_int32, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("pie_prune_before", C.c_int, [_P, C.c_int64, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("pie_retention_purge", C.c_int, [_P, C.c_int64, C.c_int32, C.c_int64, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
@@ -280,6 +281,8 @@ class PieScan:
         return s, e, u, d
 
     def set_end(self, rows, new_end):
+        """end[rows[i]] = new_end[i], the elements applied in array order: a row named more than once ends on the value of its
+        last occurrence, in `end` and in every structure derived from it (pie_set_end)."""
         rows, new_end = _col(rows, np.int32), _col(new_end, np.int64)
         self._check(self._lib.pie_set_end(self._ctx, _ptr(rows), _ptr(new_end), rows.shape[0]))
 
@@ -1051,6 +1054,17 @@ def split_wide_message(msg, u_pad, cap, words):
 
 def shard_of(user, n_shards):
     return load_library().pie_shard_of(int(user), int(n_shards))
+
+
+def set_end_last_writers(rows):
+    """Host only (pie_set_end_last_writers): uint8[k], 1 where the element is the last occurrence of its row in `rows` — the
+    elements of a set_end call that reach the device."""
+    rows = _col(rows, np.int32)
+    keep = np.empty(rows.shape[0], np.uint8)
+    rc = load_library().pie_set_end_last_writers(_ptr(rows), rows.shape[0], _ptr(keep))
+    if rc != 0:
+        raise PieError(rc, "pie_set_end_last_writers: bad argument")
+    return keep
 
 
 def batch_mask_codes(queries, n_disc, start, end, disc, fallback=None):

@@ -288,6 +288,8 @@ struct pie_ctx {
     struct AsyncStage { char* h = nullptr; char* d = nullptr; size_t bytes = 0; hipEvent_t ev = nullptr; bool pending = false; } astage[2];
     int astage_next = 0;
     bool async_mutations = true;   // PIE_ASYNC_MUTATIONS=0: every append / touch waits for its kernel (A/B runs)
+    std::vector<uint8_t> set_end_keep;   // pie_set_end: which elements of the call are the last on their row; sized by the call
+    std::vector<size_t> set_end_slots;   // ... and the scratch that finds them (set_end_last_writers)
     int* d_shard_rows = nullptr;   // pie_shard_table: local row -> global row
     int* d_shard_users = nullptr;  // ... local user -> global user
     long long shard_rows_n = 0;
@@ -3788,22 +3790,92 @@ int pie_read_columns(pie_ctx* c, int64_t* start, int64_t* end, int32_t* user, in
     return PIE_OK;
 }
 
-int pie_set_end(pie_ctx* c, const int32_t* rows, const int64_t* new_end, size_t k)
+// pie_set_end applies its elements in array order, so of the elements that name one row only the last one counts.  k_set_end
+// gives every element a thread of its own and orders nothing between them: the repeats are resolved here, on the host, and the
+// kernel only ever sees distinct rows.  keep[i] = 1 iff no later element names rows[i].  A call whose rows strictly ascend or
+// strictly descend has no repeats (one pass, no memory); any other goes through an open-addressed table of positions, at
+// most half full, sized by k alone (`slots` is scratch the caller keeps between calls).  -> false: out of memory.
+static bool set_end_last_writers(const int32_t* rows, size_t k, uint8_t* keep, std::vector<size_t>& slots)
+{
+    if (k == 0) return true;
+    size_t up = 0, down = 0; // counted, not tested element by element: the loop has no branch and vectorises
+    for (size_t i = 1; i < k; ++i) {
+        up += rows[i - 1] < rows[i] ? 1 : 0;
+        down += rows[i - 1] > rows[i] ? 1 : 0;
+    }
+    memset(keep, 1, k);
+    if (up == k - 1 || down == k - 1) return true;
+    int bits = 4;
+    while (bits < 62 && ((size_t)1 << bits) < 2 * k) ++bits;
+    const size_t n_slots = (size_t)1 << bits, mask = n_slots - 1, none = ~(size_t)0;
+    try {
+        slots.assign(n_slots, none);
+    } catch (...) {
+        return false;
+    }
+    size_t* const tab = slots.data();
+    for (size_t i = 0; i < k; ++i) {
+        const int32_t r = rows[i];
+        size_t at = (size_t)(((uint64_t)(uint32_t)r * 0x9E3779B97F4A7C15ULL) >> (64 - bits));
+        while (tab[at] != none && rows[tab[at]] != r) at = (at + 1) & mask;
+        if (tab[at] != none) keep[tab[at]] = 0; // an earlier element on the same row: this one overrides it
+        tab[at] = i;
+    }
+    return true;
+}
+
+int pie_set_end_last_writers(const int32_t* rows, size_t k, uint8_t* keep_out)
+{
+    if (k && (!rows || !keep_out)) return PIE_E_INVAL;
+    std::vector<size_t> slots;
+    return set_end_last_writers(rows, k, keep_out, slots) ? PIE_OK : PIE_E_NOMEM;
+}
+
+// [new_end kept | rows kept] of the elements with keep[i] set, in array order, into a staging area; -> their number
+static size_t set_end_stage(char* dst, const int32_t* rows, const int64_t* new_end, size_t k, const uint8_t* keep, size_t n_kept)
+{
+    if (n_kept == k) {
+        memcpy(dst, new_end, k * 8);
+        memcpy(dst + k * 8, rows, k * 4);
+        return k;
+    }
+    int64_t* e = reinterpret_cast<int64_t*>(dst);
+    int32_t* r = reinterpret_cast<int32_t*>(dst + n_kept * 8);
+    size_t j = 0;
+    for (size_t i = 0; i < k; ++i)
+        if (keep[i]) {
+            e[j] = new_end[i];
+            r[j] = rows[i];
+            ++j;
+        }
+    return j;
+}
+
+int pie_set_end(pie_ctx* c, const int32_t* rows, const int64_t* new_end, size_t k_given)
 {
     if (!c) return PIE_E_INVAL;
-    if (k == 0) return PIE_OK;
+    if (k_given == 0) return PIE_OK;
     if (!rows || !new_end) return fail(c, PIE_E_INVAL, "NULL pointer");
     if (c->n_flight || c->b_flight) return fail(c, PIE_E_STATE, "table change while a scan is in flight");
-    for (size_t i = 0; i < k; ++i)
+    for (size_t i = 0; i < k_given; ++i)
         if (rows[i] < 0 || rows[i] >= c->n) return fail(c, PIE_E_INVAL, "row %d outside the table", rows[i]);
+    // a row named more than once takes the value of its last element (the header's rule): the others are left out here
+    try {
+        c->set_end_keep.resize(k_given);
+    } catch (...) {
+        return fail(c, PIE_E_NOMEM, "no memory for %zu touches", k_given);
+    }
+    const uint8_t* keep = c->set_end_keep.data();
+    if (!set_end_last_writers(rows, k_given, c->set_end_keep.data(), c->set_end_slots)) return fail(c, PIE_E_NOMEM, "no memory for %zu touches", k_given);
+    size_t k = 0;
+    for (size_t i = 0; i < k_given; ++i) k += keep[i];
     PIE_HIP(c, hipSetDevice(c->device));
-    hot_reserve(c, (long long)k);
+    hot_reserve(c, (long long)k_given); // the bound counts every element: never less than the rows that can move to the delta
     if (c->async_mutations && !c->ord.valid) { // queued, not waited for (see AsyncStage); the rows were checked above
         pie_ctx::AsyncStage* a = nullptr;
         int rca = async_stage(c, k * 12 + 64, &a);
         if (rca) return rca;
-        memcpy(a->h, new_end, k * 8);
-        memcpy(a->h + k * 8, rows, k * 4);
+        set_end_stage(a->h, rows, new_end, k_given, keep, k);
         PIE_HIP(c, hipMemcpyAsync(a->d, a->h, k * 12, hipMemcpyHostToDevice, c->stream));
         hipLaunchKernelGGL(k_set_end, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, c->stream, c->d_end,
                            reinterpret_cast<const int*>(a->d + k * 8), reinterpret_cast<const long long*>(a->d), (long long)k, c->n,
@@ -3817,8 +3889,7 @@ int pie_set_end(pie_ctx* c, const int32_t* rows, const int64_t* new_end, size_t 
     // staged like the append path: one upload of [new_end k | rows k], one kernel (end + both keys), one wait
     int rc = ensure_stage(c, k * 12 + 64);
     if (rc) return rc;
-    memcpy(c->h_stage, new_end, k * 8);
-    memcpy(c->h_stage + k * 8, rows, k * 4);
+    set_end_stage(c->h_stage, rows, new_end, k_given, keep, k);
     PIE_HIP(c, hipMemcpyAsync(c->d_stage, c->h_stage, k * 12, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(k_set_end, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, c->stream, c->d_end,
                        reinterpret_cast<const int*>(c->d_stage + k * 8), reinterpret_cast<const long long*>(c->d_stage), (long long)k, c->n,

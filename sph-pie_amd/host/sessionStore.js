@@ -44,6 +44,7 @@ function createStore(options){
   const userIds = [];                              // dense int32 -> userId string
   let uploaded = 0;                                // rows [0, uploaded) are resident on the device
   let pendingEnd = new Map();                      // row -> BigInt new end (touch / delete of resident rows)
+                                                   // one entry per row, the last value: what pie_set_end itself does with a row named twice
   let lastPurge = null;
   let out = null;                                  // scan output arrays, sized lazily
   let generation = 0;                              // bumped by every change a scan could see AND by every native call that

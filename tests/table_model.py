@@ -113,7 +113,14 @@ class TableModel:
         self.U = int(U)
 
     def set_end(self, rows, new_end):
-        self.end[np.asarray(rows, np.int64)] = np.asarray(new_end, np.int64)
+        """The elements applied in array order: of the elements that name one row the last one gives the row its `end`
+        (include/pie_scan.h).  Said outright, not left to what numpy does with a repeated fancy index: the last occurrence of
+        every row is the first one in the reversed array, and only those elements are stored."""
+        rows, new_end = np.asarray(rows, np.int64).reshape(-1), np.asarray(new_end, np.int64).reshape(-1)
+        assert rows.size == new_end.size
+        _, first_in_reversed = np.unique(rows[::-1], return_index=True)
+        last = rows.size - 1 - first_in_reversed
+        self.end[rows[last]] = new_end[last]
 
     def _tombstone(self, sel):
         rows = np.nonzero(sel & (self.end != INT64_MIN))[0].astype(np.int32)
@@ -272,6 +279,53 @@ def ctx_with_env(pie, hot, async_mut):
                 os.environ.pop(k, None)
             else:
                 os.environ[k] = v
+
+
+# ------------------------------------------------------------------------------------------------ key-edge sweeps
+class Edge:
+    """A hand-made table in a context and in the model; sweeps of queries compared one by one."""
+
+    def __init__(self, pie, oracle, cols, U, D, hot=1, ordered=1, async_mut=1):
+        self.m = TableModel(oracle)
+        self.m.load(*cols, U, D)
+        self.ctx = ctx_with_env(pie, hot, async_mut)
+        self.ctx.set_ordered_run(ordered)
+        self.ctx.load_columns(*self.m.columns(), U)
+        self.ctx.set_disciplines(ALL, D)
+
+    def columns_match(self, tag):
+        for name, got, want in zip(("start", "end", "user", "disc"), self.ctx.read_columns(), self.m.columns()):
+            assert got.dtype == want.dtype and np.array_equal(got, want), (tag, "column " + name)
+
+    def sweep(self, tag, queries, single_every=9):
+        ctx, m = self.ctx, self.m
+        for b in range(0, len(queries), 64):
+            qs = queries[b:b + 64]
+            wants = m.scan_many(qs)
+            got = ctx.scan_batch(qs)
+            for qi in range(len(qs)):
+                same(got[qi], wants[qi], (tag, "batch at", b, "query", qs[qi]))
+        for now, cutoff, mask in queries[::single_every]:
+            ctx.set_disciplines(mask, m.D)
+            same(ctx.scan(now, cutoff), m.scan(now, cutoff, mask), (tag, "single scan", now, cutoff, mask))
+        ctx.set_disciplines(ALL, m.D)
+
+    def set_end(self, tag, rows, ne):
+        rows, ne = np.asarray(rows, np.int32), np.asarray(ne, np.int64)
+        self.ctx.set_end(rows, ne)
+        self.m.set_end(rows, ne)
+        self.columns_match(tag)
+
+
+def around(values):
+    nows = sorted({int(v) + k for v in values for k in (-1, 0, 1) if INT64_MIN < int(v) + k <= INT64_MAX})
+    return nows
+
+
+def liveness_queries(oracle, nows):
+    masks = [ALL, 0x55555555, 0xAAAAAAAA, 0x1, 0x80000001]
+    cutoffs = [INT64_MIN, oracle.T0_MS - 40 * DAY]
+    return [(now, cutoffs[i % 2], masks[i % 5]) for i, now in enumerate(nows)]
 
 
 def chain_config(seed):

@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 import table_model as T
-from table_model import ALL, DAY, HOUR, INT64_MAX, INT64_MIN, YEAR
+from table_model import ALL, DAY, HOUR, INT64_MAX, INT64_MIN, YEAR, Edge, around, liveness_queries
 
 pytestmark = pytest.mark.gpu
 
@@ -44,52 +44,7 @@ def test_model_sequences_reached_every_path():
 
 
 # ------------------------------------------------------------------------------------------------ key-edge sweeps
-class Edge:
-    """A hand-made table in a context and in the model; sweeps of queries compared one by one."""
-
-    def __init__(self, pie, oracle, cols, U, D, hot=1, ordered=1):
-        self.m = T.TableModel(oracle)
-        self.m.load(*cols, U, D)
-        self.ctx = T.ctx_with_env(pie, hot, 1)
-        self.ctx.set_ordered_run(ordered)
-        self.ctx.load_columns(*self.m.columns(), U)
-        self.ctx.set_disciplines(ALL, D)
-
-    def columns_match(self, tag):
-        for name, got, want in zip(("start", "end", "user", "disc"), self.ctx.read_columns(), self.m.columns()):
-            assert got.dtype == want.dtype and np.array_equal(got, want), (tag, "column " + name)
-
-    def sweep(self, tag, queries, single_every=9):
-        ctx, m = self.ctx, self.m
-        for b in range(0, len(queries), 64):
-            qs = queries[b:b + 64]
-            wants = m.scan_many(qs)
-            got = ctx.scan_batch(qs)
-            for qi in range(len(qs)):
-                T.same(got[qi], wants[qi], (tag, "batch at", b, "query", qs[qi]))
-        for now, cutoff, mask in queries[::single_every]:
-            ctx.set_disciplines(mask, m.D)
-            T.same(ctx.scan(now, cutoff), m.scan(now, cutoff, mask), (tag, "single scan", now, cutoff, mask))
-        ctx.set_disciplines(ALL, m.D)
-
-    def set_end(self, tag, rows, ne):
-        rows, ne = np.asarray(rows, np.int32), np.asarray(ne, np.int64)
-        self.ctx.set_end(rows, ne)
-        self.m.set_end(rows, ne)
-        self.columns_match(tag)
-
-
-def around(values):
-    nows = sorted({int(v) + k for v in values for k in (-1, 0, 1) if INT64_MIN < int(v) + k <= INT64_MAX})
-    return nows
-
-
-def liveness_queries(oracle, nows):
-    masks = [ALL, 0x55555555, 0xAAAAAAAA, 0x1, 0x80000001]
-    cutoffs = [INT64_MIN, oracle.T0_MS - 40 * DAY]
-    return [(now, cutoffs[i % 2], masks[i % 5]) for i, now in enumerate(nows)]
-
-
+# (the Edge helper, around() and liveness_queries() live in table_model.py: test_gpu_set_end_repeats.py uses them too)
 @pytest.mark.parametrize("ordered", [0, 2])
 @pytest.mark.parametrize("hot", [1, 0])
 def test_liveness_edges_on_a_lattice(pie, oracle, hot, ordered):

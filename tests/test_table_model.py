@@ -92,3 +92,25 @@ def test_lattice_values_are_bin_edges(oracle):
     # the tie table: a run of equal starts longer than a wave and than the 16-record direct bucket, for one user
     s, e, u, d, U, D = T.tie_table(oracle)
     assert np.unique(s[u == 0]).size == 1 and np.count_nonzero(u == 0) > 64 and np.any(d >= 64) and np.any(d < 0) and np.any(d == 63)
+
+
+def test_set_end_with_repeated_rows_keeps_the_last_value(oracle):
+    """TableModel.set_end against a plain loop over the elements in array order: repeats next to each other, far apart, with
+    equal and with different values, tombstones among them; rows the call does not name stay as they were."""
+    rng = np.random.default_rng(12)
+    n = 500
+    for k, distinct in ((1, 1), (2, 1), (300, 40), (16384, 40), (16384, n), (400, 400)):
+        m = T.TableModel(oracle)
+        m.load(*oracle.gen(5, n, 0, n, 7, 4, 0), 7, 4)
+        before = m.end.copy()
+        pool = rng.choice(n, min(distinct, n), replace=False)
+        rows = rng.choice(pool, k).astype(np.int32) if distinct < k else rng.permutation(n)[:k].astype(np.int32)
+        ne = rng.choice(np.array([INT64_MIN, 2 ** 63 - 1, oracle.T0_MS, oracle.T0_MS + 1], np.int64), k) + 0
+        ne[::3] = rng.integers(-2 ** 62, 2 ** 62, ne[::3].size)
+        want = [int(v) for v in before]
+        for r, v in zip(rows.tolist(), ne.tolist()):
+            want[r] = v
+        m.set_end(rows, ne)
+        assert m.end.dtype == np.int64 and [int(v) for v in m.end] == want, (k, distinct)
+        untouched = np.setdiff1d(np.arange(n), rows)
+        assert np.array_equal(m.end[untouched], before[untouched])
