@@ -388,8 +388,28 @@ typedef struct pie_table_info {
     uint64_t compactions;     /* pie_compact_rows calls that succeeded on this context */
     double compact_count_ms;  /* device time (HIP events around the two kernels) of the last compaction's count pass and prefix ... */
     double compact_write_ms;  /* ... and of its write pass */
+    /* fields below were added with the slot-ordered hot index, under the same rule */
+    double hot_build_ms;      /* device time of the hot index's last build (count, scan, and the scatter or keys + sort + gather) */
+    uint32_t hot_order;       /* records inside a bin of the index: 0 ascending row, 1 by histogram slot (the order of the index
+                               * that stands; with none, the order the next build will try: PIE_HOT_ORDER) */
+    uint32_t hot_slot_bits;   /* bits of a histogram slot in the sort key at the present user count */
 } pie_table_info;
 int pie_table_info_get(pie_ctx *ctx, pie_table_info *out);
+/* The hot index's layout, for tests and tools (host-only readers; not while a scan is in flight).  The index groups the rows
+ * whose `end` reaches the fine key's base by fine-key bin 1..127; off[k] is the first record of bin k, off[128] = n_main.
+ * Inside a bin the records stand by ascending sort key, rows ascending among equal keys, where
+ *     key = (bin << pie_hot_slot_bits(n_users)) | histogram slot of the record's user
+ * at the user count of the build (PIE_HOT_ORDER=slot, the default; hot_order = 1), or by ascending row (PIE_HOT_ORDER=row, or a
+ * slot build that found no scratch memory or no room for bin and slot in 32 bits; hot_order = 0).  The order is a locality
+ * hint for the pass's histogram atomics and reaches no result; appends that add users leave it stale until the next build.
+ * pie_hot_layout: off[129] and *n_main; user / row / bin of the n_main main records when any of the three is given (cap = room
+ * in each, PIE_E_CAPACITY when n_main is larger); pos[n_pos] = the record of rows 0 .. n_pos - 1, -1 for a row the index does
+ * not hold.  Every pointer may be NULL.  PIE_E_STATE when there is no index.
+ * pie_hot_order_key, pie_hot_slot_bits: pure host functions, no context. */
+int pie_hot_layout(pie_ctx *ctx, int64_t *off, int64_t *n_main, int32_t *user, int32_t *row, int32_t *bin, size_t cap,
+                   int32_t *pos, size_t n_pos);
+uint64_t pie_hot_order_key(uint32_t bin, int32_t user, uint32_t n_users);
+uint32_t pie_hot_slot_bits(uint32_t n_users);
 /* The ordered run (sph-pie_amd/csrc/pie_ordered.h): the table's rows a second time, in (user, start, row) order — the order
  * of every answer — so that a query is a filter over positions: no histogram atomics, no per-bucket sort, no dependence on
  * how rows are spread over users.  There is no counterpart in the reference (its Map is scanned per request,

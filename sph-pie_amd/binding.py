@@ -34,6 +34,7 @@ class PieTableInfo(C.Structure):
         ("ordered_build_ms", C.c_double), ("ordered_builds", C.c_uint64), ("ordered_positions", C.c_uint64),
         ("ordered_respreads", C.c_uint64), ("hot_rows", C.c_uint64), ("hot_bytes", C.c_uint64), ("hot_builds", C.c_uint64),
         ("compact_bytes", C.c_uint64), ("compactions", C.c_uint64), ("compact_count_ms", C.c_double), ("compact_write_ms", C.c_double),
+        ("hot_build_ms", C.c_double), ("hot_order", C.c_uint32), ("hot_slot_bits", C.c_uint32),
     ]
 
 
@@ -95,6 +96,9 @@ _SIGS = [
     ("pie_scan_batch_flush", C.c_int, [_P]),
     ("pie_batch_pack_union_device", C.c_int, [_P, _P, C.c_size_t, C.c_size_t]),
     ("pie_table_info_get", C.c_int, [_P, C.POINTER(PieTableInfo)]),
+    ("pie_hot_layout", C.c_int, [_P, _P, C.POINTER(C.c_int64), _P, _P, _P, C.c_size_t, _P, C.c_size_t]),
+    ("pie_hot_order_key", C.c_uint64, [C.c_uint32, C.c_int32, C.c_uint32]),
+    ("pie_hot_slot_bits", C.c_uint32, [C.c_uint32]),
     ("pie_scan_batch_begin", C.c_int, [_P, C.POINTER(PieQuery), C.c_int]),
     ("pie_scan_batch_finish", C.c_int, [_P, C.POINTER(C.c_size_t)]),
     ("pie_scan_batch", C.c_int, [_P, C.POINTER(PieQuery), C.c_int, C.POINTER(C.c_size_t)]),
@@ -174,6 +178,15 @@ _SIGS = [
     ("pie_comm_queue_timing", C.c_int, [_P, C.POINTER(C.c_float)]),
 ]
 ABI_SYMBOLS = [s[0] for s in _SIGS]
+
+
+def hot_order_key(bin_, user, n_users):
+    """Sort key of a hot-index record: (bin << hot_slot_bits(n_users)) | histogram slot of the user (pie_hot_order_key)."""
+    return int(load_library().pie_hot_order_key(int(bin_), int(user), int(n_users)))
+
+
+def hot_slot_bits(n_users):
+    return int(load_library().pie_hot_slot_bits(int(n_users)))
 
 _lib = None
 
@@ -415,6 +428,16 @@ class PieScan:
         ti.struct_size = C.sizeof(PieTableInfo)
         self._check(self._lib.pie_table_info_get(self._ctx, C.byref(ti)))
         return {k: getattr(ti, k) for k, _ in PieTableInfo._fields_}
+
+    def hot_layout(self):
+        """The hot index as the device holds it (pie_hot_layout): off[129], n_main, user / row / bin of the main records, pos[n]."""
+        off, nm = np.empty(129, np.int64), C.c_int64(0)
+        self._check(self._lib.pie_hot_layout(self._ctx, _ptr(off), C.byref(nm), None, None, None, 0, None, 0))
+        m = nm.value
+        user, row, bin_ = np.empty(m, np.int32), np.empty(m, np.int32), np.empty(m, np.int32)
+        pos = np.empty(self.n, np.int32)
+        self._check(self._lib.pie_hot_layout(self._ctx, None, None, _ptr(user), _ptr(row), _ptr(bin_), m, _ptr(pos), self.n))
+        return {"off": off, "n_main": m, "user": user, "row": row, "bin": bin_, "pos": pos}
 
     def in_flight_packed(self):
         """True when the oldest scan in flight was begun with scan_begin_packed."""

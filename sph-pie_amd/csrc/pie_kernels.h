@@ -884,6 +884,85 @@ __global__ __launch_bounds__(256) void k_hot_scatter(const fkey_t* __restrict__ 
     }
 }
 
+// Slot order inside a bin (PIE_HOT_ORDER=slot).  The pass gives a wave 64 consecutive records and issues one returning
+// histogram atomic per selected one; atomics execute at the memory side a 64-byte line at a time, so what a wave instruction
+// costs is the number of distinct counter lines its lanes name.  With rows ascending inside a bin the users of 64 neighbours
+// are unrelated: ~one line per selected lane.  Ordered by hist_index(user) — the counter's own address — 64 neighbours of a
+// bin of R records over U users name ~64 U / R consecutive counters: a handful of lines.  Nothing reads the order for
+// correctness (the tail sorts every bucket by (start, row), the writers use pos[] and the entry's bin), so it is a locality
+// hint only: appends that raise n_users move every hist_index and leave the order stale, and exact, until the next build.
+//   key = (bin << slot_bits) | hist_index(user), ties in ascending row order (the sort is stable, its input row-ordered)
+// k_hot_keys    what k_hot_scatter does, but it writes (key, row) pairs where that writes records
+// k_hot_gather  the records and pos[] from the sorted pairs
+__device__ __forceinline__ unsigned hot_order_key(unsigned bin, int user, int n_users, int slot_bits)
+{
+    const unsigned pad = (unsigned)((n_users + 31) >> 5) * 32u;
+    const unsigned slot = (unsigned)user < pad ? (unsigned)hist_index(user, n_users) : 0u; // an id outside the table: any slot will do
+    return (bin << slot_bits) | slot;
+}
+
+__global__ __launch_bounds__(256) void k_hot_keys(const fkey_t* __restrict__ fkey, const PayRec* __restrict__ pay, long long n, long long seg_len,
+                                                  const unsigned* __restrict__ cnt, int n_users, int slot_bits,
+                                                  unsigned* __restrict__ key, int* __restrict__ val)
+{
+    __shared__ unsigned at[4][128];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long S = (long long)gridDim.x * 4, seg = (long long)blockIdx.x * 4 + wave;
+    at[wave][lane] = cnt[(long long)lane * S + seg];
+    at[wave][lane + 64] = cnt[(long long)(lane + 64) * S + seg];
+    __builtin_amdgcn_wave_barrier();
+    const unsigned long long lt = (1ull << lane) - 1ull;
+    const long long r0 = seg * seg_len, r1 = min(n, r0 + seg_len);
+    for (long long rb = r0; rb < r1; rb += kWave) {
+        const long long r = rb + lane;
+        const unsigned k = r < r1 ? fkey[r] : 0u;
+        unsigned long long todo = __ballot(k != 0);
+        while (todo) {
+            const unsigned kb = (unsigned)__shfl((int)k, __ffsll((long long)todo) - 1, kWave);
+            const unsigned long long m = __ballot(k == kb);
+            const unsigned base = at[wave][kb];
+            if (k == kb) {
+                const unsigned e = base + (unsigned)__popcll(m & lt);
+                key[e] = hot_order_key(kb, pay[r].user, n_users, slot_bits);
+                val[e] = (int)r;
+            }
+            __builtin_amdgcn_wave_barrier();
+            if (lane == 0) at[wave][kb] = base + (unsigned)__popcll(m);
+            __builtin_amdgcn_wave_barrier();
+            todo &= ~m;
+        }
+    }
+}
+
+// off[] from counts that a device-wide scan has already turned into their exclusive prefix (the slot build: k_hot_scan's
+// one block takes 3.7 ms over cfg3's 2 x 10^6 counts); `scanned` and `cnt` are the scan's output and input
+__global__ __launch_bounds__(192) void k_hot_offsets(const unsigned* __restrict__ scanned, const unsigned* __restrict__ cnt, long long S,
+                                                     long long* __restrict__ off)
+{
+    const int t = threadIdx.x;
+    if (t < 128) off[t] = (long long)scanned[(long long)t * S];
+    if (t == 128) off[128] = (long long)scanned[128 * S - 1] + (long long)cnt[128 * S - 1];
+}
+
+__global__ __launch_bounds__(256) void k_hot_gather(const unsigned* __restrict__ key, const int* __restrict__ val, long long n_main, int slot_bits,
+                                                    const long long* __restrict__ end, const PayRec* __restrict__ pay,
+                                                    HotRec* __restrict__ rec, int* __restrict__ pos)
+{
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= n_main) return;
+    const int r = val[e];
+    const PayRec p = pay[r];
+    HotRec h;
+    h.start = p.start;
+    h.end = end[r];
+    h.user = p.user;
+    h.disc = p.disc;
+    h.row = r;
+    h.bin = (int)(key[e] >> slot_bits);
+    rec[e] = h;
+    pos[r] = (int)e;
+}
+
 __global__ __launch_bounds__(256) void k_build_key(const long long* __restrict__ end, long long row0, long long n, long long base,
                                                    int shift, lkey_t* __restrict__ key, const long long* __restrict__ start,
                                                    const int* __restrict__ user, const int* __restrict__ disc,

@@ -355,6 +355,12 @@ struct pie_ctx {
         long long n_main = 0, delta_cap = 0, delta_bound = 0;
         bool valid = false;
         bool enabled = true;      // PIE_HOT_INDEX=0: never built (A/B runs)
+        int order = 1;            // PIE_HOT_ORDER: records inside a bin by row (0) or by histogram slot (1, see k_hot_keys)
+        int recs_per_thread = 2;  // records of the pass per thread of its launch (PIE_HOT_RECS=1|2|4, a measurement switch)
+        int built_order = 0;      // what the last build produced: the slot build falls back to row order (hot_build)
+        hipEvent_t ev[2] = {};    // around the last build's work on the stream (build_ms)
+        bool timed = false;
+        double build_ms = 0;
         unsigned long long builds = 0;
     } hix;
     Slot slot[2];
@@ -626,6 +632,11 @@ void hot_free(pie_ctx* c)
     dfree(h.rec); dfree(h.pos); dfree(h.cnt); dfree(h.d_off); dfree(h.delta_n);
     h.rec_cap = h.pos_cap = h.cnt_cap = 0;
     h.valid = false;
+    for (hipEvent_t& e : h.ev) {
+        if (e) (void)hipEventDestroy(e);
+        e = nullptr;
+    }
+    h.timed = false;
 }
 
 OrdMirror ord_mirror_of(const pie_ctx* c)
@@ -1028,8 +1039,93 @@ int build_keys(pie_ctx* c, long long row0, bool rebuild = false)
     return PIE_OK;
 }
 
+// Bits of a histogram slot: the padded histogram of hist_index has 32 * ceil(U / 32) counters.
+int hot_slot_bits(unsigned long long n_users)
+{
+    const unsigned long long pad = ((n_users + 31) >> 5) * 32;
+    int b = 0;
+    while ((1ull << b) < pad) ++b;
+    return b;
+}
+
+// The slot-ordered records of a build whose counts and offsets stand (h.cnt, h.n_main): keys, one stable radix sort over the
+// bits in use, gather.  The scratch (two key and two row arrays and the sort's own) is transient: allocated here, freed before
+// returning, never part of workspace_bytes.  -> false with nothing written: no scratch, or bin and slot do not fit 32 bits.
+static bool hot_fill_by_slot(pie_ctx* c, long long blocks, long long seg_len)
+{
+    pie_ctx::HotIndex& h = c->hix;
+    hipStream_t s = c->stream;
+    const int slot_bits = hot_slot_bits((unsigned long long)c->n_users);
+    if (slot_bits + 7 > 32 || h.n_main > 0x7FFFFFFFLL) return false;
+    if (h.n_main == 0) return true;
+    const size_t m = (size_t)h.n_main, arr = (m * 4 + 255) & ~(size_t)255;
+    size_t need = 0;
+    unsigned* kz = nullptr;
+    int* vz = nullptr;
+    if (rocprim::radix_sort_pairs(nullptr, need, kz, kz, vz, vz, m, 0u, (unsigned)(slot_bits + 7), s) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    char* scratch = nullptr;
+    if (hipMalloc(&scratch, 4 * arr + need + 256) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    unsigned* k_in = reinterpret_cast<unsigned*>(scratch);
+    unsigned* k_out = reinterpret_cast<unsigned*>(scratch + arr);
+    int* v_in = reinterpret_cast<int*>(scratch + 2 * arr);
+    int* v_out = reinterpret_cast<int*>(scratch + 3 * arr);
+    void* tmp = scratch + 4 * arr;
+    hipLaunchKernelGGL(k_hot_keys, dim3((unsigned)blocks), dim3(256), 0, s, c->d_fkey, c->d_pay, c->n, seg_len, h.cnt, c->n_users, slot_bits, k_in, v_in);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = rocprim::radix_sort_pairs(tmp, need, k_in, k_out, v_in, v_out, m, 0u, (unsigned)(slot_bits + 7), s);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_hot_gather, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, k_out, v_out, h.n_main, slot_bits, c->d_end, c->d_pay, h.rec, h.pos);
+        e = hipGetLastError();
+    }
+    const hipError_t e2 = hipStreamSynchronize(s); // the scratch goes only when nothing reads it any more
+    (void)hipFree(scratch);
+    if (e != hipSuccess || e2 != hipSuccess) { // pos[] may be half written: the caller's row-order scatter rewrites all of it
+        (void)hipGetLastError();
+        return false;
+    }
+    return true;
+}
+
+// k_hot_scan's work for the slot build: a device-wide exclusive scan of the (bin, segment) counts into transient scratch,
+// off[] from it, the prefix copied back over the counts.  -> the scratch, to be freed once the stream has run; nullptr with
+// nothing launched when it cannot be had (the caller runs k_hot_scan).
+static void* hot_scan_wide(pie_ctx* c, long long S)
+{
+    pie_ctx::HotIndex& h = c->hix;
+    hipStream_t s = c->stream;
+    const size_t total = (size_t)(128 * S), arr = (total * 4 + 255) & ~(size_t)255;
+    size_t need = 0;
+    unsigned* z = nullptr;
+    if (rocprim::exclusive_scan(nullptr, need, z, z, 0u, total, rocprim::plus<unsigned int>(), s) != hipSuccess) {
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    char* scratch = nullptr;
+    if (hipMalloc(&scratch, arr + need + 256) != hipSuccess) {
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    unsigned* out = reinterpret_cast<unsigned*>(scratch);
+    if (rocprim::exclusive_scan(scratch + arr, need, h.cnt, out, 0u, total, rocprim::plus<unsigned int>(), s) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipStreamSynchronize(s);
+        (void)hipFree(scratch);
+        return nullptr;
+    }
+    hipLaunchKernelGGL(k_hot_offsets, dim3(1), dim3(192), 0, s, out, h.cnt, S, h.d_off);
+    (void)hipMemcpyAsync(h.cnt, out, total * 4, hipMemcpyDeviceToDevice, s);
+    return scratch;
+}
+
 // The hot index of the current fine key (see pie_ctx::HotIndex), on the main stream with nothing in flight; waits for the
-// bin offsets.  Device memory it cannot get leaves the batches on the key stream.
+// bin offsets.  Device memory it cannot get leaves the batches on the key stream.  Inside a bin the records stand in slot
+// order (k_hot_keys) unless PIE_HOT_ORDER=row asks for row order, or the slot build cannot run: then in row order.
 int hot_build(pie_ctx* c)
 {
     pie_ctx::HotIndex& h = c->hix;
@@ -1052,21 +1148,33 @@ int hot_build(pie_ctx* c)
         h.enabled = false;
         return PIE_OK;
     }
+    for (hipEvent_t& e : h.ev)
+        if (!e) PIE_HIP(c, hipEventCreate(&e));
+    h.timed = false;
+    PIE_HIP(c, hipEventRecord(h.ev[0], s));
     PIE_HIP(c, hipMemsetAsync(h.pos, 0xFF, (size_t)c->cap_rows * sizeof(int), s));
     hipLaunchKernelGGL(k_hot_count, dim3((unsigned)blocks), dim3(256), 0, s, c->d_fkey, c->n, seg_len, h.cnt);
-    hipLaunchKernelGGL(k_hot_scan, dim3(1), dim3(1024), 0, s, h.cnt, S, h.d_off);
-    PIE_HIP(c, hipGetLastError());
-    PIE_HIP(c, hipMemcpyAsync(h.off, h.d_off, sizeof h.off, hipMemcpyDeviceToHost, s));
-    PIE_HIP(c, hipStreamSynchronize(s));
+    void* scan_scratch = h.order == 1 ? hot_scan_wide(c, S) : nullptr;
+    if (!scan_scratch) hipLaunchKernelGGL(k_hot_scan, dim3(1), dim3(1024), 0, s, h.cnt, S, h.d_off);
+    hipError_t e_scan = hipGetLastError();
+    if (e_scan == hipSuccess) e_scan = hipMemcpyAsync(h.off, h.d_off, sizeof h.off, hipMemcpyDeviceToHost, s);
+    if (e_scan == hipSuccess) e_scan = hipStreamSynchronize(s);
+    if (scan_scratch) (void)hipFree(scan_scratch);
+    PIE_HIP(c, e_scan);
     h.n_main = h.off[128];
     h.delta_cap = h.n_main / 8 > kHotDeltaMin ? h.n_main / 8 : kHotDeltaMin;
     if (!grow(h.rec, h.rec_cap, h.n_main + h.delta_cap, sizeof(HotRec))) {
         h.enabled = false;
         return PIE_OK;
     }
-    hipLaunchKernelGGL(k_hot_scatter, dim3((unsigned)blocks), dim3(256), 0, s, c->d_fkey, c->d_end, c->d_pay, c->n, seg_len, h.cnt, h.rec, h.pos);
-    PIE_HIP(c, hipGetLastError());
+    h.built_order = h.order == 1 && hot_fill_by_slot(c, blocks, seg_len) ? 1 : 0;
+    if (h.built_order == 0) {
+        hipLaunchKernelGGL(k_hot_scatter, dim3((unsigned)blocks), dim3(256), 0, s, c->d_fkey, c->d_end, c->d_pay, c->n, seg_len, h.cnt, h.rec, h.pos);
+        PIE_HIP(c, hipGetLastError());
+    }
     PIE_HIP(c, hipMemsetAsync(h.delta_n, 0, sizeof(unsigned), s));
+    PIE_HIP(c, hipEventRecord(h.ev[1], s));
+    h.timed = true;
     h.delta_bound = 0;
     h.valid = true;
     h.builds++;
@@ -2590,7 +2698,8 @@ int batch_begin(pie_ctx* c, const pie_query* qs, int n_q, int msg_kind, int* msg
             a.hot = c->hix.rec; a.hot_lo = c->hix.off[mk]; a.hot_main = c->hix.n_main;                                  \
             a.hot_delta_n = c->hix.delta_n; a.hot_delta_cap = (unsigned)c->hix.delta_cap;                               \
             const long long recs = a.hot_main - a.hot_lo + c->hix.delta_bound;                                          \
-            const long long want = (recs + 2 * kK1Threads - 1) / (2 * kK1Threads);                                     \
+            const long long per = (long long)c->hix.recs_per_thread * kK1Threads;                                      \
+            const long long want = (recs + per - 1) / per;                                                              \
             b.k1_blocks = (int)(want < 1 ? 1 : want < b.k1_blocks ? want : b.k1_blocks);                                \
         }                                                                                                               \
         fill_batch_tables(c, b, qs, nk, a.tab);                                                                         \
@@ -3406,6 +3515,8 @@ int pie_ctx_create(int device_id, pie_ctx** ctx_out)
     if (const char* v = getenv("PIE_EXPIRED_COPY_TOTAL")) c->expired_copy_total = atoi(v) != 0;
     if (const char* v = getenv("PIE_ASYNC_MUTATIONS")) c->async_mutations = atoi(v) != 0;
     if (const char* v = getenv("PIE_HOT_INDEX")) c->hix.enabled = atoi(v) != 0;
+    if (const char* v = getenv("PIE_HOT_RECS")) { const int r = atoi(v); if (r == 1 || r == 2 || r == 4) c->hix.recs_per_thread = r; }
+    if (const char* v = getenv("PIE_HOT_ORDER")) { if (!strcmp(v, "row")) c->hix.order = 0; else if (!strcmp(v, "slot")) c->hix.order = 1; }
     if (const char* v = getenv("PIE_BATCH_LANES")) { const int l = atoi(v); if (l >= 0 && l <= kLaneMax) c->lanes_want = l; }
     if (const char* v = getenv("PIE_ORDER_BLOCK")) { const int b = atoi(v); if (b == 256 || b == 512 || b == 1024) c->order_block = b; }
     if (const char* v = getenv("PIE_RUN_SHIFT")) { const int r = atoi(v); if (r >= 0 && r <= 3) { c->run_shift = r; c->run_shift_pinned = true; } }
@@ -4906,7 +5017,7 @@ int pie_table_info_get(pie_ctx* c, pie_table_info* out)
     if (!c || !out) return PIE_E_INVAL;
     // the struct grows at its end: a caller built against the form without the compaction fields gets the fields it knows
     const uint32_t caller_size = out->struct_size;
-    if (caller_size != sizeof(pie_table_info) && caller_size != offsetof(pie_table_info, compact_bytes))
+    if (caller_size != sizeof(pie_table_info) && caller_size != offsetof(pie_table_info, hot_build_ms) && caller_size != offsetof(pie_table_info, compact_bytes))
         return fail(c, PIE_E_INVAL, "pie_table_info.struct_size mismatch");
     pie_table_info full{};
     pie_table_info* const caller = out;
@@ -4953,12 +5064,58 @@ int pie_table_info_get(pie_ctx* c, pie_table_info* out)
     out->hot_rows = c->hix.valid ? (uint64_t)c->hix.n_main : 0u;
     out->hot_bytes = (uint64_t)c->hix.rec_cap * sizeof(HotRec) + (uint64_t)c->hix.pos_cap * 4 + (uint64_t)c->hix.cnt_cap * 4 + (c->hix.d_off ? 129 * 8 + 4 : 0);
     out->hot_builds = c->hix.builds;
+    if (c->hix.timed) { // the last build's device time, read once it has run
+        float ms = 0.f;
+        if (hipEventSynchronize(c->hix.ev[1]) == hipSuccess && hipEventElapsedTime(&ms, c->hix.ev[0], c->hix.ev[1]) == hipSuccess) c->hix.build_ms = ms;
+        else (void)hipGetLastError();
+        c->hix.timed = false;
+    }
+    out->hot_build_ms = c->hix.build_ms;
+    out->hot_order = (uint32_t)(c->hix.valid ? c->hix.built_order : c->hix.order);
+    out->hot_slot_bits = (uint32_t)hot_slot_bits((unsigned long long)c->n_users);
     out->compact_bytes = c->cmp_valid ? (uint64_t)(c->cmp_n_old > 0 ? c->cmp_n_old : 1) * 4 + (uint64_t)(c->cmp_n_kept > 0 ? c->cmp_n_kept : 1) * 4 : 0u;
     out->compactions = c->compactions;
     out->compact_count_ms = c->cmp_count_ms;
     out->compact_write_ms = c->cmp_write_ms;
     full.struct_size = caller_size;
     memcpy(caller, &full, caller_size);
+    return PIE_OK;
+}
+
+uint64_t pie_hot_order_key(uint32_t bin, int32_t user, uint32_t n_users)
+{
+    const unsigned long long t = ((unsigned long long)n_users + 31) >> 5, pad = t * 32;
+    const unsigned long long u = (unsigned long long)(uint32_t)user;
+    const unsigned long long slot = u < pad ? (u & 31) * t + (u >> 5) : 0; // hist_index (pie_kernels.h)
+    return ((uint64_t)bin << hot_slot_bits(n_users)) | slot;
+}
+
+uint32_t pie_hot_slot_bits(uint32_t n_users) { return (uint32_t)hot_slot_bits(n_users); }
+
+int pie_hot_layout(pie_ctx* c, int64_t* off, int64_t* n_main, int32_t* user, int32_t* row, int32_t* bin, size_t cap, int32_t* pos, size_t n_pos)
+{
+    if (!c) return PIE_E_INVAL;
+    if (!c->hix.valid) return fail(c, PIE_E_STATE, "there is no hot index");
+    PIE_HIP(c, hipSetDevice(c->device));
+    int rc = sync_all(c);
+    if (rc) return rc;
+    const pie_ctx::HotIndex& h = c->hix;
+    if (off) for (int k = 0; k <= 128; ++k) off[k] = h.off[k];
+    if (n_main) *n_main = h.n_main;
+    if (user || row || bin) {
+        if ((long long)cap < h.n_main) return fail(c, PIE_E_CAPACITY, "the hot index holds %lld main records, room for %zu", h.n_main, cap);
+        std::vector<HotRec> rec((size_t)h.n_main);
+        if (h.n_main) PIE_HIP(c, hipMemcpy(rec.data(), h.rec, rec.size() * sizeof(HotRec), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < rec.size(); ++i) {
+            if (user) user[i] = rec[i].user;
+            if (row) row[i] = rec[i].row;
+            if (bin) bin[i] = rec[i].bin;
+        }
+    }
+    if (pos) {
+        if ((long long)n_pos > c->n) return fail(c, PIE_E_INVAL, "asked for %zu rows, table has %lld", n_pos, c->n);
+        if (n_pos) PIE_HIP(c, hipMemcpy(pos, h.pos, n_pos * 4, hipMemcpyDeviceToHost));
+    }
     return PIE_OK;
 }
 
