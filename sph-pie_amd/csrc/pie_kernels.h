@@ -2420,6 +2420,35 @@ __device__ __forceinline__ int rank_in_row16(long long s, int i)
            rank16_step<11>(s, i) + rank16_step<12>(s, i) + rank16_step<13>(s, i) + rank16_step<14>(s, i) + rank16_step<15>(s, i);
 }
 
+// Transpose of N 32 x 32 bit matrices, each held one row per lane by each half of the wave (lane r of a half: row r; bit c:
+// column c): five stages, stage J swaps the off-diagonal J x J blocks of every 2J x 2J block between the lanes r and r ^ J (one
+// swizzle inside the half, no LDS memory).  Afterwards bit c of lane r is what bit r of lane c (of the same half) was.
+// Branch-free — a lane keeps the bits `keep` of its own word and takes the rest from its partner's word rotated by J towards
+// them (the bits a rotation wraps around fall on kept positions) — and stage by stage over all N matrices, so that the N
+// swizzles of a stage are in flight together.  Every lane of the wave must be active.
+template <int J, int N>
+__device__ __forceinline__ void transpose_stage_32(unsigned (&x)[N], int lane)
+{
+    constexpr unsigned m = J == 16 ? 0x0000FFFFu : J == 8 ? 0x00FF00FFu : J == 4 ? 0x0F0F0F0Fu : J == 2 ? 0x33333333u : 0x55555555u;
+    const bool upper = (lane & J) != 0;
+    const unsigned keep = upper ? ~m : m;
+    const unsigned rot = upper ? 32u - J : (unsigned)J;
+    unsigned o[N];
+#pragma unroll
+    for (int i = 0; i < N; ++i) o[i] = (unsigned)__builtin_amdgcn_ds_swizzle((int)x[i], (J << 10) | 0x1F); // lane ^ J: and 0x1F, or 0, xor J
+#pragma unroll
+    for (int i = 0; i < N; ++i) x[i] = (x[i] & keep) | (__builtin_rotateleft32(o[i], rot) & ~keep);
+}
+template <int N>
+__device__ __forceinline__ void transpose_bits_32(unsigned (&x)[N], int lane)
+{
+    transpose_stage_32<16>(x, lane);
+    transpose_stage_32<8>(x, lane);
+    transpose_stage_32<4>(x, lane);
+    transpose_stage_32<2>(x, lane);
+    transpose_stage_32<1>(x, lane);
+}
+
 // HI = the batch holds more than 32 queries (a second mask word per row)
 template <bool HI>
 __device__ __forceinline__ void union_tail_body(const UnionTailArgs& t, int gbid)
@@ -2437,7 +2466,15 @@ __device__ __forceinline__ void union_tail_body(const UnionTailArgs& t, int gbid
     __shared__ unsigned long long s_mt[kMaskTabWords];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int nblk = t.tiles, U = t.n_users, nq = t.n_q;
-    if ((int)threadIdx.x < kMaskTabWords) s_mt[threadIdx.x] = t.mtab[threadIdx.x];
+    ScanCtl* ctl = reinterpret_cast<ScanCtl*>(t.span + t.ctl_off);
+    Summary* sum = reinterpret_cast<Summary*>(t.span + t.summary_off);
+    unsigned int* mq_slots = reinterpret_cast<unsigned int*>(t.span + t.mq_off);
+    // The block's chain of dependent round trips is what this kernel costs, so everything is issued as early
+    // as its inputs allow: the ticket first — the table load is in flight beside it and lands in LDS before the barrier —
+    // then the counts, then the granule and the bucket loads.
+    unsigned long long mt_word = 0;
+    if ((int)threadIdx.x < kMaskTabWords) mt_word = t.mtab[threadIdx.x];
+    if (threadIdx.x == 0) tile_s = atomicAdd(&ctl->ticket, 1u);
     // a slot's mask code -> the row's query mask (lo: queries 0..31, hi: 32..63)
     auto expand = [&](int code, unsigned& lo, unsigned& hi) {
         if constexpr (HI) {
@@ -2450,15 +2487,7 @@ __device__ __forceinline__ void union_tail_body(const UnionTailArgs& t, int gbid
             hi = 0;
         }
     };
-    if (t.zero_span) {
-        const int4 z = make_int4(0, 0, 0, 0);
-        int4* zs = reinterpret_cast<int4*>(t.zero_span);
-        for (long long i = (long long)gbid * BLOCK + threadIdx.x; i < t.zero_total16; i += (long long)nblk * BLOCK) zs[i] = z;
-    }
-    ScanCtl* ctl = reinterpret_cast<ScanCtl*>(t.span + t.ctl_off);
-    Summary* sum = reinterpret_cast<Summary*>(t.span + t.summary_off);
-    unsigned int* mq_slots = reinterpret_cast<unsigned int*>(t.span + t.mq_off);
-    if (threadIdx.x == 0) tile_s = atomicAdd(&ctl->ticket, 1u);
+    if ((int)threadIdx.x < kMaskTabWords) s_mt[threadIdx.x] = mt_word;
     __syncthreads();
     const int tile = (int)tile_s;
     const int u = tile * BLOCK + (int)threadIdx.x;
@@ -2469,48 +2498,44 @@ __device__ __forceinline__ void union_tail_body(const UnionTailArgs& t, int gbid
     const int nn = n_raw < cap ? n_raw : cap;
     const long long slot0 = (long long)(in_u ? u : 0) << t.dshift;
     const BktRec* src = t.direct + slot0;
+    const bool mid = nn > 8;
 
-    // the user's union bucket: up to 8 rows ordered in this thread's registers; 9 .. 64 rows by the whole wave (below)
-    long long ks[8];
-    int ki[8];
-    unsigned km[8], kh[8];
+    // the bucket loads, issued as soon as the counts are known and consumed only after the granule is out: up to 8 rows of
+    // the thread's own bucket (ordered in its registers below), and — for the first FOUR buckets of 9 .. 16 rows in this
+    // wave — one record per lane: each such bucket takes a row of 16 lanes (see below)
+    BktRec rec[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-        BktRec r;
-        r.start = INT64_MAX;
-        r.idx = INT32_MAX;
-        r.pad = 0;
-        if (nn <= 8 && k < nn) r = src[k];
-        ks[k] = r.start;
-        ki[k] = r.idx;
-        expand(r.pad, km[k], kh[k]);
+        rec[k].start = INT64_MAX;
+        rec[k].idx = INT32_MAX;
+        rec[k].pad = 0;
+        if (nn <= 8 && k < nn) rec[k] = src[k];
     }
-    if (nn >= 2 && nn <= 8) {
+    const int row = lane >> 4, l = lane & 15;
+    unsigned long long todo16 = __ballot(mid && in_u && nn <= 16);
+    const bool any16 = todo16 != 0;
+    int mine0 = -1; // the lane that owns the bucket my row of 16 holds in the first group (-1: my row idles)
+    {
+        unsigned long long t2 = todo16;
 #pragma unroll
-        for (int k = 2; k <= 8; k <<= 1) {
-#pragma unroll
-            for (int j = k >> 1; j > 0; j >>= 1) {
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    const int l = i ^ j;
-                    if (l > i) {
-                        const bool up = (i & k) == 0;
-                        const bool lt = key_less(ks[l], ki[l], ks[i], ki[i]);
-                        const bool sw = up ? lt : !lt;
-                        const long long s0 = sw ? ks[l] : ks[i], s1 = sw ? ks[i] : ks[l];
-                        const int i0 = sw ? ki[l] : ki[i], i1 = sw ? ki[i] : ki[l];
-                        const unsigned m0 = sw ? km[l] : km[i], m1 = sw ? km[i] : km[l];
-                        ks[i] = s0; ks[l] = s1; ki[i] = i0; ki[l] = i1; km[i] = m0; km[l] = m1;
-                        if constexpr (HI) {
-                            const unsigned h0 = sw ? kh[l] : kh[i], h1 = sw ? kh[i] : kh[l];
-                            kh[i] = h0; kh[l] = h1;
-                        }
-                    }
-                }
-            }
+        for (int g = 0; g < 4; ++g) {
+            const int sl = t2 ? __ffsll((long long)t2) - 1 : -1;
+            if (g == row) mine0 = sl;
+            t2 &= t2 - 1;      // (0 & anything stays 0)
         }
+        todo16 = t2;
     }
-    // ONE prefix scan: the union counts
+    int nb0 = __shfl(nn, mine0 < 0 ? 0 : mine0, kWave); // (every lane takes part in every shuffle: a source lane must be active)
+    if (mine0 < 0) nb0 = 0;
+    const int ub0 = __shfl(u, mine0 < 0 ? 0 : mine0, kWave);
+    BktRec r16;
+    r16.start = INT64_MAX;
+    r16.idx = INT32_MAX;
+    r16.pad = 0;
+    if (l < nb0) r16 = (t.direct + ((long long)ub0 << t.dshift))[l];
+
+    // ONE prefix scan: the union counts.  The tile's granule needs nothing but the counts, so it is published here, before
+    // any bucket has arrived: a later tile's look-back waits for its predecessors' tickets and counts loads, not their buckets.
     const int incl = wave_incl_scan_i32(nn, lane);
     {
         unsigned mx = (unsigned)nn;
@@ -2529,59 +2554,45 @@ __device__ __forceinline__ void union_tail_body(const UnionTailArgs& t, int gbid
         __hip_atomic_store(&pub[tile], kTileReady | ((unsigned long long)mx << 31) | (unsigned long long)tot, __ATOMIC_RELAXED,
                            __HIP_MEMORY_SCOPE_AGENT);
     }
-    // while the predecessors' granules arrive: selected rows per query (what pie_scan_batch_finish reports).  Per lane the
-    // (<= 8) masks of its bucket are added up bit-sliced — planes b0..b3: bit q of plane i = bit i of "how many of my rows
-    // query q selected" — by a carry-save adder tree, no loop over queries; then lane q of the wave collects query q's total
-    // from four ballots per query.  No branch inside the loop: the chains of consecutive queries interleave (a first version
-    // with one ballot per bucket slot and query, each behind a wave-uniform branch, cost 20 of the kernel's 50 us at Q = 64).
-    const bool mid = nn > 8;
-    unsigned acc = 0;
-    {
-        auto fa = [](unsigned a, unsigned b, unsigned c, unsigned& carry) { const unsigned x = a ^ b; carry = (a & b) | (c & x); return x ^ c; };
-        unsigned pl[4], ph[4];
-        {
-            unsigned c1, c2, c3, c4, c5, c6;
-            const unsigned s1 = fa(km[0], km[1], km[2], c1), s2 = fa(km[3], km[4], km[5], c2);
-            const unsigned s3 = km[6] ^ km[7];
-            c3 = km[6] & km[7];
-            pl[0] = fa(s1, s2, s3, c4);
-            const unsigned tw = fa(c1, c2, c3, c5);
-            pl[1] = tw ^ c4;
-            c6 = tw & c4;
-            pl[2] = c5 ^ c6;
-            pl[3] = c5 & c6;
-        }
-        if constexpr (HI) {
-            unsigned c1, c2, c3, c4, c5, c6;
-            const unsigned s1 = fa(kh[0], kh[1], kh[2], c1), s2 = fa(kh[3], kh[4], kh[5], c2);
-            const unsigned s3 = kh[6] ^ kh[7];
-            c3 = kh[6] & kh[7];
-            ph[0] = fa(s1, s2, s3, c4);
-            const unsigned tw = fa(c1, c2, c3, c5);
-            ph[1] = tw ^ c4;
-            c6 = tw & c4;
-            ph[2] = c5 ^ c6;
-            ph[3] = c5 & c6;
-        } else {
-            ph[0] = ph[1] = ph[2] = ph[3] = 0;
-        }
-        const int nq_lo = nq < 32 ? nq : 32;
-#pragma unroll 4
-        for (int q = 0; q < nq_lo; ++q) {
-            const unsigned c = (unsigned)__popcll(__ballot((pl[0] >> q) & 1u)) + 2u * (unsigned)__popcll(__ballot((pl[1] >> q) & 1u)) +
-                               4u * (unsigned)__popcll(__ballot((pl[2] >> q) & 1u)) + 8u * (unsigned)__popcll(__ballot((pl[3] >> q) & 1u));
-            if (lane == q) acc = c;
-        }
-        if constexpr (HI) {
-#pragma unroll 4
-            for (int q = 32; q < nq; ++q) {
-                const unsigned c = (unsigned)__popcll(__ballot((ph[0] >> (q - 32)) & 1u)) + 2u * (unsigned)__popcll(__ballot((ph[1] >> (q - 32)) & 1u)) +
-                                   4u * (unsigned)__popcll(__ballot((ph[2] >> (q - 32)) & 1u)) + 8u * (unsigned)__popcll(__ballot((ph[3] >> (q - 32)) & 1u));
-                if (lane == q) acc = c;
+    // the user's union bucket: up to 8 rows ordered in this thread's registers; 9 .. 64 rows by the whole wave (below)
+    long long ks[8];
+    int ki[8];
+    unsigned km[8], kh[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        ks[k] = rec[k].start;
+        ki[k] = rec[k].idx;
+        expand(rec[k].pad, km[k], kh[k]);
+    }
+    if (nn >= 2 && nn <= 8) {
+#pragma unroll
+        for (int k = 2; k <= 8; k <<= 1) {
+#pragma unroll
+            for (int j = k >> 1; j > 0; j >>= 1) {
+#pragma unroll
+                for (int i = 0; i < 8; ++i) {
+                    const int l2 = i ^ j;
+                    if (l2 > i) {
+                        const bool up = (i & k) == 0;
+                        const bool lt = key_less(ks[l2], ki[l2], ks[i], ki[i]);
+                        const bool sw = up ? lt : !lt;
+                        const long long s0 = sw ? ks[l2] : ks[i], s1 = sw ? ks[i] : ks[l2];
+                        const int i0 = sw ? ki[l2] : ki[i], i1 = sw ? ki[i] : ki[l2];
+                        const unsigned m0 = sw ? km[l2] : km[i], m1 = sw ? km[i] : km[l2];
+                        ks[i] = s0; ks[l2] = s1; ki[i] = i0; ki[l2] = i1; km[i] = m0; km[l2] = m1;
+                        if constexpr (HI) {
+                            const unsigned h0 = sw ? kh[l2] : kh[i], h1 = sw ? kh[i] : kh[l2];
+                            kh[i] = h0; kh[l2] = h1;
+                        }
+                    }
+                }
             }
         }
     }
-    // base = sum of the granules of the tiles in front of this one
+    // base = sum of the granules of the tiles in front of this one (tiles with smaller tickets only: each of them has started).
+    // Behind the sort on purpose: by now every predecessor has long published (it needs only its ticket and its counts), so
+    // the loop does not spin.  Looking back right behind the publish, with the bucket loads still in flight, is one round
+    // trip shorter on paper and was 4 us per step SLOWER on one lane and 1 us per step slower on three.
     long long part = 0;
     unsigned pmax = 0;
     {
@@ -2637,10 +2648,73 @@ __device__ __forceinline__ void union_tail_body(const UnionTailArgs& t, int gbid
     }
     // buckets of 9 .. 16 rows, FOUR at a time: each takes a row of 16 lanes, lane l of the row holds record l and finds its place
     // by comparing against the other fifteen through DPP row rotations (a heterogeneous batch — several role masks — doubles the
-    // union: a fifth of the users land here, and one at a time by the whole wave they cost more than the rest of the kernel)
+    // union: a fifth of the users land here, and one at a time by the whole wave they cost more than the rest of the kernel).
+    // The first group's records were loaded up front with the small buckets; its masks (lo16 / hi16) join the totals below.
+    unsigned lo16 = 0, hi16 = 0;
+    if (any16) {
+        const long long rq = __shfl(run, mine0 < 0 ? 0 : mine0, kWave);
+        expand(r16.pad, lo16, hi16);
+        const int rank = rank_in_row16(r16.start, r16.idx);
+        if (l < nb0) {
+            const long long pos = rq + rank;
+            t.urows[pos] = r16.idx;
+            t.umlo[pos] = lo16;
+            if constexpr (HI) t.umhi[pos] = hi16;
+            if (t.msg && pos < t.msg_cap) {
+                msg_store(msg_rows + pos, r16.idx);
+                msg_store(msg_lo + pos, (int)lo16);
+                if constexpr (HI) msg_store(msg_hi + pos, (int)hi16);
+            }
+        }
+    }
+    // selected rows per query (what pie_scan_batch_finish reports), while the stores above are acknowledged.  Per lane the
+    // masks of its own bucket (<= 8; all zero for a larger bucket) and of the one first-group record it holds are added up
+    // bit-sliced — planes b0..b3: bit q of plane i = bit i of "how many of my rows query q selected", at most 9 — by a
+    // carry-save adder tree.  Each plane is then a 64 lanes x 32 queries bit matrix whose column sums are wanted: each half of
+    // the wave transposes its 32 x 32 block (five exchange stages), after which lane q of a half holds column q of that half
+    // and one popcount gives its sum; the two halves meet in one exchange across lane 32, queries 0..31 in lanes 0..31 and
+    // (HI) 32..63 in lanes 32..63.  No loop over queries (the loop of four ballots per query this replaces was ~10^3
+    // instructions per wave at Q = 64; a still earlier one with a branch per slot and query cost 20 of the kernel's 50 us).
+    unsigned acc = 0;
     {
-        unsigned long long todo = __ballot(mid && in_u && nn <= 16);
-        const int row = lane >> 4, l = lane & 15;
+        auto fa = [](unsigned a, unsigned b, unsigned c, unsigned& carry) { const unsigned x = a ^ b; carry = (a & b) | (c & x); return x ^ c; };
+        auto planes = [&](const unsigned (&m)[8], unsigned ninth, unsigned (&p)[4]) {
+            unsigned c1, c2, c3, c4, c5;
+            const unsigned s1 = fa(m[0], m[1], m[2], c1), s2 = fa(m[3], m[4], m[5], c2), s3 = fa(m[6], m[7], ninth, c3);
+            p[0] = fa(s1, s2, s3, c4);
+            const unsigned tw = fa(c1, c2, c3, c5);
+            p[1] = tw ^ c4;
+            const unsigned c6 = tw & c4;
+            p[2] = c5 ^ c6;
+            p[3] = c5 & c6;
+        };
+        auto colsum = [](const unsigned* p) {
+            return (unsigned)__popc(p[0]) + 2u * (unsigned)__popc(p[1]) + 4u * (unsigned)__popc(p[2]) + 8u * (unsigned)__popc(p[3]);
+        };
+        if constexpr (HI) {
+            unsigned pl[4], ph[4], x[8];
+            planes(km, lo16, pl);
+            planes(kh, hi16, ph);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) { x[i] = pl[i]; x[4 + i] = ph[i]; }
+            transpose_bits_32(x, lane);
+            // lane L: rows of my half's lanes that query (L & 31) selected, and the same for query 32 + (L & 31)
+            const unsigned cl = colsum(x), ch = colsum(x + 4);
+            const unsigned other = (unsigned)__shfl_xor((int)(lane < 32 ? ch : cl), 32, kWave);
+            acc = (lane < 32 ? cl : ch) + other;
+        } else {
+            unsigned x[4];
+            planes(km, lo16, x);
+            transpose_bits_32(x, lane);
+            const unsigned cl = colsum(x);
+            const unsigned other = (unsigned)__shfl_xor((int)cl, 32, kWave);
+            acc = lane < 32 ? cl + other : 0u;
+        }
+        if (lane >= nq) acc = 0;
+    }
+    // further groups of 9 .. 16 buckets (more than four in one wave): loaded here, their totals by one ballot per query
+    {
+        unsigned long long todo = todo16;
         while (todo) {
             // the row-th pending bucket of this round (rows without one idle)
             unsigned long long t2 = todo;
@@ -2757,6 +2831,13 @@ __device__ __forceinline__ void union_tail_body(const UnionTailArgs& t, int gbid
         __syncthreads();
         const long long m_all = s_total;
         for (int uu = U + threadIdx.x; uu <= t.u_pad + 1; uu += BLOCK) msg_store(t.msg + uu, (int)m_all);
+    }
+    // the span of the batch after the next: zeroed here, behind the result stores and acknowledged with them (in front of
+    // the ticket these stores stood between the block and its first barrier)
+    if (t.zero_span) {
+        const int4 z = make_int4(0, 0, 0, 0);
+        int4* zs = reinterpret_cast<int4*>(t.zero_span);
+        for (long long i = (long long)gbid * BLOCK + threadIdx.x; i < t.zero_total16; i += (long long)nblk * BLOCK) zs[i] = z;
     }
     // completion: the last block hands the summary and the per-query totals to the host (see offsets_body)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
