@@ -988,6 +988,142 @@ __global__ __launch_bounds__(256) void k_build_key(const long long* __restrict__
 constexpr int kKeyRowsPerLoad = 8 * kWave;      // 512 rows per wave per 16-byte load (2-byte keys)
 constexpr int kFineKeyRowsPerLoad = 16 * kWave; // 1024 rows (1-byte keys)
 
+// The interleave of the walk below (a wave takes runs of 1 << run_shift consecutive chunks), cut to what one round of UNROLL
+// loads can hold
+template <int UNROLL>
+__device__ __forceinline__ int clamp_run_shift(int run_shift)
+{
+    constexpr int kLogUnroll = UNROLL >= 8 ? 3 : UNROLL >= 4 ? 2 : UNROLL >= 2 ? 1 : 0;
+    return run_shift < kLogUnroll ? (run_shift < 0 ? 0 : run_shift) : kLogUnroll;
+}
+
+// The candidate walk of every pass over the key column (single keyed scan, batch, wide batch): finds the rows with
+// key >= min_key and hands them to the caller, who queues them.  The whole wave calls push(has, row, key) together, `has`
+// telling whether the calling lane brings a row; push returns whether any lane did (wave-uniform) and adds the rows it
+// took to `pushed`, the caller's count of candidates queued so far.  Returns the most candidates one chunk held.
+template <int UNROLL, bool NT, class KT, class Push>
+__device__ __forceinline__ int walk_key_stream(const KT* __restrict__ key, long long n, unsigned min_key, int run_shift, int bid, int n_scan_blocks,
+                                               int lane, int wave, const int& pushed, Push push)
+{
+    constexpr int kPerLane = 16 / (int)sizeof(KT); // rows per lane per 16-byte load
+    constexpr int kRowsPerLoad = kPerLane * kWave;
+    // SWAR: keys are < 2^15 (< 2^7), so with the top bit of each half (byte) forced on, subtracting min_key from all of
+    // them at once never borrows across, and the top bit of a half (byte) survives exactly when that key >= min_key
+    typedef unsigned u4_t __attribute__((ext_vector_type(4)));
+    constexpr unsigned kTop = sizeof(KT) == 2 ? 0x80008000u : 0x80808080u;
+    const unsigned nkr = sizeof(KT) == 2 ? (min_key | (min_key << 16)) : min_key * 0x01010101u;
+    // Rows are dealt to the waves of the whole launch in CHUNKS of one 16-byte load per lane (1024 / 512 rows), round robin:
+    // wave g of W takes chunks g, g + W, g + 2W, ...  In a session table the live rows are the recent ones, i.e. they sit
+    // together at the end of the table (and a login burst appends there): with one contiguous row range per block the few
+    // blocks at the end would evaluate nearly every candidate while the rest of the chip idles (measured: the table pass
+    // 4x slower once 10^5 freshly appended / touched rows are live).  Interleaved, a dense stretch of the table is spread
+    // over as many waves as it has chunks.  Every load is still one contiguous, aligned KiB per wave.
+    int chunk_max = 0, chunk_mark = 0;                        // wave-uniform
+    const long long n_chunks = n / kRowsPerLoad;              // full chunks; the ragged rest goes to one wave, row by row
+    const long long W = (long long)n_scan_blocks * kK1Waves;
+    const long long gw = (long long)bid * kK1Waves + wave;
+    for (long long cb = gw << run_shift; cb < n_chunks; cb += W * UNROLL) {
+        u4_t kv[UNROLL];
+#pragma unroll
+        for (int j = 0; j < UNROLL; ++j) {
+            const long long ch = cb + (((long long)(j >> run_shift) * W) << run_shift) + (j & ((1 << run_shift) - 1));
+            kv[j] = (u4_t){0u, 0u, 0u, 0u};                    // key 0 = below every query's key: no candidates
+            if (ch < n_chunks) kv[j] = stream_load<NT>(reinterpret_cast<const u4_t*>(key + ch * kRowsPerLoad + kPerLane * lane));
+        }
+#pragma unroll
+        for (int j = 0; j < UNROLL; ++j) {
+            const long long ch = cb + (((long long)(j >> run_shift) * W) << run_shift) + (j & ((1 << run_shift) - 1));
+            if (ch >= n_chunks) continue;                      // wave-uniform
+            chunk_max = max(chunk_max, pushed - chunk_mark);   // candidates of the chunk before this one
+            chunk_mark = pushed;
+            const int r0 = (int)(ch * kRowsPerLoad + kPerLane * lane);
+            const unsigned g0 = ((kv[j].x | kTop) - nkr) & kTop, g1 = ((kv[j].y | kTop) - nkr) & kTop;
+            const unsigned g2 = ((kv[j].z | kTop) - nkr) & kTop, g3 = ((kv[j].w | kTop) - nkr) & kTop;
+            // every lane peels its flagged rows off one by one, until no lane of the wave has one left
+            if constexpr (sizeof(KT) == 2) {
+                // rows 0..3 keep their flags at bits 15/31/47/63, rows 4..7 move to bits 7/23/39/55
+                unsigned long long m = ((unsigned long long)g0 | ((unsigned long long)g1 << 32)) |
+                                       (((unsigned long long)g2 | ((unsigned long long)g3 << 32)) >> 8);
+                for (;;) {
+                    const bool has = m != 0;
+                    const int pbit = __ffsll((long long)m) - 1;         // meaningless when !has
+                    const int q = (pbit >> 4) + ((pbit & 8) ? 0 : 4);   // row within the lane's eight
+                    const unsigned w = q < 4 ? (q < 2 ? kv[j].x : kv[j].y) : (q < 6 ? kv[j].z : kv[j].w);
+                    const unsigned kq = (w >> ((q & 1) * 16)) & 0xFFFFu;
+                    if (!push(has, r0 + q, kq)) break;
+                    m &= m - 1;
+                }
+            } else {
+                // byte b of word w is row 4w + b; its flag moves to bit 8b + w
+                unsigned m = (g0 >> 7) | (g1 >> 6) | (g2 >> 5) | (g3 >> 4);
+                for (;;) {
+                    const bool has = m != 0;
+                    const int pbit = __ffs((int)m) - 1;
+                    const int w = pbit & 7, b = pbit >> 3;
+                    const unsigned word = w < 2 ? (w == 0 ? kv[j].x : kv[j].y) : (w == 2 ? kv[j].z : kv[j].w);
+                    const unsigned kq = (word >> (8 * b)) & 0xFFu;
+                    if (!push(has, r0 + 4 * w + b, kq)) break;
+                    m &= m - 1;
+                }
+            }
+        }
+    }
+    if (gw == (n_chunks >> run_shift) % W) { // the wave whose turn the next chunk would be: the table's last, partial chunk
+        for (long long r0 = n_chunks * kRowsPerLoad; r0 < n; r0 += kWave) {
+            const long long r = r0 + lane;
+            const unsigned kq = r < n ? key[r] : 0u;
+            push(r < n && kq >= min_key, (int)r, kq);
+        }
+    }
+    return max(chunk_max, pushed - chunk_mark);
+}
+
+// The candidates of one wave in the batched and the wide pass: a ring of (row, key) pairs in LDS.  push() queues the rows
+// the walk finds and, whenever a full wave of them waits, has the caller's drain(cnt) evaluate the cnt oldest (lane l: the
+// pair at slot(l)) before it drops them.
+struct CandRing {
+    int* row;
+    int* key;
+    int head, fill, pushed; // wave-uniform; pushed: candidates queued so far
+
+    __device__ __forceinline__ static CandRing of_wave(int wave)
+    {
+        __shared__ int ring_row[kK1Waves][kLiveRing];
+        __shared__ int ring_key[kK1Waves][kLiveRing];
+        return CandRing{ring_row[wave], ring_key[wave], 0, 0, 0};
+    }
+    __device__ __forceinline__ int slot(int lane) const { return (head + lane) & (kLiveRing - 1); }
+    template <class Drain>
+    __device__ __forceinline__ void take(int cnt, Drain drain)
+    {
+        drain(cnt);
+        head = (head + cnt) & (kLiveRing - 1);
+        fill -= cnt;
+    }
+    template <class Drain>
+    __device__ __forceinline__ bool push(bool cand, int r, unsigned k, Drain drain)
+    {
+        const unsigned long long b = __ballot(cand);
+        if (b == 0) return false;
+        if (cand) {
+            const int s = (head + fill + prefix_in_ballot(b)) & (kLiveRing - 1);
+            row[s] = r;
+            key[s] = (int)k;
+        }
+        fill += __popcll(b);
+        pushed += __popcll(b);
+        __builtin_amdgcn_wave_barrier();
+        if (fill >= kWave) take(kWave, drain);
+        __builtin_amdgcn_wave_barrier();
+        return true;
+    }
+    template <class Drain>
+    __device__ __forceinline__ void flush(Drain drain) // what is left at the end of the walk
+    {
+        if (fill > 0) take(fill, drain);
+    }
+};
+
 // PIPE: the evaluation of a batch of 64 candidates is split into three steps that run one batch apart — (A) take the batch
 // off the ring and issue its gathers, (B) one batch later, evaluate the predicate and issue the histogram atomics,
 // (C) one batch later again, take the returned ranks and emit — so neither the gather's nor the atomic's round trip
@@ -997,7 +1133,7 @@ __device__ __forceinline__ void scan_keyed_body(
     const PayRec* __restrict__ pay, const long long* __restrict__ end, const KT* __restrict__ key, long long n,
     long long rows_per_block, long long now, unsigned now_key, long long cutoff, unsigned long long mask, int n_users, int* __restrict__ counts,
     SelRec* __restrict__ sel, int* __restrict__ sel_rank, int* __restrict__ blk_count, Summary* __restrict__ summary,
-    DirectSlots direct, const HotSet& hot, int* __restrict__ blk_hot_base, int bid, int n_scan_blocks, int run_shift_arg)
+    DirectSlots direct, const HotSet& hot, int* __restrict__ blk_hot_base, int bid, int n_scan_blocks, int run_shift)
 {
     __shared__ SelRec stage[kK1Waves][kStage];
     __shared__ int stage_rank[kK1Waves][kStage];
@@ -1008,11 +1144,7 @@ __device__ __forceinline__ void scan_keyed_body(
     __shared__ int blk_cand;
     __shared__ int blk_chunk_max;
     __shared__ int blk_hot_cnt[kHotMax];
-    constexpr int kPerLane = 16 / (int)sizeof(KT); // rows per lane per 16-byte load
-    constexpr int kLogUnroll = UNROLL >= 8 ? 3 : UNROLL >= 4 ? 2 : UNROLL >= 2 ? 1 : 0;
-    const int run_shift = run_shift_arg < kLogUnroll ? (run_shift_arg < 0 ? 0 : run_shift_arg) : kLogUnroll;
-    int pushed = 0, chunk_max = 0; // wave-uniform: candidates queued so far; most candidates seen in one chunk
-    constexpr int kRowsPerLoad = kPerLane * kWave;
+    int pushed = 0; // wave-uniform: candidates queued so far
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = threadIdx.x >> 6;
     if (threadIdx.x == 0) { blk_cursor = 0; blk_live = 0; blk_amb = 0; blk_cand = 0; blk_chunk_max = 0; }
@@ -1127,7 +1259,7 @@ __device__ __forceinline__ void scan_keyed_body(
             step_c();
         }
     };
-    auto push = [&](bool cand, int entry) {
+    auto push_entry = [&](bool cand, int entry) {
         const unsigned long long b = __ballot(cand);
         if (b == 0) return false;
         if (cand) lring[(lhead + lfill + prefix_in_ballot(b)) & (kLiveRing - 1)] = entry;
@@ -1139,75 +1271,8 @@ __device__ __forceinline__ void scan_keyed_body(
         return true;
     };
 
-    // SWAR: keys are < 2^15 (< 2^7), so with the top bit of each half (byte) forced on, subtracting key(now) from all of
-    // them at once never borrows across, and the top bit of a half (byte) survives exactly when that key >= key(now)
-    typedef unsigned u4_t __attribute__((ext_vector_type(4)));
-    constexpr unsigned kTop = sizeof(KT) == 2 ? 0x80008000u : 0x80808080u;
-    const unsigned nkr = sizeof(KT) == 2 ? (now_key | (now_key << 16)) : now_key * 0x01010101u;
-    // Rows are dealt to the waves of the whole launch in CHUNKS of one 16-byte load per lane (1024 / 512 rows), round robin:
-    // wave g of W takes chunks g, g + W, g + 2W, ...  In a session table the live rows are the recent ones, i.e. they sit
-    // together at the end of the table (and a login burst appends there): with one contiguous row range per block the few
-    // blocks at the end would evaluate nearly every candidate while the rest of the chip idles (measured: the table pass
-    // 4x slower once 10^5 freshly appended / touched rows are live).  Interleaved, a dense stretch of the table is spread
-    // over as many waves as it has chunks.  Every load is still one contiguous, aligned KiB per wave.
-    int chunk_mark = 0;
-    const long long n_chunks = n / kRowsPerLoad;              // full chunks; the ragged rest goes to one wave, row by row
-    const long long W = (long long)n_scan_blocks * kK1Waves;
-    const long long gw = (long long)bid * kK1Waves + wave;
-    for (long long cb = gw << run_shift; cb < n_chunks; cb += W * UNROLL) {
-        u4_t kv[UNROLL];
-#pragma unroll
-        for (int j = 0; j < UNROLL; ++j) {
-            const long long ch = cb + (((long long)(j >> run_shift) * W) << run_shift) + (j & ((1 << run_shift) - 1));
-            kv[j] = (u4_t){0u, 0u, 0u, 0u};                    // key 0 = below every query's key: no candidates
-            if (ch < n_chunks) kv[j] = stream_load<NT>(reinterpret_cast<const u4_t*>(key + ch * kRowsPerLoad + kPerLane * lane));
-        }
-#pragma unroll
-        for (int j = 0; j < UNROLL; ++j) {
-            const long long ch = cb + (((long long)(j >> run_shift) * W) << run_shift) + (j & ((1 << run_shift) - 1));
-            if (ch >= n_chunks) continue;                      // wave-uniform
-            chunk_max = max(chunk_max, pushed - chunk_mark);   // candidates of the chunk before this one
-            chunk_mark = pushed;
-            const int r0 = (int)(ch * kRowsPerLoad + kPerLane * lane);
-            const unsigned g0 = ((kv[j].x | kTop) - nkr) & kTop, g1 = ((kv[j].y | kTop) - nkr) & kTop;
-            const unsigned g2 = ((kv[j].z | kTop) - nkr) & kTop, g3 = ((kv[j].w | kTop) - nkr) & kTop;
-            if constexpr (sizeof(KT) == 2) {
-                // rows 0..3 keep their flags at bits 15/31/47/63, rows 4..7 move to bits 7/23/39/55
-                unsigned long long m = ((unsigned long long)g0 | ((unsigned long long)g1 << 32)) |
-                                       (((unsigned long long)g2 | ((unsigned long long)g3 << 32)) >> 8);
-                for (;;) {
-                    const bool has = m != 0;
-                    const int pbit = __ffsll((long long)m) - 1;         // meaningless when !has
-                    const int q = (pbit >> 4) + ((pbit & 8) ? 0 : 4);   // row within the lane's eight
-                    const unsigned w = q < 4 ? (q < 2 ? kv[j].x : kv[j].y) : (q < 6 ? kv[j].z : kv[j].w);
-                    const unsigned kq = (w >> ((q & 1) * 16)) & 0xFFFFu;
-                    const int entry = (r0 + q) | (kq == now_key ? (int)0x80000000 : 0);
-                    if (!push(has, entry)) break;
-                    m &= m - 1;
-                }
-            } else {
-                // byte b of word w is row 4w + b; its flag moves to bit 8b + w
-                unsigned m = (g0 >> 7) | (g1 >> 6) | (g2 >> 5) | (g3 >> 4);
-                for (;;) {
-                    const bool has = m != 0;
-                    const int pbit = __ffs((int)m) - 1;
-                    const int w = pbit & 7, b = pbit >> 3;
-                    const unsigned word = w < 2 ? (w == 0 ? kv[j].x : kv[j].y) : (w == 2 ? kv[j].z : kv[j].w);
-                    const unsigned kq = (word >> (8 * b)) & 0xFFu;
-                    const int entry = (r0 + 4 * w + b) | (kq == now_key ? (int)0x80000000 : 0);
-                    if (!push(has, entry)) break;
-                    m &= m - 1;
-                }
-            }
-        }
-    }
-    if (gw == (n_chunks >> run_shift) % W) { // the wave whose turn the next chunk would be: the table's last, partial chunk
-        for (long long r0 = n_chunks * kRowsPerLoad; r0 < n; r0 += kWave) {
-            const long long r = r0 + lane;
-            const unsigned kq = r < n ? key[r] : 0u;
-            push(r < n && kq >= now_key, (int)r | (kq == now_key ? (int)0x80000000 : 0));
-        }
-    }
+    auto push = [&](bool cand, int row, unsigned key) { return push_entry(cand, row | (key == now_key ? (int)0x80000000 : 0)); };
+    const int chunk_max = walk_key_stream<UNROLL, NT>(key, n, now_key, clamp_run_shift<UNROLL>(run_shift), bid, n_scan_blocks, lane, wave, pushed, push);
     if (lfill > 0) drain(lfill);
     if constexpr (PIPE) { // run the last batches through the remaining steps
         step_c();
@@ -1218,7 +1283,6 @@ __device__ __forceinline__ void scan_keyed_body(
     if (lane == 0 && nlive) atomicAdd(&blk_live, nlive);
     if (lane == 0 && namb) atomicAdd(&blk_amb, namb);
     if (lane == 0 && ncand) atomicAdd(&blk_cand, ncand);
-    chunk_max = max(chunk_max, pushed - chunk_mark);
     if (lane == 0 && chunk_max) atomicMax(&blk_chunk_max, chunk_max);
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -2176,16 +2240,9 @@ __device__ __forceinline__ int rank_in_64(const T* tab, T x)
 template <int UNROLL, bool NT, class KT>
 __device__ __forceinline__ void scan_batch_body(const BatchScanArgs<KT>& a, int bid, int n_scan_blocks)
 {
-    __shared__ int ring_row[kK1Waves][kLiveRing];
-    __shared__ int ring_key[kK1Waves][kLiveRing];
     __shared__ int blk_cand;
     __shared__ int blk_chunk_max;
     __shared__ BatchTables tab;
-    constexpr int kLogUnroll = UNROLL >= 8 ? 3 : UNROLL >= 4 ? 2 : UNROLL >= 2 ? 1 : 0;
-    const int run_shift = a.run_shift < kLogUnroll ? (a.run_shift < 0 ? 0 : a.run_shift) : kLogUnroll;
-    int pushed = 0, chunk_max = 0, chunk_mark = 0;
-    constexpr int kPerLane = 16 / (int)sizeof(KT);
-    constexpr int kRowsPerLoad = kPerLane * kWave;
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = threadIdx.x >> 6;
     if (threadIdx.x == 0) { blk_cand = 0; blk_chunk_max = 0; }
@@ -2197,9 +2254,8 @@ __device__ __forceinline__ void scan_batch_body(const BatchScanArgs<KT>& a, int 
     __syncthreads();
     if (bid == 0) // the batch's mask tables for its tail (a later launch)
         for (int i = threadIdx.x; i < kMaskTabWords; i += kK1Threads) a.mtab[i] = reinterpret_cast<const unsigned long long*>(reinterpret_cast<const char*>(&tab) + offsetof(BatchTables, live))[i];
-    int* rrow = ring_row[wave];
-    int* rkey = ring_key[wave];
-    int lhead = 0, lfill = 0, ncand = 0; // wave-uniform
+    CandRing ring = CandRing::of_wave(wave);
+    int ncand = 0, chunk_max = 0; // wave-uniform
     const int cap = 1 << a.dshift;
 
     // the Q predicates of one candidate per lane, `r` = the queries whose `now` lies below the row's `end` (a prefix of the
@@ -2231,9 +2287,9 @@ __device__ __forceinline__ void scan_batch_body(const BatchScanArgs<KT>& a, int 
         PayRec pr;
         pr.start = 0; pr.user = 0; pr.disc = -1;
         if (valid) {
-            const int slot = (lhead + lane) & (kLiveRing - 1);
-            row = rrow[slot];
-            key = (unsigned)rkey[slot];
+            const int slot = ring.slot(lane);
+            row = ring.row[slot];
+            key = (unsigned)ring.key[slot];
             pr = a.pay[row]; // ONE gather per candidate, shared by all queries
         }
         // liveness: the queries whose key(now) lies below the row's key form a prefix of the sorted order; a row whose key
@@ -2243,24 +2299,8 @@ __device__ __forceinline__ void scan_batch_body(const BatchScanArgs<KT>& a, int 
         if (amb) r = rank_in_64<true>(tab.now, a.end[row]);
         emit(valid, row, pr, r);
         ncand += cnt;
-        lhead = (lhead + cnt) & (kLiveRing - 1);
-        lfill -= cnt;
     };
-    auto push = [&](bool cand, int row, unsigned key) {
-        const unsigned long long b = __ballot(cand);
-        if (b == 0) return false;
-        if (cand) {
-            const int slot = (lhead + lfill + prefix_in_ballot(b)) & (kLiveRing - 1);
-            rrow[slot] = row;
-            rkey[slot] = (int)key;
-        }
-        lfill += __popcll(b);
-        pushed += __popcll(b);
-        __builtin_amdgcn_wave_barrier();
-        if (lfill >= kWave) drain(kWave);
-        __builtin_amdgcn_wave_barrier();
-        return true;
-    };
+    auto push = [&](bool cand, int row, unsigned key) { return ring.push(cand, row, key, drain); };
 
     if (a.hot) {
         // the hot index (HotRec): one record per lane — the suffix of the batch's smallest key, then the whole delta — ranked
@@ -2282,69 +2322,11 @@ __device__ __forceinline__ void scan_batch_body(const BatchScanArgs<KT>& a, int 
             ncand += n_rec - g < kWave ? (int)(n_rec - g) : kWave;
         }
     } else {
-        // SWAR candidate test against the batch's smallest key(now) (see scan_keyed_body)
-        typedef unsigned u4_t __attribute__((ext_vector_type(4)));
-        constexpr unsigned kTop = sizeof(KT) == 2 ? 0x80008000u : 0x80808080u;
-        const unsigned mk = a.min_key;
-        const unsigned nkr = sizeof(KT) == 2 ? (mk | (mk << 16)) : mk * 0x01010101u;
-        // rows dealt to the launch's waves in chunks of one load per lane, round robin (see scan_keyed_body)
-        const long long n_chunks = a.n / kRowsPerLoad;
-        const long long W = (long long)n_scan_blocks * kK1Waves;
-        const long long gw = (long long)bid * kK1Waves + wave;
-        for (long long cb = gw << run_shift; cb < n_chunks; cb += W * UNROLL) {
-            u4_t kv[UNROLL];
-    #pragma unroll
-            for (int j = 0; j < UNROLL; ++j) {
-                const long long ch = cb + (((long long)(j >> run_shift) * W) << run_shift) + (j & ((1 << run_shift) - 1));
-                kv[j] = (u4_t){0u, 0u, 0u, 0u};
-                if (ch < n_chunks) kv[j] = stream_load<NT>(reinterpret_cast<const u4_t*>(a.key + ch * kRowsPerLoad + kPerLane * lane));
-            }
-    #pragma unroll
-            for (int j = 0; j < UNROLL; ++j) {
-                const long long ch = cb + (((long long)(j >> run_shift) * W) << run_shift) + (j & ((1 << run_shift) - 1));
-                if (ch >= n_chunks) continue;
-                chunk_max = max(chunk_max, pushed - chunk_mark);
-                chunk_mark = pushed;
-                const int r0 = (int)(ch * kRowsPerLoad + kPerLane * lane);
-                const unsigned g0 = ((kv[j].x | kTop) - nkr) & kTop, g1 = ((kv[j].y | kTop) - nkr) & kTop;
-                const unsigned g2 = ((kv[j].z | kTop) - nkr) & kTop, g3 = ((kv[j].w | kTop) - nkr) & kTop;
-                if constexpr (sizeof(KT) == 2) {
-                    unsigned long long m = ((unsigned long long)g0 | ((unsigned long long)g1 << 32)) |
-                                           (((unsigned long long)g2 | ((unsigned long long)g3 << 32)) >> 8);
-                    for (;;) {
-                        const bool has = m != 0;
-                        const int pbit = __ffsll((long long)m) - 1;
-                        const int q = (pbit >> 4) + ((pbit & 8) ? 0 : 4);
-                        const unsigned w = q < 4 ? (q < 2 ? kv[j].x : kv[j].y) : (q < 6 ? kv[j].z : kv[j].w);
-                        const unsigned kq = (w >> ((q & 1) * 16)) & 0xFFFFu;
-                        if (!push(has, r0 + q, kq)) break;
-                        m &= m - 1;
-                    }
-                } else {
-                    unsigned m = (g0 >> 7) | (g1 >> 6) | (g2 >> 5) | (g3 >> 4);
-                    for (;;) {
-                        const bool has = m != 0;
-                        const int pbit = __ffs((int)m) - 1;
-                        const int w = pbit & 7, b = pbit >> 3;
-                        const unsigned word = w < 2 ? (w == 0 ? kv[j].x : kv[j].y) : (w == 2 ? kv[j].z : kv[j].w);
-                        const unsigned kq = (word >> (8 * b)) & 0xFFu;
-                        if (!push(has, r0 + 4 * w + b, kq)) break;
-                        m &= m - 1;
-                    }
-                }
-            }
-        }
-        if (gw == (n_chunks >> run_shift) % W) {
-            for (long long r0 = n_chunks * kRowsPerLoad; r0 < a.n; r0 += kWave) {
-                const long long r = r0 + lane;
-                const unsigned kq = r < a.n ? a.key[r] : 0u;
-                push(r < a.n && kq >= mk, (int)r, kq);
-            }
-        }
+        chunk_max = walk_key_stream<UNROLL, NT>(a.key, a.n, a.min_key, clamp_run_shift<UNROLL>(a.run_shift), bid, n_scan_blocks, lane, wave, ring.pushed,
+                                                push);
     }
-    if (lfill > 0) drain(lfill);
+    ring.flush(drain);
     if (lane == 0 && ncand) atomicAdd(&blk_cand, ncand);
-    chunk_max = max(chunk_max, pushed - chunk_mark);
     if (lane == 0 && chunk_max) atomicMax(&blk_chunk_max, chunk_max);
     __syncthreads();
     if (threadIdx.x == 0) add_row_stats(a.summary, 0, 0, bid, blk_cand, blk_chunk_max);
@@ -3134,17 +3116,10 @@ __device__ __forceinline__ long long readlane_i64(long long v, int j)
 template <int UNROLL, bool NT, class KT>
 __device__ __forceinline__ void scan_wide_body(const WideScanArgs<KT>& a, int bid, int n_scan_blocks)
 {
-    __shared__ int ring_row[kK1Waves][kLiveRing];
-    __shared__ int ring_key[kK1Waves][kLiveRing];
     __shared__ alignas(16) unsigned char s_qm[kK1Waves][kWave][kWave]; // per wave: candidate j's query mask, byte l from lane l
     __shared__ unsigned s_mq[kWideMax];
     __shared__ int blk_cand;
     __shared__ int blk_chunk_max;
-    constexpr int kLogUnroll = UNROLL >= 8 ? 3 : UNROLL >= 4 ? 2 : UNROLL >= 2 ? 1 : 0;
-    const int run_shift = a.run_shift < kLogUnroll ? (a.run_shift < 0 ? 0 : a.run_shift) : kLogUnroll;
-    int pushed = 0, chunk_max = 0, chunk_mark = 0;
-    constexpr int kPerLane = 16 / (int)sizeof(KT);
-    constexpr int kRowsPerLoad = kPerLane * kWave;
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = threadIdx.x >> 6;
     if (threadIdx.x == 0) { blk_cand = 0; blk_chunk_max = 0; }
@@ -3158,10 +3133,9 @@ __device__ __forceinline__ void scan_wide_body(const WideScanArgs<KT>& a, int bi
         qnow[k] = w.now; qcut[k] = w.cutoff; qdm[k] = w.mask; qnk[k] = w.nk; qcnt[k] = 0;
     }
     __syncthreads();
-    int* rrow = ring_row[wave];
-    int* rkey = ring_key[wave];
+    CandRing ring = CandRing::of_wave(wave);
     unsigned char* qm = &s_qm[wave][0][0];
-    int lhead = 0, lfill = 0, ncand = 0; // wave-uniform
+    int ncand = 0; // wave-uniform
     const int cap = 1 << a.dshift;
 
     // evaluate `cnt` queued candidates (cnt <= 64) against every query: candidate j in turn, each lane for its eight queries
@@ -3172,9 +3146,9 @@ __device__ __forceinline__ void scan_wide_body(const WideScanArgs<KT>& a, int bi
         PayRec pr;
         pr.start = 0; pr.user = 0; pr.disc = -1;
         if (valid) {
-            const int slot = (lhead + lane) & (kLiveRing - 1);
-            row = rrow[slot];
-            key = (unsigned)rkey[slot];
+            const int slot = ring.slot(lane);
+            row = ring.row[slot];
+            key = (unsigned)ring.key[slot];
             pr = a.pay[row]; // ONE gather per candidate, shared by all queries
         }
         bool sel = false;
@@ -3228,86 +3202,13 @@ __device__ __forceinline__ void scan_wide_body(const WideScanArgs<KT>& a, int bi
         }
         __builtin_amdgcn_wave_barrier();
         ncand += cnt;
-        lhead = (lhead + cnt) & (kLiveRing - 1);
-        lfill -= cnt;
     };
-    auto push = [&](bool cand, int row, unsigned key) {
-        const unsigned long long b = __ballot(cand);
-        if (b == 0) return false;
-        if (cand) {
-            const int slot = (lhead + lfill + prefix_in_ballot(b)) & (kLiveRing - 1);
-            rrow[slot] = row;
-            rkey[slot] = (int)key;
-        }
-        lfill += __popcll(b);
-        pushed += __popcll(b);
-        __builtin_amdgcn_wave_barrier();
-        if (lfill >= kWave) drain(kWave);
-        __builtin_amdgcn_wave_barrier();
-        return true;
-    };
+    auto push = [&](bool cand, int row, unsigned key) { return ring.push(cand, row, key, drain); };
 
-    // the candidate stream of scan_batch_body: SWAR test against the smallest key(now), chunks dealt round robin
-    typedef unsigned u4_t __attribute__((ext_vector_type(4)));
-    constexpr unsigned kTop = sizeof(KT) == 2 ? 0x80008000u : 0x80808080u;
-    const unsigned mk = a.min_key;
-    const unsigned nkr = sizeof(KT) == 2 ? (mk | (mk << 16)) : mk * 0x01010101u;
-    const long long n_chunks = a.n / kRowsPerLoad;
-    const long long W = (long long)n_scan_blocks * kK1Waves;
-    const long long gw = (long long)bid * kK1Waves + wave;
-    for (long long cb = gw << run_shift; cb < n_chunks; cb += W * UNROLL) {
-        u4_t kv[UNROLL];
-#pragma unroll
-        for (int j = 0; j < UNROLL; ++j) {
-            const long long ch = cb + (((long long)(j >> run_shift) * W) << run_shift) + (j & ((1 << run_shift) - 1));
-            kv[j] = (u4_t){0u, 0u, 0u, 0u};
-            if (ch < n_chunks) kv[j] = stream_load<NT>(reinterpret_cast<const u4_t*>(a.key + ch * kRowsPerLoad + kPerLane * lane));
-        }
-#pragma unroll
-        for (int j = 0; j < UNROLL; ++j) {
-            const long long ch = cb + (((long long)(j >> run_shift) * W) << run_shift) + (j & ((1 << run_shift) - 1));
-            if (ch >= n_chunks) continue;
-            chunk_max = max(chunk_max, pushed - chunk_mark);
-            chunk_mark = pushed;
-            const int r0 = (int)(ch * kRowsPerLoad + kPerLane * lane);
-            const unsigned g0 = ((kv[j].x | kTop) - nkr) & kTop, g1 = ((kv[j].y | kTop) - nkr) & kTop;
-            const unsigned g2 = ((kv[j].z | kTop) - nkr) & kTop, g3 = ((kv[j].w | kTop) - nkr) & kTop;
-            if constexpr (sizeof(KT) == 2) {
-                unsigned long long m = ((unsigned long long)g0 | ((unsigned long long)g1 << 32)) |
-                                       (((unsigned long long)g2 | ((unsigned long long)g3 << 32)) >> 8);
-                for (;;) {
-                    const bool has = m != 0;
-                    const int pbit = __ffsll((long long)m) - 1;
-                    const int q = (pbit >> 4) + ((pbit & 8) ? 0 : 4);
-                    const unsigned w = q < 4 ? (q < 2 ? kv[j].x : kv[j].y) : (q < 6 ? kv[j].z : kv[j].w);
-                    const unsigned kq = (w >> ((q & 1) * 16)) & 0xFFFFu;
-                    if (!push(has, r0 + q, kq)) break;
-                    m &= m - 1;
-                }
-            } else {
-                unsigned m = (g0 >> 7) | (g1 >> 6) | (g2 >> 5) | (g3 >> 4);
-                for (;;) {
-                    const bool has = m != 0;
-                    const int pbit = __ffs((int)m) - 1;
-                    const int w = pbit & 7, b = pbit >> 3;
-                    const unsigned word = w < 2 ? (w == 0 ? kv[j].x : kv[j].y) : (w == 2 ? kv[j].z : kv[j].w);
-                    const unsigned kq = (word >> (8 * b)) & 0xFFu;
-                    if (!push(has, r0 + 4 * w + b, kq)) break;
-                    m &= m - 1;
-                }
-            }
-        }
-    }
-    if (gw == (n_chunks >> run_shift) % W) {
-        for (long long r0 = n_chunks * kRowsPerLoad; r0 < a.n; r0 += kWave) {
-            const long long r = r0 + lane;
-            const unsigned kq = r < a.n ? a.key[r] : 0u;
-            push(r < a.n && kq >= mk, (int)r, kq);
-        }
-    }
-    if (lfill > 0) drain(lfill);
+    const int chunk_max = walk_key_stream<UNROLL, NT>(a.key, a.n, a.min_key, clamp_run_shift<UNROLL>(a.run_shift), bid, n_scan_blocks, lane, wave,
+                                                      ring.pushed, push);
+    ring.flush(drain);
     if (lane == 0 && ncand) atomicAdd(&blk_cand, ncand);
-    chunk_max = max(chunk_max, pushed - chunk_mark);
     if (lane == 0 && chunk_max) atomicMax(&blk_chunk_max, chunk_max);
 #pragma unroll
     for (int k = 0; k < kWideQPerLane; ++k)

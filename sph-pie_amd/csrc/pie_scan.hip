@@ -2517,57 +2517,88 @@ void launch_batch_k2(pie_ctx* c, BatchSlot& b, hipStream_t s)
     b.k2_pending = false;
 }
 
-int batch_begin(pie_ctx* c, const pie_query* qs, int n_q, int msg_kind, int* msg, long long msg_stride, int u_pad, long long msg_cap,
-                int* msg_counts, long long msg_counts_stride)
+// ---- admission of a batch to a lane's slot, the steps batch_begin and wide_begin share; the callers put them in order
+
+// A table is loaded, the batch holds 1..max_q queries (`what` names the caller's kind of batch) and no single scan is in
+// flight; then the keys are rebuilt if that is due.
+int begin_checks(pie_ctx* c, const pie_query* qs, int n_q, int max_q, const char* what)
 {
     queue_forget(c); // the ordered run's union stages in the slots' workspace
     if (c->cap_rows == 0) return fail(c, PIE_E_STATE, "no table loaded");
-    if (!qs || n_q < 1 || n_q > kBatchMax) return fail(c, PIE_E_INVAL, "a batch holds 1..%d queries (got %d)", kBatchMax, n_q);
+    if (!qs || n_q < 1 || n_q > max_q) return fail(c, PIE_E_INVAL, "%s holds 1..%d queries (got %d)", what, max_q, n_q);
     if (c->n_flight) return fail(c, PIE_E_STATE, "a single scan is in flight: finish it before beginning a batch");
-    PIE_PROF_START();
-    if (c->key_rebuild && c->b_flight == 0) {
-        int rc = build_keys(c, 0, true);
-        if (rc) return rc;
-    }
-    const bool ord_batch = batch_supported(c) && ordered_batch_wanted(c) && !c->ord_lists_only;
-    bool unsupported = !ord_batch && (!batch_supported(c) || c->key_poor || c->batch_poor);
-    // dense queries (the key histogram bounds their live rows above a tenth of the table) do not belong in a batch:
-    // they would make every row a candidate for all queries; they run on the general path
-    bool dense_q[kBatchMax];
+    if (c->key_rebuild && c->b_flight == 0) return build_keys(c, 0, true);
+    return PIE_OK;
+}
+
+// Dense queries (the key histogram bounds their live rows above a tenth of the table) do not belong in a batch: they would
+// make every row a candidate for all queries; they run on the general path.  Marks them in dense[n_q] and says in *fine
+// whether the pass can read the 1-byte key.  False when nothing is left to batch (every query is dense): then there is no
+// table pass at all — a pass whose smallest key is the impossible one would still make nearly every row a candidate.
+bool classify_queries(const pie_ctx* c, const pie_query* qs, int n_q, unsigned char* dense, bool* fine)
+{
+    const bool hist_ok = !c->key_dirty && c->key_hist_rows == c->n;
     int n_batched = 0;
-    bool fine = (c->k1_keyed & 0x800) && !c->fkey_poor;
-    if (!unsupported) {
-        const bool hist_ok = !c->key_dirty && c->key_hist_rows == c->n;
-        for (int q = 0; q < n_q; ++q) {
-            dense_q[q] = hist_ok && (double)rows_keyed_at_or_above(c, qs[q].now) >= kLiveFirstBelow * (double)c->n;
-            if (!dense_q[q]) {
-                ++n_batched;
-                if (qs[q].now < c->fkey_base) fine = false;
-            }
+    *fine = (c->k1_keyed & 0x800) && !c->fkey_poor;
+    for (int q = 0; q < n_q; ++q) {
+        dense[q] = hist_ok && (double)rows_keyed_at_or_above(c, qs[q].now) >= kLiveFirstBelow * (double)c->n;
+        if (!dense[q]) {
+            ++n_batched;
+            if (qs[q].now < c->fkey_base) *fine = false;
         }
-        // nothing left to batch (every query is dense): no table pass at all — a pass whose smallest key is the impossible
-        // one would still make nearly every row a candidate
-        if (n_batched == 0) unsupported = true;
     }
-    // the lane: batches are dealt round robin; a batch on the ordered run (its staging is the scan slots') stays on lane 0 (one
-    // that only falls back queues nothing here: any lane's slot will do)
-    int lane = 0;
-    {
-        const int lanes = ord_batch ? 1 : c->n_lanes;
-        int tried = 0;
-        lane = lanes > 1 ? c->lane_rr % lanes : 0;
-        while (tried < lanes && c->lane_flight[lane] >= kBatchSlots) { lane = (lane + 1) % lanes; ++tried; }
-        if (tried == lanes)
-            return fail(c, PIE_E_STATE, "%d batches are already in flight (%d per lane, %d lane%s): call pie_scan_batch_finish first", c->b_flight,
-                        kBatchSlots, lanes, lanes > 1 ? "s" : "");
-        if (lanes > 1) c->lane_rr = (lane + 1) % lanes;
+    return n_batched > 0;
+}
+
+// Batches are dealt round robin over `lanes` lanes: the first one from lane_rr on with a free slot.  Nothing moves when all are full.
+int pick_lane(pie_ctx* c, int lanes, int* lane_out)
+{
+    int lane = lanes > 1 ? c->lane_rr % lanes : 0, tried = 0;
+    while (tried < lanes && c->lane_flight[lane] >= kBatchSlots) { lane = (lane + 1) % lanes; ++tried; }
+    if (tried == lanes)
+        return fail(c, PIE_E_STATE, "%d batches are already in flight (%d per lane, %d lane%s): finish one first", c->b_flight, kBatchSlots, lanes,
+                    lanes > 1 ? "s" : "");
+    if (lanes > 1) c->lane_rr = (lane + 1) % lanes;
+    *lane_out = lane;
+    return PIE_OK;
+}
+
+// Larger union buckets for every user (a finished batch found one that outgrew its slots), taken once no batch is in flight:
+// every slot's arrays are replaced; their contents are per-batch scratch.
+int regrow_union_buckets(pie_ctx* c)
+{
+    if (c->bdshift_want <= c->bdshift || c->b_flight != 0 || !any_lane_alloc(c)) return PIE_OK;
+    int rc = sync_all(c);
+    if (rc) return rc;
+    const size_t slots = (size_t)c->cap_users << c->bdshift_want;
+    if (slots * sizeof(BktRec) <= kDirectMaxBytes) {
+        c->bdshift = c->bdshift_want;
+        for (BatchSlot& x : c->bslot) {
+            dfree(x.direct); dfree(x.mtab); dfree(x.uoff); dfree(x.urows); dfree(x.umlo); dfree(x.umhi);
+            x.have_result = false;
+        }
+        for (char*& sp : c->bspan) dfree(sp);
+        c->bres = nullptr;
+        for (bool& a : c->lane_alloc) a = false;
+    } else {
+        c->bdshift_want = c->bdshift;
     }
-    BatchSlot* const lane_slots = c->bslot + lane * kBatchSlots;
-    BatchSlot& b = lane_slots[c->lane_next[lane]];
-    hipStream_t s = lane_stream_of(c, lane);
+    return PIE_OK;
+}
+
+// the slot the lane's next batch takes (back = 0), or the one of the batch begun `back` batches before it
+BatchSlot& lane_slot(pie_ctx* c, int lane, int back = 0)
+{
+    return c->bslot[lane * kBatchSlots + (c->lane_next[lane] + kBatchSlots - back) % kBatchSlots];
+}
+
+// The slot is claimed for a batch of n_q queries: what an earlier batch left in it is dropped, the message request and the
+// lane's stream are noted.  msg_kind as BatchSlot::msg_kind, 0 without a message.
+void claim_slot(pie_ctx* c, BatchSlot& b, int lane, int n_q, bool unsupported, int msg_kind, int* msg, long long msg_stride, int u_pad,
+                long long msg_cap, int* msg_counts, long long msg_counts_stride)
+{
     b.lane = lane;
     b.n_q = n_q;
-    b.wide = false;
     b.have_result = false;
     b.union_ok = b.union_part = false;
     b.mu = 0;
@@ -2575,54 +2606,87 @@ int batch_begin(pie_ctx* c, const pie_query* qs, int n_q, int msg_kind, int* msg
     b.msg_kind = msg ? msg_kind : 0;
     b.msg = msg; b.msg_stride = msg_stride; b.msg_u_pad = u_pad; b.msg_cap = msg_cap;
     b.msg_counts = msg_counts; b.msg_counts_stride = msg_counts_stride;
-    for (int q = 0; q < n_q; ++q) { b.q[q] = qs[q]; b.fallback[q] = false; b.idx_of[q] = nullptr; b.list_ok[q] = false; }
     b.ev_index = -1;
     b.ordered = false;
     b.unsupported = unsupported;
-    b.stream = s;
+    b.stream = lane_stream_of(c, lane);
     b.main_ordered = lane == 0;
-    if (!unsupported)
-        for (int q = 0; q < n_q; ++q) b.fallback[q] = dense_q[q];
+}
+
+// a batch none of whose queries takes a pass is in flight with nothing on the lane's stream: finish runs every query on the
+// general path
+void begin_fallback_only(pie_ctx* c, BatchSlot& b)
+{
+    b.in_flight = true;
+    b.k2_pending = false;
+    b.main_ordered = true;
+    batch_begun(c, b.lane);
+}
+
+// a lane above 0 that has queued nothing since the context was last idle goes behind the main stream (see idle_epoch)
+int order_lane_after_main(pie_ctx* c, int lane)
+{
+    if (lane == 0 || c->lane_epoch[lane] == c->idle_epoch) return PIE_OK;
+    PIE_HIP(c, hipEventRecord(c->lane_event[lane][0], c->stream));
+    PIE_HIP(c, hipStreamWaitEvent(lane_stream_of(c, lane), c->lane_event[lane][0], 0));
+    c->lane_epoch[lane] = c->idle_epoch;
+    return PIE_OK;
+}
+
+// spans (the lane's own three, in rotation): this batch's, and the one it zeroes for the batch after the next
+void take_spans(pie_ctx* c, BatchSlot& b)
+{
+    char** const lane_spans = c->bspan + b.lane * 3;
+    b.span = lane_spans[c->lane_span_next[b.lane]];
+    c->lane_span_next[b.lane] = (c->lane_span_next[b.lane] + 1) % 3;
+    b.zero_span = lane_spans[(c->lane_span_next[b.lane] + 1) % 3];
+}
+
+// the batch begun just before the next one on this lane, if its union tail still waits for a launch (tails run in the order of
+// their batches); null otherwise
+BatchSlot* waiting_tail(pie_ctx* c, int lane)
+{
+    BatchSlot& prev = lane_slot(c, lane, 1);
+    return c->lane_flight[lane] >= 1 && prev.in_flight && prev.k2_pending && !prev.ordered ? &prev : nullptr;
+}
+
+int batch_begin(pie_ctx* c, const pie_query* qs, int n_q, int msg_kind, int* msg, long long msg_stride, int u_pad, long long msg_cap,
+                int* msg_counts, long long msg_counts_stride)
+{
+    PIE_PROF_START();
+    int rc = begin_checks(c, qs, n_q, kBatchMax, "a batch");
+    if (rc) return rc;
+    const bool ord_batch = batch_supported(c) && ordered_batch_wanted(c) && !c->ord_lists_only;
+    bool unsupported = !ord_batch && (!batch_supported(c) || c->key_poor || c->batch_poor);
+    unsigned char dense_q[kBatchMax];
+    bool fine = false;
+    if (!unsupported && !classify_queries(c, qs, n_q, dense_q, &fine)) unsupported = true;
+    // a batch on the ordered run (its staging is the scan slots') stays on lane 0 (one that only falls back queues nothing here:
+    // any lane's slot will do)
+    int lane = 0;
+    rc = pick_lane(c, ord_batch ? 1 : c->n_lanes, &lane);
+    if (rc) return rc;
+    BatchSlot& b = lane_slot(c, lane);
+    claim_slot(c, b, lane, n_q, unsupported, msg_kind, msg, msg_stride, u_pad, msg_cap, msg_counts, msg_counts_stride);
+    b.wide = false;
+    for (int q = 0; q < n_q; ++q) { b.q[q] = qs[q]; b.fallback[q] = unsupported || dense_q[q]; b.idx_of[q] = nullptr; b.list_ok[q] = false; }
+    hipStream_t s = b.stream;
     PIE_PROF_TICK(0);
-    if (b.unsupported) { // finish() runs every query on the general path
-        for (int q = 0; q < n_q; ++q) b.fallback[q] = true;
-        b.in_flight = true;
-        b.k2_pending = false;
-        b.main_ordered = true; // nothing of it runs on the lane's stream
-        batch_begun(c, lane);
+    if (unsupported) {
+        begin_fallback_only(c, b);
         return PIE_OK;
     }
-    if (c->bdshift_want > c->bdshift && c->b_flight == 0 && any_lane_alloc(c)) {
-        // larger union buckets for every user (a finished batch found one that outgrew its slots): both slots' arrays are
-        // replaced; their contents are per-batch scratch
-        int rc0 = sync_all(c);
-        if (rc0) return rc0;
-        const size_t slots = (size_t)c->cap_users << c->bdshift_want;
-        if (slots * sizeof(BktRec) <= kDirectMaxBytes) {
-            c->bdshift = c->bdshift_want;
-            for (BatchSlot& x : c->bslot) {
-                dfree(x.direct); dfree(x.mtab); dfree(x.uoff); dfree(x.urows); dfree(x.umlo); dfree(x.umhi);
-                x.have_result = false;
-            }
-            for (char*& sp : c->bspan) dfree(sp);
-            c->bres = nullptr;
-            for (bool& a : c->lane_alloc) a = false;
-        } else {
-            c->bdshift_want = c->bdshift;
-        }
-    }
-    int rc = ord_batch ? PIE_OK : ensure_batch(c, lane);
+    rc = regrow_union_buckets(c);
+    if (rc) return rc;
+    rc = ord_batch ? PIE_OK : ensure_batch(c, lane);
     if (rc) return rc;
     // the 1-byte pass reads the hot index instead of the key column; built here, on the main stream, the first time it can be
     if (fine && !ord_batch && c->hix.enabled && !c->hix.valid && c->b_flight == 0) {
         rc = hot_build(c);
         if (rc) return rc;
     }
-    if (lane > 0 && c->lane_epoch[lane] != c->idle_epoch) { // see idle_epoch
-        PIE_HIP(c, hipEventRecord(c->lane_event[lane][0], c->stream));
-        PIE_HIP(c, hipStreamWaitEvent(s, c->lane_event[lane][0], 0));
-        c->lane_epoch[lane] = c->idle_epoch;
-    }
+    rc = order_lane_after_main(c, lane);
+    if (rc) return rc;
     b.fine_key = fine;
     b.hot = fine && !ord_batch && c->hix.valid;
     b.dshift = c->bdshift;
@@ -2642,14 +2706,14 @@ int batch_begin(pie_ctx* c, const pie_query* qs, int n_q, int msg_kind, int* msg
             b.ev_index = c->ring_used++;
         }
     }
+    BatchSlot* const other = waiting_tail(c, lane);
     if (ord_batch) {
         // the table's batches do not fit the general pass (skewed users): ONE pass over the run's key column for the batch (pie_ordered.h, the batched union form)
         rc = ord_batch_alloc(c);
         if (rc) return rc;
         rc = ensure_batch(c, 0);
         if (rc) return rc;
-        BatchSlot& prev = lane_slots[(c->lane_next[lane] + kBatchSlots - 1) % kBatchSlots];
-        if (c->lane_flight[lane] >= 1 && prev.in_flight && prev.k2_pending) launch_batch_k2(c, prev, s); // nothing carries it along
+        if (other) launch_batch_k2(c, *other, s); // nothing carries it along
         b.seq = ++c->bseq_counter;
         c->scans_begun++;
         if (b.ev_index >= 0) PIE_HIP(c, hipEventRecord(c->ring[b.ev_index].e0, s));
@@ -2661,19 +2725,13 @@ int batch_begin(pie_ctx* c, const pie_query* qs, int n_q, int msg_kind, int* msg
         batch_begun(c, lane);
         return PIE_OK;
     }
-    // spans (the lane's own three): this batch's and the one its tail zeroes
-    char** const lane_spans = c->bspan + lane * 3;
-    b.span = lane_spans[c->lane_span_next[lane]];
-    c->lane_span_next[lane] = (c->lane_span_next[lane] + 1) % 3;
-    b.zero_span = lane_spans[(c->lane_span_next[lane] + 1) % 3];
+    take_spans(c, b);
     b.seq = ++c->bseq_counter;
     const int plan = fine ? 3 : 2;
     b.k1_blocks = c->plan_blocks[plan];
     c->scans_begun++;
-    BatchSlot& other = lane_slots[(c->lane_next[lane] + kBatchSlots - 1) % kBatchSlots]; // the batch begun just before this one on this lane
-    const bool tail_waits = c->lane_flight[lane] >= 1 && other.in_flight && other.k2_pending && !other.ordered;
-    const bool ride = tail_waits && !c->no_ride;
-    if (tail_waits && !ride) launch_batch_k2(c, other, s);
+    const bool ride = other && !c->no_ride;
+    if (other && !ride) launch_batch_k2(c, *other, s);
     if (b.ev_index >= 0) PIE_HIP(c, hipEventRecord(c->ring[b.ev_index].e0, s));
     PIE_PROF_TICK(1);
 #define PIE_BATCH_RIDE(KT, HI)                                                                                          \
@@ -2706,10 +2764,10 @@ int batch_begin(pie_ctx* c, const pie_query* qs, int n_q, int msg_kind, int* msg
         PIE_PROF_TICK(2);                                                                                               \
         if (ride) {                                                                                                     \
             UnionTailArgs t;                                                                                            \
-            fill_tail_args(c, other, t);                                                                                \
+            fill_tail_args(c, *other, t);                                                                               \
             if (t.n_q > 32) PIE_BATCH_RIDE(KT, true);                                                                   \
             else PIE_BATCH_RIDE(KT, false);                                                                             \
-            other.k2_pending = false;                                                                                   \
+            other->k2_pending = false;                                                                                  \
         } else {                                                                                                        \
             hipLaunchKernelGGL((k_scan_batch<8, true, KT>), dim3((unsigned)b.k1_blocks), dim3(kK1Threads), 0, s, a);    \
         }                                                                                                               \
@@ -3084,87 +3142,35 @@ int ensure_wide(pie_ctx* c, BatchSlot& b)
 
 int wide_begin(pie_ctx* c, const pie_query* qs, int n_q, int* msg = nullptr, int u_pad = 0, long long msg_cap = 0)
 {
-    queue_forget(c);
-    if (c->cap_rows == 0) return fail(c, PIE_E_STATE, "no table loaded");
-    if (!qs || n_q < 1 || n_q > kWideMax) return fail(c, PIE_E_INVAL, "a wide batch holds 1..%d queries (got %d)", kWideMax, n_q);
-    if (c->n_flight) return fail(c, PIE_E_STATE, "a single scan is in flight: finish it before beginning a batch");
-    if (c->key_rebuild && c->b_flight == 0) {
-        int rc = build_keys(c, 0, true);
-        if (rc) return rc;
-    }
+    int rc = begin_checks(c, qs, n_q, kWideMax, "a wide batch");
+    if (rc) return rc;
     // a table whose batches take the ordered run, or that cannot run the batched pass: every query falls back
     const bool ord_table = batch_supported(c) && ordered_batch_wanted(c) && !c->ord_lists_only;
     bool unsupported = ord_table || !batch_supported(c) || c->key_poor || c->batch_poor;
     std::vector<unsigned char> dense((size_t)n_q, 0);
-    int n_batched = 0;
-    bool fine = (c->k1_keyed & 0x800) && !c->fkey_poor;
-    if (!unsupported) {
-        const bool hist_ok = !c->key_dirty && c->key_hist_rows == c->n;
-        for (int q = 0; q < n_q; ++q) {
-            dense[q] = hist_ok && (double)rows_keyed_at_or_above(c, qs[q].now) >= kLiveFirstBelow * (double)c->n;
-            if (!dense[q]) {
-                ++n_batched;
-                if (qs[q].now < c->fkey_base) fine = false;
-            }
-        }
-        if (n_batched == 0) unsupported = true;
-    }
+    bool fine = false;
+    if (!unsupported && !classify_queries(c, qs, n_q, dense.data(), &fine)) unsupported = true;
     int lane = 0;
-    {
-        const int lanes = ord_table ? 1 : c->n_lanes;
-        int tried = 0;
-        lane = lanes > 1 ? c->lane_rr % lanes : 0;
-        while (tried < lanes && c->lane_flight[lane] >= kBatchSlots) { lane = (lane + 1) % lanes; ++tried; }
-        if (tried == lanes)
-            return fail(c, PIE_E_STATE, "%d batches are already in flight (%d per lane, %d lane%s): finish one first", c->b_flight, kBatchSlots,
-                        lanes, lanes > 1 ? "s" : "");
-        if (lanes > 1) c->lane_rr = (lane + 1) % lanes;
-    }
-    if (!unsupported && c->bdshift_want > c->bdshift && c->b_flight == 0 && any_lane_alloc(c)) {
-        // larger union buckets (as batch_begin): every slot's arrays are replaced
-        int rc0 = sync_all(c);
-        if (rc0) return rc0;
-        const size_t slots = (size_t)c->cap_users << c->bdshift_want;
-        if (slots * sizeof(BktRec) <= kDirectMaxBytes) {
-            c->bdshift = c->bdshift_want;
-            for (BatchSlot& x : c->bslot) {
-                dfree(x.direct); dfree(x.mtab); dfree(x.uoff); dfree(x.urows); dfree(x.umlo); dfree(x.umhi);
-                x.have_result = false;
-            }
-            for (char*& sp : c->bspan) dfree(sp);
-            c->bres = nullptr;
-            for (bool& a : c->lane_alloc) a = false;
-        } else {
-            c->bdshift_want = c->bdshift;
-        }
+    rc = pick_lane(c, ord_table ? 1 : c->n_lanes, &lane);
+    if (rc) return rc;
+    if (!unsupported) {
+        rc = regrow_union_buckets(c);
+        if (rc) return rc;
     }
     // the bucket-slot masks are four times the bucket records: the same bound as the direct slots
     if (!unsupported && wide_slot_bytes(c) > kDirectMaxBytes) unsupported = true;
-    BatchSlot* const lane_slots = c->bslot + lane * kBatchSlots;
-    BatchSlot& b = lane_slots[c->lane_next[lane]];
-    hipStream_t s = lane_stream_of(c, lane);
+    BatchSlot& b = lane_slot(c, lane);
     if (!b.w) b.w = new WideSlot();
     WideSlot& w = *b.w;
     w.words = (n_q + 63) / 64;
-    int rc = unsupported ? PIE_OK : ensure_batch(c, lane);
-    if (rc) return rc;
     if (!unsupported) {
+        rc = ensure_batch(c, lane);
+        if (rc) return rc;
         rc = ensure_wide(c, b);
         if (rc) return rc;
     }
-    b.lane = lane;
-    b.n_q = n_q;
+    claim_slot(c, b, lane, n_q, unsupported, 2, msg, 0, u_pad, msg_cap, nullptr, 0); // (2: the tail writes the wide union message, pie_scan_wide_begin_union)
     b.wide = true;
-    b.have_result = false;
-    b.union_ok = b.union_part = false;
-    b.mu = 0;
-    if (c->bres == &b) c->bres = nullptr;
-    b.msg_kind = msg ? 2 : 0; b.msg = msg; b.msg_counts = nullptr; // (2: the tail writes the wide union message, pie_scan_wide_begin_union)
-    b.msg_u_pad = u_pad; b.msg_cap = msg_cap;
-    b.ev_index = -1;
-    b.ordered = false;
-    b.unsupported = unsupported;
-    b.stream = s;
     b.k2_pending = false;
     w.q.assign(qs, qs + n_q);
     w.fallback.assign((size_t)n_q, 0);
@@ -3172,30 +3178,20 @@ int wide_begin(pie_ctx* c, const pie_query* qs, int n_q, int* msg = nullptr, int
     if ((int)w.lists.size() < n_q) w.lists.resize((size_t)n_q);
     for (WideSlot::List& l : w.lists) l.ok = false;
     for (int q = 0; q < n_q; ++q) w.fallback[q] = unsupported ? 1 : dense[q];
-    if (unsupported) { // finish runs every query on the general path
-        b.main_ordered = true;
-        b.in_flight = true;
-        batch_begun(c, lane);
+    if (unsupported) {
+        begin_fallback_only(c, b);
         return PIE_OK;
     }
-    b.main_ordered = lane == 0;
-    if (lane > 0 && c->lane_epoch[lane] != c->idle_epoch) { // see idle_epoch
-        PIE_HIP(c, hipEventRecord(c->lane_event[lane][0], c->stream));
-        PIE_HIP(c, hipStreamWaitEvent(s, c->lane_event[lane][0], 0));
-        c->lane_epoch[lane] = c->idle_epoch;
-    }
+    hipStream_t s = b.stream;
+    rc = order_lane_after_main(c, lane);
+    if (rc) return rc;
     b.fine_key = fine;
     b.dshift = c->bdshift;
-    char** const lane_spans = c->bspan + lane * 3;
-    b.span = lane_spans[c->lane_span_next[lane]];
-    c->lane_span_next[lane] = (c->lane_span_next[lane] + 1) % 3;
-    b.zero_span = lane_spans[(c->lane_span_next[lane] + 1) % 3];
+    take_spans(c, b);
     b.seq = ++c->bseq_counter;
     b.k1_blocks = c->plan_blocks[fine ? 3 : 2];
     c->scans_begun++;
-    // the batch begun just before this one on this lane has its tail queued first (tails run in the order of their batches)
-    BatchSlot& other = lane_slots[(c->lane_next[lane] + kBatchSlots - 1) % kBatchSlots];
-    if (c->lane_flight[lane] >= 1 && other.in_flight && other.k2_pending && !other.ordered) launch_batch_k2(c, other, s);
+    if (BatchSlot* prev = waiting_tail(c, lane)) launch_batch_k2(c, *prev, s);
     // the queries as the lanes hold them: a query that falls back has mask 0 and selects nothing here
     const unsigned long long table = c->n_disc >= 64 ? ~0ull : ((1ull << c->n_disc) - 1ull);
     unsigned mk = fine ? 0xFFu : 0xFFFFu;
