@@ -226,9 +226,16 @@ int pie_batch_read_union(pie_ctx *ctx, int64_t *uoff_out, int32_t *rows_out, uin
  * a query index (pie_batch_read_results, pie_batch_result_device_ptrs, pie_batch_read_user_feed, pie_batch_fetch_requests) accept
  * every qi < n_q; the 32/64-bit union readers (pie_batch_union_device_ptrs, pie_batch_read_union, pie_batch_pack_union_device)
  * return PIE_E_STATE.  A wide batch whose queries fall back (dense queries, a user whose union outgrows 64 slots, bad rows), on a
- * table whose batches take the ordered run, or on a table that cannot run the batched pass, has exact per-query results and no
- * union: the wide union readers return PIE_E_STATE.  The wide state (mask words, host summaries) is allocated by the first wide
- * batch of a context. */
+ * table whose batches take the ordered run unless pie_set_wide_ordered is on, or on a table that cannot run the batched pass,
+ * has exact per-query results and no union: the wide union readers return PIE_E_STATE.  The wide state (mask words, host
+ * summaries) is allocated by the first wide batch of a context.
+ * With pie_set_wide_ordered(ctx, 1) a wide batch on a table whose batches take the ordered run (skewed users, mode 2 of
+ * pie_set_ordered_run, a table the general pass gave up on) is ONE pass over the run's key column and keeps its union like any
+ * other: per user the rows any query selects in (start, row) order with no 64-row bound per user, bounded only by the union
+ * result arrays (max(16 rows per user of capacity, rows / 16 + 4096)).  A union that outgrows them reruns every query (exact
+ * results, no union) and sends the context's later wide batches back to the per-query path until the table is loaded anew.
+ * The run holds no row whose user id lies outside [0, users) (its build leaves them out), so on a table that has such rows
+ * this pass simply never selects them, as the ordinary batch on the run does, where the general wide pass returns PIE_E_INVAL. */
 #define PIE_WIDE_MAX 512
 int pie_scan_wide_begin(pie_ctx *ctx, const pie_query *queries, int n_q);
 int pie_scan_wide_finish(pie_ctx *ctx, size_t *m_out, size_t m_cap, int *n_q_out);
@@ -248,7 +255,8 @@ int pie_batch_pack_union_wide_device(pie_ctx *ctx, void *dst_i32, size_t u_pad, 
  * until the matching finish; u_pad >= users.
  * pie_scan_wide_finish_packed finishes the oldest batch of either kind, as pie_scan_wide_finish does.  *ready_out = 1: the
  * batch kept its union and the message was complete when the call returned.  *ready_out = 0: the batch has no union (queries
- * fell back, the table is on the ordered run or cannot run the batched pass, the slot masks exceed the direct bound); the
+ * fell back, the table is on the ordered run unless pie_set_wide_ordered is on, or cannot run the batched pass, the slot masks
+ * exceed the direct bound); the
  * header — uoff[0..u_pad] and the Mu word, all -1 — is written on the context's stream (order the consumer behind
  * pie_ctx_aux_stream); the per-query results stay exact and readable through the readers above.  The first wide batch on a
  * table normally overflows its 16 union slots per user and reruns on the general path while the slot capacity grows, so it
@@ -421,6 +429,12 @@ uint32_t pie_hot_slot_bits(uint32_t n_users);
  * fresh segments (a linear pass).  Loads, sharding and back-fills (a row more than 256 rows back in its segment) invalidate
  * it (queries run on the general path until it is rebuilt).  PIE_ORDERED=0|1|2 sets the mode a context starts with. */
 int pie_set_ordered_run(pie_ctx *ctx, int mode);
+/* Wide batches on the ordered run (see pie_scan_wide_begin).  0 (default): a wide batch on a table whose batches take the
+ * ordered run reruns every query as a single scan and keeps no union.  1: it runs one pass over the run and keeps its union
+ * (and writes the message of pie_scan_wide_begin_union, ready = 1).  A table that does not take the ordered run is not
+ * affected.  PIE_E_STATE while a scan or batch is in flight, PIE_E_INVAL for any other value.  PIE_WIDE_ORDERED=1 sets the
+ * value a context starts with. */
+int pie_set_wide_ordered(pie_ctx *ctx, int on);
 /* 0: off.  n >= 1: every n-th scan carries HIP events around K1 and around the whole scan (an event between two
  * kernels costs a few microseconds of pipeline drain, so a benchmark samples). */
 int pie_set_profiling(pie_ctx *ctx, int enabled);

@@ -90,6 +90,7 @@ _SIGS = [
     ("pie_host_free", C.c_int, [_P, _P]),
     ("pie_set_scan_form", C.c_int, [_P, C.c_int]),
     ("pie_set_ordered_run", C.c_int, [_P, C.c_int]),
+    ("pie_set_wide_ordered", C.c_int, [_P, C.c_int]),
     ("pie_set_batch_lanes", C.c_int, [_P, C.c_int]),
     ("pie_batch_lanes", C.c_int, [_P]),
     ("pie_batch_room", C.c_int, [_P]),
@@ -423,6 +424,11 @@ class PieScan:
         """0: never (frees the run), 1: adaptive (default), 2: always (pie_set_ordered_run)."""
         self._check(self._lib.pie_set_ordered_run(self._ctx, int(mode)))
 
+    def set_wide_ordered(self, on):
+        """1: a wide batch on a table whose batches take the ordered run runs one pass there and keeps its union; 0 (default):
+        it reruns its queries one by one (pie_set_wide_ordered)."""
+        self._check(self._lib.pie_set_wide_ordered(self._ctx, int(on)))
+
     def table_info(self):
         ti = PieTableInfo()
         ti.struct_size = C.sizeof(PieTableInfo)
@@ -651,11 +657,19 @@ class PieScan:
         n = qis.shape[0]
         cap = int(cap_rows) if cap_rows is not None else 64 * max(n, 1)
         off = np.empty(n + 1, np.int64)
-        idx, disc = np.empty(max(cap, 1), np.int32), np.empty(max(cap, 1), np.int32)
-        start, end = np.empty(max(cap, 1), np.int64), np.empty(max(cap, 1), np.int64)
         total = C.c_size_t(0)
-        self._check(self._lib.pie_batch_fetch_requests(self._ctx, _ptr(qis), _ptr(users), n, cap, _ptr(off), _ptr(idx), _ptr(start), _ptr(end),
-                                                       _ptr(disc), C.byref(total)))
+        while True:
+            idx, disc = np.empty(max(cap, 1), np.int32), np.empty(max(cap, 1), np.int32)
+            start, end = np.empty(max(cap, 1), np.int64), np.empty(max(cap, 1), np.int64)
+            rc = self._lib.pie_batch_fetch_requests(self._ctx, _ptr(qis), _ptr(users), n, cap, _ptr(off), _ptr(idx), _ptr(start), _ptr(end),
+                                                    _ptr(disc), C.byref(total))
+            # the default room is 64 rows per request; a union on the ordered run has no such bound per user: the call says how
+            # many rows there are
+            if rc == PIE_E_CAPACITY and cap_rows is None and total.value > cap:
+                cap = int(total.value)
+                continue
+            self._check(rc)
+            break
         t = total.value
         return off, idx[:t], start[:t], end[:t], disc[:t]
 

@@ -49,6 +49,7 @@
     X(int, pie_archive_queue, (pie_ctx *, int64_t, int64_t, int32_t *, size_t, size_t *))                           \
     X(int, pie_set_profiling, (pie_ctx *, int))                                                                     \
     X(int, pie_set_ordered_run, (pie_ctx *, int))                                                                   \
+    X(int, pie_set_wide_ordered, (pie_ctx *, int))                                                                  \
     X(int, pie_set_batch_lanes, (pie_ctx *, int))                                                                   \
     X(int, pie_batch_lanes, (pie_ctx *))                                                                            \
     X(int, pie_stats_get, (pie_ctx *, pie_stats *))                                                                 \
@@ -57,6 +58,7 @@
     X(int, pie_scan_wide_begin, (pie_ctx *, const pie_query *, int))                                                \
     X(int, pie_scan_wide_finish, (pie_ctx *, size_t *, size_t, int *))                                              \
     X(int, pie_batch_read_user_feed, (pie_ctx *, int, int32_t, int32_t *, size_t, size_t *))                        \
+    X(int, pie_batch_union_wide_device_ptrs, (pie_ctx *, void **, void **, void **, int *, size_t *))               \
     X(int, pie_comm_create, (const int32_t *, int32_t, pie_comm **))                                                \
     X(int, pie_comm_destroy, (pie_comm *))                                                                          \
     X(const char *, pie_comm_last_error, (const pie_comm *))                                                        \
@@ -1882,6 +1884,34 @@ static napi_value fn_set_ordered_run(napi_env env, napi_callback_info info)
     return js_int(env, 0);
 }
 
+/* setWideOrdered(ctx, on): 1 = a wide batch on a table whose batches take the ordered run runs one pass there and keeps its
+ * union; 0 (default) = it reruns its queries one by one (pie_set_wide_ordered) */
+static napi_value fn_set_wide_ordered(napi_env env, napi_callback_info info)
+{
+    ARGS(2)
+    pie_ctx *ctx = get_ctx(env, argv[0]);
+    if (!ctx) return NULL;
+    int32_t on = 0;
+    CHECK(env, napi_get_value_int32(env, argv[1], &on));
+    const int rc = p_pie_set_wide_ordered(ctx, on);
+    if (rc != 0) return throw_pie(env, ctx, rc);
+    return js_int(env, 0);
+}
+
+/* wideUnionRows(ctx) -> union rows (Mu) of the last finished wide batch, -1 when it kept no union (its queries fell back) */
+static napi_value fn_wide_union_rows(napi_env env, napi_callback_info info)
+{
+    ARGS(1)
+    pie_ctx *ctx = get_ctx(env, argv[0]);
+    if (!ctx) return NULL;
+    size_t mu = 0;
+    int words = 0;
+    const int rc = p_pie_batch_union_wide_device_ptrs(ctx, NULL, NULL, NULL, &words, &mu);
+    if (rc == PIE_E_STATE) return js_int(env, -1);
+    if (rc != 0) return throw_pie(env, ctx, rc);
+    return js_int(env, (int64_t)mu);
+}
+
 /* setBatchLanes(ctx, n): lanes of the batched scan — independent streams whose batches run side by side — 1..4, 0 = by table
  * size (pie_set_batch_lanes) -> lanes in use now */
 static napi_value fn_set_batch_lanes(napi_env env, napi_callback_info info)
@@ -1907,7 +1937,7 @@ static napi_value init(napi_env env, napi_value exports)
         {"readColumns", fn_read_columns}, {"saveColumns", fn_save_columns}, {"loadColumnsDir", fn_load_columns_dir}, {"setEnd", fn_set_end}, {"compactRows", fn_compact_rows}, {"compactMaps", fn_compact_maps}, {"compactTranslate", fn_compact_translate}, {"deleteUser", fn_delete_user}, {"retentionPurgeTz", fn_retention_purge_tz},
         {"setDisciplines", fn_set_disc}, {"scan", fn_scan}, {"scanDevice", fn_scan_device}, {"userFeed", fn_user_feed}, {"scanAsync", fn_scan_async}, {"fetchRows", fn_fetch_rows},
         {"expiredQueue", fn_expired_queue}, {"archiveQueue", fn_archive_queue}, {"serializeEvents", fn_serialize_events}, {"serializeICal", fn_serialize_ical}, {"stats", fn_stats}, {"setProfiling", fn_set_profiling},
-        {"setOrderedRun", fn_set_ordered_run}, {"setBatchLanes", fn_set_batch_lanes},
+        {"setOrderedRun", fn_set_ordered_run}, {"setWideOrdered", fn_set_wide_ordered}, {"wideUnionRows", fn_wide_union_rows}, {"setBatchLanes", fn_set_batch_lanes},
         {"serializeCsv", fn_serialize_csv}, {"scanBatch", fn_scan_batch}, {"scanWide", fn_scan_wide}, {"batchUserFeed", fn_batch_user_feed}, {"batchFetchRequests", fn_batch_fetch_requests},
         {"commCreate", fn_comm_create}, {"commDestroy", fn_comm_destroy}, {"commWorld", fn_comm_world}, {"commCtx", fn_comm_ctx},
         {"commGenSyntheticSharded", fn_comm_gen}, {"commScanBatchGather", fn_comm_scan_gather}, {"commReadGathered", fn_comm_read}, {"commUPad", fn_comm_upad},

@@ -1203,4 +1203,383 @@ __global__ __launch_bounds__(256) void k_ord_union_publish(Summary* __restrict__
     if (lane == 0) __hip_atomic_store(&host->seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+// ------------------------------------------------------------------------------------------------ wide batches on the run (pie_set_wide_ordered)
+//
+// Up to kWideMax queries, one pass over the run's key column: the walk, the candidate ring and the position-ordered staging of
+// k_ord_batch_scan_t, the evaluation of scan_wide_body (pie_kernels.h: lane l HOLDS queries 8 l .. 8 l + 7, the wave takes its
+// queued candidates one after the other, each candidate's record gathered once whatever Q).  BatchTables has no room for 512
+// queries, so a staging record cannot carry ranks to rebuild its mask from; the mask row (`words` 64-bit words) travels through
+// a POOL instead: every drain reserves as many pool slots as it selected candidates with one atomic on a cursor, the
+// candidate's own lane stores its row id and mask row there, and the staging record carries [place in chunk | pool slot].
+//   k_ord_wide_scan     key stream -> staging records + pool entries + per-chunk union counts + per-query totals
+//   k_ord_prefix        the ONE exclusive prefix over the chunk counts (also M)
+//   k_ord_wide_emit     copy role: a thread per union position finds its staging record (two-level search, as k_ord_emit) and
+//                       copies row and mask row from the pool; user role: uoff, the largest union bucket
+//   k_ord_wide_publish  summary + per-query totals to the slot's device block (the host copies it behind the chain); the
+//                       counters it read start the next batch clean
+// The pool, urows and umask hold `ucap` rows: a store beyond is dropped and counted (n_over), and the host reruns the queries.
+// The run holds no row with a user id outside the table (its build and its appends leave them out), so there is nothing to
+// count in bad_rows here, as in k_ord_batch_scan_t.
+struct alignas(8) OrdWide {
+    unsigned place; // position within the chunk
+    unsigned slot;  // pool entry
+};
+
+struct OrdWidePool {
+    int* rows;                 // [ucap]
+    unsigned long long* mask;  // [ucap * words]
+    int words;
+    long long ucap;
+};
+
+// the counters of a wide batch on the run, in the mq area behind the batch's summary set: zero between batches
+constexpr int kOrdWideCursor = kWideMax; // word index of the pool cursor behind the kWideMax per-query totals
+
+template <class KT, int UNROLL = 4>
+__global__ __launch_bounds__(256) void k_ord_wide_scan(const OrdRec* __restrict__ pay, const long long* __restrict__ end,
+                                                       const KT* __restrict__ key, long long n_ord, long long n_chunks, unsigned min_key,
+                                                       const WideQuery* __restrict__ wq, OrdWide* __restrict__ ustage, int* __restrict__ ucount,
+                                                       OrdWidePool pool, unsigned* __restrict__ mq, Summary* __restrict__ summary)
+{
+    constexpr int kPerLane = 8;
+    constexpr int kChunk = kPerLane * kWave;
+    constexpr int kChunkShift = 9;
+    constexpr int kRing = 2 * kChunk;
+    constexpr int kUnroll = UNROLL;
+    __shared__ int ring_s[4][kRing];
+    __shared__ KT ringk_s[4][kRing];
+    __shared__ alignas(16) unsigned char s_qm[4][kWave][kWave]; // per wave: candidate j's query mask, byte l from lane l
+    __shared__ unsigned s_mq[kWideMax];
+    __shared__ int blk_cand, blk_chunk_max;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (threadIdx.x == 0) { blk_cand = 0; blk_chunk_max = 0; }
+    for (int i = threadIdx.x; i < kWideMax; i += 256) s_mq[i] = 0;
+    long long qnow[kWideQPerLane], qcut[kWideQPerLane];
+    unsigned long long qdm[kWideQPerLane];
+    unsigned qnk[kWideQPerLane], qcnt[kWideQPerLane];
+#pragma unroll
+    for (int k = 0; k < kWideQPerLane; ++k) {
+        const WideQuery w = wq[lane * kWideQPerLane + k];
+        qnow[k] = w.now; qcut[k] = w.cutoff; qdm[k] = w.mask; qnk[k] = w.nk; qcnt[k] = 0;
+    }
+    __syncthreads();
+    int* ring = ring_s[wave];
+    KT* ringk = ringk_s[wave];
+    unsigned char* qm = &s_qm[wave][0][0];
+    int head = 0, fill = 0, ncand = 0, chunk_max = 0;
+    int cur_chunk = -1, cur_cnt = 0;
+    const unsigned long long lt = (1ull << lane) - 1ull;
+    const unsigned long long le = lane == 63 ? ~0ull : ((2ull << lane) - 1ull);
+    bool a_have = false;
+    int a_cnt = 0; // wave-uniform: candidates of the batch whose gathers are in flight
+    int a_pos = 0x7FFFFFFF;
+    unsigned a_key = 0;
+    OrdRec a_pay;
+    a_pay.start = 0; a_pay.row = 0; a_pay.disc = -1;
+
+    auto step_b = [&]() { // the gathers are back: candidate j in turn, each lane for its eight queries
+        if (!a_have) return;
+        a_have = false;
+        bool sel = false;
+        for (int j = 0; j < a_cnt; ++j) {
+            const int pj = __builtin_amdgcn_readlane(a_pos, j);
+            unsigned byte = 0;
+            if (pj < n_ord) { // wave-uniform (a padding position of the key column otherwise)
+                const unsigned kj = (unsigned)__builtin_amdgcn_readlane((int)a_key, j);
+                const int dj = __builtin_amdgcn_readlane(a_pay.disc, j);
+                const long long sj = readlane_i64(a_pay.start, j);
+                // a query whose key(now) EQUALS the row's key is decided by the 8-byte `end`
+                bool amb = false;
+#pragma unroll
+                for (int k = 0; k < kWideQPerLane; ++k) amb = amb || qnk[k] == kj;
+                long long ej = 0;
+                if (__ballot(amb)) ej = end[pj];
+#pragma unroll
+                for (int k = 0; k < kWideQPerLane; ++k) {
+                    const bool live = qnk[k] < kj || (qnk[k] == kj && qnow[k] < ej);
+                    const bool hit = live && sj >= qcut[k] && ((qdm[k] >> (dj & 63)) & 1ull);
+                    byte |= hit ? (1u << k) : 0u;
+                }
+                if ((unsigned)dj >= 64u) byte = 0;
+                if (__ballot(byte != 0)) {
+#pragma unroll
+                    for (int k = 0; k < kWideQPerLane; ++k) qcnt[k] += (byte >> k) & 1u;
+                    if (lane == j) sel = true;
+                }
+                ++ncand;
+            }
+            qm[j * kWave + lane] = (unsigned char)byte;
+        }
+        __builtin_amdgcn_wave_barrier();
+        const unsigned long long sb = __ballot(sel);
+        if (sb != 0) {
+            // pool slots of this drain: one atomic for all of them
+            const int nsel = __popcll(sb);
+            unsigned base = 0;
+            if (lane == 0) base = atomicAdd(&mq[kOrdWideCursor], (unsigned)nsel);
+            base = (unsigned)__builtin_amdgcn_readfirstlane((int)base);
+            const long long slot = (long long)base + __popcll(sb & lt);
+            // positions ascend with the lane, so the lanes of one chunk are consecutive (see k_ord_scan_keyed)
+            const int ch = a_pos >> kChunkShift;
+            const int ch_below = __shfl_up(ch, 1, kWave);
+            const unsigned long long hb = __ballot(lane == 0 || ch != ch_below);
+            const int first = 63 - __clzll((long long)(hb & le));
+            int rank = __popcll(sb & lt & ~((1ull << first) - 1ull));
+            if (ch == cur_chunk) rank += cur_cnt;
+            const unsigned long long ha = hb & ~le;
+            const int seg_end = ha ? __ffsll((long long)ha) - 1 : 64;
+            const unsigned long long upto = seg_end == 64 ? ~0ull : ((1ull << seg_end) - 1ull);
+            const bool last_of_seg = sel && (sb & ~le & upto) == 0;
+            const int last = 63 - __clzll((long long)sb);
+            const int new_chunk = __shfl(ch, last, kWave);
+            const int new_cnt = __shfl(rank, last, kWave) + 1;
+            if (sel) {
+                OrdWide r;
+                r.place = (unsigned)a_pos & (unsigned)(kChunk - 1);
+                r.slot = (unsigned)slot;
+                if (rank < kChunk) ustage[((long long)ch << kChunkShift) + rank] = r; // (a chunk holds kChunk positions: always)
+                if (slot < pool.ucap) {
+                    pool.rows[slot] = a_pay.row;
+                    const unsigned long long* src = reinterpret_cast<const unsigned long long*>(qm + lane * kWave);
+                    unsigned long long* dst = pool.mask + slot * pool.words;
+                    for (int i = 0; i < pool.words; ++i) dst[i] = src[i];
+                }
+                if (last_of_seg && ch != new_chunk) ucount[ch] = rank + 1;
+            }
+            if (cur_chunk >= 0 && cur_chunk != new_chunk && __ballot(sel && ch == cur_chunk) == 0 && lane == 0) ucount[cur_chunk] = cur_cnt;
+            if (lane == 0 && (long long)base + nsel > pool.ucap) atomicAdd(&summary->n_over, 1u); // dropped, never written: the host reruns the queries
+            cur_chunk = new_chunk;
+            cur_cnt = new_cnt;
+        }
+        __builtin_amdgcn_wave_barrier();
+    };
+    auto step_a = [&](int cnt) { // form a batch of cnt <= 64 candidates and issue its gathers
+        a_pos = 0x7FFFFFFF;
+        a_key = 0;
+        a_pay.disc = -1;
+        if (lane < cnt) {
+            const int slot = (head + lane) & (kRing - 1);
+            a_pos = ring[slot];
+            a_key = ringk[slot];
+            if (a_pos < n_ord) a_pay = pay[a_pos];
+        }
+        a_cnt = cnt;
+        a_have = true;
+        head = (head + cnt) & (kRing - 1);
+        fill -= cnt;
+    };
+
+    typedef unsigned u4_t __attribute__((ext_vector_type(4)));
+    constexpr unsigned kTop = sizeof(KT) == 2 ? 0x80008000u : 0x80808080u;
+    const unsigned mk = min_key;
+    const unsigned nk_ge = sizeof(KT) == 2 ? (mk | (mk << 16)) : mk * 0x01010101u;
+    auto row_bits = [&](unsigned g0, unsigned g1, unsigned g2, unsigned g3) -> unsigned {
+        if constexpr (sizeof(KT) == 1) {
+            auto nib = [](unsigned g) { return ((((g >> 7) & 0x01010101u) * 0x01020408u) >> 24) & 0xFu; };
+            return nib(g0) | (nib(g1) << 4) | (nib(g2) << 8) | (nib(g3) << 12);
+        } else {
+            auto two = [](unsigned g) { return ((g >> 15) & 1u) | ((g >> 30) & 2u); };
+            return two(g0) | (two(g1) << 2) | (two(g2) << 4) | (two(g3) << 6);
+        }
+    };
+    const long long W = (long long)gridDim.x * 4;
+    const long long gw = (long long)blockIdx.x * 4 + wave;
+    for (long long cb = gw; cb < n_chunks; cb += W * kUnroll) {
+        u4_t kv[kUnroll];
+#pragma unroll
+        for (int j = 0; j < kUnroll; ++j) {
+            const long long ch = cb + (long long)j * W;
+            kv[j] = (u4_t){0u, 0u, 0u, 0u};
+            if (ch < n_chunks) {
+                if constexpr (sizeof(KT) == 1) {
+                    typedef unsigned u2_t __attribute__((ext_vector_type(2)));
+                    const u2_t h = __builtin_nontemporal_load(reinterpret_cast<const u2_t*>(key + (ch << kChunkShift) + kPerLane * lane));
+                    kv[j].x = h.x;
+                    kv[j].y = h.y;
+                } else kv[j] = __builtin_nontemporal_load(reinterpret_cast<const u4_t*>(key + (ch << kChunkShift) + kPerLane * lane));
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < kUnroll; ++j) {
+            const long long ch = cb + (long long)j * W;
+            if (ch >= n_chunks) continue;
+            const unsigned ge = row_bits(((kv[j].x | kTop) - nk_ge) & kTop, ((kv[j].y | kTop) - nk_ge) & kTop,
+                                         ((kv[j].z | kTop) - nk_ge) & kTop, ((kv[j].w | kTop) - nk_ge) & kTop) & 0xFFu; // 8 rows per lane
+            const int cnt = __popc(ge);
+            const int incl = wave_incl_scan_i32(cnt, lane);
+            const int total = __shfl(incl, 63, kWave);
+            if (total == 0) continue;
+            chunk_max = max(chunk_max, total);
+            int w = head + fill + incl - cnt;
+            const int p0 = (int)(ch << kChunkShift) + kPerLane * lane;
+            unsigned m = ge;
+            while (m) {
+                const int b = __ffs((int)m) - 1;
+                unsigned kq;
+                if constexpr (sizeof(KT) == 1) {
+                    const unsigned word = (b >> 2) == 0 ? kv[j].x : (b >> 2) == 1 ? kv[j].y : (b >> 2) == 2 ? kv[j].z : kv[j].w;
+                    kq = (word >> (8 * (b & 3))) & 0xFFu;
+                } else {
+                    const unsigned word = (b >> 1) == 0 ? kv[j].x : (b >> 1) == 1 ? kv[j].y : (b >> 1) == 2 ? kv[j].z : kv[j].w;
+                    kq = (word >> (16 * (b & 1))) & 0xFFFFu;
+                }
+                ring[w & (kRing - 1)] = p0 + b;
+                ringk[w & (kRing - 1)] = (KT)kq;
+                ++w;
+                m &= m - 1;
+            }
+            fill += total;
+            __builtin_amdgcn_wave_barrier();
+            while (fill >= kWave) {
+                step_b();
+                step_a(kWave);
+            }
+            __builtin_amdgcn_wave_barrier();
+        }
+    }
+    if (fill > 0) {
+        step_b();
+        step_a(fill);
+    }
+    step_b();
+    if (cur_chunk >= 0 && lane == 0) ucount[cur_chunk] = cur_cnt;
+    if (lane == 0 && ncand) atomicAdd(&blk_cand, ncand);
+    if (lane == 0 && chunk_max) atomicMax(&blk_chunk_max, chunk_max);
+    // per-query totals: once per block into LDS, once into mq (as scan_wide_body)
+#pragma unroll
+    for (int k = 0; k < kWideQPerLane; ++k)
+        if (qcnt[k]) atomicAdd(&s_mq[lane * kWideQPerLane + k], qcnt[k]);
+    __syncthreads();
+    for (int i = threadIdx.x; i < kWideMax; i += 256)
+        if (s_mq[i]) atomicAdd(&mq[i], s_mq[i]);
+    if (threadIdx.x == 0) add_row_stats(summary, 0, 0, (int)blockIdx.x, blk_cand, blk_chunk_max);
+}
+
+// behind the one k_ord_prefix: blocks [0, copy_blocks) copy, the others look after the users (255 per block, see k_ord_emit)
+__global__ __launch_bounds__(256) void k_ord_wide_emit(const long long* __restrict__ uoff_run, int n_users, long long n_ord, long long n_chunks,
+                                                       const OrdWide* __restrict__ ustage, const int* __restrict__ ucount,
+                                                       const int* __restrict__ unit_local, const long long* __restrict__ group_base, OrdWidePool pool,
+                                                       long long* __restrict__ uoff_out, int* __restrict__ urows, unsigned long long* __restrict__ umask,
+                                                       int copy_blocks, Summary* __restrict__ summary, int* __restrict__ zero_counts, long long zero_n)
+{
+    constexpr int kChunkShift = 9;
+    __shared__ long long soff[256];
+    __shared__ long long gb[1024];
+    __shared__ int wmax[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long n_groups = (n_chunks + kOrdGroup - 1) >> kOrdGroupShift;
+    // the other unit-count buffer starts the next ordered scan clean
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < zero_n; i += (long long)gridDim.x * 256) zero_counts[i] = 0;
+    if ((int)blockIdx.x < copy_blocks) {
+        const long long m_all = group_base[n_groups];
+        const long long m = m_all < pool.ucap ? m_all : pool.ucap; // what the result arrays hold (beyond: n_over, see k_ord_wide_publish)
+        const bool in_lds = n_groups < 1024;
+        if (in_lds)
+            for (int i = threadIdx.x; i <= (int)n_groups; i += 256) gb[i] = group_base[i];
+        __syncthreads();
+        for (long long k = (long long)blockIdx.x * 256 + threadIdx.x; k < m; k += (long long)copy_blocks * 256) {
+            long long lo = 0, hi = n_groups - 1; // the largest g with group_base[g] <= k: never an empty group
+            while (lo < hi) {
+                const long long mid = (lo + hi + 1) >> 1;
+                if ((in_lds ? gb[mid] : group_base[mid]) <= k) lo = mid;
+                else hi = mid - 1;
+            }
+            const int x = (int)(k - (in_lds ? gb[lo] : group_base[lo]));
+            const int* loc = unit_local + (lo << kOrdGroupShift);
+            int a = 0, b = kOrdGroup - 1;        // the largest j with loc[j] <= x: never an empty unit
+            while (a < b) {
+                const int mid = (a + b + 1) >> 1;
+                if (loc[mid] <= x) a = mid;
+                else b = mid - 1;
+            }
+            const long long unit = (lo << kOrdGroupShift) + a;
+            const int at = x - loc[a];
+            if (unit >= n_chunks || at >= (1 << kChunkShift)) continue; // (cannot be: the counts are the staged records)
+            const OrdWide r = ustage[(unit << kChunkShift) + at];
+            if ((long long)r.slot >= pool.ucap) continue;               // its pool entry was dropped: the batch is rerun
+            urows[k] = pool.rows[r.slot];
+            const unsigned long long* src = pool.mask + (long long)r.slot * pool.words;
+            unsigned long long* dst = umask + k * pool.words;
+            for (int i = 0; i < pool.words; ++i) dst[i] = src[i];
+        }
+    } else {
+        const long long u = (long long)((int)blockIdx.x - copy_blocks) * 255 + threadIdx.x;
+        long long my = 0;
+        if (u <= n_users) {
+            const long long qpos = uoff_run[u];
+            if (qpos >= n_ord) my = group_base[n_groups];
+            else {
+                const long long ch = qpos >> kChunkShift;
+                const OrdWide* rec = ustage + (ch << kChunkShift);
+                int lo = 0, hi = ucount[ch];
+                while (lo < hi) { // staged in position order: the records before my segment start
+                    const int mid = (lo + hi) >> 1;
+                    if (rec[mid].place < ((unsigned)qpos & kOrdSubMask)) lo = mid + 1;
+                    else hi = mid;
+                }
+                my = group_base[ch >> kOrdGroupShift] + unit_local[ch] + lo;
+            }
+            // a union beyond the result arrays is rerun by the host (n_over); until then no reader of uoff — the message
+            // pack behind this launch is one — may be led past the rows the arrays hold
+            if (my > pool.ucap) my = pool.ucap;
+            uoff_out[u] = my;
+        }
+        soff[threadIdx.x] = my;
+        __syncthreads();
+        int cnt = 0;
+        if (threadIdx.x < 255 && u < n_users) cnt = (int)(soff[threadIdx.x + 1] - soff[threadIdx.x]);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) cnt = max(cnt, __shfl_xor(cnt, o, kWave));
+        if (lane == 0) wmax[wave] = cnt;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const int bm = max(max(wmax[0], wmax[1]), max(wmax[2], wmax[3]));
+            if (bm > 0) atomicMax(&stat_slots(summary)[blockIdx.x & (kStatSlots - 1)].max_count, (unsigned long long)bm);
+        }
+    }
+}
+
+// one block: the batch's summary (m = union rows, the largest union bucket, candidates, n_over) and the kWideMax per-query totals
+// into `out` (Summary, padded to kSummaryBytes, then the totals), which the host copies behind the chain; every counter it read
+// starts the next batch clean
+__global__ __launch_bounds__(kWideMax) void k_ord_wide_publish(Summary* __restrict__ summary, unsigned* __restrict__ mq, long long ucap,
+                                                               char* __restrict__ out)
+{
+    const int t = threadIdx.x, lane = t & 63;
+    unsigned* out_mq = reinterpret_cast<unsigned*>(out + kSummaryBytes);
+    out_mq[t] = __hip_atomic_load(&mq[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    mq[t] = 0;
+    if (t >= 64) return;
+    unsigned long long live = 0, amb = 0, cand = 0;
+    unsigned int chunk_max = 0;
+    sum_row_stats(summary, lane, live, amb, &cand, &chunk_max);
+    unsigned long long slot_max = stat_slots(summary)[lane].max_count;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long other = __shfl_xor(slot_max, o, kWave);
+        slot_max = other > slot_max ? other : slot_max;
+    }
+    {
+        StatSlot* slot = stat_slots(summary) + lane;
+        slot->max_count = 0;
+        slot->live = 0;
+        slot->amb = 0;
+        slot->cand = 0;
+        slot->chunk_max = 0;
+    }
+    if (lane == 0) {
+        Summary o{};
+        o.m = summary->m;
+        o.max_count = (unsigned int)slot_max;
+        o.cand = cand;
+        o.chunk_max = chunk_max;
+        o.bad_rows = 0;
+        o.n_over = summary->n_over + ((long long)o.m > ucap ? 1u : 0u); // the union outgrew the result arrays: the host reruns the queries
+        summary->n_over = 0;
+        summary->max_count = 0;
+        mq[kOrdWideCursor] = 0;
+        *reinterpret_cast<Summary*>(out) = o;
+    }
+}
+
 } // namespace pie

@@ -117,6 +117,8 @@ struct WideSlot {
     unsigned long long* dmask = nullptr;    // bucket-slot masks: kWideWords words per slot
     unsigned long long* umask = nullptr;    // union masks: `words` words per union row, for up to (cap_users << dshift) rows
     int umask_words = 0;                    // mask words per row umask was sized for
+    size_t umask_rows = 0;                  // ... and union rows
+    char* d_sum = nullptr;                  // a wide batch on the run: its summary + kWideMax per-query totals (k_ord_wide_publish), copied to h_sum
     WideQuery* d_wq = nullptr;              // the batch's queries as the lanes hold them
     WideQuery* h_wq = nullptr;              // pinned staging of d_wq
     Summary* h_sum = nullptr;               // pinned: the pass's summary, then kWideMax per-query totals
@@ -216,6 +218,11 @@ struct OrderedRun {
     long long* bq_gbase = nullptr;
     OrdCtl* bq_ctl = nullptr;
     char* bq_sum[2] = {nullptr, nullptr};
+    // wide batches on the run (pie_ordered.h OrdWidePool): scratch between the pass and its emit, one set (chains run one after the other)
+    int* wp_rows = nullptr;
+    unsigned long long* wp_mask = nullptr;
+    size_t wp_cap = 0;
+    int wp_words = 0;
     int users = 0;                           // users that have a segment (>= n_users: room for users yet to come)
     long long pos_cap = 0;                   // positions the arrays hold
     int* unit_count[2] = {nullptr, nullptr}; // alternate: the finish kernel of one ordered scan zeroes the other buffer
@@ -399,6 +406,8 @@ struct pie_ctx {
                                 // per cent faster); follows the densest-chunk statistic of the last pass, see choose_run_shift
     bool batch_poor = false;    // union buckets overflowed at their largest capacity (skewed users): batches run as single scans
     bool ord_lists_only = false; // a batch's union on the ordered run outgrew the result arrays: its batches take the per-query chain
+    bool wide_ordered = false;   // pie_set_wide_ordered / PIE_WIDE_ORDERED: a wide batch on a table whose batches take the ordered run runs one pass there
+    bool wide_ord_off = false;   // ... until the union of one outgrew the result arrays: later wide batches rerun their queries, as with the switch off
     bool run_shift_pinned = false; // PIE_RUN_SHIFT=0..3 pins it (A/B runs)
     bool last_was_batch = false; // pie_stats_get describes the last finished batch rather than the last single scan
     unsigned long long bseq_counter = 0;
@@ -546,7 +555,7 @@ void free_batch(pie_ctx* c)
         b.n_q = 0;
         b.wide = false;
         if (WideSlot* w = b.w) {
-            dfree(w->dmask); dfree(w->umask); dfree(w->d_wq);
+            dfree(w->dmask); dfree(w->umask); dfree(w->d_wq); dfree(w->d_sum);
             if (w->h_wq) (void)hipHostFree(w->h_wq);
             if (w->h_sum) (void)hipHostFree(w->h_sum);
             if (w->done) (void)hipEventDestroy(w->done);
@@ -574,6 +583,8 @@ void ord_free(pie_ctx* c)
     dfree(o.pay); dfree(o.end); dfree(o.key); dfree(o.fkey); dfree(o.pos); dfree(o.uoff); dfree(o.ufill); dfree(o.pend); dfree(o.placed); dfree(o.bhead); dfree(o.bnext);
     dfree(o.alt_pay); dfree(o.alt_end); dfree(o.alt_key); dfree(o.alt_fkey); dfree(o.alt_uoff);
     dfree(o.bq_local); dfree(o.bq_gsum); dfree(o.bq_gbase); dfree(o.bq_ctl); dfree(o.bq_sum[0]); dfree(o.bq_sum[1]);
+    dfree(o.wp_rows); dfree(o.wp_mask);
+    o.wp_cap = 0; o.wp_words = 0;
     dfree(o.unit_count[0]); dfree(o.unit_count[1]); dfree(o.unit_local); dfree(o.group_sum); dfree(o.group_base); dfree(o.tile_ballot); dfree(o.tile_prefix);
     dfree(o.sum[0]); dfree(o.sum[1]);
     o.valid = false;
@@ -870,6 +881,7 @@ int ensure_capacity(pie_ctx* c, long long n, int n_users, long long keep_rows = 
         c->live_frac = -1;
         c->batch_poor = false;
         c->ord_lists_only = false;
+        c->wide_ord_off = false;
         if (!c->run_shift_pinned) c->run_shift = 0;
         c->hot_bucket = false;
         c->clustered = false;
@@ -3117,7 +3129,8 @@ int batch_pack_union(pie_ctx* c, BatchSlot& b, void* dst_i32, size_t u_pad, size
 // union row; a union row holds a bucket slot, so (cap_users << dshift) rows bound it)
 size_t wide_slot_bytes(const pie_ctx* c) { return ((size_t)c->cap_users << c->bdshift) * kWideWords * 8; }
 
-int ensure_wide(pie_ctx* c, BatchSlot& b)
+// `ordered`: a wide batch on the run has no bucket slots; its union is bounded by the result arrays (batch_ucap), not by the slots
+int ensure_wide(pie_ctx* c, BatchSlot& b, bool ordered = false)
 {
     WideSlot& w = *b.w;
     if (!w.done) PIE_HIP(c, hipEventCreateWithFlags(&w.done, hipEventDisableTiming));
@@ -3125,18 +3138,78 @@ int ensure_wide(pie_ctx* c, BatchSlot& b)
     if (!w.h_wq) PIE_HIP(c, hipHostMalloc(&w.h_wq, (size_t)kWideMax * sizeof(WideQuery), hipHostMallocDefault));
     if (!w.d_wq) PIE_HIP(c, hipMalloc(&w.d_wq, (size_t)kWideMax * sizeof(WideQuery)));
     const size_t slots = (size_t)c->cap_users << c->bdshift;
-    if (w.dshift != c->bdshift || !w.dmask) {
-        dfree(w.dmask); dfree(w.umask);
-        w.umask_words = 0;
+    if (!ordered && (w.dshift != c->bdshift || !w.dmask)) {
+        dfree(w.dmask);
         PIE_HIP(c, hipMalloc(&w.dmask, slots * kWideWords * 8));
         w.dshift = c->bdshift;
     }
-    if (w.umask_words < w.words) {
+    const size_t rows = ordered ? batch_ucap(c) : slots;
+    if (w.umask_words < w.words || w.umask_rows < rows) {
         dfree(w.umask);
         w.umask_words = 0;
-        PIE_HIP(c, hipMalloc(&w.umask, slots * (size_t)w.words * 8));
+        w.umask_rows = 0;
+        PIE_HIP(c, hipMalloc(&w.umask, rows * (size_t)w.words * 8));
         w.umask_words = w.words;
+        w.umask_rows = rows;
     }
+    if (ordered) {
+        if (!w.d_sum) PIE_HIP(c, hipMalloc(&w.d_sum, (size_t)kSummaryBytes + (size_t)kWideMax * 4));
+        OrderedRun& o = c->ord;
+        if (o.wp_cap < rows || o.wp_words < w.words) {
+            dfree(o.wp_rows); dfree(o.wp_mask);
+            o.wp_cap = 0; o.wp_words = 0;
+            PIE_HIP(c, hipMalloc(&o.wp_rows, rows * 4));
+            PIE_HIP(c, hipMalloc(&o.wp_mask, rows * (size_t)w.words * 8));
+            o.wp_cap = rows;
+            o.wp_words = w.words;
+        }
+    }
+    return PIE_OK;
+}
+
+// a wide batch on the ordered run: scan, ONE prefix, emit, publish, then the union message where one was asked for — see
+// pie_ordered.h "wide batches on the run".  Scratch as launch_ordered_union: the scan slots' record staging and two summary sets.
+int launch_ordered_wide(pie_ctx* c, BatchSlot& b, hipStream_t s, bool fine, unsigned mk)
+{
+    OrderedRun& o = c->ord;
+    WideSlot& w = *b.w;
+    const int bi = (int)(&b - c->bslot) & 1;
+    char* sums = o.bq_sum[bi];
+    int* uc = o.unit_count[o.uc_next];
+    int* uc_other = o.unit_count[o.uc_next ^ 1];
+    o.uc_next ^= 1;
+    OrdWide* ustage = reinterpret_cast<OrdWide*>(c->slot[bi].sel);
+    const long long n_chunks = (o.n + 511) >> 9;
+    Summary* sum0 = reinterpret_cast<Summary*>(sums);
+    unsigned* mq = reinterpret_cast<unsigned*>(sums + ord_sum_bytes()); // the set's mq area: kWideMax totals, then the pool cursor; zero between batches
+    const long long ucap = (long long)batch_ucap(c);
+    const OrdWidePool pool{o.wp_rows, o.wp_mask, w.words, ucap};
+    // 38 / 42 KiB of LDS per block: four / three blocks fit a CU
+    long long grid = (long long)c->n_cus * (fine ? 4 : 3);
+    if (grid > (n_chunks + 3) / 4) grid = (n_chunks + 3) / 4;
+    if (grid < 1) grid = 1;
+    b.k1_blocks = (int)grid;
+    if (fine) hipLaunchKernelGGL((k_ord_wide_scan<fkey_t>), dim3((unsigned)grid), dim3(256), 0, s, o.pay, o.end, o.fkey, o.n, n_chunks, mk, w.d_wq, ustage, uc, pool, mq, sum0);
+    else hipLaunchKernelGGL((k_ord_wide_scan<lkey_t>), dim3((unsigned)grid), dim3(256), 0, s, o.pay, o.end, o.key, o.n, n_chunks, mk, w.d_wq, ustage, uc, pool, mq, sum0);
+    long long n_groups = (n_chunks + kOrdGroup - 1) >> kOrdGroupShift;
+    if (n_groups < 1) n_groups = 1;
+    const unsigned pre_grid = (unsigned)(n_groups < (long long)c->n_cus ? n_groups : (long long)c->n_cus);
+    hipLaunchKernelGGL(k_ord_prefix, dim3(pre_grid), dim3(256), 0, s, uc, n_chunks, o.bq_local, o.bq_gsum, o.bq_gbase, o.bq_ctl, sum0, 0LL, 0LL, 0LL);
+    const int copy_blocks = c->n_cus * 8;
+    const int user_blocks = (int)(((long long)c->n_users + 1 + 254) / 255);
+    hipLaunchKernelGGL(k_ord_wide_emit, dim3((unsigned)(copy_blocks + user_blocks)), dim3(256), 0, s, o.uoff, c->n_users, o.n, n_chunks, ustage, uc, o.bq_local,
+                       o.bq_gbase, pool, b.uoff, b.urows, w.umask, copy_blocks, sum0, uc_other, o.units_cap);
+    hipLaunchKernelGGL(k_ord_wide_publish, dim3(1), dim3(kWideMax), 0, s, sum0, mq, ucap, w.d_sum);
+    if (b.msg) { // the message of pie_scan_wide_begin_union, complete when the batch's event has passed
+        const size_t total = (size_t)b.msg_u_pad + 2 + (size_t)(b.msg_cap < ucap ? b.msg_cap : ucap) * (1 + 2 * (size_t)w.words);
+        size_t pgrid = (total + 255) / 256;
+        if (pgrid > (size_t)c->n_cus * 8) pgrid = (size_t)c->n_cus * 8;
+        hipLaunchKernelGGL(k_wide_pack, dim3((unsigned)(pgrid ? pgrid : 1)), dim3(256), 0, s, c->n_users, b.msg_u_pad, (const long long*)b.uoff,
+                           (const int*)b.urows, (const unsigned long long*)w.umask, w.words, b.msg_cap, b.msg);
+    }
+    PIE_HIP(c, hipGetLastError());
+    PIE_HIP(c, hipMemcpyAsync(w.h_sum, w.d_sum, (size_t)kSummaryBytes + (size_t)b.n_q * 4, hipMemcpyDeviceToHost, s));
+    PIE_HIP(c, hipEventRecord(w.done, s));
     return PIE_OK;
 }
 
@@ -3145,28 +3218,34 @@ int wide_begin(pie_ctx* c, const pie_query* qs, int n_q, int* msg = nullptr, int
     int rc = begin_checks(c, qs, n_q, kWideMax, "a wide batch");
     if (rc) return rc;
     // a table whose batches take the ordered run, or that cannot run the batched pass: every query falls back
+    // (with pie_set_wide_ordered on, the former runs ONE pass over the run's key column: launch_ordered_wide)
     const bool ord_table = batch_supported(c) && ordered_batch_wanted(c) && !c->ord_lists_only;
-    bool unsupported = ord_table || !batch_supported(c) || c->key_poor || c->batch_poor;
+    const bool ord_wide = ord_table && c->wide_ordered && !c->wide_ord_off;
+    bool unsupported = !ord_wide && (ord_table || !batch_supported(c) || c->key_poor || c->batch_poor);
     std::vector<unsigned char> dense((size_t)n_q, 0);
     bool fine = false;
     if (!unsupported && !classify_queries(c, qs, n_q, dense.data(), &fine)) unsupported = true;
     int lane = 0;
     rc = pick_lane(c, ord_table ? 1 : c->n_lanes, &lane);
     if (rc) return rc;
-    if (!unsupported) {
+    if (!unsupported && !ord_wide) { // (a wide batch on the run has no union buckets)
         rc = regrow_union_buckets(c);
         if (rc) return rc;
     }
     // the bucket-slot masks are four times the bucket records: the same bound as the direct slots
-    if (!unsupported && wide_slot_bytes(c) > kDirectMaxBytes) unsupported = true;
+    if (!unsupported && !ord_wide && wide_slot_bytes(c) > kDirectMaxBytes) unsupported = true;
     BatchSlot& b = lane_slot(c, lane);
     if (!b.w) b.w = new WideSlot();
     WideSlot& w = *b.w;
     w.words = (n_q + 63) / 64;
     if (!unsupported) {
+        if (ord_wide) {
+            rc = ord_batch_alloc(c);
+            if (rc) return rc;
+        }
         rc = ensure_batch(c, lane);
         if (rc) return rc;
-        rc = ensure_wide(c, b);
+        rc = ensure_wide(c, b, ord_wide);
         if (rc) return rc;
     }
     claim_slot(c, b, lane, n_q, unsupported, 2, msg, 0, u_pad, msg_cap, nullptr, 0); // (2: the tail writes the wide union message, pie_scan_wide_begin_union)
@@ -3187,9 +3266,9 @@ int wide_begin(pie_ctx* c, const pie_query* qs, int n_q, int* msg = nullptr, int
     if (rc) return rc;
     b.fine_key = fine;
     b.dshift = c->bdshift;
-    take_spans(c, b);
+    if (!ord_wide) take_spans(c, b);
     b.seq = ++c->bseq_counter;
-    b.k1_blocks = c->plan_blocks[fine ? 3 : 2];
+    if (!ord_wide) b.k1_blocks = c->plan_blocks[fine ? 3 : 2]; // (launch_ordered_wide sets its own grid)
     c->scans_begun++;
     if (BatchSlot* prev = waiting_tail(c, lane)) launch_batch_k2(c, *prev, s);
     // the queries as the lanes hold them: a query that falls back has mask 0 and selects nothing here
@@ -3212,6 +3291,14 @@ int wide_begin(pie_ctx* c, const pie_query* qs, int n_q, int* msg = nullptr, int
         }
     }
     PIE_HIP(c, hipMemcpyAsync(w.d_wq, w.h_wq, (size_t)kWideMax * sizeof(WideQuery), hipMemcpyHostToDevice, s));
+    if (ord_wide) {
+        rc = launch_ordered_wide(c, b, s, fine, mk);
+        if (rc) return rc;
+        b.ordered = true;
+        b.in_flight = true;
+        batch_begun(c, lane);
+        return PIE_OK;
+    }
     char* const sp = b.span;
     Summary* const sum = reinterpret_cast<Summary*>(sp + span_counts_bytes(c) + span_tiles_bytes(c) + span_parts_bytes() + 128);
     unsigned* const mq = reinterpret_cast<unsigned*>(sp + counts_span(c));
@@ -3378,7 +3465,8 @@ int wide_finish(pie_ctx* c, size_t* m_out, size_t m_cap, int* n_q_out, int* read
             w.m[q] = mq[q];
             if (overflow) w.fallback[q] = 1;
         }
-        if (us.n_over > 0) {
+        if (us.n_over > 0 && b.ordered) c->wide_ord_off = true; // the union outgrew the result arrays on the run: later wide batches rerun their queries
+        else if (us.n_over > 0) {
             if (c->bdshift < kUnionShiftMax) c->bdshift_want = c->bdshift + 1;
             else c->batch_poor = true;
         }
@@ -3386,7 +3474,7 @@ int wide_finish(pie_ctx* c, size_t* m_out, size_t m_cap, int* n_q_out, int* read
         b.union_part = !overflow;
         b.union_ok = !overflow;
         for (int q = 0; q < b.n_q; ++q) b.union_ok = b.union_ok && !w.fallback[q];
-        choose_run_shift(c, us.cand, us.chunk_max, b.fine_key);
+        if (!b.ordered) choose_run_shift(c, us.cand, us.chunk_max, b.fine_key);
     }
     batch_left(c, b);
     unsigned bad = 0;
@@ -3517,6 +3605,7 @@ int pie_ctx_create(int device_id, pie_ctx** ctx_out)
     if (const char* v = getenv("PIE_ORDER_BLOCK")) { const int b = atoi(v); if (b == 256 || b == 512 || b == 1024) c->order_block = b; }
     if (const char* v = getenv("PIE_RUN_SHIFT")) { const int r = atoi(v); if (r >= 0 && r <= 3) { c->run_shift = r; c->run_shift_pinned = true; } }
     if (const char* v = getenv("PIE_ORDERED")) { const int m = atoi(v); if (m >= 0 && m <= 2) c->ord.mode = m; }
+    if (const char* v = getenv("PIE_WIDE_ORDERED")) c->wide_ordered = atoi(v) == 1;
     if (const char* v = getenv("PIE_ORD_GRID")) { const int g = atoi(v); if (g >= 1 && g <= 64) c->ord.grid_mult = g; }
     if (const char* v = getenv("PIE_WAIT_DEADLINE_MS")) { const double d = atof(v); if (d > 0) c->wait_deadline_ms = d; }
     if (const char* v = getenv("PIE_K1_KEYED")) {
@@ -5041,11 +5130,13 @@ int pie_table_info_get(pie_ctx* c, pie_table_info* out)
         out->workspace_bytes += (uint64_t)b.lists_q * ((uint64_t)batch_users_stride(c) * 12 + (uint64_t)batch_out_stride(c) * 4);
     for (const BatchSlot& b : c->bslot) { // the wide state of slots that ran wide batches
         if (!b.w) continue;
-        if (b.w->dmask) out->workspace_bytes += ((uint64_t)c->cap_users << b.w->dshift) * (kWideWords + (uint64_t)b.w->umask_words) * 8;
+        if (b.w->dmask) out->workspace_bytes += ((uint64_t)c->cap_users << b.w->dshift) * kWideWords * 8;
+        if (b.w->umask) out->workspace_bytes += (uint64_t)b.w->umask_rows * (uint64_t)b.w->umask_words * 8;
         if (b.w->d_wq) out->workspace_bytes += (uint64_t)kWideMax * sizeof(WideQuery);
         for (const WideSlot::List& l : b.w->lists)
             if (l.counts) out->workspace_bytes += ((uint64_t)c->cap_users + 1) * 12 + (uint64_t)l.idx_cap * 4;
     }
+    if (c->ord.wp_rows) out->workspace_bytes += (uint64_t)c->ord.wp_cap * (4 + (uint64_t)c->ord.wp_words * 8); // the pool of wide batches on the run
     out->index_build_ms = c->index_build_ms;
     out->ordered_rows = c->ord.valid ? (uint64_t)c->ord.held : 0u;
     out->ordered_positions = c->ord.valid ? (uint64_t)c->ord.n : 0u;
@@ -5127,6 +5218,15 @@ int pie_set_ordered_run(pie_ctx* c, int mode)
         PIE_HIP(c, hipStreamSynchronize(c->stream));
         ord_free(c);
     }
+    return PIE_OK;
+}
+
+int pie_set_wide_ordered(pie_ctx* c, int on)
+{
+    if (!c) return PIE_E_INVAL;
+    if (on != 0 && on != 1) return fail(c, PIE_E_INVAL, "pie_set_wide_ordered takes 0 (off) or 1 (on)");
+    if (c->n_flight || c->b_flight) return fail(c, PIE_E_STATE, "a scan is in flight");
+    c->wide_ordered = on == 1;
     return PIE_OK;
 }
 
