@@ -451,6 +451,46 @@ int32_t pie_shard_of(int32_t user, int32_t n_shards);
 int pie_shard_table(pie_ctx *ctx, int32_t rank, int32_t world, size_t *n_rows_out, int32_t *n_users_out);
 int pie_shard_maps(pie_ctx *ctx, int32_t *rows_global_out, int32_t *users_global_out);
 
+/* ---- a LIVE sharded table: createSession / touchSession / deleteSession / deleteSessionsForUser (server/sessionStore.js:12-19,
+ * 37-64) by GLOBAL id.  A context that pie_shard_table left remembers its rank, the world, and the size of the WHOLE table
+ * (N_g rows, U_g users).  Every shard is given the same call with the same arrays and keeps what is its own; nothing is
+ * exchanged.  The calls keep the shards in step with the unsharded table: a shard's rows are the whole table's rows of its
+ * users in ascending global row (less what its own compactions dropped), its row map ascends and covers every local row, its
+ * user map is the ascending list of ALL ids in [0, U_g) that hash to the rank.  New users always have ids at or above the old
+ * U_g, new rows global ids above all earlier ones, so both maps grow at their ends only and no local id ever moves; global
+ * row ids are never reused (pie_compact_rows keeps reporting the original ones).  Rows appended this way HAVE a global row:
+ * pie_queue_info, pie_queue_pack_device and the pie_comm_*_queue calls keep working.
+ * All of them return PIE_E_STATE on a context that was never sharded (or whose table was loaded or generated anew since), on
+ * one whose row map does not cover its rows (plain pie_append_rows added some), and while a scan or batch is in flight.
+ * Everything is checked before anything is staged or changed.  The device maps have room for the table's capacity and grow
+ * with it; the context keeps a host copy of the user map (4 B per local user) and none of the row map. */
+int pie_shard_info(pie_ctx *ctx, int32_t *rank_out, int32_t *world_out, int64_t *rows_global_out /* N_g */,
+                   int32_t *users_global_out /* U_g */, uint64_t *map_bytes_out /* device bytes of the two maps */);
+/* The k rows are rows [N_g, N_g + k) of the unsharded table, in array order; user_global[] holds GLOBAL ids in
+ * [0, n_users_global), n_users_global >= U_g (PIE_E_INVAL otherwise, and when N_g + k >= 2^31 - 1).  The shard keeps the rows
+ * whose user hashes to it; N_g grows by k and U_g to n_users_global on every shard whether or not it kept a row (k = 0 only
+ * raises U_g).  *first_row_out = N_g before the call, *n_kept_out = rows kept.  Queued and un-waited where pie_append_rows is. */
+int pie_shard_append_rows(pie_ctx *ctx, const int64_t *start, const int64_t *end, const int32_t *user_global, const int32_t *disc,
+                          size_t k, int32_t n_users_global, int32_t *first_row_out, size_t *n_kept_out);
+/* end[row] = new_end by GLOBAL row in [0, N_g) (PIE_E_INVAL outside).  The shard applies the elements whose row it holds; rows
+ * of other shards and rows its compactions dropped are skipped.  Repeats: the last element wins, as in pie_set_end.  A touch of a
+ * row appended by the call before finds that row (stream order), with no wait in between. */
+int pie_shard_set_end(pie_ctx *ctx, const int32_t *rows_global, const int64_t *new_end, size_t k);
+/* pie_delete_user by GLOBAL user id: a no-op (n_deleted = 0) on the shards the user does not hash to and for ids outside
+ * [0, U_g); rows_global_out (may be NULL) receives GLOBAL rows, ascending. */
+int pie_shard_delete_user(pie_ctx *ctx, int32_t user_global, int32_t *rows_global_out, size_t cap, size_t *n_deleted);
+/* k global rows -> local rows in place (-1: not held by this shard); k local rows -> global rows in place (-1: outside the
+ * map).  One small launch each, for hosts that hold a few rows of a huge table (the shape of pie_compact_translate); with
+ * them the per-shard lists of pie_prune_before / pie_retention_purge* become global rows. */
+int pie_shard_rows_to_local(pie_ctx *ctx, int32_t *rows_inout, size_t k);
+int pie_shard_rows_to_global(pie_ctx *ctx, int32_t *rows_inout, size_t k);
+/* Host only, no context, no GPU: the routing pie_shard_append_rows applies.  keep_out[i] = 1 iff pie_shard_of(user_global[i],
+ * world) == rank (any int32 is routed: routing is not validation), *n_kept_out their number; new_users_out (cap entries, may be
+ * NULL with cap 0) = the ascending ids in [users_before, users_after) that hash to rank, *n_new_out their number;
+ * PIE_E_CAPACITY (with *n_new_out set) when that exceeds cap.  For tests. */
+int pie_shard_route(const int32_t *user_global, size_t k, int32_t rank, int32_t world, uint8_t *keep_out, size_t *n_kept_out,
+                    int32_t users_before, int32_t users_after, int32_t *new_users_out, size_t cap, size_t *n_new_out);
+
 /* ---- compaction: the table's counterpart of `sessions.delete()` (server/sessionStore.js:47-53,66-73) ---------------------
  * Every mutator above appends rows or tombstones them; pie_compact_rows is what removes rows from the device table.
  * Keep, in table order, exactly the rows with end > dead_before; drop the rest.  dead_before = PIE_END_NONE drops
@@ -560,6 +600,22 @@ int pie_comm_queue_device_ptrs(pie_comm *comm, int32_t at_rank, void **rows_dev,
 /* Device time of the phases of the last queue call on the first local rank's stream (ms): [0] local queue + header exchange,
  * [1] pack, [2] payload exchange, [3] merge. */
 int pie_comm_queue_timing(pie_comm *comm, float *ms_out_4);
+
+/* ---- a live sharded table behind the communicator: pie_shard_append_rows / pie_shard_set_end / pie_shard_delete_user on every
+ * local shard, with GLOBAL ids throughout.  Nothing is exchanged: every process of a process-per-GPU communicator makes the
+ * same call with the same arrays.  Every local shard checks the call before any is changed, so a refused call changes none.
+ * PIE_E_STATE while pipelined steps of either kind are uncollected, and when the local shards disagree on the table's size.
+ * pie_comm_append_rows: *first_row_out = the table's row count before the call.  n_users may grow; that can raise the largest
+ * shard's user count, and the reservations of pie_comm_step_reserve / pie_comm_wide_step_reserve are then the caller's to renew,
+ * as after any table change (u_pad = 0 in pie_comm_scan_batch_gather follows by itself).
+ * pie_comm_delete_user: rows_out / *n_deleted are filled by the process that drives the owning rank; *owner_rank_out =
+ * pie_shard_of(user, world) (-1 for an id outside [0, users)); other processes report n_deleted = 0.
+ * pie_comm_table_size: rows and users of the whole table. */
+int pie_comm_append_rows(pie_comm *comm, const int64_t *start, const int64_t *end, const int32_t *user, const int32_t *disc, size_t k,
+                         int32_t n_users, int32_t *first_row_out);
+int pie_comm_set_end(pie_comm *comm, const int32_t *rows, const int64_t *new_end, size_t k);
+int pie_comm_delete_user(pie_comm *comm, int32_t user, int32_t *rows_out, size_t cap, size_t *n_deleted, int32_t *owner_rank_out);
+int pie_comm_table_size(pie_comm *comm, int64_t *rows_global_out, int32_t *users_global_out);
 
 /* ---- the pipelined exchange: ONE union message per step (layout: pie_scan_batch_begin_union), written by each shard's own
  * batch kernels; the exchange of step i runs on a side stream while the shards scan steps i+1, i+2.  Order of calls:

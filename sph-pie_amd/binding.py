@@ -138,6 +138,14 @@ _SIGS = [
     ("pie_shard_of", C.c_int32, [C.c_int32, C.c_int32]),
     ("pie_shard_table", C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(C.c_size_t), C.POINTER(C.c_int32)]),
     ("pie_shard_maps", C.c_int, [_P, _P, _P]),
+    ("pie_shard_info", C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]),
+    ("pie_shard_append_rows", C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_size_t)]),
+    ("pie_shard_set_end", C.c_int, [_P, _P, _P, C.c_size_t]),
+    ("pie_shard_delete_user", C.c_int, [_P, C.c_int32, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("pie_shard_rows_to_local", C.c_int, [_P, _P, C.c_size_t]),
+    ("pie_shard_rows_to_global", C.c_int, [_P, _P, C.c_size_t]),
+    ("pie_shard_route", C.c_int, [_P, C.c_size_t, C.c_int32, C.c_int32, _P, C.POINTER(C.c_size_t), C.c_int32, C.c_int32, _P, C.c_size_t,
+                                  C.POINTER(C.c_size_t)]),
     ("pie_compact_rows", C.c_int, [_P, C.c_int64, C.c_uint32, C.POINTER(C.c_size_t)]),
     ("pie_compact_maps", C.c_int, [_P, _P, _P, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     ("pie_compact_map_device_ptrs", C.c_int, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
@@ -177,6 +185,10 @@ _SIGS = [
     ("pie_comm_queue_read", C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("pie_comm_queue_device_ptrs", C.c_int, [_P, C.c_int32, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_size_t)]),
     ("pie_comm_queue_timing", C.c_int, [_P, C.POINTER(C.c_float)]),
+    ("pie_comm_append_rows", C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, C.c_int32, C.POINTER(C.c_int32)]),
+    ("pie_comm_set_end", C.c_int, [_P, _P, _P, C.c_size_t]),
+    ("pie_comm_delete_user", C.c_int, [_P, C.c_int32, _P, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int32)]),
+    ("pie_comm_table_size", C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
 ]
 ABI_SYMBOLS = [s[0] for s in _SIGS]
 
@@ -784,6 +796,54 @@ class PieScan:
         self._check(self._lib.pie_shard_maps(self._ctx, _ptr(rows), _ptr(users)))
         return rows[: self.n], users
 
+    # ---- a live sharded table: mutators by GLOBAL id (every shard is given the same call and keeps what is its own)
+    def shard_info(self):
+        """-> {rank, world, rows_global (N_g), users_global (U_g), map_bytes} of a context pie_shard_table left."""
+        r, w, n, u, b = C.c_int32(0), C.c_int32(0), C.c_int64(0), C.c_int32(0), C.c_uint64(0)
+        self._check(self._lib.pie_shard_info(self._ctx, C.byref(r), C.byref(w), C.byref(n), C.byref(u), C.byref(b)))
+        return {"rank": r.value, "world": w.value, "rows_global": n.value, "users_global": u.value, "map_bytes": b.value}
+
+    def shard_append_rows(self, start, end, user_global, disc, n_users_global):
+        """The rows are rows [N_g, N_g + k) of the unsharded table, users as GLOBAL ids; this shard keeps the rows whose user
+        hashes to it.  -> (first global row, rows kept)"""
+        start, end = _col(start, np.int64), _col(end, np.int64)
+        user_global, disc = _col(user_global, np.int32), _col(disc, np.int32)
+        k = start.shape[0]
+        if not (end.shape[0] == user_global.shape[0] == disc.shape[0] == k):
+            raise ValueError("column lengths differ")
+        first, kept = C.c_int32(0), C.c_size_t(0)
+        self._check(self._lib.pie_shard_append_rows(self._ctx, _ptr(start), _ptr(end), _ptr(user_global), _ptr(disc), k, int(n_users_global),
+                                                    C.byref(first), C.byref(kept)))
+        ti = self.table_info()  # the shard's own rows and users, from the context (host state: nothing is waited for)
+        self.n, self.n_users = int(ti["rows"]), int(ti["users"])
+        return int(first.value), int(kept.value)
+
+    def shard_set_end(self, rows_global, new_end):
+        """end = new_end by GLOBAL row; rows this shard does not hold are skipped; repeats: the last element wins."""
+        rows_global, new_end = _col(rows_global, np.int32), _col(new_end, np.int64)
+        if rows_global.shape[0] != new_end.shape[0]:
+            raise ValueError("rows and values differ in length")
+        self._check(self._lib.pie_shard_set_end(self._ctx, _ptr(rows_global), _ptr(new_end), rows_global.shape[0]))
+
+    def shard_delete_user(self, user_global):
+        """-> ascending GLOBAL rows that were tombstoned (empty on a shard the user does not hash to)."""
+        k = C.c_size_t(0)
+        rows = np.empty(max(self.n, 1), np.int32)
+        self._check(self._lib.pie_shard_delete_user(self._ctx, int(user_global), _ptr(rows), self.n, C.byref(k)))
+        return rows[: k.value].copy()
+
+    def shard_rows_to_local(self, rows_global):
+        """Global rows -> this shard's local rows (-1: not held), as a new int32 array."""
+        rows = np.array(rows_global, dtype=np.int32, copy=True).reshape(-1)
+        self._check(self._lib.pie_shard_rows_to_local(self._ctx, _ptr(rows), rows.shape[0]))
+        return rows
+
+    def shard_rows_to_global(self, rows_local):
+        """Local rows -> global rows (-1: outside the map), as a new int32 array."""
+        rows = np.array(rows_local, dtype=np.int32, copy=True).reshape(-1)
+        self._check(self._lib.pie_shard_rows_to_global(self._ctx, _ptr(rows), rows.shape[0]))
+        return rows
+
     # ---- compaction on the device
     def compact_rows(self, dead_before=INT64_MIN, shrink=False):
         """Keep, in table order, the rows with end > dead_before (the default drops tombstones only); shrink: also re-size the
@@ -1044,6 +1104,38 @@ class PieComm:
         q = C.c_size_t(0)
         return self._queue(self._lib.pie_comm_archive_queue(self._c, int(now), int(window_ms), None, 0, C.byref(q)), sources)
 
+    # ---- a live sharded table (pie_comm_append_rows ...): GLOBAL ids, nothing exchanged
+    def table_size(self):
+        """-> (rows, users) of the whole table"""
+        n, u = C.c_int64(0), C.c_int32(0)
+        self._check(self._lib.pie_comm_table_size(self._c, C.byref(n), C.byref(u)))
+        return int(n.value), int(u.value)
+
+    def append_rows(self, start, end, user, disc, n_users):
+        """createSession on every local shard; -> the table's row count before the call (the first new global row)."""
+        start, end = _col(start, np.int64), _col(end, np.int64)
+        user, disc = _col(user, np.int32), _col(disc, np.int32)
+        k = start.shape[0]
+        if not (end.shape[0] == user.shape[0] == disc.shape[0] == k):
+            raise ValueError("column lengths differ")
+        first = C.c_int32(0)
+        self._check(self._lib.pie_comm_append_rows(self._c, _ptr(start), _ptr(end), _ptr(user), _ptr(disc), k, int(n_users), C.byref(first)))
+        return int(first.value)
+
+    def set_end(self, rows, new_end):
+        """touchSession / deleteSession by global row on every local shard."""
+        rows, new_end = _col(rows, np.int32), _col(new_end, np.int64)
+        if rows.shape[0] != new_end.shape[0]:
+            raise ValueError("rows and values differ in length")
+        self._check(self._lib.pie_comm_set_end(self._c, _ptr(rows), _ptr(new_end), rows.shape[0]))
+
+    def delete_user(self, user):
+        """deleteSessionsForUser by global id -> (ascending global rows tombstoned, owning rank or -1)."""
+        cap = max(self.table_size()[0], 1)
+        rows, k, owner = np.empty(cap, np.int32), C.c_size_t(0), C.c_int32(-1)
+        self._check(self._lib.pie_comm_delete_user(self._c, int(user), _ptr(rows), cap, C.byref(k), C.byref(owner)))
+        return rows[: k.value].copy(), int(owner.value)
+
     def queue_read(self, at_rank, sources=False):
         """The merged queue of the last queue call as local rank at_rank holds it."""
         q = C.c_size_t(0)
@@ -1091,6 +1183,26 @@ def split_wide_message(msg, u_pad, cap, words):
 
 def shard_of(user, n_shards):
     return load_library().pie_shard_of(int(user), int(n_shards))
+
+
+def shard_route(user_global, rank, world, users_before=0, users_after=0, cap=None):
+    """Host only (pie_shard_route): (keep uint8[k], new users int32[]) — which rows of an append rank `rank` of `world` keeps, and
+    the ascending ids in [users_before, users_after) that hash to it.  cap: room for the new users (default: all of them; a
+    smaller one raises PieError -5 whose .n_new holds the number)."""
+    user_global = _col(user_global, np.int32)
+    k = user_global.shape[0]
+    keep = np.empty(k, np.uint8)
+    n_kept, n_new = C.c_size_t(0), C.c_size_t(0)
+    room = max(int(users_after) - int(users_before), 0) if cap is None else int(cap)
+    new = np.empty(max(room, 1), np.int32)
+    rc = load_library().pie_shard_route(_ptr(user_global), k, int(rank), int(world), _ptr(keep), C.byref(n_kept), int(users_before),
+                                        int(users_after), _ptr(new), room, C.byref(n_new))
+    if rc != 0:
+        err = PieError(rc, "pie_shard_route: %s" % ("cap %d < %d new users" % (room, n_new.value) if rc == -5 else "bad argument"))
+        err.n_new = int(n_new.value)
+        raise err
+    assert int(keep.sum()) == n_kept.value
+    return keep, new[: n_new.value].copy()
 
 
 def set_end_last_writers(rows):

@@ -22,6 +22,12 @@
 #include <string>
 #include <vector>
 
+// pie_scan.hip: what pie_shard_append_rows / pie_shard_set_end would refuse, checked with nothing staged or changed
+namespace pie_internal {
+int shard_check_append(pie_ctx* c, const int32_t* user_global, size_t k, int32_t n_users_global);
+int shard_check_set_end(pie_ctx* c, const int32_t* rows_global, const int64_t* new_end, size_t k);
+} // namespace pie_internal
+
 namespace {
 
 // the slice of the RCCL API this file uses (signatures of /opt/rocm/include/rccl/rccl.h)
@@ -1094,6 +1100,84 @@ int pie_comm_queue_timing(pie_comm* c, float* ms_out_4)
     if (!c->q_timed) return cfail(c, PIE_E_STATE, "no completed queue call to time");
     PIE_CHIP(c, hipSetDevice(c->device[0]));
     for (int i = 0; i < 4; ++i) PIE_CHIP(c, hipEventElapsedTime(&ms_out_4[i], c->q_tev[i], c->q_tev[i + 1]));
+    return PIE_OK;
+}
+
+// ---- a live sharded table: the context-level calls by global id on every local shard, nothing exchanged
+
+namespace {
+// rows and users of the whole table, which every local shard must agree on
+int table_size(pie_comm* c, int64_t* rows_out, int32_t* users_out)
+{
+    int64_t rows = 0;
+    int32_t users = 0;
+    for (int k = 0; k < c->n_local; ++k) {
+        int64_t r = 0;
+        int32_t u = 0;
+        PIE_CCTX(c, k, pie_shard_info(c->ctx[k], nullptr, nullptr, &r, &u, nullptr));
+        if (k > 0 && (r != rows || u != users))
+            return cfail(c, PIE_E_STATE, "rank %d holds a table of %lld rows / %d users, rank %d one of %lld / %d", c->rank_of[k], (long long)r, u,
+                         c->rank_of[0], (long long)rows, users);
+        rows = r;
+        users = u;
+    }
+    if (rows_out) *rows_out = rows;
+    if (users_out) *users_out = users;
+    return PIE_OK;
+}
+
+int mutate_ready(pie_comm* c, int64_t* rows_out, int32_t* users_out)
+{
+    if (c->begun != c->collected) return cfail(c, PIE_E_STATE, "pipelined steps are in flight (pie_comm_step_*): collect them first");
+    if (c->w_begun != c->w_collected) return cfail(c, PIE_E_STATE, "wide steps are in flight (pie_comm_wide_step_*): collect them first");
+    return table_size(c, rows_out, users_out);
+}
+} // namespace
+
+int pie_comm_table_size(pie_comm* c, int64_t* rows_global_out, int32_t* users_global_out)
+{
+    if (!c) return PIE_E_INVAL;
+    return table_size(c, rows_global_out, users_global_out);
+}
+
+int pie_comm_append_rows(pie_comm* c, const int64_t* start, const int64_t* end, const int32_t* user, const int32_t* disc, size_t k, int32_t n_users,
+                         int32_t* first_row_out)
+{
+    if (!c) return PIE_E_INVAL;
+    if (k > 0 && (!start || !end || !user || !disc)) return cfail(c, PIE_E_INVAL, "NULL column pointer");
+    int64_t rows = 0;
+    int rc = mutate_ready(c, &rows, nullptr);
+    if (rc) return rc;
+    for (int i = 0; i < c->n_local; ++i) PIE_CCTX(c, i, pie_internal::shard_check_append(c->ctx[i], user, k, n_users));
+    if (first_row_out) *first_row_out = (int32_t)rows;
+    for (int i = 0; i < c->n_local; ++i) PIE_CCTX(c, i, pie_shard_append_rows(c->ctx[i], start, end, user, disc, k, n_users, nullptr, nullptr));
+    return PIE_OK;
+}
+
+int pie_comm_set_end(pie_comm* c, const int32_t* rows, const int64_t* new_end, size_t k)
+{
+    if (!c) return PIE_E_INVAL;
+    int rc = mutate_ready(c, nullptr, nullptr);
+    if (rc) return rc;
+    for (int i = 0; i < c->n_local; ++i) PIE_CCTX(c, i, pie_internal::shard_check_set_end(c->ctx[i], rows, new_end, k));
+    for (int i = 0; i < c->n_local; ++i) PIE_CCTX(c, i, pie_shard_set_end(c->ctx[i], rows, new_end, k));
+    return PIE_OK;
+}
+
+int pie_comm_delete_user(pie_comm* c, int32_t user, int32_t* rows_out, size_t cap, size_t* n_deleted, int32_t* owner_rank_out)
+{
+    if (!c) return PIE_E_INVAL;
+    if (n_deleted) *n_deleted = 0;
+    if (owner_rank_out) *owner_rank_out = -1;
+    int32_t users = 0;
+    int rc = mutate_ready(c, nullptr, &users);
+    if (rc) return rc;
+    if (user < 0 || user >= users) return PIE_OK;
+    const int owner = pie_shard_of(user, c->world);
+    if (owner_rank_out) *owner_rank_out = owner;
+    const int i = local_index(c, owner);
+    if (i < 0) return PIE_OK; // the owning rank lives in another process, which makes the same call
+    PIE_CCTX(c, i, pie_shard_delete_user(c->ctx[i], user, rows_out, cap, n_deleted));
     return PIE_OK;
 }
 

@@ -4838,4 +4838,106 @@ __global__ __launch_bounds__(256) void k_compact_translate(int* __restrict__ row
     }
 }
 
+// ------------------------------------------------------------------------------------------------ sharded mutators
+//
+// A sharded context (pie_shard_table) carries two ascending maps: local row -> global row and local user -> global user.  The
+// mutators that take GLOBAL ids stand in front of the ordinary ones: they find the local id by a lower-bound search of the
+// map and then do exactly what k_append_rows / k_set_end do for that local id.
+
+// first position of the ascending map[0, n) whose entry is >= x (n when there is none): reads map[0, n) only
+__device__ __forceinline__ long long shard_lower_bound(const int* __restrict__ map, long long n, int x)
+{
+    long long lo = 0, hi = n;
+    while (lo < hi) {
+        const long long mid = lo + (hi - lo) / 2;
+        if (map[mid] < x) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// pie_shard_append_rows: k_append_rows for a staging block [start k | end k | GLOBAL user k | disc k | global row k].  The user
+// is translated through users_map[0, n_map) and the local id written back into the staging block, which the ordered run's
+// append then reads as it reads pie_append_rows' block; rows_map[row0 + t] takes the row's global id.  An id the map does
+// not hold counts into *bad and is written as user 0 (the host has checked every id: this keeps a slip from reaching an
+// index).  key / fkey / pay may be NULL (the growth path: build_keys follows).
+__global__ __launch_bounds__(256) void k_shard_append_rows(const long long* __restrict__ st_start, const long long* __restrict__ st_end,
+                                                           int* __restrict__ st_user, const int* __restrict__ st_disc,
+                                                           const int* __restrict__ st_grow, long long k, long long row0,
+                                                           const int* __restrict__ users_map, int n_map, long long* __restrict__ start,
+                                                           long long* __restrict__ end, int* __restrict__ user, int* __restrict__ disc,
+                                                           int* __restrict__ rows_map, lkey_t* __restrict__ key, long long key_base,
+                                                           int key_shift, fkey_t* __restrict__ fkey, long long fkey_base, int fkey_shift,
+                                                           PayRec* __restrict__ pay, unsigned int* __restrict__ bad, HotMirror hot)
+{
+    unsigned int local = 0;
+    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < k; t += (long long)gridDim.x * blockDim.x) {
+        const long long r = row0 + t;
+        const long long sv = st_start[t], ev = st_end[t];
+        const int gu = st_user[t], dv = st_disc[t];
+        const long long p = shard_lower_bound(users_map, (long long)n_map, gu);
+        const bool found = p < (long long)n_map && users_map[p] == gu;
+        const int uv = found ? (int)p : 0;
+        local += found ? 0u : 1u;
+        st_user[t] = uv;
+        start[r] = sv;
+        end[r] = ev;
+        user[r] = uv;
+        disc[r] = dv;
+        rows_map[r] = st_grow[t];
+        const unsigned fk = key_of(ev, fkey_base, fkey_shift, kFineKeyMax);
+        if (key) key[r] = (lkey_t)key_of(ev, key_base, key_shift);
+        if (fkey) fkey[r] = (fkey_t)fk;
+        PayRec pr;
+        pr.start = sv;
+        pr.user = uv;
+        pr.disc = dv;
+        if (pay) pay[r] = pr;
+        hot_mirror_end(hot, r, ev, fk, &pr);
+    }
+    for (int o = 32; o > 0; o >>= 1) local += __shfl_xor(local, o, kWave);
+    if ((threadIdx.x & 63) == 0 && local) atomicAdd(bad, local);
+}
+
+// pie_shard_set_end: element t names GLOBAL row grows[t]; the shard that holds it (rows_map[0, n) ascends) does what k_set_end
+// does for the local row, every other shard nothing.  The host has left one element per row (set_end_last_writers).
+__global__ __launch_bounds__(256) void k_shard_set_end(long long* __restrict__ end, const int* __restrict__ grows,
+                                                       const long long* __restrict__ new_end, long long k,
+                                                       const int* __restrict__ rows_map, long long n, lkey_t* __restrict__ key,
+                                                       long long key_base, int key_shift, fkey_t* __restrict__ fkey, long long fkey_base,
+                                                       int fkey_shift, OrdMirror ord, HotMirror hot)
+{
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= k) return;
+    const int g = grows[t];
+    const long long r = shard_lower_bound(rows_map, n, g);
+    if (r >= n || rows_map[r] != g) return;
+    const long long e = new_end[t];
+    end[r] = e;
+    const unsigned kk = key_of(e, key_base, key_shift), fk = key_of(e, fkey_base, fkey_shift, kFineKeyMax);
+    if (key) key[r] = (lkey_t)kk;
+    if (fkey) fkey[r] = (fkey_t)fk;
+    ord_mirror_end(ord, r, e, kk, fk);
+    hot_mirror_end(hot, r, e, fk);
+}
+
+// k global rows -> local rows (-1: this shard does not hold the row)
+__global__ __launch_bounds__(256) void k_shard_rows_to_local(int* __restrict__ rows, long long k, const int* __restrict__ rows_map, long long n)
+{
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < k; i += (long long)gridDim.x * blockDim.x) {
+        const int g = rows[i];
+        const long long r = shard_lower_bound(rows_map, n, g);
+        rows[i] = (r < n && rows_map[r] == g) ? (int)r : -1;
+    }
+}
+
+// k local rows src[] -> global rows dst[] (-1: outside the map); src and dst may be the same array
+__global__ __launch_bounds__(256) void k_shard_rows_to_global(const int* src, int* dst, long long k, const int* __restrict__ rows_map, long long n)
+{
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < k; i += (long long)gridDim.x * blockDim.x) {
+        const int r = src[i];
+        dst[i] = (r >= 0 && (long long)r < n) ? rows_map[r] : -1;
+    }
+}
+
 } // namespace pie

@@ -85,6 +85,10 @@
     X(int, pie_comm_expired_queue, (pie_comm *, int64_t, int64_t, int32_t *, size_t, size_t *))                     \
     X(int, pie_comm_archive_queue, (pie_comm *, int64_t, int64_t, int32_t *, size_t, size_t *))                     \
     X(int, pie_comm_queue_read, (pie_comm *, int32_t, int32_t *, int32_t *, int32_t *, size_t, size_t *))            \
+    X(int, pie_comm_append_rows, (pie_comm *, const int64_t *, const int64_t *, const int32_t *, const int32_t *, size_t, int32_t, int32_t *)) \
+    X(int, pie_comm_set_end, (pie_comm *, const int32_t *, const int64_t *, size_t))                                 \
+    X(int, pie_comm_delete_user, (pie_comm *, int32_t, int32_t *, size_t, size_t *, int32_t *))                      \
+    X(int, pie_comm_table_size, (pie_comm *, int64_t *, int32_t *))                                                  \
     X(int, pie_shard_maps, (pie_ctx *, int32_t *, int32_t *))                                                       \
     X(int, pie_compact_rows, (pie_ctx *, int64_t, uint32_t, size_t *))                                              \
     X(int, pie_compact_maps, (pie_ctx *, int32_t *, int32_t *, size_t *, size_t *))                                 \
@@ -1524,6 +1528,88 @@ static napi_value comm_queue_call(napi_env env, napi_callback_info info, int arc
 static napi_value fn_comm_expired_queue(napi_env env, napi_callback_info info) { return comm_queue_call(env, info, 0); }
 static napi_value fn_comm_archive_queue(napi_env env, napi_callback_info info) { return comm_queue_call(env, info, 1); }
 
+/* ---- a live sharded table: createSession / touchSession / deleteSession / deleteSessionsForUser (server/sessionStore.js:12-19,
+ * 37-64) on every shard of the communicator, by GLOBAL row and user id (pie_comm_append_rows ...).  Nothing is kept here: the
+ * table's size lives in the library's contexts.
+ * commAppendRows(comm, start BigInt64Array, end BigInt64Array, user Int32Array, disc Int32Array, nUsers) -> first new global row
+ * commSetEnd(comm, rows Int32Array, newEnd BigInt64Array) -> elements
+ * commDeleteUser(comm, user, rowsOut Int32Array) -> {deleted, owner}: rowsOut receives the tombstoned global rows, ascending;
+ *   throws with .code = -5 when it is too short (the rows are tombstoned all the same); owner = -1 for an unknown id
+ * commTableSize(comm) -> {rows, users} of the whole table */
+static napi_value fn_comm_append_rows(napi_env env, napi_callback_info info)
+{
+    ARGS(6)
+    comm_box *cbx = get_comm_box(env, argv[0]); /* refuses while scanAsync runs on one of the shard contexts */
+    if (!cbx) return NULL;
+    size_t n0 = 0, n1 = 0, n2 = 0, n3 = 0;
+    int64_t *s = typed(env, argv[1], napi_bigint64_array, &n0), *e = typed(env, argv[2], napi_bigint64_array, &n1);
+    int32_t *u = typed(env, argv[3], napi_int32_array, &n2), *d = typed(env, argv[4], napi_int32_array, &n3);
+    int32_t n_users = 0, first = 0;
+    if (!s || !e || !u || !d || n0 != n1 || n0 != n2 || n0 != n3) {
+        napi_throw_type_error(env, NULL, "commAppendRows(comm, BigInt64Array start, BigInt64Array end, Int32Array user, Int32Array disc, nUsers): equal lengths");
+        return NULL;
+    }
+    CHECK(env, napi_get_value_int32(env, argv[5], &n_users));
+    int rc = p_pie_comm_append_rows(cbx->comm, s, e, u, d, n0, n_users, &first);
+    if (rc) return throw_comm(env, cbx->comm, rc);
+    return js_int(env, (int64_t)first);
+}
+
+static napi_value fn_comm_set_end(napi_env env, napi_callback_info info)
+{
+    ARGS(3)
+    comm_box *cbx = get_comm_box(env, argv[0]);
+    if (!cbx) return NULL;
+    size_t k = 0, k2 = 0;
+    int32_t *rows = typed(env, argv[1], napi_int32_array, &k);
+    int64_t *ne = typed(env, argv[2], napi_bigint64_array, &k2);
+    if (!rows || !ne || k != k2) {
+        napi_throw_type_error(env, NULL, "commSetEnd(comm, Int32Array rows, BigInt64Array newEnd)");
+        return NULL;
+    }
+    int rc = p_pie_comm_set_end(cbx->comm, rows, ne, k);
+    if (rc) return throw_comm(env, cbx->comm, rc);
+    return js_int(env, (int64_t)k);
+}
+
+static napi_value fn_comm_delete_user(napi_env env, napi_callback_info info)
+{
+    ARGS(3)
+    comm_box *cbx = get_comm_box(env, argv[0]);
+    if (!cbx) return NULL;
+    int32_t user = 0, owner = -1;
+    size_t cap = 0, k = 0;
+    CHECK(env, napi_get_value_int32(env, argv[1], &user));
+    int32_t *rows = typed(env, argv[2], napi_int32_array, &cap);
+    if (!rows) {
+        napi_throw_type_error(env, NULL, "commDeleteUser(comm, user, Int32Array rowsOut)");
+        return NULL;
+    }
+    int rc = p_pie_comm_delete_user(cbx->comm, user, rows, cap, &k, &owner);
+    if (rc) return throw_comm(env, cbx->comm, rc);
+    napi_value out;
+    CHECK(env, napi_create_object(env, &out));
+    napi_set_named_property(env, out, "deleted", js_int(env, (int64_t)k));
+    napi_set_named_property(env, out, "owner", js_int(env, (int64_t)owner));
+    return out;
+}
+
+static napi_value fn_comm_table_size(napi_env env, napi_callback_info info)
+{
+    ARGS(1)
+    pie_comm *cm = get_comm(env, argv[0]);
+    if (!cm) return NULL;
+    int64_t rows = 0;
+    int32_t users = 0;
+    int rc = p_pie_comm_table_size(cm, &rows, &users);
+    if (rc) return throw_comm(env, cm, rc);
+    napi_value out;
+    CHECK(env, napi_create_object(env, &out));
+    napi_set_named_property(env, out, "rows", js_int(env, rows));
+    napi_set_named_property(env, out, "users", js_int(env, (int64_t)users));
+    return out;
+}
+
 /* shardMaps(ctx, rowsOut Int32Array[>= rows], usersOut Int32Array[>= users]) -> rows: a shard's local row -> global row and
  * local user -> global user (pie_shard_maps) */
 static napi_value fn_shard_maps(napi_env env, napi_callback_info info)
@@ -1946,6 +2032,7 @@ static napi_value init(napi_env env, napi_value exports)
         {"commStepUPad", fn_comm_step_upad}, {"commWideStepReserve", fn_comm_wide_step_reserve}, {"commWideStepBegin", fn_comm_wide_step_begin},
         {"commWideStepFinish", fn_comm_wide_step_finish}, {"commWideStepCollect", fn_comm_wide_step_collect},
         {"commWideStepStatus", fn_comm_wide_step_status}, {"commWideStepReadGathered", fn_comm_wide_step_read}, {"commExpiredQueue", fn_comm_expired_queue}, {"commArchiveQueue", fn_comm_archive_queue},
+        {"commAppendRows", fn_comm_append_rows}, {"commSetEnd", fn_comm_set_end}, {"commDeleteUser", fn_comm_delete_user}, {"commTableSize", fn_comm_table_size},
         {"shardMaps", fn_shard_maps},
     };
     for (size_t i = 0; i < sizeof table / sizeof table[0]; ++i) {

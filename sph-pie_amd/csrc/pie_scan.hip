@@ -301,6 +301,17 @@ struct pie_ctx {
     int* d_shard_users = nullptr;  // ... local user -> global user
     long long shard_rows_n = 0;
     int shard_users_n = 0;
+    // What pie_shard_table knew, for the mutators that take global ids (pie_shard_append_rows ...): the shard's place, the size of
+    // the WHOLE table (rows and users ever handed out: N_g, U_g), the room of the two device maps (entries; they grow with
+    // cap_rows / cap_users) and a host copy of the user map (4 B per local user; the row map has none).  A new table forgets it.
+    bool shard_on = false;
+    int shard_rank = 0, shard_world = 1;
+    long long shard_rows_global = 0;
+    int shard_users_global = 0;
+    long long shard_rows_cap = 0;
+    int shard_users_cap = 0;
+    std::vector<int32_t> shard_users_h;
+    std::vector<uint8_t> shard_keep;     // pie_shard_append_rows: which rows of the call this shard keeps; sized by the call
     // pie_compact_rows: the maps of the last compaction (old row -> new row or -1, new row -> old row), until rows are renumbered again
     int* d_cmp_new_of_old = nullptr;
     int* d_cmp_old_of_new = nullptr;
@@ -807,6 +818,7 @@ int ensure_capacity(pie_ctx* c, long long n, int n_users, long long keep_rows = 
     if (rc) return rc;
     ord_invalidate(c, keep_rows == 0);
     if (keep_rows == 0) cmp_forget(c); // a new table (load, gen, shard, compact) renumbers the rows: the last compaction's maps go
+    if (keep_rows == 0) c->shard_on = false; // ... and it is no shard of anything until pie_shard_table says so (pie_compact_rows restores it)
     long long rows = n > 0 ? n : 1;
     if (rows > c->cap_rows || n_users > c->cap_users) {
         int users = n_users;
@@ -3720,6 +3732,61 @@ int pie_load_columns(pie_ctx* c, const int64_t* start, const int64_t* end, const
     return build_keys(c, 0);
 }
 
+// What follows the append kernel of the in-place path, shared by pie_append_rows and pie_shard_append_rows (n_users: the
+// context's own, local, user count after the call).  Queued form: nothing is read back, the table's size moves at once.
+static int append_queued_tail(pie_ctx* c, pie_ctx::AsyncStage* a, long long old_n, size_t k, int n_users)
+{
+    PIE_HIP(c, hipGetLastError());
+    PIE_HIP(c, hipEventRecord(a->ev, c->stream));
+    a->pending = true;
+    c->n = old_n + (long long)k;
+    ord_invalidate(c);
+    if (n_users > c->n_users) set_user_count(c, n_users);
+    c->key_dirty = true;
+    c->res = nullptr;
+    for (Slot& sl : c->slot) sl.have_result = false;
+    c->bres = nullptr;
+    plan_k1(c);
+    return ensure_sel(c);
+}
+
+// Waited form: the kernel's count of bad user ids and the ordered run's bookkeeping are read once the stream has drained.
+static int append_waited_tail(pie_ctx* c, hipStream_t s, long long old_n, size_t k, int n_users, bool ord_kept, bool global_ids = false)
+{
+    PIE_HIP(c, hipGetLastError());
+    PIE_HIP(c, hipMemcpyAsync(c->h_summary, c->d_summary, sizeof(Summary), hipMemcpyDeviceToHost, s));
+    PIE_HIP(c, hipStreamSynchronize(s));
+    if (c->h_summary->bad_rows) { // the rows were written beyond n: the table itself is unchanged (the hot index is not)
+        c->hix.valid = false;
+        if (ord_kept) { // ... but some of them may sit in the run's spare slots
+            ord_invalidate(c);
+            c->ord.h_stale[0] = c->ord.h_stale[1] = 0;
+        }
+        if (global_ids) return fail(c, PIE_E_INVAL, "%u rows carry a user id the shard's user map does not hold", c->h_summary->bad_rows);
+        return fail(c, PIE_E_INVAL, "%u rows carry a user id outside [0, %d)", c->h_summary->bad_rows, n_users);
+    }
+    c->n = old_n + (long long)k;
+    if (ord_kept) {
+        volatile unsigned int* st = c->ord.h_stale; // [0] rows out of time order, [1] rows whose segment was full
+        if (st[0] == 0 && st[1] != 0) {
+            int rc2 = ord_respread(c, k, old_n, n_users);
+            if (rc2) return rc2;
+        } else if (st[0] != 0) ord_invalidate(c, false, true);
+        c->ord.h_stale[0] = c->ord.h_stale[1] = 0;
+        if (c->ord.valid) {
+            c->ord.rows = c->n;
+            c->ord.held += (long long)k;
+        }
+    } else ord_invalidate(c);
+    if (n_users > c->n_users) set_user_count(c, n_users);
+    c->key_dirty = true;
+    c->res = nullptr;
+    for (Slot& sl : c->slot) sl.have_result = false;
+    c->bres = nullptr;
+    plan_k1(c);
+    return ensure_sel(c);
+}
+
 int pie_append_rows(pie_ctx* c, const int64_t* start, const int64_t* end, const int32_t* user, const int32_t* disc,
                     size_t k, int32_t n_users)
 {
@@ -3755,18 +3822,7 @@ int pie_append_rows(pie_ctx* c, const int64_t* start, const int64_t* end, const 
                                reinterpret_cast<const int*>(a->d + k * 20), (long long)k, old_n, n_users, c->d_start, c->d_end, c->d_user,
                                c->d_disc, c->d_key, c->key_base, c->key_shift, c->d_fkey, c->fkey_base, c->fkey_shift, c->d_pay,
                                &c->d_summary->bad_rows, hot_mirror_of(c));
-            PIE_HIP(c, hipGetLastError());
-            PIE_HIP(c, hipEventRecord(a->ev, s));
-            a->pending = true;
-            c->n = old_n + (long long)k;
-            ord_invalidate(c);
-            if (n_users > c->n_users) set_user_count(c, n_users);
-            c->key_dirty = true;
-            c->res = nullptr;
-            for (Slot& sl : c->slot) sl.have_result = false;
-            c->bres = nullptr;
-            plan_k1(c);
-            return ensure_sel(c);
+            return append_queued_tail(c, a, old_n, k, n_users);
         }
         int rc0 = ensure_stage(c, k * 24 + 64);
         if (rc0) return rc0;
@@ -3790,37 +3846,7 @@ int pie_append_rows(pie_ctx* c, const int64_t* start, const int64_t* end, const 
             launch_ord_append(c, s, k, old_n, n_users, 1); // pend[] is all zero between appends (build and re-spread leave it so)
             ord_kept = true;
         }
-        PIE_HIP(c, hipGetLastError());
-        PIE_HIP(c, hipMemcpyAsync(c->h_summary, c->d_summary, sizeof(Summary), hipMemcpyDeviceToHost, s));
-        PIE_HIP(c, hipStreamSynchronize(s));
-        if (c->h_summary->bad_rows) { // the rows were written beyond n: the table itself is unchanged (the hot index is not)
-            c->hix.valid = false;
-            if (ord_kept) { // ... but some of them may sit in the run's spare slots
-                ord_invalidate(c);
-                c->ord.h_stale[0] = c->ord.h_stale[1] = 0;
-            }
-            return fail(c, PIE_E_INVAL, "%u rows carry a user id outside [0, %d)", c->h_summary->bad_rows, n_users);
-        }
-        c->n = old_n + (long long)k;
-        if (ord_kept) {
-            volatile unsigned int* st = c->ord.h_stale; // [0] rows out of time order, [1] rows whose segment was full
-            if (st[0] == 0 && st[1] != 0) {
-                int rc2 = ord_respread(c, k, old_n, n_users);
-                if (rc2) return rc2;
-            } else if (st[0] != 0) ord_invalidate(c, false, true);
-            c->ord.h_stale[0] = c->ord.h_stale[1] = 0;
-            if (c->ord.valid) {
-                c->ord.rows = c->n;
-                c->ord.held += (long long)k;
-            }
-        } else ord_invalidate(c);
-        if (n_users > c->n_users) set_user_count(c, n_users);
-        c->key_dirty = true;
-        c->res = nullptr;
-        for (Slot& sl : c->slot) sl.have_result = false;
-        c->bres = nullptr;
-        plan_k1(c);
-        return ensure_sel(c);
+        return append_waited_tail(c, s, old_n, k, n_users, ord_kept);
     }
     int rc = ensure_capacity(c, old_n + (long long)k, n_users, old_n > 0 ? old_n : 1);
     if (rc) return rc;
@@ -5410,6 +5436,23 @@ int pie_shard_table(pie_ctx* c, int32_t rank, int32_t world, size_t* n_rows_out,
     c->d_shard_users = d_users;
     c->shard_rows_n = n_local;
     c->shard_users_n = (int)u_local;
+    c->shard_rows_cap = (long long)rows;
+    c->shard_users_cap = U;
+    c->shard_rank = rank;
+    c->shard_world = world;
+    c->shard_rows_global = n;
+    c->shard_users_global = U;
+    c->shard_on = false;
+    try {
+        c->shard_users_h.assign((size_t)u_local, 0);
+    } catch (...) {
+        return fail(c, PIE_E_NOMEM, "no memory for the user map of %lld users", u_local);
+    }
+    if (u_local > 0) {
+        PIE_HIP(c, hipMemcpyAsync(c->shard_users_h.data(), d_users, (size_t)u_local * 4, hipMemcpyDeviceToHost, s));
+        PIE_HIP(c, hipStreamSynchronize(s));
+    }
+    c->shard_on = true;
     if (n_rows_out) *n_rows_out = (size_t)n_local;
     if (n_users_out) *n_users_out = users_new;
     rc = build_keys(c, 0);
@@ -5430,6 +5473,430 @@ int pie_shard_maps(pie_ctx* c, int32_t* rows_global_out, int32_t* users_global_o
     PIE_HIP(c, hipStreamSynchronize(c->stream));
     return PIE_OK;
 }
+
+// ---- mutators by GLOBAL id on a sharded context (createSession / touchSession / deleteSession / deleteSessionsForUser,
+// server/sessionStore.js:12-19,37-64, on the sharded form of the table).  Every shard is given the same call and keeps what is
+// its own; nothing is exchanged.  The context stays in step with the unsharded table: its row map ascends and covers every
+// local row, its user map is the ascending list of all global ids that hash to the rank (new ids are larger than all earlier
+// ones, so both maps only ever grow at their ends and no local id moves).
+
+static int shard_ready(pie_ctx* c, const char* what)
+{
+    if (!c->shard_on || !c->d_shard_rows || !c->d_shard_users)
+        return fail(c, PIE_E_STATE, "%s: the context holds no sharded table (pie_shard_table)", what);
+    if (c->n != c->shard_rows_n)
+        return fail(c, PIE_E_STATE, "%s: %lld rows were added after pie_shard_table: they have no global row", what, c->n - c->shard_rows_n);
+    if (c->n_flight || c->b_flight) return fail(c, PIE_E_STATE, "%s while a scan is in flight", what);
+    return PIE_OK;
+}
+
+// Both device maps as large as the table's capacity (they grow with it, geometrically as it does).  The copy is waited for: an
+// earlier queued touch may still read the old map, and this happens once per growth of the table.
+static int shard_maps_reserve(pie_ctx* c, long long rows, long long users)
+{
+    hipStream_t s = c->stream;
+    if (rows > c->shard_rows_cap) {
+        int* p = nullptr;
+        PIE_HIP(c, hipMalloc(&p, (size_t)rows * 4));
+        hipError_t e = c->shard_rows_n ? hipMemcpyAsync(p, c->d_shard_rows, (size_t)c->shard_rows_n * 4, hipMemcpyDeviceToDevice, s) : hipSuccess;
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) { (void)hipFree(p); return fail(c, PIE_E_HIP, "row map growth: %s", hipGetErrorString(e)); }
+        dfree(c->d_shard_rows);
+        c->d_shard_rows = p;
+        c->shard_rows_cap = rows;
+    }
+    if (users > c->shard_users_cap) {
+        int* p = nullptr;
+        PIE_HIP(c, hipMalloc(&p, (size_t)users * 4));
+        hipError_t e = c->shard_users_n ? hipMemcpyAsync(p, c->d_shard_users, (size_t)c->shard_users_n * 4, hipMemcpyDeviceToDevice, s) : hipSuccess;
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) { (void)hipFree(p); return fail(c, PIE_E_HIP, "user map growth: %s", hipGetErrorString(e)); }
+        dfree(c->d_shard_users);
+        c->d_shard_users = p;
+        c->shard_users_cap = (int)users;
+    }
+    return PIE_OK;
+}
+
+static size_t shard_route_rows(const int32_t* user_global, size_t k, int32_t rank, int32_t world, uint8_t* keep)
+{
+    size_t n_kept = 0;
+    for (size_t i = 0; i < k; ++i) {
+        keep[i] = pie_shard_of(user_global[i], world) == rank ? 1 : 0;
+        n_kept += keep[i];
+    }
+    return n_kept;
+}
+
+int pie_shard_route(const int32_t* user_global, size_t k, int32_t rank, int32_t world, uint8_t* keep_out, size_t* n_kept_out,
+                    int32_t users_before, int32_t users_after, int32_t* new_users_out, size_t cap, size_t* n_new_out)
+{
+    if (n_kept_out) *n_kept_out = 0;
+    if (n_new_out) *n_new_out = 0;
+    if (world < 1 || rank < 0 || rank >= world || users_before < 0) return PIE_E_INVAL;
+    if (k && (!user_global || !keep_out)) return PIE_E_INVAL;
+    const size_t n_kept = shard_route_rows(user_global, k, rank, world, keep_out);
+    if (n_kept_out) *n_kept_out = n_kept;
+    size_t n_new = 0;
+    for (int32_t u = users_before; u < users_after; ++u)
+        if (pie_shard_of(u, world) == rank) {
+            if (new_users_out && n_new < cap) new_users_out[n_new] = u;
+            ++n_new;
+        }
+    if (n_new_out) *n_new_out = n_new;
+    return n_new > cap ? PIE_E_CAPACITY : PIE_OK;
+}
+
+int pie_shard_info(pie_ctx* c, int32_t* rank_out, int32_t* world_out, int64_t* rows_global_out, int32_t* users_global_out, uint64_t* map_bytes_out)
+{
+    if (!c) return PIE_E_INVAL;
+    if (!c->shard_on) return fail(c, PIE_E_STATE, "pie_shard_info: the context holds no sharded table (pie_shard_table)");
+    if (rank_out) *rank_out = c->shard_rank;
+    if (world_out) *world_out = c->shard_world;
+    if (rows_global_out) *rows_global_out = c->shard_rows_global;
+    if (users_global_out) *users_global_out = c->shard_users_global;
+    if (map_bytes_out) *map_bytes_out = ((uint64_t)c->shard_rows_cap + (uint64_t)c->shard_users_cap) * 4u;
+    return PIE_OK;
+}
+
+} // extern "C"
+
+// What the calls below refuse, checked without staging or changing anything: the communicator asks every local shard first,
+// so that a refused call changes none of them.
+namespace pie_internal {
+int shard_check_append(pie_ctx* c, const int32_t* user_global, size_t k, int32_t n_users_global)
+{
+    if (!c) return PIE_E_INVAL;
+    int rc = shard_ready(c, "pie_shard_append_rows");
+    if (rc) return rc;
+    if (k > 0 && !user_global) return fail(c, PIE_E_INVAL, "NULL column pointer");
+    if (n_users_global < c->shard_users_global)
+        return fail(c, PIE_E_INVAL, "n_users_global may only grow (%d < %d)", n_users_global, c->shard_users_global);
+    if (c->shard_rows_global + (long long)k >= (1LL << 31) - 1 || k >= ((size_t)1 << 31))
+        return fail(c, PIE_E_INVAL, "global row count outside [0, 2^31 - 1)");
+    for (size_t i = 0; i < k; ++i)
+        if ((uint32_t)user_global[i] >= (uint32_t)n_users_global)
+            return fail(c, PIE_E_INVAL, "row %zu carries a user id outside [0, %d)", i, n_users_global);
+    return PIE_OK;
+}
+
+int shard_check_set_end(pie_ctx* c, const int32_t* rows_global, const int64_t* new_end, size_t k)
+{
+    if (!c) return PIE_E_INVAL;
+    int rc = shard_ready(c, "pie_shard_set_end");
+    if (rc) return rc;
+    if (k > 0 && (!rows_global || !new_end)) return fail(c, PIE_E_INVAL, "NULL pointer");
+    for (size_t i = 0; i < k; ++i)
+        if (rows_global[i] < 0 || (long long)rows_global[i] >= c->shard_rows_global)
+            return fail(c, PIE_E_INVAL, "global row %d outside [0, %lld)", rows_global[i], c->shard_rows_global);
+    return PIE_OK;
+}
+} // namespace pie_internal
+
+extern "C" {
+
+// the staging block of an append: [start kept | end kept | GLOBAL user kept | disc kept | global row kept | new users]
+static void shard_append_stage(char* h, const int64_t* start, const int64_t* end, const int32_t* user_global, const int32_t* disc, size_t k,
+                               const uint8_t* keep, size_t n_kept, long long first_row, int32_t users_before, int32_t users_after,
+                               int32_t rank, int32_t world)
+{
+    int64_t* hs = reinterpret_cast<int64_t*>(h);
+    int64_t* he = reinterpret_cast<int64_t*>(h + n_kept * 8);
+    int32_t* hu = reinterpret_cast<int32_t*>(h + n_kept * 16);
+    int32_t* hd = reinterpret_cast<int32_t*>(h + n_kept * 20);
+    int32_t* hg = reinterpret_cast<int32_t*>(h + n_kept * 24);
+    int32_t* hn = reinterpret_cast<int32_t*>(h + n_kept * 28);
+    size_t j = 0;
+    for (size_t i = 0; i < k; ++i)
+        if (keep[i]) {
+            hs[j] = start[i];
+            he[j] = end[i];
+            hu[j] = user_global[i];
+            hd[j] = disc[i];
+            hg[j] = (int32_t)(first_row + (long long)i);
+            ++j;
+        }
+    j = 0;
+    for (int32_t u = users_before; u < users_after; ++u)
+        if (pie_shard_of(u, world) == rank) hn[j++] = u;
+}
+
+// upload the block, extend the device user map by the new users, run the kernel on rows [old_n, old_n + n_kept)
+static int shard_append_launch(pie_ctx* c, char* h, char* d, size_t n_kept, size_t n_new, long long old_n, bool with_keys)
+{
+    hipStream_t s = c->stream;
+    PIE_HIP(c, hipMemcpyAsync(d, h, n_kept * 28 + n_new * 4, hipMemcpyHostToDevice, s));
+    if (n_new)
+        PIE_HIP(c, hipMemcpyAsync(c->d_shard_users + c->shard_users_n, d + n_kept * 28, n_new * 4, hipMemcpyDeviceToDevice, s));
+    if (n_kept == 0) return PIE_OK;
+    const unsigned grid = (unsigned)((n_kept + 255) / 256) < (unsigned)c->n_cus * 8 ? (unsigned)((n_kept + 255) / 256) : (unsigned)c->n_cus * 8;
+    hipLaunchKernelGGL(k_shard_append_rows, dim3(grid), dim3(256), 0, s, reinterpret_cast<const long long*>(d),
+                       reinterpret_cast<const long long*>(d + n_kept * 8), reinterpret_cast<int*>(d + n_kept * 16),
+                       reinterpret_cast<const int*>(d + n_kept * 20), reinterpret_cast<const int*>(d + n_kept * 24), (long long)n_kept, old_n,
+                       (const int*)c->d_shard_users, c->shard_users_n + (int)n_new, c->d_start, c->d_end, c->d_user, c->d_disc, c->d_shard_rows,
+                       with_keys ? c->d_key : (lkey_t*)nullptr, c->key_base, c->key_shift, with_keys ? c->d_fkey : (fkey_t*)nullptr, c->fkey_base,
+                       c->fkey_shift, with_keys ? c->d_pay : (PayRec*)nullptr, &c->d_summary->bad_rows, with_keys ? hot_mirror_of(c) : HotMirror{});
+    PIE_HIP(c, hipGetLastError());
+    return PIE_OK;
+}
+
+// The kernel is queued: the maps cover rows [0, old_n + n_kept) and the new users, the whole table is k rows longer.  This
+// stands BEFORE the steps that move c->n and can still fail late (the ordered run's re-spread, the staging arrays, the key
+// build), so that c->n and the map never part; a step that fails with c->n unmoved takes it back (shard_append_undo).
+struct ShardUndo {
+    long long rows_n, rows_global;
+    int users_n, users_global;
+    size_t users_h;
+};
+static int shard_append_commit(pie_ctx* c, const char* h, long long old_n, size_t n_kept, size_t n_new, size_t k, int32_t n_users_global,
+                               ShardUndo* u)
+{
+    const int32_t* hn = reinterpret_cast<const int32_t*>(h + n_kept * 28);
+    *u = ShardUndo{c->shard_rows_n, c->shard_rows_global, c->shard_users_n, c->shard_users_global, c->shard_users_h.size()};
+    try {
+        c->shard_users_h.insert(c->shard_users_h.end(), hn, hn + n_new);
+    } catch (...) {
+        return fail(c, PIE_E_NOMEM, "no memory for the user map");
+    }
+    c->shard_rows_n = old_n + (long long)n_kept;
+    c->shard_users_n += (int)n_new;
+    c->shard_rows_global += (long long)k;
+    c->shard_users_global = n_users_global;
+    return PIE_OK;
+}
+static void shard_append_undo(pie_ctx* c, const ShardUndo& u)
+{
+    c->shard_rows_n = u.rows_n;
+    c->shard_rows_global = u.rows_global;
+    c->shard_users_n = u.users_n;
+    c->shard_users_global = u.users_global;
+    c->shard_users_h.resize(u.users_h);
+}
+
+int pie_shard_append_rows(pie_ctx* c, const int64_t* start, const int64_t* end, const int32_t* user_global, const int32_t* disc,
+                          size_t k, int32_t n_users_global, int32_t* first_row_out, size_t* n_kept_out)
+{
+    if (!c) return PIE_E_INVAL;
+    if (n_kept_out) *n_kept_out = 0;
+    if (k > 0 && (!start || !end || !user_global || !disc)) return fail(c, PIE_E_INVAL, "NULL column pointer");
+    int rc = pie_internal::shard_check_append(c, user_global, k, n_users_global);
+    if (rc) return rc;
+    PIE_HIP(c, hipSetDevice(c->device));
+    const int32_t rank = c->shard_rank, world = c->shard_world, users_before = c->shard_users_global;
+    const long long first_row = c->shard_rows_global, old_n = c->n;
+    if (first_row_out) *first_row_out = (int32_t)first_row;
+    // the host routes: pure arithmetic, so the number of rows kept is known with nothing read back
+    try {
+        c->shard_keep.resize(k);
+    } catch (...) {
+        return fail(c, PIE_E_NOMEM, "no memory for %zu rows", k);
+    }
+    const uint8_t* keep = c->shard_keep.data();
+    const size_t n_kept = shard_route_rows(user_global, k, rank, world, c->shard_keep.data());
+    size_t n_new = 0;
+    for (int32_t u = users_before; u < n_users_global; ++u) n_new += pie_shard_of(u, world) == rank ? 1 : 0;
+    if (n_kept_out) *n_kept_out = n_kept;
+    const long long users_after = (long long)c->shard_users_n + (long long)n_new;
+    const int local_users = users_after > 0 ? (int)users_after : 1; // a shard with no user keeps n_users = 1
+    if (n_kept == 0 && n_new == 0) { // nothing of this call is this shard's: the whole table still grew
+        c->shard_rows_global += (long long)k;
+        c->shard_users_global = n_users_global;
+        return PIE_OK;
+    }
+    const size_t bytes = n_kept * 28 + n_new * 4 + 64;
+    ShardUndo undo{};
+    if (n_kept == 0 && local_users <= c->cap_users) {
+        // only the user map grows: the new ids go behind it in stream order; no row, no key, nothing to wait for
+        rc = shard_maps_reserve(c, c->cap_rows, c->cap_users);
+        if (rc) return rc;
+        pie_ctx::AsyncStage* a = nullptr;
+        rc = async_stage(c, bytes, &a);
+        if (rc) return rc;
+        shard_append_stage(a->h, start, end, user_global, disc, k, keep, 0, first_row, users_before, n_users_global, rank, world);
+        rc = shard_append_launch(c, a->h, a->d, 0, n_new, old_n, true);
+        if (rc) return rc;
+        PIE_HIP(c, hipEventRecord(a->ev, c->stream));
+        a->pending = true;
+        rc = shard_append_commit(c, a->h, old_n, 0, n_new, k, n_users_global, &undo);
+        if (rc) return rc;
+        if (local_users > c->n_users) { // as an in-place append that brings users and no row would leave the context
+            if (c->ord.valid && local_users > c->ord.users) ord_invalidate(c);
+            set_user_count(c, local_users);
+            c->res = nullptr;
+            for (Slot& sl : c->slot) sl.have_result = false;
+            c->bres = nullptr;
+        }
+        if (!c->async_mutations) PIE_HIP(c, hipStreamSynchronize(c->stream));
+        return PIE_OK;
+    }
+    if (n_kept > 0 && old_n > 0 && old_n + (long long)n_kept <= c->cap_rows && local_users <= c->cap_users && c->key_ok && n_kept <= ((size_t)1 << 24)) {
+        // in place, as pie_append_rows: one staged upload, one kernel, and no wait where pie_append_rows has none
+        rc = shard_maps_reserve(c, c->cap_rows, c->cap_users);
+        if (rc) return rc;
+        hot_reserve(c, (long long)n_kept);
+        if (c->async_mutations && !c->ord.valid) {
+            pie_ctx::AsyncStage* a = nullptr;
+            rc = async_stage(c, bytes, &a);
+            if (rc) return rc;
+            shard_append_stage(a->h, start, end, user_global, disc, k, keep, n_kept, first_row, users_before, n_users_global, rank, world);
+            rc = shard_append_launch(c, a->h, a->d, n_kept, n_new, old_n, true);
+            if (rc) return rc;
+            rc = shard_append_commit(c, a->h, old_n, n_kept, n_new, k, n_users_global, &undo);
+            if (rc) { c->hix.valid = false; return rc; } // the kernel fed the hot index rows the table will not hold
+            rc = append_queued_tail(c, a, old_n, n_kept, local_users);
+            if (rc && c->n == old_n) shard_append_undo(c, undo);
+            return rc;
+        }
+        rc = ensure_stage(c, bytes);
+        if (rc) return rc;
+        hipStream_t s = c->stream;
+        shard_append_stage(c->h_stage, start, end, user_global, disc, k, keep, n_kept, first_row, users_before, n_users_global, rank, world);
+        PIE_HIP(c, hipMemsetAsync(&c->d_summary->bad_rows, 0, sizeof(unsigned int), s));
+        rc = shard_append_launch(c, c->h_stage, c->d_stage, n_kept, n_new, old_n, true);
+        if (rc) return rc;
+        // the kernel left LOCAL user ids in the block: the ordered run takes the rows as it takes pie_append_rows' rows
+        bool ord_kept = false;
+        if (c->ord.valid && c->ord.rows == old_n && n_kept <= (size_t)kOrdAppendMax && local_users <= c->ord.users && c->key_ok) {
+            launch_ord_append(c, s, n_kept, old_n, local_users, 1);
+            ord_kept = true;
+        }
+        rc = shard_append_commit(c, c->h_stage, old_n, n_kept, n_new, k, n_users_global, &undo);
+        if (rc) { // the kernels fed the hot index and the run rows the table will not hold
+            c->hix.valid = false;
+            if (ord_kept) ord_invalidate(c);
+            return rc;
+        }
+        rc = append_waited_tail(c, s, old_n, n_kept, local_users, ord_kept, true);
+        if (rc && c->n == old_n) shard_append_undo(c, undo);
+        return rc;
+    }
+    // growth path, as pie_append_rows: a larger table first (the maps with it), the rows behind the resident ones, then the keys
+    rc = ensure_capacity(c, old_n + (long long)n_kept, local_users, old_n > 0 ? old_n : 1);
+    if (rc == PIE_OK) rc = shard_maps_reserve(c, c->cap_rows, c->cap_users);
+    if (rc == PIE_OK) rc = ensure_stage(c, bytes);
+    if (rc) { c->n = old_n; plan_k1(c); return rc; }
+    hipStream_t s = c->stream;
+    shard_append_stage(c->h_stage, start, end, user_global, disc, k, keep, n_kept, first_row, users_before, n_users_global, rank, world);
+    PIE_HIP(c, hipMemsetAsync(&c->d_summary->bad_rows, 0, sizeof(unsigned int), s));
+    rc = shard_append_launch(c, c->h_stage, c->d_stage, n_kept, n_new, old_n, false);
+    if (rc) { c->n = old_n; plan_k1(c); return rc; }
+    PIE_HIP(c, hipMemcpyAsync(c->h_summary, c->d_summary, sizeof(Summary), hipMemcpyDeviceToHost, s));
+    PIE_HIP(c, hipStreamSynchronize(s));
+    if (c->h_summary->bad_rows) {
+        c->n = old_n;
+        plan_k1(c);
+        return fail(c, PIE_E_INVAL, "%u rows carry a user id the shard's user map does not hold", c->h_summary->bad_rows);
+    }
+    rc = shard_append_commit(c, c->h_stage, old_n, n_kept, n_new, k, n_users_global, &undo);
+    if (rc) { c->n = old_n; plan_k1(c); return rc; }
+    return build_keys(c, old_n); // c->n and the map already agree, whatever this returns
+}
+
+int pie_shard_set_end(pie_ctx* c, const int32_t* rows_global, const int64_t* new_end, size_t k_given)
+{
+    if (!c) return PIE_E_INVAL;
+    int rc = pie_internal::shard_check_set_end(c, rows_global, new_end, k_given);
+    if (rc) return rc;
+    if (k_given == 0) return PIE_OK;
+    // equal global rows are equal local rows: the repeats are resolved over the global ids, as pie_set_end resolves them
+    try {
+        c->set_end_keep.resize(k_given);
+    } catch (...) {
+        return fail(c, PIE_E_NOMEM, "no memory for %zu touches", k_given);
+    }
+    const uint8_t* keep = c->set_end_keep.data();
+    if (!set_end_last_writers(rows_global, k_given, c->set_end_keep.data(), c->set_end_slots)) return fail(c, PIE_E_NOMEM, "no memory for %zu touches", k_given);
+    size_t k = 0;
+    for (size_t i = 0; i < k_given; ++i) k += keep[i];
+    PIE_HIP(c, hipSetDevice(c->device));
+    hot_reserve(c, (long long)k_given);
+    hipStream_t s = c->stream;
+    const unsigned grid = (unsigned)((k + 255) / 256);
+    if (c->async_mutations && !c->ord.valid) {
+        pie_ctx::AsyncStage* a = nullptr;
+        rc = async_stage(c, k * 12 + 64, &a);
+        if (rc) return rc;
+        set_end_stage(a->h, rows_global, new_end, k_given, keep, k);
+        PIE_HIP(c, hipMemcpyAsync(a->d, a->h, k * 12, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_shard_set_end, dim3(grid), dim3(256), 0, s, c->d_end, reinterpret_cast<const int*>(a->d + k * 8),
+                           reinterpret_cast<const long long*>(a->d), (long long)k, (const int*)c->d_shard_rows, c->n, c->d_key, c->key_base,
+                           c->key_shift, c->d_fkey, c->fkey_base, c->fkey_shift, ord_mirror_of(c), hot_mirror_of(c));
+        PIE_HIP(c, hipGetLastError());
+        PIE_HIP(c, hipEventRecord(a->ev, s));
+        a->pending = true;
+        c->key_dirty = true;
+        return PIE_OK;
+    }
+    rc = ensure_stage(c, k * 12 + 64);
+    if (rc) return rc;
+    set_end_stage(c->h_stage, rows_global, new_end, k_given, keep, k);
+    PIE_HIP(c, hipMemcpyAsync(c->d_stage, c->h_stage, k * 12, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_shard_set_end, dim3(grid), dim3(256), 0, s, c->d_end, reinterpret_cast<const int*>(c->d_stage + k * 8),
+                       reinterpret_cast<const long long*>(c->d_stage), (long long)k, (const int*)c->d_shard_rows, c->n, c->d_key, c->key_base,
+                       c->key_shift, c->d_fkey, c->fkey_base, c->fkey_shift, ord_mirror_of(c), hot_mirror_of(c));
+    PIE_HIP(c, hipGetLastError());
+    c->key_dirty = true;
+    PIE_HIP(c, hipStreamSynchronize(s));
+    if (c->ord.h_stale && *(volatile unsigned int*)c->ord.h_stale) { // a row the run does not hold is live again
+        *c->ord.h_stale = 0;
+        ord_invalidate(c);
+    }
+    return PIE_OK;
+}
+
+int pie_shard_delete_user(pie_ctx* c, int32_t user_global, int32_t* rows_global_out, size_t cap, size_t* n_deleted)
+{
+    if (!c) return PIE_E_INVAL;
+    if (n_deleted) *n_deleted = 0;
+    int rc = shard_ready(c, "pie_shard_delete_user");
+    if (rc) return rc;
+    // unknown ids and other shards' users: a no-op, like the falsy-id guard (sessionStore.js:56-58)
+    if (user_global < 0 || user_global >= c->shard_users_global || pie_shard_of(user_global, c->shard_world) != c->shard_rank) return PIE_OK;
+    const std::vector<int32_t>& um = c->shard_users_h;
+    const auto it = std::lower_bound(um.begin(), um.end(), user_global);
+    if (it == um.end() || *it != user_global || c->n == 0) return PIE_OK;
+    size_t k = 0;
+    rc = run_row_list<1>(c, (long long)(it - um.begin()), 0, nullptr, 0, &k); // the list stays in slot 0's out_idx
+    if (rc) return rc;
+    if (n_deleted) *n_deleted = k;
+    if (!rows_global_out || k == 0) return PIE_OK;
+    if (k > cap) return fail(c, PIE_E_CAPACITY, "list cap %zu < %zu", cap, k); // the rows are tombstoned all the same
+    hipStream_t s = c->stream;
+    int* list = c->slot[0].out_idx;
+    const unsigned grid = (unsigned)((k + 255) / 256) < (unsigned)c->n_cus * 8 ? (unsigned)((k + 255) / 256) : (unsigned)c->n_cus * 8;
+    hipLaunchKernelGGL(k_shard_rows_to_global, dim3(grid), dim3(256), 0, s, (const int*)list, list, (long long)k, (const int*)c->d_shard_rows, c->n);
+    PIE_HIP(c, hipGetLastError());
+    PIE_HIP(c, hipMemcpyAsync(rows_global_out, list, k * 4, hipMemcpyDeviceToHost, s));
+    PIE_HIP(c, hipStreamSynchronize(s));
+    return PIE_OK;
+}
+
+static int shard_translate(pie_ctx* c, int32_t* rows_inout, size_t k, bool to_local, const char* what)
+{
+    if (!c) return PIE_E_INVAL;
+    int rc = shard_ready(c, what);
+    if (rc) return rc;
+    if (k == 0) return PIE_OK;
+    if (!rows_inout) return fail(c, PIE_E_INVAL, "NULL row list");
+    PIE_HIP(c, hipSetDevice(c->device));
+    rc = ensure_stage(c, k * 4);
+    if (rc) return rc;
+    hipStream_t s = c->stream;
+    memcpy(c->h_stage, rows_inout, k * 4);
+    PIE_HIP(c, hipMemcpyAsync(c->d_stage, c->h_stage, k * 4, hipMemcpyHostToDevice, s));
+    int* d = reinterpret_cast<int*>(c->d_stage);
+    const unsigned grid = (unsigned)((k + 255) / 256) < (unsigned)c->n_cus * 8 ? (unsigned)((k + 255) / 256) : (unsigned)c->n_cus * 8;
+    if (to_local) hipLaunchKernelGGL(k_shard_rows_to_local, dim3(grid), dim3(256), 0, s, d, (long long)k, (const int*)c->d_shard_rows, c->n);
+    else hipLaunchKernelGGL(k_shard_rows_to_global, dim3(grid), dim3(256), 0, s, (const int*)d, d, (long long)k, (const int*)c->d_shard_rows, c->n);
+    PIE_HIP(c, hipGetLastError());
+    PIE_HIP(c, hipMemcpyAsync(c->h_stage, c->d_stage, k * 4, hipMemcpyDeviceToHost, s));
+    PIE_HIP(c, hipStreamSynchronize(s));
+    memcpy(rows_inout, c->h_stage, k * 4);
+    return PIE_OK;
+}
+
+int pie_shard_rows_to_local(pie_ctx* c, int32_t* rows_inout, size_t k) { return shard_translate(c, rows_inout, k, true, "pie_shard_rows_to_local"); }
+int pie_shard_rows_to_global(pie_ctx* c, int32_t* rows_inout, size_t k) { return shard_translate(c, rows_inout, k, false, "pie_shard_rows_to_global"); }
 
 // Rows per unit (= per wave) and the grid of the two compaction passes: every wave of every block owns one contiguous unit, a
 // whole number of 128-row steps; the grid comes from the chip (8 blocks per CU: the passes are streams, and a wave keeps one
@@ -5476,6 +5943,7 @@ int pie_compact_rows(pie_ctx* c, int64_t dead_before, uint32_t flags, size_t* n_
     const int users = c->n_users;
     const bool shrink = (flags & PIE_COMPACT_SHRINK) != 0;
     const bool sharded = c->d_shard_rows != nullptr;
+    const bool shard_on = c->shard_on; // ensure_capacity below takes the compacted rows for a new table: it stays the shard it was
     int blocks = 0;
     long long rpu = 0;
     compact_plan(c, n, &blocks, &rpu);
@@ -5580,7 +6048,9 @@ int pie_compact_rows(pie_ctx* c, int64_t dead_before, uint32_t flags, size_t* n_
             c->d_shard_rows = o_row;
             o_row = nullptr;
             c->shard_rows_n = shard_kept;
+            c->shard_rows_cap = (long long)rows_kept;
         }
+        c->shard_on = shard_on;
     } else {
         cmp_forget(c);
     }
