@@ -3970,6 +3970,53 @@ __global__ __launch_bounds__(256) void k_union_write(int n_users, int u_pad, con
 
 // ------------------------------------------------------------------------------------------------ table maintenance
 
+// The two row bodies of the mutators.  Every kernel that appends a row or re-ends one (k_append_rows, k_set_end and their
+// sharded forms at the end of this file) finds its (row, user) in its own way and then calls one of these: the derived state of
+// a row (both keys, the payload record, the hot index's and the ordered run's mirrors) is kept in step in one place.
+// key / fkey / pay may be NULL (the growth path of a sharded append: build_keys follows).
+
+// re-end row r: the `end` store, both keys, the ordered run's mirror, the hot index's mirror
+__device__ __forceinline__ void touch_row(long long r, long long e, long long* __restrict__ end, lkey_t* __restrict__ key,
+                                          long long key_base, int key_shift, fkey_t* __restrict__ fkey, long long fkey_base,
+                                          int fkey_shift, const OrdMirror& ord, const HotMirror& hot)
+{
+    end[r] = e;
+    const unsigned kk = key_of(e, key_base, key_shift), fk = key_of(e, fkey_base, fkey_shift, kFineKeyMax);
+    if (key) key[r] = (lkey_t)kk;
+    if (fkey) fkey[r] = (fkey_t)fk;
+    ord_mirror_end(ord, r, e, kk, fk);
+    hot_mirror_end(hot, r, e, fk);
+}
+
+// new row r: the four columns, both keys under the table's current parameters, the payload record, the hot index's mirror
+__device__ __forceinline__ void append_row(long long r, long long sv, long long ev, int uv, int dv, long long* __restrict__ start,
+                                           long long* __restrict__ end, int* __restrict__ user, int* __restrict__ disc,
+                                           lkey_t* __restrict__ key, long long key_base, int key_shift, fkey_t* __restrict__ fkey,
+                                           long long fkey_base, int fkey_shift, PayRec* __restrict__ pay, const HotMirror& hot)
+{
+    start[r] = sv;
+    end[r] = ev;
+    user[r] = uv;
+    disc[r] = dv;
+    const unsigned fk = key_of(ev, fkey_base, fkey_shift, kFineKeyMax);
+    if (key) key[r] = (lkey_t)key_of(ev, key_base, key_shift);
+    if (fkey) fkey[r] = (fkey_t)fk;
+    PayRec pr;
+    pr.start = sv;
+    pr.user = uv;
+    pr.disc = dv;
+    if (pay) pay[r] = pr;
+    hot_mirror_end(hot, r, ev, fk, &pr);
+}
+
+// the append kernels' count of refused user ids: summed over the wave, one atomic per wave that has any
+__device__ __forceinline__ void wave_count_bad(unsigned int local, unsigned int* __restrict__ bad)
+{
+    for (int o = 32; o > 0; o >>= 1) local += __shfl_xor(local, o, kWave);
+    if ((threadIdx.x & 63) == 0 && local) atomicAdd(bad, local);
+}
+
+// pie_set_end: element t re-ends row rows[t]; a row outside [0, n) is ignored.  The host has left one element per row.
 __global__ __launch_bounds__(256) void k_set_end(long long* __restrict__ end, const int* __restrict__ rows,
                                                  const long long* __restrict__ new_end, long long k, long long n,
                                                  lkey_t* __restrict__ key, long long key_base, int key_shift,
@@ -3977,20 +4024,13 @@ __global__ __launch_bounds__(256) void k_set_end(long long* __restrict__ end, co
                                                  HotMirror hot)
 {
     const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t < k && (unsigned)rows[t] < (unsigned long long)n) {
-        end[rows[t]] = new_end[t];
-        const unsigned kk = key_of(new_end[t], key_base, key_shift), fk = key_of(new_end[t], fkey_base, fkey_shift, kFineKeyMax);
-        if (key) key[rows[t]] = (lkey_t)kk;
-        if (fkey) fkey[rows[t]] = (fkey_t)fk;
-        ord_mirror_end(ord, rows[t], new_end[t], kk, fk);
-        hot_mirror_end(hot, rows[t], new_end[t], fk);
-    }
+    if (t < k && (unsigned)rows[t] < (unsigned long long)n)
+        touch_row(rows[t], new_end[t], end, key, key_base, key_shift, fkey, fkey_base, fkey_shift, ord, hot);
 }
 
 // createSession, k rows at a time (pie_append_rows' in-place path): the packed staging block [start k | end k | user k |
-// disc k] becomes rows [row0, row0 + k) of the four columns and of the derived columns (both keys under the table's current
-// parameters, the payload record), and user ids outside [0, n_users) are counted — one kernel instead of four copies, a
-// validation pass and two key passes.
+// disc k] becomes rows [row0, row0 + k) of the four columns and of the derived columns (append_row), and user ids outside
+// [0, n_users) are counted (and stored as given) — one kernel instead of four copies, a validation pass and two key passes.
 __global__ __launch_bounds__(256) void k_append_rows(const long long* __restrict__ st_start, const long long* __restrict__ st_end,
                                                      const int* __restrict__ st_user, const int* __restrict__ st_disc, long long k,
                                                      long long row0, int n_users, long long* __restrict__ start,
@@ -4001,25 +4041,12 @@ __global__ __launch_bounds__(256) void k_append_rows(const long long* __restrict
 {
     unsigned int local = 0;
     for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < k; t += (long long)gridDim.x * blockDim.x) {
-        const long long r = row0 + t;
-        const long long sv = st_start[t], ev = st_end[t];
-        const int uv = st_user[t], dv = st_disc[t];
+        const int uv = st_user[t];
         local += ((unsigned)uv >= (unsigned)n_users) ? 1u : 0u;
-        start[r] = sv;
-        end[r] = ev;
-        user[r] = uv;
-        disc[r] = dv;
-        if (key) key[r] = (lkey_t)key_of(ev, key_base, key_shift);
-        if (fkey) fkey[r] = (fkey_t)key_of(ev, fkey_base, fkey_shift, kFineKeyMax);
-        PayRec pr;
-        pr.start = sv;
-        pr.user = uv;
-        pr.disc = dv;
-        if (pay) pay[r] = pr;
-        hot_mirror_end(hot, r, ev, key_of(ev, fkey_base, fkey_shift, kFineKeyMax), &pr);
+        append_row(row0 + t, st_start[t], st_end[t], uv, st_disc[t], start, end, user, disc, key, key_base, key_shift, fkey, fkey_base,
+                   fkey_shift, pay, hot);
     }
-    for (int o = 32; o > 0; o >>= 1) local += __shfl_xor(local, o, kWave);
-    if ((threadIdx.x & 63) == 0 && local) atomicAdd(bad, local);
+    wave_count_bad(local, bad);
 }
 
 __global__ __launch_bounds__(256) void k_fetch_rows(const int* __restrict__ idx, long long m, long long n,
@@ -4841,8 +4868,8 @@ __global__ __launch_bounds__(256) void k_compact_translate(int* __restrict__ row
 // ------------------------------------------------------------------------------------------------ sharded mutators
 //
 // A sharded context (pie_shard_table) carries two ascending maps: local row -> global row and local user -> global user.  The
-// mutators that take GLOBAL ids stand in front of the ordinary ones: they find the local id by a lower-bound search of the
-// map and then do exactly what k_append_rows / k_set_end do for that local id.
+// mutators that take GLOBAL ids differ from the ordinary ones only in how they find the local id, by a lower-bound search of the
+// map: the row itself is written by the bodies k_append_rows / k_set_end call (append_row, touch_row).
 
 // first position of the ascending map[0, n) whose entry is >= x (n when there is none): reads map[0, n) only
 __device__ __forceinline__ long long shard_lower_bound(const int* __restrict__ map, long long n, int x)
@@ -4860,7 +4887,7 @@ __device__ __forceinline__ long long shard_lower_bound(const int* __restrict__ m
 // is translated through users_map[0, n_map) and the local id written back into the staging block, which the ordered run's
 // append then reads as it reads pie_append_rows' block; rows_map[row0 + t] takes the row's global id.  An id the map does
 // not hold counts into *bad and is written as user 0 (the host has checked every id: this keeps a slip from reaching an
-// index).  key / fkey / pay may be NULL (the growth path: build_keys follows).
+// index).
 __global__ __launch_bounds__(256) void k_shard_append_rows(const long long* __restrict__ st_start, const long long* __restrict__ st_end,
                                                            int* __restrict__ st_user, const int* __restrict__ st_disc,
                                                            const int* __restrict__ st_grow, long long k, long long row0,
@@ -4872,35 +4899,21 @@ __global__ __launch_bounds__(256) void k_shard_append_rows(const long long* __re
 {
     unsigned int local = 0;
     for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < k; t += (long long)gridDim.x * blockDim.x) {
-        const long long r = row0 + t;
-        const long long sv = st_start[t], ev = st_end[t];
-        const int gu = st_user[t], dv = st_disc[t];
+        const int gu = st_user[t];
         const long long p = shard_lower_bound(users_map, (long long)n_map, gu);
         const bool found = p < (long long)n_map && users_map[p] == gu;
         const int uv = found ? (int)p : 0;
         local += found ? 0u : 1u;
         st_user[t] = uv;
-        start[r] = sv;
-        end[r] = ev;
-        user[r] = uv;
-        disc[r] = dv;
-        rows_map[r] = st_grow[t];
-        const unsigned fk = key_of(ev, fkey_base, fkey_shift, kFineKeyMax);
-        if (key) key[r] = (lkey_t)key_of(ev, key_base, key_shift);
-        if (fkey) fkey[r] = (fkey_t)fk;
-        PayRec pr;
-        pr.start = sv;
-        pr.user = uv;
-        pr.disc = dv;
-        if (pay) pay[r] = pr;
-        hot_mirror_end(hot, r, ev, fk, &pr);
+        append_row(row0 + t, st_start[t], st_end[t], uv, st_disc[t], start, end, user, disc, key, key_base, key_shift, fkey, fkey_base,
+                   fkey_shift, pay, hot);
+        rows_map[row0 + t] = st_grow[t];
     }
-    for (int o = 32; o > 0; o >>= 1) local += __shfl_xor(local, o, kWave);
-    if ((threadIdx.x & 63) == 0 && local) atomicAdd(bad, local);
+    wave_count_bad(local, bad);
 }
 
-// pie_shard_set_end: element t names GLOBAL row grows[t]; the shard that holds it (rows_map[0, n) ascends) does what k_set_end
-// does for the local row, every other shard nothing.  The host has left one element per row (set_end_last_writers).
+// pie_shard_set_end: element t names GLOBAL row grows[t]; the shard that holds it (rows_map[0, n) ascends) re-ends the local
+// row, every other shard does nothing.  The host has left one element per row (set_end_last_writers).
 __global__ __launch_bounds__(256) void k_shard_set_end(long long* __restrict__ end, const int* __restrict__ grows,
                                                        const long long* __restrict__ new_end, long long k,
                                                        const int* __restrict__ rows_map, long long n, lkey_t* __restrict__ key,
@@ -4911,14 +4924,7 @@ __global__ __launch_bounds__(256) void k_shard_set_end(long long* __restrict__ e
     if (t >= k) return;
     const int g = grows[t];
     const long long r = shard_lower_bound(rows_map, n, g);
-    if (r >= n || rows_map[r] != g) return;
-    const long long e = new_end[t];
-    end[r] = e;
-    const unsigned kk = key_of(e, key_base, key_shift), fk = key_of(e, fkey_base, fkey_shift, kFineKeyMax);
-    if (key) key[r] = (lkey_t)kk;
-    if (fkey) fkey[r] = (fkey_t)fk;
-    ord_mirror_end(ord, r, e, kk, fk);
-    hot_mirror_end(hot, r, e, fk);
+    if (r < n && rows_map[r] == g) touch_row(r, new_end[t], end, key, key_base, key_shift, fkey, fkey_base, fkey_shift, ord, hot);
 }
 
 // k global rows -> local rows (-1: this shard does not hold the row)

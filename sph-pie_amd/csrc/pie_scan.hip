@@ -3732,27 +3732,81 @@ int pie_load_columns(pie_ctx* c, const int64_t* start, const int64_t* end, const
     return build_keys(c, 0);
 }
 
-// What follows the append kernel of the in-place path, shared by pie_append_rows and pie_shard_append_rows (n_users: the
-// context's own, local, user count after the call).  Queued form: nothing is read back, the table's size moves at once.
-static int append_queued_tail(pie_ctx* c, pie_ctx::AsyncStage* a, long long old_n, size_t k, int n_users)
+// ---- the small mutations (append, touch), plain and by global id: one staging helper, one launch site per kernel
+//
+// A mutation that needs nothing back from the device is queued, not waited for (see AsyncStage).  Queued and waited forms stage,
+// upload and launch alike; they differ in what follows the launch (queued: the area's event; waited: the read-back and the wait)
+// and in the bad_rows memset the waited appends put in front of it.
+static bool mutation_queued(const pie_ctx* c) { return c->async_mutations && !c->ord.valid; }
+
+// blocks of a grid-stride kernel over k elements: one per 256, at most 8 per CU
+static unsigned capped_grid(const pie_ctx* c, size_t k)
 {
-    PIE_HIP(c, hipGetLastError());
-    PIE_HIP(c, hipEventRecord(a->ev, c->stream));
-    a->pending = true;
-    c->n = old_n + (long long)k;
-    ord_invalidate(c);
-    if (n_users > c->n_users) set_user_count(c, n_users);
-    c->key_dirty = true;
+    return (unsigned)((k + 255) / 256) < (unsigned)c->n_cus * 8 ? (unsigned)((k + 255) / 256) : (unsigned)c->n_cus * 8;
+}
+
+// The staging block of one mutation: pinned host memory to fill, the device block it is uploaded to, and the AsyncStage it
+// belongs to when the mutation is queued (NULL: the context's own pair, and the mutation is waited for).
+struct Staged {
+    char* h;
+    char* d;
+    pie_ctx::AsyncStage* a;
+};
+static int stage_mutation(pie_ctx* c, size_t bytes, bool queued, Staged* st)
+{
+    pie_ctx::AsyncStage* a = nullptr;
+    int rc = queued ? async_stage(c, bytes, &a) : ensure_stage(c, bytes);
+    if (rc) return rc;
+    *st = queued ? Staged{a->h, a->d, a} : Staged{c->h_stage, c->d_stage, nullptr};
+    return PIE_OK;
+}
+// a queued mutation is in the stream: its area is busy until the event behind it
+static int stage_queued(pie_ctx* c, const Staged& st)
+{
+    PIE_HIP(c, hipEventRecord(st.a->ev, c->stream));
+    st.a->pending = true;
+    return PIE_OK;
+}
+
+static void drop_results(pie_ctx* c)
+{
     c->res = nullptr;
     for (Slot& sl : c->slot) sl.have_result = false;
     c->bres = nullptr;
+}
+
+// a failed append on a path that moved c->n (ensure_capacity) takes it back
+static int append_rollback(pie_ctx* c, long long old_n, int rc)
+{
+    c->n = old_n;
+    plan_k1(c);
+    return rc;
+}
+
+// the end of every append that added rows (n_users: the context's own, local, user count after the call)
+static int append_finish(pie_ctx* c, int n_users)
+{
+    if (n_users > c->n_users) set_user_count(c, n_users);
+    c->key_dirty = true;
+    drop_results(c);
     plan_k1(c);
     return ensure_sel(c);
 }
 
-// Waited form: the kernel's count of bad user ids and the ordered run's bookkeeping are read once the stream has drained.
-static int append_waited_tail(pie_ctx* c, hipStream_t s, long long old_n, size_t k, int n_users, bool ord_kept, bool global_ids = false)
+// What follows the append kernel of the in-place path.  Queued form: nothing is read back, the table's size moves at once.
+static int append_queued_tail(pie_ctx* c, const Staged& st, long long old_n, size_t k, int n_users)
 {
+    int rc = stage_queued(c, st);
+    if (rc) return rc;
+    c->n = old_n + (long long)k;
+    ord_invalidate(c);
+    return append_finish(c, n_users);
+}
+
+// Waited form: the kernel's count of bad user ids and the ordered run's bookkeeping are read once the stream has drained.
+static int append_waited_tail(pie_ctx* c, long long old_n, size_t k, int n_users, bool ord_kept, bool global_ids)
+{
+    hipStream_t s = c->stream;
     PIE_HIP(c, hipGetLastError());
     PIE_HIP(c, hipMemcpyAsync(c->h_summary, c->d_summary, sizeof(Summary), hipMemcpyDeviceToHost, s));
     PIE_HIP(c, hipStreamSynchronize(s));
@@ -3778,14 +3832,17 @@ static int append_waited_tail(pie_ctx* c, hipStream_t s, long long old_n, size_t
             c->ord.held += (long long)k;
         }
     } else ord_invalidate(c);
-    if (n_users > c->n_users) set_user_count(c, n_users);
-    c->key_dirty = true;
-    c->res = nullptr;
-    for (Slot& sl : c->slot) sl.have_result = false;
-    c->bres = nullptr;
-    plan_k1(c);
-    return ensure_sel(c);
+    return append_finish(c, n_users);
 }
+
+// What a sharded append adds to a plain one: k_call rows went to all shards (this one keeps k of them), n_new users join the
+// shard's user map, and the maps are committed once the kernel is queued (shard_append_commit, defined with the sharded calls).
+struct ShardAppend {
+    size_t k_call, n_new;
+    int32_t n_users_global;
+};
+static int append_launch(pie_ctx* c, const Staged& st, size_t k, long long row0, int n_users, const ShardAppend* sh, bool with_keys);
+static int append_in_place(pie_ctx* c, const Staged& st, size_t k, int n_users, const ShardAppend* sh);
 
 int pie_append_rows(pie_ctx* c, const int64_t* start, const int64_t* end, const int32_t* user, const int32_t* disc,
                     size_t k, int32_t n_users)
@@ -3797,56 +3854,25 @@ int pie_append_rows(pie_ctx* c, const int64_t* start, const int64_t* end, const 
     const long long old_n = c->n;
     if (k > 0 && old_n > 0 && old_n + (long long)k <= c->cap_rows && n_users <= c->cap_users && c->key_ok && k <= ((size_t)1 << 24)) {
         // In-place path (room for the rows and the users, key columns in step): ONE staged upload, ONE kernel that writes the
-        // four columns, both keys and the payload record of every new row and validates the user ids, ONE wait.  A login
-        // burst costs tens of microseconds, not the half-dozen blocking calls of the general path below.
+        // four columns, both keys and the payload record of every new row and validates the user ids, and ONE wait or none.  A
+        // login burst costs tens of microseconds, not the half-dozen blocking calls of the general path below.
         if (c->n_flight || c->b_flight) return fail(c, PIE_E_STATE, "table change while a scan is in flight");
         if (old_n + (long long)k >= (1LL << 31) - 1) return fail(c, PIE_E_INVAL, "row count outside [0, 2^31 - 1)");
         hot_reserve(c, (long long)k);
-        if (c->async_mutations && !c->ord.valid) {
-            // nothing to read back: user ids are checked here, the rows are staged and queued, the call returns (see AsyncStage)
+        const bool queued = mutation_queued(c);
+        if (queued) { // nothing will be read back: the user ids are checked here
             unsigned bad = 0;
             for (size_t i = 0; i < k; ++i) bad += (unsigned)user[i] >= (unsigned)n_users ? 1u : 0u;
             if (bad) return fail(c, PIE_E_INVAL, "%u rows carry a user id outside [0, %d)", bad, n_users);
-            pie_ctx::AsyncStage* a = nullptr;
-            int rca = async_stage(c, k * 24 + 64, &a);
-            if (rca) return rca;
-            memcpy(a->h, start, k * 8);
-            memcpy(a->h + k * 8, end, k * 8);
-            memcpy(a->h + k * 16, user, k * 4);
-            memcpy(a->h + k * 20, disc, k * 4);
-            hipStream_t s = c->stream;
-            PIE_HIP(c, hipMemcpyAsync(a->d, a->h, k * 24, hipMemcpyHostToDevice, s));
-            const unsigned grid = (unsigned)((k + 255) / 256) < (unsigned)c->n_cus * 8 ? (unsigned)((k + 255) / 256) : (unsigned)c->n_cus * 8;
-            hipLaunchKernelGGL(k_append_rows, dim3(grid), dim3(256), 0, s, reinterpret_cast<const long long*>(a->d),
-                               reinterpret_cast<const long long*>(a->d + k * 8), reinterpret_cast<const int*>(a->d + k * 16),
-                               reinterpret_cast<const int*>(a->d + k * 20), (long long)k, old_n, n_users, c->d_start, c->d_end, c->d_user,
-                               c->d_disc, c->d_key, c->key_base, c->key_shift, c->d_fkey, c->fkey_base, c->fkey_shift, c->d_pay,
-                               &c->d_summary->bad_rows, hot_mirror_of(c));
-            return append_queued_tail(c, a, old_n, k, n_users);
         }
-        int rc0 = ensure_stage(c, k * 24 + 64);
+        Staged st{};
+        int rc0 = stage_mutation(c, k * 24 + 64, queued, &st);
         if (rc0) return rc0;
-        char* h = c->h_stage;
-        memcpy(h, start, k * 8);
-        memcpy(h + k * 8, end, k * 8);
-        memcpy(h + k * 16, user, k * 4);
-        memcpy(h + k * 20, disc, k * 4);
-        hipStream_t s = c->stream;
-        PIE_HIP(c, hipMemcpyAsync(c->d_stage, h, k * 24, hipMemcpyHostToDevice, s));
-        PIE_HIP(c, hipMemsetAsync(&c->d_summary->bad_rows, 0, sizeof(unsigned int), s));
-        const unsigned grid = (unsigned)((k + 255) / 256) < (unsigned)c->n_cus * 8 ? (unsigned)((k + 255) / 256) : (unsigned)c->n_cus * 8;
-        hipLaunchKernelGGL(k_append_rows, dim3(grid), dim3(256), 0, s, reinterpret_cast<const long long*>(c->d_stage),
-                           reinterpret_cast<const long long*>(c->d_stage + k * 8), reinterpret_cast<const int*>(c->d_stage + k * 16),
-                           reinterpret_cast<const int*>(c->d_stage + k * 20), (long long)k, old_n, n_users, c->d_start, c->d_end, c->d_user,
-                           c->d_disc, c->d_key, c->key_base, c->key_shift, c->d_fkey, c->fkey_base, c->fkey_shift, c->d_pay,
-                           &c->d_summary->bad_rows, hot_mirror_of(c));
-        // the ordered run takes rows that arrive in time order into the spare slots of their users' segments
-        bool ord_kept = false;
-        if (c->ord.valid && c->ord.rows == old_n && k <= (size_t)kOrdAppendMax && n_users <= c->ord.users && c->key_ok) {
-            launch_ord_append(c, s, k, old_n, n_users, 1); // pend[] is all zero between appends (build and re-spread leave it so)
-            ord_kept = true;
-        }
-        return append_waited_tail(c, s, old_n, k, n_users, ord_kept);
+        memcpy(st.h, start, k * 8);
+        memcpy(st.h + k * 8, end, k * 8);
+        memcpy(st.h + k * 16, user, k * 4);
+        memcpy(st.h + k * 20, disc, k * 4);
+        return append_in_place(c, st, k, n_users, nullptr);
     }
     int rc = ensure_capacity(c, old_n + (long long)k, n_users, old_n > 0 ? old_n : 1);
     if (rc) return rc;
@@ -3857,7 +3883,7 @@ int pie_append_rows(pie_ctx* c, const int64_t* start, const int64_t* end, const 
         PIE_HIP(c, hipMemcpyAsync(c->d_disc + old_n, disc, k * 4, hipMemcpyHostToDevice, c->stream));
     }
     rc = validate_users(c, old_n);
-    if (rc) { c->n = old_n; plan_k1(c); return rc; }
+    if (rc) return append_rollback(c, old_n, rc);
     return build_keys(c, old_n);
 }
 
@@ -4073,6 +4099,49 @@ static size_t set_end_stage(char* dst, const int32_t* rows, const int64_t* new_e
     return j;
 }
 
+// pie_set_end and pie_shard_set_end behind their own checks: ids[] are local rows, or (global) global rows the kernel looks up
+// in the row map.  Equal global rows are equal local rows, so the repeats are resolved over the ids as they come: a row named
+// more than once takes the value of its last element (the header's rule), the others are left out here.
+static int set_end_apply(pie_ctx* c, const int32_t* ids, const int64_t* new_end, size_t k_given, bool global)
+{
+    try {
+        c->set_end_keep.resize(k_given);
+    } catch (...) {
+        return fail(c, PIE_E_NOMEM, "no memory for %zu touches", k_given);
+    }
+    const uint8_t* keep = c->set_end_keep.data();
+    if (!set_end_last_writers(ids, k_given, c->set_end_keep.data(), c->set_end_slots)) return fail(c, PIE_E_NOMEM, "no memory for %zu touches", k_given);
+    size_t k = 0;
+    for (size_t i = 0; i < k_given; ++i) k += keep[i];
+    PIE_HIP(c, hipSetDevice(c->device));
+    hot_reserve(c, (long long)k_given); // the bound counts every element: never less than the rows that can move to the delta
+    // staged like the append path: one upload of [new_end k | ids k], one kernel (end + both keys + mirrors), one wait or none
+    Staged st{};
+    int rc = stage_mutation(c, k * 12 + 64, mutation_queued(c), &st);
+    if (rc) return rc;
+    set_end_stage(st.h, ids, new_end, k_given, keep, k);
+    hipStream_t s = c->stream;
+    PIE_HIP(c, hipMemcpyAsync(st.d, st.h, k * 12, hipMemcpyHostToDevice, s));
+    const int* d_ids = reinterpret_cast<const int*>(st.d + k * 8);
+    const long long* d_new_end = reinterpret_cast<const long long*>(st.d);
+    const dim3 grid((unsigned)((k + 255) / 256)); // a thread per element
+    if (global)
+        hipLaunchKernelGGL(k_shard_set_end, grid, dim3(256), 0, s, c->d_end, d_ids, d_new_end, (long long)k, (const int*)c->d_shard_rows, c->n,
+                           c->d_key, c->key_base, c->key_shift, c->d_fkey, c->fkey_base, c->fkey_shift, ord_mirror_of(c), hot_mirror_of(c));
+    else
+        hipLaunchKernelGGL(k_set_end, grid, dim3(256), 0, s, c->d_end, d_ids, d_new_end, (long long)k, c->n, c->d_key, c->key_base,
+                           c->key_shift, c->d_fkey, c->fkey_base, c->fkey_shift, ord_mirror_of(c), hot_mirror_of(c));
+    PIE_HIP(c, hipGetLastError());
+    c->key_dirty = true;
+    if (st.a) return stage_queued(c, st); // the ids were checked by the caller: nothing to read back
+    PIE_HIP(c, hipStreamSynchronize(s));
+    if (c->ord.h_stale && *(volatile unsigned int*)c->ord.h_stale) { // a row the run does not hold is live again
+        *c->ord.h_stale = 0;
+        ord_invalidate(c);
+    }
+    return PIE_OK;
+}
+
 int pie_set_end(pie_ctx* c, const int32_t* rows, const int64_t* new_end, size_t k_given)
 {
     if (!c) return PIE_E_INVAL;
@@ -4081,49 +4150,7 @@ int pie_set_end(pie_ctx* c, const int32_t* rows, const int64_t* new_end, size_t 
     if (c->n_flight || c->b_flight) return fail(c, PIE_E_STATE, "table change while a scan is in flight");
     for (size_t i = 0; i < k_given; ++i)
         if (rows[i] < 0 || rows[i] >= c->n) return fail(c, PIE_E_INVAL, "row %d outside the table", rows[i]);
-    // a row named more than once takes the value of its last element (the header's rule): the others are left out here
-    try {
-        c->set_end_keep.resize(k_given);
-    } catch (...) {
-        return fail(c, PIE_E_NOMEM, "no memory for %zu touches", k_given);
-    }
-    const uint8_t* keep = c->set_end_keep.data();
-    if (!set_end_last_writers(rows, k_given, c->set_end_keep.data(), c->set_end_slots)) return fail(c, PIE_E_NOMEM, "no memory for %zu touches", k_given);
-    size_t k = 0;
-    for (size_t i = 0; i < k_given; ++i) k += keep[i];
-    PIE_HIP(c, hipSetDevice(c->device));
-    hot_reserve(c, (long long)k_given); // the bound counts every element: never less than the rows that can move to the delta
-    if (c->async_mutations && !c->ord.valid) { // queued, not waited for (see AsyncStage); the rows were checked above
-        pie_ctx::AsyncStage* a = nullptr;
-        int rca = async_stage(c, k * 12 + 64, &a);
-        if (rca) return rca;
-        set_end_stage(a->h, rows, new_end, k_given, keep, k);
-        PIE_HIP(c, hipMemcpyAsync(a->d, a->h, k * 12, hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(k_set_end, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, c->stream, c->d_end,
-                           reinterpret_cast<const int*>(a->d + k * 8), reinterpret_cast<const long long*>(a->d), (long long)k, c->n,
-                           c->d_key, c->key_base, c->key_shift, c->d_fkey, c->fkey_base, c->fkey_shift, ord_mirror_of(c), hot_mirror_of(c));
-        PIE_HIP(c, hipGetLastError());
-        PIE_HIP(c, hipEventRecord(a->ev, c->stream));
-        a->pending = true;
-        c->key_dirty = true;
-        return PIE_OK;
-    }
-    // staged like the append path: one upload of [new_end k | rows k], one kernel (end + both keys), one wait
-    int rc = ensure_stage(c, k * 12 + 64);
-    if (rc) return rc;
-    set_end_stage(c->h_stage, rows, new_end, k_given, keep, k);
-    PIE_HIP(c, hipMemcpyAsync(c->d_stage, c->h_stage, k * 12, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_set_end, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, c->stream, c->d_end,
-                       reinterpret_cast<const int*>(c->d_stage + k * 8), reinterpret_cast<const long long*>(c->d_stage), (long long)k, c->n,
-                       c->d_key, c->key_base, c->key_shift, c->d_fkey, c->fkey_base, c->fkey_shift, ord_mirror_of(c), hot_mirror_of(c));
-    PIE_HIP(c, hipGetLastError());
-    c->key_dirty = true;
-    PIE_HIP(c, hipStreamSynchronize(c->stream));
-    if (c->ord.h_stale && *(volatile unsigned int*)c->ord.h_stale) { // a row the run does not hold is live again
-        *c->ord.h_stale = 0;
-        ord_invalidate(c);
-    }
-    return PIE_OK;
+    return set_end_apply(c, rows, new_end, k_given, false);
 }
 
 int pie_delete_user(pie_ctx* c, int32_t user, int32_t* rows_out, size_t cap, size_t* n_deleted)
@@ -5621,21 +5648,32 @@ static void shard_append_stage(char* h, const int64_t* start, const int64_t* end
         if (pie_shard_of(u, world) == rank) hn[j++] = u;
 }
 
-// upload the block, extend the device user map by the new users, run the kernel on rows [old_n, old_n + n_kept)
-static int shard_append_launch(pie_ctx* c, char* h, char* d, size_t n_kept, size_t n_new, long long old_n, bool with_keys)
+// Upload an append's block, extend the device user map by a sharded append's new users, zero the count a waited append reads
+// back, and run the kernel on rows [row0, row0 + k).  with_keys false (the growth path of a sharded append): the four columns
+// and the row map only, build_keys follows.
+static int append_launch(pie_ctx* c, const Staged& st, size_t k, long long row0, int n_users, const ShardAppend* sh, bool with_keys)
 {
     hipStream_t s = c->stream;
-    PIE_HIP(c, hipMemcpyAsync(d, h, n_kept * 28 + n_new * 4, hipMemcpyHostToDevice, s));
-    if (n_new)
-        PIE_HIP(c, hipMemcpyAsync(c->d_shard_users + c->shard_users_n, d + n_kept * 28, n_new * 4, hipMemcpyDeviceToDevice, s));
-    if (n_kept == 0) return PIE_OK;
-    const unsigned grid = (unsigned)((n_kept + 255) / 256) < (unsigned)c->n_cus * 8 ? (unsigned)((n_kept + 255) / 256) : (unsigned)c->n_cus * 8;
-    hipLaunchKernelGGL(k_shard_append_rows, dim3(grid), dim3(256), 0, s, reinterpret_cast<const long long*>(d),
-                       reinterpret_cast<const long long*>(d + n_kept * 8), reinterpret_cast<int*>(d + n_kept * 16),
-                       reinterpret_cast<const int*>(d + n_kept * 20), reinterpret_cast<const int*>(d + n_kept * 24), (long long)n_kept, old_n,
-                       (const int*)c->d_shard_users, c->shard_users_n + (int)n_new, c->d_start, c->d_end, c->d_user, c->d_disc, c->d_shard_rows,
-                       with_keys ? c->d_key : (lkey_t*)nullptr, c->key_base, c->key_shift, with_keys ? c->d_fkey : (fkey_t*)nullptr, c->fkey_base,
-                       c->fkey_shift, with_keys ? c->d_pay : (PayRec*)nullptr, &c->d_summary->bad_rows, with_keys ? hot_mirror_of(c) : HotMirror{});
+    PIE_HIP(c, hipMemcpyAsync(st.d, st.h, sh ? k * 28 + sh->n_new * 4 : k * 24, hipMemcpyHostToDevice, s));
+    if (sh && sh->n_new)
+        PIE_HIP(c, hipMemcpyAsync(c->d_shard_users + c->shard_users_n, st.d + k * 28, sh->n_new * 4, hipMemcpyDeviceToDevice, s));
+    if (!st.a) PIE_HIP(c, hipMemsetAsync(&c->d_summary->bad_rows, 0, sizeof(unsigned int), s));
+    if (k == 0) return PIE_OK;
+    const long long *d_start = reinterpret_cast<const long long*>(st.d), *d_end = reinterpret_cast<const long long*>(st.d + k * 8);
+    int* d_user = reinterpret_cast<int*>(st.d + k * 16);
+    const int *d_disc = reinterpret_cast<const int*>(st.d + k * 20), *d_grow = reinterpret_cast<const int*>(st.d + k * 24);
+    lkey_t* key = with_keys ? c->d_key : nullptr;
+    fkey_t* fkey = with_keys ? c->d_fkey : nullptr;
+    PayRec* pay = with_keys ? c->d_pay : nullptr;
+    const HotMirror hot = with_keys ? hot_mirror_of(c) : HotMirror{};
+    if (sh)
+        hipLaunchKernelGGL(k_shard_append_rows, dim3(capped_grid(c, k)), dim3(256), 0, s, d_start, d_end, d_user, d_disc, d_grow, (long long)k, row0,
+                           (const int*)c->d_shard_users, c->shard_users_n + (int)sh->n_new, c->d_start, c->d_end, c->d_user, c->d_disc,
+                           c->d_shard_rows, key, c->key_base, c->key_shift, fkey, c->fkey_base, c->fkey_shift, pay, &c->d_summary->bad_rows, hot);
+    else
+        hipLaunchKernelGGL(k_append_rows, dim3(capped_grid(c, k)), dim3(256), 0, s, d_start, d_end, (const int*)d_user, d_disc, (long long)k, row0,
+                           n_users, c->d_start, c->d_end, c->d_user, c->d_disc, key, c->key_base, c->key_shift, fkey, c->fkey_base,
+                           c->fkey_shift, pay, &c->d_summary->bad_rows, hot);
     PIE_HIP(c, hipGetLastError());
     return PIE_OK;
 }
@@ -5673,6 +5711,34 @@ static void shard_append_undo(pie_ctx* c, const ShardUndo& u)
     c->shard_users_h.resize(u.users_h);
 }
 
+// The in-place path of pie_append_rows and pie_shard_append_rows from the filled staging block on: the kernel, the ordered run's
+// append (waited form only: it reads the context's own staging block, where the sharded kernel has left LOCAL user ids), the
+// shard's commit, then the queued or the waited tail.
+static int append_in_place(pie_ctx* c, const Staged& st, size_t k, int n_users, const ShardAppend* sh)
+{
+    const long long old_n = c->n;
+    int rc = append_launch(c, st, k, old_n, n_users, sh, true);
+    if (rc) return rc;
+    // the ordered run takes rows that arrive in time order into the spare slots of their users' segments
+    bool ord_kept = false;
+    if (c->ord.valid && c->ord.rows == old_n && k <= (size_t)kOrdAppendMax && n_users <= c->ord.users && c->key_ok) {
+        launch_ord_append(c, c->stream, k, old_n, n_users, 1); // pend[] is all zero between appends (build and re-spread leave it so)
+        ord_kept = true;
+    }
+    ShardUndo undo{};
+    if (sh) {
+        rc = shard_append_commit(c, st.h, old_n, k, sh->n_new, sh->k_call, sh->n_users_global, &undo);
+        if (rc) { // the kernels fed the hot index and the run rows the table will not hold
+            c->hix.valid = false;
+            if (ord_kept) ord_invalidate(c);
+            return rc;
+        }
+    }
+    rc = st.a ? append_queued_tail(c, st, old_n, k, n_users) : append_waited_tail(c, old_n, k, n_users, ord_kept, sh != nullptr);
+    if (rc && sh && c->n == old_n) shard_append_undo(c, undo);
+    return rc;
+}
+
 int pie_shard_append_rows(pie_ctx* c, const int64_t* start, const int64_t* end, const int32_t* user_global, const int32_t* disc,
                           size_t k, int32_t n_users_global, int32_t* first_row_out, size_t* n_kept_out)
 {
@@ -5704,91 +5770,48 @@ int pie_shard_append_rows(pie_ctx* c, const int64_t* start, const int64_t* end, 
         return PIE_OK;
     }
     const size_t bytes = n_kept * 28 + n_new * 4 + 64;
-    ShardUndo undo{};
-    if (n_kept == 0 && local_users <= c->cap_users) {
-        // only the user map grows: the new ids go behind it in stream order; no row, no key, nothing to wait for
+    const ShardAppend sh{k, n_new, n_users_global};
+    const bool in_place = n_kept > 0 && old_n > 0 && old_n + (long long)n_kept <= c->cap_rows && c->key_ok && n_kept <= ((size_t)1 << 24);
+    Staged st{};
+    if ((n_kept == 0 || in_place) && local_users <= c->cap_users) {
         rc = shard_maps_reserve(c, c->cap_rows, c->cap_users);
         if (rc) return rc;
-        pie_ctx::AsyncStage* a = nullptr;
-        rc = async_stage(c, bytes, &a);
+        if (in_place) hot_reserve(c, (long long)n_kept);
+        // rows and no wait where pie_append_rows has none; users alone are always queued (nothing of them is ever read back)
+        rc = stage_mutation(c, bytes, !in_place || mutation_queued(c), &st);
         if (rc) return rc;
-        shard_append_stage(a->h, start, end, user_global, disc, k, keep, 0, first_row, users_before, n_users_global, rank, world);
-        rc = shard_append_launch(c, a->h, a->d, 0, n_new, old_n, true);
-        if (rc) return rc;
-        PIE_HIP(c, hipEventRecord(a->ev, c->stream));
-        a->pending = true;
-        rc = shard_append_commit(c, a->h, old_n, 0, n_new, k, n_users_global, &undo);
+        shard_append_stage(st.h, start, end, user_global, disc, k, keep, n_kept, first_row, users_before, n_users_global, rank, world);
+        if (in_place) return append_in_place(c, st, n_kept, local_users, &sh);
+        // Only the user map grows: the new ids go behind it in stream order.  Not the n_kept == 0 case of append_in_place: no row
+        // changed, so the keys stay clean and the plans stand, and the ordered run goes only when it has no room for the users.
+        rc = append_launch(c, st, 0, old_n, local_users, &sh, true);
+        if (rc == PIE_OK) rc = stage_queued(c, st);
+        ShardUndo undo{};
+        if (rc == PIE_OK) rc = shard_append_commit(c, st.h, old_n, 0, n_new, k, n_users_global, &undo);
         if (rc) return rc;
         if (local_users > c->n_users) { // as an in-place append that brings users and no row would leave the context
             if (c->ord.valid && local_users > c->ord.users) ord_invalidate(c);
             set_user_count(c, local_users);
-            c->res = nullptr;
-            for (Slot& sl : c->slot) sl.have_result = false;
-            c->bres = nullptr;
+            drop_results(c);
         }
         if (!c->async_mutations) PIE_HIP(c, hipStreamSynchronize(c->stream));
         return PIE_OK;
     }
-    if (n_kept > 0 && old_n > 0 && old_n + (long long)n_kept <= c->cap_rows && local_users <= c->cap_users && c->key_ok && n_kept <= ((size_t)1 << 24)) {
-        // in place, as pie_append_rows: one staged upload, one kernel, and no wait where pie_append_rows has none
-        rc = shard_maps_reserve(c, c->cap_rows, c->cap_users);
-        if (rc) return rc;
-        hot_reserve(c, (long long)n_kept);
-        if (c->async_mutations && !c->ord.valid) {
-            pie_ctx::AsyncStage* a = nullptr;
-            rc = async_stage(c, bytes, &a);
-            if (rc) return rc;
-            shard_append_stage(a->h, start, end, user_global, disc, k, keep, n_kept, first_row, users_before, n_users_global, rank, world);
-            rc = shard_append_launch(c, a->h, a->d, n_kept, n_new, old_n, true);
-            if (rc) return rc;
-            rc = shard_append_commit(c, a->h, old_n, n_kept, n_new, k, n_users_global, &undo);
-            if (rc) { c->hix.valid = false; return rc; } // the kernel fed the hot index rows the table will not hold
-            rc = append_queued_tail(c, a, old_n, n_kept, local_users);
-            if (rc && c->n == old_n) shard_append_undo(c, undo);
-            return rc;
-        }
-        rc = ensure_stage(c, bytes);
-        if (rc) return rc;
-        hipStream_t s = c->stream;
-        shard_append_stage(c->h_stage, start, end, user_global, disc, k, keep, n_kept, first_row, users_before, n_users_global, rank, world);
-        PIE_HIP(c, hipMemsetAsync(&c->d_summary->bad_rows, 0, sizeof(unsigned int), s));
-        rc = shard_append_launch(c, c->h_stage, c->d_stage, n_kept, n_new, old_n, true);
-        if (rc) return rc;
-        // the kernel left LOCAL user ids in the block: the ordered run takes the rows as it takes pie_append_rows' rows
-        bool ord_kept = false;
-        if (c->ord.valid && c->ord.rows == old_n && n_kept <= (size_t)kOrdAppendMax && local_users <= c->ord.users && c->key_ok) {
-            launch_ord_append(c, s, n_kept, old_n, local_users, 1);
-            ord_kept = true;
-        }
-        rc = shard_append_commit(c, c->h_stage, old_n, n_kept, n_new, k, n_users_global, &undo);
-        if (rc) { // the kernels fed the hot index and the run rows the table will not hold
-            c->hix.valid = false;
-            if (ord_kept) ord_invalidate(c);
-            return rc;
-        }
-        rc = append_waited_tail(c, s, old_n, n_kept, local_users, ord_kept, true);
-        if (rc && c->n == old_n) shard_append_undo(c, undo);
-        return rc;
-    }
     // growth path, as pie_append_rows: a larger table first (the maps with it), the rows behind the resident ones, then the keys
     rc = ensure_capacity(c, old_n + (long long)n_kept, local_users, old_n > 0 ? old_n : 1);
     if (rc == PIE_OK) rc = shard_maps_reserve(c, c->cap_rows, c->cap_users);
-    if (rc == PIE_OK) rc = ensure_stage(c, bytes);
-    if (rc) { c->n = old_n; plan_k1(c); return rc; }
-    hipStream_t s = c->stream;
-    shard_append_stage(c->h_stage, start, end, user_global, disc, k, keep, n_kept, first_row, users_before, n_users_global, rank, world);
-    PIE_HIP(c, hipMemsetAsync(&c->d_summary->bad_rows, 0, sizeof(unsigned int), s));
-    rc = shard_append_launch(c, c->h_stage, c->d_stage, n_kept, n_new, old_n, false);
-    if (rc) { c->n = old_n; plan_k1(c); return rc; }
-    PIE_HIP(c, hipMemcpyAsync(c->h_summary, c->d_summary, sizeof(Summary), hipMemcpyDeviceToHost, s));
-    PIE_HIP(c, hipStreamSynchronize(s));
-    if (c->h_summary->bad_rows) {
-        c->n = old_n;
-        plan_k1(c);
-        return fail(c, PIE_E_INVAL, "%u rows carry a user id the shard's user map does not hold", c->h_summary->bad_rows);
-    }
-    rc = shard_append_commit(c, c->h_stage, old_n, n_kept, n_new, k, n_users_global, &undo);
-    if (rc) { c->n = old_n; plan_k1(c); return rc; }
+    if (rc == PIE_OK) rc = stage_mutation(c, bytes, false, &st);
+    if (rc) return append_rollback(c, old_n, rc);
+    shard_append_stage(st.h, start, end, user_global, disc, k, keep, n_kept, first_row, users_before, n_users_global, rank, world);
+    rc = append_launch(c, st, n_kept, old_n, local_users, &sh, false);
+    if (rc) return append_rollback(c, old_n, rc);
+    PIE_HIP(c, hipMemcpyAsync(c->h_summary, c->d_summary, sizeof(Summary), hipMemcpyDeviceToHost, c->stream));
+    PIE_HIP(c, hipStreamSynchronize(c->stream));
+    if (c->h_summary->bad_rows)
+        return append_rollback(c, old_n, fail(c, PIE_E_INVAL, "%u rows carry a user id the shard's user map does not hold", c->h_summary->bad_rows));
+    ShardUndo undo{};
+    rc = shard_append_commit(c, st.h, old_n, n_kept, n_new, k, n_users_global, &undo);
+    if (rc) return append_rollback(c, old_n, rc);
     return build_keys(c, old_n); // c->n and the map already agree, whatever this returns
 }
 
@@ -5796,52 +5819,8 @@ int pie_shard_set_end(pie_ctx* c, const int32_t* rows_global, const int64_t* new
 {
     if (!c) return PIE_E_INVAL;
     int rc = pie_internal::shard_check_set_end(c, rows_global, new_end, k_given);
-    if (rc) return rc;
-    if (k_given == 0) return PIE_OK;
-    // equal global rows are equal local rows: the repeats are resolved over the global ids, as pie_set_end resolves them
-    try {
-        c->set_end_keep.resize(k_given);
-    } catch (...) {
-        return fail(c, PIE_E_NOMEM, "no memory for %zu touches", k_given);
-    }
-    const uint8_t* keep = c->set_end_keep.data();
-    if (!set_end_last_writers(rows_global, k_given, c->set_end_keep.data(), c->set_end_slots)) return fail(c, PIE_E_NOMEM, "no memory for %zu touches", k_given);
-    size_t k = 0;
-    for (size_t i = 0; i < k_given; ++i) k += keep[i];
-    PIE_HIP(c, hipSetDevice(c->device));
-    hot_reserve(c, (long long)k_given);
-    hipStream_t s = c->stream;
-    const unsigned grid = (unsigned)((k + 255) / 256);
-    if (c->async_mutations && !c->ord.valid) {
-        pie_ctx::AsyncStage* a = nullptr;
-        rc = async_stage(c, k * 12 + 64, &a);
-        if (rc) return rc;
-        set_end_stage(a->h, rows_global, new_end, k_given, keep, k);
-        PIE_HIP(c, hipMemcpyAsync(a->d, a->h, k * 12, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_shard_set_end, dim3(grid), dim3(256), 0, s, c->d_end, reinterpret_cast<const int*>(a->d + k * 8),
-                           reinterpret_cast<const long long*>(a->d), (long long)k, (const int*)c->d_shard_rows, c->n, c->d_key, c->key_base,
-                           c->key_shift, c->d_fkey, c->fkey_base, c->fkey_shift, ord_mirror_of(c), hot_mirror_of(c));
-        PIE_HIP(c, hipGetLastError());
-        PIE_HIP(c, hipEventRecord(a->ev, s));
-        a->pending = true;
-        c->key_dirty = true;
-        return PIE_OK;
-    }
-    rc = ensure_stage(c, k * 12 + 64);
-    if (rc) return rc;
-    set_end_stage(c->h_stage, rows_global, new_end, k_given, keep, k);
-    PIE_HIP(c, hipMemcpyAsync(c->d_stage, c->h_stage, k * 12, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_shard_set_end, dim3(grid), dim3(256), 0, s, c->d_end, reinterpret_cast<const int*>(c->d_stage + k * 8),
-                       reinterpret_cast<const long long*>(c->d_stage), (long long)k, (const int*)c->d_shard_rows, c->n, c->d_key, c->key_base,
-                       c->key_shift, c->d_fkey, c->fkey_base, c->fkey_shift, ord_mirror_of(c), hot_mirror_of(c));
-    PIE_HIP(c, hipGetLastError());
-    c->key_dirty = true;
-    PIE_HIP(c, hipStreamSynchronize(s));
-    if (c->ord.h_stale && *(volatile unsigned int*)c->ord.h_stale) { // a row the run does not hold is live again
-        *c->ord.h_stale = 0;
-        ord_invalidate(c);
-    }
-    return PIE_OK;
+    if (rc || k_given == 0) return rc;
+    return set_end_apply(c, rows_global, new_end, k_given, true);
 }
 
 int pie_shard_delete_user(pie_ctx* c, int32_t user_global, int32_t* rows_global_out, size_t cap, size_t* n_deleted)
@@ -5863,7 +5842,7 @@ int pie_shard_delete_user(pie_ctx* c, int32_t user_global, int32_t* rows_global_
     if (k > cap) return fail(c, PIE_E_CAPACITY, "list cap %zu < %zu", cap, k); // the rows are tombstoned all the same
     hipStream_t s = c->stream;
     int* list = c->slot[0].out_idx;
-    const unsigned grid = (unsigned)((k + 255) / 256) < (unsigned)c->n_cus * 8 ? (unsigned)((k + 255) / 256) : (unsigned)c->n_cus * 8;
+    const unsigned grid = capped_grid(c, k);
     hipLaunchKernelGGL(k_shard_rows_to_global, dim3(grid), dim3(256), 0, s, (const int*)list, list, (long long)k, (const int*)c->d_shard_rows, c->n);
     PIE_HIP(c, hipGetLastError());
     PIE_HIP(c, hipMemcpyAsync(rows_global_out, list, k * 4, hipMemcpyDeviceToHost, s));
@@ -5885,7 +5864,7 @@ static int shard_translate(pie_ctx* c, int32_t* rows_inout, size_t k, bool to_lo
     memcpy(c->h_stage, rows_inout, k * 4);
     PIE_HIP(c, hipMemcpyAsync(c->d_stage, c->h_stage, k * 4, hipMemcpyHostToDevice, s));
     int* d = reinterpret_cast<int*>(c->d_stage);
-    const unsigned grid = (unsigned)((k + 255) / 256) < (unsigned)c->n_cus * 8 ? (unsigned)((k + 255) / 256) : (unsigned)c->n_cus * 8;
+    const unsigned grid = capped_grid(c, k);
     if (to_local) hipLaunchKernelGGL(k_shard_rows_to_local, dim3(grid), dim3(256), 0, s, d, (long long)k, (const int*)c->d_shard_rows, c->n);
     else hipLaunchKernelGGL(k_shard_rows_to_global, dim3(grid), dim3(256), 0, s, (const int*)d, d, (long long)k, (const int*)c->d_shard_rows, c->n);
     PIE_HIP(c, hipGetLastError());
@@ -6116,7 +6095,7 @@ int pie_compact_translate(pie_ctx* c, int32_t* rows_inout, size_t k)
     hipStream_t s = c->stream;
     memcpy(c->h_stage, rows_inout, k * 4);
     PIE_HIP(c, hipMemcpyAsync(c->d_stage, c->h_stage, k * 4, hipMemcpyHostToDevice, s));
-    const unsigned grid = (unsigned)((k + 255) / 256) < (unsigned)c->n_cus * 8 ? (unsigned)((k + 255) / 256) : (unsigned)c->n_cus * 8;
+    const unsigned grid = capped_grid(c, k);
     hipLaunchKernelGGL(k_compact_translate, dim3(grid), dim3(256), 0, s, reinterpret_cast<int*>(c->d_stage), (long long)k,
                        (const int*)c->d_cmp_new_of_old, c->cmp_n_old);
     PIE_HIP(c, hipGetLastError());
