@@ -112,7 +112,13 @@ int pie_read_columns(pie_ctx *ctx, int64_t *start, int64_t *end, int32_t *user, 
  * A call that names a row more than once behaves as its elements applied in array order, as two touches or deletes of one token
  * run one after the other in the reference: the last occurrence's value is the row's `end`, and every derived structure (both
  * liveness keys, the hot index, the ordered run) agrees with that value.  The repeats are resolved on the host before the
- * rows are staged (scratch sized by k, never by the table); the call stays queued and un-waited where it was. */
+ * rows are staged (scratch sized by k, never by the table); the call stays queued and un-waited where it was.
+ * Finished results under a later mutation: pie_set_end / pie_shard_set_end leave the results of a finished scan or batch as
+ * they were: every reader (pie_read_results, pie_read_user_feed, pie_batch_read_results, pie_batch_read_user_feed, the union
+ * readers, the device pointers) keeps answering for the table as the scan saw it; only the `end` column that
+ * pie_batch_fetch_requests returns beside the rows is the table's own, read when it is called.  pie_append_rows /
+ * pie_shard_append_rows that add a row or a user to the context end them: until the next finish every reader of a scan's or a
+ * batch's result returns PIE_E_STATE. */
 int pie_set_end(pie_ctx *ctx, const int32_t *rows, const int64_t *new_end, size_t k);
 /* Host only, no context, no GPU: the reduction pie_set_end applies to its call.  keep_out[i] = 1 iff element i is the last
  * occurrence of rows[i] in rows[0, k), else 0 (any int32 is a row here; k = 0 is allowed).  For tests. */

@@ -803,9 +803,11 @@ class PieScan:
         self._check(self._lib.pie_shard_info(self._ctx, C.byref(r), C.byref(w), C.byref(n), C.byref(u), C.byref(b)))
         return {"rank": r.value, "world": w.value, "rows_global": n.value, "users_global": u.value, "map_bytes": b.value}
 
-    def shard_append_rows(self, start, end, user_global, disc, n_users_global):
+    def shard_append_rows(self, start, end, user_global, disc, n_users_global, local_size=None):
         """The rows are rows [N_g, N_g + k) of the unsharded table, users as GLOBAL ids; this shard keeps the rows whose user
-        hashes to it.  -> (first global row, rows kept)"""
+        hashes to it.  local_size = (rows, users) of the shard after the call, for a caller that knows them and must not
+        wait: without it they are asked of pie_table_info_get, which waits once for the timing event of a hot-index build.
+        -> (first global row, rows kept)"""
         start, end = _col(start, np.int64), _col(end, np.int64)
         user_global, disc = _col(user_global, np.int32), _col(disc, np.int32)
         k = start.shape[0]
@@ -814,8 +816,11 @@ class PieScan:
         first, kept = C.c_int32(0), C.c_size_t(0)
         self._check(self._lib.pie_shard_append_rows(self._ctx, _ptr(start), _ptr(end), _ptr(user_global), _ptr(disc), k, int(n_users_global),
                                                     C.byref(first), C.byref(kept)))
-        ti = self.table_info()  # the shard's own rows and users, from the context (host state: nothing is waited for)
-        self.n, self.n_users = int(ti["rows"]), int(ti["users"])
+        if local_size is not None:
+            self.n, self.n_users = int(local_size[0]), int(local_size[1])
+        else:
+            ti = self.table_info()  # the shard's own rows and users, from the context (host state, but see local_size)
+            self.n, self.n_users = int(ti["rows"]), int(ti["users"])
         return int(first.value), int(kept.value)
 
     def shard_set_end(self, rows_global, new_end):

@@ -266,6 +266,22 @@ def same(got, want, tag):
         assert a.dtype == b.dtype and np.array_equal(a, b), (tag, name)
 
 
+def check_union(tag, un, wants, wide):
+    """Every query's list is a filter of the union, in order; no union row without a query, no bit beyond the batch."""
+    uoff, rows, masks = un
+    nq = len(wants)
+    bits = masks.reshape(rows.size, (nq + 63) // 64)
+    any_bit = np.zeros(rows.size, bool)
+    for qi, w in enumerate(wants):
+        sel = ((bits[:, qi // 64] >> np.uint64(qi % 64)) & np.uint64(1)) == 1
+        any_bit |= sel
+        csum = np.concatenate([[0], np.cumsum(sel)])
+        assert np.array_equal(rows[sel], w[2]) and np.array_equal(csum[uoff], w[1]), (tag, "union", "wide" if wide else "", qi)
+    assert np.all(any_bit), (tag, "a union row no query selected")
+    if nq % 64:
+        assert not np.any(bits[:, nq // 64] >> np.uint64(nq % 64)), (tag, "a query bit beyond the batch")
+
+
 def ctx_with_env(pie, hot, async_mut):
     """A context created under PIE_HOT_INDEX / PIE_ASYNC_MUTATIONS; the environment is restored before returning."""
     want = {"PIE_HOT_INDEX": "1" if hot else "0", "PIE_ASYNC_MUTATIONS": "1" if async_mut else "0"}
@@ -279,6 +295,25 @@ def ctx_with_env(pie, hot, async_mut):
                 os.environ.pop(k, None)
             else:
                 os.environ[k] = v
+
+
+def shard_owner(oracle, owner, n_users, world):
+    """owner[u] = the shard user u hashes to, extended from the users `owner` already covers to n_users."""
+    more = [oracle.shard_of(u, world) for u in range(owner.size, n_users)]
+    return np.concatenate([owner, np.array(more, np.int32)]) if more else owner
+
+
+def shard_view(m, rank, owner):
+    """The shard `rank` holds of the UNSHARDED model m, as a model of its own: the rows of the users with owner[u] == rank in
+    table order, those users re-numbered densely in ascending global id (a shard without a user keeps one).
+    -> (model, global rows it holds ascending, global users ascending)"""
+    rows = np.nonzero(owner[m.user] == rank)[0] if m.n else np.zeros(0, np.int64)
+    users = np.nonzero(owner[:m.U] == rank)[0]
+    local = np.full(m.U, -1, np.int32)
+    local[users] = np.arange(users.size, dtype=np.int32)
+    v = TableModel(m.oracle)
+    v.load(m.start[rows], m.end[rows], local[m.user[rows]], m.disc[rows], max(int(users.size), 1), m.D)
+    return v, rows.astype(np.int32), users.astype(np.int32)
 
 
 # ------------------------------------------------------------------------------------------------ key-edge sweeps
@@ -492,19 +527,7 @@ class Chain:
             assert np.array_equal(ctx.batch_read_user_feed(qi, u), w[2][w[1][u]:w[1][u + 1]]), (tag, "feed", qi, u)
 
     def check_union(self, tag, un, wants, wide):
-        """Every query's list is a filter of the union, in order; no union row without a query, no bit beyond the batch."""
-        uoff, rows, masks = un
-        nq = len(wants)
-        bits = masks.reshape(rows.size, (nq + 63) // 64)
-        any_bit = np.zeros(rows.size, bool)
-        for qi, w in enumerate(wants):
-            sel = ((bits[:, qi // 64] >> np.uint64(qi % 64)) & np.uint64(1)) == 1
-            any_bit |= sel
-            csum = np.concatenate([[0], np.cumsum(sel)])
-            assert np.array_equal(rows[sel], w[2]) and np.array_equal(csum[uoff], w[1]), (tag, "union", "wide" if wide else "", qi)
-        assert np.all(any_bit), (tag, "a union row no query selected")
-        if nq % 64:
-            assert not np.any(bits[:, nq // 64] >> np.uint64(nq % 64)), (tag, "a query bit beyond the batch")
+        check_union(tag, un, wants, wide)
 
     def one_batch(self, tag, qs):
         ctx = self.ctx
