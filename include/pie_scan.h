@@ -407,6 +407,11 @@ typedef struct pie_table_info {
     uint32_t hot_order;       /* records inside a bin of the index: 0 ascending row, 1 by histogram slot (the order of the index
                                * that stands; with none, the order the next build will try: PIE_HOT_ORDER) */
     uint32_t hot_slot_bits;   /* bits of a histogram slot in the sort key at the present user count */
+    /* fields below were added with the token index (pie_token_*), under the same rule */
+    uint64_t token_rows;      /* rows the token column covers (0: there is none) */
+    uint64_t token_bytes;     /* device memory of the token column (16 B per row of capacity), its index (4 B per slot) and the lookup staging */
+    uint64_t token_builds;    /* times the index was built from the column (pie_token_set, growth, compaction) */
+    double token_build_ms;    /* device time of the last such build (HIP events around the fill and the insert pass) */
 } pie_table_info;
 int pie_table_info_get(pie_ctx *ctx, pie_table_info *out);
 /* The hot index's layout, for tests and tools (host-only readers; not while a scan is in flight).  The index groups the rows
@@ -535,6 +540,50 @@ int pie_compact_translate(pie_ctx *ctx, int32_t *rows_inout, size_t k);
  * the contiguous unit every wave owns, blocks of the grid (any output may be NULL).  For tests that straddle the boundaries. */
 int pie_compact_geometry(pie_ctx *ctx, size_t n, int32_t *rows_per_wave_step_out, int32_t *rows_per_block_step_out,
                          int64_t *rows_per_unit_out, int32_t *blocks_out);
+
+/* ---- token index: getSession / touchSession / deleteSession BY TOKEN (server/sessionStore.js:21-53) -----------------------
+ * The reference keys its Map by sha256(token) (sessionStore.js:8-10, :17).  The table carries that key as a column of its own:
+ * the FIRST 16 BYTES of the digest as two little-endian uint64 per row, tok[row][2] (128 bits of a cryptographic hash: at 10^8
+ * rows the probability that any two sessions collide is below 10^-22).  The device never hashes a token; the host does
+ * (binding.token_key, host/tokenKeys.js).  From the column the library derives an open-addressing index — int32 slot_row[slots],
+ * -1 empty, slots = pie_token_slots_for(covered) so it is at most half full, home slot = the top log2(slots) bits of a 64-bit mix
+ * of the key (pie_token_homes), linear probing that wraps; a slot holds the row only, a probe compares against tok[row] — and a
+ * batched lookup answers all the requests of one event-loop turn in one launch.
+ * The column covers a PREFIX of the table, rows [0, covered): rows appended with pie_append_rows are not findable until
+ * pie_token_append gives them keys.  There is no deleted state: tombstoned and expired rows stay findable and report live = 0
+ * (all that `sessions.delete(hash)` on an expired lookup achieves, :30-33); an entry leaves when pie_compact_rows drops its row.
+ * Of several rows under one key (a caller error in the reference: tokens are 48 random bytes) the LARGEST row answers.
+ * Everything is queued on the context's stream, where pie_append_rows and pie_set_end queue their work: a lookup sees every
+ * append, touch and pie_token_append issued before it with no host wait in between, and waits once, for its results.
+ * What renumbers or replaces the table drops the column and index (pie_load_columns, pie_load_columns_dir, pie_gen_synthetic*,
+ * pie_shard_table).  pie_compact_rows that drops rows carries them over: the keys of the kept covered rows are gathered (they are
+ * a prefix again: covered = the kept rows whose old row was covered) and the index is rebuilt; the column keeps its capacity
+ * under PIE_COMPACT_SHRINK; if that step runs out of memory the compaction stands and the column is dropped.
+ * A SHARDED context (after pie_shard_table) is out of scope: pie_token_set returns PIE_E_STATE there.
+ * PIE_E_STATE: no table; no token column (all but pie_token_set); while a scan or batch is in flight (every call that takes a
+ * context).  PIE_E_INVAL: NULL tok with k > 0.  PIE_E_HIP "probe bound exhausted": a probe loop ran its bound of `slots` steps
+ * (an index out of step with its column — never seen; reported by the lookup or build that follows it).
+ * Memory: 16 B per row of capacity + 4 B per slot (8 .. 16 B per covered row). */
+/* keys for rows [0, n), n <= rows; replaces any earlier column; builds the index (replaces `sessions.set(hash, ...)`, :17) */
+int pie_token_set(pie_ctx *ctx, const uint64_t *tok /* [n][2] */, size_t n);
+/* createSession's `sessions.set` (:17) for rows appended since: keys for rows [covered, covered + k); PIE_E_INVAL if
+ * covered + k > rows; queued, un-waited.  An append that would make covered > slots / 2 first rebuilds the index into
+ * pie_token_slots_for(new covered) slots (the new table is allocated first: on PIE_E_NOMEM nothing has changed). */
+int pie_token_append(pie_ctx *ctx, const uint64_t *tok, size_t k);
+/* getSession for k tokens (sessionStore.js:21-35): row_out[i] = row or -1; live_out[i] = found && end > now;
+ * user/start/end of found rows (undefined for -1).  Every output pointer may be NULL.  k = 0 is allowed. */
+int pie_token_lookup(pie_ctx *ctx, const uint64_t *tok, size_t k, int64_t now, int32_t *row_out, uint8_t *live_out,
+                     int32_t *user_out, int64_t *start_out, int64_t *end_out);
+/* touchSession / deleteSession by token (:37-53): for every element whose key is found with end > now, end[row] = new_end[i],
+ * through pie_set_end's own path (repeats: last element wins; both keys, hot index and ordered run stay in step).
+ * rows_out[i] (may be NULL) = the row written or -1.  now = PIE_END_NONE applies to every found row that is not a tombstone. */
+int pie_token_set_end(pie_ctx *ctx, const uint64_t *tok, const int64_t *new_end, size_t k, int64_t now, int32_t *rows_out);
+/* tests and tools: *covered_out, *slots_out; slot_row_out[cap] (PIE_E_CAPACITY if cap < slots); tok_out[covered][2]; any may be NULL */
+int pie_token_layout(pie_ctx *ctx, size_t *covered_out, size_t *slots_out, int32_t *slot_row_out, size_t cap, uint64_t *tok_out);
+/* host only, no context, no GPU: the smallest power of two >= max(1024, 2 * covered); home_out[i] = the home slot of key i in
+ * a table of 2^log2_slots slots (log2_slots <= 32, PIE_E_INVAL otherwise) — the rule the device applies */
+size_t pie_token_slots_for(size_t covered);
+int pie_token_homes(const uint64_t *tok, size_t k, uint32_t log2_slots, uint32_t *home_out);
 
 /* Host only, no context, no GPU: what the batched pass stores per selected row.  A row's 64-bit query mask is
  * live[r] & win[w] & disc[d] (r: queries whose `now` lies below the row's end, w: queries whose cutoff is <= its start, d: its

@@ -35,6 +35,7 @@ class PieTableInfo(C.Structure):
         ("ordered_respreads", C.c_uint64), ("hot_rows", C.c_uint64), ("hot_bytes", C.c_uint64), ("hot_builds", C.c_uint64),
         ("compact_bytes", C.c_uint64), ("compactions", C.c_uint64), ("compact_count_ms", C.c_double), ("compact_write_ms", C.c_double),
         ("hot_build_ms", C.c_double), ("hot_order", C.c_uint32), ("hot_slot_bits", C.c_uint32),
+        ("token_rows", C.c_uint64), ("token_bytes", C.c_uint64), ("token_builds", C.c_uint64), ("token_build_ms", C.c_double),
     ]
 
 
@@ -189,6 +190,13 @@ _SIGS = [
     ("pie_comm_set_end", C.c_int, [_P, _P, _P, C.c_size_t]),
     ("pie_comm_delete_user", C.c_int, [_P, C.c_int32, _P, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int32)]),
     ("pie_comm_table_size", C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
+    ("pie_token_set", C.c_int, [_P, _P, C.c_size_t]),
+    ("pie_token_append", C.c_int, [_P, _P, C.c_size_t]),
+    ("pie_token_lookup", C.c_int, [_P, _P, C.c_size_t, C.c_int64, _P, _P, _P, _P, _P]),
+    ("pie_token_set_end", C.c_int, [_P, _P, _P, C.c_size_t, C.c_int64, _P]),
+    ("pie_token_layout", C.c_int, [_P, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), _P, C.c_size_t, _P]),
+    ("pie_token_slots_for", C.c_size_t, [C.c_size_t]),
+    ("pie_token_homes", C.c_int, [_P, C.c_size_t, C.c_uint32, _P]),
 ]
 ABI_SYMBOLS = [s[0] for s in _SIGS]
 
@@ -782,6 +790,44 @@ class PieScan:
         return ms.value, calls.value, alg.value
 
     # ---- sharding on the device
+    # ---- token index (pie_token_*): keys are uint64 arrays of shape (k, 2), see token_key
+    def token_set(self, keys):
+        """Keys for rows [0, len(keys)); replaces any earlier column and builds the index."""
+        keys = _keys(keys)
+        self._check(self._lib.pie_token_set(self._ctx, _ptr(keys), keys.shape[0]))
+
+    def token_append(self, keys):
+        """Keys for the rows behind the covered prefix; queued, not waited for."""
+        keys = _keys(keys)
+        self._check(self._lib.pie_token_append(self._ctx, _ptr(keys), keys.shape[0]))
+
+    def token_lookup(self, keys, now):
+        """getSession for every key -> dict of arrays: row (-1: not found), live, user, start, end."""
+        keys = _keys(keys)
+        k = keys.shape[0]
+        out = {"row": np.empty(k, np.int32), "live": np.empty(k, np.uint8), "user": np.empty(k, np.int32),
+               "start": np.empty(k, np.int64), "end": np.empty(k, np.int64)}
+        self._check(self._lib.pie_token_lookup(self._ctx, _ptr(keys), k, int(now), _ptr(out["row"]), _ptr(out["live"]), _ptr(out["user"]),
+                                               _ptr(out["start"]), _ptr(out["end"])))
+        return out
+
+    def token_set_end(self, keys, new_end, now):
+        """touchSession / deleteSession by token -> the row written per element (-1: unknown, expired or tombstoned)."""
+        keys, new_end = _keys(keys), _col(new_end, np.int64)
+        if new_end.shape[0] != keys.shape[0]:
+            raise ValueError("one new_end per key")
+        rows = np.empty(keys.shape[0], np.int32)
+        self._check(self._lib.pie_token_set_end(self._ctx, _ptr(keys), _ptr(new_end), keys.shape[0], int(now), _ptr(rows)))
+        return rows
+
+    def token_layout(self):
+        """-> (covered, slots, slot_row[slots], keys[covered, 2]) of the index, for tests and tools."""
+        cov, slots = C.c_size_t(0), C.c_size_t(0)
+        self._check(self._lib.pie_token_layout(self._ctx, C.byref(cov), C.byref(slots), None, 0, None))
+        slot_row, keys = np.empty(slots.value, np.int32), np.empty((cov.value, 2), np.uint64)
+        self._check(self._lib.pie_token_layout(self._ctx, C.byref(cov), C.byref(slots), _ptr(slot_row), slots.value, _ptr(keys)))
+        return cov.value, slots.value, slot_row, keys
+
     def shard_table(self, rank, world):
         """Keep only the rows of the users that hash to `rank` of `world`, users re-numbered densely.  -> (n_rows, n_users)"""
         n, u = C.c_size_t(0), C.c_int32(0)
@@ -1184,6 +1230,36 @@ def split_wide_message(msg, u_pad, cap, words):
     base = u_pad + 2 + cap
     masks = msg[base: base + k * 2 * words].astype("<i4").view("<u8").reshape(k, words).astype(np.uint64)
     return uoff, mu, rows, masks
+
+
+def _keys(keys):
+    keys = np.ascontiguousarray(keys, dtype=np.uint64)
+    if keys.ndim != 2 or keys.shape[1] != 2:
+        raise ValueError("token keys are a uint64 array of shape (k, 2)")
+    return keys
+
+
+def token_key(token):
+    """The key of a session token: the first 16 bytes of sha256(token) (the reference's Map key, server/sessionStore.js:8-10)
+    as two little-endian 64-bit words -> uint64 array of shape (2,)."""
+    import hashlib
+    if isinstance(token, str):
+        token = token.encode("utf-8")
+    return np.frombuffer(hashlib.sha256(token).digest()[:16], dtype="<u8").astype(np.uint64)
+
+
+def token_slots_for(covered):
+    return int(load_library().pie_token_slots_for(int(covered)))
+
+
+def token_homes(keys, log2_slots):
+    """Home slot of every key in an index of 2 ** log2_slots slots (pie_token_homes: the rule the device applies)."""
+    keys = _keys(keys)
+    out = np.empty(keys.shape[0], np.uint32)
+    rc = load_library().pie_token_homes(_ptr(keys), keys.shape[0], int(log2_slots), _ptr(out))
+    if rc != 0:
+        raise PieError(rc, "pie_token_homes")
+    return out
 
 
 def shard_of(user, n_shards):

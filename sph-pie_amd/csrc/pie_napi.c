@@ -93,7 +93,11 @@
     X(int, pie_compact_rows, (pie_ctx *, int64_t, uint32_t, size_t *))                                              \
     X(int, pie_compact_maps, (pie_ctx *, int32_t *, int32_t *, size_t *, size_t *))                                 \
     X(int, pie_compact_map_device_ptrs, (pie_ctx *, void **, void **, size_t *, size_t *))                          \
-    X(int, pie_compact_translate, (pie_ctx *, int32_t *, size_t))
+    X(int, pie_compact_translate, (pie_ctx *, int32_t *, size_t))                                                   \
+    X(int, pie_token_set, (pie_ctx *, const uint64_t *, size_t))                                                    \
+    X(int, pie_token_append, (pie_ctx *, const uint64_t *, size_t))                                                 \
+    X(int, pie_token_lookup, (pie_ctx *, const uint64_t *, size_t, int64_t, int32_t *, uint8_t *, int32_t *, int64_t *, int64_t *)) \
+    X(int, pie_token_set_end, (pie_ctx *, const uint64_t *, const int64_t *, size_t, int64_t, int32_t *))
 
 #define X(ret, name, args) static ret(*p_##name) args;
 PIE_SYMBOLS(X)
@@ -2012,6 +2016,99 @@ static napi_value fn_set_batch_lanes(napi_env env, napi_callback_info info)
     return js_int(env, p_pie_batch_lanes(ctx));
 }
 
+/* ---- token index (pie_token_*): keys travel as a BigUint64Array of length 2 k (host/tokenKeys.js) ------------------------ */
+static uint64_t *token_keys(napi_env env, napi_value v, size_t *k)
+{
+    size_t n = 0;
+    uint64_t *keys = typed(env, v, napi_biguint64_array, &n);
+    if (!keys || (n & 1)) {
+        napi_throw_type_error(env, NULL, "token keys: a BigUint64Array of two words per key");
+        return NULL;
+    }
+    *k = n / 2;
+    return keys;
+}
+
+/* tokenSet(ctx, keys) / tokenAppend(ctx, keys) -> k */
+static napi_value token_set_or_append(napi_env env, napi_callback_info info, int append)
+{
+    ARGS(2)
+    pie_ctx *ctx = get_ctx(env, argv[0]);
+    if (!ctx) return NULL;
+    size_t k = 0;
+    uint64_t *keys = token_keys(env, argv[1], &k);
+    if (!keys) return NULL;
+    int rc = append ? p_pie_token_append(ctx, keys, k) : p_pie_token_set(ctx, keys, k);
+    if (rc) return throw_pie(env, ctx, rc);
+    return js_int(env, (int64_t)k);
+}
+static napi_value fn_token_set(napi_env env, napi_callback_info info) { return token_set_or_append(env, info, 0); }
+static napi_value fn_token_append(napi_env env, napi_callback_info info) { return token_set_or_append(env, info, 1); }
+
+/* a fresh typed array of n elements of `size` bytes as property `name` of obj; -> its storage */
+static void *token_out(napi_env env, napi_value obj, const char *name, napi_typedarray_type type, size_t size, size_t n)
+{
+    napi_value buf, arr;
+    void *data = NULL;
+    if (napi_create_arraybuffer(env, n * size, &data, &buf) != napi_ok || napi_create_typedarray(env, type, n, buf, 0, &arr) != napi_ok ||
+        napi_set_named_property(env, obj, name, arr) != napi_ok) {
+        napi_throw_error(env, NULL, "N-API call failed: result array");
+        return NULL;
+    }
+    return data ? data : (void *)(uintptr_t)16;
+}
+
+/* tokenLookup(ctx, keys, now) -> {row Int32Array, live Uint8Array, user Int32Array, start BigInt64Array, end BigInt64Array} */
+static napi_value fn_token_lookup(napi_env env, napi_callback_info info)
+{
+    ARGS(3)
+    pie_ctx *ctx = get_ctx(env, argv[0]);
+    if (!ctx) return NULL;
+    size_t k = 0;
+    int64_t now = 0;
+    uint64_t *keys = token_keys(env, argv[1], &k);
+    if (!keys) return NULL;
+    if (!get_i64(env, argv[2], &now)) {
+        napi_throw_type_error(env, NULL, "tokenLookup(ctx, BigUint64Array keys, now)");
+        return NULL;
+    }
+    napi_value out;
+    CHECK(env, napi_create_object(env, &out));
+    int32_t *row = token_out(env, out, "row", napi_int32_array, 4, k);
+    uint8_t *live = token_out(env, out, "live", napi_uint8_array, 1, k);
+    int32_t *user = token_out(env, out, "user", napi_int32_array, 4, k);
+    int64_t *start = token_out(env, out, "start", napi_bigint64_array, 8, k);
+    int64_t *end = token_out(env, out, "end", napi_bigint64_array, 8, k);
+    if (!row || !live || !user || !start || !end) return NULL;
+    int rc = p_pie_token_lookup(ctx, keys, k, now, row, live, user, start, end);
+    if (rc) return throw_pie(env, ctx, rc);
+    return out;
+}
+
+/* tokenSetEnd(ctx, keys, newEnd BigInt64Array, now) -> Int32Array rows written (-1: not found, or not live at `now`) */
+static napi_value fn_token_set_end(napi_env env, napi_callback_info info)
+{
+    ARGS(4)
+    pie_ctx *ctx = get_ctx(env, argv[0]);
+    if (!ctx) return NULL;
+    size_t k = 0, k2 = 0;
+    int64_t now = 0;
+    uint64_t *keys = token_keys(env, argv[1], &k);
+    if (!keys) return NULL;
+    int64_t *ne = typed(env, argv[2], napi_bigint64_array, &k2);
+    if (!ne || k2 != k || !get_i64(env, argv[3], &now)) {
+        napi_throw_type_error(env, NULL, "tokenSetEnd(ctx, BigUint64Array keys, BigInt64Array newEnd, now)");
+        return NULL;
+    }
+    napi_value buf, out;
+    void *data = NULL;
+    CHECK(env, napi_create_arraybuffer(env, k * 4, &data, &buf));
+    int rc = p_pie_token_set_end(ctx, keys, ne, k, now, (int32_t *)data);
+    if (rc) return throw_pie(env, ctx, rc);
+    CHECK(env, napi_create_typedarray(env, napi_int32_array, k, buf, 0, &out));
+    return out;
+}
+
 static napi_value init(napi_env env, napi_value exports)
 {
     static const struct {
@@ -2034,6 +2131,7 @@ static napi_value init(napi_env env, napi_value exports)
         {"commWideStepStatus", fn_comm_wide_step_status}, {"commWideStepReadGathered", fn_comm_wide_step_read}, {"commExpiredQueue", fn_comm_expired_queue}, {"commArchiveQueue", fn_comm_archive_queue},
         {"commAppendRows", fn_comm_append_rows}, {"commSetEnd", fn_comm_set_end}, {"commDeleteUser", fn_comm_delete_user}, {"commTableSize", fn_comm_table_size},
         {"shardMaps", fn_shard_maps},
+        {"tokenSet", fn_token_set}, {"tokenAppend", fn_token_append}, {"tokenLookup", fn_token_lookup}, {"tokenSetEnd", fn_token_set_end},
     };
     for (size_t i = 0; i < sizeof table / sizeof table[0]; ++i) {
         napi_value fn;

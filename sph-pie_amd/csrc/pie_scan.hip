@@ -21,6 +21,7 @@
 #include "../../include/pie_scan.h"
 #include "pie_kernels.h"
 #include "pie_ordered.h"
+#include "pie_token.h"
 
 #include <hip/hip_runtime.h>
 
@@ -320,6 +321,23 @@ struct pie_ctx {
     long long *adopt_start = nullptr, *adopt_end = nullptr; // set by pie_compact_rows around its ensure_capacity call only: columns the
     int *adopt_user = nullptr, *adopt_disc = nullptr;       // re-allocated table takes over instead of allocating its own
     unsigned long long compactions = 0;
+    // The token column and its index (pie_token.h): absent (tok == nullptr) until pie_token_set; dropped by whatever renumbers or
+    // replaces the table; pie_compact_rows carries it over (`hold` keeps it through that call's ensure_capacity).
+    struct TokenIndex {
+        TokKey* tok = nullptr;      // [cap] keys of the rows [0, covered)
+        long long cap = 0, covered = 0;
+        int* slot_row = nullptr;    // [1 << log2_slots]
+        unsigned log2_slots = 0;
+        unsigned int* status = nullptr; // [kTokStatusWords], device
+        char* h_stage = nullptr;    // pinned host + device staging of a lookup: keys in, results and the status words out
+        char* d_stage = nullptr;
+        size_t stage_bytes = 0;
+        hipEvent_t ev[2] = {};      // around the last rebuild (build_ms)
+        bool timed = false;
+        bool hold = false;
+        double build_ms = 0;
+        unsigned long long builds = 0;
+    } tokx;
     double cmp_count_ms = 0;       // ... of its count pass and prefix alone
     double cmp_write_ms = 0;       // ... of its write pass (HIP events)
 
@@ -674,6 +692,19 @@ OrdMirror ord_mirror_of(const pie_ctx* c)
     return m;
 }
 
+// the token column and its index go (no-op when there is none); the status array, the staging and the counters stay
+void token_drop(pie_ctx* c)
+{
+    pie_ctx::TokenIndex& t = c->tokx;
+    t.hold = false;
+    if (!t.tok && !t.slot_row) return;
+    (void)hipStreamSynchronize(c->stream);
+    dfree(t.tok);
+    dfree(t.slot_row);
+    t.cap = t.covered = 0;
+    t.log2_slots = 0;
+}
+
 void cmp_forget(pie_ctx* c)
 {
     dfree(c->d_cmp_new_of_old);
@@ -818,6 +849,7 @@ int ensure_capacity(pie_ctx* c, long long n, int n_users, long long keep_rows = 
     if (rc) return rc;
     ord_invalidate(c, keep_rows == 0);
     if (keep_rows == 0) cmp_forget(c); // a new table (load, gen, shard, compact) renumbers the rows: the last compaction's maps go
+    if (keep_rows == 0 && !c->tokx.hold) token_drop(c); // ... the token keys name the old rows (pie_compact_rows carries them over itself)
     if (keep_rows == 0) c->shard_on = false; // ... and it is no shard of anything until pie_shard_table says so (pie_compact_rows restores it)
     long long rows = n > 0 ? n : 1;
     if (rows > c->cap_rows || n_users > c->cap_users) {
@@ -3641,6 +3673,12 @@ int pie_ctx_destroy(pie_ctx* c)
     dfree(c->d_shard_rows);
     dfree(c->d_shard_users);
     cmp_forget(c);
+    token_drop(c);
+    dfree(c->tokx.status);
+    dfree(c->tokx.d_stage);
+    if (c->tokx.h_stage) (void)hipHostFree(c->tokx.h_stage);
+    for (hipEvent_t e : c->tokx.ev)
+        if (e) (void)hipEventDestroy(e);
     dfree(c->d_stage);
     if (c->h_stage) (void)hipHostFree(c->h_stage);
     for (auto& a : c->astage) {
@@ -5150,12 +5188,15 @@ int pie_set_scan_form(pie_ctx* c, int form)
     return PIE_OK;
 }
 
+static void token_info(pie_ctx* c, pie_table_info* out);
+
 int pie_table_info_get(pie_ctx* c, pie_table_info* out)
 {
     if (!c || !out) return PIE_E_INVAL;
     // the struct grows at its end: a caller built against the form without the compaction fields gets the fields it knows
     const uint32_t caller_size = out->struct_size;
-    if (caller_size != sizeof(pie_table_info) && caller_size != offsetof(pie_table_info, hot_build_ms) && caller_size != offsetof(pie_table_info, compact_bytes))
+    if (caller_size != sizeof(pie_table_info) && caller_size != offsetof(pie_table_info, token_rows) && caller_size != offsetof(pie_table_info, hot_build_ms) &&
+        caller_size != offsetof(pie_table_info, compact_bytes))
         return fail(c, PIE_E_INVAL, "pie_table_info.struct_size mismatch");
     pie_table_info full{};
     pie_table_info* const caller = out;
@@ -5217,6 +5258,7 @@ int pie_table_info_get(pie_ctx* c, pie_table_info* out)
     out->compactions = c->compactions;
     out->compact_count_ms = c->cmp_count_ms;
     out->compact_write_ms = c->cmp_write_ms;
+    token_info(c, out);
     full.struct_size = caller_size;
     memcpy(caller, &full, caller_size);
     return PIE_OK;
@@ -5880,6 +5922,8 @@ int pie_shard_rows_to_global(pie_ctx* c, int32_t* rows_inout, size_t k) { return
 // Rows per unit (= per wave) and the grid of the two compaction passes: every wave of every block owns one contiguous unit, a
 // whole number of 128-row steps; the grid comes from the chip (8 blocks per CU: the passes are streams, and a wave keeps one
 // step in flight), a small table gets as many units as it has steps.
+static int token_after_compact(pie_ctx* c, long long n_old);
+
 static void compact_plan(const pie_ctx* c, long long n, int* blocks_out, long long* rows_per_unit_out)
 {
     long long blocks = (n + kCmpBlockRows - 1) / kCmpBlockRows;
@@ -6004,6 +6048,7 @@ int pie_compact_rows(pie_ctx* c, int64_t dead_before, uint32_t flags, size_t* n_
     if (!same) {
         // 3. the table takes the new columns: as a new table of the same users (what the last scans learned is forgotten, the
         // ordered run is invalid, results and queues are gone), in the old capacity or a right-sized one
+        c->tokx.hold = c->tokx.tok != nullptr; // the token column outlives the ensure_capacity below: token_after_compact renumbers it
         if (shrink) {
             // the kept rows already sit in right-sized columns: the new table is built around them (as in pie_shard_table, a
             // failure past this point leaves the context without a table)
@@ -6013,10 +6058,10 @@ int pie_compact_rows(pie_ctx* c, int64_t dead_before, uint32_t flags, size_t* n_
             o_user = o_disc = nullptr;
             rc = ensure_capacity(c, kept, users);
             dfree(c->adopt_start); dfree(c->adopt_end); dfree(c->adopt_user); dfree(c->adopt_disc); // taken (null by now) unless it failed early
-            if (rc) { cleanup(); return rc; }
+            if (rc) { token_drop(c); cleanup(); return rc; }
         } else {
             rc = ensure_capacity(c, kept, users);
-            if (rc) { cleanup(); return rc; }
+            if (rc) { token_drop(c); cleanup(); return rc; }
             dfree(c->d_start); dfree(c->d_end); dfree(c->d_user); dfree(c->d_disc);
             c->d_start = o_start; c->d_end = o_end; c->d_user = o_user; c->d_disc = o_disc;
             o_start = o_end = nullptr;
@@ -6052,9 +6097,9 @@ int pie_compact_rows(pie_ctx* c, int64_t dead_before, uint32_t flags, size_t* n_
     if (n_kept_out) *n_kept_out = (size_t)kept;
     if (same) return PIE_OK;
     rc = build_keys(c, 0);
-    if (rc) return rc;
+    if (rc) { token_drop(c); return rc; }
     PIE_HIP(c, hipStreamSynchronize(s));
-    return PIE_OK;
+    return token_after_compact(c, n);
 }
 
 int pie_compact_maps(pie_ctx* c, int32_t* new_of_old_out, int32_t* old_of_new_out, size_t* n_old_out, size_t* n_kept_out)
@@ -6133,6 +6178,377 @@ int32_t pie_shard_of(int32_t user, int32_t n_shards)
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
     z ^= z >> 31;
     return (int32_t)(z % (unsigned long long)n_shards);
+}
+
+// ---- the token column and its index (pie_token.h): getSession / touchSession / deleteSession by token hash ------------------
+// Everything is queued on the context's stream.  The host tracks `covered` and the slot count; the device tracks nothing but the
+// status words, which a lookup brings back with its results (an exhausted probe bound of an earlier, un-waited insert included).
+
+size_t pie_token_slots_for(size_t covered)
+{
+    size_t s = 1024;
+    while (s / 2 < covered && (s << 1) != 0) s <<= 1;
+    return s;
+}
+
+int pie_token_homes(const uint64_t* tok, size_t k, uint32_t log2_slots, uint32_t* home_out)
+{
+    if (log2_slots > 32 || (k && (!tok || !home_out))) return PIE_E_INVAL;
+    for (size_t i = 0; i < k; ++i) home_out[i] = (uint32_t)token_home(tok[2 * i], tok[2 * i + 1], log2_slots);
+    return PIE_OK;
+}
+
+static unsigned token_log2(size_t slots)
+{
+    unsigned b = 0;
+    while (((size_t)1 << b) < slots) ++b;
+    return b;
+}
+
+// the checks every pie_token_* call that takes a context begins with
+static int token_ready(pie_ctx* c, const char* what, bool need_column)
+{
+    if (c->cap_rows == 0) return fail(c, PIE_E_STATE, "%s: no table loaded", what);
+    if (c->n_flight || c->b_flight) return fail(c, PIE_E_STATE, "%s while a scan or batch is in flight", what);
+    if (need_column && !c->tokx.tok) return fail(c, PIE_E_STATE, "%s: the table has no token column (pie_token_set gives it one)", what);
+    return PIE_OK;
+}
+
+static int token_status_alloc(pie_ctx* c)
+{
+    if (c->tokx.status) return PIE_OK;
+    PIE_HIP(c, hipMalloc(&c->tokx.status, kTokStatusWords * sizeof(unsigned int)));
+    PIE_HIP(c, hipMemsetAsync(c->tokx.status, 0, kTokStatusWords * sizeof(unsigned int), c->stream));
+    return PIE_OK;
+}
+
+// st[] = the status words as read back behind a waited call: set -> cleared on the device, PIE_E_HIP
+static int token_status_check(pie_ctx* c, const unsigned int* st, const char* what)
+{
+    if (!st[0] && !st[1]) return PIE_OK;
+    (void)hipMemsetAsync(c->tokx.status, 0, kTokStatusWords * sizeof(unsigned int), c->stream);
+    return fail(c, PIE_E_HIP, "%s: probe bound exhausted (%s ran %llu steps without meeting an empty slot)", what,
+                st[0] ? "an insert" : "a lookup", 1ull << c->tokx.log2_slots);
+}
+
+static int token_status_wait(pie_ctx* c, const char* what)
+{
+    unsigned int st[kTokStatusWords] = {};
+    PIE_HIP(c, hipMemcpyAsync(st, c->tokx.status, sizeof st, hipMemcpyDeviceToHost, c->stream));
+    PIE_HIP(c, hipStreamSynchronize(c->stream));
+    return token_status_check(c, st, what);
+}
+
+static int token_insert(pie_ctx* c, long long row0, long long k)
+{
+    pie_ctx::TokenIndex& t = c->tokx;
+    if (k <= 0) return PIE_OK;
+    hipLaunchKernelGGL(k_token_insert, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, c->stream, (const TokKey*)t.tok, row0, k, t.slot_row,
+                       t.log2_slots, t.status);
+    PIE_HIP(c, hipGetLastError());
+    return PIE_OK;
+}
+
+// every slot empty, then the rows [0, covered) inserted; queued, timed by two events (pie_table_info.token_build_ms)
+static int token_rebuild(pie_ctx* c)
+{
+    pie_ctx::TokenIndex& t = c->tokx;
+    for (hipEvent_t& e : t.ev)
+        if (!e) PIE_HIP(c, hipEventCreate(&e));
+    PIE_HIP(c, hipEventRecord(t.ev[0], c->stream));
+    PIE_HIP(c, hipMemsetAsync(t.slot_row, 0xFF, (size_t)4 << t.log2_slots, c->stream));
+    int rc = token_insert(c, 0, t.covered);
+    if (rc) return rc;
+    PIE_HIP(c, hipEventRecord(t.ev[1], c->stream));
+    t.timed = true;
+    t.builds++;
+    return PIE_OK;
+}
+
+static void token_info(pie_ctx* c, pie_table_info* out)
+{
+    pie_ctx::TokenIndex& t = c->tokx;
+    out->token_rows = t.tok ? (uint64_t)t.covered : 0u;
+    out->token_bytes = (uint64_t)t.cap * sizeof(TokKey) + (t.slot_row ? (uint64_t)4 << t.log2_slots : 0u) +
+                       (t.status ? kTokStatusWords * sizeof(unsigned int) : 0u) + (uint64_t)t.stage_bytes;
+    out->token_builds = t.builds;
+    if (t.timed) { // the last build's device time, read once it has run
+        float ms = 0.f;
+        if (hipEventSynchronize(t.ev[1]) == hipSuccess && hipEventElapsedTime(&ms, t.ev[0], t.ev[1]) == hipSuccess) t.build_ms = ms;
+        else (void)hipGetLastError();
+        t.timed = false;
+    }
+    out->token_build_ms = t.build_ms;
+}
+
+int pie_token_set(pie_ctx* c, const uint64_t* tok, size_t n)
+{
+    if (!c) return PIE_E_INVAL;
+    int rc = token_ready(c, "pie_token_set", false);
+    if (rc) return rc;
+    if (c->shard_on) return fail(c, PIE_E_STATE, "pie_token_set: a sharded context carries no token column");
+    if (n > 0 && !tok) return fail(c, PIE_E_INVAL, "tok is NULL");
+    if ((long long)n > c->n || n > (size_t)c->n) return fail(c, PIE_E_INVAL, "%zu keys for a table of %lld rows", n, c->n);
+    PIE_HIP(c, hipSetDevice(c->device));
+    rc = token_status_alloc(c);
+    if (rc) return rc;
+    pie_ctx::TokenIndex& t = c->tokx;
+    // the new column and table first: a failure leaves what was there
+    const unsigned log2_slots = token_log2(pie_token_slots_for(n));
+    TokKey* nt = nullptr;
+    int* ns = nullptr;
+    if (hipMalloc(&nt, (size_t)c->cap_rows * sizeof(TokKey)) != hipSuccess || hipMalloc(&ns, (size_t)4 << log2_slots) != hipSuccess) {
+        (void)hipGetLastError();
+        dfree(nt);
+        return fail(c, PIE_E_NOMEM, "pie_token_set: no device memory for %lld keys and %llu slots", c->cap_rows, 1ull << log2_slots);
+    }
+    token_drop(c);
+    t.tok = nt;
+    t.cap = c->cap_rows;
+    t.slot_row = ns;
+    t.log2_slots = log2_slots;
+    t.covered = (long long)n;
+    if (n > 0) PIE_HIP(c, hipMemcpyAsync(t.tok, tok, n * sizeof(TokKey), hipMemcpyHostToDevice, c->stream));
+    rc = token_rebuild(c);
+    if (rc) return rc;
+    return token_status_wait(c, "pie_token_set");
+}
+
+int pie_token_append(pie_ctx* c, const uint64_t* tok, size_t k)
+{
+    if (!c) return PIE_E_INVAL;
+    int rc = token_ready(c, "pie_token_append", true);
+    if (rc) return rc;
+    if (k > 0 && !tok) return fail(c, PIE_E_INVAL, "tok is NULL");
+    pie_ctx::TokenIndex& t = c->tokx;
+    if (k > (size_t)(c->n - t.covered)) return fail(c, PIE_E_INVAL, "%zu keys behind %lld covered rows of a table of %lld", k, t.covered, c->n);
+    if (k == 0) return PIE_OK;
+    PIE_HIP(c, hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const long long covered = t.covered + (long long)k;
+    // everything that can fail comes first: the staging area, a longer column (the table grew), a larger table of slots
+    const bool staged = k <= ((size_t)1 << 20);
+    Staged st{};
+    if (staged && (rc = stage_mutation(c, k * sizeof(TokKey), true, &st)) != PIE_OK) return rc;
+    if (c->cap_rows > t.cap) {
+        TokKey* nt = nullptr;
+        PIE_HIP(c, hipMalloc(&nt, (size_t)c->cap_rows * sizeof(TokKey)));
+        hipError_t e = t.covered ? hipMemcpyAsync(nt, t.tok, (size_t)t.covered * sizeof(TokKey), hipMemcpyDeviceToDevice, s) : hipSuccess;
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) {
+            (void)hipFree(nt);
+            return fail(c, PIE_E_HIP, "pie_token_append: %s", hipGetErrorString(e));
+        }
+        dfree(t.tok);
+        t.tok = nt;
+        t.cap = c->cap_rows;
+    }
+    const bool grow = (unsigned long long)covered > ((1ull << t.log2_slots) >> 1);
+    unsigned log2_slots = t.log2_slots;
+    int* ns = nullptr;
+    if (grow) {
+        log2_slots = token_log2(pie_token_slots_for((size_t)covered));
+        PIE_HIP(c, hipMalloc(&ns, (size_t)4 << log2_slots));
+    }
+    hipError_t e;
+    if (staged) {
+        memcpy(st.h, tok, k * sizeof(TokKey));
+        e = hipMemcpyAsync(t.tok + t.covered, st.h, k * sizeof(TokKey), hipMemcpyHostToDevice, s);
+    } else { // a bulk load (tools): straight from the caller's memory, waited for
+        e = hipMemcpyAsync(t.tok + t.covered, tok, k * sizeof(TokKey), hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+    }
+    if (e != hipSuccess) {
+        dfree(ns);
+        return fail(c, PIE_E_HIP, "pie_token_append: %s", hipGetErrorString(e));
+    }
+    if (staged && (rc = stage_queued(c, st)) != PIE_OK) {
+        dfree(ns);
+        return rc;
+    }
+    const long long row0 = t.covered;
+    t.covered = covered;
+    if (!grow) return token_insert(c, row0, (long long)k);
+    PIE_HIP(c, hipStreamSynchronize(s)); // inserts queued earlier still write the table that goes
+    dfree(t.slot_row);
+    t.slot_row = ns;
+    t.log2_slots = log2_slots;
+    return token_rebuild(c);
+}
+
+// offsets of a lookup's staging block for k keys: [keys 16 k | end 8 k | start 8 k | row 4 k | user 4 k | live k | pad | status]
+struct TokStage {
+    size_t end, start, row, user, live, status, bytes;
+};
+static TokStage token_stage_of(size_t k)
+{
+    TokStage o;
+    o.end = k * 16; o.start = k * 24; o.row = k * 32; o.user = k * 36; o.live = k * 40;
+    o.status = (k * 41 + 15) / 16 * 16;
+    o.bytes = o.status + kTokStatusWords * sizeof(unsigned int);
+    return o;
+}
+
+// One launch for k keys; the results and the status words are in tokx.h_stage (token_stage_of) when it returns.
+static int token_lookup_run(pie_ctx* c, const uint64_t* tok, size_t k, long long now, bool want_user, bool want_start, const char* what)
+{
+    pie_ctx::TokenIndex& t = c->tokx;
+    PIE_HIP(c, hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const TokStage o = token_stage_of(k);
+    if (o.bytes > t.stage_bytes) {
+        size_t want = t.stage_bytes ? t.stage_bytes : (size_t)64 << 10;
+        while (want < o.bytes) want *= 2;
+        PIE_HIP(c, hipStreamSynchronize(s));
+        if (t.h_stage) (void)hipHostFree(t.h_stage);
+        dfree(t.d_stage);
+        t.h_stage = nullptr;
+        t.stage_bytes = 0;
+        PIE_HIP(c, hipHostMalloc(&t.h_stage, want, hipHostMallocDefault));
+        PIE_HIP(c, hipMalloc(&t.d_stage, want));
+        t.stage_bytes = want;
+    }
+    char* d = t.d_stage;
+    memcpy(t.h_stage, tok, k * sizeof(TokKey));
+    PIE_HIP(c, hipMemcpyAsync(d, t.h_stage, k * sizeof(TokKey), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_token_lookup, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const TokKey*>(d), (long long)k,
+                       (const int*)t.slot_row, t.log2_slots, (const TokKey*)t.tok, t.covered, (const long long*)c->d_end, (const long long*)c->d_start,
+                       (const int*)c->d_user, now, reinterpret_cast<int*>(d + o.row), reinterpret_cast<unsigned char*>(d + o.live),
+                       want_user ? reinterpret_cast<int*>(d + o.user) : nullptr, want_start ? reinterpret_cast<long long*>(d + o.start) : nullptr,
+                       reinterpret_cast<long long*>(d + o.end), t.status);
+    PIE_HIP(c, hipGetLastError());
+    PIE_HIP(c, hipMemcpyAsync(t.h_stage + o.end, d + o.end, o.status - o.end, hipMemcpyDeviceToHost, s));
+    PIE_HIP(c, hipMemcpyAsync(t.h_stage + o.status, t.status, kTokStatusWords * sizeof(unsigned int), hipMemcpyDeviceToHost, s));
+    PIE_HIP(c, hipStreamSynchronize(s)); // the one wait of a lookup
+    return token_status_check(c, reinterpret_cast<const unsigned int*>(t.h_stage + o.status), what);
+}
+
+int pie_token_lookup(pie_ctx* c, const uint64_t* tok, size_t k, int64_t now, int32_t* row_out, uint8_t* live_out, int32_t* user_out,
+                     int64_t* start_out, int64_t* end_out)
+{
+    if (!c) return PIE_E_INVAL;
+    int rc = token_ready(c, "pie_token_lookup", true);
+    if (rc) return rc;
+    if (k == 0) return PIE_OK;
+    if (!tok) return fail(c, PIE_E_INVAL, "tok is NULL");
+    if (k >= ((size_t)1 << 31)) return fail(c, PIE_E_INVAL, "%zu keys in one lookup", k);
+    rc = token_lookup_run(c, tok, k, (long long)now, user_out != nullptr, start_out != nullptr, "pie_token_lookup");
+    if (rc) return rc;
+    const TokStage o = token_stage_of(k);
+    const char* h = c->tokx.h_stage;
+    if (row_out) memcpy(row_out, h + o.row, k * 4);
+    if (live_out) memcpy(live_out, h + o.live, k);
+    if (user_out) memcpy(user_out, h + o.user, k * 4);
+    if (start_out) memcpy(start_out, h + o.start, k * 8);
+    if (end_out) memcpy(end_out, h + o.end, k * 8);
+    return PIE_OK;
+}
+
+// lookup, read the rows back, then pie_set_end's own path on the elements that qualify: no `end` kernel of its own
+int pie_token_set_end(pie_ctx* c, const uint64_t* tok, const int64_t* new_end, size_t k, int64_t now, int32_t* rows_out)
+{
+    if (!c) return PIE_E_INVAL;
+    int rc = token_ready(c, "pie_token_set_end", true);
+    if (rc) return rc;
+    if (k == 0) return PIE_OK;
+    if (!tok || !new_end) return fail(c, PIE_E_INVAL, "NULL pointer");
+    if (k >= ((size_t)1 << 31)) return fail(c, PIE_E_INVAL, "%zu keys in one call", k);
+    rc = token_lookup_run(c, tok, k, (long long)now, false, false, "pie_token_set_end");
+    if (rc) return rc;
+    const TokStage o = token_stage_of(k);
+    const int32_t* row = reinterpret_cast<const int32_t*>(c->tokx.h_stage + o.row);
+    const uint8_t* live = reinterpret_cast<const uint8_t*>(c->tokx.h_stage + o.live);
+    std::vector<int32_t> rows;
+    std::vector<int64_t> ends;
+    try {
+        rows.reserve(k);
+        ends.reserve(k);
+    } catch (...) {
+        return fail(c, PIE_E_NOMEM, "no memory for %zu touches", k);
+    }
+    for (size_t i = 0; i < k; ++i) {
+        const bool hit = live[i] != 0 && row[i] >= 0 && row[i] < c->n;
+        if (rows_out) rows_out[i] = hit ? row[i] : -1;
+        if (hit) {
+            rows.push_back(row[i]);
+            ends.push_back(new_end[i]);
+        }
+    }
+    if (rows.empty()) return PIE_OK;
+    return set_end_apply(c, rows.data(), ends.data(), rows.size(), false);
+}
+
+int pie_token_layout(pie_ctx* c, size_t* covered_out, size_t* slots_out, int32_t* slot_row_out, size_t cap, uint64_t* tok_out)
+{
+    if (!c) return PIE_E_INVAL;
+    int rc = token_ready(c, "pie_token_layout", true);
+    if (rc) return rc;
+    pie_ctx::TokenIndex& t = c->tokx;
+    const size_t slots = (size_t)1 << t.log2_slots;
+    if (covered_out) *covered_out = (size_t)t.covered;
+    if (slots_out) *slots_out = slots;
+    if (slot_row_out && cap < slots) return fail(c, PIE_E_CAPACITY, "pie_token_layout: %zu slots, room for %zu", slots, cap);
+    PIE_HIP(c, hipSetDevice(c->device));
+    if (slot_row_out) PIE_HIP(c, hipMemcpyAsync(slot_row_out, t.slot_row, slots * 4, hipMemcpyDeviceToHost, c->stream));
+    if (tok_out && t.covered) PIE_HIP(c, hipMemcpyAsync(tok_out, t.tok, (size_t)t.covered * sizeof(TokKey), hipMemcpyDeviceToHost, c->stream));
+    return token_status_wait(c, "pie_token_layout");
+}
+
+// pie_compact_rows dropped rows and the table stands in its new numbering (the maps of the compaction are resident): the keys of
+// the kept covered rows move to their new rows — row order was kept, so they are a prefix again — and the index is rebuilt.
+// Out of memory here drops the token column; the compaction stands either way.
+static int token_after_compact(pie_ctx* c, long long n_old)
+{
+    pie_ctx::TokenIndex& t = c->tokx;
+    t.hold = false;
+    if (!t.tok) return PIE_OK;
+    hipStream_t s = c->stream;
+    const long long kept = c->cmp_n_kept;
+    long long covered = t.covered >= n_old ? kept : 0;
+    if (t.covered < n_old && t.covered > 0 && kept > 0) { // the entries of old_of_new below the old `covered`
+        hipLaunchKernelGGL(k_compact_lower_bound, dim3(1), dim3(1), 0, s, (const int*)c->d_cmp_old_of_new, kept, t.covered, c->d_range);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(&covered, c->d_range, 8, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess || covered < 0 || covered > kept) {
+            token_drop(c);
+            return fail(c, PIE_E_HIP, "pie_compact_rows: token column: %s", hipGetErrorString(e));
+        }
+    }
+    const unsigned log2_slots = token_log2(pie_token_slots_for((size_t)covered));
+    const long long cap = c->cap_rows > t.cap ? c->cap_rows : t.cap;
+    TokKey* nt = nullptr;
+    int* ns = nullptr;
+    if (hipMalloc(&nt, (size_t)cap * sizeof(TokKey)) != hipSuccess || (log2_slots != t.log2_slots && hipMalloc(&ns, (size_t)4 << log2_slots) != hipSuccess)) {
+        (void)hipGetLastError();
+        dfree(nt);
+        token_drop(c);
+        return PIE_OK;
+    }
+    if (covered > 0) {
+        hipLaunchKernelGGL(k_token_gather, dim3(capped_grid(c, (size_t)covered)), dim3(256), 0, s, (const TokKey*)t.tok,
+                           (const int*)c->d_cmp_old_of_new, covered, t.covered, nt);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) {
+            dfree(nt);
+            dfree(ns);
+            token_drop(c);
+            return fail(c, PIE_E_HIP, "pie_compact_rows: token column: %s", hipGetErrorString(e));
+        }
+    }
+    dfree(t.tok);
+    t.tok = nt;
+    t.cap = cap;
+    t.covered = covered;
+    if (ns) {
+        dfree(t.slot_row);
+        t.slot_row = ns;
+        t.log2_slots = log2_slots;
+    }
+    int rc = token_rebuild(c);
+    if (rc) return rc;
+    return token_status_wait(c, "pie_compact_rows");
 }
 
 } // extern "C"

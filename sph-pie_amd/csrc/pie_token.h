@@ -1,0 +1,102 @@
+// pie_token.h — the token column and its index: getSession (server/sessionStore.js:21-35) for a whole event-loop turn in one
+// launch.  gfx950, wave64.  Included by pie_scan.hip, which holds the host side (pie_token_*).
+//
+// Token key: the first 16 bytes of the sha256 the reference uses as its Map key (sessionStore.js:8-10), as two little-endian
+// 64-bit words per row.  The device never hashes a token; the host does (binding.token_key, host/tokenKeys.js).
+//
+// Column:  tok[row] (16 B per row of capacity) for the rows [0, covered) — a prefix of the table.
+// Index:   slot_row[slots] (int32; -1 empty, otherwise a row), slots a power of two >= max(1024, 2 x covered): at most half full.
+//          home slot = the top log2(slots) bits of token_mix(key); linear probing, wrapping at the end of the table.
+//          The key is NOT stored in the slot: a probe reads slot_row[s], then tok[row] as one 16-byte load.
+//          There is no deleted state: an entry leaves only when compaction drops its row (the index is rebuilt then).
+// Every probe loop runs at most `slots` steps; a lane that exhausts the bound sets a status word and stops.
+#ifndef PIE_TOKEN_H
+#define PIE_TOKEN_H
+
+#include <hip/hip_runtime.h>
+
+namespace pie {
+
+typedef ulonglong2 TokKey; // .x = bytes 0..7, .y = bytes 8..15 of the sha256, little endian
+
+constexpr int kTokStatusWords = 4; // [0] an insert exhausted its probe bound, [1] a lookup did
+
+// 64-bit mix of a key: the splitmix64 finaliser (the one pie_shard_of applies to a user id) over k0 ^ rotl(k1, 32)
+__host__ __device__ __forceinline__ unsigned long long token_mix(unsigned long long k0, unsigned long long k1)
+{
+    unsigned long long z = (k0 ^ ((k1 << 32) | (k1 >> 32))) + 0x9E3779B97F4A7C15ULL;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+    return z ^ (z >> 31);
+}
+
+__host__ __device__ __forceinline__ unsigned long long token_home(unsigned long long k0, unsigned long long k1, unsigned log2_slots)
+{
+    return log2_slots ? token_mix(k0, k1) >> (64 - log2_slots) : 0ull;
+}
+
+// One lane per row of [row0, row0 + k): claim the first empty slot from the row's home.  Keys are never compared, so rows with
+// equal keys all get in.  The claim is a relaxed agent-scope compare-and-swap: every reader is a later kernel on the stream.
+__global__ __launch_bounds__(256) void k_token_insert(const TokKey* __restrict__ tok, long long row0, long long k, int* __restrict__ slot_row,
+                                                      unsigned log2_slots, unsigned int* __restrict__ status)
+{
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= k) return;
+    const long long row = row0 + t;
+    const TokKey key = tok[row];
+    const unsigned long long slots = 1ull << log2_slots, mask = slots - 1;
+    unsigned long long s = token_home(key.x, key.y, log2_slots);
+    unsigned long long step = 0;
+    for (; step < slots; ++step) {
+        int expected = -1;
+        if (__hip_atomic_compare_exchange_strong(&slot_row[s], &expected, (int)row, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;
+        s = (s + 1) & mask;
+    }
+    if (step == slots) status[0] = 1u;
+}
+
+// One lane per query key: walk from the home slot to the first empty slot; among the slots whose row carries the query's key
+// (both words) keep the largest row — of several sessions under one key the latest wins.  Outputs may be absent (NULL).
+__global__ __launch_bounds__(256) void k_token_lookup(const TokKey* __restrict__ query, long long k, const int* __restrict__ slot_row, unsigned log2_slots,
+                                                      const TokKey* __restrict__ tok, long long covered, const long long* __restrict__ end,
+                                                      const long long* __restrict__ start, const int* __restrict__ user, long long now,
+                                                      int* __restrict__ o_row, unsigned char* __restrict__ o_live, int* __restrict__ o_user,
+                                                      long long* __restrict__ o_start, long long* __restrict__ o_end, unsigned int* __restrict__ status)
+{
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= k) return;
+    const TokKey key = query[t];
+    const unsigned long long slots = 1ull << log2_slots, mask = slots - 1;
+    unsigned long long s = token_home(key.x, key.y, log2_slots);
+    int best = -1;
+    unsigned long long step = 0;
+    for (; step < slots; ++step) {
+        const int r = slot_row[s];
+        if (r < 0) break;
+        if ((long long)r < covered) { // always true for an index in step with its column; keeps the load inside it regardless
+            const TokKey have = tok[r];
+            if (have.x == key.x && have.y == key.y && r > best) best = r;
+        }
+        s = (s + 1) & mask;
+    }
+    if (step == slots) status[1] = 1u;
+    const long long e = best >= 0 ? end[best] : INT64_MIN;
+    if (o_row) o_row[t] = best;
+    if (o_live) o_live[t] = (best >= 0 && e > now) ? 1 : 0;
+    if (o_end) o_end[t] = e;
+    if (o_start) o_start[t] = best >= 0 ? start[best] : 0;
+    if (o_user) o_user[t] = best >= 0 ? user[best] : -1;
+}
+
+// the compaction hook: the keys of the kept covered rows, in their new places
+__global__ __launch_bounds__(256) void k_token_gather(const TokKey* __restrict__ tok_old, const int* __restrict__ old_of_new, long long n_new,
+                                                      long long covered_old, TokKey* __restrict__ tok_new)
+{
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n_new; i += (long long)gridDim.x * blockDim.x) {
+        const long long r = old_of_new[i];
+        if (r >= 0 && r < covered_old) tok_new[i] = tok_old[r];
+    }
+}
+
+} // namespace pie
+#endif /* PIE_TOKEN_H */

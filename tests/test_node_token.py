@@ -1,0 +1,23 @@
+"""GPU: the token index through the Node addon (tokenSet / tokenAppend / tokenLookup / tokenSetEnd, host/tokenKeys.js) — a fresh
+node child with its own timeout, as tests/test_node_compact.py runs its host test."""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+from conftest import REPO
+
+HOST = os.path.join(REPO, "sph-pie_amd", "host")
+node = shutil.which("node")
+needs_node = pytest.mark.skipif(node is None, reason="node is not installed on this machine")
+
+
+@needs_node
+@pytest.mark.gpu
+def test_token_index_through_the_node_addon(pie):
+    assert pie.build_napi() is not None, "node headers (node_api.h) not found"
+    res = subprocess.run([node, os.path.join(HOST, "test", "gpu_token_test.js")], cwd=REPO, env=dict(os.environ, TZ="UTC"),
+                         stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
+    assert res.returncode == 0, res.stdout
+    assert "host gpu_token_test ok" in res.stdout
