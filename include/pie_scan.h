@@ -677,6 +677,18 @@ int pie_comm_table_size(pie_comm *comm, int64_t *rows_global_out, int32_t *users
  *     step_reserve;  begin(0); begin(1); finish(0); begin(2); collect(0); finish(1); begin(3); collect(1); ...
  * at most three steps per batch lane of the shards (pie_set_batch_lanes: 3 .. 12) begun and unfinished, at most sixteen
  * uncollected (rotating buffer sets).  Every rank of a process-per-GPU communicator makes the same calls in the same order.
+ * These rules hold for the ordinary steps here and for the wide steps below alike (one engine runs both):
+ *   - geometry: u_pad, union_cap and the words per row of a reservation belong to the kind of step alone.  Neither the other
+ *     kind's reservation nor the synchronous path (pie_comm_reserve, pie_comm_scan_batch_gather) moves them; they change only
+ *     in step_reserve, and only while no step of the kind is in flight (PIE_E_STATE otherwise).
+ *   - begin: if a local shard cannot begin after others began, every step in flight on this process is finished and marked
+ *     failed (its collect returns PIE_E_STATE) together with what this call began; the step is not counted.
+ *   - waits: collect waits for the side stream at most PIE_WAIT_DEADLINE_MS (20 000 ms by default), then fails with PIE_E_HIP.
+ *   - a step that failed on this process (a shard's finish, the exchange, the wait) says so at its collect (PIE_E_STATE, or the
+ *     wait's own status), and its gathered buffers are never handed out.
+ *   - buffer lifetime: the gathered messages of a collected step stay valid until as many further steps have BEGUN as there
+ *     are buffer sets — sixteen here, eight for wide steps; gathered_ptr / read_gathered return PIE_E_STATE before the step's
+ *     collect, after that point, and for a failed step.  A step whose collect returned PIE_E_CAPACITY is not a failed step.
  * step_reserve: u_pad as in pie_comm_scan_batch_gather; union_cap = rows per message.
  * step_finish:  waits for the oldest begun step's summaries on every local shard (m_out: local_ranks x n_q, may be NULL),
  *               then queues its exchange; does not wait for it.
@@ -687,8 +699,9 @@ int pie_comm_step_reserve(pie_comm *comm, int32_t n_q, int32_t u_pad, size_t uni
 int pie_comm_step_begin(pie_comm *comm, const pie_query *queries, int32_t n_q);
 int pie_comm_step_finish(pie_comm *comm, size_t *m_out);
 int pie_comm_step_collect(pie_comm *comm, int64_t *step_out);
-/* The gathered union messages of a collected step as rank `at_rank` holds them (valid until four more steps have begun):
- * message of rank r at base + r * rank_stride_words; or one message copied to the host (masks_out: 64-bit mask per row). */
+/* The gathered union messages of a collected step as rank `at_rank` holds them (valid until sixteen more steps have begun):
+ * message of rank r at base + r * rank_stride_words; or one message copied to the host (masks_out: 64-bit mask per row; Mu comes
+ * from the words collect already holds, no extra copy). */
 int pie_comm_step_gathered_ptr(pie_comm *comm, int32_t at_rank, int64_t step, void **base_out, size_t *rank_stride_words,
                                size_t *u_pad_out, size_t *cap_out);
 int pie_comm_step_read_gathered(pie_comm *comm, int32_t at_rank, int32_t src_rank, int64_t step, int32_t *uoff_out /* u_pad + 1 */,
@@ -696,7 +709,8 @@ int pie_comm_step_read_gathered(pie_comm *comm, int32_t at_rank, int32_t src_ran
 
 /* ---- the pipelined WIDE exchange: the same pipeline for steps of 1..PIE_WIDE_MAX queries.  One wide union message per step
  * and shard (layout: pie_scan_wide_begin_union), written by the shard's own wide tail; entry points, counters, buffer sets and
- * u_pad of its own — a reservation here never moves the geometry of pie_comm_step_* and the reverse.  Order of calls as above:
+ * u_pad of its own — a reservation here never moves the geometry of pie_comm_step_* and the reverse.  The rules stated above
+ * for both kinds (geometry, a shard that cannot begin, bounded waits, failed steps, buffer lifetime) apply.  Order of calls as above:
  *     wide_step_reserve;  begin(0); begin(1); finish(0); begin(2); collect(0); finish(1); ...
  * The two kinds do not mix in flight: pie_comm_wide_step_begin returns PIE_E_STATE while ordinary steps are uncollected;
  * pie_comm_step_begin, pie_comm_scan_batch_gather and the queue calls return PIE_E_STATE while wide steps are uncollected.
@@ -705,9 +719,7 @@ int pie_comm_step_read_gathered(pie_comm *comm, int32_t at_rank, int32_t src_ran
  *     4 B x (u_pad + 2 + cap x (1 + 2 x words_max)) x (1 + world),   words_max = ceil(n_q_max / 64).
  * wide_step_reserve: n_q_max 1..PIE_WIDE_MAX fixes the message length; u_pad as in pie_comm_scan_batch_gather; union_cap =
  *               rows per message.  PIE_E_STATE if the geometry would change while wide steps are in flight.
- * wide_step_begin:  pie_scan_wide_begin_union on every local shard into the step's buffer set.  If a shard fails after others
- *               began, every wide step in flight on this process is finished and marked failed (its collect returns
- *               PIE_E_STATE) together with what this call began; the step is not counted.
+ * wide_step_begin:  pie_scan_wide_begin_union on every local shard into the step's buffer set.
  * wide_step_finish: waits (bounded) for the oldest begun step's batches; m_out (may be NULL): local_ranks x n_q counts,
  *               PIE_E_CAPACITY with nothing consumed if m_cap is below that.  Queues the exchange on the side streams, which
  *               wait for a context's stream only where its shard said ready = 0.  Only the prefix the step uses is exchanged:

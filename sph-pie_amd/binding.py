@@ -975,6 +975,7 @@ class PieComm:
                 self._c = None
                 raise PieError(rc, text)
         self.world = int(self._lib.pie_comm_world(self._c))
+        self._step_nq, self._wide_nq = [], []   # n_q of the ordinary / wide steps begun and not yet finished, oldest first
 
     @staticmethod
     def unique_id():
@@ -1049,7 +1050,6 @@ class PieComm:
     def step_begin(self, queries):
         arr = PieScan._queries(queries)
         self._check(self._lib.pie_comm_step_begin(self._c, arr, len(queries)))
-        self._step_nq = getattr(self, "_step_nq", [])
         self._step_nq.append(len(queries))
 
     def step_finish(self):
@@ -1085,7 +1085,6 @@ class PieComm:
     def wide_step_begin(self, queries):
         queries = list(queries)      # marshalled on every call: no identity cache
         self._check(self._lib.pie_comm_wide_step_begin(self._c, PieScan._wide_queries(queries), len(queries)))
-        self._wide_nq = getattr(self, "_wide_nq", [])
         self._wide_nq.append(len(queries))
 
     def wide_step_finish(self):

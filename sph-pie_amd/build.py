@@ -102,7 +102,7 @@ def build_napi(force=False):
             break
     if inc is None:
         return None
-    return _build(NAPI_ADDON, [src, os.path.join(REPO, "include", "pie_scan.h")],
+    return _build(NAPI_ADDON, [src, os.path.join(CSRC, "pie_nq_ring.h"), os.path.join(REPO, "include", "pie_scan.h")],
                   lambda out: ["gcc", "-O2", "-fPIC", "-shared", "-std=c11", "-Wall", "-I", inc, "-I", os.path.join(REPO, "include"),
                                "-o", out, src, "-ldl"], force)
 

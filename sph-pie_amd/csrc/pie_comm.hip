@@ -93,6 +93,22 @@ thread_local char g_comm_create_error[256] = "";
 
 } // namespace
 
+// One pipelined union exchange (the state of pie_comm_step_*, and again of pie_comm_wide_step_*): rotating buffer sets per local
+// rank, a ready and a done event per set and rank, and the gathered Mu words in mapped host memory.  Step i lives in set
+// i % sets (StepKind) from its begin until `sets` more steps have begun.
+struct pie_steps {
+    static constexpr int kMaxSets = 16;
+    std::vector<int*> msg[kMaxSets], gath[kMaxSets];       // [set][local index]: this rank's union message [L] / the gathered ones [world][L]
+    std::vector<hipEvent_t> ready[kMaxSets], done[kMaxSets];
+    int* h_mu[kMaxSets] = {};      // mapped pinned: [local index][world] the Mu word of every gathered message
+    int* h_mu_dev[kMaxSets] = {};
+    long long u_pad = 0, cap = 0, L = 0;   // users per message, union rows per message, words per message (for words_max)
+    int words_max = 0;             // mask words per union row the reservation holds
+    long long begun = 0, finished = 0, collected = 0;  // steps begun / exchanges issued / exchanges collected
+    int nq[kMaxSets] = {};
+    int rc[kMaxSets] = {};         // a step that failed on this process before its exchange completed: its collect reports it
+};
+
 // One member per LOCAL rank: a single-process communicator (pie_comm_create) holds all ranks of the node, a
 // process-per-GPU communicator (pie_comm_create_rank) holds one.
 struct pie_comm {
@@ -109,30 +125,8 @@ struct pie_comm {
     long long u_pad = 0, cap = 0, L = 0;
     int last_nq = 0;
     long long need = 0;            // row capacity the last exchange called for (the largest list / union any rank reported)
-    // pipelined union exchange (pie_comm_step_*): kSets rotating buffer sets per local rank, a side stream per local rank
-    static constexpr int kSets = 16;  // (twelve steps begun on four batch lanes + the exchanges queued and being read)
-    std::vector<hipStream_t> xstream;                 // local index -> exchange stream
-    std::vector<int*> umsg[kSets], ugath[kSets];      // [set][local index]: this rank's union message / the gathered ones [world][UL]
-    std::vector<hipEvent_t> ev_ready[kSets], ev_done[kSets];
-    int* h_mu[kSets] = {}; // mapped pinned: [local index][world] the Mu word of every gathered message
-    int* h_mu_dev[kSets] = {};
-    long long u_cap = 0, UL = 0;   // union rows per message, words per message (u_pad + 2 + mask_words' share)
-    int u_words = 2;               // words per union row in a message: row + one or two mask words
-    long long begun = 0, finished = 0, collected = 0;  // steps begun / exchanges issued / exchanges collected
-    int step_nq[kSets] = {};
-    int step_rc[kSets] = {};   // a step whose finish failed on this process: its collect reports it
-    // pipelined WIDE union exchange (pie_comm_wide_step_*): state of its own beside the above — buffer sets, counters and u_pad
-    // are not shared with the ordinary steps (a reservation of one kind never moves the other's message geometry)
-    static constexpr int kWideSets = 8;
-    std::vector<int*> wmsg[kWideSets], wgath[kWideSets];  // [set][local index]: this rank's wide message [WL] / the gathered ones [world][WL]
-    std::vector<hipEvent_t> w_ready[kWideSets], w_done[kWideSets];
-    int* w_h_mu[kWideSets] = {};   // mapped pinned: [local index][world] the Mu word of every gathered message
-    int* w_h_mu_dev[kWideSets] = {};
-    long long w_u_pad = 0, w_cap = 0, WL = 0;  // users per message, union rows per message, words per message (for w_words_max)
-    int w_words_max = 0;           // 64-bit mask words per row the reservation holds (ceil(n_q_max / 64))
-    long long w_begun = 0, w_finished = 0, w_collected = 0;
-    int w_step_nq[kWideSets] = {};
-    int w_step_rc[kWideSets] = {};
+    std::vector<hipStream_t> xstream;  // local index -> exchange stream of the pipelined steps (both kinds: they never mix in flight)
+    pie_steps ord, wide;               // pie_comm_step_* / pie_comm_wide_step_*: nothing shared, a reservation of one never moves the other's geometry
     // cross-shard dispatch queues (pie_comm_expired_queue / _archive_queue): buffers of their own, sized by the header exchange
     std::vector<int*> qh_msg, qh_gath;            // local index -> header words [2] / gathered headers [world][2]
     int* h_qhead = nullptr;                       // pinned: [local index][2] headers to send, then [world][2] as gathered
@@ -144,7 +138,7 @@ struct pie_comm {
     std::vector<hipEvent_t> q_ev;                 // local index -> completion of a queue phase
     hipEvent_t q_tev[5] = {};                     // timing of the last queue call on the first local rank's stream
     bool q_timed = false;
-    double wait_deadline_ms = 20000.0;            // bound of every wait of the queue path (PIE_WAIT_DEADLINE_MS)
+    double wait_deadline_ms = 20000.0;            // bound of every wait of the queue path and the steps (PIE_WAIT_DEADLINE_MS)
     char err[512] = "";
 };
 
@@ -228,9 +222,15 @@ pie_comm* new_comm(int world, int n_local)
 
 void free_queue_buffers(pie_comm* c);
 
-void free_step_buffers(pie_comm* c);
+void free_step_buffers(pie_comm* c, pie_steps& st);
 
-void free_wide_step_buffers(pie_comm* c, bool events);
+// the synchronous gather, the queues and the mutations stay out of the way of pipelined steps of either kind
+int steps_idle(pie_comm* c)
+{
+    if (c->ord.begun != c->ord.collected) return cfail(c, PIE_E_STATE, "pipelined steps are in flight (pie_comm_step_*): collect them first");
+    if (c->wide.begun != c->wide.collected) return cfail(c, PIE_E_STATE, "wide steps are in flight (pie_comm_wide_step_*): collect them first");
+    return PIE_OK;
+}
 
 int local_index(const pie_comm* c, int rank)
 {
@@ -345,15 +345,11 @@ int pie_comm_destroy(pie_comm* c)
         if (k < (int)c->xstream.size() && c->xstream[k]) (void)hipStreamSynchronize(c->xstream[k]);
     }
     free_buffers(c);
-    free_step_buffers(c);
-    free_wide_step_buffers(c, true);
+    free_step_buffers(c, c->ord);
+    free_step_buffers(c, c->wide);
     free_queue_buffers(c);
     for (int k = 0; k < c->n_local; ++k) {
         (void)hipSetDevice(c->device[k]);
-        for (int s = 0; s < pie_comm::kSets; ++s) {
-            if (k < (int)c->ev_ready[s].size() && c->ev_ready[s][k]) (void)hipEventDestroy(c->ev_ready[s][k]);
-            if (k < (int)c->ev_done[s].size() && c->ev_done[s][k]) (void)hipEventDestroy(c->ev_done[s][k]);
-        }
         if (k < (int)c->xstream.size() && c->xstream[k]) (void)hipStreamDestroy(c->xstream[k]);
     }
     for (int k = 0; k < c->n_local; ++k) {
@@ -391,7 +387,7 @@ namespace {
 
 // the Mu word of every gathered message (world of them, rank_stride words apart) into mapped host memory: no copy node behind
 // the exchange (a 2-D copy call cost more host time than the whole step's launches)
-__global__ void k_pick_words(const int* __restrict__ gath, long long rank_stride, long long word, int world, int* __restrict__ out)
+__global__ __launch_bounds__(64) void k_pick_words(const int* __restrict__ gath, long long rank_stride, long long word, int world, int* __restrict__ out)
 {
     const int r = (int)threadIdx.x;
     if (r < world) __hip_atomic_store(&out[r], gath[(long long)r * rank_stride + word], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -440,53 +436,6 @@ int resolve_u_pad(pie_comm* c, int32_t u_pad_in, long long* u_pad_out)
     return PIE_OK;
 }
 
-void free_step_buffers(pie_comm* c)
-{
-    for (int s = 0; s < pie_comm::kSets; ++s) {
-        for (int k = 0; k < c->n_local; ++k) {
-            (void)hipSetDevice(c->device[k]);
-            if (k < (int)c->umsg[s].size() && c->umsg[s][k]) (void)hipFree(c->umsg[s][k]);
-            if (k < (int)c->ugath[s].size() && c->ugath[s][k]) (void)hipFree(c->ugath[s][k]);
-        }
-        c->umsg[s].assign((size_t)c->n_local, nullptr);
-        c->ugath[s].assign((size_t)c->n_local, nullptr);
-        if (c->h_mu[s]) (void)hipHostFree(c->h_mu[s]);
-        c->h_mu[s] = nullptr;
-    }
-    c->u_cap = c->UL = 0;
-}
-
-// rotating buffer sets of the pipelined union exchange; only while no step is in flight
-int ensure_step_buffers(pie_comm* c, int n_q, long long u_pad, long long cap)
-{
-    const int words = n_q > 32 ? 3 : 2;
-    if (c->UL > 0 && c->u_pad == u_pad && cap <= c->u_cap && words <= c->u_words && c->umsg[0].size() == (size_t)c->n_local && c->umsg[0][0]) return PIE_OK;
-    if (c->begun != c->collected) return cfail(c, PIE_E_STATE, "steps are in flight: collect them before the message size changes");
-    free_step_buffers(c);
-    c->u_pad = u_pad;
-    c->u_cap = cap;
-    c->u_words = words > c->u_words ? words : c->u_words;
-    c->UL = u_pad + 2 + (long long)c->u_words * cap;
-    if (c->xstream.size() != (size_t)c->n_local) c->xstream.assign((size_t)c->n_local, nullptr);
-    for (int s = 0; s < pie_comm::kSets; ++s) {
-        if (c->ev_ready[s].size() != (size_t)c->n_local) { c->ev_ready[s].assign((size_t)c->n_local, nullptr); c->ev_done[s].assign((size_t)c->n_local, nullptr); }
-        PIE_CHIP(c, hipHostMalloc(&c->h_mu[s], (size_t)c->n_local * (size_t)c->world * 4, hipHostMallocMapped));
-        PIE_CHIP(c, hipHostGetDevicePointer((void**)&c->h_mu_dev[s], c->h_mu[s], 0));
-    }
-    for (int k = 0; k < c->n_local; ++k) {
-        PIE_CHIP(c, hipSetDevice(c->device[k]));
-        if (!c->xstream[k]) PIE_CHIP(c, hipStreamCreateWithFlags(&c->xstream[k], hipStreamNonBlocking));
-        for (int s = 0; s < pie_comm::kSets; ++s) {
-            PIE_CHIP(c, hipMalloc(&c->umsg[s][k], (size_t)c->UL * 4));
-            PIE_CHIP(c, hipMalloc(&c->ugath[s][k], (size_t)c->UL * 4 * (size_t)c->world));
-            PIE_CHIP(c, hipMemset(c->umsg[s][k], 0, (size_t)c->UL * 4));
-            if (!c->ev_ready[s][k]) PIE_CHIP(c, hipEventCreateWithFlags(&c->ev_ready[s][k], hipEventDisableTiming));
-            if (!c->ev_done[s][k]) PIE_CHIP(c, hipEventCreateWithFlags(&c->ev_done[s][k], hipEventDisableTiming));
-        }
-    }
-    return PIE_OK;
-}
-
 } // namespace
 
 // One synchronous step, per-query lists.  The exchange ALWAYS runs once every local shard has finished its batch — the
@@ -498,8 +447,7 @@ int pie_comm_scan_batch_gather(pie_comm* c, const pie_query* queries, int32_t n_
 {
     if (!c) return PIE_E_INVAL;
     if (!queries || n_q < 1 || n_q > PIE_BATCH_MAX) return cfail(c, PIE_E_INVAL, "a batch holds 1..%d queries (got %d)", PIE_BATCH_MAX, n_q);
-    if (c->begun != c->collected) return cfail(c, PIE_E_STATE, "pipelined steps are in flight (pie_comm_step_*): collect them first");
-    if (c->w_begun != c->w_collected) return cfail(c, PIE_E_STATE, "wide steps are in flight (pie_comm_wide_step_*): collect them first");
+    if (steps_idle(c)) return PIE_E_STATE;
     long long u_pad = 0;
     int rc = resolve_u_pad(c, u_pad_in, &u_pad);
     if (rc) return rc;
@@ -552,160 +500,6 @@ int pie_comm_scan_batch_gather(pie_comm* c, const pie_query* queries, int32_t n_
 }
 
 size_t pie_comm_needed_cap(const pie_comm* c) { return c ? (size_t)(c->need + c->need / 16 + 64) : 0; }
-
-// ---- the pipelined exchange: ONE union message per step, written by the batch's own tail kernel; the exchange of a step
-// runs on a side stream while the shards scan the next ones (the C-ABI counterpart of shard.py's BatchedFeeds.run_steps)
-int pie_comm_step_reserve(pie_comm* c, int32_t n_q, int32_t u_pad_in, size_t union_cap)
-{
-    if (!c) return PIE_E_INVAL;
-    if (n_q < 1 || n_q > PIE_BATCH_MAX) return cfail(c, PIE_E_INVAL, "bad reservation");
-    long long u_pad = 0;
-    int rc = resolve_u_pad(c, u_pad_in, &u_pad);
-    if (rc) return rc;
-    return ensure_step_buffers(c, n_q, u_pad, (long long)(union_cap > 0 ? union_cap : 1024));
-}
-
-int pie_comm_step_begin(pie_comm* c, const pie_query* queries, int32_t n_q)
-{
-    if (!c) return PIE_E_INVAL;
-    if (!queries || n_q < 1 || n_q > PIE_BATCH_MAX) return cfail(c, PIE_E_INVAL, "a batch holds 1..%d queries (got %d)", PIE_BATCH_MAX, n_q);
-    if (c->UL <= 0) return cfail(c, PIE_E_STATE, "pie_comm_step_reserve first");
-    if (c->w_begun != c->w_collected) return cfail(c, PIE_E_STATE, "wide steps are in flight (pie_comm_wide_step_*): collect them first");
-    if ((n_q > 32 ? 3 : 2) > c->u_words) return cfail(c, PIE_E_STATE, "reserved for batches of at most 32 queries: pie_comm_step_reserve again");
-    // steps begun and unfinished: what the shards' batch lanes hold (three per lane, pie_set_batch_lanes; lane 0 only on the ordered run)
-    if (c->begun - c->finished >= pie_comm::kSets - 4)
-        return cfail(c, PIE_E_STATE, "%d steps are already begun: pie_comm_step_finish first", pie_comm::kSets - 4);
-    for (int k = 0; k < c->n_local; ++k)
-        if (pie_batch_room(c->ctx[k]) <= 0)
-            return cfail(c, PIE_E_STATE, "rank %d: the steps begun fill its batch slots (three per batch lane): pie_comm_step_finish first", c->rank_of[k]);
-    if (c->begun - c->collected >= pie_comm::kSets) return cfail(c, PIE_E_STATE, "%d steps are uncollected: pie_comm_step_collect first", pie_comm::kSets);
-    const int s = (int)(c->begun % pie_comm::kSets);
-    int begun = 0, rc = PIE_OK;
-    for (int k = 0; k < c->n_local && rc == PIE_OK; ++k) {
-        rc = pie_scan_batch_begin_union(c->ctx[k], queries, n_q, c->umsg[s][k], (size_t)c->u_pad, (size_t)c->u_cap);
-        if (rc == PIE_OK) ++begun;
-        else cfail(c, rc, "rank %d: %s", c->rank_of[k], pie_last_error(c->ctx[k]));
-    }
-    if (rc != PIE_OK) { // the step is not counted; what the other shards began is finished and dropped
-        for (int k = 0; k < begun; ++k) (void)pie_scan_batch_finish_packed(c->ctx[k], nullptr, nullptr);
-        return rc;
-    }
-    c->step_nq[s] = n_q;
-    c->begun++;
-    return PIE_OK;
-}
-
-int pie_comm_step_finish(pie_comm* c, size_t* m_out)
-{
-    if (!c) return PIE_E_INVAL;
-    if (c->finished >= c->begun) return cfail(c, PIE_E_STATE, "pie_comm_step_finish without pie_comm_step_begin");
-    const int s = (int)(c->finished % pie_comm::kSets);
-    const int n_q = c->step_nq[s];
-    std::vector<size_t> m((size_t)c->n_local * (size_t)n_q, 0);
-    int first_rc = PIE_OK;
-    for (int k = 0; k < c->n_local; ++k) {
-        int ready = 0;
-        const int rc = pie_scan_batch_finish_packed(c->ctx[k], &m[(size_t)k * n_q], &ready);
-        if (rc != PIE_OK && first_rc == PIE_OK) {
-            first_rc = rc;
-            cfail(c, rc, "rank %d: %s", c->rank_of[k], pie_last_error(c->ctx[k]));
-        }
-        // ready = 0: the message was packed on the context's stream after the batch: the exchange stream waits for exactly that
-        PIE_CHIP(c, hipSetDevice(c->device[k]));
-        if (!ready) {
-            PIE_CHIP(c, hipEventRecord(c->ev_ready[s][k], c->stream[k]));
-            PIE_CHIP(c, hipStreamWaitEvent(c->xstream[k], c->ev_ready[s][k], 0));
-        }
-    }
-    c->finished++;
-    c->step_rc[s] = first_rc;
-    if (first_rc != PIE_OK) return first_rc; // every local batch has been finished; no exchange is queued for this step (its collect says so)
-    // the exchange of this step, on the side streams: nothing here waits for it
-    int rc = exchange(c, c->umsg[s], c->ugath[s], (size_t)c->UL, (size_t)c->UL, c->xstream);
-    if (rc) return rc;
-    for (int k = 0; k < c->n_local; ++k) {
-        PIE_CHIP(c, hipSetDevice(c->device[k]));
-        hipLaunchKernelGGL(k_pick_words, dim3(1), dim3(64), 0, c->xstream[k], c->ugath[s][k], (long long)c->UL, (long long)c->u_pad + 1, c->world,
-                           c->h_mu_dev[s] + (size_t)k * (size_t)c->world);
-        PIE_CHIP(c, hipEventRecord(c->ev_done[s][k], c->xstream[k]));
-    }
-    if (m_out) memcpy(m_out, m.data(), m.size() * sizeof(size_t));
-    return PIE_OK;
-}
-
-int pie_comm_step_collect(pie_comm* c, int64_t* step_out)
-{
-    if (!c) return PIE_E_INVAL;
-    if (c->collected >= c->finished) return cfail(c, PIE_E_STATE, "no exchange to collect: pie_comm_step_finish first");
-    const int s = (int)(c->collected % pie_comm::kSets);
-    if (step_out) *step_out = (int64_t)c->collected;
-    if (c->step_rc[s] != PIE_OK) {
-        c->collected++;
-        return cfail(c, PIE_E_STATE, "step %lld failed in pie_comm_step_finish (status %d): nothing was exchanged", (long long)c->collected - 1, c->step_rc[s]);
-    }
-    for (int k = 0; k < c->n_local; ++k) {
-        PIE_CHIP(c, hipSetDevice(c->device[k]));
-        PIE_CHIP(c, hipEventSynchronize(c->ev_done[s][k])); // the side stream only: the shards' scan streams run on
-    }
-    c->collected++;
-    long long need = 0;
-    bool merged_overflow = false;
-    for (int p = 0; p < c->world; ++p) { // every rank holds the same world Mu words
-        const int mu = c->h_mu[s][p];
-        if (mu < 0) merged_overflow = true;
-        if (mu > need) need = mu;
-    }
-    c->need = need;
-    if (merged_overflow)
-        return cfail(c, PIE_E_CAPACITY, "a shard's union could not be formed (Mu = -1: queries fell back and a user's merged union exceeds 32 rows, or more than 32 queries): use pie_comm_scan_batch_gather for this batch");
-    if (need > c->u_cap)
-        return cfail(c, PIE_E_CAPACITY, "a union of %lld rows exceeds the reserved capacity %lld on some rank: collect what is in flight, pie_comm_step_reserve(pie_comm_needed_cap), repeat the step", need, c->u_cap);
-    return PIE_OK;
-}
-
-int pie_comm_step_gathered_ptr(pie_comm* c, int32_t at_rank, int64_t step, void** base_out, size_t* rank_stride_words, size_t* u_pad_out, size_t* cap_out)
-{
-    if (!c) return PIE_E_INVAL;
-    const int k = local_index(c, at_rank);
-    if (k < 0 || c->UL <= 0) return cfail(c, PIE_E_STATE, "rank %d is not local to this communicator or nothing was reserved", at_rank);
-    if (step < 0 || step >= c->collected || step + pie_comm::kSets <= c->begun) return cfail(c, PIE_E_STATE, "step %lld is not collected or its buffers were reused", (long long)step);
-    if (base_out) *base_out = c->ugath[step % pie_comm::kSets][k];
-    if (rank_stride_words) *rank_stride_words = (size_t)c->UL;
-    if (u_pad_out) *u_pad_out = (size_t)c->u_pad;
-    if (cap_out) *cap_out = (size_t)c->u_cap;
-    return PIE_OK;
-}
-
-int pie_comm_step_read_gathered(pie_comm* c, int32_t at_rank, int32_t src_rank, int64_t step, int32_t* uoff_out, int32_t* rows_out, uint64_t* masks_out,
-                                size_t cap, size_t* mu_out)
-{
-    if (!c) return PIE_E_INVAL;
-    void* base = nullptr;
-    int rc = pie_comm_step_gathered_ptr(c, at_rank, step, &base, nullptr, nullptr, nullptr);
-    if (rc) return rc;
-    if (src_rank < 0 || src_rank >= c->world) return cfail(c, PIE_E_INVAL, "source rank outside the communicator");
-    const int k = local_index(c, at_rank);
-    PIE_CHIP(c, hipSetDevice(c->device[k]));
-    const int* msg = static_cast<const int*>(base) + (size_t)src_rank * (size_t)c->UL;
-    int mu32 = 0;
-    PIE_CHIP(c, hipMemcpy(&mu32, msg + c->u_pad + 1, 4, hipMemcpyDeviceToHost));
-    const size_t mu = mu32 > 0 ? (size_t)mu32 : 0;
-    if (mu_out) *mu_out = mu;
-    if (uoff_out) PIE_CHIP(c, hipMemcpy(uoff_out, msg, ((size_t)c->u_pad + 1) * 4, hipMemcpyDeviceToHost));
-    const size_t have = mu < (size_t)c->u_cap ? mu : (size_t)c->u_cap;
-    if ((rows_out || masks_out) && have > cap) return cfail(c, PIE_E_CAPACITY, "cap %zu < %zu union rows", cap, have);
-    if (rows_out && have) PIE_CHIP(c, hipMemcpy(rows_out, msg + c->u_pad + 2, have * 4, hipMemcpyDeviceToHost));
-    if (masks_out && have) {
-        std::vector<uint32_t> lo(have), hi;
-        PIE_CHIP(c, hipMemcpy(lo.data(), msg + c->u_pad + 2 + c->u_cap, have * 4, hipMemcpyDeviceToHost));
-        if (c->u_words == 3 && c->step_nq[step % pie_comm::kSets] > 32) {
-            hi.resize(have);
-            PIE_CHIP(c, hipMemcpy(hi.data(), msg + c->u_pad + 2 + 2 * c->u_cap, have * 4, hipMemcpyDeviceToHost));
-        }
-        for (size_t i = 0; i < have; ++i) masks_out[i] = (uint64_t)lo[i] | (hi.empty() ? 0ull : ((uint64_t)hi[i] << 32));
-    }
-    return PIE_OK;
-}
 
 int pie_comm_reserve(pie_comm* c, int32_t n_q, int32_t u_pad, size_t idx_cap)
 {
@@ -953,8 +747,7 @@ int comm_queue(pie_comm* c, int kind, int64_t a, int64_t b, int32_t* queue_out, 
     if (!c) return PIE_E_INVAL;
     if (q_out) *q_out = 0;
     if (c->world > kQueueMaxWorld) return cfail(c, PIE_E_INVAL, "the queue merge takes at most %d ranks (world %d)", kQueueMaxWorld, c->world);
-    if (c->begun != c->collected) return cfail(c, PIE_E_STATE, "pipelined steps are in flight (pie_comm_step_*): collect them first");
-    if (c->w_begun != c->w_collected) return cfail(c, PIE_E_STATE, "wide steps are in flight (pie_comm_wide_step_*): collect them first");
+    if (steps_idle(c)) return PIE_E_STATE;
     c->q_total = -1;
     c->q_timed = false;
     int rc = ensure_queue_heads(c);
@@ -1128,8 +921,7 @@ int table_size(pie_comm* c, int64_t* rows_out, int32_t* users_out)
 
 int mutate_ready(pie_comm* c, int64_t* rows_out, int32_t* users_out)
 {
-    if (c->begun != c->collected) return cfail(c, PIE_E_STATE, "pipelined steps are in flight (pie_comm_step_*): collect them first");
-    if (c->w_begun != c->w_collected) return cfail(c, PIE_E_STATE, "wide steps are in flight (pie_comm_wide_step_*): collect them first");
+    if (steps_idle(c)) return PIE_E_STATE;
     return table_size(c, rows_out, users_out);
 }
 } // namespace
@@ -1183,247 +975,349 @@ int pie_comm_delete_user(pie_comm* c, int32_t user, int32_t* rows_out, size_t ca
 
 } // extern "C"
 
-// ---- the pipelined WIDE exchange (pie_comm_wide_step_*): one wide union message per step (layout:
-// pie_scan_wide_begin_union), written by each shard's own wide tail; otherwise the shape of pie_comm_step_* above, with state
-// of its own.  Every wait is bounded (wait_event, PIE_WAIT_DEADLINE_MS).
+// ---- the pipelined exchanges (pie_comm_step_* and pie_comm_wide_step_*): ONE union message per step and shard, written by the
+// shard's own batch tail (layouts: pie_scan_batch_begin_union / pie_scan_wide_begin_union); the exchange of a step runs on a side
+// stream while the shards scan the next ones (the C-ABI counterpart of shard.py's BatchedFeeds.run_steps).  One engine, two
+// kinds; what differs between them is in StepKind and the four small functions below it.  For both kinds:
+//   - a step's gathered buffers are handed out from its collect until `sets` more steps have begun (16 ordinary, 8 wide), and never
+//     for a step that failed on this process;
+//   - the geometry (u_pad, cap, words per row) is the kind's own: neither the other kind's reservation nor the synchronous path
+//     (pie_comm_reserve / pie_comm_scan_batch_gather) moves it under the buffers;
+//   - a shard that cannot begin after others began drains every step in flight (step_drain): nothing is left in the shards' FIFOs;
+//   - every wait is bounded (wait_event, PIE_WAIT_DEADLINE_MS).
 namespace {
 
-void free_wide_step_buffers(pie_comm* c, bool events)
+struct StepKind {
+    bool wide;
+    int sets;              // rotating buffer sets: steps uncollected at most
+    int ahead;             // steps begun and unfinished at most (what the shards' batch lanes hold, below the sets)
+    int nq_max;
+    const char* api;       // prefix of the kind's entry points, for messages
+    const char* no_union;  // collect's text for Mu = -1
+};
+
+const StepKind kOrdinary{false, 16, 12, PIE_BATCH_MAX, "pie_comm_step",
+                         "a shard's union could not be formed (Mu = -1: queries fell back and a user's merged union exceeds 32 rows, or more than 32 queries): use pie_comm_scan_batch_gather for this batch"};
+const StepKind kWide{true, 8, 6, PIE_WIDE_MAX, "pie_comm_wide_step",
+                     "a shard's wide batch kept no union (Mu = -1, pie_comm_wide_step_status): repeat the step; dense queries go through pie_comm_scan_batch_gather"};
+
+pie_steps& steps_of(pie_comm* c, const StepKind& kd) { return kd.wide ? c->wide : c->ord; }
+
+// words per union row for n_q queries (ordinary: row + one or two 32-bit mask planes; wide: 64-bit mask words) and the message length
+int step_words(const StepKind& kd, int n_q) { return kd.wide ? (n_q + 63) / 64 : n_q > 32 ? 3 : 2; }
+long long step_msg_words(const StepKind& kd, long long u_pad, long long cap, int words)
 {
-    for (int s = 0; s < pie_comm::kWideSets; ++s) {
+    return u_pad + 2 + cap * (kd.wide ? 1 + 2 * (long long)words : (long long)words);
+}
+
+int step_ctx_begin(const StepKind& kd, pie_ctx* ctx, const pie_query* queries, int n_q, int* msg, const pie_steps& st)
+{
+    return kd.wide ? pie_scan_wide_begin_union(ctx, queries, n_q, msg, (size_t)st.u_pad, (size_t)st.cap)
+                   : pie_scan_batch_begin_union(ctx, queries, n_q, msg, (size_t)st.u_pad, (size_t)st.cap);
+}
+
+// the oldest batch in flight on a shard; m == nullptr: finished and dropped
+int step_ctx_finish(const StepKind& kd, pie_ctx* ctx, size_t* m, int n_q, int* ready)
+{
+    int nq = 0;
+    if (!m) return kd.wide ? pie_scan_wide_finish(ctx, nullptr, 0, nullptr) : pie_scan_batch_finish_packed(ctx, nullptr, nullptr);
+    return kd.wide ? pie_scan_wide_finish_packed(ctx, m, (size_t)n_q, &nq, ready) : pie_scan_batch_finish_packed(ctx, m, ready);
+}
+
+void free_step_buffers(pie_comm* c, pie_steps& st)
+{
+    for (int s = 0; s < pie_steps::kMaxSets; ++s) {
         for (int k = 0; k < c->n_local; ++k) {
             (void)hipSetDevice(c->device[k]);
-            if (k < (int)c->wmsg[s].size() && c->wmsg[s][k]) (void)hipFree(c->wmsg[s][k]);
-            if (k < (int)c->wgath[s].size() && c->wgath[s][k]) (void)hipFree(c->wgath[s][k]);
-            if (events) {
-                if (k < (int)c->w_ready[s].size() && c->w_ready[s][k]) { (void)hipEventDestroy(c->w_ready[s][k]); c->w_ready[s][k] = nullptr; }
-                if (k < (int)c->w_done[s].size() && c->w_done[s][k]) { (void)hipEventDestroy(c->w_done[s][k]); c->w_done[s][k] = nullptr; }
-            }
+            if (k < (int)st.msg[s].size() && st.msg[s][k]) (void)hipFree(st.msg[s][k]);
+            if (k < (int)st.gath[s].size() && st.gath[s][k]) (void)hipFree(st.gath[s][k]);
+            if (k < (int)st.ready[s].size() && st.ready[s][k]) (void)hipEventDestroy(st.ready[s][k]);
+            if (k < (int)st.done[s].size() && st.done[s][k]) (void)hipEventDestroy(st.done[s][k]);
         }
-        c->wmsg[s].assign((size_t)c->n_local, nullptr);
-        c->wgath[s].assign((size_t)c->n_local, nullptr);
-        if (c->w_h_mu[s]) (void)hipHostFree(c->w_h_mu[s]);
-        c->w_h_mu[s] = nullptr;
+        for (auto* v : {&st.msg[s], &st.gath[s]}) v->assign((size_t)c->n_local, nullptr);
+        for (auto* v : {&st.ready[s], &st.done[s]}) v->assign((size_t)c->n_local, nullptr);
+        if (st.h_mu[s]) (void)hipHostFree(st.h_mu[s]);
+        st.h_mu[s] = st.h_mu_dev[s] = nullptr;
     }
-    c->w_cap = c->WL = 0;
-    c->w_words_max = 0;
+    st.cap = st.L = 0;
 }
 
-long long wide_msg_words(long long u_pad, long long cap, int words) { return u_pad + 2 + cap * (1 + 2 * (long long)words); }
-
-// the gathered Mu words of a collected step whose buffers have not been reused: nullptr otherwise
-const int* wide_step_mu(pie_comm* c, int64_t step)
+// the rotating buffer sets; the geometry changes only while no step of the kind is in flight
+int step_reserve(pie_comm* c, const StepKind& kd, int32_t n_q, int32_t u_pad_in, size_t union_cap)
 {
-    if (step < 0 || step >= c->w_collected || step + pie_comm::kWideSets <= c->w_begun) return nullptr;
-    const int s = (int)(step % pie_comm::kWideSets);
-    return c->w_step_rc[s] == PIE_OK ? c->w_h_mu[s] : nullptr;
+    if (!c) return PIE_E_INVAL;
+    if (n_q < 1 || n_q > kd.nq_max) return cfail(c, PIE_E_INVAL, "%s_reserve: 1..%d queries (got %d)", kd.api, kd.nq_max, n_q);
+    pie_steps& st = steps_of(c, kd);
+    long long u_pad = 0;
+    int rc = resolve_u_pad(c, u_pad_in, &u_pad);
+    if (rc) return rc;
+    const long long cap = (long long)(union_cap > 0 ? union_cap : 1024);
+    int words = step_words(kd, n_q);
+    if (st.L > 0 && st.u_pad == u_pad && cap <= st.cap && words <= st.words_max && st.msg[0].size() == (size_t)c->n_local && st.msg[0][0]) return PIE_OK;
+    if (!kd.wide && st.words_max > words) words = st.words_max; // an ordinary reservation keeps the second mask plane once it had one
+    if (step_msg_words(kd, u_pad, cap, words) > 0x7FFFFFF0LL) return cfail(c, PIE_E_INVAL, "a message of %lld words is too long", step_msg_words(kd, u_pad, cap, words));
+    if (st.begun != st.collected) return cfail(c, PIE_E_STATE, "steps are in flight: %s_collect them before the message size changes", kd.api);
+    free_step_buffers(c, st);
+    st.u_pad = u_pad;
+    st.cap = cap;
+    st.words_max = words;
+    const long long L = step_msg_words(kd, u_pad, cap, words); // st.L is set last: a reservation that failed midway reads as none
+    if (c->xstream.size() != (size_t)c->n_local) c->xstream.assign((size_t)c->n_local, nullptr);
+    for (int s = 0; s < kd.sets; ++s) {
+        PIE_CHIP(c, hipHostMalloc(&st.h_mu[s], (size_t)c->n_local * (size_t)c->world * 4, hipHostMallocMapped));
+        PIE_CHIP(c, hipHostGetDevicePointer((void**)&st.h_mu_dev[s], st.h_mu[s], 0));
+    }
+    for (int k = 0; k < c->n_local; ++k) {
+        PIE_CHIP(c, hipSetDevice(c->device[k]));
+        if (!c->xstream[k]) PIE_CHIP(c, hipStreamCreateWithFlags(&c->xstream[k], hipStreamNonBlocking));
+        for (int s = 0; s < kd.sets; ++s) {
+            PIE_CHIP(c, hipMalloc(&st.msg[s][k], (size_t)L * 4));
+            PIE_CHIP(c, hipMalloc(&st.gath[s][k], (size_t)L * 4 * (size_t)c->world));
+            PIE_CHIP(c, hipMemset(st.msg[s][k], 0, (size_t)L * 4));
+            PIE_CHIP(c, hipEventCreateWithFlags(&st.ready[s][k], hipEventDisableTiming));
+            PIE_CHIP(c, hipEventCreateWithFlags(&st.done[s][k], hipEventDisableTiming));
+        }
+    }
+    st.L = L;
+    return PIE_OK;
 }
 
-// a partial failure left batches begun on some shards: every wide step in flight on this process is finished in order and
-// marked failed (its collect says so), then the batches of the step that failed to begin; nothing is left in the shards' FIFOs
-void wide_step_drain(pie_comm* c, int begun_here, int why)
+// a partial failure left batches begun on some shards: every step in flight on this process is finished in order and marked
+// failed (its collect says so), then the batches of the step that failed to begin; nothing is left in the shards' FIFOs
+void step_drain(pie_comm* c, const StepKind& kd, int begun_here, int why)
 {
-    while (c->w_finished < c->w_begun) {
-        const int s = (int)(c->w_finished % pie_comm::kWideSets);
-        for (int k = 0; k < c->n_local; ++k) (void)pie_scan_wide_finish(c->ctx[k], nullptr, 0, nullptr);
-        c->w_step_rc[s] = why;
-        c->w_finished++;
+    pie_steps& st = steps_of(c, kd);
+    for (; st.finished < st.begun; st.finished++) {
+        for (int k = 0; k < c->n_local; ++k) (void)step_ctx_finish(kd, c->ctx[k], nullptr, 0, nullptr);
+        st.rc[st.finished % kd.sets] = why;
     }
-    for (int k = 0; k < begun_here; ++k) (void)pie_scan_wide_finish(c->ctx[k], nullptr, 0, nullptr);
+    for (int k = 0; k < begun_here; ++k) (void)step_ctx_finish(kd, c->ctx[k], nullptr, 0, nullptr);
+}
+
+int step_begin(pie_comm* c, const StepKind& kd, const pie_query* queries, int32_t n_q)
+{
+    if (!c) return PIE_E_INVAL;
+    if (!queries || n_q < 1 || n_q > kd.nq_max) return cfail(c, PIE_E_INVAL, "%s_begin: a step holds 1..%d queries (got %d)", kd.api, kd.nq_max, n_q);
+    pie_steps& st = steps_of(c, kd);
+    const pie_steps& other = steps_of(c, kd.wide ? kOrdinary : kWide);
+    if (st.L <= 0) return cfail(c, PIE_E_STATE, "%s_reserve first", kd.api);
+    if (other.begun != other.collected) return cfail(c, PIE_E_STATE, "%s steps are in flight: collect them first", kd.wide ? "ordinary (pie_comm_step_*)" : "wide (pie_comm_wide_step_*)");
+    if (step_words(kd, n_q) > st.words_max) return cfail(c, PIE_E_STATE, "reserved for fewer than %d queries: %s_reserve again", n_q, kd.api);
+    // steps begun and unfinished: what the shards' batch lanes hold (three per lane, pie_set_batch_lanes; lane 0 only on the ordered run)
+    if (st.begun - st.finished >= kd.ahead) return cfail(c, PIE_E_STATE, "%d steps are already begun: %s_finish first", kd.ahead, kd.api);
+    for (int k = 0; k < c->n_local; ++k)
+        if (pie_batch_room(c->ctx[k]) <= 0)
+            return cfail(c, PIE_E_STATE, "rank %d: the steps begun fill its batch slots (three per batch lane): %s_finish first", c->rank_of[k], kd.api);
+    if (st.begun - st.collected >= kd.sets) return cfail(c, PIE_E_STATE, "%d steps are uncollected: %s_collect first", kd.sets, kd.api);
+    const int s = (int)(st.begun % kd.sets);
+    int begun = 0, rc = PIE_OK;
+    for (int k = 0; k < c->n_local && rc == PIE_OK; ++k) {
+        rc = step_ctx_begin(kd, c->ctx[k], queries, n_q, st.msg[s][k], st);
+        if (rc == PIE_OK) ++begun;
+        else cfail(c, rc, "rank %d: %s", c->rank_of[k], pie_last_error(c->ctx[k]));
+    }
+    if (rc != PIE_OK) { // the step is not counted
+        if (begun > 0) step_drain(c, kd, begun, rc);
+        return rc;
+    }
+    st.nq[s] = n_q;
+    st.rc[s] = PIE_OK;
+    st.begun++;
+    return PIE_OK;
+}
+
+int step_finish(pie_comm* c, const StepKind& kd, size_t* m_out, size_t m_cap)
+{
+    if (!c) return PIE_E_INVAL;
+    pie_steps& st = steps_of(c, kd);
+    if (st.finished >= st.begun) return cfail(c, PIE_E_STATE, "%s_finish without %s_begin", kd.api, kd.api);
+    const int s = (int)(st.finished % kd.sets);
+    const int n_q = st.nq[s];
+    if (m_out && m_cap < (size_t)c->n_local * (size_t)n_q)
+        return cfail(c, PIE_E_CAPACITY, "m_cap %zu < %d local ranks x %d queries", m_cap, c->n_local, n_q);
+    std::vector<size_t> m((size_t)c->n_local * (size_t)n_q, 0);
+    int first_rc = PIE_OK;
+    for (int k = 0; k < c->n_local; ++k) {
+        int ready = 0;
+        const int rc = step_ctx_finish(kd, c->ctx[k], &m[(size_t)k * n_q], n_q, &ready);
+        if (rc != PIE_OK && first_rc == PIE_OK) {
+            first_rc = rc;
+            cfail(c, rc, "rank %d: %s", c->rank_of[k], pie_last_error(c->ctx[k]));
+        }
+        // ready = 0: the message (or its Mu = -1 header) was written on the context's stream behind the batch: the exchange stream waits for exactly that
+        PIE_CHIP(c, hipSetDevice(c->device[k]));
+        if (!ready) {
+            PIE_CHIP(c, hipEventRecord(st.ready[s][k], c->stream[k]));
+            PIE_CHIP(c, hipStreamWaitEvent(c->xstream[k], st.ready[s][k], 0));
+        }
+    }
+    st.finished++;
+    st.rc[s] = first_rc;
+    if (first_rc != PIE_OK) return first_rc; // every local batch has been finished; no exchange is queued for this step (its collect says so)
+    // the exchange of this step, on the side streams: nothing here waits for it.  An ordinary step sends the whole message, a wide
+    // step only the prefix its n_q uses: every rank knows n_q, so every rank agrees on the length
+    const size_t count = (size_t)(kd.wide ? step_msg_words(kd, st.u_pad, st.cap, step_words(kd, n_q)) : st.L);
+    int rc = exchange(c, st.msg[s], st.gath[s], count, (size_t)st.L, c->xstream);
+    if (rc) return st.rc[s] = rc;
+    for (int k = 0; k < c->n_local; ++k) {
+        PIE_CHIP(c, hipSetDevice(c->device[k]));
+        hipLaunchKernelGGL(k_pick_words, dim3(1), dim3(64), 0, c->xstream[k], st.gath[s][k], st.L, st.u_pad + 1, c->world, st.h_mu_dev[s] + (size_t)k * (size_t)c->world);
+        PIE_CHIP(c, hipEventRecord(st.done[s][k], c->xstream[k]));
+    }
+    if (m_out) memcpy(m_out, m.data(), m.size() * sizeof(size_t));
+    return PIE_OK;
+}
+
+int step_collect(pie_comm* c, const StepKind& kd, int64_t* step_out)
+{
+    if (!c) return PIE_E_INVAL;
+    pie_steps& st = steps_of(c, kd);
+    if (st.collected >= st.finished) return cfail(c, PIE_E_STATE, "no exchange to collect: %s_finish first", kd.api);
+    const long long step = st.collected++;
+    const int s = (int)(step % kd.sets);
+    if (step_out) *step_out = (int64_t)step;
+    if (st.rc[s] != PIE_OK) return cfail(c, PIE_E_STATE, "step %lld failed before its exchange (status %d): nothing was exchanged", step, st.rc[s]);
+    for (int k = 0; k < c->n_local; ++k) // the side stream only: the shards' scan streams run on
+        if (int rc = wait_event(c, k, st.done[s][k], "step exchange")) return st.rc[s] = rc;
+    long long need = 0;
+    bool no_union = false;
+    for (int p = 0; p < c->world; ++p) { // every rank holds the same world Mu words
+        const int mu = st.h_mu[s][p];
+        if (mu < 0) no_union = true;
+        if (mu > need) need = mu;
+    }
+    c->need = need;
+    if (no_union) return cfail(c, PIE_E_CAPACITY, "%s", kd.no_union);
+    if (need > st.cap)
+        return cfail(c, PIE_E_CAPACITY, "a union of %lld rows exceeds the reserved capacity %lld on some rank: collect what is in flight, %s_reserve(pie_comm_needed_cap), repeat the step", need, st.cap, kd.api);
+    return PIE_OK;
+}
+
+// the gathered Mu words ([local index][world]) of a step that is collected, did not fail and whose buffers are not reused: nullptr otherwise
+const int* step_mu(pie_comm* c, const StepKind& kd, int64_t step)
+{
+    const pie_steps& st = steps_of(c, kd);
+    if (step < 0 || step >= st.collected || step + kd.sets <= st.begun) return nullptr;
+    const int s = (int)(step % kd.sets);
+    return st.rc[s] == PIE_OK ? st.h_mu[s] : nullptr;
+}
+
+int step_invalid(pie_comm* c, const StepKind& kd, int64_t step)
+{
+    return cfail(c, PIE_E_STATE, "%s: step %lld is not collected, failed before its exchange, or its buffers were reused", kd.api, (long long)step);
+}
+
+int step_gathered_ptr(pie_comm* c, const StepKind& kd, int32_t at_rank, int64_t step, void** base_out, size_t* rank_stride_words, size_t* u_pad_out, size_t* cap_out)
+{
+    if (!c) return PIE_E_INVAL;
+    const pie_steps& st = steps_of(c, kd);
+    const int k = local_index(c, at_rank);
+    if (k < 0 || st.L <= 0) return cfail(c, PIE_E_STATE, "rank %d is not local to this communicator or nothing was reserved", at_rank);
+    if (!step_mu(c, kd, step)) return step_invalid(c, kd, step);
+    if (base_out) *base_out = st.gath[step % kd.sets][k];
+    if (rank_stride_words) *rank_stride_words = (size_t)st.L;
+    if (u_pad_out) *u_pad_out = (size_t)st.u_pad;
+    if (cap_out) *cap_out = (size_t)st.cap;
+    return PIE_OK;
+}
+
+// what both read_gathered forms share: the message of src_rank as at_rank holds it, its Mu from the words collect already has,
+// the user offsets; *have_out = the union rows the message holds (PIE_E_CAPACITY if rows or masks are asked for and cap is below it)
+int step_read_head(pie_comm* c, const StepKind& kd, int32_t at_rank, int32_t src_rank, int64_t step, int32_t* uoff_out, int32_t* rows_out, bool want_rows,
+                   size_t cap, size_t* mu_out, const int** msg_out, size_t* have_out)
+{
+    void* base = nullptr;
+    int rc = step_gathered_ptr(c, kd, at_rank, step, &base, nullptr, nullptr, nullptr);
+    if (rc) return rc;
+    if (src_rank < 0 || src_rank >= c->world) return cfail(c, PIE_E_INVAL, "source rank outside the communicator");
+    const pie_steps& st = steps_of(c, kd);
+    const int k = local_index(c, at_rank);
+    PIE_CHIP(c, hipSetDevice(c->device[k]));
+    const int* msg = static_cast<const int*>(base) + (size_t)src_rank * (size_t)st.L;
+    const int mu32 = step_mu(c, kd, step)[(size_t)k * (size_t)c->world + (size_t)src_rank];
+    const size_t mu = mu32 > 0 ? (size_t)mu32 : 0;
+    if (mu_out) *mu_out = mu;
+    if (uoff_out) PIE_CHIP(c, hipMemcpy(uoff_out, msg, ((size_t)st.u_pad + 1) * 4, hipMemcpyDeviceToHost));
+    const size_t have = mu < (size_t)st.cap ? mu : (size_t)st.cap;
+    if (want_rows && have > cap) return cfail(c, PIE_E_CAPACITY, "cap %zu < %zu union rows", cap, have);
+    if (rows_out && have) PIE_CHIP(c, hipMemcpy(rows_out, msg + st.u_pad + 2, have * 4, hipMemcpyDeviceToHost));
+    *msg_out = msg;
+    *have_out = have;
+    return PIE_OK;
 }
 
 } // namespace
 
 extern "C" {
 
-int pie_comm_wide_step_reserve(pie_comm* c, int32_t n_q_max, int32_t u_pad_in, size_t union_cap)
+int pie_comm_step_reserve(pie_comm* c, int32_t n_q, int32_t u_pad, size_t union_cap) { return step_reserve(c, kOrdinary, n_q, u_pad, union_cap); }
+int pie_comm_step_begin(pie_comm* c, const pie_query* queries, int32_t n_q) { return step_begin(c, kOrdinary, queries, n_q); }
+int pie_comm_step_finish(pie_comm* c, size_t* m_out) { return step_finish(c, kOrdinary, m_out, (size_t)-1); }
+int pie_comm_step_collect(pie_comm* c, int64_t* step_out) { return step_collect(c, kOrdinary, step_out); }
+int pie_comm_step_gathered_ptr(pie_comm* c, int32_t at_rank, int64_t step, void** base_out, size_t* rank_stride_words, size_t* u_pad_out, size_t* cap_out)
 {
-    if (!c) return PIE_E_INVAL;
-    if (n_q_max < 1 || n_q_max > PIE_WIDE_MAX) return cfail(c, PIE_E_INVAL, "a wide step holds 1..%d queries (got %d)", PIE_WIDE_MAX, n_q_max);
-    long long u_pad = 0;
-    int rc = resolve_u_pad(c, u_pad_in, &u_pad);
-    if (rc) return rc;
-    const long long cap = (long long)(union_cap > 0 ? union_cap : 1024);
-    const int words = (n_q_max + 63) / 64;
-    if (wide_msg_words(u_pad, cap, words) > 0x7FFFFFF0LL) return cfail(c, PIE_E_INVAL, "a message of %lld words is too long", wide_msg_words(u_pad, cap, words));
-    if (c->WL > 0 && c->w_u_pad == u_pad && cap <= c->w_cap && words <= c->w_words_max && c->wmsg[0].size() == (size_t)c->n_local && c->wmsg[0][0]) return PIE_OK;
-    if (c->w_begun != c->w_collected) return cfail(c, PIE_E_STATE, "wide steps are in flight: collect them before the message size changes");
-    free_wide_step_buffers(c, false);
-    c->w_u_pad = u_pad;
-    c->w_cap = cap;
-    c->w_words_max = words;
-    c->WL = wide_msg_words(u_pad, cap, words);
-    if (c->xstream.size() != (size_t)c->n_local) c->xstream.assign((size_t)c->n_local, nullptr);
-    for (int s = 0; s < pie_comm::kWideSets; ++s) {
-        if (c->w_ready[s].size() != (size_t)c->n_local) { c->w_ready[s].assign((size_t)c->n_local, nullptr); c->w_done[s].assign((size_t)c->n_local, nullptr); }
-        PIE_CHIP(c, hipHostMalloc(&c->w_h_mu[s], (size_t)c->n_local * (size_t)c->world * 4, hipHostMallocMapped));
-        PIE_CHIP(c, hipHostGetDevicePointer((void**)&c->w_h_mu_dev[s], c->w_h_mu[s], 0));
-    }
-    for (int k = 0; k < c->n_local; ++k) {
-        PIE_CHIP(c, hipSetDevice(c->device[k]));
-        if (!c->xstream[k]) PIE_CHIP(c, hipStreamCreateWithFlags(&c->xstream[k], hipStreamNonBlocking));
-        for (int s = 0; s < pie_comm::kWideSets; ++s) {
-            PIE_CHIP(c, hipMalloc(&c->wmsg[s][k], (size_t)c->WL * 4));
-            PIE_CHIP(c, hipMalloc(&c->wgath[s][k], (size_t)c->WL * 4 * (size_t)c->world));
-            PIE_CHIP(c, hipMemset(c->wmsg[s][k], 0, (size_t)c->WL * 4));
-            if (!c->w_ready[s][k]) PIE_CHIP(c, hipEventCreateWithFlags(&c->w_ready[s][k], hipEventDisableTiming));
-            if (!c->w_done[s][k]) PIE_CHIP(c, hipEventCreateWithFlags(&c->w_done[s][k], hipEventDisableTiming));
-        }
-    }
-    return PIE_OK;
+    return step_gathered_ptr(c, kOrdinary, at_rank, step, base_out, rank_stride_words, u_pad_out, cap_out);
 }
 
-int pie_comm_wide_step_begin(pie_comm* c, const pie_query* queries, int32_t n_q)
-{
-    if (!c) return PIE_E_INVAL;
-    if (!queries || n_q < 1 || n_q > PIE_WIDE_MAX) return cfail(c, PIE_E_INVAL, "a wide step holds 1..%d queries (got %d)", PIE_WIDE_MAX, n_q);
-    if (c->WL <= 0) return cfail(c, PIE_E_STATE, "pie_comm_wide_step_reserve first");
-    if (c->begun != c->collected) return cfail(c, PIE_E_STATE, "ordinary steps are in flight (pie_comm_step_*): collect them first");
-    if ((n_q + 63) / 64 > c->w_words_max) return cfail(c, PIE_E_STATE, "reserved for at most %d queries: pie_comm_wide_step_reserve again", c->w_words_max * 64);
-    if (c->w_begun - c->w_finished >= pie_comm::kWideSets - 2)
-        return cfail(c, PIE_E_STATE, "%d wide steps are already begun: pie_comm_wide_step_finish first", pie_comm::kWideSets - 2);
-    for (int k = 0; k < c->n_local; ++k)
-        if (pie_batch_room(c->ctx[k]) <= 0)
-            return cfail(c, PIE_E_STATE, "rank %d: the steps begun fill its batch slots (three per batch lane): pie_comm_wide_step_finish first", c->rank_of[k]);
-    if (c->w_begun - c->w_collected >= pie_comm::kWideSets)
-        return cfail(c, PIE_E_STATE, "%d wide steps are uncollected: pie_comm_wide_step_collect first", pie_comm::kWideSets);
-    const int s = (int)(c->w_begun % pie_comm::kWideSets);
-    int begun = 0, rc = PIE_OK;
-    for (int k = 0; k < c->n_local && rc == PIE_OK; ++k) {
-        rc = pie_scan_wide_begin_union(c->ctx[k], queries, n_q, c->wmsg[s][k], (size_t)c->w_u_pad, (size_t)c->w_cap);
-        if (rc == PIE_OK) ++begun;
-        else cfail(c, rc, "rank %d: %s", c->rank_of[k], pie_last_error(c->ctx[k]));
-    }
-    if (rc != PIE_OK) { // the step is not counted
-        if (begun > 0) wide_step_drain(c, begun, rc);
-        return rc;
-    }
-    c->w_step_nq[s] = n_q;
-    c->w_step_rc[s] = PIE_OK;
-    c->w_begun++;
-    return PIE_OK;
-}
-
-int pie_comm_wide_step_finish(pie_comm* c, size_t* m_out, size_t m_cap)
-{
-    if (!c) return PIE_E_INVAL;
-    if (c->w_finished >= c->w_begun) return cfail(c, PIE_E_STATE, "pie_comm_wide_step_finish without pie_comm_wide_step_begin");
-    const int s = (int)(c->w_finished % pie_comm::kWideSets);
-    const int n_q = c->w_step_nq[s];
-    if (m_out && m_cap < (size_t)c->n_local * (size_t)n_q)
-        return cfail(c, PIE_E_CAPACITY, "m_cap %zu < %d local ranks x %d queries", m_cap, c->n_local, n_q);
-    std::vector<size_t> m((size_t)c->n_local * (size_t)n_q, 0);
-    int first_rc = PIE_OK;
-    for (int k = 0; k < c->n_local; ++k) {
-        int ready = 0, nq = 0;
-        const int rc = pie_scan_wide_finish_packed(c->ctx[k], &m[(size_t)k * n_q], (size_t)n_q, &nq, &ready);
-        if (rc != PIE_OK && first_rc == PIE_OK) {
-            first_rc = rc;
-            cfail(c, rc, "rank %d: %s", c->rank_of[k], pie_last_error(c->ctx[k]));
-        }
-        // ready = 0: the header (Mu = -1) was written on the context's stream behind the batch: the exchange stream waits for exactly that
-        PIE_CHIP(c, hipSetDevice(c->device[k]));
-        if (!ready) {
-            PIE_CHIP(c, hipEventRecord(c->w_ready[s][k], c->stream[k]));
-            PIE_CHIP(c, hipStreamWaitEvent(c->xstream[k], c->w_ready[s][k], 0));
-        }
-    }
-    c->w_finished++;
-    c->w_step_rc[s] = first_rc;
-    if (first_rc != PIE_OK) return first_rc; // every local batch has been finished; no exchange is queued for this step (its collect says so)
-    // only the prefix this step uses: every rank knows n_q, so every rank agrees on the length
-    const size_t count = (size_t)wide_msg_words(c->w_u_pad, c->w_cap, (n_q + 63) / 64);
-    int rc = exchange(c, c->wmsg[s], c->wgath[s], count, (size_t)c->WL, c->xstream);
-    if (rc) { c->w_step_rc[s] = rc; return rc; }
-    for (int k = 0; k < c->n_local; ++k) {
-        PIE_CHIP(c, hipSetDevice(c->device[k]));
-        hipLaunchKernelGGL(k_pick_words, dim3(1), dim3(64), 0, c->xstream[k], c->wgath[s][k], (long long)c->WL, (long long)c->w_u_pad + 1, c->world,
-                           c->w_h_mu_dev[s] + (size_t)k * (size_t)c->world);
-        PIE_CHIP(c, hipEventRecord(c->w_done[s][k], c->xstream[k]));
-    }
-    if (m_out) memcpy(m_out, m.data(), m.size() * sizeof(size_t));
-    return PIE_OK;
-}
-
-int pie_comm_wide_step_collect(pie_comm* c, int64_t* step_out)
-{
-    if (!c) return PIE_E_INVAL;
-    if (c->w_collected >= c->w_finished) return cfail(c, PIE_E_STATE, "no exchange to collect: pie_comm_wide_step_finish first");
-    const int s = (int)(c->w_collected % pie_comm::kWideSets);
-    if (step_out) *step_out = (int64_t)c->w_collected;
-    if (c->w_step_rc[s] != PIE_OK) {
-        c->w_collected++;
-        return cfail(c, PIE_E_STATE, "wide step %lld failed before its exchange (status %d): nothing was exchanged", (long long)c->w_collected - 1, c->w_step_rc[s]);
-    }
-    int wrc = PIE_OK;
-    for (int k = 0; k < c->n_local && wrc == PIE_OK; ++k) wrc = wait_event(c, k, c->w_done[s][k], "wide step exchange"); // the side stream only
-    c->w_collected++;
-    if (wrc != PIE_OK) { c->w_step_rc[s] = wrc; return wrc; }
-    long long need = 0;
-    bool no_union = false;
-    for (int p = 0; p < c->world; ++p) { // every rank holds the same world Mu words
-        const int mu = c->w_h_mu[s][p];
-        if (mu < 0) no_union = true;
-        if (mu > need) need = mu;
-    }
-    c->need = need;
-    if (no_union)
-        return cfail(c, PIE_E_CAPACITY, "a shard's wide batch kept no union (Mu = -1, pie_comm_wide_step_status): repeat the step; dense queries go through pie_comm_scan_batch_gather");
-    if (need > c->w_cap)
-        return cfail(c, PIE_E_CAPACITY, "a union of %lld rows exceeds the reserved capacity %lld on some rank: collect what is in flight, pie_comm_wide_step_reserve(pie_comm_needed_cap), repeat the step", need, c->w_cap);
-    return PIE_OK;
-}
-
-int pie_comm_wide_step_status(pie_comm* c, int64_t step, int32_t* mu_out)
-{
-    if (!c) return PIE_E_INVAL;
-    const int* mu = wide_step_mu(c, step);
-    if (!mu) return cfail(c, PIE_E_STATE, "wide step %lld is not collected, failed before its exchange, or its buffers were reused", (long long)step);
-    if (mu_out)
-        for (int p = 0; p < c->world; ++p) mu_out[p] = mu[p];
-    return PIE_OK;
-}
-
+int pie_comm_wide_step_reserve(pie_comm* c, int32_t n_q_max, int32_t u_pad, size_t union_cap) { return step_reserve(c, kWide, n_q_max, u_pad, union_cap); }
+int pie_comm_wide_step_begin(pie_comm* c, const pie_query* queries, int32_t n_q) { return step_begin(c, kWide, queries, n_q); }
+int pie_comm_wide_step_finish(pie_comm* c, size_t* m_out, size_t m_cap) { return step_finish(c, kWide, m_out, m_cap); }
+int pie_comm_wide_step_collect(pie_comm* c, int64_t* step_out) { return step_collect(c, kWide, step_out); }
 int pie_comm_wide_step_gathered_ptr(pie_comm* c, int32_t at_rank, int64_t step, void** base_out, size_t* rank_stride_words, size_t* u_pad_out,
                                     size_t* cap_out, int* words_out)
 {
+    const int rc = step_gathered_ptr(c, kWide, at_rank, step, base_out, rank_stride_words, u_pad_out, cap_out);
+    if (rc == PIE_OK && words_out) *words_out = step_words(kWide, c->wide.nq[step % kWide.sets]);
+    return rc;
+}
+
+// masks: planar in an ordinary message (a plane of low 32-bit words, then a plane of high words when the step had more than 32 queries)
+int pie_comm_step_read_gathered(pie_comm* c, int32_t at_rank, int32_t src_rank, int64_t step, int32_t* uoff_out, int32_t* rows_out, uint64_t* masks_out,
+                                size_t cap, size_t* mu_out)
+{
     if (!c) return PIE_E_INVAL;
-    const int k = local_index(c, at_rank);
-    if (k < 0 || c->WL <= 0) return cfail(c, PIE_E_STATE, "rank %d is not local to this communicator or nothing was reserved", at_rank);
-    if (!wide_step_mu(c, step)) return cfail(c, PIE_E_STATE, "wide step %lld is not collected, failed before its exchange, or its buffers were reused", (long long)step);
-    const int s = (int)(step % pie_comm::kWideSets);
-    if (base_out) *base_out = c->wgath[s][k];
-    if (rank_stride_words) *rank_stride_words = (size_t)c->WL;
-    if (u_pad_out) *u_pad_out = (size_t)c->w_u_pad;
-    if (cap_out) *cap_out = (size_t)c->w_cap;
-    if (words_out) *words_out = (c->w_step_nq[s] + 63) / 64;
+    const int* msg = nullptr;
+    size_t have = 0;
+    int rc = step_read_head(c, kOrdinary, at_rank, src_rank, step, uoff_out, rows_out, rows_out || masks_out, cap, mu_out, &msg, &have);
+    if (rc) return rc;
+    const pie_steps& st = c->ord;
+    if (masks_out && have) {
+        std::vector<uint32_t> lo(have), hi;
+        PIE_CHIP(c, hipMemcpy(lo.data(), msg + st.u_pad + 2 + st.cap, have * 4, hipMemcpyDeviceToHost));
+        if (st.words_max == 3 && st.nq[step % kOrdinary.sets] > 32) {
+            hi.resize(have);
+            PIE_CHIP(c, hipMemcpy(hi.data(), msg + st.u_pad + 2 + 2 * st.cap, have * 4, hipMemcpyDeviceToHost));
+        }
+        for (size_t i = 0; i < have; ++i) masks_out[i] = (uint64_t)lo[i] | (hi.empty() ? 0ull : ((uint64_t)hi[i] << 32));
+    }
     return PIE_OK;
 }
 
+// ... interleaved in a wide one: two int32 words per 64-bit mask word, low word first — the host's uint64 as it stands
 int pie_comm_wide_step_read_gathered(pie_comm* c, int32_t at_rank, int32_t src_rank, int64_t step, int32_t* uoff_out, int32_t* rows_out,
                                      uint64_t* masks_out, size_t cap, int* words_out, size_t* mu_out)
 {
     if (!c) return PIE_E_INVAL;
     if (mu_out) *mu_out = 0;
     if (words_out) *words_out = 0;
-    void* base = nullptr;
-    int words = 0;
-    int rc = pie_comm_wide_step_gathered_ptr(c, at_rank, step, &base, nullptr, nullptr, nullptr, &words);
+    const int* msg = nullptr;
+    size_t have = 0;
+    int rc = step_read_head(c, kWide, at_rank, src_rank, step, uoff_out, rows_out, rows_out || masks_out, cap, mu_out, &msg, &have);
     if (rc) return rc;
-    if (src_rank < 0 || src_rank >= c->world) return cfail(c, PIE_E_INVAL, "source rank outside the communicator");
-    const int k = local_index(c, at_rank);
-    PIE_CHIP(c, hipSetDevice(c->device[k]));
-    const int* msg = static_cast<const int*>(base) + (size_t)src_rank * (size_t)c->WL;
-    const int mu32 = wide_step_mu(c, step)[(size_t)k * (size_t)c->world + (size_t)src_rank];
-    const size_t mu = mu32 > 0 ? (size_t)mu32 : 0;
-    if (mu_out) *mu_out = mu;
+    const pie_steps& st = c->wide;
+    const int words = step_words(kWide, st.nq[step % kWide.sets]);
     if (words_out) *words_out = words;
-    if (uoff_out) PIE_CHIP(c, hipMemcpy(uoff_out, msg, ((size_t)c->w_u_pad + 1) * 4, hipMemcpyDeviceToHost));
-    const size_t have = mu < (size_t)c->w_cap ? mu : (size_t)c->w_cap;
-    if ((rows_out || masks_out) && have > cap) return cfail(c, PIE_E_CAPACITY, "cap %zu < %zu union rows", cap, have);
-    if (rows_out && have) PIE_CHIP(c, hipMemcpy(rows_out, msg + c->w_u_pad + 2, have * 4, hipMemcpyDeviceToHost));
-    // two int32 words per 64-bit mask word, low word first: the host's uint64 as it stands
-    if (masks_out && have) PIE_CHIP(c, hipMemcpy(masks_out, msg + c->w_u_pad + 2 + c->w_cap, have * (size_t)words * 8, hipMemcpyDeviceToHost));
+    if (masks_out && have) PIE_CHIP(c, hipMemcpy(masks_out, msg + st.u_pad + 2 + st.cap, have * (size_t)words * 8, hipMemcpyDeviceToHost));
+    return PIE_OK;
+}
+
+int pie_comm_wide_step_status(pie_comm* c, int64_t step, int32_t* mu_out)
+{
+    if (!c) return PIE_E_INVAL;
+    const int* mu = step_mu(c, kWide, step);
+    if (!mu) return step_invalid(c, kWide, step);
+    if (mu_out)
+        for (int p = 0; p < c->world; ++p) mu_out[p] = mu[p];
     return PIE_OK;
 }
 
@@ -1436,22 +1330,23 @@ int pie_comm_wide_step_read_feed(pie_comm* c, int32_t at_rank, int32_t src_rank,
     int words = 0;
     int rc = pie_comm_wide_step_gathered_ptr(c, at_rank, step, &base, nullptr, nullptr, nullptr, &words);
     if (rc) return rc;
-    const int n_q = c->w_step_nq[step % pie_comm::kWideSets];
-    if (src_rank < 0 || src_rank >= c->world || qi < 0 || qi >= n_q || local_user < 0 || (long long)local_user >= c->w_u_pad)
+    const pie_steps& st = c->wide;
+    const int n_q = st.nq[step % kWide.sets];
+    if (src_rank < 0 || src_rank >= c->world || qi < 0 || qi >= n_q || local_user < 0 || (long long)local_user >= st.u_pad)
         return cfail(c, PIE_E_INVAL, "source rank / query / user outside the step");
     const int k = local_index(c, at_rank);
     PIE_CHIP(c, hipSetDevice(c->device[k]));
-    const int* msg = static_cast<const int*>(base) + (size_t)src_rank * (size_t)c->WL;
+    const int* msg = static_cast<const int*>(base) + (size_t)src_rank * (size_t)st.L;
     int ab[2] = {0, 0};
     PIE_CHIP(c, hipMemcpy(ab, msg + local_user, 8, hipMemcpyDeviceToHost));
     if (ab[0] < 0 || ab[1] < ab[0]) return cfail(c, PIE_E_STATE, "rank %d kept no union in wide step %lld (Mu = -1)", src_rank, (long long)step);
-    if ((long long)ab[1] > c->w_cap) return cfail(c, PIE_E_CAPACITY, "the user's rows were cut: the union outgrew the reserved capacity %lld", c->w_cap);
+    if ((long long)ab[1] > st.cap) return cfail(c, PIE_E_CAPACITY, "the user's rows were cut: the union outgrew the reserved capacity %lld", st.cap);
     const size_t n = (size_t)(ab[1] - ab[0]);
     if (n == 0) return PIE_OK;
     std::vector<int32_t> rows(n);
     std::vector<uint64_t> masks(n * (size_t)words);
-    PIE_CHIP(c, hipMemcpy(rows.data(), msg + c->w_u_pad + 2 + ab[0], n * 4, hipMemcpyDeviceToHost));
-    PIE_CHIP(c, hipMemcpy(masks.data(), msg + c->w_u_pad + 2 + c->w_cap + (size_t)ab[0] * 2 * (size_t)words, n * (size_t)words * 8, hipMemcpyDeviceToHost));
+    PIE_CHIP(c, hipMemcpy(rows.data(), msg + st.u_pad + 2 + ab[0], n * 4, hipMemcpyDeviceToHost));
+    PIE_CHIP(c, hipMemcpy(masks.data(), msg + st.u_pad + 2 + st.cap + (size_t)ab[0] * 2 * (size_t)words, n * (size_t)words * 8, hipMemcpyDeviceToHost));
     size_t kk = 0;
     for (size_t i = 0; i < n; ++i)
         if ((masks[i * (size_t)words + (size_t)(qi >> 6)] >> (qi & 63)) & 1ull) {

@@ -22,6 +22,7 @@
 #include <string.h>
 
 #include "pie_scan.h"
+#include "pie_nq_ring.h"
 
 /* ---- the C ABI, resolved at open() ------------------------------------------------------------------ */
 #define PIE_SYMBOLS(X)                                                                                              \
@@ -1253,11 +1254,10 @@ static napi_value throw_comm(napi_env env, pie_comm *cm, int rc)
 typedef struct comm_box_s {
     pie_comm *comm;
     ctx_box *boxes; /* context handles handed out by commCtx and still alive */
-    /* queries of the WIDE steps begun and not finished on THIS communicator (at most six): kept here, not in file-static state,
-     * so two communicators (or two Node workers) never pop each other's n_q */
-    int wide_nq_ring[8];
-    unsigned wide_nq_head, wide_nq_tail;
+    pie_nq_ring step_nq, wide_nq; /* n_q of the ordinary / wide steps begun and not finished on THIS communicator */
 } comm_box;
+
+enum { STEP_SETS = 16, WIDE_STEP_SETS = 8 }; /* the rings' capacities: the buffer sets of pie_comm_step_* / pie_comm_wide_step_* */
 
 static void comm_unlink_ctx(ctx_box *b)
 {
@@ -1364,7 +1364,8 @@ static napi_value fn_comm_destroy(napi_env env, napi_callback_info info)
     comm_orphan_ctxs(b); /* handles handed out by commCtx now read as destroyed contexts */
     if (b->comm) p_pie_comm_destroy(b->comm);
     b->comm = NULL;
-    b->wide_nq_head = b->wide_nq_tail = 0;
+    nq_ring_clear(&b->step_nq);
+    nq_ring_clear(&b->wide_nq);
     return js_int(env, 0);
 }
 
@@ -1674,40 +1675,43 @@ static napi_value fn_comm_step_reserve(napi_env env, napi_callback_info info)
     return js_int(env, 0);
 }
 
-static int step_nq_ring[16];
-static unsigned step_nq_head = 0, step_nq_tail = 0; /* queries of the steps begun and not finished (three per batch lane of the shards: at most twelve) */
-
-static napi_value fn_comm_step_begin(napi_env env, napi_callback_info info)
+/* the tail of both begins: the step's n_q is kept for its finish.  After a failure that is not a plain refusal (PIE_E_STATE /
+ * PIE_E_INVAL) the ring is emptied: the library may have drained every step in flight (it does when a shard failed after others
+ * began), and then nothing is left to finish here either.  The rule errs in two rare cases the status alone cannot tell apart —
+ * the FIRST shard failing with another status (nothing was drained: the caller's next finish throws here although the library
+ * holds the step) and a later shard's own PIE_E_STATE (drained, ring kept: the next finish returns the library's PIE_E_STATE).
+ * Neither can write past a buffer: step_finish gives the library room for the largest step of the kind or tells it the room. */
+static napi_value step_begun(napi_env env, comm_box *cbx, pie_nq_ring *ring, unsigned cap, int rc, int n_q)
 {
-    ARGS(4)
-    comm_box *cbx = get_comm_box(env, argv[0]);
-    if (!cbx) return NULL;
-    pie_query q[PIE_BATCH_MAX];
-    int n_q = 0;
-    if (!read_queries(env, argv[1], argv[2], argv[3], q, &n_q)) {
-        napi_throw_type_error(env, NULL, "commStepBegin(comm, BigInt64Array nows, BigInt64Array cutoffs, BigUint64Array masks)");
-        return NULL;
+    if (rc) {
+        if (rc != PIE_E_STATE && rc != PIE_E_INVAL) nq_ring_clear(ring);
+        return throw_comm(env, cbx->comm, rc);
     }
-    int rc = p_pie_comm_step_begin(cbx->comm, q, n_q);
-    if (rc) return throw_comm(env, cbx->comm, rc);
-    step_nq_ring[step_nq_head++ & 15] = n_q;
+    nq_ring_push(ring, cap, n_q);
     return js_int(env, 0);
 }
 
-static napi_value fn_comm_step_finish(napi_env env, napi_callback_info info)
+/* both finishes: -> [rank][query] M of the oldest begun step */
+static napi_value step_finish(napi_env env, napi_value comm, int wide)
 {
-    ARGS(1)
-    comm_box *cbx = get_comm_box(env, argv[0]);
+    comm_box *cbx = get_comm_box(env, comm);
     if (!cbx) return NULL;
-    if (step_nq_tail == step_nq_head) return throw_state(env, "pie_comm error -6: commStepFinish without commStepBegin");
-    const int n_q = step_nq_ring[step_nq_tail++ & 15];
+    pie_nq_ring *ring = wide ? &cbx->wide_nq : &cbx->step_nq;
+    const unsigned cap = wide ? WIDE_STEP_SETS : STEP_SETS;
+    if (!nq_ring_count(ring))
+        return throw_state(env, wide ? "pie_comm error -6: commWideStepFinish without commWideStepBegin" : "pie_comm error -6: commStepFinish without commStepBegin");
+    const int n_q = nq_ring_front(ring, cap);
     const int world = p_pie_comm_world(cbx->comm);
-    size_t *m = (size_t *)calloc((size_t)world * (size_t)n_q, sizeof *m);
+    /* the library writes local_ranks x the step's OWN n_q: the wide call checks that against m_cap, the ordinary one has no such
+     * argument and gets room for the largest ordinary step, whatever the ring says */
+    const size_t m_cap = (size_t)world * (size_t)(wide ? n_q : PIE_BATCH_MAX);
+    size_t *m = (size_t *)calloc(m_cap, sizeof *m);
     if (!m) {
         napi_throw_error(env, NULL, "out of memory");
         return NULL;
     }
-    int rc = p_pie_comm_step_finish(cbx->comm, m);
+    int rc = wide ? p_pie_comm_wide_step_finish(cbx->comm, m, m_cap) : p_pie_comm_step_finish(cbx->comm, m);
+    if (!wide || rc != PIE_E_CAPACITY) nq_ring_pop(ring); /* a wide finish's PIE_E_CAPACITY consumed nothing */
     if (rc) {
         free(m);
         return throw_comm(env, cbx->comm, rc);
@@ -1722,6 +1726,27 @@ static napi_value fn_comm_step_finish(napi_env env, napi_callback_info info)
     }
     free(m);
     return out;
+}
+
+static napi_value fn_comm_step_begin(napi_env env, napi_callback_info info)
+{
+    ARGS(4)
+    comm_box *cbx = get_comm_box(env, argv[0]);
+    if (!cbx) return NULL;
+    pie_query q[PIE_BATCH_MAX];
+    int n_q = 0;
+    if (!read_queries(env, argv[1], argv[2], argv[3], q, &n_q)) {
+        napi_throw_type_error(env, NULL, "commStepBegin(comm, BigInt64Array nows, BigInt64Array cutoffs, BigUint64Array masks)");
+        return NULL;
+    }
+    if (nq_ring_count(&cbx->step_nq) >= STEP_SETS) return throw_state(env, "pie_comm error -6: sixteen steps are begun: commStepFinish first");
+    return step_begun(env, cbx, &cbx->step_nq, STEP_SETS, p_pie_comm_step_begin(cbx->comm, q, n_q), n_q);
+}
+
+static napi_value fn_comm_step_finish(napi_env env, napi_callback_info info)
+{
+    ARGS(1)
+    return step_finish(env, argv[0], 0);
 }
 
 static napi_value fn_comm_step_collect(napi_env env, napi_callback_info info)
@@ -1809,7 +1834,7 @@ static napi_value fn_comm_wide_step_begin(napi_env env, napi_callback_info info)
         napi_throw_type_error(env, NULL, "commWideStepBegin(comm, BigInt64Array nows, BigInt64Array cutoffs, BigUint64Array masks): 1..512 queries, equal lengths");
         return NULL;
     }
-    if (cbx->wide_nq_head - cbx->wide_nq_tail >= 8) return throw_state(env, "pie_comm error -6: eight wide steps are begun: commWideStepFinish first");
+    if (nq_ring_count(&cbx->wide_nq) >= WIDE_STEP_SETS) return throw_state(env, "pie_comm error -6: eight wide steps are begun: commWideStepFinish first");
     pie_query *q = (pie_query *)malloc(a * sizeof(pie_query));
     if (!q) {
         napi_throw_error(env, NULL, "commWideStepBegin: out of host memory");
@@ -1822,45 +1847,13 @@ static napi_value fn_comm_wide_step_begin(napi_env env, napi_callback_info info)
     }
     int rc = p_pie_comm_wide_step_begin(cbx->comm, q, (int32_t)a);
     free(q);
-    if (rc) {
-        /* a partial failure drained every wide step in flight inside the library: nothing is left to finish here either */
-        if (rc != PIE_E_STATE && rc != PIE_E_INVAL) cbx->wide_nq_tail = cbx->wide_nq_head;
-        return throw_comm(env, cbx->comm, rc);
-    }
-    cbx->wide_nq_ring[cbx->wide_nq_head++ & 7] = (int)a;
-    return js_int(env, 0);
+    return step_begun(env, cbx, &cbx->wide_nq, WIDE_STEP_SETS, rc, (int)a);
 }
 
 static napi_value fn_comm_wide_step_finish(napi_env env, napi_callback_info info)
 {
     ARGS(1)
-    comm_box *cbx = get_comm_box(env, argv[0]);
-    if (!cbx) return NULL;
-    if (cbx->wide_nq_tail == cbx->wide_nq_head) return throw_state(env, "pie_comm error -6: commWideStepFinish without commWideStepBegin");
-    const int n_q = cbx->wide_nq_ring[cbx->wide_nq_tail & 7];
-    const int world = p_pie_comm_world(cbx->comm);
-    const size_t m_cap = (size_t)world * (size_t)n_q; /* the library checks it against local_ranks x the step's own n_q */
-    size_t *m = (size_t *)calloc(m_cap, sizeof *m);
-    if (!m) {
-        napi_throw_error(env, NULL, "out of memory");
-        return NULL;
-    }
-    int rc = p_pie_comm_wide_step_finish(cbx->comm, m, m_cap);
-    if (rc != PIE_E_CAPACITY) cbx->wide_nq_tail++; /* PIE_E_CAPACITY consumed nothing */
-    if (rc) {
-        free(m);
-        return throw_comm(env, cbx->comm, rc);
-    }
-    napi_value out;
-    napi_create_array_with_length(env, (size_t)world, &out);
-    for (int r = 0; r < world; ++r) {
-        napi_value row;
-        napi_create_array_with_length(env, (size_t)n_q, &row);
-        for (int k = 0; k < n_q; ++k) napi_set_element(env, row, (uint32_t)k, js_int(env, (int64_t)m[(size_t)r * n_q + k]));
-        napi_set_element(env, out, (uint32_t)r, row);
-    }
-    free(m);
-    return out;
+    return step_finish(env, argv[0], 1);
 }
 
 static napi_value fn_comm_wide_step_collect(napi_env env, napi_callback_info info)

@@ -2,7 +2,10 @@
 (PIE_RCCL_LIB), three shards of one corpus on GPU 0.  Checks, against the oracle's scan of the unsharded table:
   - the synchronous per-query exchange, incl. the capacity overflow that every rank sees in the gathered headers;
   - the pipelined union exchange (step_begin / finish / collect, two steps begun ahead, rotating buffer sets), 7 and 40 queries;
-  - its overflow path (a union that outgrows the reservation is reported at collect, re-reserved, repeated).
+  - its overflow path (a union that outgrows the reservation is reported at collect, re-reserved, repeated);
+  - which gathered buffers are handed out: a step cut by the capacity yes; one not collected yet, or sixteen steps old, no;
+  - a shard that cannot begin: the step is refused and not counted, nothing is left in any shard, the next steps are exact;
+  - the step geometry is the steps' own: a synchronous reservation with another u_pad does not move it.
 usage: comm_stub_worker.py WORLD N_ROWS N_USERS"""
 import os
 import subprocess
@@ -24,6 +27,16 @@ import oracle_py
 import sph_pie_amd as pie
 
 T0, DAY, SEED = 1700000000000, 86400 * 1000, 0x5EED5EED
+E_CAPACITY, E_STATE = pie.binding.PIE_E_CAPACITY, -6
+
+
+def expect(code, fn, *a):
+    try:
+        fn(*a)
+    except pie.PieError as ex:
+        assert ex.code == code, ex
+        return
+    raise AssertionError("%s did not fail with %d" % (getattr(fn, "__name__", fn), code))
 
 
 def main():
@@ -112,6 +125,10 @@ def main():
         assert ex.code == pie.binding.PIE_E_CAPACITY, ex
     need = comm.needed_cap()
     assert need > 16
+    # capacity is not a failed step: its messages (cut at 16 rows) are still handed out; a step that is not collected is refused
+    for r in range(world):
+        assert comm.step_read_gathered(0, r, 0)[0].size == max(c.n_users for c in ctxs) + 1
+    expect(E_STATE, comm.step_read_gathered, 0, 0, 1)
     comm.step_reserve(len(qs), 0, need)
     nxt = run_pipelined(qs, want, 9, 1)
     # ... then a batch of 40 queries (two mask words per union row): a new reservation, more steps
@@ -119,6 +136,44 @@ def main():
     want40 = [oracle_py.scan(*cols, U, *q) for q in qs40]
     comm.step_reserve(40, 0, need)
     nxt = run_pipelined(qs40, want40, 6, nxt)
+    assert nxt == 16
+    expect(E_STATE, comm.step_read_gathered, 0, 0, nxt)     # not begun, let alone collected
+    expect(E_STATE, comm.step_read_gathered, 0, 0, 0)       # sixteen steps have begun since: its buffer set is the next step's
+    comm.step_read_gathered(0, 0, 1)
+
+    def shard_cannot_begin():
+        """A single scan in flight on the LAST rank's context: step_begin is refused with PIE_E_STATE and not counted, every
+        context's batch room is what it was, and four pipelined steps afterwards are exact and numbered without a gap.  The
+        refusal here comes from the room check step_begin makes before any shard begins.  The other branch, a shard failing after
+        others began with steps already in flight (step_drain), cannot be staged through the public API: a context refuses a
+        single scan while batches are in flight, and the room of every context is checked up front.  It is covered by being the
+        same code for the ordinary and the wide steps."""
+        nonlocal nxt
+        rooms = [c.batch_room() for c in ctxs]
+        assert min(rooms) > 0
+        ctxs[world - 1].scan_begin(qs[0][0], qs[0][1])
+        expect(E_STATE, comm.step_begin, qs)
+        ctxs[world - 1].scan_finish()
+        assert [c.batch_room() for c in ctxs] == rooms
+        nxt = run_pipelined(qs, want, 4, nxt)
+
+    shard_cannot_begin()
+    # ---- the step geometry is its own: the synchronous path's reservation, with another u_pad, does not move it.  (The step's
+    # u_pad is the LARGER of the two, so even an implementation that mixed them up would stay inside its buffers.)
+    u_max = max(c.n_users for c in ctxs)
+    comm.step_reserve(len(qs), u_max + 64, need)
+    comm.reserve(len(qs), u_max, 1024)
+    comm.step_begin(qs)
+    comm.step_finish()
+    st = comm.step_collect()
+    assert st == nxt
+    for at in range(world):
+        for r in range(world):
+            uoff, rows, masks = comm.step_read_gathered(at, r, st)
+            assert uoff.size == u_max + 64 + 1
+            assert np.all(uoff[maps[r][1].size:] == rows.size)
+    check_union(st, qs, want)
+    expect(E_STATE, comm.step_read_gathered, 0, 0, st - 16)   # more than sixteen steps old
     # the synchronous form still works between pipelined runs
     ms = comm.scan_batch_gather(qs[:3])
     assert [ms[r][0] for r in range(world)] == [int(comm.read_gathered(0, r, 0)[1].size) for r in range(world)]

@@ -6,7 +6,8 @@ unsharded table:
     which of the two is computed from the oracle's answers beforehand; then needed_cap, re-reserve, repeat;
   - 9 pipelined steps of 512 queries, 6 of 300, 4 of 65 (two steps begun ahead, the buffer sets rotate): for the last three
     steps of each run every global user's feed of every query, rebuilt from the gathered messages at every rank;
-  - wide_step_read_feed for sampled (query, user); the mutual exclusion with the ordinary steps; the ordinary steps afterwards.
+  - wide_step_read_feed for sampled (query, user); the mutual exclusion with the ordinary steps; the ordinary steps afterwards;
+  - a shard that cannot begin: the wide step is refused and not counted, nothing is left in any shard, the next steps are exact.
 usage: comm_wide_stub_worker.py WORLD N_ROWS N_USERS [no-union]   (no-union: this table's first steps must report Mu = -1)"""
 import os
 import subprocess
@@ -166,6 +167,17 @@ def main():
     # ---- the pipelined runs
     step = run_pipelined(512, 9, step)
     step = run_pipelined(300, 6, step)
+    step = run_pipelined(65, 4, step)
+    # ---- a shard that cannot begin (a single scan in flight on the LAST rank's context): PIE_E_STATE, the step is not counted,
+    # every context's batch room is what it was, four pipelined steps afterwards are exact and numbered without a gap.  The refusal
+    # comes from the room check made before any shard begins; a shard failing after others began with steps in flight cannot be
+    # staged through the public API (see comm_stub_worker.py: that branch is the same code for both kinds).
+    rooms = [c.batch_room() for c in ctxs]
+    assert min(rooms) > 0
+    ctxs[world - 1].scan_begin(all_q[0][0], all_q[0][1])
+    expect(E_STATE, comm.wide_step_begin, all_q[:65])
+    ctxs[world - 1].scan_finish()
+    assert [c.batch_room() for c in ctxs] == rooms
     step = run_pipelined(65, 4, step)
     # ---- mutual exclusion: no ordinary step while a wide step is uncollected, and the reverse
     qs7 = all_q[:7]
