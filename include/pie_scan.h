@@ -559,7 +559,8 @@ int pie_compact_geometry(pie_ctx *ctx, size_t n, int32_t *rows_per_wave_step_out
  * pie_shard_table).  pie_compact_rows that drops rows carries them over: the keys of the kept covered rows are gathered (they are
  * a prefix again: covered = the kept rows whose old row was covered) and the index is rebuilt; the column keeps its capacity
  * under PIE_COMPACT_SHRINK; if that step runs out of memory the compaction stands and the column is dropped.
- * A SHARDED context (after pie_shard_table) is out of scope: pie_token_set returns PIE_E_STATE there.
+ * A SHARDED context (after pie_shard_table) takes its column by GLOBAL row through pie_shard_token_* below; pie_token_set
+ * returns PIE_E_STATE there.
  * PIE_E_STATE: no table; no token column (all but pie_token_set); while a scan or batch is in flight (every call that takes a
  * context).  PIE_E_INVAL: NULL tok with k > 0.  PIE_E_HIP "probe bound exhausted": a probe loop ran its bound of `slots` steps
  * (an index out of step with its column — never seen; reported by the lookup or build that follows it).
@@ -584,6 +585,43 @@ int pie_token_layout(pie_ctx *ctx, size_t *covered_out, size_t *slots_out, int32
  * a table of 2^log2_slots slots (log2_slots <= 32, PIE_E_INVAL otherwise) — the rule the device applies */
 size_t pie_token_slots_for(size_t covered);
 int pie_token_homes(const uint64_t *tok, size_t k, uint32_t log2_slots, uint32_t *home_out);
+
+/* ---- the token column of a SHARDED context, by GLOBAL row.  Every shard is given the same call with the same arrays and keeps
+ * what is its own; nothing is exchanged (the rule of pie_shard_append_rows / pie_shard_set_end).
+ * Coverage: the context remembers covered_g — keys have been given for the global rows [0, covered_g), covered_g <= N_g — and
+ * holds the keys of its local rows whose global row lies below it.  The row map ascends, so these are a prefix [0, covered_l) of
+ * the local rows, covered_l = lower_bound(row map, local rows, covered_g).  Rows of other shards, and rows this shard's
+ * compactions dropped, are skipped silently.  covered_g grows on every shard alike, whether or not the shard kept a key.
+ * Slots: the index is sized by the shard's row count, which the host knows (covered_l only the device's row map knows):
+ * slots >= pie_token_slots_for(local rows) after every set and append, so it is at most half full; the token append that
+ * follows the row count passing half the slots rebuilds it into the next size — the one place an append waits.  Home slot,
+ * linear probing, the claim by compare-and-swap and the bounded probe loops with the status word are those of the plain index.
+ * pie_compact_rows that drops rows carries the column over as on a plain context: the keys of the kept covered local rows are
+ * gathered, covered_g stays, covered_l follows from the new row map, the index is rebuilt; out of memory in that step drops the
+ * column and the compaction stands.  Loads, generated tables and pie_shard_table drop the column.
+ * The plain calls on a sharded context that has a column: pie_token_append returns PIE_E_STATE (it would break covered_g);
+ * pie_token_lookup, pie_token_set_end and pie_token_layout run unchanged, in LOCAL ids.  pie_table_info.token_rows is covered_l.
+ * A key held by two shards (the same token given to sessions of users on different shards — a caller error in the reference):
+ * each shard answers for itself; pie_comm_token_lookup resolves it.
+ * PIE_E_STATE: a context that is not sharded, or whose row map does not cover its rows; no table; no column (all but
+ * pie_shard_token_set); a scan or batch in flight.  PIE_E_INVAL: NULL tok with k > 0; keys past N_g. */
+/* keys for the global rows [0, n), n <= N_g; replaces any earlier column.  Defined as: an empty column, then
+ * pie_shard_token_append of the n keys in chunks of at most 2^20 (no shard needs a device buffer of 16 n bytes).  May wait. */
+int pie_shard_token_set(pie_ctx *ctx, const uint64_t *tok /* [n][2] */, size_t n);
+/* keys for the global rows [covered_g, covered_g + k); PIE_E_INVAL if that passes N_g.  Queued and un-waited like
+ * pie_token_append, except when the column or the slot table must grow. */
+int pie_shard_token_append(pie_ctx *ctx, const uint64_t *tok, size_t k);
+/* pie_token_lookup with the row and the user as GLOBAL ids (read through the two maps); a key this shard does not hold answers
+ * -1 / live 0; of several local rows under one key the largest answers.  Every output pointer may be NULL.  k = 0 is allowed. */
+int pie_shard_token_lookup(pie_ctx *ctx, const uint64_t *tok, size_t k, int64_t now, int32_t *row_global_out, uint8_t *live_out,
+                           int32_t *user_global_out, int64_t *start_out, int64_t *end_out);
+/* one lookup, then pie_set_end's own path on the local rows found live (exactly how pie_token_set_end composes: repeats, both
+ * keys, the hot index and the ordered run stay in step).  rows_global_out[i] (may be NULL) = the global row written or -1. */
+int pie_shard_token_set_end(pie_ctx *ctx, const uint64_t *tok, const int64_t *new_end, size_t k, int64_t now, int32_t *rows_global_out);
+/* tests and tools: covered_g, covered_l, slots; slot_row_out[cap] (local rows; PIE_E_CAPACITY if cap < slots);
+ * tok_out[covered_l][2]; any may be NULL.  Waits. */
+int pie_shard_token_layout(pie_ctx *ctx, size_t *covered_global_out, size_t *covered_local_out, size_t *slots_out,
+                           int32_t *slot_row_out, size_t cap, uint64_t *tok_out);
 
 /* Host only, no context, no GPU: what the batched pass stores per selected row.  A row's 64-bit query mask is
  * live[r] & win[w] & disc[d] (r: queries whose `now` lies below the row's end, w: queries whose cutoff is <= its start, d: its
@@ -671,6 +709,20 @@ int pie_comm_append_rows(pie_comm *comm, const int64_t *start, const int64_t *en
 int pie_comm_set_end(pie_comm *comm, const int32_t *rows, const int64_t *new_end, size_t k);
 int pie_comm_delete_user(pie_comm *comm, int32_t user, int32_t *rows_out, size_t cap, size_t *n_deleted, int32_t *owner_rank_out);
 int pie_comm_table_size(pie_comm *comm, int64_t *rows_global_out, int32_t *users_global_out);
+/* The token column behind the communicator (pie_shard_token_* on every local shard; the rules above hold: PIE_E_STATE while
+ * pipelined steps are uncollected, every local shard checks a call before any is staged or changed).
+ * pie_comm_token_lookup queues the lookup on every local shard, then waits for each, and merges on the host: per key the answer
+ * with the LARGEST global row (-1 / live 0 if no local shard holds the key) with its live / user / start / end (global ids);
+ * owner_rank_out[i] (may be NULL) = the rank that answered, -1 if none.  This is the unsharded table's answer, a key held by
+ * two shards included.  In a process-per-GPU communicator a process reports what its own shards hold, as pie_comm_delete_user.
+ * pie_comm_token_set_end: that lookup, then ONE pie_comm_set_end by global row of the elements whose winner is live under `now`
+ * (PIE_END_NONE: every winner that is not a tombstone) — the unsharded pie_token_set_end's result, repeats included.
+ * rows_out[i] (may be NULL) = the global row written or -1. */
+int pie_comm_token_set(pie_comm *comm, const uint64_t *tok /* [n][2] */, size_t n);
+int pie_comm_token_append(pie_comm *comm, const uint64_t *tok, size_t k);
+int pie_comm_token_lookup(pie_comm *comm, const uint64_t *tok, size_t k, int64_t now, int32_t *row_out, uint8_t *live_out,
+                          int32_t *user_out, int64_t *start_out, int64_t *end_out, int32_t *owner_rank_out);
+int pie_comm_token_set_end(pie_comm *comm, const uint64_t *tok, const int64_t *new_end, size_t k, int64_t now, int32_t *rows_out);
 
 /* ---- the pipelined exchange: ONE union message per step (layout: pie_scan_batch_begin_union), written by each shard's own
  * batch kernels; the exchange of step i runs on a side stream while the shards scan steps i+1, i+2.  Order of calls:

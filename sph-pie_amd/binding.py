@@ -197,6 +197,15 @@ _SIGS = [
     ("pie_token_layout", C.c_int, [_P, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), _P, C.c_size_t, _P]),
     ("pie_token_slots_for", C.c_size_t, [C.c_size_t]),
     ("pie_token_homes", C.c_int, [_P, C.c_size_t, C.c_uint32, _P]),
+    ("pie_shard_token_set", C.c_int, [_P, _P, C.c_size_t]),
+    ("pie_shard_token_append", C.c_int, [_P, _P, C.c_size_t]),
+    ("pie_shard_token_lookup", C.c_int, [_P, _P, C.c_size_t, C.c_int64, _P, _P, _P, _P, _P]),
+    ("pie_shard_token_set_end", C.c_int, [_P, _P, _P, C.c_size_t, C.c_int64, _P]),
+    ("pie_shard_token_layout", C.c_int, [_P, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), _P, C.c_size_t, _P]),
+    ("pie_comm_token_set", C.c_int, [_P, _P, C.c_size_t]),
+    ("pie_comm_token_append", C.c_int, [_P, _P, C.c_size_t]),
+    ("pie_comm_token_lookup", C.c_int, [_P, _P, C.c_size_t, C.c_int64, _P, _P, _P, _P, _P, _P]),
+    ("pie_comm_token_set_end", C.c_int, [_P, _P, _P, C.c_size_t, C.c_int64, _P]),
 ]
 ABI_SYMBOLS = [s[0] for s in _SIGS]
 
@@ -876,6 +885,45 @@ class PieScan:
             raise ValueError("rows and values differ in length")
         self._check(self._lib.pie_shard_set_end(self._ctx, _ptr(rows_global), _ptr(new_end), rows_global.shape[0]))
 
+    # ---- the token column of a sharded context, by GLOBAL row (pie_shard_token_*)
+    def shard_token_set(self, keys):
+        """Keys for the global rows [0, len(keys)); the shard keeps those of the rows it holds.  Replaces any earlier column."""
+        keys = _keys(keys)
+        self._check(self._lib.pie_shard_token_set(self._ctx, _ptr(keys), keys.shape[0]))
+
+    def shard_token_append(self, keys):
+        """Keys for the global rows behind covered_g; queued, not waited for (unless the slot table must grow)."""
+        keys = _keys(keys)
+        self._check(self._lib.pie_shard_token_append(self._ctx, _ptr(keys), keys.shape[0]))
+
+    def shard_token_lookup(self, keys, now):
+        """getSession on this shard -> dict of arrays: row and user as GLOBAL ids (-1: this shard does not hold the key), live,
+        start, end."""
+        keys = _keys(keys)
+        k = keys.shape[0]
+        out = {"row": np.empty(k, np.int32), "live": np.empty(k, np.uint8), "user": np.empty(k, np.int32),
+               "start": np.empty(k, np.int64), "end": np.empty(k, np.int64)}
+        self._check(self._lib.pie_shard_token_lookup(self._ctx, _ptr(keys), k, int(now), _ptr(out["row"]), _ptr(out["live"]),
+                                                     _ptr(out["user"]), _ptr(out["start"]), _ptr(out["end"])))
+        return out
+
+    def shard_token_set_end(self, keys, new_end, now):
+        """touchSession / deleteSession by token on this shard -> the GLOBAL row written per element (-1: none)."""
+        keys, new_end = _keys(keys), _col(new_end, np.int64)
+        if new_end.shape[0] != keys.shape[0]:
+            raise ValueError("one new_end per key")
+        rows = np.empty(keys.shape[0], np.int32)
+        self._check(self._lib.pie_shard_token_set_end(self._ctx, _ptr(keys), _ptr(new_end), keys.shape[0], int(now), _ptr(rows)))
+        return rows
+
+    def shard_token_layout(self):
+        """-> (covered_global, covered_local, slots, slot_row[slots] of LOCAL rows, keys[covered_local, 2]), for tests and tools."""
+        cg, cl, slots = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+        self._check(self._lib.pie_shard_token_layout(self._ctx, C.byref(cg), C.byref(cl), C.byref(slots), None, 0, None))
+        slot_row, keys = np.empty(slots.value, np.int32), np.empty((cl.value, 2), np.uint64)
+        self._check(self._lib.pie_shard_token_layout(self._ctx, C.byref(cg), C.byref(cl), C.byref(slots), _ptr(slot_row), slots.value, _ptr(keys)))
+        return cg.value, cl.value, slots.value, slot_row, keys
+
     def shard_delete_user(self, user_global):
         """-> ascending GLOBAL rows that were tombstoned (empty on a shard the user does not hash to)."""
         k = C.c_size_t(0)
@@ -1185,6 +1233,37 @@ class PieComm:
         rows, k, owner = np.empty(cap, np.int32), C.c_size_t(0), C.c_int32(-1)
         self._check(self._lib.pie_comm_delete_user(self._c, int(user), _ptr(rows), cap, C.byref(k), C.byref(owner)))
         return rows[: k.value].copy(), int(owner.value)
+
+    # ---- the token column behind the communicator (pie_comm_token_*): keys are uint64 arrays of shape (k, 2), GLOBAL ids out
+    def token_set(self, keys):
+        """Keys for the global rows [0, len(keys)) on every local shard."""
+        keys = _keys(keys)
+        self._check(self._lib.pie_comm_token_set(self._c, _ptr(keys), keys.shape[0]))
+
+    def token_append(self, keys):
+        """Keys for the global rows behind the covered ones, on every local shard."""
+        keys = _keys(keys)
+        self._check(self._lib.pie_comm_token_append(self._c, _ptr(keys), keys.shape[0]))
+
+    def token_lookup(self, keys, now):
+        """getSession across the local shards -> dict of arrays: row (largest global row under the key, -1: none), live, user,
+        start, end, owner (the rank that answered, -1: none)."""
+        keys = _keys(keys)
+        k = keys.shape[0]
+        out = {"row": np.empty(k, np.int32), "live": np.empty(k, np.uint8), "user": np.empty(k, np.int32),
+               "start": np.empty(k, np.int64), "end": np.empty(k, np.int64), "owner": np.empty(k, np.int32)}
+        self._check(self._lib.pie_comm_token_lookup(self._c, _ptr(keys), k, int(now), _ptr(out["row"]), _ptr(out["live"]), _ptr(out["user"]),
+                                                    _ptr(out["start"]), _ptr(out["end"]), _ptr(out["owner"])))
+        return out
+
+    def token_set_end(self, keys, new_end, now):
+        """touchSession / deleteSession by token -> the global row written per element (-1: unknown, expired or tombstoned)."""
+        keys, new_end = _keys(keys), _col(new_end, np.int64)
+        if new_end.shape[0] != keys.shape[0]:
+            raise ValueError("one new_end per key")
+        rows = np.empty(keys.shape[0], np.int32)
+        self._check(self._lib.pie_comm_token_set_end(self._c, _ptr(keys), _ptr(new_end), keys.shape[0], int(now), _ptr(rows)))
+        return rows
 
     def queue_read(self, at_rank, sources=False):
         """The merged queue of the last queue call as local rank at_rank holds it."""

@@ -26,6 +26,11 @@
 namespace pie_internal {
 int shard_check_append(pie_ctx* c, const int32_t* user_global, size_t k, int32_t n_users_global);
 int shard_check_set_end(pie_ctx* c, const int32_t* rows_global, const int64_t* new_end, size_t k);
+// ... what pie_shard_token_set / pie_shard_token_append would refuse, and the two phases of pie_shard_token_lookup
+int shard_token_check(pie_ctx* c, const uint64_t* tok, size_t k, bool set);
+int shard_token_lookup_queue(pie_ctx* c, const uint64_t* tok, size_t k, int64_t now);
+int shard_token_lookup_wait(pie_ctx* c, size_t k, int32_t* row_global_out, uint8_t* live_out, int32_t* user_global_out, int64_t* start_out,
+                            int64_t* end_out);
 } // namespace pie_internal
 
 namespace {
@@ -971,6 +976,114 @@ int pie_comm_delete_user(pie_comm* c, int32_t user, int32_t* rows_out, size_t ca
     if (i < 0) return PIE_OK; // the owning rank lives in another process, which makes the same call
     PIE_CCTX(c, i, pie_shard_delete_user(c->ctx[i], user, rows_out, cap, n_deleted));
     return PIE_OK;
+}
+
+// ---- the token column behind the communicator: pie_shard_token_* on every local shard, the lookup merged on the host
+
+int pie_comm_token_set(pie_comm* c, const uint64_t* tok, size_t n)
+{
+    if (!c) return PIE_E_INVAL;
+    int rc = mutate_ready(c, nullptr, nullptr);
+    if (rc) return rc;
+    for (int i = 0; i < c->n_local; ++i) PIE_CCTX(c, i, pie_internal::shard_token_check(c->ctx[i], tok, n, true));
+    for (int i = 0; i < c->n_local; ++i) PIE_CCTX(c, i, pie_shard_token_set(c->ctx[i], tok, n));
+    return PIE_OK;
+}
+
+int pie_comm_token_append(pie_comm* c, const uint64_t* tok, size_t k)
+{
+    if (!c) return PIE_E_INVAL;
+    int rc = mutate_ready(c, nullptr, nullptr);
+    if (rc) return rc;
+    for (int i = 0; i < c->n_local; ++i) PIE_CCTX(c, i, pie_internal::shard_token_check(c->ctx[i], tok, k, false));
+    for (int i = 0; i < c->n_local; ++i) PIE_CCTX(c, i, pie_shard_token_append(c->ctx[i], tok, k));
+    return PIE_OK;
+}
+
+int pie_comm_token_lookup(pie_comm* c, const uint64_t* tok, size_t k, int64_t now, int32_t* row_out, uint8_t* live_out, int32_t* user_out,
+                          int64_t* start_out, int64_t* end_out, int32_t* owner_rank_out)
+{
+    if (!c) return PIE_E_INVAL;
+    int rc = mutate_ready(c, nullptr, nullptr);
+    if (rc) return rc;
+    if (k > 0 && !tok) return cfail(c, PIE_E_INVAL, "tok is NULL");
+    // every shard's launch and copies are in its stream before the first wait: the shards' lookups overlap
+    int queued = 0;
+    for (; queued < c->n_local; ++queued)
+        if ((rc = pie_internal::shard_token_lookup_queue(c->ctx[queued], tok, k, now)) != PIE_OK) break;
+    if (rc) { // what was queued is waited for all the same: nothing is left writing a staging block
+        const int bad = queued;
+        for (int i = 0; i < queued; ++i) (void)pie_internal::shard_token_lookup_wait(c->ctx[i], k, nullptr, nullptr, nullptr, nullptr, nullptr);
+        PIE_CCTX(c, bad, rc);
+    }
+    if (k == 0) return PIE_OK;
+    std::vector<int32_t> best, row, user;
+    std::vector<uint8_t> live;
+    std::vector<int64_t> start, end;
+    try {
+        best.assign(k, -1);
+        row.resize(k);
+        user.resize(k);
+        live.resize(k);
+        start.resize(k);
+        end.resize(k);
+    } catch (...) {
+        for (int i = 0; i < c->n_local; ++i) (void)pie_internal::shard_token_lookup_wait(c->ctx[i], k, nullptr, nullptr, nullptr, nullptr, nullptr);
+        return cfail(c, PIE_E_NOMEM, "no memory for %zu answers", k);
+    }
+    if (live_out) memset(live_out, 0, k);
+    if (owner_rank_out) for (size_t j = 0; j < k; ++j) owner_rank_out[j] = -1;
+    int first_rc = PIE_OK, first_bad = -1;
+    for (int i = 0; i < c->n_local; ++i) {
+        rc = pie_internal::shard_token_lookup_wait(c->ctx[i], k, row.data(), live.data(), user.data(), start.data(), end.data());
+        if (rc) { // keep waiting for the others
+            if (first_rc == PIE_OK) { first_rc = rc; first_bad = i; }
+            continue;
+        }
+        for (size_t j = 0; j < k; ++j) {
+            if (row[j] <= best[j]) continue;
+            best[j] = row[j];
+            if (live_out) live_out[j] = live[j];
+            if (user_out) user_out[j] = user[j];
+            if (start_out) start_out[j] = start[j];
+            if (end_out) end_out[j] = end[j];
+            if (owner_rank_out) owner_rank_out[j] = c->rank_of[i];
+        }
+    }
+    if (first_rc) PIE_CCTX(c, first_bad, first_rc);
+    if (row_out) memcpy(row_out, best.data(), k * 4);
+    return PIE_OK;
+}
+
+int pie_comm_token_set_end(pie_comm* c, const uint64_t* tok, const int64_t* new_end, size_t k, int64_t now, int32_t* rows_out)
+{
+    if (!c) return PIE_E_INVAL;
+    int rc = mutate_ready(c, nullptr, nullptr);
+    if (rc || k == 0) return rc;
+    if (!tok || !new_end) return cfail(c, PIE_E_INVAL, "NULL pointer");
+    std::vector<int32_t> row, rows;
+    std::vector<uint8_t> live;
+    std::vector<int64_t> ends;
+    try {
+        row.resize(k);
+        live.resize(k);
+        rows.reserve(k);
+        ends.reserve(k);
+    } catch (...) {
+        return cfail(c, PIE_E_NOMEM, "no memory for %zu touches", k);
+    }
+    rc = pie_comm_token_lookup(c, tok, k, now, row.data(), live.data(), nullptr, nullptr, nullptr, nullptr);
+    if (rc) return rc;
+    for (size_t i = 0; i < k; ++i) {
+        const bool hit = live[i] != 0 && row[i] >= 0;
+        if (rows_out) rows_out[i] = hit ? row[i] : -1;
+        if (hit) {
+            rows.push_back(row[i]);
+            ends.push_back(new_end[i]);
+        }
+    }
+    if (rows.empty()) return PIE_OK;
+    return pie_comm_set_end(c, rows.data(), ends.data(), rows.size());
 }
 
 } // extern "C"

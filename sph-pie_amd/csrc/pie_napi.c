@@ -98,7 +98,11 @@
     X(int, pie_token_set, (pie_ctx *, const uint64_t *, size_t))                                                    \
     X(int, pie_token_append, (pie_ctx *, const uint64_t *, size_t))                                                 \
     X(int, pie_token_lookup, (pie_ctx *, const uint64_t *, size_t, int64_t, int32_t *, uint8_t *, int32_t *, int64_t *, int64_t *)) \
-    X(int, pie_token_set_end, (pie_ctx *, const uint64_t *, const int64_t *, size_t, int64_t, int32_t *))
+    X(int, pie_token_set_end, (pie_ctx *, const uint64_t *, const int64_t *, size_t, int64_t, int32_t *))                \
+    X(int, pie_comm_token_set, (pie_comm *, const uint64_t *, size_t))                                               \
+    X(int, pie_comm_token_append, (pie_comm *, const uint64_t *, size_t))                                            \
+    X(int, pie_comm_token_lookup, (pie_comm *, const uint64_t *, size_t, int64_t, int32_t *, uint8_t *, int32_t *, int64_t *, int64_t *, int32_t *)) \
+    X(int, pie_comm_token_set_end, (pie_comm *, const uint64_t *, const int64_t *, size_t, int64_t, int32_t *))
 
 #define X(ret, name, args) static ret(*p_##name) args;
 PIE_SYMBOLS(X)
@@ -2102,6 +2106,76 @@ static napi_value fn_token_set_end(napi_env env, napi_callback_info info)
     return out;
 }
 
+/* ---- the token column behind the communicator (pie_comm_token_*): keys as tokenLookup takes them, GLOBAL ids out ----------- */
+/* commTokenSet(comm, keys) / commTokenAppend(comm, keys) -> k */
+static napi_value comm_token_set_or_append(napi_env env, napi_callback_info info, int append)
+{
+    ARGS(2)
+    comm_box *cbx = get_comm_box(env, argv[0]); /* refuses while scanAsync runs on one of the shard contexts */
+    if (!cbx) return NULL;
+    size_t k = 0;
+    uint64_t *keys = token_keys(env, argv[1], &k);
+    if (!keys) return NULL;
+    int rc = append ? p_pie_comm_token_append(cbx->comm, keys, k) : p_pie_comm_token_set(cbx->comm, keys, k);
+    if (rc) return throw_comm(env, cbx->comm, rc);
+    return js_int(env, (int64_t)k);
+}
+static napi_value fn_comm_token_set(napi_env env, napi_callback_info info) { return comm_token_set_or_append(env, info, 0); }
+static napi_value fn_comm_token_append(napi_env env, napi_callback_info info) { return comm_token_set_or_append(env, info, 1); }
+
+/* commTokenLookup(comm, keys, now) -> tokenLookup's object with global row and user, plus owner Int32Array (the rank that
+ * answered, -1: no shard holds the key) */
+static napi_value fn_comm_token_lookup(napi_env env, napi_callback_info info)
+{
+    ARGS(3)
+    comm_box *cbx = get_comm_box(env, argv[0]);
+    if (!cbx) return NULL;
+    size_t k = 0;
+    int64_t now = 0;
+    uint64_t *keys = token_keys(env, argv[1], &k);
+    if (!keys) return NULL;
+    if (!get_i64(env, argv[2], &now)) {
+        napi_throw_type_error(env, NULL, "commTokenLookup(comm, BigUint64Array keys, now)");
+        return NULL;
+    }
+    napi_value out;
+    CHECK(env, napi_create_object(env, &out));
+    int32_t *row = token_out(env, out, "row", napi_int32_array, 4, k);
+    uint8_t *live = token_out(env, out, "live", napi_uint8_array, 1, k);
+    int32_t *user = token_out(env, out, "user", napi_int32_array, 4, k);
+    int64_t *start = token_out(env, out, "start", napi_bigint64_array, 8, k);
+    int64_t *end = token_out(env, out, "end", napi_bigint64_array, 8, k);
+    int32_t *owner = token_out(env, out, "owner", napi_int32_array, 4, k);
+    if (!row || !live || !user || !start || !end || !owner) return NULL;
+    int rc = p_pie_comm_token_lookup(cbx->comm, keys, k, now, row, live, user, start, end, owner);
+    if (rc) return throw_comm(env, cbx->comm, rc);
+    return out;
+}
+
+/* commTokenSetEnd(comm, keys, newEnd BigInt64Array, now) -> Int32Array global rows written (-1: not found, or not live at `now`) */
+static napi_value fn_comm_token_set_end(napi_env env, napi_callback_info info)
+{
+    ARGS(4)
+    comm_box *cbx = get_comm_box(env, argv[0]);
+    if (!cbx) return NULL;
+    size_t k = 0, k2 = 0;
+    int64_t now = 0;
+    uint64_t *keys = token_keys(env, argv[1], &k);
+    if (!keys) return NULL;
+    int64_t *ne = typed(env, argv[2], napi_bigint64_array, &k2);
+    if (!ne || k2 != k || !get_i64(env, argv[3], &now)) {
+        napi_throw_type_error(env, NULL, "commTokenSetEnd(comm, BigUint64Array keys, BigInt64Array newEnd, now)");
+        return NULL;
+    }
+    napi_value buf, out;
+    void *data = NULL;
+    CHECK(env, napi_create_arraybuffer(env, k * 4, &data, &buf));
+    int rc = p_pie_comm_token_set_end(cbx->comm, keys, ne, k, now, (int32_t *)data);
+    if (rc) return throw_comm(env, cbx->comm, rc);
+    CHECK(env, napi_create_typedarray(env, napi_int32_array, k, buf, 0, &out));
+    return out;
+}
+
 static napi_value init(napi_env env, napi_value exports)
 {
     static const struct {
@@ -2125,6 +2199,8 @@ static napi_value init(napi_env env, napi_value exports)
         {"commAppendRows", fn_comm_append_rows}, {"commSetEnd", fn_comm_set_end}, {"commDeleteUser", fn_comm_delete_user}, {"commTableSize", fn_comm_table_size},
         {"shardMaps", fn_shard_maps},
         {"tokenSet", fn_token_set}, {"tokenAppend", fn_token_append}, {"tokenLookup", fn_token_lookup}, {"tokenSetEnd", fn_token_set_end},
+        {"commTokenSet", fn_comm_token_set}, {"commTokenAppend", fn_comm_token_append}, {"commTokenLookup", fn_comm_token_lookup},
+        {"commTokenSetEnd", fn_comm_token_set_end},
     };
     for (size_t i = 0; i < sizeof table / sizeof table[0]; ++i) {
         napi_value fn;

@@ -326,6 +326,11 @@ struct pie_ctx {
     struct TokenIndex {
         TokKey* tok = nullptr;      // [cap] keys of the rows [0, covered)
         long long cap = 0, covered = 0;
+        // A sharded context's column (pie_shard_token_*): keys were given for the GLOBAL rows [0, covered_g); the shard holds those of
+        // its local rows below that, a prefix [0, covered_l) only the device's row map knows (shard_token_covered reads it back, in
+        // calls that wait anyway).  `covered` stays 0 then.
+        bool sharded = false;
+        long long covered_g = 0;
         int* slot_row = nullptr;    // [1 << log2_slots]
         unsigned log2_slots = 0;
         unsigned int* status = nullptr; // [kTokStatusWords], device
@@ -701,7 +706,8 @@ void token_drop(pie_ctx* c)
     (void)hipStreamSynchronize(c->stream);
     dfree(t.tok);
     dfree(t.slot_row);
-    t.cap = t.covered = 0;
+    t.cap = t.covered = t.covered_g = 0;
+    t.sharded = false;
     t.log2_slots = 0;
 }
 
@@ -5188,7 +5194,7 @@ int pie_set_scan_form(pie_ctx* c, int form)
     return PIE_OK;
 }
 
-static void token_info(pie_ctx* c, pie_table_info* out);
+static int token_info(pie_ctx* c, pie_table_info* out);
 
 int pie_table_info_get(pie_ctx* c, pie_table_info* out)
 {
@@ -5258,7 +5264,8 @@ int pie_table_info_get(pie_ctx* c, pie_table_info* out)
     out->compactions = c->compactions;
     out->compact_count_ms = c->cmp_count_ms;
     out->compact_write_ms = c->cmp_write_ms;
-    token_info(c, out);
+    const int token_rc = token_info(c, out); // a sharded column reads covered_l back: that can fail
+    if (token_rc) return token_rc;
     full.struct_size = caller_size;
     memcpy(caller, &full, caller_size);
     return PIE_OK;
@@ -6249,15 +6256,16 @@ static int token_insert(pie_ctx* c, long long row0, long long k)
     return PIE_OK;
 }
 
-// every slot empty, then the rows [0, covered) inserted; queued, timed by two events (pie_table_info.token_build_ms)
-static int token_rebuild(pie_ctx* c)
+// every slot empty, then the rows [0, rows) inserted (the covered rows: `covered`, or a shard's covered_l); queued, timed by two
+// events (pie_table_info.token_build_ms)
+static int token_rebuild(pie_ctx* c, long long rows)
 {
     pie_ctx::TokenIndex& t = c->tokx;
     for (hipEvent_t& e : t.ev)
         if (!e) PIE_HIP(c, hipEventCreate(&e));
     PIE_HIP(c, hipEventRecord(t.ev[0], c->stream));
     PIE_HIP(c, hipMemsetAsync(t.slot_row, 0xFF, (size_t)4 << t.log2_slots, c->stream));
-    int rc = token_insert(c, 0, t.covered);
+    int rc = token_insert(c, 0, rows);
     if (rc) return rc;
     PIE_HIP(c, hipEventRecord(t.ev[1], c->stream));
     t.timed = true;
@@ -6265,10 +6273,33 @@ static int token_rebuild(pie_ctx* c)
     return PIE_OK;
 }
 
-static void token_info(pie_ctx* c, pie_table_info* out)
+// A sharded column's covered_l = lower_bound(rows_map, mapped rows, covered_g): one thread on the device, read back and waited for.
+static int shard_token_covered(pie_ctx* c, long long* covered_l)
 {
     pie_ctx::TokenIndex& t = c->tokx;
-    out->token_rows = t.tok ? (uint64_t)t.covered : 0u;
+    *covered_l = 0;
+    if (c->shard_rows_n <= 0 || t.covered_g <= 0 || !c->d_shard_rows) return PIE_OK;
+    hipStream_t s = c->stream;
+    long long got = -1;
+    hipLaunchKernelGGL(k_compact_lower_bound, dim3(1), dim3(1), 0, s, (const int*)c->d_shard_rows, c->shard_rows_n, t.covered_g, c->d_range);
+    PIE_HIP(c, hipGetLastError());
+    PIE_HIP(c, hipMemcpyAsync(&got, c->d_range, 8, hipMemcpyDeviceToHost, s));
+    PIE_HIP(c, hipStreamSynchronize(s));
+    if (got < 0 || got > c->shard_rows_n || got > t.cap) return fail(c, PIE_E_HIP, "token column: %lld covered rows of %lld", got, c->shard_rows_n);
+    *covered_l = got;
+    return PIE_OK;
+}
+
+static int token_info(pie_ctx* c, pie_table_info* out)
+{
+    pie_ctx::TokenIndex& t = c->tokx;
+    long long covered = t.covered;
+    if (t.tok && t.sharded) {
+        PIE_HIP(c, hipSetDevice(c->device));
+        int rc = shard_token_covered(c, &covered);
+        if (rc) return rc;
+    }
+    out->token_rows = t.tok ? (uint64_t)covered : 0u;
     out->token_bytes = (uint64_t)t.cap * sizeof(TokKey) + (t.slot_row ? (uint64_t)4 << t.log2_slots : 0u) +
                        (t.status ? kTokStatusWords * sizeof(unsigned int) : 0u) + (uint64_t)t.stage_bytes;
     out->token_builds = t.builds;
@@ -6279,6 +6310,7 @@ static void token_info(pie_ctx* c, pie_table_info* out)
         t.timed = false;
     }
     out->token_build_ms = t.build_ms;
+    return PIE_OK;
 }
 
 int pie_token_set(pie_ctx* c, const uint64_t* tok, size_t n)
@@ -6309,7 +6341,7 @@ int pie_token_set(pie_ctx* c, const uint64_t* tok, size_t n)
     t.log2_slots = log2_slots;
     t.covered = (long long)n;
     if (n > 0) PIE_HIP(c, hipMemcpyAsync(t.tok, tok, n * sizeof(TokKey), hipMemcpyHostToDevice, c->stream));
-    rc = token_rebuild(c);
+    rc = token_rebuild(c, t.covered);
     if (rc) return rc;
     return token_status_wait(c, "pie_token_set");
 }
@@ -6319,6 +6351,7 @@ int pie_token_append(pie_ctx* c, const uint64_t* tok, size_t k)
     if (!c) return PIE_E_INVAL;
     int rc = token_ready(c, "pie_token_append", true);
     if (rc) return rc;
+    if (c->tokx.sharded) return fail(c, PIE_E_STATE, "pie_token_append: the column was given by global row (pie_shard_token_append)");
     if (k > 0 && !tok) return fail(c, PIE_E_INVAL, "tok is NULL");
     pie_ctx::TokenIndex& t = c->tokx;
     if (k > (size_t)(c->n - t.covered)) return fail(c, PIE_E_INVAL, "%zu keys behind %lld covered rows of a table of %lld", k, t.covered, c->n);
@@ -6373,29 +6406,41 @@ int pie_token_append(pie_ctx* c, const uint64_t* tok, size_t k)
     dfree(t.slot_row);
     t.slot_row = ns;
     t.log2_slots = log2_slots;
-    return token_rebuild(c);
+    return token_rebuild(c, t.covered);
 }
 
-// offsets of a lookup's staging block for k keys: [keys 16 k | end 8 k | start 8 k | row 4 k | user 4 k | live k | pad | status]
+// offsets of a lookup's staging block for k keys: [keys 16 k | end 8 k | start 8 k | row 4 k | user 4 k | live k | pad | status];
+// the sharded lookup adds the GLOBAL rows (4 k) between live and the status words
 struct TokStage {
-    size_t end, start, row, user, live, status, bytes;
+    size_t end, start, row, user, live, grow, status, bytes;
 };
-static TokStage token_stage_of(size_t k)
+static TokStage token_stage_of(size_t k, bool global = false)
 {
     TokStage o;
     o.end = k * 16; o.start = k * 24; o.row = k * 32; o.user = k * 36; o.live = k * 40;
-    o.status = (k * 41 + 15) / 16 * 16;
+    o.grow = (k * 41 + 3) / 4 * 4;
+    o.status = ((global ? o.grow + k * 4 : k * 41) + 15) / 16 * 16;
     o.bytes = o.status + kTokStatusWords * sizeof(unsigned int);
     return o;
 }
 
-// One launch for k keys; the results and the status words are in tokx.h_stage (token_stage_of) when it returns.
-static int token_lookup_run(pie_ctx* c, const uint64_t* tok, size_t k, long long now, bool want_user, bool want_start, const char* what)
+// rows the column can hold keys for: what keeps a probe's 16-byte load inside it
+static long long token_bound(const pie_ctx* c)
+{
+    const pie_ctx::TokenIndex& t = c->tokx;
+    if (!t.sharded) return t.covered;
+    return c->n < t.cap ? c->n : t.cap;
+}
+
+// The queue phase of a lookup: the keys go up, one launch for k keys, the results and the status words come back into
+// tokx.h_stage (token_stage_of) — all queued on the stream, nothing waited for.  global: the sharded kernel, which also answers
+// the global row and translates the user.
+static int token_lookup_queue(pie_ctx* c, const uint64_t* tok, size_t k, long long now, bool want_user, bool want_start, bool global)
 {
     pie_ctx::TokenIndex& t = c->tokx;
     PIE_HIP(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    const TokStage o = token_stage_of(k);
+    const TokStage o = token_stage_of(k, global);
     if (o.bytes > t.stage_bytes) {
         size_t want = t.stage_bytes ? t.stage_bytes : (size_t)64 << 10;
         while (want < o.bytes) want *= 2;
@@ -6411,16 +6456,39 @@ static int token_lookup_run(pie_ctx* c, const uint64_t* tok, size_t k, long long
     char* d = t.d_stage;
     memcpy(t.h_stage, tok, k * sizeof(TokKey));
     PIE_HIP(c, hipMemcpyAsync(d, t.h_stage, k * sizeof(TokKey), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_token_lookup, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const TokKey*>(d), (long long)k,
-                       (const int*)t.slot_row, t.log2_slots, (const TokKey*)t.tok, t.covered, (const long long*)c->d_end, (const long long*)c->d_start,
-                       (const int*)c->d_user, now, reinterpret_cast<int*>(d + o.row), reinterpret_cast<unsigned char*>(d + o.live),
-                       want_user ? reinterpret_cast<int*>(d + o.user) : nullptr, want_start ? reinterpret_cast<long long*>(d + o.start) : nullptr,
-                       reinterpret_cast<long long*>(d + o.end), t.status);
+    const dim3 grid((unsigned)((k + 255) / 256));
+    int* o_user = want_user ? reinterpret_cast<int*>(d + o.user) : nullptr;
+    long long* o_start = want_start ? reinterpret_cast<long long*>(d + o.start) : nullptr;
+    if (global)
+        hipLaunchKernelGGL(k_shard_token_lookup, grid, dim3(256), 0, s, reinterpret_cast<const TokKey*>(d), (long long)k, (const int*)t.slot_row,
+                           t.log2_slots, (const TokKey*)t.tok, token_bound(c), (const long long*)c->d_end, (const long long*)c->d_start,
+                           (const int*)c->d_user, (const int*)c->d_shard_rows, c->shard_rows_n, (const int*)c->d_shard_users, c->shard_users_n, now,
+                           reinterpret_cast<int*>(d + o.row), reinterpret_cast<int*>(d + o.grow), reinterpret_cast<unsigned char*>(d + o.live),
+                           o_user, o_start, reinterpret_cast<long long*>(d + o.end), t.status);
+    else
+        hipLaunchKernelGGL(k_token_lookup, grid, dim3(256), 0, s, reinterpret_cast<const TokKey*>(d), (long long)k, (const int*)t.slot_row,
+                           t.log2_slots, (const TokKey*)t.tok, token_bound(c), (const long long*)c->d_end, (const long long*)c->d_start,
+                           (const int*)c->d_user, now, reinterpret_cast<int*>(d + o.row), reinterpret_cast<unsigned char*>(d + o.live), o_user,
+                           o_start, reinterpret_cast<long long*>(d + o.end), t.status);
     PIE_HIP(c, hipGetLastError());
     PIE_HIP(c, hipMemcpyAsync(t.h_stage + o.end, d + o.end, o.status - o.end, hipMemcpyDeviceToHost, s));
     PIE_HIP(c, hipMemcpyAsync(t.h_stage + o.status, t.status, kTokStatusWords * sizeof(unsigned int), hipMemcpyDeviceToHost, s));
-    PIE_HIP(c, hipStreamSynchronize(s)); // the one wait of a lookup
-    return token_status_check(c, reinterpret_cast<const unsigned int*>(t.h_stage + o.status), what);
+    return PIE_OK;
+}
+
+// The wait phase: the one wait of a lookup; the results and the status words are in tokx.h_stage when it returns.
+static int token_lookup_wait(pie_ctx* c, size_t k, bool global, const char* what)
+{
+    PIE_HIP(c, hipSetDevice(c->device));
+    PIE_HIP(c, hipStreamSynchronize(c->stream));
+    return token_status_check(c, reinterpret_cast<const unsigned int*>(c->tokx.h_stage + token_stage_of(k, global).status), what);
+}
+
+static int token_lookup_run(pie_ctx* c, const uint64_t* tok, size_t k, long long now, bool want_user, bool want_start, const char* what)
+{
+    int rc = token_lookup_queue(c, tok, k, now, want_user, want_start, false);
+    if (rc) return rc;
+    return token_lookup_wait(c, k, false, what);
 }
 
 int pie_token_lookup(pie_ctx* c, const uint64_t* tok, size_t k, int64_t now, int32_t* row_out, uint8_t* live_out, int32_t* user_out,
@@ -6478,20 +6546,33 @@ int pie_token_set_end(pie_ctx* c, const uint64_t* tok, const int64_t* new_end, s
     return set_end_apply(c, rows.data(), ends.data(), rows.size(), false);
 }
 
+// pie_token_layout and pie_shard_token_layout behind their checks; the covered rows are LOCAL ones (covered_l on a sharded column)
+static int token_layout_read(pie_ctx* c, const char* what, size_t* covered_global_out, size_t* covered_out, size_t* slots_out,
+                             int32_t* slot_row_out, size_t cap, uint64_t* tok_out)
+{
+    pie_ctx::TokenIndex& t = c->tokx;
+    const size_t slots = (size_t)1 << t.log2_slots;
+    if (slots_out) *slots_out = slots;
+    if (covered_global_out) *covered_global_out = (size_t)t.covered_g;
+    if (slot_row_out && cap < slots) return fail(c, PIE_E_CAPACITY, "%s: %zu slots, room for %zu", what, slots, cap);
+    PIE_HIP(c, hipSetDevice(c->device));
+    long long covered = t.covered;
+    if (t.sharded) {
+        int rc = shard_token_covered(c, &covered);
+        if (rc) return rc;
+    }
+    if (covered_out) *covered_out = (size_t)covered;
+    if (slot_row_out) PIE_HIP(c, hipMemcpyAsync(slot_row_out, t.slot_row, slots * 4, hipMemcpyDeviceToHost, c->stream));
+    if (tok_out && covered) PIE_HIP(c, hipMemcpyAsync(tok_out, t.tok, (size_t)covered * sizeof(TokKey), hipMemcpyDeviceToHost, c->stream));
+    return token_status_wait(c, what);
+}
+
 int pie_token_layout(pie_ctx* c, size_t* covered_out, size_t* slots_out, int32_t* slot_row_out, size_t cap, uint64_t* tok_out)
 {
     if (!c) return PIE_E_INVAL;
     int rc = token_ready(c, "pie_token_layout", true);
     if (rc) return rc;
-    pie_ctx::TokenIndex& t = c->tokx;
-    const size_t slots = (size_t)1 << t.log2_slots;
-    if (covered_out) *covered_out = (size_t)t.covered;
-    if (slots_out) *slots_out = slots;
-    if (slot_row_out && cap < slots) return fail(c, PIE_E_CAPACITY, "pie_token_layout: %zu slots, room for %zu", slots, cap);
-    PIE_HIP(c, hipSetDevice(c->device));
-    if (slot_row_out) PIE_HIP(c, hipMemcpyAsync(slot_row_out, t.slot_row, slots * 4, hipMemcpyDeviceToHost, c->stream));
-    if (tok_out && t.covered) PIE_HIP(c, hipMemcpyAsync(tok_out, t.tok, (size_t)t.covered * sizeof(TokKey), hipMemcpyDeviceToHost, c->stream));
-    return token_status_wait(c, "pie_token_layout");
+    return token_layout_read(c, "pie_token_layout", nullptr, covered_out, slots_out, slot_row_out, cap, tok_out);
 }
 
 // pie_compact_rows dropped rows and the table stands in its new numbering (the maps of the compaction are resident): the keys of
@@ -6504,8 +6585,18 @@ static int token_after_compact(pie_ctx* c, long long n_old)
     if (!t.tok) return PIE_OK;
     hipStream_t s = c->stream;
     const long long kept = c->cmp_n_kept;
+    // a sharded column: the new row map holds the original global ids of the kept rows, so the kept covered rows are its entries
+    // below covered_g — a prefix again; their old rows lay inside the old column
+    const long long covered_old = t.sharded ? (n_old < t.cap ? n_old : t.cap) : t.covered;
     long long covered = t.covered >= n_old ? kept : 0;
-    if (t.covered < n_old && t.covered > 0 && kept > 0) { // the entries of old_of_new below the old `covered`
+    if (t.sharded) {
+        int rc = shard_token_covered(c, &covered);
+        if (rc == PIE_OK && covered > kept) rc = fail(c, PIE_E_HIP, "pie_compact_rows: token column: %lld covered rows of %lld kept", covered, kept);
+        if (rc) {
+            token_drop(c);
+            return rc;
+        }
+    } else if (t.covered < n_old && t.covered > 0 && kept > 0) { // the entries of old_of_new below the old `covered`
         hipLaunchKernelGGL(k_compact_lower_bound, dim3(1), dim3(1), 0, s, (const int*)c->d_cmp_old_of_new, kept, t.covered, c->d_range);
         hipError_t e = hipGetLastError();
         if (e == hipSuccess) e = hipMemcpyAsync(&covered, c->d_range, 8, hipMemcpyDeviceToHost, s);
@@ -6515,7 +6606,7 @@ static int token_after_compact(pie_ctx* c, long long n_old)
             return fail(c, PIE_E_HIP, "pie_compact_rows: token column: %s", hipGetErrorString(e));
         }
     }
-    const unsigned log2_slots = token_log2(pie_token_slots_for((size_t)covered));
+    const unsigned log2_slots = token_log2(pie_token_slots_for((size_t)(t.sharded ? kept : covered))); // a shard sizes by its rows
     const long long cap = c->cap_rows > t.cap ? c->cap_rows : t.cap;
     TokKey* nt = nullptr;
     int* ns = nullptr;
@@ -6527,7 +6618,7 @@ static int token_after_compact(pie_ctx* c, long long n_old)
     }
     if (covered > 0) {
         hipLaunchKernelGGL(k_token_gather, dim3(capped_grid(c, (size_t)covered)), dim3(256), 0, s, (const TokKey*)t.tok,
-                           (const int*)c->d_cmp_old_of_new, covered, t.covered, nt);
+                           (const int*)c->d_cmp_old_of_new, covered, covered_old, nt);
         hipError_t e = hipGetLastError();
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         if (e != hipSuccess) {
@@ -6540,15 +6631,233 @@ static int token_after_compact(pie_ctx* c, long long n_old)
     dfree(t.tok);
     t.tok = nt;
     t.cap = cap;
-    t.covered = covered;
+    t.covered = t.sharded ? 0 : covered;
     if (ns) {
         dfree(t.slot_row);
         t.slot_row = ns;
         t.log2_slots = log2_slots;
     }
-    int rc = token_rebuild(c);
+    int rc = token_rebuild(c, covered);
     if (rc) return rc;
     return token_status_wait(c, "pie_compact_rows");
+}
+
+// ---- the token column of a SHARDED context, by GLOBAL row (include/pie_scan.h, pie_shard_token_*).  Every shard is given the
+// same call and keeps what is its own; nothing is exchanged.  The host knows covered_g, the shard's row count and the slot
+// count; which local rows are covered only the device's row map knows.
+
+static int shard_token_ready(pie_ctx* c, const char* what, bool need_column)
+{
+    if (c->cap_rows == 0) return fail(c, PIE_E_STATE, "%s: no table loaded", what);
+    int rc = shard_ready(c, what);
+    if (rc) return rc;
+    if (need_column && !(c->tokx.tok && c->tokx.sharded))
+        return fail(c, PIE_E_STATE, "%s: the table has no token column (pie_shard_token_set gives it one)", what);
+    return PIE_OK;
+}
+
+} // extern "C"
+
+// What pie_shard_token_set / pie_shard_token_append would refuse, checked with nothing staged or changed (the communicator asks
+// every local shard first), and the two phases of a sharded lookup, which the communicator queues on every shard before it waits
+// for any.
+namespace pie_internal {
+int shard_token_check(pie_ctx* c, const uint64_t* tok, size_t k, bool set)
+{
+    if (!c) return PIE_E_INVAL;
+    const char* what = set ? "pie_shard_token_set" : "pie_shard_token_append";
+    int rc = shard_token_ready(c, what, !set);
+    if (rc) return rc;
+    if (k > 0 && !tok) return fail(c, PIE_E_INVAL, "tok is NULL");
+    const long long from = set ? 0 : c->tokx.covered_g;
+    if (k > (size_t)(c->shard_rows_global - from))
+        return fail(c, PIE_E_INVAL, "%s: %zu keys behind %lld covered rows of a table of %lld", what, k, from, c->shard_rows_global);
+    return PIE_OK;
+}
+
+int shard_token_lookup_queue(pie_ctx* c, const uint64_t* tok, size_t k, int64_t now)
+{
+    if (!c) return PIE_E_INVAL;
+    int rc = shard_token_ready(c, "pie_shard_token_lookup", true);
+    if (rc || k == 0) return rc;
+    if (!tok) return fail(c, PIE_E_INVAL, "tok is NULL");
+    if (k >= ((size_t)1 << 31)) return fail(c, PIE_E_INVAL, "%zu keys in one lookup", k);
+    return token_lookup_queue(c, tok, k, (long long)now, true, true, true);
+}
+
+// after shard_token_lookup_queue of the same k returned PIE_OK: waits, then copies what is asked for (any pointer may be NULL)
+int shard_token_lookup_wait(pie_ctx* c, size_t k, int32_t* row_global_out, uint8_t* live_out, int32_t* user_global_out, int64_t* start_out,
+                            int64_t* end_out)
+{
+    if (!c) return PIE_E_INVAL;
+    if (k == 0) return PIE_OK;
+    int rc = token_lookup_wait(c, k, true, "pie_shard_token_lookup");
+    if (rc) return rc;
+    const TokStage o = token_stage_of(k, true);
+    const char* h = c->tokx.h_stage;
+    if (row_global_out) memcpy(row_global_out, h + o.grow, k * 4);
+    if (live_out) memcpy(live_out, h + o.live, k);
+    if (user_global_out) memcpy(user_global_out, h + o.user, k * 4);
+    if (start_out) memcpy(start_out, h + o.start, k * 8);
+    if (end_out) memcpy(end_out, h + o.end, k * 8);
+    return PIE_OK;
+}
+} // namespace pie_internal
+
+extern "C" {
+
+// One chunk (k <= 2^20 keys, checked by the caller) for the global rows [covered_g, covered_g + k): everything that can fail and
+// everything that waits comes first — the staging area, a longer column (the table grew), a larger table of slots (the shard's
+// row count passed half of them: the index is rebuilt from the covered rows) — then one upload and one launch, queued.
+static int shard_token_chunk(pie_ctx* c, const uint64_t* tok, size_t k)
+{
+    pie_ctx::TokenIndex& t = c->tokx;
+    hipStream_t s = c->stream;
+    if (c->n == 0) { // nothing of any chunk can be this shard's
+        t.covered_g += (long long)k;
+        return PIE_OK;
+    }
+    Staged st{};
+    int rc = stage_mutation(c, k * sizeof(TokKey), true, &st);
+    if (rc) return rc;
+    if (c->cap_rows > t.cap) {
+        TokKey* nt = nullptr;
+        PIE_HIP(c, hipMalloc(&nt, (size_t)c->cap_rows * sizeof(TokKey)));
+        hipError_t e = t.cap ? hipMemcpyAsync(nt, t.tok, (size_t)t.cap * sizeof(TokKey), hipMemcpyDeviceToDevice, s) : hipSuccess;
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) {
+            (void)hipFree(nt);
+            return fail(c, PIE_E_HIP, "pie_shard_token_append: %s", hipGetErrorString(e));
+        }
+        dfree(t.tok);
+        t.tok = nt;
+        t.cap = c->cap_rows;
+    }
+    if ((unsigned long long)c->n > ((1ull << t.log2_slots) >> 1)) {
+        const unsigned log2_slots = token_log2(pie_token_slots_for((size_t)c->n));
+        long long covered_l = 0;
+        rc = shard_token_covered(c, &covered_l); // waits: inserts queued earlier still write the table that goes
+        if (rc) return rc;
+        int* ns = nullptr;
+        PIE_HIP(c, hipMalloc(&ns, (size_t)4 << log2_slots));
+        dfree(t.slot_row);
+        t.slot_row = ns;
+        t.log2_slots = log2_slots;
+        rc = token_rebuild(c, covered_l);
+        if (rc) return rc;
+    }
+    memcpy(st.h, tok, k * sizeof(TokKey));
+    PIE_HIP(c, hipMemcpyAsync(st.d, st.h, k * sizeof(TokKey), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_shard_token_place, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const TokKey*>(st.d), t.covered_g,
+                       (long long)k, (const int*)c->d_shard_rows, c->shard_rows_n, t.tok, t.cap, t.slot_row, t.log2_slots, t.status);
+    PIE_HIP(c, hipGetLastError());
+    rc = stage_queued(c, st);
+    if (rc) return rc;
+    t.covered_g += (long long)k;
+    return PIE_OK;
+}
+
+static int shard_token_chunks(pie_ctx* c, const uint64_t* tok, size_t k)
+{
+    const size_t most = (size_t)1 << 20;
+    for (size_t done = 0; done < k;) {
+        const size_t kk = k - done < most ? k - done : most;
+        int rc = shard_token_chunk(c, tok + 2 * done, kk);
+        if (rc) return rc;
+        done += kk;
+    }
+    return PIE_OK;
+}
+
+int pie_shard_token_set(pie_ctx* c, const uint64_t* tok, size_t n)
+{
+    if (!c) return PIE_E_INVAL;
+    int rc = pie_internal::shard_token_check(c, tok, n, true);
+    if (rc) return rc;
+    PIE_HIP(c, hipSetDevice(c->device));
+    rc = token_status_alloc(c);
+    if (rc) return rc;
+    pie_ctx::TokenIndex& t = c->tokx;
+    // the new column and table first: a failure leaves what was there.  Slots by the shard's row count, which the host knows.
+    const unsigned log2_slots = token_log2(pie_token_slots_for((size_t)c->n));
+    TokKey* nt = nullptr;
+    int* ns = nullptr;
+    if (hipMalloc(&nt, (size_t)c->cap_rows * sizeof(TokKey)) != hipSuccess || hipMalloc(&ns, (size_t)4 << log2_slots) != hipSuccess) {
+        (void)hipGetLastError();
+        dfree(nt);
+        return fail(c, PIE_E_NOMEM, "pie_shard_token_set: no device memory for %lld keys and %llu slots", c->cap_rows, 1ull << log2_slots);
+    }
+    token_drop(c);
+    t.tok = nt;
+    t.cap = c->cap_rows;
+    t.slot_row = ns;
+    t.log2_slots = log2_slots;
+    t.sharded = true;
+    rc = token_rebuild(c, 0); // the empty column: every slot empty
+    if (rc == PIE_OK) rc = shard_token_chunks(c, tok, n);
+    if (rc) return rc;
+    PIE_HIP(c, hipEventRecord(t.ev[1], c->stream)); // token_build_ms: the fill and every chunk
+    return token_status_wait(c, "pie_shard_token_set");
+}
+
+int pie_shard_token_append(pie_ctx* c, const uint64_t* tok, size_t k)
+{
+    if (!c) return PIE_E_INVAL;
+    int rc = pie_internal::shard_token_check(c, tok, k, false);
+    if (rc || k == 0) return rc;
+    PIE_HIP(c, hipSetDevice(c->device));
+    return shard_token_chunks(c, tok, k);
+}
+
+int pie_shard_token_lookup(pie_ctx* c, const uint64_t* tok, size_t k, int64_t now, int32_t* row_global_out, uint8_t* live_out,
+                           int32_t* user_global_out, int64_t* start_out, int64_t* end_out)
+{
+    int rc = pie_internal::shard_token_lookup_queue(c, tok, k, now);
+    if (rc) return rc;
+    return pie_internal::shard_token_lookup_wait(c, k, row_global_out, live_out, user_global_out, start_out, end_out);
+}
+
+// one lookup, then pie_set_end's own path on the LOCAL rows found live, as pie_token_set_end composes
+int pie_shard_token_set_end(pie_ctx* c, const uint64_t* tok, const int64_t* new_end, size_t k, int64_t now, int32_t* rows_global_out)
+{
+    if (!c) return PIE_E_INVAL;
+    int rc = shard_token_ready(c, "pie_shard_token_set_end", true);
+    if (rc || k == 0) return rc;
+    if (!tok || !new_end) return fail(c, PIE_E_INVAL, "NULL pointer");
+    rc = pie_internal::shard_token_lookup_queue(c, tok, k, now);
+    if (rc == PIE_OK) rc = token_lookup_wait(c, k, true, "pie_shard_token_set_end");
+    if (rc) return rc;
+    const TokStage o = token_stage_of(k, true);
+    const int32_t* row = reinterpret_cast<const int32_t*>(c->tokx.h_stage + o.row);
+    const int32_t* grow = reinterpret_cast<const int32_t*>(c->tokx.h_stage + o.grow);
+    const uint8_t* live = reinterpret_cast<const uint8_t*>(c->tokx.h_stage + o.live);
+    std::vector<int32_t> rows;
+    std::vector<int64_t> ends;
+    try {
+        rows.reserve(k);
+        ends.reserve(k);
+    } catch (...) {
+        return fail(c, PIE_E_NOMEM, "no memory for %zu touches", k);
+    }
+    for (size_t i = 0; i < k; ++i) {
+        const bool hit = live[i] != 0 && row[i] >= 0 && row[i] < c->n;
+        if (rows_global_out) rows_global_out[i] = hit ? grow[i] : -1;
+        if (hit) {
+            rows.push_back(row[i]);
+            ends.push_back(new_end[i]);
+        }
+    }
+    if (rows.empty()) return PIE_OK;
+    return set_end_apply(c, rows.data(), ends.data(), rows.size(), false);
+}
+
+int pie_shard_token_layout(pie_ctx* c, size_t* covered_global_out, size_t* covered_local_out, size_t* slots_out, int32_t* slot_row_out,
+                           size_t cap, uint64_t* tok_out)
+{
+    if (!c) return PIE_E_INVAL;
+    int rc = shard_token_ready(c, "pie_shard_token_layout", true);
+    if (rc) return rc;
+    return token_layout_read(c, "pie_shard_token_layout", covered_global_out, covered_local_out, slots_out, slot_row_out, cap, tok_out);
 }
 
 } // extern "C"

@@ -1,5 +1,6 @@
 // pie_token.h — the token column and its index: getSession (server/sessionStore.js:21-35) for a whole event-loop turn in one
-// launch.  gfx950, wave64.  Included by pie_scan.hip, which holds the host side (pie_token_*).
+// launch.  gfx950, wave64.  Included by pie_scan.hip behind pie_kernels.h; pie_scan.hip holds the host side (pie_token_*,
+// pie_shard_token_*).
 //
 // Token key: the first 16 bytes of the sha256 the reference uses as its Map key (sessionStore.js:8-10), as two little-endian
 // 64-bit words per row.  The device never hashes a token; the host does (binding.token_key, host/tokenKeys.js).
@@ -55,8 +56,30 @@ __global__ __launch_bounds__(256) void k_token_insert(const TokKey* __restrict__
     if (step == slots) status[0] = 1u;
 }
 
-// One lane per query key: walk from the home slot to the first empty slot; among the slots whose row carries the query's key
-// (both words) keep the largest row — of several sessions under one key the latest wins.  Outputs may be absent (NULL).
+// The probe every lookup runs: walk from the key's home slot to the first empty slot; among the slots whose row carries the key
+// (both words) keep the largest row.  `bound` keeps the 16-byte load inside the column whatever the slot holds (always true for an
+// index in step with its column).  At most `slots` steps; a lane that exhausts them sets status[1].  -> the row, or -1.
+__device__ __forceinline__ int token_probe(TokKey key, const int* __restrict__ slot_row, unsigned log2_slots, const TokKey* __restrict__ tok,
+                                           long long bound, unsigned int* __restrict__ status)
+{
+    const unsigned long long slots = 1ull << log2_slots, mask = slots - 1;
+    unsigned long long s = token_home(key.x, key.y, log2_slots);
+    int best = -1;
+    unsigned long long step = 0;
+    for (; step < slots; ++step) {
+        const int r = slot_row[s];
+        if (r < 0) break;
+        if ((long long)r < bound) {
+            const TokKey have = tok[r];
+            if (have.x == key.x && have.y == key.y && r > best) best = r;
+        }
+        s = (s + 1) & mask;
+    }
+    if (step == slots) status[1] = 1u;
+    return best;
+}
+
+// One lane per query key: of several sessions under one key the latest (largest row) wins.  Outputs may be absent (NULL).
 __global__ __launch_bounds__(256) void k_token_lookup(const TokKey* __restrict__ query, long long k, const int* __restrict__ slot_row, unsigned log2_slots,
                                                       const TokKey* __restrict__ tok, long long covered, const long long* __restrict__ end,
                                                       const long long* __restrict__ start, const int* __restrict__ user, long long now,
@@ -65,27 +88,70 @@ __global__ __launch_bounds__(256) void k_token_lookup(const TokKey* __restrict__
 {
     const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= k) return;
-    const TokKey key = query[t];
-    const unsigned long long slots = 1ull << log2_slots, mask = slots - 1;
-    unsigned long long s = token_home(key.x, key.y, log2_slots);
-    int best = -1;
-    unsigned long long step = 0;
-    for (; step < slots; ++step) {
-        const int r = slot_row[s];
-        if (r < 0) break;
-        if ((long long)r < covered) { // always true for an index in step with its column; keeps the load inside it regardless
-            const TokKey have = tok[r];
-            if (have.x == key.x && have.y == key.y && r > best) best = r;
-        }
-        s = (s + 1) & mask;
-    }
-    if (step == slots) status[1] = 1u;
+    const int best = token_probe(query[t], slot_row, log2_slots, tok, covered, status);
     const long long e = best >= 0 ? end[best] : INT64_MIN;
     if (o_row) o_row[t] = best;
     if (o_live) o_live[t] = (best >= 0 && e > now) ? 1 : 0;
     if (o_end) o_end[t] = e;
     if (o_start) o_start[t] = best >= 0 ? start[best] : 0;
     if (o_user) o_user[t] = best >= 0 ? user[best] : -1;
+}
+
+// ---- the token column of a SHARDED context (pie_shard_token_*): keys are given by GLOBAL row; a shard keeps the keys of the rows
+// its ascending row map holds (shard_lower_bound, pie_kernels.h) and indexes them by LOCAL row, exactly as above.
+
+// pie_shard_token_append: one lane per key of the staged chunk, which belongs to the global rows [g0, g0 + k).  The lane whose
+// global row the shard holds (local row r < n_local, inside the column's capacity) stores the key as one 16-byte store to tok[r]
+// and claims a slot for r from the key's home: the same relaxed agent-scope compare-and-swap as k_token_insert.  The key a probe
+// compares against is written by the lane that claims the slot, and every reader is a later kernel on the stream.
+__global__ __launch_bounds__(256) void k_shard_token_place(const TokKey* __restrict__ staged, long long g0, long long k,
+                                                           const int* __restrict__ rows_map, long long n_local, TokKey* __restrict__ tok,
+                                                           long long cap, int* __restrict__ slot_row, unsigned log2_slots,
+                                                           unsigned int* __restrict__ status)
+{
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= k) return;
+    const long long g = g0 + t;
+    if (g > 0x7fffffffLL) return;
+    const long long r = shard_lower_bound(rows_map, n_local, (int)g);
+    if (r >= n_local || r >= cap || (long long)rows_map[r] != g) return; // another shard's row, or one this shard's compactions dropped
+    const TokKey key = staged[t];
+    tok[r] = key;
+    const unsigned long long slots = 1ull << log2_slots, mask = slots - 1;
+    unsigned long long s = token_home(key.x, key.y, log2_slots);
+    unsigned long long step = 0;
+    for (; step < slots; ++step) {
+        int expected = -1;
+        if (__hip_atomic_compare_exchange_strong(&slot_row[s], &expected, (int)r, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;
+        s = (s + 1) & mask;
+    }
+    if (step == slots) status[0] = 1u;
+}
+
+// pie_shard_token_lookup: k_token_lookup with the row and the user answered as GLOBAL ids, read through the two maps (both reads
+// bounded: best < n_local, user < n_map; -1 otherwise).  `bound` = the rows the column can hold keys for.
+__global__ __launch_bounds__(256) void k_shard_token_lookup(const TokKey* __restrict__ query, long long k, const int* __restrict__ slot_row,
+                                                            unsigned log2_slots, const TokKey* __restrict__ tok, long long bound,
+                                                            const long long* __restrict__ end, const long long* __restrict__ start,
+                                                            const int* __restrict__ user, const int* __restrict__ rows_map, long long n_local,
+                                                            const int* __restrict__ users_map, int n_map, long long now, int* __restrict__ o_row,
+                                                            int* __restrict__ o_grow, unsigned char* __restrict__ o_live, int* __restrict__ o_user,
+                                                            long long* __restrict__ o_start, long long* __restrict__ o_end,
+                                                            unsigned int* __restrict__ status)
+{
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= k) return;
+    int best = token_probe(query[t], slot_row, log2_slots, tok, bound < n_local ? bound : n_local, status);
+    const long long e = best >= 0 ? end[best] : INT64_MIN;
+    if (o_row) o_row[t] = best;
+    if (o_grow) o_grow[t] = best >= 0 ? rows_map[best] : -1;
+    if (o_live) o_live[t] = (best >= 0 && e > now) ? 1 : 0;
+    if (o_end) o_end[t] = e;
+    if (o_start) o_start[t] = best >= 0 ? start[best] : 0;
+    if (o_user) {
+        const int u = best >= 0 ? user[best] : -1;
+        o_user[t] = (u >= 0 && u < n_map) ? users_map[u] : -1;
+    }
 }
 
 // the compaction hook: the keys of the kept covered rows, in their new places
