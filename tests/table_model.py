@@ -260,6 +260,167 @@ def tie_table(oracle, seed=2):
     return start, end, user, disc, U, D
 
 
+# ------------------------------------------------------------------------------------------------ the user axis
+# Boundaries of the library along the number of users, restated from the documented rules so that the
+# CPU tests can check the tables the GPU tests rely on.
+USER_TILE = 256               # users per tile of the batched union tail (and threads of its look-back)
+MQ_SLOTS = 64                 # per-query totals are folded by tile & 63
+BATCH_MAX_TILES = 2048        # the batched pass answers up to 2048 tiles: 524 288 users
+BATCH_MAX_USERS = USER_TILE * BATCH_MAX_TILES
+FUSED_SCAN_MAX_USERS = 512 * BATCH_MAX_TILES   # single scans: the fused offsets kernel, 512 users per tile, up to 2048 tiles
+DIRECT_MAX_BYTES = 2 << 30    # bound of every array of bucket slots
+BUCKET_REC_BYTES = 16
+WIDE_MASK_BYTES = 64          # eight 64-bit mask words per bucket slot of a wide batch
+UNION_SHIFT_MAX = 6           # union buckets grow from 16 over 32 to 64 slots per user
+
+PLANT_SIZES = (1, 2, 8, 9, 16, 17, 33, 64)
+PLANT_STAGE_ROWS = (16, 17, 33, 64, 65)   # rows of a planted bucket that the queries of stage k can select: min(size, this)
+PLANT_GROW_USER = 263                     # tile 1: the one bucket of 65 rows (64 up to stage 3)
+PLANT_OFFSETS = (0, 31, 32, 63, 64, 129, 200, 255)   # users of a full tile, by PLANT_SIZES
+
+
+def batch_supported_users(n_users):
+    return (n_users + USER_TILE - 1) // USER_TILE <= BATCH_MAX_TILES
+
+
+def union_slots_fit(cap_users, shift):
+    """the union buckets of the ordinary batch may grow to 1 << shift slots per user"""
+    return (cap_users << shift) * BUCKET_REC_BYTES <= DIRECT_MAX_BYTES
+
+
+def wide_union_fits(cap_users, shift):
+    """a wide batch keeps its union: its slot masks, 64 B per bucket slot, stay within the same 2 GiB"""
+    return (cap_users << shift) * WIDE_MASK_BYTES <= DIRECT_MAX_BYTES
+
+
+def plant_places(U):
+    """[(name, tile)] of the tiles that get a set of hand-made buckets, those that exist at U users: tile 0, tile 64 (congruent
+    to tile 0 and to tile 256 mod 64), tiles 255, 256 and 257 (tile 257 is the first whose look-back makes a second trip), the last full tile
+    and the last tile, which is partial unless U is a multiple of 256."""
+    tiles, full = (U + USER_TILE - 1) // USER_TILE, U // USER_TILE
+    out, seen = [], set()
+    for name, t in (("tile 0", 0), ("tile 64", 64), ("tile 255", 255), ("tile 256", 256), ("tile 257", 257),
+                    ("last full tile", full - 1), ("last tile", tiles - 1)):
+        if 0 <= t < tiles and t not in seen:
+            seen.add(t)
+            out.append((name, t))
+    return out
+
+
+def plant_users(U):
+    """{user: bucket size}.  A full tile holds all of PLANT_SIZES at PLANT_OFFSETS (64 rows on its last user); a partial last
+    tile holds the largest sizes that fit, on its last users (64 rows on user U - 1); and PLANT_GROW_USER holds 65."""
+    planted = {}
+    for _, t in plant_places(U):
+        width = min(USER_TILE, U - t * USER_TILE)
+        for i, size in enumerate(sorted(PLANT_SIZES, reverse=True)):
+            if width == USER_TILE:
+                planted[t * USER_TILE + PLANT_OFFSETS[len(PLANT_SIZES) - 1 - i]] = size
+            elif width - 1 - i >= 0:
+                planted[t * USER_TILE + width - 1 - i] = size
+    if U > PLANT_GROW_USER and PLANT_GROW_USER not in planted:
+        planted[PLANT_GROW_USER] = 65
+    return planted
+
+
+def plant_row_end(t0, j):
+    """`end` of row j of a planted bucket: rows 0..15 outlive every stage, row 16, rows 17..32, rows 33..63 and row 64 end one
+    hour apart, so that the queries of stage k (user_axis_queries) select exactly the first PLANT_STAGE_ROWS[k] of them."""
+    tier = 0 if j < 16 else 1 if j < 17 else 2 if j < 33 else 3 if j < 64 else 4
+    return t0 + HOUR if tier == 0 else t0 - (tier + 1) * HOUR
+
+
+def user_axis_queries(t0, k, stage):
+    """k heterogeneous top-of-range queries (distinct now, cutoff and mask, as tests/test_gpu_batch.py mixes them) whose `now`
+    values all lie between the ends of two tiers of the planted rows: within ten and a half minutes below
+    t0 - (stage + 2) h + 30 min.  Query 0 has every discipline and a cutoff below every planted start, so the union of any
+    prefix of the list holds every planted row that is live at that stage; the others select subsets of them."""
+    base = t0 - (stage + 2) * HOUR + HOUR // 2
+    masks = [ALL, 0x5555555555555555, 0xAAAAAAAAAAAAAAAA, 0x00000000FFFF0000, 0x1, 0x8000000000000001]
+    return [(base - 977 * i - (i % 3) * 60000, t0 - (65 - i % 4) * DAY - 13 * i, masks[i % len(masks)]) for i in range(k)]
+
+
+def plant_user_buckets(cols, U, D, t0, seed=7):
+    """Copies of the columns with the buckets of plant_users(U) written into them.  Rows the planted users had are given an
+    `end` thirty days back (no stage selects them); every planted user then gets `size` rows taken from the other users at
+    seeded positions all over the table: starts on five values a day apart that straddle the queries' cutoffs (runs of equal
+    starts, so the (start, row) order is decided by the row index), ends by plant_row_end, disciplines in steps of five.
+    -> ((start, end, user, disc), {user: size})"""
+    s, e, u, d = [np.array(c) for c in cols]
+    planted = plant_users(U)
+    is_planted = np.zeros(U, bool)
+    is_planted[list(planted)] = True
+    own = is_planted[u]
+    e[own] = t0 - 30 * DAY
+    pool = np.random.default_rng(seed).permutation(np.nonzero(~own)[0])
+    starts = np.array([t0 - 64 * DAY - 12 * HOUR + k * DAY for k in range(5)], np.int64)
+    at = 0
+    for pi, user in enumerate(sorted(planted)):
+        size = planted[user]
+        rows, at = pool[at:at + size], at + size
+        assert rows.size == size, "the table is too small for the planted buckets"
+        j = np.arange(size)
+        u[rows] = user
+        s[rows] = starts[(j * 3 + j // 7 + pi) % 5]
+        e[rows] = [plant_row_end(t0, int(x)) for x in j]
+        d[rows] = (j * 5 + pi) % D
+    return (s, e, u, d), planted
+
+
+def union_sizes(cols, U, D, queries):
+    """int64[U]: rows of every user that at least one query selects (plain numpy, no sort)."""
+    s, e, u, d = cols
+    lim = ALL if D >= 64 else (1 << D) - 1
+    cand = np.nonzero(e > min(q[0] for q in queries))[0]
+    cs, ce, cd = s[cand], e[cand], d[cand]
+    ok = (cd >= 0) & (cd < 64)
+    sh = np.where(ok, cd, 0).astype(np.uint64)
+    any_q = np.zeros(cand.size, bool)
+    for now, cutoff, mask in queries:
+        bit = ok & (((np.uint64(mask & lim) >> sh) & np.uint64(1)) == 1)
+        any_q |= (ce > now) & (cs >= cutoff) & bit
+    return np.bincount(u[cand[any_q]], minlength=U).astype(np.int64)
+
+
+def union_from_answers(start, user, U, answers):
+    """The union of a batch from its queries' answers: per user the rows any query selects in (start, row) order, and
+    ceil(Q / 64) mask words per row.  -> (uoff int64[U + 1], rows int32[Mu], masks uint64[Mu, words])"""
+    words = (len(answers) + 63) // 64
+    bits = np.zeros((start.size, words), np.uint64)
+    for q, (_, _, idx) in enumerate(answers):
+        bits[idx, q // 64] |= np.uint64(1 << (q % 64))
+    rows = np.nonzero(bits.any(axis=1))[0]
+    rows = rows[np.lexsort((rows, start[rows], user[rows]))]
+    uoff = np.zeros(U + 1, np.int64)
+    np.cumsum(np.bincount(user[rows], minlength=U), out=uoff[1:])
+    return uoff, rows.astype(np.int32), bits[rows]
+
+
+def union_message(U, u_pad, cap, union, n_q, wide):
+    """The exchange message of a union (include/pie_scan.h): [uoff[0..U] | Mu up to word u_pad + 1 | rows[cap) | masks], the
+    masks as mask_lo[cap) (| mask_hi[cap) above 32 queries) for an ordinary batch and as 2 * words int32 per row for a wide one.
+    -> (int32 message, bool mask of the words the library writes: those of rows beyond Mu or cap are left alone)"""
+    uoff, rows, masks = union
+    mu, words = int(rows.size), masks.shape[1]
+    k = min(mu, cap)
+    per_row = 1 + 2 * words if wide else 3 if n_q > 32 else 2
+    msg, written = np.zeros(u_pad + 2 + cap * per_row, np.int32), np.zeros(u_pad + 2 + cap * per_row, bool)
+    msg[: U + 1], msg[U + 1: u_pad + 2] = uoff.astype(np.int32), mu
+    written[: u_pad + 2] = True
+    at = u_pad + 2
+    msg[at: at + k], written[at: at + k] = rows[:k], True
+    at += cap
+    if wide:
+        msg[at: at + k * 2 * words] = np.ascontiguousarray(masks[:k]).reshape(-1).view(np.int32)
+        written[at: at + k * 2 * words] = True
+    else:
+        halves = np.ascontiguousarray(masks[:k, 0]).view(np.int32).reshape(k, 2)
+        msg[at: at + k], written[at: at + k] = halves[:, 0], True
+        if n_q > 32:
+            msg[at + cap: at + cap + k], written[at + cap: at + cap + k] = halves[:, 1], True
+    return msg, written
+
+
 # ------------------------------------------------------------------------------------------------ the seeded chain
 def same(got, want, tag):
     for name, a, b in zip(("counts", "offsets", "idx"), got, want):

@@ -114,3 +114,67 @@ def test_set_end_with_repeated_rows_keeps_the_last_value(oracle):
         assert m.end.dtype == np.int64 and [int(v) for v in m.end] == want, (k, distinct)
         untouched = np.setdiff1d(np.arange(n), rows)
         assert np.array_equal(m.end[untouched], before[untouched])
+
+
+# ------------------------------------------------------------------------------------------------ the user axis
+USER_AXIS_N, USER_AXIS_D = 300007, 32
+USER_AXIS_SIZES = [65536, 65537, 65793, 100003, 262145, 524288, 524289]
+
+
+@pytest.mark.parametrize("U", USER_AXIS_SIZES)
+def test_planted_buckets_have_the_stated_sizes(oracle, U):
+    """What tests/test_gpu_user_axis.py relies on: under the queries of stage k every planted user's union holds exactly
+    min(size, PLANT_STAGE_ROWS[k]) rows for 1, 16, 64 and 512 queries alike, nobody else's exceeds 16, no bucket exceeds 64
+    before stage 4, the places cover tiles 0, 255, 256, 257 where they exist, the last full tile, user U - 1 and two tiles that
+    are congruent mod 64, and the queries' masks differ on the planted rows.  The numpy union equals the C oracle's answers."""
+    n, D, t0 = USER_AXIS_N, USER_AXIS_D, oracle.T0_MS
+    cols, planted = T.plant_user_buckets(oracle.gen(11, n, 0, n, U, D, 0), U, D, t0)
+    tiles = sorted({u // T.USER_TILE for u in planted} - {T.PLANT_GROW_USER // T.USER_TILE})
+    n_tiles = (U + T.USER_TILE - 1) // T.USER_TILE
+    assert 0 in tiles and U // T.USER_TILE - 1 in tiles and n_tiles - 1 in tiles and planted[U - 1] == 64
+    assert [t for t in (255, 256, 257) if t < n_tiles] == [t for t in (255, 256, 257) if t in tiles]
+    assert any(a != b and a % T.MQ_SLOTS == b % T.MQ_SLOTS for a in tiles for b in tiles)
+    for t in tiles:
+        if min(T.USER_TILE, U - t * T.USER_TILE) == T.USER_TILE:
+            assert sorted(planted[u] for u in planted if u // T.USER_TILE == t and u != T.PLANT_GROW_USER) == list(T.PLANT_SIZES)
+    assert planted[T.PLANT_GROW_USER] == 65 and np.all(np.bincount(cols[2], minlength=U)[list(planted)] >= 1)
+    users = np.array(sorted(planted))
+    sizes = np.array([planted[int(u)] for u in users])
+    for stage, top in enumerate(T.PLANT_STAGE_ROWS):
+        for k in (1, 16, 64, 512):
+            got = T.union_sizes(cols, U, D, T.user_axis_queries(t0, k, stage))
+            assert np.array_equal(got[users], np.minimum(sizes, top)), (stage, k)
+            assert int(got.max()) == top, (stage, k, "the largest bucket of the table is not the stage's")
+            got[users] = 0
+            assert got.max() <= 16, (stage, k, "a bucket that is not planted")
+    # one stage against the C oracle: the union, its sizes, and masks that differ inside the planted buckets
+    qs = T.user_axis_queries(t0, 16, 3)
+    answers = [oracle.scan(*cols, U, now, cutoff, mask & ((1 << D) - 1)) for now, cutoff, mask in qs]
+    uoff, rows, masks = T.union_from_answers(cols[0], cols[2], U, answers)
+    assert np.array_equal(np.diff(uoff), T.union_sizes(cols, U, D, qs))
+    T.check_union("planted", (uoff, rows, masks.reshape(-1)), answers, False)
+    big = int(users[sizes == 64][0])
+    in_big = slice(int(uoff[big]), int(uoff[big + 1]))
+    assert np.unique(masks[in_big]).size >= 8, "the queries' masks do not differ on the planted rows"
+    assert np.unique(cols[0][rows[in_big]]).size <= 5, "no equal starts inside the bucket"
+    for q, (c, off, idx) in enumerate(answers):
+        assert np.array_equal(c, np.diff(off)) and idx.size == off[-1]
+    msg, written = T.union_message(U, U + 3, rows.size + 2, (uoff, rows, masks), 16, False)
+    assert msg[U + 1] == msg[U + 4] == rows.size and not written[U + 5 + rows.size] and written[U + 5 + rows.size + 2]
+
+
+def test_user_axis_boundaries():
+    """The capacity arithmetic the GPU tests state in their docstrings."""
+    assert T.batch_supported_users(524288) and not T.batch_supported_users(524289) and T.BATCH_MAX_USERS == 524288
+    assert T.FUSED_SCAN_MAX_USERS == 1048576
+    # the wide rule: 300 000 users loaded, one more appended: the user arrays double to 600 000
+    cap = 2 * 300000
+    assert T.batch_supported_users(300001)
+    assert T.wide_union_fits(cap, 4) and T.wide_union_fits(cap, 5) and not T.wide_union_fits(cap, 6)
+    assert T.union_slots_fit(cap, T.UNION_SHIFT_MAX)
+    assert T.wide_union_fits(300000, 6), "without the doubling the rule is not reached"
+    # growth across 524 288: 524 200 users loaded, then more: 1 048 400; wide batches keep their union while buckets hold 16 slots
+    assert T.wide_union_fits(2 * 524200, 4) and T.wide_union_fits(2 * 524200, 5) and not T.wide_union_fits(2 * 524200, 6)
+    # single scans: a bucket of 100 rows asks for 128 slots; 2 GiB hold 64 per user at 1 048 577 users and 32 at 3 000 000
+    assert T.union_slots_fit(1048577, 6) and not T.union_slots_fit(1048577, 7)
+    assert T.union_slots_fit(3000000, 5) and not T.union_slots_fit(3000000, 6)
