@@ -127,6 +127,23 @@ int pie_set_end_last_writers(const int32_t *rows, size_t k, uint8_t *keep_out);
  * unknown ids are a no-op like the falsy-id guard :56-58).  rows_out (may be NULL) receives the tombstoned row
  * indices in ascending order so the host can drop their token-map entries; *n_deleted their number. */
 int pie_delete_user(pie_ctx *ctx, int32_t user, int32_t *rows_out, size_t cap, size_t *n_deleted);
+/* deleteSessionsForUser for a whole set of users in one call: afterwards the table and everything derived from it (both liveness
+ * keys, the payload column, the hot index and its delta, the ordered run's mirror, what the token index sees as live) are what
+ * k calls pie_delete_user(ctx, users[i], ...) in array order would have left, after two passes over the user column whatever k
+ * is (membership is a bit test in a bitmap of n_users bits; `end` is read only for rows whose user is in the set) and at most
+ * two waits.  rows_out (may be NULL) receives ALL tombstoned rows in ascending row order, the sorted union of the k single
+ * lists, *n_deleted their number; a cap too small tombstones the rows all the same, fills *n_deleted and per_user_out and
+ * returns PIE_E_CAPACITY.  per_user_out[i] (may be NULL) = rows tombstoned for users[i]: an id named more than once has its
+ * count at its FIRST occurrence and 0 at the later ones (the second of two deleteSessionsForUser calls finds nothing), ids < 0
+ * or >= n_users have 0 and are a no-op; the counts add up to *n_deleted.  k = 0: PIE_OK, nothing changes.  users = NULL with
+ * k > 0: PIE_E_INVAL.  PIE_E_STATE while a scan or batch is in flight (nothing changes).  Queued appends and touches are
+ * ordered in front; slot 0's finished result and the held queue go as under pie_delete_user. */
+int pie_delete_users(pie_ctx *ctx, const int32_t *users, size_t k, int32_t *rows_out, size_t cap, size_t *n_deleted,
+                     int32_t *per_user_out /* [k] */);
+/* Host only, no context, no GPU: what pie_delete_users uploads.  bits_out[(n_users + 63) / 64] = membership bitmap of the valid
+ * ids (0 <= id < n_users; bit id % 64 of word id / 64; bits at and above n_users are 0), first_out[i] = 1 iff users[i] is valid
+ * and is the first occurrence of its value, else 0.  k = 0 and n_users <= 0 are allowed.  For tests. */
+int pie_delete_users_plan(const int32_t *users, size_t k, int32_t n_users, uint64_t *bits_out, uint8_t *first_out /* [k] */);
 
 /* _pruneCalendarEvents (server/storage/sqlProvider.js:956-968): tombstone every row with start < cutoff (the
  * complement of the scan's window predicate); rows_out / n_pruned as in pie_delete_user. */
@@ -490,6 +507,10 @@ int pie_shard_set_end(pie_ctx *ctx, const int32_t *rows_global, const int64_t *n
 /* pie_delete_user by GLOBAL user id: a no-op (n_deleted = 0) on the shards the user does not hash to and for ids outside
  * [0, U_g); rows_global_out (may be NULL) receives GLOBAL rows, ascending. */
 int pie_shard_delete_user(pie_ctx *ctx, int32_t user_global, int32_t *rows_global_out, size_t cap, size_t *n_deleted);
+/* pie_delete_users by GLOBAL user ids: ids outside [0, U_g), ids that hash to another shard and ids this shard's user map does
+ * not hold are skipped (count 0); rows_global_out receives GLOBAL rows, ascending (translated on the device). */
+int pie_shard_delete_users(pie_ctx *ctx, const int32_t *users_global, size_t k, int32_t *rows_global_out, size_t cap,
+                           size_t *n_deleted, int32_t *per_user_out /* [k] */);
 /* k global rows -> local rows in place (-1: not held by this shard); k local rows -> global rows in place (-1: outside the
  * map).  One small launch each, for hosts that hold a few rows of a huge table (the shape of pie_compact_translate); with
  * them the per-shard lists of pie_prune_before / pie_retention_purge* become global rows. */
@@ -708,6 +729,11 @@ int pie_comm_append_rows(pie_comm *comm, const int64_t *start, const int64_t *en
                          int32_t n_users, int32_t *first_row_out);
 int pie_comm_set_end(pie_comm *comm, const int32_t *rows, const int64_t *new_end, size_t k);
 int pie_comm_delete_user(pie_comm *comm, int32_t user, int32_t *rows_out, size_t cap, size_t *n_deleted, int32_t *owner_rank_out);
+/* pie_shard_delete_users with the whole id list on every local shard: rows_out = the per-shard lists merged into ONE ascending
+ * list of global rows, per_user_out[i] summed over the local shards, owner_rank_out[i] (may be NULL) = pie_shard_of(users[i],
+ * world), -1 for an id outside [0, users).  A process reports what its own shards held, as pie_comm_delete_user. */
+int pie_comm_delete_users(pie_comm *comm, const int32_t *users, size_t k, int32_t *rows_out, size_t cap, size_t *n_deleted,
+                          int32_t *per_user_out /* [k] */, int32_t *owner_rank_out /* [k] */);
 int pie_comm_table_size(pie_comm *comm, int64_t *rows_global_out, int32_t *users_global_out);
 /* The token column behind the communicator (pie_shard_token_* on every local shard; the rules above hold: PIE_E_STATE while
  * pipelined steps are uncollected, every local shard checks a call before any is staged or changed).

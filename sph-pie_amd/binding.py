@@ -75,6 +75,8 @@ _SIGS = [
     ("pie_set_end", C.c_int, [_P, _P, _P, C.c_size_t]),
     ("pie_set_end_last_writers", C.c_int, [_P, C.c_size_t, _P]),
     ("pie_delete_user", C.c_int, [_P, C.c_int32, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("pie_delete_users", C.c_int, [_P, _P, C.c_size_t, _P, C.c_size_t, C.POINTER(C.c_size_t), _P]),
+    ("pie_delete_users_plan", C.c_int, [_P, C.c_size_t, C.c_int32, _P, _P]),
     ("pie_prune_before", C.c_int, [_P, C.c_int64, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("pie_retention_purge", C.c_int, [_P, C.c_int64, C.c_int32, C.c_int64, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("pie_retention_purge_tz", C.c_int, [_P, C.c_int64, C.c_int32, _P, _P, C.c_int32, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
@@ -143,6 +145,7 @@ _SIGS = [
     ("pie_shard_append_rows", C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_size_t)]),
     ("pie_shard_set_end", C.c_int, [_P, _P, _P, C.c_size_t]),
     ("pie_shard_delete_user", C.c_int, [_P, C.c_int32, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("pie_shard_delete_users", C.c_int, [_P, _P, C.c_size_t, _P, C.c_size_t, C.POINTER(C.c_size_t), _P]),
     ("pie_shard_rows_to_local", C.c_int, [_P, _P, C.c_size_t]),
     ("pie_shard_rows_to_global", C.c_int, [_P, _P, C.c_size_t]),
     ("pie_shard_route", C.c_int, [_P, C.c_size_t, C.c_int32, C.c_int32, _P, C.POINTER(C.c_size_t), C.c_int32, C.c_int32, _P, C.c_size_t,
@@ -189,6 +192,7 @@ _SIGS = [
     ("pie_comm_append_rows", C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, C.c_int32, C.POINTER(C.c_int32)]),
     ("pie_comm_set_end", C.c_int, [_P, _P, _P, C.c_size_t]),
     ("pie_comm_delete_user", C.c_int, [_P, C.c_int32, _P, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int32)]),
+    ("pie_comm_delete_users", C.c_int, [_P, _P, C.c_size_t, _P, C.c_size_t, C.POINTER(C.c_size_t), _P, _P]),
     ("pie_comm_table_size", C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     ("pie_token_set", C.c_int, [_P, _P, C.c_size_t]),
     ("pie_token_append", C.c_int, [_P, _P, C.c_size_t]),
@@ -342,6 +346,19 @@ class PieScan:
         rows = np.empty(max(self.n, 1), np.int32)
         self._check(self._lib.pie_delete_user(self._ctx, int(user), _ptr(rows), self.n, C.byref(k)))
         return rows[: k.value].copy()
+
+    def delete_users(self, users, cap=None):
+        """deleteSessionsForUser for every id of `users` in one call (pie_delete_users) -> (rows, per_user): all tombstoned rows
+        ascending, and per element the rows tombstoned for it (a repeated id counts at its first occurrence, an unknown id 0).
+        cap: entries of the row list to offer (default: the table's rows); too few raises PieError(PIE_E_CAPACITY) with the
+        rows tombstoned all the same."""
+        users = _col(users, np.int32)
+        k = C.c_size_t(0)
+        cap = self.n if cap is None else int(cap)
+        rows = np.empty(max(cap, 1), np.int32)
+        per = np.zeros(users.shape[0], np.int32)
+        self._check(self._lib.pie_delete_users(self._ctx, _ptr(users), users.shape[0], _ptr(rows), cap, C.byref(k), _ptr(per)))
+        return rows[: k.value].copy(), per
 
     def prune_before(self, cutoff):
         """Tombstone rows with start < cutoff; -> their ascending row indices."""
@@ -931,6 +948,15 @@ class PieScan:
         self._check(self._lib.pie_shard_delete_user(self._ctx, int(user_global), _ptr(rows), self.n, C.byref(k)))
         return rows[: k.value].copy()
 
+    def shard_delete_users(self, users_global):
+        """pie_delete_users by GLOBAL ids -> (ascending GLOBAL rows tombstoned, per_user); ids of other shards count 0."""
+        users = _col(users_global, np.int32)
+        k = C.c_size_t(0)
+        rows = np.empty(max(self.n, 1), np.int32)
+        per = np.zeros(users.shape[0], np.int32)
+        self._check(self._lib.pie_shard_delete_users(self._ctx, _ptr(users), users.shape[0], _ptr(rows), self.n, C.byref(k), _ptr(per)))
+        return rows[: k.value].copy(), per
+
     def shard_rows_to_local(self, rows_global):
         """Global rows -> this shard's local rows (-1: not held), as a new int32 array."""
         rows = np.array(rows_global, dtype=np.int32, copy=True).reshape(-1)
@@ -1234,6 +1260,16 @@ class PieComm:
         self._check(self._lib.pie_comm_delete_user(self._c, int(user), _ptr(rows), cap, C.byref(k), C.byref(owner)))
         return rows[: k.value].copy(), int(owner.value)
 
+    def delete_users(self, users):
+        """deleteSessionsForUser for a set of global ids in one call on every local shard -> (ascending global rows tombstoned,
+        per_user counts, owning rank per id or -1)."""
+        users = _col(users, np.int32)
+        cap = max(self.table_size()[0], 1)
+        rows, k = np.empty(cap, np.int32), C.c_size_t(0)
+        per, owners = np.zeros(users.shape[0], np.int32), np.full(users.shape[0], -1, np.int32)
+        self._check(self._lib.pie_comm_delete_users(self._c, _ptr(users), users.shape[0], _ptr(rows), cap, C.byref(k), _ptr(per), _ptr(owners)))
+        return rows[: k.value].copy(), per, owners
+
     # ---- the token column behind the communicator (pie_comm_token_*): keys are uint64 arrays of shape (k, 2), GLOBAL ids out
     def token_set(self, keys):
         """Keys for the global rows [0, len(keys)) on every local shard."""
@@ -1373,6 +1409,18 @@ def set_end_last_writers(rows):
     if rc != 0:
         raise PieError(rc, "pie_set_end_last_writers: bad argument")
     return keep
+
+
+def delete_users_plan(users, n_users):
+    """Host only (pie_delete_users_plan): what delete_users uploads -> (bits uint64[(n_users + 63) // 64], first uint8[k]): the
+    membership bitmap of the ids in [0, n_users), and 1 where an element is valid and the first occurrence of its value."""
+    users = _col(users, np.int32)
+    bits = np.full((max(int(n_users), 0) + 63) // 64, np.uint64(0xFFFFFFFFFFFFFFFF), np.uint64)   # the call clears it
+    first = np.full(users.shape[0], 255, np.uint8)
+    rc = load_library().pie_delete_users_plan(_ptr(users), users.shape[0], int(n_users), _ptr(bits), _ptr(first))
+    if rc != 0:
+        raise PieError(rc, "pie_delete_users_plan: bad argument")
+    return bits, first
 
 
 def batch_mask_codes(queries, n_disc, start, end, disc, fallback=None):

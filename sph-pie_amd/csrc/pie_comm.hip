@@ -17,6 +17,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <algorithm>
 #include <ctime>
 #include <new>
 #include <string>
@@ -31,6 +32,11 @@ int shard_token_check(pie_ctx* c, const uint64_t* tok, size_t k, bool set);
 int shard_token_lookup_queue(pie_ctx* c, const uint64_t* tok, size_t k, int64_t now);
 int shard_token_lookup_wait(pie_ctx* c, size_t k, int32_t* row_global_out, uint8_t* live_out, int32_t* user_global_out, int64_t* start_out,
                             int64_t* end_out);
+// ... and pie_shard_delete_users in three pieces: the check, the run that leaves the ascending list of global rows on the device,
+// the copy of that list
+int shard_check_delete_users(pie_ctx* c, const int32_t* users_global, size_t k);
+int shard_delete_users_run(pie_ctx* c, const int32_t* users_global, size_t k, size_t* m_out, int32_t* per_user_out);
+int shard_delete_users_copy(pie_ctx* c, int32_t* rows_global_out, size_t m);
 } // namespace pie_internal
 
 namespace {
@@ -975,6 +981,44 @@ int pie_comm_delete_user(pie_comm* c, int32_t user, int32_t* rows_out, size_t ca
     const int i = local_index(c, owner);
     if (i < 0) return PIE_OK; // the owning rank lives in another process, which makes the same call
     PIE_CCTX(c, i, pie_shard_delete_user(c->ctx[i], user, rows_out, cap, n_deleted));
+    return PIE_OK;
+}
+
+int pie_comm_delete_users(pie_comm* c, const int32_t* users, size_t k, int32_t* rows_out, size_t cap, size_t* n_deleted, int32_t* per_user_out,
+                          int32_t* owner_rank_out)
+{
+    if (!c) return PIE_E_INVAL;
+    if (n_deleted) *n_deleted = 0;
+    if (k > 0 && !users) return cfail(c, PIE_E_INVAL, "NULL user list");
+    int32_t n_users = 0;
+    int rc = mutate_ready(c, nullptr, &n_users);
+    if (rc) return rc;
+    for (int i = 0; i < c->n_local; ++i) PIE_CCTX(c, i, pie_internal::shard_check_delete_users(c->ctx[i], users, k));
+    if (per_user_out && k) memset(per_user_out, 0, k * 4);
+    if (owner_rank_out)
+        for (size_t j = 0; j < k; ++j) owner_rank_out[j] = (users[j] < 0 || users[j] >= n_users) ? -1 : pie_shard_of(users[j], c->world);
+    if (k == 0) return PIE_OK;
+    // every local shard gets the whole list; its own list (global rows, ascending) is merged behind the ones before it
+    std::vector<int32_t> merged, per;
+    try {
+        if (per_user_out) per.resize(k);
+        for (int i = 0; i < c->n_local; ++i) {
+            size_t m = 0;
+            PIE_CCTX(c, i, pie_internal::shard_delete_users_run(c->ctx[i], users, k, &m, per_user_out ? per.data() : nullptr));
+            if (per_user_out)
+                for (size_t j = 0; j < k; ++j) per_user_out[j] += per[j];
+            if (n_deleted) *n_deleted += m;
+            if (!rows_out || m == 0) continue;
+            const size_t before = merged.size();
+            merged.resize(before + m);
+            PIE_CCTX(c, i, pie_internal::shard_delete_users_copy(c->ctx[i], merged.data() + before, m));
+            std::inplace_merge(merged.begin(), merged.begin() + (std::ptrdiff_t)before, merged.end());
+        }
+    } catch (const std::bad_alloc&) {
+        return cfail(c, PIE_E_NOMEM, "no memory for the merged list");
+    }
+    if (rows_out && merged.size() > cap) return cfail(c, PIE_E_CAPACITY, "list cap %zu < %zu", cap, merged.size()); // tombstoned all the same
+    if (rows_out && !merged.empty()) memcpy(rows_out, merged.data(), merged.size() * 4);
     return PIE_OK;
 }
 

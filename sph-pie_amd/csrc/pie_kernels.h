@@ -4265,6 +4265,111 @@ __global__ __launch_bounds__(256) void k_list_write(long long* __restrict__ end,
     }
 }
 
+// ------------------------------------------------------------------------------------------------ deleteSessionsForUser, a set of users
+//
+// MODE 1 above for many users at once (pie_delete_users): membership is one bit test in a bitmap of n_users bits (<= 128 KB at
+// 2^20 users: it lives in L2), so the two passes read the user column alone, 16 bytes per lane per load, and `end` only for
+// the rows whose user is in the set: ~4 B/row per pass where k_list_count / k_list_write read 12, whatever the size of the set.
+// Every WAVE owns a contiguous quarter of its block's rows (as k_expired_stage does): the count pass leaves one count per wave,
+// k_block_prefix_wide turns them into offsets, and the write pass needs no LDS and no barrier: the rank of a hit inside a
+// wave step is four ballots (a lane's four rows are consecutive).  The list comes out ascending by row.
+typedef int i4_t __attribute__((ext_vector_type(4)));
+constexpr int kDuQuads = 4;                       // 16-byte loads a lane keeps in flight
+constexpr int kDuStepRows = kWave * 4;            // rows of one load of a wave
+constexpr int kDuWaveRows = kDuStepRows * kDuQuads;
+
+// user ids of rows [r4, r4 + 4), r4 a multiple of 4; -1 for rows at or past `hi` (hi <= n)
+__device__ __forceinline__ i4_t du_load4(const int* __restrict__ user, long long r4, long long hi, long long n)
+{
+    i4_t v = {-1, -1, -1, -1};
+    if (r4 >= hi) return v;
+    if (r4 + 4 <= n) return *reinterpret_cast<const i4_t*>(user + r4);
+    v.x = user[r4]; // the table's last, partial quad
+    if (r4 + 1 < n) v.y = user[r4 + 1];
+    if (r4 + 2 < n) v.z = user[r4 + 2];
+    return v;
+}
+
+__device__ __forceinline__ bool du_hit(const long long* end, int u, long long r, long long lo, long long hi,
+                                       const unsigned int* __restrict__ bits, int n_users)
+{
+    return r >= lo && r < hi && (unsigned)u < (unsigned)n_users && ((bits[u >> 5] >> (u & 31)) & 1u) && end[r] != INT64_MIN;
+}
+
+// WRITE = false: wave_count[4 * block + wave] = hits of the wave's rows.  WRITE = true: the hits' rows behind wave_off[...] in
+// `queue`, and every hit tombstoned exactly as k_list_write<1> does it.
+template <bool WRITE>
+__global__ __launch_bounds__(kK1Threads) void k_users_pass(long long* end, const int* __restrict__ user, long long n, long long rows_per_block,
+                                                           const unsigned int* __restrict__ bits, int n_users, int* __restrict__ wave_count,
+                                                           const long long* __restrict__ wave_off, int* __restrict__ queue, long long cap,
+                                                           lkey_t* __restrict__ key, fkey_t* __restrict__ fkey, OrdMirror ord, HotMirror hot)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long rpw = (rows_per_block + kK1Waves - 1) / kK1Waves;
+    const long long c0 = (long long)blockIdx.x * rows_per_block;
+    const long long c1 = min(n, c0 + rows_per_block);
+    const long long lo = min(c1, c0 + wave * rpw), hi = min(c1, lo + rpw);
+    long long cursor = 0;
+    if constexpr (WRITE) cursor = wave_off[(long long)blockIdx.x * kK1Waves + wave];
+    int total = 0;
+    // steps start at a multiple of 4 at or below `lo`: the rows in front of `lo` are read (they are in the table) and masked
+    for (long long t = lo & ~3LL; t < hi; t += kDuWaveRows) {
+        i4_t q[kDuQuads];
+#pragma unroll
+        for (int j = 0; j < kDuQuads; ++j) q[j] = du_load4(user, t + (long long)j * kDuStepRows + 4 * lane, hi, n);
+#pragma unroll
+        for (int j = 0; j < kDuQuads; ++j) {
+            const long long r4 = t + (long long)j * kDuStepRows + 4 * lane;
+            const bool h0 = du_hit(end, q[j].x, r4, lo, hi, bits, n_users), h1 = du_hit(end, q[j].y, r4 + 1, lo, hi, bits, n_users);
+            const bool h2 = du_hit(end, q[j].z, r4 + 2, lo, hi, bits, n_users), h3 = du_hit(end, q[j].w, r4 + 3, lo, hi, bits, n_users);
+            const unsigned long long b0 = __ballot(h0), b1 = __ballot(h1), b2 = __ballot(h2), b3 = __ballot(h3);
+            const int wtotal = __popcll(b0) + __popcll(b1) + __popcll(b2) + __popcll(b3);
+            if constexpr (WRITE) {
+                if (wtotal == 0) continue; // wave-uniform
+                // all four rows of every lane below, then this lane's own in row order
+                long long pos = cursor + prefix_in_ballot(b0) + prefix_in_ballot(b1) + prefix_in_ballot(b2) + prefix_in_ballot(b3);
+                const bool h[4] = {h0, h1, h2, h3};
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    if (!h[i]) continue;
+                    const long long r = r4 + i;
+                    if (pos < cap) queue[pos] = (int)r;
+                    ++pos;
+                    end[r] = INT64_MIN; // a tombstone's liveness keys are 0 under every base
+                    if (key) key[r] = 0;
+                    if (fkey) fkey[r] = 0;
+                    ord_mirror_end(ord, r, INT64_MIN, 0u, 0u);
+                    hot_mirror_end(hot, r, INT64_MIN, 0u);
+                }
+                cursor += wtotal;
+            } else {
+                total += wtotal;
+            }
+        }
+    }
+    if constexpr (!WRITE) {
+        if (lane == 0) wave_count[(long long)blockIdx.x * kK1Waves + wave] = total;
+    }
+}
+
+// per_user_out of pie_delete_users, over the finished list (never over the table): the user of every listed row, looked up in
+// the ascending array of the set's distinct ids, one atomic per row on that id's counter
+__global__ __launch_bounds__(256) void k_users_tally(const int* __restrict__ list, const unsigned long long* __restrict__ m_ptr, long long cap,
+                                                     const int* __restrict__ user, const int* __restrict__ ids, int d, unsigned int* __restrict__ cnt)
+{
+    const long long m = min((long long)*m_ptr, cap);
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (long long)gridDim.x * blockDim.x) {
+        const int u = user[list[i]];
+        int a = 0, b = d;
+        while (a < b) {
+            const int mid = (a + b) >> 1;
+            if (ids[mid] < u) a = mid + 1;
+            else b = mid;
+        }
+        if (a < d && ids[a] == u) atomicAdd(&cnt[a], 1u);
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ user-hash sharding on the device
 //
 // rows are partitioned by gpu = splitmix64(user) mod G (pie_shard_of; the same function in the oracle).

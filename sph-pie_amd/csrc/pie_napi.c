@@ -37,6 +37,7 @@
     X(int, pie_read_columns, (pie_ctx *, int64_t *, int64_t *, int32_t *, int32_t *, size_t))                       \
     X(int, pie_set_end, (pie_ctx *, const int32_t *, const int64_t *, size_t))                                      \
     X(int, pie_delete_user, (pie_ctx *, int32_t, int32_t *, size_t, size_t *))                                      \
+    X(int, pie_delete_users, (pie_ctx *, const int32_t *, size_t, int32_t *, size_t, size_t *, int32_t *))          \
     X(int, pie_batch_fetch_requests, (pie_ctx *, const int32_t *, const int32_t *, size_t, size_t, int64_t *, int32_t *, int64_t *, int64_t *, int32_t *, size_t *)) \
     X(int, pie_retention_purge_tz, (pie_ctx *, int64_t, int32_t, const int64_t *, const int64_t *, int32_t, int32_t *, size_t, size_t *)) \
     X(int, pie_set_disciplines, (pie_ctx *, uint64_t, int32_t))                                                     \
@@ -89,6 +90,7 @@
     X(int, pie_comm_append_rows, (pie_comm *, const int64_t *, const int64_t *, const int32_t *, const int32_t *, size_t, int32_t, int32_t *)) \
     X(int, pie_comm_set_end, (pie_comm *, const int32_t *, const int64_t *, size_t))                                 \
     X(int, pie_comm_delete_user, (pie_comm *, int32_t, int32_t *, size_t, size_t *, int32_t *))                      \
+    X(int, pie_comm_delete_users, (pie_comm *, const int32_t *, size_t, int32_t *, size_t, size_t *, int32_t *, int32_t *)) \
     X(int, pie_comm_table_size, (pie_comm *, int64_t *, int32_t *))                                                  \
     X(int, pie_shard_maps, (pie_ctx *, int32_t *, int32_t *))                                                       \
     X(int, pie_compact_rows, (pie_ctx *, int64_t, uint32_t, size_t *))                                              \
@@ -528,6 +530,34 @@ static napi_value fn_delete_user(napi_env env, napi_callback_info info)
         return NULL;
     }
     int rc = p_pie_delete_user(ctx, user, rows, cap, &k);
+    if (rc) return throw_pie(env, ctx, rc);
+    return js_int(env, (int64_t)k);
+}
+
+/* deleteUsers(ctx, users Int32Array, rowsOut Int32Array[, perUser Int32Array]) -> number of rows tombstoned for the whole set in
+ * one call (rowsOut holds them, ascending; perUser[i], as long as users, the rows of users[i]: a repeated id counts once) */
+static napi_value fn_delete_users(napi_env env, napi_callback_info info)
+{
+    size_t argc = 4;
+    napi_value argv[4];
+    CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 3) {
+        napi_throw_type_error(env, NULL, "too few arguments");
+        return NULL;
+    }
+    pie_ctx *ctx = get_ctx(env, argv[0]);
+    if (!ctx) return NULL;
+    size_t n = 0, cap = 0, np = 0, k = 0;
+    int32_t *users = typed(env, argv[1], napi_int32_array, &n);
+    int32_t *rows = typed(env, argv[2], napi_int32_array, &cap);
+    int32_t *per = argc > 3 ? typed(env, argv[3], napi_int32_array, &np) : NULL;
+    bool users_typed = false;
+    if (napi_is_typedarray(env, argv[1], &users_typed) != napi_ok) users_typed = false;
+    if (!users_typed || (!users && n) || !rows || (argc > 3 && n && (!per || np != n))) {
+        napi_throw_type_error(env, NULL, "deleteUsers(ctx, Int32Array users, Int32Array rowsOut[, Int32Array perUser])");
+        return NULL;
+    }
+    int rc = n ? p_pie_delete_users(ctx, users, n, rows, cap, &k, per) : 0;
     if (rc) return throw_pie(env, ctx, rc);
     return js_int(env, (int64_t)k);
 }
@@ -1603,6 +1633,35 @@ static napi_value fn_comm_delete_user(napi_env env, napi_callback_info info)
     return out;
 }
 
+/* commDeleteUsers(comm, users Int32Array, rowsOut Int32Array[, perUser Int32Array[, owners Int32Array]]) -> rows tombstoned over
+ * the local shards (rowsOut: global rows, ascending) */
+static napi_value fn_comm_delete_users(napi_env env, napi_callback_info info)
+{
+    size_t argc = 5;
+    napi_value argv[5];
+    CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 3) {
+        napi_throw_type_error(env, NULL, "too few arguments");
+        return NULL;
+    }
+    comm_box *cbx = get_comm_box(env, argv[0]);
+    if (!cbx) return NULL;
+    size_t n = 0, cap = 0, np = 0, no = 0, k = 0;
+    int32_t *users = typed(env, argv[1], napi_int32_array, &n);
+    int32_t *rows = typed(env, argv[2], napi_int32_array, &cap);
+    int32_t *per = argc > 3 ? typed(env, argv[3], napi_int32_array, &np) : NULL;
+    int32_t *own = argc > 4 ? typed(env, argv[4], napi_int32_array, &no) : NULL;
+    bool users_typed = false;
+    if (napi_is_typedarray(env, argv[1], &users_typed) != napi_ok) users_typed = false;
+    if (!users_typed || (!users && n) || !rows || (argc > 3 && n && (!per || np != n)) || (argc > 4 && n && (!own || no != n))) {
+        napi_throw_type_error(env, NULL, "commDeleteUsers(comm, Int32Array users, Int32Array rowsOut[, Int32Array perUser[, Int32Array owners]])");
+        return NULL;
+    }
+    int rc = n ? p_pie_comm_delete_users(cbx->comm, users, n, rows, cap, &k, per, own) : 0;
+    if (rc) return throw_comm(env, cbx->comm, rc);
+    return js_int(env, (int64_t)k);
+}
+
 static napi_value fn_comm_table_size(napi_env env, napi_callback_info info)
 {
     ARGS(1)
@@ -2184,7 +2243,7 @@ static napi_value init(napi_env env, napi_value exports)
     } table[] = {
         {"open", fn_open}, {"deviceCount", fn_device_count}, {"ctxCreate", fn_ctx_create}, {"ctxDestroy", fn_ctx_destroy},
         {"loadColumns", fn_load_columns}, {"appendRows", fn_append_rows}, {"genSynthetic", fn_gen},
-        {"readColumns", fn_read_columns}, {"saveColumns", fn_save_columns}, {"loadColumnsDir", fn_load_columns_dir}, {"setEnd", fn_set_end}, {"compactRows", fn_compact_rows}, {"compactMaps", fn_compact_maps}, {"compactTranslate", fn_compact_translate}, {"deleteUser", fn_delete_user}, {"retentionPurgeTz", fn_retention_purge_tz},
+        {"readColumns", fn_read_columns}, {"saveColumns", fn_save_columns}, {"loadColumnsDir", fn_load_columns_dir}, {"setEnd", fn_set_end}, {"compactRows", fn_compact_rows}, {"compactMaps", fn_compact_maps}, {"compactTranslate", fn_compact_translate}, {"deleteUser", fn_delete_user}, {"deleteUsers", fn_delete_users}, {"retentionPurgeTz", fn_retention_purge_tz},
         {"setDisciplines", fn_set_disc}, {"scan", fn_scan}, {"scanDevice", fn_scan_device}, {"userFeed", fn_user_feed}, {"scanAsync", fn_scan_async}, {"fetchRows", fn_fetch_rows},
         {"expiredQueue", fn_expired_queue}, {"archiveQueue", fn_archive_queue}, {"serializeEvents", fn_serialize_events}, {"serializeICal", fn_serialize_ical}, {"stats", fn_stats}, {"setProfiling", fn_set_profiling},
         {"setOrderedRun", fn_set_ordered_run}, {"setWideOrdered", fn_set_wide_ordered}, {"wideUnionRows", fn_wide_union_rows}, {"setBatchLanes", fn_set_batch_lanes},
@@ -2196,7 +2255,7 @@ static napi_value init(napi_env env, napi_value exports)
         {"commStepUPad", fn_comm_step_upad}, {"commWideStepReserve", fn_comm_wide_step_reserve}, {"commWideStepBegin", fn_comm_wide_step_begin},
         {"commWideStepFinish", fn_comm_wide_step_finish}, {"commWideStepCollect", fn_comm_wide_step_collect},
         {"commWideStepStatus", fn_comm_wide_step_status}, {"commWideStepReadGathered", fn_comm_wide_step_read}, {"commExpiredQueue", fn_comm_expired_queue}, {"commArchiveQueue", fn_comm_archive_queue},
-        {"commAppendRows", fn_comm_append_rows}, {"commSetEnd", fn_comm_set_end}, {"commDeleteUser", fn_comm_delete_user}, {"commTableSize", fn_comm_table_size},
+        {"commAppendRows", fn_comm_append_rows}, {"commSetEnd", fn_comm_set_end}, {"commDeleteUser", fn_comm_delete_user}, {"commDeleteUsers", fn_comm_delete_users}, {"commTableSize", fn_comm_table_size},
         {"shardMaps", fn_shard_maps},
         {"tokenSet", fn_token_set}, {"tokenAppend", fn_token_append}, {"tokenLookup", fn_token_lookup}, {"tokenSetEnd", fn_token_set_end},
         {"commTokenSet", fn_comm_token_set}, {"commTokenAppend", fn_comm_token_append}, {"commTokenLookup", fn_comm_token_lookup},

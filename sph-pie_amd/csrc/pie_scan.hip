@@ -4206,6 +4206,125 @@ int pie_delete_user(pie_ctx* c, int32_t user, int32_t* rows_out, size_t cap, siz
     return run_row_list<1>(c, (long long)user, 0, rows_out, cap, n_deleted);
 }
 
+int pie_delete_users_plan(const int32_t* users, size_t k, int32_t n_users, uint64_t* bits_out, uint8_t* first_out)
+{
+    if (k && (!users || !first_out)) return PIE_E_INVAL;
+    if (n_users > 0 && !bits_out) return PIE_E_INVAL;
+    const size_t words = n_users > 0 ? ((size_t)n_users + 63) / 64 : 0;
+    for (size_t w = 0; w < words; ++w) bits_out[w] = 0;
+    for (size_t i = 0; i < k; ++i) {
+        const int32_t u = users[i];
+        first_out[i] = 0;
+        if (u < 0 || u >= n_users) continue;
+        const uint64_t bit = 1ull << (u & 63);
+        if (bits_out[u >> 6] & bit) continue; // named before: the earlier element has the count
+        bits_out[u >> 6] |= bit;
+        first_out[i] = 1;
+    }
+    return PIE_OK;
+}
+
+// pie_delete_users / pie_shard_delete_users behind their own checks: users[] are the context's own (local) ids, anything outside
+// [0, n_users) is skipped.  Leaves the ascending list in slot 0's out_idx (as global rows if to_global) and its length in
+// *m_out; per_user_out was zeroed by the caller.  Host side as run_row_list<1>: same workspace, same waits.
+static int delete_users_run(pie_ctx* c, const int32_t* users, size_t k, bool to_global, size_t* m_out, int32_t* per_user_out)
+{
+    *m_out = 0;
+    const size_t words = ((size_t)c->n_users + 63) / 64;
+    std::vector<uint64_t> bits;
+    std::vector<uint8_t> first;
+    std::vector<int32_t> ids;
+    try {
+        bits.resize(words);
+        first.resize(k);
+        if (pie_delete_users_plan(users, k, c->n_users, bits.data(), first.data()) != PIE_OK) return fail(c, PIE_E_INVAL, "bad user list");
+        for (size_t w = 0; w < words; ++w) // the distinct valid ids, ascending
+            for (uint64_t b = bits[w]; b; b &= b - 1) ids.push_back((int32_t)(w * 64 + (size_t)__builtin_ctzll(b)));
+    } catch (...) {
+        return fail(c, PIE_E_NOMEM, "no memory for %zu user ids", k);
+    }
+    const size_t d = ids.size();
+    if (d == 0) return PIE_OK; // no id the table knows: as k calls that each found the falsy-id guard
+    queue_forget(c);
+    if (c->cap_rows == 0) return fail(c, PIE_E_STATE, "no table loaded");
+    if (c->n_flight || c->b_flight) return fail(c, PIE_E_STATE, "a scan is in flight");
+    PIE_HIP(c, hipSetDevice(c->device));
+    int rc = sync_all(c); // the workspace below is shared with the scans' tails, the staging block with appends / touches
+    if (rc) return rc;
+    hipStream_t s = c->stream;
+    Slot& sl = c->slot[0];
+    sl.have_result = false;
+    if (c->res == &sl) c->res = nullptr;
+    // one upload of [bitmap | distinct ids], the per-id counters behind them
+    const size_t bits_bytes = words * 8, ids_bytes = d * 4;
+    Staged st{};
+    rc = stage_mutation(c, bits_bytes + 2 * ids_bytes, false, &st);
+    if (rc) return rc;
+    memcpy(st.h, bits.data(), bits_bytes);
+    memcpy(st.h + bits_bytes, ids.data(), ids_bytes);
+    PIE_HIP(c, hipMemcpyAsync(st.d, st.h, bits_bytes + ids_bytes, hipMemcpyHostToDevice, s));
+    const unsigned int* d_bits = reinterpret_cast<const unsigned int*>(st.d); // little-endian: bit u of the 64-bit words = bit u of these
+    const int* d_ids = reinterpret_cast<const int*>(st.d + bits_bytes);
+    unsigned int* d_cnt = reinterpret_cast<unsigned int*>(st.d + bits_bytes + ids_bytes);
+    if (per_user_out) PIE_HIP(c, hipMemsetAsync(d_cnt, 0, ids_bytes, s));
+    const int blocks = c->plan_blocks[0];
+    const long long rpb = c->plan_rows[0]; // a multiple of the streaming tile: every wave's quarter starts 16-byte aligned
+    const int n_waves = blocks * kK1Waves;
+    hipLaunchKernelGGL(k_users_pass<false>, dim3(blocks), dim3(kK1Threads), 0, s, c->d_end, (const int*)c->d_user, c->n, rpb, d_bits, c->n_users,
+                       sl.blk_count, (const long long*)nullptr, (int*)nullptr, 0LL, (lkey_t*)nullptr, (fkey_t*)nullptr, OrdMirror{}, HotMirror{});
+    hipLaunchKernelGGL(k_block_prefix_wide, dim3(1), dim3(1024), 0, s, sl.blk_count, n_waves, c->d_blk_off, &c->d_summary->m,
+                       (HostSummary*)nullptr, 0ull);
+    hipLaunchKernelGGL(k_users_pass<true>, dim3(blocks), dim3(kK1Threads), 0, s, c->d_end, (const int*)c->d_user, c->n, rpb, d_bits, c->n_users,
+                       (int*)nullptr, (const long long*)c->d_blk_off, sl.out_idx, c->cap_rows, c->d_key, c->d_fkey, ord_mirror_of(c), hot_mirror_of(c));
+    if (per_user_out)
+        hipLaunchKernelGGL(k_users_tally, dim3(capped_grid(c, (size_t)c->n)), dim3(256), 0, s, (const int*)sl.out_idx,
+                           (const unsigned long long*)&c->d_summary->m, c->cap_rows, (const int*)c->d_user, d_ids, (int)d, d_cnt);
+    PIE_HIP(c, hipGetLastError());
+    PIE_HIP(c, hipMemcpyAsync(c->h_summary, c->d_summary, sizeof(Summary), hipMemcpyDeviceToHost, s));
+    char* h_cnt = st.h + bits_bytes + ids_bytes;
+    if (per_user_out) PIE_HIP(c, hipMemcpyAsync(h_cnt, d_cnt, ids_bytes, hipMemcpyDeviceToHost, s));
+    PIE_HIP(c, hipStreamSynchronize(s));
+    const size_t m = (size_t)c->h_summary->m;
+    *m_out = m;
+    if (per_user_out) { // an id's count goes to its first occurrence; the later ones keep their 0
+        const unsigned int* cnt = reinterpret_cast<const unsigned int*>(h_cnt);
+        for (size_t i = 0; i < k; ++i)
+            if (first[i]) per_user_out[i] = (int32_t)cnt[std::lower_bound(ids.begin(), ids.end(), users[i]) - ids.begin()];
+    }
+    if (to_global && m) {
+        hipLaunchKernelGGL(k_shard_rows_to_global, dim3(capped_grid(c, m)), dim3(256), 0, s, (const int*)sl.out_idx, sl.out_idx, (long long)m,
+                           (const int*)c->d_shard_rows, c->n);
+        PIE_HIP(c, hipGetLastError());
+    }
+    return PIE_OK;
+}
+
+// the list delete_users_run left on the device -> rows_out (m entries)
+static int delete_users_copy(pie_ctx* c, int32_t* rows_out, size_t m)
+{
+    if (!rows_out || m == 0) return PIE_OK;
+    PIE_HIP(c, hipMemcpyAsync(rows_out, c->slot[0].out_idx, m * 4, hipMemcpyDeviceToHost, c->stream));
+    PIE_HIP(c, hipStreamSynchronize(c->stream));
+    return PIE_OK;
+}
+
+int pie_delete_users(pie_ctx* c, const int32_t* users, size_t k, int32_t* rows_out, size_t cap, size_t* n_deleted, int32_t* per_user_out)
+{
+    if (!c) return PIE_E_INVAL;
+    if (n_deleted) *n_deleted = 0;
+    if (k == 0) return PIE_OK;
+    if (!users) return fail(c, PIE_E_INVAL, "NULL user list");
+    if (per_user_out) memset(per_user_out, 0, k * 4);
+    if (c->n == 0) return PIE_OK;
+    size_t m = 0;
+    int rc = delete_users_run(c, users, k, false, &m, per_user_out);
+    if (rc) return rc;
+    if (n_deleted) *n_deleted = m;
+    // the rows are tombstoned even when rows_out is too small to list them (PIE_E_CAPACITY then tells the count)
+    if (rows_out && m > cap) return fail(c, PIE_E_CAPACITY, "list cap %zu < %zu", cap, m);
+    return delete_users_copy(c, rows_out, m);
+}
+
 int pie_prune_before(pie_ctx* c, int64_t cutoff, int32_t* rows_out, size_t cap, size_t* n_pruned)
 {
     if (!c) return PIE_E_INVAL;
@@ -5897,6 +6016,62 @@ int pie_shard_delete_user(pie_ctx* c, int32_t user_global, int32_t* rows_global_
     PIE_HIP(c, hipMemcpyAsync(rows_global_out, list, k * 4, hipMemcpyDeviceToHost, s));
     PIE_HIP(c, hipStreamSynchronize(s));
     return PIE_OK;
+}
+
+} // extern "C"
+
+// pie_shard_delete_users in the pieces the communicator needs: the check, the run that leaves the ascending list of GLOBAL rows
+// on the device (its length in *m_out), and the copy of that list.
+namespace pie_internal {
+int shard_check_delete_users(pie_ctx* c, const int32_t* users_global, size_t k)
+{
+    if (!c) return PIE_E_INVAL;
+    int rc = shard_ready(c, "pie_shard_delete_users");
+    if (rc) return rc;
+    if (k > 0 && !users_global) return fail(c, PIE_E_INVAL, "NULL user list");
+    return PIE_OK;
+}
+
+int shard_delete_users_run(pie_ctx* c, const int32_t* users_global, size_t k, size_t* m_out, int32_t* per_user_out)
+{
+    *m_out = 0;
+    int rc = shard_check_delete_users(c, users_global, k);
+    if (rc || k == 0) return rc;
+    if (per_user_out) memset(per_user_out, 0, k * 4);
+    if (c->n == 0) return PIE_OK;
+    // unknown ids, other shards' users and ids the map does not hold: skipped (-1), like the falsy-id guard (sessionStore.js:56-58)
+    const std::vector<int32_t>& um = c->shard_users_h;
+    std::vector<int32_t> local;
+    try {
+        local.assign(k, -1);
+    } catch (...) {
+        return fail(c, PIE_E_NOMEM, "no memory for %zu user ids", k);
+    }
+    for (size_t i = 0; i < k; ++i) {
+        const int32_t g = users_global[i];
+        if (g < 0 || g >= c->shard_users_global || pie_shard_of(g, c->shard_world) != c->shard_rank) continue;
+        const auto it = std::lower_bound(um.begin(), um.end(), g);
+        if (it != um.end() && *it == g) local[i] = (int32_t)(it - um.begin());
+    }
+    return delete_users_run(c, local.data(), k, true, m_out, per_user_out);
+}
+
+int shard_delete_users_copy(pie_ctx* c, int32_t* rows_global_out, size_t m) { return delete_users_copy(c, rows_global_out, m); }
+} // namespace pie_internal
+
+extern "C" {
+
+int pie_shard_delete_users(pie_ctx* c, const int32_t* users_global, size_t k, int32_t* rows_global_out, size_t cap, size_t* n_deleted,
+                           int32_t* per_user_out)
+{
+    if (!c) return PIE_E_INVAL;
+    if (n_deleted) *n_deleted = 0;
+    size_t m = 0;
+    int rc = pie_internal::shard_delete_users_run(c, users_global, k, &m, per_user_out);
+    if (rc) return rc;
+    if (n_deleted) *n_deleted = m;
+    if (rows_global_out && m > cap) return fail(c, PIE_E_CAPACITY, "list cap %zu < %zu", cap, m); // the rows are tombstoned all the same
+    return delete_users_copy(c, rows_global_out, m);
 }
 
 static int shard_translate(pie_ctx* c, int32_t* rows_inout, size_t k, bool to_local, const char* what)

@@ -296,6 +296,35 @@ function createStore(options){
     }
   }
 
+  // deleteSessionsForUser for a whole set of users (a bulk log-out, the resets of one turn): falsy and unknown ids are dropped,
+  // the rest is ONE device call with two table passes whatever their number; the row list keeps the host map exact.
+  // -> sessions deleted
+  function deleteSessionsForUsers(userIds){
+    const known = [];
+    for(const userId of userIds || []){
+      if(!userId){
+        continue;
+      }
+      const u = userIndex.get(userId);
+      if(u !== undefined){
+        known.push(u);
+      }
+    }
+    if(known.length === 0){
+      return 0;
+    }
+    noBase('deleteSessionsForUsers');
+    flush();
+    const list = rowList();
+    const k = native.deleteUsers(ctx, Int32Array.from(known), list);
+    generation++;                                   // the call drops the device's last scan result even when k == 0
+    for(let i = 0; i < k; i++){
+      forget(list[i]);
+      retire(list[i]);
+    }
+    return k;
+  }
+
   // full-table scan on the device; `now` is sampled once (:67).  The device returns the rows that died since the
   // previous purge (prev < end <= now); rows that died earlier were already dropped from the map.
   function purgeExpiredSessions(){
@@ -497,7 +526,7 @@ function createStore(options){
   }
 
   return {
-    createSession, getSession, touchSession, deleteSession, deleteSessionsForUser, purgeExpiredSessions, purgeRetention,
+    createSession, getSession, touchSession, deleteSession, deleteSessionsForUser, deleteSessionsForUsers, purgeExpiredSessions, purgeRetention,
     SESSION_TTL_MS, SESSION_COOKIE_NAME,
     scanFeeds, scanDevice, userFeed, scanBatchDevice, batchUserFeed, batchFetch, BATCH_MAX, scanWideDevice, WIDE_MAX, fetchRows, expiredRows, archivedRows, flush, close, save, restore,
     compact, compactDevice, compactions: () => compactions, tableRows: () => base + rows.length, baseRows: () => base,
@@ -525,6 +554,7 @@ module.exports = {
   touchSession: token => store().touchSession(token),
   deleteSession: token => store().deleteSession(token),
   deleteSessionsForUser: userId => store().deleteSessionsForUser(userId),
+  deleteSessionsForUsers: userIds => store().deleteSessionsForUsers(userIds),
   purgeExpiredSessions: () => store().purgeExpiredSessions(),
   SESSION_TTL_MS,
   SESSION_COOKIE_NAME,

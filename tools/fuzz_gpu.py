@@ -76,8 +76,15 @@ while time.time() < t_end:
                     ne[: rows.size // 8] = INT64_MIN
                     ctx.set_end(rows, ne)
                     e[rows] = ne
-                elif r < 0.3:
+                elif r < 0.25:
                     gone = ctx.delete_user(int(rng.integers(U)))
+                    e[gone] = INT64_MIN
+                elif r < 0.3:   # a set of users in one call: repeats and ids outside the table among them
+                    ids = rng.integers(-1, U + 1, int(rng.integers(1, 40))).astype(np.int32)
+                    gone, per = ctx.delete_users(ids)
+                    want = np.nonzero(np.isin(u, ids[(ids >= 0) & (ids < U)]) & (e != INT64_MIN))[0]
+                    if not np.array_equal(gone, want) or int(per.sum()) != want.size:
+                        raise SystemExit("delete_users differs from the model (%s)" % what)
                     e[gone] = INT64_MIN
                 elif r < 0.4 and n < 400000:
                     k = int(rng.integers(1, 3000))
