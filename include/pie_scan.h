@@ -644,6 +644,37 @@ int pie_shard_token_set_end(pie_ctx *ctx, const uint64_t *tok, const int64_t *ne
 int pie_shard_token_layout(pie_ctx *ctx, size_t *covered_global_out, size_t *covered_local_out, size_t *slots_out,
                            int32_t *slot_row_out, size_t cap, uint64_t *tok_out);
 
+/* ---- token lookups WHILE SCANS AND BATCHES ARE IN FLIGHT.  A lookup only reads (the token column, the slots, end, start, user);
+ * scans and batches only read the table; every mutator is refused while they are in flight.  So these calls are allowed whenever
+ * the context has a table and a token column, whatever is in flight: single scans, batches on any lane, wide batches, batches on
+ * the ordered run, or nothing.  pie_token_lookup and the other synchronous calls keep their rules (PIE_E_STATE in flight).
+ * Up to 4 lookups may be begun and not finished; they finish in the order they were begun.  Each owns a slot: pinned and device
+ * staging and status words of its own, so the probe-bound report of one lookup is neither raised nor cleared by another call.
+ * Clock: now[i] belongs to key i (the requests of a turn carry their own Date.now()): live_out[i] = found && end[row] > now[i].
+ * What a lookup sees: the table after every append, touch, delete and pie_token_append queued on the context before its begin,
+ * with no host wait in between.  A mutator issued between its begin and its finish does not change its answer: that mutator's
+ * device work is ordered behind the lookup.  Calls that replace or free what a lookup reads (pie_load_columns*,
+ * pie_gen_synthetic*, pie_shard_table, pie_compact_rows, pie_token_set / pie_shard_token_set, an index rebuild or a longer
+ * column in pie_token_append / pie_shard_token_append, capacity growth in pie_append_rows / pie_shard_append_rows,
+ * pie_ctx_destroy) first wait on the host for the lookups begun; the results stay readable by finish, in the ids of the table
+ * the lookup was begun on.
+ * Waiting: the lookup runs on a stream of its own, ordered behind the context's stream only by an event recorded at begin.
+ * Neither call synchronises the context's stream or a lane's; finish polls the lookup's own event, bounded by
+ * PIE_WAIT_DEADLINE_MS like the wait on a scan summary (PIE_E_HIP past it; the slot is returned).
+ * PIE_E_STATE: no table; no token column; a fifth begin with four unfinished; finish with none begun, or by the other form
+ * than the begin; the shard form on a context that is not sharded.  PIE_E_INVAL: NULL tok or NULL now with k > 0; k >= 2^31.
+ * PIE_E_CAPACITY: cap < k — *k_out is set and the lookup stays finishable with a larger buffer.  k = 0 takes and returns a
+ * slot like any other lookup.  *k_out (may be NULL) = keys of the lookup; every output pointer may be NULL. */
+int pie_token_lookup_begin(pie_ctx *ctx, const uint64_t *tok /* [k][2] */, const int64_t *now /* [k] */, size_t k);
+int pie_token_lookup_finish(pie_ctx *ctx, int32_t *row_out, uint8_t *live_out, int32_t *user_out, int64_t *start_out,
+                            int64_t *end_out, size_t cap, size_t *k_out);
+/* lookups pie_token_lookup_begin (either form) would take now: 4 less those unfinished */
+int pie_token_lookup_room(pie_ctx *ctx);
+/* the same on a sharded context's column: rows and users answered as GLOBAL ids, as pie_shard_token_lookup answers them */
+int pie_shard_token_lookup_begin(pie_ctx *ctx, const uint64_t *tok /* [k][2] */, const int64_t *now /* [k] */, size_t k);
+int pie_shard_token_lookup_finish(pie_ctx *ctx, int32_t *row_global_out, uint8_t *live_out, int32_t *user_global_out,
+                                  int64_t *start_out, int64_t *end_out, size_t cap, size_t *k_out);
+
 /* Host only, no context, no GPU: what the batched pass stores per selected row.  A row's 64-bit query mask is
  * live[r] & win[w] & disc[d] (r: queries whose `now` lies below the row's end, w: queries whose cutoff is <= its start, d: its
  * discipline), so the pass keeps the 20-bit code r | w << 7 | d << 14 in the row's bucket slot and the tail expands it through

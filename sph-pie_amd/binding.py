@@ -206,6 +206,11 @@ _SIGS = [
     ("pie_shard_token_lookup", C.c_int, [_P, _P, C.c_size_t, C.c_int64, _P, _P, _P, _P, _P]),
     ("pie_shard_token_set_end", C.c_int, [_P, _P, _P, C.c_size_t, C.c_int64, _P]),
     ("pie_shard_token_layout", C.c_int, [_P, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), _P, C.c_size_t, _P]),
+    ("pie_token_lookup_begin", C.c_int, [_P, _P, _P, C.c_size_t]),
+    ("pie_token_lookup_finish", C.c_int, [_P, _P, _P, _P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("pie_token_lookup_room", C.c_int, [_P]),
+    ("pie_shard_token_lookup_begin", C.c_int, [_P, _P, _P, C.c_size_t]),
+    ("pie_shard_token_lookup_finish", C.c_int, [_P, _P, _P, _P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("pie_comm_token_set", C.c_int, [_P, _P, C.c_size_t]),
     ("pie_comm_token_append", C.c_int, [_P, _P, C.c_size_t]),
     ("pie_comm_token_lookup", C.c_int, [_P, _P, C.c_size_t, C.c_int64, _P, _P, _P, _P, _P, _P]),
@@ -853,6 +858,51 @@ class PieScan:
         slot_row, keys = np.empty(slots.value, np.int32), np.empty((cov.value, 2), np.uint64)
         self._check(self._lib.pie_token_layout(self._ctx, C.byref(cov), C.byref(slots), _ptr(slot_row), slots.value, _ptr(keys)))
         return cov.value, slots.value, slot_row, keys
+
+    # ---- token lookups beside scans and batches (pie_token_lookup_begin / _finish): up to four begun and not finished
+    def _token_lookup_begin(self, fn, keys, now):
+        keys = _keys(keys)
+        k = keys.shape[0]
+        now = np.ascontiguousarray(np.broadcast_to(np.asarray(now, dtype=np.int64), (k,)))  # one clock per key
+        self._check(fn(self._ctx, _ptr(keys), _ptr(now), k))
+        self._lookups = getattr(self, "_lookups", [])
+        self._lookups.append(k)   # keys of the lookups begun and not finished, oldest first: the sizes finish allocates
+
+    def _token_lookup_finish(self, fn):
+        begun = getattr(self, "_lookups", [])
+        k = begun[0] if begun else 0   # (none begun: the library refuses with PIE_E_STATE below)
+        got = C.c_size_t(0)
+        while True:
+            out = {"row": np.empty(k, np.int32), "live": np.empty(k, np.uint8), "user": np.empty(k, np.int32),
+                   "start": np.empty(k, np.int64), "end": np.empty(k, np.int64)}
+            rc = fn(self._ctx, _ptr(out["row"]), _ptr(out["live"]), _ptr(out["user"]), _ptr(out["start"]), _ptr(out["end"]), k, C.byref(got))
+            if rc != PIE_E_CAPACITY or got.value <= k:
+                break
+            k = got.value   # a lookup begun past this object (the raw ABI): the library says how many keys it carries
+        if begun and rc != PIE_E_STATE:   # the library returned the slot, finished or failed
+            begun.pop(0)
+        self._check(rc)
+        return {name: a[: got.value] for name, a in out.items()}
+
+    def token_lookup_begin(self, keys, now):
+        """Queue getSession for every key (now: one clock for all, or one per key) whatever scans and batches are in flight."""
+        self._token_lookup_begin(self._lib.pie_token_lookup_begin, keys, now)
+
+    def token_lookup_finish(self):
+        """The oldest lookup begun -> the dict token_lookup returns."""
+        return self._token_lookup_finish(self._lib.pie_token_lookup_finish)
+
+    def token_lookup_room(self):
+        """Lookups token_lookup_begin would take now."""
+        return int(self._lib.pie_token_lookup_room(self._ctx))
+
+    def shard_token_lookup_begin(self, keys, now):
+        """token_lookup_begin on a sharded context: rows and users will be answered as GLOBAL ids."""
+        self._token_lookup_begin(self._lib.pie_shard_token_lookup_begin, keys, now)
+
+    def shard_token_lookup_finish(self):
+        """The oldest lookup begun -> the dict shard_token_lookup returns."""
+        return self._token_lookup_finish(self._lib.pie_shard_token_lookup_finish)
 
     def shard_table(self, rank, world):
         """Keep only the rows of the users that hash to `rank` of `world`, users re-numbered densely.  -> (n_rows, n_users)"""

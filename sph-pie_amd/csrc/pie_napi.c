@@ -101,6 +101,11 @@
     X(int, pie_token_append, (pie_ctx *, const uint64_t *, size_t))                                                 \
     X(int, pie_token_lookup, (pie_ctx *, const uint64_t *, size_t, int64_t, int32_t *, uint8_t *, int32_t *, int64_t *, int64_t *)) \
     X(int, pie_token_set_end, (pie_ctx *, const uint64_t *, const int64_t *, size_t, int64_t, int32_t *))                \
+    X(int, pie_token_lookup_begin, (pie_ctx *, const uint64_t *, const int64_t *, size_t))                           \
+    X(int, pie_token_lookup_finish, (pie_ctx *, int32_t *, uint8_t *, int32_t *, int64_t *, int64_t *, size_t, size_t *)) \
+    X(int, pie_token_lookup_room, (pie_ctx *))                                                                       \
+    X(int, pie_scan_batch_begin, (pie_ctx *, const pie_query *, int))                                                \
+    X(int, pie_scan_batch_finish, (pie_ctx *, size_t *))                                                             \
     X(int, pie_comm_token_set, (pie_comm *, const uint64_t *, size_t))                                               \
     X(int, pie_comm_token_append, (pie_comm *, const uint64_t *, size_t))                                            \
     X(int, pie_comm_token_lookup, (pie_comm *, const uint64_t *, size_t, int64_t, int32_t *, uint8_t *, int32_t *, int64_t *, int64_t *, int32_t *)) \
@@ -185,6 +190,12 @@ typedef struct ctx_box_s {
     struct comm_box_s *parent;
     struct ctx_box_s *next;
     napi_ref comm_ref;
+    /* what this handle has begun and not finished: the keys of every token lookup (tokenLookupBegin), oldest first, and the
+     * queries of every batch (scanBatchBegin) — the sizes of the arrays their finish hands out */
+    size_t lk_k[4];
+    int lk_head, lk_n;
+    int bt_q[16];
+    int bt_head, bt_n;
 } ctx_box;
 
 static void comm_unlink_ctx(ctx_box *b);
@@ -2165,6 +2176,179 @@ static napi_value fn_token_set_end(napi_env env, napi_callback_info info)
     return out;
 }
 
+/* ---- a batch held in flight, and token lookups beside it (pie_scan_batch_begin / _finish, pie_token_lookup_begin / _finish) -----
+ * scanBatchBegin queues a batch and returns; scanBatchFinish waits for the oldest.  Between the two the turn's cookies are
+ * resolved: tokenLookupBegin queues the lookup on its own stream, tokenLookupFinish waits for it on the libuv pool (the handle is
+ * busy meanwhile, like under scanAsync) and resolves a Promise, so the event loop is never blocked by the device. */
+
+/* scanBatchBegin(ctx, nows, cutoffs, masks) -> queries begun */
+static napi_value fn_scan_batch_begin(napi_env env, napi_callback_info info)
+{
+    ARGS(4)
+    pie_ctx *ctx = get_ctx(env, argv[0]);
+    if (!ctx) return NULL;
+    ctx_box *b = get_box(env, argv[0]);
+    pie_query q[PIE_BATCH_MAX];
+    int n_q = 0;
+    if (!read_queries(env, argv[1], argv[2], argv[3], q, &n_q)) {
+        napi_throw_type_error(env, NULL, "scanBatchBegin(ctx, BigInt64Array nows, BigInt64Array cutoffs, BigUint64Array masks): 1..64 queries, equal lengths");
+        return NULL;
+    }
+    if (b->bt_n >= (int)(sizeof b->bt_q / sizeof b->bt_q[0])) return throw_state(env, "pie_scan error -6: too many batches begun and not finished");
+    int rc = p_pie_scan_batch_begin(ctx, q, n_q);
+    if (rc) return throw_pie(env, ctx, rc);
+    b->bt_q[(b->bt_head + b->bt_n) % (int)(sizeof b->bt_q / sizeof b->bt_q[0])] = n_q;
+    b->bt_n++;
+    return js_int(env, n_q);
+}
+
+/* scanBatchFinish(ctx) -> Array of M per query of the oldest batch begun; its results stay in HBM as after scanBatch */
+static napi_value fn_scan_batch_finish(napi_env env, napi_callback_info info)
+{
+    ARGS(1)
+    pie_ctx *ctx = get_ctx(env, argv[0]);
+    if (!ctx) return NULL;
+    ctx_box *b = get_box(env, argv[0]);
+    if (b->bt_n == 0) return throw_state(env, "pie_scan error -6: no batch was begun");
+    size_t m[PIE_BATCH_MAX];
+    int rc = p_pie_scan_batch_finish(ctx, m);
+    const int n_q = b->bt_q[b->bt_head];
+    b->bt_head = (b->bt_head + 1) % (int)(sizeof b->bt_q / sizeof b->bt_q[0]); /* the library dropped the batch, finished or failed */
+    b->bt_n--;
+    if (rc) return throw_pie(env, ctx, rc);
+    napi_value out;
+    CHECK(env, napi_create_array_with_length(env, (size_t)n_q, &out));
+    for (int k = 0; k < n_q; ++k) napi_set_element(env, out, (uint32_t)k, js_int(env, (int64_t)m[k]));
+    return out;
+}
+
+/* tokenLookupBegin(ctx, keys, nows BigInt64Array: one clock per key) -> k */
+static napi_value fn_token_lookup_begin(napi_env env, napi_callback_info info)
+{
+    ARGS(3)
+    pie_ctx *ctx = get_ctx(env, argv[0]);
+    if (!ctx) return NULL;
+    ctx_box *b = get_box(env, argv[0]);
+    size_t k = 0, kn = 0;
+    uint64_t *keys = token_keys(env, argv[1], &k);
+    if (!keys) return NULL;
+    int64_t *nows = typed(env, argv[2], napi_bigint64_array, &kn);
+    if (!nows || kn != k) {
+        napi_throw_type_error(env, NULL, "tokenLookupBegin(ctx, BigUint64Array keys, BigInt64Array nows): one clock per key");
+        return NULL;
+    }
+    if (b->lk_n >= 4) return throw_state(env, "pie_scan error -6: four token lookups are begun and not finished");
+    int rc = p_pie_token_lookup_begin(ctx, keys, nows, k);
+    if (rc) return throw_pie(env, ctx, rc);
+    b->lk_k[(b->lk_head + b->lk_n) % 4] = k;
+    b->lk_n++;
+    return js_int(env, (int64_t)k);
+}
+
+/* tokenLookupRoom(ctx) -> lookups tokenLookupBegin would take now */
+static napi_value fn_token_lookup_room(napi_env env, napi_callback_info info)
+{
+    ARGS(1)
+    pie_ctx *ctx = get_ctx(env, argv[0]);
+    if (!ctx) return NULL;
+    return js_int(env, p_pie_token_lookup_room(ctx));
+}
+
+typedef struct {
+    napi_async_work work;
+    napi_deferred deferred;
+    napi_ref result;
+    pie_ctx *ctx;
+    ctx_box *box;
+    size_t k;
+    int32_t *row, *user;
+    uint8_t *live;
+    int64_t *start, *end;
+    int rc;
+    char err[600];
+} lookup_job;
+
+static void lookup_exec(napi_env env, void *data)
+{
+    (void)env;
+    lookup_job *j = (lookup_job *)data;
+    j->rc = p_pie_token_lookup_finish(j->ctx, j->row, j->live, j->user, j->start, j->end, j->k, NULL);
+    if (j->rc) snprintf(j->err, sizeof j->err, "pie_scan error %d: %s", j->rc, p_pie_last_error(j->ctx));
+}
+
+static void lookup_done(napi_env env, napi_status status, void *data)
+{
+    lookup_job *j = (lookup_job *)data;
+    j->box->busy = 0;
+    napi_value out;
+    if (status != napi_ok || j->rc) {
+        napi_value msg, err, code;
+        napi_create_string_utf8(env, j->rc ? j->err : "token lookup cancelled", NAPI_AUTO_LENGTH, &msg);
+        napi_create_error(env, NULL, msg, &err);
+        napi_create_int32(env, j->rc ? j->rc : PIE_E_STATE, &code);
+        napi_set_named_property(env, err, "code", code);
+        napi_reject_deferred(env, j->deferred, err);
+    } else {
+        napi_get_reference_value(env, j->result, &out);
+        napi_resolve_deferred(env, j->deferred, out);
+    }
+    napi_delete_reference(env, j->result);
+    napi_delete_async_work(env, j->work);
+    free(j);
+}
+
+/* tokenLookupFinish(ctx) -> Promise of tokenLookup's object for the oldest lookup begun; the wait runs on the libuv pool */
+static napi_value fn_token_lookup_finish(napi_env env, napi_callback_info info)
+{
+    ARGS(1)
+    pie_ctx *ctx = get_ctx(env, argv[0]);
+    if (!ctx) return NULL;
+    ctx_box *b = get_box(env, argv[0]);
+    if (b->lk_n == 0) return throw_state(env, "pie_scan error -6: no token lookup was begun");
+    const size_t k = b->lk_k[b->lk_head];
+    lookup_job *j = (lookup_job *)calloc(1, sizeof *j);
+    if (!j) {
+        napi_throw_error(env, NULL, "out of memory");
+        return NULL;
+    }
+    napi_value out, name, promise;
+    if (napi_create_object(env, &out) != napi_ok) {
+        free(j);
+        napi_throw_error(env, NULL, "N-API call failed: result object");
+        return NULL;
+    }
+    j->ctx = ctx;
+    j->box = b;
+    j->k = k;
+    j->row = token_out(env, out, "row", napi_int32_array, 4, k);
+    j->live = token_out(env, out, "live", napi_uint8_array, 1, k);
+    j->user = token_out(env, out, "user", napi_int32_array, 4, k);
+    j->start = token_out(env, out, "start", napi_bigint64_array, 8, k);
+    j->end = token_out(env, out, "end", napi_bigint64_array, 8, k);
+    if (!j->row || !j->live || !j->user || !j->start || !j->end) {
+        free(j);
+        return NULL;
+    }
+    napi_create_string_utf8(env, "pie_token_lookup_finish", NAPI_AUTO_LENGTH, &name);
+    if (napi_create_reference(env, out, 1, &j->result) != napi_ok || napi_create_promise(env, &j->deferred, &promise) != napi_ok) {
+        free(j);
+        napi_throw_error(env, NULL, "N-API call failed: promise");
+        return NULL;
+    }
+    b->busy = 1;
+    if (napi_create_async_work(env, NULL, name, lookup_exec, lookup_done, j, &j->work) != napi_ok ||
+        napi_queue_async_work(env, j->work) != napi_ok) {
+        b->busy = 0;
+        napi_delete_reference(env, j->result);
+        free(j);
+        napi_throw_error(env, NULL, "cannot queue async work");
+        return NULL;
+    }
+    b->lk_head = (b->lk_head + 1) % 4; /* the library returns the slot whatever the wait says (cap = k: never PIE_E_CAPACITY) */
+    b->lk_n--;
+    return promise;
+}
+
 /* ---- the token column behind the communicator (pie_comm_token_*): keys as tokenLookup takes them, GLOBAL ids out ----------- */
 /* commTokenSet(comm, keys) / commTokenAppend(comm, keys) -> k */
 static napi_value comm_token_set_or_append(napi_env env, napi_callback_info info, int append)
@@ -2260,6 +2444,8 @@ static napi_value init(napi_env env, napi_value exports)
         {"tokenSet", fn_token_set}, {"tokenAppend", fn_token_append}, {"tokenLookup", fn_token_lookup}, {"tokenSetEnd", fn_token_set_end},
         {"commTokenSet", fn_comm_token_set}, {"commTokenAppend", fn_comm_token_append}, {"commTokenLookup", fn_comm_token_lookup},
         {"commTokenSetEnd", fn_comm_token_set_end},
+        {"scanBatchBegin", fn_scan_batch_begin}, {"scanBatchFinish", fn_scan_batch_finish}, {"tokenLookupBegin", fn_token_lookup_begin},
+        {"tokenLookupFinish", fn_token_lookup_finish}, {"tokenLookupRoom", fn_token_lookup_room},
     };
     for (size_t i = 0; i < sizeof table / sizeof table[0]; ++i) {
         napi_value fn;

@@ -342,6 +342,22 @@ struct pie_ctx {
         bool hold = false;
         double build_ms = 0;
         unsigned long long builds = 0;
+        // Lookups that run beside scans and batches (pie_token_lookup_begin / _finish): a stream of their own, created at the
+        // first begin, and kTokLookups slots handed out and returned in order.  A slot owns its pinned and device staging
+        // (token_flight_stage_of: keys and clocks in, results and ITS status words out) and two events: `order` is recorded on
+        // the context's stream at begin (the mutations queued so far), `done` on the lookup stream behind the results' copy.
+        struct Lookup {
+            char* h = nullptr;
+            char* d = nullptr;
+            size_t bytes = 0, k = 0;
+            hipEvent_t order = nullptr, done = nullptr;
+            bool landed = false;    // `done` was waited for (token_lookups_land): the results are in h
+            bool global = false;    // begun by the shard form: rows and users are GLOBAL ids
+        } lk[kTokLookups];
+        hipStream_t lk_stream = nullptr;
+        int lk_head = 0, lk_n = 0;  // the oldest unfinished lookup; how many are unfinished
+        bool lk_stale = false;      // a finish returned its slot without having seen `done`: the next begin drains lk_stream first
+        std::vector<std::pair<char*, char*>> lk_retired; // (pinned, device) staging a slot outgrew, until token_lookups_release
     } tokx;
     double cmp_count_ms = 0;       // ... of its count pass and prefix alone
     double cmp_write_ms = 0;       // ... of its write pass (HIP events)
@@ -697,13 +713,61 @@ OrdMirror ord_mirror_of(const pie_ctx* c)
     return m;
 }
 
+// The one wait of a lookup begun beside scans and batches (pie_token_lookup_begin): on its own event, polled and bounded like
+// the wait on a scan summary (PIE_WAIT_DEADLINE_MS) — never on the context's stream or a lane's.
+int token_lookup_landed(pie_ctx* c, pie_ctx::TokenIndex::Lookup& l, const char* what)
+{
+    if (l.landed) return PIE_OK;
+    timespec t0{};
+    clock_gettime(CLOCK_MONOTONIC, &t0);
+    for (unsigned long long spins = 0;; ++spins) {
+        const hipError_t e = hipEventQuery(l.done);
+        if (e == hipSuccess) break;
+        timespec t1{};
+        clock_gettime(CLOCK_MONOTONIC, &t1);
+        const double waited_ms = (double)(t1.tv_sec - t0.tv_sec) * 1e3 + (double)(t1.tv_nsec - t0.tv_nsec) * 1e-6;
+        if (e != hipErrorNotReady) return fail(c, PIE_E_HIP, "%s: token lookup failed: %s", what, hipGetErrorString(e));
+        if (waited_ms > c->wait_deadline_ms)
+            return fail(c, PIE_E_HIP, "%s: token lookup not finished within %.0f ms (PIE_WAIT_DEADLINE_MS): kernel hung?", what, waited_ms);
+        if (spins > 64) sched_yield();
+        else __builtin_ia32_pause();
+    }
+    l.landed = true;
+    return PIE_OK;
+}
+
+// Every lookup begun and not finished has run: its results are in its slot's pinned staging, where its finish reads them, in the
+// ids of the table it was begun on.  Whatever replaces or frees something such a lookup reads (the columns, the token column, the
+// slots, a shard's maps) calls this first; with none begun it costs nothing.
+int token_lookups_land(pie_ctx* c, const char* what)
+{
+    pie_ctx::TokenIndex& t = c->tokx;
+    for (int i = 0; i < t.lk_n; ++i) {
+        int rc = token_lookup_landed(c, t.lk[(t.lk_head + i) % kTokLookups], what);
+        if (rc) return rc;
+    }
+    return PIE_OK;
+}
+
+// the staging blocks the lookup slots outgrew: released where the context has been drained anyway (the frees wait for the device)
+void token_lookups_release(pie_ctx* c)
+{
+    for (auto& p : c->tokx.lk_retired) {
+        if (p.first) (void)hipHostFree(p.first);
+        if (p.second) (void)hipFree(p.second);
+    }
+    c->tokx.lk_retired.clear();
+}
+
 // the token column and its index go (no-op when there is none); the status array, the staging and the counters stay
 void token_drop(pie_ctx* c)
 {
     pie_ctx::TokenIndex& t = c->tokx;
     t.hold = false;
     if (!t.tok && !t.slot_row) return;
+    (void)token_lookups_land(c, "token column");
     (void)hipStreamSynchronize(c->stream);
+    token_lookups_release(c);
     dfree(t.tok);
     dfree(t.slot_row);
     t.cap = t.covered = t.covered_g = 0;
@@ -851,7 +915,11 @@ int ensure_capacity(pie_ctx* c, long long n, int n_users, long long keep_rows = 
     if (n < 0 || n >= (1LL << 31) - 1) return fail(c, PIE_E_INVAL, "row count %lld outside [0, 2^31 - 1)", n);
     if (n_users < 1) return fail(c, PIE_E_INVAL, "n_users must be >= 1 (got %d)", n_users);
     if (c->n_flight || c->b_flight) return fail(c, PIE_E_STATE, "table change while a scan is in flight");
-    int rc = sync_all(c);
+    int rc = PIE_OK;
+    // a new table, or columns that are about to move: the token lookups begun on the old ones land first
+    if (keep_rows == 0 || n > c->cap_rows || n_users > c->cap_users) rc = token_lookups_land(c, "table change");
+    if (rc) return rc;
+    rc = sync_all(c);
     if (rc) return rc;
     ord_invalidate(c, keep_rows == 0);
     if (keep_rows == 0) cmp_forget(c); // a new table (load, gen, shard, compact) renumbers the rows: the last compaction's maps go
@@ -3674,6 +3742,7 @@ int pie_ctx_destroy(pie_ctx* c)
     g_prof.report();
 #endif
     (void)hipSetDevice(c->device);
+    (void)token_lookups_land(c, "pie_ctx_destroy");
     (void)hipStreamSynchronize(c->stream);
     free_table(c);
     dfree(c->d_shard_rows);
@@ -3685,6 +3754,15 @@ int pie_ctx_destroy(pie_ctx* c)
     if (c->tokx.h_stage) (void)hipHostFree(c->tokx.h_stage);
     for (hipEvent_t e : c->tokx.ev)
         if (e) (void)hipEventDestroy(e);
+    if (c->tokx.lk_stream) (void)hipStreamSynchronize(c->tokx.lk_stream);
+    token_lookups_release(c);
+    for (auto& l : c->tokx.lk) {
+        if (l.h) (void)hipHostFree(l.h);
+        dfree(l.d);
+        if (l.order) (void)hipEventDestroy(l.order);
+        if (l.done) (void)hipEventDestroy(l.done);
+    }
+    if (c->tokx.lk_stream) (void)hipStreamDestroy(c->tokx.lk_stream);
     dfree(c->d_stage);
     if (c->h_stage) (void)hipHostFree(c->h_stage);
     for (auto& a : c->astage) {
@@ -5690,6 +5768,10 @@ static int shard_ready(pie_ctx* c, const char* what)
 static int shard_maps_reserve(pie_ctx* c, long long rows, long long users)
 {
     hipStream_t s = c->stream;
+    if (rows > c->shard_rows_cap || users > c->shard_users_cap) { // a token lookup begun earlier reads the maps that go
+        int rc = token_lookups_land(c, "map growth");
+        if (rc) return rc;
+    }
     if (rows > c->shard_rows_cap) {
         int* p = nullptr;
         PIE_HIP(c, hipMalloc(&p, (size_t)rows * 4));
@@ -6141,7 +6223,9 @@ int pie_compact_rows(pie_ctx* c, int64_t dead_before, uint32_t flags, size_t* n_
     if (c->cap_rows == 0) return fail(c, PIE_E_STATE, "no table loaded");
     if (c->n_flight || c->b_flight) return fail(c, PIE_E_STATE, "a scan is in flight");
     PIE_HIP(c, hipSetDevice(c->device));
-    int rc = sync_all(c); // queued appends and touches land first
+    int rc = token_lookups_land(c, "pie_compact_rows"); // token lookups begun on this numbering keep their answers
+    if (rc) return rc;
+    rc = sync_all(c); // queued appends and touches land first
     if (rc) return rc;
     hipStream_t s = c->stream;
     const long long n = c->n;
@@ -6477,6 +6561,7 @@ static int token_info(pie_ctx* c, pie_table_info* out)
     out->token_rows = t.tok ? (uint64_t)covered : 0u;
     out->token_bytes = (uint64_t)t.cap * sizeof(TokKey) + (t.slot_row ? (uint64_t)4 << t.log2_slots : 0u) +
                        (t.status ? kTokStatusWords * sizeof(unsigned int) : 0u) + (uint64_t)t.stage_bytes;
+    for (const auto& l : t.lk) out->token_bytes += (uint64_t)l.bytes;
     out->token_builds = t.builds;
     if (t.timed) { // the last build's device time, read once it has run
         float ms = 0.f;
@@ -6538,6 +6623,9 @@ int pie_token_append(pie_ctx* c, const uint64_t* tok, size_t k)
     const bool staged = k <= ((size_t)1 << 20);
     Staged st{};
     if (staged && (rc = stage_mutation(c, k * sizeof(TokKey), true, &st)) != PIE_OK) return rc;
+    // a longer column or a larger table of slots frees what a lookup begun earlier (pie_token_lookup_begin) reads: those land first
+    if ((c->cap_rows > t.cap || (unsigned long long)covered > ((1ull << t.log2_slots) >> 1)) && (rc = token_lookups_land(c, "pie_token_append")) != PIE_OK)
+        return rc;
     if (c->cap_rows > t.cap) {
         TokKey* nt = nullptr;
         PIE_HIP(c, hipMalloc(&nt, (size_t)c->cap_rows * sizeof(TokKey)));
@@ -6895,6 +6983,8 @@ static int shard_token_chunk(pie_ctx* c, const uint64_t* tok, size_t k)
     Staged st{};
     int rc = stage_mutation(c, k * sizeof(TokKey), true, &st);
     if (rc) return rc;
+    if ((c->cap_rows > t.cap || (unsigned long long)c->n > ((1ull << t.log2_slots) >> 1)) && (rc = token_lookups_land(c, "pie_shard_token_append")) != PIE_OK)
+        return rc;
     if (c->cap_rows > t.cap) {
         TokKey* nt = nullptr;
         PIE_HIP(c, hipMalloc(&nt, (size_t)c->cap_rows * sizeof(TokKey)));
@@ -7033,6 +7123,181 @@ int pie_shard_token_layout(pie_ctx* c, size_t* covered_global_out, size_t* cover
     int rc = shard_token_ready(c, "pie_shard_token_layout", true);
     if (rc) return rc;
     return token_layout_read(c, "pie_shard_token_layout", covered_global_out, covered_local_out, slots_out, slot_row_out, cap, tok_out);
+}
+
+// ---- lookups beside scans and batches (pie_token_lookup_begin / _finish, include/pie_scan.h).  A lookup only reads, and so do
+// scans and batches; every mutator is refused while those are in flight.  So a lookup needs no empty pipeline, only a stream, a
+// staging area and status words that are not the context's: tokx.lk.
+
+// a slot's staging for k keys: up go [keys 16 k | now 8 k | status (zeroed)], back come [status | end 8 k | start 8 k | row 4 k |
+// user 4 k | live k] — one copy each way; `row` holds the GLOBAL row in the shard form
+struct TokFlightStage {
+    size_t now, status, end, start, row, user, live, bytes;
+};
+static TokFlightStage token_flight_stage_of(size_t k)
+{
+    TokFlightStage o;
+    o.now = k * 16;
+    o.status = k * 24;
+    o.end = o.status + kTokStatusWords * sizeof(unsigned int);
+    o.start = o.end + k * 8;
+    o.row = o.start + k * 8;
+    o.user = o.row + k * 4;
+    o.live = o.user + k * 4;
+    o.bytes = (o.live + k + 15) / 16 * 16;
+    return o;
+}
+
+static int token_flight_ready(pie_ctx* c, const char* what, bool global)
+{
+    if (c->cap_rows == 0) return fail(c, PIE_E_STATE, "%s: no table loaded", what);
+    if (global) {
+        if (!c->shard_on || !c->d_shard_rows || !c->d_shard_users)
+            return fail(c, PIE_E_STATE, "%s: the context holds no sharded table (pie_shard_table)", what);
+        if (c->n != c->shard_rows_n)
+            return fail(c, PIE_E_STATE, "%s: %lld rows were added after pie_shard_table: they have no global row", what, c->n - c->shard_rows_n);
+        if (!(c->tokx.tok && c->tokx.sharded))
+            return fail(c, PIE_E_STATE, "%s: the table has no token column (pie_shard_token_set gives it one)", what);
+    } else if (!c->tokx.tok) {
+        return fail(c, PIE_E_STATE, "%s: the table has no token column (pie_token_set gives it one)", what);
+    }
+    return PIE_OK;
+}
+
+static int token_flight_begin(pie_ctx* c, const uint64_t* tok, const int64_t* now, size_t k, bool global, const char* what)
+{
+    if (!c) return PIE_E_INVAL;
+    int rc = token_flight_ready(c, what, global);
+    if (rc) return rc;
+    pie_ctx::TokenIndex& t = c->tokx;
+    if (t.lk_n >= kTokLookups) return fail(c, PIE_E_STATE, "%s: %d lookups are begun and not finished", what, t.lk_n);
+    if (k > 0 && (!tok || !now)) return fail(c, PIE_E_INVAL, "%s: NULL pointer", what);
+    if (k >= ((size_t)1 << 31)) return fail(c, PIE_E_INVAL, "%s: %zu keys in one lookup", what, k);
+    PIE_HIP(c, hipSetDevice(c->device));
+    if (!t.lk_stream) PIE_HIP(c, hipStreamCreateWithFlags(&t.lk_stream, hipStreamNonBlocking));
+    pie_ctx::TokenIndex::Lookup& l = t.lk[(t.lk_head + t.lk_n) % kTokLookups]; // free: lookups finish in the order they began
+    if (!l.order) PIE_HIP(c, hipEventCreateWithFlags(&l.order, hipEventDisableTiming));
+    if (!l.done) PIE_HIP(c, hipEventCreateWithFlags(&l.done, hipEventDisableTiming));
+    const TokFlightStage o = token_flight_stage_of(k);
+    if (t.lk_stale) { // a finish gave up on its wait: what it left on the lookup stream may still use a slot's staging
+        PIE_HIP(c, hipStreamSynchronize(t.lk_stream));
+        t.lk_stale = false;
+    }
+    if (o.bytes > l.bytes) {
+        // This slot's staging alone grows; the lookups in flight keep theirs.  The new blocks come first and the old ones are
+        // only set aside (hipFree and hipHostFree wait for the whole device, the lanes' kernels included): they are released by
+        // the next call that has drained the context anyway (token_drop, pie_ctx_destroy).  256 KiB hold 5 300 keys.
+        size_t want = l.bytes ? l.bytes : (size_t)256 << 10;
+        while (want < o.bytes) want *= 2;
+        char *nh = nullptr, *nd = nullptr;
+        PIE_HIP(c, hipHostMalloc(&nh, want, hipHostMallocDefault));
+        if (hipMalloc(&nd, want) != hipSuccess) {
+            (void)hipGetLastError();
+            (void)hipHostFree(nh);
+            return fail(c, PIE_E_NOMEM, "%s: no device memory for the staging of %zu keys", what, k);
+        }
+        try {
+            if (l.h || l.d) t.lk_retired.push_back({l.h, l.d});
+        } catch (...) {
+            (void)hipHostFree(nh);
+            (void)hipFree(nd);
+            return fail(c, PIE_E_NOMEM, "%s: out of host memory", what);
+        }
+        l.h = nh;
+        l.d = nd;
+        l.bytes = want;
+    }
+    hipStream_t s = t.lk_stream;
+    // behind the appends, touches, deletes and token appends queued so far, and behind nothing that comes later
+    PIE_HIP(c, hipEventRecord(l.order, c->stream));
+    PIE_HIP(c, hipStreamWaitEvent(s, l.order, 0));
+    if (k > 0) {
+        memcpy(l.h, tok, k * sizeof(TokKey));
+        memcpy(l.h + o.now, now, k * 8);
+        memset(l.h + o.status, 0, kTokStatusWords * sizeof(unsigned int));
+        PIE_HIP(c, hipMemcpyAsync(l.d, l.h, o.end, hipMemcpyHostToDevice, s));
+        char* d = l.d;
+        const dim3 grid((unsigned)((k + 255) / 256));
+        if (global)
+            hipLaunchKernelGGL(k_shard_token_lookup_now, grid, dim3(256), 0, s, reinterpret_cast<const TokKey*>(d),
+                               reinterpret_cast<const long long*>(d + o.now), (long long)k, (const int*)t.slot_row, t.log2_slots,
+                               (const TokKey*)t.tok, token_bound(c), (const long long*)c->d_end, (const long long*)c->d_start,
+                               (const int*)c->d_user, (const int*)c->d_shard_rows, c->shard_rows_n, (const int*)c->d_shard_users,
+                               c->shard_users_n, reinterpret_cast<int*>(d + o.row), reinterpret_cast<unsigned char*>(d + o.live),
+                               reinterpret_cast<int*>(d + o.user), reinterpret_cast<long long*>(d + o.start),
+                               reinterpret_cast<long long*>(d + o.end), reinterpret_cast<unsigned int*>(d + o.status));
+        else
+            hipLaunchKernelGGL(k_token_lookup_now, grid, dim3(256), 0, s, reinterpret_cast<const TokKey*>(d),
+                               reinterpret_cast<const long long*>(d + o.now), (long long)k, (const int*)t.slot_row, t.log2_slots,
+                               (const TokKey*)t.tok, token_bound(c), (const long long*)c->d_end, (const long long*)c->d_start,
+                               (const int*)c->d_user, reinterpret_cast<int*>(d + o.row), reinterpret_cast<unsigned char*>(d + o.live),
+                               reinterpret_cast<int*>(d + o.user), reinterpret_cast<long long*>(d + o.start),
+                               reinterpret_cast<long long*>(d + o.end), reinterpret_cast<unsigned int*>(d + o.status));
+        PIE_HIP(c, hipGetLastError());
+        PIE_HIP(c, hipMemcpyAsync(l.h + o.status, d + o.status, o.bytes - o.status, hipMemcpyDeviceToHost, s));
+    }
+    PIE_HIP(c, hipEventRecord(l.done, s));
+    // whatever is queued on the context's stream from here on (a touch, a delete, an append) runs behind this lookup's reads
+    PIE_HIP(c, hipStreamWaitEvent(c->stream, l.done, 0));
+    l.k = k;
+    l.landed = false;
+    l.global = global;
+    t.lk_n++;
+    return PIE_OK;
+}
+
+static int token_flight_finish(pie_ctx* c, int32_t* row_out, uint8_t* live_out, int32_t* user_out, int64_t* start_out, int64_t* end_out,
+                               size_t cap, size_t* k_out, bool global, const char* what)
+{
+    if (!c) return PIE_E_INVAL;
+    pie_ctx::TokenIndex& t = c->tokx;
+    if (t.lk_n == 0) return fail(c, PIE_E_STATE, "%s: no lookup was begun", what);
+    pie_ctx::TokenIndex::Lookup& l = t.lk[t.lk_head];
+    if (l.global != global) return fail(c, PIE_E_STATE, "%s: the oldest lookup was begun by the %s form", what, l.global ? "shard" : "plain");
+    const size_t k = l.k;
+    if (k_out) *k_out = k;
+    if (cap < k) return fail(c, PIE_E_CAPACITY, "%s: %zu keys, room for %zu", what, k, cap);
+    PIE_HIP(c, hipSetDevice(c->device));
+    int rc = token_lookup_landed(c, l, what);
+    t.lk_head = (t.lk_head + 1) % kTokLookups; // the slot is returned whatever the wait said
+    t.lk_n--;
+    if (rc) t.lk_stale = true; // its copy may still be pending: the next begin drains the lookup stream before it touches a slot
+    if (rc || k == 0) return rc;
+    const TokFlightStage o = token_flight_stage_of(k);
+    const char* h = l.h;
+    const unsigned int* st = reinterpret_cast<const unsigned int*>(h + o.status);
+    if (st[0] || st[1])
+        return fail(c, PIE_E_HIP, "%s: probe bound exhausted (a lookup ran %llu steps without meeting an empty slot)", what, 1ull << t.log2_slots);
+    if (row_out) memcpy(row_out, h + o.row, k * 4);
+    if (live_out) memcpy(live_out, h + o.live, k);
+    if (user_out) memcpy(user_out, h + o.user, k * 4);
+    if (start_out) memcpy(start_out, h + o.start, k * 8);
+    if (end_out) memcpy(end_out, h + o.end, k * 8);
+    return PIE_OK;
+}
+
+int pie_token_lookup_begin(pie_ctx* c, const uint64_t* tok, const int64_t* now, size_t k)
+{
+    return token_flight_begin(c, tok, now, k, false, "pie_token_lookup_begin");
+}
+
+int pie_token_lookup_finish(pie_ctx* c, int32_t* row_out, uint8_t* live_out, int32_t* user_out, int64_t* start_out, int64_t* end_out, size_t cap,
+                            size_t* k_out)
+{
+    return token_flight_finish(c, row_out, live_out, user_out, start_out, end_out, cap, k_out, false, "pie_token_lookup_finish");
+}
+
+int pie_token_lookup_room(pie_ctx* c) { return c ? kTokLookups - c->tokx.lk_n : 0; }
+
+int pie_shard_token_lookup_begin(pie_ctx* c, const uint64_t* tok, const int64_t* now, size_t k)
+{
+    return token_flight_begin(c, tok, now, k, true, "pie_shard_token_lookup_begin");
+}
+
+int pie_shard_token_lookup_finish(pie_ctx* c, int32_t* row_global_out, uint8_t* live_out, int32_t* user_global_out, int64_t* start_out,
+                                  int64_t* end_out, size_t cap, size_t* k_out)
+{
+    return token_flight_finish(c, row_global_out, live_out, user_global_out, start_out, end_out, cap, k_out, true, "pie_shard_token_lookup_finish");
 }
 
 } // extern "C"

@@ -21,6 +21,7 @@ namespace pie {
 typedef ulonglong2 TokKey; // .x = bytes 0..7, .y = bytes 8..15 of the sha256, little endian
 
 constexpr int kTokStatusWords = 4; // [0] an insert exhausted its probe bound, [1] a lookup did
+constexpr int kTokLookups = 4;     // lookups begun and not finished beside scans and batches (pie_token_lookup_begin)
 
 // 64-bit mix of a key: the splitmix64 finaliser (the one pie_shard_of applies to a user id) over k0 ^ rotl(k1, 32)
 __host__ __device__ __forceinline__ unsigned long long token_mix(unsigned long long k0, unsigned long long k1)
@@ -152,6 +153,53 @@ __global__ __launch_bounds__(256) void k_shard_token_lookup(const TokKey* __rest
         const int u = best >= 0 ? user[best] : -1;
         o_user[t] = (u >= 0 && u < n_map) ? users_map[u] : -1;
     }
+}
+
+// ---- lookups that run beside scans and batches (pie_token_lookup_begin / _finish): the same probe on a stream of the lookup's
+// own.  Each key carries its own clock (now[t]: the requests of a turn were stamped one by one) and `status` points at the status
+// words of the lookup's slot, so the report of one lookup is nobody else's.  One lane per key, a grid of ceil(k / 256) blocks that
+// come and go (no persistent grid, no LDS, no barrier): a turn's worth of keys is a handful of waves for a few microseconds, which
+// leaves the wave slots and the LDS of every CU to the batch lanes' kernels.
+__global__ __launch_bounds__(256) void k_token_lookup_now(const TokKey* __restrict__ query, const long long* __restrict__ now, long long k,
+                                                          const int* __restrict__ slot_row, unsigned log2_slots, const TokKey* __restrict__ tok,
+                                                          long long covered, const long long* __restrict__ end,
+                                                          const long long* __restrict__ start, const int* __restrict__ user,
+                                                          int* __restrict__ o_row, unsigned char* __restrict__ o_live, int* __restrict__ o_user,
+                                                          long long* __restrict__ o_start, long long* __restrict__ o_end,
+                                                          unsigned int* __restrict__ status)
+{
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= k) return;
+    const int best = token_probe(query[t], slot_row, log2_slots, tok, covered, status);
+    const long long e = best >= 0 ? end[best] : INT64_MIN;
+    o_row[t] = best;
+    o_live[t] = (best >= 0 && e > now[t]) ? 1 : 0;
+    o_end[t] = e;
+    o_start[t] = best >= 0 ? start[best] : 0;
+    o_user[t] = best >= 0 ? user[best] : -1;
+}
+
+// the shard form: the row and the user answered as GLOBAL ids through the two maps, as k_shard_token_lookup reads them
+__global__ __launch_bounds__(256) void k_shard_token_lookup_now(const TokKey* __restrict__ query, const long long* __restrict__ now, long long k,
+                                                                const int* __restrict__ slot_row, unsigned log2_slots,
+                                                                const TokKey* __restrict__ tok, long long bound, const long long* __restrict__ end,
+                                                                const long long* __restrict__ start, const int* __restrict__ user,
+                                                                const int* __restrict__ rows_map, long long n_local,
+                                                                const int* __restrict__ users_map, int n_map, int* __restrict__ o_grow,
+                                                                unsigned char* __restrict__ o_live, int* __restrict__ o_user,
+                                                                long long* __restrict__ o_start, long long* __restrict__ o_end,
+                                                                unsigned int* __restrict__ status)
+{
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= k) return;
+    const int best = token_probe(query[t], slot_row, log2_slots, tok, bound < n_local ? bound : n_local, status);
+    const long long e = best >= 0 ? end[best] : INT64_MIN;
+    o_grow[t] = best >= 0 ? rows_map[best] : -1;
+    o_live[t] = (best >= 0 && e > now[t]) ? 1 : 0;
+    o_end[t] = e;
+    o_start[t] = best >= 0 ? start[best] : 0;
+    const int u = best >= 0 ? user[best] : -1;
+    o_user[t] = (u >= 0 && u < n_map) ? users_map[u] : -1;
 }
 
 // the compaction hook: the keys of the kept covered rows, in their new places

@@ -215,7 +215,86 @@ function createFeedService(store, options){
     return bodies;
   }
 
-  return {scan, eventsForUser, eventsJsonForUser, eventsJsonForRequests, icsForUser, allFeeds, scansRun: () => scansRun,
+  // ---- a whole turn BY COOKIE on the device's token index (pie_token_*; the table's token column is the caller's to keep:
+  // native.tokenSet / tokenAppend) --------------------------------------------------------------------------------------------
+  // requests: [{token, query}] -> Promise of [{status, body}] in request order: 200 with the feed of the session's user, or 401
+  // {"error":"Authentication required"} for an unknown, expired or deleted session — getSession's rule with the request's own
+  // clock (query.now, else Date.now()).  The queries of a batch do not depend on who asks, so the batch can be queued before
+  // anybody is authenticated: with {authInFlight: true} the turn's batch is begun, the cookies are resolved by ONE
+  // tokenLookupBegin / tokenLookupFinish while it is in flight (the wait runs on the libuv pool), and the batch is finished
+  // after.  Without the option the lookup is the drained tokenLookup ahead of the batch, one call per distinct clock.  Same
+  // statuses and bytes either way.
+  const authInFlight = opts.authInFlight === true;
+  const DENIED = Buffer.from(JSON.stringify({error: 'Authentication required'}));
+  const {keysOfTokens} = require('./tokenKeys');
+  let lookupsInFlight = 0;
+  function lookupDrained(keys, nows){
+    const n = nows.length;
+    const live = new Uint8Array(n), user = new Int32Array(n);
+    const byNow = new Map();
+    nows.forEach((t, i) => { if(!byNow.has(t)){ byNow.set(t, []); } byNow.get(t).push(i); });
+    for(const [t, members] of byNow){
+      const part = new BigUint64Array(2 * members.length);
+      members.forEach((i, j) => { part[2 * j] = keys[2 * i]; part[2 * j + 1] = keys[2 * i + 1]; });
+      const got = store.native.tokenLookup(store.ctx, part, t);
+      members.forEach((i, j) => { live[i] = got.live[j]; user[i] = got.user[j]; });
+    }
+    return {live, user};
+  }
+  async function serveTurn(requests){
+    const n = requests.length;
+    const out = new Array(n);
+    if(n === 0){ return out; }
+    const ks = requests.map(r => key(r.query));
+    const keys = keysOfTokens(requests.map(r => (typeof r.token === 'string' ? r.token : '')));
+    const nows = BigInt64Array.from(ks, k => BigInt(k.now));
+    const groups = [];
+    const byKey = new Map();
+    ks.forEach((k, i) => {
+      const id = k.now + '|' + k.cutoff + '|' + k.filter;
+      let g = byKey.get(id);
+      if(g === undefined){ g = {k, members: []}; byKey.set(id, g); groups.push(g); }
+      g.members.push(i);
+    });
+    const maxQ = store.BATCH_MAX || 16;
+    let auth = null;
+    if(!authInFlight){ store.flush(); auth = lookupDrained(keys, nows); }
+    for(let at = 0; at < groups.length; at += maxQ){
+      const chunk = groups.slice(at, at + maxQ);
+      const qs = chunk.map(g => ({now: g.k.now, cutoff: g.k.cutoff, disciplines: g.k.disciplines}));
+      if(authInFlight){
+        store.scanBatchBegin(qs);
+        try{
+          if(auth === null){
+            store.native.tokenLookupBegin(store.ctx, keys, nows);
+            lookupsInFlight++;
+            auth = await store.native.tokenLookupFinish(store.ctx);
+          }
+        }finally{
+          store.scanBatchFinish();
+        }
+      }else{
+        store.scanBatchDevice(qs);
+      }
+      batchesRun++;
+      last = null;
+      const members = [];
+      chunk.forEach((g, qi) => { for(const i of g.members){ if(requests[i].token && auth.live[i] === 1){ members.push([i, qi, auth.user[i]]); } } });
+      if(members.length > 0){
+        const f = store.batchFetch(Int32Array.from(members, m => m[1]), Int32Array.from(members, m => m[2]));
+        members.forEach((m, k) => {
+          const a = Number(f.off[k]), b = Number(f.off[k + 1]);
+          out[m[0]] = {status: 200, body: b === a ? Buffer.from('{"events":[]}')
+            : eventsJsonFromColumns(f.idx.subarray(a, b), f.start.subarray(a, b), f.end.subarray(a, b), f.disc.subarray(a, b))};
+        });
+      }
+    }
+    for(let i = 0; i < n; i++){ if(out[i] === undefined){ out[i] = {status: 401, body: DENIED}; } }
+    return out;
+  }
+
+  return {serveTurn, authInFlight: () => authInFlight, lookupsInFlight: () => lookupsInFlight,
+    scan, eventsForUser, eventsJsonForUser, eventsJsonForRequests, icsForUser, allFeeds, scansRun: () => scansRun,
     batchesRun: () => batchesRun, timing: () => Object.assign({}, timing)};
 }
 

@@ -35,7 +35,10 @@ function sendJson(res, status, body){
 function createServer(options){
   const store = options.store;
   const findUserById = options.findUserById;
-  const feeds = options.feeds || createFeedService(store, options);
+  // PIE_AUTH_IN_FLIGHT=1: the feed service resolves a turn's cookies while the turn's batch is in flight (feedService.serveTurn)
+  const feedOptions = options.authInFlight === undefined && process.env.PIE_AUTH_IN_FLIGHT === '1'
+    ? Object.assign({}, options, {authInFlight: true}) : options;
+  const feeds = options.feeds || createFeedService(store, feedOptions);
   const drone = disciplineConfig.findDiscipline('drones') || disciplineConfig.DEFAULT_DISCIPLINE;
   const readRoles = new Set(['lead', 'operator', 'crew'].map(lv => (drone ? disciplineConfig.getRoleKey(drone.id, lv) : null)).filter(Boolean));
 
@@ -118,7 +121,7 @@ function createServer(options){
     return sendJson(res, 200, {events});
   }
 
-  return http.createServer((req, res) => {
+  const server = http.createServer((req, res) => {
     try{
       const path = (req.url || '').split('?')[0];
       if(req.method === 'GET' && path === '/api/calendar'){
@@ -149,6 +152,8 @@ function createServer(options){
       return sendJson(res, status, payload);
     }
   });
+  server.feeds = feeds;   // the feed service behind the routes (its options included: feeds.authInFlight())
+  return server;
 }
 
 module.exports = {createServer, readSessionToken};

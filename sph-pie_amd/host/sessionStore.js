@@ -429,6 +429,15 @@ function createStore(options){
     if(queries.length < 1 || queries.length > BATCH_MAX){ throw new Error('a batch holds 1..' + BATCH_MAX + ' queries'); }
     return scanQueries(queries, 'scanBatch');
   }
+  // the same batch held IN FLIGHT: begin queues it and returns, finish waits for the oldest one begun.  Between the two the
+  // device takes token lookups (native.tokenLookupBegin / tokenLookupFinish) and nothing else of this store.
+  function scanBatchBegin(queries){
+    if(queries.length < 1 || queries.length > BATCH_MAX){ throw new Error('a batch holds 1..' + BATCH_MAX + ' queries'); }
+    return scanQueries(queries, 'scanBatchBegin');
+  }
+  function scanBatchFinish(){
+    return native.scanBatchFinish(ctx);
+  }
   // a WIDE batch (pie_scan_wide_*): up to WIDE_MAX queries in one table pass; batchUserFeed / batchFetch then take qi < WIDE_MAX
   const WIDE_MAX = 512;
   function scanWideDevice(queries){
@@ -528,7 +537,7 @@ function createStore(options){
   return {
     createSession, getSession, touchSession, deleteSession, deleteSessionsForUser, deleteSessionsForUsers, purgeExpiredSessions, purgeRetention,
     SESSION_TTL_MS, SESSION_COOKIE_NAME,
-    scanFeeds, scanDevice, userFeed, scanBatchDevice, batchUserFeed, batchFetch, BATCH_MAX, scanWideDevice, WIDE_MAX, fetchRows, expiredRows, archivedRows, flush, close, save, restore,
+    scanFeeds, scanDevice, userFeed, scanBatchDevice, scanBatchBegin, scanBatchFinish, batchUserFeed, batchFetch, BATCH_MAX, scanWideDevice, WIDE_MAX, fetchRows, expiredRows, archivedRows, flush, close, save, restore,
     compact, compactDevice, compactions: () => compactions, tableRows: () => base + rows.length, baseRows: () => base,
     userIds: () => userIds,
     userIndexOf: userId => (userIndex.has(userId) ? userIndex.get(userId) : -1),
