@@ -429,6 +429,9 @@ typedef struct pie_table_info {
     uint64_t token_bytes;     /* device memory of the token column (16 B per row of capacity), its index (4 B per slot) and the lookup staging */
     uint64_t token_builds;    /* times the index was built from the column (pie_token_set, growth, compaction) */
     double token_build_ms;    /* device time of the last such build (HIP events around the fill and the insert pass) */
+    /* fields below were added with the in-flight expired queue (pie_expired_queue_begin), under the same rule */
+    uint64_t expired_inflight_bytes; /* device memory of its scratch (one count and one offset per unit) and its queue buffer */
+    double expired_inflight_ms;      /* device time of the last pass that has run (HIP events on its own stream) */
 } pie_table_info;
 int pie_table_info_get(pie_ctx *ctx, pie_table_info *out);
 /* The hot index's layout, for tests and tools (host-only readers; not while a scan is in flight).  The index groups the rows
@@ -675,7 +678,43 @@ int pie_shard_token_lookup_begin(pie_ctx *ctx, const uint64_t *tok /* [k][2] */,
 int pie_shard_token_lookup_finish(pie_ctx *ctx, int32_t *row_global_out, uint8_t *live_out, int32_t *user_global_out,
                                   int64_t *start_out, int64_t *end_out, size_t cap, size_t *k_out);
 
-/* Host only, no context, no GPU: what the batched pass stores per selected row.  A row's 64-bit query mask is
+/* ---- the expired queue WHILE SCANS AND BATCHES ARE IN FLIGHT.  pie_expired_queue borrows the scan slots' workspace and is
+ * refused in flight; this form has a stream, scratch, a queue buffer and a summary of its own, and only reads the table.  So the
+ * calls are allowed whenever the context has a table, whatever is in flight: single scans, batches on any lane, wide batches,
+ * batches on the ordered run, token lookups, or nothing.  pie_expired_queue keeps its rules.
+ * Result: exactly the queue pie_expired_queue(prev_now, now) returns on the same table — ascending rows with
+ * prev_now < end <= now (prev_now >= now: empty).  The shard form answers in GLOBAL rows through the shard's row map.
+ * One queue may be begun and not finished.  It touches neither the scan slots, nor the finished scan's or batch's result and its
+ * readers, nor the queue pie_queue_info / pie_queue_pack_device / pie_comm_*_queue know, nor the profiling ring, nor pie_stats.
+ * What it sees: the table after every append, touch and delete queued on the context before its begin, with no host wait.  A
+ * mutator issued between begin and finish does not change the answer: its device work is ordered behind the pass.  Calls that
+ * replace or free what the pass reads (pie_load_columns*, pie_gen_synthetic*, pie_shard_table, pie_compact_rows, capacity growth
+ * in pie_append_rows / pie_shard_append_rows, a rebuild of the key columns, pie_ctx_destroy) first wait on the host for it; the
+ * result stays readable by finish, in the ids of the table it was begun on.
+ * Buffer: the pass writes into a device buffer of its own, cap_rows x 4 B, kept between calls and reallocated only when a begin
+ * asks for more.  cap_rows = 0 counts only.  *q_out (may be NULL) is always the true length.
+ *   finish with queue_out != NULL and cap < the begin's cap_rows: PIE_E_INVAL, nothing consumed.
+ *   a queue longer than cap_rows (> 0): its first cap_rows rows are copied — a true ascending prefix — and finish returns
+ *   PIE_E_CAPACITY with *q_out set; the pass is consumed, the caller begins again with room.
+ * Waiting: the pass runs on a stream of its own, ordered behind the context's stream only by an event recorded at begin.
+ * Neither call synchronises the context's stream or a lane's; finish polls the pass's summary word, bounded by
+ * PIE_WAIT_DEADLINE_MS (PIE_E_HIP past it; the pass is consumed).
+ * PIE_E_STATE: no table; a second begin; finish with none begun, or by the other form than the begin; the shard form on a
+ * context that is not sharded or whose row map does not cover its rows.  PIE_E_INVAL: NULL context; cap_rows >= 2^31.
+ * An empty table gives PIE_OK and an empty queue. */
+int pie_expired_queue_begin(pie_ctx *ctx, int64_t prev_now, int64_t now, size_t cap_rows);
+int pie_expired_queue_finish(pie_ctx *ctx, int32_t *queue_out, size_t cap, size_t *q_out);
+/* queues pie_expired_queue_begin (either form) would take now: 1 or 0; PIE_E_INVAL for a NULL context */
+int pie_expired_queue_room(pie_ctx *ctx);
+int pie_shard_expired_queue_begin(pie_ctx *ctx, int64_t prev_now, int64_t now, size_t cap_rows);
+int pie_shard_expired_queue_finish(pie_ctx *ctx, int32_t *rows_global_out, size_t cap, size_t *q_out);
+/* Host only, for tests: how the pass cuts a table of n rows on this context's device — the rows a wave reads per step, the rows
+ * of a unit (the contiguous range one wave walks alone; the pass has ceil(n / rows_per_unit) of them) and the blocks of its
+ * grid (four waves each, units taken grid-stride).  Any output may be NULL.  PIE_E_INVAL: NULL context, n >= 2^31 - 1. */
+int pie_expired_inflight_geometry(pie_ctx *ctx, size_t n, int32_t *rows_per_wave_step_out, int64_t *rows_per_unit_out,
+                                  int32_t *blocks_out);
+
+/* Host only, no context, no GPU: what the batched pass stores per selected row. A row's 64-bit query mask is
  * live[r] & win[w] & disc[d] (r: queries whose `now` lies below the row's end, w: queries whose cutoff is <= its start, d: its
  * discipline), so the pass keeps the 20-bit code r | w << 7 | d << 14 in the row's bucket slot and the tail expands it through
  * the batch's tables.  For every given row: code_out = that code, mask_out = the code expanded through the tables the host

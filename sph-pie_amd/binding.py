@@ -36,6 +36,7 @@ class PieTableInfo(C.Structure):
         ("compact_bytes", C.c_uint64), ("compactions", C.c_uint64), ("compact_count_ms", C.c_double), ("compact_write_ms", C.c_double),
         ("hot_build_ms", C.c_double), ("hot_order", C.c_uint32), ("hot_slot_bits", C.c_uint32),
         ("token_rows", C.c_uint64), ("token_bytes", C.c_uint64), ("token_builds", C.c_uint64), ("token_build_ms", C.c_double),
+        ("expired_inflight_bytes", C.c_uint64), ("expired_inflight_ms", C.c_double),
     ]
 
 
@@ -211,6 +212,12 @@ _SIGS = [
     ("pie_token_lookup_room", C.c_int, [_P]),
     ("pie_shard_token_lookup_begin", C.c_int, [_P, _P, _P, C.c_size_t]),
     ("pie_shard_token_lookup_finish", C.c_int, [_P, _P, _P, _P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("pie_expired_queue_begin", C.c_int, [_P, C.c_int64, C.c_int64, C.c_size_t]),
+    ("pie_expired_queue_finish", C.c_int, [_P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("pie_expired_queue_room", C.c_int, [_P]),
+    ("pie_shard_expired_queue_begin", C.c_int, [_P, C.c_int64, C.c_int64, C.c_size_t]),
+    ("pie_shard_expired_queue_finish", C.c_int, [_P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("pie_expired_inflight_geometry", C.c_int, [_P, C.c_size_t, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     ("pie_comm_token_set", C.c_int, [_P, _P, C.c_size_t]),
     ("pie_comm_token_append", C.c_int, [_P, _P, C.c_size_t]),
     ("pie_comm_token_lookup", C.c_int, [_P, _P, C.c_size_t, C.c_int64, _P, _P, _P, _P, _P, _P]),
@@ -903,6 +910,51 @@ class PieScan:
     def shard_token_lookup_finish(self):
         """The oldest lookup begun -> the dict shard_token_lookup returns."""
         return self._token_lookup_finish(self._lib.pie_shard_token_lookup_finish)
+
+    # ---- the expired queue beside scans and batches (pie_expired_queue_begin / _finish): one begun and not finished
+    def _expired_queue_begin(self, fn, prev_now, now, cap_rows):
+        cap = self.n if cap_rows is None else int(cap_rows)
+        self._check(fn(self._ctx, int(prev_now), int(now), cap))
+        self._expq_cap = cap   # the room the finish has to offer
+
+    def _expired_queue_finish(self, fn):
+        cap = getattr(self, "_expq_cap", 0)
+        out = np.empty(max(cap, 1), np.int32)
+        q = C.c_size_t(0)
+        rc = fn(self._ctx, _ptr(out) if cap else None, cap, C.byref(q))
+        if rc == PIE_E_CAPACITY:   # the queue outgrew the begin's cap_rows: its length and its first cap_rows rows go with the error
+            err = PieError(rc, self._lib.pie_last_error(self._ctx).decode())
+            err.length, err.prefix = q.value, out[:cap].copy()
+            raise err
+        self._check(rc)
+        return out[: q.value].copy() if cap else q.value
+
+    def expired_queue_begin(self, prev_now, now, cap_rows=None):
+        """Queue the expired queue (ascending rows with prev_now < end <= now) whatever scans and batches are in flight.
+        cap_rows: rows to make room for (default: every row of the table); 0 counts only."""
+        self._expired_queue_begin(self._lib.pie_expired_queue_begin, prev_now, now, cap_rows)
+
+    def expired_queue_finish(self):
+        """The queue begun -> its rows (its length when the begin said cap_rows=0).  A queue longer than the begin's cap_rows
+        raises PieError(PIE_E_CAPACITY) carrying .length and .prefix."""
+        return self._expired_queue_finish(self._lib.pie_expired_queue_finish)
+
+    def expired_queue_room(self):
+        """1 when expired_queue_begin would be taken now, 0 while one is begun and not finished."""
+        return int(self._lib.pie_expired_queue_room(self._ctx))
+
+    def shard_expired_queue_begin(self, prev_now, now, cap_rows=None):
+        """expired_queue_begin on a sharded context: the rows will be answered as GLOBAL rows."""
+        self._expired_queue_begin(self._lib.pie_shard_expired_queue_begin, prev_now, now, cap_rows)
+
+    def shard_expired_queue_finish(self):
+        return self._expired_queue_finish(self._lib.pie_shard_expired_queue_finish)
+
+    def expired_inflight_geometry(self, n):
+        """How the in-flight pass cuts a table of n rows -> (rows_per_wave_step, rows_per_unit, blocks)."""
+        step, unit, blocks = C.c_int32(0), C.c_int64(0), C.c_int32(0)
+        self._check(self._lib.pie_expired_inflight_geometry(self._ctx, int(n), C.byref(step), C.byref(unit), C.byref(blocks)))
+        return step.value, unit.value, blocks.value
 
     def shard_table(self, rank, world):
         """Keep only the rows of the users that hash to `rank` of `world`, users re-numbered densely.  -> (n_rows, n_users)"""

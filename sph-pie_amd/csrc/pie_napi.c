@@ -104,6 +104,9 @@
     X(int, pie_token_lookup_begin, (pie_ctx *, const uint64_t *, const int64_t *, size_t))                           \
     X(int, pie_token_lookup_finish, (pie_ctx *, int32_t *, uint8_t *, int32_t *, int64_t *, int64_t *, size_t, size_t *)) \
     X(int, pie_token_lookup_room, (pie_ctx *))                                                                       \
+    X(int, pie_expired_queue_begin, (pie_ctx *, int64_t, int64_t, size_t))                                           \
+    X(int, pie_expired_queue_finish, (pie_ctx *, int32_t *, size_t, size_t *))                                       \
+    X(int, pie_expired_queue_room, (pie_ctx *))                                                                      \
     X(int, pie_scan_batch_begin, (pie_ctx *, const pie_query *, int))                                                \
     X(int, pie_scan_batch_finish, (pie_ctx *, size_t *))                                                             \
     X(int, pie_comm_token_set, (pie_comm *, const uint64_t *, size_t))                                               \
@@ -196,6 +199,9 @@ typedef struct ctx_box_s {
     int lk_head, lk_n;
     int bt_q[16];
     int bt_head, bt_n;
+    /* the expired queue begun beside them (expiredQueueBegin): the rows its finish has to make room for */
+    size_t eq_cap;
+    int eq_begun;
 } ctx_box;
 
 static void comm_unlink_ctx(ctx_box *b);
@@ -2349,6 +2355,130 @@ static napi_value fn_token_lookup_finish(napi_env env, napi_callback_info info)
     return promise;
 }
 
+/* ---- the expired queue beside scans and batches (pie_expired_queue_begin / _finish / _room) ---------------------------------
+ * expiredQueueBegin queues the pass on its own stream and returns; expiredQueueFinish waits for it on the libuv pool (the handle
+ * is busy meanwhile) and resolves a Promise of the queue, so a purge tick never blocks the event loop or drains the batches. */
+
+/* expiredQueueBegin(ctx, prevNow, now, capRows) -> capRows */
+static napi_value fn_expired_queue_begin(napi_env env, napi_callback_info info)
+{
+    ARGS(4)
+    pie_ctx *ctx = get_ctx(env, argv[0]);
+    if (!ctx) return NULL;
+    ctx_box *b = get_box(env, argv[0]);
+    int64_t prev, now, cap;
+    if (!get_i64(env, argv[1], &prev) || !get_i64(env, argv[2], &now) || !get_i64(env, argv[3], &cap) || cap < 0) {
+        napi_throw_type_error(env, NULL, "expiredQueueBegin(ctx, prevNow, now, capRows)");
+        return NULL;
+    }
+    int rc = p_pie_expired_queue_begin(ctx, prev, now, (size_t)cap);
+    if (rc) return throw_pie(env, ctx, rc);
+    b->eq_cap = (size_t)cap;
+    b->eq_begun = 1;
+    return js_int(env, cap);
+}
+
+/* expiredQueueRoom(ctx) -> 1 when expiredQueueBegin would be taken now, else 0 */
+static napi_value fn_expired_queue_room(napi_env env, napi_callback_info info)
+{
+    ARGS(1)
+    pie_ctx *ctx = get_ctx(env, argv[0]);
+    if (!ctx) return NULL;
+    return js_int(env, p_pie_expired_queue_room(ctx));
+}
+
+typedef struct {
+    napi_async_work work;
+    napi_deferred deferred;
+    pie_ctx *ctx;
+    ctx_box *box;
+    size_t cap, q;
+    int32_t *rows;
+    int rc;
+    char err[600];
+} expq_job;
+
+static void expq_exec(napi_env env, void *data)
+{
+    (void)env;
+    expq_job *j = (expq_job *)data;
+    j->rc = p_pie_expired_queue_finish(j->ctx, j->cap ? j->rows : NULL, j->cap, &j->q);
+    if (j->rc) snprintf(j->err, sizeof j->err, "pie_scan error %d: %s", j->rc, p_pie_last_error(j->ctx));
+}
+
+static void expq_done(napi_env env, napi_status status, void *data)
+{
+    expq_job *j = (expq_job *)data;
+    j->box->busy = 0;
+    napi_value out = NULL, buf;
+    void *mem = NULL;
+    const size_t rows = j->q < j->cap ? j->q : j->cap;
+    int ok = status == napi_ok && !j->rc;
+    if (ok) {
+        ok = napi_create_arraybuffer(env, rows * 4, &mem, &buf) == napi_ok &&
+             napi_create_typedarray(env, napi_int32_array, rows, buf, 0, &out) == napi_ok;
+        if (ok && rows) memcpy(mem, j->rows, rows * 4);
+        if (!ok) snprintf(j->err, sizeof j->err, "N-API call failed: result array");
+    }
+    if (ok) {
+        napi_resolve_deferred(env, j->deferred, out);
+    } else {
+        napi_value msg, err, code, length;
+        napi_create_string_utf8(env, j->rc || status == napi_ok ? j->err : "expired queue cancelled", NAPI_AUTO_LENGTH, &msg);
+        napi_create_error(env, NULL, msg, &err);
+        napi_create_int32(env, j->rc ? j->rc : PIE_E_STATE, &code);
+        napi_set_named_property(env, err, "code", code);
+        if (j->rc == PIE_E_CAPACITY) { /* the true length: begin again with room for it */
+            napi_create_int64(env, (int64_t)j->q, &length);
+            napi_set_named_property(env, err, "length", length);
+        }
+        napi_reject_deferred(env, j->deferred, err);
+    }
+    napi_delete_async_work(env, j->work);
+    free(j->rows);
+    free(j);
+}
+
+/* expiredQueueFinish(ctx) -> Promise of an Int32Array: the queue begun (empty when the begin said capRows = 0; its `length`
+ * rides on the rejection when it outgrew capRows, code -5); the wait runs on the libuv pool */
+static napi_value fn_expired_queue_finish(napi_env env, napi_callback_info info)
+{
+    ARGS(1)
+    pie_ctx *ctx = get_ctx(env, argv[0]);
+    if (!ctx) return NULL;
+    ctx_box *b = get_box(env, argv[0]);
+    if (!b->eq_begun) return throw_state(env, "pie_scan error -6: no expired queue was begun");
+    expq_job *j = (expq_job *)calloc(1, sizeof *j);
+    if (j) j->rows = (int32_t *)malloc((b->eq_cap ? b->eq_cap : 1) * 4);
+    if (!j || !j->rows) {
+        free(j);
+        napi_throw_error(env, NULL, "out of memory");
+        return NULL;
+    }
+    napi_value name, promise;
+    j->ctx = ctx;
+    j->box = b;
+    j->cap = b->eq_cap;
+    napi_create_string_utf8(env, "pie_expired_queue_finish", NAPI_AUTO_LENGTH, &name);
+    if (napi_create_promise(env, &j->deferred, &promise) != napi_ok) {
+        free(j->rows);
+        free(j);
+        napi_throw_error(env, NULL, "N-API call failed: promise");
+        return NULL;
+    }
+    b->busy = 1;
+    if (napi_create_async_work(env, NULL, name, expq_exec, expq_done, j, &j->work) != napi_ok ||
+        napi_queue_async_work(env, j->work) != napi_ok) {
+        b->busy = 0;
+        free(j->rows);
+        free(j);
+        napi_throw_error(env, NULL, "cannot queue async work");
+        return NULL;
+    }
+    b->eq_begun = 0; /* the library consumes the pass whatever the wait says (cap = capRows: never PIE_E_INVAL) */
+    return promise;
+}
+
 /* ---- the token column behind the communicator (pie_comm_token_*): keys as tokenLookup takes them, GLOBAL ids out ----------- */
 /* commTokenSet(comm, keys) / commTokenAppend(comm, keys) -> k */
 static napi_value comm_token_set_or_append(napi_env env, napi_callback_info info, int append)
@@ -2446,6 +2576,7 @@ static napi_value init(napi_env env, napi_value exports)
         {"commTokenSetEnd", fn_comm_token_set_end},
         {"scanBatchBegin", fn_scan_batch_begin}, {"scanBatchFinish", fn_scan_batch_finish}, {"tokenLookupBegin", fn_token_lookup_begin},
         {"tokenLookupFinish", fn_token_lookup_finish}, {"tokenLookupRoom", fn_token_lookup_room},
+        {"expiredQueueBegin", fn_expired_queue_begin}, {"expiredQueueFinish", fn_expired_queue_finish}, {"expiredQueueRoom", fn_expired_queue_room},
     };
     for (size_t i = 0; i < sizeof table / sizeof table[0]; ++i) {
         napi_value fn;

@@ -22,6 +22,7 @@
 #include "pie_kernels.h"
 #include "pie_ordered.h"
 #include "pie_token.h"
+#include "pie_expq.h"
 
 #include <hip/hip_runtime.h>
 
@@ -359,6 +360,31 @@ struct pie_ctx {
         bool lk_stale = false;      // a finish returned its slot without having seen `done`: the next begin drains lk_stream first
         std::vector<std::pair<char*, char*>> lk_retired; // (pinned, device) staging a slot outgrew, until token_lookups_release
     } tokx;
+    // The expired queue that runs beside scans and batches (pie_expired_queue_begin / _finish): a stream, scratch (one count and
+    // one offset per unit, pie_expq_plan.h), a queue buffer and a mapped summary of its own, all created at the first begin.
+    // `order` is recorded on the context's stream at begin, `done` on the pass's stream behind its last kernel (with `t0` ahead of
+    // its first: the device time of the pass).  One pass may be begun and not finished.
+    struct ExpiredFlight {
+        hipStream_t stream = nullptr;
+        hipEvent_t order = nullptr, t0 = nullptr, done = nullptr;
+        char* d_scratch = nullptr;
+        int* d_buf = nullptr;
+        size_t buf_rows = 0;
+        HostSummary* h_sum = nullptr;
+        HostSummary* h_sum_dev = nullptr;
+        unsigned long long seq = 0;  // of the pass begun last
+        size_t cap_rows = 0;         // what its begin asked for
+        bool begun = false;
+        bool launched = false;       // it has kernels (not an empty table or an empty window)
+        bool landed = false;         // its summary was seen (expq_land): nothing of it reads the table any more
+        bool global = false;         // begun by the shard form: the buffer holds GLOBAL rows
+        bool stale = false;          // a wait gave up: the next begin drains the pass's stream first
+        bool timed = false;          // t0 / done of a pass whose time has not been read yet
+        double ms = 0;
+        int blocks_per_cu = kExpqBlocksPerCu;
+        int max_blocks = 0;          // PIE_EXPQ_MAX_BLOCKS: a cap on the grid (0: none)
+        std::vector<int*> retired;   // buffers a begin outgrew, until the context has been drained anyway
+    } expq;
     double cmp_count_ms = 0;       // ... of its count pass and prefix alone
     double cmp_write_ms = 0;       // ... of its write pass (HIP events)
 
@@ -749,6 +775,42 @@ int token_lookups_land(pie_ctx* c, const char* what)
     return PIE_OK;
 }
 
+// The one wait of the expired queue begun beside scans and batches: on ITS summary word (and its own event, for a failure), polled
+// and bounded by PIE_WAIT_DEADLINE_MS — never on the context's stream or a lane's.  Past it nothing of the pass reads the table.
+int expq_land(pie_ctx* c, const char* what)
+{
+    pie_ctx::ExpiredFlight& x = c->expq;
+    if (!x.begun || x.landed) return PIE_OK;
+    volatile unsigned long long* hs = &x.h_sum->seq;
+    timespec t0{};
+    clock_gettime(CLOCK_MONOTONIC, &t0);
+    for (unsigned long long spins = 1; *hs != x.seq; ++spins) {
+        if ((spins & 0xFF) == 0) {
+            const hipError_t e = hipEventQuery(x.done);
+            timespec t1{};
+            clock_gettime(CLOCK_MONOTONIC, &t1);
+            const double waited_ms = (double)(t1.tv_sec - t0.tv_sec) * 1e3 + (double)(t1.tv_nsec - t0.tv_nsec) * 1e-6;
+            if (e != hipSuccess && e != hipErrorNotReady) return fail(c, PIE_E_HIP, "%s: expired queue in flight failed: %s", what, hipGetErrorString(e));
+            if (e == hipSuccess && *hs != x.seq) return fail(c, PIE_E_HIP, "%s: expired queue in flight ended without its summary", what);
+            if (waited_ms > c->wait_deadline_ms)
+                return fail(c, PIE_E_HIP, "%s: expired queue in flight not finished within %.0f ms (PIE_WAIT_DEADLINE_MS): kernel hung?", what, waited_ms);
+            if (spins > 4096) sched_yield();
+        } else {
+            __builtin_ia32_pause();
+        }
+    }
+    __atomic_thread_fence(__ATOMIC_ACQUIRE);
+    x.landed = true;
+    return PIE_OK;
+}
+
+// the queue buffers a begin outgrew: released where the context has been drained anyway (hipFree waits for the device)
+void expq_release(pie_ctx* c)
+{
+    for (int* p : c->expq.retired) (void)hipFree(p);
+    c->expq.retired.clear();
+}
+
 // the staging blocks the lookup slots outgrew: released where the context has been drained anyway (the frees wait for the device)
 void token_lookups_release(pie_ctx* c)
 {
@@ -787,6 +849,7 @@ void free_table(pie_ctx* c)
 {
     for (int l = 1; l < kLaneMax; ++l) // nothing of a lane's may still be running when its arrays go
         if (c->lane_stream[l]) (void)hipStreamSynchronize(c->lane_stream[l]);
+    expq_release(c);
     dfree(c->d_union); dfree(c->d_union_cnt); dfree(c->d_union_local); dfree(c->d_union_off);
     c->union_users = 0;
     ord_free(c);
@@ -918,6 +981,8 @@ int ensure_capacity(pie_ctx* c, long long n, int n_users, long long keep_rows = 
     int rc = PIE_OK;
     // a new table, or columns that are about to move: the token lookups begun on the old ones land first
     if (keep_rows == 0 || n > c->cap_rows || n_users > c->cap_users) rc = token_lookups_land(c, "table change");
+    if (rc) return rc;
+    if (keep_rows == 0 || n > c->cap_rows || n_users > c->cap_users) rc = expq_land(c, "table change"); // ... and the expired queue begun on them
     if (rc) return rc;
     rc = sync_all(c);
     if (rc) return rc;
@@ -1092,6 +1157,8 @@ int build_keys(pie_ctx* c, long long row0, bool rebuild = false)
     if (full_build && !(rebuild && c->key_ok && c->ord.valid && c->ord.rows == c->n)) ord_invalidate(c);
     timespec tb0{};
     if (full_build) { // index_build_ms of pie_table_info: everything from here to the last key kernel's completion
+        const int land_rc = expq_land(c, "key build"); // an expired queue in flight reads the keys under the old parameters
+        if (land_rc) return land_rc;
         PIE_HIP(c, hipStreamSynchronize(s));
         clock_gettime(CLOCK_MONOTONIC, &tb0);
     }
@@ -3726,6 +3793,8 @@ int pie_ctx_create(int device_id, pie_ctx** ctx_out)
     if (const char* v = getenv("PIE_WIDE_ORDERED")) c->wide_ordered = atoi(v) == 1;
     if (const char* v = getenv("PIE_ORD_GRID")) { const int g = atoi(v); if (g >= 1 && g <= 64) c->ord.grid_mult = g; }
     if (const char* v = getenv("PIE_WAIT_DEADLINE_MS")) { const double d = atof(v); if (d > 0) c->wait_deadline_ms = d; }
+    if (const char* v = getenv("PIE_EXPQ_BLOCKS_PER_CU")) { const int g = atoi(v); if (g >= 1 && g <= 16) c->expq.blocks_per_cu = g; }
+    if (const char* v = getenv("PIE_EXPQ_MAX_BLOCKS")) { const int g = atoi(v); if (g >= 1) c->expq.max_blocks = g; }
     if (const char* v = getenv("PIE_K1_KEYED")) {
         const int k = (int)strtol(v, nullptr, 0);
         c->keyed_enabled = k != 0;
@@ -3743,6 +3812,7 @@ int pie_ctx_destroy(pie_ctx* c)
 #endif
     (void)hipSetDevice(c->device);
     (void)token_lookups_land(c, "pie_ctx_destroy");
+    (void)expq_land(c, "pie_ctx_destroy");
     (void)hipStreamSynchronize(c->stream);
     free_table(c);
     dfree(c->d_shard_rows);
@@ -3763,6 +3833,14 @@ int pie_ctx_destroy(pie_ctx* c)
         if (l.done) (void)hipEventDestroy(l.done);
     }
     if (c->tokx.lk_stream) (void)hipStreamDestroy(c->tokx.lk_stream);
+    if (c->expq.stream) (void)hipStreamSynchronize(c->expq.stream);
+    expq_release(c);
+    dfree(c->expq.d_scratch);
+    dfree(c->expq.d_buf);
+    if (c->expq.h_sum) (void)hipHostFree(c->expq.h_sum);
+    for (hipEvent_t e : {c->expq.order, c->expq.t0, c->expq.done})
+        if (e) (void)hipEventDestroy(e);
+    if (c->expq.stream) (void)hipStreamDestroy(c->expq.stream);
     dfree(c->d_stage);
     if (c->h_stage) (void)hipHostFree(c->h_stage);
     for (auto& a : c->astage) {
@@ -5398,7 +5476,8 @@ int pie_table_info_get(pie_ctx* c, pie_table_info* out)
     if (!c || !out) return PIE_E_INVAL;
     // the struct grows at its end: a caller built against the form without the compaction fields gets the fields it knows
     const uint32_t caller_size = out->struct_size;
-    if (caller_size != sizeof(pie_table_info) && caller_size != offsetof(pie_table_info, token_rows) && caller_size != offsetof(pie_table_info, hot_build_ms) &&
+    if (caller_size != sizeof(pie_table_info) && caller_size != offsetof(pie_table_info, expired_inflight_bytes) &&
+        caller_size != offsetof(pie_table_info, token_rows) && caller_size != offsetof(pie_table_info, hot_build_ms) &&
         caller_size != offsetof(pie_table_info, compact_bytes))
         return fail(c, PIE_E_INVAL, "pie_table_info.struct_size mismatch");
     pie_table_info full{};
@@ -5461,6 +5540,17 @@ int pie_table_info_get(pie_ctx* c, pie_table_info* out)
     out->compactions = c->compactions;
     out->compact_count_ms = c->cmp_count_ms;
     out->compact_write_ms = c->cmp_write_ms;
+    {
+        pie_ctx::ExpiredFlight& x = c->expq;
+        out->expired_inflight_bytes = (x.d_scratch ? (uint64_t)expq_scratch_of().bytes : 0u) + (uint64_t)x.buf_rows * 4;
+        if (x.timed && !(x.begun && !x.landed)) { // the last pass's device time, read once it has run
+            float ms = 0.f;
+            if (hipEventSynchronize(x.done) == hipSuccess && hipEventElapsedTime(&ms, x.t0, x.done) == hipSuccess) x.ms = ms;
+            else (void)hipGetLastError();
+            x.timed = false;
+        }
+        out->expired_inflight_ms = x.ms;
+    }
     const int token_rc = token_info(c, out); // a sharded column reads covered_l back: that can fail
     if (token_rc) return token_rc;
     full.struct_size = caller_size;
@@ -5633,7 +5723,9 @@ int pie_shard_table(pie_ctx* c, int32_t rank, int32_t world, size_t* n_rows_out,
     if (c->cap_rows == 0) return fail(c, PIE_E_STATE, "no table loaded");
     if (c->n_flight || c->b_flight) return fail(c, PIE_E_STATE, "a scan is in flight");
     PIE_HIP(c, hipSetDevice(c->device));
-    int rc = sync_all(c);
+    int rc = expq_land(c, "pie_shard_table"); // an expired queue begun on the whole table keeps its answer
+    if (rc) return rc;
+    rc = sync_all(c);
     if (rc) return rc;
     hipStream_t s = c->stream;
     const long long n = c->n;
@@ -5770,6 +5862,8 @@ static int shard_maps_reserve(pie_ctx* c, long long rows, long long users)
     hipStream_t s = c->stream;
     if (rows > c->shard_rows_cap || users > c->shard_users_cap) { // a token lookup begun earlier reads the maps that go
         int rc = token_lookups_land(c, "map growth");
+        if (rc) return rc;
+        rc = expq_land(c, "map growth"); // the shard form of the expired queue in flight reads the row map
         if (rc) return rc;
     }
     if (rows > c->shard_rows_cap) {
@@ -6224,6 +6318,8 @@ int pie_compact_rows(pie_ctx* c, int64_t dead_before, uint32_t flags, size_t* n_
     if (c->n_flight || c->b_flight) return fail(c, PIE_E_STATE, "a scan is in flight");
     PIE_HIP(c, hipSetDevice(c->device));
     int rc = token_lookups_land(c, "pie_compact_rows"); // token lookups begun on this numbering keep their answers
+    if (rc) return rc;
+    rc = expq_land(c, "pie_compact_rows"); // ... and so does the expired queue in flight
     if (rc) return rc;
     rc = sync_all(c); // queued appends and touches land first
     if (rc) return rc;
@@ -7298,6 +7394,187 @@ int pie_shard_token_lookup_finish(pie_ctx* c, int32_t* row_global_out, uint8_t* 
                                   int64_t* end_out, size_t cap, size_t* k_out)
 {
     return token_flight_finish(c, row_global_out, live_out, user_global_out, start_out, end_out, cap, k_out, true, "pie_shard_token_lookup_finish");
+}
+
+// ---- the expired queue beside scans and batches (pie_expired_queue_begin / _finish, include/pie_scan.h; kernels: pie_expq.h).
+// pie_expired_queue is refused in flight only because it borrows the scan slots' workspace; this form owns what it writes
+// (c->expq) and reads what scans and batches read.
+
+static int expq_begin(pie_ctx* c, int64_t prev_now, int64_t now, size_t cap_rows, bool global, const char* what)
+{
+    if (!c) return PIE_E_INVAL;
+    if (c->cap_rows == 0) return fail(c, PIE_E_STATE, "%s: no table loaded", what);
+    if (global) {
+        if (!c->shard_on || !c->d_shard_rows) return fail(c, PIE_E_STATE, "%s: the context holds no sharded table (pie_shard_table)", what);
+        if (c->n != c->shard_rows_n)
+            return fail(c, PIE_E_STATE, "%s: %lld rows were added after pie_shard_table: they have no global row", what, c->n - c->shard_rows_n);
+    }
+    pie_ctx::ExpiredFlight& x = c->expq;
+    if (x.begun) return fail(c, PIE_E_STATE, "%s: an expired queue is begun and not finished", what);
+    if (cap_rows >= ((size_t)1 << 31)) return fail(c, PIE_E_INVAL, "%s: cap_rows %zu", what, cap_rows);
+    const ExpqPlan plan = expq_plan_of(c->n, c->n_cus, x.blocks_per_cu, x.max_blocks);
+    if (plan.units < 0) return fail(c, PIE_E_INVAL, "%s: no plan for %lld rows", what, c->n);
+    PIE_HIP(c, hipSetDevice(c->device));
+    const ExpqScratch sc = expq_scratch_of();
+    if (!x.stream) PIE_HIP(c, hipStreamCreateWithFlags(&x.stream, hipStreamNonBlocking));
+    if (!x.order) PIE_HIP(c, hipEventCreateWithFlags(&x.order, hipEventDisableTiming));
+    if (!x.t0) PIE_HIP(c, hipEventCreate(&x.t0));
+    if (!x.done) PIE_HIP(c, hipEventCreate(&x.done));
+    if (!x.h_sum) {
+        HostSummary* h = nullptr;
+        PIE_HIP(c, hipHostMalloc(&h, sizeof(HostSummary), hipHostMallocMapped));
+        memset(h, 0, sizeof(HostSummary));
+        if (hipHostGetDevicePointer((void**)&x.h_sum_dev, h, 0) != hipSuccess) {
+            (void)hipGetLastError();
+            (void)hipHostFree(h);
+            return fail(c, PIE_E_HIP, "%s: no device view of the summary", what);
+        }
+        x.h_sum = h;
+    }
+    if (!x.d_scratch) {
+        char* d = nullptr;
+        if (hipMalloc(&d, sc.bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(c, PIE_E_NOMEM, "%s: no device memory for the scratch", what);
+        }
+        if (hipMemsetAsync(d + sc.ctl, 0, sc.bytes - sc.ctl, x.stream) != hipSuccess) { // the done counter; every pass leaves it at zero
+            (void)hipGetLastError();
+            (void)hipFree(d);
+            return fail(c, PIE_E_HIP, "%s: cannot clear the scratch", what);
+        }
+        x.d_scratch = d;
+    }
+    if (x.stale) { // a wait gave up on the last pass: what it left on the stream may still write the buffer
+        PIE_HIP(c, hipStreamSynchronize(x.stream));
+        x.stale = false;
+    }
+    if (cap_rows > x.buf_rows) {
+        // the new buffer comes first and the old one is only set aside: hipFree waits for the whole device, the lanes' kernels
+        // included.  It is released by the next call that has drained the context anyway (free_table, pie_ctx_destroy).
+        const size_t rows = expq_buffer_rows(x.buf_rows, cap_rows);
+        int* nb = nullptr;
+        if (hipMalloc(&nb, rows * 4) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(c, PIE_E_NOMEM, "%s: no device memory for a queue of %zu rows", what, cap_rows);
+        }
+        try {
+            if (x.d_buf) x.retired.push_back(x.d_buf);
+        } catch (...) {
+            (void)hipFree(nb);
+            return fail(c, PIE_E_NOMEM, "%s: out of host memory", what);
+        }
+        x.d_buf = nb;
+        x.buf_rows = rows;
+    }
+    x.launched = c->n > 0 && prev_now < now; // an empty table or an empty window: an empty queue, nothing to run
+    if (x.launched) {
+        hipStream_t s = x.stream;
+        // behind the appends, touches and deletes queued so far, and behind nothing that comes later
+        PIE_HIP(c, hipEventRecord(x.order, c->stream));
+        PIE_HIP(c, hipStreamWaitEvent(s, x.order, 0));
+        PIE_HIP(c, hipEventRecord(x.t0, s));
+        int* d_count = reinterpret_cast<int*>(x.d_scratch + sc.counts);
+        long long* d_off = reinterpret_cast<long long*>(x.d_scratch + sc.offsets);
+        ExpqCtl* d_ctl = reinterpret_cast<ExpqCtl*>(x.d_scratch + sc.ctl);
+        const bool keyed = c->key_ok && c->keyed_enabled && c->d_key && !getenv("PIE_EXPIRED_ON_END"); // pie_expired_queue's choice
+        const unsigned kp = keyed ? host_key_of(c, prev_now) : 0u, kn = keyed ? host_key_of(c, now) : 0u;
+        const int units = (int)plan.units;
+        const int* map = global ? (const int*)c->d_shard_rows : (const int*)nullptr;
+        const unsigned long long seq = x.seq + 1;
+        const bool count_only = cap_rows == 0;
+        const dim3 grid((unsigned)plan.blocks), block(256);
+#define PIE_EXPQ_LAUNCH(KEYED, WRITE)                                                                                                    \
+    hipLaunchKernelGGL((k_expq_pass<KEYED, WRITE>), grid, block, 0, s, (const lkey_t*)c->d_key, (const long long*)c->d_end, c->n,         \
+                       plan.rows_per_unit, units, (long long)prev_now, (long long)now, kp, kn, d_count, (const long long*)d_off, x.d_buf, \
+                       (long long)cap_rows, map, d_ctl, x.h_sum_dev, seq)
+        if (keyed) PIE_EXPQ_LAUNCH(true, false);
+        else PIE_EXPQ_LAUNCH(false, false);
+        // a counting pass ends with the prefix kernel, which then hands the length to the host itself
+        hipLaunchKernelGGL(k_block_prefix_wide, dim3(1), dim3(1024), 0, s, (const int*)d_count, units, d_off, (unsigned long long*)nullptr,
+                           count_only ? x.h_sum_dev : (HostSummary*)nullptr, seq);
+        if (!count_only) {
+            if (keyed) PIE_EXPQ_LAUNCH(true, true);
+            else PIE_EXPQ_LAUNCH(false, true);
+        }
+#undef PIE_EXPQ_LAUNCH
+        const hipError_t le = hipGetLastError();
+        // `done` and the context's wait for it are queued even behind a failed launch: what did start must not be overtaken
+        const hipError_t re = hipEventRecord(x.done, s);
+        const hipError_t we = re == hipSuccess ? hipStreamWaitEvent(c->stream, x.done, 0) : re;
+        if (le != hipSuccess || we != hipSuccess) {
+            x.stale = true;
+            return fail(c, PIE_E_HIP, "%s: %s", what, hipGetErrorString(le != hipSuccess ? le : we));
+        }
+        x.seq = seq;
+        x.timed = true;
+    }
+    x.cap_rows = cap_rows;
+    x.global = global;
+    x.landed = !x.launched;
+    x.begun = true;
+    return PIE_OK;
+}
+
+static int expq_finish(pie_ctx* c, int32_t* queue_out, size_t cap, size_t* q_out, bool global, const char* what)
+{
+    if (!c) return PIE_E_INVAL;
+    pie_ctx::ExpiredFlight& x = c->expq;
+    if (!x.begun) return fail(c, PIE_E_STATE, "%s: no expired queue was begun", what);
+    if (x.global != global) return fail(c, PIE_E_STATE, "%s: the queue was begun by the %s form", what, x.global ? "shard" : "plain");
+    if (queue_out && cap < x.cap_rows) return fail(c, PIE_E_INVAL, "%s: room for %zu rows, the begin asked for %zu", what, cap, x.cap_rows);
+    PIE_HIP(c, hipSetDevice(c->device));
+    const int rc = expq_land(c, what);
+    x.begun = false; // the pass is consumed whatever the wait said
+    if (rc) {
+        x.stale = true;
+        return rc;
+    }
+    const size_t len = x.launched ? (size_t)x.h_sum->s.m : 0;
+    if (q_out) *q_out = len;
+    const size_t rows = len < x.cap_rows ? len : x.cap_rows;
+    if (queue_out && rows) {
+        const hipError_t ce = hipMemcpyAsync(queue_out, x.d_buf, rows * 4, hipMemcpyDeviceToHost, x.stream);
+        const hipError_t se = ce == hipSuccess ? hipStreamSynchronize(x.stream) : ce; // the pass's own stream, nobody else's
+        if (se != hipSuccess) {
+            x.stale = true;
+            return fail(c, PIE_E_HIP, "%s: %s", what, hipGetErrorString(se));
+        }
+    }
+    if (x.cap_rows > 0 && len > x.cap_rows) return fail(c, PIE_E_CAPACITY, "%s: %zu rows, the begin asked for %zu", what, len, x.cap_rows);
+    return PIE_OK;
+}
+
+int pie_expired_queue_begin(pie_ctx* c, int64_t prev_now, int64_t now, size_t cap_rows)
+{
+    return expq_begin(c, prev_now, now, cap_rows, false, "pie_expired_queue_begin");
+}
+
+int pie_expired_queue_finish(pie_ctx* c, int32_t* queue_out, size_t cap, size_t* q_out)
+{
+    return expq_finish(c, queue_out, cap, q_out, false, "pie_expired_queue_finish");
+}
+
+int pie_expired_queue_room(pie_ctx* c) { return c ? (c->expq.begun ? 0 : 1) : PIE_E_INVAL; }
+
+int pie_shard_expired_queue_begin(pie_ctx* c, int64_t prev_now, int64_t now, size_t cap_rows)
+{
+    return expq_begin(c, prev_now, now, cap_rows, true, "pie_shard_expired_queue_begin");
+}
+
+int pie_shard_expired_queue_finish(pie_ctx* c, int32_t* rows_global_out, size_t cap, size_t* q_out)
+{
+    return expq_finish(c, rows_global_out, cap, q_out, true, "pie_shard_expired_queue_finish");
+}
+
+int pie_expired_inflight_geometry(pie_ctx* c, size_t n, int32_t* rows_per_wave_step_out, int64_t* rows_per_unit_out, int32_t* blocks_out)
+{
+    if (!c) return PIE_E_INVAL;
+    if (n >= (size_t)kExpqMaxRows) return fail(c, PIE_E_INVAL, "pie_expired_inflight_geometry: %zu rows", n);
+    const ExpqPlan p = expq_plan_of((long long)n, c->n_cus, c->expq.blocks_per_cu, c->expq.max_blocks);
+    if (rows_per_wave_step_out) *rows_per_wave_step_out = p.rows_per_wave_step;
+    if (rows_per_unit_out) *rows_per_unit_out = p.rows_per_unit;
+    if (blocks_out) *blocks_out = p.blocks;
+    return PIE_OK;
 }
 
 } // extern "C"

@@ -118,6 +118,19 @@ async function dispatchExpiredSessions(store, prevNow, now, send){
   return drain(store, store.expiredRows(prevNow, now), send, 'session.expired', 'session-expired-entry');
 }
 
+// The same dispatch from the asynchronous source (store.expiredRowsInFlight): the queue is computed while the store's batches
+// stay in flight; `whenIdle` (optional, may be async) runs between the queue's arrival and the first fetch of its rows — the
+// place where the caller finishes the batches it held in flight.  Same entries, same order, same summary.
+async function dispatchExpiredSessionsInFlight(store, prevNow, now, send, whenIdle){
+  let rows;
+  try{
+    rows = await store.expiredRowsInFlight(prevNow, now);
+  }finally{
+    if(whenIdle){ await whenIdle(); }
+  }
+  return drain(store, rows, send, 'session.expired', 'session-expired-entry');
+}
+
 // The reference's daily-archive trigger (/root/reference/server/storage/sqlProvider.js:758-861) on sessions: every
 // session of every user whose earliest session is at least windowMs (default 12 h = AUTO_ARCHIVE_WINDOW_MS, :9) old,
 // users in first-appearance order, dispatched one at a time.
@@ -156,5 +169,5 @@ async function drain(store, rows, send, event, kind){
   return summary;
 }
 
-module.exports = {dispatchExpiredSessions, dispatchArchivedGroups, buildExpiredSessionPayload, EXPORT_COLUMNS, buildTableRow,
+module.exports = {dispatchExpiredSessions, dispatchExpiredSessionsInFlight, dispatchArchivedGroups, buildExpiredSessionPayload, EXPORT_COLUMNS, buildTableRow,
   buildMessagePayload, csvEscape, buildCsvRow, buildEntryPayload, buildQueuePayload, queueCsv};

@@ -293,7 +293,38 @@ function createFeedService(store, options){
     return out;
   }
 
+  // ---- the purge tick: dispatch, in row order, the sessions that expired since the previous tick (prev tick's now < end <= now;
+  // dispatchQueue.js).  send(payload, meta) is the caller's transport.  By default the queue is the drained store.expiredRows.
+  // With {purgeInFlight: true} it is computed by expiredQueueBegin / expiredQueueFinish while the turn's batch (`queries`, as
+  // serveTurn builds them: [{now, cutoff, disciplines}], at most BATCH_MAX) stays in flight; the wait runs on the libuv pool, the
+  // batch is finished after, and only then are the queued rows fetched and dispatched.  Same entries either way.
+  const purgeInFlight = opts.purgeInFlight === true;
+  const dispatchQueue = require('./dispatchQueue');
+  let lastTick = null;
+  let ticksInFlight = 0;
+  async function purgeTick(now, send, queries){
+    const t = now === undefined ? Date.now() : now;
+    let summary;
+    if(purgeInFlight){
+      const qs = (queries || []).slice(0, store.BATCH_MAX || 16);
+      if(qs.length > 0){
+        store.scanBatchBegin(qs);
+        batchesRun++;
+        last = null;
+      }else{
+        store.flush();
+      }
+      ticksInFlight++;
+      summary = await dispatchQueue.dispatchExpiredSessionsInFlight(store, lastTick, t, send, () => { if(qs.length > 0){ store.scanBatchFinish(); } });
+    }else{
+      summary = await dispatchQueue.dispatchExpiredSessions(store, lastTick, t, send);
+    }
+    lastTick = t;
+    return summary;
+  }
+
   return {serveTurn, authInFlight: () => authInFlight, lookupsInFlight: () => lookupsInFlight,
+    purgeTick, purgeInFlight: () => purgeInFlight, ticksInFlight: () => ticksInFlight,
     scan, eventsForUser, eventsJsonForUser, eventsJsonForRequests, icsForUser, allFeeds, scansRun: () => scansRun,
     batchesRun: () => batchesRun, timing: () => Object.assign({}, timing)};
 }

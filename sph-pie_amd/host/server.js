@@ -36,8 +36,12 @@ function createServer(options){
   const store = options.store;
   const findUserById = options.findUserById;
   // PIE_AUTH_IN_FLIGHT=1: the feed service resolves a turn's cookies while the turn's batch is in flight (feedService.serveTurn)
-  const feedOptions = options.authInFlight === undefined && process.env.PIE_AUTH_IN_FLIGHT === '1'
+  // PIE_PURGE_IN_FLIGHT=1: its purge tick computes the expired queue while the turn's batch is in flight (feedService.purgeTick)
+  let feedOptions = options.authInFlight === undefined && process.env.PIE_AUTH_IN_FLIGHT === '1'
     ? Object.assign({}, options, {authInFlight: true}) : options;
+  if(options.purgeInFlight === undefined && process.env.PIE_PURGE_IN_FLIGHT === '1'){
+    feedOptions = Object.assign({}, feedOptions, {purgeInFlight: true});
+  }
   const feeds = options.feeds || createFeedService(store, feedOptions);
   const drone = disciplineConfig.findDiscipline('drones') || disciplineConfig.DEFAULT_DISCIPLINE;
   const readRoles = new Set(['lead', 'operator', 'crew'].map(lv => (drone ? disciplineConfig.getRoleKey(drone.id, lv) : null)).filter(Boolean));

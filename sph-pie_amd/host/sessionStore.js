@@ -410,6 +410,25 @@ function createStore(options){
     return list.slice(0, k);
   }
 
+  // The same queue WHILE BATCHES ARE IN FLIGHT (native.expiredQueueBegin / expiredQueueFinish): -> Promise of the rows.  Nothing
+  // is flushed or drained: the pass sees the table the batches in flight see (scanBatchBegin flushed before it queued them),
+  // runs on its own stream, and is waited for on the libuv pool.  capRows: the room to start with (default 4096 rows); a longer
+  // queue is begun again with room for its true length, which the rejection carries.
+  async function expiredRowsInFlight(prevNow, now, capRows){
+    noBase('expiredRowsInFlight');
+    const prev = prevNow === null || prevNow === undefined ? END_NONE : prevNow;
+    let cap = capRows === undefined ? 4096 : capRows;
+    for(;;){
+      native.expiredQueueBegin(ctx, prev, now, cap);
+      try{
+        return await native.expiredQueueFinish(ctx);
+      }catch(err){
+        if(err.code !== -5 || !(err.length > cap)){ throw err; }
+        cap = err.length;
+      }
+    }
+  }
+
   // the reference's archive chain on the session table (sqlProvider.js:758-816): rows of every user whose earliest
   // session is at least windowMs old, users in order of first appearance, rows in table order
   function archivedRows(now, windowMs){
@@ -537,7 +556,7 @@ function createStore(options){
   return {
     createSession, getSession, touchSession, deleteSession, deleteSessionsForUser, deleteSessionsForUsers, purgeExpiredSessions, purgeRetention,
     SESSION_TTL_MS, SESSION_COOKIE_NAME,
-    scanFeeds, scanDevice, userFeed, scanBatchDevice, scanBatchBegin, scanBatchFinish, batchUserFeed, batchFetch, BATCH_MAX, scanWideDevice, WIDE_MAX, fetchRows, expiredRows, archivedRows, flush, close, save, restore,
+    scanFeeds, scanDevice, userFeed, scanBatchDevice, scanBatchBegin, scanBatchFinish, batchUserFeed, batchFetch, BATCH_MAX, scanWideDevice, WIDE_MAX, fetchRows, expiredRows, expiredRowsInFlight, archivedRows, flush, close, save, restore,
     compact, compactDevice, compactions: () => compactions, tableRows: () => base + rows.length, baseRows: () => base,
     userIds: () => userIds,
     userIndexOf: userId => (userIndex.has(userId) ? userIndex.get(userId) : -1),
