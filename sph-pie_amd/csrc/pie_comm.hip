@@ -8,6 +8,7 @@
 // rank posts one ncclSend per peer and one ncclRecv per peer — each shard's message crosses its own link to each peer
 // once — rather than a ring that would bound the step by one link.
 #include "../../include/pie_scan.h"
+#include "pie_wait.h"
 
 #include <hip/hip_runtime.h>
 
@@ -18,7 +19,6 @@
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
-#include <ctime>
 #include <new>
 #include <string>
 #include <vector>
@@ -671,23 +671,13 @@ __global__ __launch_bounds__(256) void k_merge_archive(const int* __restrict__ g
 int wait_event(pie_comm* c, int k, hipEvent_t ev, const char* what)
 {
     PIE_CHIP(c, hipSetDevice(c->device[k]));
-    timespec t0{};
-    clock_gettime(CLOCK_MONOTONIC, &t0);
-    for (unsigned long long spins = 0;; ++spins) {
-        const hipError_t e = hipEventQuery(ev);
-        if (e == hipSuccess) return PIE_OK;
-        if (e != hipErrorNotReady) return cfail(c, PIE_E_HIP, "rank %d, %s: %s", c->rank_of[k], what, hipGetErrorString(e));
-        timespec t1{};
-        clock_gettime(CLOCK_MONOTONIC, &t1);
-        const double ms = (double)(t1.tv_sec - t0.tv_sec) * 1e3 + (double)(t1.tv_nsec - t0.tv_nsec) * 1e-6;
-        if (ms > c->wait_deadline_ms)
-            return cfail(c, PIE_E_HIP, "rank %d: %s not complete within %.0f ms (PIE_WAIT_DEADLINE_MS): a peer never sent?", c->rank_of[k], what, ms);
-        if (spins < 256) __builtin_ia32_pause();
-        else {
-            const timespec nap{0, 20000};
-            nanosleep(&nap, nullptr);
-        }
-    }
+    hipError_t e = hipSuccess; // the one query per spin is both the thing waited for and the probe
+    const pie::WaitResult w = pie::bounded_wait([&] { return (e = hipEventQuery(ev)) == hipSuccess; },
+                                                [&] { return e == hipErrorNotReady ? pie::kProbeNotReady : (int)e; }, c->wait_deadline_ms,
+                                                pie::kNoGraceLimit, pie::kPaceCommEvent);
+    if (w.end == pie::WaitEnd::Ready) return PIE_OK;
+    if (w.end == pie::WaitEnd::Failed) return cfail(c, PIE_E_HIP, "rank %d, %s: %s", c->rank_of[k], what, hipGetErrorString((hipError_t)w.err));
+    return cfail(c, PIE_E_HIP, "rank %d: %s not complete within %.0f ms (PIE_WAIT_DEADLINE_MS): a peer never sent?", c->rank_of[k], what, w.waited_ms);
 }
 
 void free_queue_buffers(pie_comm* c)

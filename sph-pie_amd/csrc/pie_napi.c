@@ -127,16 +127,22 @@ static void *g_lib;
         }                                                                \
     } while (0)
 
+/* an Error with `text` and a numeric `code`: what every throw, rejection and callback error of this addon is */
+static napi_value error_with_code(napi_env env, const char *text, int code)
+{
+    napi_value msg, err, num;
+    napi_create_string_utf8(env, text, NAPI_AUTO_LENGTH, &msg);
+    napi_create_error(env, NULL, msg, &err);
+    napi_create_int32(env, code, &num);
+    napi_set_named_property(env, err, "code", num);
+    return err;
+}
+
 static napi_value throw_pie(napi_env env, pie_ctx *ctx, int rc)
 {
-    napi_value msg, err, code;
     char buf[640];
     snprintf(buf, sizeof buf, "pie_scan error %d: %s", rc, p_pie_last_error ? p_pie_last_error(ctx) : "library not open");
-    napi_create_string_utf8(env, buf, NAPI_AUTO_LENGTH, &msg);
-    napi_create_error(env, NULL, msg, &err);
-    napi_create_int32(env, rc, &code);
-    napi_set_named_property(env, err, "code", code);
-    napi_throw(env, err);
+    napi_throw(env, error_with_code(env, buf, rc));
     return NULL;
 }
 
@@ -220,12 +226,7 @@ static void box_finalize(napi_env env, void *data, void *hint)
 
 static napi_value throw_state(napi_env env, const char *text)
 {
-    napi_value msg, err, code;
-    napi_create_string_utf8(env, text, NAPI_AUTO_LENGTH, &msg);
-    napi_create_error(env, NULL, msg, &err);
-    napi_create_int32(env, PIE_E_STATE, &code);
-    napi_set_named_property(env, err, "code", code);
-    napi_throw(env, err);
+    napi_throw(env, error_with_code(env, text, PIE_E_STATE));
     return NULL;
 }
 
@@ -716,6 +717,32 @@ static napi_value fn_user_feed(napi_env env, napi_callback_info info)
     return js_int(env, (int64_t)k);
 }
 
+/* A job on the libuv pool: the handle is busy from here until the job's `done` runs on the main thread.  0: nothing was queued
+ * and an error is thrown (the caller frees its job). */
+static int queue_promise_job(napi_env env, ctx_box *b, const char *name, napi_async_execute_callback exec,
+                             napi_async_complete_callback done, void *job, napi_async_work *work)
+{
+    napi_value res;
+    napi_create_string_utf8(env, name, NAPI_AUTO_LENGTH, &res);
+    b->busy = 1;
+    if (napi_create_async_work(env, NULL, res, exec, done, job, work) == napi_ok && napi_queue_async_work(env, *work) == napi_ok) return 1;
+    b->busy = 0;
+    napi_throw_error(env, NULL, "cannot queue async work");
+    return 0;
+}
+
+/* The rejection of such a job's promise: an Error with `text`, `code` (PIE_E_STATE for a job that was cancelled: rc 0) and, when
+ * the result outgrew its room (PIE_E_CAPACITY, length >= 0), the true `length`. */
+static void reject_with_code(napi_env env, napi_deferred deferred, int rc, const char *text, int64_t length)
+{
+    napi_value err = error_with_code(env, text, rc ? rc : PIE_E_STATE), len;
+    if (rc == PIE_E_CAPACITY && length >= 0) {
+        napi_create_int64(env, length, &len);
+        napi_set_named_property(env, err, "length", len);
+    }
+    napi_reject_deferred(env, deferred, err);
+}
+
 /* scanAsync(ctx, now, cutoff, counts, offsets, idx, callback(err, m)) — same scan on the libuv pool */
 typedef struct {
     napi_async_work work;
@@ -746,11 +773,7 @@ static void scan_done(napi_env env, napi_status status, void *data)
     napi_get_reference_value(env, j->cb, &cb);
     napi_get_global(env, &global);
     if (status != napi_ok || j->rc) {
-        napi_value msg, code;
-        napi_create_string_utf8(env, j->rc ? j->err : "scan cancelled", NAPI_AUTO_LENGTH, &msg);
-        napi_create_error(env, NULL, msg, &args[0]);
-        napi_create_int32(env, j->rc, &code);
-        napi_set_named_property(env, args[0], "code", code);
+        args[0] = error_with_code(env, j->rc ? j->err : "scan cancelled", j->rc);
         napi_get_undefined(env, &args[1]);
     } else {
         napi_get_null(env, &args[0]);
@@ -787,16 +810,10 @@ static napi_value fn_scan_async(napi_env env, napi_callback_info info)
         napi_throw_type_error(env, NULL, "scanAsync(ctx, now, cutoff, Int32Array[>= users], BigInt64Array[>= users + 1], Int32Array, cb)");
         return NULL;
     }
-    napi_value name;
-    napi_create_string_utf8(env, "pie_scan", NAPI_AUTO_LENGTH, &name);
     napi_create_reference(env, argv[6], 1, &j->cb);
     for (int i = 0; i < 3; ++i) napi_create_reference(env, argv[3 + i], 1, &j->keep[i]); /* keep buffers alive */
-    j->box->busy = 1;
-    if (napi_create_async_work(env, NULL, name, scan_exec, scan_done, j, &j->work) != napi_ok ||
-        napi_queue_async_work(env, j->work) != napi_ok) {
-        j->box->busy = 0;
+    if (!queue_promise_job(env, j->box, "pie_scan", scan_exec, scan_done, j, &j->work)) { /* its callback stands in for the promise */
         free(j);
-        napi_throw_error(env, NULL, "cannot queue async work");
         return NULL;
     }
     return js_int(env, 0);
@@ -1291,14 +1308,9 @@ static napi_value fn_batch_user_feed(napi_env env, napi_callback_info info)
 /* ---- communicator: the sharded table over several GPUs (pie_comm_*, RCCL behind the C ABI) -------------------------- */
 static napi_value throw_comm(napi_env env, pie_comm *cm, int rc)
 {
-    napi_value msg, err, code;
     char buf[640];
     snprintf(buf, sizeof buf, "pie_comm error %d: %s", rc, p_pie_comm_last_error ? p_pie_comm_last_error(cm) : "library not open");
-    napi_create_string_utf8(env, buf, NAPI_AUTO_LENGTH, &msg);
-    napi_create_error(env, NULL, msg, &err);
-    napi_create_int32(env, rc, &code);
-    napi_set_named_property(env, err, "code", code);
-    napi_throw(env, err);
+    napi_throw(env, error_with_code(env, buf, rc));
     return NULL;
 }
 
@@ -2288,12 +2300,7 @@ static void lookup_done(napi_env env, napi_status status, void *data)
     j->box->busy = 0;
     napi_value out;
     if (status != napi_ok || j->rc) {
-        napi_value msg, err, code;
-        napi_create_string_utf8(env, j->rc ? j->err : "token lookup cancelled", NAPI_AUTO_LENGTH, &msg);
-        napi_create_error(env, NULL, msg, &err);
-        napi_create_int32(env, j->rc ? j->rc : PIE_E_STATE, &code);
-        napi_set_named_property(env, err, "code", code);
-        napi_reject_deferred(env, j->deferred, err);
+        reject_with_code(env, j->deferred, j->rc, j->rc ? j->err : "token lookup cancelled", -1);
     } else {
         napi_get_reference_value(env, j->result, &out);
         napi_resolve_deferred(env, j->deferred, out);
@@ -2317,7 +2324,7 @@ static napi_value fn_token_lookup_finish(napi_env env, napi_callback_info info)
         napi_throw_error(env, NULL, "out of memory");
         return NULL;
     }
-    napi_value out, name, promise;
+    napi_value out, promise;
     if (napi_create_object(env, &out) != napi_ok) {
         free(j);
         napi_throw_error(env, NULL, "N-API call failed: result object");
@@ -2335,19 +2342,14 @@ static napi_value fn_token_lookup_finish(napi_env env, napi_callback_info info)
         free(j);
         return NULL;
     }
-    napi_create_string_utf8(env, "pie_token_lookup_finish", NAPI_AUTO_LENGTH, &name);
     if (napi_create_reference(env, out, 1, &j->result) != napi_ok || napi_create_promise(env, &j->deferred, &promise) != napi_ok) {
         free(j);
         napi_throw_error(env, NULL, "N-API call failed: promise");
         return NULL;
     }
-    b->busy = 1;
-    if (napi_create_async_work(env, NULL, name, lookup_exec, lookup_done, j, &j->work) != napi_ok ||
-        napi_queue_async_work(env, j->work) != napi_ok) {
-        b->busy = 0;
+    if (!queue_promise_job(env, b, "pie_token_lookup_finish", lookup_exec, lookup_done, j, &j->work)) {
         napi_delete_reference(env, j->result);
         free(j);
-        napi_throw_error(env, NULL, "cannot queue async work");
         return NULL;
     }
     b->lk_head = (b->lk_head + 1) % 4; /* the library returns the slot whatever the wait says (cap = k: never PIE_E_CAPACITY) */
@@ -2422,17 +2424,8 @@ static void expq_done(napi_env env, napi_status status, void *data)
     }
     if (ok) {
         napi_resolve_deferred(env, j->deferred, out);
-    } else {
-        napi_value msg, err, code, length;
-        napi_create_string_utf8(env, j->rc || status == napi_ok ? j->err : "expired queue cancelled", NAPI_AUTO_LENGTH, &msg);
-        napi_create_error(env, NULL, msg, &err);
-        napi_create_int32(env, j->rc ? j->rc : PIE_E_STATE, &code);
-        napi_set_named_property(env, err, "code", code);
-        if (j->rc == PIE_E_CAPACITY) { /* the true length: begin again with room for it */
-            napi_create_int64(env, (int64_t)j->q, &length);
-            napi_set_named_property(env, err, "length", length);
-        }
-        napi_reject_deferred(env, j->deferred, err);
+    } else { /* with the true length when the queue outgrew its room: begin again with room for it */
+        reject_with_code(env, j->deferred, j->rc, j->rc || status == napi_ok ? j->err : "expired queue cancelled", (int64_t)j->q);
     }
     napi_delete_async_work(env, j->work);
     free(j->rows);
@@ -2455,24 +2448,19 @@ static napi_value fn_expired_queue_finish(napi_env env, napi_callback_info info)
         napi_throw_error(env, NULL, "out of memory");
         return NULL;
     }
-    napi_value name, promise;
+    napi_value promise;
     j->ctx = ctx;
     j->box = b;
     j->cap = b->eq_cap;
-    napi_create_string_utf8(env, "pie_expired_queue_finish", NAPI_AUTO_LENGTH, &name);
     if (napi_create_promise(env, &j->deferred, &promise) != napi_ok) {
         free(j->rows);
         free(j);
         napi_throw_error(env, NULL, "N-API call failed: promise");
         return NULL;
     }
-    b->busy = 1;
-    if (napi_create_async_work(env, NULL, name, expq_exec, expq_done, j, &j->work) != napi_ok ||
-        napi_queue_async_work(env, j->work) != napi_ok) {
-        b->busy = 0;
+    if (!queue_promise_job(env, b, "pie_expired_queue_finish", expq_exec, expq_done, j, &j->work)) {
         free(j->rows);
         free(j);
-        napi_throw_error(env, NULL, "cannot queue async work");
         return NULL;
     }
     b->eq_begun = 0; /* the library consumes the pass whatever the wait says (cap = capRows: never PIE_E_INVAL) */

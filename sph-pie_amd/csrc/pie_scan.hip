@@ -23,6 +23,7 @@
 #include "pie_ordered.h"
 #include "pie_token.h"
 #include "pie_expq.h"
+#include "pie_wait.h"
 
 #include <hip/hip_runtime.h>
 
@@ -37,7 +38,6 @@
 #include <algorithm>
 #include <cstring>
 #include <ctime>
-#include <sched.h>
 #include <string>
 #include <vector>
 
@@ -246,6 +246,19 @@ struct OrderedRun {
     double build_ms = 0;
 };
 
+// A side pass runs beside scans and batches on a stream of its own: the token lookups and the expired queue in flight (side_open
+// ... side_release below).  It is fenced against the context's stream both ways, once per begin (SideFence); a block it outgrew is
+// only set aside, because hipFree and hipHostFree wait for the whole device, the lanes' kernels included.
+struct SidePass {
+    hipStream_t stream = nullptr; // non-blocking, created at the first begin
+    bool stale = false;           // a wait gave up or a begin failed half-way: the next begin drains the stream first
+    std::vector<std::pair<void*, void*>> retired; // (pinned, device) blocks a begin outgrew, until side_release
+};
+struct SideFence {
+    hipEvent_t order = nullptr; // recorded on the context's stream at begin: the pass runs behind the mutations queued so far
+    hipEvent_t done = nullptr;  // recorded on the side stream behind the pass; the context's stream waits for it
+};
+
 } // namespace
 
 struct pie_ctx {
@@ -343,30 +356,28 @@ struct pie_ctx {
         bool hold = false;
         double build_ms = 0;
         unsigned long long builds = 0;
-        // Lookups that run beside scans and batches (pie_token_lookup_begin / _finish): a stream of their own, created at the
-        // first begin, and kTokLookups slots handed out and returned in order.  A slot owns its pinned and device staging
-        // (token_flight_stage_of: keys and clocks in, results and ITS status words out) and two events: `order` is recorded on
-        // the context's stream at begin (the mutations queued so far), `done` on the lookup stream behind the results' copy.
+        // Lookups that run beside scans and batches (pie_token_lookup_begin / _finish): one side pass and kTokLookups slots
+        // handed out and returned in order.  A slot owns its pinned and device staging (token_flight_stage_of: keys and clocks
+        // in, results and ITS status words out) and its fence: `done` sits behind the results' copy.
         struct Lookup {
             char* h = nullptr;
             char* d = nullptr;
             size_t bytes = 0, k = 0;
-            hipEvent_t order = nullptr, done = nullptr;
+            SideFence fence;
             bool landed = false;    // `done` was waited for (token_lookups_land): the results are in h
             bool global = false;    // begun by the shard form: rows and users are GLOBAL ids
         } lk[kTokLookups];
-        hipStream_t lk_stream = nullptr;
+        SidePass side;              // stale: a finish returned its slot without having seen `done`
         int lk_head = 0, lk_n = 0;  // the oldest unfinished lookup; how many are unfinished
-        bool lk_stale = false;      // a finish returned its slot without having seen `done`: the next begin drains lk_stream first
-        std::vector<std::pair<char*, char*>> lk_retired; // (pinned, device) staging a slot outgrew, until token_lookups_release
     } tokx;
-    // The expired queue that runs beside scans and batches (pie_expired_queue_begin / _finish): a stream, scratch (one count and
-    // one offset per unit, pie_expq_plan.h), a queue buffer and a mapped summary of its own, all created at the first begin.
-    // `order` is recorded on the context's stream at begin, `done` on the pass's stream behind its last kernel (with `t0` ahead of
-    // its first: the device time of the pass).  One pass may be begun and not finished.
+    // The expired queue that runs beside scans and batches (pie_expired_queue_begin / _finish): a side pass with scratch (one
+    // count and one offset per unit, pie_expq_plan.h), a queue buffer and a mapped summary of its own, all created at the first
+    // begin.  `done` sits behind its last kernel, `t0` ahead of its first (the device time of the pass).  One pass may be begun
+    // and not finished.
     struct ExpiredFlight {
-        hipStream_t stream = nullptr;
-        hipEvent_t order = nullptr, t0 = nullptr, done = nullptr;
+        SidePass side;
+        SideFence fence;             // `done` keeps its timing: t0 .. done is the pass
+        hipEvent_t t0 = nullptr;
         char* d_scratch = nullptr;
         int* d_buf = nullptr;
         size_t buf_rows = 0;
@@ -378,12 +389,10 @@ struct pie_ctx {
         bool launched = false;       // it has kernels (not an empty table or an empty window)
         bool landed = false;         // its summary was seen (expq_land): nothing of it reads the table any more
         bool global = false;         // begun by the shard form: the buffer holds GLOBAL rows
-        bool stale = false;          // a wait gave up: the next begin drains the pass's stream first
         bool timed = false;          // t0 / done of a pass whose time has not been read yet
         double ms = 0;
         int blocks_per_cu = kExpqBlocksPerCu;
         int max_blocks = 0;          // PIE_EXPQ_MAX_BLOCKS: a cap on the grid (0: none)
-        std::vector<int*> retired;   // buffers a begin outgrew, until the context has been drained anyway
     } expq;
     double cmp_count_ms = 0;       // ... of its count pass and prefix alone
     double cmp_write_ms = 0;       // ... of its write pass (HIP events)
@@ -739,25 +748,81 @@ OrdMirror ord_mirror_of(const pie_ctx* c)
     return m;
 }
 
-// The one wait of a lookup begun beside scans and batches (pie_token_lookup_begin): on its own event, polled and bounded like
-// the wait on a scan summary (PIE_WAIT_DEADLINE_MS) — never on the context's stream or a lane's.
+// ---- the waits (pie_wait.h): nothing below polls a query or a mapped word itself.  hipSuccess is kProbeDone.
+int probe_of(hipError_t e) { return e == hipErrorNotReady ? kProbeNotReady : (int)e; }
+// for a summary word in mapped host memory to take the value `want`; `query` says how the stream or event behind it fares
+template <class Query>
+WaitResult word_wait(pie_ctx* c, const volatile unsigned long long* word, unsigned long long want, Query query, double drained_grace_ms, WaitPace pace)
+{
+    return bounded_wait([=] { return *word == want; }, [&] { return probe_of(query()); }, c->wait_deadline_ms, drained_grace_ms, pace);
+}
+
+// for an event: the one query per spin is both the thing waited for and the probe
+WaitResult event_wait(pie_ctx* c, hipEvent_t ev)
+{
+    hipError_t e = hipSuccess;
+    return bounded_wait([&] { return (e = hipEventQuery(ev)) == hipSuccess; }, [&] { return probe_of(e); }, c->wait_deadline_ms, kNoGraceLimit, kPaceEvent);
+}
+
+// ---- side passes (SidePass, SideFence).  The caller has set the device.
+int side_open(pie_ctx* c, SidePass& sp)
+{
+    if (!sp.stream) PIE_HIP(c, hipStreamCreateWithFlags(&sp.stream, hipStreamNonBlocking));
+    if (sp.stale) PIE_HIP(c, hipStreamSynchronize(sp.stream)); // what a given-up wait left there may still use what the next pass touches
+    sp.stale = false;
+    return PIE_OK;
+}
+
+// the pass runs behind the appends, touches and deletes queued on the context's stream so far, and behind nothing that comes later
+int side_enter(pie_ctx* c, SidePass& sp, SideFence& f, unsigned done_flags)
+{
+    if (!f.order) PIE_HIP(c, hipEventCreateWithFlags(&f.order, hipEventDisableTiming));
+    if (!f.done) PIE_HIP(c, hipEventCreateWithFlags(&f.done, done_flags));
+    PIE_HIP(c, hipEventRecord(f.order, c->stream));
+    PIE_HIP(c, hipStreamWaitEvent(sp.stream, f.order, 0));
+    return PIE_OK;
+}
+
+// whatever is queued on the context's stream from here on (a touch, a delete, an append) runs behind the pass's reads
+hipError_t side_leave(pie_ctx* c, SidePass& sp, SideFence& f)
+{
+    const hipError_t e = hipEventRecord(f.done, sp.stream);
+    return e == hipSuccess ? hipStreamWaitEvent(c->stream, f.done, 0) : e;
+}
+
+// a block the pass outgrew, its replacement already allocated: set aside until side_release (false: out of host memory)
+bool side_retire(SidePass& sp, void* host_ptr, void* dev_ptr) try {
+    if (host_ptr || dev_ptr) sp.retired.push_back({host_ptr, dev_ptr});
+    return true;
+} catch (...) {
+    return false;
+}
+
+// called where the context has been drained anyway (the frees wait for the device)
+void side_release(SidePass& sp)
+{
+    for (auto& p : sp.retired) {
+        if (p.first) (void)hipHostFree(p.first);
+        if (p.second) (void)hipFree(p.second);
+    }
+    sp.retired.clear();
+}
+
+void side_close(SidePass& sp)
+{
+    if (sp.stream) (void)hipStreamSynchronize(sp.stream);
+    side_release(sp);
+    if (sp.stream) (void)hipStreamDestroy(sp.stream); // pie_ctx_destroy, ahead of freeing what the pass owns
+}
+
+// the one wait of a lookup begun beside scans and batches: on its own event, never on the context's stream or a lane's
 int token_lookup_landed(pie_ctx* c, pie_ctx::TokenIndex::Lookup& l, const char* what)
 {
     if (l.landed) return PIE_OK;
-    timespec t0{};
-    clock_gettime(CLOCK_MONOTONIC, &t0);
-    for (unsigned long long spins = 0;; ++spins) {
-        const hipError_t e = hipEventQuery(l.done);
-        if (e == hipSuccess) break;
-        timespec t1{};
-        clock_gettime(CLOCK_MONOTONIC, &t1);
-        const double waited_ms = (double)(t1.tv_sec - t0.tv_sec) * 1e3 + (double)(t1.tv_nsec - t0.tv_nsec) * 1e-6;
-        if (e != hipErrorNotReady) return fail(c, PIE_E_HIP, "%s: token lookup failed: %s", what, hipGetErrorString(e));
-        if (waited_ms > c->wait_deadline_ms)
-            return fail(c, PIE_E_HIP, "%s: token lookup not finished within %.0f ms (PIE_WAIT_DEADLINE_MS): kernel hung?", what, waited_ms);
-        if (spins > 64) sched_yield();
-        else __builtin_ia32_pause();
-    }
+    const WaitResult w = event_wait(c, l.fence.done);
+    if (w.end == WaitEnd::Failed) return fail(c, PIE_E_HIP, "%s: token lookup failed: %s", what, hipGetErrorString((hipError_t)w.err));
+    if (w.end != WaitEnd::Ready)
+        return fail(c, PIE_E_HIP, "%s: token lookup not finished within %.0f ms (PIE_WAIT_DEADLINE_MS): kernel hung?", what, w.waited_ms);
     l.landed = true;
     return PIE_OK;
 }
@@ -775,50 +840,26 @@ int token_lookups_land(pie_ctx* c, const char* what)
     return PIE_OK;
 }
 
-// The one wait of the expired queue begun beside scans and batches: on ITS summary word (and its own event, for a failure), polled
-// and bounded by PIE_WAIT_DEADLINE_MS — never on the context's stream or a lane's.  Past it nothing of the pass reads the table.
+// The one wait of the expired queue begun beside scans and batches: on ITS summary word (and its own event, for a failure), never
+// on the context's stream or a lane's.  Past it nothing of the pass reads the table.
 int expq_land(pie_ctx* c, const char* what)
 {
     pie_ctx::ExpiredFlight& x = c->expq;
     if (!x.begun || x.landed) return PIE_OK;
-    volatile unsigned long long* hs = &x.h_sum->seq;
-    timespec t0{};
-    clock_gettime(CLOCK_MONOTONIC, &t0);
-    for (unsigned long long spins = 1; *hs != x.seq; ++spins) {
-        if ((spins & 0xFF) == 0) {
-            const hipError_t e = hipEventQuery(x.done);
-            timespec t1{};
-            clock_gettime(CLOCK_MONOTONIC, &t1);
-            const double waited_ms = (double)(t1.tv_sec - t0.tv_sec) * 1e3 + (double)(t1.tv_nsec - t0.tv_nsec) * 1e-6;
-            if (e != hipSuccess && e != hipErrorNotReady) return fail(c, PIE_E_HIP, "%s: expired queue in flight failed: %s", what, hipGetErrorString(e));
-            if (e == hipSuccess && *hs != x.seq) return fail(c, PIE_E_HIP, "%s: expired queue in flight ended without its summary", what);
-            if (waited_ms > c->wait_deadline_ms)
-                return fail(c, PIE_E_HIP, "%s: expired queue in flight not finished within %.0f ms (PIE_WAIT_DEADLINE_MS): kernel hung?", what, waited_ms);
-            if (spins > 4096) sched_yield();
-        } else {
-            __builtin_ia32_pause();
-        }
-    }
-    __atomic_thread_fence(__ATOMIC_ACQUIRE);
+    const WaitResult w = word_wait(c, &x.h_sum->seq, x.seq, [&] { return hipEventQuery(x.fence.done); }, 0.0, kPaceSideSummary);
+    if (w.end == WaitEnd::Failed) return fail(c, PIE_E_HIP, "%s: expired queue in flight failed: %s", what, hipGetErrorString((hipError_t)w.err));
+    if (w.end == WaitEnd::Drained) return fail(c, PIE_E_HIP, "%s: expired queue in flight ended without its summary", what);
+    if (w.end == WaitEnd::Deadline)
+        return fail(c, PIE_E_HIP, "%s: expired queue in flight not finished within %.0f ms (PIE_WAIT_DEADLINE_MS): kernel hung?", what, w.waited_ms);
     x.landed = true;
     return PIE_OK;
 }
 
-// the queue buffers a begin outgrew: released where the context has been drained anyway (hipFree waits for the device)
-void expq_release(pie_ctx* c)
+// both side passes have run: for whatever replaces something that both read (the columns, a shard's maps, the row numbering)
+int side_passes_land(pie_ctx* c, const char* what)
 {
-    for (int* p : c->expq.retired) (void)hipFree(p);
-    c->expq.retired.clear();
-}
-
-// the staging blocks the lookup slots outgrew: released where the context has been drained anyway (the frees wait for the device)
-void token_lookups_release(pie_ctx* c)
-{
-    for (auto& p : c->tokx.lk_retired) {
-        if (p.first) (void)hipHostFree(p.first);
-        if (p.second) (void)hipFree(p.second);
-    }
-    c->tokx.lk_retired.clear();
+    const int rc = token_lookups_land(c, what);
+    return rc ? rc : expq_land(c, what);
 }
 
 // the token column and its index go (no-op when there is none); the status array, the staging and the counters stay
@@ -829,7 +870,7 @@ void token_drop(pie_ctx* c)
     if (!t.tok && !t.slot_row) return;
     (void)token_lookups_land(c, "token column");
     (void)hipStreamSynchronize(c->stream);
-    token_lookups_release(c);
+    side_release(t.side);
     dfree(t.tok);
     dfree(t.slot_row);
     t.cap = t.covered = t.covered_g = 0;
@@ -849,7 +890,7 @@ void free_table(pie_ctx* c)
 {
     for (int l = 1; l < kLaneMax; ++l) // nothing of a lane's may still be running when its arrays go
         if (c->lane_stream[l]) (void)hipStreamSynchronize(c->lane_stream[l]);
-    expq_release(c);
+    side_release(c->expq.side);
     dfree(c->d_union); dfree(c->d_union_cnt); dfree(c->d_union_local); dfree(c->d_union_off);
     c->union_users = 0;
     ord_free(c);
@@ -979,10 +1020,8 @@ int ensure_capacity(pie_ctx* c, long long n, int n_users, long long keep_rows = 
     if (n_users < 1) return fail(c, PIE_E_INVAL, "n_users must be >= 1 (got %d)", n_users);
     if (c->n_flight || c->b_flight) return fail(c, PIE_E_STATE, "table change while a scan is in flight");
     int rc = PIE_OK;
-    // a new table, or columns that are about to move: the token lookups begun on the old ones land first
-    if (keep_rows == 0 || n > c->cap_rows || n_users > c->cap_users) rc = token_lookups_land(c, "table change");
-    if (rc) return rc;
-    if (keep_rows == 0 || n > c->cap_rows || n_users > c->cap_users) rc = expq_land(c, "table change"); // ... and the expired queue begun on them
+    // a new table, or columns that are about to move: the token lookups and the expired queue begun on the old ones land first
+    if (keep_rows == 0 || n > c->cap_rows || n_users > c->cap_users) rc = side_passes_land(c, "table change");
     if (rc) return rc;
     rc = sync_all(c);
     if (rc) return rc;
@@ -2273,37 +2312,19 @@ int scan_finish(pie_ctx* c, Slot* which)
     // wait for K2's last block to publish the summary in mapped host memory (no copy node, no event wait).  The wait is
     // bounded (PIE_WAIT_DEADLINE_MS, default 20 s): a kernel that never finishes must not hang the caller — in the Node
     // host that is the JS main thread.  The slot stays in flight until its summary has been read, so an error return
-    // leaves the context consistent: the failed scan is dropped (no result), the stream is left to drain.
+    // leaves the context consistent: the failed scan is dropped (no result), the stream is left to drain.  Drained: the stream
+    // has drained but the mapped write is not visible; the device copy is read instead (the ordered run has none and waits on).
     {
-        volatile unsigned long long* seq = &sl.h_sum->seq;
-        unsigned long long spins = 0;
-        bool from_device = false;
-        timespec t0{};
-        clock_gettime(CLOCK_MONOTONIC, &t0);
-        while (*seq != sl.seq) {
-            __builtin_ia32_pause();
-            if ((++spins & 0x3FFFF) == 0) { // every ~1 ms: is the stream still healthy, is the deadline up?
-                hipError_t q = hipStreamQuery(c->stream);
-                if (q == hipSuccess && *seq != sl.seq && !sl.ordered) {
-                    // the stream drained but the mapped write is not visible: read the device copy instead
-                    from_device = true;
-                    break;
-                }
-                timespec t1{};
-                clock_gettime(CLOCK_MONOTONIC, &t1);
-                const double waited_ms = (double)(t1.tv_sec - t0.tv_sec) * 1e3 + (double)(t1.tv_nsec - t0.tv_nsec) * 1e-6;
-                if ((q != hipSuccess && q != hipErrorNotReady) || waited_ms > c->wait_deadline_ms) {
-                    sl.in_flight = false;
-                    sl.have_result = false;
-                    c->n_flight--;
-                    if (c->res == &sl) c->res = nullptr;
-                    if (q != hipSuccess && q != hipErrorNotReady) return fail(c, PIE_E_HIP, "scan failed: %s", hipGetErrorString(q));
-                    return fail(c, PIE_E_HIP, "scan summary not published within %.0f ms (PIE_WAIT_DEADLINE_MS): kernel hung?", c->wait_deadline_ms);
-                }
-            }
+        const WaitResult w = word_wait(c, &sl.h_sum->seq, sl.seq, [&] { return hipStreamQuery(c->stream); }, sl.ordered ? kNoGraceLimit : 0.0, kPaceSummary);
+        if (w.end == WaitEnd::Failed || w.end == WaitEnd::Deadline) {
+            sl.in_flight = false;
+            sl.have_result = false;
+            c->n_flight--;
+            if (c->res == &sl) c->res = nullptr;
+            if (w.end == WaitEnd::Failed) return fail(c, PIE_E_HIP, "scan failed: %s", hipGetErrorString((hipError_t)w.err));
+            return fail(c, PIE_E_HIP, "scan summary not published within %.0f ms (PIE_WAIT_DEADLINE_MS): kernel hung?", c->wait_deadline_ms);
         }
-        __atomic_thread_fence(__ATOMIC_ACQUIRE);
-        if (from_device) {
+        if (w.end == WaitEnd::Drained) {
             // K2 writes live / amb only to the host copy: take every other field from the device Summary and the row
             // statistics from their slots (the same sum K2's last block makes)
             std::vector<unsigned char> raw(span_stats_bytes());
@@ -3138,28 +3159,12 @@ int batch_finish(pie_ctx* c, int* ready_out)
         }
         PIE_PROF_TICK(5);
         // wait for the batch's summary (mapped host memory, seq last); bounded like the single-scan wait
-        timespec t0{};
-        clock_gettime(CLOCK_MONOTONIC, &t0);
-        {
-            volatile unsigned long long* seq = &b.bh->seq;
-            unsigned long long spins = 0;
-            while (*seq != b.seq) {
-                __builtin_ia32_pause();
-                if ((++spins & 0x3FFFF) == 0) {
-                    hipError_t e = hipStreamQuery(s);
-                    timespec t1{};
-                    clock_gettime(CLOCK_MONOTONIC, &t1);
-                    const double waited_ms = (double)(t1.tv_sec - t0.tv_sec) * 1e3 + (double)(t1.tv_nsec - t0.tv_nsec) * 1e-6;
-                    const bool bad = e != hipSuccess && e != hipErrorNotReady;
-                    if (bad || waited_ms > c->wait_deadline_ms || (e == hipSuccess && *seq != b.seq && waited_ms > 1000.0)) {
-                        batch_left(c, b);
-                        if (bad) return fail(c, PIE_E_HIP, "batched scan failed: %s", hipGetErrorString(e));
-                        return fail(c, PIE_E_HIP, "batch summary not published within %.0f ms (PIE_WAIT_DEADLINE_MS): kernel hung?", waited_ms);
-                    }
-                }
-            }
+        const WaitResult w = word_wait(c, &b.bh->seq, b.seq, [&] { return hipStreamQuery(s); }, 1000.0, kPaceSummary);
+        if (w.end != WaitEnd::Ready) {
+            batch_left(c, b);
+            if (w.end == WaitEnd::Failed) return fail(c, PIE_E_HIP, "batched scan failed: %s", hipGetErrorString((hipError_t)w.err));
+            return fail(c, PIE_E_HIP, "batch summary not published within %.0f ms (PIE_WAIT_DEADLINE_MS): kernel hung?", w.waited_ms);
         }
-        __atomic_thread_fence(__ATOMIC_ACQUIRE);
         PIE_PROF_TICK(6);
         bool overflow = false;
         {
@@ -3625,21 +3630,11 @@ int wide_finish(pie_ctx* c, size_t* m_out, size_t m_cap, int* n_q_out, int* read
     WideSlot& w = *b.w;
     if (!b.unsupported) {
         // wait for the summary's copy, bounded like batch_finish's wait (PIE_WAIT_DEADLINE_MS)
-        timespec t0{};
-        clock_gettime(CLOCK_MONOTONIC, &t0);
-        for (unsigned long long spins = 0;; ++spins) {
-            const hipError_t e = hipEventQuery(w.done);
-            if (e == hipSuccess) break;
-            timespec t1{};
-            clock_gettime(CLOCK_MONOTONIC, &t1);
-            const double waited_ms = (double)(t1.tv_sec - t0.tv_sec) * 1e3 + (double)(t1.tv_nsec - t0.tv_nsec) * 1e-6;
-            if (e != hipErrorNotReady || waited_ms > c->wait_deadline_ms) {
-                batch_left(c, b);
-                if (e != hipErrorNotReady) return fail(c, PIE_E_HIP, "wide batch failed: %s", hipGetErrorString(e));
-                return fail(c, PIE_E_HIP, "wide batch not finished within %.0f ms (PIE_WAIT_DEADLINE_MS): kernel hung?", waited_ms);
-            }
-            if (spins > 64) sched_yield();
-            else __builtin_ia32_pause();
+        const WaitResult wr = event_wait(c, w.done);
+        if (wr.end != WaitEnd::Ready) {
+            batch_left(c, b);
+            if (wr.end == WaitEnd::Failed) return fail(c, PIE_E_HIP, "wide batch failed: %s", hipGetErrorString((hipError_t)wr.err));
+            return fail(c, PIE_E_HIP, "wide batch not finished within %.0f ms (PIE_WAIT_DEADLINE_MS): kernel hung?", wr.waited_ms);
         }
         const Summary us = *w.h_sum;
         const unsigned* mq = reinterpret_cast<const unsigned*>(reinterpret_cast<const char*>(w.h_sum) + kSummaryBytes);
@@ -3811,8 +3806,7 @@ int pie_ctx_destroy(pie_ctx* c)
     g_prof.report();
 #endif
     (void)hipSetDevice(c->device);
-    (void)token_lookups_land(c, "pie_ctx_destroy");
-    (void)expq_land(c, "pie_ctx_destroy");
+    (void)side_passes_land(c, "pie_ctx_destroy");
     (void)hipStreamSynchronize(c->stream);
     free_table(c);
     dfree(c->d_shard_rows);
@@ -3824,23 +3818,19 @@ int pie_ctx_destroy(pie_ctx* c)
     if (c->tokx.h_stage) (void)hipHostFree(c->tokx.h_stage);
     for (hipEvent_t e : c->tokx.ev)
         if (e) (void)hipEventDestroy(e);
-    if (c->tokx.lk_stream) (void)hipStreamSynchronize(c->tokx.lk_stream);
-    token_lookups_release(c);
+    side_close(c->tokx.side);
     for (auto& l : c->tokx.lk) {
         if (l.h) (void)hipHostFree(l.h);
         dfree(l.d);
-        if (l.order) (void)hipEventDestroy(l.order);
-        if (l.done) (void)hipEventDestroy(l.done);
+        for (hipEvent_t e : {l.fence.order, l.fence.done})
+            if (e) (void)hipEventDestroy(e);
     }
-    if (c->tokx.lk_stream) (void)hipStreamDestroy(c->tokx.lk_stream);
-    if (c->expq.stream) (void)hipStreamSynchronize(c->expq.stream);
-    expq_release(c);
+    side_close(c->expq.side);
     dfree(c->expq.d_scratch);
     dfree(c->expq.d_buf);
     if (c->expq.h_sum) (void)hipHostFree(c->expq.h_sum);
-    for (hipEvent_t e : {c->expq.order, c->expq.t0, c->expq.done})
+    for (hipEvent_t e : {c->expq.fence.order, c->expq.t0, c->expq.fence.done})
         if (e) (void)hipEventDestroy(e);
-    if (c->expq.stream) (void)hipStreamDestroy(c->expq.stream);
     dfree(c->d_stage);
     if (c->h_stage) (void)hipHostFree(c->h_stage);
     for (auto& a : c->astage) {
@@ -5234,23 +5224,10 @@ int pie_expired_queue(pie_ctx* c, int64_t prev_now, int64_t now, int32_t* queue_
     } else {
         // bounded wait like a scan's; the gather behind the prefix kernel may still run when the length is known (everything that
         // reads the queue afterwards is queued on this stream, behind it)
-        volatile unsigned long long* hs = &q.h_sum->seq;
-        unsigned long long spins = 0;
-        timespec t0{};
-        clock_gettime(CLOCK_MONOTONIC, &t0);
-        while (*hs != seq) {
-            __builtin_ia32_pause();
-            if ((++spins & 0x3FFFF) == 0) {
-                const hipError_t e = hipStreamQuery(s);
-                timespec t1{};
-                clock_gettime(CLOCK_MONOTONIC, &t1);
-                const double waited_ms = (double)(t1.tv_sec - t0.tv_sec) * 1e3 + (double)(t1.tv_nsec - t0.tv_nsec) * 1e-6;
-                if (e != hipSuccess && e != hipErrorNotReady) return fail(c, PIE_E_HIP, "expired queue failed: %s", hipGetErrorString(e));
-                if (waited_ms > c->wait_deadline_ms || (e == hipSuccess && *hs != seq && waited_ms > 1000.0))
-                    return fail(c, PIE_E_HIP, "expired-queue length not published within %.0f ms (PIE_WAIT_DEADLINE_MS): kernel hung?", waited_ms);
-            }
-        }
-        __atomic_thread_fence(__ATOMIC_ACQUIRE);
+        const WaitResult w = word_wait(c, &q.h_sum->seq, seq, [&] { return hipStreamQuery(s); }, 1000.0, kPaceSummary);
+        if (w.end == WaitEnd::Failed) return fail(c, PIE_E_HIP, "expired queue failed: %s", hipGetErrorString((hipError_t)w.err));
+        if (w.end != WaitEnd::Ready)
+            return fail(c, PIE_E_HIP, "expired-queue length not published within %.0f ms (PIE_WAIT_DEADLINE_MS): kernel hung?", w.waited_ms);
         k = (size_t)q.h_sum->s.m;
     }
     c->q_kind = 1;
@@ -5545,7 +5522,7 @@ int pie_table_info_get(pie_ctx* c, pie_table_info* out)
         out->expired_inflight_bytes = (x.d_scratch ? (uint64_t)expq_scratch_of().bytes : 0u) + (uint64_t)x.buf_rows * 4;
         if (x.timed && !(x.begun && !x.landed)) { // the last pass's device time, read once it has run
             float ms = 0.f;
-            if (hipEventSynchronize(x.done) == hipSuccess && hipEventElapsedTime(&ms, x.t0, x.done) == hipSuccess) x.ms = ms;
+            if (hipEventSynchronize(x.fence.done) == hipSuccess && hipEventElapsedTime(&ms, x.t0, x.fence.done) == hipSuccess) x.ms = ms;
             else (void)hipGetLastError();
             x.timed = false;
         }
@@ -5861,9 +5838,7 @@ static int shard_maps_reserve(pie_ctx* c, long long rows, long long users)
 {
     hipStream_t s = c->stream;
     if (rows > c->shard_rows_cap || users > c->shard_users_cap) { // a token lookup begun earlier reads the maps that go
-        int rc = token_lookups_land(c, "map growth");
-        if (rc) return rc;
-        rc = expq_land(c, "map growth"); // the shard form of the expired queue in flight reads the row map
+        const int rc = side_passes_land(c, "map growth"); // ... and the shard form of the expired queue in flight reads the row map
         if (rc) return rc;
     }
     if (rows > c->shard_rows_cap) {
@@ -6317,9 +6292,7 @@ int pie_compact_rows(pie_ctx* c, int64_t dead_before, uint32_t flags, size_t* n_
     if (c->cap_rows == 0) return fail(c, PIE_E_STATE, "no table loaded");
     if (c->n_flight || c->b_flight) return fail(c, PIE_E_STATE, "a scan is in flight");
     PIE_HIP(c, hipSetDevice(c->device));
-    int rc = token_lookups_land(c, "pie_compact_rows"); // token lookups begun on this numbering keep their answers
-    if (rc) return rc;
-    rc = expq_land(c, "pie_compact_rows"); // ... and so does the expired queue in flight
+    int rc = side_passes_land(c, "pie_compact_rows"); // token lookups and the expired queue begun on this numbering keep their answers
     if (rc) return rc;
     rc = sync_all(c); // queued appends and touches land first
     if (rc) return rc;
@@ -7270,19 +7243,12 @@ static int token_flight_begin(pie_ctx* c, const uint64_t* tok, const int64_t* no
     if (k > 0 && (!tok || !now)) return fail(c, PIE_E_INVAL, "%s: NULL pointer", what);
     if (k >= ((size_t)1 << 31)) return fail(c, PIE_E_INVAL, "%s: %zu keys in one lookup", what, k);
     PIE_HIP(c, hipSetDevice(c->device));
-    if (!t.lk_stream) PIE_HIP(c, hipStreamCreateWithFlags(&t.lk_stream, hipStreamNonBlocking));
+    if ((rc = side_open(c, t.side)) != PIE_OK) return rc;
     pie_ctx::TokenIndex::Lookup& l = t.lk[(t.lk_head + t.lk_n) % kTokLookups]; // free: lookups finish in the order they began
-    if (!l.order) PIE_HIP(c, hipEventCreateWithFlags(&l.order, hipEventDisableTiming));
-    if (!l.done) PIE_HIP(c, hipEventCreateWithFlags(&l.done, hipEventDisableTiming));
     const TokFlightStage o = token_flight_stage_of(k);
-    if (t.lk_stale) { // a finish gave up on its wait: what it left on the lookup stream may still use a slot's staging
-        PIE_HIP(c, hipStreamSynchronize(t.lk_stream));
-        t.lk_stale = false;
-    }
     if (o.bytes > l.bytes) {
-        // This slot's staging alone grows; the lookups in flight keep theirs.  The new blocks come first and the old ones are
-        // only set aside (hipFree and hipHostFree wait for the whole device, the lanes' kernels included): they are released by
-        // the next call that has drained the context anyway (token_drop, pie_ctx_destroy).  256 KiB hold 5 300 keys.
+        // This slot's staging alone grows; the lookups in flight keep theirs, and the old blocks wait for the next call that
+        // has drained the context anyway (token_drop, pie_ctx_destroy).  256 KiB hold 5 300 keys.
         size_t want = l.bytes ? l.bytes : (size_t)256 << 10;
         while (want < o.bytes) want *= 2;
         char *nh = nullptr, *nd = nullptr;
@@ -7292,9 +7258,7 @@ static int token_flight_begin(pie_ctx* c, const uint64_t* tok, const int64_t* no
             (void)hipHostFree(nh);
             return fail(c, PIE_E_NOMEM, "%s: no device memory for the staging of %zu keys", what, k);
         }
-        try {
-            if (l.h || l.d) t.lk_retired.push_back({l.h, l.d});
-        } catch (...) {
+        if (!side_retire(t.side, l.h, l.d)) {
             (void)hipHostFree(nh);
             (void)hipFree(nd);
             return fail(c, PIE_E_NOMEM, "%s: out of host memory", what);
@@ -7303,10 +7267,8 @@ static int token_flight_begin(pie_ctx* c, const uint64_t* tok, const int64_t* no
         l.d = nd;
         l.bytes = want;
     }
-    hipStream_t s = t.lk_stream;
-    // behind the appends, touches, deletes and token appends queued so far, and behind nothing that comes later
-    PIE_HIP(c, hipEventRecord(l.order, c->stream));
-    PIE_HIP(c, hipStreamWaitEvent(s, l.order, 0));
+    hipStream_t s = t.side.stream;
+    if ((rc = side_enter(c, t.side, l.fence, hipEventDisableTiming)) != PIE_OK) return rc;
     if (k > 0) {
         memcpy(l.h, tok, k * sizeof(TokKey));
         memcpy(l.h + o.now, now, k * 8);
@@ -7332,9 +7294,7 @@ static int token_flight_begin(pie_ctx* c, const uint64_t* tok, const int64_t* no
         PIE_HIP(c, hipGetLastError());
         PIE_HIP(c, hipMemcpyAsync(l.h + o.status, d + o.status, o.bytes - o.status, hipMemcpyDeviceToHost, s));
     }
-    PIE_HIP(c, hipEventRecord(l.done, s));
-    // whatever is queued on the context's stream from here on (a touch, a delete, an append) runs behind this lookup's reads
-    PIE_HIP(c, hipStreamWaitEvent(c->stream, l.done, 0));
+    PIE_HIP(c, side_leave(c, t.side, l.fence));
     l.k = k;
     l.landed = false;
     l.global = global;
@@ -7357,7 +7317,7 @@ static int token_flight_finish(pie_ctx* c, int32_t* row_out, uint8_t* live_out, 
     int rc = token_lookup_landed(c, l, what);
     t.lk_head = (t.lk_head + 1) % kTokLookups; // the slot is returned whatever the wait said
     t.lk_n--;
-    if (rc) t.lk_stale = true; // its copy may still be pending: the next begin drains the lookup stream before it touches a slot
+    if (rc) t.side.stale = true; // its copy may still be pending: the next begin drains the lookup stream before it touches a slot
     if (rc || k == 0) return rc;
     const TokFlightStage o = token_flight_stage_of(k);
     const char* h = l.h;
@@ -7416,10 +7376,9 @@ static int expq_begin(pie_ctx* c, int64_t prev_now, int64_t now, size_t cap_rows
     if (plan.units < 0) return fail(c, PIE_E_INVAL, "%s: no plan for %lld rows", what, c->n);
     PIE_HIP(c, hipSetDevice(c->device));
     const ExpqScratch sc = expq_scratch_of();
-    if (!x.stream) PIE_HIP(c, hipStreamCreateWithFlags(&x.stream, hipStreamNonBlocking));
-    if (!x.order) PIE_HIP(c, hipEventCreateWithFlags(&x.order, hipEventDisableTiming));
+    const int open_rc = side_open(c, x.side); // stale: what a given-up wait left on the stream may still write the buffer
+    if (open_rc) return open_rc;
     if (!x.t0) PIE_HIP(c, hipEventCreate(&x.t0));
-    if (!x.done) PIE_HIP(c, hipEventCreate(&x.done));
     if (!x.h_sum) {
         HostSummary* h = nullptr;
         PIE_HIP(c, hipHostMalloc(&h, sizeof(HostSummary), hipHostMallocMapped));
@@ -7437,29 +7396,22 @@ static int expq_begin(pie_ctx* c, int64_t prev_now, int64_t now, size_t cap_rows
             (void)hipGetLastError();
             return fail(c, PIE_E_NOMEM, "%s: no device memory for the scratch", what);
         }
-        if (hipMemsetAsync(d + sc.ctl, 0, sc.bytes - sc.ctl, x.stream) != hipSuccess) { // the done counter; every pass leaves it at zero
+        if (hipMemsetAsync(d + sc.ctl, 0, sc.bytes - sc.ctl, x.side.stream) != hipSuccess) { // the done counter; every pass leaves it at zero
             (void)hipGetLastError();
             (void)hipFree(d);
             return fail(c, PIE_E_HIP, "%s: cannot clear the scratch", what);
         }
         x.d_scratch = d;
     }
-    if (x.stale) { // a wait gave up on the last pass: what it left on the stream may still write the buffer
-        PIE_HIP(c, hipStreamSynchronize(x.stream));
-        x.stale = false;
-    }
     if (cap_rows > x.buf_rows) {
-        // the new buffer comes first and the old one is only set aside: hipFree waits for the whole device, the lanes' kernels
-        // included.  It is released by the next call that has drained the context anyway (free_table, pie_ctx_destroy).
+        // the old buffer waits for the next call that has drained the context anyway (free_table, pie_ctx_destroy)
         const size_t rows = expq_buffer_rows(x.buf_rows, cap_rows);
         int* nb = nullptr;
         if (hipMalloc(&nb, rows * 4) != hipSuccess) {
             (void)hipGetLastError();
             return fail(c, PIE_E_NOMEM, "%s: no device memory for a queue of %zu rows", what, cap_rows);
         }
-        try {
-            if (x.d_buf) x.retired.push_back(x.d_buf);
-        } catch (...) {
+        if (!side_retire(x.side, nullptr, x.d_buf)) {
             (void)hipFree(nb);
             return fail(c, PIE_E_NOMEM, "%s: out of host memory", what);
         }
@@ -7468,10 +7420,9 @@ static int expq_begin(pie_ctx* c, int64_t prev_now, int64_t now, size_t cap_rows
     }
     x.launched = c->n > 0 && prev_now < now; // an empty table or an empty window: an empty queue, nothing to run
     if (x.launched) {
-        hipStream_t s = x.stream;
-        // behind the appends, touches and deletes queued so far, and behind nothing that comes later
-        PIE_HIP(c, hipEventRecord(x.order, c->stream));
-        PIE_HIP(c, hipStreamWaitEvent(s, x.order, 0));
+        hipStream_t s = x.side.stream;
+        const int enter_rc = side_enter(c, x.side, x.fence, hipEventDefault); // `done` is timed
+        if (enter_rc) return enter_rc;
         PIE_HIP(c, hipEventRecord(x.t0, s));
         int* d_count = reinterpret_cast<int*>(x.d_scratch + sc.counts);
         long long* d_off = reinterpret_cast<long long*>(x.d_scratch + sc.offsets);
@@ -7499,10 +7450,9 @@ static int expq_begin(pie_ctx* c, int64_t prev_now, int64_t now, size_t cap_rows
 #undef PIE_EXPQ_LAUNCH
         const hipError_t le = hipGetLastError();
         // `done` and the context's wait for it are queued even behind a failed launch: what did start must not be overtaken
-        const hipError_t re = hipEventRecord(x.done, s);
-        const hipError_t we = re == hipSuccess ? hipStreamWaitEvent(c->stream, x.done, 0) : re;
+        const hipError_t we = side_leave(c, x.side, x.fence);
         if (le != hipSuccess || we != hipSuccess) {
-            x.stale = true;
+            x.side.stale = true;
             return fail(c, PIE_E_HIP, "%s: %s", what, hipGetErrorString(le != hipSuccess ? le : we));
         }
         x.seq = seq;
@@ -7526,17 +7476,17 @@ static int expq_finish(pie_ctx* c, int32_t* queue_out, size_t cap, size_t* q_out
     const int rc = expq_land(c, what);
     x.begun = false; // the pass is consumed whatever the wait said
     if (rc) {
-        x.stale = true;
+        x.side.stale = true;
         return rc;
     }
     const size_t len = x.launched ? (size_t)x.h_sum->s.m : 0;
     if (q_out) *q_out = len;
     const size_t rows = len < x.cap_rows ? len : x.cap_rows;
     if (queue_out && rows) {
-        const hipError_t ce = hipMemcpyAsync(queue_out, x.d_buf, rows * 4, hipMemcpyDeviceToHost, x.stream);
-        const hipError_t se = ce == hipSuccess ? hipStreamSynchronize(x.stream) : ce; // the pass's own stream, nobody else's
+        const hipError_t ce = hipMemcpyAsync(queue_out, x.d_buf, rows * 4, hipMemcpyDeviceToHost, x.side.stream);
+        const hipError_t se = ce == hipSuccess ? hipStreamSynchronize(x.side.stream) : ce; // the pass's own stream, nobody else's
         if (se != hipSuccess) {
-            x.stale = true;
+            x.side.stale = true;
             return fail(c, PIE_E_HIP, "%s: %s", what, hipGetErrorString(se));
         }
     }

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from table_model import same
+from token_model import TokenModel
 
 pytestmark = pytest.mark.gpu
 
@@ -304,6 +305,75 @@ def test_ordering_against_mutators(pie, oracle):
         ctx.append_rows(*columns(big, 24), U)
         assert np.array_equal(ctx.expired_queue_finish(), want)
         in_flight(ctx, oracle, np.concatenate([e2, big]), tag="after the growth")
+
+
+@pytest.mark.parametrize("change", ["load", "append", "compact"])
+def test_both_side_passes_begun_under_a_table_change(pie, oracle, change):
+    """an expired queue and two token lookups are begun, then the table is replaced, outgrown or renumbered under all three: each
+    finish gives the old table's answer (the oracle's queue, the dict model's rows), and a fresh begin / finish of each sees
+    the new table"""
+    def lookup_is(got, want, tag):
+        assert np.array_equal(got["row"], want["row"]) and np.array_equal(got["live"], want["live"]), tag
+        f = want["found"]
+        for col in ("user", "start", "end"):
+            assert np.array_equal(got[col][f], want[col][f]), (tag, col)
+
+    with new_ctx(pie) as ctx:
+        _, unit = row_counts(ctx)
+        n = unit + 1
+        e = ends(n, "random", 51)
+        cols = load(ctx, e, 51)
+        model = TokenModel(*cols)
+        keys = np.random.default_rng(52).integers(0, 2 ** 64, (n + 600, 2), dtype=np.uint64)
+        ctx.token_set(keys[:n])
+        model.token_set(keys[:n])
+        asks = (keys[:n:37], np.concatenate([keys[n - 300:n], keys[n:n + 40]]))     # the second: the last rows and keys no row has
+        clocks = (NOW, PREV)
+        want_queue = oracle.expired_queue(e, PREV, NOW)
+        want_rows = [{k: np.array(v) for k, v in model.lookup(a, t).items()} for a, t in zip(asks, clocks)]
+        assert want_queue.size > 100 and all(w["found"].any() and w["live"].any() for w in want_rows) and not want_rows[1]["found"].all()
+        ctx.expired_queue_begin(PREV, NOW)
+        for a, t in zip(asks, clocks):
+            ctx.token_lookup_begin(a, t)
+        assert ctx.expired_queue_room() == 0 and ctx.token_lookup_room() == 2
+        if change == "load":
+            e = ends(777, "every", 53)
+            cols = load(ctx, e, 53)
+            model = TokenModel(*cols)
+        elif change == "append":
+            more = ends(500, "alternating", 54)
+            grow = columns(more, 54)
+            ctx.append_rows(*grow, U)
+            model.append_rows(*grow)
+            e = np.concatenate([e, more])
+        else:
+            assert (e == END_NONE).sum() > 100
+            assert ctx.compact_rows() == (e != END_NONE).sum()
+            new_of_old = model.compact()
+            e = e[e != END_NONE]
+        assert np.array_equal(ctx.expired_queue_finish(), want_queue), (change, "the old table's queue")
+        for i, want in enumerate(want_rows):
+            lookup_is(ctx.token_lookup_finish(), want, (change, "the old table's rows, lookup", i))
+        assert ctx.expired_queue_room() == 1 and ctx.token_lookup_room() == 4
+        # afterwards: the new table
+        if change == "load":
+            keys = np.random.default_rng(55).integers(0, 2 ** 64, (777, 2), dtype=np.uint64)
+            ctx.token_set(keys)
+            model.token_set(keys)
+            asks = (keys[::5], keys[700:])
+        elif change == "append":
+            ctx.token_append(keys[n:n + 500])
+            model.token_append(keys[n:n + 500])
+        assert np.array_equal(model.end, e)
+        in_flight(ctx, oracle, e, tag=(change, "the new table's queue"))
+        for i, (a, t) in enumerate(zip(asks, clocks)):
+            ctx.token_lookup_begin(a, t)
+            got = ctx.token_lookup_finish()
+            lookup_is(got, model.lookup(a, t), (change, "the new table's rows, lookup", i))
+            if change == "append" and i == 1:
+                assert np.array_equal(got["row"][300:], np.arange(n, n + 40)), "the keys no row had name the appended rows"
+            if change == "compact" and i == 0:
+                assert np.array_equal(got["row"], new_of_old[::37]) and not np.array_equal(got["row"], want_rows[0]["row"])
 
 
 def test_state_rules(pie, oracle):
