@@ -898,6 +898,50 @@ int pie_comm_wide_step_read_gathered(pie_comm *comm, int32_t at_rank, int32_t sr
 int pie_comm_wide_step_read_feed(pie_comm *comm, int32_t at_rank, int32_t src_rank, int64_t step, int32_t qi, int32_t local_user,
                                  int32_t *idx_out, size_t idx_cap, size_t *k_out);
 
+/* ---- token lookups and the purge tick WHILE STEPS ARE IN FLIGHT: pie_shard_token_lookup_begin / _finish and
+ * pie_shard_expired_queue_begin / _finish on every local shard.  A multi-GPU server answers getSession (server/index.js:84,
+ * server/sessionStore.js:21-35) and computes its purge queue (server/sessionStore.js:66-73) without collecting the steps it keeps
+ * in flight.  pie_comm_token_lookup and pie_comm_expired_queue keep their rule (PIE_E_STATE while steps are uncollected).
+ * Both families:
+ *   - allowed whenever every local shard has a table (lookups: and a token column), whatever is in flight: ordinary steps, wide
+ *     steps, the synchronous gather's batches, or nothing;
+ *   - no RCCL call; neither the exchange streams nor a step buffer set is touched; no context's stream or lane is synchronised:
+ *     each shard's pass runs on its own side stream, and every host wait is bounded by PIE_WAIT_DEADLINE_MS (PIE_E_HIP past it);
+ *   - in a process-per-GPU communicator a process reports what its own shards hold, as pie_comm_token_lookup and
+ *     pie_comm_delete_users do;
+ *   - begin asks every local shard before it begins on any.  If a shard still refuses after others began, what was begun is
+ *     finished and discarded: every shard's room is what it was before the call;
+ *   - the communicator counts what it has begun.  A shard whose own room does not match that count (pie_shard_* was used on a
+ *     context from pie_comm_ctx directly): begin returns PIE_E_STATE and takes no slot anywhere;
+ *   - pie_comm_destroy lands whatever was begun and not finished.
+ * Token lookup: up to 4 begun and unfinished, finished in begin order; now[i] belongs to key i.  Per key the local shard with the
+ * LARGEST global row answers, with its live / user / start / end in global ids; owner_rank_out[i] = the rank that answered, -1 if
+ * none: pie_comm_token_lookup's merge, the unsharded table's answer, a key held by two shards included.  cap < k:
+ * PIE_E_CAPACITY with *k_out set, the lookup stays finishable.  k = 0 takes and returns a slot.  Every output may be NULL.
+ * pie_comm_token_lookup_room: the smallest room any local shard has left (4 less the lookups begun and unfinished).
+ * Expired queue: one begun and unfinished.  Result: the ascending global rows with prev_now < end <= now that the local shards
+ * hold — what pie_comm_expired_queue returns on the same table in a single-process communicator; owner_rank_out[i] = the rank
+ * that holds row i (pie_shard_of of its user).  Every shard's pass is begun with cap_rows; finish waits (bounded) for each and
+ * merges the shards' ascending lists ON THE DEVICE of the first local rank, on that shard's pass stream: one element per lane,
+ * placed by co-rank (its index plus a lower bound in every other list), read from the shards' own queue buffers; lists held on
+ * other devices are first copied over device to device, asynchronously, behind their pass.  *q_out (may be NULL) is always the
+ * true total.  cap_rows = 0 counts only.  A total above cap_rows: the first cap_rows merged rows — a true ascending prefix,
+ * since they only ever come from the first cap_rows rows of each list — are returned with PIE_E_CAPACITY; the queue is consumed.
+ * rows_out or owner_rank_out != NULL with cap below the begin's cap_rows: PIE_E_INVAL, nothing consumed.
+ * The merged list stays with the communicator until the next begin: pie_comm_inflight_queue_device_ptrs hands out the device
+ * arrays on the first local rank's device (*n_out rows held = min(total, cap_rows); *q_out the total; PIE_E_STATE before a finish).
+ * PIE_E_STATE: a shard without a table / a token column / whose row map does not cover its rows; a fifth lookup, a second queue;
+ * finish with none begun.  PIE_E_INVAL: NULL communicator; NULL tok or now with k > 0; k or cap_rows >= 2^31.
+ * Like the steps, this has run against a one-GPU stand-in for RCCL only, never across GPUs. */
+int pie_comm_token_lookup_begin(pie_comm *comm, const uint64_t *tok /* [k][2] */, const int64_t *now /* [k] */, size_t k);
+int pie_comm_token_lookup_finish(pie_comm *comm, int32_t *row_out, uint8_t *live_out, int32_t *user_out, int64_t *start_out,
+                                 int64_t *end_out, int32_t *owner_rank_out, size_t cap, size_t *k_out);
+int pie_comm_token_lookup_room(pie_comm *comm);
+int pie_comm_expired_queue_begin(pie_comm *comm, int64_t prev_now, int64_t now, size_t cap_rows);
+int pie_comm_expired_queue_finish(pie_comm *comm, int32_t *rows_out, int32_t *owner_rank_out, size_t cap, size_t *q_out);
+int pie_comm_expired_queue_room(pie_comm *comm);
+int pie_comm_inflight_queue_device_ptrs(pie_comm *comm, void **rows_dev, void **owner_rank_dev, size_t *n_out, size_t *q_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -222,6 +222,13 @@ _SIGS = [
     ("pie_comm_token_append", C.c_int, [_P, _P, C.c_size_t]),
     ("pie_comm_token_lookup", C.c_int, [_P, _P, C.c_size_t, C.c_int64, _P, _P, _P, _P, _P, _P]),
     ("pie_comm_token_set_end", C.c_int, [_P, _P, _P, C.c_size_t, C.c_int64, _P]),
+    ("pie_comm_token_lookup_begin", C.c_int, [_P, _P, _P, C.c_size_t]),
+    ("pie_comm_token_lookup_finish", C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("pie_comm_token_lookup_room", C.c_int, [_P]),
+    ("pie_comm_expired_queue_begin", C.c_int, [_P, C.c_int64, C.c_int64, C.c_size_t]),
+    ("pie_comm_expired_queue_finish", C.c_int, [_P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("pie_comm_expired_queue_room", C.c_int, [_P]),
+    ("pie_comm_inflight_queue_device_ptrs", C.c_int, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
 ]
 ABI_SYMBOLS = [s[0] for s in _SIGS]
 
@@ -1402,6 +1409,67 @@ class PieComm:
         rows = np.empty(keys.shape[0], np.int32)
         self._check(self._lib.pie_comm_token_set_end(self._c, _ptr(keys), _ptr(new_end), keys.shape[0], int(now), _ptr(rows)))
         return rows
+
+    # ---- token lookups and the expired queue while steps are in flight (pie_comm_token_lookup_begin ..., pie_comm_expired_queue_begin ...)
+    def token_lookup_begin(self, keys, now):
+        """Queue getSession for every key on every local shard (now: one clock for all, or one per key), whatever steps are in
+        flight.  Up to four may be begun and not finished."""
+        keys = _keys(keys)
+        k = keys.shape[0]
+        now = np.ascontiguousarray(np.broadcast_to(np.asarray(now, dtype=np.int64), (k,)))
+        self._check(self._lib.pie_comm_token_lookup_begin(self._c, _ptr(keys), _ptr(now), k))
+
+    def token_lookup_finish(self):
+        """The oldest lookup begun -> the dict token_lookup returns (owner included)."""
+        got = C.c_size_t(0)
+        rc = self._lib.pie_comm_token_lookup_finish(self._c, None, None, None, None, None, None, 0, C.byref(got))   # its size; k = 0 finishes here
+        if rc == PIE_E_CAPACITY:
+            k = got.value
+            out = {"row": np.empty(k, np.int32), "live": np.empty(k, np.uint8), "user": np.empty(k, np.int32),
+                   "start": np.empty(k, np.int64), "end": np.empty(k, np.int64), "owner": np.empty(k, np.int32)}
+            rc = self._lib.pie_comm_token_lookup_finish(self._c, _ptr(out["row"]), _ptr(out["live"]), _ptr(out["user"]), _ptr(out["start"]),
+                                                        _ptr(out["end"]), _ptr(out["owner"]), k, C.byref(got))
+        else:
+            out = {"row": np.empty(0, np.int32), "live": np.empty(0, np.uint8), "user": np.empty(0, np.int32),
+                   "start": np.empty(0, np.int64), "end": np.empty(0, np.int64), "owner": np.empty(0, np.int32)}
+        self._check(rc)
+        return out
+
+    def token_lookup_room(self):
+        """Lookups token_lookup_begin would take now: the smallest room any local shard has left."""
+        return int(self._lib.pie_comm_token_lookup_room(self._c))
+
+    def expired_queue_begin(self, prev_now, now, cap_rows=None):
+        """Queue the expired queue on every local shard, whatever steps are in flight.  cap_rows: rows to make room for (default:
+        every row of the table); 0 counts only."""
+        cap = self.table_size()[0] if cap_rows is None else int(cap_rows)
+        self._check(self._lib.pie_comm_expired_queue_begin(self._c, int(prev_now), int(now), cap))
+        self._expq_cap = cap
+
+    def expired_queue_finish(self):
+        """The queue begun -> (ascending global rows, owning rank of each), merged on the first local rank's device; its length
+        when the begin said cap_rows=0.  A queue longer than the begin's cap_rows raises PieError(PIE_E_CAPACITY) carrying
+        .length, .prefix and .prefix_owner."""
+        cap = getattr(self, "_expq_cap", 0)
+        rows, owner = np.empty(max(cap, 1), np.int32), np.empty(max(cap, 1), np.int32)
+        q = C.c_size_t(0)
+        rc = self._lib.pie_comm_expired_queue_finish(self._c, _ptr(rows) if cap else None, _ptr(owner) if cap else None, cap, C.byref(q))
+        if rc == PIE_E_CAPACITY:
+            err = PieError(rc, self._lib.pie_comm_last_error(self._c).decode())
+            err.length, err.prefix, err.prefix_owner = q.value, rows[:cap].copy(), owner[:cap].copy()
+            raise err
+        self._check(rc)
+        return (rows[: q.value].copy(), owner[: q.value].copy()) if cap else q.value
+
+    def expired_queue_room(self):
+        """1 when expired_queue_begin would be taken now, else 0."""
+        return int(self._lib.pie_comm_expired_queue_room(self._c))
+
+    def inflight_queue_device_ptrs(self):
+        """-> (rows device pointer, owner-rank device pointer, rows held, total) of the last expired_queue_finish."""
+        rows, owner, n, q = _P(), _P(), C.c_size_t(0), C.c_size_t(0)
+        self._check(self._lib.pie_comm_inflight_queue_device_ptrs(self._c, C.byref(rows), C.byref(owner), C.byref(n), C.byref(q)))
+        return rows.value, owner.value, int(n.value), int(q.value)
 
     def queue_read(self, at_rank, sources=False):
         """The merged queue of the last queue call as local rank at_rank holds it."""

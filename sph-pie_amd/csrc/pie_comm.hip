@@ -37,6 +37,13 @@ int shard_token_lookup_wait(pie_ctx* c, size_t k, int32_t* row_global_out, uint8
 int shard_check_delete_users(pie_ctx* c, const int32_t* users_global, size_t k);
 int shard_delete_users_run(pie_ctx* c, const int32_t* users_global, size_t k, size_t* m_out, int32_t* per_user_out);
 int shard_delete_users_copy(pie_ctx* c, int32_t* rows_global_out, size_t m);
+// ... and what the in-flight calls need beyond pie_shard_token_lookup_* / pie_shard_expired_queue_*: a begin's checks with nothing
+// begun, the newest lookup taken back, the finished queue left in the pass's own buffer (its bounded wait; the pass is consumed)
+int shard_token_flight_check(pie_ctx* c, const char* what);
+int shard_expq_check(pie_ctx* c, const char* what);
+int shard_token_flight_drop_last(pie_ctx* c, const char* what);
+int shard_expq_take(pie_ctx* c, const char* what, const int32_t** rows_dev_out, size_t* len_out, void** stream_out, void** done_out);
+void shard_expq_stale(pie_ctx* c);
 } // namespace pie_internal
 
 namespace {
@@ -150,6 +157,24 @@ struct pie_comm {
     hipEvent_t q_tev[5] = {};                     // timing of the last queue call on the first local rank's stream
     bool q_timed = false;
     double wait_deadline_ms = 20000.0;            // bound of every wait of the queue path and the steps (PIE_WAIT_DEADLINE_MS)
+    // token lookups and the expired queue while steps are in flight (pie_comm_token_lookup_begin ..., pie_comm_expired_queue_begin
+    // ...): what the communicator has begun on every local shard, and the merged queue on the first local rank's device
+    static constexpr int kLookups = 4;            // a shard's own slots (pie_token_lookup_room of an idle shard)
+    size_t lk_k[kLookups] = {};                   // keys of the lookups begun and unfinished, a ring from lk_head
+    int lk_head = 0, lk_n = 0;
+    bool xq_begun = false;
+    bool xq_stage_all = false;                    // PIE_COMM_STAGE_ALL=1: every shard's list is brought over, same device or not (tests)
+    size_t xq_cap_rows = 0;                       // of the begin
+    int *xq_rows = nullptr, *xq_owner = nullptr;  // the merged list: global rows, owning ranks
+    size_t xq_room = 0;
+    int* xq_stage = nullptr;                      // lists brought over from other devices, back to back
+    size_t xq_stage_room = 0;
+    void* xq_desc = nullptr;                      // the merge's descriptor (MergeDesc) on the device
+    char* xq_h = nullptr;                         // pinned: the descriptor going up, then rows and owners coming back
+    size_t xq_h_room = 0;                         // rows it holds behind the descriptor
+    hipEvent_t xq_ev = nullptr;
+    long long xq_total = -1, xq_have = 0;         // of the last finish: the true total (-1: none), the rows the merged list holds
+    std::vector<void*> xq_retired_dev, xq_retired_host; // blocks a begin outgrew: freed at destroy (a free waits for the whole device)
     char err[512] = "";
 };
 
@@ -228,12 +253,15 @@ pie_comm* new_comm(int world, int n_local)
     for (auto* v : {&c->qh_msg, &c->qh_gath, &c->q_msg, &c->q_gath, &c->q_rows, &c->q_src_rank, &c->q_src_row}) v->assign((size_t)n_local, nullptr);
     c->q_ev.assign((size_t)n_local, nullptr);
     if (const char* v = getenv("PIE_WAIT_DEADLINE_MS")) { const double d = atof(v); if (d > 0) c->wait_deadline_ms = d; }
+    if (const char* v = getenv("PIE_COMM_STAGE_ALL")) c->xq_stage_all = atoi(v) != 0;
     return c;
 }
 
 void free_queue_buffers(pie_comm* c);
 
 void free_step_buffers(pie_comm* c, pie_steps& st);
+
+void inflight_close(pie_comm* c);
 
 // the synchronous gather, the queues and the mutations stay out of the way of pipelined steps of either kind
 int steps_idle(pie_comm* c)
@@ -347,6 +375,7 @@ int pie_comm_create_rank(const void* id_128, int32_t rank, int32_t world, int32_
 int pie_comm_destroy(pie_comm* c)
 {
     if (!c) return PIE_OK;
+    inflight_close(c); // lookups and a queue begun and not finished land first (bounded waits)
     for (int k = 0; k < c->n_local; ++k) {
         (void)hipSetDevice(c->device[k]);
         if (c->stream[k]) (void)hipStreamSynchronize(c->stream[k]);
@@ -1502,6 +1531,367 @@ int pie_comm_wide_step_read_feed(pie_comm* c, int32_t at_rank, int32_t src_rank,
         }
     if (k_out) *k_out = kk;
     if (idx_out && kk > idx_cap) return cfail(c, PIE_E_CAPACITY, "idx_cap %zu < %zu rows", idx_cap, kk);
+    return PIE_OK;
+}
+
+} // extern "C"
+
+// ---- token lookups and the expired queue WHILE STEPS ARE IN FLIGHT (pie_comm_token_lookup_begin / _finish / _room,
+// pie_comm_expired_queue_begin / _finish / _room): pie_shard_token_lookup_* / pie_shard_expired_queue_* on every local shard.  No
+// RCCL call, no exchange stream, no step buffer set, no wait on a context's stream or a lane: every shard's pass runs on its own
+// side stream and every host wait is a bounded one (pie_wait.h).  The communicator counts what it has begun; a shard whose own
+// room says otherwise was used directly (pie_shard_* on a context from pie_comm_ctx) and the begin is refused with nothing taken.
+namespace {
+
+constexpr int kMergeMaxLists = 64; // local ranks at most (pie_comm_create: 1..64)
+
+// what the merge reads: every local shard's ascending list of GLOBAL rows (the shard's own queue buffer, or its copy on the
+// merging device), its kept length, its rank, and the lists' running lengths; `count` lists, pre[count] elements
+struct MergeDesc {
+    const int* rows[kMergeMaxLists];
+    long long pre[kMergeMaxLists + 1];
+    int n[kMergeMaxLists];
+    int rank[kMergeMaxLists];
+    int count, pad;
+};
+
+// One lane per element, placed by co-rank: its index in its own list plus, for every other list, how many of that list's rows
+// are smaller (a lower bound; global rows are unique across shards).  No atomics, no wave waits for another.  A position at or
+// past out_cap is not written: the first out_cap merged rows only ever come from the first out_cap rows of each list.
+__global__ __launch_bounds__(256) void k_merge_shard_queues(const MergeDesc* __restrict__ desc, long long out_cap, int* __restrict__ out_rows,
+                                                            int* __restrict__ out_rank)
+{
+    __shared__ MergeDesc s;
+    for (int w = (int)threadIdx.x; w < (int)(sizeof(MergeDesc) / 4); w += (int)blockDim.x)
+        reinterpret_cast<int*>(&s)[w] = reinterpret_cast<const int*>(desc)[w];
+    __syncthreads();
+    const int count = min(max(s.count, 0), kMergeMaxLists);
+    const long long total = s.pre[count];
+    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long long)gridDim.x * blockDim.x) {
+        int r = 0;
+        while (r + 1 < count && s.pre[r + 1] <= e) ++r;
+        const long long i = e - s.pre[r];
+        if (i >= s.n[r]) continue; // (a descriptor that does not add up reads nothing)
+        const int v = s.rows[r][i];
+        long long pos = i;
+        for (int p = 0; p < count; ++p) {
+            if (p == r) continue;
+            const int* other = s.rows[p];
+            int lo = 0, hi = s.n[p];
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (other[mid] < v) lo = mid + 1;
+                else hi = mid;
+            }
+            pos += lo;
+        }
+        if (pos < out_cap) {
+            out_rows[pos] = v;
+            out_rank[pos] = s.rank[r];
+        }
+    }
+}
+
+bool xq_staged(const pie_comm* c, int k) { return c->xq_stage_all || c->device[k] != c->device[0]; }
+
+// The merged list, the staging of lists held on other devices, the descriptor and the pinned block, sized by the begin.  A block
+// a begin outgrew is set aside until pie_comm_destroy: hipFree and hipHostFree wait for the whole device, the steps included.
+int xq_ensure(pie_comm* c, size_t cap_rows)
+{
+    PIE_CHIP(c, hipSetDevice(c->device[0]));
+    if (!c->xq_ev) PIE_CHIP(c, hipEventCreateWithFlags(&c->xq_ev, hipEventDisableTiming));
+    if (!c->xq_desc) PIE_CHIP(c, hipMalloc(&c->xq_desc, sizeof(MergeDesc)));
+    try {
+        if (!c->xq_h || cap_rows > c->xq_room) {
+            size_t rows = c->xq_room ? c->xq_room : 4096;
+            while (rows < cap_rows) rows *= 2;
+            int *nr = nullptr, *no = nullptr;
+            char* nh = nullptr;
+            c->xq_retired_dev.reserve(c->xq_retired_dev.size() + 2);
+            c->xq_retired_host.reserve(c->xq_retired_host.size() + 1);
+            PIE_CHIP(c, hipMalloc(&nr, rows * 4));
+            if (hipMalloc(&no, rows * 4) != hipSuccess || hipHostMalloc(&nh, sizeof(MergeDesc) + rows * 8, hipHostMallocDefault) != hipSuccess) {
+                (void)hipGetLastError();
+                c->xq_retired_dev.push_back(nr);
+                if (no) c->xq_retired_dev.push_back(no);
+                return cfail(c, PIE_E_NOMEM, "no memory for a merged queue of %zu rows", cap_rows);
+            }
+            if (c->xq_rows) c->xq_retired_dev.push_back(c->xq_rows);
+            if (c->xq_owner) c->xq_retired_dev.push_back(c->xq_owner);
+            if (c->xq_h) c->xq_retired_host.push_back(c->xq_h);
+            c->xq_rows = nr;
+            c->xq_owner = no;
+            c->xq_h = nh;
+            c->xq_room = rows;
+        }
+        size_t staged = 0;
+        for (int k = 0; k < c->n_local; ++k) staged += xq_staged(c, k) ? 1 : 0;
+        if (staged * cap_rows > c->xq_stage_room) {
+            size_t rows = c->xq_stage_room ? c->xq_stage_room : 4096;
+            while (rows < staged * cap_rows) rows *= 2;
+            int* ns = nullptr;
+            c->xq_retired_dev.reserve(c->xq_retired_dev.size() + 1);
+            PIE_CHIP(c, hipMalloc(&ns, rows * 4));
+            if (c->xq_stage) c->xq_retired_dev.push_back(c->xq_stage);
+            c->xq_stage = ns;
+            c->xq_stage_room = rows;
+        }
+    } catch (const std::bad_alloc&) {
+        return cfail(c, PIE_E_NOMEM, "out of host memory");
+    }
+    return PIE_OK;
+}
+
+// pie_comm_destroy: what was begun and not finished lands (every wait bounded), then the buffers go
+void inflight_close(pie_comm* c)
+{
+    for (; c->lk_n > 0; c->lk_n--)
+        for (int k = 0; k < c->n_local; ++k)
+            if (c->ctx[k]) (void)pie_shard_token_lookup_finish(c->ctx[k], nullptr, nullptr, nullptr, nullptr, nullptr, (size_t)-1, nullptr);
+    if (c->xq_begun)
+        for (int k = 0; k < c->n_local; ++k)
+            if (c->ctx[k]) (void)pie_shard_expired_queue_finish(c->ctx[k], nullptr, 0, nullptr);
+    c->xq_begun = false;
+    if (c->n_local > 0) (void)hipSetDevice(c->device[0]);
+    for (void* p : c->xq_retired_dev) (void)hipFree(p);
+    for (void* p : c->xq_retired_host) (void)hipHostFree(p);
+    c->xq_retired_dev.clear();
+    c->xq_retired_host.clear();
+    for (void* p : {(void*)c->xq_rows, (void*)c->xq_owner, (void*)c->xq_stage, c->xq_desc})
+        if (p) (void)hipFree(p);
+    if (c->xq_h) (void)hipHostFree(c->xq_h);
+    if (c->xq_ev) (void)hipEventDestroy(c->xq_ev);
+    c->xq_rows = c->xq_owner = c->xq_stage = nullptr;
+    c->xq_desc = nullptr;
+    c->xq_h = nullptr;
+    c->xq_ev = nullptr;
+    c->xq_room = c->xq_stage_room = 0;
+    c->xq_total = -1;
+}
+
+} // namespace
+
+extern "C" {
+
+int pie_comm_token_lookup_room(pie_comm* c)
+{
+    if (!c) return PIE_E_INVAL;
+    int room = pie_comm::kLookups - c->lk_n;
+    for (int k = 0; k < c->n_local; ++k) room = std::min(room, pie_token_lookup_room(c->ctx[k]));
+    return room;
+}
+
+int pie_comm_token_lookup_begin(pie_comm* c, const uint64_t* tok, const int64_t* now, size_t k)
+{
+    if (!c) return PIE_E_INVAL;
+    const char* what = "pie_comm_token_lookup_begin";
+    // every local shard is asked before any begins
+    for (int i = 0; i < c->n_local; ++i) PIE_CCTX(c, i, pie_internal::shard_token_flight_check(c->ctx[i], what));
+    for (int i = 0; i < c->n_local; ++i) {
+        const int begun = pie_comm::kLookups - pie_token_lookup_room(c->ctx[i]);
+        if (begun != c->lk_n)
+            return cfail(c, PIE_E_STATE, "%s: rank %d has %d lookups begun, the communicator %d: pie_shard_token_lookup_* was used on its context directly",
+                         what, c->rank_of[i], begun, c->lk_n);
+    }
+    if (c->lk_n >= pie_comm::kLookups) return cfail(c, PIE_E_STATE, "%s: %d lookups are begun and not finished", what, c->lk_n);
+    if (k > 0 && (!tok || !now)) return cfail(c, PIE_E_INVAL, "%s: NULL pointer", what);
+    if (k >= ((size_t)1 << 31)) return cfail(c, PIE_E_INVAL, "%s: %zu keys in one lookup", what, k);
+    for (int i = 0; i < c->n_local; ++i) {
+        const int rc = pie_shard_token_lookup_begin(c->ctx[i], tok, now, k);
+        if (rc == PIE_OK) continue;
+        cfail(c, rc, "rank %d: %s", c->rank_of[i], pie_last_error(c->ctx[i]));
+        for (int j = 0; j < i; ++j) (void)pie_internal::shard_token_flight_drop_last(c->ctx[j], what); // finished and discarded
+        return rc;
+    }
+    c->lk_k[(c->lk_head + c->lk_n) % pie_comm::kLookups] = k;
+    c->lk_n++;
+    return PIE_OK;
+}
+
+int pie_comm_token_lookup_finish(pie_comm* c, int32_t* row_out, uint8_t* live_out, int32_t* user_out, int64_t* start_out, int64_t* end_out,
+                                 int32_t* owner_rank_out, size_t cap, size_t* k_out)
+{
+    if (!c) return PIE_E_INVAL;
+    const char* what = "pie_comm_token_lookup_finish";
+    if (c->lk_n == 0) return cfail(c, PIE_E_STATE, "%s: no lookup was begun", what);
+    const size_t k = c->lk_k[c->lk_head];
+    if (k_out) *k_out = k;
+    if (cap < k) return cfail(c, PIE_E_CAPACITY, "%s: %zu keys, room for %zu", what, k, cap);
+    std::vector<int32_t> best, row, user;
+    std::vector<uint8_t> live;
+    std::vector<int64_t> start, end;
+    try {
+        best.assign(k, -1);
+        row.resize(k);
+        user.resize(k);
+        live.resize(k);
+        start.resize(k);
+        end.resize(k);
+    } catch (...) {
+        return cfail(c, PIE_E_NOMEM, "%s: no memory for %zu answers", what, k); // nothing consumed
+    }
+    if (live_out && k) memset(live_out, 0, k);
+    if (owner_rank_out) for (size_t j = 0; j < k; ++j) owner_rank_out[j] = -1;
+    // the merge pie_comm_token_lookup does: per key the shard with the largest global row answers
+    int first_rc = PIE_OK, first_bad = -1;
+    for (int i = 0; i < c->n_local; ++i) {
+        size_t kk = 0;
+        int rc = pie_shard_token_lookup_finish(c->ctx[i], row.data(), live.data(), user.data(), start.data(), end.data(), k, &kk);
+        if (rc == PIE_OK && kk != k) rc = PIE_E_STATE; // (not the lookup the communicator began)
+        if (rc) { // the other shards' slots are returned all the same
+            if (first_rc == PIE_OK) { first_rc = rc; first_bad = i; }
+            continue;
+        }
+        for (size_t j = 0; j < k; ++j) {
+            if (row[j] <= best[j]) continue;
+            best[j] = row[j];
+            if (live_out) live_out[j] = live[j];
+            if (user_out) user_out[j] = user[j];
+            if (start_out) start_out[j] = start[j];
+            if (end_out) end_out[j] = end[j];
+            if (owner_rank_out) owner_rank_out[j] = c->rank_of[i];
+        }
+    }
+    c->lk_head = (c->lk_head + 1) % pie_comm::kLookups;
+    c->lk_n--;
+    if (first_rc) return cfail(c, first_rc, "rank %d: %s", c->rank_of[first_bad], pie_last_error(c->ctx[first_bad]));
+    if (row_out && k) memcpy(row_out, best.data(), k * 4);
+    return PIE_OK;
+}
+
+int pie_comm_expired_queue_room(pie_comm* c)
+{
+    if (!c) return PIE_E_INVAL;
+    int room = c->xq_begun ? 0 : 1;
+    for (int k = 0; k < c->n_local; ++k) room = std::min(room, pie_expired_queue_room(c->ctx[k]));
+    return room;
+}
+
+int pie_comm_expired_queue_begin(pie_comm* c, int64_t prev_now, int64_t now, size_t cap_rows)
+{
+    if (!c) return PIE_E_INVAL;
+    const char* what = "pie_comm_expired_queue_begin";
+    for (int i = 0; i < c->n_local; ++i) PIE_CCTX(c, i, pie_internal::shard_expq_check(c->ctx[i], what));
+    for (int i = 0; i < c->n_local; ++i)
+        if ((pie_expired_queue_room(c->ctx[i]) == 0) != c->xq_begun)
+            return cfail(c, PIE_E_STATE, "%s: rank %d %s a queue begun, the communicator %s: pie_shard_expired_queue_* was used on its context directly",
+                         what, c->rank_of[i], c->xq_begun ? "has not" : "has", c->xq_begun ? "has" : "has none");
+    if (c->xq_begun) return cfail(c, PIE_E_STATE, "%s: an expired queue is begun and not finished", what);
+    if (cap_rows >= ((size_t)1 << 31)) return cfail(c, PIE_E_INVAL, "%s: cap_rows %zu", what, cap_rows);
+    if (cap_rows > 0) {
+        const int rc = xq_ensure(c, cap_rows);
+        if (rc) return rc;
+    }
+    for (int i = 0; i < c->n_local; ++i) {
+        const int rc = pie_shard_expired_queue_begin(c->ctx[i], prev_now, now, cap_rows);
+        if (rc == PIE_OK) continue;
+        cfail(c, rc, "rank %d: %s", c->rank_of[i], pie_last_error(c->ctx[i]));
+        for (int j = 0; j < i; ++j) (void)pie_shard_expired_queue_finish(c->ctx[j], nullptr, 0, nullptr); // finished and discarded
+        return rc;
+    }
+    c->xq_cap_rows = cap_rows;
+    c->xq_begun = true;
+    c->xq_total = -1; // the merged list of the queue before is gone
+    c->xq_have = 0;
+    return PIE_OK;
+}
+
+int pie_comm_expired_queue_finish(pie_comm* c, int32_t* rows_out, int32_t* owner_rank_out, size_t cap, size_t* q_out)
+{
+    if (!c) return PIE_E_INVAL;
+    const char* what = "pie_comm_expired_queue_finish";
+    if (!c->xq_begun) return cfail(c, PIE_E_STATE, "%s: no expired queue was begun", what);
+    const size_t cap_rows = c->xq_cap_rows;
+    if ((rows_out || owner_rank_out) && cap < cap_rows)
+        return cfail(c, PIE_E_INVAL, "%s: room for %zu rows, the begin asked for %zu", what, cap, cap_rows);
+    // 1. every shard's bounded wait; its list stays in its own queue buffer
+    const int32_t* list[kMergeMaxLists] = {};
+    size_t len[kMergeMaxLists] = {};
+    void* done[kMergeMaxLists] = {};
+    void* s0 = nullptr;
+    int first_rc = PIE_OK, first_bad = -1;
+    for (int i = 0; i < c->n_local; ++i) {
+        void* s = nullptr;
+        const int rc = pie_internal::shard_expq_take(c->ctx[i], what, &list[i], &len[i], &s, &done[i]);
+        if (rc && first_rc == PIE_OK) { first_rc = rc; first_bad = i; }
+        if (i == 0) s0 = s;
+    }
+    c->xq_begun = false; // consumed on every shard, whatever the waits said
+    if (first_rc) return cfail(c, first_rc, "rank %d: %s", c->rank_of[first_bad], pie_last_error(c->ctx[first_bad]));
+    size_t total = 0, kept_sum = 0;
+    for (int i = 0; i < c->n_local; ++i) {
+        total += len[i];
+        kept_sum += std::min(len[i], cap_rows);
+    }
+    if (q_out) *q_out = total;
+    const size_t have = std::min(kept_sum, cap_rows);
+    if (have > 0) {
+        // 2. lists held on other devices come over behind their pass; 3. the merge, on the first shard's pass stream
+        hipStream_t ms = (hipStream_t)s0;
+        MergeDesc* d = reinterpret_cast<MergeDesc*>(c->xq_h);
+        memset(d, 0, sizeof(MergeDesc));
+        PIE_CHIP(c, hipSetDevice(c->device[0]));
+        size_t staged_at = 0;
+        long long acc = 0;
+        const bool to_host = rows_out || owner_rank_out;
+        hipError_t e = hipSuccess;
+        for (int i = 0; i < c->n_local && e == hipSuccess; ++i) {
+            const size_t kept = std::min(len[i], cap_rows);
+            d->rows[i] = list[i];
+            d->n[i] = (int)kept;
+            d->rank[i] = c->rank_of[i];
+            d->pre[i] = acc;
+            acc += (long long)kept;
+            if (kept == 0) continue;
+            if (i > 0 && done[i]) e = hipStreamWaitEvent(ms, (hipEvent_t)done[i], 0);
+            if (e == hipSuccess && xq_staged(c, i)) {
+                int* dst = c->xq_stage + staged_at;
+                staged_at += kept;
+                e = c->device[i] != c->device[0] ? hipMemcpyPeerAsync(dst, c->device[0], list[i], c->device[i], kept * 4, ms)
+                                                 : hipMemcpyAsync(dst, list[i], kept * 4, hipMemcpyDeviceToDevice, ms);
+                d->rows[i] = dst;
+            }
+        }
+        d->pre[c->n_local] = acc;
+        d->count = c->n_local;
+        int* h_rows = reinterpret_cast<int*>(c->xq_h + sizeof(MergeDesc));
+        int* h_owner = h_rows + c->xq_room;
+        if (e == hipSuccess) e = hipMemcpyAsync(c->xq_desc, d, sizeof(MergeDesc), hipMemcpyHostToDevice, ms);
+        if (e == hipSuccess) {
+            const long long blocks = std::min<long long>((acc + 255) / 256, 2048);
+            hipLaunchKernelGGL(k_merge_shard_queues, dim3((unsigned)blocks), dim3(256), 0, ms, (const MergeDesc*)c->xq_desc, (long long)have, c->xq_rows,
+                               c->xq_owner);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess && to_host && rows_out) e = hipMemcpyAsync(h_rows, c->xq_rows, have * 4, hipMemcpyDeviceToHost, ms);
+        if (e == hipSuccess && to_host && owner_rank_out) e = hipMemcpyAsync(h_owner, c->xq_owner, have * 4, hipMemcpyDeviceToHost, ms);
+        if (e == hipSuccess) e = hipEventRecord(c->xq_ev, ms);
+        if (e != hipSuccess) {
+            pie_internal::shard_expq_stale(c->ctx[0]); // what was queued may still read a shard's buffer: the next begin drains the stream
+            return cfail(c, PIE_E_HIP, "%s: %s", what, hipGetErrorString(e));
+        }
+        const int rc = wait_event(c, 0, c->xq_ev, "in-flight queue merge");
+        if (rc) {
+            pie_internal::shard_expq_stale(c->ctx[0]);
+            return rc;
+        }
+        if (rows_out) memcpy(rows_out, h_rows, have * 4);
+        if (owner_rank_out) memcpy(owner_rank_out, h_owner, have * 4);
+    }
+    c->xq_total = (long long)total;
+    c->xq_have = (long long)have;
+    if (cap_rows > 0 && total > cap_rows) return cfail(c, PIE_E_CAPACITY, "%s: %zu rows, the begin asked for %zu", what, total, cap_rows);
+    return PIE_OK;
+}
+
+int pie_comm_inflight_queue_device_ptrs(pie_comm* c, void** rows_dev, void** owner_rank_dev, size_t* n_out, size_t* q_out)
+{
+    if (!c) return PIE_E_INVAL;
+    if (c->xq_total < 0) return cfail(c, PIE_E_STATE, "no merged in-flight queue: pie_comm_expired_queue_begin / _finish first");
+    if (rows_dev) *rows_dev = c->xq_have ? c->xq_rows : nullptr;
+    if (owner_rank_dev) *owner_rank_dev = c->xq_have ? c->xq_owner : nullptr;
+    if (n_out) *n_out = (size_t)c->xq_have;
+    if (q_out) *q_out = (size_t)c->xq_total;
     return PIE_OK;
 }
 

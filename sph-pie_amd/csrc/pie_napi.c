@@ -112,7 +112,13 @@
     X(int, pie_comm_token_set, (pie_comm *, const uint64_t *, size_t))                                               \
     X(int, pie_comm_token_append, (pie_comm *, const uint64_t *, size_t))                                            \
     X(int, pie_comm_token_lookup, (pie_comm *, const uint64_t *, size_t, int64_t, int32_t *, uint8_t *, int32_t *, int64_t *, int64_t *, int32_t *)) \
-    X(int, pie_comm_token_set_end, (pie_comm *, const uint64_t *, const int64_t *, size_t, int64_t, int32_t *))
+    X(int, pie_comm_token_set_end, (pie_comm *, const uint64_t *, const int64_t *, size_t, int64_t, int32_t *))                     \
+    X(int, pie_comm_token_lookup_begin, (pie_comm *, const uint64_t *, const int64_t *, size_t))                     \
+    X(int, pie_comm_token_lookup_finish, (pie_comm *, int32_t *, uint8_t *, int32_t *, int64_t *, int64_t *, int32_t *, size_t, size_t *)) \
+    X(int, pie_comm_token_lookup_room, (pie_comm *))                                                                 \
+    X(int, pie_comm_expired_queue_begin, (pie_comm *, int64_t, int64_t, size_t))                                     \
+    X(int, pie_comm_expired_queue_finish, (pie_comm *, int32_t *, int32_t *, size_t, size_t *))                      \
+    X(int, pie_comm_expired_queue_room, (pie_comm *))
 
 #define X(ret, name, args) static ret(*p_##name) args;
 PIE_SYMBOLS(X)
@@ -1318,6 +1324,13 @@ typedef struct comm_box_s {
     pie_comm *comm;
     ctx_box *boxes; /* context handles handed out by commCtx and still alive */
     pie_nq_ring step_nq, wide_nq; /* n_q of the ordinary / wide steps begun and not finished on THIS communicator */
+    /* what THIS communicator has begun beside its steps and not finished: the keys of every lookup (commTokenLookupBegin), oldest
+     * first, and the rows the queue's finish has to make room for (commExpiredQueueBegin) */
+    size_t lk_k[4];
+    int lk_head, lk_n;
+    size_t eq_cap;
+    int eq_begun;
+    int busy; /* a finish of either is waiting on the libuv pool: one thread per communicator */
 } comm_box;
 
 enum { STEP_SETS = 16, WIDE_STEP_SETS = 8 }; /* the rings' capacities: the buffer sets of pie_comm_step_* / pie_comm_wide_step_* */
@@ -1349,6 +1362,7 @@ static void comm_orphan_ctxs(comm_box *cb)
 
 static int comm_any_busy(const comm_box *cb)
 {
+    if (cb->busy) return 1;
     for (const ctx_box *b = cb->boxes; b; b = b->next)
         if (b->busy) return 1;
     return 0;
@@ -1429,6 +1443,7 @@ static napi_value fn_comm_destroy(napi_env env, napi_callback_info info)
     b->comm = NULL;
     nq_ring_clear(&b->step_nq);
     nq_ring_clear(&b->wide_nq);
+    b->lk_head = b->lk_n = b->eq_begun = 0; /* pie_comm_destroy landed what was begun */
     return js_int(env, 0);
 }
 
@@ -1453,6 +1468,7 @@ static napi_value fn_comm_ctx(napi_env env, napi_callback_info info)
     void *pcb = NULL;
     CHECK(env, napi_get_value_external(env, argv[0], &pcb));
     comm_box *cb = (comm_box *)pcb;
+    if (cb->busy) return throw_state(env, "pie_comm error -6: a finish of this communicator is waiting on the pool");
     ctx_box *b = (ctx_box *)calloc(1, sizeof *b);
     napi_value ext;
     if (!b || napi_create_reference(env, argv[0], 1, &b->comm_ref) != napi_ok) {
@@ -2537,6 +2553,253 @@ static napi_value fn_comm_token_set_end(napi_env env, napi_callback_info info)
     return out;
 }
 
+/* ---- token lookups and the purge tick while steps are in flight (pie_comm_token_lookup_begin / _finish / _room,
+ * pie_comm_expired_queue_begin / _finish / _room).  A begin queues the work on every local shard's side stream and returns; a finish
+ * waits on the libuv pool and resolves a Promise, so neither the event loop nor the steps in flight wait for it.  The communicator
+ * and the contexts handed out by commCtx are busy meanwhile (one thread per communicator). */
+static void comm_set_busy(comm_box *cb, int v)
+{
+    cb->busy = v;
+    for (ctx_box *b = cb->boxes; b; b = b->next) b->busy = v;
+}
+
+static int queue_comm_job(napi_env env, comm_box *cb, const char *name, napi_async_execute_callback exec, napi_async_complete_callback done,
+                          void *job, napi_async_work *work)
+{
+    napi_value res;
+    napi_create_string_utf8(env, name, NAPI_AUTO_LENGTH, &res);
+    comm_set_busy(cb, 1);
+    if (napi_create_async_work(env, NULL, res, exec, done, job, work) == napi_ok && napi_queue_async_work(env, *work) == napi_ok) return 1;
+    comm_set_busy(cb, 0);
+    napi_throw_error(env, NULL, "cannot queue async work");
+    return 0;
+}
+
+/* commTokenLookupBegin(comm, keys, nows BigInt64Array: one clock per key) -> k */
+static napi_value fn_comm_token_lookup_begin(napi_env env, napi_callback_info info)
+{
+    ARGS(3)
+    comm_box *cbx = get_comm_box(env, argv[0]);
+    if (!cbx) return NULL;
+    size_t k = 0, kn = 0;
+    uint64_t *keys = token_keys(env, argv[1], &k);
+    if (!keys) return NULL;
+    int64_t *nows = typed(env, argv[2], napi_bigint64_array, &kn);
+    if (!nows || kn != k) {
+        napi_throw_type_error(env, NULL, "commTokenLookupBegin(comm, BigUint64Array keys, BigInt64Array nows): one clock per key");
+        return NULL;
+    }
+    if (cbx->lk_n >= 4) return throw_state(env, "pie_comm error -6: four token lookups are begun and not finished");
+    int rc = p_pie_comm_token_lookup_begin(cbx->comm, keys, nows, k);
+    if (rc) return throw_comm(env, cbx->comm, rc);
+    cbx->lk_k[(cbx->lk_head + cbx->lk_n) % 4] = k;
+    cbx->lk_n++;
+    return js_int(env, (int64_t)k);
+}
+
+/* commTokenLookupRoom(comm) -> lookups commTokenLookupBegin would take now */
+static napi_value fn_comm_token_lookup_room(napi_env env, napi_callback_info info)
+{
+    ARGS(1)
+    comm_box *cbx = get_comm_box(env, argv[0]);
+    if (!cbx) return NULL;
+    return js_int(env, p_pie_comm_token_lookup_room(cbx->comm));
+}
+
+typedef struct {
+    napi_async_work work;
+    napi_deferred deferred;
+    napi_ref result;
+    comm_box *box;
+    size_t k;
+    int32_t *row, *user, *owner;
+    uint8_t *live;
+    int64_t *start, *end;
+    int rc;
+    char err[600];
+} comm_lookup_job;
+
+static void comm_lookup_exec(napi_env env, void *data)
+{
+    (void)env;
+    comm_lookup_job *j = (comm_lookup_job *)data;
+    j->rc = p_pie_comm_token_lookup_finish(j->box->comm, j->row, j->live, j->user, j->start, j->end, j->owner, j->k, NULL);
+    if (j->rc) snprintf(j->err, sizeof j->err, "pie_comm error %d: %s", j->rc, p_pie_comm_last_error(j->box->comm));
+}
+
+static void comm_lookup_done(napi_env env, napi_status status, void *data)
+{
+    comm_lookup_job *j = (comm_lookup_job *)data;
+    comm_set_busy(j->box, 0);
+    napi_value out;
+    if (status != napi_ok || j->rc) {
+        reject_with_code(env, j->deferred, j->rc, j->rc ? j->err : "token lookup cancelled", -1);
+    } else {
+        napi_get_reference_value(env, j->result, &out);
+        napi_resolve_deferred(env, j->deferred, out);
+    }
+    napi_delete_reference(env, j->result);
+    napi_delete_async_work(env, j->work);
+    free(j);
+}
+
+/* commTokenLookupFinish(comm) -> Promise of commTokenLookup's object for the oldest lookup begun; the wait runs on the libuv pool */
+static napi_value fn_comm_token_lookup_finish(napi_env env, napi_callback_info info)
+{
+    ARGS(1)
+    comm_box *cbx = get_comm_box(env, argv[0]);
+    if (!cbx) return NULL;
+    if (cbx->lk_n == 0) return throw_state(env, "pie_comm error -6: no token lookup was begun");
+    const size_t k = cbx->lk_k[cbx->lk_head];
+    comm_lookup_job *j = (comm_lookup_job *)calloc(1, sizeof *j);
+    if (!j) {
+        napi_throw_error(env, NULL, "out of memory");
+        return NULL;
+    }
+    napi_value out, promise;
+    if (napi_create_object(env, &out) != napi_ok) {
+        free(j);
+        napi_throw_error(env, NULL, "N-API call failed: result object");
+        return NULL;
+    }
+    j->box = cbx;
+    j->k = k;
+    j->row = token_out(env, out, "row", napi_int32_array, 4, k);
+    j->live = token_out(env, out, "live", napi_uint8_array, 1, k);
+    j->user = token_out(env, out, "user", napi_int32_array, 4, k);
+    j->start = token_out(env, out, "start", napi_bigint64_array, 8, k);
+    j->end = token_out(env, out, "end", napi_bigint64_array, 8, k);
+    j->owner = token_out(env, out, "owner", napi_int32_array, 4, k);
+    if (!j->row || !j->live || !j->user || !j->start || !j->end || !j->owner) {
+        free(j);
+        return NULL;
+    }
+    if (napi_create_reference(env, out, 1, &j->result) != napi_ok || napi_create_promise(env, &j->deferred, &promise) != napi_ok) {
+        free(j);
+        napi_throw_error(env, NULL, "N-API call failed: promise");
+        return NULL;
+    }
+    if (!queue_comm_job(env, cbx, "pie_comm_token_lookup_finish", comm_lookup_exec, comm_lookup_done, j, &j->work)) {
+        napi_delete_reference(env, j->result);
+        free(j);
+        return NULL;
+    }
+    cbx->lk_head = (cbx->lk_head + 1) % 4; /* the library returns the slots whatever the waits say (cap = k: never PIE_E_CAPACITY) */
+    cbx->lk_n--;
+    return promise;
+}
+
+/* commExpiredQueueBegin(comm, prevNow, now, capRows) -> capRows */
+static napi_value fn_comm_expired_queue_begin(napi_env env, napi_callback_info info)
+{
+    ARGS(4)
+    comm_box *cbx = get_comm_box(env, argv[0]);
+    if (!cbx) return NULL;
+    int64_t prev, now, cap;
+    if (!get_i64(env, argv[1], &prev) || !get_i64(env, argv[2], &now) || !get_i64(env, argv[3], &cap) || cap < 0) {
+        napi_throw_type_error(env, NULL, "commExpiredQueueBegin(comm, prevNow, now, capRows)");
+        return NULL;
+    }
+    int rc = p_pie_comm_expired_queue_begin(cbx->comm, prev, now, (size_t)cap);
+    if (rc) return throw_comm(env, cbx->comm, rc);
+    cbx->eq_cap = (size_t)cap;
+    cbx->eq_begun = 1;
+    return js_int(env, cap);
+}
+
+/* commExpiredQueueRoom(comm) -> 1 when commExpiredQueueBegin would be taken now, else 0 */
+static napi_value fn_comm_expired_queue_room(napi_env env, napi_callback_info info)
+{
+    ARGS(1)
+    comm_box *cbx = get_comm_box(env, argv[0]);
+    if (!cbx) return NULL;
+    return js_int(env, p_pie_comm_expired_queue_room(cbx->comm));
+}
+
+typedef struct {
+    napi_async_work work;
+    napi_deferred deferred;
+    comm_box *box;
+    size_t cap, q;
+    int32_t *rows, *owner; /* one block: rows[cap] then owner[cap] */
+    int rc;
+    char err[600];
+} comm_expq_job;
+
+static void comm_expq_exec(napi_env env, void *data)
+{
+    (void)env;
+    comm_expq_job *j = (comm_expq_job *)data;
+    j->rc = p_pie_comm_expired_queue_finish(j->box->comm, j->cap ? j->rows : NULL, j->cap ? j->owner : NULL, j->cap, &j->q);
+    if (j->rc) snprintf(j->err, sizeof j->err, "pie_comm error %d: %s", j->rc, p_pie_comm_last_error(j->box->comm));
+}
+
+static int comm_expq_array(napi_env env, napi_value out, const char *name, const int32_t *src, size_t n)
+{
+    napi_value buf, arr;
+    void *mem = NULL;
+    if (napi_create_arraybuffer(env, n * 4, &mem, &buf) != napi_ok || napi_create_typedarray(env, napi_int32_array, n, buf, 0, &arr) != napi_ok) return 0;
+    if (n) memcpy(mem, src, n * 4);
+    return napi_set_named_property(env, out, name, arr) == napi_ok;
+}
+
+static void comm_expq_done(napi_env env, napi_status status, void *data)
+{
+    comm_expq_job *j = (comm_expq_job *)data;
+    comm_set_busy(j->box, 0);
+    napi_value out = NULL;
+    const size_t rows = j->q < j->cap ? j->q : j->cap;
+    int ok = status == napi_ok && !j->rc;
+    if (ok) {
+        ok = napi_create_object(env, &out) == napi_ok && comm_expq_array(env, out, "rows", j->rows, rows) &&
+             comm_expq_array(env, out, "owner", j->owner, rows);
+        if (!ok) snprintf(j->err, sizeof j->err, "N-API call failed: result arrays");
+    }
+    if (ok) {
+        napi_resolve_deferred(env, j->deferred, out);
+    } else { /* with the true length when the queue outgrew its room: begin again with room for it */
+        reject_with_code(env, j->deferred, j->rc, j->rc || status == napi_ok ? j->err : "expired queue cancelled", (int64_t)j->q);
+    }
+    napi_delete_async_work(env, j->work);
+    free(j->rows);
+    free(j);
+}
+
+/* commExpiredQueueFinish(comm) -> Promise of {rows Int32Array, owner Int32Array}: the merged queue in global rows and the rank that
+ * holds each (both empty when the begin said capRows = 0; the true `length` rides on the rejection when the queue outgrew
+ * capRows, code -5); the wait runs on the libuv pool */
+static napi_value fn_comm_expired_queue_finish(napi_env env, napi_callback_info info)
+{
+    ARGS(1)
+    comm_box *cbx = get_comm_box(env, argv[0]);
+    if (!cbx) return NULL;
+    if (!cbx->eq_begun) return throw_state(env, "pie_comm error -6: no expired queue was begun");
+    comm_expq_job *j = (comm_expq_job *)calloc(1, sizeof *j);
+    if (j) j->rows = (int32_t *)malloc((cbx->eq_cap ? cbx->eq_cap : 1) * 8);
+    if (!j || !j->rows) {
+        free(j);
+        napi_throw_error(env, NULL, "out of memory");
+        return NULL;
+    }
+    napi_value promise;
+    j->box = cbx;
+    j->cap = cbx->eq_cap;
+    j->owner = j->rows + (cbx->eq_cap ? cbx->eq_cap : 1);
+    if (napi_create_promise(env, &j->deferred, &promise) != napi_ok) {
+        free(j->rows);
+        free(j);
+        napi_throw_error(env, NULL, "N-API call failed: promise");
+        return NULL;
+    }
+    if (!queue_comm_job(env, cbx, "pie_comm_expired_queue_finish", comm_expq_exec, comm_expq_done, j, &j->work)) {
+        free(j->rows);
+        free(j);
+        return NULL;
+    }
+    cbx->eq_begun = 0; /* the library consumes the queue whatever the waits say (cap = capRows: never PIE_E_INVAL) */
+    return promise;
+}
+
 static napi_value init(napi_env env, napi_value exports)
 {
     static const struct {
@@ -2565,6 +2828,9 @@ static napi_value init(napi_env env, napi_value exports)
         {"scanBatchBegin", fn_scan_batch_begin}, {"scanBatchFinish", fn_scan_batch_finish}, {"tokenLookupBegin", fn_token_lookup_begin},
         {"tokenLookupFinish", fn_token_lookup_finish}, {"tokenLookupRoom", fn_token_lookup_room},
         {"expiredQueueBegin", fn_expired_queue_begin}, {"expiredQueueFinish", fn_expired_queue_finish}, {"expiredQueueRoom", fn_expired_queue_room},
+        {"commTokenLookupBegin", fn_comm_token_lookup_begin}, {"commTokenLookupFinish", fn_comm_token_lookup_finish},
+        {"commTokenLookupRoom", fn_comm_token_lookup_room}, {"commExpiredQueueBegin", fn_comm_expired_queue_begin},
+        {"commExpiredQueueFinish", fn_comm_expired_queue_finish}, {"commExpiredQueueRoom", fn_comm_expired_queue_room},
     };
     for (size_t i = 0; i < sizeof table / sizeof table[0]; ++i) {
         napi_value fn;

@@ -7360,15 +7360,23 @@ int pie_shard_token_lookup_finish(pie_ctx* c, int32_t* row_global_out, uint8_t* 
 // pie_expired_queue is refused in flight only because it borrows the scan slots' workspace; this form owns what it writes
 // (c->expq) and reads what scans and batches read.
 
-static int expq_begin(pie_ctx* c, int64_t prev_now, int64_t now, size_t cap_rows, bool global, const char* what)
+// the table a begin needs (the shard form: one whose row map covers its rows)
+static int expq_ready(pie_ctx* c, bool global, const char* what)
 {
-    if (!c) return PIE_E_INVAL;
     if (c->cap_rows == 0) return fail(c, PIE_E_STATE, "%s: no table loaded", what);
     if (global) {
         if (!c->shard_on || !c->d_shard_rows) return fail(c, PIE_E_STATE, "%s: the context holds no sharded table (pie_shard_table)", what);
         if (c->n != c->shard_rows_n)
             return fail(c, PIE_E_STATE, "%s: %lld rows were added after pie_shard_table: they have no global row", what, c->n - c->shard_rows_n);
     }
+    return PIE_OK;
+}
+
+static int expq_begin(pie_ctx* c, int64_t prev_now, int64_t now, size_t cap_rows, bool global, const char* what)
+{
+    if (!c) return PIE_E_INVAL;
+    const int ready_rc = expq_ready(c, global, what);
+    if (ready_rc) return ready_rc;
     pie_ctx::ExpiredFlight& x = c->expq;
     if (x.begun) return fail(c, PIE_E_STATE, "%s: an expired queue is begun and not finished", what);
     if (cap_rows >= ((size_t)1 << 31)) return fail(c, PIE_E_INVAL, "%s: cap_rows %zu", what, cap_rows);
@@ -7528,3 +7536,54 @@ int pie_expired_inflight_geometry(pie_ctx* c, size_t n, int32_t* rows_per_wave_s
 }
 
 } // extern "C"
+
+// What the communicator's in-flight calls (pie_comm_token_lookup_begin ..., pie_comm_expired_queue_begin ...) need of a shard
+// beyond the pie_shard_* entry points: the checks of a begin with nothing begun, the newest lookup taken back, and the finished
+// queue left where the pass wrote it.
+namespace pie_internal {
+int shard_token_flight_check(pie_ctx* c, const char* what) { return c ? token_flight_ready(c, what, true) : PIE_E_INVAL; }
+
+int shard_expq_check(pie_ctx* c, const char* what) { return c ? expq_ready(c, true, what) : PIE_E_INVAL; }
+
+// the lookup begun LAST is waited for (bounded) and its slot returned: a begin that went through here and failed on another shard
+int shard_token_flight_drop_last(pie_ctx* c, const char* what)
+{
+    if (!c) return PIE_E_INVAL;
+    pie_ctx::TokenIndex& t = c->tokx;
+    if (t.lk_n == 0) return fail(c, PIE_E_STATE, "%s: no lookup was begun", what);
+    if (hipSetDevice(c->device) != hipSuccess) (void)hipGetLastError();
+    const int rc = token_lookup_landed(c, t.lk[(t.lk_head + t.lk_n - 1) % kTokLookups], what);
+    t.lk_n--;
+    if (rc) t.side.stale = true;
+    return rc;
+}
+
+// pie_shard_expired_queue_finish without its copy: the bounded wait for the pass, which is consumed whatever the wait said.  The
+// queue stays in the pass's own buffer (GLOBAL rows, the first min(*len_out, cap_rows) of them) until the shard's next begin;
+// *stream_out is the pass's stream, *done_out the event behind its last kernel (nullptr: the pass had none).
+int shard_expq_take(pie_ctx* c, const char* what, const int32_t** rows_dev_out, size_t* len_out, void** stream_out, void** done_out)
+{
+    if (!c) return PIE_E_INVAL;
+    pie_ctx::ExpiredFlight& x = c->expq;
+    if (!x.begun) return fail(c, PIE_E_STATE, "%s: no expired queue was begun", what);
+    if (!x.global) return fail(c, PIE_E_STATE, "%s: the queue was begun by the plain form", what);
+    PIE_HIP(c, hipSetDevice(c->device));
+    const int rc = expq_land(c, what);
+    x.begun = false;
+    if (rc) {
+        x.side.stale = true;
+        return rc;
+    }
+    *rows_dev_out = x.d_buf;
+    *len_out = x.launched ? (size_t)x.h_sum->s.m : 0;
+    *stream_out = x.side.stream;
+    *done_out = x.launched ? x.fence.done : nullptr;
+    return PIE_OK;
+}
+
+// a reader of the pass's buffer on *stream_out gave up its wait: the shard's next begin drains that stream first
+void shard_expq_stale(pie_ctx* c)
+{
+    if (c) c->expq.side.stale = true;
+}
+} // namespace pie_internal

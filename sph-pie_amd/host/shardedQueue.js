@@ -9,6 +9,10 @@
 //     native   the addon (pieNative.load())
 //     comm     a communicator (native.commCreate) whose shards hold the table (commGenSyntheticSharded, or loaded and sharded)
 //     userIds  global user id -> userId string (default: 'user-' + id, the names of a synthetic base)
+// expiredRowsInFlight(prevNow, now) is the purge tick of a server that keeps pipelined steps in flight (commStepBegin ...): the
+// queue is begun on every shard's side stream (pie_comm_expired_queue_begin), the wait runs on the libuv pool, and the merged
+// rows come back with their owning rank; nothing is collected or drained.  The local row of each is found in the shard's row
+// map as read at creation, so fetchRows and dispatchQueue.dispatchExpiredSessions work on the result as on expiredRows'.
 const SESSION_TTL_MS = 12 * 60 * 60 * 1000;
 const END_NONE = -(2n ** 63n);
 const PIE_E_CAPACITY = -5;
@@ -26,7 +30,7 @@ function createShardedQueue(native, comm, options){
     const rowMap = new Int32Array(Math.max(rows, 1)), userMap = new Int32Array(Math.max(users, 1)).fill(-1);
     native.shardMaps(ctx, rowMap, userMap);
     for(let u = 0; u < users; u++){ nUsers = Math.max(nUsers, userMap[u] + 1); }
-    shards.push({ctx, users: userMap});
+    shards.push({ctx, users: userMap, rows: rowMap.subarray(0, rows)});
     totalRows += rows;
   }
   let userIds = opts.userIds || null;
@@ -54,6 +58,39 @@ function createShardedQueue(native, comm, options){
   function expiredRows(prevNow, now){
     const prev = prevNow === null || prevNow === undefined ? END_NONE : prevNow;
     return merged((rows, rank, local) => native.commExpiredQueue(comm, prev, now, rows, rank, local));
+  }
+
+  let flightRoom = 1024;                            // rows the next in-flight tick makes room for
+
+  // local row of a global row on its shard: the row maps are ascending
+  function localRow(rank, g){
+    const map = shards[rank].rows;
+    let lo = 0, hi = map.length;
+    while(lo < hi){
+      const mid = (lo + hi) >> 1;
+      if(map[mid] < g){ lo = mid + 1; }else{ hi = mid; }
+    }
+    if(lo >= map.length || map[lo] !== g){ throw new Error('row ' + g + ' is not in the map of rank ' + rank + ' (rows were added after the source was created)'); }
+    return lo;
+  }
+
+  // the same queue while steps stay in flight -> Promise of the rows; one tick at a time (commExpiredQueueRoom)
+  async function expiredRowsInFlight(prevNow, now){
+    const prev = prevNow === null || prevNow === undefined ? END_NONE : prevNow;
+    let room = Math.min(flightRoom, Math.max(totalRows, 1));
+    for(;;){
+      native.commExpiredQueueBegin(comm, prev, now, room);
+      try{
+        const got = await native.commExpiredQueueFinish(comm);
+        const local = Int32Array.from(got.rows, (g, i) => localRow(got.owner[i], g));
+        last = {rows: got.rows, rank: got.owner, local};
+        return last.rows;
+      }catch(err){
+        if(err.code !== PIE_E_CAPACITY || room >= totalRows){ throw err; }
+        room = Math.max(totalRows, 1);              // the queue outgrew its room: the whole table's, once
+        flightRoom = Math.max(flightRoom, Number(err.length) * 2); // the next tick asks for twice what this one needed
+      }
+    }
   }
 
   // the archive queue of the whole table: users whose earliest session is at least windowMs old, in order of first appearance
@@ -99,7 +136,7 @@ function createShardedQueue(native, comm, options){
   }
 
   return {
-    expiredRows, archivedRows, fetchRows,
+    expiredRows, expiredRowsInFlight, archivedRows, fetchRows,
     userIds: () => {
       if(userIds === null){ userIds = Array.from({length: nUsers}, (_, g) => 'user-' + g); }
       return userIds;
