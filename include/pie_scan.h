@@ -68,6 +68,13 @@ typedef struct pie_stats {
     uint32_t key_ambiguous; /* keyed form: rows of the last scan whose key equalled the query's and needed the full compare (saturating) */
     uint64_t live;         /* rows with end > now seen by the last scan */
     uint64_t candidates;   /* keyed form: rows whose key was >= the query's, i.e. payload records the table pass gathered */
+    /* fields below were added with the bucket-order route counters: a caller that sets struct_size to the size without them gets
+       the rest.  They describe the last single scan answered by the general path (0 after a batch, an ordered-run scan or the
+       partitioned path). */
+    uint32_t n_small;      /* buckets of 17..512 rows (and the 1..16-row buckets of hot users): ordered by one wave each */
+    uint32_t n_over;       /* listed buckets with staged records: outgrew the direct slots, belong to a hot user, or no slots exist */
+    uint32_t n_hot;        /* users the scan reported for the next scan's hot set (bucket > 1/256 of the previous M), at most 32 */
+    uint32_t direct_shift; /* log2 of the direct-slot capacity per user the scan ran with (4 .. 9; 0: no direct slots) */
 } pie_stats;
 
 /* ---- lifecycle ------------------------------------------------------------------------------------- */

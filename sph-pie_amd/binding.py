@@ -54,6 +54,7 @@ class PieStats(C.Structure):
         ("selected", C.c_uint64), ("alg_bytes", C.c_uint64), ("k1_ms_sum", C.c_double), ("scan_ms_sum", C.c_double),
         ("max_bucket", C.c_uint32), ("n_segments", C.c_uint32), ("n_big", C.c_uint32), ("k1_blocks", C.c_uint32),
         ("k1_variant", C.c_uint32), ("key_ambiguous", C.c_uint32), ("live", C.c_uint64), ("candidates", C.c_uint64),
+        ("n_small", C.c_uint32), ("n_over", C.c_uint32), ("n_hot", C.c_uint32), ("direct_shift", C.c_uint32),
     ]
 
 

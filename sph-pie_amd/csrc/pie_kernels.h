@@ -55,7 +55,7 @@ struct Summary {
     unsigned int bad_rows;      // rows whose user id fell outside [0, U): never selected, reported
     unsigned long long q;       // expired-queue length (pie_expired_queue)
     unsigned long long live;    // rows with end > now seen by K1 (drives the choice of K1 variant for the next scan)
-    unsigned int n_small;       // entries in the small-segment list (17..256 rows: one wave each)
+    unsigned int n_small;       // entries in the small-segment list (17..512 rows, or any size of a hot user: one wave each)
     unsigned int pad;
     unsigned long long amb;     // keyed table pass: rows whose liveness key equalled the query's (full `end` compare needed);
                                 // streaming pass: selected rows whose lane neighbour selected a row of the same user
@@ -127,7 +127,7 @@ constexpr int kK1Waves = kK1Threads / kWave;
 constexpr int kUnitRows = 2 * kWave;            // one int64x2 load per lane
 constexpr int kStage = 128;                     // per-wave LDS ring of selected records
 constexpr int kTinyMax = 16;
-constexpr int kSmallMax = 512;                  // buckets of 17..512 rows: sorted by ONE wave in LDS, no block barriers
+constexpr int kSmallMax = 512;                  // buckets of 17..512 rows: sorted by ONE wave in registers (no LDS, no block barriers)
 constexpr int kSegMax = 4096;
 constexpr int kScanTile = 2048;                 // counts per K2 block of the unfused form (256 threads x 8)
 

@@ -2027,7 +2027,7 @@ static napi_value fn_comm_wide_step_read(napi_env env, napi_callback_info info)
     return out;
 }
 
-/* stats(ctx) -> {rows, users, selected, algBytes, k1MsSum, scanMsSum, nProfiled, maxBucket} */
+/* stats(ctx) -> {rows, users, selected, algBytes, k1MsSum, scanMsSum, nProfiled, maxBucket, k1Variant, nSmall, nOver, nHot, directShift} */
 static napi_value fn_stats(napi_env env, napi_callback_info info)
 {
     ARGS(1)
@@ -2046,6 +2046,7 @@ static napi_value fn_stats(napi_env env, napi_callback_info info)
     PUT("rows", st.rows) PUT("users", st.users) PUT("selected", st.selected) PUT("algBytes", st.alg_bytes)
     PUT("k1MsSum", st.k1_ms_sum) PUT("scanMsSum", st.scan_ms_sum) PUT("nProfiled", st.n_profiled)
     PUT("maxBucket", st.max_bucket) PUT("k1Variant", st.k1_variant)
+    PUT("nSmall", st.n_small) PUT("nOver", st.n_over) PUT("nHot", st.n_hot) PUT("directShift", st.direct_shift)
 #undef PUT
     return o;
 }

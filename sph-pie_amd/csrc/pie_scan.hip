@@ -102,6 +102,7 @@ struct Slot {
     int k1_blocks = 0;
     long long rows_per_block = 0;
     int variant = 0;
+    int dshift = 0;    // log2 of the direct-slot capacity this scan ran with (0: no direct slots), for pie_stats
     int ev_index = -1; // index into the event ring, -1 = not profiled
 };
 
@@ -2109,6 +2110,7 @@ int scan_begin(pie_ctx* c, long long now, long long cutoff, int* msg, int msg_u_
     } else c->ord.wanted = 0;
     Slot& sl = c->slot[c->next_slot];
     hipStream_t s = c->stream;
+    sl.dshift = sl.direct ? c->dshift : 0;
     sl.ev_index = -1;
     if (c->profiling && (c->scans_begun % (unsigned long long)c->profile_every) == 0) {
         if (c->ring_used == kEventRing) {
@@ -5632,10 +5634,16 @@ int pie_set_profiling(pie_ctx* c, int enabled)
 int pie_stats_get(pie_ctx* c, pie_stats* out)
 {
     if (!c || !out) return PIE_E_INVAL;
-    if (out->struct_size != sizeof(pie_stats)) return fail(c, PIE_E_INVAL, "pie_stats.struct_size mismatch");
+    // the struct grows at its end (as pie_table_info does): a caller built against the form without the route counters gets the
+    // fields it knows
+    const uint32_t caller_size = out->struct_size;
+    if (caller_size != sizeof(pie_stats) && caller_size != offsetof(pie_stats, n_small)) return fail(c, PIE_E_INVAL, "pie_stats.struct_size mismatch");
     PIE_HIP(c, hipSetDevice(c->device));
     int rc = resolve_events(c);
     if (rc) return rc;
+    pie_stats full{};
+    pie_stats* const caller = out;
+    out = &full;
     const Slot* sl = c->res;
     out->n_profiled = c->n_profiled;
     out->rows = (uint64_t)c->n;
@@ -5652,6 +5660,12 @@ int pie_stats_get(pie_ctx* c, pie_stats* out)
     out->key_ambiguous = (c->res && (c->res->variant & 0x400)) ? (uint32_t)(c->res->last.amb > 0xFFFFFFFFull ? 0xFFFFFFFFull : c->res->last.amb) : 0u;
     out->live = sl ? sl->last.live : 0;
     out->candidates = (sl && (sl->variant & 0x400)) ? sl->last.cand : 0;
+    // the K2 route counters: words of the summary record the scan published anyway, and the capacity the host chose
+    const bool k2_route = sl && !sl->ordered && !sl->fast;
+    out->n_small = k2_route ? sl->last.n_small : 0;
+    out->n_over = k2_route ? sl->last.n_over : 0;
+    out->n_hot = k2_route ? (sl->last.n_hot < (unsigned)kHotMax ? sl->last.n_hot : (unsigned)kHotMax) : 0;
+    out->direct_shift = k2_route ? (uint32_t)sl->dshift : 0;
     if (c->last_was_batch && c->bres && c->bres->have_result) {
         // the last finished thing was a batch: selected = rows over all its queries, form = keyed | 0x1000 (batched)
         const BatchSlot& b = *c->bres;
@@ -5666,12 +5680,15 @@ int pie_stats_get(pie_ctx* c, pie_stats* out)
         out->selected = m;
         out->max_bucket = mx;
         out->n_segments = out->n_big = 0;
+        out->n_small = out->n_over = out->n_hot = out->direct_shift = 0;
         out->k1_blocks = (uint32_t)b.k1_blocks;
         out->k1_variant = b.unsupported ? 0u : b.ordered ? (0x3400u | (b.fine_key ? 0x800u : 0u)) : (0x1485u | (b.fine_key ? 0x800u : 0u));
         out->key_ambiguous = 0;
         out->live = 0;
         out->candidates = b.unsupported ? 0 : b.last[0].cand;
     }
+    full.struct_size = caller_size;
+    memcpy(caller, &full, caller_size);
     return PIE_OK;
 }
 
