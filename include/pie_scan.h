@@ -521,6 +521,19 @@ int pie_shard_delete_user(pie_ctx *ctx, int32_t user_global, int32_t *rows_globa
  * not hold are skipped (count 0); rows_global_out receives GLOBAL rows, ascending (translated on the device). */
 int pie_shard_delete_users(pie_ctx *ctx, const int32_t *users_global, size_t k, int32_t *rows_global_out, size_t cap,
                            size_t *n_deleted, int32_t *per_user_out /* [k] */);
+/* pie_prune_before / pie_retention_purge / pie_retention_purge_tz (_pruneCalendarEvents, server/storage/sqlProvider.js:956-968;
+ * _purgeExpiredArchives / _isArchiveExpired / _addMonths, :863-890, 991-1009) on a shard, answered in GLOBAL rows: each call
+ * tombstones and lists exactly the local rows the plain call would on the same context, and rows_global_out (may be NULL)
+ * receives their ORIGINAL global rows, ascending (the row map ascends, so local order is global order).  The write pass stores
+ * row_map[row] itself: no translation pass follows.  Everything the plain calls maintain stays in step as under them (both
+ * keys, the hot index, the ordered run's mirror, the held queue, slot 0's result).  PIE_E_STATE on a context that is not
+ * sharded or whose row map does not cover its rows; all other rules are the plain calls': a cap too small tombstones the rows
+ * all the same and returns PIE_E_CAPACITY with *n_out set. */
+int pie_shard_prune_before(pie_ctx *ctx, int64_t cutoff, int32_t *rows_global_out, size_t cap, size_t *n_out);
+int pie_shard_retention_purge(pie_ctx *ctx, int64_t now, int32_t months, int64_t tz_offset_ms, int32_t *rows_global_out, size_t cap,
+                              size_t *n_out);
+int pie_shard_retention_purge_tz(pie_ctx *ctx, int64_t now, int32_t months, const int64_t *transitions_utc_ms, const int64_t *offsets_ms,
+                                 int32_t n_transitions, int32_t *rows_global_out, size_t cap, size_t *n_out);
 /* k global rows -> local rows in place (-1: not held by this shard); k local rows -> global rows in place (-1: outside the
  * map).  One small launch each, for hosts that hold a few rows of a huge table (the shape of pie_compact_translate); with
  * them the per-shard lists of pie_prune_before / pie_retention_purge* become global rows. */
@@ -789,8 +802,17 @@ int pie_comm_queue_read(pie_comm *comm, int32_t at_rank, int32_t *rows_out, int3
 int pie_comm_queue_device_ptrs(pie_comm *comm, int32_t at_rank, void **rows_dev, void **src_rank_dev, void **src_row_dev,
                                size_t *q_out);
 /* Device time of the phases of the last queue call on the first local rank's stream (ms): [0] local queue + header exchange,
- * [1] pack, [2] payload exchange, [3] merge. */
+ * [1] pack, [2] payload exchange, [3] merge.  After pie_comm_prune_before / pie_comm_retention_purge* (kind
+ * PIE_COMM_QUEUE_MAINT): [0] the shards' list passes, [1] the copies of lists held on other devices, [2] 0 (nothing is
+ * exchanged), [3] the merge kernel. */
 int pie_comm_queue_timing(pie_comm *comm, float *ms_out_4);
+/* Which call left the merged queue the readers above answer from. */
+#define PIE_COMM_QUEUE_NONE    0
+#define PIE_COMM_QUEUE_EXPIRED 1 /* pie_comm_expired_queue */
+#define PIE_COMM_QUEUE_ARCHIVE 2 /* pie_comm_archive_queue */
+#define PIE_COMM_QUEUE_MAINT   3 /* pie_comm_prune_before / pie_comm_retention_purge / pie_comm_retention_purge_tz: the rows the call
+                                    tombstoned; held by the FIRST local rank only (the readers refuse another at_rank: PIE_E_STATE) */
+int pie_comm_queue_kind(const pie_comm *comm);
 
 /* ---- a live sharded table behind the communicator: pie_shard_append_rows / pie_shard_set_end / pie_shard_delete_user on every
  * local shard, with GLOBAL ids throughout.  Nothing is exchanged: every process of a process-per-GPU communicator makes the
@@ -812,6 +834,33 @@ int pie_comm_delete_user(pie_comm *comm, int32_t user, int32_t *rows_out, size_t
 int pie_comm_delete_users(pie_comm *comm, const int32_t *users, size_t k, int32_t *rows_out, size_t cap, size_t *n_deleted,
                           int32_t *per_user_out /* [k] */, int32_t *owner_rank_out /* [k] */);
 int pie_comm_table_size(pie_comm *comm, int64_t *rows_global_out, int32_t *users_global_out);
+/* A sharded table that ages: _pruneCalendarEvents (server/storage/sqlProvider.js:956-968), _purgeExpiredArchives /
+ * _isArchiveExpired / _addMonths (:863-890, 991-1009) and the removal of dead rows (`sessions.delete()`, server/sessionStore.js:
+ * 47-53) behind the communicator.  The rules above hold: PIE_E_STATE while pipelined steps of either kind are uncollected or the
+ * local shards disagree on the table's size; every local shard checks the call before any is changed; nothing is exchanged, and
+ * in a process-per-GPU communicator every process makes the same call and reports what its own shards held.  Token lookups and
+ * an expired queue begun on a shard's side stream land as under the shard's own calls.
+ * The three lists: every local shard runs its shard form (pie_shard_prune_before ...) with the list left on its device; the
+ * lists are merged ON THE DEVICE of the first local rank (lists held on other devices are copied over first) into ONE ascending
+ * list of global rows.  rows_out (may be NULL) receives it, *n_out its length; a cap below it returns PIE_E_CAPACITY with *n_out
+ * set, the rows tombstoned all the same.  Either way the merged list stays with the communicator as a queue of kind
+ * PIE_COMM_QUEUE_MAINT: pie_comm_queue_read / pie_comm_queue_device_ptrs (at_rank = the first local rank) give global row,
+ * source rank and source local row, pie_comm_queue_timing its device times.
+ * pie_comm_compact_rows: pie_compact_rows(dead_before, flags) on every local shard; *kept_total_out = the kept rows of the local
+ * shards, kept_local_out[i] (may be NULL) those of the i-th local shard.  Global rows are NOT renumbered: the table keeps its
+ * N_g, the next pie_comm_append_rows starts there, every pie_comm_* call keeps naming and reporting the original global rows,
+ * and a global row that was dropped behaves as a row no shard holds (pie_comm_set_end skips it, token lookups answer -1; token
+ * columns are carried over as pie_compact_rows does).  A merged queue the communicator held is forgotten (its source rows named
+ * the old numbering).  Reservations of pie_comm_step_reserve / pie_comm_wide_step_reserve are the caller's to renew afterwards,
+ * as after any table change.  If a shard fails part-way (PIE_E_NOMEM), that status is returned and the shards before it stay
+ * compacted: that is a valid table, because global ids do not move; *kept_total_out and kept_local_out cover the shards done. */
+int pie_comm_prune_before(pie_comm *comm, int64_t cutoff, int32_t *rows_out, size_t cap, size_t *n_out);
+int pie_comm_retention_purge(pie_comm *comm, int64_t now, int32_t months, int64_t tz_offset_ms, int32_t *rows_out, size_t cap,
+                             size_t *n_out);
+int pie_comm_retention_purge_tz(pie_comm *comm, int64_t now, int32_t months, const int64_t *transitions_utc_ms, const int64_t *offsets_ms,
+                                int32_t n_transitions, int32_t *rows_out, size_t cap, size_t *n_out);
+int pie_comm_compact_rows(pie_comm *comm, int64_t dead_before, uint32_t flags, size_t *kept_total_out,
+                          size_t *kept_local_out /* [local ranks], may be NULL */);
 /* The token column behind the communicator (pie_shard_token_* on every local shard; the rules above hold: PIE_E_STATE while
  * pipelined steps are uncollected, every local shard checks a call before any is staged or changed).
  * pie_comm_token_lookup queues the lookup on every local shard, then waits for each, and merges on the host: per key the answer

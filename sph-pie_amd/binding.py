@@ -148,6 +148,9 @@ _SIGS = [
     ("pie_shard_set_end", C.c_int, [_P, _P, _P, C.c_size_t]),
     ("pie_shard_delete_user", C.c_int, [_P, C.c_int32, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("pie_shard_delete_users", C.c_int, [_P, _P, C.c_size_t, _P, C.c_size_t, C.POINTER(C.c_size_t), _P]),
+    ("pie_shard_prune_before", C.c_int, [_P, C.c_int64, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("pie_shard_retention_purge", C.c_int, [_P, C.c_int64, C.c_int32, C.c_int64, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("pie_shard_retention_purge_tz", C.c_int, [_P, C.c_int64, C.c_int32, _P, _P, C.c_int32, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("pie_shard_rows_to_local", C.c_int, [_P, _P, C.c_size_t]),
     ("pie_shard_rows_to_global", C.c_int, [_P, _P, C.c_size_t]),
     ("pie_shard_route", C.c_int, [_P, C.c_size_t, C.c_int32, C.c_int32, _P, C.POINTER(C.c_size_t), C.c_int32, C.c_int32, _P, C.c_size_t,
@@ -195,6 +198,11 @@ _SIGS = [
     ("pie_comm_set_end", C.c_int, [_P, _P, _P, C.c_size_t]),
     ("pie_comm_delete_user", C.c_int, [_P, C.c_int32, _P, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int32)]),
     ("pie_comm_delete_users", C.c_int, [_P, _P, C.c_size_t, _P, C.c_size_t, C.POINTER(C.c_size_t), _P, _P]),
+    ("pie_comm_prune_before", C.c_int, [_P, C.c_int64, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("pie_comm_retention_purge", C.c_int, [_P, C.c_int64, C.c_int32, C.c_int64, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("pie_comm_retention_purge_tz", C.c_int, [_P, C.c_int64, C.c_int32, _P, _P, C.c_int32, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("pie_comm_compact_rows", C.c_int, [_P, C.c_int64, C.c_uint32, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    ("pie_comm_queue_kind", C.c_int, [_P]),
     ("pie_comm_table_size", C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     ("pie_token_set", C.c_int, [_P, _P, C.c_size_t]),
     ("pie_token_append", C.c_int, [_P, _P, C.c_size_t]),
@@ -1067,6 +1075,27 @@ class PieScan:
         self._check(self._lib.pie_shard_delete_users(self._ctx, _ptr(users), users.shape[0], _ptr(rows), self.n, C.byref(k), _ptr(per)))
         return rows[: k.value].copy(), per
 
+    def shard_prune_before(self, cutoff, cap=None):
+        """pie_prune_before on a shard -> the ascending GLOBAL rows tombstoned (cap: entries offered, default the shard's rows)."""
+        k = C.c_size_t(0)
+        cap = self.n if cap is None else int(cap)
+        rows = np.empty(max(cap, 1), np.int32)
+        self._check(self._lib.pie_shard_prune_before(self._ctx, int(cutoff), _ptr(rows), cap, C.byref(k)))
+        return rows[: k.value].copy()
+
+    def shard_retention_purge(self, now, months=2, tz_offset_ms=0, tz_table=None, cap=None):
+        """pie_retention_purge / _tz on a shard -> the ascending GLOBAL rows tombstoned; tz_table as in retention_purge."""
+        k = C.c_size_t(0)
+        cap = self.n if cap is None else int(cap)
+        rows = np.empty(max(cap, 1), np.int32)
+        if tz_table is not None:
+            T, off = _tz_pair(tz_table)
+            self._check(self._lib.pie_shard_retention_purge_tz(self._ctx, int(now), int(months), _ptr(T), _ptr(off), int(T.shape[0]), _ptr(rows), cap,
+                                                               C.byref(k)))
+        else:
+            self._check(self._lib.pie_shard_retention_purge(self._ctx, int(now), int(months), int(tz_offset_ms), _ptr(rows), cap, C.byref(k)))
+        return rows[: k.value].copy()
+
     def shard_rows_to_local(self, rows_global):
         """Global rows -> this shard's local rows (-1: not held), as a new int32 array."""
         rows = np.array(rows_global, dtype=np.int32, copy=True).reshape(-1)
@@ -1380,6 +1409,48 @@ class PieComm:
         self._check(self._lib.pie_comm_delete_users(self._c, _ptr(users), users.shape[0], _ptr(rows), cap, C.byref(k), _ptr(per), _ptr(owners)))
         return rows[: k.value].copy(), per, owners
 
+    # ---- a sharded table that ages (pie_comm_prune_before / _retention_purge* / _compact_rows)
+    def local_rank_ids(self):
+        """The ranks this process drives, ascending."""
+        return [r for r in range(self.world) if self._lib.pie_comm_ctx(self._c, r)]
+
+    def _maint(self, call, cap, sources):
+        """cap: entries of the list to offer (default: the table's rows); the merged list stays readable through queue_read."""
+        cap = max(self.table_size()[0], 1) if cap is None else int(cap)
+        rows, k = np.empty(max(cap, 1), np.int32), C.c_size_t(0)
+        self.last_n = 0
+        rc = call(_ptr(rows), cap, C.byref(k))
+        self.last_n = int(k.value)
+        self._check(rc)
+        if sources:
+            return self.queue_read(self.local_rank_ids()[0], sources=True)
+        return rows[: k.value].copy()
+
+    def prune_before(self, cutoff, cap=None, sources=False):
+        """_pruneCalendarEvents on every local shard -> the ascending global rows tombstoned, merged on the first local rank's
+        device; sources=True: (rows, source rank, source local row).  last_n holds the total, also after PIE_E_CAPACITY."""
+        return self._maint(lambda r, c, k: self._lib.pie_comm_prune_before(self._c, int(cutoff), r, c, k), cap, sources)
+
+    def retention_purge(self, now, months=2, tz_offset_ms=0, tz_table=None, cap=None, sources=False):
+        """_purgeExpiredArchives on every local shard (tz_table as in PieScan.retention_purge) -> as prune_before."""
+        if tz_table is not None:
+            T, off = _tz_pair(tz_table)
+            return self._maint(lambda r, c, k: self._lib.pie_comm_retention_purge_tz(self._c, int(now), int(months), _ptr(T), _ptr(off),
+                                                                                     int(T.shape[0]), r, c, k), cap, sources)
+        return self._maint(lambda r, c, k: self._lib.pie_comm_retention_purge(self._c, int(now), int(months), int(tz_offset_ms), r, c, k),
+                           cap, sources)
+
+    def compact_rows(self, dead_before=INT64_MIN, shrink=False):
+        """pie_compact_rows on every local shard; global rows keep their numbers -> (kept rows in all, kept rows per local shard)."""
+        n_local = int(self._lib.pie_comm_local_ranks(self._c))
+        total, per = C.c_size_t(0), (C.c_size_t * max(n_local, 1))()
+        self._check(self._lib.pie_comm_compact_rows(self._c, int(dead_before), PIE_COMPACT_SHRINK if shrink else 0, C.byref(total), per))
+        return int(total.value), [int(v) for v in per][:n_local]
+
+    def queue_kind(self):
+        """-> 0 none, 1 expired queue, 2 archive queue, 3 the list of a prune / retention purge"""
+        return int(self._lib.pie_comm_queue_kind(self._c))
+
     # ---- the token column behind the communicator (pie_comm_token_*): keys are uint64 arrays of shape (k, 2), GLOBAL ids out
     def token_set(self, keys):
         """Keys for the global rows [0, len(keys)) on every local shard."""
@@ -1609,6 +1680,13 @@ def batch_mask_codes(queries, n_disc, start, end, disc, fallback=None):
     if rc != 0:
         raise PieError(rc, "pie_batch_mask_codes: bad argument")
     return codes, masks
+
+
+def _tz_pair(tz_table):
+    T, off = np.ascontiguousarray(tz_table[0], np.int64), np.ascontiguousarray(tz_table[1], np.int64)
+    if off.shape[0] != T.shape[0] + 1:
+        raise ValueError("a table of n transitions carries n + 1 offsets")
+    return T, off
 
 
 def tz_table(zone, from_ms=0, to_ms=4102444800000):

@@ -44,6 +44,13 @@ int shard_expq_check(pie_ctx* c, const char* what);
 int shard_token_flight_drop_last(pie_ctx* c, const char* what);
 int shard_expq_take(pie_ctx* c, const char* what, const int32_t** rows_dev_out, size_t* len_out, void** stream_out, void** done_out);
 void shard_expq_stale(pie_ctx* c);
+// ... and pie_shard_prune_before / pie_shard_retention_purge / _tz (kind 2 / 3 / 4) in two pieces: the check, and the run that
+// leaves the ascending global rows and, beside them, the local rows on the device; what pie_compact_rows would refuse on a shard
+int shard_check_row_list(pie_ctx* c, int kind, int32_t months, int64_t tz_offset_ms, const int64_t* transitions, const int64_t* offsets,
+                         int32_t n_transitions);
+int shard_row_list_run(pie_ctx* c, int kind, int64_t a, int32_t months, int64_t tz_offset_ms, const int64_t* transitions, const int64_t* offsets,
+                       int32_t n_transitions, size_t* m_out, const int32_t** rows_global_dev, const int32_t** rows_local_dev);
+int shard_check_compact(pie_ctx* c, uint32_t flags);
 } // namespace pie_internal
 
 namespace {
@@ -153,6 +160,13 @@ struct pie_comm {
     std::vector<int*> q_rows, q_src_rank, q_src_row; // local index -> the merged queue
     long long q_out_cap = 0;
     long long q_total = -1;                       // length of the merged queue (-1: none)
+    int q_kind = 0;                               // PIE_COMM_QUEUE_*: which call left it
+    // the merged list of pie_comm_prune_before / pie_comm_retention_purge*: on the first local rank's device only
+    int *mq_rows = nullptr, *mq_rank = nullptr, *mq_row = nullptr;
+    long long mq_cap = 0;
+    int* mq_stage = nullptr;                      // lists of shards on other devices, global rows then local rows, back to back
+    long long mq_stage_cap = 0;
+    void* mq_desc = nullptr;                      // the merge's descriptor on the device
     std::vector<hipEvent_t> q_ev;                 // local index -> completion of a queue phase
     hipEvent_t q_tev[5] = {};                     // timing of the last queue call on the first local rank's stream
     bool q_timed = false;
@@ -724,6 +738,12 @@ void free_queue_buffers(pie_comm* c)
     c->h_qhead = nullptr;
     c->q_msg_words = c->q_out_cap = 0;
     c->q_total = -1;
+    c->q_kind = 0;
+    for (void* p : {(void*)c->mq_rows, (void*)c->mq_rank, (void*)c->mq_row, (void*)c->mq_stage, c->mq_desc})
+        if (p) (void)hipFree(p);
+    c->mq_rows = c->mq_rank = c->mq_row = c->mq_stage = nullptr;
+    c->mq_desc = nullptr;
+    c->mq_cap = c->mq_stage_cap = 0;
 }
 
 // header buffers and events: once per communicator
@@ -779,6 +799,7 @@ int comm_queue(pie_comm* c, int kind, int64_t a, int64_t b, int32_t* queue_out, 
     if (c->world > kQueueMaxWorld) return cfail(c, PIE_E_INVAL, "the queue merge takes at most %d ranks (world %d)", kQueueMaxWorld, c->world);
     if (steps_idle(c)) return PIE_E_STATE;
     c->q_total = -1;
+    c->q_kind = 0;
     c->q_timed = false;
     int rc = ensure_queue_heads(c);
     if (rc) return rc;
@@ -864,6 +885,7 @@ int comm_queue(pie_comm* c, int kind, int64_t a, int64_t b, int32_t* queue_out, 
         if (rc) return rc;
     }
     c->q_total = total;
+    c->q_kind = kind == 1 ? PIE_COMM_QUEUE_EXPIRED : PIE_COMM_QUEUE_ARCHIVE;
     c->q_timed = true;
     if (q_out) *q_out = (size_t)total;
     if (queue_out && (size_t)total > cap) return cfail(c, PIE_E_CAPACITY, "queue cap %zu < %lld", cap, total);
@@ -894,6 +916,14 @@ int pie_comm_queue_device_ptrs(pie_comm* c, int32_t at_rank, void** rows_dev, vo
     const int k = local_index(c, at_rank);
     if (k < 0) return cfail(c, PIE_E_INVAL, "rank %d is not local to this communicator", at_rank);
     if (c->q_total < 0) return cfail(c, PIE_E_STATE, "no merged queue: pie_comm_expired_queue / pie_comm_archive_queue first");
+    if (c->q_kind == PIE_COMM_QUEUE_MAINT) { // merged on the first local rank's device only
+        if (k != 0) return cfail(c, PIE_E_STATE, "the list of a prune / retention purge is held by the first local rank (%d) only", c->rank_of[0]);
+        if (rows_dev) *rows_dev = c->q_total ? c->mq_rows : nullptr;
+        if (src_rank_dev) *src_rank_dev = c->q_total ? c->mq_rank : nullptr;
+        if (src_row_dev) *src_row_dev = c->q_total ? c->mq_row : nullptr;
+        if (q_out) *q_out = (size_t)c->q_total;
+        return PIE_OK;
+    }
     if (rows_dev) *rows_dev = c->q_rows[k];
     if (src_rank_dev) *src_rank_dev = c->q_src_rank[k];
     if (src_row_dev) *src_row_dev = c->q_src_row[k];
@@ -916,6 +946,8 @@ int pie_comm_queue_read(pie_comm* c, int32_t at_rank, int32_t* rows_out, int32_t
     if (src_row_out) PIE_CHIP(c, hipMemcpy(src_row_out, src_row, q * 4, hipMemcpyDeviceToHost));
     return PIE_OK;
 }
+
+int pie_comm_queue_kind(const pie_comm* c) { return c && c->q_total >= 0 ? c->q_kind : PIE_COMM_QUEUE_NONE; }
 
 int pie_comm_queue_timing(pie_comm* c, float* ms_out_4)
 {
@@ -1549,6 +1581,7 @@ constexpr int kMergeMaxLists = 64; // local ranks at most (pie_comm_create: 1..6
 // merging device), its kept length, its rank, and the lists' running lengths; `count` lists, pre[count] elements
 struct MergeDesc {
     const int* rows[kMergeMaxLists];
+    const int* local[kMergeMaxLists];   // SRC_ROW only: every list's local rows, element for element
     long long pre[kMergeMaxLists + 1];
     int n[kMergeMaxLists];
     int rank[kMergeMaxLists];
@@ -1558,8 +1591,10 @@ struct MergeDesc {
 // One lane per element, placed by co-rank: its index in its own list plus, for every other list, how many of that list's rows
 // are smaller (a lower bound; global rows are unique across shards).  No atomics, no wave waits for another.  A position at or
 // past out_cap is not written: the first out_cap merged rows only ever come from the first out_cap rows of each list.
+// SRC_ROW (the lists of a prune / retention purge): the element's local row on its shard goes with it.
+template <bool SRC_ROW>
 __global__ __launch_bounds__(256) void k_merge_shard_queues(const MergeDesc* __restrict__ desc, long long out_cap, int* __restrict__ out_rows,
-                                                            int* __restrict__ out_rank)
+                                                            int* __restrict__ out_rank, int* __restrict__ out_row)
 {
     __shared__ MergeDesc s;
     for (int w = (int)threadIdx.x; w < (int)(sizeof(MergeDesc) / 4); w += (int)blockDim.x)
@@ -1588,6 +1623,7 @@ __global__ __launch_bounds__(256) void k_merge_shard_queues(const MergeDesc* __r
         if (pos < out_cap) {
             out_rows[pos] = v;
             out_rank[pos] = s.rank[r];
+            if constexpr (SRC_ROW) out_row[pos] = s.local[r][i];
         }
     }
 }
@@ -1859,8 +1895,8 @@ int pie_comm_expired_queue_finish(pie_comm* c, int32_t* rows_out, int32_t* owner
         if (e == hipSuccess) e = hipMemcpyAsync(c->xq_desc, d, sizeof(MergeDesc), hipMemcpyHostToDevice, ms);
         if (e == hipSuccess) {
             const long long blocks = std::min<long long>((acc + 255) / 256, 2048);
-            hipLaunchKernelGGL(k_merge_shard_queues, dim3((unsigned)blocks), dim3(256), 0, ms, (const MergeDesc*)c->xq_desc, (long long)have, c->xq_rows,
-                               c->xq_owner);
+            hipLaunchKernelGGL(k_merge_shard_queues<false>, dim3((unsigned)blocks), dim3(256), 0, ms, (const MergeDesc*)c->xq_desc, (long long)have,
+                               c->xq_rows, c->xq_owner, (int*)nullptr);
             e = hipGetLastError();
         }
         if (e == hipSuccess && to_host && rows_out) e = hipMemcpyAsync(h_rows, c->xq_rows, have * 4, hipMemcpyDeviceToHost, ms);
@@ -1892,6 +1928,164 @@ int pie_comm_inflight_queue_device_ptrs(pie_comm* c, void** rows_dev, void** own
     if (owner_rank_dev) *owner_rank_dev = c->xq_have ? c->xq_owner : nullptr;
     if (n_out) *n_out = (size_t)c->xq_have;
     if (q_out) *q_out = (size_t)c->xq_total;
+    return PIE_OK;
+}
+
+} // extern "C"
+
+// ---- a sharded table that ages: pruneCalendarEvents / purgeExpiredArchives / sessions.delete() (server/storage/sqlProvider.js:
+// 956-968, 863-890, 991-1009) behind the communicator.  Every local shard runs its shard form with the list left on its device
+// (global rows in the write pass's one store, local rows beside them); the lists are merged on the first local rank's device by
+// k_merge_shard_queues<true>, lists held on other devices copied over first.  Nothing is exchanged.
+namespace {
+
+int maint_ensure(pie_comm* c, long long total, long long staged_words)
+{
+    PIE_CHIP(c, hipSetDevice(c->device[0]));
+    if (!c->mq_desc) PIE_CHIP(c, hipMalloc(&c->mq_desc, sizeof(MergeDesc)));
+    if (total > c->mq_cap) {
+        for (int** p : {&c->mq_rows, &c->mq_rank, &c->mq_row})
+            if (*p) { PIE_CHIP(c, hipFree(*p)); *p = nullptr; }
+        c->mq_cap = 0;
+        const long long o = total + total / 16 + 64;
+        for (int** p : {&c->mq_rows, &c->mq_rank, &c->mq_row}) PIE_CHIP(c, hipMalloc(p, (size_t)o * 4));
+        c->mq_cap = o;
+    }
+    if (staged_words > c->mq_stage_cap) {
+        if (c->mq_stage) { PIE_CHIP(c, hipFree(c->mq_stage)); c->mq_stage = nullptr; }
+        c->mq_stage_cap = 0;
+        const long long o = staged_words + staged_words / 16 + 64;
+        PIE_CHIP(c, hipMalloc(&c->mq_stage, (size_t)o * 4));
+        c->mq_stage_cap = o;
+    }
+    return PIE_OK;
+}
+
+// kind 2: prune (a = cutoff), 3: retention under a fixed offset (a = now), 4: under a zone table (a = now)
+int comm_maint_list(pie_comm* c, int kind, int64_t a, int32_t months, int64_t tz_offset_ms, const int64_t* transitions, const int64_t* offsets,
+                    int32_t n_transitions, int32_t* rows_out, size_t cap, size_t* n_out)
+{
+    if (!c) return PIE_E_INVAL;
+    if (n_out) *n_out = 0;
+    if (c->n_local > kMergeMaxLists) return cfail(c, PIE_E_INVAL, "the merge takes at most %d local ranks", kMergeMaxLists);
+    int rc = mutate_ready(c, nullptr, nullptr);
+    if (rc) return rc;
+    for (int i = 0; i < c->n_local; ++i)
+        PIE_CCTX(c, i, pie_internal::shard_check_row_list(c->ctx[i], kind, months, tz_offset_ms, transitions, offsets, n_transitions));
+    rc = ensure_queue_heads(c); // (the timing events)
+    if (rc) return rc;
+    c->q_total = -1;
+    c->q_kind = PIE_COMM_QUEUE_NONE;
+    c->q_timed = false;
+    PIE_CHIP(c, hipSetDevice(c->device[0]));
+    PIE_CHIP(c, hipEventRecord(c->q_tev[0], c->stream[0]));
+    // 1. every shard's two passes; its lists stay in its own workspace
+    const int32_t* glist[kMergeMaxLists] = {};
+    const int32_t* llist[kMergeMaxLists] = {};
+    size_t len[kMergeMaxLists] = {};
+    long long total = 0, staged = 0;
+    for (int i = 0; i < c->n_local; ++i) {
+        PIE_CCTX(c, i, pie_internal::shard_row_list_run(c->ctx[i], kind, a, months, tz_offset_ms, transitions, offsets, n_transitions, &len[i],
+                                                        &glist[i], &llist[i]));
+        total += (long long)len[i];
+        if (xq_staged(c, i)) staged += 2 * (long long)len[i];
+    }
+    if (n_out) *n_out = (size_t)total;
+    if (total >= 0x7FFFFFFFLL) return cfail(c, PIE_E_INVAL, "a merged list of %lld rows does not fit int32", total);
+    PIE_CHIP(c, hipSetDevice(c->device[0]));
+    hipStream_t ms = c->stream[0];
+    PIE_CHIP(c, hipEventRecord(c->q_tev[1], ms));
+    if (total > 0) {
+        rc = maint_ensure(c, total, staged);
+        if (rc) return rc;
+        // 2. lists held on other devices come over (every shard's passes were waited for); 3. the merge
+        MergeDesc d;
+        memset(&d, 0, sizeof d);
+        long long acc = 0, staged_at = 0;
+        for (int i = 0; i < c->n_local; ++i) {
+            d.rows[i] = glist[i];
+            d.local[i] = llist[i];
+            d.n[i] = (int)len[i];
+            d.rank[i] = c->rank_of[i];
+            d.pre[i] = acc;
+            acc += (long long)len[i];
+            if (len[i] == 0 || !xq_staged(c, i)) continue;
+            int* dg = c->mq_stage + staged_at;
+            int* dl = dg + len[i];
+            staged_at += 2 * (long long)len[i];
+            if (c->device[i] != c->device[0]) {
+                PIE_CHIP(c, hipMemcpyPeerAsync(dg, c->device[0], glist[i], c->device[i], len[i] * 4, ms));
+                PIE_CHIP(c, hipMemcpyPeerAsync(dl, c->device[0], llist[i], c->device[i], len[i] * 4, ms));
+            } else {
+                PIE_CHIP(c, hipMemcpyAsync(dg, glist[i], len[i] * 4, hipMemcpyDeviceToDevice, ms));
+                PIE_CHIP(c, hipMemcpyAsync(dl, llist[i], len[i] * 4, hipMemcpyDeviceToDevice, ms));
+            }
+            d.rows[i] = dg;
+            d.local[i] = dl;
+        }
+        d.pre[c->n_local] = acc;
+        d.count = c->n_local;
+        PIE_CHIP(c, hipMemcpy(c->mq_desc, &d, sizeof d, hipMemcpyHostToDevice)); // no merge of this communicator is running: every call waits for its own
+        PIE_CHIP(c, hipEventRecord(c->q_tev[2], ms));
+        PIE_CHIP(c, hipEventRecord(c->q_tev[3], ms));
+        const long long blocks = std::min<long long>((acc + 255) / 256, 2048);
+        hipLaunchKernelGGL(k_merge_shard_queues<true>, dim3((unsigned)blocks), dim3(256), 0, ms, (const MergeDesc*)c->mq_desc, c->mq_cap, c->mq_rows,
+                           c->mq_rank, c->mq_row);
+        PIE_CHIP(c, hipGetLastError());
+    } else {
+        PIE_CHIP(c, hipEventRecord(c->q_tev[2], ms));
+        PIE_CHIP(c, hipEventRecord(c->q_tev[3], ms));
+    }
+    PIE_CHIP(c, hipEventRecord(c->q_tev[4], ms));
+    PIE_CHIP(c, hipEventRecord(c->q_ev[0], ms));
+    rc = wait_event(c, 0, c->q_ev[0], "maintenance list merge");
+    if (rc) return rc;
+    c->q_total = total;
+    c->q_kind = PIE_COMM_QUEUE_MAINT;
+    c->q_timed = true;
+    if (rows_out && (size_t)total > cap) return cfail(c, PIE_E_CAPACITY, "list cap %zu < %lld", cap, total); // tombstoned all the same
+    if (rows_out && total) PIE_CHIP(c, hipMemcpy(rows_out, c->mq_rows, (size_t)total * 4, hipMemcpyDeviceToHost));
+    return PIE_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int pie_comm_prune_before(pie_comm* c, int64_t cutoff, int32_t* rows_out, size_t cap, size_t* n_out)
+{
+    return comm_maint_list(c, 2, cutoff, 0, 0, nullptr, nullptr, 0, rows_out, cap, n_out);
+}
+
+int pie_comm_retention_purge(pie_comm* c, int64_t now, int32_t months, int64_t tz_offset_ms, int32_t* rows_out, size_t cap, size_t* n_out)
+{
+    return comm_maint_list(c, 3, now, months, tz_offset_ms, nullptr, nullptr, 0, rows_out, cap, n_out);
+}
+
+int pie_comm_retention_purge_tz(pie_comm* c, int64_t now, int32_t months, const int64_t* transitions, const int64_t* offsets, int32_t n_transitions,
+                                int32_t* rows_out, size_t cap, size_t* n_out)
+{
+    return comm_maint_list(c, 4, now, months, 0, transitions, offsets, n_transitions, rows_out, cap, n_out);
+}
+
+int pie_comm_compact_rows(pie_comm* c, int64_t dead_before, uint32_t flags, size_t* kept_total_out, size_t* kept_local_out)
+{
+    if (!c) return PIE_E_INVAL;
+    if (kept_total_out) *kept_total_out = 0;
+    int rc = mutate_ready(c, nullptr, nullptr);
+    if (rc) return rc;
+    for (int i = 0; i < c->n_local; ++i) PIE_CCTX(c, i, pie_internal::shard_check_compact(c->ctx[i], flags));
+    c->q_total = -1; // a merged queue's source rows name the numbering that goes
+    c->q_kind = PIE_COMM_QUEUE_NONE;
+    c->q_timed = false;
+    size_t total = 0;
+    for (int i = 0; i < c->n_local; ++i) {
+        size_t kept = 0;
+        PIE_CCTX(c, i, pie_compact_rows(c->ctx[i], dead_before, flags, &kept)); // the shards before it stay compacted: global ids do not move
+        if (kept_local_out) kept_local_out[i] = kept;
+        total += kept;
+        if (kept_total_out) *kept_total_out = total;
+    }
     return PIE_OK;
 }
 

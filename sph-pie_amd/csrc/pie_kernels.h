@@ -4227,11 +4227,15 @@ __global__ __launch_bounds__(256) void k_list_count(const long long* __restrict_
     if (threadIdx.x == 0) blk_count[blockIdx.x] = (int)local;
 }
 
-template <int MODE>
+// MAPPED (a shard that answers in GLOBAL rows, pie_shard_prune_before / pie_shard_retention_purge*): the one store of a hit
+// is row_map[r], the shard's ascending local row -> global row map, as k_expq_pass does it; no gather behind the write.
+// local_q (MAPPED only, may be NULL): the same position also receives the local row (the communicator's source rows).
+template <int MODE, bool MAPPED = false>
 __global__ __launch_bounds__(256) void k_list_write(long long* __restrict__ end, const int* __restrict__ user, long long n,
                                                     long long rows_per_block, long long a, long long b,
                                                     const long long* __restrict__ blk_off, int* __restrict__ queue, long long cap,
-                                                    lkey_t* __restrict__ key, fkey_t* __restrict__ fkey, OrdMirror ord, HotMirror hot)
+                                                    lkey_t* __restrict__ key, fkey_t* __restrict__ fkey, OrdMirror ord, HotMirror hot,
+                                                    const int* __restrict__ row_map = nullptr, int* __restrict__ local_q = nullptr)
 {
     __shared__ int wcount[4];
     __shared__ long long carry_s;
@@ -4249,7 +4253,14 @@ __global__ __launch_bounds__(256) void k_list_write(long long* __restrict__ end,
         long long base = carry_s;
         for (int w = 0; w < wave; ++w) base += wcount[w];
         const long long pos = base + prefix_in_ballot(bal);
-        if (hit && pos < cap) queue[pos] = (int)r;
+        if constexpr (MAPPED) {
+            if (hit && pos < cap) {
+                queue[pos] = row_map[r];
+                if (local_q) local_q[pos] = (int)r;
+            }
+        } else {
+            if (hit && pos < cap) queue[pos] = (int)r;
+        }
         if constexpr (MODE != 0) {
             if (hit) { // a tombstone's liveness keys are 0 under every base
                 end[r] = INT64_MIN;

@@ -92,6 +92,10 @@
     X(int, pie_comm_delete_user, (pie_comm *, int32_t, int32_t *, size_t, size_t *, int32_t *))                      \
     X(int, pie_comm_delete_users, (pie_comm *, const int32_t *, size_t, int32_t *, size_t, size_t *, int32_t *, int32_t *)) \
     X(int, pie_comm_table_size, (pie_comm *, int64_t *, int32_t *))                                                  \
+    X(int32_t, pie_comm_local_ranks, (const pie_comm *))                                                              \
+    X(int, pie_comm_prune_before, (pie_comm *, int64_t, int32_t *, size_t, size_t *))                                \
+    X(int, pie_comm_retention_purge_tz, (pie_comm *, int64_t, int32_t, const int64_t *, const int64_t *, int32_t, int32_t *, size_t, size_t *)) \
+    X(int, pie_comm_compact_rows, (pie_comm *, int64_t, uint32_t, size_t *, size_t *))                               \
     X(int, pie_shard_maps, (pie_ctx *, int32_t *, int32_t *))                                                       \
     X(int, pie_compact_rows, (pie_ctx *, int64_t, uint32_t, size_t *))                                              \
     X(int, pie_compact_maps, (pie_ctx *, int32_t *, int32_t *, size_t *, size_t *))                                 \
@@ -1707,6 +1711,90 @@ static napi_value fn_comm_delete_users(napi_env env, napi_callback_info info)
     return js_int(env, (int64_t)k);
 }
 
+/* A sharded table that ages (pie_comm_prune_before / pie_comm_retention_purge_tz / pie_comm_compact_rows; _pruneCalendarEvents,
+ * sqlProvider.js:956-968; _purgeExpiredArchives, :863-890, 991-1009; sessions.delete(), sessionStore.js:47-53):
+ * commPruneBefore(comm, cutoff, rows Int32Array[, srcRank Int32Array, srcRow Int32Array]) -> n
+ * commRetentionPurge(comm, now, months, transitions BigInt64Array[n], offsets BigInt64Array[n + 1], rows[, srcRank, srcRow]) -> n
+ *   rows receives the tombstoned GLOBAL rows, ascending, merged on the first local rank's device; srcRank / srcRow (both or
+ *   neither) the shard that holds each and its local row there.  The zone table is host/tzTable.js's (no transitions: a fixed
+ *   offset).  Throws with .code = -5 when rows is too short: the rows are tombstoned all the same.
+ * commCompactRows(comm, deadBefore BigInt|Number, shrink[, keptLocal Int32Array[local ranks]]) -> rows kept over the local shards;
+ *   global rows keep their numbers */
+static napi_value comm_maint_call(napi_env env, napi_callback_info info, int retention)
+{
+    size_t argc = 8;
+    napi_value argv[8];
+    CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    const char *usage = retention ? "commRetentionPurge(comm, now, months, BigInt64Array transitions[n], BigInt64Array offsets[n + 1], Int32Array rows[, Int32Array srcRank, Int32Array srcRow])"
+                                  : "commPruneBefore(comm, cutoff, Int32Array rows[, Int32Array srcRank, Int32Array srcRow])";
+    const size_t base = retention ? 6 : 3;
+    if (argc != base && argc != base + 2) {
+        napi_throw_type_error(env, NULL, usage);
+        return NULL;
+    }
+    comm_box *cbx = get_comm_box(env, argv[0]); /* refuses while scanAsync runs on one of the shard contexts */
+    if (!cbx) return NULL;
+    pie_comm *cm = cbx->comm;
+    int64_t a = 0;
+    int32_t months = 0;
+    size_t nt = 0, no = 0, cap = 0, c1 = 0, c2 = 0, n = 0;
+    int64_t *tr = NULL, *off = NULL;
+    bool ok = get_i64(env, argv[1], &a) != 0;
+    if (ok && retention) {
+        ok = napi_get_value_int32(env, argv[2], &months) == napi_ok;
+        tr = typed(env, argv[3], napi_bigint64_array, &nt);
+        off = typed(env, argv[4], napi_bigint64_array, &no);
+        ok = ok && off && (tr || nt == 0) && no == nt + 1;
+    }
+    int32_t *rows = typed(env, argv[base - 1], napi_int32_array, &cap);
+    int32_t *src_rank = argc == base + 2 ? typed(env, argv[base], napi_int32_array, &c1) : NULL;
+    int32_t *src_row = argc == base + 2 ? typed(env, argv[base + 1], napi_int32_array, &c2) : NULL;
+    if (!ok || !rows || (argc == base + 2 && (!src_rank || !src_row))) {
+        napi_throw_type_error(env, NULL, usage);
+        return NULL;
+    }
+    int rc = retention ? p_pie_comm_retention_purge_tz(cm, a, months, tr, off, (int32_t)nt, rows, cap, &n) : p_pie_comm_prune_before(cm, a, rows, cap, &n);
+    if (rc) return throw_comm(env, cm, rc);
+    if (src_rank) {
+        int32_t at = 0; /* the first local rank holds the merged list */
+        while (at < p_pie_comm_world(cm) && !p_pie_comm_ctx(cm, at)) ++at;
+        rc = p_pie_comm_queue_read(cm, at, NULL, src_rank, src_row, c1 < c2 ? c1 : c2, &n);
+        if (rc) return throw_comm(env, cm, rc);
+    }
+    return js_int(env, (int64_t)n);
+}
+static napi_value fn_comm_prune_before(napi_env env, napi_callback_info info) { return comm_maint_call(env, info, 0); }
+static napi_value fn_comm_retention_purge(napi_env env, napi_callback_info info) { return comm_maint_call(env, info, 1); }
+
+static napi_value fn_comm_compact_rows(napi_env env, napi_callback_info info)
+{
+    size_t argc = 4;
+    napi_value argv[4];
+    CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    const char *usage = "commCompactRows(comm, deadBefore BigInt|Number, shrink[, Int32Array keptLocal[local ranks]])";
+    if (argc < 3) {
+        napi_throw_type_error(env, NULL, usage);
+        return NULL;
+    }
+    comm_box *cbx = get_comm_box(env, argv[0]);
+    if (!cbx) return NULL;
+    pie_comm *cm = cbx->comm;
+    int64_t dead_before = 0;
+    bool shrink = false;
+    size_t nl = 0, total = 0, per[64] = {0};
+    const int32_t n_local = p_pie_comm_local_ranks(cm);
+    int32_t *kept_local = argc > 3 ? typed(env, argv[3], napi_int32_array, &nl) : NULL;
+    if (!get_i64(env, argv[1], &dead_before) || napi_get_value_bool(env, argv[2], &shrink) != napi_ok || n_local < 0 || n_local > 64 ||
+        (argc > 3 && (!kept_local || nl < (size_t)n_local))) {
+        napi_throw_type_error(env, NULL, usage);
+        return NULL;
+    }
+    int rc = p_pie_comm_compact_rows(cm, dead_before, shrink ? PIE_COMPACT_SHRINK : 0u, &total, per);
+    for (int32_t i = 0; kept_local && i < n_local; ++i) kept_local[i] = (int32_t)per[i];
+    if (rc) return throw_comm(env, cm, rc);
+    return js_int(env, (int64_t)total);
+}
+
 static napi_value fn_comm_table_size(napi_env env, napi_callback_info info)
 {
     ARGS(1)
@@ -2821,7 +2909,7 @@ static napi_value init(napi_env env, napi_value exports)
         {"commStepUPad", fn_comm_step_upad}, {"commWideStepReserve", fn_comm_wide_step_reserve}, {"commWideStepBegin", fn_comm_wide_step_begin},
         {"commWideStepFinish", fn_comm_wide_step_finish}, {"commWideStepCollect", fn_comm_wide_step_collect},
         {"commWideStepStatus", fn_comm_wide_step_status}, {"commWideStepReadGathered", fn_comm_wide_step_read}, {"commExpiredQueue", fn_comm_expired_queue}, {"commArchiveQueue", fn_comm_archive_queue},
-        {"commAppendRows", fn_comm_append_rows}, {"commSetEnd", fn_comm_set_end}, {"commDeleteUser", fn_comm_delete_user}, {"commDeleteUsers", fn_comm_delete_users}, {"commTableSize", fn_comm_table_size},
+        {"commAppendRows", fn_comm_append_rows}, {"commSetEnd", fn_comm_set_end}, {"commDeleteUser", fn_comm_delete_user}, {"commDeleteUsers", fn_comm_delete_users}, {"commPruneBefore", fn_comm_prune_before}, {"commRetentionPurge", fn_comm_retention_purge}, {"commCompactRows", fn_comm_compact_rows}, {"commTableSize", fn_comm_table_size},
         {"shardMaps", fn_shard_maps},
         {"tokenSet", fn_token_set}, {"tokenAppend", fn_token_append}, {"tokenLookup", fn_token_lookup}, {"tokenSetEnd", fn_token_set_end},
         {"commTokenSet", fn_comm_token_set}, {"commTokenAppend", fn_comm_token_append}, {"commTokenLookup", fn_comm_token_lookup},

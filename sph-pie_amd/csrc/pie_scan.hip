@@ -2506,8 +2506,10 @@ int run_scan(pie_ctx* c, long long now, long long cutoff)
 
 // ordered list of the rows matching a one-column predicate (expired queue / user match), through slot 0's
 // workspace: blk_count + blk_off for the per-block prefix, out_idx as the device-side list
-template <int MODE>
-int run_row_list(pie_ctx* c, long long a, long long b, int32_t* out, size_t cap, size_t* k_out)
+// MAPPED: the context is a shard whose row map covers its rows (the caller checked); the list holds GLOBAL rows, stored by the
+// write pass itself.  want_local (MAPPED only): the local rows go beside them into slot 1's out_idx, whose result is given up.
+template <int MODE, bool MAPPED = false>
+int run_row_list(pie_ctx* c, long long a, long long b, int32_t* out, size_t cap, size_t* k_out, bool want_local = false)
 {
     if (k_out) *k_out = 0;
     queue_forget(c);
@@ -2527,8 +2529,21 @@ int run_row_list(pie_ctx* c, long long a, long long b, int32_t* out, size_t cap,
     const int* col2 = (MODE == 2 || MODE == 3 || MODE == 4) ? reinterpret_cast<const int*>(c->d_start) : c->d_user;
     hipLaunchKernelGGL(k_list_count<MODE>, dim3(blocks), dim3(256), 0, s, c->d_end, col2, c->n, rpb, a, b, sl.blk_count);
     hipLaunchKernelGGL(k_block_prefix, dim3(1), dim3(256), 0, s, sl.blk_count, blocks, c->d_blk_off, &c->d_summary->m);
-    hipLaunchKernelGGL(k_list_write<MODE>, dim3(blocks), dim3(256), 0, s, c->d_end, col2, c->n, rpb, a, b,
-                       c->d_blk_off, sl.out_idx, c->cap_rows, c->d_key, c->d_fkey, ord_mirror_of(c), hot_mirror_of(c));
+    if constexpr (MAPPED) {
+        int* local_q = nullptr;
+        if (want_local) {
+            c->slot[1].have_result = false;
+            c->res = nullptr;
+            local_q = c->slot[1].out_idx;
+        }
+        hipLaunchKernelGGL((k_list_write<MODE, true>), dim3(blocks), dim3(256), 0, s, c->d_end, col2, c->n, rpb, a, b,
+                           c->d_blk_off, sl.out_idx, c->cap_rows, c->d_key, c->d_fkey, ord_mirror_of(c), hot_mirror_of(c),
+                           (const int*)c->d_shard_rows, local_q);
+    } else {
+        hipLaunchKernelGGL((k_list_write<MODE, false>), dim3(blocks), dim3(256), 0, s, c->d_end, col2, c->n, rpb, a, b,
+                           c->d_blk_off, sl.out_idx, c->cap_rows, c->d_key, c->d_fkey, ord_mirror_of(c), hot_mirror_of(c),
+                           (const int*)nullptr, (int*)nullptr);
+    }
     PIE_HIP(c, hipGetLastError());
     PIE_HIP(c, hipMemcpyAsync(c->h_summary, c->d_summary, sizeof(Summary), hipMemcpyDeviceToHost, s));
     PIE_HIP(c, hipStreamSynchronize(s));
@@ -4473,32 +4488,38 @@ int pie_delete_users(pie_ctx* c, const int32_t* users, size_t k, int32_t* rows_o
     return delete_users_copy(c, rows_out, m);
 }
 
-int pie_prune_before(pie_ctx* c, int64_t cutoff, int32_t* rows_out, size_t cap, size_t* n_pruned)
+// The three maintenance lists behind their plain and their shard entries.  `mapped`: the context is a shard whose row map
+// covers its rows (the entry checked that): the list holds GLOBAL rows; want_local as in run_row_list.
+static int prune_impl(pie_ctx* c, int64_t cutoff, int32_t* rows_out, size_t cap, size_t* n_pruned, bool mapped, bool want_local)
 {
-    if (!c) return PIE_E_INVAL;
     if (n_pruned) *n_pruned = 0;
     if (c->n == 0) return PIE_OK;
+    if (mapped) return run_row_list<2, true>(c, (long long)cutoff, 0, rows_out, cap, n_pruned, want_local);
     return run_row_list<2>(c, (long long)cutoff, 0, rows_out, cap, n_pruned);
 }
 
-int pie_retention_purge(pie_ctx* c, int64_t now, int32_t months, int64_t tz_offset_ms, int32_t* rows_out, size_t cap,
-                        size_t* n_purged)
+static int retention_check(pie_ctx* c, int32_t months, int64_t tz_offset_ms)
 {
-    if (!c) return PIE_E_INVAL;
-    if (n_purged) *n_purged = 0;
     if (months < -32768 || months > 32767) return fail(c, PIE_E_INVAL, "months outside int16");
     if (tz_offset_ms % 60000 != 0 || tz_offset_ms > 86400000LL || tz_offset_ms < -86400000LL)
         return fail(c, PIE_E_INVAL, "tz offset must be whole minutes within a day");
+    return PIE_OK;
+}
+
+static int retention_impl(pie_ctx* c, int64_t now, int32_t months, int64_t tz_offset_ms, int32_t* rows_out, size_t cap, size_t* n_purged,
+                          bool mapped, bool want_local)
+{
+    if (n_purged) *n_purged = 0;
+    const int rc = retention_check(c, months, tz_offset_ms);
+    if (rc) return rc;
     if (c->n == 0) return PIE_OK;
     const long long packed = ((tz_offset_ms / 60000) << 16) | (long long)((unsigned)months & 0xFFFFu);
+    if (mapped) return run_row_list<3, true>(c, (long long)now, packed, rows_out, cap, n_purged, want_local);
     return run_row_list<3>(c, (long long)now, packed, rows_out, cap, n_purged);
 }
 
-int pie_retention_purge_tz(pie_ctx* c, int64_t now, int32_t months, const int64_t* transitions_utc_ms, const int64_t* offsets_ms,
-                           int32_t n_transitions, int32_t* rows_out, size_t cap, size_t* n_purged)
+static int retention_tz_check(pie_ctx* c, int32_t months, const int64_t* transitions_utc_ms, const int64_t* offsets_ms, int32_t n_transitions)
 {
-    if (!c) return PIE_E_INVAL;
-    if (n_purged) *n_purged = 0;
     if (months < -32768 || months > 32767) return fail(c, PIE_E_INVAL, "months outside int16");
     if (n_transitions < 0 || n_transitions > 65536 || !offsets_ms || (n_transitions > 0 && !transitions_utc_ms))
         return fail(c, PIE_E_INVAL, "bad transition table");
@@ -4509,12 +4530,45 @@ int pie_retention_purge_tz(pie_ctx* c, int64_t now, int32_t months, const int64_
     for (int i = 1; i < n; ++i)
         if (transitions_utc_ms[i] <= transitions_utc_ms[i - 1] || transitions_utc_ms[i] + offsets_ms[i] <= transitions_utc_ms[i - 1] + offsets_ms[i - 1])
             return fail(c, PIE_E_INVAL, "transitions must ascend (entry %d)", i);
+    return PIE_OK;
+}
+
+static int retention_tz_impl(pie_ctx* c, int64_t now, int32_t months, const int64_t* transitions_utc_ms, const int64_t* offsets_ms,
+                             int32_t n_transitions, int32_t* rows_out, size_t cap, size_t* n_purged, bool mapped, bool want_local);
+
+int pie_prune_before(pie_ctx* c, int64_t cutoff, int32_t* rows_out, size_t cap, size_t* n_pruned)
+{
+    if (!c) return PIE_E_INVAL;
+    return prune_impl(c, cutoff, rows_out, cap, n_pruned, false, false);
+}
+
+int pie_retention_purge(pie_ctx* c, int64_t now, int32_t months, int64_t tz_offset_ms, int32_t* rows_out, size_t cap,
+                        size_t* n_purged)
+{
+    if (!c) return PIE_E_INVAL;
+    return retention_impl(c, now, months, tz_offset_ms, rows_out, cap, n_purged, false, false);
+}
+
+int pie_retention_purge_tz(pie_ctx* c, int64_t now, int32_t months, const int64_t* transitions_utc_ms, const int64_t* offsets_ms,
+                           int32_t n_transitions, int32_t* rows_out, size_t cap, size_t* n_purged)
+{
+    if (!c) return PIE_E_INVAL;
+    return retention_tz_impl(c, now, months, transitions_utc_ms, offsets_ms, n_transitions, rows_out, cap, n_purged, false, false);
+}
+
+static int retention_tz_impl(pie_ctx* c, int64_t now, int32_t months, const int64_t* transitions_utc_ms, const int64_t* offsets_ms,
+                             int32_t n_transitions, int32_t* rows_out, size_t cap, size_t* n_purged, bool mapped, bool want_local)
+{
+    if (n_purged) *n_purged = 0;
+    int rc = retention_tz_check(c, months, transitions_utc_ms, offsets_ms, n_transitions);
+    if (rc) return rc;
+    const int n = n_transitions;
     if (c->n == 0) return PIE_OK;
     PIE_HIP(c, hipSetDevice(c->device));
     // the table on the device: [n, months, T[n], L[n], off[n + 1]] through the context's staging block
     const size_t words = 2 + (size_t)n * 2 + (size_t)n + 1;
     if (c->n_flight || c->b_flight) return fail(c, PIE_E_STATE, "a scan is in flight");
-    int rc = sync_all(c); // the staging block is shared with appends / touches
+    rc = sync_all(c); // the staging block is shared with appends / touches
     if (rc) return rc;
     rc = ensure_stage(c, words * 8);
     if (rc) return rc;
@@ -4527,6 +4581,7 @@ int pie_retention_purge_tz(pie_ctx* c, int64_t now, int32_t months, const int64_
     }
     for (int i = 0; i <= n; ++i) h[2 + 2 * n + i] = offsets_ms[i];
     PIE_HIP(c, hipMemcpyAsync(c->d_stage, c->h_stage, words * 8, hipMemcpyHostToDevice, c->stream));
+    if (mapped) return run_row_list<4, true>(c, (long long)now, (long long)(uintptr_t)c->d_stage, rows_out, cap, n_purged, want_local);
     return run_row_list<4>(c, (long long)now, (long long)(uintptr_t)c->d_stage, rows_out, cap, n_purged);
 }
 
@@ -6241,6 +6296,82 @@ int pie_shard_delete_users(pie_ctx* c, const int32_t* users_global, size_t k, in
     if (rows_global_out && m > cap) return fail(c, PIE_E_CAPACITY, "list cap %zu < %zu", cap, m); // the rows are tombstoned all the same
     return delete_users_copy(c, rows_global_out, m);
 }
+
+// ---- pruneCalendarEvents / purgeExpiredArchives (server/storage/sqlProvider.js:956-968, 863-890, 991-1009) on a shard, answered
+// in GLOBAL rows: the plain call's passes on the same table, the write pass storing row_map[row] (k_list_write<MODE, true>)
+int pie_shard_prune_before(pie_ctx* c, int64_t cutoff, int32_t* rows_global_out, size_t cap, size_t* n_out)
+{
+    if (!c) return PIE_E_INVAL;
+    if (n_out) *n_out = 0;
+    const int rc = shard_ready(c, "pie_shard_prune_before");
+    if (rc) return rc;
+    return prune_impl(c, cutoff, rows_global_out, cap, n_out, true, false);
+}
+
+int pie_shard_retention_purge(pie_ctx* c, int64_t now, int32_t months, int64_t tz_offset_ms, int32_t* rows_global_out, size_t cap, size_t* n_out)
+{
+    if (!c) return PIE_E_INVAL;
+    if (n_out) *n_out = 0;
+    const int rc = shard_ready(c, "pie_shard_retention_purge");
+    if (rc) return rc;
+    return retention_impl(c, now, months, tz_offset_ms, rows_global_out, cap, n_out, true, false);
+}
+
+int pie_shard_retention_purge_tz(pie_ctx* c, int64_t now, int32_t months, const int64_t* transitions_utc_ms, const int64_t* offsets_ms,
+                                 int32_t n_transitions, int32_t* rows_global_out, size_t cap, size_t* n_out)
+{
+    if (!c) return PIE_E_INVAL;
+    if (n_out) *n_out = 0;
+    const int rc = shard_ready(c, "pie_shard_retention_purge_tz");
+    if (rc) return rc;
+    return retention_tz_impl(c, now, months, transitions_utc_ms, offsets_ms, n_transitions, rows_global_out, cap, n_out, true, false);
+}
+
+} // extern "C"
+
+// The three shard forms in the pieces the communicator needs: what a call would refuse, checked with nothing changed; the run
+// that leaves the ascending GLOBAL rows in slot 0's out_idx and the LOCAL rows beside them in slot 1's; and where they are.
+// kind 2: prune (a = cutoff), 3: retention under a fixed offset (a = now, tz_offset_ms), 4: under a zone table (a = now).
+namespace pie_internal {
+int shard_check_row_list(pie_ctx* c, int kind, int32_t months, int64_t tz_offset_ms, const int64_t* transitions, const int64_t* offsets,
+                         int32_t n_transitions)
+{
+    if (!c) return PIE_E_INVAL;
+    const char* what = kind == 2 ? "pie_shard_prune_before" : kind == 3 ? "pie_shard_retention_purge" : "pie_shard_retention_purge_tz";
+    int rc = shard_ready(c, what);
+    if (rc) return rc;
+    if (kind == 3) return retention_check(c, months, tz_offset_ms);
+    if (kind == 4) return retention_tz_check(c, months, transitions, offsets, n_transitions);
+    return PIE_OK;
+}
+
+int shard_row_list_run(pie_ctx* c, int kind, int64_t a, int32_t months, int64_t tz_offset_ms, const int64_t* transitions, const int64_t* offsets,
+                       int32_t n_transitions, size_t* m_out, const int32_t** rows_global_dev, const int32_t** rows_local_dev)
+{
+    *m_out = 0;
+    int rc = shard_check_row_list(c, kind, months, tz_offset_ms, transitions, offsets, n_transitions);
+    if (rc) return rc;
+    if (kind == 2) rc = prune_impl(c, a, nullptr, 0, m_out, true, true);
+    else if (kind == 3) rc = retention_impl(c, a, months, tz_offset_ms, nullptr, 0, m_out, true, true);
+    else rc = retention_tz_impl(c, a, months, transitions, offsets, n_transitions, nullptr, 0, m_out, true, true);
+    *rows_global_dev = c->slot[0].out_idx;
+    *rows_local_dev = c->slot[1].out_idx;
+    return rc;
+}
+
+// what pie_compact_rows would refuse before it moves anything, on a shard of a live sharded table
+int shard_check_compact(pie_ctx* c, uint32_t flags)
+{
+    if (!c) return PIE_E_INVAL;
+    const int rc = shard_ready(c, "pie_compact_rows");
+    if (rc) return rc;
+    if (flags & ~PIE_COMPACT_SHRINK) return fail(c, PIE_E_INVAL, "unknown compaction flags 0x%x", flags);
+    if (c->cap_rows == 0) return fail(c, PIE_E_STATE, "no table loaded");
+    return PIE_OK;
+}
+} // namespace pie_internal
+
+extern "C" {
 
 static int shard_translate(pie_ctx* c, int32_t* rows_inout, size_t k, bool to_local, const char* what)
 {

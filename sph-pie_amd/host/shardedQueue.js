@@ -23,16 +23,21 @@ function createShardedQueue(native, comm, options){
   const shards = [];
   let totalRows = 0;
   let nUsers = 0;
-  for(let r = 0; r < world; r++){
-    const ctx = native.commCtx(comm, r);
-    const st = native.stats(ctx);
-    const rows = Number(st.rows), users = Number(st.users);
-    const rowMap = new Int32Array(Math.max(rows, 1)), userMap = new Int32Array(Math.max(users, 1)).fill(-1);
-    native.shardMaps(ctx, rowMap, userMap);
-    for(let u = 0; u < users; u++){ nUsers = Math.max(nUsers, userMap[u] + 1); }
-    shards.push({ctx, users: userMap, rows: rowMap.subarray(0, rows)});
-    totalRows += rows;
+  // every shard's maps as they stand (at creation, and again after a compaction: the shards' local rows move, global rows do not)
+  function readMaps(){
+    totalRows = 0;
+    for(let r = 0; r < world; r++){
+      const ctx = shards[r] ? shards[r].ctx : native.commCtx(comm, r);
+      const st = native.stats(ctx);
+      const rows = Number(st.rows), users = Number(st.users);
+      const rowMap = new Int32Array(Math.max(rows, 1)), userMap = new Int32Array(Math.max(users, 1)).fill(-1);
+      native.shardMaps(ctx, rowMap, userMap);
+      for(let u = 0; u < users; u++){ nUsers = Math.max(nUsers, userMap[u] + 1); }
+      shards[r] = {ctx, users: userMap, rows: rowMap.subarray(0, rows)};
+      totalRows += rows;
+    }
   }
+  readMaps();
   let userIds = opts.userIds || null;
 
   // the merged queue of the last call and where each row lives
@@ -99,6 +104,44 @@ function createShardedQueue(native, comm, options){
     return merged((rows, rank, local) => native.commArchiveQueue(comm, now, w, rows, rank, local));
   }
 
+  // ---- a sharded table that ages (pie_comm_prune_before / pie_comm_retention_purge_tz / pie_comm_compact_rows).  The lists are the
+  // rows the call tombstoned: ascending global rows with their owning rank (the host drops their token-map entries); they are
+  // also the `last` queue, so fetchRows reads them.  A list is never longer than the shards' rows, which is the room offered.
+  function maintained(call){
+    if(cap < totalRows){
+      cap = totalRows;
+      bufRows = new Int32Array(cap); bufRank = new Int32Array(cap); bufLocal = new Int32Array(cap);
+    }
+    const n = call(bufRows, bufRank, bufLocal);
+    last = {rows: bufRows.slice(0, n), rank: bufRank.slice(0, n), local: bufLocal.slice(0, n)};
+    return {rows: last.rows, rank: last.rank};
+  }
+
+  // _pruneCalendarEvents (server/storage/sqlProvider.js:956-968): every row with start < cutoff
+  function pruneBefore(cutoff){
+    return maintained((rows, rank, local) => native.commPruneBefore(comm, cutoff, rows, rank, local));
+  }
+
+  // _purgeExpiredArchives (sqlProvider.js:863-890, 991-1009): every row with now >= addMonths(start, months) on a LOCAL date;
+  // zone = {transitions, offsets} (tzTable.buildTzTable), default this process's zone
+  function purgeRetention(now, months, zone){
+    const tz = zone || require('./tzTable').defaultTzTable();
+    const at = now === undefined || now === null ? Date.now() : now;
+    return maintained((rows, rank, local) => native.commRetentionPurge(comm, at, months === undefined ? 2 : months, tz.transitions, tz.offsets,
+                                                                       rows, rank, local));
+  }
+
+  // drop the dead rows on every shard (end <= deadBefore; default: tombstones only).  Global rows keep their numbers; the shards'
+  // local rows move, so the maps are read again and the last queue is forgotten.  -> {kept, keptLocal}
+  function compact(deadBefore, o){
+    const keptLocal = new Int32Array(world);
+    const kept = native.commCompactRows(comm, deadBefore === undefined || deadBefore === null ? END_NONE : deadBefore,
+                                        Boolean(o && o.shrink), keptLocal);
+    last = null;
+    readMaps();
+    return {kept, keptLocal: Array.from(keptLocal)};
+  }
+
   // columns of global rows of the last queue (any subset, any order): {start, end, user (global id), disc}
   function fetchRows(globalRows){
     const m = globalRows.length;
@@ -136,7 +179,7 @@ function createShardedQueue(native, comm, options){
   }
 
   return {
-    expiredRows, expiredRowsInFlight, archivedRows, fetchRows,
+    expiredRows, expiredRowsInFlight, archivedRows, fetchRows, pruneBefore, purgeRetention, compact,
     userIds: () => {
       if(userIds === null){ userIds = Array.from({length: nUsers}, (_, g) => 'user-' + g); }
       return userIds;
