@@ -630,6 +630,48 @@ int pie_token_layout(pie_ctx *ctx, size_t *covered_out, size_t *slots_out, int32
 size_t pie_token_slots_for(size_t covered);
 int pie_token_homes(const uint64_t *tok, size_t k, uint32_t log2_slots, uint32_t *home_out);
 
+/* ---- a whole event-loop TURN by token: an ORDERED list of getSession / touchSession / deleteSession calls
+ * (server/sessionStore.js:21-53), each with its own clock, in one upload, one kernel, one download and one wait.  The results
+ * equal the calls made one by one: a touch changes what the next get of the same token returns, a delete makes the following
+ * touch a no-op, a get after a touch sees the new end.
+ * A key's row is the one pie_token_lookup finds: the largest row under the key, or -1.  Let e be that row's `end`.  The ops are
+ * applied in array order; ops with different keys never interact (distinct keys have distinct rows).
+ *     op      condition                     live_out              end_out        effect
+ *     GET     always                        found && e > now      e              none
+ *     TOUCH   found && e > now              1                     new_end        e := new_end
+ *     TOUCH   otherwise                     0                     e              none
+ *     DELETE  found && e != PIE_END_NONE    0                     PIE_END_NONE   e := PIE_END_NONE (liveness not consulted, :47-53)
+ *     DELETE  otherwise                     0                     e              none
+ * row_out = the row, or -1 when the key is not found; for DELETE also -1 when the row was already a tombstone (the rule of
+ * pie_token_set_end's rows_out under now = PIE_END_NONE).  user_out and start_out as in pie_token_lookup (undefined for -1);
+ * end_out of a key that is not found is PIE_END_NONE.
+ * A get or touch that finds its row expired writes nothing: expired rows stay findable and report live = 0, the rule of the
+ * whole token index.  That equals the reference's `sessions.delete(hash)` on an expired lookup (:30-33) whenever the clocks of
+ * one key's ops do not decrease within the turn: a row found expired at `now` is expired at every later clock.
+ * Every write of `end` goes through the path pie_set_end's kernel takes, once per row that ends the turn with another value
+ * than it began with: both keys, the hot index and the ordered run stay in step.
+ * Cost: one lane per key; the ops of one key are applied by that lane one after another, so a turn in which every op names
+ * one token costs k serial steps.
+ * Every output pointer may be NULL.  k = 0 is allowed.  Like the other synchronous token calls a turn sees every append, touch
+ * and pie_token_append queued before it with no host wait in between; it waits once, bounded by PIE_WAIT_DEADLINE_MS.
+ * PIE_E_STATE: no table; no token column; a scan or batch in flight (a turn mutates).  PIE_E_INVAL: NULL ops with k > 0;
+ * k >= 2^31; an unknown kind; reserved != 0 — nothing is changed. */
+#define PIE_TURN_GET    0
+#define PIE_TURN_TOUCH  1
+#define PIE_TURN_DELETE 2
+typedef struct pie_turn_op {   /* 40 bytes, no padding */
+    uint64_t tok[2];           /* key as in pie_token_* */
+    int64_t  now;              /* the call's own clock */
+    int64_t  new_end;          /* TOUCH only */
+    int32_t  kind, reserved;   /* reserved = 0 */
+} pie_turn_op;
+/* host only, no context, no GPU: the chains the device walks.  next_out[i] = the index of the next op with op i's key, or -1;
+ * head_out[i] = 1 iff no earlier op has that key.  One pass through an open-addressed table sized by k.  PIE_E_INVAL: a NULL
+ * pointer with k > 0; k >= 2^31.  Kinds and reserved words are not looked at. */
+int pie_token_turn_plan(const pie_turn_op *ops, size_t k, int32_t *next_out /* [k] */, uint8_t *head_out /* [k] */);
+int pie_token_turn(pie_ctx *ctx, const pie_turn_op *ops, size_t k, int32_t *row_out, uint8_t *live_out, int32_t *user_out,
+                   int64_t *start_out, int64_t *end_out);
+
 /* ---- the token column of a SHARDED context, by GLOBAL row.  Every shard is given the same call with the same arrays and keeps
  * what is its own; nothing is exchanged (the rule of pie_shard_append_rows / pie_shard_set_end).
  * Coverage: the context remembers covered_g — keys have been given for the global rows [0, covered_g), covered_g <= N_g — and
@@ -662,6 +704,11 @@ int pie_shard_token_lookup(pie_ctx *ctx, const uint64_t *tok, size_t k, int64_t 
 /* one lookup, then pie_set_end's own path on the local rows found live (exactly how pie_token_set_end composes: repeats, both
  * keys, the hot index and the ordered run stay in step).  rows_global_out[i] (may be NULL) = the global row written or -1. */
 int pie_shard_token_set_end(pie_ctx *ctx, const uint64_t *tok, const int64_t *new_end, size_t k, int64_t now, int32_t *rows_global_out);
+/* pie_token_turn on this shard's column: the same rules and the same single launch, the row and the user answered as GLOBAL ids
+ * (read through the two maps, as pie_shard_token_lookup reads them).  A key this shard does not hold answers -1 / live 0 /
+ * PIE_END_NONE for every op of its chain, and the chain changes nothing. */
+int pie_shard_token_turn(pie_ctx *ctx, const pie_turn_op *ops, size_t k, int32_t *row_global_out, uint8_t *live_out,
+                         int32_t *user_global_out, int64_t *start_out, int64_t *end_out);
 /* tests and tools: covered_g, covered_l, slots; slot_row_out[cap] (local rows; PIE_E_CAPACITY if cap < slots);
  * tok_out[covered_l][2]; any may be NULL.  Waits. */
 int pie_shard_token_layout(pie_ctx *ctx, size_t *covered_global_out, size_t *covered_local_out, size_t *slots_out,
@@ -875,6 +922,14 @@ int pie_comm_token_append(pie_comm *comm, const uint64_t *tok, size_t k);
 int pie_comm_token_lookup(pie_comm *comm, const uint64_t *tok, size_t k, int64_t now, int32_t *row_out, uint8_t *live_out,
                           int32_t *user_out, int64_t *start_out, int64_t *end_out, int32_t *owner_rank_out);
 int pie_comm_token_set_end(pie_comm *comm, const uint64_t *tok, const int64_t *new_end, size_t k, int64_t now, int32_t *rows_out);
+/* pie_token_turn across the local shards: every local shard is given the same turn (pie_shard_token_turn); all are checked before
+ * any is changed and all are queued before any is waited for.  Per op the answer comes from the shard with the LARGEST global row
+ * (pie_comm_token_lookup's merge), owner_rank_out[i] (may be NULL) = its rank, -1 if no local shard holds the key.  With every
+ * key held by one shard — tokens are 48 random bytes — this is the unsharded pie_token_turn's result.  A key held by two shards
+ * (a caller error in the reference) has its chain applied by each shard to its own latest row.  PIE_E_STATE while pipelined steps
+ * are uncollected; PIE_E_INVAL as pie_token_turn. */
+int pie_comm_token_turn(pie_comm *comm, const pie_turn_op *ops, size_t k, int32_t *row_out, uint8_t *live_out,
+                        int32_t *owner_rank_out, int32_t *user_out, int64_t *start_out, int64_t *end_out);
 
 /* ---- the pipelined exchange: ONE union message per step (layout: pie_scan_batch_begin_union), written by each shard's own
  * batch kernels; the exchange of step i runs on a side stream while the shards scan steps i+1, i+2.  Order of calls:

@@ -211,6 +211,9 @@ _SIGS = [
     ("pie_token_layout", C.c_int, [_P, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), _P, C.c_size_t, _P]),
     ("pie_token_slots_for", C.c_size_t, [C.c_size_t]),
     ("pie_token_homes", C.c_int, [_P, C.c_size_t, C.c_uint32, _P]),
+    ("pie_token_turn_plan", C.c_int, [_P, C.c_size_t, _P, _P]),
+    ("pie_token_turn", C.c_int, [_P, _P, C.c_size_t, _P, _P, _P, _P, _P]),
+    ("pie_shard_token_turn", C.c_int, [_P, _P, C.c_size_t, _P, _P, _P, _P, _P]),
     ("pie_shard_token_set", C.c_int, [_P, _P, C.c_size_t]),
     ("pie_shard_token_append", C.c_int, [_P, _P, C.c_size_t]),
     ("pie_shard_token_lookup", C.c_int, [_P, _P, C.c_size_t, C.c_int64, _P, _P, _P, _P, _P]),
@@ -231,6 +234,7 @@ _SIGS = [
     ("pie_comm_token_append", C.c_int, [_P, _P, C.c_size_t]),
     ("pie_comm_token_lookup", C.c_int, [_P, _P, C.c_size_t, C.c_int64, _P, _P, _P, _P, _P, _P]),
     ("pie_comm_token_set_end", C.c_int, [_P, _P, _P, C.c_size_t, C.c_int64, _P]),
+    ("pie_comm_token_turn", C.c_int, [_P, _P, C.c_size_t, _P, _P, _P, _P, _P, _P]),
     ("pie_comm_token_lookup_begin", C.c_int, [_P, _P, _P, C.c_size_t]),
     ("pie_comm_token_lookup_finish", C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("pie_comm_token_lookup_room", C.c_int, [_P]),
@@ -874,6 +878,20 @@ class PieScan:
         self._check(self._lib.pie_token_set_end(self._ctx, _ptr(keys), _ptr(new_end), keys.shape[0], int(now), _ptr(rows)))
         return rows
 
+    def _token_turn(self, fn, ops):
+        ops = turn_ops(ops)
+        k = ops.shape[0]
+        out = {"row": np.empty(k, np.int32), "live": np.empty(k, np.uint8), "user": np.empty(k, np.int32),
+               "start": np.empty(k, np.int64), "end": np.empty(k, np.int64)}
+        self._check(fn(self._ctx, _ptr(ops), k, _ptr(out["row"]), _ptr(out["live"]), _ptr(out["user"]), _ptr(out["start"]), _ptr(out["end"])))
+        return out
+
+    def token_turn(self, ops):
+        """A whole turn in one launch: ops is a TURN_OP array (or what turn_ops takes), applied in order, each op with its own
+        clock -> the dict token_lookup returns, one entry per op (pie_token_turn: live = the call succeeded, end = the row's end
+        after the op)."""
+        return self._token_turn(self._lib.pie_token_turn, ops)
+
     def token_layout(self):
         """-> (covered, slots, slot_row[slots], keys[covered, 2]) of the index, for tests and tools."""
         cov, slots = C.c_size_t(0), C.c_size_t(0)
@@ -1050,6 +1068,10 @@ class PieScan:
         rows = np.empty(keys.shape[0], np.int32)
         self._check(self._lib.pie_shard_token_set_end(self._ctx, _ptr(keys), _ptr(new_end), keys.shape[0], int(now), _ptr(rows)))
         return rows
+
+    def shard_token_turn(self, ops):
+        """token_turn on this shard's column: rows and users as GLOBAL ids; a key the shard does not hold answers -1 / 0."""
+        return self._token_turn(self._lib.pie_shard_token_turn, ops)
 
     def shard_token_layout(self):
         """-> (covered_global, covered_local, slots, slot_row[slots] of LOCAL rows, keys[covered_local, 2]), for tests and tools."""
@@ -1482,6 +1504,16 @@ class PieComm:
         self._check(self._lib.pie_comm_token_set_end(self._c, _ptr(keys), _ptr(new_end), keys.shape[0], int(now), _ptr(rows)))
         return rows
 
+    def token_turn(self, ops):
+        """A whole turn on every local shard, merged per op -> the dict token_lookup returns (owner included), one entry per op."""
+        ops = turn_ops(ops)
+        k = ops.shape[0]
+        out = {"row": np.empty(k, np.int32), "live": np.empty(k, np.uint8), "user": np.empty(k, np.int32),
+               "start": np.empty(k, np.int64), "end": np.empty(k, np.int64), "owner": np.empty(k, np.int32)}
+        self._check(self._lib.pie_comm_token_turn(self._c, _ptr(ops), k, _ptr(out["row"]), _ptr(out["live"]), _ptr(out["owner"]),
+                                                  _ptr(out["user"]), _ptr(out["start"]), _ptr(out["end"])))
+        return out
+
     # ---- token lookups and the expired queue while steps are in flight (pie_comm_token_lookup_begin ..., pie_comm_expired_queue_begin ...)
     def token_lookup_begin(self, keys, now):
         """Queue getSession for every key on every local shard (now: one clock for all, or one per key), whatever steps are in
@@ -1602,6 +1634,39 @@ def token_key(token):
     if isinstance(token, str):
         token = token.encode("utf-8")
     return np.frombuffer(hashlib.sha256(token).digest()[:16], dtype="<u8").astype(np.uint64)
+
+
+# pie_turn_op (include/pie_scan.h): one op of a turn, 40 bytes without padding
+TURN_GET, TURN_TOUCH, TURN_DELETE = 0, 1, 2
+TURN_OP = np.dtype([("tok", "<u8", (2,)), ("now", "<i8"), ("new_end", "<i8"), ("kind", "<i4"), ("reserved", "<i4")])
+assert TURN_OP.itemsize == 40
+
+
+def turn_ops(ops=None, keys=None, now=None, new_end=None, kind=None):
+    """-> a contiguous TURN_OP array: `ops` as given (a TURN_OP array), or built from keys (k, 2), and now / new_end / kind
+    (one value for all, or one per op)."""
+    if ops is not None:
+        ops = np.ascontiguousarray(ops)
+        if ops.dtype != TURN_OP or ops.ndim != 1:
+            raise ValueError("a turn is a one-dimensional array of binding.TURN_OP")
+        return ops
+    keys = _keys(keys)
+    out = np.zeros(keys.shape[0], TURN_OP)
+    out["tok"], out["now"], out["kind"] = keys, now, kind
+    out["new_end"] = 0 if new_end is None else new_end
+    return out
+
+
+def token_turn_plan(ops):
+    """Host only (pie_token_turn_plan): (next int32[k], head uint8[k]) — the next op with the same key (-1: none) and whether
+    the op is the first of its key: the chains the device walks."""
+    ops = turn_ops(ops)
+    k = ops.shape[0]
+    nxt, head = np.empty(k, np.int32), np.empty(k, np.uint8)
+    rc = load_library().pie_token_turn_plan(_ptr(ops), k, _ptr(nxt), _ptr(head))
+    if rc != 0:
+        raise PieError(rc, "pie_token_turn_plan: bad argument")
+    return nxt, head
 
 
 def token_slots_for(covered):

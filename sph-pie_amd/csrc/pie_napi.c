@@ -104,6 +104,8 @@
     X(int, pie_token_set, (pie_ctx *, const uint64_t *, size_t))                                                    \
     X(int, pie_token_append, (pie_ctx *, const uint64_t *, size_t))                                                 \
     X(int, pie_token_lookup, (pie_ctx *, const uint64_t *, size_t, int64_t, int32_t *, uint8_t *, int32_t *, int64_t *, int64_t *)) \
+    X(int, pie_token_turn, (pie_ctx *, const pie_turn_op *, size_t, int32_t *, uint8_t *, int32_t *, int64_t *, int64_t *)) \
+    X(int, pie_comm_token_turn, (pie_comm *, const pie_turn_op *, size_t, int32_t *, uint8_t *, int32_t *, int32_t *, int64_t *, int64_t *)) \
     X(int, pie_token_set_end, (pie_ctx *, const uint64_t *, const int64_t *, size_t, int64_t, int32_t *))                \
     X(int, pie_token_lookup_begin, (pie_ctx *, const uint64_t *, const int64_t *, size_t))                           \
     X(int, pie_token_lookup_finish, (pie_ctx *, int32_t *, uint8_t *, int32_t *, int64_t *, int64_t *, size_t, size_t *)) \
@@ -2299,6 +2301,66 @@ static napi_value fn_token_set_end(napi_env env, napi_callback_info info)
     return out;
 }
 
+/* ---- a whole turn in one launch (pie_token_turn): the ops travel as four parallel typed arrays and are packed into pie_turn_op
+ * here.  turn_ops -> a malloc'ed array of *k ops (NULL with an exception pending; k = 0 gives a one-op block nobody reads). */
+static pie_turn_op *turn_ops(napi_env env, napi_value *argv, const char *usage, size_t *k)
+{
+    size_t kn = 0, ke = 0, kk = 0;
+    uint64_t *keys = token_keys(env, argv[0], k);
+    if (!keys) return NULL;
+    int64_t *nows = typed(env, argv[1], napi_bigint64_array, &kn);
+    int64_t *ends = typed(env, argv[2], napi_bigint64_array, &ke);
+    uint8_t *kinds = typed(env, argv[3], napi_uint8_array, &kk);
+    if (!nows || !ends || !kinds || kn != *k || ke != *k || kk != *k) {
+        napi_throw_type_error(env, NULL, usage);
+        return NULL;
+    }
+    pie_turn_op *ops = calloc(*k ? *k : 1, sizeof(pie_turn_op));
+    if (!ops) {
+        napi_throw_error(env, NULL, "out of memory");
+        return NULL;
+    }
+    for (size_t i = 0; i < *k; ++i) {
+        ops[i].tok[0] = keys[2 * i];
+        ops[i].tok[1] = keys[2 * i + 1];
+        ops[i].now = nows[i];
+        ops[i].new_end = ends[i];
+        ops[i].kind = kinds[i]; /* 0 get, 1 touch, 2 delete; anything else is the library's to refuse */
+    }
+    return ops;
+}
+
+/* tokenTurn(ctx, keys BigUint64Array[2k], nows BigInt64Array, newEnds BigInt64Array, kinds Uint8Array) -> tokenLookup's object,
+ * one entry per op, the ops applied in order (include/pie_scan.h, pie_token_turn) */
+static napi_value fn_token_turn(napi_env env, napi_callback_info info)
+{
+    ARGS(5)
+    pie_ctx *ctx = get_ctx(env, argv[0]);
+    if (!ctx) return NULL;
+    size_t k = 0;
+    pie_turn_op *ops = turn_ops(env, argv + 1, "tokenTurn(ctx, BigUint64Array keys, BigInt64Array nows, BigInt64Array newEnds, Uint8Array kinds)", &k);
+    if (!ops) return NULL;
+    napi_value out;
+    if (napi_create_object(env, &out) != napi_ok) {
+        free(ops);
+        napi_throw_error(env, NULL, "N-API call failed: result object");
+        return NULL;
+    }
+    int32_t *row = token_out(env, out, "row", napi_int32_array, 4, k);
+    uint8_t *live = token_out(env, out, "live", napi_uint8_array, 1, k);
+    int32_t *user = token_out(env, out, "user", napi_int32_array, 4, k);
+    int64_t *start = token_out(env, out, "start", napi_bigint64_array, 8, k);
+    int64_t *end = token_out(env, out, "end", napi_bigint64_array, 8, k);
+    if (!row || !live || !user || !start || !end) {
+        free(ops);
+        return NULL;
+    }
+    int rc = p_pie_token_turn(ctx, ops, k, row, live, user, start, end);
+    free(ops);
+    if (rc) return throw_pie(env, ctx, rc);
+    return out;
+}
+
 /* ---- a batch held in flight, and token lookups beside it (pie_scan_batch_begin / _finish, pie_token_lookup_begin / _finish) -----
  * scanBatchBegin queues a batch and returns; scanBatchFinish waits for the oldest.  Between the two the turn's cookies are
  * resolved: tokenLookupBegin queues the lookup on its own stream, tokenLookupFinish waits for it on the libuv pool (the handle is
@@ -2618,6 +2680,37 @@ static napi_value fn_comm_token_lookup(napi_env env, napi_callback_info info)
     return out;
 }
 
+/* commTokenTurn(comm, keys, nows, newEnds, kinds) -> tokenTurn's object with global row and user, plus owner Int32Array */
+static napi_value fn_comm_token_turn(napi_env env, napi_callback_info info)
+{
+    ARGS(5)
+    comm_box *cbx = get_comm_box(env, argv[0]);
+    if (!cbx) return NULL;
+    size_t k = 0;
+    pie_turn_op *ops = turn_ops(env, argv + 1, "commTokenTurn(comm, BigUint64Array keys, BigInt64Array nows, BigInt64Array newEnds, Uint8Array kinds)", &k);
+    if (!ops) return NULL;
+    napi_value out;
+    if (napi_create_object(env, &out) != napi_ok) {
+        free(ops);
+        napi_throw_error(env, NULL, "N-API call failed: result object");
+        return NULL;
+    }
+    int32_t *row = token_out(env, out, "row", napi_int32_array, 4, k);
+    uint8_t *live = token_out(env, out, "live", napi_uint8_array, 1, k);
+    int32_t *user = token_out(env, out, "user", napi_int32_array, 4, k);
+    int64_t *start = token_out(env, out, "start", napi_bigint64_array, 8, k);
+    int64_t *end = token_out(env, out, "end", napi_bigint64_array, 8, k);
+    int32_t *owner = token_out(env, out, "owner", napi_int32_array, 4, k);
+    if (!row || !live || !user || !start || !end || !owner) {
+        free(ops);
+        return NULL;
+    }
+    int rc = p_pie_comm_token_turn(cbx->comm, ops, k, row, live, owner, user, start, end);
+    free(ops);
+    if (rc) return throw_comm(env, cbx->comm, rc);
+    return out;
+}
+
 /* commTokenSetEnd(comm, keys, newEnd BigInt64Array, now) -> Int32Array global rows written (-1: not found, or not live at `now`) */
 static napi_value fn_comm_token_set_end(napi_env env, napi_callback_info info)
 {
@@ -2912,6 +3005,7 @@ static napi_value init(napi_env env, napi_value exports)
         {"commAppendRows", fn_comm_append_rows}, {"commSetEnd", fn_comm_set_end}, {"commDeleteUser", fn_comm_delete_user}, {"commDeleteUsers", fn_comm_delete_users}, {"commPruneBefore", fn_comm_prune_before}, {"commRetentionPurge", fn_comm_retention_purge}, {"commCompactRows", fn_comm_compact_rows}, {"commTableSize", fn_comm_table_size},
         {"shardMaps", fn_shard_maps},
         {"tokenSet", fn_token_set}, {"tokenAppend", fn_token_append}, {"tokenLookup", fn_token_lookup}, {"tokenSetEnd", fn_token_set_end},
+        {"tokenTurn", fn_token_turn}, {"commTokenTurn", fn_comm_token_turn},
         {"commTokenSet", fn_comm_token_set}, {"commTokenAppend", fn_comm_token_append}, {"commTokenLookup", fn_comm_token_lookup},
         {"commTokenSetEnd", fn_comm_token_set_end},
         {"scanBatchBegin", fn_scan_batch_begin}, {"scanBatchFinish", fn_scan_batch_finish}, {"tokenLookupBegin", fn_token_lookup_begin},

@@ -22,6 +22,7 @@
 #include "pie_kernels.h"
 #include "pie_ordered.h"
 #include "pie_token.h"
+#include "pie_turn_plan.h"
 #include "pie_expq.h"
 #include "pie_wait.h"
 
@@ -353,6 +354,8 @@ struct pie_ctx {
         char* d_stage = nullptr;
         size_t stage_bytes = 0;
         hipEvent_t ev[2] = {};      // around the last rebuild (build_ms)
+        hipEvent_t turn_done = nullptr;     // behind a turn's download (pie_token_turn): what its one wait polls
+        std::vector<int32_t> turn_slots;    // scratch of the turn's plan (pie_turn_plan.h), kept between calls
         bool timed = false;
         bool hold = false;
         double build_ms = 0;
@@ -3833,6 +3836,7 @@ int pie_ctx_destroy(pie_ctx* c)
     dfree(c->tokx.status);
     dfree(c->tokx.d_stage);
     if (c->tokx.h_stage) (void)hipHostFree(c->tokx.h_stage);
+    if (c->tokx.turn_done) (void)hipEventDestroy(c->tokx.turn_done);
     for (hipEvent_t e : c->tokx.ev)
         if (e) (void)hipEventDestroy(e);
     side_close(c->tokx.side);
@@ -6912,6 +6916,24 @@ static long long token_bound(const pie_ctx* c)
     return c->n < t.cap ? c->n : t.cap;
 }
 
+// tokx.h_stage / d_stage hold at least `bytes` (they grow by doubling; growing waits for what still uses the old pair)
+static int token_stage_room(pie_ctx* c, size_t bytes)
+{
+    pie_ctx::TokenIndex& t = c->tokx;
+    if (bytes <= t.stage_bytes) return PIE_OK;
+    size_t want = t.stage_bytes ? t.stage_bytes : (size_t)64 << 10;
+    while (want < bytes) want *= 2;
+    PIE_HIP(c, hipStreamSynchronize(c->stream));
+    if (t.h_stage) (void)hipHostFree(t.h_stage);
+    dfree(t.d_stage);
+    t.h_stage = nullptr;
+    t.stage_bytes = 0;
+    PIE_HIP(c, hipHostMalloc(&t.h_stage, want, hipHostMallocDefault));
+    PIE_HIP(c, hipMalloc(&t.d_stage, want));
+    t.stage_bytes = want;
+    return PIE_OK;
+}
+
 // The queue phase of a lookup: the keys go up, one launch for k keys, the results and the status words come back into
 // tokx.h_stage (token_stage_of) — all queued on the stream, nothing waited for.  global: the sharded kernel, which also answers
 // the global row and translates the user.
@@ -6921,18 +6943,8 @@ static int token_lookup_queue(pie_ctx* c, const uint64_t* tok, size_t k, long lo
     PIE_HIP(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
     const TokStage o = token_stage_of(k, global);
-    if (o.bytes > t.stage_bytes) {
-        size_t want = t.stage_bytes ? t.stage_bytes : (size_t)64 << 10;
-        while (want < o.bytes) want *= 2;
-        PIE_HIP(c, hipStreamSynchronize(s));
-        if (t.h_stage) (void)hipHostFree(t.h_stage);
-        dfree(t.d_stage);
-        t.h_stage = nullptr;
-        t.stage_bytes = 0;
-        PIE_HIP(c, hipHostMalloc(&t.h_stage, want, hipHostMallocDefault));
-        PIE_HIP(c, hipMalloc(&t.d_stage, want));
-        t.stage_bytes = want;
-    }
+    int rc = token_stage_room(c, o.bytes);
+    if (rc) return rc;
     char* d = t.d_stage;
     memcpy(t.h_stage, tok, k * sizeof(TokKey));
     PIE_HIP(c, hipMemcpyAsync(d, t.h_stage, k * sizeof(TokKey), hipMemcpyHostToDevice, s));
@@ -7024,6 +7036,117 @@ int pie_token_set_end(pie_ctx* c, const uint64_t* tok, const int64_t* new_end, s
     }
     if (rows.empty()) return PIE_OK;
     return set_end_apply(c, rows.data(), ends.data(), rows.size(), false);
+}
+
+// ---- a whole turn in one launch (pie_token_turn, pie_shard_token_turn; include/pie_scan.h, k_token_turn in pie_token.h)
+
+// offsets of a turn's staging block for k ops: [ops 40 k | next 4 k | pad | results as TokStage orders them: end 8 k | start 8 k |
+// row 4 k | user 4 k | live k | pad | status].  The sharded kernel answers GLOBAL rows in `row`.
+struct TurnStage {
+    size_t next, end, start, row, user, live, status, bytes;
+};
+static TurnStage turn_stage_of(size_t k)
+{
+    TurnStage o;
+    o.next = k * 40;
+    o.end = (k * 44 + 15) / 16 * 16;
+    o.start = o.end + k * 8; o.row = o.end + k * 16; o.user = o.end + k * 20; o.live = o.end + k * 24;
+    o.status = (o.end + k * 25 + 15) / 16 * 16;
+    o.bytes = o.status + kTokStatusWords * sizeof(unsigned int);
+    return o;
+}
+
+// What every form refuses beyond its state checks, with nothing staged or changed.  k > 0.
+static int token_turn_args(pie_ctx* c, const pie_turn_op* ops, size_t k, const char* what)
+{
+    if (!ops) return fail(c, PIE_E_INVAL, "%s: ops is NULL", what);
+    if (k >= ((size_t)1 << 31)) return fail(c, PIE_E_INVAL, "%s: %zu ops in one turn", what, k);
+    const size_t bad = turn_first_bad(ops, k);
+    if (bad < k) return fail(c, PIE_E_INVAL, "%s: op %zu has kind %d, reserved %d", what, bad, (int)ops[bad].kind, (int)ops[bad].reserved);
+    return PIE_OK;
+}
+
+// The queue phase (the checks are behind the caller, k > 0): the plan on the host, ONE upload of [ops | next], ONE kernel, ONE
+// download of the results and the status words, and an event behind them.  Nothing is waited for.
+static int token_turn_queue(pie_ctx* c, const pie_turn_op* ops, size_t k, bool global, const char* what)
+{
+    pie_ctx::TokenIndex& t = c->tokx;
+    PIE_HIP(c, hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const TurnStage o = turn_stage_of(k);
+    int rc = token_stage_room(c, o.bytes);
+    if (rc) return rc;
+    if (!t.turn_done) PIE_HIP(c, hipEventCreateWithFlags(&t.turn_done, hipEventDisableTiming));
+    // the plan straight into the pinned block: next[] where the device reads it, the head flags (built where the `live` results
+    // will land) into the reserved word of the staged ops
+    memcpy(t.h_stage, ops, k * sizeof(pie_turn_op));
+    pie_turn_op* staged = reinterpret_cast<pie_turn_op*>(t.h_stage);
+    uint8_t* head = reinterpret_cast<uint8_t*>(t.h_stage + o.live);
+    if (!turn_plan(ops, k, reinterpret_cast<int32_t*>(t.h_stage + o.next), head, t.turn_slots)) return fail(c, PIE_E_NOMEM, "%s: no memory for %zu ops", what, k);
+    for (size_t i = 0; i < k; ++i) staged[i].reserved = head[i];
+    hot_reserve(c, (long long)k); // the bound counts every op: never less than the rows that can move to the delta
+    char* d = t.d_stage;
+    PIE_HIP(c, hipMemcpyAsync(d, t.h_stage, o.next + k * 4, hipMemcpyHostToDevice, s));
+    const dim3 grid((unsigned)((k + 255) / 256)); // a thread per op
+    TurnMaps maps{};
+    if (global) maps = TurnMaps{(const int*)c->d_shard_rows, c->shard_rows_n, (const int*)c->d_shard_users, c->shard_users_n};
+    auto launch = global ? k_token_turn<true> : k_token_turn<false>;
+    hipLaunchKernelGGL(launch, grid, dim3(256), 0, s, reinterpret_cast<const TurnOp*>(d), reinterpret_cast<const int*>(d + o.next), (long long)k,
+                       (const int*)t.slot_row, t.log2_slots, (const TokKey*)t.tok, token_bound(c), c->d_end, (const long long*)c->d_start,
+                       (const int*)c->d_user, maps, c->d_key, c->key_base, c->key_shift, c->d_fkey, c->fkey_base, c->fkey_shift,
+                       ord_mirror_of(c), hot_mirror_of(c), reinterpret_cast<int*>(d + o.row), reinterpret_cast<unsigned char*>(d + o.live),
+                       reinterpret_cast<int*>(d + o.user), reinterpret_cast<long long*>(d + o.start), reinterpret_cast<long long*>(d + o.end),
+                       t.status);
+    PIE_HIP(c, hipGetLastError());
+    c->key_dirty = true;
+    PIE_HIP(c, hipMemcpyAsync(t.h_stage + o.end, d + o.end, o.status - o.end, hipMemcpyDeviceToHost, s));
+    PIE_HIP(c, hipMemcpyAsync(t.h_stage + o.status, t.status, kTokStatusWords * sizeof(unsigned int), hipMemcpyDeviceToHost, s));
+    PIE_HIP(c, hipEventRecord(t.turn_done, s));
+    return PIE_OK;
+}
+
+// The wait phase: the one wait of a turn, on its own event and bounded (pie_wait.h); then what set_end_apply does behind its
+// wait (a row the ordered run does not hold came back to life: the run goes), the status words, and the results.
+static int token_turn_wait(pie_ctx* c, size_t k, const char* what, int32_t* row_out, uint8_t* live_out, int32_t* user_out, int64_t* start_out,
+                           int64_t* end_out)
+{
+    pie_ctx::TokenIndex& t = c->tokx;
+    PIE_HIP(c, hipSetDevice(c->device));
+    const WaitResult w = event_wait(c, t.turn_done);
+    if (w.end == WaitEnd::Failed) return fail(c, PIE_E_HIP, "%s: the turn failed: %s", what, hipGetErrorString((hipError_t)w.err));
+    if (w.end != WaitEnd::Ready) return fail(c, PIE_E_HIP, "%s: not finished within %.0f ms (PIE_WAIT_DEADLINE_MS): kernel hung?", what, w.waited_ms);
+    if (c->ord.h_stale && *(volatile unsigned int*)c->ord.h_stale) {
+        *c->ord.h_stale = 0;
+        ord_invalidate(c);
+    }
+    const TurnStage o = turn_stage_of(k);
+    const char* h = t.h_stage;
+    int rc = token_status_check(c, reinterpret_cast<const unsigned int*>(h + o.status), what);
+    if (rc) return rc;
+    if (row_out) memcpy(row_out, h + o.row, k * 4);
+    if (live_out) memcpy(live_out, h + o.live, k);
+    if (user_out) memcpy(user_out, h + o.user, k * 4);
+    if (start_out) memcpy(start_out, h + o.start, k * 8);
+    if (end_out) memcpy(end_out, h + o.end, k * 8);
+    return PIE_OK;
+}
+
+int pie_token_turn_plan(const pie_turn_op* ops, size_t k, int32_t* next_out, uint8_t* head_out)
+{
+    if (k >= ((size_t)1 << 31) || (k && (!ops || !next_out || !head_out))) return PIE_E_INVAL;
+    std::vector<int32_t> slots;
+    return turn_plan(ops, k, next_out, head_out, slots) ? PIE_OK : PIE_E_NOMEM;
+}
+
+int pie_token_turn(pie_ctx* c, const pie_turn_op* ops, size_t k, int32_t* row_out, uint8_t* live_out, int32_t* user_out, int64_t* start_out,
+                   int64_t* end_out)
+{
+    if (!c) return PIE_E_INVAL;
+    int rc = token_ready(c, "pie_token_turn", true);
+    if (rc || k == 0) return rc;
+    if ((rc = token_turn_args(c, ops, k, "pie_token_turn")) != PIE_OK) return rc;
+    if ((rc = token_turn_queue(c, ops, k, false, "pie_token_turn")) != PIE_OK) return rc;
+    return token_turn_wait(c, k, "pie_token_turn", row_out, live_out, user_out, start_out, end_out);
 }
 
 // pie_token_layout and pie_shard_token_layout behind their checks; the covered rows are LOCAL ones (covered_l on a sharded column)
@@ -7182,9 +7305,39 @@ int shard_token_lookup_wait(pie_ctx* c, size_t k, int32_t* row_global_out, uint8
     if (end_out) memcpy(end_out, h + o.end, k * 8);
     return PIE_OK;
 }
+
+// The phases of pie_shard_token_turn, which the communicator runs shard by shard: every check with nothing staged or changed
+// (k = 0 passes the state checks alone), the queue phase, the wait phase.
+int shard_token_turn_check(pie_ctx* c, const pie_turn_op* ops, size_t k)
+{
+    if (!c) return PIE_E_INVAL;
+    int rc = shard_token_ready(c, "pie_shard_token_turn", true);
+    if (rc || k == 0) return rc;
+    return token_turn_args(c, ops, k, "pie_shard_token_turn");
+}
+
+int shard_token_turn_queue(pie_ctx* c, const pie_turn_op* ops, size_t k)
+{
+    return k == 0 ? PIE_OK : token_turn_queue(c, ops, k, true, "pie_shard_token_turn");
+}
+
+int shard_token_turn_wait(pie_ctx* c, size_t k, int32_t* row_global_out, uint8_t* live_out, int32_t* user_global_out, int64_t* start_out,
+                          int64_t* end_out)
+{
+    return k == 0 ? PIE_OK : token_turn_wait(c, k, "pie_shard_token_turn", row_global_out, live_out, user_global_out, start_out, end_out);
+}
 } // namespace pie_internal
 
 extern "C" {
+
+int pie_shard_token_turn(pie_ctx* c, const pie_turn_op* ops, size_t k, int32_t* row_global_out, uint8_t* live_out, int32_t* user_global_out,
+                         int64_t* start_out, int64_t* end_out)
+{
+    int rc = pie_internal::shard_token_turn_check(c, ops, k);
+    if (rc || k == 0) return rc;
+    if ((rc = pie_internal::shard_token_turn_queue(c, ops, k)) != PIE_OK) return rc;
+    return pie_internal::shard_token_turn_wait(c, k, row_global_out, live_out, user_global_out, start_out, end_out);
+}
 
 // One chunk (k <= 2^20 keys, checked by the caller) for the global rows [covered_g, covered_g + k): everything that can fail and
 // everything that waits comes first — the staging area, a longer column (the table grew), a larger table of slots (the shard's

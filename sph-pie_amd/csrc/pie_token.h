@@ -202,6 +202,89 @@ __global__ __launch_bounds__(256) void k_shard_token_lookup_now(const TokKey* __
     o_user[t] = (u >= 0 && u < n_map) ? users_map[u] : -1;
 }
 
+// ---- a whole turn (pie_token_turn / pie_shard_token_turn, include/pie_scan.h): an ordered list of get / touch / delete ops, each
+// with its own clock (sessionStore.js:21-53), answered and applied in one launch.
+//
+// The host has cut the turn into chains (pie_turn_plan.h): the ops that name one key, in array order, linked through next[].  One
+// thread per op; a thread whose op is not the head of a chain returns.  A head thread probes the index once (token_probe: the
+// bounded loop and the status word of every lookup), reads end / start / user of the row once, then walks its chain with `e`, the
+// row's `end`, in a register: every op is judged against the `e` the ops before it left, and its results are written where the op
+// stands in the array.  If `e` ends the walk with another value than the row had, touch_row stores it — once, and nowhere else:
+// `end`, both keys, the ordered run's mirror and the hot index's mirror move together.
+// Distinct keys have distinct rows (a key's row is the largest row that carries it), and all the ops of one key are walked by one
+// thread: no two threads ever write the same row, and no thread reads an `end` another one writes.  So the kernel needs no atomic
+// of its own, no barrier and no LDS, and nothing in it spins: the probe runs at most `slots` steps, the walk at most k (next[]
+// ascends; an entry that does not is the end of the chain).  A chain is walked by ONE lane: a turn in which every op names one
+// token costs k serial steps.
+// The uploaded array is the caller's pie_turn_op array with the `reserved` word (0 in the ABI) carrying the head flag.
+struct alignas(8) TurnOp {
+    unsigned long long k0, k1;
+    long long now, new_end;
+    int kind, head;
+};
+static_assert(sizeof(TurnOp) == 40, "TurnOp mirrors pie_turn_op");
+constexpr int kTurnGet = 0, kTurnTouch = 1, kTurnDelete = 2;
+
+// the two maps of a sharded context (kShard): rows and users are answered as GLOBAL ids, as k_shard_token_lookup answers them
+struct TurnMaps {
+    const int* rows;
+    long long n_local;
+    const int* users;
+    int n_users;
+};
+
+template <bool kShard>
+__global__ __launch_bounds__(256) void k_token_turn(const TurnOp* __restrict__ ops, const int* __restrict__ next, long long k,
+                                                    const int* __restrict__ slot_row, unsigned log2_slots, const TokKey* __restrict__ tok,
+                                                    long long bound, long long* __restrict__ end, const long long* __restrict__ start,
+                                                    const int* __restrict__ user, TurnMaps maps, lkey_t* __restrict__ key, long long key_base,
+                                                    int key_shift, fkey_t* __restrict__ fkey, long long fkey_base, int fkey_shift, OrdMirror ord,
+                                                    HotMirror hot, int* __restrict__ o_row, unsigned char* __restrict__ o_live,
+                                                    int* __restrict__ o_user, long long* __restrict__ o_start, long long* __restrict__ o_end,
+                                                    unsigned int* __restrict__ status)
+{
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= k) return;
+    TurnOp op = ops[t];
+    if (!op.head) return;
+    TokKey want;
+    want.x = op.k0;
+    want.y = op.k1;
+    const int best = token_probe(want, slot_row, log2_slots, tok, kShard && maps.n_local < bound ? maps.n_local : bound, status);
+    const bool found = best >= 0;
+    const long long e0 = found ? end[best] : INT64_MIN;
+    const long long sv = found ? start[best] : 0;
+    int uv = found ? user[best] : -1, rv = best;
+    if (kShard) {
+        rv = found ? maps.rows[best] : -1;
+        uv = (uv >= 0 && uv < maps.n_users) ? maps.users[uv] : -1;
+    }
+    long long e = e0, j = t;
+    for (long long step = 0; step < k; ++step) {
+        int r = rv;
+        unsigned char live = 0;
+        if (op.kind == kTurnTouch) {
+            if (found && e > op.now) {
+                e = op.new_end;
+                live = 1;
+            }
+        } else if (op.kind == kTurnDelete) {
+            if (found && e != INT64_MIN) e = INT64_MIN;
+            else r = -1;
+        } else live = (found && e > op.now) ? 1 : 0;
+        o_row[j] = r;
+        o_live[j] = live;
+        o_end[j] = e;
+        o_start[j] = sv;
+        o_user[j] = uv;
+        const long long nx = next[j];
+        if (nx <= j || nx >= k) break;
+        j = nx;
+        op = ops[j];
+    }
+    if (e != e0) touch_row(best, e, end, key, key_base, key_shift, fkey, fkey_base, fkey_shift, ord, hot);
+}
+
 // the compaction hook: the keys of the kept covered rows, in their new places
 __global__ __launch_bounds__(256) void k_token_gather(const TokKey* __restrict__ tok_old, const int* __restrict__ old_of_new, long long n_new,
                                                       long long covered_old, TokKey* __restrict__ tok_new)

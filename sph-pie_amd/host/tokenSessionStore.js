@@ -1,0 +1,167 @@
+'use strict';
+// Session store with the reference module's interface (server/sessionStore.js:75-84: createSession, getSession, touchSession,
+// deleteSession, deleteSessionsForUser, purgeExpiredSessions, SESSION_TTL_MS, SESSION_COOKIE_NAME — synchronous, never throwing
+// on a miss, null for "no session") that keeps NO per-session state on the host: no token map, no row mirror.
+//
+// The sessions are the rows of the device table; the token -> row map is the device's token column and its index (pie_token_*,
+// include/pie_scan.h).  createSession appends one row and its key (appendRows + tokenAppend, queued, nothing waited for);
+// everything by token is a TURN: an ordered list of get / touch / del calls, each with its own clock, answered and applied by
+// the device in one upload, one kernel, one download and one wait (tokenTurn -> pie_token_turn), with the results the
+// reference gives when the calls are made one after another (:21-53).  turn(calls) is that list as the caller's event-loop turn
+// collected it; getSession, touchSession and deleteSession are turns of one.
+// What the host keeps: the user-id strings (dense int32 <-> userId, as host/sessionStore.js keeps them) and a row count.
+//
+// A session found expired writes nothing (the reference drops it from its Map, :30-33); the row stays findable and answers
+// "no session" at every later clock, which is the same as long as the clocks of one token do not decrease.  purgeExpiredSessions
+// turns the expired rows into tombstones, as deleteSession and deleteSessionsForUser do with theirs.
+const crypto = require('crypto');
+const disciplineConfig = require('./disciplineConfig');
+const pieNative = require('./pieNative');
+const {keyOfToken} = require('./tokenKeys');
+
+const SESSION_TTL_MS = 12 * 60 * 60 * 1000;
+const SESSION_COOKIE_NAME = 'mt_session';
+const END_NONE = -(2n ** 63n);          // PIE_END_NONE: tombstone, never live
+const KIND = {get: 0, touch: 1, del: 2};   // PIE_TURN_GET / _TOUCH / _DELETE
+
+function createStore(options){
+  const opts = options || {};
+  const native = pieNative.load();                 // throws if the addon / HIP library is missing
+  const ctx = native.ctxCreate(opts.device === undefined ? 0 : opts.device);   // throws without a GPU
+  if(opts.orderedRun !== undefined){ native.setOrderedRun(ctx, opts.orderedRun); }
+  const userIndex = new Map();                     // userId string -> dense int32
+  const userIds = [];                              // dense int32 -> userId string
+  let nRows = 0;                                   // rows of the device table = sessions ever created here
+
+  function denseUser(userId){
+    let u = userIndex.get(userId);
+    if(u === undefined){
+      u = userIds.length;
+      userIndex.set(userId, u);
+      userIds.push(userId);
+    }
+    return u;
+  }
+
+  function createSession(userId, disciplineId){
+    const token = crypto.randomBytes(48).toString('hex');
+    const now = Date.now();
+    const expiresAt = now + SESSION_TTL_MS;
+    const disc = disciplineId === undefined
+      ? (disciplineConfig.DEFAULT_DISCIPLINE ? disciplineConfig.disciplineIndex(disciplineConfig.DEFAULT_DISCIPLINE.id) : 0)
+      : disciplineConfig.disciplineIndex(disciplineId);
+    const s = BigInt64Array.of(BigInt(now)), e = BigInt64Array.of(BigInt(expiresAt));
+    const u = Int32Array.of(denseUser(userId)), d = Int32Array.of(disc);
+    if(nRows === 0){                               // the first session: the table and the column come with it
+      native.loadColumns(ctx, s, e, u, d, userIds.length);
+      native.tokenSet(ctx, keyOfToken(token));
+    }else{
+      native.appendRows(ctx, s, e, u, d, userIds.length);
+      native.tokenAppend(ctx, keyOfToken(token));
+    }
+    nRows++;
+    return {token, expiresAt};
+  }
+
+  // calls: [{op: 'get' | 'touch' | 'del', token, now?}] -> the reference's return values in order: getSession's
+  // {userId, createdAt, expiresAt} or null, touchSession's {userId, expiresAt} or null, undefined for del.
+  // now defaults to Date.now() at the time of this call; a falsy token is answered on the host (null / no-op, :22, :48).
+  function turn(calls){
+    const results = new Array(calls.length);
+    const sent = [];                               // positions of the calls that go to the device
+    for(let i = 0; i < calls.length; i++){
+      if(KIND[calls[i].op] === undefined){ throw new TypeError('turn: op is get, touch or del'); }
+      results[i] = calls[i].op === 'del' ? undefined : null;
+      if(calls[i].token && nRows > 0){ sent.push(i); }
+    }
+    const k = sent.length;
+    if(k === 0){
+      return results;
+    }
+    const clock = Date.now();
+    const keys = new BigUint64Array(2 * k), nows = new BigInt64Array(k), newEnds = new BigInt64Array(k), kinds = new Uint8Array(k);
+    for(let j = 0; j < k; j++){
+      const c = calls[sent[j]];
+      const now = c.now === undefined ? clock : c.now;
+      keys.set(keyOfToken(c.token), 2 * j);
+      nows[j] = BigInt(now);
+      kinds[j] = KIND[c.op];
+      newEnds[j] = c.op === 'touch' ? BigInt(now + SESSION_TTL_MS) : 0n;
+    }
+    const got = native.tokenTurn(ctx, keys, nows, newEnds, kinds);
+    for(let j = 0; j < k; j++){
+      if(got.live[j] !== 1){
+        continue;                                  // unknown, expired or deleted: null (undefined for del) stands
+      }
+      const userId = userIds[got.user[j]];
+      results[sent[j]] = kinds[j] === KIND.get ? {userId, createdAt: Number(got.start[j]), expiresAt: Number(got.end[j])}
+                                                : {userId, expiresAt: Number(got.end[j])};
+    }
+    return results;
+  }
+
+  const getSession = token => turn([{op: 'get', token}])[0];
+  const touchSession = token => turn([{op: 'touch', token}])[0];
+  const deleteSession = token => { turn([{op: 'del', token}]); };
+
+  // full-table scan on the device (user == x, strict); the rows it tombstones are nobody's to remember here
+  function deleteSessionsForUser(userId){
+    if(!userId || nRows === 0){
+      return;
+    }
+    const u = userIndex.get(userId);
+    if(u === undefined){
+      return;
+    }
+    native.deleteUser(ctx, u, new Int32Array(nRows));
+  }
+
+  // `now` is sampled once (:67); every row with end <= now that is not a tombstone becomes one
+  function purgeExpiredSessions(){
+    if(nRows === 0){
+      return undefined;
+    }
+    const list = new Int32Array(nRows);
+    const k = native.expiredQueue(ctx, END_NONE, Date.now(), list);
+    if(k > 0){
+      native.setEnd(ctx, list.subarray(0, k), new BigInt64Array(k).fill(END_NONE));
+    }
+    return undefined;
+  }
+
+  function close(){
+    native.ctxDestroy(ctx);
+  }
+
+  return {
+    createSession, getSession, touchSession, deleteSession, deleteSessionsForUser, purgeExpiredSessions, turn,
+    SESSION_TTL_MS, SESSION_COOKIE_NAME,
+    tableRows: () => nRows,
+    userIds: () => userIds,
+    close, native, ctx
+  };
+}
+
+// module-level singleton with the reference's export names; created on first use so that requiring this file
+// on a machine without a GPU fails at the first call, with the library's own error text.
+let shared = null;
+function store(){
+  if(shared === null){
+    shared = createStore();
+  }
+  return shared;
+}
+
+module.exports = {
+  createSession: (userId, disciplineId) => store().createSession(userId, disciplineId),
+  getSession: token => store().getSession(token),
+  touchSession: token => store().touchSession(token),
+  deleteSession: token => store().deleteSession(token),
+  deleteSessionsForUser: userId => store().deleteSessionsForUser(userId),
+  purgeExpiredSessions: () => store().purgeExpiredSessions(),
+  turn: calls => store().turn(calls),
+  SESSION_TTL_MS,
+  SESSION_COOKIE_NAME,
+  createStore,
+  sharedStore: store
+};
