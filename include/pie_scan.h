@@ -745,6 +745,50 @@ int pie_shard_token_lookup_begin(pie_ctx *ctx, const uint64_t *tok /* [k][2] */,
 int pie_shard_token_lookup_finish(pie_ctx *ctx, int32_t *row_global_out, uint8_t *live_out, int32_t *user_global_out,
                                   int64_t *start_out, int64_t *end_out, size_t cap, size_t *k_out);
 
+/* ---- token TURNS WHILE SCANS AND BATCHES ARE IN FLIGHT: touchSession on every authenticated request (server/sessionStore.js:
+ * 37-45) without draining the pipeline.  The ops, the results and the effect on the table are exactly pie_token_turn's (the
+ * table at PIE_TURN_GET / TOUCH / DELETE above); the shard form answers rows and users as GLOBAL ids, as pie_shard_token_turn.
+ * Allowed whenever the context has a table and a token column, whatever is in flight: single scans, batches on any lane, batches
+ * whose union tail still rides, wide batches, in-flight lookups, the in-flight expired queue, or nothing.
+ * Slots: up to 4 turns may be begun and not finished; they finish in the order they were begun.  Each owns its pinned and device
+ * staging, its status words and its event; nothing is shared with pie_token_turn or pie_token_lookup.  The staging of a slot grows
+ * only when a begin brings more ops than the slot has held before.
+ * Visibility is QUEUE ORDER, not the moment of finish:
+ *   - a scan, batch or wide batch begun before pie_token_turn_begin answers for the table before the turn;
+ *   - one begun after it sees every write of the turn; two turns apply in begin order;
+ *   - pie_token_lookup_begin / pie_expired_queue_begin issued after it see it, those issued before it do not;
+ *   - the exception: a query that a batch's finish reruns on the general path (a dense query, a union bucket that outgrew its
+ *     slots: see pie_scan_batch_begin) is answered for the table as it stands at that finish.
+ * How: the turn's kernel runs on the context's stream.  Begin first launches every union tail that still waits for a launch
+ * (what pie_scan_batch_flush does: a tail rebuilds the masks from the table), makes the context's stream wait for an event on
+ * every lane that has a batch in flight, queues the turn, and records one event behind it that every lane's next begin waits for
+ * once.  There is no host wait in begin.  The lanes stand still for the length of the turn's kernel.
+ * Waiting: finish waits once, for the turn's own event, bounded by PIE_WAIT_DEADLINE_MS (PIE_E_HIP past it; the slot is
+ * returned).  It never waits on the context's stream or a lane's.
+ * The ordered run: on a context whose ordered run is valid begin returns PIE_E_STATE.  The host sees the run's stale flag (a row
+ * outside the run came back to life) only at a wait, so a batch begun between begin and finish could read a stale run.
+ * pie_token_turn keeps serving such a table.
+ * The other calls: pie_token_turn, pie_token_set, pie_token_append, pie_token_set_end, pie_append_rows, pie_set_end,
+ * pie_delete_user(s), pie_prune_before, pie_retention_purge*, pie_expired_queue and every pie_shard_* call that checks the
+ * shard's state return PIE_E_STATE while a turn is begun and not finished, besides their rule for scans and batches.  Calls
+ * that replace or free the table, the token column or a shard's maps (loads, pie_gen_synthetic*, pie_shard_table,
+ * pie_compact_rows, pie_ctx_destroy) first wait on the host for the turns begun; their results stay readable by finish, in the
+ * ids of the table they were begun on.
+ * PIE_E_STATE: no table; no token column; an ordered run that is valid; a fifth begin with four unfinished (no slot is taken);
+ * finish with none begun, or by the other form than the begin; the shard form on a context that is not sharded or whose row map
+ * does not cover its rows.  PIE_E_INVAL: pie_token_turn's cases (NULL context; NULL ops with k > 0; k >= 2^31; an unknown kind;
+ * reserved != 0) — nothing is changed.  PIE_E_CAPACITY: cap < k at finish — *k_out is set and the turn stays begun.  *k_out (may
+ * be NULL) = ops of the turn; every output pointer may be NULL.  k = 0 takes and returns a slot and queues nothing.
+ * pie_token_turn_room: turns a begin (either form) would take now, 4 less those unfinished; PIE_E_INVAL for a NULL context.
+ * There is no pie_comm_* form. */
+int pie_token_turn_begin(pie_ctx *ctx, const pie_turn_op *ops, size_t k);
+int pie_token_turn_finish(pie_ctx *ctx, int32_t *row_out, uint8_t *live_out, int32_t *user_out, int64_t *start_out,
+                          int64_t *end_out, size_t cap, size_t *k_out);
+int pie_token_turn_room(pie_ctx *ctx);
+int pie_shard_token_turn_begin(pie_ctx *ctx, const pie_turn_op *ops, size_t k);
+int pie_shard_token_turn_finish(pie_ctx *ctx, int32_t *row_global_out, uint8_t *live_out, int32_t *user_global_out,
+                                int64_t *start_out, int64_t *end_out, size_t cap, size_t *k_out);
+
 /* ---- the expired queue WHILE SCANS AND BATCHES ARE IN FLIGHT.  pie_expired_queue borrows the scan slots' workspace and is
  * refused in flight; this form has a stream, scratch, a queue buffer and a summary of its own, and only reads the table.  So the
  * calls are allowed whenever the context has a table, whatever is in flight: single scans, batches on any lane, wide batches,

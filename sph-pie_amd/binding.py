@@ -224,6 +224,11 @@ _SIGS = [
     ("pie_token_lookup_room", C.c_int, [_P]),
     ("pie_shard_token_lookup_begin", C.c_int, [_P, _P, _P, C.c_size_t]),
     ("pie_shard_token_lookup_finish", C.c_int, [_P, _P, _P, _P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("pie_token_turn_begin", C.c_int, [_P, _P, C.c_size_t]),
+    ("pie_token_turn_finish", C.c_int, [_P, _P, _P, _P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("pie_token_turn_room", C.c_int, [_P]),
+    ("pie_shard_token_turn_begin", C.c_int, [_P, _P, C.c_size_t]),
+    ("pie_shard_token_turn_finish", C.c_int, [_P, _P, _P, _P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("pie_expired_queue_begin", C.c_int, [_P, C.c_int64, C.c_int64, C.c_size_t]),
     ("pie_expired_queue_finish", C.c_int, [_P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("pie_expired_queue_room", C.c_int, [_P]),
@@ -944,6 +949,44 @@ class PieScan:
     def shard_token_lookup_finish(self):
         """The oldest lookup begun -> the dict shard_token_lookup returns."""
         return self._token_lookup_finish(self._lib.pie_shard_token_lookup_finish)
+
+    # ---- turns beside scans and batches (pie_token_turn_begin / _finish): up to four begun and not finished
+    def _token_turn_begin(self, fn, ops):
+        ops = turn_ops(ops)
+        self._check(fn(self._ctx, _ptr(ops), ops.shape[0]))
+
+    def _token_turn_finish(self, fn):
+        got = C.c_size_t(0)
+        rc = fn(self._ctx, None, None, None, None, None, 0, C.byref(got))   # its size (k = 0 finishes here); none begun: PIE_E_STATE
+        if rc != PIE_E_CAPACITY:
+            self._check(rc)
+        k = got.value
+        out = {"row": np.empty(k, np.int32), "live": np.empty(k, np.uint8), "user": np.empty(k, np.int32),
+               "start": np.empty(k, np.int64), "end": np.empty(k, np.int64)}
+        if rc == PIE_E_CAPACITY:
+            self._check(fn(self._ctx, _ptr(out["row"]), _ptr(out["live"]), _ptr(out["user"]), _ptr(out["start"]), _ptr(out["end"]), k, C.byref(got)))
+        return out
+
+    def token_turn_begin(self, ops):
+        """Queue a whole turn (what token_turn takes) whatever scans and batches are in flight: scans and batches begun before
+        it answer for the table before the turn, those begun after it see its writes."""
+        self._token_turn_begin(self._lib.pie_token_turn_begin, ops)
+
+    def token_turn_finish(self):
+        """The oldest turn begun -> the dict token_turn returns."""
+        return self._token_turn_finish(self._lib.pie_token_turn_finish)
+
+    def token_turn_room(self):
+        """Turns token_turn_begin would take now."""
+        return int(self._lib.pie_token_turn_room(self._ctx))
+
+    def shard_token_turn_begin(self, ops):
+        """token_turn_begin on a sharded context: rows and users will be answered as GLOBAL ids."""
+        self._token_turn_begin(self._lib.pie_shard_token_turn_begin, ops)
+
+    def shard_token_turn_finish(self):
+        """The oldest turn begun -> the dict shard_token_turn returns."""
+        return self._token_turn_finish(self._lib.pie_shard_token_turn_finish)
 
     # ---- the expired queue beside scans and batches (pie_expired_queue_begin / _finish): one begun and not finished
     def _expired_queue_begin(self, fn, prev_now, now, cap_rows):

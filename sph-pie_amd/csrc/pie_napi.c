@@ -110,6 +110,9 @@
     X(int, pie_token_lookup_begin, (pie_ctx *, const uint64_t *, const int64_t *, size_t))                           \
     X(int, pie_token_lookup_finish, (pie_ctx *, int32_t *, uint8_t *, int32_t *, int64_t *, int64_t *, size_t, size_t *)) \
     X(int, pie_token_lookup_room, (pie_ctx *))                                                                       \
+    X(int, pie_token_turn_begin, (pie_ctx *, const pie_turn_op *, size_t))                                           \
+    X(int, pie_token_turn_finish, (pie_ctx *, int32_t *, uint8_t *, int32_t *, int64_t *, int64_t *, size_t, size_t *)) \
+    X(int, pie_token_turn_room, (pie_ctx *))                                                                         \
     X(int, pie_expired_queue_begin, (pie_ctx *, int64_t, int64_t, size_t))                                           \
     X(int, pie_expired_queue_finish, (pie_ctx *, int32_t *, size_t, size_t *))                                       \
     X(int, pie_expired_queue_room, (pie_ctx *))                                                                      \
@@ -217,6 +220,9 @@ typedef struct ctx_box_s {
     int lk_head, lk_n;
     int bt_q[16];
     int bt_head, bt_n;
+    /* ... and the ops of every turn begun beside them (tokenTurnBegin), oldest first */
+    size_t tn_k[4];
+    int tn_head, tn_n;
     /* the expired queue begun beside them (expiredQueueBegin): the rows its finish has to make room for */
     size_t eq_cap;
     int eq_begun;
@@ -2524,6 +2530,96 @@ static napi_value fn_token_lookup_finish(napi_env env, napi_callback_info info)
     return promise;
 }
 
+/* ---- turns beside a batch held in flight (pie_token_turn_begin / _finish / _room): tokenTurnBegin queues the turn on the context's
+ * stream, fenced against the batch lanes by the library, and returns; tokenTurnFinish waits for the turn's own event on the libuv
+ * pool (the handle is busy meanwhile) and resolves a Promise of tokenTurn's object. */
+
+/* tokenTurnBegin(ctx, keys, nows, newEnds, kinds) -> k */
+static napi_value fn_token_turn_begin(napi_env env, napi_callback_info info)
+{
+    ARGS(5)
+    pie_ctx *ctx = get_ctx(env, argv[0]);
+    if (!ctx) return NULL;
+    ctx_box *b = get_box(env, argv[0]);
+    size_t k = 0;
+    pie_turn_op *ops = turn_ops(env, argv + 1, "tokenTurnBegin(ctx, BigUint64Array keys, BigInt64Array nows, BigInt64Array newEnds, Uint8Array kinds)", &k);
+    if (!ops) return NULL;
+    if (b->tn_n >= 4) {
+        free(ops);
+        return throw_state(env, "pie_scan error -6: four token turns are begun and not finished");
+    }
+    int rc = p_pie_token_turn_begin(ctx, ops, k);
+    free(ops);
+    if (rc) return throw_pie(env, ctx, rc);
+    b->tn_k[(b->tn_head + b->tn_n) % 4] = k;
+    b->tn_n++;
+    return js_int(env, (int64_t)k);
+}
+
+/* tokenTurnRoom(ctx) -> turns tokenTurnBegin would take now */
+static napi_value fn_token_turn_room(napi_env env, napi_callback_info info)
+{
+    ARGS(1)
+    pie_ctx *ctx = get_ctx(env, argv[0]);
+    if (!ctx) return NULL;
+    return js_int(env, p_pie_token_turn_room(ctx));
+}
+
+static void turn_exec(napi_env env, void *data)
+{
+    (void)env;
+    lookup_job *j = (lookup_job *)data;
+    j->rc = p_pie_token_turn_finish(j->ctx, j->row, j->live, j->user, j->start, j->end, j->k, NULL);
+    if (j->rc) snprintf(j->err, sizeof j->err, "pie_scan error %d: %s", j->rc, p_pie_last_error(j->ctx));
+}
+
+/* tokenTurnFinish(ctx) -> Promise of tokenTurn's object for the oldest turn begun; the wait runs on the libuv pool */
+static napi_value fn_token_turn_finish(napi_env env, napi_callback_info info)
+{
+    ARGS(1)
+    pie_ctx *ctx = get_ctx(env, argv[0]);
+    if (!ctx) return NULL;
+    ctx_box *b = get_box(env, argv[0]);
+    if (b->tn_n == 0) return throw_state(env, "pie_scan error -6: no token turn was begun");
+    const size_t k = b->tn_k[b->tn_head];
+    lookup_job *j = (lookup_job *)calloc(1, sizeof *j);
+    if (!j) {
+        napi_throw_error(env, NULL, "out of memory");
+        return NULL;
+    }
+    napi_value out, promise;
+    if (napi_create_object(env, &out) != napi_ok) {
+        free(j);
+        napi_throw_error(env, NULL, "N-API call failed: result object");
+        return NULL;
+    }
+    j->ctx = ctx;
+    j->box = b;
+    j->k = k;
+    j->row = token_out(env, out, "row", napi_int32_array, 4, k);
+    j->live = token_out(env, out, "live", napi_uint8_array, 1, k);
+    j->user = token_out(env, out, "user", napi_int32_array, 4, k);
+    j->start = token_out(env, out, "start", napi_bigint64_array, 8, k);
+    j->end = token_out(env, out, "end", napi_bigint64_array, 8, k);
+    if (!j->row || !j->live || !j->user || !j->start || !j->end) {
+        free(j);
+        return NULL;
+    }
+    if (napi_create_reference(env, out, 1, &j->result) != napi_ok || napi_create_promise(env, &j->deferred, &promise) != napi_ok) {
+        free(j);
+        napi_throw_error(env, NULL, "N-API call failed: promise");
+        return NULL;
+    }
+    if (!queue_promise_job(env, b, "pie_token_turn_finish", turn_exec, lookup_done, j, &j->work)) {
+        napi_delete_reference(env, j->result);
+        free(j);
+        return NULL;
+    }
+    b->tn_head = (b->tn_head + 1) % 4; /* the library returns the slot whatever the wait says (cap = k: never PIE_E_CAPACITY) */
+    b->tn_n--;
+    return promise;
+}
+
 /* ---- the expired queue beside scans and batches (pie_expired_queue_begin / _finish / _room) ---------------------------------
  * expiredQueueBegin queues the pass on its own stream and returns; expiredQueueFinish waits for it on the libuv pool (the handle
  * is busy meanwhile) and resolves a Promise of the queue, so a purge tick never blocks the event loop or drains the batches. */
@@ -3010,6 +3106,7 @@ static napi_value init(napi_env env, napi_value exports)
         {"commTokenSetEnd", fn_comm_token_set_end},
         {"scanBatchBegin", fn_scan_batch_begin}, {"scanBatchFinish", fn_scan_batch_finish}, {"tokenLookupBegin", fn_token_lookup_begin},
         {"tokenLookupFinish", fn_token_lookup_finish}, {"tokenLookupRoom", fn_token_lookup_room},
+        {"tokenTurnBegin", fn_token_turn_begin}, {"tokenTurnFinish", fn_token_turn_finish}, {"tokenTurnRoom", fn_token_turn_room},
         {"expiredQueueBegin", fn_expired_queue_begin}, {"expiredQueueFinish", fn_expired_queue_finish}, {"expiredQueueRoom", fn_expired_queue_room},
         {"commTokenLookupBegin", fn_comm_token_lookup_begin}, {"commTokenLookupFinish", fn_comm_token_lookup_finish},
         {"commTokenLookupRoom", fn_comm_token_lookup_room}, {"commExpiredQueueBegin", fn_comm_expired_queue_begin},

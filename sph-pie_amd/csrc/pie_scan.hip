@@ -373,6 +373,20 @@ struct pie_ctx {
         } lk[kTokLookups];
         SidePass side;              // stale: a finish returned its slot without having seen `done`
         int lk_head = 0, lk_n = 0;  // the oldest unfinished lookup; how many are unfinished
+        // Turns begun beside scans and batches (pie_token_turn_begin / _finish): kTokTurns slots handed out and returned in
+        // order.  The turn runs on the CONTEXT's stream (it mutates: see turn_fence); a slot owns its pinned and device staging
+        // (turn_flight_stage_of: ops, chains and ITS zeroed status words in, the status words and the results out) and the
+        // event behind its download, the one thing its finish waits for.  A block a slot outgrew goes to side.retired.
+        struct Turn {
+            char* h = nullptr;
+            char* d = nullptr;
+            size_t bytes = 0, k = 0;
+            hipEvent_t done = nullptr;
+            bool landed = false;    // `done` was waited for (token_turns_land): the results are in h
+            bool global = false;    // begun by the shard form: rows and users are GLOBAL ids
+        } tn[kTokTurns];
+        int tn_head = 0, tn_n = 0;  // the oldest unfinished turn; how many are unfinished
+        bool tn_stale = false;      // a finish returned its slot without having seen `done`: the next begin drains the stream first
     } tokx;
     // The expired queue that runs beside scans and batches (pie_expired_queue_begin / _finish): a side pass with scratch (one
     // count and one offset per unit, pie_expq_plan.h), a queue buffer and a mapped summary of its own, all created at the first
@@ -483,6 +497,12 @@ struct pie_ctx {
     // stream, so the first batch a lane begins after the context was idle waits for what the main stream holds.
     unsigned long long idle_epoch = 1;                // bumped whenever the last batch in flight leaves
     unsigned long long lane_epoch[kLaneMax] = {};     // the idle epoch the lane's stream was last ordered behind the main stream in
+    // A turn begun with batches in flight (pie_token_turn_begin) mutates on the main stream between two fences: the main stream
+    // first waits for every lane that has a batch in flight, and `mut_event` is recorded behind the turn's kernel.  A lane's next
+    // launch waits for that event once (lane_after_mutation): the mutation epoch of its last wait against the context's.
+    hipEvent_t mut_event = nullptr;
+    unsigned long long mut_epoch = 0;                 // bumped by every turn begun in flight
+    unsigned long long lane_mut_epoch[kLaneMax] = {}; // the mutation epoch the lane's stream last waited for
     long long* d_mat_tile = nullptr;   // materialisation scratch: [kBatchMax][tiles + 1] tile sums / prefixes
     unsigned int* d_mat_qmax = nullptr; // ... [kBatchMax] largest per-user count
     int mat_tiles = 0;
@@ -834,6 +854,8 @@ int token_lookup_landed(pie_ctx* c, pie_ctx::TokenIndex::Lookup& l, const char* 
 // Every lookup begun and not finished has run: its results are in its slot's pinned staging, where its finish reads them, in the
 // ids of the table it was begun on.  Whatever replaces or frees something such a lookup reads (the columns, the token column, the
 // slots, a shard's maps) calls this first; with none begun it costs nothing.
+// The turns begun beside scans and batches (pie_token_turn_begin) land with them: a turn reads and writes what a lookup reads.
+int token_turns_land(pie_ctx* c, const char* what);
 int token_lookups_land(pie_ctx* c, const char* what)
 {
     pie_ctx::TokenIndex& t = c->tokx;
@@ -841,8 +863,35 @@ int token_lookups_land(pie_ctx* c, const char* what)
         int rc = token_lookup_landed(c, t.lk[(t.lk_head + i) % kTokLookups], what);
         if (rc) return rc;
     }
+    return token_turns_land(c, what);
+}
+
+// the one wait of a turn begun beside scans and batches: on its own event, never on the context's stream or a lane's
+int token_turn_landed(pie_ctx* c, pie_ctx::TokenIndex::Turn& u, const char* what)
+{
+    if (u.landed) return PIE_OK;
+    const WaitResult w = event_wait(c, u.done);
+    if (w.end == WaitEnd::Failed) return fail(c, PIE_E_HIP, "%s: the turn failed: %s", what, hipGetErrorString((hipError_t)w.err));
+    if (w.end != WaitEnd::Ready)
+        return fail(c, PIE_E_HIP, "%s: the turn not finished within %.0f ms (PIE_WAIT_DEADLINE_MS): kernel hung?", what, w.waited_ms);
+    u.landed = true;
     return PIE_OK;
 }
+
+// Every turn begun and not finished has run: the table holds its writes and its results are in its slot's pinned staging, where
+// its finish reads them, in the ids of the table it was begun on.
+int token_turns_land(pie_ctx* c, const char* what)
+{
+    pie_ctx::TokenIndex& t = c->tokx;
+    for (int i = 0; i < t.tn_n; ++i) {
+        int rc = token_turn_landed(c, t.tn[(t.tn_head + i) % kTokTurns], what);
+        if (rc) return rc;
+    }
+    return PIE_OK;
+}
+
+// every synchronous mutator is refused while a turn is begun and not finished (the turn's results belong to its queue position)
+bool turns_begun(const pie_ctx* c) { return c->tokx.tn_n > 0; }
 
 // The one wait of the expired queue begun beside scans and batches: on ITS summary word (and its own event, for a failure), never
 // on the context's stream or a lane's.  Past it nothing of the pass reads the table.
@@ -2519,6 +2568,7 @@ int run_row_list(pie_ctx* c, long long a, long long b, int32_t* out, size_t cap,
     if (c->cap_rows == 0) return fail(c, PIE_E_STATE, "no table loaded");
     if (c->n == 0) return PIE_OK;
     if (c->n_flight || c->b_flight) return fail(c, PIE_E_STATE, "a scan is in flight");
+    if (turns_begun(c)) return fail(c, PIE_E_STATE, "a token turn is begun and not finished (pie_token_turn_finish)");
     PIE_HIP(c, hipSetDevice(c->device));
     int rc = sync_all(c); // the workspace below is shared with the scans' tails
     if (rc) return rc;
@@ -2871,6 +2921,16 @@ int order_lane_after_main(pie_ctx* c, int lane)
     return PIE_OK;
 }
 
+// a lane above 0 whose stream has not yet waited for the last turn begun in flight (turn_fence_leave) does so before its next
+// launch: that launch reads the table the turn left
+int lane_after_mutation(pie_ctx* c, int lane)
+{
+    if (lane == 0 || c->lane_mut_epoch[lane] == c->mut_epoch) return PIE_OK;
+    PIE_HIP(c, hipStreamWaitEvent(lane_stream_of(c, lane), c->mut_event, 0));
+    c->lane_mut_epoch[lane] = c->mut_epoch;
+    return PIE_OK;
+}
+
 // spans (the lane's own three, in rotation): this batch's, and the one it zeroes for the batch after the next
 void take_spans(pie_ctx* c, BatchSlot& b)
 {
@@ -2924,6 +2984,8 @@ int batch_begin(pie_ctx* c, const pie_query* qs, int n_q, int msg_kind, int* msg
         if (rc) return rc;
     }
     rc = order_lane_after_main(c, lane);
+    if (rc) return rc;
+    rc = lane_after_mutation(c, lane);
     if (rc) return rc;
     b.fine_key = fine;
     b.hot = fine && !ord_batch && c->hix.valid;
@@ -3474,6 +3536,8 @@ int wide_begin(pie_ctx* c, const pie_query* qs, int n_q, int* msg = nullptr, int
     hipStream_t s = b.stream;
     rc = order_lane_after_main(c, lane);
     if (rc) return rc;
+    rc = lane_after_mutation(c, lane);
+    if (rc) return rc;
     b.fine_key = fine;
     b.dshift = c->bdshift;
     if (!ord_wide) take_spans(c, b);
@@ -3846,6 +3910,12 @@ int pie_ctx_destroy(pie_ctx* c)
         for (hipEvent_t e : {l.fence.order, l.fence.done})
             if (e) (void)hipEventDestroy(e);
     }
+    for (auto& u : c->tokx.tn) {
+        if (u.h) (void)hipHostFree(u.h);
+        dfree(u.d);
+        if (u.done) (void)hipEventDestroy(u.done);
+    }
+    if (c->mut_event) (void)hipEventDestroy(c->mut_event);
     side_close(c->expq.side);
     dfree(c->expq.d_scratch);
     dfree(c->expq.d_buf);
@@ -4061,6 +4131,7 @@ int pie_append_rows(pie_ctx* c, const int64_t* start, const int64_t* end, const 
     if (!c) return PIE_E_INVAL;
     if (k > 0 && (!start || !end || !user || !disc)) return fail(c, PIE_E_INVAL, "NULL column pointer");
     if (n_users < c->n_users) return fail(c, PIE_E_INVAL, "n_users may only grow (%d < %d)", n_users, c->n_users);
+    if (turns_begun(c)) return fail(c, PIE_E_STATE, "a token turn is begun and not finished (pie_token_turn_finish)");
     PIE_HIP(c, hipSetDevice(c->device));
     const long long old_n = c->n;
     if (k > 0 && old_n > 0 && old_n + (long long)k <= c->cap_rows && n_users <= c->cap_users && c->key_ok && k <= ((size_t)1 << 24)) {
@@ -4068,6 +4139,7 @@ int pie_append_rows(pie_ctx* c, const int64_t* start, const int64_t* end, const 
         // four columns, both keys and the payload record of every new row and validates the user ids, and ONE wait or none.  A
         // login burst costs tens of microseconds, not the half-dozen blocking calls of the general path below.
         if (c->n_flight || c->b_flight) return fail(c, PIE_E_STATE, "table change while a scan is in flight");
+        if (turns_begun(c)) return fail(c, PIE_E_STATE, "a token turn is begun and not finished (pie_token_turn_finish)");
         if (old_n + (long long)k >= (1LL << 31) - 1) return fail(c, PIE_E_INVAL, "row count outside [0, 2^31 - 1)");
         hot_reserve(c, (long long)k);
         const bool queued = mutation_queued(c);
@@ -4359,6 +4431,7 @@ int pie_set_end(pie_ctx* c, const int32_t* rows, const int64_t* new_end, size_t 
     if (k_given == 0) return PIE_OK;
     if (!rows || !new_end) return fail(c, PIE_E_INVAL, "NULL pointer");
     if (c->n_flight || c->b_flight) return fail(c, PIE_E_STATE, "table change while a scan is in flight");
+    if (turns_begun(c)) return fail(c, PIE_E_STATE, "a token turn is begun and not finished (pie_token_turn_finish)");
     for (size_t i = 0; i < k_given; ++i)
         if (rows[i] < 0 || rows[i] >= c->n) return fail(c, PIE_E_INVAL, "row %d outside the table", rows[i]);
     return set_end_apply(c, rows, new_end, k_given, false);
@@ -4415,6 +4488,7 @@ static int delete_users_run(pie_ctx* c, const int32_t* users, size_t k, bool to_
     queue_forget(c);
     if (c->cap_rows == 0) return fail(c, PIE_E_STATE, "no table loaded");
     if (c->n_flight || c->b_flight) return fail(c, PIE_E_STATE, "a scan is in flight");
+    if (turns_begun(c)) return fail(c, PIE_E_STATE, "a token turn is begun and not finished (pie_token_turn_finish)");
     PIE_HIP(c, hipSetDevice(c->device));
     int rc = sync_all(c); // the workspace below is shared with the scans' tails, the staging block with appends / touches
     if (rc) return rc;
@@ -4572,6 +4646,7 @@ static int retention_tz_impl(pie_ctx* c, int64_t now, int32_t months, const int6
     // the table on the device: [n, months, T[n], L[n], off[n + 1]] through the context's staging block
     const size_t words = 2 + (size_t)n * 2 + (size_t)n + 1;
     if (c->n_flight || c->b_flight) return fail(c, PIE_E_STATE, "a scan is in flight");
+    if (turns_begun(c)) return fail(c, PIE_E_STATE, "a token turn is begun and not finished (pie_token_turn_finish)");
     rc = sync_all(c); // the staging block is shared with appends / touches
     if (rc) return rc;
     rc = ensure_stage(c, words * 8);
@@ -5905,6 +5980,7 @@ static int shard_ready(pie_ctx* c, const char* what)
     if (c->n != c->shard_rows_n)
         return fail(c, PIE_E_STATE, "%s: %lld rows were added after pie_shard_table: they have no global row", what, c->n - c->shard_rows_n);
     if (c->n_flight || c->b_flight) return fail(c, PIE_E_STATE, "%s while a scan is in flight", what);
+    if (turns_begun(c)) return fail(c, PIE_E_STATE, "a token turn is begun and not finished (pie_token_turn_finish)");
     return PIE_OK;
 }
 
@@ -6783,6 +6859,7 @@ static int token_info(pie_ctx* c, pie_table_info* out)
     out->token_bytes = (uint64_t)t.cap * sizeof(TokKey) + (t.slot_row ? (uint64_t)4 << t.log2_slots : 0u) +
                        (t.status ? kTokStatusWords * sizeof(unsigned int) : 0u) + (uint64_t)t.stage_bytes;
     for (const auto& l : t.lk) out->token_bytes += (uint64_t)l.bytes;
+    for (const auto& u : t.tn) out->token_bytes += (uint64_t)u.bytes;
     out->token_builds = t.builds;
     if (t.timed) { // the last build's device time, read once it has run
         float ms = 0.f;
@@ -6799,6 +6876,7 @@ int pie_token_set(pie_ctx* c, const uint64_t* tok, size_t n)
     if (!c) return PIE_E_INVAL;
     int rc = token_ready(c, "pie_token_set", false);
     if (rc) return rc;
+    if (turns_begun(c)) return fail(c, PIE_E_STATE, "%s: a token turn is begun and not finished (pie_token_turn_finish)", "pie_token_set");
     if (c->shard_on) return fail(c, PIE_E_STATE, "pie_token_set: a sharded context carries no token column");
     if (n > 0 && !tok) return fail(c, PIE_E_INVAL, "tok is NULL");
     if ((long long)n > c->n || n > (size_t)c->n) return fail(c, PIE_E_INVAL, "%zu keys for a table of %lld rows", n, c->n);
@@ -6832,6 +6910,7 @@ int pie_token_append(pie_ctx* c, const uint64_t* tok, size_t k)
     if (!c) return PIE_E_INVAL;
     int rc = token_ready(c, "pie_token_append", true);
     if (rc) return rc;
+    if (turns_begun(c)) return fail(c, PIE_E_STATE, "%s: a token turn is begun and not finished (pie_token_turn_finish)", "pie_token_append");
     if (c->tokx.sharded) return fail(c, PIE_E_STATE, "pie_token_append: the column was given by global row (pie_shard_token_append)");
     if (k > 0 && !tok) return fail(c, PIE_E_INVAL, "tok is NULL");
     pie_ctx::TokenIndex& t = c->tokx;
@@ -7010,6 +7089,7 @@ int pie_token_set_end(pie_ctx* c, const uint64_t* tok, const int64_t* new_end, s
     if (!c) return PIE_E_INVAL;
     int rc = token_ready(c, "pie_token_set_end", true);
     if (rc) return rc;
+    if (turns_begun(c)) return fail(c, PIE_E_STATE, "%s: a token turn is begun and not finished (pie_token_turn_finish)", "pie_token_set_end");
     if (k == 0) return PIE_OK;
     if (!tok || !new_end) return fail(c, PIE_E_INVAL, "NULL pointer");
     if (k >= ((size_t)1 << 31)) return fail(c, PIE_E_INVAL, "%zu keys in one call", k);
@@ -7144,6 +7224,7 @@ int pie_token_turn(pie_ctx* c, const pie_turn_op* ops, size_t k, int32_t* row_ou
     if (!c) return PIE_E_INVAL;
     int rc = token_ready(c, "pie_token_turn", true);
     if (rc || k == 0) return rc;
+    if (turns_begun(c)) return fail(c, PIE_E_STATE, "%s: a token turn is begun and not finished (pie_token_turn_finish)", "pie_token_turn");
     if ((rc = token_turn_args(c, ops, k, "pie_token_turn")) != PIE_OK) return rc;
     if ((rc = token_turn_queue(c, ops, k, false, "pie_token_turn")) != PIE_OK) return rc;
     return token_turn_wait(c, k, "pie_token_turn", row_out, live_out, user_out, start_out, end_out);
@@ -7655,6 +7736,189 @@ int pie_shard_token_lookup_finish(pie_ctx* c, int32_t* row_global_out, uint8_t* 
                                   int64_t* end_out, size_t cap, size_t* k_out)
 {
     return token_flight_finish(c, row_global_out, live_out, user_global_out, start_out, end_out, cap, k_out, true, "pie_shard_token_lookup_finish");
+}
+
+// ---- turns beside scans and batches (pie_token_turn_begin / _finish, include/pie_scan.h).  A turn MUTATES, and
+// scans and batches read what it writes: `end`, both keys, the hot index.  Every single scan and every batch of lane 0 is queued
+// on the context's stream, so stream order already puts the turn between them.  The other lanes are fenced by events: the
+// context's stream waits for every lane that has a batch in flight (turn_fence_enter), the turn's kernel runs, an event is
+// recorded behind it, and every lane's next begin waits for that event once (lane_after_mutation).  Nothing here waits on the host.
+
+// a slot's staging for k ops: up go [ops 40 k | next 4 k | pad | status (zeroed)], back come [status | end 8 k | start 8 k |
+// row 4 k | user 4 k | live k] — one copy each way; `row` holds the GLOBAL row in the shard form
+struct TurnFlightStage {
+    size_t next, status, end, start, row, user, live, bytes;
+};
+static TurnFlightStage turn_flight_stage_of(size_t k)
+{
+    TurnFlightStage o;
+    o.next = k * 40;
+    o.status = (k * 44 + 15) / 16 * 16;
+    o.end = o.status + kTokStatusWords * sizeof(unsigned int);
+    o.start = o.end + k * 8;
+    o.row = o.start + k * 8;
+    o.user = o.row + k * 4;
+    o.live = o.user + k * 4;
+    o.bytes = (o.live + k + 15) / 16 * 16;
+    return o;
+}
+
+// What stands in front of the turn's kernel on the context's stream.  First every union tail that still waits for a launch: a
+// tail rebuilds its batch's masks from the table, so it must run before `end` changes (what pie_scan_batch_flush does; a begin
+// after it carries no tail).  Then the lanes above 0 that have a batch in flight: an event on each, and the context's stream
+// waits for it.  A lane with nothing in flight has had its last summary read by the host: nothing of it reads the table any more.
+// The side passes (lookups, the expired queue) fenced the context's stream behind themselves when they were begun (side_leave).
+static int turn_fence_enter(pie_ctx* c)
+{
+    int rc = pie_scan_batch_flush(c);
+    if (rc) return rc;
+    for (int lane = 1; lane < kLaneMax; ++lane) {
+        if (c->lane_flight[lane] == 0 || !c->lane_stream[lane]) continue;
+        if (!c->lane_event[lane][1]) PIE_HIP(c, hipEventCreateWithFlags(&c->lane_event[lane][1], hipEventDisableTiming));
+        PIE_HIP(c, hipEventRecord(c->lane_event[lane][1], c->lane_stream[lane]));
+        PIE_HIP(c, hipStreamWaitEvent(c->stream, c->lane_event[lane][1], 0));
+    }
+    return PIE_OK;
+}
+
+// ... and behind it: the event the lanes' next launches wait for, under a new mutation epoch
+static int turn_fence_leave(pie_ctx* c)
+{
+    PIE_HIP(c, hipEventRecord(c->mut_event, c->stream));
+    c->mut_epoch++;
+    return PIE_OK;
+}
+
+static int turn_flight_begin(pie_ctx* c, const pie_turn_op* ops, size_t k, bool global, const char* what)
+{
+    if (!c) return PIE_E_INVAL;
+    int rc = token_flight_ready(c, what, global);
+    if (rc) return rc;
+    pie_ctx::TokenIndex& t = c->tokx;
+    if (k > 0 && (rc = token_turn_args(c, ops, k, what)) != PIE_OK) return rc;
+    // the host learns of a row the run does not hold coming back to life (the run's stale flag) only at a wait: a batch begun
+    // between this begin and its finish could read a stale run
+    if (c->ord.valid) return fail(c, PIE_E_STATE, "%s: the table has an ordered run (pie_token_turn keeps it in step; pie_set_ordered_run(0) drops it)", what);
+    if (t.tn_n >= kTokTurns) return fail(c, PIE_E_STATE, "%s: %d turns are begun and not finished", what, t.tn_n);
+    PIE_HIP(c, hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    if (t.tn_stale) { // a finish gave up on its wait: that turn's download may still be on its way into a slot
+        PIE_HIP(c, hipStreamSynchronize(s));
+        t.tn_stale = false;
+    }
+    pie_ctx::TokenIndex::Turn& u = t.tn[(t.tn_head + t.tn_n) % kTokTurns]; // free: turns finish in the order they began
+    const TurnFlightStage o = turn_flight_stage_of(k);
+    if (o.bytes > u.bytes) {
+        // This slot's staging alone grows; the turns in flight keep theirs, and the old blocks wait for the next call that has
+        // drained the context anyway (token_drop, pie_ctx_destroy), as a lookup slot's do.  256 KiB hold 3 700 ops.
+        size_t want = u.bytes ? u.bytes : (size_t)256 << 10;
+        while (want < o.bytes) want *= 2;
+        char *nh = nullptr, *nd = nullptr;
+        PIE_HIP(c, hipHostMalloc(&nh, want, hipHostMallocDefault));
+        if (hipMalloc(&nd, want) != hipSuccess) {
+            (void)hipGetLastError();
+            (void)hipHostFree(nh);
+            return fail(c, PIE_E_NOMEM, "%s: no device memory for the staging of %zu ops", what, k);
+        }
+        if (!side_retire(t.side, u.h, u.d)) {
+            (void)hipHostFree(nh);
+            (void)hipFree(nd);
+            return fail(c, PIE_E_NOMEM, "%s: out of host memory", what);
+        }
+        u.h = nh;
+        u.d = nd;
+        u.bytes = want;
+    }
+    if (!u.done) PIE_HIP(c, hipEventCreateWithFlags(&u.done, hipEventDisableTiming));
+    if (!c->mut_event) PIE_HIP(c, hipEventCreateWithFlags(&c->mut_event, hipEventDisableTiming));
+    if (k > 0) {
+        // the plan on the host, straight into the pinned block (as token_turn_queue stages it): next[] where the device reads it,
+        // the head flags (built where the `live` results will land) into the reserved word of the staged ops
+        memcpy(u.h, ops, k * sizeof(pie_turn_op));
+        pie_turn_op* staged = reinterpret_cast<pie_turn_op*>(u.h);
+        uint8_t* head = reinterpret_cast<uint8_t*>(u.h + o.live);
+        if (!turn_plan(ops, k, reinterpret_cast<int32_t*>(u.h + o.next), head, t.turn_slots)) return fail(c, PIE_E_NOMEM, "%s: no memory for %zu ops", what, k);
+        for (size_t i = 0; i < k; ++i) staged[i].reserved = head[i];
+        memset(u.h + o.status, 0, kTokStatusWords * sizeof(unsigned int));
+        if ((rc = turn_fence_enter(c)) != PIE_OK) return rc;
+        // Host-side state the synchronous turn moves too; both are flags, and what they set off waits for an idle context
+        // (DESIGN.md 4.w): the hot index's delta bound (past it the index is given up: later batches read the key column, which
+        // the kernel keeps in step) and key_dirty (the re-fit is gated on nothing in flight and runs on this stream).
+        hot_reserve(c, (long long)k);
+        char* d = u.d;
+        PIE_HIP(c, hipMemcpyAsync(d, u.h, o.end, hipMemcpyHostToDevice, s));
+        const dim3 grid((unsigned)((k + 255) / 256)); // a thread per op
+        TurnMaps maps{};
+        if (global) maps = TurnMaps{(const int*)c->d_shard_rows, c->shard_rows_n, (const int*)c->d_shard_users, c->shard_users_n};
+        auto launch = global ? k_token_turn<true> : k_token_turn<false>;
+        hipLaunchKernelGGL(launch, grid, dim3(256), 0, s, reinterpret_cast<const TurnOp*>(d), reinterpret_cast<const int*>(d + o.next), (long long)k,
+                           (const int*)t.slot_row, t.log2_slots, (const TokKey*)t.tok, token_bound(c), c->d_end, (const long long*)c->d_start,
+                           (const int*)c->d_user, maps, c->d_key, c->key_base, c->key_shift, c->d_fkey, c->fkey_base, c->fkey_shift,
+                           OrdMirror{}, hot_mirror_of(c), reinterpret_cast<int*>(d + o.row), reinterpret_cast<unsigned char*>(d + o.live),
+                           reinterpret_cast<int*>(d + o.user), reinterpret_cast<long long*>(d + o.start), reinterpret_cast<long long*>(d + o.end),
+                           reinterpret_cast<unsigned int*>(d + o.status));
+        PIE_HIP(c, hipGetLastError());
+        c->key_dirty = true;
+        if ((rc = turn_fence_leave(c)) != PIE_OK) return rc;
+        PIE_HIP(c, hipMemcpyAsync(u.h + o.status, d + o.status, o.bytes - o.status, hipMemcpyDeviceToHost, s));
+        PIE_HIP(c, hipEventRecord(u.done, s));
+    }
+    u.k = k;
+    u.landed = k == 0;
+    u.global = global;
+    t.tn_n++;
+    return PIE_OK;
+}
+
+static int turn_flight_finish(pie_ctx* c, int32_t* row_out, uint8_t* live_out, int32_t* user_out, int64_t* start_out, int64_t* end_out,
+                              size_t cap, size_t* k_out, bool global, const char* what)
+{
+    if (!c) return PIE_E_INVAL;
+    pie_ctx::TokenIndex& t = c->tokx;
+    if (t.tn_n == 0) return fail(c, PIE_E_STATE, "%s: no turn was begun", what);
+    pie_ctx::TokenIndex::Turn& u = t.tn[t.tn_head];
+    if (u.global != global) return fail(c, PIE_E_STATE, "%s: the oldest turn was begun by the %s form", what, u.global ? "shard" : "plain");
+    const size_t k = u.k;
+    if (k_out) *k_out = k;
+    if (cap < k) return fail(c, PIE_E_CAPACITY, "%s: %zu ops, room for %zu", what, k, cap);
+    PIE_HIP(c, hipSetDevice(c->device));
+    int rc = token_turn_landed(c, u, what);
+    t.tn_head = (t.tn_head + 1) % kTokTurns; // the slot is returned whatever the wait said
+    t.tn_n--;
+    if (rc) t.tn_stale = true; // its download may still be pending: the next begin drains before it touches a slot
+    if (rc || k == 0) return rc;
+    const TurnFlightStage o = turn_flight_stage_of(k);
+    const char* h = u.h;
+    const unsigned int* st = reinterpret_cast<const unsigned int*>(h + o.status);
+    if (st[0] || st[1])
+        return fail(c, PIE_E_HIP, "%s: probe bound exhausted (a lookup ran %llu steps without meeting an empty slot)", what, 1ull << t.log2_slots);
+    if (row_out) memcpy(row_out, h + o.row, k * 4);
+    if (live_out) memcpy(live_out, h + o.live, k);
+    if (user_out) memcpy(user_out, h + o.user, k * 4);
+    if (start_out) memcpy(start_out, h + o.start, k * 8);
+    if (end_out) memcpy(end_out, h + o.end, k * 8);
+    return PIE_OK;
+}
+
+int pie_token_turn_begin(pie_ctx* c, const pie_turn_op* ops, size_t k) { return turn_flight_begin(c, ops, k, false, "pie_token_turn_begin"); }
+
+int pie_token_turn_finish(pie_ctx* c, int32_t* row_out, uint8_t* live_out, int32_t* user_out, int64_t* start_out, int64_t* end_out, size_t cap,
+                          size_t* k_out)
+{
+    return turn_flight_finish(c, row_out, live_out, user_out, start_out, end_out, cap, k_out, false, "pie_token_turn_finish");
+}
+
+int pie_token_turn_room(pie_ctx* c) { return c ? kTokTurns - c->tokx.tn_n : PIE_E_INVAL; }
+
+int pie_shard_token_turn_begin(pie_ctx* c, const pie_turn_op* ops, size_t k)
+{
+    return turn_flight_begin(c, ops, k, true, "pie_shard_token_turn_begin");
+}
+
+int pie_shard_token_turn_finish(pie_ctx* c, int32_t* row_global_out, uint8_t* live_out, int32_t* user_global_out, int64_t* start_out,
+                                int64_t* end_out, size_t cap, size_t* k_out)
+{
+    return turn_flight_finish(c, row_global_out, live_out, user_global_out, start_out, end_out, cap, k_out, true, "pie_shard_token_turn_finish");
 }
 
 // ---- the expired queue beside scans and batches (pie_expired_queue_begin / _finish, include/pie_scan.h; kernels: pie_expq.h).

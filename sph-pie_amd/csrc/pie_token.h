@@ -22,6 +22,7 @@ typedef ulonglong2 TokKey; // .x = bytes 0..7, .y = bytes 8..15 of the sha256, l
 
 constexpr int kTokStatusWords = 4; // [0] an insert exhausted its probe bound, [1] a lookup did
 constexpr int kTokLookups = 4;     // lookups begun and not finished beside scans and batches (pie_token_lookup_begin)
+constexpr int kTokTurns = 4;       // turns begun and not finished beside scans and batches (pie_token_turn_begin)
 
 // 64-bit mix of a key: the splitmix64 finaliser (the one pie_shard_of applies to a user id) over k0 ^ rotl(k1, 32)
 __host__ __device__ __forceinline__ unsigned long long token_mix(unsigned long long k0, unsigned long long k1)
@@ -217,6 +218,9 @@ __global__ __launch_bounds__(256) void k_shard_token_lookup_now(const TokKey* __
 // ascends; an entry that does not is the end of the chain).  A chain is walked by ONE lane: a turn in which every op names one
 // token costs k serial steps.
 // The uploaded array is the caller's pie_turn_op array with the `reserved` word (0 in the ABI) carrying the head flag.
+// `status` is whatever the host hands in: the context's words for pie_token_turn, the words inside the staging of its own slot for
+// a turn begun beside scans and batches (pie_token_turn_begin).  The kernel only ever raises status[1] (token_probe), so a turn
+// neither raises nor clears the report of another; the in-flight form needs no variant of the kernel.
 struct alignas(8) TurnOp {
     unsigned long long k0, k1;
     long long now, new_end;

@@ -224,7 +224,38 @@ function createFeedService(store, options){
   // tokenLookupBegin / tokenLookupFinish while it is in flight (the wait runs on the libuv pool), and the batch is finished
   // after.  Without the option the lookup is the drained tokenLookup ahead of the batch, one call per distinct clock.  Same
   // statuses and bytes either way.
+  // With {turns: true} the cookies become ONE get-and-touch list — per request getSession, then touchSession with the request's
+  // clock (server/sessionStore.js:21-45: the reference extends a session on every authenticated request) — run by
+  // tokenTurnBegin / tokenTurnFinish while the turn's batch stays in flight.  The batch was begun before the turn, so the rows
+  // of every feed are those of the table before the touches (a touch applies to a live session and keeps it live: it moves no
+  // row into or out of a feed); the `end` a body prints is the table's own when the rows are fetched, the touched one, as in
+  // the reference, which touches before it lists.  Same statuses, and the same bytes as the default path on a table that got
+  // the same touches.  The ends the touches wrote are in touchedEnds() (0n where the session was not live).
   const authInFlight = opts.authInFlight === true;
+  const turns = opts.turns === true;
+  const sessionTtlMs = opts.sessionTtlMs === undefined ? 12 * 60 * 60 * 1000 : opts.sessionTtlMs;
+  let turnsInFlight = 0;
+  let touched = new BigInt64Array(0);
+  async function authByTurn(keys, nows){
+    const n = nows.length;
+    const k2 = new BigUint64Array(4 * n), n2 = new BigInt64Array(2 * n), e2 = new BigInt64Array(2 * n), kinds = new Uint8Array(2 * n);
+    for(let i = 0; i < n; i++){
+      for(const j of [2 * i, 2 * i + 1]){ k2[2 * j] = keys[2 * i]; k2[2 * j + 1] = keys[2 * i + 1]; n2[j] = nows[i]; }
+      kinds[2 * i + 1] = 1;
+      e2[2 * i + 1] = nows[i] + BigInt(sessionTtlMs);
+    }
+    store.native.tokenTurnBegin(store.ctx, k2, n2, e2, kinds);
+    turnsInFlight++;
+    const got = await store.native.tokenTurnFinish(store.ctx);
+    const live = new Uint8Array(n), user = new Int32Array(n);
+    touched = new BigInt64Array(n);
+    for(let i = 0; i < n; i++){
+      live[i] = got.live[2 * i];
+      user[i] = got.user[2 * i];
+      touched[i] = got.live[2 * i + 1] === 1 ? got.end[2 * i + 1] : 0n;
+    }
+    return {live, user};
+  }
   const DENIED = Buffer.from(JSON.stringify({error: 'Authentication required'}));
   const {keysOfTokens} = require('./tokenKeys');
   let lookupsInFlight = 0;
@@ -258,11 +289,18 @@ function createFeedService(store, options){
     });
     const maxQ = store.BATCH_MAX || 16;
     let auth = null;
-    if(!authInFlight){ store.flush(); auth = lookupDrained(keys, nows); }
+    if(!authInFlight && !turns){ store.flush(); auth = lookupDrained(keys, nows); }
     for(let at = 0; at < groups.length; at += maxQ){
       const chunk = groups.slice(at, at + maxQ);
       const qs = chunk.map(g => ({now: g.k.now, cutoff: g.k.cutoff, disciplines: g.k.disciplines}));
-      if(authInFlight){
+      if(turns){
+        store.scanBatchBegin(qs);
+        try{
+          if(auth === null){ auth = await authByTurn(keys, nows); }
+        }finally{
+          store.scanBatchFinish();
+        }
+      }else if(authInFlight){
         store.scanBatchBegin(qs);
         try{
           if(auth === null){
@@ -323,7 +361,7 @@ function createFeedService(store, options){
     return summary;
   }
 
-  return {serveTurn, authInFlight: () => authInFlight, lookupsInFlight: () => lookupsInFlight,
+  return {serveTurn, turns: () => turns, turnsInFlight: () => turnsInFlight, touchedEnds: () => touched, authInFlight: () => authInFlight, lookupsInFlight: () => lookupsInFlight,
     purgeTick, purgeInFlight: () => purgeInFlight, ticksInFlight: () => ticksInFlight,
     scan, eventsForUser, eventsJsonForUser, eventsJsonForRequests, icsForUser, allFeeds, scansRun: () => scansRun,
     batchesRun: () => batchesRun, timing: () => Object.assign({}, timing)};

@@ -66,7 +66,7 @@ function createStore(options){
   // calls: [{op: 'get' | 'touch' | 'del', token, now?}] -> the reference's return values in order: getSession's
   // {userId, createdAt, expiresAt} or null, touchSession's {userId, expiresAt} or null, undefined for del.
   // now defaults to Date.now() at the time of this call; a falsy token is answered on the host (null / no-op, :22, :48).
-  function turn(calls){
+  function packTurn(calls){
     const results = new Array(calls.length);
     const sent = [];                               // positions of the calls that go to the device
     for(let i = 0; i < calls.length; i++){
@@ -75,9 +75,6 @@ function createStore(options){
       if(calls[i].token && nRows > 0){ sent.push(i); }
     }
     const k = sent.length;
-    if(k === 0){
-      return results;
-    }
     const clock = Date.now();
     const keys = new BigUint64Array(2 * k), nows = new BigInt64Array(k), newEnds = new BigInt64Array(k), kinds = new Uint8Array(k);
     for(let j = 0; j < k; j++){
@@ -88,16 +85,45 @@ function createStore(options){
       kinds[j] = KIND[c.op];
       newEnds[j] = c.op === 'touch' ? BigInt(now + SESSION_TTL_MS) : 0n;
     }
-    const got = native.tokenTurn(ctx, keys, nows, newEnds, kinds);
-    for(let j = 0; j < k; j++){
+    return {results, sent, keys, nows, newEnds, kinds};
+  }
+
+  function unpackTurn(p, got){
+    for(let j = 0; j < p.sent.length; j++){
       if(got.live[j] !== 1){
         continue;                                  // unknown, expired or deleted: null (undefined for del) stands
       }
       const userId = userIds[got.user[j]];
-      results[sent[j]] = kinds[j] === KIND.get ? {userId, createdAt: Number(got.start[j]), expiresAt: Number(got.end[j])}
-                                                : {userId, expiresAt: Number(got.end[j])};
+      p.results[p.sent[j]] = p.kinds[j] === KIND.get ? {userId, createdAt: Number(got.start[j]), expiresAt: Number(got.end[j])}
+                                                     : {userId, expiresAt: Number(got.end[j])};
     }
-    return results;
+    return p.results;
+  }
+
+  function turn(calls){
+    const p = packTurn(calls);
+    if(p.sent.length === 0){
+      return p.results;
+    }
+    return unpackTurn(p, native.tokenTurn(ctx, p.keys, p.nows, p.newEnds, p.kinds));
+  }
+
+  // The same list while scans and batches are in flight on this context (pie_token_turn_begin / _finish): the turn is queued
+  // behind what was begun before it and ahead of what is begun after it, and the wait runs on the libuv pool.  -> Promise of
+  // what turn(calls) returns.  With no slot free (four turns begun and not finished) it is the synchronous turn, which needs
+  // nothing in flight.
+  let turnsInFlight = 0;
+  async function turnAsync(calls){
+    const p = packTurn(calls);
+    if(p.sent.length === 0){
+      return p.results;
+    }
+    if(native.tokenTurnRoom(ctx) <= 0){
+      return unpackTurn(p, native.tokenTurn(ctx, p.keys, p.nows, p.newEnds, p.kinds));
+    }
+    native.tokenTurnBegin(ctx, p.keys, p.nows, p.newEnds, p.kinds);
+    turnsInFlight++;
+    return unpackTurn(p, await native.tokenTurnFinish(ctx));
   }
 
   const getSession = token => turn([{op: 'get', token}])[0];
@@ -134,7 +160,8 @@ function createStore(options){
   }
 
   return {
-    createSession, getSession, touchSession, deleteSession, deleteSessionsForUser, purgeExpiredSessions, turn,
+    createSession, getSession, touchSession, deleteSession, deleteSessionsForUser, purgeExpiredSessions, turn, turnAsync,
+    turnsInFlight: () => turnsInFlight,
     SESSION_TTL_MS, SESSION_COOKIE_NAME,
     tableRows: () => nRows,
     userIds: () => userIds,
@@ -160,6 +187,7 @@ module.exports = {
   deleteSessionsForUser: userId => store().deleteSessionsForUser(userId),
   purgeExpiredSessions: () => store().purgeExpiredSessions(),
   turn: calls => store().turn(calls),
+  turnAsync: calls => store().turnAsync(calls),
   SESSION_TTL_MS,
   SESSION_COOKIE_NAME,
   createStore,
