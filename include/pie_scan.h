@@ -672,6 +672,44 @@ int pie_token_turn_plan(const pie_turn_op *ops, size_t k, int32_t *next_out /* [
 int pie_token_turn(pie_ctx *ctx, const pie_turn_op *ops, size_t k, int32_t *row_out, uint8_t *live_out, int32_t *user_out,
                    int64_t *start_out, int64_t *end_out);
 
+/* ---- a turn that LOGS IN: createSession (server/sessionStore.js:12-19) joins get / touch / delete as a fourth kind, and the
+ * whole ordered list is still one upload, one kernel, one download and one wait.  Only pie_session_turn takes the kind:
+ * pie_token_turn, pie_token_turn_begin, the shard forms and the communicator's keep refusing it with PIE_E_INVAL.
+ * GET, TOUCH and DELETE follow the table above exactly.  A CREATE op carries the key `tok`, start = now, end = new_end, and
+ * user[i] / disc[i] (the two arrays are read at CREATE ops only; both may be NULL in a turn without one).
+ *     op      condition   row_out        live_out        end_out    start_out  user_out   effect
+ *     CREATE  always      the new row    new_end > now   new_end    now        user[i]    a row is appended, its key indexed
+ * The j-th CREATE of the array, counting from 0, becomes row rows + j of the table (the host computes it; no device atomic).
+ * From that op on the key's row is the new row — the largest row under a key answers — so later ops of the same key in the turn
+ * act on the new row, with e = new_end; earlier ops acted on whatever row the key had before, or on none.  A change earlier ops
+ * left in the old row's `end` is stored (pie_set_end's path) before the chain moves to the new row.  Two CREATEs of one key
+ * both get rows; the later one answers afterwards.  A CREATE with new_end <= now answers live 0 and is findable.
+ * The defining equivalence: the table, the token column and index, both keys, the payload, the hot index, later scan results and
+ * every output equal those of the calls made one by one, where a CREATE is pie_append_rows of one row followed by
+ * pie_token_append of its key and every other op is a pie_token_turn of one op.
+ * Room: when the rows, the users (n_users, which may only grow, as in pie_append_rows), the key columns, the token column or
+ * the slots (token_rows + creates > slots / 2) have no room in place, the call first makes room the way pie_append_rows and
+ * pie_token_append do — a larger table, a key build, a longer column, a rebuild into pie_token_slots_for(new covered) slots —
+ * and may wait there; lookups begun in flight land first.  PIE_E_NOMEM there changes nothing.  After that the turn is one
+ * upload, one kernel, one download and one wait bounded by PIE_WAIT_DEADLINE_MS.
+ * Ordered run: a turn with at least one CREATE drops a valid ordered run (later scans rebuild it or take the general path); a
+ * turn without one treats the run as pie_token_turn does.  A turn without a CREATE is pie_token_turn, plus the growth of the
+ * user count to n_users as pie_append_rows(k = 0) does it.  k = 0 is allowed.  Every output pointer may be NULL.
+ * PIE_E_STATE: no table; no token column; a sharded context; a scan or batch in flight; a turn begun and not finished; a CREATE
+ * while the column does not cover every row (the column is a prefix).  PIE_E_INVAL: NULL context; NULL ops with k > 0;
+ * k >= 2^31; a kind outside 0..3; reserved != 0; n_users below the context's user count; a CREATE with NULL user or disc, or
+ * with user[i] outside [0, n_users) (checked on the host before anything is staged); a row count reaching 2^31 - 1.
+ * On any error nothing is changed. */
+#define PIE_TURN_CREATE 3
+int pie_session_turn(pie_ctx *ctx, const pie_turn_op *ops, size_t k, const int32_t *user /* [k] */, const int32_t *disc /* [k] */,
+                     int32_t n_users, int32_t *row_out, uint8_t *live_out, int32_t *user_out, int64_t *start_out, int64_t *end_out);
+/* host only, no context, no GPU: pie_token_turn_plan's chains (next_out, head_out) plus the row every CREATE gets on a table of
+ * row0 rows: new_row_out[i] = row0 + j for the j-th CREATE, -1 for every other op; *n_create_out = the number of CREATEs.
+ * PIE_E_INVAL: a NULL array with k > 0; k >= 2^31; row0 < 0; a kind outside 0..3 or reserved != 0; row0 + CREATEs reaching
+ * 2^31 - 1.  Nothing is written then.  n_create_out may be NULL. */
+int pie_session_turn_plan(const pie_turn_op *ops, size_t k, int64_t row0, int32_t *next_out /* [k] */, uint8_t *head_out /* [k] */,
+                          int32_t *new_row_out /* [k] */, size_t *n_create_out);
+
 /* ---- the token column of a SHARDED context, by GLOBAL row.  Every shard is given the same call with the same arrays and keeps
  * what is its own; nothing is exchanged (the rule of pie_shard_append_rows / pie_shard_set_end).
  * Coverage: the context remembers covered_g — keys have been given for the global rows [0, covered_g), covered_g <= N_g — and

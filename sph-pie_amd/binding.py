@@ -214,7 +214,9 @@ _SIGS = [
     ("pie_token_turn_plan", C.c_int, [_P, C.c_size_t, _P, _P]),
     ("pie_token_turn", C.c_int, [_P, _P, C.c_size_t, _P, _P, _P, _P, _P]),
     ("pie_shard_token_turn", C.c_int, [_P, _P, C.c_size_t, _P, _P, _P, _P, _P]),
-    ("pie_shard_token_set", C.c_int, [_P, _P, C.c_size_t]),
+    ("pie_session_turn", C.c_int, [_P, _P, C.c_size_t, _P, _P, C.c_int32, _P, _P, _P, _P, _P]),
+    ("pie_session_turn_plan", C.c_int, [_P, C.c_size_t, C.c_int64, _P, _P, _P, C.POINTER(C.c_size_t)]),
+    ("pie_shard_token_set",C.c_int, [_P, _P, C.c_size_t]),
     ("pie_shard_token_append", C.c_int, [_P, _P, C.c_size_t]),
     ("pie_shard_token_lookup", C.c_int, [_P, _P, C.c_size_t, C.c_int64, _P, _P, _P, _P, _P]),
     ("pie_shard_token_set_end", C.c_int, [_P, _P, _P, C.c_size_t, C.c_int64, _P]),
@@ -896,6 +898,26 @@ class PieScan:
         clock -> the dict token_lookup returns, one entry per op (pie_token_turn: live = the call succeeded, end = the row's end
         after the op)."""
         return self._token_turn(self._lib.pie_token_turn, ops)
+
+    def session_turn(self, ops, user=None, disc=None, n_users=None):
+        """A turn that may log in (pie_session_turn): ops may carry kind TURN_CREATE, whose row is made of tok, start = now,
+        end = new_end, user[i] and disc[i] (one entry per op; read at creates only; both may be None in a turn without one).
+        n_users: the user count after the turn (default: unchanged) -> the dict token_turn returns."""
+        ops = turn_ops(ops)
+        k = ops.shape[0]
+        user = None if user is None else _col(user, np.int32)
+        disc = None if disc is None else _col(disc, np.int32)
+        for a in (user, disc):
+            if a is not None and a.shape != (k,):
+                raise ValueError("one user and one disc per op")
+        n_users = self.n_users if n_users is None else int(n_users)
+        out = {"row": np.empty(k, np.int32), "live": np.empty(k, np.uint8), "user": np.empty(k, np.int32),
+               "start": np.empty(k, np.int64), "end": np.empty(k, np.int64)}
+        self._check(self._lib.pie_session_turn(self._ctx, _ptr(ops), k, _ptr(user), _ptr(disc), n_users, _ptr(out["row"]), _ptr(out["live"]),
+                                               _ptr(out["user"]), _ptr(out["start"]), _ptr(out["end"])))
+        self.n += int(np.count_nonzero(ops["kind"] == TURN_CREATE))
+        self.n_users = n_users
+        return out
 
     def token_layout(self):
         """-> (covered, slots, slot_row[slots], keys[covered, 2]) of the index, for tests and tools."""
@@ -1681,6 +1703,7 @@ def token_key(token):
 
 # pie_turn_op (include/pie_scan.h): one op of a turn, 40 bytes without padding
 TURN_GET, TURN_TOUCH, TURN_DELETE = 0, 1, 2
+TURN_CREATE = 3  # pie_session_turn only
 TURN_OP = np.dtype([("tok", "<u8", (2,)), ("now", "<i8"), ("new_end", "<i8"), ("kind", "<i4"), ("reserved", "<i4")])
 assert TURN_OP.itemsize == 40
 
@@ -1710,6 +1733,19 @@ def token_turn_plan(ops):
     if rc != 0:
         raise PieError(rc, "pie_token_turn_plan: bad argument")
     return nxt, head
+
+
+def session_turn_plan(ops, row0):
+    """Host only (pie_session_turn_plan): token_turn_plan's (next, head) plus new_row int32[k] — the row every TURN_CREATE op
+    gets on a table of row0 rows (-1 for the other kinds) — and the number of creates."""
+    ops = turn_ops(ops)
+    k = ops.shape[0]
+    nxt, head, new_row = np.empty(k, np.int32), np.empty(k, np.uint8), np.empty(k, np.int32)
+    n_create = C.c_size_t(0)
+    rc = load_library().pie_session_turn_plan(_ptr(ops), k, int(row0), _ptr(nxt), _ptr(head), _ptr(new_row), C.byref(n_create))
+    if rc != 0:
+        raise PieError(rc, "pie_session_turn_plan: bad argument")
+    return nxt, head, new_row, int(n_create.value)
 
 
 def token_slots_for(covered):

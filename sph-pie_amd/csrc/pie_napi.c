@@ -105,6 +105,7 @@
     X(int, pie_token_append, (pie_ctx *, const uint64_t *, size_t))                                                 \
     X(int, pie_token_lookup, (pie_ctx *, const uint64_t *, size_t, int64_t, int32_t *, uint8_t *, int32_t *, int64_t *, int64_t *)) \
     X(int, pie_token_turn, (pie_ctx *, const pie_turn_op *, size_t, int32_t *, uint8_t *, int32_t *, int64_t *, int64_t *)) \
+    X(int, pie_session_turn, (pie_ctx *, const pie_turn_op *, size_t, const int32_t *, const int32_t *, int32_t, int32_t *, uint8_t *, int32_t *, int64_t *, int64_t *)) \
     X(int, pie_comm_token_turn, (pie_comm *, const pie_turn_op *, size_t, int32_t *, uint8_t *, int32_t *, int32_t *, int64_t *, int64_t *)) \
     X(int, pie_token_set_end, (pie_ctx *, const uint64_t *, const int64_t *, size_t, int64_t, int32_t *))                \
     X(int, pie_token_lookup_begin, (pie_ctx *, const uint64_t *, const int64_t *, size_t))                           \
@@ -2367,6 +2368,45 @@ static napi_value fn_token_turn(napi_env env, napi_callback_info info)
     return out;
 }
 
+/* sessionTurn(ctx, keys, nows, newEnds, kinds, users Int32Array, discs Int32Array, nUsers) -> tokenTurn's object; kind 3 creates
+ * a session of users[i] / discs[i] (read at creates only) with start = nows[i], end = newEnds[i] (pie_session_turn) */
+static napi_value fn_session_turn(napi_env env, napi_callback_info info)
+{
+    static const char usage[] = "sessionTurn(ctx, BigUint64Array keys, BigInt64Array nows, BigInt64Array newEnds, Uint8Array kinds, Int32Array users, Int32Array discs, nUsers)";
+    ARGS(8)
+    pie_ctx *ctx = get_ctx(env, argv[0]);
+    if (!ctx) return NULL;
+    size_t k = 0, ku = 0, kd = 0;
+    int32_t n_users = 0;
+    int32_t *users = typed(env, argv[5], napi_int32_array, &ku);
+    int32_t *discs = typed(env, argv[6], napi_int32_array, &kd);
+    if (!users || !discs || napi_get_value_int32(env, argv[7], &n_users) != napi_ok) {
+        napi_throw_type_error(env, NULL, usage);
+        return NULL;
+    }
+    pie_turn_op *ops = turn_ops(env, argv + 1, usage, &k);
+    if (!ops) return NULL;
+    napi_value out;
+    if (ku != k || kd != k || napi_create_object(env, &out) != napi_ok) {
+        free(ops);
+        napi_throw_type_error(env, NULL, usage);
+        return NULL;
+    }
+    int32_t *row = token_out(env, out, "row", napi_int32_array, 4, k);
+    uint8_t *live = token_out(env, out, "live", napi_uint8_array, 1, k);
+    int32_t *user = token_out(env, out, "user", napi_int32_array, 4, k);
+    int64_t *start = token_out(env, out, "start", napi_bigint64_array, 8, k);
+    int64_t *end = token_out(env, out, "end", napi_bigint64_array, 8, k);
+    if (!row || !live || !user || !start || !end) {
+        free(ops);
+        return NULL;
+    }
+    int rc = p_pie_session_turn(ctx, ops, k, users, discs, n_users, row, live, user, start, end);
+    free(ops);
+    if (rc) return throw_pie(env, ctx, rc);
+    return out;
+}
+
 /* ---- a batch held in flight, and token lookups beside it (pie_scan_batch_begin / _finish, pie_token_lookup_begin / _finish) -----
  * scanBatchBegin queues a batch and returns; scanBatchFinish waits for the oldest.  Between the two the turn's cookies are
  * resolved: tokenLookupBegin queues the lookup on its own stream, tokenLookupFinish waits for it on the libuv pool (the handle is
@@ -3101,7 +3141,7 @@ static napi_value init(napi_env env, napi_value exports)
         {"commAppendRows", fn_comm_append_rows}, {"commSetEnd", fn_comm_set_end}, {"commDeleteUser", fn_comm_delete_user}, {"commDeleteUsers", fn_comm_delete_users}, {"commPruneBefore", fn_comm_prune_before}, {"commRetentionPurge", fn_comm_retention_purge}, {"commCompactRows", fn_comm_compact_rows}, {"commTableSize", fn_comm_table_size},
         {"shardMaps", fn_shard_maps},
         {"tokenSet", fn_token_set}, {"tokenAppend", fn_token_append}, {"tokenLookup", fn_token_lookup}, {"tokenSetEnd", fn_token_set_end},
-        {"tokenTurn", fn_token_turn}, {"commTokenTurn", fn_comm_token_turn},
+        {"tokenTurn", fn_token_turn}, {"sessionTurn", fn_session_turn}, {"commTokenTurn", fn_comm_token_turn},
         {"commTokenSet", fn_comm_token_set}, {"commTokenAppend", fn_comm_token_append}, {"commTokenLookup", fn_comm_token_lookup},
         {"commTokenSetEnd", fn_comm_token_set_end},
         {"scanBatchBegin", fn_scan_batch_begin}, {"scanBatchFinish", fn_scan_batch_finish}, {"tokenLookupBegin", fn_token_lookup_begin},

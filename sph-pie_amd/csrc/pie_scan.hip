@@ -6829,6 +6829,45 @@ static int token_rebuild(pie_ctx* c, long long rows)
     return PIE_OK;
 }
 
+// Room for a plain column to cover `covered` rows (pie_token_append, pie_session_turn): a column as long as the table's capacity
+// (the table grew) and slots that stay at most half full — a larger table of slots is rebuilt from the rows covered NOW, the
+// caller inserts the rest.  Both free what a lookup begun earlier (pie_token_lookup_begin) reads: those land first.  May wait.
+static int token_make_room(pie_ctx* c, long long covered, const char* what)
+{
+    pie_ctx::TokenIndex& t = c->tokx;
+    hipStream_t s = c->stream;
+    const bool longer = c->cap_rows > t.cap, grow = (unsigned long long)covered > ((1ull << t.log2_slots) >> 1);
+    if (!longer && !grow) return PIE_OK;
+    int rc = token_lookups_land(c, what);
+    if (rc) return rc;
+    // the allocations first: a failure leaves what was there
+    TokKey* nt = nullptr;
+    int* ns = nullptr;
+    const unsigned log2_slots = grow ? token_log2(pie_token_slots_for((size_t)covered)) : t.log2_slots;
+    if ((longer && hipMalloc(&nt, (size_t)c->cap_rows * sizeof(TokKey)) != hipSuccess) || (grow && hipMalloc(&ns, (size_t)4 << log2_slots) != hipSuccess)) {
+        (void)hipGetLastError();
+        dfree(nt);
+        return fail(c, PIE_E_NOMEM, "%s: no device memory for %lld keys and %llu slots", what, c->cap_rows, 1ull << log2_slots);
+    }
+    hipError_t e = longer && t.covered ? hipMemcpyAsync(nt, t.tok, (size_t)t.covered * sizeof(TokKey), hipMemcpyDeviceToDevice, s) : hipSuccess;
+    if (e == hipSuccess) e = hipStreamSynchronize(s); // the copy has run; inserts queued earlier still write the table of slots that goes
+    if (e != hipSuccess) {
+        dfree(nt);
+        dfree(ns);
+        return fail(c, PIE_E_HIP, "%s: %s", what, hipGetErrorString(e));
+    }
+    if (longer) {
+        dfree(t.tok);
+        t.tok = nt;
+        t.cap = c->cap_rows;
+    }
+    if (!grow) return PIE_OK;
+    dfree(t.slot_row);
+    t.slot_row = ns;
+    t.log2_slots = log2_slots;
+    return token_rebuild(c, t.covered);
+}
+
 // A sharded column's covered_l = lower_bound(rows_map, mapped rows, covered_g): one thread on the device, read back and waited for.
 static int shard_token_covered(pie_ctx* c, long long* covered_l)
 {
@@ -6923,29 +6962,7 @@ int pie_token_append(pie_ctx* c, const uint64_t* tok, size_t k)
     const bool staged = k <= ((size_t)1 << 20);
     Staged st{};
     if (staged && (rc = stage_mutation(c, k * sizeof(TokKey), true, &st)) != PIE_OK) return rc;
-    // a longer column or a larger table of slots frees what a lookup begun earlier (pie_token_lookup_begin) reads: those land first
-    if ((c->cap_rows > t.cap || (unsigned long long)covered > ((1ull << t.log2_slots) >> 1)) && (rc = token_lookups_land(c, "pie_token_append")) != PIE_OK)
-        return rc;
-    if (c->cap_rows > t.cap) {
-        TokKey* nt = nullptr;
-        PIE_HIP(c, hipMalloc(&nt, (size_t)c->cap_rows * sizeof(TokKey)));
-        hipError_t e = t.covered ? hipMemcpyAsync(nt, t.tok, (size_t)t.covered * sizeof(TokKey), hipMemcpyDeviceToDevice, s) : hipSuccess;
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) {
-            (void)hipFree(nt);
-            return fail(c, PIE_E_HIP, "pie_token_append: %s", hipGetErrorString(e));
-        }
-        dfree(t.tok);
-        t.tok = nt;
-        t.cap = c->cap_rows;
-    }
-    const bool grow = (unsigned long long)covered > ((1ull << t.log2_slots) >> 1);
-    unsigned log2_slots = t.log2_slots;
-    int* ns = nullptr;
-    if (grow) {
-        log2_slots = token_log2(pie_token_slots_for((size_t)covered));
-        PIE_HIP(c, hipMalloc(&ns, (size_t)4 << log2_slots));
-    }
+    if ((rc = token_make_room(c, covered, "pie_token_append")) != PIE_OK) return rc;
     hipError_t e;
     if (staged) {
         memcpy(st.h, tok, k * sizeof(TokKey));
@@ -6954,22 +6971,11 @@ int pie_token_append(pie_ctx* c, const uint64_t* tok, size_t k)
         e = hipMemcpyAsync(t.tok + t.covered, tok, k * sizeof(TokKey), hipMemcpyHostToDevice, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
     }
-    if (e != hipSuccess) {
-        dfree(ns);
-        return fail(c, PIE_E_HIP, "pie_token_append: %s", hipGetErrorString(e));
-    }
-    if (staged && (rc = stage_queued(c, st)) != PIE_OK) {
-        dfree(ns);
-        return rc;
-    }
+    if (e != hipSuccess) return fail(c, PIE_E_HIP, "pie_token_append: %s", hipGetErrorString(e));
+    if (staged && (rc = stage_queued(c, st)) != PIE_OK) return rc;
     const long long row0 = t.covered;
     t.covered = covered;
-    if (!grow) return token_insert(c, row0, (long long)k);
-    PIE_HIP(c, hipStreamSynchronize(s)); // inserts queued earlier still write the table that goes
-    dfree(t.slot_row);
-    t.slot_row = ns;
-    t.log2_slots = log2_slots;
-    return token_rebuild(c, t.covered);
+    return token_insert(c, row0, (long long)k);
 }
 
 // offsets of a lookup's staging block for k keys: [keys 16 k | end 8 k | start 8 k | row 4 k | user 4 k | live k | pad | status];
@@ -7121,15 +7127,18 @@ int pie_token_set_end(pie_ctx* c, const uint64_t* tok, const int64_t* new_end, s
 // ---- a whole turn in one launch (pie_token_turn, pie_shard_token_turn; include/pie_scan.h, k_token_turn in pie_token.h)
 
 // offsets of a turn's staging block for k ops: [ops 40 k | next 4 k | pad | results as TokStage orders them: end 8 k | start 8 k |
-// row 4 k | user 4 k | live k | pad | status].  The sharded kernel answers GLOBAL rows in `row`.
+// row 4 k | user 4 k | live k | pad | status].  The sharded kernel answers GLOBAL rows in `row`.  A turn with n_create CREATE ops
+// (pie_session_turn) carries their users and disciplines behind next[]: [.. | next 4 k | cuser 4 n_create | cdisc 4 n_create | pad ..].
 struct TurnStage {
-    size_t next, end, start, row, user, live, status, bytes;
+    size_t next, cuser, cdisc, end, start, row, user, live, status, bytes;
 };
-static TurnStage turn_stage_of(size_t k)
+static TurnStage turn_stage_of(size_t k, size_t n_create = 0)
 {
     TurnStage o;
     o.next = k * 40;
-    o.end = (k * 44 + 15) / 16 * 16;
+    o.cuser = k * 44;
+    o.cdisc = o.cuser + n_create * 4;
+    o.end = (o.cdisc + n_create * 4 + 15) / 16 * 16;
     o.start = o.end + k * 8; o.row = o.end + k * 16; o.user = o.end + k * 20; o.live = o.end + k * 24;
     o.status = (o.end + k * 25 + 15) / 16 * 16;
     o.bytes = o.status + kTokStatusWords * sizeof(unsigned int);
@@ -7188,7 +7197,7 @@ static int token_turn_queue(pie_ctx* c, const pie_turn_op* ops, size_t k, bool g
 // The wait phase: the one wait of a turn, on its own event and bounded (pie_wait.h); then what set_end_apply does behind its
 // wait (a row the ordered run does not hold came back to life: the run goes), the status words, and the results.
 static int token_turn_wait(pie_ctx* c, size_t k, const char* what, int32_t* row_out, uint8_t* live_out, int32_t* user_out, int64_t* start_out,
-                           int64_t* end_out)
+                           int64_t* end_out, size_t n_create = 0)
 {
     pie_ctx::TokenIndex& t = c->tokx;
     PIE_HIP(c, hipSetDevice(c->device));
@@ -7199,7 +7208,7 @@ static int token_turn_wait(pie_ctx* c, size_t k, const char* what, int32_t* row_
         *c->ord.h_stale = 0;
         ord_invalidate(c);
     }
-    const TurnStage o = turn_stage_of(k);
+    const TurnStage o = turn_stage_of(k, n_create);
     const char* h = t.h_stage;
     int rc = token_status_check(c, reinterpret_cast<const unsigned int*>(h + o.status), what);
     if (rc) return rc;
@@ -7228,6 +7237,115 @@ int pie_token_turn(pie_ctx* c, const pie_turn_op* ops, size_t k, int32_t* row_ou
     if ((rc = token_turn_args(c, ops, k, "pie_token_turn")) != PIE_OK) return rc;
     if ((rc = token_turn_queue(c, ops, k, false, "pie_token_turn")) != PIE_OK) return rc;
     return token_turn_wait(c, k, "pie_token_turn", row_out, live_out, user_out, start_out, end_out);
+}
+
+// ---- a turn that logs in (pie_session_turn; include/pie_scan.h, k_session_turn in pie_token.h)
+
+int pie_session_turn_plan(const pie_turn_op* ops, size_t k, int64_t row0, int32_t* next_out, uint8_t* head_out, int32_t* new_row_out,
+                          size_t* n_create_out)
+{
+    if (k >= ((size_t)1 << 31) || row0 < 0 || (k && (!ops || !next_out || !head_out || !new_row_out))) return PIE_E_INVAL;
+    if (session_turn_first_bad(ops, k) < k) return PIE_E_INVAL;
+    if (row0 + (int64_t)session_turn_creates(ops, k) >= ((int64_t)1 << 31) - 1) return PIE_E_INVAL;
+    std::vector<int32_t> slots;
+    if (!turn_plan(ops, k, next_out, head_out, slots)) return PIE_E_NOMEM;
+    const size_t n_create = session_turn_rows(ops, k, row0, new_row_out);
+    if (n_create_out) *n_create_out = n_create;
+    return PIE_OK;
+}
+
+// The queue phase of a turn with n_create > 0 creates (the checks and the room are behind the caller): the plan on the host, ONE
+// upload of [ops | next | cuser | cdisc], ONE kernel, ONE download of the results and the status words, an event behind them.
+static int session_turn_queue(pie_ctx* c, const pie_turn_op* ops, size_t k, const int32_t* user, const int32_t* disc, size_t n_create,
+                              const char* what)
+{
+    pie_ctx::TokenIndex& t = c->tokx;
+    hipStream_t s = c->stream;
+    const TurnStage o = turn_stage_of(k, n_create);
+    int rc = token_stage_room(c, o.bytes);
+    if (rc) return rc;
+    if (!t.turn_done) PIE_HIP(c, hipEventCreateWithFlags(&t.turn_done, hipEventDisableTiming));
+    memcpy(t.h_stage, ops, k * sizeof(pie_turn_op));
+    pie_turn_op* staged = reinterpret_cast<pie_turn_op*>(t.h_stage);
+    uint8_t* head = reinterpret_cast<uint8_t*>(t.h_stage + o.live);
+    if (!turn_plan(ops, k, reinterpret_cast<int32_t*>(t.h_stage + o.next), head, t.turn_slots)) return fail(c, PIE_E_NOMEM, "%s: no memory for %zu ops", what, k);
+    // the reserved word of a staged op: the head flag in bit 0, above it the ordinal of a create (its row is rows + ordinal)
+    int32_t* cuser = reinterpret_cast<int32_t*>(t.h_stage + o.cuser);
+    int32_t* cdisc = reinterpret_cast<int32_t*>(t.h_stage + o.cdisc);
+    uint32_t j = 0;
+    for (size_t i = 0; i < k; ++i) {
+        uint32_t word = head[i];
+        if (ops[i].kind == PIE_TURN_CREATE) {
+            word |= j << 1;
+            cuser[j] = user[i];
+            cdisc[j] = disc[i];
+            ++j;
+        }
+        staged[i].reserved = (int32_t)word;
+    }
+    hot_reserve(c, (long long)k); // every delta record of the turn is owed to an op of its own: a touch, a delete or a create
+    ord_invalidate(c);            // the run does not take the new rows: it goes before the kernel could mirror into it
+    char* d = t.d_stage;
+    PIE_HIP(c, hipMemcpyAsync(d, t.h_stage, o.cdisc + n_create * 4, hipMemcpyHostToDevice, s));
+    const bool keys = c->key_ok; // a table too large to carry the derived columns runs without them
+    hipLaunchKernelGGL(k_session_turn, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const TurnOp*>(d),
+                       reinterpret_cast<const int*>(d + o.next), (long long)k, reinterpret_cast<const int*>(d + o.cuser),
+                       reinterpret_cast<const int*>(d + o.cdisc), c->n, t.slot_row, t.log2_slots, t.tok, t.covered, c->d_start, c->d_end, c->d_user,
+                       c->d_disc, keys ? c->d_key : nullptr, c->key_base, c->key_shift, keys ? c->d_fkey : nullptr, c->fkey_base, c->fkey_shift,
+                       keys ? c->d_pay : nullptr, ord_mirror_of(c), hot_mirror_of(c), reinterpret_cast<int*>(d + o.row),
+                       reinterpret_cast<unsigned char*>(d + o.live), reinterpret_cast<int*>(d + o.user), reinterpret_cast<long long*>(d + o.start),
+                       reinterpret_cast<long long*>(d + o.end), t.status);
+    PIE_HIP(c, hipGetLastError());
+    PIE_HIP(c, hipMemcpyAsync(t.h_stage + o.end, d + o.end, o.status - o.end, hipMemcpyDeviceToHost, s));
+    PIE_HIP(c, hipMemcpyAsync(t.h_stage + o.status, t.status, kTokStatusWords * sizeof(unsigned int), hipMemcpyDeviceToHost, s));
+    PIE_HIP(c, hipEventRecord(t.turn_done, s));
+    return PIE_OK;
+}
+
+int pie_session_turn(pie_ctx* c, const pie_turn_op* ops, size_t k, const int32_t* user, const int32_t* disc, int32_t n_users, int32_t* row_out,
+                     uint8_t* live_out, int32_t* user_out, int64_t* start_out, int64_t* end_out)
+{
+    if (!c) return PIE_E_INVAL;
+    const char* const what = "pie_session_turn";
+    int rc = token_ready(c, what, true);
+    if (rc) return rc;
+    if (c->shard_on || c->tokx.sharded) return fail(c, PIE_E_STATE, "%s: a sharded context", what);
+    if (turns_begun(c)) return fail(c, PIE_E_STATE, "%s: a token turn is begun and not finished (pie_token_turn_finish)", what);
+    if (n_users < c->n_users) return fail(c, PIE_E_INVAL, "%s: n_users may only grow (%d < %d)", what, n_users, c->n_users);
+    if (k > 0 && !ops) return fail(c, PIE_E_INVAL, "%s: ops is NULL", what);
+    if (k >= ((size_t)1 << 31)) return fail(c, PIE_E_INVAL, "%s: %zu ops in one turn", what, k);
+    const size_t bad = session_turn_first_bad(ops, k);
+    if (bad < k) return fail(c, PIE_E_INVAL, "%s: op %zu has kind %d, reserved %d", what, bad, (int)ops[bad].kind, (int)ops[bad].reserved);
+    const size_t n_create = session_turn_creates(ops, k);
+    if (n_create == 0) { // pie_token_turn, behind the growth of the user count as an append of no rows does it
+        if (n_users > c->n_users && (rc = pie_append_rows(c, nullptr, nullptr, nullptr, nullptr, 0, n_users)) != PIE_OK) return rc;
+        if (k == 0) return PIE_OK;
+        if ((rc = token_turn_queue(c, ops, k, false, what)) != PIE_OK) return rc;
+        return token_turn_wait(c, k, what, row_out, live_out, user_out, start_out, end_out);
+    }
+    pie_ctx::TokenIndex& t = c->tokx;
+    const long long old_n = c->n, creates = (long long)n_create;
+    if (!user || !disc) return fail(c, PIE_E_INVAL, "%s: a create without %s", what, user ? "disc" : "user");
+    for (size_t i = 0; i < k; ++i)
+        if (ops[i].kind == PIE_TURN_CREATE && (unsigned)user[i] >= (unsigned)n_users)
+            return fail(c, PIE_E_INVAL, "%s: op %zu carries user %d outside [0, %d)", what, i, user[i], n_users);
+    if (t.covered < old_n) return fail(c, PIE_E_STATE, "%s: the token column covers %lld of %lld rows (pie_token_append the rest first)", what, t.covered, old_n);
+    if (old_n + creates >= (1LL << 31) - 1) return fail(c, PIE_E_INVAL, "%s: row count outside [0, 2^31 - 1)", what);
+    PIE_HIP(c, hipSetDevice(c->device));
+    // Room, by the routines pie_append_rows and pie_token_append make it with; the table's size does not move here.
+    if (old_n + creates > c->cap_rows || n_users > c->cap_users || !c->key_ok) {
+        rc = append_rollback(c, old_n, ensure_capacity(c, old_n + creates, n_users, old_n > 0 ? old_n : 1));
+        if (rc == PIE_OK) rc = build_keys(c, old_n); // every row: the columns moved, or were not keyed
+        if (rc) return rc;
+    }
+    if ((rc = token_make_room(c, old_n + creates, what)) != PIE_OK) return rc;
+    if ((rc = session_turn_queue(c, ops, k, user, disc, n_create, what)) != PIE_OK) return rc;
+    // the host's picture moves as an append moves it; the rows are in the stream behind everything queued so far
+    c->n = old_n + creates;
+    t.covered = c->n;
+    rc = append_finish(c, n_users);
+    const int rc_wait = token_turn_wait(c, k, what, row_out, live_out, user_out, start_out, end_out, n_create);
+    return rc_wait ? rc_wait : rc;
 }
 
 // pie_token_layout and pie_shard_token_layout behind their checks; the covered rows are LOCAL ones (covered_l on a sharded column)

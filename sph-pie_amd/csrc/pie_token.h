@@ -227,7 +227,26 @@ struct alignas(8) TurnOp {
     int kind, head;
 };
 static_assert(sizeof(TurnOp) == 40, "TurnOp mirrors pie_turn_op");
-constexpr int kTurnGet = 0, kTurnTouch = 1, kTurnDelete = 2;
+constexpr int kTurnGet = 0, kTurnTouch = 1, kTurnDelete = 2, kTurnCreate = 3;
+
+// One get / touch / delete op against its key's row, whose `end` is `e` (the rules of the table in include/pie_scan.h): `e` moves
+// as the op says, `r` becomes -1 for a delete that wrote nothing.  -> live_out.  Shared by k_token_turn and k_session_turn.
+__device__ __forceinline__ unsigned char turn_apply(const TurnOp& op, bool found, long long& e, int& r)
+{
+    if (op.kind == kTurnTouch) {
+        if (found && e > op.now) {
+            e = op.new_end;
+            return 1;
+        }
+        return 0;
+    }
+    if (op.kind == kTurnDelete) {
+        if (found && e != INT64_MIN) e = INT64_MIN;
+        else r = -1;
+        return 0;
+    }
+    return (found && e > op.now) ? 1 : 0;
+}
 
 // the two maps of a sharded context (kShard): rows and users are answered as GLOBAL ids, as k_shard_token_lookup answers them
 struct TurnMaps {
@@ -266,16 +285,7 @@ __global__ __launch_bounds__(256) void k_token_turn(const TurnOp* __restrict__ o
     long long e = e0, j = t;
     for (long long step = 0; step < k; ++step) {
         int r = rv;
-        unsigned char live = 0;
-        if (op.kind == kTurnTouch) {
-            if (found && e > op.now) {
-                e = op.new_end;
-                live = 1;
-            }
-        } else if (op.kind == kTurnDelete) {
-            if (found && e != INT64_MIN) e = INT64_MIN;
-            else r = -1;
-        } else live = (found && e > op.now) ? 1 : 0;
+        const unsigned char live = turn_apply(op, found, e, r);
         o_row[j] = r;
         o_live[j] = live;
         o_end[j] = e;
@@ -287,6 +297,86 @@ __global__ __launch_bounds__(256) void k_token_turn(const TurnOp* __restrict__ o
         op = ops[j];
     }
     if (e != e0) touch_row(best, e, end, key, key_base, key_shift, fkey, fkey_base, fkey_shift, ord, hot);
+}
+
+// ---- a turn that logs in (pie_session_turn): k_token_turn's walk with a fourth kind, CREATE.  Unsharded tables only.
+//
+// The uploaded op's `head` word carries the head flag in bit 0 and, for a CREATE, the create's ordinal j in the bits above: the
+// j-th create of the array becomes row row0 + j (the host counted; no device atomic) and takes user / disc from the compact
+// arrays cuser[j] / cdisc[j].  The host has made room: row0 + creates <= the capacity of the columns, of tok[] and of the hot
+// index's pos[], and the slots stay at most half full with every create in.
+// A head lane probes ONCE, before anything its chain creates, and walks the chain as k_token_turn does, with the row it is on and
+// that row's `end` in registers.  At a CREATE the lane
+//   1. stores the change earlier ops left in the old row's `end` (touch_row),
+//   2. writes the new row (append_row: four columns, both keys, the payload record, the hot mirror),
+//   3. stores tok[new row] as one 16-byte store,
+//   4. claims the first empty slot from the key's home — k_token_insert's relaxed agent-scope compare-and-swap and its
+//      `slots`-step bound; exhaustion raises status[0],
+//   5. goes on with the new row's values in registers.  It does not probe again.
+// The hazard: a lane probing for ANOTHER key can meet a slot claimed in this same launch, whose tok[] entry is not written yet
+// (or not visible yet), and memory past the covered prefix can hold stale keys after a compaction.  So every probe of this kernel
+// runs with `bound` = the rows covered BEFORE the turn: token_probe steps over a slot that names a newer row without reading tok.
+// That is enough: (a) a key's pre-existing entries all lie between its home and the first slot that was empty at launch, and
+// inserts only fill empty slots, so a probe that steps over new entries still reaches every old one, and one that reads a slot as
+// still empty stops where it would have stopped before the launch; (b) all the ops of one key belong to one lane, so the rows a
+// launch creates under a key matter to that lane alone, which has them in registers.  Readers of the new entries are later
+// kernels on the stream.  No spin, no barrier, no LDS; the only atomics are the slot claim and the hot mirror's own.
+// Rows: distinct keys have distinct rows and every new row belongs to one create, so no two lanes write one row.
+__global__ __launch_bounds__(256) void k_session_turn(const TurnOp* __restrict__ ops, const int* __restrict__ next, long long k,
+                                                      const int* __restrict__ cuser, const int* __restrict__ cdisc, long long row0,
+                                                      int* slot_row, unsigned log2_slots, TokKey* tok, long long bound, long long* start,
+                                                      long long* end, int* user, int* disc, lkey_t* key, long long key_base, int key_shift,
+                                                      fkey_t* fkey, long long fkey_base, int fkey_shift, PayRec* pay, OrdMirror ord,
+                                                      HotMirror hot, int* __restrict__ o_row, unsigned char* __restrict__ o_live,
+                                                      int* __restrict__ o_user, long long* __restrict__ o_start,
+                                                      long long* __restrict__ o_end, unsigned int* __restrict__ status)
+{
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= k) return;
+    TurnOp op = ops[t];
+    if (!(op.head & 1)) return;
+    TokKey want;
+    want.x = op.k0;
+    want.y = op.k1;
+    int row = token_probe(want, slot_row, log2_slots, tok, bound, status);
+    bool found = row >= 0;
+    long long e0 = found ? end[row] : INT64_MIN, sv = found ? start[row] : 0;
+    int uv = found ? user[row] : -1;
+    long long e = e0, j = t;
+    const unsigned long long slots = 1ull << log2_slots, mask = slots - 1;
+    for (long long step = 0; step < k; ++step) {
+        int r = row;
+        unsigned char live;
+        if (op.kind == kTurnCreate) {
+            if (found && e != e0) touch_row(row, e, end, key, key_base, key_shift, fkey, fkey_base, fkey_shift, ord, hot);
+            const long long c = (long long)((unsigned)op.head >> 1);
+            row = r = (int)(row0 + c);
+            found = true;
+            sv = op.now;
+            e = e0 = op.new_end;
+            uv = cuser[c];
+            append_row(row, sv, e, uv, cdisc[c], start, end, user, disc, key, key_base, key_shift, fkey, fkey_base, fkey_shift, pay, hot);
+            tok[row] = want;
+            unsigned long long s = token_home(want.x, want.y, log2_slots), tries = 0;
+            for (; tries < slots; ++tries) {
+                int expected = -1;
+                if (__hip_atomic_compare_exchange_strong(&slot_row[s], &expected, row, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;
+                s = (s + 1) & mask;
+            }
+            if (tries == slots) status[0] = 1u;
+            live = e > op.now ? 1 : 0;
+        } else live = turn_apply(op, found, e, r);
+        o_row[j] = r;
+        o_live[j] = live;
+        o_end[j] = e;
+        o_start[j] = sv;
+        o_user[j] = uv;
+        const long long nx = next[j];
+        if (nx <= j || nx >= k) break;
+        j = nx;
+        op = ops[j];
+    }
+    if (found && e != e0) touch_row(row, e, end, key, key_base, key_shift, fkey, fkey_base, fkey_shift, ord, hot);
 }
 
 // the compaction hook: the keys of the kept covered rows, in their new places

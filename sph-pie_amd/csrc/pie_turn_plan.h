@@ -1,4 +1,4 @@
-// pie_turn_plan.h — how a turn (pie_token_turn, include/pie_scan.h) is cut into chains: plain functions, no HIP, so a host-only
+// pie_turn_plan.h — how a turn (pie_token_turn, pie_session_turn; include/pie_scan.h) is cut into chains: plain functions, no HIP, so a host-only
 // program can check them (tests/turn_plan_test.cpp).
 //
 // The ops of a turn that name one key form a CHAIN in array order; ops with different keys never interact.  next[i] = the next op
@@ -49,6 +49,34 @@ inline bool turn_plan(const pie_turn_op* ops, size_t k, int32_t* next, uint8_t* 
         tab[at] = (int32_t)i;
     }
     return true;
+}
+
+// ---- a turn that logs in (pie_session_turn): kind PIE_TURN_CREATE joins the three above.  The chains are the same chains (a
+// create is one more op of its key's chain); what the plan adds is the row every create gets, with no device atomic: the j-th
+// create of the array, counting from 0, becomes row row0 + j.
+
+// kind in {GET, TOUCH, DELETE, CREATE} and reserved == 0 for every op -> the index of the first op that fails, or k
+inline size_t session_turn_first_bad(const pie_turn_op* ops, size_t k)
+{
+    for (size_t i = 0; i < k; ++i)
+        if (ops[i].kind < PIE_TURN_GET || ops[i].kind > PIE_TURN_CREATE || ops[i].reserved != 0) return i;
+    return k;
+}
+
+inline size_t session_turn_creates(const pie_turn_op* ops, size_t k)
+{
+    size_t n = 0;
+    for (size_t i = 0; i < k; ++i) n += ops[i].kind == PIE_TURN_CREATE ? 1 : 0;
+    return n;
+}
+
+// new_row[i] = row0 + (creates before op i) for a create, -1 otherwise -> the number of creates.  The caller has checked that
+// row0 + the creates stays below 2^31 - 1.
+inline size_t session_turn_rows(const pie_turn_op* ops, size_t k, int64_t row0, int32_t* new_row)
+{
+    size_t j = 0;
+    for (size_t i = 0; i < k; ++i) new_row[i] = ops[i].kind == PIE_TURN_CREATE ? (int32_t)(row0 + (int64_t)j++) : -1;
+    return j;
 }
 
 } // namespace pie

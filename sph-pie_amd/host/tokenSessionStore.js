@@ -4,11 +4,13 @@
 // on a miss, null for "no session") that keeps NO per-session state on the host: no token map, no row mirror.
 //
 // The sessions are the rows of the device table; the token -> row map is the device's token column and its index (pie_token_*,
-// include/pie_scan.h).  createSession appends one row and its key (appendRows + tokenAppend, queued, nothing waited for);
-// everything by token is a TURN: an ordered list of get / touch / del calls, each with its own clock, answered and applied by
-// the device in one upload, one kernel, one download and one wait (tokenTurn -> pie_token_turn), with the results the
-// reference gives when the calls are made one after another (:21-53).  turn(calls) is that list as the caller's event-loop turn
-// collected it; getSession, touchSession and deleteSession are turns of one.
+// include/pie_scan.h).  Everything is a TURN: an ordered list of create / get / touch / del calls, each with its own clock,
+// answered and applied by the device in one upload, one kernel, one download and one wait, with the results the reference gives
+// when the calls are made one after another (:12-53).  A turn with a create in it goes through sessionTurn (pie_session_turn:
+// the new rows, their keys and the index entries are written by the turn's own kernel), one without through tokenTurn
+// (pie_token_turn).  turn(calls) is that list as the caller's event-loop turn collected it; createSession, getSession,
+// touchSession and deleteSession are turns of one.  Only the first session of an empty store is made another way: the table and
+// the column come with it (loadColumns + tokenSet).
 // What the host keeps: the user-id strings (dense int32 <-> userId, as host/sessionStore.js keeps them) and a row count.
 //
 // A session found expired writes nothing (the reference drops it from its Map, :30-33); the row stays findable and answers
@@ -22,7 +24,7 @@ const {keyOfToken} = require('./tokenKeys');
 const SESSION_TTL_MS = 12 * 60 * 60 * 1000;
 const SESSION_COOKIE_NAME = 'mt_session';
 const END_NONE = -(2n ** 63n);          // PIE_END_NONE: tombstone, never live
-const KIND = {get: 0, touch: 1, del: 2};   // PIE_TURN_GET / _TOUCH / _DELETE
+const KIND = {get: 0, touch: 1, del: 2, create: 3};   // PIE_TURN_GET / _TOUCH / _DELETE / _CREATE
 
 function createStore(options){
   const opts = options || {};
@@ -43,55 +45,67 @@ function createStore(options){
     return u;
   }
 
-  function createSession(userId, disciplineId){
-    const token = crypto.randomBytes(48).toString('hex');
-    const now = Date.now();
+  const discOf = disciplineId => disciplineId === undefined
+    ? (disciplineConfig.DEFAULT_DISCIPLINE ? disciplineConfig.disciplineIndex(disciplineConfig.DEFAULT_DISCIPLINE.id) : 0)
+    : disciplineConfig.disciplineIndex(disciplineId);
+
+  // the first session of an empty store: the table and the column come with it
+  function firstSession(call, clock){
+    if(!call.userId){ throw new TypeError('turn: a create carries a userId'); }
+    const token = call.token || crypto.randomBytes(48).toString('hex');
+    const now = call.now === undefined ? clock : call.now;
     const expiresAt = now + SESSION_TTL_MS;
-    const disc = disciplineId === undefined
-      ? (disciplineConfig.DEFAULT_DISCIPLINE ? disciplineConfig.disciplineIndex(disciplineConfig.DEFAULT_DISCIPLINE.id) : 0)
-      : disciplineConfig.disciplineIndex(disciplineId);
-    const s = BigInt64Array.of(BigInt(now)), e = BigInt64Array.of(BigInt(expiresAt));
-    const u = Int32Array.of(denseUser(userId)), d = Int32Array.of(disc);
-    if(nRows === 0){                               // the first session: the table and the column come with it
-      native.loadColumns(ctx, s, e, u, d, userIds.length);
-      native.tokenSet(ctx, keyOfToken(token));
-    }else{
-      native.appendRows(ctx, s, e, u, d, userIds.length);
-      native.tokenAppend(ctx, keyOfToken(token));
-    }
-    nRows++;
+    const u = Int32Array.of(denseUser(call.userId)), d = Int32Array.of(discOf(call.disciplineId));
+    native.loadColumns(ctx, BigInt64Array.of(BigInt(now)), BigInt64Array.of(BigInt(expiresAt)), u, d, userIds.length);
+    native.tokenSet(ctx, keyOfToken(token));
+    nRows = 1;
     return {token, expiresAt};
   }
 
-  // calls: [{op: 'get' | 'touch' | 'del', token, now?}] -> the reference's return values in order: getSession's
-  // {userId, createdAt, expiresAt} or null, touchSession's {userId, expiresAt} or null, undefined for del.
-  // now defaults to Date.now() at the time of this call; a falsy token is answered on the host (null / no-op, :22, :48).
+  const createSession = (userId, disciplineId) => turn([{op: 'create', userId, disciplineId}])[0];
+
+  // calls: [{op: 'get' | 'touch' | 'del', token, now?} | {op: 'create', userId, disciplineId?, now?, token?}] -> the reference's
+  // return values in order: createSession's {token, expiresAt}, getSession's {userId, createdAt, expiresAt} or null,
+  // touchSession's {userId, expiresAt} or null, undefined for del.
+  // now defaults to Date.now() at the time of this call; a falsy token is answered on the host (null / no-op, :22, :48).  A
+  // create's token defaults to 48 random bytes in hex (:13); the field exists so that a test can replay a recorded trace.
   function packTurn(calls){
     const results = new Array(calls.length);
     const sent = [];                               // positions of the calls that go to the device
+    let creates = 0;
     for(let i = 0; i < calls.length; i++){
-      if(KIND[calls[i].op] === undefined){ throw new TypeError('turn: op is get, touch or del'); }
+      if(KIND[calls[i].op] === undefined){ throw new TypeError('turn: op is create, get, touch or del'); }
+      if(calls[i].op === 'create' && !calls[i].userId){ throw new TypeError('turn: a create carries a userId'); }
       results[i] = calls[i].op === 'del' ? undefined : null;
-      if(calls[i].token && nRows > 0){ sent.push(i); }
+      if(calls[i].op === 'create'){ creates++; sent.push(i); }
+      else if(calls[i].token && nRows > 0){ sent.push(i); }
     }
     const k = sent.length;
     const clock = Date.now();
     const keys = new BigUint64Array(2 * k), nows = new BigInt64Array(k), newEnds = new BigInt64Array(k), kinds = new Uint8Array(k);
+    const users = creates ? new Int32Array(k) : null, discs = creates ? new Int32Array(k) : null;
     for(let j = 0; j < k; j++){
       const c = calls[sent[j]];
       const now = c.now === undefined ? clock : c.now;
-      keys.set(keyOfToken(c.token), 2 * j);
+      let token = c.token;
+      if(c.op === 'create'){
+        token = token || crypto.randomBytes(48).toString('hex');
+        users[j] = denseUser(c.userId);
+        discs[j] = discOf(c.disciplineId);
+        results[sent[j]] = {token, expiresAt: now + SESSION_TTL_MS};
+      }
+      keys.set(keyOfToken(token), 2 * j);
       nows[j] = BigInt(now);
       kinds[j] = KIND[c.op];
-      newEnds[j] = c.op === 'touch' ? BigInt(now + SESSION_TTL_MS) : 0n;
+      newEnds[j] = c.op === 'touch' || c.op === 'create' ? BigInt(now + SESSION_TTL_MS) : 0n;
     }
-    return {results, sent, keys, nows, newEnds, kinds};
+    return {results, sent, keys, nows, newEnds, kinds, users, discs, creates};
   }
 
   function unpackTurn(p, got){
     for(let j = 0; j < p.sent.length; j++){
-      if(got.live[j] !== 1){
-        continue;                                  // unknown, expired or deleted: null (undefined for del) stands
+      if(got.live[j] !== 1 || p.kinds[j] === KIND.create){
+        continue;                                  // unknown, expired or deleted: null (undefined for del) stands; a create has its answer
       }
       const userId = userIds[got.user[j]];
       p.results[p.sent[j]] = p.kinds[j] === KIND.get ? {userId, createdAt: Number(got.start[j]), expiresAt: Number(got.end[j])}
@@ -101,19 +115,36 @@ function createStore(options){
   }
 
   function turn(calls){
+    if(nRows === 0){                               // nothing to find yet: everything ahead of the first create answers on the host
+      const first = calls.findIndex(c => c.op === 'create');
+      if(first >= 0){
+        const ahead = packTurn(calls.slice(0, first)).results;
+        const made = firstSession(calls[first], Date.now());
+        return ahead.concat([made], turn(calls.slice(first + 1)));
+      }
+    }
     const p = packTurn(calls);
     if(p.sent.length === 0){
       return p.results;
     }
-    return unpackTurn(p, native.tokenTurn(ctx, p.keys, p.nows, p.newEnds, p.kinds));
+    if(p.creates === 0){
+      return unpackTurn(p, native.tokenTurn(ctx, p.keys, p.nows, p.newEnds, p.kinds));
+    }
+    const got = native.sessionTurn(ctx, p.keys, p.nows, p.newEnds, p.kinds, p.users, p.discs, userIds.length);
+    nRows += p.creates;
+    return unpackTurn(p, got);
   }
 
   // The same list while scans and batches are in flight on this context (pie_token_turn_begin / _finish): the turn is queued
   // behind what was begun before it and ahead of what is begun after it, and the wait runs on the libuv pool.  -> Promise of
   // what turn(calls) returns.  With no slot free (four turns begun and not finished) it is the synchronous turn, which needs
-  // nothing in flight.
+  // nothing in flight.  A list with a create in it is the synchronous turn too: logins while batches are in flight are not
+  // built yet (pie_token_turn_begin takes no create op).
   let turnsInFlight = 0;
   async function turnAsync(calls){
+    if(calls.some(c => c.op === 'create')){
+      return turn(calls);
+    }
     const p = packTurn(calls);
     if(p.sent.length === 0){
       return p.results;
