@@ -360,30 +360,32 @@ struct pie_ctx {
         bool hold = false;
         double build_ms = 0;
         unsigned long long builds = 0;
-        // Lookups that run beside scans and batches (pie_token_lookup_begin / _finish): one side pass and kTokLookups slots
-        // handed out and returned in order.  A slot owns its pinned and device staging (token_flight_stage_of: keys and clocks
-        // in, results and ITS status words out) and its fence: `done` sits behind the results' copy.
-        struct Lookup {
+        // What a lookup or a turn begun beside scans and batches holds until its finish: its own pinned and device staging
+        // (lookup_flight_stage_of / turn_flight_stage_of: inputs and ITS zeroed status words in, the status words and the
+        // results out), which only ever grows (slot_stage_room).
+        struct FlightSlot {
             char* h = nullptr;
             char* d = nullptr;
             size_t bytes = 0, k = 0;
-            SideFence fence;
-            bool landed = false;    // `done` was waited for (token_lookups_land): the results are in h
+            bool landed = false;    // its `done` event was waited for (flight_slot_landed): the results are in h
             bool global = false;    // begun by the shard form: rows and users are GLOBAL ids
+        };
+        // Lookups that run beside scans and batches (pie_token_lookup_begin / _finish): one side pass and kTokLookups slots
+        // handed out and returned in order.  A slot owns its fence: `done` sits behind the results' copy.
+        struct Lookup : FlightSlot {
+            SideFence fence;
+            hipEvent_t done_event() const { return fence.done; }
+            static constexpr const char *noun = "lookup", *unit = "keys", *subject = "token lookup";
         } lk[kTokLookups];
         SidePass side;              // stale: a finish returned its slot without having seen `done`
         int lk_head = 0, lk_n = 0;  // the oldest unfinished lookup; how many are unfinished
         // Turns begun beside scans and batches (pie_token_turn_begin / _finish): kTokTurns slots handed out and returned in
-        // order.  The turn runs on the CONTEXT's stream (it mutates: see turn_fence); a slot owns its pinned and device staging
-        // (turn_flight_stage_of: ops, chains and ITS zeroed status words in, the status words and the results out) and the
-        // event behind its download, the one thing its finish waits for.  A block a slot outgrew goes to side.retired.
-        struct Turn {
-            char* h = nullptr;
-            char* d = nullptr;
-            size_t bytes = 0, k = 0;
+        // order.  The turn runs on the CONTEXT's stream (it mutates: see turn_fence); a slot owns the event behind its
+        // download, the one thing its finish waits for.  A block a slot outgrew goes to side.retired.
+        struct Turn : FlightSlot {
             hipEvent_t done = nullptr;
-            bool landed = false;    // `done` was waited for (token_turns_land): the results are in h
-            bool global = false;    // begun by the shard form: rows and users are GLOBAL ids
+            hipEvent_t done_event() const { return done; }
+            static constexpr const char *noun = "turn", *unit = "ops", *subject = "the turn";
         } tn[kTokTurns];
         int tn_head = 0, tn_n = 0;  // the oldest unfinished turn; how many are unfinished
         bool tn_stale = false;      // a finish returned its slot without having seen `done`: the next begin drains the stream first
@@ -839,54 +841,153 @@ void side_close(SidePass& sp)
     if (sp.stream) (void)hipStreamDestroy(sp.stream); // pie_ctx_destroy, ahead of freeing what the pass owns
 }
 
-// the one wait of a lookup begun beside scans and batches: on its own event, never on the context's stream or a lane's
-int token_lookup_landed(pie_ctx* c, pie_ctx::TokenIndex::Lookup& l, const char* what)
+// the one wait of a lookup or a turn begun beside scans and batches: on its own event, never on the context's stream or a lane's
+template <class Slot>
+int flight_slot_landed(pie_ctx* c, Slot& sl, const char* what)
 {
-    if (l.landed) return PIE_OK;
-    const WaitResult w = event_wait(c, l.fence.done);
-    if (w.end == WaitEnd::Failed) return fail(c, PIE_E_HIP, "%s: token lookup failed: %s", what, hipGetErrorString((hipError_t)w.err));
+    if (sl.landed) return PIE_OK;
+    const WaitResult w = event_wait(c, sl.done_event());
+    if (w.end == WaitEnd::Failed) return fail(c, PIE_E_HIP, "%s: %s failed: %s", what, Slot::subject, hipGetErrorString((hipError_t)w.err));
     if (w.end != WaitEnd::Ready)
-        return fail(c, PIE_E_HIP, "%s: token lookup not finished within %.0f ms (PIE_WAIT_DEADLINE_MS): kernel hung?", what, w.waited_ms);
-    l.landed = true;
+        return fail(c, PIE_E_HIP, "%s: %s not finished within %.0f ms (PIE_WAIT_DEADLINE_MS): kernel hung?", what, Slot::subject, w.waited_ms);
+    sl.landed = true;
     return PIE_OK;
 }
 
 // Every lookup begun and not finished has run: its results are in its slot's pinned staging, where its finish reads them, in the
 // ids of the table it was begun on.  Whatever replaces or frees something such a lookup reads (the columns, the token column, the
 // slots, a shard's maps) calls this first; with none begun it costs nothing.
-// The turns begun beside scans and batches (pie_token_turn_begin) land with them: a turn reads and writes what a lookup reads.
-int token_turns_land(pie_ctx* c, const char* what);
+// The turns begun beside scans and batches (pie_token_turn_begin) land with them: a turn reads and writes what a lookup reads;
+// past this the table holds their writes.
 int token_lookups_land(pie_ctx* c, const char* what)
 {
     pie_ctx::TokenIndex& t = c->tokx;
     for (int i = 0; i < t.lk_n; ++i) {
-        int rc = token_lookup_landed(c, t.lk[(t.lk_head + i) % kTokLookups], what);
+        int rc = flight_slot_landed(c, t.lk[(t.lk_head + i) % kTokLookups], what);
         if (rc) return rc;
     }
-    return token_turns_land(c, what);
-}
-
-// the one wait of a turn begun beside scans and batches: on its own event, never on the context's stream or a lane's
-int token_turn_landed(pie_ctx* c, pie_ctx::TokenIndex::Turn& u, const char* what)
-{
-    if (u.landed) return PIE_OK;
-    const WaitResult w = event_wait(c, u.done);
-    if (w.end == WaitEnd::Failed) return fail(c, PIE_E_HIP, "%s: the turn failed: %s", what, hipGetErrorString((hipError_t)w.err));
-    if (w.end != WaitEnd::Ready)
-        return fail(c, PIE_E_HIP, "%s: the turn not finished within %.0f ms (PIE_WAIT_DEADLINE_MS): kernel hung?", what, w.waited_ms);
-    u.landed = true;
+    for (int i = 0; i < t.tn_n; ++i) {
+        int rc = flight_slot_landed(c, t.tn[(t.tn_head + i) % kTokTurns], what);
+        if (rc) return rc;
+    }
     return PIE_OK;
 }
 
-// Every turn begun and not finished has run: the table holds its writes and its results are in its slot's pinned staging, where
-// its finish reads them, in the ids of the table it was begun on.
-int token_turns_land(pie_ctx* c, const char* what)
+// ---- the staging layouts of the token calls (pie_token_*, further down).  Every form brings its results back in one order, [end 8 k | start 8 k | row 4 k | user 4 k | live k]
+// from some base; `row` holds the GLOBAL row wherever a shard form has only one row to give.
+struct TokResults {
+    size_t end, start, row, user, live, past; // past: the first byte behind `live`
+    explicit TokResults(size_t base = 0, size_t k = 0)
+        : end(base), start(base + k * 8), row(base + k * 16), user(base + k * 20), live(base + k * 24), past(base + k * 25) {}
+};
+
+// what the caller asked for, out of the pinned block h (any pointer may be NULL)
+void token_results_out(const char* h, const TokResults& r, size_t k, int32_t* row_out, uint8_t* live_out, int32_t* user_out,
+                              int64_t* start_out, int64_t* end_out)
 {
-    pie_ctx::TokenIndex& t = c->tokx;
-    for (int i = 0; i < t.tn_n; ++i) {
-        int rc = token_turn_landed(c, t.tn[(t.tn_head + i) % kTokTurns], what);
-        if (rc) return rc;
-    }
+    if (row_out) memcpy(row_out, h + r.row, k * 4);
+    if (live_out) memcpy(live_out, h + r.live, k);
+    if (user_out) memcpy(user_out, h + r.user, k * 4);
+    if (start_out) memcpy(start_out, h + r.start, k * 8);
+    if (end_out) memcpy(end_out, h + r.end, k * 8);
+}
+
+// A staging block: the keys (16 k) or the ops (40 k) at 0, the form's other inputs, the results, the status words; [0, up) goes
+// up.  The synchronous forms (tokx.h_stage) keep the status words last and fill them from the context's (token_stage_download).
+// The in-flight forms (a slot's block) send their own up, zeroed, and keep them right ahead of the results: one copy of
+// [status, bytes) brings both back.
+struct TokStage {
+    size_t now = 0;                        // in-flight lookup: a clock per key
+    size_t next = 0, cuser = 0, cdisc = 0; // turn: the chains; the users and disciplines of its creates
+    size_t grow = 0;                       // synchronous shard lookup: the GLOBAL rows, beside the local ones in res.row
+    size_t up = 0;
+    TokResults res;
+    size_t status = 0, bytes = 0;
+};
+constexpr size_t kTokStatusBytes = kTokStatusWords * sizeof(unsigned int);
+size_t pad16(size_t x) { return (x + 15) / 16 * 16; }
+
+// a lookup: [keys 16 k | results | pad | status]; the sharded lookup adds the GLOBAL rows (4 k) between live and the status words
+TokStage lookup_stage_of(size_t k, bool global = false)
+{
+    TokStage o;
+    o.up = k * 16;
+    o.res = TokResults(o.up, k);
+    o.grow = (o.res.past + 3) / 4 * 4;
+    o.status = pad16(global ? o.grow + k * 4 : o.res.past);
+    o.bytes = o.status + kTokStatusBytes;
+    return o;
+}
+
+// a turn: [ops 40 k | next 4 k | cuser 4 n_create | cdisc 4 n_create | pad | results | pad | status]; only a turn that logs in
+// (pie_session_turn) has creates
+TokStage turn_stage_of(size_t k, size_t n_create = 0)
+{
+    TokStage o;
+    o.next = k * 40;
+    o.cuser = k * 44;
+    o.cdisc = o.cuser + n_create * 4;
+    o.up = o.cdisc + n_create * 4;
+    o.res = TokResults(pad16(o.up), k);
+    o.status = pad16(o.res.past);
+    o.bytes = o.status + kTokStatusBytes;
+    return o;
+}
+
+TokStage flight_stage_of(size_t status, size_t k)
+{
+    TokStage o;
+    o.status = status;
+    o.res = TokResults(status + kTokStatusBytes, k);
+    o.up = o.res.end;
+    o.bytes = pad16(o.res.past);
+    return o;
+}
+
+// a lookup's slot: [keys 16 k | now 8 k | status | results]
+TokStage lookup_flight_stage_of(size_t k)
+{
+    TokStage o = flight_stage_of(k * 24, k);
+    o.now = k * 16;
+    return o;
+}
+
+// a turn's slot: [ops 40 k | next 4 k | pad | status | results]
+TokStage turn_flight_stage_of(size_t k)
+{
+    TokStage o = flight_stage_of(pad16(k * 44), k);
+    o.next = k * 40;
+    return o;
+}
+
+template <class T>
+T* stage_at(char* block, size_t offset) { return reinterpret_cast<T*>(block + offset); }
+
+// The finish of the oldest lookup or turn of a ring of slots: the form it was begun by, the caller's room, the one wait, then the
+// slot's own status words and the results.  The slot is returned whatever the wait said; if it failed, the slot's download may
+// still be pending, and `stale` makes the next begin drain the stream before it touches a slot.
+template <class Slot, int N>
+int flight_finish(pie_ctx* c, Slot (&ring)[N], int& head, int& n, bool& stale, TokStage (*stage_of)(size_t), int32_t* row_out,
+                         uint8_t* live_out, int32_t* user_out, int64_t* start_out, int64_t* end_out, size_t cap, size_t* k_out, bool global,
+                         const char* what)
+{
+    if (n == 0) return fail(c, PIE_E_STATE, "%s: no %s was begun", what, Slot::noun);
+    Slot& sl = ring[head];
+    if (sl.global != global) return fail(c, PIE_E_STATE, "%s: the oldest %s was begun by the %s form", what, Slot::noun, sl.global ? "shard" : "plain");
+    const size_t k = sl.k;
+    if (k_out) *k_out = k;
+    if (cap < k) return fail(c, PIE_E_CAPACITY, "%s: %zu %s, room for %zu", what, k, Slot::unit, cap);
+    PIE_HIP(c, hipSetDevice(c->device));
+    int rc = flight_slot_landed(c, sl, what);
+    head = (head + 1) % N;
+    n--;
+    if (rc) stale = true;
+    if (rc || k == 0) return rc;
+    const TokStage o = stage_of(k);
+    const unsigned int* st = stage_at<const unsigned int>(sl.h, o.status);
+    if (st[0] || st[1])
+        return fail(c, PIE_E_HIP, "%s: probe bound exhausted (a lookup ran %llu steps without meeting an empty slot)", what, 1ull << c->tokx.log2_slots);
+    token_results_out(sl.h, o.res, k, row_out, live_out, user_out, start_out, end_out);
     return PIE_OK;
 }
 
@@ -5973,12 +6074,20 @@ int pie_shard_maps(pie_ctx* c, int32_t* rows_global_out, int32_t* users_global_o
 // local row, its user map is the ascending list of all global ids that hash to the rank (new ids are larger than all earlier
 // ones, so both maps only ever grow at their ends and no local id moves).
 
-static int shard_ready(pie_ctx* c, const char* what)
+// the table a call by GLOBAL id needs, in flight or not: both maps, the row map covering every local row
+static int shard_table_ready(pie_ctx* c, const char* what)
 {
     if (!c->shard_on || !c->d_shard_rows || !c->d_shard_users)
         return fail(c, PIE_E_STATE, "%s: the context holds no sharded table (pie_shard_table)", what);
     if (c->n != c->shard_rows_n)
         return fail(c, PIE_E_STATE, "%s: %lld rows were added after pie_shard_table: they have no global row", what, c->n - c->shard_rows_n);
+    return PIE_OK;
+}
+
+static int shard_ready(pie_ctx* c, const char* what)
+{
+    int rc = shard_table_ready(c, what);
+    if (rc) return rc;
     if (c->n_flight || c->b_flight) return fail(c, PIE_E_STATE, "%s while a scan is in flight", what);
     if (turns_begun(c)) return fail(c, PIE_E_STATE, "a token turn is begun and not finished (pie_token_turn_finish)");
     return PIE_OK;
@@ -6768,11 +6877,11 @@ static unsigned token_log2(size_t slots)
     return b;
 }
 
-// the checks every pie_token_* call that takes a context begins with
-static int token_ready(pie_ctx* c, const char* what, bool need_column)
+// the checks every pie_token_* call that takes a context begins with; idle = false: the call runs beside scans and batches
+static int token_ready(pie_ctx* c, const char* what, bool need_column, bool idle = true)
 {
     if (c->cap_rows == 0) return fail(c, PIE_E_STATE, "%s: no table loaded", what);
-    if (c->n_flight || c->b_flight) return fail(c, PIE_E_STATE, "%s while a scan or batch is in flight", what);
+    if (idle && (c->n_flight || c->b_flight)) return fail(c, PIE_E_STATE, "%s while a scan or batch is in flight", what);
     if (need_column && !c->tokx.tok) return fail(c, PIE_E_STATE, "%s: the table has no token column (pie_token_set gives it one)", what);
     return PIE_OK;
 }
@@ -6978,21 +7087,6 @@ int pie_token_append(pie_ctx* c, const uint64_t* tok, size_t k)
     return token_insert(c, row0, (long long)k);
 }
 
-// offsets of a lookup's staging block for k keys: [keys 16 k | end 8 k | start 8 k | row 4 k | user 4 k | live k | pad | status];
-// the sharded lookup adds the GLOBAL rows (4 k) between live and the status words
-struct TokStage {
-    size_t end, start, row, user, live, grow, status, bytes;
-};
-static TokStage token_stage_of(size_t k, bool global = false)
-{
-    TokStage o;
-    o.end = k * 16; o.start = k * 24; o.row = k * 32; o.user = k * 36; o.live = k * 40;
-    o.grow = (k * 41 + 3) / 4 * 4;
-    o.status = ((global ? o.grow + k * 4 : k * 41) + 15) / 16 * 16;
-    o.bytes = o.status + kTokStatusWords * sizeof(unsigned int);
-    return o;
-}
-
 // rows the column can hold keys for: what keeps a probe's 16-byte load inside it
 static long long token_bound(const pie_ctx* c)
 {
@@ -7019,38 +7113,45 @@ static int token_stage_room(pie_ctx* c, size_t bytes)
     return PIE_OK;
 }
 
+// the results and the context's status words come back into tokx.h_stage: queued, not waited for
+static int token_stage_download(pie_ctx* c, const TokStage& o)
+{
+    pie_ctx::TokenIndex& t = c->tokx;
+    PIE_HIP(c, hipMemcpyAsync(t.h_stage + o.res.end, t.d_stage + o.res.end, o.status - o.res.end, hipMemcpyDeviceToHost, c->stream));
+    PIE_HIP(c, hipMemcpyAsync(t.h_stage + o.status, t.status, kTokStatusBytes, hipMemcpyDeviceToHost, c->stream));
+    return PIE_OK;
+}
+
 // The queue phase of a lookup: the keys go up, one launch for k keys, the results and the status words come back into
-// tokx.h_stage (token_stage_of) — all queued on the stream, nothing waited for.  global: the sharded kernel, which also answers
+// tokx.h_stage (lookup_stage_of) — all queued on the stream, nothing waited for.  global: the sharded kernel, which also answers
 // the global row and translates the user.
 static int token_lookup_queue(pie_ctx* c, const uint64_t* tok, size_t k, long long now, bool want_user, bool want_start, bool global)
 {
     pie_ctx::TokenIndex& t = c->tokx;
     PIE_HIP(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    const TokStage o = token_stage_of(k, global);
+    const TokStage o = lookup_stage_of(k, global);
     int rc = token_stage_room(c, o.bytes);
     if (rc) return rc;
     char* d = t.d_stage;
-    memcpy(t.h_stage, tok, k * sizeof(TokKey));
-    PIE_HIP(c, hipMemcpyAsync(d, t.h_stage, k * sizeof(TokKey), hipMemcpyHostToDevice, s));
+    memcpy(t.h_stage, tok, o.up);
+    PIE_HIP(c, hipMemcpyAsync(d, t.h_stage, o.up, hipMemcpyHostToDevice, s));
     const dim3 grid((unsigned)((k + 255) / 256));
-    int* o_user = want_user ? reinterpret_cast<int*>(d + o.user) : nullptr;
-    long long* o_start = want_start ? reinterpret_cast<long long*>(d + o.start) : nullptr;
+    int* o_user = want_user ? stage_at<int>(d, o.res.user) : nullptr;
+    long long* o_start = want_start ? stage_at<long long>(d, o.res.start) : nullptr;
     if (global)
-        hipLaunchKernelGGL(k_shard_token_lookup, grid, dim3(256), 0, s, reinterpret_cast<const TokKey*>(d), (long long)k, (const int*)t.slot_row,
+        hipLaunchKernelGGL(k_shard_token_lookup, grid, dim3(256), 0, s, stage_at<const TokKey>(d, 0), (long long)k, (const int*)t.slot_row,
                            t.log2_slots, (const TokKey*)t.tok, token_bound(c), (const long long*)c->d_end, (const long long*)c->d_start,
                            (const int*)c->d_user, (const int*)c->d_shard_rows, c->shard_rows_n, (const int*)c->d_shard_users, c->shard_users_n, now,
-                           reinterpret_cast<int*>(d + o.row), reinterpret_cast<int*>(d + o.grow), reinterpret_cast<unsigned char*>(d + o.live),
-                           o_user, o_start, reinterpret_cast<long long*>(d + o.end), t.status);
+                           stage_at<int>(d, o.res.row), stage_at<int>(d, o.grow), stage_at<unsigned char>(d, o.res.live), o_user, o_start,
+                           stage_at<long long>(d, o.res.end), t.status);
     else
-        hipLaunchKernelGGL(k_token_lookup, grid, dim3(256), 0, s, reinterpret_cast<const TokKey*>(d), (long long)k, (const int*)t.slot_row,
+        hipLaunchKernelGGL(k_token_lookup, grid, dim3(256), 0, s, stage_at<const TokKey>(d, 0), (long long)k, (const int*)t.slot_row,
                            t.log2_slots, (const TokKey*)t.tok, token_bound(c), (const long long*)c->d_end, (const long long*)c->d_start,
-                           (const int*)c->d_user, now, reinterpret_cast<int*>(d + o.row), reinterpret_cast<unsigned char*>(d + o.live), o_user,
-                           o_start, reinterpret_cast<long long*>(d + o.end), t.status);
+                           (const int*)c->d_user, now, stage_at<int>(d, o.res.row), stage_at<unsigned char>(d, o.res.live), o_user, o_start,
+                           stage_at<long long>(d, o.res.end), t.status);
     PIE_HIP(c, hipGetLastError());
-    PIE_HIP(c, hipMemcpyAsync(t.h_stage + o.end, d + o.end, o.status - o.end, hipMemcpyDeviceToHost, s));
-    PIE_HIP(c, hipMemcpyAsync(t.h_stage + o.status, t.status, kTokStatusWords * sizeof(unsigned int), hipMemcpyDeviceToHost, s));
-    return PIE_OK;
+    return token_stage_download(c, o);
 }
 
 // The wait phase: the one wait of a lookup; the results and the status words are in tokx.h_stage when it returns.
@@ -7058,7 +7159,7 @@ static int token_lookup_wait(pie_ctx* c, size_t k, bool global, const char* what
 {
     PIE_HIP(c, hipSetDevice(c->device));
     PIE_HIP(c, hipStreamSynchronize(c->stream));
-    return token_status_check(c, reinterpret_cast<const unsigned int*>(c->tokx.h_stage + token_stage_of(k, global).status), what);
+    return token_status_check(c, stage_at<const unsigned int>(c->tokx.h_stage, lookup_stage_of(k, global).status), what);
 }
 
 static int token_lookup_run(pie_ctx* c, const uint64_t* tok, size_t k, long long now, bool want_user, bool want_start, const char* what)
@@ -7079,13 +7180,7 @@ int pie_token_lookup(pie_ctx* c, const uint64_t* tok, size_t k, int64_t now, int
     if (k >= ((size_t)1 << 31)) return fail(c, PIE_E_INVAL, "%zu keys in one lookup", k);
     rc = token_lookup_run(c, tok, k, (long long)now, user_out != nullptr, start_out != nullptr, "pie_token_lookup");
     if (rc) return rc;
-    const TokStage o = token_stage_of(k);
-    const char* h = c->tokx.h_stage;
-    if (row_out) memcpy(row_out, h + o.row, k * 4);
-    if (live_out) memcpy(live_out, h + o.live, k);
-    if (user_out) memcpy(user_out, h + o.user, k * 4);
-    if (start_out) memcpy(start_out, h + o.start, k * 8);
-    if (end_out) memcpy(end_out, h + o.end, k * 8);
+    token_results_out(c->tokx.h_stage, lookup_stage_of(k).res, k, row_out, live_out, user_out, start_out, end_out);
     return PIE_OK;
 }
 
@@ -7101,9 +7196,9 @@ int pie_token_set_end(pie_ctx* c, const uint64_t* tok, const int64_t* new_end, s
     if (k >= ((size_t)1 << 31)) return fail(c, PIE_E_INVAL, "%zu keys in one call", k);
     rc = token_lookup_run(c, tok, k, (long long)now, false, false, "pie_token_set_end");
     if (rc) return rc;
-    const TokStage o = token_stage_of(k);
-    const int32_t* row = reinterpret_cast<const int32_t*>(c->tokx.h_stage + o.row);
-    const uint8_t* live = reinterpret_cast<const uint8_t*>(c->tokx.h_stage + o.live);
+    const TokStage o = lookup_stage_of(k);
+    const int32_t* row = stage_at<const int32_t>(c->tokx.h_stage, o.res.row);
+    const uint8_t* live = stage_at<const uint8_t>(c->tokx.h_stage, o.res.live);
     std::vector<int32_t> rows;
     std::vector<int64_t> ends;
     try {
@@ -7126,25 +7221,6 @@ int pie_token_set_end(pie_ctx* c, const uint64_t* tok, const int64_t* new_end, s
 
 // ---- a whole turn in one launch (pie_token_turn, pie_shard_token_turn; include/pie_scan.h, k_token_turn in pie_token.h)
 
-// offsets of a turn's staging block for k ops: [ops 40 k | next 4 k | pad | results as TokStage orders them: end 8 k | start 8 k |
-// row 4 k | user 4 k | live k | pad | status].  The sharded kernel answers GLOBAL rows in `row`.  A turn with n_create CREATE ops
-// (pie_session_turn) carries their users and disciplines behind next[]: [.. | next 4 k | cuser 4 n_create | cdisc 4 n_create | pad ..].
-struct TurnStage {
-    size_t next, cuser, cdisc, end, start, row, user, live, status, bytes;
-};
-static TurnStage turn_stage_of(size_t k, size_t n_create = 0)
-{
-    TurnStage o;
-    o.next = k * 40;
-    o.cuser = k * 44;
-    o.cdisc = o.cuser + n_create * 4;
-    o.end = (o.cdisc + n_create * 4 + 15) / 16 * 16;
-    o.start = o.end + k * 8; o.row = o.end + k * 16; o.user = o.end + k * 20; o.live = o.end + k * 24;
-    o.status = (o.end + k * 25 + 15) / 16 * 16;
-    o.bytes = o.status + kTokStatusWords * sizeof(unsigned int);
-    return o;
-}
-
 // What every form refuses beyond its state checks, with nothing staged or changed.  k > 0.
 static int token_turn_args(pie_ctx* c, const pie_turn_op* ops, size_t k, const char* what)
 {
@@ -7155,42 +7231,91 @@ static int token_turn_args(pie_ctx* c, const pie_turn_op* ops, size_t k, const c
     return PIE_OK;
 }
 
-// The queue phase (the checks are behind the caller, k > 0): the plan on the host, ONE upload of [ops | next], ONE kernel, ONE
-// download of the results and the status words, and an event behind them.  Nothing is waited for.
-static int token_turn_queue(pie_ctx* c, const pie_turn_op* ops, size_t k, bool global, const char* what)
+// A turn's inputs into the pinned block h as `o` lays them out: [ops | next | cuser | cdisc].  The plan (pie_turn_plan.h) goes
+// straight in: next[] where the device reads it, the head flags (built where the `live` results will land) into the reserved word
+// of the staged ops.  That word carries the head flag in bit 0 and above it the ordinal of a CREATE (its row is rows + ordinal),
+// whose user and discipline go to the compact arrays; without a create it is the head flag alone, and user / disc are not read.
+static int turn_stage_fill(pie_ctx* c, char* h, const TokStage& o, const pie_turn_op* ops, size_t k, const int32_t* user, const int32_t* disc,
+                           const char* what)
+{
+    memcpy(h, ops, k * sizeof(pie_turn_op));
+    pie_turn_op* staged = stage_at<pie_turn_op>(h, 0);
+    uint8_t* head = stage_at<uint8_t>(h, o.res.live);
+    if (!turn_plan(ops, k, stage_at<int32_t>(h, o.next), head, c->tokx.turn_slots)) return fail(c, PIE_E_NOMEM, "%s: no memory for %zu ops", what, k);
+    int32_t* cuser = stage_at<int32_t>(h, o.cuser);
+    int32_t* cdisc = stage_at<int32_t>(h, o.cdisc);
+    uint32_t j = 0;
+    for (size_t i = 0; i < k; ++i) {
+        uint32_t word = head[i];
+        if (ops[i].kind == PIE_TURN_CREATE) {
+            word |= j << 1;
+            cuser[j] = user[i];
+            cdisc[j] = disc[i];
+            ++j;
+        }
+        staged[i].reserved = (int32_t)word;
+    }
+    return PIE_OK;
+}
+
+// What a create-free turn queues on the context's stream: ONE upload of the block's inputs, ONE k_token_turn with a thread per op.
+// `status` are the words the kernel reports into: the context's, or the ones inside the slot's block.  `ord` is the ordered run
+// the kernel keeps in step: ord_mirror_of(c) for the synchronous turn, none for a turn begun beside scans and batches (which is
+// refused on a table that has a run: the host would learn of a stale run only at a wait).
+static int token_turn_launch(pie_ctx* c, const char* h, char* d, const TokStage& o, size_t k, bool global, unsigned int* status, OrdMirror ord)
+{
+    pie_ctx::TokenIndex& t = c->tokx;
+    hot_reserve(c, (long long)k); // the bound counts every op: never less than the rows that can move to the delta
+    PIE_HIP(c, hipMemcpyAsync(d, h, o.up, hipMemcpyHostToDevice, c->stream));
+    ShardMaps maps{};
+    if (global) maps = ShardMaps{(const int*)c->d_shard_rows, c->shard_rows_n, (const int*)c->d_shard_users, c->shard_users_n};
+    hipLaunchKernelGGL(global ? k_token_turn<true> : k_token_turn<false>, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, c->stream,
+                       stage_at<const TurnOp>(d, 0), stage_at<const int>(d, o.next), (long long)k, (const int*)t.slot_row, t.log2_slots,
+                       (const TokKey*)t.tok, token_bound(c), c->d_end, (const long long*)c->d_start, (const int*)c->d_user, maps, c->d_key,
+                       c->key_base, c->key_shift, c->d_fkey, c->fkey_base, c->fkey_shift, ord, hot_mirror_of(c), stage_at<int>(d, o.res.row),
+                       stage_at<unsigned char>(d, o.res.live), stage_at<int>(d, o.res.user), stage_at<long long>(d, o.res.start),
+                       stage_at<long long>(d, o.res.end), status);
+    PIE_HIP(c, hipGetLastError());
+    c->key_dirty = true;
+    return PIE_OK;
+}
+
+// ... and a turn that logs in (the room is behind the caller): ONE upload of [ops | next | cuser | cdisc], ONE k_session_turn
+static int session_turn_launch(pie_ctx* c, const TokStage& o, size_t k)
+{
+    pie_ctx::TokenIndex& t = c->tokx;
+    hot_reserve(c, (long long)k); // every delta record of the turn is owed to an op of its own: a touch, a delete or a create
+    ord_invalidate(c);            // the run does not take the new rows: it goes before the kernel could mirror into it
+    char* d = t.d_stage;
+    PIE_HIP(c, hipMemcpyAsync(d, t.h_stage, o.up, hipMemcpyHostToDevice, c->stream));
+    const bool keys = c->key_ok; // a table too large to carry the derived columns runs without them
+    hipLaunchKernelGGL(k_session_turn, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, c->stream, stage_at<const TurnOp>(d, 0),
+                       stage_at<const int>(d, o.next), (long long)k, stage_at<const int>(d, o.cuser), stage_at<const int>(d, o.cdisc), c->n,
+                       t.slot_row, t.log2_slots, t.tok, t.covered, c->d_start, c->d_end, c->d_user, c->d_disc, keys ? c->d_key : nullptr,
+                       c->key_base, c->key_shift, keys ? c->d_fkey : nullptr, c->fkey_base, c->fkey_shift, keys ? c->d_pay : nullptr,
+                       ord_mirror_of(c), hot_mirror_of(c), stage_at<int>(d, o.res.row), stage_at<unsigned char>(d, o.res.live),
+                       stage_at<int>(d, o.res.user), stage_at<long long>(d, o.res.start), stage_at<long long>(d, o.res.end), t.status);
+    PIE_HIP(c, hipGetLastError());
+    return PIE_OK;
+}
+
+// The queue phase (the checks are behind the caller, k > 0): the plan on the host, ONE upload, ONE kernel, ONE download of the
+// results and the status words, and an event behind them.  Nothing is waited for.  n_create > 0: the turn logs in
+// (pie_session_turn), and user / disc name who.
+static int token_turn_queue(pie_ctx* c, const pie_turn_op* ops, size_t k, bool global, const char* what, const int32_t* user = nullptr,
+                            const int32_t* disc = nullptr, size_t n_create = 0)
 {
     pie_ctx::TokenIndex& t = c->tokx;
     PIE_HIP(c, hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    const TurnStage o = turn_stage_of(k);
+    const TokStage o = turn_stage_of(k, n_create);
     int rc = token_stage_room(c, o.bytes);
     if (rc) return rc;
     if (!t.turn_done) PIE_HIP(c, hipEventCreateWithFlags(&t.turn_done, hipEventDisableTiming));
-    // the plan straight into the pinned block: next[] where the device reads it, the head flags (built where the `live` results
-    // will land) into the reserved word of the staged ops
-    memcpy(t.h_stage, ops, k * sizeof(pie_turn_op));
-    pie_turn_op* staged = reinterpret_cast<pie_turn_op*>(t.h_stage);
-    uint8_t* head = reinterpret_cast<uint8_t*>(t.h_stage + o.live);
-    if (!turn_plan(ops, k, reinterpret_cast<int32_t*>(t.h_stage + o.next), head, t.turn_slots)) return fail(c, PIE_E_NOMEM, "%s: no memory for %zu ops", what, k);
-    for (size_t i = 0; i < k; ++i) staged[i].reserved = head[i];
-    hot_reserve(c, (long long)k); // the bound counts every op: never less than the rows that can move to the delta
-    char* d = t.d_stage;
-    PIE_HIP(c, hipMemcpyAsync(d, t.h_stage, o.next + k * 4, hipMemcpyHostToDevice, s));
-    const dim3 grid((unsigned)((k + 255) / 256)); // a thread per op
-    TurnMaps maps{};
-    if (global) maps = TurnMaps{(const int*)c->d_shard_rows, c->shard_rows_n, (const int*)c->d_shard_users, c->shard_users_n};
-    auto launch = global ? k_token_turn<true> : k_token_turn<false>;
-    hipLaunchKernelGGL(launch, grid, dim3(256), 0, s, reinterpret_cast<const TurnOp*>(d), reinterpret_cast<const int*>(d + o.next), (long long)k,
-                       (const int*)t.slot_row, t.log2_slots, (const TokKey*)t.tok, token_bound(c), c->d_end, (const long long*)c->d_start,
-                       (const int*)c->d_user, maps, c->d_key, c->key_base, c->key_shift, c->d_fkey, c->fkey_base, c->fkey_shift,
-                       ord_mirror_of(c), hot_mirror_of(c), reinterpret_cast<int*>(d + o.row), reinterpret_cast<unsigned char*>(d + o.live),
-                       reinterpret_cast<int*>(d + o.user), reinterpret_cast<long long*>(d + o.start), reinterpret_cast<long long*>(d + o.end),
-                       t.status);
-    PIE_HIP(c, hipGetLastError());
-    c->key_dirty = true;
-    PIE_HIP(c, hipMemcpyAsync(t.h_stage + o.end, d + o.end, o.status - o.end, hipMemcpyDeviceToHost, s));
-    PIE_HIP(c, hipMemcpyAsync(t.h_stage + o.status, t.status, kTokStatusWords * sizeof(unsigned int), hipMemcpyDeviceToHost, s));
-    PIE_HIP(c, hipEventRecord(t.turn_done, s));
+    if ((rc = turn_stage_fill(c, t.h_stage, o, ops, k, user, disc, what)) != PIE_OK) return rc;
+    rc = n_create ? session_turn_launch(c, o, k) : token_turn_launch(c, t.h_stage, t.d_stage, o, k, global, t.status, ord_mirror_of(c));
+    if (rc == PIE_OK) rc = token_stage_download(c, o);
+    if (rc) return rc;
+    PIE_HIP(c, hipEventRecord(t.turn_done, c->stream));
     return PIE_OK;
 }
 
@@ -7208,15 +7333,10 @@ static int token_turn_wait(pie_ctx* c, size_t k, const char* what, int32_t* row_
         *c->ord.h_stale = 0;
         ord_invalidate(c);
     }
-    const TurnStage o = turn_stage_of(k, n_create);
-    const char* h = t.h_stage;
-    int rc = token_status_check(c, reinterpret_cast<const unsigned int*>(h + o.status), what);
+    const TokStage o = turn_stage_of(k, n_create);
+    int rc = token_status_check(c, stage_at<const unsigned int>(t.h_stage, o.status), what);
     if (rc) return rc;
-    if (row_out) memcpy(row_out, h + o.row, k * 4);
-    if (live_out) memcpy(live_out, h + o.live, k);
-    if (user_out) memcpy(user_out, h + o.user, k * 4);
-    if (start_out) memcpy(start_out, h + o.start, k * 8);
-    if (end_out) memcpy(end_out, h + o.end, k * 8);
+    token_results_out(t.h_stage, o.res, k, row_out, live_out, user_out, start_out, end_out);
     return PIE_OK;
 }
 
@@ -7251,54 +7371,6 @@ int pie_session_turn_plan(const pie_turn_op* ops, size_t k, int64_t row0, int32_
     if (!turn_plan(ops, k, next_out, head_out, slots)) return PIE_E_NOMEM;
     const size_t n_create = session_turn_rows(ops, k, row0, new_row_out);
     if (n_create_out) *n_create_out = n_create;
-    return PIE_OK;
-}
-
-// The queue phase of a turn with n_create > 0 creates (the checks and the room are behind the caller): the plan on the host, ONE
-// upload of [ops | next | cuser | cdisc], ONE kernel, ONE download of the results and the status words, an event behind them.
-static int session_turn_queue(pie_ctx* c, const pie_turn_op* ops, size_t k, const int32_t* user, const int32_t* disc, size_t n_create,
-                              const char* what)
-{
-    pie_ctx::TokenIndex& t = c->tokx;
-    hipStream_t s = c->stream;
-    const TurnStage o = turn_stage_of(k, n_create);
-    int rc = token_stage_room(c, o.bytes);
-    if (rc) return rc;
-    if (!t.turn_done) PIE_HIP(c, hipEventCreateWithFlags(&t.turn_done, hipEventDisableTiming));
-    memcpy(t.h_stage, ops, k * sizeof(pie_turn_op));
-    pie_turn_op* staged = reinterpret_cast<pie_turn_op*>(t.h_stage);
-    uint8_t* head = reinterpret_cast<uint8_t*>(t.h_stage + o.live);
-    if (!turn_plan(ops, k, reinterpret_cast<int32_t*>(t.h_stage + o.next), head, t.turn_slots)) return fail(c, PIE_E_NOMEM, "%s: no memory for %zu ops", what, k);
-    // the reserved word of a staged op: the head flag in bit 0, above it the ordinal of a create (its row is rows + ordinal)
-    int32_t* cuser = reinterpret_cast<int32_t*>(t.h_stage + o.cuser);
-    int32_t* cdisc = reinterpret_cast<int32_t*>(t.h_stage + o.cdisc);
-    uint32_t j = 0;
-    for (size_t i = 0; i < k; ++i) {
-        uint32_t word = head[i];
-        if (ops[i].kind == PIE_TURN_CREATE) {
-            word |= j << 1;
-            cuser[j] = user[i];
-            cdisc[j] = disc[i];
-            ++j;
-        }
-        staged[i].reserved = (int32_t)word;
-    }
-    hot_reserve(c, (long long)k); // every delta record of the turn is owed to an op of its own: a touch, a delete or a create
-    ord_invalidate(c);            // the run does not take the new rows: it goes before the kernel could mirror into it
-    char* d = t.d_stage;
-    PIE_HIP(c, hipMemcpyAsync(d, t.h_stage, o.cdisc + n_create * 4, hipMemcpyHostToDevice, s));
-    const bool keys = c->key_ok; // a table too large to carry the derived columns runs without them
-    hipLaunchKernelGGL(k_session_turn, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const TurnOp*>(d),
-                       reinterpret_cast<const int*>(d + o.next), (long long)k, reinterpret_cast<const int*>(d + o.cuser),
-                       reinterpret_cast<const int*>(d + o.cdisc), c->n, t.slot_row, t.log2_slots, t.tok, t.covered, c->d_start, c->d_end, c->d_user,
-                       c->d_disc, keys ? c->d_key : nullptr, c->key_base, c->key_shift, keys ? c->d_fkey : nullptr, c->fkey_base, c->fkey_shift,
-                       keys ? c->d_pay : nullptr, ord_mirror_of(c), hot_mirror_of(c), reinterpret_cast<int*>(d + o.row),
-                       reinterpret_cast<unsigned char*>(d + o.live), reinterpret_cast<int*>(d + o.user), reinterpret_cast<long long*>(d + o.start),
-                       reinterpret_cast<long long*>(d + o.end), t.status);
-    PIE_HIP(c, hipGetLastError());
-    PIE_HIP(c, hipMemcpyAsync(t.h_stage + o.end, d + o.end, o.status - o.end, hipMemcpyDeviceToHost, s));
-    PIE_HIP(c, hipMemcpyAsync(t.h_stage + o.status, t.status, kTokStatusWords * sizeof(unsigned int), hipMemcpyDeviceToHost, s));
-    PIE_HIP(c, hipEventRecord(t.turn_done, s));
     return PIE_OK;
 }
 
@@ -7339,7 +7411,7 @@ int pie_session_turn(pie_ctx* c, const pie_turn_op* ops, size_t k, const int32_t
         if (rc) return rc;
     }
     if ((rc = token_make_room(c, old_n + creates, what)) != PIE_OK) return rc;
-    if ((rc = session_turn_queue(c, ops, k, user, disc, n_create, what)) != PIE_OK) return rc;
+    if ((rc = token_turn_queue(c, ops, k, false, what, user, disc, n_create)) != PIE_OK) return rc;
     // the host's picture moves as an append moves it; the rows are in the stream behind everything queued so far
     c->n = old_n + creates;
     t.covered = c->n;
@@ -7448,10 +7520,11 @@ static int token_after_compact(pie_ctx* c, long long n_old)
 // same call and keeps what is its own; nothing is exchanged.  The host knows covered_g, the shard's row count and the slot
 // count; which local rows are covered only the device's row map knows.
 
-static int shard_token_ready(pie_ctx* c, const char* what, bool need_column)
+// idle = false: the call runs beside scans, batches and begun turns, and asks for the sharded table alone
+static int shard_token_ready(pie_ctx* c, const char* what, bool need_column, bool idle = true)
 {
     if (c->cap_rows == 0) return fail(c, PIE_E_STATE, "%s: no table loaded", what);
-    int rc = shard_ready(c, what);
+    int rc = idle ? shard_ready(c, what) : shard_table_ready(c, what);
     if (rc) return rc;
     if (need_column && !(c->tokx.tok && c->tokx.sharded))
         return fail(c, PIE_E_STATE, "%s: the table has no token column (pie_shard_token_set gives it one)", what);
@@ -7495,13 +7568,10 @@ int shard_token_lookup_wait(pie_ctx* c, size_t k, int32_t* row_global_out, uint8
     if (k == 0) return PIE_OK;
     int rc = token_lookup_wait(c, k, true, "pie_shard_token_lookup");
     if (rc) return rc;
-    const TokStage o = token_stage_of(k, true);
-    const char* h = c->tokx.h_stage;
-    if (row_global_out) memcpy(row_global_out, h + o.grow, k * 4);
-    if (live_out) memcpy(live_out, h + o.live, k);
-    if (user_global_out) memcpy(user_global_out, h + o.user, k * 4);
-    if (start_out) memcpy(start_out, h + o.start, k * 8);
-    if (end_out) memcpy(end_out, h + o.end, k * 8);
+    const TokStage o = lookup_stage_of(k, true);
+    TokResults global = o.res; // this form alone has two rows to give: the caller gets the GLOBAL one
+    global.row = o.grow;
+    token_results_out(c->tokx.h_stage, global, k, row_global_out, live_out, user_global_out, start_out, end_out);
     return PIE_OK;
 }
 
@@ -7661,10 +7731,10 @@ int pie_shard_token_set_end(pie_ctx* c, const uint64_t* tok, const int64_t* new_
     rc = pie_internal::shard_token_lookup_queue(c, tok, k, now);
     if (rc == PIE_OK) rc = token_lookup_wait(c, k, true, "pie_shard_token_set_end");
     if (rc) return rc;
-    const TokStage o = token_stage_of(k, true);
-    const int32_t* row = reinterpret_cast<const int32_t*>(c->tokx.h_stage + o.row);
-    const int32_t* grow = reinterpret_cast<const int32_t*>(c->tokx.h_stage + o.grow);
-    const uint8_t* live = reinterpret_cast<const uint8_t*>(c->tokx.h_stage + o.live);
+    const TokStage o = lookup_stage_of(k, true);
+    const int32_t* row = stage_at<const int32_t>(c->tokx.h_stage, o.res.row);
+    const int32_t* grow = stage_at<const int32_t>(c->tokx.h_stage, o.grow);
+    const uint8_t* live = stage_at<const uint8_t>(c->tokx.h_stage, o.res.live);
     std::vector<int32_t> rows;
     std::vector<int64_t> ends;
     try {
@@ -7698,39 +7768,36 @@ int pie_shard_token_layout(pie_ctx* c, size_t* covered_global_out, size_t* cover
 // scans and batches; every mutator is refused while those are in flight.  So a lookup needs no empty pipeline, only a stream, a
 // staging area and status words that are not the context's: tokx.lk.
 
-// a slot's staging for k keys: up go [keys 16 k | now 8 k | status (zeroed)], back come [status | end 8 k | start 8 k | row 4 k |
-// user 4 k | live k] — one copy each way; `row` holds the GLOBAL row in the shard form
-struct TokFlightStage {
-    size_t now, status, end, start, row, user, live, bytes;
-};
-static TokFlightStage token_flight_stage_of(size_t k)
+// A slot's staging holds `bytes`.  This slot's staging alone grows (from 256 KiB, which hold 5 300 keys or 3 700 ops, by
+// doubling); the lookups and turns in flight keep theirs, and the old blocks wait for the next call that has drained the context
+// anyway (token_drop, pie_ctx_destroy).
+static int slot_stage_room(pie_ctx* c, SidePass& side, pie_ctx::TokenIndex::FlightSlot& sl, size_t bytes, size_t k, const char* what,
+                           const char* unit)
 {
-    TokFlightStage o;
-    o.now = k * 16;
-    o.status = k * 24;
-    o.end = o.status + kTokStatusWords * sizeof(unsigned int);
-    o.start = o.end + k * 8;
-    o.row = o.start + k * 8;
-    o.user = o.row + k * 4;
-    o.live = o.user + k * 4;
-    o.bytes = (o.live + k + 15) / 16 * 16;
-    return o;
+    if (bytes <= sl.bytes) return PIE_OK;
+    size_t want = sl.bytes ? sl.bytes : (size_t)256 << 10;
+    while (want < bytes) want *= 2;
+    char *nh = nullptr, *nd = nullptr;
+    PIE_HIP(c, hipHostMalloc(&nh, want, hipHostMallocDefault));
+    if (hipMalloc(&nd, want) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipHostFree(nh);
+        return fail(c, PIE_E_NOMEM, "%s: no device memory for the staging of %zu %s", what, k, unit);
+    }
+    if (!side_retire(side, sl.h, sl.d)) {
+        (void)hipHostFree(nh);
+        (void)hipFree(nd);
+        return fail(c, PIE_E_NOMEM, "%s: out of host memory", what);
+    }
+    sl.h = nh;
+    sl.d = nd;
+    sl.bytes = want;
+    return PIE_OK;
 }
 
 static int token_flight_ready(pie_ctx* c, const char* what, bool global)
 {
-    if (c->cap_rows == 0) return fail(c, PIE_E_STATE, "%s: no table loaded", what);
-    if (global) {
-        if (!c->shard_on || !c->d_shard_rows || !c->d_shard_users)
-            return fail(c, PIE_E_STATE, "%s: the context holds no sharded table (pie_shard_table)", what);
-        if (c->n != c->shard_rows_n)
-            return fail(c, PIE_E_STATE, "%s: %lld rows were added after pie_shard_table: they have no global row", what, c->n - c->shard_rows_n);
-        if (!(c->tokx.tok && c->tokx.sharded))
-            return fail(c, PIE_E_STATE, "%s: the table has no token column (pie_shard_token_set gives it one)", what);
-    } else if (!c->tokx.tok) {
-        return fail(c, PIE_E_STATE, "%s: the table has no token column (pie_token_set gives it one)", what);
-    }
-    return PIE_OK;
+    return global ? shard_token_ready(c, what, true, false) : token_ready(c, what, true, false);
 }
 
 static int token_flight_begin(pie_ctx* c, const uint64_t* tok, const int64_t* now, size_t k, bool global, const char* what)
@@ -7745,52 +7812,30 @@ static int token_flight_begin(pie_ctx* c, const uint64_t* tok, const int64_t* no
     PIE_HIP(c, hipSetDevice(c->device));
     if ((rc = side_open(c, t.side)) != PIE_OK) return rc;
     pie_ctx::TokenIndex::Lookup& l = t.lk[(t.lk_head + t.lk_n) % kTokLookups]; // free: lookups finish in the order they began
-    const TokFlightStage o = token_flight_stage_of(k);
-    if (o.bytes > l.bytes) {
-        // This slot's staging alone grows; the lookups in flight keep theirs, and the old blocks wait for the next call that
-        // has drained the context anyway (token_drop, pie_ctx_destroy).  256 KiB hold 5 300 keys.
-        size_t want = l.bytes ? l.bytes : (size_t)256 << 10;
-        while (want < o.bytes) want *= 2;
-        char *nh = nullptr, *nd = nullptr;
-        PIE_HIP(c, hipHostMalloc(&nh, want, hipHostMallocDefault));
-        if (hipMalloc(&nd, want) != hipSuccess) {
-            (void)hipGetLastError();
-            (void)hipHostFree(nh);
-            return fail(c, PIE_E_NOMEM, "%s: no device memory for the staging of %zu keys", what, k);
-        }
-        if (!side_retire(t.side, l.h, l.d)) {
-            (void)hipHostFree(nh);
-            (void)hipFree(nd);
-            return fail(c, PIE_E_NOMEM, "%s: out of host memory", what);
-        }
-        l.h = nh;
-        l.d = nd;
-        l.bytes = want;
-    }
+    const TokStage o = lookup_flight_stage_of(k);
+    if ((rc = slot_stage_room(c, t.side, l, o.bytes, k, what, l.unit)) != PIE_OK) return rc;
     hipStream_t s = t.side.stream;
     if ((rc = side_enter(c, t.side, l.fence, hipEventDisableTiming)) != PIE_OK) return rc;
     if (k > 0) {
         memcpy(l.h, tok, k * sizeof(TokKey));
         memcpy(l.h + o.now, now, k * 8);
-        memset(l.h + o.status, 0, kTokStatusWords * sizeof(unsigned int));
-        PIE_HIP(c, hipMemcpyAsync(l.d, l.h, o.end, hipMemcpyHostToDevice, s));
+        memset(l.h + o.status, 0, kTokStatusBytes);
+        PIE_HIP(c, hipMemcpyAsync(l.d, l.h, o.up, hipMemcpyHostToDevice, s));
         char* d = l.d;
         const dim3 grid((unsigned)((k + 255) / 256));
         if (global)
-            hipLaunchKernelGGL(k_shard_token_lookup_now, grid, dim3(256), 0, s, reinterpret_cast<const TokKey*>(d),
-                               reinterpret_cast<const long long*>(d + o.now), (long long)k, (const int*)t.slot_row, t.log2_slots,
-                               (const TokKey*)t.tok, token_bound(c), (const long long*)c->d_end, (const long long*)c->d_start,
-                               (const int*)c->d_user, (const int*)c->d_shard_rows, c->shard_rows_n, (const int*)c->d_shard_users,
-                               c->shard_users_n, reinterpret_cast<int*>(d + o.row), reinterpret_cast<unsigned char*>(d + o.live),
-                               reinterpret_cast<int*>(d + o.user), reinterpret_cast<long long*>(d + o.start),
-                               reinterpret_cast<long long*>(d + o.end), reinterpret_cast<unsigned int*>(d + o.status));
+            hipLaunchKernelGGL(k_shard_token_lookup_now, grid, dim3(256), 0, s, stage_at<const TokKey>(d, 0), stage_at<const long long>(d, o.now),
+                               (long long)k, (const int*)t.slot_row, t.log2_slots, (const TokKey*)t.tok, token_bound(c), (const long long*)c->d_end,
+                               (const long long*)c->d_start, (const int*)c->d_user, (const int*)c->d_shard_rows, c->shard_rows_n,
+                               (const int*)c->d_shard_users, c->shard_users_n, stage_at<int>(d, o.res.row), stage_at<unsigned char>(d, o.res.live),
+                               stage_at<int>(d, o.res.user), stage_at<long long>(d, o.res.start), stage_at<long long>(d, o.res.end),
+                               stage_at<unsigned int>(d, o.status));
         else
-            hipLaunchKernelGGL(k_token_lookup_now, grid, dim3(256), 0, s, reinterpret_cast<const TokKey*>(d),
-                               reinterpret_cast<const long long*>(d + o.now), (long long)k, (const int*)t.slot_row, t.log2_slots,
-                               (const TokKey*)t.tok, token_bound(c), (const long long*)c->d_end, (const long long*)c->d_start,
-                               (const int*)c->d_user, reinterpret_cast<int*>(d + o.row), reinterpret_cast<unsigned char*>(d + o.live),
-                               reinterpret_cast<int*>(d + o.user), reinterpret_cast<long long*>(d + o.start),
-                               reinterpret_cast<long long*>(d + o.end), reinterpret_cast<unsigned int*>(d + o.status));
+            hipLaunchKernelGGL(k_token_lookup_now, grid, dim3(256), 0, s, stage_at<const TokKey>(d, 0), stage_at<const long long>(d, o.now),
+                               (long long)k, (const int*)t.slot_row, t.log2_slots, (const TokKey*)t.tok, token_bound(c), (const long long*)c->d_end,
+                               (const long long*)c->d_start, (const int*)c->d_user, stage_at<int>(d, o.res.row),
+                               stage_at<unsigned char>(d, o.res.live), stage_at<int>(d, o.res.user), stage_at<long long>(d, o.res.start),
+                               stage_at<long long>(d, o.res.end), stage_at<unsigned int>(d, o.status));
         PIE_HIP(c, hipGetLastError());
         PIE_HIP(c, hipMemcpyAsync(l.h + o.status, d + o.status, o.bytes - o.status, hipMemcpyDeviceToHost, s));
     }
@@ -7807,29 +7852,8 @@ static int token_flight_finish(pie_ctx* c, int32_t* row_out, uint8_t* live_out, 
 {
     if (!c) return PIE_E_INVAL;
     pie_ctx::TokenIndex& t = c->tokx;
-    if (t.lk_n == 0) return fail(c, PIE_E_STATE, "%s: no lookup was begun", what);
-    pie_ctx::TokenIndex::Lookup& l = t.lk[t.lk_head];
-    if (l.global != global) return fail(c, PIE_E_STATE, "%s: the oldest lookup was begun by the %s form", what, l.global ? "shard" : "plain");
-    const size_t k = l.k;
-    if (k_out) *k_out = k;
-    if (cap < k) return fail(c, PIE_E_CAPACITY, "%s: %zu keys, room for %zu", what, k, cap);
-    PIE_HIP(c, hipSetDevice(c->device));
-    int rc = token_lookup_landed(c, l, what);
-    t.lk_head = (t.lk_head + 1) % kTokLookups; // the slot is returned whatever the wait said
-    t.lk_n--;
-    if (rc) t.side.stale = true; // its copy may still be pending: the next begin drains the lookup stream before it touches a slot
-    if (rc || k == 0) return rc;
-    const TokFlightStage o = token_flight_stage_of(k);
-    const char* h = l.h;
-    const unsigned int* st = reinterpret_cast<const unsigned int*>(h + o.status);
-    if (st[0] || st[1])
-        return fail(c, PIE_E_HIP, "%s: probe bound exhausted (a lookup ran %llu steps without meeting an empty slot)", what, 1ull << t.log2_slots);
-    if (row_out) memcpy(row_out, h + o.row, k * 4);
-    if (live_out) memcpy(live_out, h + o.live, k);
-    if (user_out) memcpy(user_out, h + o.user, k * 4);
-    if (start_out) memcpy(start_out, h + o.start, k * 8);
-    if (end_out) memcpy(end_out, h + o.end, k * 8);
-    return PIE_OK;
+    return flight_finish(c, t.lk, t.lk_head, t.lk_n, t.side.stale, lookup_flight_stage_of, row_out, live_out, user_out, start_out, end_out, cap,
+                         k_out, global, what);
 }
 
 int pie_token_lookup_begin(pie_ctx* c, const uint64_t* tok, const int64_t* now, size_t k)
@@ -7861,25 +7885,6 @@ int pie_shard_token_lookup_finish(pie_ctx* c, int32_t* row_global_out, uint8_t* 
 // on the context's stream, so stream order already puts the turn between them.  The other lanes are fenced by events: the
 // context's stream waits for every lane that has a batch in flight (turn_fence_enter), the turn's kernel runs, an event is
 // recorded behind it, and every lane's next begin waits for that event once (lane_after_mutation).  Nothing here waits on the host.
-
-// a slot's staging for k ops: up go [ops 40 k | next 4 k | pad | status (zeroed)], back come [status | end 8 k | start 8 k |
-// row 4 k | user 4 k | live k] — one copy each way; `row` holds the GLOBAL row in the shard form
-struct TurnFlightStage {
-    size_t next, status, end, start, row, user, live, bytes;
-};
-static TurnFlightStage turn_flight_stage_of(size_t k)
-{
-    TurnFlightStage o;
-    o.next = k * 40;
-    o.status = (k * 44 + 15) / 16 * 16;
-    o.end = o.status + kTokStatusWords * sizeof(unsigned int);
-    o.start = o.end + k * 8;
-    o.row = o.start + k * 8;
-    o.user = o.row + k * 4;
-    o.live = o.user + k * 4;
-    o.bytes = (o.live + k + 15) / 16 * 16;
-    return o;
-}
 
 // What stands in front of the turn's kernel on the context's stream.  First every union tail that still waits for a launch: a
 // tail rebuilds its batch's masks from the table, so it must run before `end` changes (what pie_scan_batch_flush does; a begin
@@ -7925,58 +7930,19 @@ static int turn_flight_begin(pie_ctx* c, const pie_turn_op* ops, size_t k, bool 
         t.tn_stale = false;
     }
     pie_ctx::TokenIndex::Turn& u = t.tn[(t.tn_head + t.tn_n) % kTokTurns]; // free: turns finish in the order they began
-    const TurnFlightStage o = turn_flight_stage_of(k);
-    if (o.bytes > u.bytes) {
-        // This slot's staging alone grows; the turns in flight keep theirs, and the old blocks wait for the next call that has
-        // drained the context anyway (token_drop, pie_ctx_destroy), as a lookup slot's do.  256 KiB hold 3 700 ops.
-        size_t want = u.bytes ? u.bytes : (size_t)256 << 10;
-        while (want < o.bytes) want *= 2;
-        char *nh = nullptr, *nd = nullptr;
-        PIE_HIP(c, hipHostMalloc(&nh, want, hipHostMallocDefault));
-        if (hipMalloc(&nd, want) != hipSuccess) {
-            (void)hipGetLastError();
-            (void)hipHostFree(nh);
-            return fail(c, PIE_E_NOMEM, "%s: no device memory for the staging of %zu ops", what, k);
-        }
-        if (!side_retire(t.side, u.h, u.d)) {
-            (void)hipHostFree(nh);
-            (void)hipFree(nd);
-            return fail(c, PIE_E_NOMEM, "%s: out of host memory", what);
-        }
-        u.h = nh;
-        u.d = nd;
-        u.bytes = want;
-    }
+    const TokStage o = turn_flight_stage_of(k);
+    if ((rc = slot_stage_room(c, t.side, u, o.bytes, k, what, u.unit)) != PIE_OK) return rc;
     if (!u.done) PIE_HIP(c, hipEventCreateWithFlags(&u.done, hipEventDisableTiming));
     if (!c->mut_event) PIE_HIP(c, hipEventCreateWithFlags(&c->mut_event, hipEventDisableTiming));
     if (k > 0) {
-        // the plan on the host, straight into the pinned block (as token_turn_queue stages it): next[] where the device reads it,
-        // the head flags (built where the `live` results will land) into the reserved word of the staged ops
-        memcpy(u.h, ops, k * sizeof(pie_turn_op));
-        pie_turn_op* staged = reinterpret_cast<pie_turn_op*>(u.h);
-        uint8_t* head = reinterpret_cast<uint8_t*>(u.h + o.live);
-        if (!turn_plan(ops, k, reinterpret_cast<int32_t*>(u.h + o.next), head, t.turn_slots)) return fail(c, PIE_E_NOMEM, "%s: no memory for %zu ops", what, k);
-        for (size_t i = 0; i < k; ++i) staged[i].reserved = head[i];
-        memset(u.h + o.status, 0, kTokStatusWords * sizeof(unsigned int));
+        if ((rc = turn_stage_fill(c, u.h, o, ops, k, nullptr, nullptr, what)) != PIE_OK) return rc;
+        memset(u.h + o.status, 0, kTokStatusBytes);
         if ((rc = turn_fence_enter(c)) != PIE_OK) return rc;
-        // Host-side state the synchronous turn moves too; both are flags, and what they set off waits for an idle context
-        // (DESIGN.md 4.w): the hot index's delta bound (past it the index is given up: later batches read the key column, which
-        // the kernel keeps in step) and key_dirty (the re-fit is gated on nothing in flight and runs on this stream).
-        hot_reserve(c, (long long)k);
+        // Host-side state the synchronous turn moves too (token_turn_launch); both are flags, and what they set off waits for an
+        // idle context: the hot index's delta bound (past it the index is given up: later batches read the key
+        // column, which the kernel keeps in step) and key_dirty (the re-fit is gated on nothing in flight and runs on this stream).
         char* d = u.d;
-        PIE_HIP(c, hipMemcpyAsync(d, u.h, o.end, hipMemcpyHostToDevice, s));
-        const dim3 grid((unsigned)((k + 255) / 256)); // a thread per op
-        TurnMaps maps{};
-        if (global) maps = TurnMaps{(const int*)c->d_shard_rows, c->shard_rows_n, (const int*)c->d_shard_users, c->shard_users_n};
-        auto launch = global ? k_token_turn<true> : k_token_turn<false>;
-        hipLaunchKernelGGL(launch, grid, dim3(256), 0, s, reinterpret_cast<const TurnOp*>(d), reinterpret_cast<const int*>(d + o.next), (long long)k,
-                           (const int*)t.slot_row, t.log2_slots, (const TokKey*)t.tok, token_bound(c), c->d_end, (const long long*)c->d_start,
-                           (const int*)c->d_user, maps, c->d_key, c->key_base, c->key_shift, c->d_fkey, c->fkey_base, c->fkey_shift,
-                           OrdMirror{}, hot_mirror_of(c), reinterpret_cast<int*>(d + o.row), reinterpret_cast<unsigned char*>(d + o.live),
-                           reinterpret_cast<int*>(d + o.user), reinterpret_cast<long long*>(d + o.start), reinterpret_cast<long long*>(d + o.end),
-                           reinterpret_cast<unsigned int*>(d + o.status));
-        PIE_HIP(c, hipGetLastError());
-        c->key_dirty = true;
+        if ((rc = token_turn_launch(c, u.h, d, o, k, global, stage_at<unsigned int>(d, o.status), OrdMirror{})) != PIE_OK) return rc;
         if ((rc = turn_fence_leave(c)) != PIE_OK) return rc;
         PIE_HIP(c, hipMemcpyAsync(u.h + o.status, d + o.status, o.bytes - o.status, hipMemcpyDeviceToHost, s));
         PIE_HIP(c, hipEventRecord(u.done, s));
@@ -7993,29 +7959,8 @@ static int turn_flight_finish(pie_ctx* c, int32_t* row_out, uint8_t* live_out, i
 {
     if (!c) return PIE_E_INVAL;
     pie_ctx::TokenIndex& t = c->tokx;
-    if (t.tn_n == 0) return fail(c, PIE_E_STATE, "%s: no turn was begun", what);
-    pie_ctx::TokenIndex::Turn& u = t.tn[t.tn_head];
-    if (u.global != global) return fail(c, PIE_E_STATE, "%s: the oldest turn was begun by the %s form", what, u.global ? "shard" : "plain");
-    const size_t k = u.k;
-    if (k_out) *k_out = k;
-    if (cap < k) return fail(c, PIE_E_CAPACITY, "%s: %zu ops, room for %zu", what, k, cap);
-    PIE_HIP(c, hipSetDevice(c->device));
-    int rc = token_turn_landed(c, u, what);
-    t.tn_head = (t.tn_head + 1) % kTokTurns; // the slot is returned whatever the wait said
-    t.tn_n--;
-    if (rc) t.tn_stale = true; // its download may still be pending: the next begin drains before it touches a slot
-    if (rc || k == 0) return rc;
-    const TurnFlightStage o = turn_flight_stage_of(k);
-    const char* h = u.h;
-    const unsigned int* st = reinterpret_cast<const unsigned int*>(h + o.status);
-    if (st[0] || st[1])
-        return fail(c, PIE_E_HIP, "%s: probe bound exhausted (a lookup ran %llu steps without meeting an empty slot)", what, 1ull << t.log2_slots);
-    if (row_out) memcpy(row_out, h + o.row, k * 4);
-    if (live_out) memcpy(live_out, h + o.live, k);
-    if (user_out) memcpy(user_out, h + o.user, k * 4);
-    if (start_out) memcpy(start_out, h + o.start, k * 8);
-    if (end_out) memcpy(end_out, h + o.end, k * 8);
-    return PIE_OK;
+    return flight_finish(c, t.tn, t.tn_head, t.tn_n, t.tn_stale, turn_flight_stage_of, row_out, live_out, user_out, start_out, end_out, cap, k_out,
+                         global, what);
 }
 
 int pie_token_turn_begin(pie_ctx* c, const pie_turn_op* ops, size_t k) { return turn_flight_begin(c, ops, k, false, "pie_token_turn_begin"); }
@@ -8235,7 +8180,7 @@ int shard_token_flight_drop_last(pie_ctx* c, const char* what)
     pie_ctx::TokenIndex& t = c->tokx;
     if (t.lk_n == 0) return fail(c, PIE_E_STATE, "%s: no lookup was begun", what);
     if (hipSetDevice(c->device) != hipSuccess) (void)hipGetLastError();
-    const int rc = token_lookup_landed(c, t.lk[(t.lk_head + t.lk_n - 1) % kTokLookups], what);
+    const int rc = flight_slot_landed(c, t.lk[(t.lk_head + t.lk_n - 1) % kTokLookups], what);
     t.lk_n--;
     if (rc) t.side.stale = true;
     return rc;

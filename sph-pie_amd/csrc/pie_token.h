@@ -38,24 +38,30 @@ __host__ __device__ __forceinline__ unsigned long long token_home(unsigned long 
     return log2_slots ? token_mix(k0, k1) >> (64 - log2_slots) : 0ull;
 }
 
-// One lane per row of [row0, row0 + k): claim the first empty slot from the row's home.  Keys are never compared, so rows with
-// equal keys all get in.  The claim is a relaxed agent-scope compare-and-swap: every reader is a later kernel on the stream.
+// Claim the first empty slot from the key's home for `row`.  Keys are never compared, so rows with equal keys all get in.  The
+// claim is a relaxed agent-scope compare-and-swap: every reader is a later kernel on the stream.  At most `slots` steps; a lane
+// that exhausts them sets status[0].
+__device__ __forceinline__ void token_claim(TokKey key, int row, int* slot_row, unsigned log2_slots, unsigned int* status)
+{
+    const unsigned long long slots = 1ull << log2_slots, mask = slots - 1;
+    unsigned long long s = token_home(key.x, key.y, log2_slots);
+    unsigned long long step = 0;
+    for (; step < slots; ++step) {
+        int expected = -1;
+        if (__hip_atomic_compare_exchange_strong(&slot_row[s], &expected, row, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;
+        s = (s + 1) & mask;
+    }
+    if (step == slots) status[0] = 1u;
+}
+
+// One lane per row of [row0, row0 + k): token_claim for the row's key.
 __global__ __launch_bounds__(256) void k_token_insert(const TokKey* __restrict__ tok, long long row0, long long k, int* __restrict__ slot_row,
                                                       unsigned log2_slots, unsigned int* __restrict__ status)
 {
     const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= k) return;
     const long long row = row0 + t;
-    const TokKey key = tok[row];
-    const unsigned long long slots = 1ull << log2_slots, mask = slots - 1;
-    unsigned long long s = token_home(key.x, key.y, log2_slots);
-    unsigned long long step = 0;
-    for (; step < slots; ++step) {
-        int expected = -1;
-        if (__hip_atomic_compare_exchange_strong(&slot_row[s], &expected, (int)row, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;
-        s = (s + 1) & mask;
-    }
-    if (step == slots) status[0] = 1u;
+    token_claim(tok[row], (int)row, slot_row, log2_slots, status);
 }
 
 // The probe every lookup runs: walk from the key's home slot to the first empty slot; among the slots whose row carries the key
@@ -81,7 +87,34 @@ __device__ __forceinline__ int token_probe(TokKey key, const int* __restrict__ s
     return best;
 }
 
-// One lane per query key: of several sessions under one key the latest (largest row) wins.  Outputs may be absent (NULL).
+// the two maps of a sharded context (kShard): rows and users are answered as GLOBAL ids, both reads bounded (best < n_local by the
+// probe's bound, user < n_users; -1 otherwise)
+struct ShardMaps {
+    const int* rows;
+    long long n_local;
+    const int* users;
+    int n_users;
+};
+
+// What every lookup answers for key t once its probe gave `best`: of several sessions under one key the latest (largest row) won.
+// kShard: the row and the user as GLOBAL ids through the two maps.  kOptional: an output may be absent (NULL), and what it would
+// have held is not read.  *now is the key's clock, read where `live` is decided.
+template <bool kShard, bool kOptional>
+__device__ __forceinline__ void token_answer(long long t, int best, const long long* now, const long long* end, const long long* start, const int* user,
+                                             ShardMaps maps, int* o_row, unsigned char* o_live, int* o_user, long long* o_start, long long* o_end)
+{
+    const long long e = best >= 0 ? end[best] : INT64_MIN;
+    if (!kOptional || o_row) o_row[t] = !kShard ? best : best >= 0 ? maps.rows[best] : -1;
+    if (!kOptional || o_live) o_live[t] = (best >= 0 && e > *now) ? 1 : 0;
+    if (!kOptional || o_end) o_end[t] = e;
+    if (!kOptional || o_start) o_start[t] = best >= 0 ? start[best] : 0;
+    if (!kOptional || o_user) {
+        const int u = best >= 0 ? user[best] : -1;
+        o_user[t] = !kShard ? u : (u >= 0 && u < maps.n_users) ? maps.users[u] : -1;
+    }
+}
+
+// One lane per query key, one clock for all of them.  Outputs may be absent (NULL).
 __global__ __launch_bounds__(256) void k_token_lookup(const TokKey* __restrict__ query, long long k, const int* __restrict__ slot_row, unsigned log2_slots,
                                                       const TokKey* __restrict__ tok, long long covered, const long long* __restrict__ end,
                                                       const long long* __restrict__ start, const int* __restrict__ user, long long now,
@@ -91,12 +124,7 @@ __global__ __launch_bounds__(256) void k_token_lookup(const TokKey* __restrict__
     const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= k) return;
     const int best = token_probe(query[t], slot_row, log2_slots, tok, covered, status);
-    const long long e = best >= 0 ? end[best] : INT64_MIN;
-    if (o_row) o_row[t] = best;
-    if (o_live) o_live[t] = (best >= 0 && e > now) ? 1 : 0;
-    if (o_end) o_end[t] = e;
-    if (o_start) o_start[t] = best >= 0 ? start[best] : 0;
-    if (o_user) o_user[t] = best >= 0 ? user[best] : -1;
+    token_answer<false, true>(t, best, &now, end, start, user, ShardMaps{}, o_row, o_live, o_user, o_start, o_end);
 }
 
 // ---- the token column of a SHARDED context (pie_shard_token_*): keys are given by GLOBAL row; a shard keeps the keys of the rows
@@ -104,8 +132,8 @@ __global__ __launch_bounds__(256) void k_token_lookup(const TokKey* __restrict__
 
 // pie_shard_token_append: one lane per key of the staged chunk, which belongs to the global rows [g0, g0 + k).  The lane whose
 // global row the shard holds (local row r < n_local, inside the column's capacity) stores the key as one 16-byte store to tok[r]
-// and claims a slot for r from the key's home: the same relaxed agent-scope compare-and-swap as k_token_insert.  The key a probe
-// compares against is written by the lane that claims the slot, and every reader is a later kernel on the stream.
+// and claims a slot for r (token_claim).  The key a probe compares against is written by the lane that claims the slot, and
+// every reader is a later kernel on the stream.
 __global__ __launch_bounds__(256) void k_shard_token_place(const TokKey* __restrict__ staged, long long g0, long long k,
                                                            const int* __restrict__ rows_map, long long n_local, TokKey* __restrict__ tok,
                                                            long long cap, int* __restrict__ slot_row, unsigned log2_slots,
@@ -119,19 +147,11 @@ __global__ __launch_bounds__(256) void k_shard_token_place(const TokKey* __restr
     if (r >= n_local || r >= cap || (long long)rows_map[r] != g) return; // another shard's row, or one this shard's compactions dropped
     const TokKey key = staged[t];
     tok[r] = key;
-    const unsigned long long slots = 1ull << log2_slots, mask = slots - 1;
-    unsigned long long s = token_home(key.x, key.y, log2_slots);
-    unsigned long long step = 0;
-    for (; step < slots; ++step) {
-        int expected = -1;
-        if (__hip_atomic_compare_exchange_strong(&slot_row[s], &expected, (int)r, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;
-        s = (s + 1) & mask;
-    }
-    if (step == slots) status[0] = 1u;
+    token_claim(key, (int)r, slot_row, log2_slots, status);
 }
 
-// pie_shard_token_lookup: k_token_lookup with the row and the user answered as GLOBAL ids, read through the two maps (both reads
-// bounded: best < n_local, user < n_map; -1 otherwise).  `bound` = the rows the column can hold keys for.
+// pie_shard_token_lookup: k_token_lookup with the row (o_grow) and the user answered as GLOBAL ids; the LOCAL row, which only this
+// form gives beside the global one, goes to o_row.  `bound` = the rows the column can hold keys for.
 __global__ __launch_bounds__(256) void k_shard_token_lookup(const TokKey* __restrict__ query, long long k, const int* __restrict__ slot_row,
                                                             unsigned log2_slots, const TokKey* __restrict__ tok, long long bound,
                                                             const long long* __restrict__ end, const long long* __restrict__ start,
@@ -143,24 +163,17 @@ __global__ __launch_bounds__(256) void k_shard_token_lookup(const TokKey* __rest
 {
     const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= k) return;
-    int best = token_probe(query[t], slot_row, log2_slots, tok, bound < n_local ? bound : n_local, status);
-    const long long e = best >= 0 ? end[best] : INT64_MIN;
+    const int best = token_probe(query[t], slot_row, log2_slots, tok, bound < n_local ? bound : n_local, status);
     if (o_row) o_row[t] = best;
-    if (o_grow) o_grow[t] = best >= 0 ? rows_map[best] : -1;
-    if (o_live) o_live[t] = (best >= 0 && e > now) ? 1 : 0;
-    if (o_end) o_end[t] = e;
-    if (o_start) o_start[t] = best >= 0 ? start[best] : 0;
-    if (o_user) {
-        const int u = best >= 0 ? user[best] : -1;
-        o_user[t] = (u >= 0 && u < n_map) ? users_map[u] : -1;
-    }
+    token_answer<true, true>(t, best, &now, end, start, user, ShardMaps{rows_map, n_local, users_map, n_map}, o_grow, o_live, o_user, o_start, o_end);
 }
 
-// ---- lookups that run beside scans and batches (pie_token_lookup_begin / _finish): the same probe on a stream of the lookup's
-// own.  Each key carries its own clock (now[t]: the requests of a turn were stamped one by one) and `status` points at the status
-// words of the lookup's slot, so the report of one lookup is nobody else's.  One lane per key, a grid of ceil(k / 256) blocks that
-// come and go (no persistent grid, no LDS, no barrier): a turn's worth of keys is a handful of waves for a few microseconds, which
-// leaves the wave slots and the LDS of every CU to the batch lanes' kernels.
+// ---- lookups that run beside scans and batches (pie_token_lookup_begin / _finish): the same probe and the same answer on a
+// stream of the lookup's own.  Each key carries its own clock (now[t]: the requests of a turn were stamped one by one), every
+// output is written, and `status` points at the status words of the lookup's slot, so the report of one lookup is nobody else's.
+// One lane per key, a grid of ceil(k / 256) blocks that come and go (no persistent grid, no LDS, no barrier): a turn's worth of
+// keys is a handful of waves for a few microseconds, which leaves the wave slots and the LDS of every CU to the batch lanes'
+// kernels.
 __global__ __launch_bounds__(256) void k_token_lookup_now(const TokKey* __restrict__ query, const long long* __restrict__ now, long long k,
                                                           const int* __restrict__ slot_row, unsigned log2_slots, const TokKey* __restrict__ tok,
                                                           long long covered, const long long* __restrict__ end,
@@ -172,15 +185,10 @@ __global__ __launch_bounds__(256) void k_token_lookup_now(const TokKey* __restri
     const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= k) return;
     const int best = token_probe(query[t], slot_row, log2_slots, tok, covered, status);
-    const long long e = best >= 0 ? end[best] : INT64_MIN;
-    o_row[t] = best;
-    o_live[t] = (best >= 0 && e > now[t]) ? 1 : 0;
-    o_end[t] = e;
-    o_start[t] = best >= 0 ? start[best] : 0;
-    o_user[t] = best >= 0 ? user[best] : -1;
+    token_answer<false, false>(t, best, now + t, end, start, user, ShardMaps{}, o_row, o_live, o_user, o_start, o_end);
 }
 
-// the shard form: the row and the user answered as GLOBAL ids through the two maps, as k_shard_token_lookup reads them
+// the shard form: the row and the user answered as GLOBAL ids through the two maps
 __global__ __launch_bounds__(256) void k_shard_token_lookup_now(const TokKey* __restrict__ query, const long long* __restrict__ now, long long k,
                                                                 const int* __restrict__ slot_row, unsigned log2_slots,
                                                                 const TokKey* __restrict__ tok, long long bound, const long long* __restrict__ end,
@@ -194,13 +202,7 @@ __global__ __launch_bounds__(256) void k_shard_token_lookup_now(const TokKey* __
     const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= k) return;
     const int best = token_probe(query[t], slot_row, log2_slots, tok, bound < n_local ? bound : n_local, status);
-    const long long e = best >= 0 ? end[best] : INT64_MIN;
-    o_grow[t] = best >= 0 ? rows_map[best] : -1;
-    o_live[t] = (best >= 0 && e > now[t]) ? 1 : 0;
-    o_end[t] = e;
-    o_start[t] = best >= 0 ? start[best] : 0;
-    const int u = best >= 0 ? user[best] : -1;
-    o_user[t] = (u >= 0 && u < n_map) ? users_map[u] : -1;
+    token_answer<true, false>(t, best, now + t, end, start, user, ShardMaps{rows_map, n_local, users_map, n_map}, o_grow, o_live, o_user, o_start, o_end);
 }
 
 // ---- a whole turn (pie_token_turn / pie_shard_token_turn, include/pie_scan.h): an ordered list of get / touch / delete ops, each
@@ -248,19 +250,11 @@ __device__ __forceinline__ unsigned char turn_apply(const TurnOp& op, bool found
     return (found && e > op.now) ? 1 : 0;
 }
 
-// the two maps of a sharded context (kShard): rows and users are answered as GLOBAL ids, as k_shard_token_lookup answers them
-struct TurnMaps {
-    const int* rows;
-    long long n_local;
-    const int* users;
-    int n_users;
-};
-
 template <bool kShard>
 __global__ __launch_bounds__(256) void k_token_turn(const TurnOp* __restrict__ ops, const int* __restrict__ next, long long k,
                                                     const int* __restrict__ slot_row, unsigned log2_slots, const TokKey* __restrict__ tok,
                                                     long long bound, long long* __restrict__ end, const long long* __restrict__ start,
-                                                    const int* __restrict__ user, TurnMaps maps, lkey_t* __restrict__ key, long long key_base,
+                                                    const int* __restrict__ user, ShardMaps maps, lkey_t* __restrict__ key, long long key_base,
                                                     int key_shift, fkey_t* __restrict__ fkey, long long fkey_base, int fkey_shift, OrdMirror ord,
                                                     HotMirror hot, int* __restrict__ o_row, unsigned char* __restrict__ o_live,
                                                     int* __restrict__ o_user, long long* __restrict__ o_start, long long* __restrict__ o_end,
@@ -310,8 +304,7 @@ __global__ __launch_bounds__(256) void k_token_turn(const TurnOp* __restrict__ o
 //   1. stores the change earlier ops left in the old row's `end` (touch_row),
 //   2. writes the new row (append_row: four columns, both keys, the payload record, the hot mirror),
 //   3. stores tok[new row] as one 16-byte store,
-//   4. claims the first empty slot from the key's home — k_token_insert's relaxed agent-scope compare-and-swap and its
-//      `slots`-step bound; exhaustion raises status[0],
+//   4. claims the first empty slot from the key's home (token_claim: exhaustion raises status[0]),
 //   5. goes on with the new row's values in registers.  It does not probe again.
 // The hazard: a lane probing for ANOTHER key can meet a slot claimed in this same launch, whose tok[] entry is not written yet
 // (or not visible yet), and memory past the covered prefix can hold stale keys after a compaction.  So every probe of this kernel
@@ -343,7 +336,6 @@ __global__ __launch_bounds__(256) void k_session_turn(const TurnOp* __restrict__
     long long e0 = found ? end[row] : INT64_MIN, sv = found ? start[row] : 0;
     int uv = found ? user[row] : -1;
     long long e = e0, j = t;
-    const unsigned long long slots = 1ull << log2_slots, mask = slots - 1;
     for (long long step = 0; step < k; ++step) {
         int r = row;
         unsigned char live;
@@ -357,13 +349,7 @@ __global__ __launch_bounds__(256) void k_session_turn(const TurnOp* __restrict__
             uv = cuser[c];
             append_row(row, sv, e, uv, cdisc[c], start, end, user, disc, key, key_base, key_shift, fkey, fkey_base, fkey_shift, pay, hot);
             tok[row] = want;
-            unsigned long long s = token_home(want.x, want.y, log2_slots), tries = 0;
-            for (; tries < slots; ++tries) {
-                int expected = -1;
-                if (__hip_atomic_compare_exchange_strong(&slot_row[s], &expected, row, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;
-                s = (s + 1) & mask;
-            }
-            if (tries == slots) status[0] = 1u;
+            token_claim(want, row, slot_row, log2_slots, status);
             live = e > op.now ? 1 : 0;
         } else live = turn_apply(op, found, e, r);
         o_row[j] = r;

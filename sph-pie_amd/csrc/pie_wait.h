@@ -28,7 +28,7 @@ struct WaitPace {
 };
 // The paces were tuned against the measured finish latencies of their sites; they are not interchangeable.
 constexpr WaitPace kPaceSummary{0x3FFFF, 0, WaitPace::Pause};   // scan_finish, batch_finish, pie_expired_queue: a probe per ~1 ms of pauses
-constexpr WaitPace kPaceEvent{0, 65, WaitPace::Yield};          // wide_finish, token_lookup_landed: the event every spin
+constexpr WaitPace kPaceEvent{0, 65, WaitPace::Yield};          // wide_finish, flight_slot_landed: the event every spin
 constexpr WaitPace kPaceSideSummary{0xFF, 4096, WaitPace::Yield}; // expq_land
 constexpr WaitPace kPaceCommEvent{0, 256, WaitPace::Nap20us};   // wait_event (pie_comm.hip)
 constexpr double kNoGraceLimit = std::numeric_limits<double>::infinity(); // drained_grace_ms: a done probe never ends the wait

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from session_turn_model import CREATE, SessionTurnModel
 from table_model import ctx_with_env
 from token_model import END_NONE, check_layout
 from trace_replay import load_trace
@@ -170,6 +171,40 @@ def test_seeded_random_turns(oracle, gpu_ctx):
     for now in (NOW, NOW + 10 ** 8, NOW - 3 * 10 ** 8):
         for a, b in zip(ctx.scan(now, 0), oracle.scan(model.start, model.end, model.user, model.disc, U, now, 0, mask)):
             assert np.array_equal(a, b), "the derived keys fell out of step"
+
+
+def test_staging_growth(pie):
+    """The staging of the synchronous turns on a context of its own, whose first block (64 KiB) holds about 900 ops: a turn of 10
+    ops, one of 4 096 that outgrows the block, then a turn of 2 048 ops that logs 100 sessions in, whose create arrays move the
+    results inside the block."""
+    with pie.PieScan(0) as ctx:
+        cols = columns(61)
+        ctx.load_columns(*cols, U)
+        model = SessionTurnModel(*cols)
+        keys = random_keys(1061, N)
+        ctx.token_set(keys)
+        model.token_set(keys)
+        rng = np.random.default_rng(62)
+        hot_keys = keys[rng.choice(N, 8, replace=False)]
+        bytes_seen = []
+        for k in (10, 4096):
+            ops = random_ops(rng, k, keys, model, hot_keys)
+            same_turn(ctx.token_turn(ops), model.turn(ops), k)
+            columns_match(ctx, model)
+            bytes_seen.append(ctx.table_info()["token_bytes"])
+        assert bytes_seen[1] > bytes_seen[0], "the staging did not grow"
+        ops = random_ops(rng, 2048, keys, model, hot_keys)
+        at = rng.choice(2048, 100, replace=False)
+        ops["kind"][at] = CREATE
+        ops["tok"][at[10:]] = random_keys(63, 90)        # ten creates keep their key: some log in under a key of the table or a chain's
+        ops["new_end"][at] = ops["now"][at] + rng.integers(1, 6 * 10 ** 8, 100)
+        user, disc = rng.integers(0, U, 2048).astype(np.int32), rng.integers(0, D, 2048).astype(np.int32)
+        want = model.turn(ops, user, disc)
+        same_turn(ctx.session_turn(ops, user, disc, U), want, "2 048 ops, 100 creates")
+        assert np.array_equal(want["row"][np.sort(at)], N + np.arange(100)) and ctx.n == N + 100
+        columns_match(ctx, model)
+        got, back = ctx.token_lookup(keys, NOW), model.lookup(keys, NOW)
+        assert np.array_equal(got["row"], back["row"]) and np.array_equal(got["end"], back["end"])
 
 
 def test_probe_runs_that_wrap(pie, gpu_ctx):

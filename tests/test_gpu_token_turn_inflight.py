@@ -214,6 +214,46 @@ def test_four_turns_back_to_back(pie, oracle):
         columns_match(ctx, model)
 
 
+def mixed_turn(model, keys, seed, k):
+    """k get / touch / delete ops, each with a clock of its own on both sides of the rows' ends: about 20 % name keys the table does
+    not hold, about 10 % name the token of an earlier op of the turn (chains form)"""
+    rng = np.random.default_rng(seed)
+    tok = keys[rng.choice(keys.shape[0], k, replace=False)]
+    unknown = rng.random(k) < 0.2
+    tok[unknown] = random_keys(seed + 500, int(unknown.sum()))
+    for i in np.nonzero(rng.random(k) < 0.1)[0][1:]:
+        tok[i] = tok[rng.integers(0, i)]
+    clock = int(np.median(model.end[model.end != END_NONE]))
+    now = clock + rng.integers(-40 * DAY, 40 * DAY, k)
+    kind = rng.choice([GET, TOUCH, DELETE], k, p=[0.5, 0.3, 0.2])
+    return make_ops(tok, now, kind, np.where(kind == TOUCH, now + rng.integers(1, 40 * DAY, k), 0))
+
+
+def test_turn_staging_growth(pie, oracle):
+    ctx, model, keys = new_ctx(pie, oracle, 8)
+    with ctx:
+        for i in range(4):                           # every slot has been used: each owns a first block (256 KiB, about 3 700 ops)
+            ctx.token_turn_begin(make_ops(keys[i:i + 1], oracle.T0_MS, GET))
+            ctx.token_turn_finish()
+        bytes_before = ctx.table_info()["token_bytes"]
+        qs = queries(oracle, 0, 8)
+        before = answers(oracle, model, qs)
+        ctx.scan_batch_begin(qs)
+        small, big = mixed_turn(model, keys, 80, 30), mixed_turn(model, keys, 81, 8192)
+        names = np.unique(big["tok"], axis=0).shape[0]
+        assert 0.05 * 8192 < 8192 - names < 0.15 * 8192, "about a tenth of the ops repeat a token"
+        ctx.token_turn_begin(small)
+        ctx.token_turn_begin(big)                    # outgrows its slot's block while the small turn is unfinished
+        want_small, want_big = model.turn(small), model.turn(big)
+        assert 0.15 * 8192 < np.count_nonzero(~want_big["found"]) < 0.25 * 8192 and 0 < want_big["live"].sum() < names
+        assert all(np.any((big["kind"] == kind) & (want_big["row"] >= 0)) for kind in (GET, TOUCH, DELETE))
+        same_turn(ctx.token_turn_finish(), want_small, "the small turn")
+        same_turn(ctx.token_turn_finish(), want_big, "8 192 ops")
+        check_finished_batch(ctx, list(ctx.scan_batch_finish()), before, False, "the batch begun before the turns")
+        columns_match(ctx, model)
+        assert ctx.table_info()["token_bytes"] > bytes_before, "no slot grew"
+
+
 def test_order_against_the_side_passes(pie, oracle):
     ctx, model, keys = new_ctx(pie, oracle, 6)
     with ctx:
