@@ -81,6 +81,14 @@ def add_months(ts, months, tz_offset_ms=0):
 
 
 # ------------------------------------------------------------------------------------------------ the model
+def tombstone(end, sel):
+    """The one rule of deleteSessionsForUser, prune and retention: the selected rows that are not tombstones yet become
+    tombstones, in place -> those rows, ascending.  tests/turn_model.py deletes a user through it too."""
+    rows = np.nonzero(sel & (end != INT64_MIN))[0].astype(np.int32)
+    end[rows] = INT64_MIN
+    return rows
+
+
 class TableModel:
     """start / end / user / disc and the user and discipline counts; every table operation of include/pie_scan.h restated."""
 
@@ -123,9 +131,7 @@ class TableModel:
         self.end[rows[last]] = new_end[last]
 
     def _tombstone(self, sel):
-        rows = np.nonzero(sel & (self.end != INT64_MIN))[0].astype(np.int32)
-        self.end[rows] = INT64_MIN
-        return rows
+        return tombstone(self.end, sel)
 
     def delete_user(self, u):
         if not 0 <= u < self.U:

@@ -7,6 +7,9 @@ answered each call is recorded.  test_model_sequences_reached_every_path then re
 test_liveness_edges_on_a_lattice / test_cutoff_and_tie_edges: hand-made tables whose values sit on the bin edges of both
 liveness keys, on `start == cutoff` and on long runs of equal starts, swept value by value.
 
+These chains carry no token column: the session-store half of the ABI (tokens, turns, in-flight forms, pie_delete_users,
+compaction with keys) has a chain of its own, tests/test_gpu_store_chain.py over tests/store_chain.py.
+
 No expected value comes from another GPU context: the model is the only source (index on against off is compared in
 test_gpu_hot_index.py)."""
 import numpy as np

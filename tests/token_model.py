@@ -49,6 +49,9 @@ class TokenModel:
     def lookup(self, keys, now):
         row = self.rows_of(keys)
         found = row >= 0
+        if self.end.size == 0:                       # no row yet: nothing is found, and there is no row 0 to stand in
+            z = np.zeros(row.size, np.int64)
+            return {"row": row, "live": z.astype(np.uint8), "user": z.astype(np.int32), "start": z, "end": z.copy(), "found": found}
         safe = np.where(found, row, 0)
         return {"row": row, "live": (found & (self.end[safe] > now)).astype(np.uint8), "user": self.user[safe], "start": self.start[safe],
                 "end": self.end[safe], "found": found}

@@ -12,6 +12,7 @@ import hashlib
 
 import numpy as np
 
+from table_model import tombstone
 from token_model import END_NONE, TokenModel, key_of
 
 GET, TOUCH, DELETE = 0, 1, 2
@@ -55,7 +56,8 @@ class TurnModel(TokenModel):
         return out
 
     def delete_user(self, u):
-        self.end[self.user == u] = END_NONE
+        """-> the rows tombstoned, ascending (tests/table_model.py's rule; an id no row carries matches nothing)"""
+        return tombstone(self.end, self.user == u)
 
     def purge(self, now):
         """purgeExpiredSessions: every row with end <= now that is not a tombstone -> tombstone; -> those rows"""
