@@ -673,8 +673,9 @@ int pie_token_turn(pie_ctx *ctx, const pie_turn_op *ops, size_t k, int32_t *row_
                    int64_t *start_out, int64_t *end_out);
 
 /* ---- a turn that LOGS IN: createSession (server/sessionStore.js:12-19) joins get / touch / delete as a fourth kind, and the
- * whole ordered list is still one upload, one kernel, one download and one wait.  Only pie_session_turn takes the kind:
- * pie_token_turn, pie_token_turn_begin, the shard forms and the communicator's keep refusing it with PIE_E_INVAL.
+ * whole ordered list is still one upload, one kernel, one download and one wait.  Only pie_session_turn and its shard and
+ * communicator forms (pie_shard_session_turn, pie_comm_session_turn) take the kind: pie_token_turn, pie_token_turn_begin,
+ * pie_shard_token_turn, pie_shard_token_turn_begin and pie_comm_token_turn keep refusing it with PIE_E_INVAL.
  * GET, TOUCH and DELETE follow the table above exactly.  A CREATE op carries the key `tok`, start = now, end = new_end, and
  * user[i] / disc[i] (the two arrays are read at CREATE ops only; both may be NULL in a turn without one).
  *     op      condition   row_out        live_out        end_out    start_out  user_out   effect
@@ -747,6 +748,50 @@ int pie_shard_token_set_end(pie_ctx *ctx, const uint64_t *tok, const int64_t *ne
  * PIE_END_NONE for every op of its chain, and the chain changes nothing. */
 int pie_shard_token_turn(pie_ctx *ctx, const pie_turn_op *ops, size_t k, int32_t *row_global_out, uint8_t *live_out,
                          int32_t *user_global_out, int64_t *start_out, int64_t *end_out);
+/* pie_session_turn on this shard of a sharded table: the turn that LOGS IN, given to every shard with the same arrays (GLOBAL user
+ * ids in user_global[], read at CREATE ops only; n_users_global may only grow).  GET, TOUCH and DELETE answer as
+ * pie_shard_token_turn.  The j-th CREATE of the array, counting from 0, becomes GLOBAL row N_g + j on every shard; the shard with
+ * pie_shard_of(user, world) == rank keeps the row, as LOCAL row local rows + (the CREATEs it kept before that one).  All of this
+ * is host arithmetic (pie_shard_session_turn_plan); there is no device atomic and nothing is exchanged.
+ *     op      on the shard that      row_global_out   live_out        end_out       start_out  user_global_out
+ *     CREATE  keeps the row          N_g + j          new_end > now   new_end       now        user_global[i]
+ *     CREATE  does not keep it       -1               0               PIE_END_NONE  0          -1
+ * On the shard that keeps it, later ops of the key act on the new row, and a change earlier ops left in the old row's `end` is
+ * stored first (pie_session_turn's rule).  On a shard that does not, the chain goes on with whatever row the key had there: the
+ * rule for a key held by two shards above.
+ * The defining equivalence, per shard: every output, the table, the row map, the user map, the token column (covered_g,
+ * covered_l, keys, slots), both key columns, the payload, the hot index and later scans equal those of the same ops made one by
+ * one on that shard, where a CREATE is pie_shard_append_rows of one row (n_users_global) followed by pie_shard_token_append of its
+ * key and every other op is a pie_shard_token_turn of one op.  Afterwards N_g and covered_g have grown by the number of CREATEs
+ * on every shard alike.
+ * Room, with the shard's own sizes: local rows + kept CREATEs against the capacity of the columns; its users, after the new ones
+ * it owns, against the capacity of the user arrays (both maps grow with the table); a longer token column; the slots
+ * (local rows + kept > slots / 2) rebuilt into pie_token_slots_for of that count.  Lookups begun in flight land first; the call
+ * may wait there.  The shard's new users go behind the device user map in stream order, ahead of the kernel.  After that the
+ * turn is one upload, one kernel, one download and one wait bounded by PIE_WAIT_DEADLINE_MS — also on a shard that keeps no
+ * CREATE and holds none of the keys, which still runs its chains.  With k = 0, or no CREATE and no new user, the call is
+ * pie_shard_token_turn; a turn without a CREATE that grows n_users_global is pie_shard_append_rows(k = 0) followed by the turn.
+ * Ordered run: a turn in which the shard keeps a CREATE drops its valid ordered run; any other turn keeps it in step.
+ * PIE_E_STATE: a context that is not sharded, or whose row map does not cover its rows; no table; no column; a scan or batch in
+ * flight; a turn begun and not finished; a CREATE while covered_g < N_g.  PIE_E_INVAL: NULL context; NULL ops with k > 0;
+ * k >= 2^31; a kind outside 0..3; reserved != 0; n_users_global below the table's; a CREATE with NULL user_global or disc, or with
+ * a user outside [0, n_users_global) (checked on the host before anything is staged); N_g + CREATEs reaching 2^31 - 1.  On any
+ * error nothing is changed.  Every output pointer may be NULL.  pie_session_turn keeps refusing sharded contexts, and
+ * pie_shard_token_turn, pie_shard_token_turn_begin and pie_comm_token_turn keep refusing the kind. */
+int pie_shard_session_turn(pie_ctx *ctx, const pie_turn_op *ops, size_t k, const int32_t *user_global /* [k] */,
+                           const int32_t *disc /* [k] */, int32_t n_users_global, int32_t *row_global_out, uint8_t *live_out,
+                           int32_t *user_global_out, int64_t *start_out, int64_t *end_out);
+/* host only, no context, no GPU: pie_token_turn_plan's chains plus the rows every CREATE gets on shard `rank` of `world`, on a
+ * table of rows_global0 rows of which the shard holds rows_local0: new_row_global_out[i] = rows_global0 + j for the j-th CREATE,
+ * new_row_local_out[i] = rows_local0 + (the CREATEs before it that the shard keeps) when pie_shard_of(user_global[i], world) ==
+ * rank, -1 otherwise and for every other op.  *n_create_out = the CREATEs, *n_kept_out = those the shard keeps (either may be
+ * NULL).  PIE_E_INVAL: a NULL array with k > 0 (user_global only when there is a CREATE); k >= 2^31; a negative row count or
+ * rows_local0 > rows_global0; rank outside [0, world); a kind outside 0..3 or reserved != 0; rows_global0 + CREATEs reaching
+ * 2^31 - 1.  Nothing is written then. */
+int pie_shard_session_turn_plan(const pie_turn_op *ops, size_t k, const int32_t *user_global /* [k] */, int64_t rows_global0,
+                                int64_t rows_local0, int32_t rank, int32_t world, int32_t *next_out /* [k] */,
+                                uint8_t *head_out /* [k] */, int32_t *new_row_global_out /* [k] */,
+                                int32_t *new_row_local_out /* [k] */, size_t *n_create_out, size_t *n_kept_out);
 /* tests and tools: covered_g, covered_l, slots; slot_row_out[cap] (local rows; PIE_E_CAPACITY if cap < slots);
  * tok_out[covered_l][2]; any may be NULL.  Waits. */
 int pie_shard_token_layout(pie_ctx *ctx, size_t *covered_global_out, size_t *covered_local_out, size_t *slots_out,
@@ -1012,6 +1057,17 @@ int pie_comm_token_set_end(pie_comm *comm, const uint64_t *tok, const int64_t *n
  * are uncollected; PIE_E_INVAL as pie_token_turn. */
 int pie_comm_token_turn(pie_comm *comm, const pie_turn_op *ops, size_t k, int32_t *row_out, uint8_t *live_out,
                         int32_t *owner_rank_out, int32_t *user_out, int64_t *start_out, int64_t *end_out);
+/* pie_session_turn across the local shards: every local shard is given the same turn (pie_shard_session_turn), user[] and n_users
+ * in GLOBAL ids.  All local shards are checked before any is changed, room is made on all of them before any is queued, and all
+ * are queued before any is waited for.  Per op the answer comes from the shard with the largest global row (pie_comm_token_turn's
+ * merge), owner_rank_out likewise; a CREATE is kept by one shard, which answers it.  With every key held by one shard this is the
+ * unsharded pie_session_turn's result; afterwards the table is N_g + CREATEs rows long on every shard.  In place of the three
+ * calls a login cost before (pie_comm_append_rows of one row, pie_comm_token_append of its key, pie_comm_token_turn of the rest).
+ * PIE_E_STATE while pipelined steps of either kind are uncollected, when the local shards disagree on N_g, and as
+ * pie_shard_session_turn; PIE_E_INVAL as pie_shard_session_turn.  An error changes no shard. */
+int pie_comm_session_turn(pie_comm *comm, const pie_turn_op *ops, size_t k, const int32_t *user /* [k] */, const int32_t *disc /* [k] */,
+                          int32_t n_users, int32_t *row_out, uint8_t *live_out, int32_t *owner_rank_out, int32_t *user_out,
+                          int64_t *start_out, int64_t *end_out);
 
 /* ---- the pipelined exchange: ONE union message per step (layout: pie_scan_batch_begin_union), written by each shard's own
  * batch kernels; the exchange of step i runs on a side stream while the shards scan steps i+1, i+2.  Order of calls:

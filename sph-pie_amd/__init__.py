@@ -7,7 +7,7 @@ BASELINE.json's north_star; nothing else of sph-pie is rebuilt here).
   shard.py   user-hash sharding + all-gather of per-user feeds (torch.distributed; nccl == RCCL on ROCm)
 """
 from .binding import (ABI_SYMBOLS, PIE_BATCH_MAX, PIE_WIDE_MAX, PIE_END_NONE, PIE_GEN_CLUSTERED, PIE_GEN_INTERVAL, PIE_GEN_TIME_ORDERED, PieComm, PieError, PieScan,
-                      batch_mask_codes, delete_users_plan, hot_order_key, hot_slot_bits, load_library, set_end_last_writers, shard_of, shard_route, split_wide_message, token_homes, token_key, token_slots_for, token_turn_plan, session_turn_plan, turn_ops, tz_table, TURN_OP, TURN_GET, TURN_TOUCH, TURN_DELETE, TURN_CREATE)
+                      batch_mask_codes, delete_users_plan, hot_order_key, hot_slot_bits, load_library, set_end_last_writers, shard_of, shard_route, split_wide_message, token_homes, token_key, token_slots_for, token_turn_plan, session_turn_plan, shard_session_turn_plan, turn_ops, tz_table, TURN_OP, TURN_GET, TURN_TOUCH, TURN_DELETE, TURN_CREATE)
 from .build import UBENCH_LIB, build_all, build_hip, build_napi, build_oracle, build_ubench
 
 
@@ -21,4 +21,4 @@ def zipf_cdf(n_users, exponent=1.1):
     return np.maximum.accumulate(thr)
 
 __all__ = ["ABI_SYMBOLS", "PIE_BATCH_MAX", "PIE_WIDE_MAX", "PIE_END_NONE", "PIE_GEN_CLUSTERED", "PIE_GEN_INTERVAL", "PIE_GEN_TIME_ORDERED", "PieComm", "PieError", "PieScan",
-           "batch_mask_codes", "delete_users_plan", "hot_order_key", "hot_slot_bits", "load_library", "set_end_last_writers", "shard_of", "shard_route", "split_wide_message", "token_homes", "token_key", "token_slots_for", "token_turn_plan", "session_turn_plan", "turn_ops", "TURN_OP", "TURN_GET", "TURN_TOUCH", "TURN_DELETE", "TURN_CREATE", "tz_table", "zipf_cdf", "build_all", "build_hip", "build_napi", "build_oracle", "build_ubench", "UBENCH_LIB"]
+           "batch_mask_codes", "delete_users_plan", "hot_order_key", "hot_slot_bits", "load_library", "set_end_last_writers", "shard_of", "shard_route", "split_wide_message", "token_homes", "token_key", "token_slots_for", "token_turn_plan", "session_turn_plan", "shard_session_turn_plan", "turn_ops", "TURN_OP", "TURN_GET", "TURN_TOUCH", "TURN_DELETE", "TURN_CREATE", "tz_table", "zipf_cdf", "build_all", "build_hip", "build_napi", "build_oracle", "build_ubench", "UBENCH_LIB"]

@@ -216,6 +216,9 @@ _SIGS = [
     ("pie_shard_token_turn", C.c_int, [_P, _P, C.c_size_t, _P, _P, _P, _P, _P]),
     ("pie_session_turn", C.c_int, [_P, _P, C.c_size_t, _P, _P, C.c_int32, _P, _P, _P, _P, _P]),
     ("pie_session_turn_plan", C.c_int, [_P, C.c_size_t, C.c_int64, _P, _P, _P, C.POINTER(C.c_size_t)]),
+    ("pie_shard_session_turn", C.c_int, [_P, _P, C.c_size_t, _P, _P, C.c_int32, _P, _P, _P, _P, _P]),
+    ("pie_shard_session_turn_plan", C.c_int, [_P, C.c_size_t, _P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P,
+                                              C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     ("pie_shard_token_set",C.c_int, [_P, _P, C.c_size_t]),
     ("pie_shard_token_append", C.c_int, [_P, _P, C.c_size_t]),
     ("pie_shard_token_lookup", C.c_int, [_P, _P, C.c_size_t, C.c_int64, _P, _P, _P, _P, _P]),
@@ -242,6 +245,7 @@ _SIGS = [
     ("pie_comm_token_lookup", C.c_int, [_P, _P, C.c_size_t, C.c_int64, _P, _P, _P, _P, _P, _P]),
     ("pie_comm_token_set_end", C.c_int, [_P, _P, _P, C.c_size_t, C.c_int64, _P]),
     ("pie_comm_token_turn", C.c_int, [_P, _P, C.c_size_t, _P, _P, _P, _P, _P, _P]),
+    ("pie_comm_session_turn", C.c_int, [_P, _P, C.c_size_t, _P, _P, C.c_int32, _P, _P, _P, _P, _P, _P]),
     ("pie_comm_token_lookup_begin", C.c_int, [_P, _P, _P, C.c_size_t]),
     ("pie_comm_token_lookup_finish", C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("pie_comm_token_lookup_room", C.c_int, [_P]),
@@ -1134,6 +1138,37 @@ class PieScan:
         self._check(self._lib.pie_shard_token_set_end(self._ctx, _ptr(keys), _ptr(new_end), keys.shape[0], int(now), _ptr(rows)))
         return rows
 
+    def shard_session_turn(self, ops, user_global=None, disc=None, n_users_global=None, local_size=None):
+        """A turn that may log in, on this shard (pie_shard_session_turn): every shard is given the same ops, users as GLOBAL
+        ids (one per op, read at creates only; both arrays may be None in a turn without one).  n_users_global: the table's
+        user count after the turn (default: unchanged).  local_size as in shard_append_rows -> the dict shard_token_turn
+        returns; a create another shard keeps answers row -1 / live 0 / end PIE_END_NONE / user -1."""
+        ops = turn_ops(ops)
+        k = ops.shape[0]
+        user_global = None if user_global is None else _col(user_global, np.int32)
+        disc = None if disc is None else _col(disc, np.int32)
+        for a in (user_global, disc):
+            if a is not None and a.shape != (k,):
+                raise ValueError("one user and one disc per op")
+        if n_users_global is None:
+            n_users_global = self.shard_info()["users_global"]
+        out = {"row": np.empty(k, np.int32), "live": np.empty(k, np.uint8), "user": np.empty(k, np.int32),
+               "start": np.empty(k, np.int64), "end": np.empty(k, np.int64)}
+        self._check(self._lib.pie_shard_session_turn(self._ctx, _ptr(ops), k, _ptr(user_global), _ptr(disc), int(n_users_global),
+                                                     _ptr(out["row"]), _ptr(out["live"]), _ptr(out["user"]), _ptr(out["start"]),
+                                                     _ptr(out["end"])))
+        if local_size is not None:
+            self.n, self.n_users = int(local_size[0]), int(local_size[1])
+        else:
+            ti = self.table_info()
+            self.n, self.n_users = int(ti["rows"]), int(ti["users"])
+        return out
+
+    @staticmethod
+    def shard_session_turn_plan(ops, user_global, rows_global0, rows_local0, rank, world):
+        """Host only: see the module's shard_session_turn_plan."""
+        return shard_session_turn_plan(ops, user_global, rows_global0, rows_local0, rank, world)
+
     def shard_token_turn(self, ops):
         """token_turn on this shard's column: rows and users as GLOBAL ids; a key the shard does not hold answers -1 / 0."""
         return self._token_turn(self._lib.pie_shard_token_turn, ops)
@@ -1579,6 +1614,25 @@ class PieComm:
                                                   _ptr(out["user"]), _ptr(out["start"]), _ptr(out["end"])))
         return out
 
+    def session_turn(self, ops, user=None, disc=None, n_users=None):
+        """A turn that may log in, on every local shard, merged per op (pie_comm_session_turn): user / disc one entry per op in
+        GLOBAL ids (read at creates only), n_users the table's user count after the turn (default: unchanged) -> the dict
+        token_turn returns (owner included)."""
+        ops = turn_ops(ops)
+        k = ops.shape[0]
+        user = None if user is None else _col(user, np.int32)
+        disc = None if disc is None else _col(disc, np.int32)
+        for a in (user, disc):
+            if a is not None and a.shape != (k,):
+                raise ValueError("one user and one disc per op")
+        n_users = self.table_size()[1] if n_users is None else int(n_users)
+        out = {"row": np.empty(k, np.int32), "live": np.empty(k, np.uint8), "user": np.empty(k, np.int32),
+               "start": np.empty(k, np.int64), "end": np.empty(k, np.int64), "owner": np.empty(k, np.int32)}
+        self._check(self._lib.pie_comm_session_turn(self._c, _ptr(ops), k, _ptr(user), _ptr(disc), n_users, _ptr(out["row"]),
+                                                    _ptr(out["live"]), _ptr(out["owner"]), _ptr(out["user"]), _ptr(out["start"]),
+                                                    _ptr(out["end"])))
+        return out
+
     # ---- token lookups and the expired queue while steps are in flight (pie_comm_token_lookup_begin ..., pie_comm_expired_queue_begin ...)
     def token_lookup_begin(self, keys, now):
         """Queue getSession for every key on every local shard (now: one clock for all, or one per key), whatever steps are in
@@ -1703,7 +1757,7 @@ def token_key(token):
 
 # pie_turn_op (include/pie_scan.h): one op of a turn, 40 bytes without padding
 TURN_GET, TURN_TOUCH, TURN_DELETE = 0, 1, 2
-TURN_CREATE = 3  # pie_session_turn only
+TURN_CREATE = 3  # pie_session_turn, pie_shard_session_turn and pie_comm_session_turn only
 TURN_OP = np.dtype([("tok", "<u8", (2,)), ("now", "<i8"), ("new_end", "<i8"), ("kind", "<i4"), ("reserved", "<i4")])
 assert TURN_OP.itemsize == 40
 
@@ -1746,6 +1800,25 @@ def session_turn_plan(ops, row0):
     if rc != 0:
         raise PieError(rc, "pie_session_turn_plan: bad argument")
     return nxt, head, new_row, int(n_create.value)
+
+
+def shard_session_turn_plan(ops, user_global, rows_global0, rows_local0, rank, world):
+    """Host only (pie_shard_session_turn_plan): token_turn_plan's (next, head), then new_row_global int32[k] — rows_global0 + j for
+    the j-th TURN_CREATE op — and new_row_local int32[k] — rows_local0 + (the creates before it that rank `rank` of `world` keeps)
+    for a create whose user hashes to the rank — both -1 elsewhere, then the number of creates and of kept creates."""
+    ops = turn_ops(ops)
+    k = ops.shape[0]
+    user_global = None if user_global is None else _col(user_global, np.int32)
+    if user_global is not None and user_global.shape != (k,):
+        raise ValueError("one user per op")
+    nxt, head = np.empty(k, np.int32), np.empty(k, np.uint8)
+    row_g, row_l = np.empty(k, np.int32), np.empty(k, np.int32)
+    n_create, n_kept = C.c_size_t(0), C.c_size_t(0)
+    rc = load_library().pie_shard_session_turn_plan(_ptr(ops), k, _ptr(user_global), int(rows_global0), int(rows_local0), int(rank), int(world),
+                                                    _ptr(nxt), _ptr(head), _ptr(row_g), _ptr(row_l), C.byref(n_create), C.byref(n_kept))
+    if rc != 0:
+        raise PieError(rc, "pie_shard_session_turn_plan: bad argument")
+    return nxt, head, row_g, row_l, int(n_create.value), int(n_kept.value)
 
 
 def token_slots_for(covered):

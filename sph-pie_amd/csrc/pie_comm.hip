@@ -37,6 +37,11 @@ int shard_token_turn_check(pie_ctx* c, const pie_turn_op* ops, size_t k);
 int shard_token_turn_queue(pie_ctx* c, const pie_turn_op* ops, size_t k);
 int shard_token_turn_wait(pie_ctx* c, size_t k, int32_t* row_global_out, uint8_t* live_out, int32_t* user_global_out, int64_t* start_out,
                           int64_t* end_out);
+int shard_session_turn_check(pie_ctx* c, const pie_turn_op* ops, size_t k, const int32_t* user_global, const int32_t* disc, int32_t n_users_global);
+int shard_session_turn_room(pie_ctx* c, const pie_turn_op* ops, size_t k, const int32_t* user_global, int32_t n_users_global);
+int shard_session_turn_queue(pie_ctx* c, const pie_turn_op* ops, size_t k, const int32_t* user_global, const int32_t* disc, int32_t n_users_global);
+int shard_session_turn_wait(pie_ctx* c, size_t k, int32_t* row_global_out, uint8_t* live_out, int32_t* user_global_out, int64_t* start_out,
+                            int64_t* end_out);
 // ... and pie_shard_delete_users in three pieces: the check, the run that leaves the ascending list of global rows on the device,
 // the copy of that list
 int shard_check_delete_users(pie_ctx* c, const int32_t* users_global, size_t k);
@@ -1233,6 +1238,64 @@ int pie_comm_token_turn(pie_comm* c, const pie_turn_op* ops, size_t k, int32_t* 
             best[j] = row[j];
             if (live_out) live_out[j] = live[j];
             if (user_out) user_out[j] = user[j];
+            if (start_out) start_out[j] = start[j];
+            if (end_out) end_out[j] = end[j];
+            if (owner_rank_out) owner_rank_out[j] = c->rank_of[i];
+        }
+    }
+    if (first_rc) PIE_CCTX(c, first_bad, first_rc);
+    if (row_out) memcpy(row_out, best.data(), k * 4);
+    return PIE_OK;
+}
+
+// The turn that logs in, on every local shard (pie_shard_session_turn's phases): all checked before any is changed, room made on
+// all before any is queued, all queued before any is waited for, then pie_comm_token_turn's merge per op.  A create is kept by
+// one shard and answered -1 by the others, so the merge hands out the keeper's answer.
+int pie_comm_session_turn(pie_comm* c, const pie_turn_op* ops, size_t k, const int32_t* user, const int32_t* disc, int32_t n_users,
+                          int32_t* row_out, uint8_t* live_out, int32_t* owner_rank_out, int32_t* user_out, int64_t* start_out, int64_t* end_out)
+{
+    if (!c) return PIE_E_INVAL;
+    int rc = mutate_ready(c, nullptr, nullptr);
+    if (rc) return rc;
+    for (int i = 0; i < c->n_local; ++i) PIE_CCTX(c, i, pie_internal::shard_session_turn_check(c->ctx[i], ops, k, user, disc, n_users));
+    std::vector<int32_t> best, row, usr;
+    std::vector<uint8_t> live;
+    std::vector<int64_t> start, end;
+    try {
+        best.assign(k, -1);
+        row.resize(k);
+        usr.resize(k);
+        live.resize(k);
+        start.resize(k);
+        end.resize(k);
+    } catch (...) {
+        return cfail(c, PIE_E_NOMEM, "no memory for %zu answers", k);
+    }
+    for (int i = 0; i < c->n_local; ++i) PIE_CCTX(c, i, pie_internal::shard_session_turn_room(c->ctx[i], ops, k, user, n_users));
+    int queued = 0;
+    for (; queued < c->n_local; ++queued)
+        if ((rc = pie_internal::shard_session_turn_queue(c->ctx[queued], ops, k, user, disc, n_users)) != PIE_OK) break;
+    if (rc) { // what was queued is waited for all the same: nothing is left writing a staging block
+        const int bad = queued;
+        for (int i = 0; i < queued; ++i) (void)pie_internal::shard_session_turn_wait(c->ctx[i], k, nullptr, nullptr, nullptr, nullptr, nullptr);
+        PIE_CCTX(c, bad, rc);
+    }
+    if (k == 0) return PIE_OK;
+    if (live_out) memset(live_out, 0, k);
+    if (owner_rank_out) for (size_t j = 0; j < k; ++j) owner_rank_out[j] = -1;
+    if (end_out) for (size_t j = 0; j < k; ++j) end_out[j] = PIE_END_NONE;
+    int first_rc = PIE_OK, first_bad = -1;
+    for (int i = 0; i < c->n_local; ++i) {
+        rc = pie_internal::shard_session_turn_wait(c->ctx[i], k, row.data(), live.data(), usr.data(), start.data(), end.data());
+        if (rc) { // keep waiting for the others
+            if (first_rc == PIE_OK) { first_rc = rc; first_bad = i; }
+            continue;
+        }
+        for (size_t j = 0; j < k; ++j) {
+            if (row[j] <= best[j]) continue;
+            best[j] = row[j];
+            if (live_out) live_out[j] = live[j];
+            if (user_out) user_out[j] = usr[j];
             if (start_out) start_out[j] = start[j];
             if (end_out) end_out[j] = end[j];
             if (owner_rank_out) owner_rank_out[j] = c->rank_of[i];

@@ -107,6 +107,7 @@
     X(int, pie_token_turn, (pie_ctx *, const pie_turn_op *, size_t, int32_t *, uint8_t *, int32_t *, int64_t *, int64_t *)) \
     X(int, pie_session_turn, (pie_ctx *, const pie_turn_op *, size_t, const int32_t *, const int32_t *, int32_t, int32_t *, uint8_t *, int32_t *, int64_t *, int64_t *)) \
     X(int, pie_comm_token_turn, (pie_comm *, const pie_turn_op *, size_t, int32_t *, uint8_t *, int32_t *, int32_t *, int64_t *, int64_t *)) \
+    X(int, pie_comm_session_turn, (pie_comm *, const pie_turn_op *, size_t, const int32_t *, const int32_t *, int32_t, int32_t *, uint8_t *, int32_t *, int32_t *, int64_t *, int64_t *)) \
     X(int, pie_token_set_end, (pie_ctx *, const uint64_t *, const int64_t *, size_t, int64_t, int32_t *))                \
     X(int, pie_token_lookup_begin, (pie_ctx *, const uint64_t *, const int64_t *, size_t))                           \
     X(int, pie_token_lookup_finish, (pie_ctx *, int32_t *, uint8_t *, int32_t *, int64_t *, int64_t *, size_t, size_t *)) \
@@ -2847,6 +2848,46 @@ static napi_value fn_comm_token_turn(napi_env env, napi_callback_info info)
     return out;
 }
 
+/* commSessionTurn(comm, keys, nows, newEnds, kinds, users Int32Array, discs Int32Array, nUsers) -> commTokenTurn's object; kind 3
+ * creates a session of users[i] / discs[i] (GLOBAL ids, read at creates only) on the shard that owns the user (pie_comm_session_turn) */
+static napi_value fn_comm_session_turn(napi_env env, napi_callback_info info)
+{
+    static const char usage[] = "commSessionTurn(comm, BigUint64Array keys, BigInt64Array nows, BigInt64Array newEnds, Uint8Array kinds, Int32Array users, Int32Array discs, nUsers)";
+    ARGS(8)
+    comm_box *cbx = get_comm_box(env, argv[0]);
+    if (!cbx) return NULL;
+    size_t k = 0, ku = 0, kd = 0;
+    int32_t n_users = 0;
+    int32_t *users = typed(env, argv[5], napi_int32_array, &ku);
+    int32_t *discs = typed(env, argv[6], napi_int32_array, &kd);
+    if (!users || !discs || napi_get_value_int32(env, argv[7], &n_users) != napi_ok) {
+        napi_throw_type_error(env, NULL, usage);
+        return NULL;
+    }
+    pie_turn_op *ops = turn_ops(env, argv + 1, usage, &k);
+    if (!ops) return NULL;
+    napi_value out;
+    if (ku != k || kd != k || napi_create_object(env, &out) != napi_ok) {
+        free(ops);
+        napi_throw_type_error(env, NULL, usage);
+        return NULL;
+    }
+    int32_t *row = token_out(env, out, "row", napi_int32_array, 4, k);
+    uint8_t *live = token_out(env, out, "live", napi_uint8_array, 1, k);
+    int32_t *user = token_out(env, out, "user", napi_int32_array, 4, k);
+    int64_t *start = token_out(env, out, "start", napi_bigint64_array, 8, k);
+    int64_t *end = token_out(env, out, "end", napi_bigint64_array, 8, k);
+    int32_t *owner = token_out(env, out, "owner", napi_int32_array, 4, k);
+    if (!row || !live || !user || !start || !end || !owner) {
+        free(ops);
+        return NULL;
+    }
+    int rc = p_pie_comm_session_turn(cbx->comm, ops, k, users, discs, n_users, row, live, owner, user, start, end);
+    free(ops);
+    if (rc) return throw_comm(env, cbx->comm, rc);
+    return out;
+}
+
 /* commTokenSetEnd(comm, keys, newEnd BigInt64Array, now) -> Int32Array global rows written (-1: not found, or not live at `now`) */
 static napi_value fn_comm_token_set_end(napi_env env, napi_callback_info info)
 {
@@ -3142,6 +3183,7 @@ static napi_value init(napi_env env, napi_value exports)
         {"shardMaps", fn_shard_maps},
         {"tokenSet", fn_token_set}, {"tokenAppend", fn_token_append}, {"tokenLookup", fn_token_lookup}, {"tokenSetEnd", fn_token_set_end},
         {"tokenTurn", fn_token_turn}, {"sessionTurn", fn_session_turn}, {"commTokenTurn", fn_comm_token_turn},
+        {"commSessionTurn", fn_comm_session_turn},
         {"commTokenSet", fn_comm_token_set}, {"commTokenAppend", fn_comm_token_append}, {"commTokenLookup", fn_comm_token_lookup},
         {"commTokenSetEnd", fn_comm_token_set_end},
         {"scanBatchBegin", fn_scan_batch_begin}, {"scanBatchFinish", fn_scan_batch_finish}, {"tokenLookupBegin", fn_token_lookup_begin},

@@ -356,6 +356,10 @@ struct pie_ctx {
         hipEvent_t ev[2] = {};      // around the last rebuild (build_ms)
         hipEvent_t turn_done = nullptr;     // behind a turn's download (pie_token_turn): what its one wait polls
         std::vector<int32_t> turn_slots;    // scratch of the turn's plan (pie_turn_plan.h), kept between calls
+        // a sharded turn that logs in (pie_shard_session_turn), from its queue phase to its wait: the creates and the new users
+        // that shaped its staging block (turn_stage_of)
+        size_t turn_creates = 0, turn_new_users = 0;
+        int turn_late_rc = 0;               // ... and what failed behind its launch (the wait phase reports it)
         bool timed = false;
         bool hold = false;
         double build_ms = 0;
@@ -899,6 +903,7 @@ void token_results_out(const char* h, const TokResults& r, size_t k, int32_t* ro
 struct TokStage {
     size_t now = 0;                        // in-flight lookup: a clock per key
     size_t next = 0, cuser = 0, cdisc = 0; // turn: the chains; the users and disciplines of its creates
+    size_t crow = 0, newu = 0;             // sharded turn that logs in: the LOCAL row of every create (-1: another shard's); the new users
     size_t grow = 0;                       // synchronous shard lookup: the GLOBAL rows, beside the local ones in res.row
     size_t up = 0;
     TokResults res;
@@ -919,15 +924,18 @@ TokStage lookup_stage_of(size_t k, bool global = false)
     return o;
 }
 
-// a turn: [ops 40 k | next 4 k | cuser 4 n_create | cdisc 4 n_create | pad | results | pad | status]; only a turn that logs in
-// (pie_session_turn) has creates
-TokStage turn_stage_of(size_t k, size_t n_create = 0)
+// a turn: [ops 40 k | next 4 k | cuser 4 n_create | cdisc 4 n_create | crow 4 n_create | newu 4 n_new | pad | results | pad |
+// status]; only a turn that logs in (pie_session_turn) has creates, and only its shard form (pie_shard_session_turn) has crow and
+// the new users of its user map
+TokStage turn_stage_of(size_t k, size_t n_create = 0, bool shard = false, size_t n_new = 0)
 {
     TokStage o;
     o.next = k * 40;
     o.cuser = k * 44;
     o.cdisc = o.cuser + n_create * 4;
-    o.up = o.cdisc + n_create * 4;
+    o.crow = o.cdisc + n_create * 4;
+    o.newu = o.crow + (shard ? n_create * 4 : 0);
+    o.up = o.newu + (shard ? n_new * 4 : 0);
     o.res = TokResults(pad16(o.up), k);
     o.status = pad16(o.res.past);
     o.bytes = o.status + kTokStatusBytes;
@@ -6842,15 +6850,7 @@ int pie_batch_mask_codes(const pie_query* queries, int n_q, const uint8_t* fallb
     return PIE_OK;
 }
 
-int32_t pie_shard_of(int32_t user, int32_t n_shards)
-{
-    if (n_shards <= 1) return 0;
-    unsigned long long z = (unsigned long long)(uint32_t)user + 0x9E3779B97F4A7C15ULL;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    z ^= z >> 31;
-    return (int32_t)(z % (unsigned long long)n_shards);
-}
+int32_t pie_shard_of(int32_t user, int32_t n_shards) { return shard_of(user, n_shards); }
 
 // ---- the token column and its index (pie_token.h): getSession / touchSession / deleteSession by token hash ------------------
 // Everything is queued on the context's stream.  The host tracks `covered` and the slot count; the device tracks nothing but the
@@ -6897,8 +6897,9 @@ static int token_status_alloc(pie_ctx* c)
 // st[] = the status words as read back behind a waited call: set -> cleared on the device, PIE_E_HIP
 static int token_status_check(pie_ctx* c, const unsigned int* st, const char* what)
 {
-    if (!st[0] && !st[1]) return PIE_OK;
+    if (!st[0] && !st[1] && !st[2]) return PIE_OK;
     (void)hipMemsetAsync(c->tokx.status, 0, kTokStatusWords * sizeof(unsigned int), c->stream);
+    if (st[2]) return fail(c, PIE_E_HIP, "%s: a create names a user the shard's user map does not hold", what);
     return fail(c, PIE_E_HIP, "%s: probe bound exhausted (%s ran %llu steps without meeting an empty slot)", what,
                 st[0] ? "an insert" : "a lookup", 1ull << c->tokx.log2_slots);
 }
@@ -7280,21 +7281,44 @@ static int token_turn_launch(pie_ctx* c, const char* h, char* d, const TokStage&
     return PIE_OK;
 }
 
-// ... and a turn that logs in (the room is behind the caller): ONE upload of [ops | next | cuser | cdisc], ONE k_session_turn
-static int session_turn_launch(pie_ctx* c, const TokStage& o, size_t k)
+// What the shard form of a turn that logs in knows beside the turn itself (pie_shard_session_turn): how many of the creates the
+// shard keeps and how many of the call's new users it owns.
+struct ShardTurn {
+    size_t n_kept, n_new;
+    int32_t n_users_global;
+};
+
+// ... and a turn that logs in (the room is behind the caller): ONE upload of [ops | next | cuser | cdisc], ONE k_session_turn.
+// sh (a sharded context): the block also carries [crow | new users]; the new users go behind the device user map in stream order,
+// before the kernel, as append_launch puts them there; the run goes only when the shard keeps a create.
+static int session_turn_launch(pie_ctx* c, const TokStage& o, size_t k, const ShardTurn* sh = nullptr)
 {
     pie_ctx::TokenIndex& t = c->tokx;
-    hot_reserve(c, (long long)k); // every delta record of the turn is owed to an op of its own: a touch, a delete or a create
-    ord_invalidate(c);            // the run does not take the new rows: it goes before the kernel could mirror into it
+    hot_reserve(c, (long long)k);           // every delta record of the turn is owed to an op of its own: a touch, a delete or a create
+    if (!sh || sh->n_kept) ord_invalidate(c); // the run does not take the new rows: it goes before the kernel could mirror into it
     char* d = t.d_stage;
     PIE_HIP(c, hipMemcpyAsync(d, t.h_stage, o.up, hipMemcpyHostToDevice, c->stream));
+    if (sh && sh->n_new)
+        PIE_HIP(c, hipMemcpyAsync(c->d_shard_users + c->shard_users_n, d + o.newu, sh->n_new * 4, hipMemcpyDeviceToDevice, c->stream));
     const bool keys = c->key_ok; // a table too large to carry the derived columns runs without them
-    hipLaunchKernelGGL(k_session_turn, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, c->stream, stage_at<const TurnOp>(d, 0),
-                       stage_at<const int>(d, o.next), (long long)k, stage_at<const int>(d, o.cuser), stage_at<const int>(d, o.cdisc), c->n,
-                       t.slot_row, t.log2_slots, t.tok, t.covered, c->d_start, c->d_end, c->d_user, c->d_disc, keys ? c->d_key : nullptr,
-                       c->key_base, c->key_shift, keys ? c->d_fkey : nullptr, c->fkey_base, c->fkey_shift, keys ? c->d_pay : nullptr,
-                       ord_mirror_of(c), hot_mirror_of(c), stage_at<int>(d, o.res.row), stage_at<unsigned char>(d, o.res.live),
-                       stage_at<int>(d, o.res.user), stage_at<long long>(d, o.res.start), stage_at<long long>(d, o.res.end), t.status);
+    const dim3 grid((unsigned)((k + 255) / 256));
+    if (sh) {
+        const ShardMaps maps{(const int*)c->d_shard_rows, c->shard_rows_n, (const int*)c->d_shard_users, c->shard_users_n + (int)sh->n_new};
+        hipLaunchKernelGGL(k_session_turn<true>, grid, dim3(256), 0, c->stream, stage_at<const TurnOp>(d, 0), stage_at<const int>(d, o.next),
+                           (long long)k, stage_at<const int>(d, o.cuser), stage_at<const int>(d, o.cdisc), stage_at<const int>(d, o.crow),
+                           c->shard_rows_global, t.slot_row, t.log2_slots, t.tok, token_bound(c), c->d_start, c->d_end, c->d_user, c->d_disc,
+                           maps, c->d_shard_rows, keys ? c->d_key : nullptr, c->key_base, c->key_shift, keys ? c->d_fkey : nullptr,
+                           c->fkey_base, c->fkey_shift, keys ? c->d_pay : nullptr, ord_mirror_of(c), hot_mirror_of(c),
+                           stage_at<int>(d, o.res.row), stage_at<unsigned char>(d, o.res.live), stage_at<int>(d, o.res.user),
+                           stage_at<long long>(d, o.res.start), stage_at<long long>(d, o.res.end), t.status);
+    } else
+        hipLaunchKernelGGL(k_session_turn<false>, grid, dim3(256), 0, c->stream, stage_at<const TurnOp>(d, 0), stage_at<const int>(d, o.next),
+                           (long long)k, stage_at<const int>(d, o.cuser), stage_at<const int>(d, o.cdisc), (const int*)nullptr, c->n,
+                           t.slot_row, t.log2_slots, t.tok, t.covered, c->d_start, c->d_end, c->d_user, c->d_disc, ShardMaps{}, (int*)nullptr,
+                           keys ? c->d_key : nullptr, c->key_base, c->key_shift, keys ? c->d_fkey : nullptr, c->fkey_base, c->fkey_shift,
+                           keys ? c->d_pay : nullptr, ord_mirror_of(c), hot_mirror_of(c), stage_at<int>(d, o.res.row),
+                           stage_at<unsigned char>(d, o.res.live), stage_at<int>(d, o.res.user), stage_at<long long>(d, o.res.start),
+                           stage_at<long long>(d, o.res.end), t.status);
     PIE_HIP(c, hipGetLastError());
     return PIE_OK;
 }
@@ -7303,16 +7327,25 @@ static int session_turn_launch(pie_ctx* c, const TokStage& o, size_t k)
 // results and the status words, and an event behind them.  Nothing is waited for.  n_create > 0: the turn logs in
 // (pie_session_turn), and user / disc name who.
 static int token_turn_queue(pie_ctx* c, const pie_turn_op* ops, size_t k, bool global, const char* what, const int32_t* user = nullptr,
-                            const int32_t* disc = nullptr, size_t n_create = 0)
+                            const int32_t* disc = nullptr, size_t n_create = 0, const ShardTurn* sh = nullptr)
 {
     pie_ctx::TokenIndex& t = c->tokx;
     PIE_HIP(c, hipSetDevice(c->device));
-    const TokStage o = turn_stage_of(k, n_create);
+    const TokStage o = turn_stage_of(k, n_create, sh != nullptr, sh ? sh->n_new : 0);
     int rc = token_stage_room(c, o.bytes);
     if (rc) return rc;
     if (!t.turn_done) PIE_HIP(c, hipEventCreateWithFlags(&t.turn_done, hipEventDisableTiming));
     if ((rc = turn_stage_fill(c, t.h_stage, o, ops, k, user, disc, what)) != PIE_OK) return rc;
-    rc = n_create ? session_turn_launch(c, o, k) : token_turn_launch(c, t.h_stage, t.d_stage, o, k, global, t.status, ord_mirror_of(c));
+    if (sh) { // the shard's own part of the plan: the LOCAL row of every create it keeps, the users it gains
+        int32_t* crow = stage_at<int32_t>(t.h_stage, o.crow);
+        int32_t* per_op = stage_at<int32_t>(t.h_stage, o.res.row); // scratch: the results have not landed there yet
+        shard_session_turn_rows(ops, k, user, c->shard_rows_global, c->n, c->shard_rank, c->shard_world, nullptr, per_op, nullptr);
+        size_t j = 0;
+        for (size_t i = 0; i < k; ++i)
+            if (ops[i].kind == PIE_TURN_CREATE) crow[j++] = per_op[i];
+        shard_new_users(c->shard_users_global, sh->n_users_global, c->shard_rank, c->shard_world, stage_at<int32_t>(t.h_stage, o.newu));
+    }
+    rc = n_create ? session_turn_launch(c, o, k, sh) : token_turn_launch(c, t.h_stage, t.d_stage, o, k, global, t.status, ord_mirror_of(c));
     if (rc == PIE_OK) rc = token_stage_download(c, o);
     if (rc) return rc;
     PIE_HIP(c, hipEventRecord(t.turn_done, c->stream));
@@ -7322,7 +7355,7 @@ static int token_turn_queue(pie_ctx* c, const pie_turn_op* ops, size_t k, bool g
 // The wait phase: the one wait of a turn, on its own event and bounded (pie_wait.h); then what set_end_apply does behind its
 // wait (a row the ordered run does not hold came back to life: the run goes), the status words, and the results.
 static int token_turn_wait(pie_ctx* c, size_t k, const char* what, int32_t* row_out, uint8_t* live_out, int32_t* user_out, int64_t* start_out,
-                           int64_t* end_out, size_t n_create = 0)
+                           int64_t* end_out, size_t n_create = 0, bool shard = false, size_t n_new = 0)
 {
     pie_ctx::TokenIndex& t = c->tokx;
     PIE_HIP(c, hipSetDevice(c->device));
@@ -7333,7 +7366,7 @@ static int token_turn_wait(pie_ctx* c, size_t k, const char* what, int32_t* row_
         *c->ord.h_stale = 0;
         ord_invalidate(c);
     }
-    const TokStage o = turn_stage_of(k, n_create);
+    const TokStage o = turn_stage_of(k, n_create, shard, n_new);
     int rc = token_status_check(c, stage_at<const unsigned int>(t.h_stage, o.status), what);
     if (rc) return rc;
     token_results_out(t.h_stage, o.res, k, row_out, live_out, user_out, start_out, end_out);
@@ -7608,6 +7641,46 @@ int pie_shard_token_turn(pie_ctx* c, const pie_turn_op* ops, size_t k, int32_t* 
     return pie_internal::shard_token_turn_wait(c, k, row_global_out, live_out, user_global_out, start_out, end_out);
 }
 
+// Room for a sharded column on a shard of `rows` local rows (pie_shard_token_append: the rows it holds; pie_shard_session_turn:
+// with the creates it keeps): a column as long as the table's capacity (the table grew) and slots that stay at most half full —
+// the shard's row count passed half of them: the index is rebuilt from the covered rows into pie_token_slots_for(rows).  Both
+// free what a lookup begun earlier reads: those land first.  May wait.
+static int shard_token_make_room(pie_ctx* c, long long rows, const char* what)
+{
+    pie_ctx::TokenIndex& t = c->tokx;
+    hipStream_t s = c->stream;
+    const bool longer = c->cap_rows > t.cap, grow = (unsigned long long)rows > ((1ull << t.log2_slots) >> 1);
+    int rc = PIE_OK;
+    if ((longer || grow) && (rc = token_lookups_land(c, what)) != PIE_OK) return rc;
+    if (longer) {
+        TokKey* nt = nullptr;
+        PIE_HIP(c, hipMalloc(&nt, (size_t)c->cap_rows * sizeof(TokKey)));
+        hipError_t e = t.cap ? hipMemcpyAsync(nt, t.tok, (size_t)t.cap * sizeof(TokKey), hipMemcpyDeviceToDevice, s) : hipSuccess;
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) {
+            (void)hipFree(nt);
+            return fail(c, PIE_E_HIP, "%s: %s", what, hipGetErrorString(e));
+        }
+        dfree(t.tok);
+        t.tok = nt;
+        t.cap = c->cap_rows;
+    }
+    if (grow) {
+        const unsigned log2_slots = token_log2(pie_token_slots_for((size_t)rows));
+        long long covered_l = 0;
+        rc = shard_token_covered(c, &covered_l); // waits: inserts queued earlier still write the table that goes
+        if (rc) return rc;
+        int* ns = nullptr;
+        PIE_HIP(c, hipMalloc(&ns, (size_t)4 << log2_slots));
+        dfree(t.slot_row);
+        t.slot_row = ns;
+        t.log2_slots = log2_slots;
+        rc = token_rebuild(c, covered_l);
+        if (rc) return rc;
+    }
+    return PIE_OK;
+}
+
 // One chunk (k <= 2^20 keys, checked by the caller) for the global rows [covered_g, covered_g + k): everything that can fail and
 // everything that waits comes first — the staging area, a longer column (the table grew), a larger table of slots (the shard's
 // row count passed half of them: the index is rebuilt from the covered rows) — then one upload and one launch, queued.
@@ -7622,34 +7695,7 @@ static int shard_token_chunk(pie_ctx* c, const uint64_t* tok, size_t k)
     Staged st{};
     int rc = stage_mutation(c, k * sizeof(TokKey), true, &st);
     if (rc) return rc;
-    if ((c->cap_rows > t.cap || (unsigned long long)c->n > ((1ull << t.log2_slots) >> 1)) && (rc = token_lookups_land(c, "pie_shard_token_append")) != PIE_OK)
-        return rc;
-    if (c->cap_rows > t.cap) {
-        TokKey* nt = nullptr;
-        PIE_HIP(c, hipMalloc(&nt, (size_t)c->cap_rows * sizeof(TokKey)));
-        hipError_t e = t.cap ? hipMemcpyAsync(nt, t.tok, (size_t)t.cap * sizeof(TokKey), hipMemcpyDeviceToDevice, s) : hipSuccess;
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) {
-            (void)hipFree(nt);
-            return fail(c, PIE_E_HIP, "pie_shard_token_append: %s", hipGetErrorString(e));
-        }
-        dfree(t.tok);
-        t.tok = nt;
-        t.cap = c->cap_rows;
-    }
-    if ((unsigned long long)c->n > ((1ull << t.log2_slots) >> 1)) {
-        const unsigned log2_slots = token_log2(pie_token_slots_for((size_t)c->n));
-        long long covered_l = 0;
-        rc = shard_token_covered(c, &covered_l); // waits: inserts queued earlier still write the table that goes
-        if (rc) return rc;
-        int* ns = nullptr;
-        PIE_HIP(c, hipMalloc(&ns, (size_t)4 << log2_slots));
-        dfree(t.slot_row);
-        t.slot_row = ns;
-        t.log2_slots = log2_slots;
-        rc = token_rebuild(c, covered_l);
-        if (rc) return rc;
-    }
+    if ((rc = shard_token_make_room(c, c->n, "pie_shard_token_append")) != PIE_OK) return rc;
     memcpy(st.h, tok, k * sizeof(TokKey));
     PIE_HIP(c, hipMemcpyAsync(st.d, st.h, k * sizeof(TokKey), hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(k_shard_token_place, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const TokKey*>(st.d), t.covered_g,
@@ -7762,6 +7808,175 @@ int pie_shard_token_layout(pie_ctx* c, size_t* covered_global_out, size_t* cover
     int rc = shard_token_ready(c, "pie_shard_token_layout", true);
     if (rc) return rc;
     return token_layout_read(c, "pie_shard_token_layout", covered_global_out, covered_local_out, slots_out, slot_row_out, cap, tok_out);
+}
+
+// ---- a turn that logs in on a sharded table (pie_shard_session_turn; include/pie_scan.h, k_session_turn<true> in pie_token.h).
+// Every shard is given the same turn.  Which create is whose, the global and the local row of each and the users a shard gains
+// are host arithmetic (pie_turn_plan.h); nothing is exchanged and nothing is counted on the device.
+
+int pie_shard_session_turn_plan(const pie_turn_op* ops, size_t k, const int32_t* user_global, int64_t rows_global0, int64_t rows_local0,
+                                int32_t rank, int32_t world, int32_t* next_out, uint8_t* head_out, int32_t* new_row_global_out,
+                                int32_t* new_row_local_out, size_t* n_create_out, size_t* n_kept_out)
+{
+    if (k >= ((size_t)1 << 31) || rows_global0 < 0 || rows_local0 < 0 || rows_local0 > rows_global0 || world < 1 || rank < 0 || rank >= world)
+        return PIE_E_INVAL;
+    if (k && (!ops || !next_out || !head_out || !new_row_global_out || !new_row_local_out)) return PIE_E_INVAL;
+    if (session_turn_first_bad(ops, k) < k) return PIE_E_INVAL;
+    const size_t n_create = session_turn_creates(ops, k);
+    if (n_create && !user_global) return PIE_E_INVAL;
+    if (rows_global0 + (int64_t)n_create >= ((int64_t)1 << 31) - 1) return PIE_E_INVAL;
+    std::vector<int32_t> slots;
+    if (!turn_plan(ops, k, next_out, head_out, slots)) return PIE_E_NOMEM;
+    size_t n_kept = 0;
+    shard_session_turn_rows(ops, k, user_global, rows_global0, rows_local0, rank, world, new_row_global_out, new_row_local_out, &n_kept);
+    if (n_create_out) *n_create_out = n_create;
+    if (n_kept_out) *n_kept_out = n_kept;
+    return PIE_OK;
+}
+
+} // extern "C"
+
+// The phases of pie_shard_session_turn, which the communicator runs shard by shard: every check with nothing staged or changed;
+// the room (the one phase that may wait or re-allocate); the queue phase; the wait phase.
+namespace pie_internal {
+int shard_session_turn_check(pie_ctx* c, const pie_turn_op* ops, size_t k, const int32_t* user_global, const int32_t* disc, int32_t n_users_global)
+{
+    if (!c) return PIE_E_INVAL;
+    const char* const what = "pie_shard_session_turn";
+    int rc = shard_token_ready(c, what, true);
+    if (rc) return rc;
+    if (n_users_global < c->shard_users_global)
+        return fail(c, PIE_E_INVAL, "%s: n_users_global may only grow (%d < %d)", what, n_users_global, c->shard_users_global);
+    if (k > 0 && !ops) return fail(c, PIE_E_INVAL, "%s: ops is NULL", what);
+    if (k >= ((size_t)1 << 31)) return fail(c, PIE_E_INVAL, "%s: %zu ops in one turn", what, k);
+    const size_t bad = session_turn_first_bad(ops, k);
+    if (bad < k) return fail(c, PIE_E_INVAL, "%s: op %zu has kind %d, reserved %d", what, bad, (int)ops[bad].kind, (int)ops[bad].reserved);
+    const size_t n_create = session_turn_creates(ops, k);
+    if (n_create == 0) return PIE_OK;
+    if (!user_global || !disc) return fail(c, PIE_E_INVAL, "%s: a create without %s", what, user_global ? "disc" : "user");
+    for (size_t i = 0; i < k; ++i)
+        if (ops[i].kind == PIE_TURN_CREATE && (uint32_t)user_global[i] >= (uint32_t)n_users_global)
+            return fail(c, PIE_E_INVAL, "%s: op %zu carries user %d outside [0, %d)", what, i, user_global[i], n_users_global);
+    if (c->tokx.covered_g < c->shard_rows_global)
+        return fail(c, PIE_E_STATE, "%s: the token column covers %lld of %lld global rows (pie_shard_token_append the rest first)", what,
+                    c->tokx.covered_g, c->shard_rows_global);
+    if (c->shard_rows_global + (long long)n_create >= (1LL << 31) - 1) return fail(c, PIE_E_INVAL, "%s: global row count outside [0, 2^31 - 1)", what);
+    return PIE_OK;
+}
+
+// what the turn means to this shard (behind shard_session_turn_check): the creates it keeps, the users it gains
+static ShardTurn shard_turn_of(const pie_ctx* c, const pie_turn_op* ops, size_t k, const int32_t* user_global, int32_t n_users_global)
+{
+    ShardTurn sh{};
+    sh.n_kept = session_turn_creates(ops, k) ? shard_session_turn_kept(ops, k, user_global, c->shard_rank, c->shard_world) : 0;
+    sh.n_new = shard_new_users(c->shard_users_global, n_users_global, c->shard_rank, c->shard_world);
+    sh.n_users_global = n_users_global;
+    return sh;
+}
+
+// the context's own (local) user count once the shard holds n_new more users; a shard with no user keeps n_users = 1
+static int shard_local_users(const pie_ctx* c, size_t n_new)
+{
+    const long long users = (long long)c->shard_users_n + (long long)n_new;
+    return users > 0 ? (int)users : 1;
+}
+
+// Room, by the routines pie_shard_append_rows and pie_shard_token_append make it with; neither the table's size nor the user
+// count moves here: the communicator makes room on every shard before it changes any.  A turn without a create needs none
+// ahead of time (its new users come in the queue phase, as pie_shard_append_rows(k = 0) brings them).
+int shard_session_turn_room(pie_ctx* c, const pie_turn_op* ops, size_t k, const int32_t* user_global, int32_t n_users_global)
+{
+    const char* const what = "pie_shard_session_turn";
+    const size_t n_create = session_turn_creates(ops, k);
+    if (n_create == 0) return PIE_OK;
+    PIE_HIP(c, hipSetDevice(c->device));
+    const ShardTurn sh = shard_turn_of(c, ops, k, user_global, n_users_global);
+    const long long old_n = c->n, rows = old_n + (long long)sh.n_kept;
+    const int local_users = shard_local_users(c, sh.n_new);
+    try {
+        c->shard_users_h.reserve(c->shard_users_h.size() + sh.n_new); // the commit behind the launch cannot fail
+    } catch (...) {
+        return fail(c, PIE_E_NOMEM, "%s: no memory for the user map", what);
+    }
+    int rc = PIE_OK;
+    if (rows > c->cap_rows || local_users > c->cap_users || !c->key_ok) {
+        rc = append_rollback(c, old_n, ensure_capacity(c, rows, local_users, old_n > 0 ? old_n : 1));
+        if (rc == PIE_OK) rc = build_keys(c, old_n); // every row: the columns moved, or were not keyed
+        if (rc) return rc;
+    }
+    if ((rc = shard_maps_reserve(c, c->cap_rows, c->cap_users)) != PIE_OK) return rc;
+    if ((rc = shard_token_make_room(c, rows, what)) != PIE_OK) return rc;
+    return token_stage_room(c, turn_stage_of(k, n_create, true, sh.n_new).bytes);
+}
+
+// One upload, one kernel, one download, nothing waited for (an error means nothing was launched); then the host's picture moves as a sharded append and a token append
+// move it: the maps, N_g and covered_g on every shard alike, the rows and the users this shard gained.
+int shard_session_turn_queue(pie_ctx* c, const pie_turn_op* ops, size_t k, const int32_t* user_global, const int32_t* disc, int32_t n_users_global)
+{
+    const char* const what = "pie_shard_session_turn";
+    pie_ctx::TokenIndex& t = c->tokx;
+    const size_t n_create = session_turn_creates(ops, k);
+    t.turn_creates = n_create;
+    t.turn_new_users = 0;
+    t.turn_late_rc = PIE_OK;
+    if (n_create == 0) { // pie_shard_token_turn, behind the growth of the user count as an append of no rows does it
+        if (n_users_global > c->shard_users_global) {
+            const int rc = pie_shard_append_rows(c, nullptr, nullptr, nullptr, nullptr, 0, n_users_global, nullptr, nullptr);
+            if (rc) return rc;
+        }
+        return k == 0 ? PIE_OK : token_turn_queue(c, ops, k, true, what);
+    }
+    const ShardTurn sh = shard_turn_of(c, ops, k, user_global, n_users_global);
+    const TokStage o = turn_stage_of(k, n_create, true, sh.n_new);
+    // token_turn_queue fails before its launch (the staging, the plan) or, behind it, where only the runtime itself can fail
+    // (the download, the event): such a context has a device error pending and is not used further, as on the unsharded path.
+    int rc = token_turn_queue(c, ops, k, true, what, user_global, disc, n_create, &sh);
+    if (rc) return rc;
+    t.turn_new_users = sh.n_new;
+    const int32_t* newu = stage_at<const int32_t>(t.h_stage, o.newu);
+    c->shard_users_h.insert(c->shard_users_h.end(), newu, newu + sh.n_new); // reserved by the room phase
+    const long long old_n = c->n;
+    c->shard_rows_n = old_n + (long long)sh.n_kept;
+    c->shard_users_n += (int)sh.n_new;
+    c->shard_rows_global += (long long)n_create;
+    c->shard_users_global = n_users_global;
+    t.covered_g += (long long)n_create;
+    c->n = old_n + (long long)sh.n_kept;
+    const int local_users = shard_local_users(c, 0);
+    if (sh.n_kept) {
+        t.turn_late_rc = append_finish(c, local_users);
+        return PIE_OK;
+    }
+    c->key_dirty = true; // the touches and deletes of the turn, as token_turn_launch leaves it
+    if (local_users > c->n_users) { // as pie_shard_append_rows leaves a context that gained users and no row
+        if (c->ord.valid && local_users > c->ord.users) ord_invalidate(c);
+        set_user_count(c, local_users);
+        drop_results(c);
+    }
+    return PIE_OK;
+}
+
+int shard_session_turn_wait(pie_ctx* c, size_t k, int32_t* row_global_out, uint8_t* live_out, int32_t* user_global_out, int64_t* start_out,
+                            int64_t* end_out)
+{
+    if (k == 0) return PIE_OK;
+    const pie_ctx::TokenIndex& t = c->tokx;
+    const int rc = token_turn_wait(c, k, "pie_shard_session_turn", row_global_out, live_out, user_global_out, start_out, end_out,
+                                   t.turn_creates, t.turn_creates > 0, t.turn_new_users);
+    return rc ? rc : t.turn_late_rc;
+}
+} // namespace pie_internal
+
+extern "C" {
+
+int pie_shard_session_turn(pie_ctx* c, const pie_turn_op* ops, size_t k, const int32_t* user_global, const int32_t* disc, int32_t n_users_global,
+                           int32_t* row_global_out, uint8_t* live_out, int32_t* user_global_out, int64_t* start_out, int64_t* end_out)
+{
+    int rc = pie_internal::shard_session_turn_check(c, ops, k, user_global, disc, n_users_global);
+    if (rc) return rc;
+    if ((rc = pie_internal::shard_session_turn_room(c, ops, k, user_global, n_users_global)) != PIE_OK) return rc;
+    if ((rc = pie_internal::shard_session_turn_queue(c, ops, k, user_global, disc, n_users_global)) != PIE_OK) return rc;
+    return pie_internal::shard_session_turn_wait(c, k, row_global_out, live_out, user_global_out, start_out, end_out);
 }
 
 // ---- lookups beside scans and batches (pie_token_lookup_begin / _finish, include/pie_scan.h).  A lookup only reads, and so do

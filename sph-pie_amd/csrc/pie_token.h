@@ -20,7 +20,7 @@ namespace pie {
 
 typedef ulonglong2 TokKey; // .x = bytes 0..7, .y = bytes 8..15 of the sha256, little endian
 
-constexpr int kTokStatusWords = 4; // [0] an insert exhausted its probe bound, [1] a lookup did
+constexpr int kTokStatusWords = 4; // [0] an insert exhausted its probe bound, [1] a lookup did, [2] a sharded create's user is unknown
 constexpr int kTokLookups = 4;     // lookups begun and not finished beside scans and batches (pie_token_lookup_begin)
 constexpr int kTokTurns = 4;       // turns begun and not finished beside scans and batches (pie_token_turn_begin)
 
@@ -293,7 +293,8 @@ __global__ __launch_bounds__(256) void k_token_turn(const TurnOp* __restrict__ o
     if (e != e0) touch_row(best, e, end, key, key_base, key_shift, fkey, fkey_base, fkey_shift, ord, hot);
 }
 
-// ---- a turn that logs in (pie_session_turn): k_token_turn's walk with a fourth kind, CREATE.  Unsharded tables only.
+// ---- a turn that logs in (pie_session_turn, pie_shard_session_turn): k_token_turn's walk with a fourth kind, CREATE.  The plain
+// form first; what kShard adds stands below it.
 //
 // The uploaded op's `head` word carries the head flag in bit 0 and, for a CREATE, the create's ordinal j in the bits above: the
 // j-th create of the array becomes row row0 + j (the host counted; no device atomic) and takes user / disc from the compact
@@ -315,10 +316,22 @@ __global__ __launch_bounds__(256) void k_token_turn(const TurnOp* __restrict__ o
 // launch creates under a key matter to that lane alone, which has them in registers.  Readers of the new entries are later
 // kernels on the stream.  No spin, no barrier, no LDS; the only atomics are the slot claim and the hot mirror's own.
 // Rows: distinct keys have distinct rows and every new row belongs to one create, so no two lanes write one row.
+//
+// kShard (pie_shard_session_turn): the same walk on one shard of a sharded table.  row0 is N_g, the GLOBAL row count before the
+// turn: the create of ordinal j is global row N_g + j on every shard.  crow[j] is the LOCAL row the shard gives it, or -1 when
+// another shard keeps it; cuser[j] is the GLOBAL user, found in the user map by shard_lower_bound as k_shard_append_rows finds it
+// (the new users of the call are behind the map in stream order).  A kept create also stores rows_map[local row] = N_g + j; the
+// local rows ascend with the ordinal, so the map stays ascending.  A create the shard does not keep answers -1 / 0 / INT64_MIN /
+// -1 and leaves the lane on whatever row the key had here; so does one whose user the map does not hold, which also raises
+// status[2] (the host has checked every id: this keeps a slip from reaching an index).  Rows and users are answered as GLOBAL
+// ids, as k_token_turn<true> answers them.  The argument about probes carries over with `bound` = min(bound, the local rows
+// before the turn): all of them are covered, because the host refuses a create while covered_g < N_g.
+template <bool kShard>
 __global__ __launch_bounds__(256) void k_session_turn(const TurnOp* __restrict__ ops, const int* __restrict__ next, long long k,
-                                                      const int* __restrict__ cuser, const int* __restrict__ cdisc, long long row0,
-                                                      int* slot_row, unsigned log2_slots, TokKey* tok, long long bound, long long* start,
-                                                      long long* end, int* user, int* disc, lkey_t* key, long long key_base, int key_shift,
+                                                      const int* __restrict__ cuser, const int* __restrict__ cdisc,
+                                                      const int* __restrict__ crow, long long row0, int* slot_row, unsigned log2_slots,
+                                                      TokKey* tok, long long bound, long long* start, long long* end, int* user, int* disc,
+                                                      ShardMaps maps, int* rows_map, lkey_t* key, long long key_base, int key_shift,
                                                       fkey_t* fkey, long long fkey_base, int fkey_shift, PayRec* pay, OrdMirror ord,
                                                       HotMirror hot, int* __restrict__ o_row, unsigned char* __restrict__ o_live,
                                                       int* __restrict__ o_user, long long* __restrict__ o_start,
@@ -331,32 +344,55 @@ __global__ __launch_bounds__(256) void k_session_turn(const TurnOp* __restrict__
     TokKey want;
     want.x = op.k0;
     want.y = op.k1;
-    int row = token_probe(want, slot_row, log2_slots, tok, bound, status);
+    int row = token_probe(want, slot_row, log2_slots, tok, kShard && maps.n_local < bound ? maps.n_local : bound, status);
     bool found = row >= 0;
     long long e0 = found ? end[row] : INT64_MIN, sv = found ? start[row] : 0;
-    int uv = found ? user[row] : -1;
+    int uv = found ? user[row] : -1, rv = row; // what the lane answers for its row and user: GLOBAL ids on a shard
+    if (kShard) {
+        rv = found ? maps.rows[row] : -1;
+        uv = (uv >= 0 && uv < maps.n_users) ? maps.users[uv] : -1;
+    }
     long long e = e0, j = t;
     for (long long step = 0; step < k; ++step) {
-        int r = row;
+        int r = rv;
         unsigned char live;
+        bool kept = true;
         if (op.kind == kTurnCreate) {
-            if (found && e != e0) touch_row(row, e, end, key, key_base, key_shift, fkey, fkey_base, fkey_shift, ord, hot);
             const long long c = (long long)((unsigned)op.head >> 1);
-            row = r = (int)(row0 + c);
-            found = true;
-            sv = op.now;
-            e = e0 = op.new_end;
-            uv = cuser[c];
-            append_row(row, sv, e, uv, cdisc[c], start, end, user, disc, key, key_base, key_shift, fkey, fkey_base, fkey_shift, pay, hot);
-            tok[row] = want;
-            token_claim(want, row, slot_row, log2_slots, status);
-            live = e > op.now ? 1 : 0;
+            long long nr = row0 + c;
+            int lu = cuser[c]; // the user as the row stores it: the LOCAL id on a shard
+            if (kShard) {
+                nr = crow[c];
+                kept = nr >= 0;
+                if (kept) {
+                    const long long p = shard_lower_bound(maps.users, (long long)maps.n_users, lu);
+                    if (p < (long long)maps.n_users && maps.users[p] == lu) lu = (int)p;
+                    else {
+                        status[2] = 1u;
+                        kept = false;
+                    }
+                }
+            }
+            if (kept) {
+                if (found && e != e0) touch_row(row, e, end, key, key_base, key_shift, fkey, fkey_base, fkey_shift, ord, hot);
+                row = (int)nr;
+                rv = r = kShard ? (int)(row0 + c) : row;
+                found = true;
+                sv = op.now;
+                e = e0 = op.new_end;
+                uv = cuser[c];
+                append_row(row, sv, e, lu, cdisc[c], start, end, user, disc, key, key_base, key_shift, fkey, fkey_base, fkey_shift, pay, hot);
+                if (kShard) rows_map[row] = rv;
+                tok[row] = want;
+                token_claim(want, row, slot_row, log2_slots, status);
+            }
+            live = kept && e > op.now ? 1 : 0;
         } else live = turn_apply(op, found, e, r);
-        o_row[j] = r;
+        o_row[j] = kept ? r : -1;
         o_live[j] = live;
-        o_end[j] = e;
-        o_start[j] = sv;
-        o_user[j] = uv;
+        o_end[j] = kept ? e : INT64_MIN;
+        o_start[j] = kept ? sv : 0;
+        o_user[j] = kept ? uv : -1;
         const long long nx = next[j];
         if (nx <= j || nx >= k) break;
         j = nx;
