@@ -465,7 +465,9 @@ uint32_t pie_hot_slot_bits(uint32_t n_users);
  * appends: a new row is inserted at its place in its user's segment, which ends in spare slots — for a session store's
  * createSession that place is the end; a row a little late shifts the few behind it; a full segment moves the run into
  * fresh segments (a linear pass).  Loads, sharding and back-fills (a row more than 256 rows back in its segment) invalidate
- * it (queries run on the general path until it is rebuilt).  PIE_ORDERED=0|1|2 sets the mode a context starts with. */
+ * it (queries run on the general path until it is rebuilt).  A turn that logs in (pie_session_turn and its shard forms, a
+ * PIE_TURN_CREATE among the ops) drops it too, unless pie_set_turn_ordered is on: then the rows the turn creates are inserted
+ * as an append's rows are.  PIE_ORDERED=0|1|2 sets the mode a context starts with. */
 int pie_set_ordered_run(pie_ctx *ctx, int mode);
 /* Wide batches on the ordered run (see pie_scan_wide_begin).  0 (default): a wide batch on a table whose batches take the
  * ordered run reruns every query as a single scan and keeps no union.  1: it runs one pass over the run and keeps its union
@@ -473,6 +475,18 @@ int pie_set_ordered_run(pie_ctx *ctx, int mode);
  * affected.  PIE_E_STATE while a scan or batch is in flight, PIE_E_INVAL for any other value.  PIE_WIDE_ORDERED=1 sets the
  * value a context starts with. */
 int pie_set_wide_ordered(pie_ctx *ctx, int on);
+/* Turns that log in on a table with a valid ordered run (pie_session_turn, pie_shard_session_turn, pie_comm_session_turn: set it
+ * on every shard's context, pie_comm_ctx).  0 (default): a turn in which the context keeps at least one PIE_TURN_CREATE drops the
+ * run.  1: such a turn keeps the run where pie_append_rows would keep it — the run is valid and covers every row, the context
+ * keeps at most 4096 creates, its user count after the turn is within the users the run has segments for, the key columns are in
+ * step, and the table does not have to grow.  Behind the turn's kernel the created rows are read back from the table (with the
+ * `end` the turn's later ops left them) and inserted into their users' segments; a full segment re-spreads the run; a row more
+ * than 256 rows back in its segment, or a row the run does not hold that the turn brought back to life, drops it.  Results,
+ * the table and every index are the same with 0 and 1: only whether the run survives differs.  Create-free turns, pie_token_turn
+ * and the turns begun in flight (pie_token_turn_begin) are not affected.  PIE_E_INVAL for a NULL context or any other value;
+ * PIE_E_STATE while a scan or batch is in flight or a turn is begun and not finished.  PIE_TURN_ORDERED=1 sets the value a
+ * context starts with. */
+int pie_set_turn_ordered(pie_ctx *ctx, int on);
 /* 0: off.  n >= 1: every n-th scan carries HIP events around K1 and around the whole scan (an event between two
  * kernels costs a few microseconds of pipeline drain, so a benchmark samples). */
 int pie_set_profiling(pie_ctx *ctx, int enabled);
@@ -693,8 +707,9 @@ int pie_token_turn(pie_ctx *ctx, const pie_turn_op *ops, size_t k, int32_t *row_
  * pie_token_append do — a larger table, a key build, a longer column, a rebuild into pie_token_slots_for(new covered) slots —
  * and may wait there; lookups begun in flight land first.  PIE_E_NOMEM there changes nothing.  After that the turn is one
  * upload, one kernel, one download and one wait bounded by PIE_WAIT_DEADLINE_MS.
- * Ordered run: a turn with at least one CREATE drops a valid ordered run (later scans rebuild it or take the general path); a
- * turn without one treats the run as pie_token_turn does.  A turn without a CREATE is pie_token_turn, plus the growth of the
+ * Ordered run: a turn with at least one CREATE drops a valid ordered run (later scans rebuild it or take the general path),
+ * unless pie_set_turn_ordered is on and the run can take the rows as it takes an append's (see there); a turn without one treats
+ * the run as pie_token_turn does.  A turn without a CREATE is pie_token_turn, plus the growth of the
  * user count to n_users as pie_append_rows(k = 0) does it.  k = 0 is allowed.  Every output pointer may be NULL.
  * PIE_E_STATE: no table; no token column; a sharded context; a scan or batch in flight; a turn begun and not finished; a CREATE
  * while the column does not cover every row (the column is a prefix).  PIE_E_INVAL: NULL context; NULL ops with k > 0;
@@ -771,7 +786,8 @@ int pie_shard_token_turn(pie_ctx *ctx, const pie_turn_op *ops, size_t k, int32_t
  * turn is one upload, one kernel, one download and one wait bounded by PIE_WAIT_DEADLINE_MS — also on a shard that keeps no
  * CREATE and holds none of the keys, which still runs its chains.  With k = 0, or no CREATE and no new user, the call is
  * pie_shard_token_turn; a turn without a CREATE that grows n_users_global is pie_shard_append_rows(k = 0) followed by the turn.
- * Ordered run: a turn in which the shard keeps a CREATE drops its valid ordered run; any other turn keeps it in step.
+ * Ordered run: a turn in which the shard keeps a CREATE drops its valid ordered run (with pie_set_turn_ordered on for the shard's
+ * context: keeps it where an append of those rows would, in the shard's own LOCAL numbers); any other turn keeps it in step.
  * PIE_E_STATE: a context that is not sharded, or whose row map does not cover its rows; no table; no column; a scan or batch in
  * flight; a turn begun and not finished; a CREATE while covered_g < N_g.  PIE_E_INVAL: NULL context; NULL ops with k > 0;
  * k >= 2^31; a kind outside 0..3; reserved != 0; n_users_global below the table's; a CREATE with NULL user_global or disc, or with

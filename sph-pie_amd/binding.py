@@ -96,6 +96,7 @@ _SIGS = [
     ("pie_set_scan_form", C.c_int, [_P, C.c_int]),
     ("pie_set_ordered_run", C.c_int, [_P, C.c_int]),
     ("pie_set_wide_ordered", C.c_int, [_P, C.c_int]),
+    ("pie_set_turn_ordered", C.c_int, [_P, C.c_int]),
     ("pie_set_batch_lanes", C.c_int, [_P, C.c_int]),
     ("pie_batch_lanes", C.c_int, [_P]),
     ("pie_batch_room", C.c_int, [_P]),
@@ -517,6 +518,11 @@ class PieScan:
         """1: a wide batch on a table whose batches take the ordered run runs one pass there and keeps its union; 0 (default):
         it reruns its queries one by one (pie_set_wide_ordered)."""
         self._check(self._lib.pie_set_wide_ordered(self._ctx, int(on)))
+
+    def set_turn_ordered(self, on):
+        """1: a turn that logs in (session_turn with creates, also on a shard) keeps a valid ordered run where append_rows would
+        keep it: the created rows are inserted in place; 0 (default): such a turn drops the run (pie_set_turn_ordered)."""
+        self._check(self._lib.pie_set_turn_ordered(self._ctx, int(on)))
 
     def table_info(self):
         ti = PieTableInfo()

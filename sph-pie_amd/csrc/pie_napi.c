@@ -52,6 +52,8 @@
     X(int, pie_set_profiling, (pie_ctx *, int))                                                                     \
     X(int, pie_set_ordered_run, (pie_ctx *, int))                                                                   \
     X(int, pie_set_wide_ordered, (pie_ctx *, int))                                                                  \
+    X(int, pie_set_turn_ordered, (pie_ctx *, int))                                                                  \
+    X(int, pie_table_info_get, (pie_ctx *, pie_table_info *))                                                       \
     X(int, pie_set_batch_lanes, (pie_ctx *, int))                                                                   \
     X(int, pie_batch_lanes, (pie_ctx *))                                                                            \
     X(int, pie_stats_get, (pie_ctx *, pie_stats *))                                                                 \
@@ -2149,6 +2151,29 @@ static napi_value fn_stats(napi_env env, napi_callback_info info)
     return o;
 }
 
+/* tableInfo(ctx) -> {rows, users, orderedRows, orderedBuilds, orderedRespreads, tokenRows}: the ordered run as pie_table_info
+ * reports it (orderedRows 0: there is none, or it was invalidated) */
+static napi_value fn_table_info(napi_env env, napi_callback_info info)
+{
+    ARGS(1)
+    pie_ctx *ctx = get_ctx(env, argv[0]);
+    if (!ctx) return NULL;
+    pie_table_info ti;
+    memset(&ti, 0, sizeof ti);
+    ti.struct_size = sizeof ti;
+    int rc = p_pie_table_info_get(ctx, &ti);
+    if (rc) return throw_pie(env, ctx, rc);
+    napi_value o, v;
+    napi_create_object(env, &o);
+#define PUT(name, val)                      \
+    napi_create_double(env, (double)(val), &v); \
+    napi_set_named_property(env, o, name, v);
+    PUT("rows", ti.rows) PUT("users", ti.users) PUT("orderedRows", ti.ordered_rows) PUT("orderedBuilds", ti.ordered_builds)
+    PUT("orderedRespreads", ti.ordered_respreads) PUT("tokenRows", ti.token_rows)
+#undef PUT
+    return o;
+}
+
 static napi_value fn_set_profiling(napi_env env, napi_callback_info info)
 {
     ARGS(2)
@@ -2184,6 +2209,20 @@ static napi_value fn_set_wide_ordered(napi_env env, napi_callback_info info)
     int32_t on = 0;
     CHECK(env, napi_get_value_int32(env, argv[1], &on));
     const int rc = p_pie_set_wide_ordered(ctx, on);
+    if (rc != 0) return throw_pie(env, ctx, rc);
+    return js_int(env, 0);
+}
+
+/* setTurnOrdered(ctx, on): 1 = a turn that logs in keeps a valid ordered run where an append would (the created rows are inserted
+ * in place); 0 (default) = such a turn drops the run (pie_set_turn_ordered) */
+static napi_value fn_set_turn_ordered(napi_env env, napi_callback_info info)
+{
+    ARGS(2)
+    pie_ctx *ctx = get_ctx(env, argv[0]);
+    if (!ctx) return NULL;
+    int32_t on = 0;
+    CHECK(env, napi_get_value_int32(env, argv[1], &on));
+    const int rc = p_pie_set_turn_ordered(ctx, on);
     if (rc != 0) return throw_pie(env, ctx, rc);
     return js_int(env, 0);
 }
@@ -3170,7 +3209,7 @@ static napi_value init(napi_env env, napi_value exports)
         {"readColumns", fn_read_columns}, {"saveColumns", fn_save_columns}, {"loadColumnsDir", fn_load_columns_dir}, {"setEnd", fn_set_end}, {"compactRows", fn_compact_rows}, {"compactMaps", fn_compact_maps}, {"compactTranslate", fn_compact_translate}, {"deleteUser", fn_delete_user}, {"deleteUsers", fn_delete_users}, {"retentionPurgeTz", fn_retention_purge_tz},
         {"setDisciplines", fn_set_disc}, {"scan", fn_scan}, {"scanDevice", fn_scan_device}, {"userFeed", fn_user_feed}, {"scanAsync", fn_scan_async}, {"fetchRows", fn_fetch_rows},
         {"expiredQueue", fn_expired_queue}, {"archiveQueue", fn_archive_queue}, {"serializeEvents", fn_serialize_events}, {"serializeICal", fn_serialize_ical}, {"stats", fn_stats}, {"setProfiling", fn_set_profiling},
-        {"setOrderedRun", fn_set_ordered_run}, {"setWideOrdered", fn_set_wide_ordered}, {"wideUnionRows", fn_wide_union_rows}, {"setBatchLanes", fn_set_batch_lanes},
+        {"setOrderedRun", fn_set_ordered_run}, {"setWideOrdered", fn_set_wide_ordered}, {"setTurnOrdered", fn_set_turn_ordered}, {"tableInfo", fn_table_info}, {"wideUnionRows", fn_wide_union_rows}, {"setBatchLanes", fn_set_batch_lanes},
         {"serializeCsv", fn_serialize_csv}, {"scanBatch", fn_scan_batch}, {"scanWide", fn_scan_wide}, {"batchUserFeed", fn_batch_user_feed}, {"batchFetchRequests", fn_batch_fetch_requests},
         {"commCreate", fn_comm_create}, {"commDestroy", fn_comm_destroy}, {"commWorld", fn_comm_world}, {"commCtx", fn_comm_ctx},
         {"commGenSyntheticSharded", fn_comm_gen}, {"commScanBatchGather", fn_comm_scan_gather}, {"commReadGathered", fn_comm_read}, {"commUPad", fn_comm_upad},

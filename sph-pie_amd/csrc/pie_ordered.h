@@ -239,6 +239,25 @@ __global__ __launch_bounds__(256) void k_ord_append(const long long* __restrict_
     ufill[u] = fill;
 }
 
+// createSession inside a turn (pie_session_turn with pie_set_turn_ordered on): the rows [row0, row0 + k) are in the TABLE when the
+// turn's kernel has finished, each with the `end` the later ops of its chain left it (a create followed by a touch or a delete of
+// the same token).  One thread per row copies the four fields into a staging block the run owns, laid out as k_ord_append reads
+// it ([start k | end k | user k | disc k], 16-byte aligned, 64 ints of slack behind it for the long-chain read); k_ord_append_mark
+// and k_ord_append then run on that block as they run on an append's, in pass 1 and, after a re-spread, in pass 2.
+__global__ __launch_bounds__(256) void k_ord_stage_rows(const long long* __restrict__ start, const long long* __restrict__ end,
+                                                        const int* __restrict__ user, const int* __restrict__ disc, long long row0, int k,
+                                                        long long* __restrict__ st_start, long long* __restrict__ st_end,
+                                                        int* __restrict__ st_user, int* __restrict__ st_disc)
+{
+    const int t = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (t >= k) return;
+    const long long r = row0 + t;
+    st_start[t] = start[r];
+    st_end[t] = end[r];
+    st_user[t] = user[r];
+    st_disc[t] = disc[r];
+}
+
 // Fresh spare slots for every segment: the rows of the run move from (uoff_old, *_old) to (uoff_new, *_new), each user's rows
 // staying in order at the head of its new segment.  A linear pass over the positions — no sort, nothing of the table is read.
 __global__ __launch_bounds__(256) void k_ord_respread(long long n_old, int seg_users, const long long* __restrict__ uoff_old,

@@ -189,6 +189,9 @@ struct BatchSlot {
 
 // the ordered run of the resident table (pie_ordered.h)
 constexpr int kOrdAppendMax = 4096; // rows of one append the run takes in place (a larger append drops the run)
+// the run's own staging block for the rows of a turn: [start | end | user | disc] of up to kOrdAppendMax rows, and the 64 ints
+// k_ord_append's long-chain path may read past the user column
+constexpr size_t kOrdTurnStageBytes = (size_t)kOrdAppendMax * 24 + 64 * 4 + 64;
 
 struct OrderedRun {
     int grid_mult = 12;      // PIE_ORD_GRID: blocks per CU of the key-stream kernels on the 1-byte key
@@ -210,6 +213,7 @@ struct OrderedRun {
     int* bhead = nullptr;                    // [users] head of the user's chain of rows in the append in progress (-1 between appends)
     int* bnext = nullptr;                    // [kOrdAppendMax] the chains: the row of the same user that came before this one, or -1
     int* placed = nullptr;                   // [2][4096] outcome per row of the append in progress (+ the copy pass 2 reads)
+    char* tstage = nullptr;                  // the rows a turn created, gathered from the table for k_ord_append (k_ord_stage_rows)
     OrdRec* alt_pay = nullptr;               // the arrays a re-spread moves the run into (allocated at the first one), then swapped
     long long* alt_end = nullptr;
     lkey_t* alt_key = nullptr;
@@ -359,6 +363,11 @@ struct pie_ctx {
         // a sharded turn that logs in (pie_shard_session_turn), from its queue phase to its wait: the creates and the new users
         // that shaped its staging block (turn_stage_of)
         size_t turn_creates = 0, turn_new_users = 0;
+        // a turn whose created rows went into the ordered run (pie_set_turn_ordered), from its launch to its wait: how many rows,
+        // the first of them, and the user count the insert ran with; 0 rows: the run was not kept, or the turn created nothing
+        size_t turn_ord_k = 0;
+        long long turn_ord_row0 = 0;
+        int turn_ord_users = 0;
         int turn_late_rc = 0;               // ... and what failed behind its launch (the wait phase reports it)
         bool timed = false;
         bool hold = false;
@@ -522,6 +531,7 @@ struct pie_ctx {
     bool batch_poor = false;    // union buckets overflowed at their largest capacity (skewed users): batches run as single scans
     bool ord_lists_only = false; // a batch's union on the ordered run outgrew the result arrays: its batches take the per-query chain
     bool wide_ordered = false;   // pie_set_wide_ordered / PIE_WIDE_ORDERED: a wide batch on a table whose batches take the ordered run runs one pass there
+    bool turn_ordered = false;   // pie_set_turn_ordered / PIE_TURN_ORDERED: a turn that logs in keeps a valid ordered run where an append would
     bool wide_ord_off = false;   // ... until the union of one outgrew the result arrays: later wide batches rerun their queries, as with the switch off
     bool run_shift_pinned = false; // PIE_RUN_SHIFT=0..3 pins it (A/B runs)
     bool last_was_batch = false; // pie_stats_get describes the last finished batch rather than the last single scan
@@ -695,7 +705,7 @@ void free_batch(pie_ctx* c)
 void ord_free(pie_ctx* c)
 {
     OrderedRun& o = c->ord;
-    dfree(o.pay); dfree(o.end); dfree(o.key); dfree(o.fkey); dfree(o.pos); dfree(o.uoff); dfree(o.ufill); dfree(o.pend); dfree(o.placed); dfree(o.bhead); dfree(o.bnext);
+    dfree(o.pay); dfree(o.end); dfree(o.key); dfree(o.fkey); dfree(o.pos); dfree(o.uoff); dfree(o.ufill); dfree(o.pend); dfree(o.placed); dfree(o.bhead); dfree(o.bnext); dfree(o.tstage);
     dfree(o.alt_pay); dfree(o.alt_end); dfree(o.alt_key); dfree(o.alt_fkey); dfree(o.alt_uoff);
     dfree(o.bq_local); dfree(o.bq_gsum); dfree(o.bq_gbase); dfree(o.bq_ctl); dfree(o.bq_sum[0]); dfree(o.bq_sum[1]);
     dfree(o.wp_rows); dfree(o.wp_mask);
@@ -1854,6 +1864,7 @@ int ord_alloc(pie_ctx* c)
                     hipMalloc(&o.ufill, ((size_t)c->cap_users + 1) * 4) == hipSuccess &&
                     hipMalloc(&o.pend, ((size_t)c->cap_users + 1) * 4) == hipSuccess && hipMalloc(&o.placed, 2 * (size_t)kOrdAppendMax * 4) == hipSuccess &&
                     hipMalloc(&o.bhead, ((size_t)c->cap_users + 1) * 4) == hipSuccess && hipMalloc(&o.bnext, (size_t)kOrdAppendMax * 4) == hipSuccess &&
+                    hipMalloc(&o.tstage, kOrdTurnStageBytes) == hipSuccess &&
                     hipMalloc(&o.unit_count[0], units * 4) == hipSuccess && hipMalloc(&o.unit_count[1], units * 4) == hipSuccess &&
                     hipMalloc(&o.unit_local, units * 4) == hipSuccess && hipMalloc(&o.group_sum, (units / 1024 + 2) * 8) == hipSuccess &&
                     hipMalloc(&o.group_base, (units / 1024 + 2) * 8) == hipSuccess &&
@@ -1981,23 +1992,26 @@ int build_ordered(pie_ctx* c)
     return PIE_OK;
 }
 
-void launch_ord_append(pie_ctx* c, hipStream_t s, size_t k, long long row0, int n_users, int pass)
+// stage: the device block that holds the k rows as [start k | end k | user k | disc k]: the append's own staging block, or the
+// run's (ord.tstage) for the rows of a turn
+void launch_ord_append(pie_ctx* c, hipStream_t s, const char* stage, size_t k, long long row0, int n_users, int pass)
 {
     OrderedRun& o = c->ord;
     const unsigned grid = (unsigned)((k + 255) / 256);
-    const int* st_user = reinterpret_cast<const int*>(c->d_stage + k * 16);
+    const int* st_user = reinterpret_cast<const int*>(stage + k * 16);
     if (pass == 2) (void)hipMemcpyAsync(o.placed + kOrdAppendMax, o.placed, k * 4, hipMemcpyDeviceToDevice, s);
     hipLaunchKernelGGL(k_ord_append_mark, dim3(grid), dim3(256), 0, s, st_user, (int)k, n_users, o.placed + kOrdAppendMax, pass, o.bhead, o.bnext);
-    hipLaunchKernelGGL(k_ord_append, dim3(grid), dim3(256), 0, s, reinterpret_cast<const long long*>(c->d_stage),
-                       reinterpret_cast<const long long*>(c->d_stage + k * 8), st_user, reinterpret_cast<const int*>(c->d_stage + k * 20), (int)k,
+    hipLaunchKernelGGL(k_ord_append, dim3(grid), dim3(256), 0, s, reinterpret_cast<const long long*>(stage),
+                       reinterpret_cast<const long long*>(stage + k * 8), st_user, reinterpret_cast<const int*>(stage + k * 20), (int)k,
                        row0, n_users, c->key_base, c->key_shift, c->fkey_base, c->fkey_shift, o.uoff, o.ufill, o.pay, o.end, o.key, o.fkey,
                        o.pos, o.stale, o.placed + kOrdAppendMax, o.placed, pass == 1 ? o.pend : (int*)nullptr, pass, o.bhead, o.bnext);
 }
 
 // Segments are full: give every user fresh spare slots (its rows, the rows of this append still waiting, a sixteenth more,
-// four) and move the run there — a linear pass, no sort.  Then the waiting rows of the append (still in the staging block)
-// take their places.  Returns with the run valid, or invalid when it no longer fits / the second pass failed too.
-int ord_respread(pie_ctx* c, size_t k, long long row0, int n_users)
+// four) and move the run there — a linear pass, no sort.  Then the waiting rows of the append (still in the staging block
+// `stage`, as launch_ord_append read them in pass 1) take their places.  Returns with the run valid, or invalid when it no longer
+// fits / the second pass failed too.
+int ord_respread(pie_ctx* c, const char* stage, size_t k, long long row0, int n_users)
 {
     OrderedRun& o = c->ord;
     hipStream_t s = c->stream;
@@ -2047,7 +2061,7 @@ int ord_respread(pie_ctx* c, size_t k, long long row0, int n_users)
     o.n = total;
     o.respreads++;
     o.h_stale[0] = o.h_stale[1] = 0;
-    launch_ord_append(c, s, k, row0, n_users, 2);
+    launch_ord_append(c, s, stage, k, row0, n_users, 2);
     PIE_HIP(c, hipGetLastError());
     PIE_HIP(c, hipStreamSynchronize(s));
     if (*(volatile unsigned int*)&o.h_stale[0] || *(volatile unsigned int*)&o.h_stale[1]) {
@@ -3979,6 +3993,7 @@ int pie_ctx_create(int device_id, pie_ctx** ctx_out)
     if (const char* v = getenv("PIE_RUN_SHIFT")) { const int r = atoi(v); if (r >= 0 && r <= 3) { c->run_shift = r; c->run_shift_pinned = true; } }
     if (const char* v = getenv("PIE_ORDERED")) { const int m = atoi(v); if (m >= 0 && m <= 2) c->ord.mode = m; }
     if (const char* v = getenv("PIE_WIDE_ORDERED")) c->wide_ordered = atoi(v) == 1;
+    if (const char* v = getenv("PIE_TURN_ORDERED")) c->turn_ordered = atoi(v) == 1;
     if (const char* v = getenv("PIE_ORD_GRID")) { const int g = atoi(v); if (g >= 1 && g <= 64) c->ord.grid_mult = g; }
     if (const char* v = getenv("PIE_WAIT_DEADLINE_MS")) { const double d = atof(v); if (d > 0) c->wait_deadline_ms = d; }
     if (const char* v = getenv("PIE_EXPQ_BLOCKS_PER_CU")) { const int g = atoi(v); if (g >= 1 && g <= 16) c->expq.blocks_per_cu = g; }
@@ -4213,7 +4228,7 @@ static int append_waited_tail(pie_ctx* c, long long old_n, size_t k, int n_users
     if (ord_kept) {
         volatile unsigned int* st = c->ord.h_stale; // [0] rows out of time order, [1] rows whose segment was full
         if (st[0] == 0 && st[1] != 0) {
-            int rc2 = ord_respread(c, k, old_n, n_users);
+            int rc2 = ord_respread(c, c->d_stage, k, old_n, n_users);
             if (rc2) return rc2;
         } else if (st[0] != 0) ord_invalidate(c, false, true);
         c->ord.h_stale[0] = c->ord.h_stale[1] = 0;
@@ -5841,6 +5856,16 @@ int pie_set_wide_ordered(pie_ctx* c, int on)
     return PIE_OK;
 }
 
+int pie_set_turn_ordered(pie_ctx* c, int on)
+{
+    if (!c) return PIE_E_INVAL;
+    if (on != 0 && on != 1) return fail(c, PIE_E_INVAL, "pie_set_turn_ordered takes 0 (off) or 1 (on)");
+    if (c->n_flight || c->b_flight) return fail(c, PIE_E_STATE, "a scan is in flight");
+    if (turns_begun(c)) return fail(c, PIE_E_STATE, "a token turn is begun and not finished (pie_token_turn_finish)");
+    c->turn_ordered = on == 1;
+    return PIE_OK;
+}
+
 int pie_host_alloc(pie_ctx* c, size_t bytes, void** host_out, void** dev_out)
 {
     if (!c || !host_out || !dev_out || bytes == 0) return PIE_E_INVAL;
@@ -6310,7 +6335,7 @@ static int append_in_place(pie_ctx* c, const Staged& st, size_t k, int n_users, 
     // the ordered run takes rows that arrive in time order into the spare slots of their users' segments
     bool ord_kept = false;
     if (c->ord.valid && c->ord.rows == old_n && k <= (size_t)kOrdAppendMax && n_users <= c->ord.users && c->key_ok) {
-        launch_ord_append(c, c->stream, k, old_n, n_users, 1); // pend[] is all zero between appends (build and re-spread leave it so)
+        launch_ord_append(c, c->stream, c->d_stage, k, old_n, n_users, 1); // pend[] is all zero between appends (build and re-spread leave it so)
         ord_kept = true;
     }
     ShardUndo undo{};
@@ -7291,11 +7316,20 @@ struct ShardTurn {
 // ... and a turn that logs in (the room is behind the caller): ONE upload of [ops | next | cuser | cdisc], ONE k_session_turn.
 // sh (a sharded context): the block also carries [crow | new users]; the new users go behind the device user map in stream order,
 // before the kernel, as append_launch puts them there; the run goes only when the shard keeps a create.
-static int session_turn_launch(pie_ctx* c, const TokStage& o, size_t k, const ShardTurn* sh = nullptr)
+// n_kept creates become the context's rows [c->n, c->n + n_kept); users_after is its own (local) user count after the turn.
+// The ordered run: dropped before the kernel could mirror into it, or — pie_set_turn_ordered, under append_in_place's
+// condition — kept: the kernel mirrors the stores to the rows from before the turn, and behind it the created rows are gathered
+// from the TABLE (k_ord_stage_rows: a later op of the turn may have re-ended one) and inserted as an append's rows are.
+// tokx.turn_ord_k tells the wait phase (turn_ord_tail) that it owes the run's bookkeeping.
+static int session_turn_launch(pie_ctx* c, const TokStage& o, size_t k, size_t n_kept, int users_after, const ShardTurn* sh = nullptr)
 {
     pie_ctx::TokenIndex& t = c->tokx;
     hot_reserve(c, (long long)k);           // every delta record of the turn is owed to an op of its own: a touch, a delete or a create
-    if (!sh || sh->n_kept) ord_invalidate(c); // the run does not take the new rows: it goes before the kernel could mirror into it
+    const long long old_n = c->n;
+    const bool ord_kept = c->turn_ordered && n_kept > 0 && c->ord.valid && c->ord.rows == old_n && n_kept <= (size_t)kOrdAppendMax &&
+                          users_after <= c->ord.users && c->key_ok;
+    if (n_kept && !ord_kept) ord_invalidate(c); // the run does not take the new rows: it goes before the kernel could mirror into it
+    t.turn_ord_k = 0;
     char* d = t.d_stage;
     PIE_HIP(c, hipMemcpyAsync(d, t.h_stage, o.up, hipMemcpyHostToDevice, c->stream));
     if (sh && sh->n_new)
@@ -7320,14 +7354,26 @@ static int session_turn_launch(pie_ctx* c, const TokStage& o, size_t k, const Sh
                            stage_at<unsigned char>(d, o.res.live), stage_at<int>(d, o.res.user), stage_at<long long>(d, o.res.start),
                            stage_at<long long>(d, o.res.end), t.status);
     PIE_HIP(c, hipGetLastError());
+    if (ord_kept) {
+        OrderedRun& r = c->ord;
+        t.turn_ord_k = n_kept; // from here on the run holds, or may hold, rows of the turn: the wait phase settles it
+        t.turn_ord_row0 = old_n;
+        t.turn_ord_users = users_after;
+        hipLaunchKernelGGL(k_ord_stage_rows, dim3((unsigned)((n_kept + 255) / 256)), dim3(256), 0, c->stream, (const long long*)c->d_start,
+                           (const long long*)c->d_end, (const int*)c->d_user, (const int*)c->d_disc, old_n, (int)n_kept,
+                           reinterpret_cast<long long*>(r.tstage), reinterpret_cast<long long*>(r.tstage + n_kept * 8),
+                           reinterpret_cast<int*>(r.tstage + n_kept * 16), reinterpret_cast<int*>(r.tstage + n_kept * 20));
+        launch_ord_append(c, c->stream, r.tstage, n_kept, old_n, users_after, 1); // pend[] is all zero between appends
+        PIE_HIP(c, hipGetLastError());
+    }
     return PIE_OK;
 }
 
 // The queue phase (the checks are behind the caller, k > 0): the plan on the host, ONE upload, ONE kernel, ONE download of the
 // results and the status words, and an event behind them.  Nothing is waited for.  n_create > 0: the turn logs in
-// (pie_session_turn), and user / disc name who.
+// (pie_session_turn), user / disc name who, and users_after is the context's own (local) user count after the turn.
 static int token_turn_queue(pie_ctx* c, const pie_turn_op* ops, size_t k, bool global, const char* what, const int32_t* user = nullptr,
-                            const int32_t* disc = nullptr, size_t n_create = 0, const ShardTurn* sh = nullptr)
+                            const int32_t* disc = nullptr, size_t n_create = 0, const ShardTurn* sh = nullptr, int users_after = 0)
 {
     pie_ctx::TokenIndex& t = c->tokx;
     PIE_HIP(c, hipSetDevice(c->device));
@@ -7345,11 +7391,39 @@ static int token_turn_queue(pie_ctx* c, const pie_turn_op* ops, size_t k, bool g
             if (ops[i].kind == PIE_TURN_CREATE) crow[j++] = per_op[i];
         shard_new_users(c->shard_users_global, sh->n_users_global, c->shard_rank, c->shard_world, stage_at<int32_t>(t.h_stage, o.newu));
     }
-    rc = n_create ? session_turn_launch(c, o, k, sh) : token_turn_launch(c, t.h_stage, t.d_stage, o, k, global, t.status, ord_mirror_of(c));
+    t.turn_ord_k = 0;
+    rc = n_create ? session_turn_launch(c, o, k, sh ? sh->n_kept : n_create, users_after, sh)
+                  : token_turn_launch(c, t.h_stage, t.d_stage, o, k, global, t.status, ord_mirror_of(c));
     if (rc == PIE_OK) rc = token_stage_download(c, o);
-    if (rc) return rc;
-    PIE_HIP(c, hipEventRecord(t.turn_done, c->stream));
-    return PIE_OK;
+    if (rc == PIE_OK && hipEventRecord(t.turn_done, c->stream) != hipSuccess) rc = fail(c, PIE_E_HIP, "%s: hipEventRecord failed", what);
+    if (rc && t.turn_ord_k) { // nobody will wait for the insert: the run may hold some of the turn's rows and not others
+        t.turn_ord_k = 0;
+        ord_invalidate(c);
+    }
+    return rc;
+}
+
+// Behind the wait of a turn whose created rows went into the ordered run (session_turn_launch): what append_waited_tail does with
+// the run's two mapped words.  [0]: a row far out of time order, or a row the run does not hold that an op of the turn brought
+// back to life — the run goes either way; [1] alone: a full segment — re-spread, then pass 2 from the run's own staging block.
+// c->n already counts the turn's rows.  failed: the status words reported a slip, so a planned row may not have been written.
+static int turn_ord_tail(pie_ctx* c, bool failed)
+{
+    pie_ctx::TokenIndex& t = c->tokx;
+    const size_t kept = t.turn_ord_k;
+    t.turn_ord_k = 0;
+    int rc = PIE_OK;
+    volatile unsigned int* st = c->ord.h_stale;
+    // plain ord_invalidate, not append_waited_tail's out_of_order form: here word 0 also counts revived rows, which say nothing
+    // about how the table is fed, so a run that dies this way raises `need` step by step instead of straight to 4 096
+    if (failed || st[0] != 0) ord_invalidate(c);
+    else if (st[1] != 0 && (rc = ord_respread(c, c->ord.tstage, kept, t.turn_ord_row0, t.turn_ord_users)) != PIE_OK) ord_invalidate(c);
+    c->ord.h_stale[0] = c->ord.h_stale[1] = 0;
+    if (c->ord.valid) {
+        c->ord.rows = c->n;
+        c->ord.held += (long long)kept;
+    }
+    return rc;
 }
 
 // The wait phase: the one wait of a turn, on its own event and bounded (pie_wait.h); then what set_end_apply does behind its
@@ -7360,17 +7434,23 @@ static int token_turn_wait(pie_ctx* c, size_t k, const char* what, int32_t* row_
     pie_ctx::TokenIndex& t = c->tokx;
     PIE_HIP(c, hipSetDevice(c->device));
     const WaitResult w = event_wait(c, t.turn_done);
+    if (w.end != WaitEnd::Ready && t.turn_ord_k) { // the insert's outcome will never be read: the run may miss rows of the turn
+        t.turn_ord_k = 0;
+        ord_invalidate(c);
+    }
     if (w.end == WaitEnd::Failed) return fail(c, PIE_E_HIP, "%s: the turn failed: %s", what, hipGetErrorString((hipError_t)w.err));
     if (w.end != WaitEnd::Ready) return fail(c, PIE_E_HIP, "%s: not finished within %.0f ms (PIE_WAIT_DEADLINE_MS): kernel hung?", what, w.waited_ms);
-    if (c->ord.h_stale && *(volatile unsigned int*)c->ord.h_stale) {
+    const TokStage o = turn_stage_of(k, n_create, shard, n_new);
+    int rc = token_status_check(c, stage_at<const unsigned int>(t.h_stage, o.status), what);
+    int rc_ord = PIE_OK;
+    if (t.turn_ord_k) rc_ord = turn_ord_tail(c, rc != PIE_OK);
+    else if (c->ord.h_stale && *(volatile unsigned int*)c->ord.h_stale) {
         *c->ord.h_stale = 0;
         ord_invalidate(c);
     }
-    const TokStage o = turn_stage_of(k, n_create, shard, n_new);
-    int rc = token_status_check(c, stage_at<const unsigned int>(t.h_stage, o.status), what);
     if (rc) return rc;
     token_results_out(t.h_stage, o.res, k, row_out, live_out, user_out, start_out, end_out);
-    return PIE_OK;
+    return rc_ord;
 }
 
 int pie_token_turn_plan(const pie_turn_op* ops, size_t k, int32_t* next_out, uint8_t* head_out)
@@ -7444,7 +7524,7 @@ int pie_session_turn(pie_ctx* c, const pie_turn_op* ops, size_t k, const int32_t
         if (rc) return rc;
     }
     if ((rc = token_make_room(c, old_n + creates, what)) != PIE_OK) return rc;
-    if ((rc = token_turn_queue(c, ops, k, false, what, user, disc, n_create)) != PIE_OK) return rc;
+    if ((rc = token_turn_queue(c, ops, k, false, what, user, disc, n_create, nullptr, n_users)) != PIE_OK) return rc;
     // the host's picture moves as an append moves it; the rows are in the stream behind everything queued so far
     c->n = old_n + creates;
     t.covered = c->n;
@@ -7930,7 +8010,7 @@ int shard_session_turn_queue(pie_ctx* c, const pie_turn_op* ops, size_t k, const
     const TokStage o = turn_stage_of(k, n_create, true, sh.n_new);
     // token_turn_queue fails before its launch (the staging, the plan) or, behind it, where only the runtime itself can fail
     // (the download, the event): such a context has a device error pending and is not used further, as on the unsharded path.
-    int rc = token_turn_queue(c, ops, k, true, what, user_global, disc, n_create, &sh);
+    int rc = token_turn_queue(c, ops, k, true, what, user_global, disc, n_create, &sh, shard_local_users(c, sh.n_new));
     if (rc) return rc;
     t.turn_new_users = sh.n_new;
     const int32_t* newu = stage_at<const int32_t>(t.h_stage, o.newu);

@@ -352,6 +352,10 @@ __global__ __launch_bounds__(256) void k_session_turn(const TurnOp* __restrict__
         rv = found ? maps.rows[row] : -1;
         uv = (uv >= 0 && uv < maps.n_users) ? maps.users[uv] : -1;
     }
+    // the ordered run (ord, when the host keeps it through the turn) holds the rows from before the turn only: a row the turn itself
+    // creates has no pos[] entry until the insert behind this kernel has run, so a store to one changes the table alone
+    const long long first_new = kShard ? maps.n_local : row0;
+    const OrdMirror no_ord{};
     long long e = e0, j = t;
     for (long long step = 0; step < k; ++step) {
         int r = rv;
@@ -374,7 +378,8 @@ __global__ __launch_bounds__(256) void k_session_turn(const TurnOp* __restrict__
                 }
             }
             if (kept) {
-                if (found && e != e0) touch_row(row, e, end, key, key_base, key_shift, fkey, fkey_base, fkey_shift, ord, hot);
+                if (found && e != e0)
+                    touch_row(row, e, end, key, key_base, key_shift, fkey, fkey_base, fkey_shift, row < first_new ? ord : no_ord, hot);
                 row = (int)nr;
                 rv = r = kShard ? (int)(row0 + c) : row;
                 found = true;
@@ -398,7 +403,7 @@ __global__ __launch_bounds__(256) void k_session_turn(const TurnOp* __restrict__
         j = nx;
         op = ops[j];
     }
-    if (found && e != e0) touch_row(row, e, end, key, key_base, key_shift, fkey, fkey_base, fkey_shift, ord, hot);
+    if (found && e != e0) touch_row(row, e, end, key, key_base, key_shift, fkey, fkey_base, fkey_shift, row < first_new ? ord : no_ord, hot);
 }
 
 // the compaction hook: the keys of the kept covered rows, in their new places

@@ -31,6 +31,9 @@ function createStore(options){
   const native = pieNative.load();                 // throws if the addon / HIP library is missing
   const ctx = native.ctxCreate(opts.device === undefined ? 0 : opts.device);   // throws without a GPU
   if(opts.orderedRun !== undefined){ native.setOrderedRun(ctx, opts.orderedRun); }
+  // turnOrdered: a turn with a create in it (createSession is one) keeps a valid ordered run where an append would, instead of
+  // dropping it (pie_set_turn_ordered; off by default, PIE_TURN_ORDERED=1 sets the context's own default)
+  if(opts.turnOrdered !== undefined){ native.setTurnOrdered(ctx, opts.turnOrdered ? 1 : 0); }
   const userIndex = new Map();                     // userId string -> dense int32
   const userIds = [];                              // dense int32 -> userId string
   let nRows = 0;                                   // rows of the device table = sessions ever created here
