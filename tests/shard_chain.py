@@ -55,6 +55,23 @@ STATES = (
 # decided by the device alone (the hot index and the ordered run); the model-only run records a stand-in for the ordered run's
 DEVICE_STATES = ("turn_on_live_hot_index_then_batch", "plain_turn_kept_ordered_run", "refused_turn_begin_on_ordered_run")
 HOST_STATES = tuple(s for s in STATES if s not in DEVICE_STATES) + ("host:turn_begin_in_ordered_chain",)
+# ... and what the chains that log in through pie_shard_session_turn (cfg["logins"]) add
+LOGIN_STATES = (
+    "shard_create_after_one_rank_compacted",             # the last compaction that dropped rows left some rank alone
+    "shard_create_doubled_slots_on_one_rank",
+    "shard_create_outgrew_capacity_on_one_rank",
+    "shard_create_first_user_of_empty_rank",
+    "shard_create_over_dropped_rows_key",                # a create under the key of a row a shard's compaction dropped
+    "shard_create_kept_by_no_live_rank_row",             # a rank that keeps no create of the turn and answers -1 for all of them
+    "shard_create_refused_short_column",                 # covered_g < N_g: PIE_E_STATE on every rank, nothing changed
+    "shard_turn_kept_ordered_run_on_keeping_rank_only",  # pie_set_turn_ordered: the keeping rank's run took the rows, another's is untouched
+    "shard_turn_create_with_lookup_begun",               # a lookup begun on one rank lands first (the header's rule), then the turn
+    "shard_turn_refused_on_one_rank_with_batch",         # PIE_E_STATE on the rank with a batch in flight, nothing changed there
+)
+LOGIN_DEVICE_STATES = ("shard_turn_kept_ordered_run_on_keeping_rank_only",)
+LOGIN_HOST_STATES = tuple(s for s in LOGIN_STATES if s not in LOGIN_DEVICE_STATES)
+# the stand-ins StoreChain.do_logins records on its way (this chain inherits it)
+LOGIN_STAND_INS = ("host:login_landed_uncovered_tail", "host:login_full_segment", "host:login_chain_of_one_user")
 
 _TZ = {}
 
@@ -185,6 +202,64 @@ class ShardStoreModel(ShardTokenModel):
             tm.index = merged
         return outs
 
+    def session_turn_plan(self, ops, user_global, U):
+        """pie_shard_session_turn_plan's four outputs restated from owner[] -> per rank (new_row_global[k], new_row_local[k],
+        creates, creates the rank keeps): the j-th create gets global row N + j on every rank, and on the rank that owns its
+        user the local row `rows the rank holds + creates it kept before this one`; -1 everywhere else"""
+        from session_turn_model import CREATE
+        owner = shard_owner(self.oracle, self.owner, int(U), self.world)
+        is_create = ops["kind"] == CREATE
+        row_g = np.where(is_create, self.N + np.cumsum(is_create) - 1, -1).astype(np.int32)
+        own = np.where(is_create, owner[np.where(is_create, np.asarray(user_global, np.int64), 0)], -1)
+        out = []
+        for r in range(self.world):
+            mine = own == r
+            row_l = np.where(mine, int(self.held(r).size) + np.cumsum(mine) - 1, -1).astype(np.int32)
+            out.append((row_g, row_l, int(is_create.sum()), int(mine.sum())))
+        return out
+
+    def session_turn(self, ops, user_global, disc, U=None):
+        """pie_shard_session_turn on every rank -> the answers per rank.  The header's defining equivalence, op by op: a CREATE is
+        pie_shard_append_rows of one row and pie_shard_token_append of its key (the rank that owns the user answers the GLOBAL
+        row, every other rank -1 / live 0 / END_NONE / user -1), every other op a pie_shard_token_turn of one op on every rank.
+        The unsharded StoreModel decides rows, liveness and ends.  The two mirrored sizes follow the turn's own room rule, made
+        once for the whole call: local rows + kept creates against the capacity, and against half the slots."""
+        from session_turn_model import CREATE
+        U = self.U if U is None else int(U)
+        k = ops.shape[0]
+        plan = self.session_turn_plan(ops, user_global, U)
+        cap, slots = list(self.cap), list(self.slots)
+        for r in range(self.world):
+            n, kept = int(self.held(r).size), plan[r][3]
+            if kept and n + kept > cap[r]:
+                cap[r] = max(n + kept, 2 * cap[r])
+            if kept and n + kept > slots[r] // 2:
+                slots[r] = slots_for(n + kept)
+        outs = [{"row": np.full(k, -1, np.int32), "live": np.zeros(k, np.uint8), "user": np.full(k, -1, np.int32),
+                 "start": np.zeros(k, np.int64), "end": np.full(k, END_NONE, np.int64), "found": np.zeros(k, bool)} for _ in range(self.world)]
+        at = 0
+        while at < k:
+            if int(ops[at]["kind"]) == CREATE:
+                now, new_end, u = int(ops[at]["now"]), int(ops[at]["new_end"]), int(user_global[at])
+                self.append_rows([now], [new_end], [u], [disc[at]], max(U, self.U))
+                self.token_append(np.asarray(ops[at]["tok"], np.uint64).reshape(1, 2))
+                o = outs[int(self.owner[u])]
+                o["row"][at], o["live"][at], o["user"][at], o["start"][at], o["end"][at], o["found"][at] = self.N - 1, new_end > now, u, now, new_end, True
+                at += 1
+                continue
+            to = at
+            while to < k and int(ops[to]["kind"]) != CREATE:
+                to += 1
+            for r, part in enumerate(self.turn(ops[at:to])):
+                for col in outs[r]:
+                    outs[r][col][at:to] = part[col]
+            at = to
+        if U > self.U:                                 # (a turn without a create still raises U_g)
+            z = np.zeros(0, np.int64)
+            self.append_rows(z, z, z.astype(np.int32), z.astype(np.int32), U)
+        self.cap, self.slots = cap, slots
+        return outs, plan
+
     def delete_user(self, u):
         rows = self.tm.delete_user(u) if 0 <= u < self.U else np.zeros(0, np.int32)
         return [rows if 0 <= u < self.U and self.owner[u] == r else np.zeros(0, np.int32) for r in range(self.world)]
@@ -231,8 +306,8 @@ class ShardStoreModel(ShardTokenModel):
 
 
 class ShardModelStore:
-    """what tests/session_turn_model.replay_g5_sessions drives, on ShardStoreModel: a login is pie_shard_append_rows of one row and
-    pie_shard_token_append of its key, every other run of ops a pie_shard_token_turn on every rank, merged by the largest row"""
+    """what tests/session_turn_model.replay_g5_sessions drives, on ShardStoreModel: every turn, logins included, goes through
+    ShardStoreModel.session_turn on every rank and is merged by the largest global row"""
 
     def __init__(self, oracle, n_users, world):
         z64, z32 = np.zeros(0, np.int64), np.zeros(0, np.int32)
@@ -241,29 +316,9 @@ class ShardModelStore:
         self.U = n_users
 
     def turn(self, ops, user, disc):
-        from session_turn_model import CREATE
-        sm, k = self.sm, ops.shape[0]
-        out = {"row": np.full(k, -1, np.int32), "live": np.zeros(k, np.uint8), "user": np.full(k, -1, np.int32),
-               "start": np.zeros(k, np.int64), "end": np.full(k, END_NONE, np.int64)}
-        at = 0
-        while at < k:
-            if int(ops[at]["kind"]) == CREATE:
-                now, new_end = int(ops[at]["now"]), int(ops[at]["new_end"])
-                kept = sm.append_rows([now], [new_end], [user[at]], [disc[at]], self.U)
-                assert sum(kept) == 1
-                sm.token_append(np.asarray(ops[at]["tok"], np.uint64).reshape(1, 2))
-                out["row"][at], out["live"][at], out["user"][at] = sm.N - 1, new_end > now, user[at]
-                out["start"][at], out["end"][at] = now, new_end
-                at += 1
-                continue
-            to = at
-            while to < k and int(ops[to]["kind"]) != CREATE:
-                to += 1
-            part = merge(sm.turn(ops[at:to]))
-            for col in out:
-                out[col][at:to] = part[col]
-            at = to
-        return out
+        outs, plan = self.sm.session_turn(ops, user, disc, self.U)
+        assert sum(p[3] for p in plan) == plan[0][2], "the ranks keep the creates between them"
+        return merge(outs)
 
     def delete_user(self, u):
         self.sm.delete_user(u)
@@ -285,6 +340,7 @@ class CtxDriver:
                 c = ctx_with_env(pie, cfg["hot"], cfg["async"])
                 self.ctxs.append(c)
                 c.set_ordered_run(cfg["ordered"])
+                c.set_turn_ordered(cfg.get("turn_ordered", 0))
                 c.set_batch_lanes(cfg["lanes"])
                 c.gen_synthetic(cfg["gen_seed"], n, 0, n, U, D, 0)
                 c.shard_table(r, cfg["world"])
@@ -331,6 +387,13 @@ def shard_config(seed):
     }
 
 
+def shard_logins_config(seed):
+    """the draws of a chain that logs in, from a stream of their own (shard_config's stay what they were): the sizes of the designed
+    shard chains, a mode that builds runs more often than not, the switch mostly on"""
+    rng = np.random.default_rng([seed, 0x10616])
+    return {"n": int(rng.choice([65, 4099])), "hot": 0, "ordered": int(rng.choice([0, 1, 2, 2])), "turn_ordered": int(rng.choice([0, 1, 1, 1]))}
+
+
 class ShardChain(StoreChain):
     """One seeded chain: `world` shards of one generated table with a token column, a context configuration, 25 to 40 steps (or
     the fixed list `script`).  Every step is one mutator or in-flight form, the state checks on every rank, and the readers."""
@@ -338,10 +401,19 @@ class ShardChain(StoreChain):
     OPS = ("append", "append", "append", "token_append", "set_end", "set_end", "token_set_end", "token_turn", "token_turn",
            "delete_user", "delete_users", "prune", "retention", "retention_tz", "compact", "compact", "compact",
            "inflight_lookup", "inflight_turn", "inflight_purge", "refusals")
+    OPS_LOGINS = OPS + ("session_turn", "session_turn", "session_turn", "logins", "logins", "logins_chain", "logins_undo")
+    NEW_OPS = ("session_turn", "logins", "logins_chain", "logins_undo")
 
     def __init__(self, pie, oracle, seed, cfg=None, script=None, log=None):
         self.pie, self.oracle, self.seed = pie, oracle, seed
-        self.cfg = dict(shard_config(seed), **(cfg or {}))
+        self.cfg = dict(shard_config(seed), logins=0, turn_ordered=0)
+        if (cfg or {}).get("logins"):
+            self.cfg.update(shard_logins_config(seed))
+            if self.cfg["U"] == 499:
+                self.cfg["U"] = 64
+        self.cfg.update(cfg or {})
+        self.ops = self.OPS_LOGINS if self.cfg["logins"] else self.OPS
+        self.since_compact, self.login_since_begin = None, False      # (StoreChain.do_logins' bookkeeping)
         self.script, self.log = script, log
         self.rng = np.random.default_rng([seed, 0x5A4E])
         self.t0 = oracle.T0_MS
@@ -382,7 +454,7 @@ class ShardChain(StoreChain):
             steps = len(self.script) if self.script else c["steps"]
             for step in range(-1, steps):
                 self.step = step
-                op = "load" if step < 0 else self.script[step] if self.script else str(rng.choice(self.OPS))
+                op = "load" if step < 0 else self.script[step] if self.script else str(rng.choice(self.ops))
                 tag = "seed %s world %d step %d %s" % (self.seed, self.world, step, op)
                 if self.log:
                     self.log("%s N %d U %d covered %d slots %s cap %s" % (tag, sm.N, sm.U, sm.covered_g, sm.slots, sm.cap))
@@ -416,7 +488,7 @@ class ShardChain(StoreChain):
 
     # ---- bookkeeping
     def saw(self, state):
-        assert state in STATES or state in HOST_STATES, state
+        assert state in STATES or state in HOST_STATES or state in LOGIN_STATES or state in LOGIN_STAND_INS, state
         self.states[state] = self.states.get(state, 0) + 1
 
     def skip(self, tag):
@@ -765,6 +837,144 @@ class ShardChain(StoreChain):
                 self.turn_on((tag, k), r, ops, want[r])
         self.check_state((tag, k))
 
+    # ---- turns that log in: pie_shard_session_turn on every rank, users as GLOBAL ids
+    def do_session_turn(self, tag, variant=None):
+        """StoreChain.turn_ops' mix (creates with clocks anywhere, known and tombstoned keys re-used), some creates naming users no
+        rank has yet, one under the key of a row a compaction dropped"""
+        rng, sm = self.rng, self.sm
+        k, p = int(rng.choice([1, 7, 64, 257, 300])), float(rng.choice([0.0, 0.1, 0.2, 0.4]))
+        new_users = int(rng.choice([0, 0, 1, 3]))
+        if variant == "users":                       # (designed chains) 64 ops, 40 % creates, three of them for users nobody has yet
+            k, p, new_users = 64, 0.4, 3
+        ops, user, disc = self.turn_ops(k, p)
+        is_create = np.nonzero(ops["kind"] == 3)[0]
+        new_users = min(new_users, is_create.size)
+        user[is_create[:new_users]] = sm.U + np.arange(new_users)
+        gone_keyed = np.nonzero(sm.gone[:sm.covered_g])[0]
+        if is_create.size and gone_keyed.size:
+            ops["tok"][is_create[-1]] = sm.tm.keys[int(rng.choice(gone_keyed))]
+        self.apply_turn((tag, k, p), ops, user, disc, True, sm.U + new_users)
+
+    def apply_turn(self, tag, ops, user, disc, session=True, U2=None):
+        """one turn that may log in, given to every context with the same arrays; the answers, the plan's four outputs and the
+        ordered run's bookkeeping per rank, then everything check_state checks after a mutator"""
+        rng, sm, drv, world = self.rng, self.sm, self.drv, self.world
+        U2 = sm.U if U2 is None else U2
+        is_create = ops["kind"] == 3
+        if is_create.any() and sm.covered_g < sm.N:
+            # a keyed turn is only defined with covered_g == N_g: every rank refuses, none changes
+            self.expect(tag, PIE_E_STATE, lambda c: c.shard_session_turn(ops, user, disc, U2))
+            self.saw("shard_create_refused_short_column")
+            self.check_state((tag, "refused"))
+        if is_create.any() and (sm.covered_g < sm.N or sm.N + int(is_create.sum()) > MAX_ROWS):
+            ops, user, disc, U2 = ops[~is_create], user[~is_create], disc[~is_create], sm.U
+            is_create = is_create[~is_create]
+        if ops.shape[0] == 0:
+            return self.skip(tag)
+        creates, N0 = int(is_create.sum()), sm.N
+        top = int(sm.tm.start.max()) if N0 else INT64_MIN
+        in_order = bool(np.all(ops["now"][is_create] >= top))
+        held0 = [int(sm.held(r).size) for r in range(world)]
+        users0 = [int(sm.users_of(r).size) for r in range(world)]
+        cap0, slots0 = list(sm.cap), list(sm.slots)
+        dropped_keys = {tuple(k) for k in sm.tm.keys[np.nonzero(sm.gone[:sm.covered_g])[0]].tolist()} if creates else set()
+        if creates and any(tuple(k) in dropped_keys for k in ops["tok"][is_create].tolist()):
+            self.saw("shard_create_over_dropped_rows_key")
+        if creates and self.part_compacted:
+            self.saw("shard_create_after_one_rank_compacted")
+        # one rank with something of its own in flight: a batch refuses the turn there (PIE_E_STATE, nothing changed on it); a lookup
+        # begun does not: it lands first
+        busy = int(rng.integers(world))
+        how = str(rng.choice(["none", "batch", "lookup"])) if creates else "none"
+        qs = self.query_set(16, dense=False)
+        lkeys = np.concatenate([self.issued[:200], self.absent[:4]])
+        lnow = self.clocks(lkeys.shape[0])
+        lwant = sm.shard_lookup(busy, lkeys, lnow) if how == "lookup" else None
+        if how == "batch" and held0[busy] > 0:
+            self.saw("shard_turn_refused_on_one_rank_with_batch")
+            if drv:
+                c = self.ctx = drv.ctxs[busy]
+                wants = sm.view(busy)[0].scan_many(qs)
+                c.scan_batch_begin(qs)
+                self.expect_one(tag, PIE_E_STATE, busy, lambda x: x.shard_session_turn(ops, user, disc, U2))
+                self.finish_one((tag, "rank", busy, "the batch in flight"), False, qs, wants)
+                self.check_state((tag, "refused on one rank"))
+        if how == "lookup":
+            self.saw("shard_turn_create_with_lookup_begun")
+            if drv:
+                drv.ctxs[busy].shard_token_lookup_begin(lkeys, lnow)
+        before = drv.each(lambda c: c.table_info()) if drv else None
+        want, plan = sm.session_turn(ops, user, disc, U2)
+        kept = [p[3] for p in plan]
+        assert sum(kept) == creates, (tag, "the model's shards do not keep the creates between them")
+        merged, whole = merge(want), None
+        if creates:
+            assert np.array_equal(merged["row"][is_create], N0 + np.arange(creates)), (tag, "the merged answer of a create is its global row")
+        if drv:
+            for r, c in enumerate(drv.ctxs):
+                _, _, row_g, row_l, n_create, n_kept = self.pie.shard_session_turn_plan(ops, user, N0, held0[r], r, world)
+                assert np.array_equal(row_g, plan[r][0]) and np.array_equal(row_l, plan[r][1]), (tag, "rank", r, "the plan's rows")
+                assert (n_create, n_kept) == plan[r][2:], (tag, "rank", r, "the plan's counts", n_create, n_kept, plan[r][2:])
+            got = drv.each(lambda c: c.shard_session_turn(ops, user, disc, U2))
+            if how == "lookup":
+                self.same_lookup(drv.ctxs[busy].shard_token_lookup_finish(), lwant, (tag, "rank", busy, "the lookup begun before the turn"))
+            for r in range(world):
+                self.check_turn(tag, r, got[r], want[r])
+                other = is_create & ~want[r]["found"]
+                assert np.all(got[r]["row"][other] == -1) and np.all(got[r]["user"][other] == -1), (tag, "rank", r, "a create another rank keeps")
+            self.same_lookup_rows(tag, merge(got), merged)
+            self.check_runs_after_logins(tag, before, drv.each(lambda c: c.table_info()), kept, in_order, cap0, users0)
+        if creates:
+            grew = [r for r in range(world) if sm.cap[r] > cap0[r]]
+            doubled = [r for r in range(world) if sm.slots[r] > slots0[r]]
+            if grew and len(grew) < world:
+                self.saw("shard_create_outgrew_capacity_on_one_rank")
+            if doubled and len(doubled) < world:
+                self.saw("shard_create_doubled_slots_on_one_rank")
+            if grew or doubled:
+                self.reshaped = True
+            if any(not users0[r] and kept[r] for r in range(world)):
+                self.saw("shard_create_first_user_of_empty_rank")
+            if world > 1 and any(k == 0 for k in kept):
+                self.saw("shard_create_kept_by_no_live_rank_row")
+            self.issued = np.concatenate([self.issued, ops["tok"][is_create]])
+            self.shrunk = False
+            named = set(user[is_create].tolist())
+            self.rowless = [g for g in self.rowless if g not in named]
+        self.check_state(tag)
+
+    def same_lookup_rows(self, tag, got, want):
+        for col in ("row", "live"):
+            assert np.array_equal(got[col], want[col]), (tag, "merged by the largest global row", col, np.nonzero(got[col] != want[col])[0][:8])
+
+    def check_runs_after_logins(self, tag, before, after, kept, in_order, cap0, users0):
+        """StoreChain.check_run_after_logins per rank, in the rank's local numbers: a rank that keeps no create is untouched; one
+        that keeps some drops its run with the switch off or when its columns grew, and keeps it — every kept row in it, no build —
+        when the run was valid, the creates came in order and the rank gained no user; everywhere else a valid run is kept whole
+        or dropped (a valid run holding no row reports 0, like no run, and is left undecided).  The scans and batches behind the
+        turn are compared with the model on every rank by the readers; that a query which took the run before a keeping turn still
+        takes it (k1_variant & 0x2000) is checked by StoreChain alone, on plain contexts."""
+        sm, on = self.sm, bool(self.cfg["turn_ordered"])
+        took, untouched = False, False
+        for r in range(self.world):
+            b, a = int(before[r]["ordered_rows"]), int(after[r]["ordered_rows"])
+            t = (tag, "rank", r, "ordered run", b, a, kept[r])
+            if kept[r] == 0:
+                assert a == b and after[r]["ordered_builds"] == before[r]["ordered_builds"], (t, "a rank that keeps no create")
+                untouched = untouched or b > 0
+            elif not on or sm.cap[r] > cap0[r]:
+                assert a == 0, (t, "switch off, or columns that moved")
+            elif b > 0 and in_order and kept[r] <= 4096 and int(sm.users_of(r).size) == users0[r]:
+                assert a == b + kept[r] and after[r]["ordered_builds"] == before[r]["ordered_builds"], (t, "in-order logins on a valid run")
+                assert int(after[r]["ordered_respreads"]) - int(before[r]["ordered_respreads"]) in (0, 1), t
+                took = True
+            elif b > 0:
+                # a create before the top, or a rank that gained a user (the run has room for the users its columns had room for
+                # when it was built, which the chain does not mirror): kept whole or dropped, nothing in between
+                assert a == 0 or (a == b + kept[r] and after[r]["ordered_builds"] == before[r]["ordered_builds"]), (t, "neither kept nor dropped")
+        if took and untouched:
+            self.saw("shard_turn_kept_ordered_run_on_keeping_rank_only")
+
     # ---- deletes and maintenance by global id
     def do_delete_user(self, tag):
         rng, sm = self.rng, self.sm
@@ -1074,6 +1284,24 @@ DESIGNED = {
     "empty_rank": ({"world": 5, "n": 65, "U": 7, "D": 8, "hot": 0, "ordered": 1, "lanes": 1, "async": 0, "dup": True},
                    ["append:users", "delete_user", "append:users", "append:wave", "append:rank600", "token_append", "compact:shrink_some", "append:one_rank", "token_turn", "token_set_end", "inflight_turn", "refusals"]),
 }
+
+
+# Chains that log in through the turn (a dict of their own: DESIGNED's names give its chains their seeds)
+DESIGNED_LOGINS = {
+    # world 5 over 7 users starts with a rank that owns nobody: new users until it gains one, by a create
+    "empty_rank": ({"world": 5, "n": 65, "U": 7, "D": 8, "hot": 0, "ordered": 2, "lanes": 2, "async": 0, "dup": False, "turn_ordered": 1, "logins": 1},
+                   ["session_turn:users", "session_turn:users", "logins", "session_turn:users", "session_turn:users", "logins_chain"]),
+    # about 500 rows and 1 024 slots a rank: a few logins carry one rank past half its slots before the other; one-user chains are
+    # kept by one rank, whose run takes them while the other's stays as it was
+    "slots": ({"world": 2, "n": 1000, "U": 64, "D": 8, "hot": 0, "ordered": 2, "lanes": 2, "async": 1, "dup": False, "turn_ordered": 1, "logins": 1},
+              ["logins", "logins_chain", "logins", "logins_chain", "logins_undo", "compact:one", "logins_chain", "logins", "logins_chain",
+               "inflight_turn", "logins"]),
+}
+
+
+def run_designed_logins(pie, oracle, name):
+    cfg, script = DESIGNED_LOGINS[name]
+    return ShardChain(pie, oracle, 9300 + sorted(DESIGNED_LOGINS).index(name), cfg, script).run()
 
 
 def run_shard_chain(pie, oracle, seed, cfg=None, script=None, log=None):

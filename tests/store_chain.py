@@ -13,7 +13,12 @@ decided without a device.
 
 StoreChain(pie or None, oracle, seed) drives a context and the model side by side, or — pie = None — the model alone with the
 very same random draws (no draw depends on the device).  The model is the only source of expected values; the first difference
-raises, tagged with seed, step and op.  Nothing here needs a GPU to import."""
+raises, tagged with seed, step and op.  Nothing here needs a GPU to import.
+
+cfg["logins"] (off unless asked for) makes a chain of another kind: OPS_LOGINS adds turns whose creates are stamped at or after the
+table's top, pie_set_turn_ordered is part of the configuration (logins_config, a random stream of its own), and after every
+creating turn check_run_after_logins decides on the host whether the ordered run had to survive.  A chain without the option
+draws exactly what it drew before the option existed (tests/golden/store_chain_oplog.txt)."""
 import numpy as np
 
 from compact_model import CompactModel, compact_maps, translate
@@ -46,6 +51,29 @@ STATES = (
     "refused_session_turn_with_batch",
     "refused_create_on_short_column",
 )
+# ... and what the chains that log in (cfg["logins"]) add: a creating turn under pie_set_turn_ordered, in the state the others leave
+LOGIN_STATES = (
+    "creating_turn_kept_ordered_run",         # the run valid before, every row of the turn in it afterwards, nothing rebuilt
+    "kept_run_then_batch_on_run",             # the batch that took the run before a keeping turn takes it afterwards
+    "kept_run_respread",                      # ordered_respreads rose inside a turn
+    "kept_run_after_compact_shrink",          # the first turn that keeps the run since a compaction dropped rows (with
+    "kept_run_after_compact_noshrink",        # PIE_COMPACT_SHRINK the turn right behind it has to grow the columns, and drops it)
+    "kept_run_with_live_hot_index",
+    "kept_run_create_then_delete_in_turn",    # a later op of the turn ended a row it created: the insert reads the table's `end`
+    "kept_run_then_refused_inflight_begin",   # pie_token_turn_begin refused on the run a creating turn kept
+    "back_fill_dropped_run",                  # a create before the table's top, the run gone
+    "growth_dropped_run_switch_on",
+)
+# (A row the run does not hold was a tombstone, end = INT64_MIN, when the run was built.  turn_apply in sph-pie_amd/csrc/pie_token.h
+# is the only place a get / touch / delete of k_token_turn and k_session_turn moves `end`: a TOUCH writes only when `e > op.now`,
+# which INT64_MIN never is for an int64 clock; a DELETE writes INT64_MIN; a CREATE writes a row of its own at or behind the turn's
+# first new row.  So no op of a turn brings such a row back to life, and "a creating turn revived a row and dropped the run" is
+# not a state a chain can arrive at.  pie_set_end can revive one, outside a turn: do_set_end does, between the logins, and
+# the first login the host expects to keep the run after it is recorded as host:login_since_set_end_revived_row.)
+LOGIN_HOST_STATES = ("host:login_in_order_switch_on", "host:login_in_order_switch_off", "host:login_grew_switch_on", "host:login_before_top",
+                     "host:login_create_then_delete", "host:login_since_compact_shrink", "host:login_since_compact_noshrink",
+                     "host:login_full_segment", "host:login_chain_of_one_user", "host:login_landed_uncovered_tail",
+                     "host:begin_after_login", "host:login_since_set_end_revived_row")
 # decided by the device alone (the hot index and the ordered run); the model-only run records a stand-in for two of them
 DEVICE_STATES = ("turn_on_live_hot_index_then_batch", "hot_index_rebuilt_between_turns", "plain_turn_kept_ordered_run",
                  "creating_turn_dropped_ordered_run", "refused_begin_on_ordered_run")
@@ -155,6 +183,16 @@ def store_config(seed):
     }
 
 
+def logins_config(seed):
+    """the draws of a chain that logs in, from a stream of their own (store_config's draws stay what they were): the sizes of the
+    existing `ordered` designed chain and below, a mode that builds runs, the switch mostly on"""
+    rng = np.random.default_rng([seed, 0x10615])
+    return {
+        "n": int(rng.choice([1, 700, 3000, 4099])), "U": int(rng.choice([7, 64])), "D": int(rng.choice([1, 8])), "hot": 0,
+        "ordered": int(rng.choice([1, 2, 2, 2])), "turn_ordered": int(rng.choice([0, 1, 1, 1])),
+    }
+
+
 class StoreChain(Chain):
     """One seeded chain: a table with a token column, a context configuration, 30 to 50 steps (or the fixed list `script`).
     Every step is one mutator or in-flight form, the state checks, and the readers.  run() raises at the first difference."""
@@ -162,10 +200,16 @@ class StoreChain(Chain):
     OPS = ("session_turn", "session_turn", "session_turn", "session_turn", "token_turn", "token_set_end", "set_end", "set_end",
            "append", "append", "delete_user", "delete_users", "prune", "retention", "compact", "compact", "compact",
            "inflight_turn", "inflight_lookup", "inflight_purge", "turn_vs_batch")
+    # cfg["logins"]: the same mix with the in-order logins among it (a tuple of its own: OPS draws what it always drew)
+    OPS_LOGINS = OPS + ("logins", "logins", "logins", "logins", "logins_chain", "logins_full", "logins_undo", "logins_late")
 
     def __init__(self, pie, oracle, seed, cfg=None, script=None, log=None):
         self.pie, self.oracle, self.seed = pie, oracle, seed
-        self.cfg = dict(store_config(seed), **(cfg or {}))
+        self.cfg = dict(store_config(seed), logins=0, turn_ordered=0)
+        if (cfg or {}).get("logins"):
+            self.cfg.update(logins_config(seed))
+        self.cfg.update(cfg or {})
+        self.ops = self.OPS_LOGINS if self.cfg["logins"] else self.OPS
         self.script = script
         self.rng = np.random.default_rng([seed, 0x570E])
         self.log = log
@@ -186,6 +230,14 @@ class StoreChain(Chain):
         self.builds_at_turn, self.dropped_since_turn, self.rebuilt_since_turn = None, False, False
         self.builds0 = 0
         self.compactions = 0
+        # chains that log in
+        self.skipped = 0                                # steps that gave the library no call of their op: no room for the logins, a
+                                                        # turn left without an op, a purge tick on a table without rows
+        self.last_scan, self.last_batch = None, None    # the readers' last scan and batch, for the same queries around a turn
+        self.since_compact = None                       # "shrink" / "noshrink": rows dropped, and no turn has kept the run since
+        self.kept_builds = None                         # ordered_builds at the last turn that kept the run
+        self.login_since_begin = False
+        self.host_kept_seen, self.revived_since_kept = False, False   # pie_set_end revived a tombstone since the last keeping login
 
     # ---- set-up
     def make_table(self):
@@ -205,6 +257,7 @@ class StoreChain(Chain):
             keys = self.rng.integers(0, 2 ** 64, (m.n, 2), dtype=np.uint64)
             if self.ctx:
                 ctx.set_ordered_run(c["ordered"])
+                ctx.set_turn_ordered(c["turn_ordered"])
                 ctx.set_batch_lanes(c["lanes"])
                 ctx.set_wide_ordered(c["wide_ordered"])
                 ctx.load_columns(*m.columns(), m.U)
@@ -217,7 +270,7 @@ class StoreChain(Chain):
             steps = len(self.script) if self.script else c["steps"]
             for step in range(-1, steps):
                 self.step = step
-                op = "load" if step < 0 else self.script[step] if self.script else str(self.rng.choice(self.OPS))
+                op = "load" if step < 0 else self.script[step] if self.script else str(self.rng.choice(self.ops))
                 tag = "seed %d step %d %s" % (self.seed, step, op)
                 if self.log:
                     self.log("%s n %d covered %d slots %d cap %d" % (tag, m.n, m.covered, m.slots, m.cap))
@@ -239,7 +292,7 @@ class StoreChain(Chain):
 
     # ---- bookkeeping
     def saw(self, state):
-        assert state in STATES or state in HOST_STATES, state
+        assert state in STATES or state in HOST_STATES or state in LOGIN_STATES or state in LOGIN_HOST_STATES, state
         self.states[state] = self.states.get(state, 0) + 1
 
     def info(self):
@@ -354,7 +407,9 @@ class StoreChain(Chain):
             same(ctx.scan(now, cutoff), m.scan(now, cutoff, self.mask), (tag, "scan", kind, now, cutoff))
         self.scanned_since_drop = True
         # one batch of sixteen: without a dense query on even steps (a batch that keeps its union), with one on odd steps
-        self.one_batch((tag, "batch"), self.query_set(16, dense=bool(self.step % 2)), False)
+        qs = self.query_set(16, dense=bool(self.step % 2))
+        self.last_scan, self.last_batch = (now, cutoff), qs
+        self.one_batch((tag, "batch"), qs, False)
         if self.step % 4 == 3:
             self.one_batch((tag, "wide"), self.query_set(70, dense=False), True)
             now = self.pick_now(str(rng.choice(["sparse", "below_p90", "above", "dense"])))
@@ -425,6 +480,7 @@ class StoreChain(Chain):
             ops, user, disc = ops[~is_create], user[~is_create], disc[~is_create]
             is_create = is_create[~is_create]
         if ops.shape[0] == 0:
+            self.skipped += 1                    # a turn of creates alone, all of them refused: nothing was run
             return
         creates = int(is_create.sum())
         if creates:
@@ -444,13 +500,21 @@ class StoreChain(Chain):
                 self.saw("host:creating_turn_in_ordered_chain")
         before = self.info() if ctx else None
         slots, cap = m.slots, m.cap
+        logins = bool(creates and self.cfg["logins"])
+        n_before = m.n
+        in_order = bool(np.all(ops["now"][is_create] >= (int(m.start.max()) if m.n else INT64_MIN))) if creates else True
+        probe = self.run_probe((tag, "before the turn")) if logins and ctx and before["ordered_rows"] > 0 else None
         want = m.turn(ops, user, disc)
+        if logins:
+            host_kept = self.login_host_states(creates, in_order, m.cap > cap, bool(np.any(m.end[n_before:] == END_NONE)))
         if ctx:
             got = ctx.session_turn(ops, user, disc, m.U) if session else ctx.token_turn(ops)
             same_turn(got, want, tag)
             f = want["found"]
             assert np.array_equal(got["user"][f], want["user"][f]) and np.array_equal(got["start"][f], want["start"][f]), (tag, "user / start")
             after = ctx.table_info()
+            if logins:
+                self.check_run_after_logins(tag, before, after, creates, in_order, m.cap > cap, n_before, probe)
             if creates and after["token_builds"] > before["token_builds"]:
                 self.saw("create_doubled_slots")
             if creates and after["table_bytes"] > before["table_bytes"]:
@@ -469,6 +533,8 @@ class StoreChain(Chain):
                 self.saw("create_doubled_slots")
             if creates and m.cap > cap:
                 self.saw("create_outgrew_capacity")
+        if logins and host_kept:
+            self.since_compact = None
         if creates:
             self.issued = np.concatenate([self.issued, ops["tok"][is_create]])
             self.column_last, self.straddle = "turn", None
@@ -477,6 +543,168 @@ class StoreChain(Chain):
                 self.reshaped = True
         self.touched = True
         self.check_state(tag)
+
+    # ---- turns that log in under pie_set_turn_ordered (cfg["logins"])
+    def run_probe(self, tag):
+        """the readers' last scan and last batch once more, against the model -> (the scan took the run, the batch took it).
+        No draw: the model-only run makes none here either."""
+        ctx, m = self.ctx, self.m
+        now, cutoff = self.last_scan
+        same(ctx.scan(now, cutoff), m.scan(now, cutoff, self.mask), (tag, "scan", now, cutoff))
+        scan_on_run = bool(ctx.stats()["k1_variant"] & 0x2000)
+        qs = self.last_batch
+        wants = m.scan_many(qs)
+        ctx.scan_batch_begin(qs)
+        self.finish_one((tag, "batch"), False, qs, wants)
+        return scan_on_run, bool(ctx.stats()["k1_variant"] & 0x2000)
+
+    def login_host_states(self, creates, in_order, grew, ended_own):
+        """what a host can say of a creating turn: the stand-ins the model-only run records"""
+        on = bool(self.cfg["turn_ordered"])
+        host_kept = on and in_order and not grew and creates <= 4096
+        self.saw("host:login_grew_switch_on" if on and grew else "host:login_before_top" if not in_order else
+                 "host:login_in_order_switch_on" if on else "host:login_in_order_switch_off")
+        if host_kept and ended_own:
+            self.saw("host:login_create_then_delete")
+        if host_kept and self.since_compact:
+            self.saw("host:login_since_compact_" + self.since_compact)
+        if host_kept and self.revived_since_kept:
+            self.saw("host:login_since_set_end_revived_row")
+        if host_kept:
+            self.host_kept_seen, self.revived_since_kept = True, False
+        self.login_since_begin = True
+        return host_kept
+
+    def check_run_after_logins(self, tag, before, after, creates, in_order, grew, n_before, probe):
+        """the run's bookkeeping behind a turn with creates, decided here wherever a host can decide it (include/pie_scan.h,
+        pie_set_turn_ordered): switch off or a table that grew -> dropped; a valid run, the switch on, no growth, at most 4 096
+        creates, no new user, every start at or after the table's top -> kept with every created row in it, nothing rebuilt, at
+        most one re-spread; a create before the top -> kept or dropped (the 256 of the header are run positions), recorded.
+        ordered_rows counts the rows the run HOLDS: rows that were tombstones (end = END_NONE) when it was built are not in it, so
+        in a chain that deletes, a valid run reports fewer rows than the table has, and what a keeping turn owes is + creates; where
+        the run held the whole table before, it holds the whole table afterwards.  Whether the run was valid before the turn is
+        read from the device (a mode-1 run exists or not by the library's own choice): a run the library lost without cause before
+        the turn goes unnoticed here, and is bounded only by the states the chains must reach."""
+        ctx, m = self.ctx, self.m
+        on = bool(self.cfg["turn_ordered"])
+        rows = lambda i: int(i["ordered_rows"])
+        valid = rows(before) > 0
+        assert (after["table_bytes"] > before["table_bytes"]) == grew, (tag, "the model's capacity and the table's disagree on growth")
+        if not on or grew:
+            assert rows(after) == 0, (tag, "a run behind a creating turn with the switch off, or on columns that moved", rows(after))
+            if valid and on:
+                self.saw("growth_dropped_run_switch_on")
+            return
+        if not valid:
+            return      # no run, or a valid one that holds no row (it reports 0 as well): nothing to decide
+        kept = rows(after) > 0
+        if in_order and creates <= 4096:
+            assert kept, (tag, "in-order logins dropped a valid run", rows(before), n_before, creates)
+        if not kept:
+            self.saw("back_fill_dropped_run")
+            return
+        assert rows(after) == rows(before) + creates, (tag, "rows the kept run holds", rows(before), creates, rows(after))
+        if rows(before) == n_before:
+            assert rows(after) == m.n
+        assert after["ordered_builds"] == before["ordered_builds"], (tag, "a kept run was rebuilt inside the turn")
+        respread = int(after["ordered_respreads"]) - int(before["ordered_respreads"])
+        assert respread in (0, 1), (tag, "re-spreads inside one turn", respread)
+        self.saw("creating_turn_kept_ordered_run")
+        if respread:
+            self.saw("kept_run_respread")
+        if self.since_compact:
+            self.saw("kept_run_after_compact_" + self.since_compact)
+        if before["hot_rows"] > 0 and after["hot_rows"] > 0:
+            self.saw("kept_run_with_live_hot_index")
+        if np.any(m.end[n_before:] == END_NONE):
+            self.saw("kept_run_create_then_delete_in_turn")
+        self.kept_builds = int(after["ordered_builds"])
+        # the queries that took the run before the turn take it behind it, and answer for the table with the new rows
+        scan_was, batch_was = probe
+        scan_is, batch_is = self.run_probe((tag, "behind the keeping turn"))
+        assert scan_is or not scan_was, (tag, "the scan that took the run before a keeping turn left it", self.last_scan)
+        assert batch_is or not batch_was, (tag, "the batch that took the run before a keeping turn left it")
+        if batch_was and batch_is:
+            self.saw("kept_run_then_batch_on_run")
+        info = ctx.table_info()
+        assert rows(info) == rows(after) and info["ordered_builds"] == after["ordered_builds"], (tag, "the reads behind the turn ran on the run it kept")
+
+    def do_logins(self, tag, variant="plain"):
+        """a session turn whose creates carry clocks at or after every start of the table (tests/test_gpu_turn_ordered.logins),
+        in any array order, among gets, touches and deletes of known keys and of keys the same turn creates.
+        chain: 2 to 9 creates of one user, the starts descending; full: 25 creates of one user, more than a segment's spare slots
+        (test_a_full_segment); undo: a create whose row a later op of the turn deletes; late: one create five minutes before the
+        top; far: one create a day before the first row of the user with the most rows."""
+        rng, m = self.rng, self.m
+        if self.pending is not None:          # pie_token_append on the uncovered tail first: a create needs the whole column
+            self.pending_due = self.step
+            self.land_pending(tag)
+            self.saw("host:login_landed_uncovered_tail")
+        top = int(m.start.max()) if m.n else self.t0 - DAY
+        kc = {"plain": int(rng.integers(1, 40)), "chain": int(rng.integers(2, 10)), "full": 25}.get(variant, int(rng.integers(2, 40)))
+        ko = int(rng.integers(0, 60))
+        if m.n + kc > MAX_ROWS:
+            self.skipped += 1
+            return
+        new = rng.integers(0, 2 ** 64, (kc, 2), dtype=np.uint64)
+        tomb = self.tombstoned_keys()
+        if tomb.shape[0] and rng.random() < 0.5:
+            new[kc - 1] = tomb[int(rng.integers(tomb.shape[0]))]      # a login under a key whose row a maintenance call ended
+        at = top + np.sort(rng.integers(0, 1000, kc))
+        user = rng.integers(0, m.U, kc)
+        if variant in ("chain", "full"):
+            user[:] = int(rng.integers(m.U))
+            self.saw("host:login_full_segment" if variant == "full" else "host:login_chain_of_one_user")
+        if variant == "chain":
+            at = top + 10 * (kc - np.arange(kc))
+        if variant == "late":
+            at[-1] = top - 5 * 60 * 1000
+        if variant == "far" and m.n:
+            user[-1] = int(np.bincount(m.user, minlength=m.U).argmax())
+            at[-1] = int(m.start[m.user == user[-1]].min()) - DAY
+        creates = np.zeros(kc, TURN_OP)
+        creates["tok"], creates["now"], creates["kind"] = new, at, CREATE
+        creates["new_end"] = self.clocks(kc) + rng.integers(-HOUR, 12 * HOUR, kc)
+        others = np.zeros(ko, TURN_OP)
+        others["tok"] = self.some_keys(ko)
+        others["kind"] = rng.choice([GET, TOUCH, DELETE], ko, p=[0.8, 0.15, 0.05])
+        others["now"] = self.clocks(ko)
+        others["new_end"] = np.where(others["kind"] == TOUCH, others["now"] + rng.integers(-HOUR, 12 * HOUR, ko), 0)
+        if ko and kc > 1:
+            others["tok"][0] = new[0]             # an op on a key the same turn creates, before or behind its create
+            others["now"][0] = top
+        order = rng.permutation(kc + ko) if variant != "chain" else np.arange(kc + ko)
+        ops = np.concatenate([creates, others])[order]
+        u = np.concatenate([user, rng.integers(0, m.U, ko)])[order].astype(np.int32)
+        d = rng.integers(0, m.D, kc + ko).astype(np.int32)
+        if variant == "undo" or rng.random() < 0.2:   # ... and a delete behind it: the row is in the table with `end` = END_NONE
+            gone = np.zeros(1, TURN_OP)
+            gone["tok"], gone["now"], gone["kind"] = new[int(rng.integers(kc))], top, DELETE
+            ops, u, d = np.concatenate([ops, gone]), np.concatenate([u, u[:1]]), np.concatenate([d, d[:1]])
+        self.apply_turn((tag, variant, kc, ko), ops, u, d, session=True)
+
+    def do_logins_chain(self, tag):
+        self.do_logins(tag, "chain")
+
+    def do_logins_full(self, tag):
+        self.do_logins(tag, "full")
+
+    def do_logins_undo(self, tag):
+        self.do_logins(tag, "undo")
+
+    def do_logins_late(self, tag):
+        self.do_logins(tag, "late")
+
+    def do_logins_far(self, tag):
+        self.do_logins(tag, "far")
+
+    def do_dense_scans(self, tag):
+        """(designed chains) three scans that select most of the table: what makes mode 1 build the ordered run"""
+        now = self.pick_now("dense")
+        self.last_scan = (now, INT64_MIN)
+        for i in range(3):
+            if self.ctx:
+                same(self.ctx.scan(now, INT64_MIN), self.m.scan(now, INT64_MIN, self.mask), (tag, "dense scan", i, now))
 
     def do_session_turn(self, tag):
         k, p = int(self.rng.choice([1, 7, 64, 257, 300])), float(self.rng.choice([0.0, 0.1, 0.2, 0.4]))
@@ -525,7 +753,10 @@ class StoreChain(Chain):
         rows, ne = np.concatenate([rows, rows[twice]]), np.concatenate([ne, self.t0 + np.arange(twice.size)]).astype(np.int64)
         if self.ctx:
             self.ctx.set_end(rows, ne)
+        was_dead = m.end[rows] == END_NONE
         m.set_end(rows, ne)
+        if self.host_kept_seen and np.any(was_dead & (m.end[rows] != END_NONE)):
+            self.revived_since_kept = True        # a tombstone came back to life between two logins that keep the run
         self.touched = True
         self.check_state((tag, k))
 
@@ -646,6 +877,7 @@ class StoreChain(Chain):
             assert np.array_equal(self.ctx.compact_translate(probe), translate(new_of_old, probe)), (tag, "translate")
         if dropped:
             self.column_last = "compact_shrink" if shrink else "compact_noshrink"
+            self.since_compact = "shrink" if shrink else "noshrink"
             self.reshaped = True
             self.scanned_since_drop = False
             if cov_old < n_old and np.any(new_of_old[:cov_old] < 0) and np.any(new_of_old[cov_old:] < 0):
@@ -689,6 +921,9 @@ class StoreChain(Chain):
         k = int(self.rng.choice([1, 7, 64, 257, 300]))
         ops, _, _ = self.turn_ops(k, 0.0)
         begun = self.begin_batches(tag)
+        if self.cfg["logins"] and self.login_since_begin:
+            self.saw("host:begin_after_login")
+            self.login_since_begin = False
         if self.cfg["ordered"] == 2:
             self.saw("host:begin_in_ordered_chain")
         elif not ctx:                         # never a run: the begin is taken, and a synchronous mutator behind it refused
@@ -702,6 +937,8 @@ class StoreChain(Chain):
             # a valid ordered run: begin is refused; the batches land, and the turn goes through the synchronous call
             self.refused(tag, lambda: ctx.token_turn_begin(ops), unchanged=False)
             self.saw("refused_begin_on_ordered_run")
+            if self.kept_builds == int(ctx.table_info()["ordered_builds"]):      # the very run a creating turn kept
+                self.saw("kept_run_then_refused_inflight_begin")
             self.finish_batches(tag, begun)
             return self.apply_turn((tag, "synchronous"), ops, None, None, session=False)
         before = self.info()
@@ -745,6 +982,7 @@ class StoreChain(Chain):
         now = int(np.quantile(live, float(self.rng.uniform(0.0, 0.15)))) if live.size else self.t0
         begun = self.begin_batches(tag)
         if m.n == 0:                                      # (a begin for no rows only counts)
+            self.skipped += 1
             if ctx:
                 self.finish_batches(tag, begun)
             return
@@ -794,3 +1032,26 @@ def run_store_chain(pie, oracle, seed, cfg=None, script=None, log=None):
 def run_designed(pie, oracle, name):
     cfg, script = DESIGNED[name]
     return run_store_chain(pie, oracle, 9000 + sorted(DESIGNED).index(name), cfg, script)
+
+
+# Chains that log in with pie_set_turn_ordered on (a dict of their own: DESIGNED's names give its chains their seeds).  A freshly
+# loaded table fits its columns exactly: the first login grows them and drops the run, the readers' scan rebuilds it (mode 2), and
+# the logins after that find room.  A compaction with PIE_COMPACT_SHRINK puts the table back into that state.
+DESIGNED_LOGINS = {
+    "kept": ({"n": 3000, "U": 64, "D": 8, "hot": 0, "ordered": 2, "lanes": 2, "async": 0, "wide_ordered": 1, "turn_ordered": 1, "logins": 1},
+             ["logins", "logins", "logins_full", "logins_full", "logins_chain", "logins_undo", "inflight_turn", "append", "logins",
+              "compact_in_place", "logins", "delete_user", "prune", "logins", "compact_shrink", "logins", "logins", "retention",
+              "logins_late", "logins", "session_turn", "logins"]),
+    "far": ({"n": 3000, "U": 7, "D": 8, "hot": 0, "ordered": 2, "lanes": 1, "async": 1, "wide_ordered": 0, "turn_ordered": 1, "logins": 1},
+            ["logins", "logins", "logins_far", "logins", "delete_users", "logins_far", "logins"]),
+    # mode 1 on a table without skew: dense scans build the run and take it, the batches stay on the general pass and its hot index
+    "hot": ({"n": 20000, "U": 499, "D": 32, "hot": 1, "ordered": 1, "lanes": 3, "async": 1, "wide_ordered": 0, "turn_ordered": 1, "logins": 1},
+            ["logins", "dense_scans", "logins", "token_turn", "logins", "logins_undo", "logins_full", "inflight_turn"]),
+    "off": ({"n": 700, "U": 64, "D": 8, "hot": 0, "ordered": 2, "lanes": 2, "async": 0, "wide_ordered": 0, "turn_ordered": 0, "logins": 1},
+            ["logins", "logins", "logins_chain", "inflight_turn"]),
+}
+
+
+def run_designed_logins(pie, oracle, name):
+    cfg, script = DESIGNED_LOGINS[name]
+    return run_store_chain(pie, oracle, 9200 + sorted(DESIGNED_LOGINS).index(name), cfg, script)

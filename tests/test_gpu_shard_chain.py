@@ -15,7 +15,7 @@ model alone that the lists reach the ones a host can decide, execute every op in
 import pytest
 
 import shard_chain as S
-from test_shard_chain_cpu import SEEDS
+from test_shard_chain_cpu import LOGIN_SEEDS, SEEDS
 
 pytestmark = pytest.mark.gpu
 
@@ -43,3 +43,31 @@ def test_shard_chains_reached_every_state():
     by_state = {state: sorted((c for c, r in REACHED.items() if state in r), key=str) for state in S.STATES}
     print("states reached:", by_state)
     assert not [s for s in S.STATES if not by_state[s]], "no chain arrived at %s" % [s for s in S.STATES if not by_state[s]]
+
+
+LOGINS_REACHED = {}
+
+
+@pytest.mark.parametrize("seed", LOGIN_SEEDS)
+def test_shard_login_chains(pie, oracle, seed):
+    """the same mix with pie_shard_session_turn among it (users as global ids, some of them new, in-order logins), the plan's four
+    outputs per rank against the model's restatement, pie_set_turn_ordered drawn per chain"""
+    ch = S.run_shard_chain(pie, oracle, seed, {"logins": 1})
+    LOGINS_REACHED["login seed %d" % seed] = dict(ch.states)
+    print("login seed %d world %d: %.1f s, reached %s" % (seed, ch.world, ch.seconds, sorted(s for s in ch.states if s in S.LOGIN_STATES)))
+
+
+@pytest.mark.parametrize("name", sorted(S.DESIGNED_LOGINS))
+def test_designed_shard_login_chains(pie, oracle, name):
+    ch = S.run_designed_logins(pie, oracle, name)
+    LOGINS_REACHED["login " + name] = dict(ch.states)
+    print("chain %s world %d: %.1f s, reached %s" % (name, ch.world, ch.seconds, sorted(s for s in ch.states if s in S.LOGIN_STATES)))
+
+
+def test_shard_login_chains_reached_every_state():
+    want = ["login seed %d" % s for s in LOGIN_SEEDS] + ["login " + n for n in sorted(S.DESIGNED_LOGINS)]
+    missing = [c for c in want if c not in LOGINS_REACHED]
+    assert not missing, "chains %s failed or were deselected: their records are missing, run the whole file" % missing
+    by_state = {state: sorted(c for c, r in LOGINS_REACHED.items() if state in r) for state in S.LOGIN_STATES}
+    print("states reached:", by_state)
+    assert not [s for s in S.LOGIN_STATES if not by_state[s]], "no chain arrived at %s" % [s for s in S.LOGIN_STATES if not by_state[s]]

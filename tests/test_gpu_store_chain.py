@@ -12,11 +12,12 @@ reaches the ones a host can decide."""
 import pytest
 
 import store_chain as S
-from test_store_chain_cpu import SEEDS
+from test_store_chain_cpu import LOGIN_SEEDS, SEEDS
 
 pytestmark = pytest.mark.gpu
 
 REACHED = {}   # chain -> the states it recorded; filled by the chain tests, read by the test after them
+LOGINS_REACHED = {}
 
 
 @pytest.mark.parametrize("seed", SEEDS)
@@ -40,3 +41,28 @@ def test_store_chains_reached_every_state():
     by_state = {state: sorted((c for c, r in REACHED.items() if state in r), key=str) for state in S.STATES}
     print("states reached:", by_state)
     assert not [s for s in S.STATES if not by_state[s]], "no chain arrived at %s" % [s for s in S.STATES if not by_state[s]]
+
+
+@pytest.mark.parametrize("seed", LOGIN_SEEDS)
+def test_login_chains(pie, oracle, seed):
+    """the same mix with turns that log in in time order among it, pie_set_turn_ordered drawn per chain: the run's bookkeeping is
+    decided on the host after every creating turn (StoreChain.check_run_after_logins)"""
+    ch = S.run_store_chain(pie, oracle, seed, {"logins": 1})
+    LOGINS_REACHED["login seed %d" % seed] = dict(ch.states)
+    print("login seed %d reached %s" % (seed, sorted(ch.states)))
+
+
+@pytest.mark.parametrize("name", sorted(S.DESIGNED_LOGINS))
+def test_designed_login_chains(pie, oracle, name):
+    ch = S.run_designed_logins(pie, oracle, name)
+    LOGINS_REACHED["login " + name] = dict(ch.states)
+    print("chain %s reached %s" % (name, sorted(ch.states)))
+
+
+def test_login_chains_reached_every_state():
+    want = ["login seed %d" % s for s in LOGIN_SEEDS] + ["login " + n for n in sorted(S.DESIGNED_LOGINS)]
+    missing = [c for c in want if c not in LOGINS_REACHED]
+    assert not missing, "chains %s failed or were deselected: their records are missing, run the whole file" % missing
+    by_state = {state: sorted(c for c, r in LOGINS_REACHED.items() if state in r) for state in S.LOGIN_STATES}
+    print("states reached:", by_state)
+    assert not [s for s in S.LOGIN_STATES if not by_state[s]], "no chain arrived at %s" % [s for s in S.LOGIN_STATES if not by_state[s]]

@@ -6,7 +6,11 @@
      per-rank lookup of every key equals StoreModel.lookup (ShardChain.readers); the cached per-rank lookup is held against
      tests/shard_token_model.ShardTokenModel's own.
   3. The conditions that keep the GPU test from passing by never arriving anywhere: the seed list reaches every state a host can
-     decide, every op kind is executed (not skipped) in every world, no chain skips more than a quarter of its steps."""
+     decide, every op kind is executed (not skipped) in every world, no chain skips more than a quarter of its steps.
+  4. Every chain logs the op it drew at each step and the sizes it met; the lines equal tests/golden/shard_chain_oplog.txt,
+     recorded before the session-store chains learned to log in: whatever is added beside these chains moves no draw of theirs."""
+import os
+
 import numpy as np
 import pytest
 
@@ -20,7 +24,11 @@ from turn_model import g5_key
 # Chosen here, on the model: together with the designed scripts they meet the three conditions of (3).
 SEEDS = [0, 1, 2, 3, 4, 5, 6, 7, 9, 17, 18]
 
+# ... and the chains that log in through pie_shard_session_turn (cfg["logins"])
+LOGIN_SEEDS = [8, 5, 10, 12, 22, 14, 1]
+
 RAN = {}
+LOGINS_RAN = {}
 
 
 class Checked(S.ShardChain):
@@ -103,6 +111,56 @@ def test_the_lists_meet_the_conditions():
             if w == world:
                 done |= set(executed)
         assert not set(S.ShardChain.OPS) - done, "world %d never executed %s" % (world, sorted(set(S.ShardChain.OPS) - done))
+
+
+def test_old_seeds_replay_line_for_line(oracle):
+    """(tag, N, U, covered, slots, cap) of every step of every chain from before the logins, model only, as recorded"""
+    lines = []
+    for seed in SEEDS:
+        S.run_shard_chain(None, oracle, seed, log=lines.append)
+    for name in sorted(S.DESIGNED):
+        cfg, script = S.DESIGNED[name]
+        S.run_shard_chain(None, oracle, 9100 + sorted(S.DESIGNED).index(name), cfg, script, log=lines.append)
+    with open(os.path.join(GOLDEN, "shard_chain_oplog.txt")) as f:
+        want = f.read().splitlines()
+    assert len(lines) == len(want)
+    assert lines == want, next((a, b) for a, b in zip(lines, want) if a != b)
+
+
+@pytest.mark.parametrize("seed", LOGIN_SEEDS)
+def test_login_chain_on_the_model_alone(oracle, seed):
+    ch = Checked(None, oracle, seed, {"logins": 1}).run()
+    steps = ch.cfg["steps"]
+    assert ch.cfg["n"] <= 4099 and ch.cfg["U"] <= 64 and ch.sm.N <= S.MAX_ROWS
+    assert ch.skipped * 10 <= steps, "the chain skipped %d of its %d steps" % (ch.skipped, steps)
+    LOGINS_RAN[seed] = (ch.world, dict(ch.states), dict(ch.executed))
+
+
+@pytest.mark.parametrize("name", sorted(S.DESIGNED_LOGINS))
+def test_designed_login_chain_on_the_model_alone(oracle, name):
+    cfg, script = S.DESIGNED_LOGINS[name]
+    ch = Checked(None, oracle, 9300 + sorted(S.DESIGNED_LOGINS).index(name), cfg, script).run()
+    assert ch.skipped == 0
+    LOGINS_RAN[name] = (ch.world, dict(ch.states), dict(ch.executed))
+    want = {"empty_rank": ["shard_create_first_user_of_empty_rank", "shard_create_kept_by_no_live_rank_row"],
+            "slots": ["shard_create_doubled_slots_on_one_rank", "shard_create_after_one_rank_compacted"]}[name]
+    assert not [s for s in want if s not in ch.states], (sorted(ch.states), want)
+
+
+def test_the_login_lists_meet_the_conditions():
+    missing = [s for s in LOGIN_SEEDS + sorted(S.DESIGNED_LOGINS) if s not in LOGINS_RAN]
+    assert not missing, "chains %s failed or were deselected: run the whole file" % missing
+    by_state = {s: sorted((c for c, r in LOGINS_RAN.items() if s in r[1]), key=str) for s in S.LOGIN_HOST_STATES}
+    print("states the login chains reached on the model:", by_state)
+    assert not [s for s in S.LOGIN_HOST_STATES if not by_state[s]], "no chain arrived at %s" % [s for s in S.LOGIN_HOST_STATES if not by_state[s]]
+    seeded = {c: r for c, r in LOGINS_RAN.items() if c in LOGIN_SEEDS}
+    assert {r[0] for r in seeded.values()} == {1, 2, 3, 5}, "the seeds do not cover worlds 1, 2, 3 and 5"
+    for world in (1, 2, 3, 5):
+        done = set()
+        for w, _, executed in seeded.values():
+            if w == world:
+                done |= set(executed)
+        assert not set(S.ShardChain.NEW_OPS) - done, "world %d never executed %s" % (world, sorted(set(S.ShardChain.NEW_OPS) - done))
 
 
 def test_world_five_starts_with_an_empty_rank(oracle):

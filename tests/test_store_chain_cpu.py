@@ -5,7 +5,12 @@
      run makes, so what the model alone arrives at the GPU run arrives at too.  After every compaction the chain checks that a
      lookup of every issued key equals the answer before it pushed through new_of_old (StoreChain.do_compact).
   3. The seed list reaches every state that can be decided without a device — the cap that keeps the GPU test from passing by
-     never arriving anywhere — and the two sizes the model mirrors follow the library's own host-side rules."""
+     never arriving anywhere — and the two sizes the model mirrors follow the library's own host-side rules.
+  4. The chains that log in under pie_set_turn_ordered (cfg["logins"]) are chains of their own: the old seeds, replayed with a
+     log, draw line for line what they drew before those chains existed (tests/golden/store_chain_oplog.txt); the new seed list
+     reaches every stand-in state of S.LOGIN_HOST_STATES and skips at most a tenth of its steps."""
+import os
+
 import numpy as np
 import pytest
 
@@ -18,7 +23,11 @@ from turn_model import GET, g5_key, make_ops
 # Chosen here, on the model: together they reach every state of S.HOST_STATES (test_seed_list_reaches_every_host_state).
 SEEDS = [41, 26, 4, 11, 3, 8, 30, 42, 49, 6, 16, 60]
 
+# ... and the chains that log in (cfg["logins"]): every S.LOGIN_HOST_STATES between them, at most a tenth of the steps skipped
+LOGIN_SEEDS = [2, 3, 5, 9, 16, 17, 20, 0]
+
 REACHED = {}
+LOGINS_RAN = {}
 
 
 @pytest.mark.parametrize("chunk", [None, 64, 7, 1])
@@ -78,3 +87,48 @@ def test_mirrored_sizes_follow_the_library(pie, oracle):
     assert (m.slots, m.builds, m.cap, m.covered) == (1024, 2, 213, 213)
     assert m.turn(make_ops(keys[300:301], 5, GET))["row"].tolist() == [0]
     assert np.array_equal(m.compact(S.END_NONE, shrink=True), np.arange(213)) and m.builds == 2, "nothing to drop, nothing to give back"
+
+
+def test_old_seeds_replay_line_for_line(oracle):
+    """every chain from before the logins, model only: the op drawn at each step and the sizes it met (tag, n, covered, slots,
+    cap) are the recorded ones, so no new op name or config key has moved a draw of theirs"""
+    lines = []
+    for seed in SEEDS:
+        S.run_store_chain(None, oracle, seed, log=lines.append)
+    for name in sorted(S.DESIGNED):
+        cfg, script = S.DESIGNED[name]
+        S.run_store_chain(None, oracle, 9000 + sorted(S.DESIGNED).index(name), cfg, script, log=lines.append)
+    with open(os.path.join(GOLDEN, "store_chain_oplog.txt")) as f:
+        want = f.read().splitlines()
+    assert len(lines) == len(want) == 525
+    assert lines == want, next((a, b) for a, b in zip(lines, want) if a != b)
+
+
+@pytest.mark.parametrize("seed", LOGIN_SEEDS)
+def test_login_chain_on_the_model_alone(oracle, seed):
+    ch = S.run_store_chain(None, oracle, seed, {"logins": 1})
+    c = ch.cfg
+    assert c["n"] <= 4099 and c["U"] <= 64 and c["D"] <= 8 and ch.m.n <= S.MAX_ROWS
+    assert ch.skipped * 10 <= c["steps"], "the chain skipped %d of its %d steps" % (ch.skipped, c["steps"])
+    LOGINS_RAN[seed] = dict(ch.states)
+
+
+@pytest.mark.parametrize("name", sorted(S.DESIGNED_LOGINS))
+def test_designed_login_chain_on_the_model_alone(oracle, name):
+    ch = S.run_designed_logins(None, oracle, name)
+    assert ch.skipped == 0
+    want = {"kept": ["host:login_in_order_switch_on", "host:login_grew_switch_on", "host:login_full_segment", "host:login_chain_of_one_user",
+                     "host:login_create_then_delete", "host:login_since_compact_shrink", "host:login_since_compact_noshrink",
+                     "host:login_before_top", "host:begin_after_login", "create_over_foreign_tombstone"],
+            "far": ["host:login_before_top", "host:login_in_order_switch_on"], "hot": ["host:login_in_order_switch_on", "host:begin_after_login"],
+            "off": ["host:login_in_order_switch_off", "host:begin_after_login"]}[name]
+    assert not [s for s in want if s not in ch.states], (sorted(ch.states), want)
+
+
+def test_login_seed_list_reaches_every_host_state():
+    missing = [s for s in LOGIN_SEEDS if s not in LOGINS_RAN]
+    assert not missing, "chains %s failed or were deselected: run the whole file" % missing
+    by_state = {s: sorted(seed for seed, r in LOGINS_RAN.items() if s in r) for s in S.LOGIN_HOST_STATES + ("create_over_foreign_tombstone",)}
+    print("states the login chains reached on the model:", by_state)
+    assert not [s for s, seeds in by_state.items() if not seeds], "no chain arrived at %s" % [s for s, seeds in by_state.items() if not seeds]
+    assert {S.logins_config(seed)["turn_ordered"] for seed in LOGIN_SEEDS} == {0, 1}, "the switch on and off"
