@@ -19,6 +19,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
+#include <initializer_list>
 #include <new>
 #include <string>
 #include <vector>
@@ -195,7 +196,6 @@ struct pie_comm {
     size_t xq_stage_room = 0;
     void* xq_desc = nullptr;                      // the merge's descriptor (MergeDesc) on the device
     char* xq_h = nullptr;                         // pinned: the descriptor going up, then rows and owners coming back
-    size_t xq_h_room = 0;                         // rows it holds behind the descriptor
     hipEvent_t xq_ev = nullptr;
     long long xq_total = -1, xq_have = 0;         // of the last finish: the true total (-1: none), the rows the merged list holds
     std::vector<void*> xq_retired_dev, xq_retired_host; // blocks a begin outgrew: freed at destroy (a free waits for the whole device)
@@ -615,7 +615,54 @@ int pie_comm_read_gathered(pie_comm* c, int32_t at_rank, int32_t src_rank, int32
 // rank, how many of that rank's keys are smaller (a lower bound): no sort, no atomics, the same result on every rank.
 namespace {
 
-constexpr int kQueueMaxWorld = 64; // one lane per rank in the archive merge
+constexpr int kMergeMaxLists = 64; // lists one merge takes: the ranks of a communicator (pie_comm_create: 1..64), one lane each in the archive merge
+
+// what the co-rank merge reads: `count` ascending lists of GLOBAL rows (a gathered message's rows, a shard's own queue buffer, or
+// its copy on the merging device), every list's kept length and rank, the lists' running lengths (pre[count] elements in all)
+struct MergeDesc {
+    const int* rows[kMergeMaxLists];
+    const int* local[kMergeMaxLists];   // SRC_ROW only: every list's local rows, element for element
+    long long pre[kMergeMaxLists + 1];
+    int n[kMergeMaxLists];
+    int rank[kMergeMaxLists];
+    int count, pad;
+};
+
+// One lane per element, placed by co-rank: its index in its own list plus, for every other list, how many of that list's rows
+// are smaller (a lower bound; global rows are unique across shards).  No atomics, no wave waits for another.  A position at or
+// past out_cap is not written: the first out_cap merged rows only ever come from the first out_cap rows of each list.
+// SRC_ROW: the element's local row on its shard goes with it.  `s` sits in LDS (every lane indexes it by its own list).
+template <bool SRC_ROW>
+__device__ __forceinline__ void merge_by_corank(const MergeDesc& s, long long out_cap, int* __restrict__ out_rows, int* __restrict__ out_rank,
+                                                int* __restrict__ out_row)
+{
+    const int count = min(max(s.count, 0), kMergeMaxLists);
+    const long long total = s.pre[count];
+    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long long)gridDim.x * blockDim.x) {
+        int r = 0;
+        while (r + 1 < count && s.pre[r + 1] <= e) ++r;
+        const long long i = e - s.pre[r];
+        if (i >= s.n[r]) continue; // (a descriptor that does not add up reads nothing)
+        const int v = s.rows[r][i];
+        long long pos = i;
+        for (int p = 0; p < count; ++p) {
+            if (p == r) continue;
+            const int* other = s.rows[p];
+            int lo = 0, hi = s.n[p];
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (other[mid] < v) lo = mid + 1;
+                else hi = mid;
+            }
+            pos += lo;
+        }
+        if (pos < out_cap) {
+            out_rows[pos] = v;
+            out_rank[pos] = s.rank[r];
+            if constexpr (SRC_ROW) out_row[pos] = s.local[r][i];
+        }
+    }
+}
 
 // rows / groups of every gathered message, clamped to the message's capacities (the kernels never read past a message)
 __device__ void queue_heads(const int* __restrict__ gath, long long ql, long long cap_rows, long long cap_groups, int world, int* s_n, int* s_g,
@@ -637,38 +684,41 @@ __device__ void queue_heads(const int* __restrict__ gath, long long ql, long lon
     __syncthreads();
 }
 
-// expired queue: one lane per element, the merged position by co-rank (binary search in every other rank's list)
+// expired queue: the co-rank merge of the gathered messages; list p is rank p's, its length clamped as queue_heads clamps it
 __global__ __launch_bounds__(256) void k_merge_expired(const int* __restrict__ gath, long long ql, long long cap_rows, int world, long long out_cap,
                                                        int* __restrict__ out_rows, int* __restrict__ out_rank, int* __restrict__ out_row)
 {
-    __shared__ int s_n[kQueueMaxWorld], s_g[kQueueMaxWorld];
-    __shared__ long long s_pre[kQueueMaxWorld + 1];
-    queue_heads(gath, ql, cap_rows, 0, world, s_n, s_g, s_pre, false);
-    const long long total = s_pre[world];
-    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long long)gridDim.x * blockDim.x) {
-        int r = 0;
-        while (s_pre[r + 1] <= e) ++r;
-        const long long i = e - s_pre[r];
-        const int* grow = gath + (long long)r * ql + 2;
-        const int v = grow[i];
-        long long pos = i;
+    __shared__ MergeDesc s;
+    if (threadIdx.x == 0) {
+        world = min(world, kMergeMaxLists);
+        long long acc = 0;
         for (int p = 0; p < world; ++p) {
-            if (p == r) continue;
-            const int* other = gath + (long long)p * ql + 2;
-            int lo = 0, hi = s_n[p];
-            while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                if (other[mid] < v) lo = mid + 1;
-                else hi = mid;
-            }
-            pos += lo;
+            const int* m = gath + (long long)p * ql;
+            s.rows[p] = m + 2;
+            s.local[p] = s.rows[p] + cap_rows;
+            s.n[p] = (int)min(max((long long)m[0], 0LL), cap_rows);
+            s.rank[p] = p;
+            s.pre[p] = acc;
+            acc += s.n[p];
         }
-        if (pos < out_cap) {
-            out_rows[pos] = v;
-            out_rank[pos] = r;
-            out_row[pos] = grow[cap_rows + i];
-        }
+        s.pre[world] = acc;
+        s.count = world;
     }
+    __syncthreads();
+    merge_by_corank<true>(s, out_cap, out_rows, out_rank, out_row);
+}
+
+// the lists of local shards, named by a descriptor in device memory: <false> the in-flight expired queue (rows and owners), <true>
+// the lists of a prune / retention purge (the local row too)
+template <bool SRC_ROW>
+__global__ __launch_bounds__(256) void k_merge_shard_queues(const MergeDesc* __restrict__ desc, long long out_cap, int* __restrict__ out_rows,
+                                                            int* __restrict__ out_rank, int* __restrict__ out_row)
+{
+    __shared__ MergeDesc s;
+    for (int w = (int)threadIdx.x; w < (int)(sizeof(MergeDesc) / 4); w += (int)blockDim.x)
+        reinterpret_cast<int*>(&s)[w] = reinterpret_cast<const int*>(desc)[w];
+    __syncthreads();
+    merge_by_corank<SRC_ROW>(s, out_cap, out_rows, out_rank, out_row);
 }
 
 // archive queue: one wave per group; lane p finds how many of rank p's groups have a smaller key (the global row of a group's first
@@ -676,8 +726,8 @@ __global__ __launch_bounds__(256) void k_merge_expired(const int* __restrict__ g
 __global__ __launch_bounds__(256) void k_merge_archive(const int* __restrict__ gath, long long ql, long long cap_rows, long long cap_groups, int world,
                                                        long long out_cap, int* __restrict__ out_rows, int* __restrict__ out_rank, int* __restrict__ out_row)
 {
-    __shared__ int s_n[kQueueMaxWorld], s_g[kQueueMaxWorld];
-    __shared__ long long s_pre[kQueueMaxWorld + 1];
+    __shared__ int s_n[kMergeMaxLists], s_g[kMergeMaxLists];
+    __shared__ long long s_pre[kMergeMaxLists + 1];
     queue_heads(gath, ql, cap_rows, cap_groups, world, s_n, s_g, s_pre, true);
     const long long groups = s_pre[world];
     const int lane = (int)(threadIdx.x & 63);
@@ -806,7 +856,7 @@ int comm_queue(pie_comm* c, int kind, int64_t a, int64_t b, int32_t* queue_out, 
 {
     if (!c) return PIE_E_INVAL;
     if (q_out) *q_out = 0;
-    if (c->world > kQueueMaxWorld) return cfail(c, PIE_E_INVAL, "the queue merge takes at most %d ranks (world %d)", kQueueMaxWorld, c->world);
+    if (c->world > kMergeMaxLists) return cfail(c, PIE_E_INVAL, "the queue merge takes at most %d ranks (world %d)", kMergeMaxLists, c->world);
     if (steps_idle(c)) return PIE_E_STATE;
     c->q_total = -1;
     c->q_kind = 0;
@@ -1105,6 +1155,121 @@ int pie_comm_token_append(pie_comm* c, const uint64_t* tok, size_t k)
     return PIE_OK;
 }
 
+} // extern "C"
+
+namespace {
+
+// The per-key answer merge of the lookups and the turns: every local shard answers every key, per key the shard with the largest
+// global row wins (a shard that does not hold the key answers -1).  One shard's answers land in the scratch, take() folds them
+// into the caller's outputs (each may be NULL).
+struct KeyMerge {
+    int32_t* row_out;
+    uint8_t* live_out;
+    int32_t* user_out;
+    int64_t *start_out, *end_out;
+    int32_t* owner_rank_out;
+    size_t k = 0;
+    std::vector<int32_t> best, row, user;
+    std::vector<uint8_t> live;
+    std::vector<int64_t> start, end;
+
+    bool alloc(size_t keys)
+    {
+        try {
+            best.assign(keys, -1);
+            row.resize(keys);
+            user.resize(keys);
+            live.resize(keys);
+            start.resize(keys);
+            end.resize(keys);
+        } catch (...) {
+            return false;
+        }
+        k = keys;
+        return true;
+    }
+    // what a key no shard holds reads as; end_none: its end too (the turns), else end_out[j] is left as the caller had it
+    void preset(bool end_none)
+    {
+        if (live_out && k) memset(live_out, 0, k);
+        if (owner_rank_out) for (size_t j = 0; j < k; ++j) owner_rank_out[j] = -1;
+        if (end_none && end_out) for (size_t j = 0; j < k; ++j) end_out[j] = PIE_END_NONE;
+    }
+    void take(int owner_rank)
+    {
+        // (locals: the byte stores to live_out may alias this object, not these)
+        int32_t *const b = best.data(), *const uo = user_out, *const oo = owner_rank_out;
+        uint8_t* const lo = live_out;
+        int64_t *const so = start_out, *const eo = end_out;
+        const int32_t *const r = row.data(), *const u = user.data();
+        const uint8_t* const l = live.data();
+        const int64_t *const s = start.data(), *const e = end.data();
+        for (size_t j = 0, n = k; j < n; ++j) {
+            if (r[j] <= b[j]) continue;
+            b[j] = r[j];
+            if (lo) lo[j] = l[j];
+            if (uo) uo[j] = u[j];
+            if (so) so[j] = s[j];
+            if (eo) eo[j] = e[j];
+            if (oo) oo[j] = owner_rank;
+        }
+    }
+    void write_rows()
+    {
+        if (row_out && k) memcpy(row_out, best.data(), k * 4);
+    }
+};
+
+// a shard's wait phase: shard_token_lookup_wait, shard_token_turn_wait, shard_session_turn_wait, shard_lookup_finish
+typedef int (*ShardWait)(pie_ctx*, size_t, int32_t*, uint8_t*, int32_t*, int64_t*, int64_t*);
+
+// pie_shard_token_lookup_finish as a wait phase: the oldest lookup in flight, which must be the one of k keys the communicator began
+int shard_lookup_finish(pie_ctx* x, size_t k, int32_t* row, uint8_t* live, int32_t* user, int64_t* start, int64_t* end)
+{
+    size_t kk = 0;
+    const int rc = pie_shard_token_lookup_finish(x, row, live, user, start, end, k, &kk);
+    return rc == PIE_OK && kk != k ? PIE_E_STATE : rc;
+}
+
+// the first n local shards are waited for and their answers dropped: nothing is left writing a staging block
+void wait_out(pie_comm* c, int n, size_t k, ShardWait wait)
+{
+    for (int i = 0; i < n; ++i) (void)wait(c->ctx[i], k, nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+
+// queue(ctx) on every local shard, so that the shards' launches and copies overlap: all are in their streams before the first
+// wait.  A shard that refuses is reported once what was queued before it has been waited for.
+template <class Queue>
+int queue_all(pie_comm* c, size_t k, Queue queue, ShardWait wait)
+{
+    for (int i = 0; i < c->n_local; ++i) {
+        const int rc = queue(c->ctx[i]);
+        if (rc == PIE_OK) continue;
+        wait_out(c, i, k, wait);
+        PIE_CCTX(c, i, rc);
+    }
+    return PIE_OK;
+}
+
+// every local shard is waited for, whatever the ones before it returned; those that succeeded are merged, the first that failed
+// is reported; row_out is written only when none failed
+int wait_and_merge(pie_comm* c, KeyMerge& m, ShardWait wait)
+{
+    int first_rc = PIE_OK, first_bad = -1;
+    for (int i = 0; i < c->n_local; ++i) {
+        const int rc = wait(c->ctx[i], m.k, m.row.data(), m.live.data(), m.user.data(), m.start.data(), m.end.data());
+        if (rc == PIE_OK) m.take(c->rank_of[i]);
+        else if (first_rc == PIE_OK) { first_rc = rc; first_bad = i; }
+    }
+    if (first_rc) PIE_CCTX(c, first_bad, first_rc);
+    m.write_rows();
+    return PIE_OK;
+}
+
+} // namespace
+
+extern "C" {
+
 int pie_comm_token_lookup(pie_comm* c, const uint64_t* tok, size_t k, int64_t now, int32_t* row_out, uint8_t* live_out, int32_t* user_out,
                           int64_t* start_out, int64_t* end_out, int32_t* owner_rank_out)
 {
@@ -1112,52 +1277,16 @@ int pie_comm_token_lookup(pie_comm* c, const uint64_t* tok, size_t k, int64_t no
     int rc = mutate_ready(c, nullptr, nullptr);
     if (rc) return rc;
     if (k > 0 && !tok) return cfail(c, PIE_E_INVAL, "tok is NULL");
-    // every shard's launch and copies are in its stream before the first wait: the shards' lookups overlap
-    int queued = 0;
-    for (; queued < c->n_local; ++queued)
-        if ((rc = pie_internal::shard_token_lookup_queue(c->ctx[queued], tok, k, now)) != PIE_OK) break;
-    if (rc) { // what was queued is waited for all the same: nothing is left writing a staging block
-        const int bad = queued;
-        for (int i = 0; i < queued; ++i) (void)pie_internal::shard_token_lookup_wait(c->ctx[i], k, nullptr, nullptr, nullptr, nullptr, nullptr);
-        PIE_CCTX(c, bad, rc);
-    }
-    if (k == 0) return PIE_OK;
-    std::vector<int32_t> best, row, user;
-    std::vector<uint8_t> live;
-    std::vector<int64_t> start, end;
-    try {
-        best.assign(k, -1);
-        row.resize(k);
-        user.resize(k);
-        live.resize(k);
-        start.resize(k);
-        end.resize(k);
-    } catch (...) {
-        for (int i = 0; i < c->n_local; ++i) (void)pie_internal::shard_token_lookup_wait(c->ctx[i], k, nullptr, nullptr, nullptr, nullptr, nullptr);
+    const ShardWait wait = pie_internal::shard_token_lookup_wait;
+    rc = queue_all(c, k, [&](pie_ctx* x) { return pie_internal::shard_token_lookup_queue(x, tok, k, now); }, wait);
+    if (rc || k == 0) return rc;
+    KeyMerge m{row_out, live_out, user_out, start_out, end_out, owner_rank_out};
+    if (!m.alloc(k)) {
+        wait_out(c, c->n_local, k, wait);
         return cfail(c, PIE_E_NOMEM, "no memory for %zu answers", k);
     }
-    if (live_out) memset(live_out, 0, k);
-    if (owner_rank_out) for (size_t j = 0; j < k; ++j) owner_rank_out[j] = -1;
-    int first_rc = PIE_OK, first_bad = -1;
-    for (int i = 0; i < c->n_local; ++i) {
-        rc = pie_internal::shard_token_lookup_wait(c->ctx[i], k, row.data(), live.data(), user.data(), start.data(), end.data());
-        if (rc) { // keep waiting for the others
-            if (first_rc == PIE_OK) { first_rc = rc; first_bad = i; }
-            continue;
-        }
-        for (size_t j = 0; j < k; ++j) {
-            if (row[j] <= best[j]) continue;
-            best[j] = row[j];
-            if (live_out) live_out[j] = live[j];
-            if (user_out) user_out[j] = user[j];
-            if (start_out) start_out[j] = start[j];
-            if (end_out) end_out[j] = end[j];
-            if (owner_rank_out) owner_rank_out[j] = c->rank_of[i];
-        }
-    }
-    if (first_rc) PIE_CCTX(c, first_bad, first_rc);
-    if (row_out) memcpy(row_out, best.data(), k * 4);
-    return PIE_OK;
+    m.preset(false);
+    return wait_and_merge(c, m, wait);
 }
 
 int pie_comm_token_set_end(pie_comm* c, const uint64_t* tok, const int64_t* new_end, size_t k, int64_t now, int32_t* rows_out)
@@ -1201,51 +1330,14 @@ int pie_comm_token_turn(pie_comm* c, const pie_turn_op* ops, size_t k, int32_t* 
     if (rc) return rc;
     for (int i = 0; i < c->n_local; ++i) PIE_CCTX(c, i, pie_internal::shard_token_turn_check(c->ctx[i], ops, k));
     if (k == 0) return PIE_OK;
-    std::vector<int32_t> best, row, user;
-    std::vector<uint8_t> live;
-    std::vector<int64_t> start, end;
-    try {
-        best.assign(k, -1);
-        row.resize(k);
-        user.resize(k);
-        live.resize(k);
-        start.resize(k);
-        end.resize(k);
-    } catch (...) {
-        return cfail(c, PIE_E_NOMEM, "no memory for %zu answers", k);
-    }
-    int queued = 0;
-    for (; queued < c->n_local; ++queued)
-        if ((rc = pie_internal::shard_token_turn_queue(c->ctx[queued], ops, k)) != PIE_OK) break;
-    if (rc) { // what was queued is waited for all the same: nothing is left writing a staging block
-        const int bad = queued;
-        for (int i = 0; i < queued; ++i) (void)pie_internal::shard_token_turn_wait(c->ctx[i], k, nullptr, nullptr, nullptr, nullptr, nullptr);
-        PIE_CCTX(c, bad, rc);
-    }
-    if (live_out) memset(live_out, 0, k);
-    if (owner_rank_out) for (size_t j = 0; j < k; ++j) owner_rank_out[j] = -1;
-    if (end_out) for (size_t j = 0; j < k; ++j) end_out[j] = PIE_END_NONE;
+    KeyMerge m{row_out, live_out, user_out, start_out, end_out, owner_rank_out};
+    if (!m.alloc(k)) return cfail(c, PIE_E_NOMEM, "no memory for %zu answers", k); // nothing queued yet
+    const ShardWait wait = pie_internal::shard_token_turn_wait;
+    rc = queue_all(c, k, [&](pie_ctx* x) { return pie_internal::shard_token_turn_queue(x, ops, k); }, wait);
+    if (rc) return rc;
     // (a DELETE that met a tombstone answers -1 on its own shard too: it merges as a key nobody holds, which reads the same)
-    int first_rc = PIE_OK, first_bad = -1;
-    for (int i = 0; i < c->n_local; ++i) {
-        rc = pie_internal::shard_token_turn_wait(c->ctx[i], k, row.data(), live.data(), user.data(), start.data(), end.data());
-        if (rc) { // keep waiting for the others
-            if (first_rc == PIE_OK) { first_rc = rc; first_bad = i; }
-            continue;
-        }
-        for (size_t j = 0; j < k; ++j) {
-            if (row[j] <= best[j]) continue;
-            best[j] = row[j];
-            if (live_out) live_out[j] = live[j];
-            if (user_out) user_out[j] = user[j];
-            if (start_out) start_out[j] = start[j];
-            if (end_out) end_out[j] = end[j];
-            if (owner_rank_out) owner_rank_out[j] = c->rank_of[i];
-        }
-    }
-    if (first_rc) PIE_CCTX(c, first_bad, first_rc);
-    if (row_out) memcpy(row_out, best.data(), k * 4);
-    return PIE_OK;
+    m.preset(true);
+    return wait_and_merge(c, m, wait);
 }
 
 // The turn that logs in, on every local shard (pie_shard_session_turn's phases): all checked before any is changed, room made on
@@ -1258,52 +1350,14 @@ int pie_comm_session_turn(pie_comm* c, const pie_turn_op* ops, size_t k, const i
     int rc = mutate_ready(c, nullptr, nullptr);
     if (rc) return rc;
     for (int i = 0; i < c->n_local; ++i) PIE_CCTX(c, i, pie_internal::shard_session_turn_check(c->ctx[i], ops, k, user, disc, n_users));
-    std::vector<int32_t> best, row, usr;
-    std::vector<uint8_t> live;
-    std::vector<int64_t> start, end;
-    try {
-        best.assign(k, -1);
-        row.resize(k);
-        usr.resize(k);
-        live.resize(k);
-        start.resize(k);
-        end.resize(k);
-    } catch (...) {
-        return cfail(c, PIE_E_NOMEM, "no memory for %zu answers", k);
-    }
+    KeyMerge m{row_out, live_out, user_out, start_out, end_out, owner_rank_out};
+    if (!m.alloc(k)) return cfail(c, PIE_E_NOMEM, "no memory for %zu answers", k); // nothing changed yet
     for (int i = 0; i < c->n_local; ++i) PIE_CCTX(c, i, pie_internal::shard_session_turn_room(c->ctx[i], ops, k, user, n_users));
-    int queued = 0;
-    for (; queued < c->n_local; ++queued)
-        if ((rc = pie_internal::shard_session_turn_queue(c->ctx[queued], ops, k, user, disc, n_users)) != PIE_OK) break;
-    if (rc) { // what was queued is waited for all the same: nothing is left writing a staging block
-        const int bad = queued;
-        for (int i = 0; i < queued; ++i) (void)pie_internal::shard_session_turn_wait(c->ctx[i], k, nullptr, nullptr, nullptr, nullptr, nullptr);
-        PIE_CCTX(c, bad, rc);
-    }
-    if (k == 0) return PIE_OK;
-    if (live_out) memset(live_out, 0, k);
-    if (owner_rank_out) for (size_t j = 0; j < k; ++j) owner_rank_out[j] = -1;
-    if (end_out) for (size_t j = 0; j < k; ++j) end_out[j] = PIE_END_NONE;
-    int first_rc = PIE_OK, first_bad = -1;
-    for (int i = 0; i < c->n_local; ++i) {
-        rc = pie_internal::shard_session_turn_wait(c->ctx[i], k, row.data(), live.data(), usr.data(), start.data(), end.data());
-        if (rc) { // keep waiting for the others
-            if (first_rc == PIE_OK) { first_rc = rc; first_bad = i; }
-            continue;
-        }
-        for (size_t j = 0; j < k; ++j) {
-            if (row[j] <= best[j]) continue;
-            best[j] = row[j];
-            if (live_out) live_out[j] = live[j];
-            if (user_out) user_out[j] = usr[j];
-            if (start_out) start_out[j] = start[j];
-            if (end_out) end_out[j] = end[j];
-            if (owner_rank_out) owner_rank_out[j] = c->rank_of[i];
-        }
-    }
-    if (first_rc) PIE_CCTX(c, first_bad, first_rc);
-    if (row_out) memcpy(row_out, best.data(), k * 4);
-    return PIE_OK;
+    const ShardWait wait = pie_internal::shard_session_turn_wait;
+    rc = queue_all(c, k, [&](pie_ctx* x) { return pie_internal::shard_session_turn_queue(x, ops, k, user, disc, n_users); }, wait);
+    if (rc || k == 0) return rc; // (an empty turn still ran its room and queue phases)
+    m.preset(true);
+    return wait_and_merge(c, m, wait);
 }
 
 } // extern "C"
@@ -1700,60 +1754,62 @@ int pie_comm_wide_step_read_feed(pie_comm* c, int32_t at_rank, int32_t src_rank,
 // room says otherwise was used directly (pie_shard_* on a context from pie_comm_ctx) and the begin is refused with nothing taken.
 namespace {
 
-constexpr int kMergeMaxLists = 64; // local ranks at most (pie_comm_create: 1..64)
+bool xq_staged(const pie_comm* c, int k) { return c->xq_stage_all || c->device[k] != c->device[0]; }
 
-// what the merge reads: every local shard's ascending list of GLOBAL rows (the shard's own queue buffer, or its copy on the
-// merging device), its kept length, its rank, and the lists' running lengths; `count` lists, pre[count] elements
-struct MergeDesc {
-    const int* rows[kMergeMaxLists];
-    const int* local[kMergeMaxLists];   // SRC_ROW only: every list's local rows, element for element
-    long long pre[kMergeMaxLists + 1];
-    int n[kMergeMaxLists];
-    int rank[kMergeMaxLists];
-    int count, pad;
+// every local shard's ascending list as the shard holds it: global rows, the local rows beside them (all NULL: none ride along),
+// the rows of it that are merged, and the event its pass is done at (NULL: already waited for)
+struct ShardLists {
+    const int32_t* rows[kMergeMaxLists] = {};
+    const int32_t* local[kMergeMaxLists] = {};
+    size_t kept[kMergeMaxLists] = {};
+    void* done[kMergeMaxLists] = {};
 };
 
-// One lane per element, placed by co-rank: its index in its own list plus, for every other list, how many of that list's rows
-// are smaller (a lower bound; global rows are unique across shards).  No atomics, no wave waits for another.  A position at or
-// past out_cap is not written: the first out_cap merged rows only ever come from the first out_cap rows of each list.
-// SRC_ROW (the lists of a prune / retention purge): the element's local row on its shard goes with it.
-template <bool SRC_ROW>
-__global__ __launch_bounds__(256) void k_merge_shard_queues(const MergeDesc* __restrict__ desc, long long out_cap, int* __restrict__ out_rows,
-                                                            int* __restrict__ out_rank, int* __restrict__ out_row)
+// The merge of the local shards' lists on the first local rank's device, queued on `ms` (that device is current): lists that
+// xq_staged names are copied into `stage` first (global rows, then local rows, back to back), each behind its shard's done event;
+// the descriptor goes up from `pinned` asynchronously, or (NULL) from the stack with a copy that waits; the events of
+// `before_launch` are recorded between the upload and k_merge_shard_queues<out_row != NULL>.  The buffers are the caller's.
+hipError_t merge_shard_lists(pie_comm* c, const ShardLists& in, hipStream_t ms, MergeDesc* pinned, void* desc_dev, int* stage,
+                             std::initializer_list<hipEvent_t> before_launch, long long out_cap, int* out_rows, int* out_rank, int* out_row)
 {
-    __shared__ MergeDesc s;
-    for (int w = (int)threadIdx.x; w < (int)(sizeof(MergeDesc) / 4); w += (int)blockDim.x)
-        reinterpret_cast<int*>(&s)[w] = reinterpret_cast<const int*>(desc)[w];
-    __syncthreads();
-    const int count = min(max(s.count, 0), kMergeMaxLists);
-    const long long total = s.pre[count];
-    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long long)gridDim.x * blockDim.x) {
-        int r = 0;
-        while (r + 1 < count && s.pre[r + 1] <= e) ++r;
-        const long long i = e - s.pre[r];
-        if (i >= s.n[r]) continue; // (a descriptor that does not add up reads nothing)
-        const int v = s.rows[r][i];
-        long long pos = i;
-        for (int p = 0; p < count; ++p) {
-            if (p == r) continue;
-            const int* other = s.rows[p];
-            int lo = 0, hi = s.n[p];
-            while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                if (other[mid] < v) lo = mid + 1;
-                else hi = mid;
-            }
-            pos += lo;
-        }
-        if (pos < out_cap) {
-            out_rows[pos] = v;
-            out_rank[pos] = s.rank[r];
-            if constexpr (SRC_ROW) out_row[pos] = s.local[r][i];
+    MergeDesc on_stack;
+    MergeDesc* d = pinned ? pinned : &on_stack;
+    memset(d, 0, sizeof(MergeDesc));
+    hipError_t e = hipSuccess;
+    long long acc = 0;
+    for (int i = 0; i < c->n_local; ++i) {
+        const size_t kept = in.kept[i];
+        d->rows[i] = in.rows[i];
+        d->local[i] = in.local[i];
+        d->n[i] = (int)kept;
+        d->rank[i] = c->rank_of[i];
+        d->pre[i] = acc;
+        acc += (long long)kept;
+        if (kept == 0) continue;
+        if (i > 0 && in.done[i] && (e = hipStreamWaitEvent(ms, (hipEvent_t)in.done[i], 0)) != hipSuccess) return e;
+        if (!xq_staged(c, i)) continue;
+        for (const int** list : {&d->rows[i], &d->local[i]}) {
+            if (!*list) continue;
+            e = c->device[i] != c->device[0] ? hipMemcpyPeerAsync(stage, c->device[0], *list, c->device[i], kept * 4, ms)
+                                             : hipMemcpyAsync(stage, *list, kept * 4, hipMemcpyDeviceToDevice, ms);
+            if (e != hipSuccess) return e;
+            *list = stage;
+            stage += kept;
         }
     }
+    d->pre[c->n_local] = acc;
+    d->count = c->n_local;
+    e = pinned ? hipMemcpyAsync(desc_dev, d, sizeof(MergeDesc), hipMemcpyHostToDevice, ms) : hipMemcpy(desc_dev, d, sizeof(MergeDesc), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return e;
+    for (hipEvent_t ev : before_launch)
+        if ((e = hipEventRecord(ev, ms)) != hipSuccess) return e;
+    const long long blocks = std::min<long long>((acc + 255) / 256, 2048);
+    if (out_row)
+        hipLaunchKernelGGL(k_merge_shard_queues<true>, dim3((unsigned)blocks), dim3(256), 0, ms, (const MergeDesc*)desc_dev, out_cap, out_rows, out_rank, out_row);
+    else
+        hipLaunchKernelGGL(k_merge_shard_queues<false>, dim3((unsigned)blocks), dim3(256), 0, ms, (const MergeDesc*)desc_dev, out_cap, out_rows, out_rank, out_row);
+    return hipGetLastError();
 }
-
-bool xq_staged(const pie_comm* c, int k) { return c->xq_stage_all || c->device[k] != c->device[0]; }
 
 // The merged list, the staging of lists held on other devices, the descriptor and the pinned block, sized by the begin.  A block
 // a begin outgrew is set aside until pie_comm_destroy: hipFree and hipHostFree wait for the whole device, the steps included.
@@ -1878,46 +1934,14 @@ int pie_comm_token_lookup_finish(pie_comm* c, int32_t* row_out, uint8_t* live_ou
     const size_t k = c->lk_k[c->lk_head];
     if (k_out) *k_out = k;
     if (cap < k) return cfail(c, PIE_E_CAPACITY, "%s: %zu keys, room for %zu", what, k, cap);
-    std::vector<int32_t> best, row, user;
-    std::vector<uint8_t> live;
-    std::vector<int64_t> start, end;
-    try {
-        best.assign(k, -1);
-        row.resize(k);
-        user.resize(k);
-        live.resize(k);
-        start.resize(k);
-        end.resize(k);
-    } catch (...) {
-        return cfail(c, PIE_E_NOMEM, "%s: no memory for %zu answers", what, k); // nothing consumed
-    }
-    if (live_out && k) memset(live_out, 0, k);
-    if (owner_rank_out) for (size_t j = 0; j < k; ++j) owner_rank_out[j] = -1;
-    // the merge pie_comm_token_lookup does: per key the shard with the largest global row answers
-    int first_rc = PIE_OK, first_bad = -1;
-    for (int i = 0; i < c->n_local; ++i) {
-        size_t kk = 0;
-        int rc = pie_shard_token_lookup_finish(c->ctx[i], row.data(), live.data(), user.data(), start.data(), end.data(), k, &kk);
-        if (rc == PIE_OK && kk != k) rc = PIE_E_STATE; // (not the lookup the communicator began)
-        if (rc) { // the other shards' slots are returned all the same
-            if (first_rc == PIE_OK) { first_rc = rc; first_bad = i; }
-            continue;
-        }
-        for (size_t j = 0; j < k; ++j) {
-            if (row[j] <= best[j]) continue;
-            best[j] = row[j];
-            if (live_out) live_out[j] = live[j];
-            if (user_out) user_out[j] = user[j];
-            if (start_out) start_out[j] = start[j];
-            if (end_out) end_out[j] = end[j];
-            if (owner_rank_out) owner_rank_out[j] = c->rank_of[i];
-        }
-    }
+    KeyMerge m{row_out, live_out, user_out, start_out, end_out, owner_rank_out};
+    if (!m.alloc(k)) return cfail(c, PIE_E_NOMEM, "%s: no memory for %zu answers", what, k); // nothing consumed
+    m.preset(false);
+    // the merge pie_comm_token_lookup does; a shard that fails does not keep the others' slots from being returned
+    const int rc = wait_and_merge(c, m, shard_lookup_finish);
     c->lk_head = (c->lk_head + 1) % pie_comm::kLookups;
     c->lk_n--;
-    if (first_rc) return cfail(c, first_rc, "rank %d: %s", c->rank_of[first_bad], pie_last_error(c->ctx[first_bad]));
-    if (row_out && k) memcpy(row_out, best.data(), k * 4);
-    return PIE_OK;
+    return rc;
 }
 
 int pie_comm_expired_queue_room(pie_comm* c)
@@ -1966,14 +1990,12 @@ int pie_comm_expired_queue_finish(pie_comm* c, int32_t* rows_out, int32_t* owner
     if ((rows_out || owner_rank_out) && cap < cap_rows)
         return cfail(c, PIE_E_INVAL, "%s: room for %zu rows, the begin asked for %zu", what, cap, cap_rows);
     // 1. every shard's bounded wait; its list stays in its own queue buffer
-    const int32_t* list[kMergeMaxLists] = {};
-    size_t len[kMergeMaxLists] = {};
-    void* done[kMergeMaxLists] = {};
+    ShardLists in;
     void* s0 = nullptr;
     int first_rc = PIE_OK, first_bad = -1;
     for (int i = 0; i < c->n_local; ++i) {
         void* s = nullptr;
-        const int rc = pie_internal::shard_expq_take(c->ctx[i], what, &list[i], &len[i], &s, &done[i]);
+        const int rc = pie_internal::shard_expq_take(c->ctx[i], what, &in.rows[i], &in.kept[i], &s, &in.done[i]);
         if (rc && first_rc == PIE_OK) { first_rc = rc; first_bad = i; }
         if (i == 0) s0 = s;
     }
@@ -1981,51 +2003,23 @@ int pie_comm_expired_queue_finish(pie_comm* c, int32_t* rows_out, int32_t* owner
     if (first_rc) return cfail(c, first_rc, "rank %d: %s", c->rank_of[first_bad], pie_last_error(c->ctx[first_bad]));
     size_t total = 0, kept_sum = 0;
     for (int i = 0; i < c->n_local; ++i) {
-        total += len[i];
-        kept_sum += std::min(len[i], cap_rows);
+        total += in.kept[i];
+        in.kept[i] = std::min(in.kept[i], cap_rows); // (a shard's list is cut at what the begin asked for)
+        kept_sum += in.kept[i];
     }
     if (q_out) *q_out = total;
     const size_t have = std::min(kept_sum, cap_rows);
     if (have > 0) {
-        // 2. lists held on other devices come over behind their pass; 3. the merge, on the first shard's pass stream
+        // 2. lists held on other devices come over behind their pass; 3. the merge, on the first shard's pass stream, its descriptor
+        // going up from the pinned block
         hipStream_t ms = (hipStream_t)s0;
-        MergeDesc* d = reinterpret_cast<MergeDesc*>(c->xq_h);
-        memset(d, 0, sizeof(MergeDesc));
         PIE_CHIP(c, hipSetDevice(c->device[0]));
-        size_t staged_at = 0;
-        long long acc = 0;
-        const bool to_host = rows_out || owner_rank_out;
-        hipError_t e = hipSuccess;
-        for (int i = 0; i < c->n_local && e == hipSuccess; ++i) {
-            const size_t kept = std::min(len[i], cap_rows);
-            d->rows[i] = list[i];
-            d->n[i] = (int)kept;
-            d->rank[i] = c->rank_of[i];
-            d->pre[i] = acc;
-            acc += (long long)kept;
-            if (kept == 0) continue;
-            if (i > 0 && done[i]) e = hipStreamWaitEvent(ms, (hipEvent_t)done[i], 0);
-            if (e == hipSuccess && xq_staged(c, i)) {
-                int* dst = c->xq_stage + staged_at;
-                staged_at += kept;
-                e = c->device[i] != c->device[0] ? hipMemcpyPeerAsync(dst, c->device[0], list[i], c->device[i], kept * 4, ms)
-                                                 : hipMemcpyAsync(dst, list[i], kept * 4, hipMemcpyDeviceToDevice, ms);
-                d->rows[i] = dst;
-            }
-        }
-        d->pre[c->n_local] = acc;
-        d->count = c->n_local;
         int* h_rows = reinterpret_cast<int*>(c->xq_h + sizeof(MergeDesc));
         int* h_owner = h_rows + c->xq_room;
-        if (e == hipSuccess) e = hipMemcpyAsync(c->xq_desc, d, sizeof(MergeDesc), hipMemcpyHostToDevice, ms);
-        if (e == hipSuccess) {
-            const long long blocks = std::min<long long>((acc + 255) / 256, 2048);
-            hipLaunchKernelGGL(k_merge_shard_queues<false>, dim3((unsigned)blocks), dim3(256), 0, ms, (const MergeDesc*)c->xq_desc, (long long)have,
-                               c->xq_rows, c->xq_owner, (int*)nullptr);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess && to_host && rows_out) e = hipMemcpyAsync(h_rows, c->xq_rows, have * 4, hipMemcpyDeviceToHost, ms);
-        if (e == hipSuccess && to_host && owner_rank_out) e = hipMemcpyAsync(h_owner, c->xq_owner, have * 4, hipMemcpyDeviceToHost, ms);
+        hipError_t e = merge_shard_lists(c, in, ms, reinterpret_cast<MergeDesc*>(c->xq_h), c->xq_desc, c->xq_stage, {}, (long long)have, c->xq_rows,
+                                         c->xq_owner, nullptr);
+        if (e == hipSuccess && rows_out) e = hipMemcpyAsync(h_rows, c->xq_rows, have * 4, hipMemcpyDeviceToHost, ms);
+        if (e == hipSuccess && owner_rank_out) e = hipMemcpyAsync(h_owner, c->xq_owner, have * 4, hipMemcpyDeviceToHost, ms);
         if (e == hipSuccess) e = hipEventRecord(c->xq_ev, ms);
         if (e != hipSuccess) {
             pie_internal::shard_expq_stale(c->ctx[0]); // what was queued may still read a shard's buffer: the next begin drains the stream
@@ -2105,15 +2099,13 @@ int comm_maint_list(pie_comm* c, int kind, int64_t a, int32_t months, int64_t tz
     PIE_CHIP(c, hipSetDevice(c->device[0]));
     PIE_CHIP(c, hipEventRecord(c->q_tev[0], c->stream[0]));
     // 1. every shard's two passes; its lists stay in its own workspace
-    const int32_t* glist[kMergeMaxLists] = {};
-    const int32_t* llist[kMergeMaxLists] = {};
-    size_t len[kMergeMaxLists] = {};
+    ShardLists in;
     long long total = 0, staged = 0;
     for (int i = 0; i < c->n_local; ++i) {
-        PIE_CCTX(c, i, pie_internal::shard_row_list_run(c->ctx[i], kind, a, months, tz_offset_ms, transitions, offsets, n_transitions, &len[i],
-                                                        &glist[i], &llist[i]));
-        total += (long long)len[i];
-        if (xq_staged(c, i)) staged += 2 * (long long)len[i];
+        PIE_CCTX(c, i, pie_internal::shard_row_list_run(c->ctx[i], kind, a, months, tz_offset_ms, transitions, offsets, n_transitions, &in.kept[i],
+                                                        &in.rows[i], &in.local[i]));
+        total += (long long)in.kept[i];
+        if (xq_staged(c, i)) staged += 2 * (long long)in.kept[i];
     }
     if (n_out) *n_out = (size_t)total;
     if (total >= 0x7FFFFFFFLL) return cfail(c, PIE_E_INVAL, "a merged list of %lld rows does not fit int32", total);
@@ -2123,40 +2115,10 @@ int comm_maint_list(pie_comm* c, int kind, int64_t a, int32_t months, int64_t tz
     if (total > 0) {
         rc = maint_ensure(c, total, staged);
         if (rc) return rc;
-        // 2. lists held on other devices come over (every shard's passes were waited for); 3. the merge
-        MergeDesc d;
-        memset(&d, 0, sizeof d);
-        long long acc = 0, staged_at = 0;
-        for (int i = 0; i < c->n_local; ++i) {
-            d.rows[i] = glist[i];
-            d.local[i] = llist[i];
-            d.n[i] = (int)len[i];
-            d.rank[i] = c->rank_of[i];
-            d.pre[i] = acc;
-            acc += (long long)len[i];
-            if (len[i] == 0 || !xq_staged(c, i)) continue;
-            int* dg = c->mq_stage + staged_at;
-            int* dl = dg + len[i];
-            staged_at += 2 * (long long)len[i];
-            if (c->device[i] != c->device[0]) {
-                PIE_CHIP(c, hipMemcpyPeerAsync(dg, c->device[0], glist[i], c->device[i], len[i] * 4, ms));
-                PIE_CHIP(c, hipMemcpyPeerAsync(dl, c->device[0], llist[i], c->device[i], len[i] * 4, ms));
-            } else {
-                PIE_CHIP(c, hipMemcpyAsync(dg, glist[i], len[i] * 4, hipMemcpyDeviceToDevice, ms));
-                PIE_CHIP(c, hipMemcpyAsync(dl, llist[i], len[i] * 4, hipMemcpyDeviceToDevice, ms));
-            }
-            d.rows[i] = dg;
-            d.local[i] = dl;
-        }
-        d.pre[c->n_local] = acc;
-        d.count = c->n_local;
-        PIE_CHIP(c, hipMemcpy(c->mq_desc, &d, sizeof d, hipMemcpyHostToDevice)); // no merge of this communicator is running: every call waits for its own
-        PIE_CHIP(c, hipEventRecord(c->q_tev[2], ms));
-        PIE_CHIP(c, hipEventRecord(c->q_tev[3], ms));
-        const long long blocks = std::min<long long>((acc + 255) / 256, 2048);
-        hipLaunchKernelGGL(k_merge_shard_queues<true>, dim3((unsigned)blocks), dim3(256), 0, ms, (const MergeDesc*)c->mq_desc, c->mq_cap, c->mq_rows,
-                           c->mq_rank, c->mq_row);
-        PIE_CHIP(c, hipGetLastError());
+        // 2. lists held on other devices come over (every shard's passes were waited for); 3. the merge.  The descriptor goes up
+        // with a copy that waits: no merge of this communicator is running, every call waits for its own
+        PIE_CHIP(c, merge_shard_lists(c, in, ms, nullptr, c->mq_desc, c->mq_stage, {c->q_tev[2], c->q_tev[3]}, c->mq_cap, c->mq_rows, c->mq_rank,
+                                      c->mq_row));
     } else {
         PIE_CHIP(c, hipEventRecord(c->q_tev[2], ms));
         PIE_CHIP(c, hipEventRecord(c->q_tev[3], ms));

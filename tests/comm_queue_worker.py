@@ -6,6 +6,8 @@ usage: comm_queue_worker.py CASE
            touches and tombstones applied to the shards), archive windows (no group, some, all, now - window below int64),
            sources, every local rank's copy, the capacity error and its repeat
   errors   refusal while a pipelined step is uncollected; a shard with rows its map does not cover fails every rank alike
+  edges    worlds 3 and 5 (a rank without rows), 20 000 rows: expired windows whose merged queue holds exactly 0, 1, 255, 256, 257
+           and 4 097 rows, and one whose rows all sit on one shard; rows, sources, and the in-flight form on the same communicator
   cfg5     world 8, 10^8 rows, 10^5 users: one expired and one archive queue
   real     world 1 through the real RCCL (prints "skip: ..." when it does not load)"""
 import ctypes as C
@@ -193,6 +195,64 @@ def case_errors():
     print("errors ok")
 
 
+EDGE_TOTALS = (0, 1, 255, 256, 257, 4097)   # around one block of the merge (256 lanes) and past sixteen of them
+
+
+def edge_windows(end, rank_of_row):
+    """Windows (prev, now, total) cut from the sorted end column: one per EDGE_TOTALS whose queue holds exactly that many rows,
+    then the longest one (total None) whose rows all sit on one shard.  A window is the sorted positions [a, b) with a new end
+    value beginning at a and at b, so prev = the end before a, now = the end at b - 1."""
+    order = np.argsort(end, kind="stable")
+    se, rs = end[order], rank_of_row[order]
+    cuts = np.flatnonzero(np.diff(se) > 0) + 1
+    is_cut = np.zeros(se.size + 1, bool)
+    is_cut[cuts] = True
+    is_cut[se.size] = True
+    mid = int(se[se.size // 2])
+    out = [(mid, mid, 0)]
+    for total in EDGE_TOTALS[1:]:
+        a = next(int(a) for a in cuts[cuts.size // 3:] if a + total <= se.size and is_cut[a + total])
+        out.append((int(se[a - 1]), int(se[a + total - 1]), total))
+    # maximal runs of one rank in end order, shrunk to the cuts inside them
+    edges = np.concatenate(([0], np.flatnonzero(np.diff(rs) != 0) + 1, [se.size]))
+    best = (0, 0)
+    for p, q in zip(edges[:-1], edges[1:]):
+        inner = cuts[(cuts >= p) & (cuts <= q)]
+        if inner.size >= 2 and inner[-1] - inner[0] > best[1] - best[0]:
+            best = (int(inner[0]), int(inner[-1]))
+    assert best[1] - best[0] >= 2, "no run of two rows on one shard"
+    out.append((int(se[best[0] - 1]), int(se[best[1] - 1]), None))
+    return out
+
+
+def case_edges():
+    """The synchronous expired queue at the merge's block boundaries, and the in-flight form beside it on the same communicator."""
+    checks = 0
+    for world, n, U in [(3, 20_000, 1000), (5, 20_000, 7)]:
+        # the windows are designed and checked on the host, with the oracle alone, before anything runs on the GPU
+        _, end, user, _ = oracle_py.gen(SEED, n, 0, n, U, 32, 1)
+        owner = np.array([pie.shard_of(int(u), world) for u in user], np.int32)
+        windows = edge_windows(end, owner)
+        wants = [oracle_py.expired_queue(end, p, q) for p, q, _ in windows]
+        assert [w.size for w in wants[:-1]] == list(EDGE_TOTALS), [w.size for w in wants]
+        assert wants[-1].size >= 2 and np.unique(owner[wants[-1]]).size == 1
+        t = Sharded(world, n, U)
+        assert np.array_equal(t.rank_of_row, owner)
+        if U == 7:
+            assert min(m.size for m in t.rows_g) == 0, "7 users over 5 ranks leave one rank without rows"
+        for (p, q, _), want in zip(windows, wants):
+            rows, src_rank, src_row = t.comm.expired_queue(p, q, sources=True)
+            assert np.array_equal(rows, want), (world, p, q, rows.size, want.size)
+            t.check_sources(rows, src_rank, src_row)
+            t.comm.expired_queue_begin(p, q, cap_rows=want.size)     # (0 rows: the begin counts only)
+            res = t.comm.expired_queue_finish()
+            rows2, owner2 = res if want.size else (np.zeros(0, np.int32), np.zeros(0, np.int32))
+            assert (want.size or res == 0) and np.array_equal(rows2, want) and np.array_equal(owner2, src_rank), (world, p, q)
+            checks += 1
+        t.comm.close()
+    print("edges ok: %d windows" % checks)
+
+
 def case_cfg5():
     t = Sharded(8, 10 ** 8, 10 ** 5)
     e = t.expired(T0 - 6 * 3600 * 1000 - 3600 * 1000, T0 - 6 * 3600 * 1000, full=False)
@@ -217,4 +277,4 @@ def case_real():
 
 
 if __name__ == "__main__":
-    {"worlds": case_worlds, "errors": case_errors, "cfg5": case_cfg5, "real": case_real}[CASE]()
+    {"worlds": case_worlds, "errors": case_errors, "edges": case_edges, "cfg5": case_cfg5, "real": case_real}[CASE]()

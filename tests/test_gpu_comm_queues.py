@@ -31,6 +31,14 @@ def test_queue_errors_are_the_same_on_every_rank(pie, oracle):
     assert "errors ok" in run_worker("errors", 600)
 
 
+def test_expired_queue_at_the_merge_block_edges(pie, oracle):
+    """Worlds 3 and 5 (a rank without rows) over 20 000 rows: windows cut from the sorted end column so that the merged queue
+    holds exactly 0, 1, 255, 256, 257 and 4 097 rows, and one whose rows all sit on one shard.  Each equals the oracle's queue
+    of the unsharded table, its sources name the same global rows on their shards' maps, and the in-flight form on the same
+    communicator (cap_rows = the total) returns the same rows and owners."""
+    assert "edges ok: 14 windows" in run_worker("edges", 300)
+
+
 def test_config5_sharded_queues(pie, oracle):
     """BASELINE config 5 shape: 8 shards of 10^8 sessions / 10^5 users on one GPU, one expired and one archive queue."""
     assert "cfg5 ok" in run_worker("cfg5", 1500)
