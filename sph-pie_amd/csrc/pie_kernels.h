@@ -3970,9 +3970,10 @@ __global__ __launch_bounds__(256) void k_union_write(int n_users, int u_pad, con
 
 // ------------------------------------------------------------------------------------------------ table maintenance
 
-// The two row bodies of the mutators.  Every kernel that appends a row or re-ends one (k_append_rows, k_set_end and their
-// sharded forms at the end of this file) finds its (row, user) in its own way and then calls one of these: the derived state of
-// a row (both keys, the payload record, the hot index's and the ordered run's mirrors) is kept in step in one place.
+// The three row bodies of the mutators.  Every kernel that appends a row, re-ends one or deletes one (k_append_rows, k_set_end
+// and their sharded forms at the end of this file; k_list_write and k_users_pass<true> below) finds its (row, user) in its own
+// way and then calls one of these: the derived state of a row (both keys, the payload record, the hot index's and the ordered
+// run's mirrors) is kept in step in one place.
 // key / fkey / pay may be NULL (the growth path of a sharded append: build_keys follows).
 
 // re-end row r: the `end` store, both keys, the ordered run's mirror, the hot index's mirror
@@ -3986,6 +3987,18 @@ __device__ __forceinline__ void touch_row(long long r, long long e, long long* _
     if (fkey) fkey[r] = (fkey_t)fk;
     ord_mirror_end(ord, r, e, kk, fk);
     hot_mirror_end(hot, r, e, fk);
+}
+
+// delete row r: THE tombstone.  end = INT64_MIN and both liveness keys 0 — by definition, under every base and shift, which is
+// why this does not go through touch_row (it derives the keys from `e`) — and both mirrors told the same.
+__device__ __forceinline__ void tombstone_row(long long* __restrict__ end, lkey_t* __restrict__ key, fkey_t* __restrict__ fkey,
+                                              const OrdMirror& ord, const HotMirror& hot, long long r)
+{
+    end[r] = INT64_MIN;
+    if (key) key[r] = 0;
+    if (fkey) fkey[r] = 0;
+    ord_mirror_end(ord, r, INT64_MIN, 0u, 0u);
+    hot_mirror_end(hot, r, INT64_MIN, 0u);
 }
 
 // new row r: the four columns, both keys under the table's current parameters, the payload record, the hot index's mirror
@@ -4078,15 +4091,79 @@ __global__ __launch_bounds__(256) void k_validate_users(const int* __restrict__ 
 // ------------------------------------------------------------------------------------------------ ordered row lists
 
 // Order-preserving compaction of the rows matching a one-column predicate, in three steps:
-// per-block counts -> prefix (k_block_prefix) -> ordered write.
-//   MODE 0  newly expired: prev_now < end <= now ("next" row of SURVEY.md §8f-1: dead per
-//           /root/reference/server/sessionStore.js:69 at `now`, not yet dead at `prev_now`)
-//   MODE 1  deleteSessionsForUser (/root/reference/server/sessionStore.js:55-64): user == target, strict
-//           match; the write step tombstones the row (end = INT64_MIN: never live again)
-//   MODE 3  retention purge with calendar months (see add_months_ms); tombstones like MODE 1; `aux` = start column
-//   MODE 2  _pruneCalendarEvents (/root/reference/server/storage/sqlProvider.js:956-968): start < cutoff, the
-//           complement of the window predicate; tombstones like MODE 1.  `aux` is the start column here.
-// Calendar-month arithmetic of /root/reference/server/storage/sqlProvider.js:999-1009 (_addMonths:
+// per-block counts (block_count_rows) -> prefix (k_block_prefix) -> ordered write (BlockPlace).  The predicates of k_list_*:
+//   kExpired      newly expired: prev_now < end <= now ("next" row of SURVEY.md §8f-1: dead per server/sessionStore.js:69 at
+//                 `now`, not yet dead at `prev_now`); a = prev_now, b = now.  The only mode that leaves the row alone.
+//   kOneUser      deleteSessionsForUser (server/sessionStore.js:55-64): user == a, strict match; the write step tombstones
+//                 the row (tombstone_row: never live again), as every mode below does
+//   kPrune        _pruneCalendarEvents (server/storage/sqlProvider.js:956-968): start < a, the complement of the window predicate
+//   kRetention    retention purge with calendar months under a fixed offset (see add_months_ms): a = now, b = retention_pack()
+//   kRetentionTz  the same under a real time zone (add_months_tz): a = now, b = the device address of the zone's table
+enum ListMode : int { kExpired = 0, kOneUser = 1, kPrune = 2, kRetention = 3, kRetentionTz = 4 };
+
+// the columns a predicate may read, each under its own type (a mode reads `end` and one of the other two)
+struct ListCols {
+    const long long* end;
+    const int* user;
+    const long long* start;
+};
+
+// kRetention's `b`: months in the low 16 bits (signed), the zone's fixed offset in whole minutes above them.  Packed here by the
+// host, unpacked by list_match and nowhere else.
+__host__ __device__ inline long long retention_pack(int months, long long tz_minutes)
+{
+    return (tz_minutes << 16) | (long long)((unsigned)months & 0xFFFFu);
+}
+
+// The per-block count of the three steps: blk_count[block] = rows of [block * rows_per_block, ...) that `hit` accepts.
+// lds4 is the kernel's own LDS (4 long long).
+template <class Hit>
+__device__ __forceinline__ void block_count_rows(long long n, long long rows_per_block, int* __restrict__ blk_count, long long* lds4,
+                                                 Hit hit)
+{
+    const long long c0 = (long long)blockIdx.x * rows_per_block;
+    const long long c1 = min(n, c0 + rows_per_block);
+    long long local = 0;
+    for (long long r = c0 + threadIdx.x; r < c1; r += blockDim.x) local += hit(r) ? 1 : 0;
+    local = block_sum_256(local, lds4);
+    if (threadIdx.x == 0) blk_count[blockIdx.x] = (int)local;
+}
+
+// The block-ordered write of the three steps (256 threads): every wave brings the number of hits it has in a step, and gets
+// back the position of its first one — the block's offset, the hits of the steps before, the hits of the waves below.  The
+// caller adds the hit's rank inside its wave (one ballot, or two for kernels that hold two rows per lane).
+// Every thread of the block calls begin() once, then base() and advance() once per step, all at block-uniform places: base()
+// holds one barrier, advance() two.  The kernel declares the one `__shared__ BlockPlace`.
+struct BlockPlace {
+    int wcount[kK1Waves];
+    long long carry;
+
+    __device__ __forceinline__ void begin(const long long* __restrict__ blk_off)
+    {
+        if (threadIdx.x == 0) carry = blk_off[blockIdx.x];
+        __syncthreads();
+    }
+    // wave_total is wave-uniform
+    __device__ __forceinline__ long long base(int wave_total)
+    {
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        if (lane == 0) wcount[wave] = wave_total;
+        __syncthreads();
+        long long at = carry;
+        for (int w = 0; w < wave; ++w) at += wcount[w];
+        return at;
+    }
+    // after the step's stores: the next step starts behind this one's hits
+    __device__ __forceinline__ void advance()
+    {
+        __syncthreads();
+        if (threadIdx.x == 0) carry += wcount[0] + wcount[1] + wcount[2] + wcount[3];
+        __syncthreads();
+    }
+};
+static_assert(kK1Waves == 4, "BlockPlace::advance sums four waves");
+
+// Calendar-month arithmetic of server/storage/sqlProvider.js:999-1009 (_addMonths:
 // `date.setMonth(date.getMonth() + months)` on a local-time Date), in integers: local = UTC + tz (fixed offset),
 // civil date from the day number, month index shifted, day number of (year', month', 1) + (day - 1) — the
 // normalisation JS's MakeDay performs, so "Dec 31 + 2 months" lands on Mar 3 (Mar 2 in a leap year) — and back.
@@ -4185,74 +4262,63 @@ __device__ __forceinline__ long long shift_months_local(long long local, int mon
     return days2 * kDay + ms_of_day;                                          // < ~9e15 * small: fits
 }
 
-template <int MODE>
-__device__ __forceinline__ bool list_match(const long long* __restrict__ end, const int* __restrict__ user, long long r,
-                                           long long a, long long b)
+template <ListMode MODE>
+__device__ __forceinline__ bool list_match(const ListCols& col, long long r, long long a, long long b)
 {
-    if constexpr (MODE == 0) {
-        const long long e = end[r];
+    if constexpr (MODE == kExpired) {
+        const long long e = col.end[r];
         return e <= b && e > a;
-    } else if constexpr (MODE == 1) {
-        return user[r] == (int)a && end[r] != INT64_MIN;
-    } else if constexpr (MODE == 2) {
-        return reinterpret_cast<const long long*>(user)[r] < a && end[r] != INT64_MIN;
+    } else if constexpr (MODE == kOneUser) {
+        return col.user[r] == (int)a && col.end[r] != INT64_MIN;
+    } else if constexpr (MODE == kPrune) {
+        return col.start[r] < a && col.end[r] != INT64_MIN;
     } else {
-        // MODE 3  retention purge (/root/reference/server/storage/sqlProvider.js:863-890,991-997): now >= addMonths(start,
-        //         months); `a` = now, `b` packs months (low 16 bits, signed) and the zone offset in minutes (above)
-        if (end[r] == INT64_MIN) return false;
+        // retention purge (server/storage/sqlProvider.js:863-890,991-997): now >= addMonths(start, months); `a` = now
+        if (col.end[r] == INT64_MIN) return false;
         bool ok;
-        if constexpr (MODE == 4) { // ... under a real time zone: `b` = device address of the zone's transition table (TzView)
+        if constexpr (MODE == kRetentionTz) { // `b` is a device address: the zone's transition table (TzView), words [1] = months
             const long long* tab = reinterpret_cast<const long long*>(b);
-            const long long expiry = add_months_tz(reinterpret_cast<const long long*>(user)[r], (int)tab[1], tz_view(tab), ok);
+            const long long expiry = add_months_tz(col.start[r], (int)tab[1], tz_view(tab), ok);
             return ok && a >= expiry;
         }
-        const int months = (int)(short)(b & 0xFFFF);
+        const int months = (int)(short)(b & 0xFFFF); // retention_pack, unpacked
         const long long tz_ms = (b >> 16) * 60000LL;
-        const long long expiry = add_months_ms(reinterpret_cast<const long long*>(user)[r], months, tz_ms, ok);
+        const long long expiry = add_months_ms(col.start[r], months, tz_ms, ok);
         return ok && a >= expiry;
     }
 }
 
-template <int MODE>
-__global__ __launch_bounds__(256) void k_list_count(const long long* __restrict__ end, const int* __restrict__ user, long long n,
-                                                    long long rows_per_block, long long a, long long b,
-                                                    int* __restrict__ blk_count)
+template <ListMode MODE>
+__global__ __launch_bounds__(256) void k_list_count(const long long* __restrict__ end, const int* __restrict__ user,
+                                                    const long long* __restrict__ start, long long n, long long rows_per_block,
+                                                    long long a, long long b, int* __restrict__ blk_count)
 {
     __shared__ long long lds4[4];
-    const long long c0 = (long long)blockIdx.x * rows_per_block;
-    const long long c1 = min(n, c0 + rows_per_block);
-    long long local = 0;
-    for (long long r = c0 + threadIdx.x; r < c1; r += blockDim.x) local += list_match<MODE>(end, user, r, a, b) ? 1 : 0;
-    local = block_sum_256(local, lds4);
-    if (threadIdx.x == 0) blk_count[blockIdx.x] = (int)local;
+    const ListCols col{end, user, start};
+    block_count_rows(n, rows_per_block, blk_count, lds4, [&](long long r) { return list_match<MODE>(col, r, a, b); });
 }
 
 // MAPPED (a shard that answers in GLOBAL rows, pie_shard_prune_before / pie_shard_retention_purge*): the one store of a hit
 // is row_map[r], the shard's ascending local row -> global row map, as k_expq_pass does it; no gather behind the write.
 // local_q (MAPPED only, may be NULL): the same position also receives the local row (the communicator's source rows).
-template <int MODE, bool MAPPED = false>
-__global__ __launch_bounds__(256) void k_list_write(long long* __restrict__ end, const int* __restrict__ user, long long n,
-                                                    long long rows_per_block, long long a, long long b,
-                                                    const long long* __restrict__ blk_off, int* __restrict__ queue, long long cap,
-                                                    lkey_t* __restrict__ key, fkey_t* __restrict__ fkey, OrdMirror ord, HotMirror hot,
+template <ListMode MODE, bool MAPPED = false>
+__global__ __launch_bounds__(256) void k_list_write(long long* __restrict__ end, const int* __restrict__ user,
+                                                    const long long* __restrict__ start, long long n, long long rows_per_block,
+                                                    long long a, long long b, const long long* __restrict__ blk_off,
+                                                    int* __restrict__ queue, long long cap, lkey_t* __restrict__ key,
+                                                    fkey_t* __restrict__ fkey, OrdMirror ord, HotMirror hot,
                                                     const int* __restrict__ row_map = nullptr, int* __restrict__ local_q = nullptr)
 {
-    __shared__ int wcount[4];
-    __shared__ long long carry_s;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    __shared__ BlockPlace place;
+    const ListCols col{end, user, start};
     const long long c0 = (long long)blockIdx.x * rows_per_block;
     const long long c1 = min(n, c0 + rows_per_block);
-    if (threadIdx.x == 0) carry_s = blk_off[blockIdx.x];
-    __syncthreads();
-    for (long long r0 = c0; r0 < c1; r0 += blockDim.x) {
+    place.begin(blk_off);
+    for (long long r0 = c0; r0 < c1; r0 += blockDim.x) { // block-uniform bounds: every thread meets every barrier
         const long long r = r0 + threadIdx.x;
-        const bool hit = r < c1 && list_match<MODE>(end, user, r, a, b);
+        const bool hit = r < c1 && list_match<MODE>(col, r, a, b);
         const unsigned long long bal = __ballot(hit);
-        if (lane == 0) wcount[wave] = __popcll(bal);
-        __syncthreads();
-        long long base = carry_s;
-        for (int w = 0; w < wave; ++w) base += wcount[w];
-        const long long pos = base + prefix_in_ballot(bal);
+        const long long pos = place.base(__popcll(bal)) + prefix_in_ballot(bal);
         if constexpr (MAPPED) {
             if (hit && pos < cap) {
                 queue[pos] = row_map[r];
@@ -4261,18 +4327,10 @@ __global__ __launch_bounds__(256) void k_list_write(long long* __restrict__ end,
         } else {
             if (hit && pos < cap) queue[pos] = (int)r;
         }
-        if constexpr (MODE != 0) {
-            if (hit) { // a tombstone's liveness keys are 0 under every base
-                end[r] = INT64_MIN;
-                if (key) key[r] = 0;
-                if (fkey) fkey[r] = 0;
-                ord_mirror_end(ord, r, INT64_MIN, 0u, 0u);
-                hot_mirror_end(hot, r, INT64_MIN, 0u);
-            }
+        if constexpr (MODE != kExpired) {
+            if (hit) tombstone_row(end, key, fkey, ord, hot, r);
         }
-        __syncthreads();
-        if (threadIdx.x == 0) carry_s += wcount[0] + wcount[1] + wcount[2] + wcount[3];
-        __syncthreads();
+        place.advance();
     }
 }
 
@@ -4308,7 +4366,7 @@ __device__ __forceinline__ bool du_hit(const long long* end, int u, long long r,
 }
 
 // WRITE = false: wave_count[4 * block + wave] = hits of the wave's rows.  WRITE = true: the hits' rows behind wave_off[...] in
-// `queue`, and every hit tombstoned exactly as k_list_write<1> does it.
+// `queue`, and every hit tombstoned (tombstone_row).
 template <bool WRITE>
 __global__ __launch_bounds__(kK1Threads) void k_users_pass(long long* end, const int* __restrict__ user, long long n, long long rows_per_block,
                                                            const unsigned int* __restrict__ bits, int n_users, int* __restrict__ wave_count,
@@ -4346,11 +4404,7 @@ __global__ __launch_bounds__(kK1Threads) void k_users_pass(long long* end, const
                     const long long r = r4 + i;
                     if (pos < cap) queue[pos] = (int)r;
                     ++pos;
-                    end[r] = INT64_MIN; // a tombstone's liveness keys are 0 under every base
-                    if (key) key[r] = 0;
-                    if (fkey) fkey[r] = 0;
-                    ord_mirror_end(ord, r, INT64_MIN, 0u, 0u);
-                    hot_mirror_end(hot, r, INT64_MIN, 0u);
+                    tombstone_row(end, key, fkey, ord, hot, r);
                 }
                 cursor += wtotal;
             } else {
@@ -4415,15 +4469,10 @@ __global__ __launch_bounds__(256) void k_shard_row_count(const int* __restrict__
                                                          const int* __restrict__ local_of_global, int n_users, int* __restrict__ blk_count)
 {
     __shared__ long long lds4[4];
-    const long long c0 = (long long)blockIdx.x * rows_per_block;
-    const long long c1 = min(n, c0 + rows_per_block);
-    long long local = 0;
-    for (long long r = c0 + threadIdx.x; r < c1; r += blockDim.x) {
+    block_count_rows(n, rows_per_block, blk_count, lds4, [&](long long r) {
         const int u = user[r];
-        local += ((unsigned)u < (unsigned)n_users && local_of_global[u] >= 0) ? 1 : 0;
-    }
-    local = block_sum_256(local, lds4);
-    if (threadIdx.x == 0) blk_count[blockIdx.x] = (int)local;
+        return (unsigned)u < (unsigned)n_users && local_of_global[u] >= 0;
+    });
 }
 
 __global__ __launch_bounds__(256) void k_shard_row_write(const long long* __restrict__ start, const long long* __restrict__ end,
@@ -4433,14 +4482,11 @@ __global__ __launch_bounds__(256) void k_shard_row_write(const long long* __rest
                                                          long long* __restrict__ o_end, int* __restrict__ o_user, int* __restrict__ o_disc,
                                                          int* __restrict__ o_row)
 {
-    __shared__ int wcount[4];
-    __shared__ long long carry_s;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    __shared__ BlockPlace place;
     const long long c0 = (long long)blockIdx.x * rows_per_block;
     const long long c1 = min(n, c0 + rows_per_block);
-    if (threadIdx.x == 0) carry_s = blk_off[blockIdx.x];
-    __syncthreads();
-    for (long long r0 = c0; r0 < c1; r0 += blockDim.x) {
+    place.begin(blk_off);
+    for (long long r0 = c0; r0 < c1; r0 += blockDim.x) { // block-uniform bounds: every thread meets every barrier
         const long long r = r0 + threadIdx.x;
         int lu = -1;
         if (r < c1) {
@@ -4449,11 +4495,7 @@ __global__ __launch_bounds__(256) void k_shard_row_write(const long long* __rest
         }
         const bool hit = lu >= 0;
         const unsigned long long bal = __ballot(hit);
-        if (lane == 0) wcount[wave] = __popcll(bal);
-        __syncthreads();
-        long long base = carry_s;
-        for (int w = 0; w < wave; ++w) base += wcount[w];
-        const long long pos = base + prefix_in_ballot(bal);
+        const long long pos = place.base(__popcll(bal)) + prefix_in_ballot(bal);
         if (hit) {
             o_start[pos] = start[r];
             o_end[pos] = end[r];
@@ -4461,9 +4503,7 @@ __global__ __launch_bounds__(256) void k_shard_row_write(const long long* __rest
             o_disc[pos] = disc[r];
             o_row[pos] = (int)r;
         }
-        __syncthreads();
-        if (threadIdx.x == 0) carry_s += wcount[0] + wcount[1] + wcount[2] + wcount[3];
-        __syncthreads();
+        place.advance();
     }
 }
 
@@ -4721,16 +4761,16 @@ __global__ __launch_bounds__(256) void k_arch_select(const long long* __restrict
                                                      const long long* __restrict__ blk_off, unsigned int* __restrict__ keys, int* __restrict__ rows)
 {
     extern __shared__ unsigned int l_bits[];
-    __shared__ int wcount[4];
-    __shared__ long long carry_s;
+    __shared__ BlockPlace place; // the count form uses its wcount alone
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if constexpr (LDS_BITS) {
         for (int i = threadIdx.x; i < words; i += 256) l_bits[i] = bits[i];
     }
     const long long c0 = (long long)blockIdx.x * rows_per_block; // rows_per_block is even
     const long long c1 = min(n, c0 + rows_per_block);
-    if (threadIdx.x == 0) carry_s = WRITE ? blk_off[blockIdx.x] : 0;
-    __syncthreads();
+    // one barrier either way: it also publishes l_bits
+    if constexpr (WRITE) place.begin(blk_off);
+    else __syncthreads();
     const unsigned int* bt = LDS_BITS ? l_bits : bits;
     long long total = 0;
     for (long long r0 = c0; r0 < c1; r0 += 512) { // 256 threads x 2 rows
@@ -4748,30 +4788,21 @@ __global__ __launch_bounds__(256) void k_arch_select(const long long* __restrict
             h0 = end[r] != INT64_MIN && (unsigned)g0 < (unsigned)n_users && ((bt[g0 >> 5] >> (g0 & 31)) & 1u);
         }
         const unsigned long long b0 = __ballot(h0), b1 = __ballot(h1);
-        const int mine = (h0 ? 1 : 0) + (h1 ? 1 : 0);
-        // rows of a lane are consecutive: position inside the wave = both rows of every lane below + this lane's own
-        const int before = prefix_in_ballot(b0) + prefix_in_ballot(b1);
         const int wtotal = __popcll(b0) + __popcll(b1);
         if constexpr (WRITE) {
-            if (lane == 0) wcount[wave] = wtotal;
-            __syncthreads();
-            long long base = carry_s;
-            for (int w = 0; w < wave; ++w) base += wcount[w];
-            long long pos = base + before;
+            // rows of a lane are consecutive: position inside the wave = both rows of every lane below + this lane's own
+            long long pos = place.base(wtotal) + prefix_in_ballot(b0) + prefix_in_ballot(b1);
             if (h0) { keys[pos] = (unsigned)g0; rows[pos] = (int)r; ++pos; }
             if (h1) { keys[pos] = (unsigned)g1; rows[pos] = (int)(r + 1); }
-            __syncthreads();
-            if (threadIdx.x == 0) carry_s += wcount[0] + wcount[1] + wcount[2] + wcount[3];
-            __syncthreads();
+            place.advance();
         } else {
-            (void)mine; (void)before;
             total += wtotal; // wave-uniform
         }
     }
     if constexpr (!WRITE) {
-        if (lane == 0) wcount[wave] = (int)total;
+        if (lane == 0) place.wcount[wave] = (int)total;
         __syncthreads();
-        if (threadIdx.x == 0) blk_count[blockIdx.x] = wcount[0] + wcount[1] + wcount[2] + wcount[3];
+        if (threadIdx.x == 0) blk_count[blockIdx.x] = place.wcount[0] + place.wcount[1] + place.wcount[2] + place.wcount[3];
     }
 }
 // after the stable sort by group: the head of a group's run is its first row, head and tail give its place and size

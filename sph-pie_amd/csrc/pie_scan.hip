@@ -2679,58 +2679,120 @@ int run_scan(pie_ctx* c, long long now, long long cutoff)
     return scan_finish(c);
 }
 
+// ---------------------------------------------------------------------------------------------- synchronous row lists
+// The calls that walk the table once and answer with an ordered list of rows (run_row_list, delete_users_run,
+// pie_expired_queue, pie_archive_queue) enter and leave through the three helpers below.
+
+// What a call does on entry, in this order: forget the device-side queue; refuse "no table loaded"; report an empty table
+// (*empty: the caller returns PIE_OK in its own way); refuse "a scan is in flight"; [kRefuseTurns] refuse a begun token turn;
+// select the device; [kSyncAll] wait for every stream of the context; [kDropSlot0 / kDropSlots] give up the scan result whose
+// workspace the list is about to use (drop_results).  kChecksOnly stops before the device is selected.
+//
+//   call                             kRefuseTurns  kSyncAll  results given up
+//   run_row_list (row_list)          yes           yes       slot 0 (kDropSlot0); slot 1 later, when local rows are wanted
+//   delete_users_run                 yes           yes       slot 0 (kDropSlot0)
+//   pie_expired_queue                no            no        slots 0 and 1 (kDropSlots)
+//   pie_expired_queue, two-pass arm  kChecksOnly, then row_list's own entry
+//   pie_archive_queue                no            yes       slots 0 and 1, by itself after its allocations (drop_results)
+enum ListEnter : unsigned { kChecksOnly = 0, kRefuseTurns = 1, kSyncAll = 2, kDropSlot0 = 4, kDropSlots = 8 };
+
+// both = false: slot 0's result, and the context's current result only if it was that one; both = true: both slots', and the
+// current result whichever it was
+void drop_results(pie_ctx* c, bool both)
+{
+    c->slot[0].have_result = false;
+    if (both) c->slot[1].have_result = false;
+    if (both || c->res == &c->slot[0]) c->res = nullptr;
+}
+
+int list_enter(pie_ctx* c, unsigned flags, bool* empty)
+{
+    *empty = false;
+    queue_forget(c);
+    if (c->cap_rows == 0) return fail(c, PIE_E_STATE, "no table loaded");
+    if (c->n == 0) { *empty = true; return PIE_OK; }
+    if (c->n_flight || c->b_flight) return fail(c, PIE_E_STATE, "a scan is in flight");
+    if (flags == kChecksOnly) return PIE_OK;
+    if ((flags & kRefuseTurns) && turns_begun(c)) return fail(c, PIE_E_STATE, "a token turn is begun and not finished (pie_token_turn_finish)");
+    PIE_HIP(c, hipSetDevice(c->device));
+    if (flags & kSyncAll) { // the workspace is shared with the scans' tails, the staging block with appends / touches
+        const int rc = sync_all(c);
+        if (rc) return rc;
+    }
+    if (flags & (kDropSlot0 | kDropSlots)) drop_results(c, (flags & kDropSlots) != 0);
+    return PIE_OK;
+}
+
+// the list's length: what the prefix kernel left in d_summary->m, behind everything queued on s
+int list_total(pie_ctx* c, hipStream_t s, size_t* m)
+{
+    PIE_HIP(c, hipMemcpyAsync(c->h_summary, c->d_summary, sizeof(Summary), hipMemcpyDeviceToHost, s));
+    PIE_HIP(c, hipStreamSynchronize(s));
+    *m = (size_t)c->h_summary->m;
+    return PIE_OK;
+}
+
+// m rows of the device-side list -> out (may be NULL: nothing is copied).  A list longer than `cap` is refused here, AFTER
+// the write pass: the rows are tombstoned all the same, and PIE_E_CAPACITY tells the count the caller has already stored.
+int list_copy_out(pie_ctx* c, const int* dev, size_t m, int32_t* out, size_t cap, const char* what)
+{
+    if (out && m > cap) return fail(c, PIE_E_CAPACITY, "%s cap %zu < %zu", what, cap, m);
+    if (out && m) {
+        PIE_HIP(c, hipMemcpyAsync(out, dev, m * 4, hipMemcpyDeviceToHost, c->stream));
+        PIE_HIP(c, hipStreamSynchronize(c->stream));
+    }
+    return PIE_OK;
+}
+
 // ordered list of the rows matching a one-column predicate (expired queue / user match), through slot 0's
 // workspace: blk_count + blk_off for the per-block prefix, out_idx as the device-side list
 // MAPPED: the context is a shard whose row map covers its rows (the caller checked); the list holds GLOBAL rows, stored by the
 // write pass itself.  want_local (MAPPED only): the local rows go beside them into slot 1's out_idx, whose result is given up.
-template <int MODE, bool MAPPED = false>
+template <ListMode MODE, bool MAPPED = false>
 int run_row_list(pie_ctx* c, long long a, long long b, int32_t* out, size_t cap, size_t* k_out, bool want_local = false)
 {
     if (k_out) *k_out = 0;
-    queue_forget(c);
-    if (c->cap_rows == 0) return fail(c, PIE_E_STATE, "no table loaded");
-    if (c->n == 0) return PIE_OK;
-    if (c->n_flight || c->b_flight) return fail(c, PIE_E_STATE, "a scan is in flight");
-    if (turns_begun(c)) return fail(c, PIE_E_STATE, "a token turn is begun and not finished (pie_token_turn_finish)");
-    PIE_HIP(c, hipSetDevice(c->device));
-    int rc = sync_all(c); // the workspace below is shared with the scans' tails
-    if (rc) return rc;
+    bool empty;
+    int rc = list_enter(c, kRefuseTurns | kSyncAll | kDropSlot0, &empty);
+    if (rc || empty) return rc;
     hipStream_t s = c->stream;
     Slot& sl = c->slot[0];
-    sl.have_result = false;
-    if (c->res == &sl) c->res = nullptr;
     const int blocks = c->plan_blocks[0];
     const long long rpb = c->plan_rows[0];
-    // MODE 2 matches on the start column: it travels through the kernels' generic second-column pointer
-    const int* col2 = (MODE == 2 || MODE == 3 || MODE == 4) ? reinterpret_cast<const int*>(c->d_start) : c->d_user;
-    hipLaunchKernelGGL(k_list_count<MODE>, dim3(blocks), dim3(256), 0, s, c->d_end, col2, c->n, rpb, a, b, sl.blk_count);
+    hipLaunchKernelGGL(k_list_count<MODE>, dim3(blocks), dim3(256), 0, s, c->d_end, c->d_user, c->d_start, c->n, rpb, a, b, sl.blk_count);
     hipLaunchKernelGGL(k_block_prefix, dim3(1), dim3(256), 0, s, sl.blk_count, blocks, c->d_blk_off, &c->d_summary->m);
+    const int* row_map = nullptr;
+    int* local_q = nullptr;
     if constexpr (MAPPED) {
-        int* local_q = nullptr;
+        row_map = c->d_shard_rows;
         if (want_local) {
             c->slot[1].have_result = false;
             c->res = nullptr;
             local_q = c->slot[1].out_idx;
         }
-        hipLaunchKernelGGL((k_list_write<MODE, true>), dim3(blocks), dim3(256), 0, s, c->d_end, col2, c->n, rpb, a, b,
-                           c->d_blk_off, sl.out_idx, c->cap_rows, c->d_key, c->d_fkey, ord_mirror_of(c), hot_mirror_of(c),
-                           (const int*)c->d_shard_rows, local_q);
-    } else {
-        hipLaunchKernelGGL((k_list_write<MODE, false>), dim3(blocks), dim3(256), 0, s, c->d_end, col2, c->n, rpb, a, b,
-                           c->d_blk_off, sl.out_idx, c->cap_rows, c->d_key, c->d_fkey, ord_mirror_of(c), hot_mirror_of(c),
-                           (const int*)nullptr, (int*)nullptr);
     }
+    hipLaunchKernelGGL((k_list_write<MODE, MAPPED>), dim3(blocks), dim3(256), 0, s, c->d_end, c->d_user, c->d_start, c->n, rpb, a, b,
+                       c->d_blk_off, sl.out_idx, c->cap_rows, c->d_key, c->d_fkey, ord_mirror_of(c), hot_mirror_of(c), row_map, local_q);
     PIE_HIP(c, hipGetLastError());
-    PIE_HIP(c, hipMemcpyAsync(c->h_summary, c->d_summary, sizeof(Summary), hipMemcpyDeviceToHost, s));
-    PIE_HIP(c, hipStreamSynchronize(s));
-    const size_t k = (size_t)c->h_summary->m;
+    size_t k = 0;
+    rc = list_total(c, s, &k);
+    if (rc) return rc;
     if (k_out) *k_out = k;
-    if (out && k > cap) return fail(c, PIE_E_CAPACITY, "list cap %zu < %zu", cap, k);
-    if (out && k) {
-        PIE_HIP(c, hipMemcpyAsync(out, sl.out_idx, k * 4, hipMemcpyDeviceToHost, s));
-        PIE_HIP(c, hipStreamSynchronize(s));
+    return list_copy_out(c, sl.out_idx, k, out, cap, "list"); // after the write pass: see list_copy_out
+}
+
+// The one way in: which instantiation a (mode, mapped) pair runs.  Shards answer the three maintenance lists in global rows;
+// the expired queue and the one-user delete have no mapped form.
+int row_list(pie_ctx* c, ListMode mode, bool mapped, long long a, long long b, int32_t* out, size_t cap, size_t* k_out, bool want_local)
+{
+    switch (mode) {
+    case kExpired: return run_row_list<kExpired>(c, a, b, out, cap, k_out);
+    case kOneUser: return run_row_list<kOneUser>(c, a, b, out, cap, k_out);
+    case kPrune: return mapped ? run_row_list<kPrune, true>(c, a, b, out, cap, k_out, want_local) : run_row_list<kPrune>(c, a, b, out, cap, k_out);
+    case kRetention: return mapped ? run_row_list<kRetention, true>(c, a, b, out, cap, k_out, want_local) : run_row_list<kRetention>(c, a, b, out, cap, k_out);
+    case kRetentionTz: return mapped ? run_row_list<kRetentionTz, true>(c, a, b, out, cap, k_out, want_local) : run_row_list<kRetentionTz>(c, a, b, out, cap, k_out);
     }
-    return PIE_OK;
+    return fail(c, PIE_E_INVAL, "unknown list mode %d", (int)mode);
 }
 
 
@@ -4567,7 +4629,7 @@ int pie_delete_user(pie_ctx* c, int32_t user, int32_t* rows_out, size_t cap, siz
     if (n_deleted) *n_deleted = 0;
     if (c->n == 0 || user < 0 || user >= c->n_users) return PIE_OK; // unknown / falsy id: no-op (sessionStore.js:56-58)
     // the rows are tombstoned even when rows_out is too small to list them (PIE_E_CAPACITY then tells the count)
-    return run_row_list<1>(c, (long long)user, 0, rows_out, cap, n_deleted);
+    return row_list(c, kOneUser, false, (long long)user, 0, rows_out, cap, n_deleted, false);
 }
 
 int pie_delete_users_plan(const int32_t* users, size_t k, int32_t n_users, uint64_t* bits_out, uint8_t* first_out)
@@ -4609,17 +4671,11 @@ static int delete_users_run(pie_ctx* c, const int32_t* users, size_t k, bool to_
     }
     const size_t d = ids.size();
     if (d == 0) return PIE_OK; // no id the table knows: as k calls that each found the falsy-id guard
-    queue_forget(c);
-    if (c->cap_rows == 0) return fail(c, PIE_E_STATE, "no table loaded");
-    if (c->n_flight || c->b_flight) return fail(c, PIE_E_STATE, "a scan is in flight");
-    if (turns_begun(c)) return fail(c, PIE_E_STATE, "a token turn is begun and not finished (pie_token_turn_finish)");
-    PIE_HIP(c, hipSetDevice(c->device));
-    int rc = sync_all(c); // the workspace below is shared with the scans' tails, the staging block with appends / touches
-    if (rc) return rc;
+    bool empty; // never: both callers return before this on a table of no rows
+    int rc = list_enter(c, kRefuseTurns | kSyncAll | kDropSlot0, &empty);
+    if (rc || empty) return rc;
     hipStream_t s = c->stream;
     Slot& sl = c->slot[0];
-    sl.have_result = false;
-    if (c->res == &sl) c->res = nullptr;
     // one upload of [bitmap | distinct ids], the per-id counters behind them
     const size_t bits_bytes = words * 8, ids_bytes = d * 4;
     Staged st{};
@@ -4645,11 +4701,11 @@ static int delete_users_run(pie_ctx* c, const int32_t* users, size_t k, bool to_
         hipLaunchKernelGGL(k_users_tally, dim3(capped_grid(c, (size_t)c->n)), dim3(256), 0, s, (const int*)sl.out_idx,
                            (const unsigned long long*)&c->d_summary->m, c->cap_rows, (const int*)c->d_user, d_ids, (int)d, d_cnt);
     PIE_HIP(c, hipGetLastError());
-    PIE_HIP(c, hipMemcpyAsync(c->h_summary, c->d_summary, sizeof(Summary), hipMemcpyDeviceToHost, s));
     char* h_cnt = st.h + bits_bytes + ids_bytes;
-    if (per_user_out) PIE_HIP(c, hipMemcpyAsync(h_cnt, d_cnt, ids_bytes, hipMemcpyDeviceToHost, s));
-    PIE_HIP(c, hipStreamSynchronize(s));
-    const size_t m = (size_t)c->h_summary->m;
+    if (per_user_out) PIE_HIP(c, hipMemcpyAsync(h_cnt, d_cnt, ids_bytes, hipMemcpyDeviceToHost, s)); // list_total waits for it too
+    size_t m = 0;
+    rc = list_total(c, s, &m);
+    if (rc) return rc;
     *m_out = m;
     if (per_user_out) { // an id's count goes to its first occurrence; the later ones keep their 0
         const unsigned int* cnt = reinterpret_cast<const unsigned int*>(h_cnt);
@@ -4664,13 +4720,10 @@ static int delete_users_run(pie_ctx* c, const int32_t* users, size_t k, bool to_
     return PIE_OK;
 }
 
-// the list delete_users_run left on the device -> rows_out (m entries)
-static int delete_users_copy(pie_ctx* c, int32_t* rows_out, size_t m)
+// the list delete_users_run left on the device -> rows_out (m entries; more than `cap` are refused, tombstoned all the same)
+static int delete_users_copy(pie_ctx* c, int32_t* rows_out, size_t cap, size_t m)
 {
-    if (!rows_out || m == 0) return PIE_OK;
-    PIE_HIP(c, hipMemcpyAsync(rows_out, c->slot[0].out_idx, m * 4, hipMemcpyDeviceToHost, c->stream));
-    PIE_HIP(c, hipStreamSynchronize(c->stream));
-    return PIE_OK;
+    return list_copy_out(c, c->slot[0].out_idx, m, rows_out, cap, "list");
 }
 
 int pie_delete_users(pie_ctx* c, const int32_t* users, size_t k, int32_t* rows_out, size_t cap, size_t* n_deleted, int32_t* per_user_out)
@@ -4686,8 +4739,7 @@ int pie_delete_users(pie_ctx* c, const int32_t* users, size_t k, int32_t* rows_o
     if (rc) return rc;
     if (n_deleted) *n_deleted = m;
     // the rows are tombstoned even when rows_out is too small to list them (PIE_E_CAPACITY then tells the count)
-    if (rows_out && m > cap) return fail(c, PIE_E_CAPACITY, "list cap %zu < %zu", cap, m);
-    return delete_users_copy(c, rows_out, m);
+    return delete_users_copy(c, rows_out, cap, m);
 }
 
 // The three maintenance lists behind their plain and their shard entries.  `mapped`: the context is a shard whose row map
@@ -4696,8 +4748,7 @@ static int prune_impl(pie_ctx* c, int64_t cutoff, int32_t* rows_out, size_t cap,
 {
     if (n_pruned) *n_pruned = 0;
     if (c->n == 0) return PIE_OK;
-    if (mapped) return run_row_list<2, true>(c, (long long)cutoff, 0, rows_out, cap, n_pruned, want_local);
-    return run_row_list<2>(c, (long long)cutoff, 0, rows_out, cap, n_pruned);
+    return row_list(c, kPrune, mapped, (long long)cutoff, 0, rows_out, cap, n_pruned, want_local);
 }
 
 static int retention_check(pie_ctx* c, int32_t months, int64_t tz_offset_ms)
@@ -4715,9 +4766,7 @@ static int retention_impl(pie_ctx* c, int64_t now, int32_t months, int64_t tz_of
     const int rc = retention_check(c, months, tz_offset_ms);
     if (rc) return rc;
     if (c->n == 0) return PIE_OK;
-    const long long packed = ((tz_offset_ms / 60000) << 16) | (long long)((unsigned)months & 0xFFFFu);
-    if (mapped) return run_row_list<3, true>(c, (long long)now, packed, rows_out, cap, n_purged, want_local);
-    return run_row_list<3>(c, (long long)now, packed, rows_out, cap, n_purged);
+    return row_list(c, kRetention, mapped, (long long)now, retention_pack(months, tz_offset_ms / 60000), rows_out, cap, n_purged, want_local);
 }
 
 static int retention_tz_check(pie_ctx* c, int32_t months, const int64_t* transitions_utc_ms, const int64_t* offsets_ms, int32_t n_transitions)
@@ -4784,8 +4833,8 @@ static int retention_tz_impl(pie_ctx* c, int64_t now, int32_t months, const int6
     }
     for (int i = 0; i <= n; ++i) h[2 + 2 * n + i] = offsets_ms[i];
     PIE_HIP(c, hipMemcpyAsync(c->d_stage, c->h_stage, words * 8, hipMemcpyHostToDevice, c->stream));
-    if (mapped) return run_row_list<4, true>(c, (long long)now, (long long)(uintptr_t)c->d_stage, rows_out, cap, n_purged, want_local);
-    return run_row_list<4>(c, (long long)now, (long long)(uintptr_t)c->d_stage, rows_out, cap, n_purged);
+    const long long zone_table = (long long)(uintptr_t)c->d_stage; // kRetentionTz's `b` is a device address (list_match reads it back)
+    return row_list(c, kRetentionTz, mapped, (long long)now, zone_table, rows_out, cap, n_purged, want_local);
 }
 
 int pie_set_disciplines(pie_ctx* c, uint64_t mask, int32_t n_disc)
@@ -5427,25 +5476,23 @@ int pie_expired_queue(pie_ctx* c, int64_t prev_now, int64_t now, int32_t* queue_
 {
     if (!c) return PIE_E_INVAL;
     if (q_out) *q_out = 0;
-    queue_forget(c);
-    if (c->cap_rows == 0) return fail(c, PIE_E_STATE, "no table loaded");
-    if (c->n == 0) { c->q_kind = 1; return PIE_OK; } // an empty queue: nothing on the device to read
-    if (c->n_flight || c->b_flight) return fail(c, PIE_E_STATE, "a scan is in flight");
-    if (getenv("PIE_EXPIRED_TWO_PASS")) { // the count / prefix / write form, kept for A-B runs
+    const bool two_pass = getenv("PIE_EXPIRED_TWO_PASS") != nullptr; // the count / prefix / write form, kept for A-B runs
+    bool empty;
+    int rc = list_enter(c, two_pass ? kChecksOnly : kDropSlots, &empty);
+    if (rc) return rc;
+    if (empty) { c->q_kind = 1; return PIE_OK; } // an empty queue: nothing on the device to read
+    if (two_pass) {
         size_t k = 0;
-        const int rc = run_row_list<0>(c, (long long)prev_now, (long long)now, queue_out, cap, &k);
+        rc = row_list(c, kExpired, false, (long long)prev_now, (long long)now, queue_out, cap, &k, false);
         if (rc == PIE_OK || rc == PIE_E_CAPACITY) { c->q_kind = 1; c->q_rows = (long long)k; c->q_dev = c->slot[0].out_idx; }
         if (q_out) *q_out = k;
         return rc;
     }
-    PIE_HIP(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
     // workspace: slot 0's out_idx is the device-side queue, slot 1's out_idx the per-wave staging, slot 0's
     // blk_count the per-wave counts (4 per block of the liveness-first plan: <= the streaming plan's block count)
     Slot& q = c->slot[0];
     Slot& st = c->slot[1];
-    q.have_result = st.have_result = false;
-    c->res = nullptr;
     const int blocks = c->plan_blocks[1];
     const long long rpb = c->plan_rows[1];
     const int n_waves = blocks * kK1Waves;
@@ -5478,9 +5525,8 @@ int pie_expired_queue(pie_ctx* c, int64_t prev_now, int64_t now, int32_t* queue_
     }
     size_t k = 0;
     if (c->expired_copy_total) {
-        PIE_HIP(c, hipMemcpyAsync(c->h_summary, c->d_summary, sizeof(Summary), hipMemcpyDeviceToHost, s));
-        PIE_HIP(c, hipStreamSynchronize(s));
-        k = (size_t)c->h_summary->m;
+        rc = list_total(c, s, &k);
+        if (rc) return rc;
     } else {
         // bounded wait like a scan's; the gather behind the prefix kernel may still run when the length is known (everything that
         // reads the queue afterwards is queued on this stream, behind it)
@@ -5494,12 +5540,7 @@ int pie_expired_queue(pie_ctx* c, int64_t prev_now, int64_t now, int32_t* queue_
     c->q_rows = (long long)k;
     c->q_dev = q.out_idx;
     if (q_out) *q_out = k;
-    if (queue_out && k > cap) return fail(c, PIE_E_CAPACITY, "queue cap %zu < %zu", cap, k);
-    if (queue_out && k) {
-        PIE_HIP(c, hipMemcpyAsync(queue_out, q.out_idx, k * 4, hipMemcpyDeviceToHost, s));
-        PIE_HIP(c, hipStreamSynchronize(s));
-    }
-    return PIE_OK;
+    return list_copy_out(c, q.out_idx, k, queue_out, cap, "queue");
 }
 
 // The reference's archive chain on the device: group stats -> threshold on the host (U values) -> group-qualified
@@ -5521,13 +5562,10 @@ int pie_archive_queue(pie_ctx* c, int64_t now, int64_t window_ms, int32_t* queue
 {
     if (!c) return PIE_E_INVAL;
     if (q_out) *q_out = 0;
-    queue_forget(c);
-    if (c->cap_rows == 0) return fail(c, PIE_E_STATE, "no table loaded");
-    if (c->n == 0) { c->q_kind = 2; return PIE_OK; } // an empty queue: nothing on the device to read
-    if (c->n_flight || c->b_flight) return fail(c, PIE_E_STATE, "a scan is in flight");
-    PIE_HIP(c, hipSetDevice(c->device));
-    int rc = sync_all(c);
+    bool empty;
+    int rc = list_enter(c, kSyncAll, &empty); // the slots' results are given up below, once nothing can fail for want of memory
     if (rc) return rc;
+    if (empty) { c->q_kind = 2; return PIE_OK; } // an empty queue: nothing on the device to read
     rc = ensure_sel(c);
     if (rc) return rc;
     hipStream_t s = c->stream;
@@ -5554,8 +5592,7 @@ int pie_archive_queue(pie_ctx* c, int64_t now, int64_t window_ms, int32_t* queue
     unsigned int* d_nqual = reinterpret_cast<unsigned int*>(carve(256));
     Slot& sl = c->slot[0];
     Slot& other = c->slot[1];
-    sl.have_result = other.have_result = false;
-    c->res = nullptr;
+    drop_results(c, true);
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     if (c->profiling) {
         PIE_HIP(c, hipEventCreate(&ev0));
@@ -5580,10 +5617,10 @@ int pie_archive_queue(pie_ctx* c, int64_t now, int64_t window_ms, int32_t* queue
     hipLaunchKernelGGL(k_block_prefix, dim3(1), dim3(256), 0, s, sl.blk_count, blocks, c->d_blk_off, &c->d_summary->m);
     PIE_HIP(c, hipGetLastError());
     unsigned int n_qual = 0;
-    PIE_HIP(c, hipMemcpyAsync(c->h_summary, c->d_summary, sizeof(Summary), hipMemcpyDeviceToHost, s));
-    PIE_HIP(c, hipMemcpyAsync(&n_qual, d_nqual, 4, hipMemcpyDeviceToHost, s));
-    PIE_HIP(c, hipStreamSynchronize(s));
-    const size_t q = (size_t)c->h_summary->m;
+    PIE_HIP(c, hipMemcpyAsync(&n_qual, d_nqual, 4, hipMemcpyDeviceToHost, s)); // list_total waits for it too
+    size_t q = 0;
+    rc = list_total(c, s, &q);
+    if (rc) return rc;
     if (q_out) *q_out = q;
     c->arch_alg_bytes = 32ull * (unsigned long long)c->n + 4ull * q;
     if (queue_out && q > cap) return fail(c, PIE_E_CAPACITY, "queue cap %zu < %zu", cap, q);
@@ -6448,7 +6485,7 @@ int pie_shard_delete_user(pie_ctx* c, int32_t user_global, int32_t* rows_global_
     const auto it = std::lower_bound(um.begin(), um.end(), user_global);
     if (it == um.end() || *it != user_global || c->n == 0) return PIE_OK;
     size_t k = 0;
-    rc = run_row_list<1>(c, (long long)(it - um.begin()), 0, nullptr, 0, &k); // the list stays in slot 0's out_idx
+    rc = row_list(c, kOneUser, false, (long long)(it - um.begin()), 0, nullptr, 0, &k, false); // the list stays in slot 0's out_idx
     if (rc) return rc;
     if (n_deleted) *n_deleted = k;
     if (!rows_global_out || k == 0) return PIE_OK;
@@ -6501,7 +6538,7 @@ int shard_delete_users_run(pie_ctx* c, const int32_t* users_global, size_t k, si
     return delete_users_run(c, local.data(), k, true, m_out, per_user_out);
 }
 
-int shard_delete_users_copy(pie_ctx* c, int32_t* rows_global_out, size_t m) { return delete_users_copy(c, rows_global_out, m); }
+int shard_delete_users_copy(pie_ctx* c, int32_t* rows_global_out, size_t m) { return delete_users_copy(c, rows_global_out, m, m); }
 } // namespace pie_internal
 
 extern "C" {
@@ -6515,8 +6552,7 @@ int pie_shard_delete_users(pie_ctx* c, const int32_t* users_global, size_t k, in
     int rc = pie_internal::shard_delete_users_run(c, users_global, k, &m, per_user_out);
     if (rc) return rc;
     if (n_deleted) *n_deleted = m;
-    if (rows_global_out && m > cap) return fail(c, PIE_E_CAPACITY, "list cap %zu < %zu", cap, m); // the rows are tombstoned all the same
-    return delete_users_copy(c, rows_global_out, m);
+    return delete_users_copy(c, rows_global_out, cap, m); // refuses a list above cap; the rows are tombstoned all the same
 }
 
 // ---- pruneCalendarEvents / purgeExpiredArchives (server/storage/sqlProvider.js:956-968, 863-890, 991-1009) on a shard, answered
