@@ -391,6 +391,12 @@ int pie_archive_stats(pie_ctx *ctx, double *ms_sum_out, uint32_t *calls_out, uin
  * pie_queue_info: kind 1 = expired, 2 = archive (0: none — a scan, batch or table change since forgot it), its rows, and for
  * the archive queue its groups.  PIE_E_STATE when there is none, or when the table holds rows its shard map does not cover
  * (appended after pie_shard_table: they have no global row).
+ * What forgets it: every scan begin, and a batch that stages in the scan slots' workspace; every call that answers with a row
+ * list (prune, purge, delete_user(s), the two queue calls themselves, one that fails for capacity included); a load, generate,
+ * shard or compaction; and every call that adds rows or writes `end` through the table's own mutators — pie_append_rows,
+ * pie_set_end, their pie_shard_* and pie_token_* forms and a turn that logs in — whether it ran in place or had to grow the
+ * table.  A queue of row indices from before such a change is never handed out.  (pie_expired_queue_begin / _finish and a token
+ * turn that only touches or deletes leave it alone.)
  * pie_queue_pack_device: pack it into ONE int32 message in caller-owned device memory, one launch on the context's stream:
  *   [ n_rows | n_groups | global rows (cap_rows) | local rows (cap_rows) | group offsets (cap_groups + 1) ]
  * global row = the shard map's entry (the row itself on a context that was never sharded); group offsets = the exclusive

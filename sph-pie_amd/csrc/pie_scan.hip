@@ -554,7 +554,7 @@ struct pie_ctx {
     double arch_ms_sum = 0;                // with profiling on: device time of the archive chains (first kernel -> last sort)
     unsigned arch_calls = 0;
     // the queue the last pie_expired_queue / pie_archive_queue left on the device (pie_queue_info, pie_queue_pack_device); any
-    // call that reuses the slots' workspace forgets it (queue_forget)
+    // call that reuses the slots' workspace or changes the table forgets it (queue_forget)
     int q_kind = 0;                        // 0: none, 1: expired, 2: archive
     long long q_rows = 0;                  // its length
     int q_groups = 0;                      // archive: qualifying groups
@@ -1197,6 +1197,7 @@ int ensure_capacity(pie_ctx* c, long long n, int n_users, long long keep_rows = 
     if (rc) return rc;
     rc = sync_all(c);
     if (rc) return rc;
+    queue_forget(c); // a new table, or rows about to be added: the held queue is of the table as it was
     ord_invalidate(c, keep_rows == 0);
     if (keep_rows == 0) cmp_forget(c); // a new table (load, gen, shard, compact) renumbers the rows: the last compaction's maps go
     if (keep_rows == 0 && !c->tokx.hold) token_drop(c); // ... the token keys name the old rows (pie_compact_rows carries them over itself)
@@ -4255,6 +4256,7 @@ static int append_finish(pie_ctx* c, int n_users)
 {
     if (n_users > c->n_users) set_user_count(c, n_users);
     c->key_dirty = true;
+    queue_forget(c); // the held queue names groups as the table was before the rows came
     drop_results(c);
     plan_k1(c);
     return ensure_sel(c);
@@ -4583,6 +4585,7 @@ static int set_end_apply(pie_ctx* c, const int32_t* ids, const int64_t* new_end,
     size_t k = 0;
     for (size_t i = 0; i < k_given; ++i) k += keep[i];
     PIE_HIP(c, hipSetDevice(c->device));
+    queue_forget(c); // a touch or a tombstone can move a row into or out of the held queue
     hot_reserve(c, (long long)k_given); // the bound counts every element: never less than the rows that can move to the delta
     // staged like the append path: one upload of [new_end k | ids k], one kernel (end + both keys + mirrors), one wait or none
     Staged st{};
