@@ -449,9 +449,14 @@ def check_union(tag, un, wants, wide):
         assert not np.any(bits[:, nq // 64] >> np.uint64(nq % 64)), (tag, "a query bit beyond the batch")
 
 
-def ctx_with_env(pie, hot, async_mut):
-    """A context created under PIE_HOT_INDEX / PIE_ASYNC_MUTATIONS; the environment is restored before returning."""
-    want = {"PIE_HOT_INDEX": "1" if hot else "0", "PIE_ASYNC_MUTATIONS": "1" if async_mut else "0"}
+def ctx_with_env(pie, hot=None, async_mut=None, **env):
+    """A context created under PIE_HOT_INDEX / PIE_ASYNC_MUTATIONS (where given) and any further variables passed by name; the
+    environment is restored before returning."""
+    want = dict(env)
+    if hot is not None:
+        want["PIE_HOT_INDEX"] = "1" if hot else "0"
+    if async_mut is not None:
+        want["PIE_ASYNC_MUTATIONS"] = "1" if async_mut else "0"
     old = {k: os.environ.get(k) for k in want}
     os.environ.update(want)
     try:

@@ -1,7 +1,8 @@
 """GPU: the ordered run (sph-pie_amd/csrc/pie_ordered.h: the table a second time in (user, start, row) order; a query is a
 filter over positions) against the oracle — bit-exact counts / offsets / idx — in both of its forms (dense, keyed on the 2- and
 the 1-byte key), on ragged / empty / skewed tables, after every writer of `end`, after the changes that invalidate it, and under
-the adaptive rule that builds it.  Through the C ABI (ctypes)."""
+the adaptive rule that builds it.  Through the C ABI (ctypes).  The boundaries of its kernels (cross-chunk carries, unit and group
+boundaries, insert edges) are driven by designed tables in test_gpu_ordered_paths.py / ordered_cases.py / test_ordered_cases_cpu.py."""
 import numpy as np
 import pytest
 
